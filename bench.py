@@ -7,11 +7,13 @@ over the whole image: primal tracing kernel -> box film -> loss gradient
 (consumes the stored primal radiance as state_in) [-> one all-reduce of the
 gradient grids when N > 1].  One *sample* = one camera ray (pixel x spp).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (see the keys below).  Inputs (the synthetic 256^3
-dust-devil grids) are resident in HBM before the timed region starts.
+Rank 0 prints ONE JSON line (see the keys below); `ms_per_step` is the wall time of
+one of the K timed steps.  Inputs (the synthetic 256^3 dust-devil grids, seeded) are
+resident in HBM before the timed region starts.  --dump-outputs DIR writes the last
+timed step's image and gradient grids as .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -563,6 +565,34 @@ def other_configs(torch, u, synthetic, dev, integ_name="volpathsimple-drt", only
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000      # --dump-outputs writes at most this much in all: under 64 MB, cheap to keep and compare
+
+
+def dump_outputs(out_dir, img, grads):
+    """--dump-outputs: what the last timed step hands its caller - the developed image and the gradient grids - as
+    DIR/<name>.npy, so that two builds run with the same arguments can be compared output for output.  The budget is
+    split evenly over the arrays; an array within its share is written whole (float32 as computed), a larger one as a
+    fixed sample: the entries of its flattened array at sorted indices drawn without replacement by
+    numpy.random.default_rng(0), written as <name>_sample.npy (the same indices for the same shape in every run)."""
+    import numpy as np
+    import torch
+    arrays = {"image": img}
+    for k, g in grads.items():
+        if k != "_flat":
+            arrays["grad_" + k.removeprefix("medium1.").removesuffix(".data")] = g
+    os.makedirs(out_dir, exist_ok=True)
+    max_elems = DUMP_BUDGET_BYTES // 8 // len(arrays)          # (8 bytes: room for float64)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        if t.numel() > max_elems:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=max_elems, replace=False, shuffle=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -582,7 +612,11 @@ def main():
                     help="run ONE entry of other_configs and print it (counter passes of a single configuration under rocprofv3)")
     ap.add_argument("--cpu-spp", type=int, default=0, help="spp of the bounded CPU sample (0 = auto)")
     ap.add_argument("--debug-flags", type=int, default=0, help="profiling ablations (drt_set_debug_flags); invalidates the result")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (image, gradient grids) to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -669,10 +703,13 @@ def main():
     h.enable_timing(True)       # HIP event pairs around every tracing launch, on the launch stream
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        img_last = step(args.warmup + i)
     sync()
     elapsed = time.perf_counter() - t0
     u.verify_pending()                               # (the deferred check of the last step's gradient all-reduce)
+    if args.dump_outputs and rank == 0:              # before the counter step below overwrites the gradient grids
+        dump_outputs(args.dump_outputs, img_last, grads)
+    img_last = None
     t_primal = h.read_timings(0)
     t_adjoint = h.read_timings(1)
     t_untile = h.read_timings(2)
