@@ -217,6 +217,49 @@ int drt_film_develop(drt_handle h, const float *L, uint64_t n_pixels, uint32_t s
 int drt_film_backward(drt_handle h, const float *grad_image, uint64_t n_pixels, uint32_t spp,
                       float *dL);
 
+/* Loss-fused film (opt-in; the calls above are unchanged).  The pixel-separable image losses of the reference
+ * (python/losses.py: average, l1, l2, huber, mean_relative_absolute_error, mean_relative_squared_error), each
+ * normalised by the number of image entries n_pixels * 3, computed on the device beside the film.
+ * Reference values: `dense` [n_pixels][3], or the batched gather (optimize.py:90-107) of `images`
+ * (n_sensors, height, width, channels = 3 | 4) at sensor_idx[p], (x, y) = pixel_idx[2p], pixel_idx[2p + 1];
+ * neither for DRT_LOSS_AVERAGE.  An index outside the images is not read: it makes the loss NaN (the indices
+ * are device data; refusing them would need a host wait). */
+typedef enum drt_loss_kind {
+    DRT_LOSS_AVERAGE = 0,
+    DRT_LOSS_L1 = 1,
+    DRT_LOSS_L2 = 2,
+    DRT_LOSS_HUBER = 3,   /* loss_param = delta (the signed test residual < delta, losses.py:26-30) */
+    DRT_LOSS_MRAE = 4,    /* loss_param = epsilon */
+    DRT_LOSS_MRSE = 5     /* loss_param = epsilon */
+} drt_loss_kind;
+
+typedef struct drt_loss_ref {
+    const float *dense;
+    const float *images;
+    int32_t n_sensors, height, width, channels;
+    const int32_t *sensor_idx;
+    const int32_t *pixel_idx;
+} drt_loss_ref;
+
+/* image[p] = drt_film_develop's image, bit for bit; loss_out[0] = the loss (deterministic: per-workgroup partial
+ * sums, then one fixed-order sum; no float atomics).  L: [n_pixels*spp][3]. */
+int drt_film_loss_forward(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, const drt_loss_ref *ref,
+                          int32_t loss_kind, float loss_param, float *image_out, float *loss_out);
+/* grad_image = upstream[0] * d loss / d image at `image` (the forward's image), in torch autograd's operation order
+ * for losses.py.  `upstream`: DEVICE pointer to the scalar gradient of the loss (never read on the host). */
+int drt_film_loss_grad(drt_handle h, const float *image, uint64_t n_pixels, const drt_loss_ref *ref, int32_t loss_kind,
+                       float loss_param, const float *upstream, float *grad_image_out);
+/* drt_render_backward / drt_nerf_render_backward with the image gradient grad_image [n_pixels][3] in place of the
+ * per-ray dL: ray i of the job belongs to pixel i / spp, n_rays must equal n_pixels * spp.  The gradients are those
+ * of the per-ray calls with dL = drt_film_backward(grad_image), bit for bit. */
+int drt_render_backward_px(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
+                           uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
+                           const float *L_in, float *grad_sigma_t, float *grad_albedo);
+int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                                const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
+                                float *grad_emission);
+
 /* Multi-GPU gradient exchange (no handle: works on any gradient buffer of the current device, on `hip_stream`).
  * mask[b] = 1 if block b (block_floats = 64 | 128 | 256 consecutive floats, buf 16-byte aligned) holds anything but
  * zeros (NaN / inf count), else 0.  The host side (distributed.py) all-reduces the masks (MAX) and then only the

@@ -78,6 +78,10 @@ struct drt_handle_s {
     hipEvent_t ev_split = nullptr, ev_hist = nullptr;
     hipStream_t nerf_stream = nullptr;  // the nerf half of the fused pass runs beside the volpathsimple half (drt_fused_render_*)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    double *d_loss_partials = nullptr;   // per-workgroup sums of drt_film_loss_forward
+    size_t loss_partials_bytes = 0;
+    float *d_dl_px = nullptr;            // per-ray dL for the queued tracer, expanded from Params::dL_pix (drt_render_backward_px)
+    size_t dl_px_bytes = 0;
     uint32_t *d_nerf_bounds = nullptr; // 32 bytes: max |dL|, |L_in|, |emission|, non-finite flag, largest negative density of a nerf tile adjoint launch (drt_nerf_tile.hip)
     // path cache (drt_coop.hip): written by the primal launch of an H1 step, read by the adjoint launch of the
     // same job if nothing happened to the handle in between
@@ -352,6 +356,19 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
     if (super) {
         drt::Params Q = P;
         Q.queues = h->d_queues;
+        if (adjoint && sq_ok && P.dL_pix) {
+            // the queued tracer reads δL per ray only: its adjoint instantiations sit at the register limit, and the per-pixel read
+            // (load_dL) measurably slowed the default path - expand the image gradient for it (film_backward_kernel: the same bits)
+            const uint64_t px = (P.n_rays + P.spp - 1) / P.spp;   // the pixels of rays [0, n_rays) (a sub-batch may end mid-pixel)
+            const size_t need = (size_t) px * P.spp * 3 * sizeof(float);
+            if (need > h->dl_px_bytes) {
+                if (h->d_dl_px) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_dl_px); h->d_dl_px = nullptr; h->dl_px_bytes = 0; }
+                DRT_HIP_CHECK(h, hipMalloc((void **) &h->d_dl_px, need));
+                h->dl_px_bytes = need;
+            }
+            DRT_HIP_CHECK(h, drt::launch_film_backward(P.dL_pix, px, P.spp, h->d_dl_px, h->stream));
+            Q.dL = h->d_dl_px; Q.dL_pix = nullptr;
+        }
         const uint64_t span = P.n_rays - P.ray_first;
         // round 4: the queued tracer (drt_sq.hip) where the ray records fit LDS next to the majorants; test hook 4096 keeps
         // the round-3 kernel (drt_super.hip), which also serves what the queued one does not take
@@ -876,6 +893,8 @@ int drt_destroy(drt_handle h)
     if (h->ev_fork) (void) hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void) hipEventDestroy(h->ev_join);
     if (h->d_nerf_bounds) (void) hipFree(h->d_nerf_bounds);
+    if (h->d_loss_partials) (void) hipFree(h->d_loss_partials);
+    if (h->d_dl_px) (void) hipFree(h->d_dl_px);
     if (h->ev_split) (void) hipEventDestroy(h->ev_split);
     if (h->ev_hist) (void) hipEventDestroy(h->ev_hist);
     if (h->d_pcache) (void) hipFree(h->d_pcache);
@@ -898,6 +917,8 @@ int drt_release_scratch(drt_handle h)
     h->d_pcache = nullptr; h->pcache_bytes = 0; h->pcache_sig.valid = false; h->order_valid = false; h->order_rays = 0;
     if (h->d_tail) (void) hipFree(h->d_tail);
     h->d_tail = nullptr; h->tail_entries = 0;
+    if (h->d_dl_px) (void) hipFree(h->d_dl_px);
+    h->d_dl_px = nullptr; h->dl_px_bytes = 0;
     return DRT_OK;
 }
 
@@ -1251,19 +1272,15 @@ int drt_render_primal(drt_handle h, const float *rays_o, const float *rays_d, ui
     return rc;
 }
 
-int drt_render_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
-                        uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL,
-                        const float *L_in, float *grad_sigma_t, float *grad_albedo)
+// the adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel, drt_render_backward_px) is given
+static int render_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                           uint32_t seed, const float *dL, const float *dL_pix, const float *L_in, float *grad_sigma_t, float *grad_albedo)
 {
-    if (h && n_rays == 0) return DRT_OK;
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
-    if (n_rays && (!dL || !L_in || !grad_sigma_t || !grad_albedo))
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward: null dL / L_in / gradient buffer");
+    int rc;
     DeviceGuard g(h->device);
     drt::Params P;
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    P.dL = dL; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_albedo;
+    P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_albedo;
     // capacity: 48 sigma_t and 6 colour records per ray (headline workload: 12.3 and 1.4); beyond it the
     // tracer falls back to direct atomics (emit_record), so this is a performance choice only
     const uint64_t job_rays = n_rays;
@@ -1273,6 +1290,18 @@ int drt_render_backward(drt_handle h, const float *rays_o, const float *rays_d, 
     });
     h->pcache_sig.valid = false;
     return rc;
+}
+
+int drt_render_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
+                        uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL,
+                        const float *L_in, float *grad_sigma_t, float *grad_albedo)
+{
+    if (h && n_rays == 0) return DRT_OK;
+    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
+    if (rc) return rc;
+    if (n_rays && (!dL || !L_in || !grad_sigma_t || !grad_albedo))
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward: null dL / L_in / gradient buffer");
+    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo);
 }
 
 static int nerf_fill(drt_handle h, drt::Params &P, const drt_nerf_config *cfg, const float *emission, bool fused_half = false)
@@ -1339,6 +1368,10 @@ int drt_nerf_render_primal(drt_handle h, const drt_nerf_config *cfg, const float
     return nerf_primal(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_out, false);
 }
 
+static int nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *dL_pix,
+                                const float *L_in, float *grad_sigma_t, float *grad_emission);
+
 int drt_nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
                              const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
                              const float *dL, const float *L_in, float *grad_sigma_t, float *grad_emission)
@@ -1348,12 +1381,20 @@ int drt_nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const flo
     if (rc) return rc;
     if (!dL || !L_in || !grad_sigma_t || !grad_emission)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward: null dL / L_in / gradient buffer");
+    return nerf_render_backward(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_emission);
+}
+
+// the nerf adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given
+static int nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *dL_pix,
+                                const float *L_in, float *grad_sigma_t, float *grad_emission)
+{
     DeviceGuard g(h->device);
     drt::Params P;
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    rc = nerf_fill(h, P, cfg, emission);
+    int rc = nerf_fill(h, P, cfg, emission);
     if (rc) return rc;
-    P.dL = dL; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_emission;
+    P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_emission;
     // (sensor rays: sigma_t and the emission of a query from ONE 256-byte block of a four-channel copy made for this call)
     const bool tile = drt::nerf_tile_supported(P) && !dbg(h->debug_flags, 512u);
     const bool g4 = tile && ensure_grid4(h, P, emission) == DRT_OK;   // (no memory / a grid beyond the copy's index range: the separate lookups)
@@ -1682,3 +1723,117 @@ int drt_read_timings(drt_handle h, int backward, float *out_ms, int capacity)
 }
 
 }  // extern "C"
+
+// ---- loss-fused film (drt_loss.hip) and the pixel-gradient backward calls ---------------------------------------------------------------------
+namespace {
+
+// a grow-only device buffer of the handle: (re)allocated behind the handle's stream when too small
+int grow_scratch(drt_handle h, void **buf, size_t *have, size_t need)
+{
+    if (need <= *have) return DRT_OK;
+    if (*buf) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(*buf); *buf = nullptr; *have = 0; }
+    DRT_HIP_CHECK(h, hipMalloc(buf, need));
+    *have = need;
+    return DRT_OK;
+}
+
+int loss_args(drt_handle h, const char *what, uint64_t n_pixels, const drt_loss_ref *ref, int32_t kind, float param, drt::LossRef &R)
+{
+    if (n_pixels == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: n_pixels must be > 0", what);
+    if (n_pixels > (0xffffffffull / 3) * 256) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: too many pixels for one launch", what);
+    if (kind < DRT_LOSS_AVERAGE || kind > DRT_LOSS_MRSE)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: unknown loss_kind %d (0 average, 1 l1, 2 l2, 3 huber, 4 mrae, 5 mrse)", what, (int) kind);
+    if (kind >= DRT_LOSS_HUBER && !(std::isfinite(param) && param >= 0.0f))
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: %s must be finite and >= 0, got %g", what, kind == DRT_LOSS_HUBER ? "delta" : "epsilon",
+                    (double) param);
+    R = drt::LossRef{};
+    if (!ref || (!ref->dense && !ref->images)) {
+        if (kind != DRT_LOSS_AVERAGE) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: this loss needs reference values", what);
+        return DRT_OK;
+    }
+    if (ref->dense && ref->images) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: give dense reference values or reference images, not both", what);
+    if (ref->dense) { R.dense = ref->dense; return DRT_OK; }
+    if (!ref->sensor_idx || !ref->pixel_idx) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: reference images need sensor_idx and pixel_idx", what);
+    if (ref->n_sensors <= 0 || ref->height <= 0 || ref->width <= 0)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: reference images of shape (%d, %d, %d, %d)", what, (int) ref->n_sensors, (int) ref->height,
+                    (int) ref->width, (int) ref->channels);
+    if (ref->channels != 3 && ref->channels != 4)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: reference images must have 3 or 4 channels, got %d", what, (int) ref->channels);
+    R.images = ref->images; R.sensor_idx = ref->sensor_idx; R.pixel_idx = ref->pixel_idx;
+    R.n_sensors = ref->n_sensors; R.height = ref->height; R.width = ref->width; R.channels = ref->channels;
+    return DRT_OK;
+}
+
+// the pixel-gradient arguments of drt_*render_backward_px
+int check_px(drt_handle h, const char *what, uint64_t n_rays, uint32_t spp, const float *grad_image, uint64_t n_pixels)
+{
+    if (n_pixels == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: n_pixels must be > 0", what);
+    if (!grad_image) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null grad_image", what);
+    if (n_rays != n_pixels * spp)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: n_rays (%llu) must equal n_pixels * spp (%llu * %u)", what, (unsigned long long) n_rays,
+                    (unsigned long long) n_pixels, (unsigned) spp);
+    return DRT_OK;
+}
+
+}  // namespace
+
+int drt_film_loss_forward(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, const drt_loss_ref *ref,
+                          int32_t loss_kind, float loss_param, float *image_out, float *loss_out)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (spp == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_loss_forward: spp must be > 0");
+    if (!L || !image_out || !loss_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_loss_forward: null L / image_out / loss_out");
+    drt::LossRef R;
+    int rc = loss_args(h, "drt_film_loss_forward", n_pixels, ref, loss_kind, loss_param, R);
+    if (rc) return rc;
+    DeviceGuard g(h->device);
+    rc = grow_scratch(h, (void **) &h->d_loss_partials, &h->loss_partials_bytes, drt::film_loss_partials(n_pixels, spp) * sizeof(double));
+    if (rc) return rc;
+    DRT_HIP_CHECK(h, drt::launch_film_loss_forward(L, n_pixels, spp, R, loss_kind, loss_param, image_out, loss_out, h->d_loss_partials,
+                                                   h->stream));
+    return DRT_OK;
+}
+
+int drt_film_loss_grad(drt_handle h, const float *image, uint64_t n_pixels, const drt_loss_ref *ref, int32_t loss_kind,
+                       float loss_param, const float *upstream, float *grad_image_out)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (!image || !upstream || !grad_image_out)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_loss_grad: null image / upstream / grad_image_out");
+    drt::LossRef R;
+    int rc = loss_args(h, "drt_film_loss_grad", n_pixels, ref, loss_kind, loss_param, R);
+    if (rc) return rc;
+    DeviceGuard g(h->device);
+    DRT_HIP_CHECK(h, drt::launch_film_loss_grad(image, n_pixels, R, loss_kind, loss_param, upstream, grad_image_out, h->stream));
+    return DRT_OK;
+}
+
+int drt_render_backward_px(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
+                           uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
+                           const float *L_in, float *grad_sigma_t, float *grad_albedo)
+{
+    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
+    if (rc) return rc;
+    if (!L_in || !grad_sigma_t || !grad_albedo)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_px: null L_in / gradient buffer");
+    rc = check_px(h, "drt_render_backward_px", n_rays, spp, grad_image, n_pixels);
+    if (rc) return rc;
+    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo);
+}
+
+int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                                const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
+                                float *grad_emission)
+{
+    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false);
+    if (rc) return rc;
+    if (!cfg || !emission) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px: null config / emission grid");
+    if (cfg->queries_per_ray < 2) return fail(h, DRT_ERR_INVALID_ARGUMENT, "queries_per_ray must be >= 2");
+    if (!L_in || !grad_sigma_t || !grad_emission)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px: null L_in / gradient buffer");
+    rc = check_px(h, "drt_nerf_render_backward_px", n_rays, spp, grad_image, n_pixels);
+    if (rc) return rc;
+    return nerf_render_backward(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t,
+                                grad_emission);
+}

@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
             else if (P.ray_hash[i] == hsh) tr.pc = P.path_cache + (size_t) i * P.path_cache_cap * 2;
         }
         if (ADJ) {
-            dL[0] = P.dL[3 * i]; dL[1] = P.dL[3 * i + 1]; dL[2] = P.dL[3 * i + 2];
+            load_dL(P, i, dL);
             Lin[0] = P.L_in[3 * i]; Lin[1] = P.L_in[3 * i + 1]; Lin[2] = P.L_in[3 * i + 2];
         }
     }

@@ -332,6 +332,9 @@ struct Params {
     // crx / cry / crz; in every other unit these fields are never read.  (At the end of the block: no other field moves.)
     int crx, cry, crz, colour_own;
     uint32_t sq_rounds;             // queued tracer, primal launches in index order: the medium is thin as far as the host knows (drt_capi.cpp: majorant read-back) - the ROUNDS kernels
+    // loss-fused backward (drt_*render_backward_px): set instead of dL - the image gradient [pixels][3]; local ray i reads pixel i / spp (load_dL).
+    // (At the end of the block, as the colour fields: moving the fields before it changed the queued tracer's code and broke its tail launch.)
+    const float *dL_pix;
 };
 
 // ---------------------------------------------------------------------------
@@ -1184,6 +1187,20 @@ __device__ __forceinline__ void sensor_ray(const Params &P, uint32_t pixel, floa
     d = v3(fmaf(P.cam_left[0], cx, fmaf(P.cam_up[0], cy, P.cam_dir[0] * cz)),
            fmaf(P.cam_left[1], cx, fmaf(P.cam_up[1], cy, P.cam_dir[1] * cz)),
            fmaf(P.cam_left[2], cx, fmaf(P.cam_up[2], cy, P.cam_dir[2] * cz)));
+}
+
+// δL of local ray i where its path starts: the per-ray buffer, or - loss-fused backward (drt_*render_backward_px) - the image gradient of its
+// pixel i / spp times 1/spp, the product film_backward_kernel forms: the same bits without the [rays][3] buffer
+template <typename I>
+__device__ __forceinline__ void load_dL(const Params &P, I i, float dL[3])
+{
+    if (P.dL_pix) {
+        const uint64_t p = (uint32_t) i / P.spp;          // (32-bit: local ray indices are < 2^32, check_job)
+        const float inv = 1.0f / (float) P.spp;
+        dL[0] = P.dL_pix[3 * p] * inv; dL[1] = P.dL_pix[3 * p + 1] * inv; dL[2] = P.dL_pix[3 * p + 2] * inv;
+    } else {
+        dL[0] = P.dL[3 * i]; dL[1] = P.dL[3 * i + 1]; dL[2] = P.dL[3 * i + 2];
+    }
 }
 
 }  // namespace drt

@@ -7,6 +7,7 @@
 #include "drt_launch.h"
 #include "drt_coop_tracer.h"
 #include "drt_nerf_kernel.h"
+#include "drt_film.h"
 
 #ifndef DRT_TRACE_WAVES
 #define DRT_TRACE_WAVES 4      // waves per SIMD the tracing kernels are compiled for (VGPR <= 128)
@@ -472,7 +473,8 @@ __global__ void __launch_bounds__(256, DRT_TRACE_WAVES) trace_kernel(const Param
         }
         float L[3];
         if (ADJ) {
-            float dL[3] = { P.dL[3 * i], P.dL[3 * i + 1], P.dL[3 * i + 2] };
+            float dL[3];
+            load_dL(P, i, dL);
             float Lin[3] = { P.L_in[3 * i], P.L_in[3 * i + 1], P.L_in[3 * i + 2] };
             tr.template sample<true, false>(S, ray, dL, Lin, nullptr, L);
         } else {
@@ -747,16 +749,13 @@ __global__ void __launch_bounds__(256) batch_raygen_kernel(const float *sensors,
     rays_d[3 * (size_t) rl] = d.x; rays_d[3 * (size_t) rl + 1] = d.y; rays_d[3 * (size_t) rl + 2] = d.z;
 }
 
-// box film: image[p] = mean_spp L (batched.py:176-197)
+// box film: image[p] = mean_spp L (batched.py:176-197); the summation orders live in drt_film.h (the loss-fused film shares them)
 __global__ void __launch_bounds__(256) film_develop_kernel(const float *L, uint64_t n_pixels, uint32_t spp, float *image)
 {
     uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;   // one thread per (pixel, channel)
     if (t >= n_pixels * 3) return;
     uint64_t p = t / 3; uint32_t c = (uint32_t)(t - p * 3);
-    const float *src = L + 3 * p * spp + c;
-    float s = 0.0f;
-    for (uint32_t j = 0; j < spp; ++j) s += src[3 * (uint64_t) j];
-    image[t] = s * (1.0f / (float) spp);
+    image[t] = film_channel_sum(L, p, c, spp) * (1.0f / (float) spp);
 }
 
 // the same for many samples per pixel (the optimisation loop develops 1024 spp): one wave per pixel - lane l sums the
@@ -766,11 +765,8 @@ __global__ void __launch_bounds__(256) film_develop_wave_kernel(const float *L, 
     const uint64_t p = (uint64_t) blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p >= n_pixels) return;
     const uint32_t lane = threadIdx.x & 63u;
-    const float *src = L + 3 * p * spp;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
-    for (uint32_t j = lane; j < spp; j += 64u) { s0 += src[3 * (uint64_t) j]; s1 += src[3 * (uint64_t) j + 1]; s2 += src[3 * (uint64_t) j + 2]; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off, 64); s1 += __shfl_down(s1, off, 64); s2 += __shfl_down(s2, off, 64); }
+    float s0, s1, s2;
+    film_wave_sums(L, p, spp, lane, s0, s1, s2);
     if (lane == 0) {
         const float inv = 1.0f / (float) spp;
         image[3 * p] = s0 * inv; image[3 * p + 1] = s1 * inv; image[3 * p + 2] = s2 * inv;
@@ -979,7 +975,7 @@ hipError_t launch_film_develop(const float *L, uint64_t n_pixels, uint32_t spp, 
 {
     uint64_t n = n_pixels * 3;
     if (n == 0) return hipSuccess;
-    if (spp >= 128) hipLaunchKernelGGL(film_develop_wave_kernel, dim3((unsigned)((n_pixels + 3) / 4)), dim3(256), 0, stream, L, n_pixels, spp, image);
+    if (spp >= kFilmWaveSpp) hipLaunchKernelGGL(film_develop_wave_kernel, dim3((unsigned)((n_pixels + 3) / 4)), dim3(256), 0, stream, L, n_pixels, spp, image);
     else hipLaunchKernelGGL(film_develop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, L, n_pixels, spp, image);
     return hipGetLastError();
 }

@@ -115,6 +115,21 @@ hipError_t launch_film_develop(const float *L, uint64_t n_pixels, uint32_t spp, 
                                hipStream_t stream);
 hipError_t launch_film_backward(const float *grad_image, uint64_t n_pixels, uint32_t spp, float *dL,
                                 hipStream_t stream);
+// loss-fused film (drt_loss.hip): the reference values of a film_loss_* launch - a dense [n_pixels, 3] array, or the batched gather
+// images[(sensor_idx[p] * H + y) * W + x][c] with (x, y) = pixel_idx[2p], pixel_idx[2p + 1]; neither: no reference (the `average` loss)
+struct LossRef {
+    const float *dense;
+    const float *images;
+    const int32_t *sensor_idx, *pixel_idx;
+    int32_t n_sensors, height, width, channels;
+};
+enum LossKind : int { kLossAverage = 0, kLossL1 = 1, kLossL2 = 2, kLossHuber = 3, kLossMRAE = 4, kLossMRSE = 5 };
+// partial sums (doubles) the forward launch needs: one per workgroup
+uint64_t film_loss_partials(uint64_t n_pixels, uint32_t spp);
+hipError_t launch_film_loss_forward(const float *L, uint64_t n_pixels, uint32_t spp, const LossRef &R, int kind, float param,
+                                    float *image, float *loss, double *partials, hipStream_t stream);
+hipError_t launch_film_loss_grad(const float *image, uint64_t n_pixels, const LossRef &R, int kind, float param, const float *upstream,
+                                 float *grad_image, hipStream_t stream);
 uint32_t host_alt_seed(uint32_t seed, bool sensor_flow);
 hipError_t launch_debug_eval(const Params &P, int op, const float *in, uint64_t n, float *out, hipStream_t stream);
 

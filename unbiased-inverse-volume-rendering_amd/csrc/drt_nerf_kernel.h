@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
         float result[3] = { 0.0f, 0.0f, 0.0f }, dL[3] = { 0.0f, 0.0f, 0.0f };
         if constexpr (ADJ) {
             result[0] = P.L_in[3 * i]; result[1] = P.L_in[3 * i + 1]; result[2] = P.L_in[3 * i + 2];
-            dL[0] = P.dL[3 * i]; dL[1] = P.dL[3 * i + 1]; dL[2] = P.dL[3 * i + 2];
+            load_dL(P, i, dL);
         }
         float throughput = 1.0f, weights_sum = 0.0f;
         Hit si = box_hit(P, o, d);                                           // nerf.py:67-79

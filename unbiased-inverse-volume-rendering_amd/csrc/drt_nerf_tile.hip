@@ -117,16 +117,24 @@ __device__ __forceinline__ void eval4_at(const Params &P, const Stencil &s, floa
 // max |dL|, max |L_in| over the rays of the launch and max |emission| over the grid -> out[0..2] (float bits; zeroed by the caller):
 // what the fixed-point units of the window follow from
 // out[4]: the largest NEGATIVE density of the grid, as a magnitude (identity activation: a = exp(-sigma dt) > 1 there, throughput and weights can grow)
-__global__ void __launch_bounds__(256) nerf_tile_bounds_kernel(const float *dL, const float *L_in, size_t n_ray_floats, const float *em, size_t n_em,
+// dL_pix (loss-fused backward; dL is then unused): the image gradient of exactly the pixels the launch's rays cover, n_px_floats floats, each
+// times inv_spp as the rays read it (load_dL) - the same maximum as over the per-ray buffer, bit for bit (x -> x * inv_spp is monotonic)
+__global__ void __launch_bounds__(256) nerf_tile_bounds_kernel(const float *dL, const float *L_in, size_t n_ray_floats, const float *dL_pix,
+                                                               size_t n_px_floats, float inv_spp, const float *em, size_t n_em,
                                                                const float *sig, size_t n_sig, uint32_t *out)
 {
     float m[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
     const size_t stride = (size_t) gridDim.x * blockDim.x, i0 = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     bool bad = false;                                                   // a non-finite input: fixed point cannot carry it - out[3] makes the pass say so
-    for (size_t i = i0; i < n_ray_floats; i += stride) {
-        const float a = fabsf(dL[i]), b = fabsf(L_in[i]);
-        bad = bad || !(a < kInf) || !(b < kInf);
-        m[0] = fmaxf(m[0], a); m[1] = fmaxf(m[1], b);
+    if (dL_pix) {
+        for (size_t i = i0; i < n_ray_floats; i += stride) { const float b = fabsf(L_in[i]); bad = bad || !(b < kInf); m[1] = fmaxf(m[1], b); }
+        for (size_t i = i0; i < n_px_floats; i += stride) { const float a = fabsf(dL_pix[i] * inv_spp); bad = bad || !(a < kInf); m[0] = fmaxf(m[0], a); }
+    } else {
+        for (size_t i = i0; i < n_ray_floats; i += stride) {
+            const float a = fabsf(dL[i]), b = fabsf(L_in[i]);
+            bad = bad || !(a < kInf) || !(b < kInf);
+            m[0] = fmaxf(m[0], a); m[1] = fmaxf(m[1], b);
+        }
     }
     for (size_t i = i0; i < n_em; i += stride) { const float a = fabsf(em[i]); bad = bad || !(a < kInf); m[2] = fmaxf(m[2], a); }
     for (size_t i = i0; i < n_sig; i += stride) { const float a = sig[i]; bad = bad || !(fabsf(a) < kInf); m[3] = fmaxf(m[3], -a); }
@@ -223,7 +231,7 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
         const float ux = S.next_1d(), uy = S.next_1d();
         sensor_ray(P, gi / P.spp, ux, uy, o, d);
         result[0] = P.L_in[3 * i]; result[1] = P.L_in[3 * i + 1]; result[2] = P.L_in[3 * i + 2];
-        dL[0] = P.dL[3 * i]; dL[1] = P.dL[3 * i + 1]; dL[2] = P.dL[3 * i + 2];
+        load_dL(P, i, dL);
         Hit si = box_hit(P, o, d);
         active = si.valid;
         if (active) {
@@ -467,8 +475,12 @@ hipError_t launch_nerf_tile_adjoint(const Params &P, bool g4, bool count, uint32
         hipError_t e = hipMemsetAsync(bounds, 0, 8 * sizeof(uint32_t), stream);
         if (e != hipSuccess) return e;
         const size_t n_em = (size_t) P.rx * P.ry * P.rz * 3;
-        hipLaunchKernelGGL(nerf_tile_bounds_kernel, dim3(2048), dim3(256), 0, stream, P.dL + 3 * P.ray_first, P.L_in + 3 * P.ray_first,
-                           (size_t) (P.n_rays - P.ray_first) * 3, P.emission, n_em, P.sigma_t, n_em / 3, bounds);
+        // (pixel layout: the pixels of rays ray_first .. n_rays - 1, both ends included)
+        const uint64_t px_first = P.ray_first / P.spp, px_last = (P.n_rays - 1) / P.spp;
+        hipLaunchKernelGGL(nerf_tile_bounds_kernel, dim3(2048), dim3(256), 0, stream, P.dL_pix ? nullptr : P.dL + 3 * P.ray_first,
+                           P.L_in + 3 * P.ray_first, (size_t) (P.n_rays - P.ray_first) * 3,
+                           P.dL_pix ? P.dL_pix + 3 * px_first : nullptr, (size_t) (px_last - px_first + 1) * 3, 1.0f / (float) P.spp,
+                           P.emission, n_em, P.sigma_t, n_em / 3, bounds);
         T.bounds = bounds;
     }
     T.tiles_x = ((uint32_t) P.width + 7u) / 8u;

@@ -215,6 +215,58 @@ public:
         { py::gil_scoped_release nogil; rc = drt_film_backward(h_, ptr<const float>(grad_image), n_pixels, spp, ptr<float>(dL)); }
         check(rc, "drt_film_backward");
     }
+    static drt_loss_ref loss_ref(uintptr_t dense, uintptr_t images, std::array<int32_t, 4> shape, uintptr_t sensor_idx, uintptr_t pixel_idx)
+    {
+        drt_loss_ref r{};
+        r.dense = ptr<const float>(dense); r.images = ptr<const float>(images);
+        r.n_sensors = shape[0]; r.height = shape[1]; r.width = shape[2]; r.channels = shape[3];
+        r.sensor_idx = ptr<const int32_t>(sensor_idx); r.pixel_idx = ptr<const int32_t>(pixel_idx);
+        return r;
+    }
+    void film_loss_forward(uintptr_t L, uint64_t n_pixels, uint32_t spp, uintptr_t dense, uintptr_t images, std::array<int32_t, 4> shape,
+                           uintptr_t sensor_idx, uintptr_t pixel_idx, int kind, float param, uintptr_t image, uintptr_t loss)
+    {
+        const drt_loss_ref r = loss_ref(dense, images, shape, sensor_idx, pixel_idx);
+        int rc;
+        { py::gil_scoped_release nogil; rc = drt_film_loss_forward(h_, ptr<const float>(L), n_pixels, spp, &r, kind, param, ptr<float>(image), ptr<float>(loss)); }
+        check(rc, "drt_film_loss_forward");
+    }
+    void film_loss_grad(uintptr_t image, uint64_t n_pixels, uintptr_t dense, uintptr_t images, std::array<int32_t, 4> shape,
+                        uintptr_t sensor_idx, uintptr_t pixel_idx, int kind, float param, uintptr_t upstream, uintptr_t grad_image)
+    {
+        const drt_loss_ref r = loss_ref(dense, images, shape, sensor_idx, pixel_idx);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_film_loss_grad(h_, ptr<const float>(image), n_pixels, &r, kind, param, ptr<const float>(upstream), ptr<float>(grad_image));
+        }
+        check(rc, "drt_film_loss_grad");
+    }
+    void render_backward_px(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed,
+                            uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_render_backward_px(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(grad_image),
+                                        n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo));
+        }
+        check(rc, "drt_render_backward_px");
+    }
+    void nerf_render_backward_px(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                 uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
+                                 uintptr_t g_emission)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_backward_px(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
+                                             seed, ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
+                                             ptr<float>(g_emission));
+        }
+        check(rc, "drt_nerf_render_backward_px");
+    }
     void debug_eval(int op, uintptr_t in, uint64_t n, uintptr_t out)
     {
         int rc;
@@ -323,6 +375,10 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
              py::arg("pix"), py::arg("batch_first") = 0)
         .def("film_develop", &Integrator::film_develop)
         .def("film_backward", &Integrator::film_backward)
+        .def("film_loss_forward", &Integrator::film_loss_forward)
+        .def("film_loss_grad", &Integrator::film_loss_grad)
+        .def("render_backward_px", &Integrator::render_backward_px)
+        .def("nerf_render_backward_px", &Integrator::nerf_render_backward_px)
         .def("debug_eval", &Integrator::debug_eval)
         .def("set_debug_flags", &Integrator::set_debug_flags)
         .def("enable_counters", &Integrator::enable_counters)

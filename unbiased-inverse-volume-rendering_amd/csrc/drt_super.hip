@@ -531,7 +531,7 @@ __global__ void __launch_bounds__(ADJ ? DRT_SUPER_THREADS_ADJ : DRT_SUPER_THREAD
                         beta[0] = beta[1] = beta[2] = 1.0f;
                         result[0] = result[1] = result[2] = 0.0f;
                         if constexpr (ADJ) {
-                            dL[0] = P.dL[3 * i]; dL[1] = P.dL[3 * i + 1]; dL[2] = P.dL[3 * i + 2];
+                            load_dL(P, i, dL);
                             result[0] = P.L_in[3 * i]; result[1] = P.L_in[3 * i + 1]; result[2] = P.L_in[3 * i + 2];
                         }
                         depth = 0; escaped = false; has_scattered = false; scat_once = false;

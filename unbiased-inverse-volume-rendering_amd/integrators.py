@@ -135,6 +135,27 @@ class _DeviceIntegrator:
         h.film_backward(grad_image.data_ptr(), n_pix, int(spp), dL.data_ptr())
         return dL
 
+    # -- loss-fused film (drt_film_loss_*, csrc/drt_loss.hip): `ref` = loss_fused.LossRef ----------------------
+    def develop_loss(self, scene: Scene, L: torch.Tensor, spp: int, ref, kind: int, param: float):
+        """-> (image [n_pix, 3], loss 0-d): the image of `develop`, bit for bit, and the loss against `ref`."""
+        h, dev = self._bind(scene)
+        _check(L, None, dev, "L")
+        n_pix = L.shape[0] // spp
+        img = torch.empty((n_pix, 3), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        h.film_loss_forward(L.data_ptr(), n_pix, int(spp), *ref.native_args(), int(kind), float(param), img.data_ptr(), loss.data_ptr())
+        return img, loss
+
+    def loss_grad(self, scene: Scene, image: torch.Tensor, ref, kind: int, param: float, upstream: torch.Tensor) -> torch.Tensor:
+        """d loss / d image times the 0-d device tensor `upstream` (read by the kernel, never on the host)."""
+        h, dev = self._bind(scene)
+        _check(image, None, dev, "image")
+        _check(upstream, (), dev, "upstream")
+        grad = torch.empty_like(image)
+        h.film_loss_grad(image.data_ptr(), image.shape[0], *ref.native_args(), int(kind), float(param), upstream.data_ptr(),
+                         grad.data_ptr())
+        return grad
+
     def native_handle(self, scene: Scene):
         return self._bind(scene)[0]
 
@@ -302,6 +323,21 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         raise NotImplementedError("forward-mode differentiation is not supported "
                                   "(render_batch_forward raises in the reference too, batched.py:200-209)")
 
+    def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
+                           state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
+        """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] in place of the per-ray δL
+        (drt_render_backward_px): the same gradients as with δL = film_backward(grad_image)."""
+        h, dev = self._bind(scene)
+        self._set_rays(h, ray)
+        n, ro, rd = self._ray_ptrs(ray, dev)
+        _check(grad_image, (n // int(ray.spp), 3), dev, "grad_image")
+        _check(state_in, (n, 3), dev, "state_in")
+        gs, ga = grads[SIGMA_T_KEY], grads[ALBEDO_KEY]
+        _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
+        _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
+        h.render_backward_px(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
+                             grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
+
     def _native_props(self) -> dict:
         return self.props()
 
@@ -398,6 +434,23 @@ class NeRFIntegrator(_DeviceIntegrator):
             return None, True, None
         raise NotImplementedError("forward-mode differentiation is not supported")
 
+    def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
+                           state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
+        """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] in place of the per-ray δL
+        (drt_nerf_render_backward_px)."""
+        h, dev = self._bind(scene)
+        em = scene.medium.emission
+        _check(em, None, dev, "emission")
+        self._set_rays(h, ray)
+        n, ro, rd = self._ray_ptrs(ray, dev)
+        _check(grad_image, (n // int(ray.spp), 3), dev, "grad_image")
+        _check(state_in, (n, 3), dev, "state_in")
+        gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
+        _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
+        _check(ge, tuple(em.shape), dev, "grads[emission]")
+        h.nerf_render_backward_px(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
+                                  grad_image.data_ptr(), grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
+
 
 class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
     """BASELINE config 5: the `nerf` march (python/integrators/nerf.py) and `volpathsimple` scattering
@@ -440,6 +493,9 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
             return super().film_backward(scene, grad_image, spp)
         return torch.cat([super().film_backward(scene, grad_image[:, :3].contiguous(), spp),
                           super().film_backward(scene, grad_image[:, 3:].contiguous(), spp)], dim=1)
+
+    def sample_backward_px(self, *args, **kwargs):
+        raise ValueError("nerf+volpathsimple renders a 6-channel image: the loss-fused backward pass has no 3-channel reference for it")
 
     def sample(self, mode, scene: Scene, sampler: IndependentSampler, ray: RayBatch,
                δL: Optional[torch.Tensor] = None, state_in: Optional[torch.Tensor] = None,

@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from . import losses
 from .batched import gather_ref_values, render_batch, sensors_to_device
 from .integrators import sample_tea_32
+from .loss_fused import render_batch_loss, render_loss, resolve_loss
 from .opt_config import get_int_config
 from .render import render, render_primal
 from .scene import ALBEDO_KEY, EMISSION_KEY, SIGMA_T_KEY, GridMedium, Scene
@@ -52,6 +53,9 @@ class OptimizationConfig:
     opt_type: str = 'adam'
     opt_args: Optional[Dict] = None
     loss: Callable = losses.l1
+    # opt-in: film, loss and its gradient fused on the device (loss_fused.render_loss / render_batch_loss); a loss or a run it
+    # does not support raises at start-up
+    fused_loss: bool = False
 
     def __post_init__(self):
         self.upsample_at = set()
@@ -372,6 +376,10 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     from .distributed import ShardSpec, allreduce_scalar, local_loss_scale, verify_pending
     from . import losses as _losses
     shard = shard or ShardSpec()
+    if opt_config.fused_loss:
+        resolve_loss(opt_config.loss)                                  # (raises for a loss the fused kernels do not have)
+        if shard.world > 1:
+            raise ValueError("fused_loss=True: sharded runs are not supported by the loss-fused path")
     if shard.partitioned:
         # every rank back-propagates its share n_local / n_global of the loss: that is the global gradient only for losses
         # that are sums over entries, and needs at least one entry per rank (an empty share's loss is 0 / 0)
@@ -492,7 +500,16 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         # leaves: what the integrator differentiates; only the optimised ones require (and receive) gradients
         leaves = {k: (params[k].detach().requires_grad_(True) if k in params else grids[k].detach())
                   for k in integrator.param_keys}
-        if opt_config.batch_size is not None:                          # batched rendering (:332-341)
+        if opt_config.fused_loss and opt_config.batch_size is not None:   # the same step, film + loss + gather fused (loss_fused.py)
+            loss_value, image, _, _ = render_batch_loss(
+                opt_config.batch_size, scene, ref_images, loss=opt_config.loss, sensors=sensors, params=leaves, integrator=integrator,
+                spp=spp_primal, spp_grad=spp_grad, seed=seed, seed_grad=seed_grad, sensor_table=table)
+        elif opt_config.fused_loss:
+            s_i = int(torch.rand((), generator=host_rng).item() * n_sensors)
+            loss_value, image = render_loss(scene, ref_images[s_i].reshape(-1, 3), loss=opt_config.loss, params=leaves,
+                                            integrator=integrator, sensor=s_i, spp=spp_primal, spp_grad=spp_grad, seed=seed,
+                                            seed_grad=seed_grad)
+        elif opt_config.batch_size is not None:                        # batched rendering (:332-341)
             image, _, _, sensor_idx, pixel_idx = render_batch(
                 opt_config.batch_size, scene, sensors=sensors, params=leaves, integrator=integrator,
                 spp=spp_primal, spp_grad=spp_grad, seed=seed, seed_grad=seed_grad, sensor_table=table, shard=shard)
@@ -506,8 +523,9 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             n_global = ref_values.shape[0]
             if shard.partitioned:
                 ref_values = ref_values[shard.pixel_indices(n_global, ref_values.device)]
-        # the losses normalise by the local entry count: scale to this rank's share of the global loss
-        loss_value = opt_config.loss(image, ref_values) * local_loss_scale(image.shape[0], n_global)
+        if not opt_config.fused_loss:
+            # the losses normalise by the local entry count: scale to this rank's share of the global loss
+            loss_value = opt_config.loss(image, ref_values) * local_loss_scale(image.shape[0], n_global)
         loss_value.backward()                                          # dr.backward (:350)
         done = opt.step({k: leaves[k].grad for k in keys if k in leaves and leaves[k].requires_grad},    # :352
                         bounds=param_bounds(scene_config, keys))
