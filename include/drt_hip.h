@@ -174,6 +174,21 @@ int drt_nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const flo
                              const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
                              const float *dL, const float *L_in, float *grad_sigma_t, float *grad_emission);
 
+/* Forward mode of sample(): dL_out[n][3] = J(ray) . (t_sigma_t, t_albedo) for the paths the primal call with the same
+ * rays / seed / spp traces; L_in is that call's output.  The tangent grids have the layouts of the parameters (and of
+ * the gradients): t_sigma_t (Z,Y,X,1), t_albedo (Z,Y,X,3) on the colour grid's lattice.  A NULL tangent is zero.  The
+ * estimator is the adjoint's, transposed: for any dL, sum_i <dL_i, dL_out_i> equals sum_v <grad_v, t_v> of
+ * drt_render_backward up to the order of float summation.  Writes dL_out (no accumulation), once per ray and without
+ * atomics: the result repeats bit for bit.  Ray / seed / offset / interleave conventions as for drt_render_*. */
+int drt_render_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
+                       uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
+                       float *dL_out);
+/* Forward mode of the nerf march: dL_out[n][3] = J(ray) . (t_sigma_t, t_emission), by dual numbers through the march (no
+ * L_in needed).  At the relu kink the derivative is taken as the adjoint takes it (none unless the raw density is > 0). */
+int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                            const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                            const float *t_sigma_t, const float *t_emission, float *dL_out);
+
 /* BASELINE config 5: the `nerf` march and volpathsimple scattering over ONE set of grids [sigma_t, r, g, b] in one call.
  * The reference's scenes bind ONE asset as the medium's albedo and emission grid (python/scene_config.py:109-110), so the
  * colour grid given to drt_set_medium as `albedo` is both.  Per ray, the pass computes NeRFIntegrator.sample (nerf.py:47-148;

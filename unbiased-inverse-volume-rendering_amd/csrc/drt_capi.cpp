@@ -1402,6 +1402,54 @@ static int nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const 
     return nerf_backward(h, P, cfg, g4);
 }
 
+// ---- forward mode: one launch over the job's rays, dL_out written once per ray.  No sub-batches (nothing is recorded), no path cache, no
+// ray schedule from a primal pass (the forward kernels finish every path on its own lane; an order would only be a schedule anyway)
+static void forward_params(drt::Params &P, const float *t_sigma, const float *t_colour, float *dL_out)
+{
+    // (the tangents travel where the gradients would, read only: the kernels gather where the adjoint splats; J t goes to L_out)
+    P.g_sigma = const_cast<float *>(t_sigma); P.g_albedo = const_cast<float *>(t_colour); P.L_out = dL_out;
+    P.path_cache = nullptr; P.ray_hash = nullptr; P.path_cache_cap = 0; P.path_cache_mode = 0;
+    P.block_cost = nullptr; P.block_order = nullptr; P.ray_perm = nullptr; P.ray_iters = nullptr;
+    P.rec_buf[0] = P.rec_buf[1] = nullptr; P.rec_cursor = nullptr;
+    P.tail_pool = nullptr; P.tail_count = nullptr; P.tail_cap = 0; P.tail_mode = 0;
+    P.dL = nullptr; P.dL_pix = nullptr; P.gt = nullptr;
+}
+
+int drt_render_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
+                       uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
+                       float *dL_out)
+{
+    if (h && n_rays == 0) return DRT_OK;
+    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
+    if (rc) return rc;
+    if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward: null L_in / dL_out");
+    DeviceGuard g(h->device);
+    drt::Params P;
+    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    forward_params(P, t_sigma_t, t_albedo, dL_out);
+    P.L_in = L_in;
+    DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd(P, h->stream) : drt::launch_trace_coop_fwd(P, h->stream));
+    return DRT_OK;
+}
+
+int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                            const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                            const float *t_sigma_t, const float *t_emission, float *dL_out)
+{
+    if (h && n_rays == 0) return DRT_OK;
+    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false);
+    if (rc) return rc;
+    if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward: null dL_out");
+    DeviceGuard g(h->device);
+    drt::Params P;
+    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    rc = nerf_fill(h, P, cfg, emission);
+    if (rc) return rc;
+    forward_params(P, t_sigma_t, t_emission, dL_out);
+    DRT_HIP_CHECK(h, P.colour_own ? drt::launch_nerf_own_fwd(P, h->stream) : drt::launch_nerf_fwd(P, h->stream));
+    return DRT_OK;
+}
+
 // ---- nerf + volpathsimple over one set of grids (BASELINE config 5): two dense passes on two streams, see drt_fused_render_* below ------------
 // the interleaved four-channel apron-brick copy [sigma_t, r, g, b] (eval4): (re)built when the parameter grids changed since the last copy
 // `rgb`: the colour grid of the copy - the medium's albedo (the fused pass: the copy is kept until the parameters change) or the caller's emission

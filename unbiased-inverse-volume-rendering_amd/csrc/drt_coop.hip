@@ -119,4 +119,10 @@ hipError_t launch_trace_coop(const Params &P, bool adjoint, bool count, hipStrea
     return launch_trace_coop_t<false>(P, adjoint, count, stream, between, between_ctx, called);
 }
 
+hipError_t launch_trace_coop_fwd(const Params &P, hipStream_t stream)
+{
+    if (P.mgrid) return launch_trace_coop_super_fwd(P, stream);      // drt_coop_super.hip
+    return launch_trace_coop_fwd_t<false>(P, stream);
+}
+
 }  // namespace drt

@@ -145,6 +145,88 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
 }
 
 
+// Forward mode (drt_render_forward): CoopTracer<FWD> runs the adjoint's paths with dL = 1, gathering from the tangent grids where the
+// adjoint splats (the tangent grids are Params::g_sigma / g_albedo), and writes J t of its ray to L_out - once, from the ray's own lane (no hand-off, no tail pool, no atomics: the result is
+// bit-reproducible).  The global majorant's NEE walks take every step on the walk's own lane (CoopTracer::coop_rt).
+template <bool ENV, bool SPEC, bool SUPER>
+__global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(const Params P)
+{
+    uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map (see trace_coop_kernel)
+#if DRT_XCD_RUN > 0
+    {
+        const uint32_t span = 8u * DRT_XCD_RUN;
+        const uint32_t full = (gridDim.x / span) * span;
+        if (b < full) {
+            uint32_t grp = b / span, r = b % span;
+            b = grp * span + (r % 8u) * DRT_XCD_RUN + r / 8u;
+        }
+    }
+#endif
+    const uint64_t i = P.ray_first + (uint64_t) b * blockDim.x + threadIdx.x;
+    CoopTracer<false, ENV, false, SPEC, false, SUPER, true> tr(P);
+    __shared__ uint32_t slot_lds[4 * 64];
+    tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
+    __shared__ uint64_t jump_lds[2 * (kJumpMax + 1)];
+    if (threadIdx.x <= kJumpMax) { jump_lds[2 * threadIdx.x] = kJump.A[threadIdx.x]; jump_lds[2 * threadIdx.x + 1] = kJump.G[threadIdx.x]; }
+    tr.jump = jump_lds;
+    __syncthreads();
+    __shared__ uint32_t occ_lds[kOccWords];
+    if (P.occ && !dbg(P.debug_flags, 16u)) {
+        for (int w = threadIdx.x; w < P.occ_words; w += blockDim.x) occ_lds[w] = P.occ[w];
+        __syncthreads();
+        tr.occ = occ_lds;
+    }
+    if constexpr (SUPER) {
+        __shared__ uint32_t mocc_lds[kOccWords];
+        if (P.mocc && P.mocc_words <= kOccWords && !dbg(P.debug_flags, 8388608u)) {
+            for (int w = threadIdx.x; w < P.mocc_words; w += blockDim.x) mocc_lds[w] = P.mocc[w];
+            __syncthreads();
+            tr.mocc = mocc_lds;
+        }
+    }
+    const bool job = i < P.n_rays;
+    Pcg32 S; S.state = 0; S.inc = 1;
+    Ray ray; ray.o = v3(0, 0, 0); ray.d = v3(0, 0, 1); ray.maxt = kLargest;
+    const float ones[3] = { 1.0f, 1.0f, 1.0f };
+    float Lin[3] = { 0, 0, 0 };
+    tr.tg[0] = tr.tg[1] = tr.tg[2] = 0.0f;
+    tr.fsum = 0.0f;
+    if (job) {
+        uint64_t g64 = P.chunk ? P.ray_offset + (i / P.chunk) * P.stride + (i % P.chunk) : P.ray_offset + i;
+        uint32_t gi = (uint32_t) g64;
+        tr.ray_index = gi;
+        S.seed(P.seed, gi);
+        if (P.sensor_flow) {
+            float ux = S.next_1d(), uy = S.next_1d();
+            sensor_ray(P, gi / P.spp, ux, uy, ray.o, ray.d);
+        } else {
+            ray.o = v3(P.rays_o[3 * i], P.rays_o[3 * i + 1], P.rays_o[3 * i + 2]);
+            ray.d = v3(P.rays_d[3 * i], P.rays_d[3 * i + 1], P.rays_d[3 * i + 2]);
+        }
+        Lin[0] = P.L_in[3 * i]; Lin[1] = P.L_in[3 * i + 1]; Lin[2] = P.L_in[3 * i + 2];
+    }
+    float L[3];
+    tr.template sample<true, false>(job, S, ray, ones, Lin, nullptr, L);
+    if (job) { P.L_out[3 * i] = tr.tg[0]; P.L_out[3 * i + 1] = tr.tg[1]; P.L_out[3 * i + 2] = tr.tg[2]; }
+}
+
+template <bool SUPER>
+hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
+{
+    if (P.n_rays <= P.ray_first) return hipSuccess;
+    dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
+    const bool env = P.env_pix != nullptr;
+    const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, 2097152u);
+    if (spec) {
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER>), grid, block, 0, stream, P);
+    } else {
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER>), grid, block, 0, stream, P);
+    }
+    return hipGetLastError();
+}
+
 // launch of the instantiation that fits the job
 template <bool SUPER>
 hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between = nullptr,

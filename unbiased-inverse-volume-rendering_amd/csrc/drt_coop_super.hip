@@ -10,4 +10,6 @@ hipError_t launch_trace_coop_super(const Params &P, bool adjoint, bool count, hi
     return launch_trace_coop_t<true>(P, adjoint, count, stream);
 }
 
+hipError_t launch_trace_coop_super_fwd(const Params &P, hipStream_t stream) { return launch_trace_coop_fwd_t<true>(P, stream); }
+
 }  // namespace drt

@@ -110,7 +110,13 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 // (Medium::sample_interaction walks the supergrid cells, dda_collision in drt_device.h), the steps of a walk are no
 // longer independent, and every tracking step is taken on the walk's own lane - the same loops, path cache, record
 // streams and estimator specialisation otherwise, so that ONE tracer serves every configuration.
-template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false>
+// FWD: forward mode (trace_coop_fwd_kernel).  The adjoint pass is linear in dL, and each of its splats adds
+// sum_k dL_k w_k c dq(x)/dtheta to the gradient of a trilinear lookup q; its transpose adds w_k c q_t(x) to channel k of
+// the ray's tangent tg[], with q_t the same lookup into the tangent grid (gather_sigma_t / gather_colour).  So sample<true>
+// runs with dL = 1 and every splat becomes a gather - same paths, same random numbers.  Where the adjoint has summed the
+// channels before its splat (the NEE walk's a_sum, the scatter sites' gs) the channels are kept apart.  Every ray ends on
+// its own lane: no hand-off (wgc), no tail pool, no path cache, no atomics.
+template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false>
 struct CoopTracer {
     const Params &P;
     float maj, inv_maj;
@@ -127,6 +133,8 @@ struct CoopTracer {
     uint32_t work;          // tracking steps of this ray's main path (primal pass: feeds block_cost)
     uint32_t iters;         // bounce-loop iterations of this ray's main path (primal pass: feeds ray_perm)
     uint32_t cnt[C_COUNT];
+    float tg[3];            // FWD: this ray's tangent J t
+    float fsum;             // FWD: sum over the steps of the current transmittance walk of -(1/maj) / tr * sigma_t'(p)
 
     __device__ __forceinline__ CoopTracer(const Params &p) : P(p)
     {
@@ -221,7 +229,7 @@ struct CoopTracer {
         while (pending) {
             const int Jprof = __popcll(pending); (void) Jprof;
             round_begin(2);
-            if (SUPER || (kSolo && __popcll(pending) >= DRT_COOP_SOLO_MIN)) {
+            if (SUPER || (ADJ && FWD) || (kSolo && __popcll(pending) >= DRT_COOP_SOLO_MIN)) {
                 // more than half of the lanes carry a walk: a round would give every walk ONE lane (m = 1) - take that
                 // step on the walk's own lane, without the slot table, the gathers and the jump-ahead (same arithmetic).
                 // With a supergrid every step is taken this way.
@@ -236,7 +244,8 @@ struct CoopTracer {
                     const float Tout = inside ? T * tr : T;
                     if (inside) {
                         count(C_RT);
-                        if constexpr (ADJ) if (tr > 0.0f) {                     // :487-492
+                        if constexpr (ADJ && FWD) { if (tr > 0.0f) fsum += (-lim / tr) * gather_sigma_t(P, p); }   // (forward walks: every step on its own lane)
+                        else if constexpr (ADJ) if (tr > 0.0f) {                // :487-492
                             splat_sigma_t<DEFER>(P, p, -(a_sum * lim) / tr, rec);
                             count(C_RT_ADJ);
                         }
@@ -250,7 +259,7 @@ struct CoopTracer {
                 round_end(2, Jprof);
                 continue;
             }
-            if constexpr (!SUPER) {
+            if constexpr (!SUPER && !(ADJ && FWD)) {
                 int m, lg, js, c, owner, my_rank; bool serve;
                 round_setup(job, pending, m, lg, js, c, serve, owner, my_rank);
                 // the walk this lane serves
@@ -432,7 +441,7 @@ struct CoopTracer {
                 walk = si.valid; tmax = si.t;
             }
         }
-        const float a_sum = (ADJ && job) ? (adj[0] + adj[1]) + adj[2] : 0.0f;
+        const float a_sum = (ADJ && !FWD && job) ? (adj[0] + adj[1]) + adj[2] : 0.0f;
         uint32_t steps = 0;
         float T = coop_rt<ADJ>(walk, p, wd, tmax, S, a_sum, &steps);
         if (!walk) T = 0.0f;
@@ -454,11 +463,19 @@ struct CoopTracer {
     {
         Pcg32 clone = S;                                                        // :383
         float emitted[3];
-        float ds_pdf = sample_emitter<false>(job, p, S, nullptr, emitted, cmode, ce);   // :385
+        // (forward mode: the walk that measures the transmittance gathers its tangent too - the adjoint walks the clone again)
+        constexpr bool kFwd = ADJ && FWD;
+        if constexpr (kFwd) fsum = 0.0f;
+        float ds_pdf = sample_emitter<kFwd>(job, p, S, nullptr, emitted, cmode, ce);   // :385
         float w = mis_weight(ds_pdf, kInvFourPi);                               // :391
 #pragma unroll
         for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * kInvFourPi) * w) * emitted[k] : 0.0f;
-        if constexpr (ADJ) {                                                    // :393-401
+        if constexpr (kFwd) {                                                   // :393-401 transposed: a_sum = sum_k dL_k contrib_k, kept apart
+            if (job) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) tg[k] += (dL[k] * contrib[k]) * fsum;
+            }
+        } else if constexpr (ADJ) {                                             // :393-401
             float adj[3] = { 0.0f, 0.0f, 0.0f };
             if (job) { adj[0] = dL[0] * contrib[0]; adj[1] = dL[1] * contrib[1]; adj[2] = dL[2] * contrib[2]; }
             float unused[3];
@@ -545,7 +562,7 @@ struct CoopTracer {
             count(C_DRT);
         }
         float Li[3];
-        if constexpr (SPEC) {
+        if constexpr (SPEC && !FWD) {
             if (wgc) {                                                          // (workgroup-uniform: set by the kernel)
                 // hand-off mode: everything the final splat needs is computed now and travels with the recursive path
                 Tail tl;
@@ -565,6 +582,14 @@ struct CoopTracer {
             if constexpr (!G4) eval_albedo(P, p, alb);                          // :578
             count(C_ALB);
             float ww = w * W;
+            if constexpr (FWD) {                                                // :577-581 transposed: (sigma_t albedo_k)' per channel
+                const float ts = gather_sigma_t(P, p);
+                float ta[3];
+                gather_colour(P, p, ta);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) tg[k] += ((ww * adj[k]) * Li[k]) * (alb[k] * ts + sig * ta[k]);
+                return;
+            }
             float gs = 0.0f, ga[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -579,6 +604,13 @@ struct CoopTracer {
     // backpropagate_transmittance (volpathsimple.py:584-607)
     __device__ __forceinline__ void backprop_transmittance(Pcg32 &A, const Ray &ray, float interval, const float dL[3], const float result[3])
     {
+        if constexpr (FWD) {                                                    // transposed: adjw = sum_k dL_k result_k, kept apart
+            float s = 0.0f;
+            for (int j = 0; j < 4; ++j) s += gather_sigma_t(P, ray_at(ray.o, ray.d, A.next_1d() * interval));   // :595
+#pragma unroll
+            for (int k = 0; k < 3; ++k) tg[k] += -((dL[k] * result[k]) * (interval / 4.0f)) * s;
+            return;
+        }
         float adjw = (dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2];
         float g = -(adjw * (interval / 4.0f));
         for (int j = 0; j < 4; ++j) {
@@ -800,7 +832,7 @@ struct CoopTracer {
         int it = 0;                                                             // bounce-loop iterations this ray has run
         // recursive paths of the specialised adjoint kernels: sparse waves hand their last paths to wave 0 (wg_handoff)
         // ... and so do the main paths of the specialised primal kernels (their radiance is then written by wg_handoff)
-        constexpr bool kWgc = !ADJ && SPEC;
+        constexpr bool kWgc = !ADJ && SPEC && !FWD;
         bool wgc_on = false;
         Tail tl;
         uint32_t taken = 0;
@@ -882,15 +914,26 @@ struct CoopTracer {
                         w = s2 / (1.0f + s2);
                     }
                     float inv_pdf = 1.0f / mei.sigma_t;
-                    float gs = 0.0f, ga[3];
+                    if constexpr (FWD) {                                        // :170 transposed: (sigma_t albedo_k)' per channel
+                        const float ts = gather_sigma_t(P, mei.p);
+                        float ta[3];
+                        gather_colour(P, mei.p, ta);
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        float Li = result[k] / fmaxf(1e-8f, albedo[k]);         // :167
-                        float a = ((w * dL[k]) * Li) * inv_pdf;
-                        gs += a * albedo[k];
-                        ga[k] = a * mei.sigma_t;
+                        for (int k = 0; k < 3; ++k) {
+                            float Li = result[k] / fmaxf(1e-8f, albedo[k]);     // :167
+                            tg[k] += (((w * dL[k]) * Li) * inv_pdf) * (albedo[k] * ts + mei.sigma_t * ta[k]);
+                        }
+                    } else {
+                        float gs = 0.0f, ga[3];
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            float Li = result[k] / fmaxf(1e-8f, albedo[k]);     // :167
+                            float a = ((w * dL[k]) * Li) * inv_pdf;
+                            gs += a * albedo[k];
+                            ga[k] = a * mei.sigma_t;
+                        }
+                        splat_scatter<DEFER>(P, mei.p, gs, ga, rec); count(C_SC); count(C_SC_ALB);
                     }
-                    splat_scatter<DEFER>(P, mei.p, gs, ga, rec); count(C_SC); count(C_SC_ALB);
                 }
                 if (run) backprop_transmittance(A, ray, did_escape ? si.t : mei.t, dL, result);   // :181-189
             }

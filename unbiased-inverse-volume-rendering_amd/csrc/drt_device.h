@@ -264,6 +264,9 @@ struct Params {
     // outputs / adjoint inputs
     float *L_out;
     const float *dL, *L_in;
+    // adjoint: the gradient grids; forward mode (drt_*render_forward): the TANGENT grids, read only - the transpose reads where the splat writes,
+    // in the same layout (or nullptr: zero tangent) - and L_out receives J t per ray.  (No new fields: a field behind dL_pix changes the code of
+    // the nerf tile adjoint, whose NerfTile argument follows this block in the kernarg segment.)
     float *g_sigma, *g_albedo;
     // library-owned gradient scratch: 4 planes [sigma_t, r, g, b] in an APRON layout: one 64-byte
     // line per base corner block (3 voxels along x) holds all 8 corners of a splat -> one atomic
@@ -1122,6 +1125,40 @@ __device__ __forceinline__ void splat_scatter(const Params &P, V3 p, float gs, c
     } else {
         splat_sigma_t<false>(P, p, gs, rec);
         splat_albedo<false>(P, p, ga, rec);
+    }
+}
+
+// Forward mode: the transposes of the splats.  A splat adds w_k * g * scale to corner k of the trilinear footprint of p; its transpose reads
+// the tangent grid at the same 8 corners with the same weights (axis_setup + stencil_weights: the footprint make_grad_indices lays out in the
+// apron scratch, whose slots untile to these voxels; clamped corners coincide in both) and the same scale.  The tangent grids are in the
+// caller's layout (Params::g_sigma / g_albedo in forward mode).  No occupancy skip: a tangent may be non-zero where every sigma_t corner is 0.
+__device__ __forceinline__ float gather_sigma_t(const Params &P, V3 p)
+{
+    if (!P.g_sigma) return 0.0f;
+    const Stencil s = make_stencil(P, p);
+    float w[8]; int idx[8];
+    stencil_weights(s, w);
+    stencil_indices(s, idx);
+    float v = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v += w[k] * P.g_sigma[idx[k]];
+    return v * P.scale;
+}
+
+// colour (albedo / emission) tangent at p: the transpose of splat_albedo / splat_colour_own (make_stencil_colour: the own lattice in drt_own.hip)
+__device__ __forceinline__ void gather_colour(const Params &P, V3 p, float out[3])
+{
+    out[0] = out[1] = out[2] = 0.0f;
+    if (!P.g_albedo) return;
+    const Stencil s = make_stencil_colour(P, p);
+    float w[8]; int idx[8];
+    stencil_weights(s, w);
+    stencil_indices(s, idx);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float *t = P.g_albedo + 3 * (size_t) idx[k];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[c] += w[k] * t[c];
     }
 }
 

@@ -936,6 +936,7 @@ hipError_t launch_brick_sigma(const float *src, float *dst, int rx, int ry, int 
 }
 
 hipError_t launch_nerf(const Params &P, bool adjoint, bool count, hipStream_t stream) { return launch_nerf_t(P, adjoint, count, stream); }
+hipError_t launch_nerf_fwd(const Params &P, hipStream_t stream) { return launch_nerf_fwd_t(P, stream); }
 
 hipError_t launch_untile(const Params &P, hipStream_t stream)
 {

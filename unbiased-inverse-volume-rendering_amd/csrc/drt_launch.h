@@ -54,6 +54,14 @@ hipError_t launch_trace_coop_super(const Params &P, bool adjoint, bool count, hi
 typedef hipError_t (*coop_between_fn)(void *ctx);
 hipError_t launch_trace_coop(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between = nullptr,
                              void *between_ctx = nullptr, bool *called = nullptr);
+// Forward mode (drt_*render_forward): L_out = J t per ray, with the tangent grids in Params::g_sigma / g_albedo (read only).  The volpathsimple kernels are
+// CoopTracer<FWD> for every kind of majorant (drt_coop.hip, drt_coop_super.hip; drt_own.hip for colour grids on their own lattice); the nerf
+// kernel marches with dual numbers (drt_nerf_kernel.h)
+hipError_t launch_trace_coop_fwd(const Params &P, hipStream_t stream);
+hipError_t launch_trace_coop_super_fwd(const Params &P, hipStream_t stream);
+hipError_t launch_trace_own_fwd(const Params &P, hipStream_t stream);
+hipError_t launch_nerf_fwd(const Params &P, hipStream_t stream);
+hipError_t launch_nerf_own_fwd(const Params &P, hipStream_t stream);
 hipError_t launch_ray_perm(const uint8_t *iters, uint64_t n_rays, uint16_t *perm, uint32_t *block_cost, hipStream_t stream);
 hipError_t launch_block_order(const uint32_t *cost, uint32_t n_blocks, uint32_t *order, bool heavy_first, hipStream_t stream);
 hipError_t launch_untile(const Params &P, hipStream_t stream);

@@ -127,6 +127,93 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
     }
 }
 
+// ---------------------------------------------------------------------------
+// Forward mode of the march (drt_nerf_render_forward): the primal of nerf_kernel with dual numbers, J t written to L_out.  Each query
+// looks up sigma_t' and emission' in the tangent grids (Params::g_sigma / g_albedo) through the stencils of the adjoint's splats
+// (gather_sigma_t / gather_colour, no occupancy skip), and the derivative is carried through the opacity, the throughput, the weights
+// and the emitter term behind the medium.  The relu kink takes the adjoint's convention: no derivative unless raw > 0.  One ray per
+// lane, one write per ray.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P)
+{
+    uint64_t i = P.ray_first + (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    __shared__ uint32_t occ_lds[kOccWords];
+    const uint32_t *occ = nullptr;
+    if (P.occ) {
+        for (int w = threadIdx.x; w < P.occ_words; w += blockDim.x) occ_lds[w] = P.occ[w];
+        __syncthreads();
+        occ = occ_lds;
+    }
+    if (i >= P.n_rays) return;
+    uint64_t g64 = P.chunk ? P.ray_offset + (i / P.chunk) * P.stride + (i % P.chunk) : P.ray_offset + i;
+    uint32_t gi = (uint32_t) g64;
+    Pcg32 S; S.seed(P.seed, gi);
+    V3 o, d;
+    if (P.sensor_flow) {
+        float ux = S.next_1d(), uy = S.next_1d();
+        sensor_ray(P, gi / P.spp, ux, uy, o, d);
+    } else {
+        o = v3(P.rays_o[3 * i], P.rays_o[3 * i + 1], P.rays_o[3 * i + 2]);
+        d = v3(P.rays_d[3 * i], P.rays_d[3 * i + 1], P.rays_d[3 * i + 2]);
+    }
+    float dres[3] = { 0.0f, 0.0f, 0.0f };                                // the tangent of `result`
+    float throughput = 1.0f, weights_sum = 0.0f, dthroughput = 0.0f, dweights_sum = 0.0f;
+    Hit si = box_hit(P, o, d);                                           // nerf.py:67-79
+    bool active = si.valid, escaped = !active;
+    if (active) {
+        o = offset_p(si, d);
+        si = box_hit(P, o, d);
+        active = si.valid;
+    }
+    if (active) {
+        const int N = P.nerf_queries;
+        float step = P.nerf_jitter ? (si.t - 0.0f) / (float) N : (si.t - 0.0f) / (float)(N - 1);   // :6-10,82
+        float t_a = 0.0f;
+        float jit = S.next_1d();                                         // :88
+        for (int j = 0; j < N; ++j) {                                    // :94-129
+            float t_b = P.nerf_jitter ? step * ((float)(j + 1) + jit) : step * (float)(j + 1);
+            float dt = t_b - t_a;
+            V3 p = ray_at(o, d, t_b);
+            const float raw = eval_sigma_t(P, p, occ);
+            const float sigma = P.nerf_relu ? fmaxf(0.0f, raw) : raw;
+            const float dsigma = (P.nerf_relu && !(raw > 0.0f)) ? 0.0f : gather_sigma_t(P, p);
+            const bool last = !(j + 1 < N);
+            const float a = last ? 1.0f : drt_expf(-sigma * dt);         // :104-106
+            const float da = last ? 0.0f : (-dt * a) * dsigma;
+            const float weight = (1.0f - a) * throughput;
+            const float dweight = (1.0f - a) * dthroughput - da * throughput;
+            float em[3], dem[3];
+            eval_rgb(P, P.emission, p, em);
+            gather_colour(P, p, dem);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dres[k] += dweight * em[k] + weight * dem[k];
+            t_a = t_b;
+            if (!last) {                                                 // :117-120
+                dthroughput = dthroughput * (a + 1e-10f) + throughput * da;
+                throughput *= a + 1e-10f;
+                weights_sum += weight; dweights_sum += dweight;
+            }
+        }
+    }
+    bool active_e = escaped || active;                                   // :131-146
+    if (P.hide_emitters) active_e = active_e && (weights_sum > 0.0f);
+    if (active_e) {
+        float Le[3];
+        if (P.env_pix) emitter_eval<true>(P, d, Le); else emitter_eval<false>(P, d, Le);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dres[k] += -dweights_sum * Le[k];
+    }
+    P.L_out[3 * i] = dres[0]; P.L_out[3 * i + 1] = dres[1]; P.L_out[3 * i + 2] = dres[2];
+}
+
+hipError_t launch_nerf_fwd_t(const Params &P, hipStream_t stream)
+{
+    if (P.n_rays <= P.ray_first) return hipSuccess;
+    dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
+    hipLaunchKernelGGL(nerf_fwd_kernel, grid, block, 0, stream, P);
+    return hipGetLastError();
+}
+
 hipError_t launch_nerf_t(const Params &P, bool adjoint, bool count, hipStream_t stream)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;

@@ -22,4 +22,12 @@ hipError_t launch_trace_own(const Params &P, bool adjoint, bool count, hipStream
 
 hipError_t launch_nerf_own(const Params &P, bool adjoint, bool count, hipStream_t stream) { return launch_nerf_t(P, adjoint, count, stream); }
 
+hipError_t launch_trace_own_fwd(const Params &P, hipStream_t stream)
+{
+    if (P.mgrid) return launch_trace_coop_fwd_t<true>(P, stream);
+    return launch_trace_coop_fwd_t<false>(P, stream);
+}
+
+hipError_t launch_nerf_own_fwd(const Params &P, hipStream_t stream) { return launch_nerf_fwd_t(P, stream); }
+
 }  // namespace drt

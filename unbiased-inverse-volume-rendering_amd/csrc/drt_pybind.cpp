@@ -166,6 +166,29 @@ public:
         }
         check(rc, "drt_nerf_render_backward");
     }
+    void render_forward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
+                        uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_render_forward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
+                                    ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out));
+        }
+        check(rc, "drt_render_forward");
+    }
+    void nerf_render_forward(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                             uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_emission, uintptr_t dL_out)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_forward(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
+                                         spp, seed, ptr<const float>(t_sigma), ptr<const float>(t_emission), ptr<float>(dL_out));
+        }
+        check(rc, "drt_nerf_render_forward");
+    }
     void fused_render_primal(const py::dict &props, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp,
                              uint32_t seed, uintptr_t L_nerf, uintptr_t L_drt)
     {
@@ -368,6 +391,8 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("render_backward", &Integrator::render_backward)
         .def("nerf_render_primal", &Integrator::nerf_render_primal)
         .def("nerf_render_backward", &Integrator::nerf_render_backward)
+        .def("render_forward", &Integrator::render_forward)
+        .def("nerf_render_forward", &Integrator::nerf_render_forward)
         .def("fused_render_primal", &Integrator::fused_render_primal)
         .def("fused_render_backward", &Integrator::fused_render_backward)
         .def("batch_sample_rays", &Integrator::batch_sample_rays, py::arg("sensors"), py::arg("n_sensors"), py::arg("batch"),

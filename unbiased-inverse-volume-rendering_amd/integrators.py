@@ -159,6 +159,28 @@ class _DeviceIntegrator:
     def native_handle(self, scene: Scene):
         return self._bind(scene)[0]
 
+    # -- forward mode -------------------------------------------------------------------------------------------
+    forward_needs_state = True      # sample(Forward) needs the primal radiance (state_in): volpathsimple's transposed adjoint does
+
+    def check_tangents(self, scene: Scene, tangents) -> Dict[str, Optional[torch.Tensor]]:
+        """The tangents of sample(Forward) / render_forward, checked on the host before any handle exists: a dict from keys of
+        `param_keys` to float32 contiguous tensors shaped and placed like the parameter grid (a missing key or None: zero tangent)."""
+        if tangents is None:
+            tangents = {}
+        if not isinstance(tangents, dict):
+            raise TypeError("tangents must be a dict {parameter key: tensor}")
+        extra = sorted(set(tangents) - set(self.param_keys))
+        if extra:
+            raise ValueError(f"tangents for unknown parameters {extra} (this integrator's parameters: {list(self.param_keys)})")
+        out = {}
+        for k in self.param_keys:
+            t = tangents.get(k)
+            if t is not None:
+                grid = _grid_of(scene, k)
+                _check(t, tuple(grid.shape), grid.device if isinstance(grid, torch.Tensor) else t.device, f"tangents['{k}']")
+            out[k] = t
+        return out
+
     def _colour_grid(self, scene: Scene):
         """The colour grid whose lattice the handle is told about (drt_set_colour_resolution): the albedo here, the emission for `nerf`."""
         return scene.medium.albedo
@@ -258,6 +280,18 @@ class _DeviceIntegrator:
         return n, 0, 0
 
 
+def _grid_of(scene: Scene, key: str):
+    m = scene.medium
+    grid = {SIGMA_T_KEY: m.sigma_t, ALBEDO_KEY: m.albedo, EMISSION_KEY: m.emission}[key]
+    if grid is None:
+        raise ValueError(f"the scene's medium has no '{key}' grid")
+    return grid
+
+
+def _ptr(t: Optional[torch.Tensor]) -> int:
+    return 0 if t is None else t.data_ptr()
+
+
 class VolpathSimpleIntegrator(_DeviceIntegrator):
     """Differential-ratio-tracking volumetric path tracer (volpathsimple.py:10-36).
 
@@ -294,12 +328,19 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
 
     def sample(self, mode, scene: Scene, sampler: IndependentSampler, ray: RayBatch,
                δL: Optional[torch.Tensor] = None, state_in: Optional[torch.Tensor] = None,
-               active=None, grads: Optional[Dict[str, torch.Tensor]] = None, **kwargs):
+               active=None, grads: Optional[Dict[str, torch.Tensor]] = None,
+               tangents: Optional[Dict[str, torch.Tensor]] = None, **kwargs):
         """-> (L, valid, state_out).  Primal: L = state_out = radiance [n,3].
         Backward: gradients are ACCUMULATED into `grads[key]` (tensors shaped like the
-        parameters); returns (None, True, None).  Extra kwargs (`depth`, `reparam`)
+        parameters); returns (None, True, None).  Forward: state_in = the primal radiance of the
+        same rays / seed, `tangents` = {key: tangent grid} (missing: zero); returns (dL, True, None)
+        with dL [n,3] = J t per ray (drt_render_forward).  Extra kwargs (`depth`, `reparam`)
         are absorbed like the reference does (volpathsimple.py:47)."""
         mode = ADMode(int(mode))
+        if mode == ADMode.Forward:
+            tangents = self.check_tangents(scene, tangents)
+            if state_in is None:
+                raise ValueError("sample(Forward) needs state_in (the primal radiance of the same rays and seed)")
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)
@@ -320,8 +361,11 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
             h.render_backward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
                               δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
             return None, True, None
-        raise NotImplementedError("forward-mode differentiation is not supported "
-                                  "(render_batch_forward raises in the reference too, batched.py:200-209)")
+        _check(state_in, (n, 3), dev, "state_in")
+        dL = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        h.render_forward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
+                         _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr())
+        return dL, True, None
 
     def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
@@ -361,6 +405,7 @@ class NeRFIntegrator(_DeviceIntegrator):
 
     param_keys = (SIGMA_T_KEY, EMISSION_KEY)
     needs_albedo = False
+    forward_needs_state = False     # the forward march carries its own dual numbers
 
     def _colour_grid(self, scene: Scene):
         return scene.medium.emission
@@ -403,10 +448,14 @@ class NeRFIntegrator(_DeviceIntegrator):
 
     def sample(self, mode, scene: Scene, sampler: IndependentSampler, ray: RayBatch,
                δL: Optional[torch.Tensor] = None, state_in: Optional[torch.Tensor] = None,
-               active=None, grads: Optional[Dict[str, torch.Tensor]] = None, **kwargs):
+               active=None, grads: Optional[Dict[str, torch.Tensor]] = None,
+               tangents: Optional[Dict[str, torch.Tensor]] = None, **kwargs):
         """-> (L, valid, state_out) (nerf.py:47-58); Backward accumulates into `grads`
-        (keys sigma_t / emission)."""
+        (keys sigma_t / emission); Forward returns (dL [n,3] = J t per ray, True, None) for
+        `tangents` = {key: tangent grid} (missing: zero; state_in is not needed)."""
         mode = ADMode(int(mode))
+        if mode == ADMode.Forward:
+            tangents = self.check_tangents(scene, tangents)
         h, dev = self._bind(scene)
         em = scene.medium.emission
         if not isinstance(em, torch.Tensor):
@@ -432,7 +481,10 @@ class NeRFIntegrator(_DeviceIntegrator):
             h.nerf_render_backward(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp),
                                    sampler.seed_value, δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
             return None, True, None
-        raise NotImplementedError("forward-mode differentiation is not supported")
+        dL = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        h.nerf_render_forward(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
+                              _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
+        return dL, True, None
 
     def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):

@@ -10,6 +10,9 @@ at (seed_grad, spp_grad):
     (3) sample(Backward, same sampler, dL, state_in = L)    -> gradients
 exposed to PyTorch through a `torch.autograd.Function` so that
 `loss.backward()` / an optimizer work like `dr.backward(loss)` / `opt.step()`.
+Forward mode (`render_forward`, the op's `jvp` for `torch.autograd.forward_ad`): the derivative
+image dI/dθ·t, Mitsuba's `dr.forward` / `render_forward`, from the same paths as the adjoint
+(sample(Forward): the adjoint transposed, csrc/drt_coop_tracer.h).
 """
 from __future__ import annotations
 
@@ -112,6 +115,23 @@ def render_backward(scene: Scene, integrator, grad_image: torch.Tensor, sensor: 
     return grads
 
 
+def render_forward(scene: Scene, integrator, tangents: Optional[Dict[str, torch.Tensor]], sensor: int = 0, spp: int = 1,
+                   seed: int = 0, shard: Optional[ShardSpec] = None) -> torch.Tensor:
+    """Forward-mode derivative image of the local pixels, [n_local_pixels, 3]: J·t for the tangents `tangents`
+    ({key of integrator.param_keys: tensor shaped like that grid}; a missing key or None is a zero tangent).  The primal
+    pass at (seed, spp) gives the tangent pass its state_in; both trace the same paths, and the film develops the per-ray
+    tangents with its summation order.  For any image gradient g, <g, render_forward(t)> equals <render_backward(g), t> at
+    the same seed and spp up to float summation order.  A sharded call returns its local pixels and never communicates."""
+    tangents = integrator.check_tangents(scene, tangents)
+    batch = _sensor_batch(scene, sensor, spp, shard)
+    sampler = IndependentSampler(seed, spp)
+    state = None
+    if integrator.forward_needs_state:
+        _, _, state = integrator.sample(ADMode.Primal, scene, sampler.clone(), batch)
+    dL, _, _ = integrator.sample(ADMode.Forward, scene, sampler, batch, state_in=state, tangents=tangents)
+    return integrator.develop(scene, dL, spp)
+
+
 class _RenderOp(torch.autograd.Function):
     """Counterpart of `mi._RenderOp` / `_BatchedRenderOp` (batched.py:13-85)."""
 
@@ -129,6 +149,13 @@ class _RenderOp(torch.autograd.Function):
         k0, k1 = ctx.integrator.param_keys
         return g[k0], g[k1], None, None, None, None, None, None, None, None
 
+    @staticmethod
+    def jvp(ctx, t0, t1, *_):
+        # Mitsuba's convention: the tangent image is its own estimate at (seed_grad, spp_grad), as the gradient is (batched.py:58-66)
+        k0, k1 = ctx.integrator.param_keys
+        tangents = {k: (t.contiguous() if t is not None else None) for k, t in ((k0, t0), (k1, t1))}
+        return render_forward(ctx.scene, ctx.integrator, tangents, ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard)
+
 
 def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integrator=None,
            sensor: int = 0, spp: int = 1, spp_grad: int = 0, seed: int = 0, seed_grad: int = 0,
@@ -136,7 +163,7 @@ def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integ
     """`mi.render`: image of the local pixels, [n_local_pixels, 3] (the whole image,
     row-major, when unsharded - reshape to (H, W, 3)).  Differentiable with respect to
     the integrator's `param_keys` (sigma_t + albedo for `volpathsimple`, sigma_t + emission
-    for `nerf`)."""
+    for `nerf`), in reverse mode and - dual tensors of `torch.autograd.forward_ad` - in forward mode."""
     if integrator is None:
         raise ValueError("render: an integrator is required")
     if spp_grad == 0:
