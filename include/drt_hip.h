@@ -102,6 +102,14 @@ int drt_set_medium(drt_handle h, const float *sigma_t, const float *albedo, cons
  * the backward calls then have that shape.  NULL or {0,0,0}: sigma_t's lattice (what drt_set_medium leaves; call this after it).  Scenes
  * whose lattices differ run the kernels of csrc/drt_own.hip: correct (parity: tests/test_gpu_lattice.py), not the tuned path. */
 int drt_set_colour_resolution(drt_handle h, const int32_t res[3]);
+/* Phase function of the medium (the medium's `phase_function()`, volpathsimple.py:202-231, 380-392, 616-646).  A handle starts
+ * isotropic; drt_set_medium leaves the phase as it is.  kind DRT_PHASE_ISOTROPIC (g must be 0) or DRT_PHASE_HG, Mitsuba's `hg` plugin
+ * with asymmetry g, finite and |g| < 1 (g > 0 scatters forward).  HG runs the HG instantiations of the production tracers (csrc/drt_sq_hg.hip
+ * for supergrids, drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip); a test hook that routes a launch to an older tracer generation
+ * is refused with DRT_ERR_UNSUPPORTED.  Setting another phase invalidates what the handle planned from earlier paths (path cache, ray
+ * order); setting the same one again changes nothing.  No gradient with respect to g. */
+enum { DRT_PHASE_ISOTROPIC = 0, DRT_PHASE_HG = 1 };
+int drt_set_phase(drt_handle h, int32_t kind, float g);
 /* params.update(opt) after an optimizer step (python/optimize.py:354) and
  * medium.set_majorant_resolution_factor (:195-199): refresh the majorant from
  * the (same) parameter buffers.  No host synchronisation. */
@@ -340,7 +348,9 @@ int drt_read_timings(drt_handle h, int backward, float *out_ms, int capacity);
  * patterns, 7 sensor ray (pixel bits, ux, uy), 8 mis_weight / div / sqrt / fma,
  * 9 majorant supergrid cell (index bits), 10 exp, 11 atan2(y, x), 12 envmap eval(d)
  * rgb + pdf_direction(d), 13 envmap sample_direction(u1, u2) -> d, pdf, 14 Medium::sample_interaction_drt
- * (E2) from o along d to the box exit with the stream PCG32(tea32(0x5eed, item)) -> valid, t', W, maxt. */
+ * (E2) from o along d to the box exit with the stream PCG32(tea32(0x5eed, item)) -> valid, t', W, maxt,
+ * 15 Henyey-Greenstein sample (u1, u2, wi.xyz, g) -> wo.xyz, pdf, 16 Henyey-Greenstein eval (wo.xyz, wi.xyz) with the
+ * handle's g (drt_set_phase) -> pdf. */
 int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out);
 
 /* Profiling ablations / kernel selection for experiments; 0 in production.

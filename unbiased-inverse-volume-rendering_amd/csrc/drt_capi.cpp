@@ -24,6 +24,7 @@ struct drt_handle_s {
     drt_config cfg{};
     drt::Params base{};            // scene part of the kernel parameter block
     bool have_medium = false, have_emitter = false, have_sensor = false;
+    int32_t phase_kind = DRT_PHASE_ISOTROPIC;   // drt_set_phase (the asymmetry g travels in base.phase_g)
     float *d_majorant = nullptr;   // [2]
     // the global majorant as the HOST last saw it: drt_params_changed copies it to pinned memory behind the reduction and records an event; launches
     // look at it when the event has completed (never waiting) - a hint for kernel choice only (a thin medium: Params::sq_rounds), stale by design
@@ -326,6 +327,27 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
     //   32 / 65536 / 134217728) and the plain per-lane Tracer (drt_kernels.hip; hooks 8 / 32768) - where the variant tests keep them in lock-step.
     //   Colour grids on their own lattice (drt_set_colour_resolution): the kernels of drt_own.hip - CoopTracer with either kind of majorant, compiled
     //   with the colour lookups and splats on that lattice; no tail pool, no queued tracer (correct first: the configurations it serves are rare).
+    //   Henyey-Greenstein phase (drt_set_phase): the same choice among the HG instantiations - the queued tracer (drt_sq_hg.hip) for the
+    //   supergrids it takes, CoopTracer<HG> otherwise (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip) - without tail launches or
+    //   hand-off, and no ROUNDS kernels; the older generations have no HG code.
+    const bool hg = h->phase_kind == DRT_PHASE_HG;
+    if (hg && dbg(h->debug_flags, 32u | 65536u | 134217728u | 8u | 32768u))
+        return fail(h, DRT_ERR_UNSUPPORTED, "the Henyey-Greenstein phase function has no code in the older tracer generations: the test hook "
+                                            "routes this launch to one of them (debug flags 0x%x)", h->debug_flags);
+    auto launch_coop_hg = [&]() -> int {
+        drt::Params Q = P;
+        Q.tail_pool = nullptr; Q.tail_count = nullptr; Q.tail_cap = 0; Q.tail_mode = 0;
+        if (P.mgrid) Q.ray_perm = nullptr;
+        if (P.colour_own) DRT_HIP_CHECK(h, drt::launch_trace_own_hg(Q, adjoint, h->counting, h->stream));
+        else DRT_HIP_CHECK(h, drt::launch_trace_coop_hg(Q, adjoint, h->counting, h->stream));
+        if (h->timing) {
+            DRT_HIP_CHECK(h, hipEventRecord(b, h->stream));
+            h->timed[which].emplace_back(a, b);
+        }
+        return DRT_OK;
+    };
+    // (test hook 4096, which keeps supergrid launches off the queued tracer: CoopTracer<SUPER, HG> here - the HG kernels' tracer-agreement tests)
+    if (hg && (P.colour_own || !P.mgrid || dbg(h->debug_flags, 4096u))) return launch_coop_hg();
     if (P.colour_own) {
         drt::Params Q = P;
         Q.tail_pool = nullptr; Q.tail_count = nullptr; Q.tail_cap = 0; Q.tail_mode = 0;
@@ -353,6 +375,7 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
     const bool super3 = false;
 #endif
     const bool super = (super_path && sq_ok) || super3;
+    if (hg && !super) return launch_coop_hg();                                // (supergrids the queued tracer does not take)
     if (super) {
         drt::Params Q = P;
         Q.queues = h->d_queues;
@@ -423,7 +446,7 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
         else if (h->majorant_pending) (void) hipGetLastError();                        // (hipErrorNotReady is not an error)
         {
             const float dx = P.bmax[0] - P.bmin[0], dy = P.bmax[1] - P.bmin[1], dz = P.bmax[2] - P.bmin[2];
-            Q.sq_rounds = (!adjoint && h->majorant_seen >= 0.0f && h->majorant_seen * std::sqrt(dx * dx + dy * dy + dz * dz) < 3.0f) ? 1u : 0u;
+            Q.sq_rounds = (!hg && !adjoint && h->majorant_seen >= 0.0f && h->majorant_seen * std::sqrt(dx * dx + dy * dy + dz * dz) < 3.0f) ? 1u : 0u;
         }
         DRT_HIP_CHECK(h, hipMemsetAsync(h->d_queues, 0, 8 * sizeof(unsigned long long), h->stream));
         if (queued) {
@@ -454,7 +477,7 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
 #define DRT_SQ_TAIL_THIN 0          // 0: primal launches over a thin medium (the ROUNDS kernels) make no tail launch - their few real paths are short, a second
                                     // launch over the whole chip costs more than they do (config3_as_reproduce 302-305 -> 308-310 iterations/s); 1: they do
 #endif
-            const bool tail = DRT_SQ_TAIL && (big || solo) && !dbg(h->debug_flags, 268435456u) && (DRT_SQ_TAIL_THIN || !Q.sq_rounds);
+            const bool tail = !hg && DRT_SQ_TAIL && (big || solo) && !dbg(h->debug_flags, 268435456u) && (DRT_SQ_TAIL_THIN || !Q.sq_rounds);
             if (tail) {
                 const size_t cap = (size_t) h->n_cus * drt::sq_tail_push();
                 const size_t need_b = 256 + cap * drt::sq_tail_entry_quads() * sizeof(uint4);
@@ -467,7 +490,11 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
                     Q.tail_count = (uint32_t *) h->d_sq_tail; Q.tail_pool = (uint4 *) ((char *) h->d_sq_tail + 256); Q.tail_cap = (uint32_t) cap; Q.tail_mode = 0;
                 }
             }
-            DRT_HIP_CHECK(h, drt::launch_trace_sq(Q, adjoint, h->counting, h->n_cus, h->stream));
+            if (hg) {
+                Q.tail_pool = nullptr; Q.tail_count = nullptr; Q.tail_cap = 0; Q.tail_mode = 0;
+                DRT_HIP_CHECK(h, drt::launch_trace_sq_hg(Q, adjoint, h->counting, h->n_cus, h->stream));
+            }
+            else DRT_HIP_CHECK(h, drt::launch_trace_sq(Q, adjoint, h->counting, h->n_cus, h->stream));
             if (tail && Q.tail_pool) {
                 hipEvent_t ta = nullptr, tb = nullptr;
                 if (big) {
@@ -1090,6 +1117,26 @@ int drt_set_colour_resolution(drt_handle h, const int32_t res[3])
     return DRT_OK;
 }
 
+int drt_set_phase(drt_handle h, int32_t kind, float g)
+{
+    // (the arguments are checked before the handle: a wrong call is refused with its own message even without one)
+    if (kind != DRT_PHASE_ISOTROPIC && kind != DRT_PHASE_HG)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase: unknown phase kind %d (0 isotropic, 1 hg)", (int) kind);
+    if (!std::isfinite(g) || !(std::fabs(g) < 1.0f))
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase: g must be finite with |g| < 1 (got %g)", (double) g);
+    if (kind == DRT_PHASE_ISOTROPIC && g != 0.0f)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase: the isotropic phase function has g = 0 (got %g)", (double) g);
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    const float gg = kind == DRT_PHASE_HG ? g : 0.0f;
+    if (kind == h->phase_kind && std::memcmp(&gg, &h->base.phase_g, sizeof(float)) == 0) return DRT_OK;   // the same phase: every plan stays
+    h->phase_kind = kind; h->base.phase_g = gg;
+    // other paths: the path cache and the ray-order permutation of the last primal launch describe the old ones (scene_version is part of
+    // the job signature they are tied to), and so does the supergrid ray order an adjoint launch would reuse
+    h->scene_version++;
+    h->pcache_sig.valid = false; h->perm_valid = false; h->order_valid = false; h->order_unit = 0;
+    return DRT_OK;
+}
+
 int drt_set_emitter_constant(drt_handle h, const float radiance[3])
 {
     if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
@@ -1428,7 +1475,9 @@ int drt_render_forward(drt_handle h, const float *rays_o, const float *rays_d, u
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
     forward_params(P, t_sigma_t, t_albedo, dL_out);
     P.L_in = L_in;
-    DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd(P, h->stream) : drt::launch_trace_coop_fwd(P, h->stream));
+    if (h->phase_kind == DRT_PHASE_HG)
+        DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_hg(P, h->stream) : drt::launch_trace_coop_fwd_hg(P, h->stream));
+    else DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd(P, h->stream) : drt::launch_trace_coop_fwd(P, h->stream));
     return DRT_OK;
 }
 

@@ -13,7 +13,8 @@ using namespace coop;
 
 // TAIL: the second launch of a specialised kernel - its workgroups start from 256 paths of the tail pool each
 // (CoopTracer::wg_handoff) instead of from rays, and finish them
-template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false>
+// HG: Henyey-Greenstein phase function (CoopTracer); those kernels run without hand-off and tail pool
+template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, bool HG = false>
 __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRIMAL) trace_coop_kernel(const Params P)
 {
     if constexpr (TAIL) { if (blockIdx.x * 256u >= *P.tail_count) return; }   // (workgroup-uniform) nothing for this workgroup
@@ -35,12 +36,12 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
     if constexpr (ADJ && !SUPER) {                              // rays of similar length share a wave (ray_perm_kernel)
         if (P.ray_perm) i = (i_block & ~(uint64_t) (kPermGroup - 1)) + P.ray_perm[i_block + threadIdx.x];
     }
-    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER> tr(P);
+    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, HG> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     tr.i_block = TAIL ? 0 : i_block;
     tr.tail_load = TAIL;
-    if constexpr (SPEC) {                                       // sparse waves hand their last (adjoint: recursive, primal: main) paths to wave 0 (wg_handoff)
+    if constexpr (SPEC && !HG) {                                // sparse waves hand their last (adjoint: recursive, primal: main) paths to wave 0 (wg_handoff)
         __shared__ uint32_t wgc_lds[kWgcWords];
         static_assert(DRT_COOP_WAVES >= 1, "");
         if (threadIdx.x < 4) wgc_lds[threadIdx.x] = 0xffffffffu; // nothing published yet (made visible by the barrier below)
@@ -148,7 +149,7 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
 // Forward mode (drt_render_forward): CoopTracer<FWD> runs the adjoint's paths with dL = 1, gathering from the tangent grids where the
 // adjoint splats (the tangent grids are Params::g_sigma / g_albedo), and writes J t of its ray to L_out - once, from the ray's own lane (no hand-off, no tail pool, no atomics: the result is
 // bit-reproducible).  The global majorant's NEE walks take every step on the walk's own lane (CoopTracer::coop_rt).
-template <bool ENV, bool SPEC, bool SUPER>
+template <bool ENV, bool SPEC, bool SUPER, bool HG = false>
 __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(const Params P)
 {
     uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map (see trace_coop_kernel)
@@ -163,7 +164,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     }
 #endif
     const uint64_t i = P.ray_first + (uint64_t) b * blockDim.x + threadIdx.x;
-    CoopTracer<false, ENV, false, SPEC, false, SUPER, true> tr(P);
+    CoopTracer<false, ENV, false, SPEC, false, SUPER, true, HG> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     __shared__ uint64_t jump_lds[2 * (kJumpMax + 1)];
@@ -210,7 +211,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     if (job) { P.L_out[3 * i] = tr.tg[0]; P.L_out[3 * i + 1] = tr.tg[1]; P.L_out[3 * i + 2] = tr.tg[2]; }
 }
 
-template <bool SUPER>
+template <bool SUPER, bool HG = false>
 hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
@@ -218,29 +219,29 @@ hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
     const bool env = P.env_pix != nullptr;
     const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, 2097152u);
     if (spec) {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, HG>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, HG>), grid, block, 0, stream, P);
     } else {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER, HG>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER, HG>), grid, block, 0, stream, P);
     }
     return hipGetLastError();
 }
 
-// launch of the instantiation that fits the job
-template <bool SUPER>
+// launch of the instantiation that fits the job (HG: the Henyey-Greenstein instantiations - no tail pool, no hand-off)
+template <bool SUPER, bool HG = false>
 hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between = nullptr,
                                void *between_ctx = nullptr, bool *called = nullptr)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
     const bool env = P.env_pix != nullptr, defer = adjoint && P.rec_buf[0] != nullptr;
-#define DRT_COOP_LAUNCH(A, C, E, D) hipLaunchKernelGGL((trace_coop_kernel<A, C, E, D, false, SUPER>), grid, block, 0, stream, P)
+#define DRT_COOP_LAUNCH(A, C, E, D) hipLaunchKernelGGL((trace_coop_kernel<A, C, E, D, false, SUPER, false, HG>), grid, block, 0, stream, P)
     // the registered `volpathsimple-drt` configuration (either emitter): specialised kernels
     const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !count && !dbg(P.debug_flags, 2097152u);
 #if DRT_PHASE_PROFILE
     // experiment build: the counting launches run the specialised kernels too (their counters then hold phase cycles)
-    if (P.use_nee && P.use_drt && P.use_drt_subsampling && count && !env) {
+    if (!HG && P.use_nee && P.use_drt && P.use_drt_subsampling && count && !env) {
         if (!adjoint) { hipLaunchKernelGGL((trace_coop_kernel<false, true, false, false, true, SUPER>), grid, block, 0, stream, P); return hipGetLastError(); }
         if (defer) { hipLaunchKernelGGL((trace_coop_kernel<true, true, false, true, true, SUPER>), grid, block, 0, stream, P); return hipGetLastError(); }
     }
@@ -249,7 +250,7 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
     // (adjoint only: a tail launch exposes the longest path of the job - ~0.5 ms - which the primal pass has nothing to
     // hide behind: primal 2.58 -> 2.85 ms with it, adjoint tracer 6.19 -> 5.99 ms)
     // (capacity invariant of the pool's reservation, CoopTracer::wg_handoff: one push of <= DRT_TAIL_PUSH entries per workgroup)
-    const bool tail = !SUPER && adjoint && P.tail_pool && P.tail_count && P.tail_cap >= 256u && !dbg(P.debug_flags, 33554432u) &&
+    const bool tail = !SUPER && !HG && adjoint && P.tail_pool && P.tail_count && P.tail_cap >= 256u && !dbg(P.debug_flags, 33554432u) &&
                       (uint64_t) P.tail_cap >= (uint64_t) DRT_TAIL_PUSH * grid.x;
     Params T = P;
     if (spec && (!adjoint || defer)) {
@@ -265,14 +266,14 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
     const dim3 tgrid(tail ? P.tail_cap / 256u : 1u);
     // (pool capacity = 1/8 of the launch's rays; the tail kernel's surplus workgroups return at once)
     if (spec && !adjoint) {
-        if (env) hipLaunchKernelGGL((trace_coop_kernel<false, false, true, false, true, SUPER>), grid, block, 0, stream, M);
-        else hipLaunchKernelGGL((trace_coop_kernel<false, false, false, false, true, SUPER>), grid, block, 0, stream, M);
+        if (env) hipLaunchKernelGGL((trace_coop_kernel<false, false, true, false, true, SUPER, false, HG>), grid, block, 0, stream, M);
+        else hipLaunchKernelGGL((trace_coop_kernel<false, false, false, false, true, SUPER, false, HG>), grid, block, 0, stream, M);
         return hipGetLastError();
     }
     if (spec && defer) {
-        if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, SUPER>), grid, block, 0, stream, M);
-        else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, SUPER>), grid, block, 0, stream, M);
-        if constexpr (!SUPER) if (tail) {
+        if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, SUPER, false, HG>), grid, block, 0, stream, M);
+        else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, SUPER, false, HG>), grid, block, 0, stream, M);
+        if constexpr (!SUPER && !HG) if (tail) {
             if (between) {                                     // (e.g. the early histogram pass of the record streams)
                 hipError_t e = between(between_ctx);
                 if (e != hipSuccess) return e;

@@ -116,7 +116,11 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 // runs with dL = 1 and every splat becomes a gather - same paths, same random numbers.  Where the adjoint has summed the
 // channels before its splat (the NEE walk's a_sum, the scatter sites' gs) the channels are kept apart.  Every ray ends on
 // its own lane: no hand-off (wgc), no tail pool, no path cache, no atomics.
-template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false>
+// HG: the Henyey-Greenstein phase function with asymmetry Params::phase_g (drt_set_phase) instead of the isotropic one, at every site
+// that samples or evaluates the phase function: the scatter sites of main and recursive paths (volpathsimple.py:221-230, 630-646), the
+// NEE phase value and MIS weight (:386-391), and the escape MIS weight through last_pdf (:273-277).  The incoming direction of a
+// scatter is wi = -d of the ray that reached it.  Without hand-off or tail pool: a handed-off path would have to carry its last pdf.
+template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, bool HG = false>
 struct CoopTracer {
     const Params &P;
     float maj, inv_maj;
@@ -135,12 +139,15 @@ struct CoopTracer {
     uint32_t cnt[C_COUNT];
     float tg[3];            // FWD: this ray's tangent J t
     float fsum;             // FWD: sum over the steps of the current transmittance walk of -(1/maj) / tr * sigma_t'(p)
+    V3 hg_wi, hg_wd;        // HG: the incoming direction at the current vertex (set before each NEE / recursive path), the emitter direction
+                            // sample_emitter drew (members, not parameters: the isotropic instantiations keep the signatures they compile from)
 
     __device__ __forceinline__ CoopTracer(const Params &p) : P(p)
     {
         maj = p.majorant[0]; inv_maj = p.majorant[1];
         ray_index = 0; rec = nullptr; slots = nullptr; occ = nullptr; jump = nullptr; pc = nullptr; work = 0; iters = 0;
         mocc = nullptr; wgc = nullptr; i_block = 0; tail_load = false;
+        if constexpr (HG) { hg_wi = v3(0, 0, 1); hg_wd = v3(0, 0, 1); }
 #if DRT_PHASE_PROFILE
         ph_t = __builtin_readcyclecounter();
 #endif
@@ -453,10 +460,11 @@ struct CoopTracer {
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) out[k] = val[k] * T;
+        if constexpr (HG) hg_wd = wd;
         return pdf;
     }
 
-    // sample_emitter_for_nee (volpathsimple.py:380-403)
+    // sample_emitter_for_nee (volpathsimple.py:380-403); HG: hg_wi is the incoming direction at p
     template <bool ADJ>
     __device__ __forceinline__ void sample_emitter_for_nee(bool job, V3 p, Pcg32 &S, const float beta[3], const float *dL, float contrib[3],
                                            int cmode = 0, uint4 *ce = nullptr)
@@ -467,9 +475,16 @@ struct CoopTracer {
         constexpr bool kFwd = ADJ && FWD;
         if constexpr (kFwd) fsum = 0.0f;
         float ds_pdf = sample_emitter<kFwd>(job, p, S, nullptr, emitted, cmode, ce);   // :385
-        float w = mis_weight(ds_pdf, kInvFourPi);                               // :391
+        if constexpr (HG) {                                                     // phase_val = phase_pdf = eval(wd, wi) (:386-388)
+            const float pv = hg_eval(P.phase_g, hg_wd, hg_wi);
+            float w = mis_weight(ds_pdf, pv);                                   // :391
 #pragma unroll
-        for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * kInvFourPi) * w) * emitted[k] : 0.0f;
+            for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * pv) * w) * emitted[k] : 0.0f;
+        } else {
+            float w = mis_weight(ds_pdf, kInvFourPi);                           // :391
+#pragma unroll
+            for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * kInvFourPi) * w) * emitted[k] : 0.0f;
+        }
         if constexpr (kFwd) {                                                   // :393-401 transposed: a_sum = sum_k dL_k contrib_k, kept apart
             if (job) {
 #pragma unroll
@@ -509,6 +524,7 @@ struct CoopTracer {
 
     // sample_recursive (volpathsimple.py:610-655)
     // `tail`: hand-off mode - the path's end (Li, gradient splat) happens inside sample(), on whichever lane it ends
+    // HG: hg_wi is the incoming direction at p, -sub_ray.d (volpathsimple.py:566, 630)
     __device__ __forceinline__ void sample_recursive(bool job, Pcg32 &A, V3 p, int depth, float Li[3], Tail *tail = nullptr)
     {
         Li[0] = Li[1] = Li[2] = 0.0f;
@@ -530,7 +546,8 @@ struct CoopTracer {
         if (job) {
             (void) A.next_1d();                                                 // :632
             float ux = A.next_1d(), uy = A.next_1d();
-            rr.d = square_to_uniform_sphere(ux, uy);
+            if constexpr (HG) rr.d = hg_sample(P.phase_g, ux, uy, hg_wi, ps.last_pdf);
+            else rr.d = square_to_uniform_sphere(ux, uy);
             Hit sn = box_hit(P, p, rr.d);                                       // :637
             rr.maxt = sn.valid ? sn.t : kLargest;                               // :639-640
             ps.si = sn;
@@ -562,7 +579,7 @@ struct CoopTracer {
             count(C_DRT);
         }
         float Li[3];
-        if constexpr (SPEC && !FWD) {
+        if constexpr (SPEC && !FWD && !HG) {
             if (wgc) {                                                          // (workgroup-uniform: set by the kernel)
                 // hand-off mode: everything the final splat needs is computed now and travels with the recursive path
                 Tail tl;
@@ -576,6 +593,7 @@ struct CoopTracer {
                 return;
             }
         }
+        if constexpr (HG) hg_wi = v3(-sub.d.x, -sub.d.y, -sub.d.z);
         sample_recursive(found, A, p, depth, Li);                               // :565-568
         if (found) {
             float w = P.use_drt_mis ? 1.0f / (1.0f + sig * sig) : 1.0f;         // :571-575
@@ -832,7 +850,7 @@ struct CoopTracer {
         int it = 0;                                                             // bounce-loop iterations this ray has run
         // recursive paths of the specialised adjoint kernels: sparse waves hand their last paths to wave 0 (wg_handoff)
         // ... and so do the main paths of the specialised primal kernels (their radiance is then written by wg_handoff)
-        constexpr bool kWgc = !ADJ && SPEC && !FWD;
+        constexpr bool kWgc = !ADJ && SPEC && !FWD && !HG;
         bool wgc_on = false;
         Tail tl;
         uint32_t taken = 0;
@@ -948,6 +966,7 @@ struct CoopTracer {
             if (use_nee()) {
                 float nee[3];
                 phase(RECURSIVE ? C_SC : C_TR);
+                if constexpr (HG) hg_wi = v3(-ray.d.x, -ray.d.y, -ray.d.z);
                 sample_emitter_for_nee<ADJ>(nee_job, mei.p, S, beta, dL, nee, nee_job ? cmode : 0, ce ? ce + 1 : nullptr);
                 phase(RECURSIVE ? C_RT_ADJ : C_RT);
                 if (nee_job) {
@@ -960,8 +979,11 @@ struct CoopTracer {
                 if (did_scatter) {                                              // :221-230
                     (void) S.next_1d();
                     float ux = S.next_1d(), uy = S.next_1d();
-                    ray.o = mei.p; ray.d = square_to_uniform_sphere(ux, uy); ray.maxt = kLargest;
-                    last_pdf = kInvFourPi;
+                    if constexpr (HG) { ray.o = mei.p; ray.d = hg_sample(P.phase_g, ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf); ray.maxt = kLargest; }
+                    else {
+                        ray.o = mei.p; ray.d = square_to_uniform_sphere(ux, uy); ray.maxt = kLargest;
+                        last_pdf = kInvFourPi;
+                    }
                 }
                 si = box_hit(P, ray.o, ray.d);                                  // :233-235
                 ray.maxt = isfinite(si.t) ? si.t : kLargest;

@@ -183,6 +183,53 @@ __device__ __forceinline__ V3 square_to_uniform_sphere(float ux, float uy)
     return V3{ r * c, r * s, z };
 }
 
+// ---------------------------------------------------------------------------
+// Henyey-Greenstein phase function (Mitsuba 3, src/phase/hg.cpp), as published:
+//   eval(wo, wi) = (1 - g^2) / (4 pi (1 + g^2 + 2 g mu)^(3/2)),  mu = dot(wo, wi),  wi = -d_in (g > 0 scatters forward)
+//   sample(u):     sqr_term  = (1 - g^2) / (1 - g + 2 g u.x)
+//                  cos_theta = (1 + g^2 - sqr_term^2) / (2 g)             (|g| < 2^-24: 1 - 2 u.x, the uniform fallback)
+//                  sin_theta = safe_sqrt(1 - cos_theta^2), phi = 2 pi u.y
+//                  wo = Frame3f(wi).to_world(sin_theta cos phi, sin theta sin phi, -cos_theta), pdf = eval_hg(-cos_theta)
+// Frame3f(n): tangents from coordinate_system (Duff et al. 2017, "Building an orthonormal basis, revisited").
+// "Perfect importance sampling": the sampled weight is 1 and pdf = eval.  The phase site consumes the same draws as the
+// isotropic one (next_1d unused, then next_2d), so the sampler streams of a path do not depend on the phase function.
+// ---------------------------------------------------------------------------
+constexpr float kHgEps = 5.9604644775390625e-8f;                          // dr::Epsilon<float> = 2^-24
+
+__device__ __forceinline__ float hg_eval_cos(float g, float mu)
+{
+    const float temp = (1.0f + g * g) + (2.0f * g) * mu;
+    return (kInvFourPi * (1.0f - g * g)) / (temp * sqrtf(temp));
+}
+
+__device__ __forceinline__ float hg_eval(float g, V3 wo, V3 wi)
+{
+    return hg_eval_cos(g, (wo.x * wi.x + wo.y * wi.y) + wo.z * wi.z);
+}
+
+__device__ __forceinline__ V3 hg_sample(float g, float ux, float uy, V3 wi, float &pdf)
+{
+    float cos_t;
+    if (fabsf(g) < kHgEps) cos_t = 1.0f - 2.0f * ux;
+    else {
+        const float sqr_term = (1.0f - g * g) / ((1.0f - g) + (2.0f * g) * ux);
+        cos_t = ((1.0f + g * g) - sqr_term * sqr_term) / (2.0f * g);
+    }
+    const float sin_t = sqrtf(fmaxf(0.0f, 1.0f - cos_t * cos_t));
+    float sp, cp;
+    drt_sincos_2pi(uy, sp, cp);
+    const float lx = sin_t * cp, ly = sin_t * sp, lz = -cos_t;
+    // coordinate_system(wi): sign = dr::sign(n.z) (n.z >= 0: +1), a = -1 / (sign + n.z), b = n.x n.y a; dr::mulsign(v, n.z) flips v by
+    // the sign BIT of n.z, dr::mulsign_neg by its complement
+    const float sgn = wi.z >= 0.0f ? 1.0f : -1.0f, msg = copysignf(1.0f, wi.z);
+    const float a = -1.0f / (sgn + wi.z);
+    const float b = (wi.x * wi.y) * a;
+    const V3 s = v3(msg * ((wi.x * wi.x) * a) + 1.0f, msg * b, -msg * wi.x);
+    const V3 t = v3(b, fmaf(wi.y, wi.y * a, sgn), -wi.y);
+    pdf = hg_eval_cos(g, -cos_t);
+    return v3((s.x * lx + t.x * ly) + wi.x * lz, (s.y * lx + t.y * ly) + wi.y * lz, (s.z * lx + t.z * ly) + wi.z * lz);
+}
+
 // atan2 with a specified instruction sequence (Cephes atanf polynomial on min/max in [0,1]);
 // atan2(0,0) = 0.  Same sequence as the oracle's, so envmap lookups are bit-identical.
 __device__ __forceinline__ float drt_atan2f(float y, float x)
@@ -225,6 +272,10 @@ struct Params {
     // colour grid (albedo = emission, scene_config.py:109-110) for the fused nerf + volpathsimple pass (eval4), or nullptr
     const float4 *grid4;
     int g4_nbx;                // lines per grid row = ceil(rx / 3)
+    // Henyey-Greenstein asymmetry g (drt_set_phase): read only by the HG instantiations of CoopTracer; 0 for an isotropic handle.  It
+    // fills the four bytes of padding in front of `majorant`: no field moves and the block keeps its size (the kernarg offsets of every
+    // kernel stay as they are).
+    float phase_g;
     const float *majorant;     // device: [0] = scale*max(sigma_t), [1] = 1/[0] (0 if [0]==0)
     const float *mgrid;        // majorant supergrid, one majorant per cell (x fastest), or nullptr
     const uint32_t *mocc;      // bit c = supergrid cell c has a non-zero majorant (the DDA skips the others without a load)
@@ -339,6 +390,7 @@ struct Params {
     // (At the end of the block, as the colour fields: moving the fields before it changed the queued tracer's code and broke its tail launch.)
     const float *dL_pix;
 };
+static_assert(offsetof(Params, majorant) == offsetof(Params, g4_nbx) + 8, "Params::phase_g must stay in the padding in front of majorant");
 
 // ---------------------------------------------------------------------------
 // envmap emitter [M3-ext] (volpathsimple.py:273,284,419; include/drt_hip.h: drt_set_emitter_envmap)

@@ -830,6 +830,12 @@ __global__ void __launch_bounds__(256) debug_eval_kernel(const Params P, int op,
             else { coop::CoopTracer<false, false, false> tr(P); tr.occ = P.occ; ok = tr.sample_interaction_drt(r, A, t, W); }
             o[0] = ok ? 1.0f : 0.0f; o[1] = t; o[2] = W; o[3] = r.maxt;
         } break;
+        case 15: {                                      // Henyey-Greenstein sample (u1, u2, wi, g) -> wo, pdf
+            float pdf;
+            V3 d = hg_sample(a[5], a[0], a[1], v3(a[2], a[3], a[4]), pdf);
+            o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = pdf;
+        } break;
+        case 16: o[0] = hg_eval(P.phase_g, v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5])); break;   // ... eval (wo, wi), the handle's g
         case 9: if (P.mgrid) { o[0] = P.mgrid[__float_as_uint(a[0])]; } break;
         case 8: o[0] = mis_weight(a[0], a[1]); o[1] = a[0] / a[1]; o[2] = sqrtf(a[0]); o[3] = fmaf(a[0], a[1], a[2]); break;
         default: break;

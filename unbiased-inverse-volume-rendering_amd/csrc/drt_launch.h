@@ -62,6 +62,16 @@ hipError_t launch_trace_coop_super_fwd(const Params &P, hipStream_t stream);
 hipError_t launch_trace_own_fwd(const Params &P, hipStream_t stream);
 hipError_t launch_nerf_fwd(const Params &P, hipStream_t stream);
 hipError_t launch_nerf_own_fwd(const Params &P, hipStream_t stream);
+// Henyey-Greenstein phase function (drt_set_phase; Params::phase_g): CoopTracer<HG> for every kind of majorant, both AD modes and forward
+// mode (drt_coop_hg.hip, drt_coop_super_hg.hip; drt_own_hg.hip for colour grids on their own lattice).  No tail pool, no hand-off.
+hipError_t launch_trace_coop_hg(const Params &P, bool adjoint, bool count, hipStream_t stream);
+hipError_t launch_trace_coop_super_hg(const Params &P, bool adjoint, bool count, hipStream_t stream);
+hipError_t launch_trace_own_hg(const Params &P, bool adjoint, bool count, hipStream_t stream);
+hipError_t launch_trace_coop_fwd_hg(const Params &P, hipStream_t stream);
+hipError_t launch_trace_coop_super_fwd_hg(const Params &P, hipStream_t stream);
+hipError_t launch_trace_own_fwd_hg(const Params &P, hipStream_t stream);
+// ... and the queued supergrid tracer's (drt_sq_hg.hip): as launch_trace_sq, without tail launch (Params::tail_pool / tail_mode must be unset)
+hipError_t launch_trace_sq_hg(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
 hipError_t launch_ray_perm(const uint8_t *iters, uint64_t n_rays, uint16_t *perm, uint32_t *block_cost, hipStream_t stream);
 hipError_t launch_block_order(const uint32_t *cost, uint32_t n_blocks, uint32_t *order, bool heavy_first, hipStream_t stream);
 hipError_t launch_untile(const Params &P, hipStream_t stream);

@@ -129,6 +129,7 @@ constexpr int kSqTailQuads = 20;   // uint4 per pool entry: 7 (the LDS record) +
 // path)?  32 buckets of 0.25 ms of the workgroup's clock x {paths, sum of ages (1.28 us), sum of iterations, paths older than half
 // of the launch so far, largest age}; read with drt_sq_debug_read (tools/finish_age_profile.py)
 __device__ unsigned long long g_sq_dbg[160];
+#ifndef DRT_SQ_HG_UNIT
 extern "C" int drt_sq_debug_read(unsigned long long *out, int n, int reset)
 {
     if (n > 160) n = 160;
@@ -136,6 +137,7 @@ extern "C" int drt_sq_debug_read(unsigned long long *out, int n, int reset)
     if (e == hipSuccess && reset) { static unsigned long long z[160]; e = hipMemcpyToSymbol(HIP_SYMBOL(g_sq_dbg), z, sizeof(z)); }
     return (int) e;
 }
+#endif
 #endif
 
 namespace drt {
@@ -269,9 +271,15 @@ __device__ __forceinline__ void sq_push_all(unsigned long long *ctl, uint16_t *q
 // ROUNDS (primal kernels of launches in index order over a THIN medium, Params::sq_rounds): the regeneration block hands the records whose ray was over
 // at once their next ray in the same block.  An instantiation of its own: compiled into the others the loop cost the headline's primal launch 0.15 ms
 // without running once (profiles/r06_sq_instruction_budget.txt)
-template <bool ADJ, bool COUNT, bool ENV, bool MG, bool QUAD = false, bool TAILM = false, bool ROUNDS = false>
+// HG (drt_sq_hg.hip; never with TAILM or ROUNDS): the Henyey-Greenstein phase function with asymmetry Params::phase_g (drt_set_phase) at the NEE
+// block, phase sampling and the escape MIS weight.  A record then owns one more uint4 of global memory, behind part a / part b of its workgroup:
+// {wi, last pdf} - the incoming direction of the current vertex (the emitter-direction block stores it before it replaces rd: with use_nee every
+// phase sampling follows that block at the same vertex) and the pdf of the last phase sampling (read at the escape only by primal and recursive
+// paths, which are never suspended: the quadratic detour restores the main path's rd, and its own emitter-direction block stores it again).
+template <bool ADJ, bool COUNT, bool ENV, bool MG, bool QUAD = false, bool TAILM = false, bool ROUNDS = false, bool HG = false>
 __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P)
 {
+    static_assert(!HG || (!TAILM && !ROUNDS), "the HG kernels have no tail launch and no ROUNDS variant");
     constexpr int NWV = DRT_SQ_THREADS / 64;
     constexpr int R4 = 7;                                                    // uint4 per ray record in LDS
     static_assert(ADJ || !QUAD, "the primal pass of the quadratic estimator is the ordinary one");
@@ -282,6 +290,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
     constexpr bool SOLO = TAILM && !MG;
     constexpr int NB = QUAD ? 9 : 6;                                         // uint4 of part b of the global record (adjoint)
     constexpr int NC = ADJ ? 3 + NB : 3;                                     // uint4 per ray in global memory (Params::sq_cold)
+    constexpr int NCW = NC + (HG ? 1 : 0);                                   // ... HG: + {wi, last pdf}
     // LDS record: [0] {tn.x, tn.y, tn.z, cell} [1] {td.x, td.y, td.z, steps left (9 bits per axis) + direction signs}
     // [2] {tau, tmax, t, acc} - the flight (a finished flight leaves its cell's majorant, 0: left the segment, in [0].x) -
     // [3] {rd, wmax} [4] {wo, wt} [5] {G.state, G.inc}: the generator the current walk draws from (the alt sampler in the main
@@ -379,8 +388,10 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
     const int lin_y = gx, lin_z = gx * gy;
 
     uint32_t *rec = recst + wave * 8;                                          // record-stream state of this wave (emit_record)
-    uint4 *cold_a = (uint4 *) P.sq_cold + (size_t) blockIdx.x * NC * NRAY;    // [NRAY][3] uint4 of this workgroup
+    uint4 *cold_a = (uint4 *) P.sq_cold + (size_t) blockIdx.x * NCW * NRAY;   // [NRAY][3] uint4 of this workgroup
     uint4 *cold_b = cold_a + 3 * NRAY;                                        // [NRAY][6] (adjoint; QUAD: [9], the last three: the suspended main path)
+    float4 *cold_h = (float4 *) (cold_a + NC * NRAY);                         // HG: [NRAY] {wi, last pdf}
+    (void) cold_h;
     const uint32_t xcc = sq_xcc_id();
     // (with a ray order the queue positions cover whole units: the last unit may reach past the launch's last ray)
     const uint64_t span = P.order ? (uint64_t) P.order_units * P.order_unit : P.n_rays - P.ray_first;
@@ -993,11 +1004,22 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                 // (recomputed from the direction; behind the NEE block of the same pass the density is the one it just evaluated)
                 const float ds_pdf = (ENV && behind_nee && nee_pdf_ok) ? emitter_sample_value_with_pdf<ENV>(P, rd, nee_pdf, val)
                                                                        : emitter_sample_value<ENV>(P, rd, val);
+                if constexpr (HG) {                                         // phase_val = phase_pdf = eval(rd, wi) (:386-388)
+                    const float4 hw = cold_h[id];
+                    const float pv = hg_eval(P.phase_g, rd, v3(hw.x, hw.y, hw.z));
+                    const float w = mis_weight(ds_pdf, pv);                 // :391
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        contrib[k] = ((beta[k] * pv) * w) * (val[k] * wt);
+                        result[k] = (ADJ && !rec_mode) ? result[k] - contrib[k] : result[k] + contrib[k];   // :211-214
+                    }
+                } else {
                 const float w = mis_weight(ds_pdf, kInvFourPi);             // :391
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     contrib[k] = ((beta[k] * kInvFourPi) * w) * (val[k] * wt);
                     result[k] = (ADJ && !rec_mode) ? result[k] - contrib[k] : result[k] + contrib[k];   // :211-214
+                }
                 }
                 ph = SP_PHASE;
                 if constexpr (ADJ) {
@@ -1067,6 +1089,12 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                     ++pc_it;                                                    // next bounce-loop iteration (path cache index)
                     (void) S.next_1d();
                     float ux = S.next_1d(), uy = S.next_1d();
+                    if constexpr (HG) {                                         // wi: stored by the emitter-direction block, or -rd without NEE
+                        float4 hw = cold_h[id];
+                        const V3 wi = P.use_nee ? v3(hw.x, hw.y, hw.z) : v3(-rd.x, -rd.y, -rd.z);
+                        rd = hg_sample(P.phase_g, ux, uy, wi, hw.w);
+                        cold_h[id] = hw;
+                    } else
                     rd = square_to_uniform_sphere(ux, uy);                      // (ro is the scatter point already)
                     scat_once = true;
                     Hit h = box_hit(P, ro, rd);                                 // :233-235
@@ -1202,6 +1230,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                 SQ_BLK(5, ph == SP_NEE);
                 if (ph == SP_NEE) {
                     if (ADJ && !rec_mode) Cst = S.state;                        // :383
+                    if constexpr (HG) cold_h[id] = make_float4(-rd.x, -rd.y, -rd.z, cold_h[id].w);   // wi of this vertex
                     float ux = S.next_1d(), uy = S.next_1d();                   // :418
                     rd = emitter_sample_dir<ENV>(P, ux, uy);
                     Hit h = box_hit(P, ro, rd);                                 // :427-428
@@ -1230,7 +1259,8 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                             float w = 1.0f, Le[3];
                             // (radiance and density of the direction from the same taps of the map: emitter_eval_pdf)
                             const float e_pdf = emitter_eval_pdf<ENV>(P, rd, Le);
-                            if (P.use_nee) w = mis_weight(scat_once ? kInvFourPi : 1.0f, has_scattered ? e_pdf : 0.0f);
+                            if constexpr (HG) { if (P.use_nee) w = mis_weight(scat_once ? cold_h[id].w : 1.0f, has_scattered ? e_pdf : 0.0f); }
+                            else if (P.use_nee) w = mis_weight(scat_once ? kInvFourPi : 1.0f, has_scattered ? e_pdf : 0.0f);
 #pragma unroll
                             for (int k = 0; k < 3; ++k) result[k] += (beta[k] * w) * Le[k];
                         }
@@ -1581,6 +1611,7 @@ static uint32_t sq_rays_for(const Params &P, size_t *bytes, bool *global_majoran
 }
 
 // the tail launch runs its records to their ends without queue hops (SOLO) unless the majorants are read from L2 (MG)
+#ifndef DRT_SQ_HG_UNIT
 bool sq_tail_solo(const Params &P)
 {
     bool mg = false;
@@ -1590,16 +1621,22 @@ bool sq_tail_solo(const Params &P)
 uint32_t sq_tail_push() { return DRT_SQ_TAIL_PUSH + 64; }   // (the hand-over's count of live records may be low by one batch)
 size_t sq_tail_entry_quads() { return kSqTailQuads; }
 
-size_t sq_cold_bytes(int n_cus) { return (size_t) n_cus * 12 * DRT_SQ_MAX_RAYS * sizeof(uint4); }   // (3 + 9: the quadratic estimator's adjoint records)
+// (3 + 9: the quadratic estimator's adjoint records; + 1: {wi, last pdf} of the HG kernels)
+size_t sq_cold_bytes(int n_cus) { return (size_t) n_cus * 13 * DRT_SQ_MAX_RAYS * sizeof(uint4); }
 
 bool sq_supported(const Params &P)
 {
     return P.mgrid && P.gx <= 511 && P.gy <= 511 && P.gz <= 511 && P.max_depth <= 1000 && sq_rays_for(P, nullptr) != 0;
 }
 
-hipError_t launch_trace_sq(const Params &Pin, bool adjoint, bool count, int n_cus, hipStream_t stream)
+#endif
+
+// HG: the Henyey-Greenstein instantiations (drt_sq_hg.hip): no tail launch, no ROUNDS kernels
+template <bool HG>
+static hipError_t launch_trace_sq_t(const Params &Pin, bool adjoint, bool count, int n_cus, hipStream_t stream)
 {
     if (Pin.n_rays <= Pin.ray_first) return hipSuccess;
+    if (HG && (Pin.tail_mode || Pin.tail_pool)) return hipErrorInvalidValue;
     size_t lds = 0;
     bool mg = false;
     const uint32_t nray = sq_rays_for(Pin, &lds, &mg);
@@ -1626,7 +1663,7 @@ hipError_t launch_trace_sq(const Params &Pin, bool adjoint, bool count, int n_cu
     hipError_t e = hipSuccess;
     const bool quad = adjoint && P.use_drt && !P.use_drt_subsampling;           // quadratic DRT: the QUAD instantiations of the adjoint kernels
     const bool tailm = P.tail_mode != 0u;
-    const bool rounds = DRT_SQ_REGEN_FINISH >= 2 && P.sq_rounds != 0u && !P.order;
+    const bool rounds = !HG && DRT_SQ_REGEN_FINISH >= 2 && P.sq_rounds != 0u && !P.order;
 #define DRT_SQ_LAUNCH(A, C, E) do { if (tailm) DRT_SQ_LAUNCH_Q(A, C, E, true); else DRT_SQ_LAUNCH_Q(A, C, E, false); } while (0)
 #define DRT_SQ_LAUNCH_Q(A, C, E, T) do { if (A && quad) { if (mg) DRT_SQ_LAUNCH_(A, C, E, true, A, T); else DRT_SQ_LAUNCH_(A, C, E, false, A, T); } \
                                     else { if (mg) DRT_SQ_LAUNCH_(A, C, E, true, false, T); else DRT_SQ_LAUNCH_(A, C, E, false, false, T); } } while (0)
@@ -1634,7 +1671,7 @@ hipError_t launch_trace_sq(const Params &Pin, bool adjoint, bool count, int n_cu
                                               else DRT_SQ_LAUNCH_R(A, C, E, M, Q, T, false); } while (0)
 #define DRT_SQ_LAUNCH_R(A, C, E, M, Q, T, R)                                                                         \
     do {                                                                                                          \
-        auto kern = trace_sq_kernel<A, C, E, M, Q, T, R>;                                                         \
+        auto kern = trace_sq_kernel<A, C, E, M, Q, (T) && !HG, (R) && !HG, HG>;                                   \
         static std::atomic<size_t> lds_set[64];                                                                        \
         int dev_ = 0;                                                                                             \
         if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) dev_ = 63;                               \
@@ -1662,5 +1699,17 @@ hipError_t launch_trace_sq(const Params &Pin, bool adjoint, bool count, int n_cu
 #undef DRT_SQ_LAUNCH_R
     return hipGetLastError();
 }
+
+#ifndef DRT_SQ_HG_UNIT
+hipError_t launch_trace_sq(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream)
+{
+    return launch_trace_sq_t<false>(P, adjoint, count, n_cus, stream);
+}
+#else
+hipError_t launch_trace_sq_hg(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream)
+{
+    return launch_trace_sq_t<true>(P, adjoint, count, n_cus, stream);
+}
+#endif
 
 }  // namespace drt

@@ -22,7 +22,8 @@ def _scene_with(scene: Scene, values: Dict[str, torch.Tensor]) -> Scene:
     m = scene.medium
     medium = GridMedium(sigma_t=values.get(SIGMA_T_KEY, m.sigma_t), albedo=values.get(ALBEDO_KEY, m.albedo),
                         bbox_min=m.bbox_min, bbox_max=m.bbox_max, scale=m.scale,
-                        majorant_resolution_factor=m.majorant_resolution_factor, emission=values.get(EMISSION_KEY, m.emission))
+                        majorant_resolution_factor=m.majorant_resolution_factor, emission=values.get(EMISSION_KEY, m.emission),
+                        phase=m.phase)
     return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
 
 

@@ -20,7 +20,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from ._native import native
-from .scene import ALBEDO_KEY, EMISSION_KEY, SIGMA_T_KEY, PerspectiveSensor, Scene
+from .scene import ALBEDO_KEY, EMISSION_KEY, SIGMA_T_KEY, PerspectiveSensor, Scene, _check_phase
 
 
 class ADMode(IntEnum):
@@ -220,6 +220,13 @@ class _DeviceIntegrator:
         key = (st.data_ptr(), st._version) + al_key + (tuple(st.shape), cshape,
                tuple(m.bbox_min), tuple(m.bbox_max), float(m.scale), int(m.majorant_resolution_factor))
         self._bind_emitter(h, idx, scene.emitter, dev)
+        # the phase function (drt_set_phase): part of what the handle is bound to, kept apart from the grids' key because
+        # changing it rebuilds nothing - the library only drops the plans it made from the old paths
+        ph = _check_phase(m.phase)
+        pkey = (int(ph.kind), float(ph.g))
+        if self._bound_phase.get(idx) != pkey:
+            h.set_phase(*pkey)
+            self._bound_phase[idx] = pkey
         bound = self._bound.get(idx)
         if bound is None or bound[0] != key:
             z, y, x = st.shape[:3]
@@ -316,6 +323,7 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         self._handles: Dict[int, object] = {}
         self._bound: Dict[int, tuple] = {}
         self._bound_emitter: Dict[int, tuple] = {}
+        self._bound_phase: Dict[int, tuple] = {}
 
     # -- reference surface ---------------------------------------------------
     def aovs(self):
@@ -430,6 +438,7 @@ class NeRFIntegrator(_DeviceIntegrator):
         self._handles: Dict[int, object] = {}
         self._bound: Dict[int, tuple] = {}
         self._bound_emitter: Dict[int, tuple] = {}
+        self._bound_phase: Dict[int, tuple] = {}
 
     def aovs(self):
         return []

@@ -354,7 +354,7 @@ def _scene_with(scene: Scene, params: Dict[str, torch.Tensor], factor: int) -> S
     m = scene.medium
     medium = GridMedium(sigma_t=params.get(SIGMA_T_KEY, m.sigma_t), albedo=params.get(ALBEDO_KEY, m.albedo),
                         bbox_min=m.bbox_min, bbox_max=m.bbox_max, scale=m.scale, majorant_resolution_factor=factor,
-                        emission=params.get(EMISSION_KEY, m.emission))
+                        emission=params.get(EMISSION_KEY, m.emission), phase=m.phase)
     return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
 
 

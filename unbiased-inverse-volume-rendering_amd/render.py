@@ -67,7 +67,7 @@ def _with_params(scene: Scene, keys, tensors) -> Scene:
     vals.update(dict(zip(keys, tensors)))
     medium = GridMedium(sigma_t=vals[SIGMA_T_KEY], albedo=vals[ALBEDO_KEY], bbox_min=m.bbox_min, bbox_max=m.bbox_max,
                         scale=m.scale, majorant_resolution_factor=m.majorant_resolution_factor,
-                        emission=vals[EMISSION_KEY])
+                        emission=vals[EMISSION_KEY], phase=m.phase)
     return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
 
 

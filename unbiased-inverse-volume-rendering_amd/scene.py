@@ -11,6 +11,7 @@ and are addressed by the reference's keys (`medium1.sigma_t.data`,
 from __future__ import annotations
 
 import math
+import warnings
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
@@ -91,10 +92,48 @@ class EnvmapEmitter:
         return ((c, 0.0, s), (0.0, 1.0, 0.0), (-s, 0.0, c))
 
 
+@dataclass(frozen=True)
+class IsotropicPhase:
+    """Mitsuba's `isotropic` phase function, the default of every medium: p = 1 / (4 pi)."""
+    kind = 0        # DRT_PHASE_ISOTROPIC (include/drt_hip.h)
+
+    @property
+    def g(self) -> float:
+        return 0.0
+
+
+@dataclass(frozen=True)
+class HGPhase:
+    """Mitsuba's `hg` phase function (src/phase/hg.cpp): Henyey-Greenstein with asymmetry `g`, finite with |g| < 1;
+    g > 0 scatters forward.  `<phase type="hg"><float name="g" value="0.8"/></phase>`, or `<medium>.phase_function.g` in
+    `mi.traverse`.  HG with g = 0 is its own warp, not the isotropic one (as in Mitsuba); no gradient with respect to g."""
+    g: float = 0.8
+    kind = 1        # DRT_PHASE_HG
+
+    def __post_init__(self):
+        if isinstance(self.g, bool) or not isinstance(self.g, (int, float, np.floating, np.integer)):
+            raise TypeError(f"HGPhase.g must be a real number, got {type(self.g).__name__}")
+        g = float(self.g)
+        if not math.isfinite(g) or not abs(float(np.float32(g))) < 1.0:      # (the kernels take g as float32)
+            raise ValueError(f"HGPhase.g must be finite with |g| < 1 (in float32 too), got {g}")
+        if 0.0 < abs(g) < 1e-3:
+            # Mitsuba's inverted CDF cancels in float32 there: |cos_theta| can exceed 1 and sampled directions are not unit vectors
+            warnings.warn(f"HGPhase(g={g}): for 0 < |g| < 1e-3 the published sampling formula loses its precision in float32 (directions off "
+                          "unit length); use IsotropicPhase() or HGPhase(0.0) for an isotropic medium", RuntimeWarning, stacklevel=2)
+        object.__setattr__(self, "g", g)
+
+
+def _check_phase(phase):
+    if not isinstance(phase, (IsotropicPhase, HGPhase)):
+        raise TypeError(f"GridMedium.phase must be IsotropicPhase() or HGPhase(g), got {type(phase).__name__}")
+    return phase
+
+
 @dataclass
 class GridMedium:
-    """`heterogeneous` medium with `gridvolume` sigma_t / albedo and an isotropic
-    phase function, bounded by an axis-aligned box (tests/test_integrators.py:79-111).
+    """`heterogeneous` medium with `gridvolume` sigma_t / albedo and a phase function
+    (`IsotropicPhase()`, the default, or `HGPhase(g)`), bounded by an axis-aligned box
+    (tests/test_integrators.py:79-111).
 
     sigma_t : (Z, Y, X, 1) float32, albedo : (Z, Y, X, 3) float32 - numpy arrays or
     torch tensors (device tensors for the HIP path).
@@ -109,6 +148,11 @@ class GridMedium:
     majorant_resolution_factor: int = 0
     # (Z, Y, X, 3) emission grid, only read by the `nerf` integrator (medium.get_emission, nerf.py:164)
     emission: object = None
+    # medium.phase_function() (volpathsimple.py:202-231, 380-392, 616-646); the `nerf` integrator has none
+    phase: object = field(default_factory=IsotropicPhase)
+
+    def __post_init__(self):
+        _check_phase(self.phase)
 
     @property
     def resolution(self):
@@ -175,7 +219,7 @@ def scene_to(scene: Scene, device) -> Scene:
 
     medium = GridMedium(sigma_t=conv(m.sigma_t), albedo=conv(m.albedo), bbox_min=tuple(m.bbox_min),
                         bbox_max=tuple(m.bbox_max), scale=m.scale,
-                        majorant_resolution_factor=m.majorant_resolution_factor, emission=conv(m.emission))
+                        majorant_resolution_factor=m.majorant_resolution_factor, emission=conv(m.emission), phase=m.phase)
     emitter = scene.emitter
     if isinstance(emitter, EnvmapEmitter):
         emitter = EnvmapEmitter(pixels=conv(emitter.pixels), scale=emitter.scale, to_world=emitter.to_world)

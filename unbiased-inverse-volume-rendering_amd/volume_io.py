@@ -51,7 +51,7 @@ def read_vol(path: str):
 
 
 def medium_from_vol(medium_filename: str, albedo_filename=None, emission_filename=None, albedo_value: float = 0.6,
-                    scale: float = 1.0, majorant_resolution_factor: int = 0, device=None):
+                    scale: float = 1.0, majorant_resolution_factor: int = 0, device=None, phase=None):
     """A `GridMedium` from `.vol` files - the `medium_filename` / `albedo_filename` / `emission_filename` variables of
     the reference's scene descriptions (python/scene_config.py:84-141), e.g. the checkpoints of a previous run for a
     warm start (`janga-smoke-from-nerf`: `<output>/<run>/nerf/params/final-medium1_sigma_t.vol`, :123-141).
@@ -60,9 +60,9 @@ def medium_from_vol(medium_filename: str, albedo_filename=None, emission_filenam
     `albedo_value` on sigma_t's lattice.  An albedo / emission file keeps ITS OWN resolution (the reference pairs a
     264x136x136 density with 256x128x128 albedo / emission grids, :108-110; Mitsuba interpolates every grid on its own
     lattice): the integrators then run the own-lattice kernels (drt_set_colour_resolution, csrc/drt_own.hip).  Albedo and
-    emission files must share one lattice."""
+    emission files must share one lattice.  `phase`: the medium's phase function (default IsotropicPhase())."""
     import torch
-    from .scene import GridMedium
+    from .scene import GridMedium, IsotropicPhase
     sig, bmin, bmax = read_vol(medium_filename)
     if sig.shape[3] != 1:
         raise ValueError(f"{medium_filename}: expected a 1-channel density grid, found {sig.shape[3]} channels")
@@ -91,4 +91,4 @@ def medium_from_vol(medium_filename: str, albedo_filename=None, emission_filenam
     to = (lambda t: t.to(device)) if device is not None else (lambda t: t)
     return GridMedium(sigma_t=to(torch.from_numpy(sig.copy())), albedo=to(albedo), bbox_min=bmin, bbox_max=bmax, scale=scale,
                       majorant_resolution_factor=majorant_resolution_factor,
-                      emission=to(emission) if emission is not None else None)
+                      emission=to(emission) if emission is not None else None, phase=IsotropicPhase() if phase is None else phase)
