@@ -107,7 +107,8 @@ int drt_set_colour_resolution(drt_handle h, const int32_t res[3]);
  * with asymmetry g, finite and |g| < 1 (g > 0 scatters forward).  HG runs the HG instantiations of the production tracers (csrc/drt_sq_hg.hip
  * for supergrids, drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip); a test hook that routes a launch to an older tracer generation
  * is refused with DRT_ERR_UNSUPPORTED.  Setting another phase invalidates what the handle planned from earlier paths (path cache, ray
- * order); setting the same one again changes nothing.  No gradient with respect to g. */
+ * order); setting the same one again changes nothing.  The gradient with respect to g: drt_render_backward_phase,
+ * drt_render_backward_px_phase and drt_render_forward_phase (an extension of the reference, whose volpathsimple has none). */
 enum { DRT_PHASE_ISOTROPIC = 0, DRT_PHASE_HG = 1 };
 int drt_set_phase(drt_handle h, int32_t kind, float g);
 /* params.update(opt) after an optimizer step (python/optimize.py:354) and
@@ -160,6 +161,14 @@ int drt_render_primal(drt_handle h, const float *rays_o, const float *rays_d, ui
 int drt_render_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
                         uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL,
                         const float *L_in, float *grad_sigma_t, float *grad_albedo);
+/* drt_render_backward that also differentiates with respect to the Henyey-Greenstein asymmetry g (drt_set_phase): grad_phase_g is a
+ * DEVICE pointer to one float, accumulated with += (NULL: exactly drt_render_backward).  Estimator: the score d/dg log p_g(mu) of every
+ * direction a main path samples times the radiance it collects after it, plus the log-derivatives of the NEE and escape MIS weights.
+ * A non-NULL grad_phase_g on an isotropic handle is refused with DRT_ERR_UNSUPPORTED; the grid gradients are those of drt_render_backward.
+ * The g-gradient kernels have no counting variants: on a handle with counters enabled (drt_enable_counters) a call with a non-NULL
+ * grad_phase_g adds nothing to the counters (so does drt_render_forward_phase with t_phase_g != 0). */
+int drt_render_backward_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                              uint32_t seed, const float *dL, const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g);
 
 /* NeRFIntegrator properties (python/integrators/nerf.py:30-35; density_noise_std is
  * effectively unsupported in the reference, nerf.py:160-162, and is not exposed). */
@@ -191,6 +200,11 @@ int drt_nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const flo
 int drt_render_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
                        uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
                        float *dL_out);
+/* drt_render_forward with a tangent t_phase_g of the Henyey-Greenstein asymmetry g as well: J t includes t_phase_g dL/dg, the transpose of
+ * drt_render_backward_phase's estimator.  t_phase_g = 0: exactly drt_render_forward; non-zero on an isotropic handle: DRT_ERR_UNSUPPORTED. */
+int drt_render_forward_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
+                             uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
+                             float *dL_out, float t_phase_g);
 /* Forward mode of the nerf march: dL_out[n][3] = J(ray) . (t_sigma_t, t_emission), by dual numbers through the march (no
  * L_in needed).  At the relu kink the derivative is taken as the adjoint takes it (none unless the raw density is > 0). */
 int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
@@ -278,6 +292,10 @@ int drt_film_loss_grad(drt_handle h, const float *image, uint64_t n_pixels, cons
 int drt_render_backward_px(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
                            uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
                            const float *L_in, float *grad_sigma_t, float *grad_albedo);
+/* ... and with grad_phase_g as in drt_render_backward_phase */
+int drt_render_backward_px_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
+                                 uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
+                                 const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g);
 int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
                                 const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
                                 const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,

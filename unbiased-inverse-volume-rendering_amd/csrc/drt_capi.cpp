@@ -330,7 +330,10 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
     //   Henyey-Greenstein phase (drt_set_phase): the same choice among the HG instantiations - the queued tracer (drt_sq_hg.hip) for the
     //   supergrids it takes, CoopTracer<HG> otherwise (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip) - without tail launches or
     //   hand-off, and no ROUNDS kernels; the older generations have no HG code.
+    //   The g-gradient (drt_render_backward_phase: an HG adjoint launch with a sink in Params::L_out) runs the GG instantiations of the same
+    //   kernels; the counting kernels have none (such a launch counts nothing).
     const bool hg = h->phase_kind == DRT_PHASE_HG;
+    const bool gg = hg && adjoint && P.L_out != nullptr;
     if (hg && dbg(h->debug_flags, 32u | 65536u | 134217728u | 8u | 32768u))
         return fail(h, DRT_ERR_UNSUPPORTED, "the Henyey-Greenstein phase function has no code in the older tracer generations: the test hook "
                                             "routes this launch to one of them (debug flags 0x%x)", h->debug_flags);
@@ -338,7 +341,8 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
         drt::Params Q = P;
         Q.tail_pool = nullptr; Q.tail_count = nullptr; Q.tail_cap = 0; Q.tail_mode = 0;
         if (P.mgrid) Q.ray_perm = nullptr;
-        if (P.colour_own) DRT_HIP_CHECK(h, drt::launch_trace_own_hg(Q, adjoint, h->counting, h->stream));
+        if (gg) DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_gg(Q, h->stream) : drt::launch_trace_coop_gg(Q, h->stream));
+        else if (P.colour_own) DRT_HIP_CHECK(h, drt::launch_trace_own_hg(Q, adjoint, h->counting, h->stream));
         else DRT_HIP_CHECK(h, drt::launch_trace_coop_hg(Q, adjoint, h->counting, h->stream));
         if (h->timing) {
             DRT_HIP_CHECK(h, hipEventRecord(b, h->stream));
@@ -492,7 +496,8 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
             }
             if (hg) {
                 Q.tail_pool = nullptr; Q.tail_count = nullptr; Q.tail_cap = 0; Q.tail_mode = 0;
-                DRT_HIP_CHECK(h, drt::launch_trace_sq_hg(Q, adjoint, h->counting, h->n_cus, h->stream));
+                if (gg) DRT_HIP_CHECK(h, drt::launch_trace_sq_gg(Q, h->n_cus, h->stream));
+                else DRT_HIP_CHECK(h, drt::launch_trace_sq_hg(Q, adjoint, h->counting, h->n_cus, h->stream));
             }
             else DRT_HIP_CHECK(h, drt::launch_trace_sq(Q, adjoint, h->counting, h->n_cus, h->stream));
             if (tail && Q.tail_pool) {
@@ -1320,14 +1325,18 @@ int drt_render_primal(drt_handle h, const float *rays_o, const float *rays_d, ui
 }
 
 // the adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel, drt_render_backward_px) is given
+// grad_phase_g (drt_render_backward_phase, an HG handle): dLoss/dg is added to *grad_phase_g - it travels in Params::L_out, which no adjoint
+// kernel otherwise reads or writes, and selects the GG kernels (timed_launch)
 static int render_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
-                           uint32_t seed, const float *dL, const float *dL_pix, const float *L_in, float *grad_sigma_t, float *grad_albedo)
+                           uint32_t seed, const float *dL, const float *dL_pix, const float *L_in, float *grad_sigma_t, float *grad_albedo,
+                           float *grad_phase_g = nullptr)
 {
     int rc;
     DeviceGuard g(h->device);
     drt::Params P;
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
     P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_albedo;
+    P.L_out = grad_phase_g;
     // capacity: 48 sigma_t and 6 colour records per ray (headline workload: 12.3 and 1.4); beyond it the
     // tracer falls back to direct atomics (emit_record), so this is a performance choice only
     const uint64_t job_rays = n_rays;
@@ -1349,6 +1358,28 @@ int drt_render_backward(drt_handle h, const float *rays_o, const float *rays_d, 
     if (n_rays && (!dL || !L_in || !grad_sigma_t || !grad_albedo))
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward: null dL / L_in / gradient buffer");
     return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo);
+}
+
+// the g-gradient arguments of the *_phase entry points: only an HG handle has a g to differentiate
+static int check_phase_grad(drt_handle h, const char *what, bool wanted)
+{
+    if (wanted && h->phase_kind != DRT_PHASE_HG)
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the handle's phase function is isotropic - a gradient with respect to g needs the "
+                                            "Henyey-Greenstein phase function (drt_set_phase(DRT_PHASE_HG, 0.0) for an isotropic medium)", what);
+    return DRT_OK;
+}
+
+int drt_render_backward_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                              uint32_t seed, const float *dL, const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g)
+{
+    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
+    if (rc) return rc;
+    rc = check_phase_grad(h, "drt_render_backward_phase", grad_phase_g != nullptr);
+    if (rc) return rc;
+    if (n_rays == 0) return DRT_OK;
+    if (!dL || !L_in || !grad_sigma_t || !grad_albedo)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_phase: null dL / L_in / gradient buffer");
+    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo, grad_phase_g);
 }
 
 static int nerf_fill(drt_handle h, drt::Params &P, const drt_nerf_config *cfg, const float *emission, bool fused_half = false)
@@ -1462,6 +1493,24 @@ static void forward_params(drt::Params &P, const float *t_sigma, const float *t_
     P.dL = nullptr; P.dL_pix = nullptr; P.gt = nullptr;
 }
 
+// t_phase_g != 0 (drt_render_forward_phase, an HG handle): the GG kernels, which add t_g dL/dg (Params::phase_tg, in padding of the block)
+static int render_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                          uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo, float *dL_out, float t_phase_g)
+{
+    DeviceGuard g(h->device);
+    drt::Params P;
+    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    forward_params(P, t_sigma_t, t_albedo, dL_out);
+    P.L_in = L_in;
+    P.phase_tg = t_phase_g;
+    if (t_phase_g != 0.0f)                                      // (drt_render_forward_phase with a g tangent: an HG handle)
+        DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_gg(P, h->stream) : drt::launch_trace_coop_fwd_gg(P, h->stream));
+    else if (h->phase_kind == DRT_PHASE_HG)
+        DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_hg(P, h->stream) : drt::launch_trace_coop_fwd_hg(P, h->stream));
+    else DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd(P, h->stream) : drt::launch_trace_coop_fwd(P, h->stream));
+    return DRT_OK;
+}
+
 int drt_render_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
                        uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
                        float *dL_out)
@@ -1470,15 +1519,21 @@ int drt_render_forward(drt_handle h, const float *rays_o, const float *rays_d, u
     int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
     if (rc) return rc;
     if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward: null L_in / dL_out");
-    DeviceGuard g(h->device);
-    drt::Params P;
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    forward_params(P, t_sigma_t, t_albedo, dL_out);
-    P.L_in = L_in;
-    if (h->phase_kind == DRT_PHASE_HG)
-        DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_hg(P, h->stream) : drt::launch_trace_coop_fwd_hg(P, h->stream));
-    else DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd(P, h->stream) : drt::launch_trace_coop_fwd(P, h->stream));
-    return DRT_OK;
+    return render_forward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_in, t_sigma_t, t_albedo, dL_out, 0.0f);
+}
+
+int drt_render_forward_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
+                             uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
+                             float *dL_out, float t_phase_g)
+{
+    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
+    if (rc) return rc;
+    if (!std::isfinite(t_phase_g)) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase: t_phase_g must be finite");
+    rc = check_phase_grad(h, "drt_render_forward_phase", t_phase_g != 0.0f);
+    if (rc) return rc;
+    if (n_rays == 0) return DRT_OK;
+    if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase: null L_in / dL_out");
+    return render_forward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_in, t_sigma_t, t_albedo, dL_out, t_phase_g);
 }
 
 int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
@@ -1916,6 +1971,22 @@ int drt_render_backward_px(drt_handle h, const float *rays_o, const float *rays_
     rc = check_px(h, "drt_render_backward_px", n_rays, spp, grad_image, n_pixels);
     if (rc) return rc;
     return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo);
+}
+
+int drt_render_backward_px_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
+                                 uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
+                                 const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g)
+{
+    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
+    if (rc) return rc;
+    rc = check_phase_grad(h, "drt_render_backward_px_phase", grad_phase_g != nullptr);
+    if (rc) return rc;
+    if (!L_in || !grad_sigma_t || !grad_albedo)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_px_phase: null L_in / gradient buffer");
+    rc = check_px(h, "drt_render_backward_px_phase", n_rays, spp, grad_image, n_pixels);
+    if (rc) return rc;
+    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo,
+                           grad_phase_g);
 }
 
 int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,

@@ -17,4 +17,17 @@ hipError_t launch_trace_coop_fwd_hg(const Params &P, hipStream_t stream)
     return launch_trace_coop_fwd_t<false, true>(P, stream);
 }
 
+// ... with the g-gradient (GG): the adjoint adds dLoss/dg to *P.L_out, forward mode adds t_g (P.phase_tg) times dL/dg to J t
+hipError_t launch_trace_coop_gg(const Params &P, hipStream_t stream)
+{
+    if (P.mgrid) return launch_trace_coop_super_gg(P, stream);                   // drt_coop_super_hg.hip
+    return launch_trace_coop_gg_t<false>(P, stream);
+}
+
+hipError_t launch_trace_coop_fwd_gg(const Params &P, hipStream_t stream)
+{
+    if (P.mgrid) return launch_trace_coop_super_fwd_gg(P, stream);               // drt_coop_super_hg.hip
+    return launch_trace_coop_fwd_t<false, true, true>(P, stream);
+}
+
 }  // namespace drt

@@ -14,7 +14,8 @@ using namespace coop;
 // TAIL: the second launch of a specialised kernel - its workgroups start from 256 paths of the tail pool each
 // (CoopTracer::wg_handoff) instead of from rays, and finish them
 // HG: Henyey-Greenstein phase function (CoopTracer); those kernels run without hand-off and tail pool
-template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, bool HG = false>
+// GG (adjoint, with HG): the g-gradient too - each wave adds the sum of its lanes' terms to *Params::L_out with one atomic at its end
+template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, bool HG = false, bool GG = false>
 __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRIMAL) trace_coop_kernel(const Params P)
 {
     if constexpr (TAIL) { if (blockIdx.x * 256u >= *P.tail_count) return; }   // (workgroup-uniform) nothing for this workgroup
@@ -36,7 +37,8 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
     if constexpr (ADJ && !SUPER) {                              // rays of similar length share a wave (ray_perm_kernel)
         if (P.ray_perm) i = (i_block & ~(uint64_t) (kPermGroup - 1)) + P.ray_perm[i_block + threadIdx.x];
     }
-    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, HG> tr(P);
+    static_assert(!GG || (ADJ && HG && !TAIL), "the g-gradient kernels are HG adjoint kernels");
+    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, HG, GG> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     tr.i_block = TAIL ? 0 : i_block;
@@ -125,6 +127,12 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
         if (job && !(SPEC && tr.wgc)) { P.L_out[3 * i] = L[0]; P.L_out[3 * i + 1] = L[1]; P.L_out[3 * i + 2] = L[2]; }   // (hand-off: written by wg_handoff)
     }
     if constexpr (ADJ && DEFER) close_records(P, tr.rec);
+    if constexpr (GG) {                                         // dLoss/dg: one atomic per wave (every lane of the wave is here)
+        float v = tr.g_acc;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if ((threadIdx.x & 63) == 0 && v != 0.0f) atomicAdd(P.L_out, v);
+    }
     if constexpr (!ADJ) {
         if (P.ray_iters && job && !(SPEC && tr.wgc)) P.ray_iters[i] = (uint8_t) (tr.iters < 255u ? tr.iters : 255u);   // sort key of ray_perm_kernel
         if (P.block_cost && !TAIL) {
@@ -149,7 +157,8 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
 // Forward mode (drt_render_forward): CoopTracer<FWD> runs the adjoint's paths with dL = 1, gathering from the tangent grids where the
 // adjoint splats (the tangent grids are Params::g_sigma / g_albedo), and writes J t of its ray to L_out - once, from the ray's own lane (no hand-off, no tail pool, no atomics: the result is
 // bit-reproducible).  The global majorant's NEE walks take every step on the walk's own lane (CoopTracer::coop_rt).
-template <bool ENV, bool SPEC, bool SUPER, bool HG = false>
+// GG (with HG): J t includes t_g (Params::phase_tg) times the derivative with respect to g
+template <bool ENV, bool SPEC, bool SUPER, bool HG = false, bool GG = false>
 __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(const Params P)
 {
     uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map (see trace_coop_kernel)
@@ -164,7 +173,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     }
 #endif
     const uint64_t i = P.ray_first + (uint64_t) b * blockDim.x + threadIdx.x;
-    CoopTracer<false, ENV, false, SPEC, false, SUPER, true, HG> tr(P);
+    CoopTracer<false, ENV, false, SPEC, false, SUPER, true, HG, GG> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     __shared__ uint64_t jump_lds[2 * (kJumpMax + 1)];
@@ -211,7 +220,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     if (job) { P.L_out[3 * i] = tr.tg[0]; P.L_out[3 * i + 1] = tr.tg[1]; P.L_out[3 * i + 2] = tr.tg[2]; }
 }
 
-template <bool SUPER, bool HG = false>
+template <bool SUPER, bool HG = false, bool GG = false>
 hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
@@ -219,11 +228,11 @@ hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
     const bool env = P.env_pix != nullptr;
     const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, 2097152u);
     if (spec) {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, HG>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, HG>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, HG, GG>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, HG, GG>), grid, block, 0, stream, P);
     } else {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER, HG>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER, HG>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER, HG, GG>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER, HG, GG>), grid, block, 0, stream, P);
     }
     return hipGetLastError();
 }
@@ -295,6 +304,24 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
         else       { if (env) DRT_COOP_LAUNCH(true, false, true, false); else DRT_COOP_LAUNCH(true, false, false, false); }
     }
 #undef DRT_COOP_LAUNCH
+    return hipGetLastError();
+}
+
+// the adjoint launch with the g-gradient (HG + GG instantiations; dLoss/dg is added to *P.L_out): the choice launch_trace_coop_t makes for
+// an HG adjoint launch, without the counting kernels (a counting handle's g-gradient launches count nothing)
+template <bool SUPER>
+hipError_t launch_trace_coop_gg_t(const Params &P, hipStream_t stream)
+{
+    if (P.n_rays <= P.ray_first) return hipSuccess;
+    if (!P.L_out || P.tail_pool) return hipErrorInvalidValue;
+    dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
+    const bool env = P.env_pix != nullptr, defer = P.rec_buf[0] != nullptr;
+    const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, 2097152u);
+#define DRT_COOP_LAUNCH_GG(E, D, SP) hipLaunchKernelGGL((trace_coop_kernel<true, false, E, D, SP, SUPER, false, true, true>), grid, block, 0, stream, P)
+    if (spec && defer) { if (env) DRT_COOP_LAUNCH_GG(true, true, true); else DRT_COOP_LAUNCH_GG(false, true, true); }
+    else if (defer) { if (env) DRT_COOP_LAUNCH_GG(true, true, false); else DRT_COOP_LAUNCH_GG(false, true, false); }
+    else { if (env) DRT_COOP_LAUNCH_GG(true, false, false); else DRT_COOP_LAUNCH_GG(false, false, false); }
+#undef DRT_COOP_LAUNCH_GG
     return hipGetLastError();
 }
 

@@ -11,4 +11,7 @@ hipError_t launch_trace_coop_super_hg(const Params &P, bool adjoint, bool count,
 
 hipError_t launch_trace_coop_super_fwd_hg(const Params &P, hipStream_t stream) { return launch_trace_coop_fwd_t<true, true>(P, stream); }
 
+hipError_t launch_trace_coop_super_gg(const Params &P, hipStream_t stream) { return launch_trace_coop_gg_t<true>(P, stream); }
+hipError_t launch_trace_coop_super_fwd_gg(const Params &P, hipStream_t stream) { return launch_trace_coop_fwd_t<true, true, true>(P, stream); }
+
 }  // namespace drt

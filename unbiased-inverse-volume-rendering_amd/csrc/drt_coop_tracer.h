@@ -120,8 +120,14 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 // that samples or evaluates the phase function: the scatter sites of main and recursive paths (volpathsimple.py:221-230, 630-646), the
 // NEE phase value and MIS weight (:386-391), and the escape MIS weight through last_pdf (:273-277).  The incoming direction of a
 // scatter is wi = -d of the ray that reached it.  Without hand-off or tail pool: a handed-off path would have to carry its last pdf.
-template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, bool HG = false>
+// GG (with HG): the derivative with respect to g as well, from the main path only ("Gradient with respect to g"): the score
+// hg_score of every sampled direction and the explicit terms of the two MIS weights.  Adjoint: g_acc sums <dL, .> of the terms on each lane
+// (the kernel adds a wave's sum to Params::L_out once); forward mode: g_S carries the scores sampled so far and every contribution adds
+// c (g_S + explicit term) t_g (Params::phase_tg) to tg.
+template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, bool HG = false,
+          bool GG = false>
 struct CoopTracer {
+    static_assert(!GG || HG, "the g-gradient exists for the Henyey-Greenstein phase function only");
     const Params &P;
     float maj, inv_maj;
     const uint32_t *mocc;   // SUPER: non-empty supergrid cells (LDS copy) or nullptr
@@ -141,6 +147,8 @@ struct CoopTracer {
     float fsum;             // FWD: sum over the steps of the current transmittance walk of -(1/maj) / tr * sigma_t'(p)
     V3 hg_wi, hg_wd;        // HG: the incoming direction at the current vertex (set before each NEE / recursive path), the emitter direction
                             // sample_emitter drew (members, not parameters: the isotropic instantiations keep the signatures they compile from)
+    float g_acc;            // GG, adjoint: this lane's share of dLoss/dg
+    float g_S;              // GG, forward mode: sum of the scores of the directions the main path has sampled
 
     __device__ __forceinline__ CoopTracer(const Params &p) : P(p)
     {
@@ -148,6 +156,7 @@ struct CoopTracer {
         ray_index = 0; rec = nullptr; slots = nullptr; occ = nullptr; jump = nullptr; pc = nullptr; work = 0; iters = 0;
         mocc = nullptr; wgc = nullptr; i_block = 0; tail_load = false;
         if constexpr (HG) { hg_wi = v3(0, 0, 1); hg_wd = v3(0, 0, 1); }
+        if constexpr (GG) { g_acc = 0.0f; g_S = 0.0f; }
 #if DRT_PHASE_PROFILE
         ph_t = __builtin_readcyclecounter();
 #endif
@@ -475,7 +484,15 @@ struct CoopTracer {
         constexpr bool kFwd = ADJ && FWD;
         if constexpr (kFwd) fsum = 0.0f;
         float ds_pdf = sample_emitter<kFwd>(job, p, S, nullptr, emitted, cmode, ce);   // :385
-        if constexpr (HG) {                                                     // phase_val = phase_pdf = eval(wd, wi) (:386-388)
+        float gx = 0.0f;                                                        // GG (main path): (2w - 1) hg_score(mu_e), the NEE term's log-derivative
+        if constexpr (GG && ADJ) {
+            const float mu = (hg_wd.x * hg_wi.x + hg_wd.y * hg_wi.y) + hg_wd.z * hg_wi.z;
+            const float pv = hg_eval_cos(P.phase_g, mu);
+            float w = mis_weight(ds_pdf, pv);                                   // :391
+#pragma unroll
+            for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * pv) * w) * emitted[k] : 0.0f;
+            gx = (2.0f * w - 1.0f) * hg_score(P.phase_g, mu);
+        } else if constexpr (HG) {                                              // phase_val = phase_pdf = eval(wd, wi) (:386-388)
             const float pv = hg_eval(P.phase_g, hg_wd, hg_wi);
             float w = mis_weight(ds_pdf, pv);                                   // :391
 #pragma unroll
@@ -489,10 +506,16 @@ struct CoopTracer {
             if (job) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) tg[k] += (dL[k] * contrib[k]) * fsum;
+                if constexpr (GG) {
+                    const float f = (g_S + gx) * P.phase_tg;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) tg[k] += (dL[k] * contrib[k]) * f;
+                }
             }
         } else if constexpr (ADJ) {                                             // :393-401
             float adj[3] = { 0.0f, 0.0f, 0.0f };
             if (job) { adj[0] = dL[0] * contrib[0]; adj[1] = dL[1] * contrib[1]; adj[2] = dL[2] * contrib[2]; }
+            if constexpr (GG) { if (job) g_acc += gx * ((adj[0] + adj[1]) + adj[2]); }
             float unused[3];
             (void) sample_emitter<true>(job, p, clone, adj, unused);
         }
@@ -838,6 +861,8 @@ struct CoopTracer {
         }
         bool has_scattered = RECURSIVE ? (active && !escaped) : false;          // :84-89
         float last_pdf = RECURSIVE ? ps->last_pdf : 1.0f;
+        constexpr bool kGG = GG && ADJ && !RECURSIVE;                           // the g-gradient terms: main path of the adjoint / forward pass
+        float s_last = 0.0f;                                                    // kGG: score of the last sampled direction
 
         // DRTReservoir(n=1) + DRTPathState (:94-96, :710-765)
         int r_depth = -1; float r_si_t = kInf; Ray r_ray = ray;
@@ -979,7 +1004,14 @@ struct CoopTracer {
                 if (did_scatter) {                                              // :221-230
                     (void) S.next_1d();
                     float ux = S.next_1d(), uy = S.next_1d();
-                    if constexpr (HG) { ray.o = mei.p; ray.d = hg_sample(P.phase_g, ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf); ray.maxt = kLargest; }
+                    if constexpr (kGG) {                                        // the score term: s(mu) times what the path collects after it
+                        float mu;
+                        ray.o = mei.p; ray.d = hg_sample(P.phase_g, ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf, mu); ray.maxt = kLargest;
+                        s_last = hg_score(P.phase_g, mu);
+                        if constexpr (FWD) g_S += s_last;
+                        else g_acc += s_last * ((dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2]);   // result: L below this vertex
+                    }
+                    else if constexpr (HG) { ray.o = mei.p; ray.d = hg_sample(P.phase_g, ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf); ray.maxt = kLargest; }
                     else {
                         ray.o = mei.p; ray.d = square_to_uniform_sphere(ux, uy); ray.maxt = kLargest;
                         last_pdf = kInvFourPi;
@@ -1012,6 +1044,19 @@ struct CoopTracer {
                     for (int k = 0; k < 3; ++k) adj[k] = (dd != 0.0f ? (ws * r_cw[k]) / dd : 0.0f) * dL[k];
                 }
                 drt_backprop(rjob, A, r_ray, r_si_t, r_depth, adj);
+            }
+            if constexpr (kGG) {                                                // the escape hit (:263-287) of a path that has scattered
+                if (job && escaped && has_scattered) {
+                    float Le[3];
+                    const float e_pdf = emitter_eval_pdf<ENV>(P, ray.d, Le);
+                    const float w = use_nee() ? mis_weight(last_pdf, e_pdf) : 1.0f;
+                    const float ex = use_nee() ? (2.0f * (1.0f - w)) * s_last : 0.0f;   // the MIS weight's log-derivative
+                    if constexpr (FWD) {                                        // c (g_S + ex) t_g, c = the emission the primal pass added
+                        const float f = (g_S + ex) * P.phase_tg;
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) tg[k] += (dL[k] * ((beta[k] * w) * Le[k])) * f;
+                    } else g_acc += ex * ((dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2]);   // result: that emission
+                }
             }
         } else {                                                                // :263-287
             if (job && !wgc_on) add_escaped_emission(escaped, depth, has_scattered, last_pdf, ray.d, beta, result);   // (hand-off mode: done in wg_handoff)

@@ -207,7 +207,8 @@ __device__ __forceinline__ float hg_eval(float g, V3 wo, V3 wi)
     return hg_eval_cos(g, (wo.x * wi.x + wo.y * wi.y) + wo.z * wi.z);
 }
 
-__device__ __forceinline__ V3 hg_sample(float g, float ux, float uy, V3 wi, float &pdf)
+// (mu: the cosine the sampled direction's pdf was evaluated at, hg_eval_cos(g, mu) = pdf - what hg_score takes)
+__device__ __forceinline__ V3 hg_sample(float g, float ux, float uy, V3 wi, float &pdf, float &mu)
 {
     float cos_t;
     if (fabsf(g) < kHgEps) cos_t = 1.0f - 2.0f * ux;
@@ -226,8 +227,25 @@ __device__ __forceinline__ V3 hg_sample(float g, float ux, float uy, V3 wi, floa
     const float b = (wi.x * wi.y) * a;
     const V3 s = v3(msg * ((wi.x * wi.x) * a) + 1.0f, msg * b, -msg * wi.x);
     const V3 t = v3(b, fmaf(wi.y, wi.y * a, sgn), -wi.y);
-    pdf = hg_eval_cos(g, -cos_t);
+    mu = -cos_t;
+    pdf = hg_eval_cos(g, mu);
     return v3((s.x * lx + t.x * ly) + wi.x * lz, (s.y * lx + t.y * ly) + wi.y * lz, (s.z * lx + t.z * ly) + wi.z * lz);
+}
+
+__device__ __forceinline__ V3 hg_sample(float g, float ux, float uy, V3 wi, float &pdf)
+{
+    float mu;
+    return hg_sample(g, ux, uy, wi, pdf, mu);
+}
+
+// Score of the Henyey-Greenstein density with respect to its asymmetry (an extension: Mitsuba's `hg` has no gradient for g):
+//   d/dg log hg_eval_cos(g, mu) = -2g / (1 - g^2) - 3 (g + mu) / (1 + g^2 + 2 g mu)
+// The g-gradient of a path is its contribution times the sum of the scores of the directions it sampled, plus the explicit
+// terms of the MIS weights ("Gradient with respect to g").
+__device__ __forceinline__ float hg_score(float g, float mu)
+{
+    const float temp = (1.0f + g * g) + (2.0f * g) * mu;
+    return (-2.0f * g) / (1.0f - g * g) - (3.0f * (g + mu)) / temp;
 }
 
 // atan2 with a specified instruction sequence (Cephes atanf polynomial on min/max in [0,1]);
@@ -312,6 +330,10 @@ struct Params {
     uint64_t ray_first;
     uint64_t chunk, stride;    // global index of local ray i = ray_offset + (i/chunk)*stride + i%chunk (chunk 0: + i)
     uint32_t spp, seed, alt_seed;
+    // forward mode with a g tangent (drt_render_forward_phase): t_g, read only by the HG + GG forward kernels.  It fills the four bytes of
+    // padding in front of L_out (no field moves).  The adjoint's g-gradient sink (drt_render_backward_phase) travels in L_out, which the
+    // adjoint kernels never read or write.
+    float phase_tg;
     // outputs / adjoint inputs
     float *L_out;
     const float *dL, *L_in;
@@ -391,6 +413,8 @@ struct Params {
     const float *dL_pix;
 };
 static_assert(offsetof(Params, majorant) == offsetof(Params, g4_nbx) + 8, "Params::phase_g must stay in the padding in front of majorant");
+static_assert(offsetof(Params, L_out) == offsetof(Params, alt_seed) + 8, "Params::phase_tg must stay in the padding in front of L_out");
+static_assert(sizeof(Params) == 752, "the kernel parameter block keeps its size");
 
 // ---------------------------------------------------------------------------
 // envmap emitter [M3-ext] (volpathsimple.py:273,284,419; include/drt_hip.h: drt_set_emitter_envmap)

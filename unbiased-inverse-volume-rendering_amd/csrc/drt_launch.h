@@ -72,6 +72,15 @@ hipError_t launch_trace_coop_super_fwd_hg(const Params &P, hipStream_t stream);
 hipError_t launch_trace_own_fwd_hg(const Params &P, hipStream_t stream);
 // ... and the queued supergrid tracer's (drt_sq_hg.hip): as launch_trace_sq, without tail launch (Params::tail_pool / tail_mode must be unset)
 hipError_t launch_trace_sq_hg(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
+// ... with the derivative with respect to g (the GG instantiations): the adjoint launches add dLoss/dg to *Params::L_out (one atomic per
+// wave), the forward ones add t_g (Params::phase_tg) times dL/dg to J t.  Without counting kernels.
+hipError_t launch_trace_coop_gg(const Params &P, hipStream_t stream);
+hipError_t launch_trace_coop_super_gg(const Params &P, hipStream_t stream);
+hipError_t launch_trace_own_gg(const Params &P, hipStream_t stream);
+hipError_t launch_trace_coop_fwd_gg(const Params &P, hipStream_t stream);
+hipError_t launch_trace_coop_super_fwd_gg(const Params &P, hipStream_t stream);
+hipError_t launch_trace_own_fwd_gg(const Params &P, hipStream_t stream);
+hipError_t launch_trace_sq_gg(const Params &P, int n_cus, hipStream_t stream);
 hipError_t launch_ray_perm(const uint8_t *iters, uint64_t n_rays, uint16_t *perm, uint32_t *block_cost, hipStream_t stream);
 hipError_t launch_block_order(const uint32_t *cost, uint32_t n_blocks, uint32_t *order, bool heavy_first, hipStream_t stream);
 hipError_t launch_untile(const Params &P, hipStream_t stream);

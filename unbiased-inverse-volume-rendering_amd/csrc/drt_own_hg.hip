@@ -17,4 +17,16 @@ hipError_t launch_trace_own_fwd_hg(const Params &P, hipStream_t stream)
     return launch_trace_coop_fwd_t<false, true>(P, stream);
 }
 
+hipError_t launch_trace_own_gg(const Params &P, hipStream_t stream)
+{
+    if (P.mgrid) return launch_trace_coop_gg_t<true>(P, stream);
+    return launch_trace_coop_gg_t<false>(P, stream);
+}
+
+hipError_t launch_trace_own_fwd_gg(const Params &P, hipStream_t stream)
+{
+    if (P.mgrid) return launch_trace_coop_fwd_t<true, true, true>(P, stream);
+    return launch_trace_coop_fwd_t<false, true, true>(P, stream);
+}
+
 }  // namespace drt

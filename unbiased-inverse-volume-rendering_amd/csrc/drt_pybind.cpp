@@ -132,6 +132,17 @@ public:
         }
         check(rc, "drt_render_backward");
     }
+    void render_backward_phase(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dL,
+                               uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_phase)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_render_backward_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
+                                           ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo), ptr<float>(g_phase));
+        }
+        check(rc, "drt_render_backward_phase");
+    }
     static drt_nerf_config nerf_cfg(const py::dict &p)
     {
         drt_nerf_config c{};
@@ -177,6 +188,17 @@ public:
                                     ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out));
         }
         check(rc, "drt_render_forward");
+    }
+    void render_forward_phase(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
+                              uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out, float t_phase)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_render_forward_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
+                                          ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), t_phase);
+        }
+        check(rc, "drt_render_forward_phase");
     }
     void nerf_render_forward(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
                              uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_emission, uintptr_t dL_out)
@@ -276,6 +298,18 @@ public:
                                         n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo));
         }
         check(rc, "drt_render_backward_px");
+    }
+    void render_backward_px_phase(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed,
+                                  uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_phase)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_render_backward_px_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
+                                              ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
+                                              ptr<float>(g_albedo), ptr<float>(g_phase));
+        }
+        check(rc, "drt_render_backward_px_phase");
     }
     void nerf_render_backward_px(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
                                  uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
@@ -391,6 +425,9 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("set_sensor_perspective", &Integrator::set_sensor_perspective)
         .def("render_primal", &Integrator::render_primal)
         .def("render_backward", &Integrator::render_backward)
+        .def("render_backward_phase", &Integrator::render_backward_phase)
+        .def("render_forward_phase", &Integrator::render_forward_phase)
+        .def("render_backward_px_phase", &Integrator::render_backward_px_phase)
         .def("nerf_render_primal", &Integrator::nerf_render_primal)
         .def("nerf_render_backward", &Integrator::nerf_render_backward)
         .def("render_forward", &Integrator::render_forward)

@@ -276,10 +276,15 @@ __device__ __forceinline__ void sq_push_all(unsigned long long *ctl, uint16_t *q
 // {wi, last pdf} - the incoming direction of the current vertex (the emitter-direction block stores it before it replaces rd: with use_nee every
 // phase sampling follows that block at the same vertex) and the pdf of the last phase sampling (read at the escape only by primal and recursive
 // paths, which are never suspended: the quadratic detour restores the main path's rd, and its own emitter-direction block stores it again).
-template <bool ADJ, bool COUNT, bool ENV, bool MG, bool QUAD = false, bool TAILM = false, bool ROUNDS = false, bool HG = false>
+// GG (HG adjoint kernels of drt_sq_hg.hip, launch_trace_sq_gg): the derivative with respect to g of the main paths as well ("Gradient
+// with respect to g"): the score of each phase sampling times <dL, result> (result: the radiance below the vertex), the NEE term and the escape
+// term.  Each lane sums them over the records it serves; a wave adds its sum to *Params::L_out once, at its end.  A record owns one more uint4 of
+// global memory: {score, pdf} of the main path's last phase sampling (the quadratic detour's recursive paths overwrite the last pdf in {wi, last pdf}).
+template <bool ADJ, bool COUNT, bool ENV, bool MG, bool QUAD = false, bool TAILM = false, bool ROUNDS = false, bool HG = false, bool GG = false>
 __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P)
 {
     static_assert(!HG || (!TAILM && !ROUNDS), "the HG kernels have no tail launch and no ROUNDS variant");
+    static_assert(!GG || (HG && ADJ), "the g-gradient kernels are HG adjoint kernels");
     constexpr int NWV = DRT_SQ_THREADS / 64;
     constexpr int R4 = 7;                                                    // uint4 per ray record in LDS
     static_assert(ADJ || !QUAD, "the primal pass of the quadratic estimator is the ordinary one");
@@ -290,7 +295,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
     constexpr bool SOLO = TAILM && !MG;
     constexpr int NB = QUAD ? 9 : 6;                                         // uint4 of part b of the global record (adjoint)
     constexpr int NC = ADJ ? 3 + NB : 3;                                     // uint4 per ray in global memory (Params::sq_cold)
-    constexpr int NCW = NC + (HG ? 1 : 0);                                   // ... HG: + {wi, last pdf}
+    constexpr int NCW = NC + (HG ? 1 : 0) + (GG ? 1 : 0);                    // ... HG: + {wi, last pdf}; GG: + {score, pdf} of the main path
     // LDS record: [0] {tn.x, tn.y, tn.z, cell} [1] {td.x, td.y, td.z, steps left (9 bits per axis) + direction signs}
     // [2] {tau, tmax, t, acc} - the flight (a finished flight leaves its cell's majorant, 0: left the segment, in [0].x) -
     // [3] {rd, wmax} [4] {wo, wt} [5] {G.state, G.inc}: the generator the current walk draws from (the alt sampler in the main
@@ -392,6 +397,9 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
     uint4 *cold_b = cold_a + 3 * NRAY;                                        // [NRAY][6] (adjoint; QUAD: [9], the last three: the suspended main path)
     float4 *cold_h = (float4 *) (cold_a + NC * NRAY);                         // HG: [NRAY] {wi, last pdf}
     (void) cold_h;
+    float2 *cold_g = (float2 *) (cold_a + (NC + 1) * NRAY);                   // GG: [NRAY] {score, pdf} of the main path's last phase sampling
+    (void) cold_g;
+    float g_acc = 0.0f;                                                        // GG: this lane's share of dLoss/dg
     const uint32_t xcc = sq_xcc_id();
     // (with a ray order the queue positions cover whole units: the last unit may reach past the launch's last ray)
     const uint64_t span = P.order ? (uint64_t) P.order_units * P.order_unit : P.n_rays - P.ray_first;
@@ -1004,7 +1012,18 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                 // (recomputed from the direction; behind the NEE block of the same pass the density is the one it just evaluated)
                 const float ds_pdf = (ENV && behind_nee && nee_pdf_ok) ? emitter_sample_value_with_pdf<ENV>(P, rd, nee_pdf, val)
                                                                        : emitter_sample_value<ENV>(P, rd, val);
-                if constexpr (HG) {                                         // phase_val = phase_pdf = eval(rd, wi) (:386-388)
+                if constexpr (GG) {                                         // ... and the NEE term of the g-gradient: (2w - 1) s(mu_e) <dL, contrib>
+                    const float4 hw = cold_h[id];
+                    const float mu = (rd.x * hw.x + rd.y * hw.y) + rd.z * hw.z;
+                    const float pv = hg_eval_cos(P.phase_g, mu);
+                    const float w = mis_weight(ds_pdf, pv);                 // :391
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        contrib[k] = ((beta[k] * pv) * w) * (val[k] * wt);
+                        result[k] = (ADJ && !rec_mode) ? result[k] - contrib[k] : result[k] + contrib[k];   // :211-214
+                    }
+                    if (!rec_mode) g_acc += ((2.0f * w - 1.0f) * hg_score(P.phase_g, mu)) * ((dL[0] * contrib[0] + dL[1] * contrib[1]) + dL[2] * contrib[2]);
+                } else if constexpr (HG) {                                  // phase_val = phase_pdf = eval(rd, wi) (:386-388)
                     const float4 hw = cold_h[id];
                     const float pv = hg_eval(P.phase_g, rd, v3(hw.x, hw.y, hw.z));
                     const float w = mis_weight(ds_pdf, pv);                 // :391
@@ -1092,6 +1111,15 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                     if constexpr (HG) {                                         // wi: stored by the emitter-direction block, or -rd without NEE
                         float4 hw = cold_h[id];
                         const V3 wi = P.use_nee ? v3(hw.x, hw.y, hw.z) : v3(-rd.x, -rd.y, -rd.z);
+                        if constexpr (GG) {                                     // the score term: s(mu) <dL, result> (result: L below this vertex)
+                            float mu;
+                            rd = hg_sample(P.phase_g, ux, uy, wi, hw.w, mu);
+                            if (!rec_mode) {
+                                const float sc = hg_score(P.phase_g, mu);
+                                g_acc += sc * ((dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2]);
+                                cold_g[id] = make_float2(sc, hw.w);
+                            }
+                        } else
                         rd = hg_sample(P.phase_g, ux, uy, wi, hw.w);
                         cold_h[id] = hw;
                     } else
@@ -1263,6 +1291,15 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                             else if (P.use_nee) w = mis_weight(scat_once ? kInvFourPi : 1.0f, has_scattered ? e_pdf : 0.0f);
 #pragma unroll
                             for (int k = 0; k < 3; ++k) result[k] += (beta[k] * w) * Le[k];
+                        }
+                    }
+                    if constexpr (GG) {                                         // the escape term: 2 (1 - w) s(mu_last) <dL, result>
+                        if (!rec_mode && escaped && has_scattered && P.use_nee) {   // (result: the emission the primal pass added, :263-287)
+                            float Le[3];
+                            const float e_pdf = emitter_eval_pdf<ENV>(P, rd, Le);
+                            const float2 sg = cold_g[id];
+                            const float w = mis_weight(sg.y, e_pdf);
+                            g_acc += ((2.0f * (1.0f - w)) * sg.x) * ((dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2]);
                         }
                     }
                     if constexpr (!ADJ) {
@@ -1578,6 +1615,12 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
             if (lane == 0 && v) atomicAdd(P.counters + s, (unsigned long long) v);
         }
     }
+    if constexpr (GG) {                                                        // dLoss/dg: one atomic per wave (every lane of the wave is here)
+        float v = g_acc;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0 && v != 0.0f) atomicAdd(P.L_out, v);
+    }
 #undef SQ_COUNT
 #undef SQ_PROF
 #undef SQ_STAMP
@@ -1622,7 +1665,8 @@ uint32_t sq_tail_push() { return DRT_SQ_TAIL_PUSH + 64; }   // (the hand-over's 
 size_t sq_tail_entry_quads() { return kSqTailQuads; }
 
 // (3 + 9: the quadratic estimator's adjoint records; + 1: {wi, last pdf} of the HG kernels)
-size_t sq_cold_bytes(int n_cus) { return (size_t) n_cus * 13 * DRT_SQ_MAX_RAYS * sizeof(uint4); }
+// (+ 1: {score, pdf} of the g-gradient kernels)
+size_t sq_cold_bytes(int n_cus) { return (size_t) n_cus * 14 * DRT_SQ_MAX_RAYS * sizeof(uint4); }
 
 bool sq_supported(const Params &P)
 {
@@ -1631,12 +1675,14 @@ bool sq_supported(const Params &P)
 
 #endif
 
-// HG: the Henyey-Greenstein instantiations (drt_sq_hg.hip): no tail launch, no ROUNDS kernels
-template <bool HG>
+// HG: the Henyey-Greenstein instantiations (drt_sq_hg.hip): no tail launch, no ROUNDS kernels.  GG: their adjoint launches with the g-gradient
+// (into *Params::L_out), without counting kernels
+template <bool HG, bool GG = false>
 static hipError_t launch_trace_sq_t(const Params &Pin, bool adjoint, bool count, int n_cus, hipStream_t stream)
 {
     if (Pin.n_rays <= Pin.ray_first) return hipSuccess;
     if (HG && (Pin.tail_mode || Pin.tail_pool)) return hipErrorInvalidValue;
+    if (GG && (!adjoint || count || !Pin.L_out)) return hipErrorInvalidValue;
     size_t lds = 0;
     bool mg = false;
     const uint32_t nray = sq_rays_for(Pin, &lds, &mg);
@@ -1671,7 +1717,7 @@ static hipError_t launch_trace_sq_t(const Params &Pin, bool adjoint, bool count,
                                               else DRT_SQ_LAUNCH_R(A, C, E, M, Q, T, false); } while (0)
 #define DRT_SQ_LAUNCH_R(A, C, E, M, Q, T, R)                                                                         \
     do {                                                                                                          \
-        auto kern = trace_sq_kernel<A, C, E, M, Q, (T) && !HG, (R) && !HG, HG>;                                   \
+        auto kern = trace_sq_kernel<A, C, E, M, Q, (T) && !HG, (R) && !HG, HG, (A) && !(C) && GG>;               \
         static std::atomic<size_t> lds_set[64];                                                                        \
         int dev_ = 0;                                                                                             \
         if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) dev_ = 63;                               \
@@ -1709,6 +1755,11 @@ hipError_t launch_trace_sq(const Params &P, bool adjoint, bool count, int n_cus,
 hipError_t launch_trace_sq_hg(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream)
 {
     return launch_trace_sq_t<true>(P, adjoint, count, n_cus, stream);
+}
+
+hipError_t launch_trace_sq_gg(const Params &P, int n_cus, hipStream_t stream)
+{
+    return launch_trace_sq_t<true, true>(P, true, false, n_cus, stream);
 }
 #endif
 

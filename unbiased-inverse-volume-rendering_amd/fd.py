@@ -15,7 +15,7 @@ import torch
 
 from .image_io import write_image
 from .render import render_primal
-from .scene import ALBEDO_KEY, EMISSION_KEY, SIGMA_T_KEY, GridMedium, Scene
+from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, require_hg
 
 
 def _scene_with(scene: Scene, values: Dict[str, torch.Tensor]) -> Scene:
@@ -23,7 +23,7 @@ def _scene_with(scene: Scene, values: Dict[str, torch.Tensor]) -> Scene:
     medium = GridMedium(sigma_t=values.get(SIGMA_T_KEY, m.sigma_t), albedo=values.get(ALBEDO_KEY, m.albedo),
                         bbox_min=m.bbox_min, bbox_max=m.bbox_max, scale=m.scale,
                         majorant_resolution_factor=m.majorant_resolution_factor, emission=values.get(EMISSION_KEY, m.emission),
-                        phase=m.phase)
+                        phase=HGPhase(float(values[PHASE_G_KEY])) if PHASE_G_KEY in values else m.phase)
     return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
 
 
@@ -32,9 +32,12 @@ def fd_gradients(output_dir: Optional[str], scene: Scene, params: Dict[str, torc
                  central: bool = False) -> Dict[str, np.ndarray]:
     """python/fd.py:10-77.  `params`: {key: device grid (Z, Y, X, C)} - the entries to differentiate (they replace the
     scene's grids); `loss_fn(image)` with image (H, W, 3) -> scalar tensor.  Returns {key: array of d loss / d entry}.
-    `central=True` uses (loss(+eps) - loss(-eps)) / (2 eps) instead of the reference's forward difference."""
+    `central=True` uses (loss(+eps) - loss(-eps)) / (2 eps) instead of the reference's forward difference.
+    PHASE_G_KEY: the asymmetry g of an HG medium, a 0-d tensor (the result is a 0-d array)."""
     if integrator is None:
         raise ValueError("fd_gradients needs the integrator to render with")
+    if PHASE_G_KEY in params:
+        require_hg(scene, "fd_gradients")
     s = scene.sensors[sensor]
 
     def loss_of(values, fname=None):
@@ -43,7 +46,8 @@ def fd_gradients(output_dir: Optional[str], scene: Scene, params: Dict[str, torc
             write_image(os.path.join(output_dir, fname), img)
         return float(loss_fn(img))
 
-    values = {k: v.detach().clone() for k, v in params.items()}
+    values = {k: (v.detach().clone() if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float32))
+              for k, v in params.items()}
     loss_center = loss_of(values, 'fd_center.pfm')
     results = {}
     for run_i, k in enumerate(values):

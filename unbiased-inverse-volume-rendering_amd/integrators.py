@@ -20,7 +20,7 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from ._native import native
-from .scene import ALBEDO_KEY, EMISSION_KEY, SIGMA_T_KEY, PerspectiveSensor, Scene, _check_phase
+from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, PerspectiveSensor, Scene, _check_phase, require_hg
 
 
 class ADMode(IntEnum):
@@ -114,6 +114,7 @@ class _DeviceIntegrator:
     sensor binding, box film helpers."""
 
     param_keys = (SIGMA_T_KEY, ALBEDO_KEY)       # the differentiable grids this integrator reads
+    phase_grad = False                           # differentiable with respect to the phase function's g (PHASE_G_KEY) as well
     needs_albedo = True
 
     def _native_props(self) -> dict:
@@ -169,7 +170,8 @@ class _DeviceIntegrator:
             tangents = {}
         if not isinstance(tangents, dict):
             raise TypeError("tangents must be a dict {parameter key: tensor}")
-        extra = sorted(set(tangents) - set(self.param_keys))
+        tg = tangents.get(PHASE_G_KEY)
+        extra = sorted(set(tangents) - set(self.param_keys) - {PHASE_G_KEY})
         if extra:
             raise ValueError(f"tangents for unknown parameters {extra} (this integrator's parameters: {list(self.param_keys)})")
         out = {}
@@ -179,7 +181,31 @@ class _DeviceIntegrator:
                 grid = _grid_of(scene, k)
                 _check(t, tuple(grid.shape), grid.device if isinstance(grid, torch.Tensor) else t.device, f"tangents['{k}']")
             out[k] = t
+        if tg is not None:                       # the g tangent: a number (a 0-d tensor is read to the host)
+            self._refuse_phase_grad(scene)
+            if isinstance(tg, torch.Tensor):
+                if tg.numel() != 1 or not tg.dtype.is_floating_point:
+                    raise TypeError(f"tangents['{PHASE_G_KEY}'] must be a number or a 1-element float tensor, got shape {tuple(tg.shape)} {tg.dtype}")
+                tg = tg.item()
+            out[PHASE_G_KEY] = float(tg)
         return out
+
+    def _refuse_phase_grad(self, scene: Scene):
+        if not self.phase_grad:
+            raise ValueError(f"the {self.__class__.__name__} has no gradient with respect to {PHASE_G_KEY} (only volpathsimple samples "
+                             "a phase function)")
+        require_hg(scene, self.__class__.__name__)
+
+    def _phase_grad_ptr(self, scene: Scene, grads: Dict[str, torch.Tensor], dev) -> int:
+        """The device address of grads[PHASE_G_KEY] (one float32, accumulated), or 0 when the g-gradient is not asked for."""
+        gg = grads.get(PHASE_G_KEY)
+        if gg is None:
+            return 0
+        self._refuse_phase_grad(scene)
+        _check(gg, None, dev, f"grads['{PHASE_G_KEY}']")
+        if gg.numel() != 1:
+            raise ValueError(f"grads['{PHASE_G_KEY}'] must hold one float, got shape {tuple(gg.shape)}")
+        return gg.data_ptr()
 
     def _colour_grid(self, scene: Scene):
         """The colour grid whose lattice the handle is told about (drt_set_colour_resolution): the albedo here, the emission for `nerf`."""
@@ -305,6 +331,7 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
     Assumptions inherited from the reference: no surfaces, a single medium inside a
     convex (here: axis-aligned box) boundary with a null BSDF, one infinite emitter.
     """
+    phase_grad = True
 
     def __init__(self, props: Optional[dict] = None):
         props = dict(props or {})
@@ -343,7 +370,9 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         parameters); returns (None, True, None).  Forward: state_in = the primal radiance of the
         same rays / seed, `tangents` = {key: tangent grid} (missing: zero); returns (dL, True, None)
         with dL [n,3] = J t per ray (drt_render_forward).  Extra kwargs (`depth`, `reparam`)
-        are absorbed like the reference does (volpathsimple.py:47)."""
+        are absorbed like the reference does (volpathsimple.py:47).
+        With an HG medium, grads[PHASE_G_KEY] (one float32 on the device, accumulated) receives dLoss/dg
+        and tangents[PHASE_G_KEY] (a number) adds t_g dL/dg to the forward result."""
         mode = ADMode(int(mode))
         if mode == ADMode.Forward:
             tangents = self.check_tangents(scene, tangents)
@@ -366,13 +395,23 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
             gs, ga = grads[SIGMA_T_KEY], grads[ALBEDO_KEY]
             _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
             _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
-            h.render_backward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-                              δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
+            gp = self._phase_grad_ptr(scene, grads, dev)
+            if gp:
+                h.render_backward_phase(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
+                                        δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gp)
+            else:
+                h.render_backward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
+                                  δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
             return None, True, None
         _check(state_in, (n, 3), dev, "state_in")
         dL = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        h.render_forward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
-                         _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr())
+        tg = tangents.get(PHASE_G_KEY)
+        if tg:
+            h.render_forward_phase(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
+                                   _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr(), tg)
+        else:
+            h.render_forward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
+                             _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr())
         return dL, True, None
 
     def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
@@ -387,8 +426,13 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         gs, ga = grads[SIGMA_T_KEY], grads[ALBEDO_KEY]
         _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
         _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
-        h.render_backward_px(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
-                             grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
+        gp = self._phase_grad_ptr(scene, grads, dev)
+        if gp:
+            h.render_backward_px_phase(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
+                                       grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gp)
+        else:
+            h.render_backward_px(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
+                                 grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
 
     def _native_props(self) -> dict:
         return self.props()
@@ -465,6 +509,8 @@ class NeRFIntegrator(_DeviceIntegrator):
         mode = ADMode(int(mode))
         if mode == ADMode.Forward:
             tangents = self.check_tangents(scene, tangents)
+        if grads is not None and grads.get(PHASE_G_KEY) is not None:
+            self._refuse_phase_grad(scene)
         h, dev = self._bind(scene)
         em = scene.medium.emission
         if not isinstance(em, torch.Tensor):
@@ -499,6 +545,8 @@ class NeRFIntegrator(_DeviceIntegrator):
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
         """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] in place of the per-ray δL
         (drt_nerf_render_backward_px)."""
+        if grads.get(PHASE_G_KEY) is not None:
+            self._refuse_phase_grad(scene)
         h, dev = self._bind(scene)
         em = scene.medium.emission
         _check(em, None, dev, "emission")
@@ -523,6 +571,8 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
     integrator, and the backward pass accumulates both integrators' gradients into the same two grids.
     Properties: those of `volpathsimple` plus the `nerf` ones (`queries_per_ray`, `jittering_enabled`,
     `activation`, `nerf_hide_emitters`)."""
+
+    phase_grad = False          # (the fused pass has no g-gradient kernels)
 
     def __init__(self, props: Optional[dict] = None):
         props = dict(props or {})
@@ -564,6 +614,8 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
         """-> (L [n, 6], valid, state_out); Backward: δL / state_in are [n, 6], gradients accumulate into
         grads[sigma_t] and grads[albedo] (= the colour grid: albedo and emission are one parameter)."""
         mode = ADMode(int(mode))
+        if (grads is not None and grads.get(PHASE_G_KEY) is not None) or (kwargs.get("tangents") or {}).get(PHASE_G_KEY) is not None:
+            self._refuse_phase_grad(scene)
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)

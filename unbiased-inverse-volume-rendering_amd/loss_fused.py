@@ -23,7 +23,7 @@ import torch
 from . import losses
 from .batched import sample_batch, sensors_to_device
 from .integrators import ADMode, FusedNerfDrtIntegrator, IndependentSampler, RayBatch, sample_tea_32
-from .render import _grid, _sensor_batch, _with_params, alloc_grads
+from .render import _grid, _sensor_batch, _with_params, alloc_grads, g_grad, grad_keys, phase_param
 
 # name -> (drt_loss_kind, keyword of its parameter, default of the parameter)
 LOSS_KINDS = {
@@ -126,8 +126,8 @@ class _LossRenderOp(torch.autograd.Function):
     """render + develop + loss; backward: grad-seed primal, film_loss_grad on the forward image, the pixel-gradient adjoint."""
 
     @staticmethod
-    def forward(ctx, p0, p1, scene, integrator, sensor, spp, spp_grad, seed, seed_grad, ref, kind, param):
-        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()))
+    def forward(ctx, p0, p1, g, scene, integrator, sensor, spp, spp_grad, seed, seed_grad, ref, kind, param):
+        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()), None if g is None else float(g.detach()))
         batch = _sensor_batch(sc, sensor, spp, None)
         L, _, _ = integrator.sample(ADMode.Primal, sc, IndependentSampler(seed, spp), batch)
         image, loss = integrator.develop_loss(sc, L, spp, ref, kind, param)
@@ -143,10 +143,11 @@ class _LossRenderOp(torch.autograd.Function):
         sampler = IndependentSampler(ctx.seed_grad, ctx.spp_grad)
         L, _, state = integ.sample(ADMode.Primal, sc, sampler.clone(), batch)
         grad_image = integ.loss_grad(sc, ctx.image, ctx.ref, ctx.kind, ctx.param, grad_loss.contiguous())
-        grads = alloc_grads(sc, integ.param_keys)
+        want_g = ctx.needs_input_grad[2]
+        grads = alloc_grads(sc, grad_keys(integ, want_g))
         integ.sample_backward_px(sc, sampler, batch, grad_image, state, grads)
         k0, k1 = integ.param_keys
-        return (grads[k0], grads[k1]) + (None,) * 10
+        return (grads[k0], grads[k1], g_grad(grads, want_g)) + (None,) * 10
 
 
 def render_loss(scene, ref_image, loss=losses.l1, params: Optional[Dict[str, torch.Tensor]] = None, integrator=None,
@@ -154,7 +155,8 @@ def render_loss(scene, ref_image, loss=losses.l1, params: Optional[Dict[str, tor
                 loss_args: Optional[dict] = None, shard=None):
     """`loss(render(scene, params, integrator, sensor, spp, spp_grad, seed, seed_grad), ref_image)` with the film, the loss and
     its gradient fused on the device.  -> (loss 0-d, differentiable with respect to the integrator's `param_keys`;
-    image [n_pixels, 3], detached).  `ref_image`: (H, W, 3) or [n_pixels, 3] on the parameters' device."""
+    image [n_pixels, 3], detached).  `ref_image`: (H, W, 3) or [n_pixels, 3] on the parameters' device.  `params[PHASE_G_KEY]`:
+    the HG asymmetry g as in `render`."""
     what = "render_loss"
     _check_integrator(integrator, what)
     _check_shard(shard, what)
@@ -167,14 +169,15 @@ def render_loss(scene, ref_image, loss=losses.l1, params: Optional[Dict[str, tor
     dense = _ref_tensor(ref_image, params[keys[0]].device, "ref_image").reshape(-1, 3)
     if dense.shape[0] != n_pix:
         raise ValueError(f"{what}: ref_image holds {dense.shape[0]} pixels, the sensor {n_pix}")
-    return _LossRenderOp.apply(params[keys[0]], params[keys[1]], scene, integrator, int(sensor), int(spp), spp_grad, int(seed),
+    g = phase_param(scene, integrator, params, params[keys[0]].device)
+    return _LossRenderOp.apply(params[keys[0]], params[keys[1]], g, scene, integrator, int(sensor), int(spp), spp_grad, int(seed),
                                seed_grad, LossRef(dense=dense), kind, param)
 
 
 class _BatchedLossRenderOp(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, p0, p1, scene, integrator, sensor_table, ref_images, batch_size, spp, spp_grad, seed, seed_grad, kind, param):
-        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()))
+    def forward(ctx, p0, p1, g, scene, integrator, sensor_table, ref_images, batch_size, spp, spp_grad, seed, seed_grad, kind, param):
+        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()), None if g is None else float(g.detach()))
         ro, rd, sidx, pix = sample_batch(integrator, sc, sensor_table, batch_size, spp, seed, 1)
         batch = RayBatch(n_rays=batch_size * spp, spp=spp, o=ro, d=rd)
         L, _, _ = integrator.sample(ADMode.Primal, sc, IndependentSampler(seed, spp), batch)
@@ -193,10 +196,11 @@ class _BatchedLossRenderOp(torch.autograd.Function):
         sampler = IndependentSampler(ctx.seed_grad, ctx.spp_grad)
         L, _, state = integ.sample(ADMode.Primal, sc, sampler.clone(), batch)
         grad_image = integ.loss_grad(sc, ctx.image, ctx.ref, ctx.kind, ctx.param, grad_loss.contiguous())
-        grads = alloc_grads(sc, integ.param_keys)
+        want_g = ctx.needs_input_grad[2]
+        grads = alloc_grads(sc, grad_keys(integ, want_g))
         integ.sample_backward_px(sc, sampler, batch, grad_image, state, grads)
         k0, k1 = integ.param_keys
-        return (grads[k0], grads[k1]) + (None,) * 11
+        return (grads[k0], grads[k1], g_grad(grads, want_g)) + (None,) * 11
 
 
 def render_batch_loss(batch_size: int, scene, ref_images, loss=losses.l1, sensors=None,
@@ -205,7 +209,7 @@ def render_batch_loss(batch_size: int, scene, ref_images, loss=losses.l1, sensor
                       loss_args: Optional[dict] = None, shard=None):
     """`loss(render_batch(...)[0], gather_ref_values(ref_images, sensor_idx, pixel_idx))` with the gather, the film, the loss and
     its gradient fused on the device.  -> (loss 0-d, image [batch_size, 3] detached, sensor_idx, pixel_idx).
-    `ref_images`: (n_sensors, H, W, 3|4), one image per sensor of `sensors`."""
+    `ref_images`: (n_sensors, H, W, 3|4), one image per sensor of `sensors`.  `params[PHASE_G_KEY]`: the HG asymmetry g as in `render`."""
     what = "render_batch_loss"
     _check_integrator(integrator, what)
     _check_shard(shard, what)
@@ -223,8 +227,9 @@ def render_batch_loss(batch_size: int, scene, ref_images, loss=losses.l1, sensor
     if (ref_images.shape[0], ref_images.shape[1], ref_images.shape[2]) != (len(sensors), sensors[0].height, sensors[0].width):
         raise ValueError(f"{what}: ref_images of shape {tuple(ref_images.shape)} do not match {len(sensors)} sensors of "
                          f"{sensors[0].width}x{sensors[0].height}")
+    g = phase_param(scene, integrator, params, dev)
     if sensor_table is None:
         sensor_table = sensors_to_device(sensors, dev)
-    loss_v, image, sidx, pix = _BatchedLossRenderOp.apply(params[keys[0]], params[keys[1]], scene, integrator, sensor_table, ref_images,
+    loss_v, image, sidx, pix = _BatchedLossRenderOp.apply(params[keys[0]], params[keys[1]], g, scene, integrator, sensor_table, ref_images,
                                                           int(batch_size), int(spp), spp_grad, int(seed), seed_grad, kind, param)
     return loss_v, image, sidx, pix

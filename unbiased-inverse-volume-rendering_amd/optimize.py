@@ -21,7 +21,7 @@ from .integrators import sample_tea_32
 from .loss_fused import render_batch_loss, render_loss, resolve_loss
 from .opt_config import get_int_config
 from .render import render, render_primal
-from .scene import ALBEDO_KEY, EMISSION_KEY, SIGMA_T_KEY, GridMedium, Scene
+from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, require_hg
 from .image_io import read_image, write_image
 from .volume_io import write_vol
 
@@ -172,7 +172,7 @@ class Adam:
             t += 1
             lr = self.lr.get(k, self.lr_default)
             lr_t = lr * (1 - self.beta_2 ** t) ** 0.5 / (1 - self.beta_1 ** t)
-            if _fused_adam_ok(p, g, m, v):
+            if k != PHASE_G_KEY and _fused_adam_ok(p, g, m, v):     # (the scalar g takes the torch ops: the kernel is for grids)
                 # one fused pass on the device (drt_adam_step) instead of seven elementwise kernels
                 from ._native import native
                 with torch.cuda.device(p.device):
@@ -205,6 +205,9 @@ class SGD(Adam):
         return set()
 
 
+PHASE_G_LIMIT = 0.99      # |g| of an optimised HG asymmetry: HGPhase needs |g| < 1, and the phase function degenerates towards it
+
+
 def param_bounds(scene_config: SceneConfig, keys) -> Dict[str, tuple]:
     """The valid range of each parameter (optimize.py:169-179), (lo, hi) with None = open."""
     out = {}
@@ -215,6 +218,8 @@ def param_bounds(scene_config: SceneConfig, keys) -> Dict[str, tuple]:
             out[k] = (0.0, None)
         elif k.endswith('albedo.data'):
             out[k] = (0.0, 1.0)
+        elif k == PHASE_G_KEY:
+            out[k] = (-PHASE_G_LIMIT, PHASE_G_LIMIT)
     return out
 
 
@@ -230,6 +235,8 @@ def enforce_valid_params(scene_config: SceneConfig, opt, skip=()) -> None:
             v.clamp_(min=0)
         elif k.endswith('albedo.data'):
             v.clamp_(0, 1)
+        elif k == PHASE_G_KEY:
+            v.clamp_(-PHASE_G_LIMIT, PHASE_G_LIMIT)
         else:
             raise ValueError(k)
 
@@ -264,6 +271,10 @@ def save_params(output_dir: str, scene_config: SceneConfig, params: Dict[str, to
     """python/util.py:55-71: one `.vol` per parameter, `<name>-medium1_sigma_t.vol`."""
     os.makedirs(output_dir, exist_ok=True)                            # util.py:57 (create_checkpoint always does)
     for key in scene_config.param_keys:
+        if key == PHASE_G_KEY:                                        # a scalar: one line of text, `<name>-medium1_phase_function_g.txt`
+            with open(os.path.join(output_dir, f'{name}-medium1_phase_function_g.txt'), 'w') as f:
+                f.write(f'{float(params[key]):.9g}\n')
+            continue
         if not key.endswith('.data'):
             raise NotImplementedError(f'Checkpointing of parameter {key}')
         var_name = '_'.join(key[:-len('.data')].strip().split('.'))
@@ -358,6 +369,17 @@ def _scene_with(scene: Scene, params: Dict[str, torch.Tensor], factor: int) -> S
     return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
 
 
+def _scene_at_g(scene: Scene, params: Dict[str, torch.Tensor]) -> Scene:
+    """`scene` with the optimised HG asymmetry params[PHASE_G_KEY] (read to the host), or `scene` itself when g is not optimised."""
+    if PHASE_G_KEY not in params:
+        return scene
+    m = scene.medium
+    medium = GridMedium(sigma_t=m.sigma_t, albedo=m.albedo, bbox_min=m.bbox_min, bbox_max=m.bbox_max, scale=m.scale,
+                        majorant_resolution_factor=m.majorant_resolution_factor, emission=m.emission,
+                        phase=HGPhase(float(params[PHASE_G_KEY])))
+    return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
+
+
 def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, scene_config: SceneConfig,
                      int_config, ref_images: Optional[torch.Tensor] = None, progress: Optional[Callable] = None,
                      shard=None):
@@ -368,6 +390,9 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     `scene_config.param_keys` may be any subset / superset of the integrator's keys (the reference's configs
     list sigma_t, albedo AND emission whatever the integrator, scene_config.py:148): keys the integrator does
     not read simply receive no gradient, keys it reads but that are not optimised are taken from the scene.
+    PHASE_G_KEY optimises the HG asymmetry g of a medium with `HGPhase` (volpathsimple only), starting from
+    `start_from_value[PHASE_G_KEY]` (None: the scene's g), clamped to |g| <= 0.99 after each step.  Its cost: every
+    render reads the new g to the host once (the handle takes g by value), one device synchronisation per iteration.
 
     `shard` (a `ShardSpec` with world > 1, one process per GPU): the batch / the image pixels of every
     iteration are dealt across the ranks, the local loss is scaled to its share of the global loss and the
@@ -410,6 +435,10 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     dev = scene0.medium.sigma_t.device
     integrator = int_config.create(max_depth=scene_config.max_depth)
     keys = list(scene_config.param_keys)
+    grid_keys = [k for k in keys if k != PHASE_G_KEY]
+    if PHASE_G_KEY in keys:
+        require_hg(scene0, "run_optimization")
+        integrator._refuse_phase_grad(scene0)                           # (nerf has no phase function)
     sensors = [scene0.sensors[i] for i in scene_config.sensors]
     n_sensors = len(sensors)
     film = (sensors[0].width, sensors[0].height)
@@ -435,7 +464,13 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     base_res = tuple(scene0.medium.sigma_t.shape[:3])
     n_up = len(opt_config.upsample) if opt_config.upsample else 0
     params: Dict[str, torch.Tensor] = {}
-    for k in keys:
+    if PHASE_G_KEY in keys:
+        v = scene_config.start_from_value[PHASE_G_KEY]
+        v = scene0.medium.phase.g if v is None else float(v)
+        if not abs(v) <= PHASE_G_LIMIT:
+            raise ValueError(f'start value of "{PHASE_G_KEY}" must satisfy |g| <= {PHASE_G_LIMIT}, got {v}')
+        params[PHASE_G_KEY] = torch.tensor(v, dtype=torch.float32, device=dev)
+    for k in grid_keys:
         if k not in full:
             raise ValueError(f'Unknown parameter key "{k}" (known: {sorted(full)})')
         channels = 1 if k == SIGMA_T_KEY else 3
@@ -477,7 +512,7 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     if writer and opt_config.checkpoint_initial:
         save_params(os.path.join(output_dir, 'params'), scene_config, params, 'initial', scene.medium)
     if writer:
-        render_previews(output_dir, opt_config, scene_config, scene, integrator, 'initial')   # optimize.py:320
+        render_previews(output_dir, opt_config, scene_config, _scene_at_g(scene, params), integrator, 'initial')   # optimize.py:320
         for s in scene_config.preview_sensors:                         # the matching references, for comparison (:321-324)
             if s in scene_config.sensors:
                 write_image(os.path.join(output_dir, f'ref_{s:04d}{IMAGE_EXT}'), ref_images[scene_config.sensors.index(s)])
@@ -489,7 +524,7 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         seed_grad = sample_tea_32(2 * it_i + 1, opt_config.base_seed)[0]
         opt.set_learning_rate(opt_config.learning_rates(scene_config, it_i))
         if opt_config.should_upsample(it_i):                           # optimize.py:228-252
-            for k in keys:
+            for k in grid_keys:
                 old = opt[k]
                 new_res = tuple(2 * r for r in old.shape[:3]) + (old.shape[-1],)
                 opt[k] = upsample_grid(old, new_res)
@@ -500,6 +535,8 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         # leaves: what the integrator differentiates; only the optimised ones require (and receive) gradients
         leaves = {k: (params[k].detach().requires_grad_(True) if k in params else grids[k].detach())
                   for k in integrator.param_keys}
+        if PHASE_G_KEY in params:
+            leaves[PHASE_G_KEY] = params[PHASE_G_KEY].detach().requires_grad_(True)
         if opt_config.fused_loss and opt_config.batch_size is not None:   # the same step, film + loss + gather fused (loss_fused.py)
             loss_value, image, _, _ = render_batch_loss(
                 opt_config.batch_size, scene, ref_images, loss=opt_config.loss, sensors=sensors, params=leaves, integrator=integrator,
@@ -540,12 +577,13 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         if writer and it_i > 0 and opt_config.checkpoint_stride and it_i % opt_config.checkpoint_stride == 0:
             save_params(os.path.join(output_dir, 'params'), scene_config, params, f'{it_i:08d}', scene.medium)
         if writer and it_i > 0 and opt_config.preview_stride and it_i % opt_config.preview_stride == 0:   # :357-358
-            render_previews(output_dir, opt_config, scene_config, scene, integrator, it_i)
+            render_previews(output_dir, opt_config, scene_config, _scene_at_g(scene, params), integrator, it_i)
         if progress:
             progress(it_i, history[-1])
     if shard.partitioned:
         # the packed all-reduce of the last backward pass left its check to "the next call": this is it (raised, never silent)
         verify_pending()
+    scene = _scene_at_g(scene, params)                                 # the scene returned (and previewed) carries the optimised g
     if writer and opt_config.checkpoint_final:
         save_params(os.path.join(output_dir, 'params'), scene_config, params, 'final', scene.medium)
     if writer:

@@ -20,9 +20,9 @@ from typing import Dict, Optional
 
 import torch
 
-from .distributed import ShardSpec, allreduce_gradients, gradient_support
+from .distributed import COMPACT_BLOCK_FLOATS, ShardSpec, allreduce_gradients, gradient_support
 from .integrators import ADMode, IndependentSampler, RayBatch, sample_tea_32
-from .scene import ALBEDO_KEY, EMISSION_KEY, SIGMA_T_KEY, GridMedium, Scene
+from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, check_phase_g
 
 
 def _grid(scene: Scene, key: str):
@@ -36,15 +36,25 @@ def alloc_grads(scene: Scene, keys=(SIGMA_T_KEY, ALBEDO_KEY)) -> Dict[str, torch
     collective.  (A fresh buffer per backward: autograd hands these tensors out as `.grad`, so they cannot
     be pooled; the cost is one caching-allocator hit plus a 256 MiB memset = 0.05 ms at 256^3, and the
     benchmark's step pays the same memset.)"""
+    want_g = PHASE_G_KEY in keys
+    keys = [k for k in keys if k != PHASE_G_KEY]
     grids = [_grid(scene, k) for k in keys]
     # every grid starts at a multiple of 4 floats: its view is 16-byte aligned whatever the voxel counts (the fused Adam
     # step and the block-mask kernel read float4s); the up to 3 padding floats per grid stay zero
     pad = lambda n: (n + 3) // 4 * 4
-    flat = torch.zeros(sum(pad(g.numel()) for g in grids), dtype=torch.float32, device=grids[0].device)
+    size = sum(pad(g.numel()) for g in grids)
+    # PHASE_G_KEY: one more slot behind the grids (a 0-d view), in a compaction block of its own - never inside a grid's block, so the
+    # packed all-reduce always carries it (distributed.gradient_support marks every block that is not wholly inside a sparse plane)
+    g_off = (size + COMPACT_BLOCK_FLOATS - 1) // COMPACT_BLOCK_FLOATS * COMPACT_BLOCK_FLOATS
+    if want_g:
+        size = g_off + COMPACT_BLOCK_FLOATS
+    flat = torch.zeros(size, dtype=torch.float32, device=grids[0].device)
     out, off = {"_flat": flat}, 0
     for k, g in zip(keys, grids):
         out[k] = flat[off:off + g.numel()].view(g.shape)
         off += pad(g.numel())
+    if want_g:
+        out[PHASE_G_KEY] = flat[g_off:g_off + 1].view(())
     return out
 
 
@@ -61,13 +71,13 @@ def sharded_support(scene: Scene, grads: Dict[str, torch.Tensor], shard: Optiona
     return gradient_support(scene.medium.sigma_t, grads, sparse_keys=(ALBEDO_KEY,))
 
 
-def _with_params(scene: Scene, keys, tensors) -> Scene:
+def _with_params(scene: Scene, keys, tensors, phase_g: Optional[float] = None) -> Scene:
     m = scene.medium
     vals = {SIGMA_T_KEY: m.sigma_t, ALBEDO_KEY: m.albedo, EMISSION_KEY: m.emission}
     vals.update(dict(zip(keys, tensors)))
     medium = GridMedium(sigma_t=vals[SIGMA_T_KEY], albedo=vals[ALBEDO_KEY], bbox_min=m.bbox_min, bbox_max=m.bbox_max,
                         scale=m.scale, majorant_resolution_factor=m.majorant_resolution_factor,
-                        emission=vals[EMISSION_KEY], phase=m.phase)
+                        emission=vals[EMISSION_KEY], phase=m.phase if phase_g is None else HGPhase(phase_g))
     return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
 
 
@@ -92,7 +102,7 @@ def render_primal(scene: Scene, integrator, sensor: int = 0, spp: int = 1, seed:
 def render_backward(scene: Scene, integrator, grad_image: torch.Tensor, sensor: int = 0,
                     spp: int = 1, seed: int = 0, shard: Optional[ShardSpec] = None,
                     grads: Optional[Dict[str, torch.Tensor]] = None,
-                    allreduce: bool = True, strict: Optional[bool] = True) -> Dict[str, torch.Tensor]:
+                    allreduce: bool = True, strict: Optional[bool] = True, keys=None) -> Dict[str, torch.Tensor]:
     """The H1 sequence (batched.py:212-326) for the local pixels; returns the
     gradient grids - summed over all ranks when the pixels were dealt across a process group
     (`shard.world > 1`); an unsharded call never communicates.  For the sum to be the gradient of
@@ -100,13 +110,15 @@ def render_backward(scene: Scene, integrator, grad_image: torch.Tensor, sensor: 
     pixels (a mean over the local pixels only over-scales it by `world`: use
     `distributed.local_loss_scale`).  `strict` (sharded calls): True - the check of the packed all-reduce is looked at before this
     call returns (a one-off call has no next call that would look); False / None - it is left to the next backward pass or
-    `distributed.verify_pending()` (the autograd ops inside an optimisation loop, which ends with `verify_pending`)."""
+    `distributed.verify_pending()` (the autograd ops inside an optimisation loop, which ends with `verify_pending`).
+    `keys`: the gradients to allocate when `grads` is None (default: integrator.param_keys); with PHASE_G_KEY among them (or in
+    `grads`) the result also holds dLoss/dg of an HG medium, a 0-d view of the same flat buffer (one collective when sharded)."""
     batch = _sensor_batch(scene, sensor, spp, shard)
     sampler = IndependentSampler(seed, spp)
     L, _, state_out = integrator.sample(ADMode.Primal, scene, sampler.clone(), batch)     # :255-264
     dL = integrator.film_backward(scene, grad_image, spp)                                  # :272-306
     if grads is None:
-        grads = alloc_grads(scene, integrator.param_keys)
+        grads = alloc_grads(scene, integrator.param_keys if keys is None else tuple(keys))
     support = sharded_support(scene, grads, shard) if allreduce else None
     integrator.sample(ADMode.Backward, scene, sampler, batch, δL=dL, state_in=state_out,  # :309-318
                       grads=grads)
@@ -118,7 +130,8 @@ def render_backward(scene: Scene, integrator, grad_image: torch.Tensor, sensor: 
 def render_forward(scene: Scene, integrator, tangents: Optional[Dict[str, torch.Tensor]], sensor: int = 0, spp: int = 1,
                    seed: int = 0, shard: Optional[ShardSpec] = None) -> torch.Tensor:
     """Forward-mode derivative image of the local pixels, [n_local_pixels, 3]: J·t for the tangents `tangents`
-    ({key of integrator.param_keys: tensor shaped like that grid}; a missing key or None is a zero tangent).  The primal
+    ({key of integrator.param_keys: tensor shaped like that grid, PHASE_G_KEY: a number for an HG medium}; a missing key or None
+    is a zero tangent).  The primal
     pass at (seed, spp) gives the tangent pass its state_in; both trace the same paths, and the film develops the per-ray
     tangents with its summation order.  For any image gradient g, <g, render_forward(t)> equals <render_backward(g), t> at
     the same seed and spp up to float summation order.  A sharded call returns its local pixels and never communicates."""
@@ -157,13 +170,60 @@ class _RenderOp(torch.autograd.Function):
         return render_forward(ctx.scene, ctx.integrator, tangents, ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard)
 
 
+def phase_param(scene: Scene, integrator, params: Dict[str, torch.Tensor], device):
+    """params[PHASE_G_KEY], checked (volpathsimple, an HG medium, a 0-d float32 tensor on `device`), or None when absent."""
+    if params.get(PHASE_G_KEY) is None:
+        return None
+    integrator._refuse_phase_grad(scene)
+    return check_phase_g(params[PHASE_G_KEY], device)
+
+
+def grad_keys(integrator, want_g: bool):
+    """The gradients a backward pass allocates: the integrator's grids, and the g slot when g requires grad."""
+    return tuple(integrator.param_keys) + ((PHASE_G_KEY,) if want_g else ())
+
+
+def g_grad(grads: Dict[str, torch.Tensor], want_g: bool):
+    """The g-gradient an autograd op returns: a copy of the 0-d slot, so that `g.grad` does not keep the flat gradient buffer alive."""
+    return grads[PHASE_G_KEY].clone() if want_g else None
+
+
+class _RenderOpG(torch.autograd.Function):
+    """_RenderOp with the Henyey-Greenstein asymmetry g (PHASE_G_KEY) as a third input: a 0-d device tensor, read to the host once
+    per call (the handle takes g by value)."""
+
+    @staticmethod
+    def forward(ctx, p0, p1, g, scene, integrator, sensor, spp, spp_grad, seed, seed_grad, shard):
+        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()), float(g.detach()))
+        ctx.scene, ctx.integrator, ctx.sensor = sc, integrator, sensor
+        ctx.spp_grad, ctx.seed_grad, ctx.shard = spp_grad, seed_grad, shard
+        return render_primal(sc, integrator, sensor, spp, seed, shard)
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        k0, k1 = ctx.integrator.param_keys
+        want_g = ctx.needs_input_grad[2]
+        gr = render_backward(ctx.scene, ctx.integrator, grad_image.contiguous(), ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard,
+                             strict=False, keys=grad_keys(ctx.integrator, want_g))
+        return gr[k0], gr[k1], g_grad(gr, want_g), None, None, None, None, None, None, None, None
+
+    @staticmethod
+    def jvp(ctx, t0, t1, tg, *_):
+        k0, k1 = ctx.integrator.param_keys
+        tangents = {k: (t.contiguous() if t is not None else None) for k, t in ((k0, t0), (k1, t1))}
+        tangents[PHASE_G_KEY] = tg                 # (read to the host by check_tangents)
+        return render_forward(ctx.scene, ctx.integrator, tangents, ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard)
+
+
 def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integrator=None,
            sensor: int = 0, spp: int = 1, spp_grad: int = 0, seed: int = 0, seed_grad: int = 0,
            shard: Optional[ShardSpec] = None) -> torch.Tensor:
     """`mi.render`: image of the local pixels, [n_local_pixels, 3] (the whole image,
     row-major, when unsharded - reshape to (H, W, 3)).  Differentiable with respect to
     the integrator's `param_keys` (sigma_t + albedo for `volpathsimple`, sigma_t + emission
-    for `nerf`), in reverse mode and - dual tensors of `torch.autograd.forward_ad` - in forward mode."""
+    for `nerf`), in reverse mode and - dual tensors of `torch.autograd.forward_ad` - in forward mode.  With
+    `params[PHASE_G_KEY] = g` (a 0-d float32 device tensor; volpathsimple and a medium with `HGPhase`) the image is rendered
+    with that g, which overrides `medium.phase.g`, and is differentiable with respect to it as well."""
     if integrator is None:
         raise ValueError("render: an integrator is required")
     if spp_grad == 0:
@@ -181,5 +241,9 @@ def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integ
         if not isinstance(params[k], torch.Tensor):
             raise TypeError(f"render: params['{k}'] must be a torch device tensor "
                             "(the DRT integrator has no CPU path; use scene_to(scene, device))")
+    g = phase_param(scene, integrator, params, params[keys[0]].device)
+    if g is not None:
+        return _RenderOpG.apply(params[keys[0]], params[keys[1]], g, scene, integrator, sensor,
+                                int(spp), int(spp_grad), int(seed), int(seed_grad), shard)
     return _RenderOp.apply(params[keys[0]], params[keys[1]], scene, integrator, sensor,
                            int(spp), int(spp_grad), int(seed), int(seed_grad), shard)

@@ -20,6 +20,9 @@ import numpy as np
 SIGMA_T_KEY = "medium1.sigma_t.data"
 ALBEDO_KEY = "medium1.albedo.data"
 EMISSION_KEY = "medium1.emission.data"
+# the Henyey-Greenstein asymmetry of the medium's phase function (`mi.traverse`: medium1.phase_function.g) - a 0-d float32 device tensor in
+# render(params=...), never one of an integrator's `param_keys` (those are the grids)
+PHASE_G_KEY = "medium1.phase_function.g"
 
 
 def _normalize(v):
@@ -106,7 +109,8 @@ class IsotropicPhase:
 class HGPhase:
     """Mitsuba's `hg` phase function (src/phase/hg.cpp): Henyey-Greenstein with asymmetry `g`, finite with |g| < 1;
     g > 0 scatters forward.  `<phase type="hg"><float name="g" value="0.8"/></phase>`, or `<medium>.phase_function.g` in
-    `mi.traverse`.  HG with g = 0 is its own warp, not the isotropic one (as in Mitsuba); no gradient with respect to g."""
+    `mi.traverse`.  HG with g = 0 is its own warp, not the isotropic one (as in Mitsuba).  Differentiable with respect to g
+    through `PHASE_G_KEY` (render(params=...), render_backward(keys=...), tangents of forward mode)."""
     g: float = 0.8
     kind = 1        # DRT_PHASE_HG
 
@@ -121,6 +125,25 @@ class HGPhase:
             warnings.warn(f"HGPhase(g={g}): for 0 < |g| < 1e-3 the published sampling formula loses its precision in float32 (directions off "
                           "unit length); use IsotropicPhase() or HGPhase(0.0) for an isotropic medium", RuntimeWarning, stacklevel=2)
         object.__setattr__(self, "g", g)
+
+
+def check_phase_g(g, device=None):
+    """A g parameter of render(params={PHASE_G_KEY: g}): a 0-d float32 tensor on the device (it may require grad)."""
+    import torch
+    if not isinstance(g, torch.Tensor):
+        raise TypeError(f"params['{PHASE_G_KEY}'] must be a 0-d float32 device tensor, got {type(g).__name__}")
+    if g.dtype != torch.float32 or g.dim() != 0:
+        raise TypeError(f"params['{PHASE_G_KEY}'] must be a 0-d float32 tensor, got dtype {g.dtype} and shape {tuple(g.shape)}")
+    if g.device.type == "cpu" or (device is not None and g.device != torch.device(device)):
+        raise ValueError(f"params['{PHASE_G_KEY}'] is on {g.device}: it must be on the scene's device" + (f" ({device})" if device is not None else ""))
+    return g
+
+
+def require_hg(scene, what: str):
+    """The g-gradient needs a medium with the Henyey-Greenstein phase function."""
+    if not isinstance(scene.medium.phase, HGPhase):
+        raise ValueError(f"{what}: a gradient with respect to {PHASE_G_KEY} needs GridMedium(phase=HGPhase(g)); the medium's phase "
+                         f"function is {type(scene.medium.phase).__name__} - use HGPhase(0.0) for an isotropic medium whose g is optimised")
 
 
 def _check_phase(phase):
