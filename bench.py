@@ -7,13 +7,19 @@ over the whole image: primal tracing kernel -> box film -> loss gradient
 (consumes the stored primal radiance as state_in) [-> one all-reduce of the
 gradient grids when N > 1].  One *sample* = one camera ray (pixel x spp).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line (see the keys below); `ms_per_step` is the wall time of
 one of the K timed steps.  Inputs (the synthetic 256^3 dust-devil grids, seeded) are
 resident in HBM before the timed region starts.  --dump-outputs DIR writes the last
 timed step's image and gradient grids as .npy files (dump_outputs).
+
+A plain run sets up, warms up, times the K steps, dumps and prints: nothing else.  --full
+adds, after the timed steps, the measurements the headline figure does not need: the
+event counters of one more step and the HBM roofline they price, the CPU baseline and
+the other BASELINE configurations (`roofline`, `counters_*`, `cpu_baseline`,
+`other_configs`; null in a plain run).
 """
 import argparse
 import json
@@ -605,11 +611,16 @@ def main():
     ap.add_argument("--integrator", default="volpathsimple-drt")
     ap.add_argument("--majorant-factor", type=int, default=8,
                     help="majorant_resolution_factor of the medium (reference scenes: 8, scene_config.py:36; 0 = global majorant)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the event counters of one "
+                         "more step and the roofline they price (`roofline`, `counters_*`), the CPU baseline (`cpu_baseline`) and "
+                         "the other BASELINE configurations (`other_configs`); without it those fields are null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="skip the other BASELINE configurations (reported under `other_configs`, outside the timed loop)")
+                    help="with --full: skip the other BASELINE configurations (reported under `other_configs`, outside the timed loop)")
     ap.add_argument("--only-config", default=None,
-                    help="run ONE entry of other_configs and print it (counter passes of a single configuration under rocprofv3)")
+                    help="run ONE entry of other_configs and print it, instead of the headline line "
+                         "(counter passes of a single configuration under rocprofv3)")
     ap.add_argument("--cpu-spp", type=int, default=0, help="spp of the bounded CPU sample (0 = auto)")
     ap.add_argument("--debug-flags", type=int, default=0, help="profiling ablations (drt_set_debug_flags); invalidates the result")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -721,60 +732,60 @@ def main():
     elapsed = float(el.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = n_total * args.steps / elapsed / 1e6
-
-    # ---- event counts of ONE step (deterministic; outside the timed region) ------------
-    h.enable_counters(True)
-    seed_c = u.sample_tea_32(2 * args.warmup + 1, seed_base)[0]
-    sampler = u.IndependentSampler(seed_c, spp)
-    h.reset_counters()
-    L, _, state = integ.sample(u.ADMode.Primal, scene, sampler.clone(), batch)
-    cnt_p = {k: int(v) for k, v in h.get_counters().items()}
-    img = integ.develop(scene, L, spp)
-    dL = integ.film_backward(scene, loss_scale * (img - 0.5), spp)
-    h.reset_counters()
-    grads["_flat"].zero_()
-    integ.sample(u.ADMode.Backward, scene, sampler, batch, δL=dL, state_in=state, grads=grads)
-    cnt_a = {k: int(v) for k, v in h.get_counters().items()}
-    h.enable_counters(False)
-    n_local = batch.n_rays
-    bytes_p = algorithmic_bytes(cnt_p, n_local, primal_io=True, adjoint_io=False) - 24 * n_local  # rays generated on device
-    bytes_a = algorithmic_bytes(cnt_a, n_local, primal_io=False, adjoint_io=True)
-    avg_p = sum(t_primal) / max(1, len(t_primal))
-    avg_a = sum(t_adjoint) / max(1, len(t_adjoint))
-    avg_r = sum(t_untile) / max(1, len(t_untile))
-    # the adjoint's splats are finished by the gradient reduction that follows the tracer (record
-    # partition + LDS tile reduction, or the apron-scratch reduction): price the pass as a whole
+    # HIP-event times of the timed steps' launches.  The adjoint's splats are finished by the gradient reduction that
+    # follows the tracer (record partition + LDS tile reduction, or the apron-scratch reduction): price the pass as a whole
     # (sub-batches are pipelined over two streams, so the pass is timed as a whole on the launch stream;
     # tracer / reduction times are sums over the sub-batch launches of one step)
+    avg_p = sum(t_primal) / max(1, len(t_primal))
     per_step = max(1, len(t_pass))
     avg_a = sum(t_adjoint) / per_step
     avg_r = sum(t_untile) / per_step
     avg_pass = sum(t_pass) / per_step
-    ach_a = bytes_a / (avg_pass * 1e-3) / 1e9 if avg_pass > 0 else 0.0
-    ach_p = bytes_p / (avg_p * 1e-3) / 1e9 if avg_p > 0 else 0.0
-    # HBM-side traffic of the adjoint pass: a hardware-counter figure (rocprofv3 --pmc passes, tools/pmc_to_traffic.py) that
-    # this run cannot measure itself.  The committed profile is quoted ONLY if it was taken from the very kernel sources
-    # this run executes (hash over csrc/ + include/, recorded by tools/pmc_to_traffic.py); otherwise the field is null.
-    traffic, traffic_source = committed_traffic(f"{args.workload}-{args.res}-{args.film}x{spp}" +
-                                                (f"-factor{args.majorant_factor}" if args.majorant_factor else ""))
-    roofline = {
-        "bound": "hbm", "kernel": ("adjoint pass (sample(Backward)): " + ("trace_sq_kernel<adjoint>" if args.majorant_factor else "trace_coop_kernel<adjoint>") + " (dominant, sum_tracer_ms) + record partition + tile_reduce"),
-        "achieved": round(ach_a, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": round(ach_a / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
-        # what actually binds the pass (SURVEY.md 8d "secondary ceilings"): vector-instruction issue of the tracers (lanes
-        # active, VALU-busy) and the LDS-atomic rate of tile_reduce; from the committed counter pass, hash-gated like `traffic`
-        "secondary": committed_secondary(f"{args.workload}-{args.res}-{args.film}x{spp}" +
-                                         (f"-factor{args.majorant_factor}" if args.majorant_factor else ""), cnt_a),
-        "algorithmic_bytes_per_launch": bytes_a, "avg_launch_ms": round(avg_pass, 4),
-        "sum_tracer_ms": round(avg_a, 4), "sum_reduction_ms": round(avg_r, 4),
-        "bytes_per_sample_h1": round((bytes_p + bytes_a) / n_local, 1),
-        "primal": {"achieved": round(ach_p, 2), "frac": round(ach_p / HBM_PEAK_GBS, 5),
-                   "algorithmic_bytes_per_launch": bytes_p, "avg_launch_ms": round(avg_p, 4)},
-    }
 
-    # ---- CPU baseline: the oracle (a port, NOT the reference's llvm_ad_rgb) ------------
+    # ---- --full: event counts of ONE more step (deterministic) and the roofline they price -----
+    cnt_p = cnt_a = roofline = None
+    if args.full:
+        h.enable_counters(True)
+        seed_c = u.sample_tea_32(2 * args.warmup + 1, seed_base)[0]
+        sampler = u.IndependentSampler(seed_c, spp)
+        h.reset_counters()
+        L, _, state = integ.sample(u.ADMode.Primal, scene, sampler.clone(), batch)
+        cnt_p = {k: int(v) for k, v in h.get_counters().items()}
+        img = integ.develop(scene, L, spp)
+        dL = integ.film_backward(scene, loss_scale * (img - 0.5), spp)
+        h.reset_counters()
+        grads["_flat"].zero_()
+        integ.sample(u.ADMode.Backward, scene, sampler, batch, δL=dL, state_in=state, grads=grads)
+        cnt_a = {k: int(v) for k, v in h.get_counters().items()}
+        h.enable_counters(False)
+        n_local = batch.n_rays
+        bytes_p = algorithmic_bytes(cnt_p, n_local, primal_io=True, adjoint_io=False) - 24 * n_local  # rays generated on device
+        bytes_a = algorithmic_bytes(cnt_a, n_local, primal_io=False, adjoint_io=True)
+        ach_a = bytes_a / (avg_pass * 1e-3) / 1e9 if avg_pass > 0 else 0.0
+        ach_p = bytes_p / (avg_p * 1e-3) / 1e9 if avg_p > 0 else 0.0
+        # HBM-side traffic of the adjoint pass: a hardware-counter figure (rocprofv3 --pmc passes, tools/pmc_to_traffic.py) that
+        # this run cannot measure itself.  The committed profile is quoted ONLY if it was taken from the very kernel sources
+        # this run executes (hash over csrc/ + include/, recorded by tools/pmc_to_traffic.py); otherwise the field is null.
+        traffic, traffic_source = committed_traffic(f"{args.workload}-{args.res}-{args.film}x{spp}" +
+                                                    (f"-factor{args.majorant_factor}" if args.majorant_factor else ""))
+        roofline = {
+            "bound": "hbm", "kernel": ("adjoint pass (sample(Backward)): " + ("trace_sq_kernel<adjoint>" if args.majorant_factor else "trace_coop_kernel<adjoint>") + " (dominant, sum_tracer_ms) + record partition + tile_reduce"),
+            "achieved": round(ach_a, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(ach_a / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
+            # what actually binds the pass (SURVEY.md 8d "secondary ceilings"): vector-instruction issue of the tracers (lanes
+            # active, VALU-busy) and the LDS-atomic rate of tile_reduce; from the committed counter pass, hash-gated like `traffic`
+            "secondary": committed_secondary(f"{args.workload}-{args.res}-{args.film}x{spp}" +
+                                             (f"-factor{args.majorant_factor}" if args.majorant_factor else ""), cnt_a),
+            "algorithmic_bytes_per_launch": bytes_a, "avg_launch_ms": round(avg_pass, 4),
+            "sum_tracer_ms": round(avg_a, 4), "sum_reduction_ms": round(avg_r, 4),
+            "bytes_per_sample_h1": round((bytes_p + bytes_a) / n_local, 1),
+            "primal": {"achieved": round(ach_p, 2), "frac": round(ach_p / HBM_PEAK_GBS, 5),
+                       "algorithmic_bytes_per_launch": bytes_p, "avg_launch_ms": round(avg_p, 4)},
+        }
+
+    # ---- --full: CPU baseline: the oracle (a port, NOT the reference's llvm_ad_rgb) ---------
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import binding as ob
         cores = os.cpu_count() or 1
         cpu_scene = u.Scene(medium=u.GridMedium(sigma_t=scene.medium.sigma_t.cpu().numpy(),
@@ -828,9 +839,9 @@ def main():
             "primal_pass_only": round(n_pixels * cpu_spp / dt_primal / 1e6, 4),
         }
 
-    # ---- the other BASELINE configurations (outside the timed loop; N = 1 only) ---------
+    # ---- --full: the other BASELINE configurations (outside the timed loop; N = 1 only) ----
     other = None
-    if rank == 0 and world == 1 and not args.no_extra_configs and args.workload == "dust-devil" and args.res == 256:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_configs and args.workload == "dust-devil" and args.res == 256:
         grads = L = state = img = dL = None          # free the headline buffers first
         torch.cuda.empty_cache()
         h.release_scratch()
@@ -872,10 +883,10 @@ def main():
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{args.workload} {args.res}^3 sigma_t+albedo, {sensor.width}x{sensor.height}x{spp}spp, "
                                    f"{args.integrator}, max_depth 64, majorant_resolution_factor {args.majorant_factor} "
-                                   f"({'the reference default, scene_config.py:36; the global majorant is reported under other_configs.headline_global_majorant' if args.majorant_factor == 8 else 'global majorant; the reference default 8 is reported under other_configs.headline_majorant_factor8'}), single sensor, "
+                                   f"({'the reference default, scene_config.py:36; with --full the global majorant is reported under other_configs.headline_global_majorant' if args.majorant_factor == 8 else 'global majorant; with --full the reference default 8 is reported under other_configs.headline_majorant_factor8'}), single sensor, "
                                    f"image tiles sharded over {world} GPU(s)",
                        "n_samples_per_step": n_total, "grid": [args.res] * 3, "film": [sensor.width, sensor.height],
                        "spp": spp, "integrator": args.integrator, "side": side},

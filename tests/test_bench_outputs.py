@@ -1,5 +1,6 @@
 """bench.py --dump-outputs: what the timed path computed in its last step, written as .npy files within a fixed budget,
-the same from run to run for the same arguments; --steps sets the number of timed steps."""
+the same from run to run for the same arguments; --steps sets the number of timed steps.  A plain run's line carries the
+headline figure alone; --full adds the counter step, the roofline and the CPU baseline after the timed steps."""
 import json
 import os
 import subprocess
@@ -66,3 +67,28 @@ def test_bench_dumps_the_last_timed_step_reproducibly(gpu, tmp_path):
     # another step count ends on another step (seeded per step), so the image changes
     run(tmp_path / "c", 2)
     assert not np.array_equal(img, np.load(tmp_path / "c" / "image.npy"))
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_leaves_the_side_measurements_to_full(gpu, tmp_path):
+    def run(out, *extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--res", "32", "--film", "64", "--spp", "4", "--dump-outputs", str(out), *extra],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-6000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+    plain, full = run(tmp_path / "plain"), run(tmp_path / "full", "--full")
+    for res in (plain, full):
+        assert res["unit"] == "Msamples/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+        assert res["value"] > 0 and res["ms_per_step"] > 0 and res["steps"] == 2 and res["warmup"] == 1
+        assert res["t_primal_ms"] > 0 and res["t_adjoint_ms"] > 0            # HIP-event times of the timed steps
+    assert plain["metric"] == full["metric"]
+    assert plain["full"] is False and full["full"] is True
+    for k in ("roofline", "counters_primal", "counters_adjoint", "cpu_baseline", "other_configs"):
+        assert plain[k] is None, k
+    assert full["roofline"]["frac"] > 0 and full["counters_primal"]["n_dt"] > 0 and full["counters_adjoint"]
+    assert full["cpu_baseline"]["value"] > 0
+    assert full["other_configs"] is None                                     # (the other configurations run beside 256^3 only)
+    # --full measures after the timed steps: what they computed is the same
+    np.testing.assert_array_equal(np.load(tmp_path / "plain" / "image.npy"), np.load(tmp_path / "full" / "image.npy"))

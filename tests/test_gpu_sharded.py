@@ -37,9 +37,9 @@ def test_sharded_batched_render_and_optimisation_two_processes(gpu, factor):
 
 
 def test_bench_two_ranks_on_one_device(gpu):
-    """bench.py's N > 1 path (image tiles dealt to the ranks, one all-reduce per step), smoke-sized."""
+    """bench.py's N > 1 path (image tiles dealt to the ranks, one all-reduce per step), smoke-sized; --full for the roofline."""
     r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--res", "32",
-                   "--film", "64", "--spp", "4", "--no-cpu-baseline", "--no-extra-configs"],
+                   "--film", "64", "--spp", "4", "--full", "--no-cpu-baseline", "--no-extra-configs"],
                   env_extra={"DRT_BENCH_SAME_DEVICE": "1", "DRT_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stdout[-3000:] + "\n" + r.stderr[-6000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

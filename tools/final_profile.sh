@@ -9,8 +9,9 @@
 tag=${1:-final}
 R=/root/repo/gpurun_out/$tag
 mkdir -p $R
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-B="python /root/repo/bench.py --no-cpu-baseline --no-extra-configs"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-configs"
 for f in 8 0; do
   sfx=""; [ $f == 0 ] && sfx="_factor0"
   (timeout 600 rocprofv3 --kernel-trace --stats -d $R/prof$f -o hl -- $B --majorant-factor $f > $R/bench_under_rocprof$sfx.json 2>> $R/err.txt)
@@ -44,8 +45,8 @@ python tools/pmc_to_util.py $R/fused_pmc_util.txt $R/kernel_stats_fused.csv fuse
 rm -rf $R/pmc_traffic_alb0
 rm -rf $R/pmc_traffic_c4 $R/pmc_util0 $R/pmc_util8 $R/pmc_traffic0 $R/pmc_traffic8 $R/pmc_traffic_fused $R/pmc_traffic_env8 $R/pmc_util_fused $R/prof0 $R/prof8 $R/prof_fused
 cp $R/roofline_traffic.json profiles/roofline_traffic.json      # the bench lines below quote it (same kernel sources: hash checked)
-(timeout 1500 python bench.py > $R/bench.json 2>> $R/err.txt)
-(timeout 600 python bench.py --majorant-factor 0 --no-extra-configs --no-cpu-baseline > $R/bench_factor0.json 2>> $R/err.txt)
+(timeout 1500 python bench.py --full > $R/bench.json 2>> $R/err.txt)
+(timeout 600 python bench.py --full --majorant-factor 0 --no-extra-configs --no-cpu-baseline > $R/bench_factor0.json 2>> $R/err.txt)
 [ -f $R/traffic_alb0.json ] && python tools/traffic_by_buffer.py $R/roofline_traffic.json $R/traffic_alb0.json $R/bench.json dust-devil-256-512x32-factor8 > $R/traffic_by_buffer.txt
 python - <<P
 import json

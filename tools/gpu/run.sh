@@ -5,7 +5,7 @@
 #   tests[:EXPR]        pytest -m gpu (-k EXPR), tail of the log
 #   vtests:V:EXPR       pytest -m gpu -k EXPR with LD_LIBRARY_PATH=variants/V (the production library only: hooks tests keep the in-tree one)
 #   smoke               __graft_entry__.smoke()
-#   bench               headline line (no side configs, no CPU baseline)
+#   bench               headline line with its roofline (--full, no side configs, no CPU baseline)
 #   only:NAME           bench.py --only-config NAME
 #   sweep:V1,V2,..      tools/gpu/sweep2.sh over variant libraries (variants/V/libdrt_hip.so; "default" = the in-tree library)
 #   sweep3:V1,..        headline + config3_as_reproduce per variant
@@ -32,7 +32,7 @@ for step in "$@"; do
       v=${arg%%:*}; ex=${arg#*:}
       LD_LIBRARY_PATH=variants/$v timeout 2400 python -m pytest tests -m gpu -x -q -k "$ex" > $R/pytest_$v.txt 2>&1; tail -n 6 $R/pytest_$v.txt ;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 4 ;;
-    bench) timeout 300 python bench.py --no-cpu-baseline --no-extra-configs > $R/bench_headline.json 2> $R/bench_err.txt
+    bench) timeout 300 python bench.py --full --no-cpu-baseline --no-extra-configs > $R/bench_headline.json 2> $R/bench_err.txt
            python -c "import json; d=json.load(open('$R/bench_headline.json')); print(d['value'], d['t_primal_ms'], d['t_adjoint_ms'], d['t_grad_reduce_ms'], d['roofline']['frac'])" ;;
     only) timeout 1200 python bench.py --only-config $arg > $R/only_$arg.json 2>> $R/bench_err.txt
           python -c "import json; d=json.load(open('$R/only_$arg.json')); print(json.dumps(d)[:1500])" ;;
