@@ -371,31 +371,47 @@ int drt_read_timings(drt_handle h, int backward, float *out_ms, int capacity);
  * handle's g (drt_set_phase) -> pdf. */
 int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out);
 
-/* Profiling ablations / kernel selection for experiments; 0 in production.
- * bit 0 (1): skip the gradient atomics; bit 1 (2): per-lane (uncoalesced) atomics; bit 3 (8): force the
- * one-ray-per-lane tracing kernels; bit 4 (16): no empty-space bitmask; bit 5 (32): state-machine
- * kernel for the adjoint too; bit 7 (128): gradient splats as atomics into the apron scratch (the path
- * used when the grid has more than 4096 tiles or the record streams exceed the memory budget) instead
- * of deferred records; bit 8 (256): two-chunk record streams (exercises the out-of-chunks fallback);
- * bit 9 (512): the nerf adjoint of sensor rays through the record path (nerf_kernel + deferred splatting, as explicit ray batches go)
- * instead of the LDS-window kernel drt_nerf_tile.hip; bit 10 (1024): reduction without the flush (timing only); bit 11 (2048):
- * overlap the tracer of ray sub-batch b with the reduction of sub-batch b - 1 on a side stream (also
- * DRT_PIPELINE in the environment; measured slower); bit 13
- * (8192): exact checksum of the flushed sums; bit 14 (16384): 8 MB record budget, i.e. many ray
- * sub-batches (test hook); bit 15 (32768): plain one-ray-per-lane adjoint kernel instead of the
- * wave-cooperative tracking loops (drt_coop.hip); bit 16 (65536): state-machine kernel for the primal
- * (default: the cooperative kernel, which also writes the path cache); bit 20 (1048576): no path
- * cache (the adjoint pass walks its primal path again); bit 18 (262144): pretend that the record
- * streams cannot be allocated (the job then takes the atomic path, as it does when hipMalloc fails); bit 19
- * (524288): pretend that they cannot be (re)allocated from the second ray sub-batch on (the remaining rays take
- * the atomic path); bit 21 (2097152): generic tracing kernels instead of the ones specialised for the registered
- * `volpathsimple-drt` estimator; bit 25 (33554432): no workgroup hand-off of sparse waves' paths (every wave runs
- * its own paths to the end); bit 26 (67108864): none in the primal pass only; bit 27 (134217728): supergrid scenes in
- * the older kernels instead of drt_super.hip; bit 28 (268435456): no early histogram pass beside the adjoint's tail launch (queued tracer: no tail pool);
- * bit 29 (536870912): the supergrid tracer takes its rays in index order (production: thick pixels first); bit 30
- * (1073741824): launches of fewer than 1.5 M rays are scheduled like large ones (ray order, tail launch) - the small scenes
- * of the tests then cover those schedules; bit 31 (2147483648): the queued supergrid tracer walks every flight (production: the
- * primary-segment flights of pixels whose rays cross only empty supergrid cells are ended at their set-up). */
+/* Test hooks: profiling ablations, kernel selection, simulated out-of-memory.  0 in production: only the library flavour built with
+ * -DDRT_TEST_HOOKS (libdrt_hip_hooks.so) accepts non-zero flags.  Every bit that is tested, by its name in csrc/drt_device.h (enum Hook):
+ *  bit  0 (1)          kHookNoGradAtomics       skip the gradient atomics (timing only)
+ *  bit  1 (2)          kHookPerLaneAtomics      per-lane (uncoalesced) gradient atomics
+ *  bit  3 (8)          kHookPerLanePrimal       the plain one-ray-per-lane tracing kernel for primal launches; never the state machine
+ *  bit  4 (16)         kHookNoOccupancy         no empty-space bitmask
+ *  bit  5 (32)         kHookWavefrontAdjoint    the state-machine kernel (drt_wavefront.hip) for the adjoint too
+ *  bit  6 (64)         kHookUntileKeepScratch   untile pass without re-zeroing the apron scratch it reads (timing only)
+ *  bit  7 (128)        kHookAtomicGradients     gradient splats as atomics into the apron scratch (the path used when the grid has more than
+ *                                               16384 tiles or the record streams exceed the memory budget) instead of deferred records
+ *  bit  8 (256)        kHookTinyRecordStreams   two-chunk record streams (exercises the out-of-chunks fallback)
+ *  bit  9 (512)        kHookNerfRecordPath      the nerf adjoint of sensor rays through the record path (nerf_kernel + deferred splatting, as
+ *                                               explicit ray batches go) instead of the LDS-window kernel drt_nerf_tile.hip
+ *  bit 10 (1024)       kHookReduceNoFlush       reduction without the flush (timing only)
+ *  bit 11 (2048)       kHookPipelineBatches     overlap the tracer of ray sub-batch b with the reduction of sub-batch b - 1 on a side stream
+ *                                               (measured slower)
+ *  bit 12 (4096)       kHookNoQueuedTracer      keep supergrid launches off the queued tracer (drt_sq.hip): the round-3 kernel drt_super.hip
+ *                                               where it serves, CoopTracer<SUPER> otherwise
+ *  bit 14 (16384)      kHookSmallRecordBudget   8 MB record budget, i.e. many ray sub-batches
+ *  bit 15 (32768)      kHookPerLaneAdjoint      plain one-ray-per-lane adjoint kernel instead of the wave-cooperative tracking loops (drt_coop.hip)
+ *  bit 16 (65536)      kHookWavefrontPrimal     state-machine kernel for the primal (default: the cooperative kernel, which also writes the
+ *                                               path cache)
+ *  bit 18 (262144)     kHookNoRecordMemory      pretend that the record streams cannot be allocated (the job then takes the atomic path, as it
+ *                                               does when hipMalloc fails)
+ *  bit 19 (524288)     kHookNoRecordMemoryLater pretend that they cannot be (re)allocated from the second ray sub-batch on (the remaining rays
+ *                                               take the atomic path)
+ *  bit 20 (1048576)    kHookNoPathCache         no path cache (the adjoint pass walks its primal path again)
+ *  bit 21 (2097152)    kHookGenericKernels      generic tracing kernels instead of the ones specialised for the registered `volpathsimple-drt`
+ *                                               estimator
+ *  bit 22 (4194304)    kHookNoRaySchedule       no ray schedule / iteration counts from the primal pass
+ *  bit 23 (8388608)    kHookNoSupergridMask     no LDS copy of the supergrid's non-empty-cell bitmask
+ *  bit 24 (16777216)   kHookPlainBlockMap       plain XCD block map (production: heavy blocks of the previous launch first)
+ *  bit 25 (33554432)   kHookNoHandOff           no workgroup hand-off of sparse waves' paths (every wave runs its own paths to the end)
+ *  bit 26 (67108864)   kHookNoHandOffPrimal     none in the primal pass only
+ *  bit 27 (134217728)  kHookWavefrontSupergrid  supergrid scenes in the older kernels instead of the supergrid tracers
+ *  bit 28 (268435456)  kHookNoTailOverlap       no early histogram pass beside the adjoint's tail launch (queued tracer: no tail pool)
+ *  bit 29 (536870912)  kHookIndexOrder          the supergrid tracer takes its rays in index order (production: thick pixels first)
+ *  bit 30 (1073741824) kHookScheduleSmall       launches of fewer than 1.5 M rays are scheduled like large ones (ray order, tail launch) - the
+ *                                               small scenes of the tests then cover those schedules
+ *  bit 31 (2147483648) kHookWalkEmptyPixels     the queued supergrid tracer walks every flight (production: the primary-segment flights of
+ *                                               pixels whose rays cross only empty supergrid cells are ended at their set-up) */
 int drt_set_debug_flags(drt_handle h, uint32_t flags);
 
 const char *drt_version(void);

@@ -18,6 +18,44 @@
 #include <utility>
 #include <vector>
 
+using namespace drt;   // (the test hooks' names, dbg)
+
+// ---- build-time knobs (_build.py forwards DRT_* integers from the environment as -D) ----------------------------------------------------------
+#ifndef DRT_PATH_CACHE_CAP
+#define DRT_PATH_CACHE_CAP 64       // depth of the path cache (kPathCacheCap)
+#endif
+#ifndef DRT_ORDER_ITERS
+#define DRT_ORDER_ITERS 1           // adjoint launches of the supergrid tracer: units ordered by the primal pass's iteration counts too (0: as the primal launch)
+#endif
+#ifndef DRT_SQ_UNIT_EMPTY
+#define DRT_SQ_UNIT_EMPTY 1         // pixels whose rays cross only empty supergrid cells are flagged: their primary-segment flights are not walked
+#endif
+#ifndef DRT_SQ_TAIL
+#define DRT_SQ_TAIL 1               // adjoint launches of the queued tracer: drained workgroups hand their last records to a tail pool; 0: they finish them
+#endif
+#ifndef DRT_SQ_TAIL_SOLO
+#define DRT_SQ_TAIL_SOLO 3          // bit 0: primal launches, bit 1: adjoint launches below the size of the overlapped tail
+#endif
+#ifndef DRT_SQ_TAIL_THIN
+#define DRT_SQ_TAIL_THIN 0          // 0: primal launches over a thin medium (the ROUNDS kernels) make no tail launch - their few real paths are short, a second
+                                    // launch over the whole chip costs more than they do (config3_as_reproduce 302-305 -> 308-310 iterations/s); 1: they do
+#endif
+
+// A device buffer the handle owns: freed with the handle, replaced only by resize().
+enum AllocMode { kMust, kBestEffort };
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    template <class T> T *as() const { return (T *) p; }
+    void release() { if (p) (void) hipFree(p); p = nullptr; bytes = 0; }
+    int resize(drt_handle h, size_t need, AllocMode mode, bool wait_side = false, bool pretend_no_memory = false);
+    int grow(drt_handle h, size_t need, AllocMode mode) { return need <= bytes ? DRT_OK : resize(h, need, mode); }
+};
+
 struct drt_handle_s {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -34,31 +72,26 @@ struct drt_handle_s {
     float majorant_seen = -1.0f;   // < 0: never seen
     uint32_t *d_scratch = nullptr; // [1]
     unsigned long long *d_counters = nullptr;   // [C_COUNT]
-    float *d_gt = nullptr;         // gradient scratch, 4 planes (always zero between launches)
+    DevBuf gt;                     // gradient scratch, 4 planes of floats (always zero between launches)
     unsigned long long *d_queues = nullptr;   // 8 per-XCD ray queue heads (wavefront kernel)
-    void *d_sq_cold = nullptr;                // queued supergrid tracer: adjoint path state kept in global memory (drt_sq.hip)
-    void *d_uempty = nullptr;                 // per pixel: its rays cross only empty supergrid cells (build_unit_empty; queued supergrid tracer)
-    size_t uempty_bytes = 0;
-    void *d_order = nullptr;                  // ray order of the supergrid tracer's current launch (build_super_order)
-    size_t order_bytes = 0;
+    DevBuf sq_cold;                           // queued supergrid tracer: adjoint path state kept in global memory (drt_sq.hip)
+    DevBuf uempty;                            // per pixel: its rays cross only empty supergrid cells (build_unit_empty; queued supergrid tracer)
+    DevBuf order;                             // ray order of the supergrid tracer's current launch (build_super_order)
     uint64_t order_first = 0, order_end = 0;  // ... made by the primal launch over these rays of the job the path cache describes:
     uint32_t order_unit = 0;                  //     the adjoint launch over the same rays takes it as it is (0: none)
-    void *d_tail = nullptr;                   // tail pool of the cooperative kernels: [counter, pad to 256 B][entries x 128 B]
-    size_t tail_entries = 0;
+    DevBuf tail;                              // tail pool of the cooperative kernels: [counter, pad to 256 B][entries x 128 B]
     int n_cus = 256;
-    float *d_sigma_b = nullptr;    // bricked copy of sigma_t (refreshed by drt_params_changed)
+    DevBuf sigma_b;                // bricked copy of sigma_t, floats (refreshed by drt_params_changed)
     uint32_t *d_occ = nullptr;     // empty-space bitmask (kOccWords words)
-    float *d_mgrid = nullptr;      // majorant supergrid (refreshed by drt_params_changed)
+    DevBuf mgrid;                  // majorant supergrid, floats | non-empty bitmask | the same, dilated by one cell (refreshed by drt_params_changed)
     float *d_env = nullptr;        // envmap emitter: pixels | marginal CDF | conditional CDFs (one allocation)
-    float4 *d_grid4 = nullptr;     // interleaved four-channel apron-brick copy (fused pass), built on demand
-    size_t grid4_quads = 0;
+    DevBuf grid4;                  // interleaved four-channel apron-brick copy, float4s (fused pass), built on demand
     uint64_t grid4_version = 0;    // medium_version the copy was built at (0: never)
     uint64_t medium_version = 0;   // bumped whenever the parameter grids (may) have changed: drt_set_medium / drt_params_changed
     // deferred splatting (drt_deferred.hip): record streams in / tile-sorted, chunk fills, partition tables.
     // Two slots: sub-batch b traces into slot b % 2 while slot (b - 1) % 2 is reduced on the side stream.
     struct RecSlot {
-        void *mem = nullptr;           // one allocation, carved up in ensure_deferred
-        size_t bytes = 0;
+        DevBuf mem;                    // one allocation, carved up in ensure_deferred
         uint64_t rays = 0;             // ray count the current carving was sized for
         int bins = 0;
         bool tiny = false;
@@ -74,29 +107,22 @@ struct drt_handle_s {
     const drt::DeferredPlan *early_plan = nullptr;
     bool early_done = false;
     bool early_partition = false;             // ... and it was the whole partition (histogram .. scatter: the queued tracer's tail launch), not just the histogram
-    void *d_sq_tail = nullptr;                // tail pool of the queued tracer's adjoint launches: 256-byte header {count, .., dummy cursors} + entries
-    size_t sq_tail_bytes = 0;
-    hipEvent_t ev_split = nullptr, ev_hist = nullptr;
+    DevBuf sq_tail;                           // tail pool of the queued tracer's adjoint launches: 256-byte header {count, .., dummy cursors} + entries
+    hipEvent_t ev_split = nullptr, ev_hist = nullptr;   // around a tail launch: the main launch's records are complete / their histogram or partition on `side` is done
     hipStream_t nerf_stream = nullptr;  // the nerf half of the fused pass runs beside the volpathsimple half (drt_fused_render_*)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    double *d_loss_partials = nullptr;   // per-workgroup sums of drt_film_loss_forward
-    size_t loss_partials_bytes = 0;
-    float *d_dl_px = nullptr;            // per-ray dL for the queued tracer, expanded from Params::dL_pix (drt_render_backward_px)
-    size_t dl_px_bytes = 0;
-    uint32_t *d_nerf_bounds = nullptr; // 32 bytes: max |dL|, |L_in|, |emission|, non-finite flag, largest negative density of a nerf tile adjoint launch (drt_nerf_tile.hip)
+    DevBuf loss_partials;                // per-workgroup sums (doubles) of drt_film_loss_forward
+    DevBuf dl_px;                        // per-ray dL (floats) for the queued tracer, expanded from Params::dL_pix (drt_render_backward_px)
+    DevBuf nerf_bounds;                // 32 bytes: max |dL|, |L_in|, |emission|, non-finite flag, largest negative density of a nerf tile adjoint launch (drt_nerf_tile.hip)
     // path cache (drt_coop.hip): written by the primal launch of an H1 step, read by the adjoint launch of the
     // same job if nothing happened to the handle in between
-    void *d_pcache = nullptr;          // [rays][kPathCacheCap][2] uint4 | [rays] hash words
-    size_t pcache_bytes = 0;
+    DevBuf pcache;                     // [rays][kPathCacheCap][2] uint4 | [rays] hash words
     uint32_t pcache_cap = 0;           // bounce-loop iterations per ray of the cache as the last primal launch laid it out
     struct JobSig { uint64_t n_rays, ray_offset, chunk, stride; uint32_t spp, seed; const void *rays_o, *rays_d; uint64_t scene_version; bool valid; } pcache_sig{};
     bool order_valid = false;          // block_order of the last primal launch is usable
     bool perm_valid = false;           // ray_perm was written by the primal launch the path cache signature describes
     uint64_t order_rays = 0;           // ray count of the launch that produced the stored order (0: none)
     uint64_t scene_version = 0;        // bumped by every call that changes the medium / emitter / sensor / integrator state
-    size_t mgrid_cells = 0;
-    size_t sigma_b_floats = 0;
-    size_t gt_floats = 0;
     bool counting = false;
     uint64_t chunk = 0, stride = 0;   // ray interleave (drt_set_ray_interleave)
     uint32_t debug_flags = 0;
@@ -106,8 +132,6 @@ struct drt_handle_s {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timed[4];   // primal, adjoint, gradient reduction, whole backward pass
     std::string error;
 };
-
-using drt::dbg;
 
 namespace {
 
@@ -131,6 +155,8 @@ int fail(drt_handle h, int code, const char *fmt, ...)
         if (e_ != hipSuccess)                                                               \
             return fail(h, DRT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
     } while (0)
+// a step that has set its own message: its code is the call's
+#define DRT_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
 
 struct DeviceGuard {
     int prev = -1;
@@ -187,21 +213,86 @@ void fill_job(drt_handle h, drt::Params &P, const float *rays_o, const float *ra
     P.unit_empty = nullptr; P.empty_unit = 0;
 }
 
+}  // namespace
+
+// The one place a buffer of the handle is replaced (contents lost): wait for the work that may still use the old one - the handle's stream;
+// wait_side: the side stream too -, free it, allocate.  kMust: a failed allocation is the call's error.  kBestEffort: it leaves p null and
+// clears the sticky HIP error - the caller carries on without the feature (pretend_no_memory: a test hook asks for just that).
+int DevBuf::resize(drt_handle h, size_t need, AllocMode mode, bool wait_side, bool pretend_no_memory)
+{
+    if (p) {
+        DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+        if (wait_side && h->side) DRT_HIP_CHECK(h, hipStreamSynchronize(h->side));
+        release();
+    }
+    if (mode == kBestEffort) {
+        if (pretend_no_memory || hipMalloc(&p, need) != hipSuccess) { (void) hipGetLastError(); p = nullptr; return DRT_OK; }
+    } else DRT_HIP_CHECK(h, hipMalloc(&p, need));
+    bytes = need;
+    return DRT_OK;
+}
+
+namespace {
+
+void destroy_pair(std::pair<hipEvent_t, hipEvent_t> &p) { (void) hipEventDestroy(p.first); (void) hipEventDestroy(p.second); }
+
 void clear_timings(drt_handle h)
 {
     for (auto &v : h->timed) {
-        for (auto &p : v) { (void) hipEventDestroy(p.first); (void) hipEventDestroy(p.second); }
+        for (auto &p : v) destroy_pair(p);
         v.clear();
     }
 }
 
-// launch bracketed by an event pair on the handle's stream when timing is enabled
-#ifndef DRT_PATH_CACHE_CAP
-#define DRT_PATH_CACHE_CAP 64
-#endif
-#ifndef DRT_ORDER_ITERS
-#define DRT_ORDER_ITERS 1           // adjoint launches of the supergrid tracer: units ordered by the primal pass's iteration counts too (0: as the primal launch)
-#endif
+// HIP event pair around a piece of work on one stream while timing is on (otherwise both calls do nothing): begin() records the first,
+// end() records the second and files the pair in h->timed[which].  A span that is never ended - an error in between - destroys its events.
+struct TimedSpan {
+    drt_handle h = nullptr;
+    hipStream_t st = nullptr;
+    hipEvent_t a = nullptr, b = nullptr;
+    ~TimedSpan() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
+    hipError_t begin(drt_handle handle, hipStream_t stream)
+    {
+        h = handle; st = stream;
+        if (!h->timing) return hipSuccess;
+        hipError_t e = hipEventCreate(&a);
+        if (e == hipSuccess) e = hipEventCreate(&b);
+        if (e == hipSuccess) e = hipEventRecord(a, st);
+        return e;
+    }
+    hipError_t end(int which)
+    {
+        if (!a || !b) return hipSuccess;
+        const hipError_t e = hipEventRecord(b, st);
+        if (e != hipSuccess) return e;
+        h->timed[which].emplace_back(a, b);
+        a = b = nullptr;
+        return hipSuccess;
+    }
+};
+
+// the high-priority stream of the overlapped reductions / of the early histogram pass, made when a launch first wants it
+int ensure_side_stream(drt_handle h)
+{
+    if (h->side) return DRT_OK;
+    int lo = 0, hi = 0;
+    DRT_HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
+    DRT_HIP_CHECK(h, hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, hi));
+    return DRT_OK;
+}
+
+// ... and a pair of events that order two streams against each other (no timing), made likewise
+int ensure_event_pair(drt_handle h, hipEvent_t &a, hipEvent_t &b)
+{
+    if (a) return DRT_OK;
+    DRT_HIP_CHECK(h, hipEventCreateWithFlags(&a, hipEventDisableTiming));
+    DRT_HIP_CHECK(h, hipEventCreateWithFlags(&b, hipEventDisableTiming));
+    return DRT_OK;
+}
+
+// this launch has no tail pool: every path ends where it is
+void no_tail(drt::Params &P) { P.tail_pool = nullptr; P.tail_count = nullptr; P.tail_cap = 0; P.tail_mode = 0; }
+
 constexpr uint32_t kPathCacheCap = DRT_PATH_CACHE_CAP;  // bounce-loop iterations cached per ray (headline: 2.4 on average)
 constexpr uint64_t kHeavyFirstMaxBlocks = 12288;       // launches up to this many 256-ray blocks run heavy blocks first
 constexpr uint64_t kPathCacheMaxRays = 1ull << 24;     // larger primal launches (reference renders) skip the cache
@@ -230,7 +321,7 @@ void bind_path_cache_write(drt_handle h, drt::Params &P)
 {
     h->pcache_sig.valid = false;
     if (P.n_rays != h->order_rays) h->order_rays = 0;           // another launch shape re-carves the buffer: the stored order dies
-    if (dbg(h->debug_flags, 1048576u) || P.n_rays > kPathCacheMaxRays) return;
+    if (dbg(h->debug_flags, kHookNoPathCache) || P.n_rays > kPathCacheMaxRays) return;
     const size_t n_blocks = (size_t) ((P.n_rays + 255) / 256);
     const size_t perm_slots = ((size_t) P.n_rays + drt::kPermGroup - 1) / drt::kPermGroup * drt::kPermGroup;
     const size_t rest = (size_t) P.n_rays * sizeof(uint32_t) + 2 * n_blocks * sizeof(uint32_t) + perm_slots * 3 + 16;
@@ -240,28 +331,27 @@ void bind_path_cache_write(drt_handle h, drt::Params &P)
     // memory too (run_backward), and a handle on a smaller device, or one that shares its device with other ranks, must leave them room; otherwise
     // halved until it fits (from 4 iterations down: no cache - deep main paths then walk again in the adjoint pass, results unchanged).
     uint32_t cap = kPathCacheCap;
-    if (entry_bytes(cap) + rest > h->pcache_bytes) {
+    if (entry_bytes(cap) + rest > h->pcache.bytes) {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void) hipGetLastError(); free_b = 0; }
-        size_t budget = h->pcache_bytes + free_b / 2;
+        size_t budget = h->pcache.bytes + free_b / 2;
         if (budget > kPathCacheMaxBytes) budget = kPathCacheMaxBytes;
         while (cap >= 4u && entry_bytes(cap) + rest > budget) cap /= 2u;
         if (cap < 4u) return;
     }
     const size_t entries = entry_bytes(cap), need = entries + rest;
-    if (need > h->pcache_bytes) {
-        if (h->d_pcache) { if (hipStreamSynchronize(h->stream) != hipSuccess) return; (void) hipFree(h->d_pcache); h->d_pcache = nullptr; h->pcache_bytes = 0; }
+    if (need > h->pcache.bytes) {
+        if (h->pcache.resize(h, need, kBestEffort) != DRT_OK) return;   // (the stream could not be waited for: the old buffer stays, this launch goes without)
         h->order_rays = 0;
-        if (hipMalloc(&h->d_pcache, need) != hipSuccess) { (void) hipGetLastError(); h->d_pcache = nullptr; return; }
-        h->pcache_bytes = need;
+        if (!h->pcache.p) return;
     }
     h->pcache_cap = cap;
-    P.path_cache = (uint4 *) h->d_pcache;
-    P.ray_hash = (uint32_t *) ((char *) h->d_pcache + entries);
+    P.path_cache = h->pcache.as<uint4>();
+    P.ray_hash = (uint32_t *) (h->pcache.as<char>() + entries);
     P.path_cache_cap = cap; P.path_cache_mode = 1;
     P.block_cost = P.ray_hash + P.n_rays;
     if (hipMemsetAsync(P.block_cost, 0, n_blocks * sizeof(uint32_t), h->stream) != hipSuccess) { (void) hipGetLastError(); P.block_cost = nullptr; }
-    if (!dbg(h->debug_flags, 4194304u)) P.ray_iters = (uint8_t *) (perm_base(P.ray_hash, P.n_rays) + perm_slots);   // written by the cooperative primal kernel only
+    if (!dbg(h->debug_flags, kHookNoRaySchedule)) P.ray_iters = (uint8_t *) (perm_base(P.ray_hash, P.n_rays) + perm_slots);   // written by the cooperative primal kernel only
     h->perm_valid = false;
     h->pcache_sig = job_sig(h, P);
 }
@@ -270,19 +360,18 @@ void bind_path_cache_write(drt_handle h, drt::Params &P)
 void bind_path_cache_read(drt_handle h, drt::Params &P, uint64_t job_rays)
 {
     drt::Params J = P; J.n_rays = job_rays;
-    if (!h->pcache_sig.valid || dbg(h->debug_flags, 1048576u) || !same_job(h->pcache_sig, job_sig(h, J))) return;
+    if (!h->pcache_sig.valid || dbg(h->debug_flags, kHookNoPathCache) || !same_job(h->pcache_sig, job_sig(h, J))) return;
     const size_t entries = (size_t) job_rays * h->pcache_cap * 2 * sizeof(uint4);   // (the depth the primal pass of this job wrote)
-    P.path_cache = (uint4 *) h->d_pcache;
-    P.ray_hash = (uint32_t *) ((char *) h->d_pcache + entries);
+    P.path_cache = h->pcache.as<uint4>();
+    P.ray_hash = (uint32_t *) (h->pcache.as<char>() + entries);
     P.path_cache_cap = h->pcache_cap; P.path_cache_mode = 2;
-    const bool no_lpt = dbg(h->debug_flags, 16777216u);   // test hook: plain XCD block map
     // (measured: film 184^2 x 32 spp, the per-rank share at 8 GPUs: adjoint 2.22 -> 1.70 ms; 256^2: 3.11 -> 2.85 ms; at
     //  the full 512^2 the XCD-contiguous block map is worth more than the order: 9.48 vs 10.02 ms)
-    if (!no_lpt && P.ray_first == 0 && P.n_rays == job_rays && h->order_valid)
+    if (!dbg(h->debug_flags, kHookPlainBlockMap) && P.ray_first == 0 && P.n_rays == job_rays && h->order_valid)
         P.block_order = P.ray_hash + job_rays + (job_rays + 255) / 256;
-    if (h->perm_valid && !dbg(h->debug_flags, 4194304u)) P.ray_perm = perm_base(P.ray_hash, job_rays);
+    if (h->perm_valid && !dbg(h->debug_flags, kHookNoRaySchedule)) P.ray_perm = perm_base(P.ray_hash, job_rays);
     // (the iteration counts of the primal pass: the supergrid tracer's adjoint launches order their rays by them)
-    if (!dbg(h->debug_flags, 4194304u)) {
+    if (!dbg(h->debug_flags, kHookNoRaySchedule)) {
         const size_t perm_slots = ((size_t) job_rays + drt::kPermGroup - 1) / drt::kPermGroup * drt::kPermGroup;
         P.ray_iters = (uint8_t *) (perm_base(P.ray_hash, job_rays) + perm_slots);
     }
@@ -300,326 +389,332 @@ hipError_t early_histogram_between(void *ctx)
     if (e == hipSuccess) e = hipEventRecord(h->ev_split, h->stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(h->side, h->ev_split, 0);
     // (timed like the rest of the reduction: its own event pair on the side stream, summed into the reduction time)
-    hipEvent_t ta = nullptr, tb = nullptr;
-    if (e == hipSuccess && h->timing) { e = hipEventCreate(&ta); if (e == hipSuccess) e = hipEventCreate(&tb); if (e == hipSuccess) e = hipEventRecord(ta, h->side); }
+    TimedSpan span;
+    if (e == hipSuccess) e = span.begin(h, h->side);
     if (e == hipSuccess) e = drt::launch_deferred_early_histogram(*c->P, *h->early_plan, h->side);
-    if (e == hipSuccess && h->timing) { e = hipEventRecord(tb, h->side); if (e == hipSuccess) h->timed[2].emplace_back(ta, tb); }
+    if (e == hipSuccess) e = span.end(2);
     if (e == hipSuccess) e = hipEventRecord(h->ev_hist, h->side);
     return e;
 }
 
-int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
+// ---- which call reaches which kernel --------------------------------------------------------------------------------------------------------
+enum class Route {
+    kCoop,       // CoopTracer / CoopTracer<SUPER> (drt_coop.hip, drt_coop_super.hip)
+    kCoopHG,     // CoopTracer<HG> / <GG> (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip)
+    kOwn,        // CoopTracer with the colour grids on their own lattice (drt_own.hip)
+    kQueued,     // the queued supergrid tracer (drt_sq.hip, drt_sq_hg.hip)
+#ifdef DRT_TEST_HOOKS
+    kSuper3,     // the round-3 supergrid kernel (drt_super.hip)
+    kWavefront,  // the round-2 state machine of whole flights (drt_wavefront.hip)
+    kPerLane,    // the plain per-lane Tracer (drt_kernels.hip)
+#endif
+};
+// hg: the HG instantiations (drt_set_phase); gg: ... with the g-gradient, an HG adjoint launch with a sink in Params::L_out
+struct Choice { Route route; bool hg, gg; };
+
+// Kernel choice - which call reaches which kernel (DESIGN.md section 1 has the table); launches nothing, allocates nothing:
+//   global majorant (majorant_resolution_factor 0): CoopTracer (drt_coop.hip: one ray per lane, wave-cooperative tracking rounds), both passes;
+//   majorant supergrid (the reference's default 8): the queued tracer (drt_sq.hip: rays are records, waves take batches of one kind of work),
+//   both passes, every estimator - where its records fit LDS next to the supergrid's majorants or cell bitmask (sq_supported: up to ~99^3 cells,
+//   max_depth <= 1000) and the adjoint's splats travel as records; otherwise (larger supergrids, the atomic gradient path of grids beyond 16384
+//   reduction tiles or without record memory): CoopTracer<SUPER> (drt_coop_super.hip: own-lane tracking steps through the supergrid).
+//   Every primal kernel writes the path cache the adjoint pass of the job reads.  Only the library flavour with test hooks also holds the older
+//   generations - the round-3 supergrid kernel (drt_super.hip; kHookNoQueuedTracer), the round-2 state machine of whole flights (drt_wavefront.hip;
+//   kHookWavefrontAdjoint / Primal / Supergrid) and the plain per-lane Tracer (drt_kernels.hip; kHookPerLanePrimal / Adjoint) - where the variant
+//   tests keep them in lock-step.
+//   Colour grids on their own lattice (drt_set_colour_resolution): the kernels of drt_own.hip - CoopTracer with either kind of majorant, compiled
+//   with the colour lookups and splats on that lattice; no tail pool, no queued tracer (correct first: the configurations it serves are rare).
+//   Henyey-Greenstein phase (drt_set_phase): the same choice among the HG instantiations - the queued tracer (drt_sq_hg.hip) for the
+//   supergrids it takes, CoopTracer<HG> otherwise (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip) - without tail launches or
+//   hand-off, and no ROUNDS kernels; the older generations have no HG code.
+//   The g-gradient (drt_render_backward_phase: an HG adjoint launch with a sink in Params::L_out) runs the GG instantiations of the same
+//   kernels; the counting kernels have none (such a launch counts nothing).
+Choice choose_tracer(drt_handle h, const drt::Params &P, bool adjoint)
 {
-    hipEvent_t a = nullptr, b = nullptr;
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventCreate(&a));
-        DRT_HIP_CHECK(h, hipEventCreate(&b));
-        DRT_HIP_CHECK(h, hipEventRecord(a, h->stream));
-    }
-    // Kernel choice - which call reaches which kernel (DESIGN.md section 1 has the table):
-    //   global majorant (majorant_resolution_factor 0): CoopTracer (drt_coop.hip: one ray per lane, wave-cooperative tracking rounds), both passes;
-    //   majorant supergrid (the reference's default 8): the queued tracer (drt_sq.hip: rays are records, waves take batches of one kind of work),
-    //   both passes, every estimator - where its records fit LDS next to the supergrid's majorants or cell bitmask (sq_supported: up to ~99^3 cells,
-    //   max_depth <= 1000) and the adjoint's splats travel as records; otherwise (larger supergrids, the atomic gradient path of grids beyond 16384
-    //   reduction tiles or without record memory): CoopTracer<SUPER> (drt_coop_super.hip: own-lane tracking steps through the supergrid).
-    //   Every primal kernel writes the path cache the adjoint pass of the job reads.  Only the library flavour with test hooks also holds the older
-    //   generations - the round-3 supergrid kernel (drt_super.hip; hook 4096), the round-2 state machine of whole flights (drt_wavefront.hip; hooks
-    //   32 / 65536 / 134217728) and the plain per-lane Tracer (drt_kernels.hip; hooks 8 / 32768) - where the variant tests keep them in lock-step.
-    //   Colour grids on their own lattice (drt_set_colour_resolution): the kernels of drt_own.hip - CoopTracer with either kind of majorant, compiled
-    //   with the colour lookups and splats on that lattice; no tail pool, no queued tracer (correct first: the configurations it serves are rare).
-    //   Henyey-Greenstein phase (drt_set_phase): the same choice among the HG instantiations - the queued tracer (drt_sq_hg.hip) for the
-    //   supergrids it takes, CoopTracer<HG> otherwise (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip) - without tail launches or
-    //   hand-off, and no ROUNDS kernels; the older generations have no HG code.
-    //   The g-gradient (drt_render_backward_phase: an HG adjoint launch with a sink in Params::L_out) runs the GG instantiations of the same
-    //   kernels; the counting kernels have none (such a launch counts nothing).
-    const bool hg = h->phase_kind == DRT_PHASE_HG;
-    const bool gg = hg && adjoint && P.L_out != nullptr;
-    if (hg && dbg(h->debug_flags, 32u | 65536u | 134217728u | 8u | 32768u))
-        return fail(h, DRT_ERR_UNSUPPORTED, "the Henyey-Greenstein phase function has no code in the older tracer generations: the test hook "
-                                            "routes this launch to one of them (debug flags 0x%x)", h->debug_flags);
-    auto launch_coop_hg = [&]() -> int {
-        drt::Params Q = P;
-        Q.tail_pool = nullptr; Q.tail_count = nullptr; Q.tail_cap = 0; Q.tail_mode = 0;
-        if (P.mgrid) Q.ray_perm = nullptr;
-        if (gg) DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_gg(Q, h->stream) : drt::launch_trace_coop_gg(Q, h->stream));
-        else if (P.colour_own) DRT_HIP_CHECK(h, drt::launch_trace_own_hg(Q, adjoint, h->counting, h->stream));
-        else DRT_HIP_CHECK(h, drt::launch_trace_coop_hg(Q, adjoint, h->counting, h->stream));
-        if (h->timing) {
-            DRT_HIP_CHECK(h, hipEventRecord(b, h->stream));
-            h->timed[which].emplace_back(a, b);
-        }
-        return DRT_OK;
-    };
-    // (test hook 4096, which keeps supergrid launches off the queued tracer: CoopTracer<SUPER, HG> here - the HG kernels' tracer-agreement tests)
-    if (hg && (P.colour_own || !P.mgrid || dbg(h->debug_flags, 4096u))) return launch_coop_hg();
-    if (P.colour_own) {
-        drt::Params Q = P;
-        Q.tail_pool = nullptr; Q.tail_count = nullptr; Q.tail_cap = 0; Q.tail_mode = 0;
-        if (P.mgrid) Q.ray_perm = nullptr;
-        DRT_HIP_CHECK(h, drt::launch_trace_own(Q, adjoint, h->counting, h->stream));
-        if (h->timing) {
-            DRT_HIP_CHECK(h, hipEventRecord(b, h->stream));
-            h->timed[which].emplace_back(a, b);
-        }
-        return DRT_OK;
-    }
+    const uint32_t f = h->debug_flags;
+    const bool hg = h->phase_kind == DRT_PHASE_HG, gg = hg && adjoint && P.L_out != nullptr;
+    auto to = [=](Route r) { return Choice{ r, hg, gg }; };
+    // (kHookNoQueuedTracer: CoopTracer<SUPER, HG> here - the HG kernels' tracer-agreement tests)
+    if (hg && (P.colour_own || !P.mgrid || dbg(f, kHookNoQueuedTracer))) return to(Route::kCoopHG);
+    if (P.colour_own) return to(Route::kOwn);
+    // a supergrid launch: not when a test hook or the atomic gradient path (an adjoint launch without record streams) routes it to the older kernels
+    const bool super_path = P.mgrid && !dbg(f, kHookOlderTracers) && (!adjoint || P.rec_buf[0] != nullptr);
+    if (super_path && !dbg(f, kHookNoQueuedTracer) && drt::sq_supported(P)) return to(Route::kQueued);
+#ifdef DRT_TEST_HOOKS
     const bool quadratic = h->cfg.use_drt && !h->cfg.use_drt_subsampling;
-    // (the records' global halves, ~44 MB, are allocated only by a launch that will run the queued kernel: not when a test hook or the atomic
-    //  gradient path routes this launch to the older kernels)
-    const bool super_path = P.mgrid && !dbg(h->debug_flags, (134217728u | 8u | 32u | 32768u | 65536u)) && (!adjoint || P.rec_buf[0] != nullptr);
-    bool sq_ok = super_path && !dbg(h->debug_flags, 4096u) && drt::sq_supported(P);
-    if (sq_ok && !h->d_sq_cold && hipMalloc(&h->d_sq_cold, drt::sq_cold_bytes(h->n_cus)) != hipSuccess) {
-        (void) hipGetLastError(); h->d_sq_cold = nullptr; sq_ok = false;
+    if (super_path && !quadratic && dbg(f, kHookNoQueuedTracer) && drt::super_supported(P)) return to(Route::kSuper3);
+#endif
+    if (hg) return to(Route::kCoopHG);                                     // (supergrids the queued tracer does not take)
+#ifdef DRT_TEST_HOOKS
+    // (kHookWavefrontSupergrid = supergrid scenes in the round-2 kernels - the state machine of whole flights for the primal pass,
+    //  kHookWavefrontPrimal = that kernel for any primal pass, kHookWavefrontAdjoint = for the adjoint too)
+    const bool sm_primal = !adjoint && ((P.mgrid != nullptr && dbg(f, kHookWavefrontSupergrid)) || dbg(f, kHookWavefrontPrimal)) && !dbg(f, kHookPerLanePrimal);
+    const bool sm_adjoint = adjoint && dbg(f, kHookWavefrontAdjoint) && !quadratic && !dbg(f, kHookPerLanePrimal);
+    if (sm_primal || sm_adjoint) return to(Route::kWavefront);
+    if (dbg(f, adjoint ? kHookPerLaneAdjoint : kHookPerLanePrimal)) return to(Route::kPerLane);
+#endif
+    return to(Route::kCoop);
+}
+
+// CoopTracer<HG> / <GG> and the kernels of drt_own.hip: no tail pool, no ray schedule on a supergrid
+int launch_coop_hg_or_own(drt_handle h, const drt::Params &P, bool adjoint, const Choice &c)
+{
+    drt::Params Q = P;
+    no_tail(Q);
+    if (P.mgrid) Q.ray_perm = nullptr;
+    if (c.gg) DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_gg(Q, h->stream) : drt::launch_trace_coop_gg(Q, h->stream));
+    else if (!c.hg) DRT_HIP_CHECK(h, drt::launch_trace_own(Q, adjoint, h->counting, h->stream));
+    else if (P.colour_own) DRT_HIP_CHECK(h, drt::launch_trace_own_hg(Q, adjoint, h->counting, h->stream));
+    else DRT_HIP_CHECK(h, drt::launch_trace_coop_hg(Q, adjoint, h->counting, h->stream));
+    return DRT_OK;
+}
+
+// CoopTracer, either kind of majorant
+int launch_coop(drt_handle h, const drt::Params &P, bool adjoint)
+{
+    // tail pool: room for 1/8 of the launch's rays (a workgroup sends at most DRT_TAIL_PUSH = 24 of its 256; a full pool only means that the rest stays where it is), kept while it is big enough;
+    // without it (allocation failed) the kernels simply finish every path where it is
+    drt::Params PT = P;
+    no_tail(PT);
+    // (launches of fewer than 1.5 M rays finish every path where it is: the tail launch costs them the job's longest
+    //  path once more - 512^2 x 4 spp, an eighth of the headline: adjoint 1.81 -> 1.65 ms without it, x 8 spp 2.22 / 2.20,
+    //  x 32 spp 5.78 / 6.88; kHookScheduleSmall: small launches are scheduled like large ones)
+    const bool tail_pays = P.n_rays - P.ray_first >= (3u << 19) || dbg(h->debug_flags, kHookScheduleSmall);
+    if (adjoint && !P.mgrid && P.n_rays > P.ray_first && tail_pays) {
+        const size_t want = (((size_t) (P.n_rays - P.ray_first) / 8 + 255) / 256) * 256;
+        DRT_TRY(h->tail.grow(h, want ? 256 + want * 128 : 0, kBestEffort));
+        if (h->tail.p && want >= 256) {
+            PT.tail_count = h->tail.as<uint32_t>(); PT.tail_pool = (uint4 *) (h->tail.as<char>() + 256); PT.tail_cap = (uint32_t) want;
+        }
     }
-    // Production: the queued tracer or - supergrids it does not take, the atomic gradient path - CoopTracer<SUPER> below.  The flavour with test
-    // hooks also keeps the round-3 kernel (drt_super.hip; hook 4096) and the round-2 state machine (drt_wavefront.hip; hooks 32 / 65536 / 134217728).
-#ifdef DRT_TEST_HOOKS
-    const bool super3 = super_path && !sq_ok && !quadratic && dbg(h->debug_flags, 4096u) && drt::super_supported(P);
-#else
-    const bool super3 = false;
-#endif
-    const bool super = (super_path && sq_ok) || super3;
-    if (hg && !super) return launch_coop_hg();                                // (supergrids the queued tracer does not take)
-    if (super) {
-        drt::Params Q = P;
-        Q.queues = h->d_queues;
-        if (adjoint && sq_ok && P.dL_pix) {
-            // the queued tracer reads δL per ray only: its adjoint instantiations sit at the register limit, and the per-pixel read
-            // (load_dL) measurably slowed the default path - expand the image gradient for it (film_backward_kernel: the same bits)
-            const uint64_t px = (P.n_rays + P.spp - 1) / P.spp;   // the pixels of rays [0, n_rays) (a sub-batch may end mid-pixel)
-            const size_t need = (size_t) px * P.spp * 3 * sizeof(float);
-            if (need > h->dl_px_bytes) {
-                if (h->d_dl_px) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_dl_px); h->d_dl_px = nullptr; h->dl_px_bytes = 0; }
-                DRT_HIP_CHECK(h, hipMalloc((void **) &h->d_dl_px, need));
-                h->dl_px_bytes = need;
-            }
-            DRT_HIP_CHECK(h, drt::launch_film_backward(P.dL_pix, px, P.spp, h->d_dl_px, h->stream));
-            Q.dL = h->d_dl_px; Q.dL_pix = nullptr;
-        }
-        const uint64_t span = P.n_rays - P.ray_first;
-        // round 4: the queued tracer (drt_sq.hip) where the ray records fit LDS next to the majorants; test hook 4096 keeps
-        // the round-3 kernel (drt_super.hip), which also serves what the queued one does not take
-        const bool queued = sq_ok;
-#ifndef DRT_SQ_UNIT_EMPTY
-#define DRT_SQ_UNIT_EMPTY 1         // pixels whose rays cross only empty supergrid cells are flagged: their primary-segment flights are not walked
-#endif
-        // (sensor rays whose units are whole pixels: sub-batches, interleaved chunks and offsets that cut a pixel's rays get no flags)
-        if (DRT_SQ_UNIT_EMPTY && queued && P.sensor_flow && P.mocc && P.spp && span < (1ull << 31) && P.ray_first % P.spp == 0 &&
-            P.ray_offset % P.spp == 0 && P.chunk % P.spp == 0 && P.stride % P.spp == 0 && !dbg(h->debug_flags, 2147483648u)) {
-            const uint32_t eunits = (uint32_t) ((span + P.spp - 1) / P.spp);
-            if (eunits > h->uempty_bytes) {
-                if (h->d_uempty) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_uempty); h->d_uempty = nullptr; h->uempty_bytes = 0; }
-                if (hipMalloc(&h->d_uempty, eunits) == hipSuccess) h->uempty_bytes = eunits; else { (void) hipGetLastError(); h->d_uempty = nullptr; }
-            }
-            if (h->d_uempty) {
-                DRT_HIP_CHECK(h, drt::build_unit_empty(P, P.spp, eunits, (uint8_t *) h->d_uempty, h->stream));
-                Q.unit_empty = (const uint8_t *) h->d_uempty; Q.empty_unit = P.spp;
-            }
-        }
-        // Ray order: the longest paths first - units of one pixel's rays by the majorant optical depth along the pixel's ray
-        // (drt_super.hip).  Best effort (no memory: index order); test hook 536870912: index order.
-        const uint32_t unit = P.spp >= 4u ? P.spp : 16u;
-        // (units of more rays than a CU traces at a time - the optimisation loop's primal launches, 1024 rays per pixel -
-        //  are too coarse to be scheduled: measured 3-5 % slower in that order than in index order)
-        // (and launches of fewer than 1.5 M rays - six rounds of the chip's 196 608 lanes - gain nothing: 512^2 x 4 spp 1.53 -> 1.69 ms,
-        //  x 8 spp 1.89 -> 1.79 ms, x 32 spp 4.17 -> 3.75 ms; test hook 1073741824 orders launches from 4096 rays on)
-        //  round 4, queued tracer: a rank's share of the headline at 8 GPUs, 512^2 x 32 spp / 8 = 1 M rays: step 3.83 -> 3.68 ms in that order)
-        const uint64_t min_span = dbg(h->debug_flags, 1073741824u) ? 4096u : (1u << 20);
-        if (span >= min_span && span < (1ull << 31) && unit <= 256u && !dbg(h->debug_flags, 536870912u)) {
-            const uint32_t units = (uint32_t) ((span + unit - 1) / unit);
-            const size_t need = drt::super_order_bytes(units);
-            if (need > h->order_bytes) {
-                if (h->d_order) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_order); h->d_order = nullptr; h->order_bytes = 0; h->order_unit = 0; }
-                if (hipMalloc(&h->d_order, need) == hipSuccess) h->order_bytes = need; else { (void) hipGetLastError(); h->d_order = nullptr; }
-            }
-            if (h->d_order) {
-                // (adjoint launches behind the primal pass of the same job: the primal pass counted every ray's bounce-loop iterations -
-                //  units with a long main path start first, whatever the optical depth along their pixel's ray says)
-                const uint8_t *iters = (DRT_ORDER_ITERS && adjoint && P.path_cache_mode == 2 && sq_ok) ? P.ray_iters : nullptr;
-                const bool reuse = !iters && adjoint && P.path_cache_mode == 2 && h->order_unit == unit && h->order_first == P.ray_first && h->order_end == P.n_rays;
-                if (!reuse) DRT_HIP_CHECK(h, drt::build_super_order(P, unit, units, h->d_order, h->stream, iters));
-                h->order_unit = (!adjoint && P.path_cache_mode == 1) || reuse ? unit : 0u;
-                h->order_first = P.ray_first; h->order_end = P.n_rays;
-                Q.order = (const uint32_t *) h->d_order; Q.order_unit = unit; Q.order_units = units;
-            }
-        }
-        Q.ray_perm = nullptr; Q.block_order = nullptr;
-        // thin medium (as far as the host has seen its majorant - drt_params_changed - without waiting for anything)?  Primal launches in index order then
-        // run the ROUNDS kernels (drt_sq.hip): an optimisation's first iterations, where nearly every ray is over before it begins
-        if (h->majorant_pending && hipEventQuery(h->ev_majorant) == hipSuccess) { h->majorant_seen = *h->h_majorant; h->majorant_pending = false; }
-        else if (h->majorant_pending) (void) hipGetLastError();                        // (hipErrorNotReady is not an error)
-        {
-            const float dx = P.bmax[0] - P.bmin[0], dy = P.bmax[1] - P.bmin[1], dz = P.bmax[2] - P.bmin[2];
-            Q.sq_rounds = (!hg && !adjoint && h->majorant_seen >= 0.0f && h->majorant_seen * std::sqrt(dx * dx + dy * dy + dz * dz) < 3.0f) ? 1u : 0u;
-        }
-        DRT_HIP_CHECK(h, hipMemsetAsync(h->d_queues, 0, 8 * sizeof(unsigned long long), h->stream));
-        if (queued) {
-            Q.sq_cold = h->d_sq_cold;
-#ifndef DRT_SQ_TAIL
-#define DRT_SQ_TAIL 1               // adjoint launches of the queued tracer: drained workgroups hand their last records to a tail pool; 0: they finish them
-#endif
-            // Tail pool (adjoint, deferred splats, the reduction of this very launch follows on h->stream): the last paths of a launch are latency - a
-            // few records per CU, 0.45 ms of the headline's adjoint launch.  Drained workgroups write them to the pool and end; the partition
-            // passes of the gradient reduction (histogram, offsets, scan, scatter: they do not touch the gradient grids) run on a side stream
-            // BESIDE the tail launch, which finishes the pooled records with its splats as direct atomics; tile_reduce follows both.
-            // Below 2 M rays this overlapped kind does not pay (a rank's share of the headline at 8 GPUs, 1 M rays: 3.19 ms per step without the pool,
-            // 3.31 with it - such a launch IS its longest path, a second launch only adds its own start; at 4 GPUs, 2 M rays: 4.00 / 4.07 ms): those
-            // launches take the SOLO kind below.
-            // (test hooks: 268435456 no tail pool, 1073741824 launches from 4096 rays on have one)
-            const uint64_t tail_min = dbg(h->debug_flags, 1073741824u) ? 4096u : (1u << 21);
-            const bool big = adjoint && h->early_plan && Q.rec_buf[0] && span >= tail_min;
-            // Round 5, SOLO tails: where the majorants fit LDS the tail launch runs its records to their ends in registers, without queue hops
-            // (drt_sq.hip: SOLO) - a lone ray's bounce then costs its lookups and one wave's instructions, not eight hand-overs.  That pays
-            // without anything running beside it: the primal launch and the small adjoint launches (a rank's share at 8 GPUs) hand their last
-            // records to a tail launch over the whole chip.  (test hook 268435456: no tail pool of either kind)
-#ifndef DRT_SQ_TAIL_SOLO
-#define DRT_SQ_TAIL_SOLO 3          // bit 0: primal launches, bit 1: adjoint launches below the size of the overlapped tail
-#endif
-            const bool solo = drt::sq_tail_solo(Q) && span >= 8192u && !big &&
-                              (adjoint ? ((DRT_SQ_TAIL_SOLO & 2) != 0 && Q.rec_buf[0] != nullptr) : (DRT_SQ_TAIL_SOLO & 1) != 0);
-#ifndef DRT_SQ_TAIL_THIN
-#define DRT_SQ_TAIL_THIN 0          // 0: primal launches over a thin medium (the ROUNDS kernels) make no tail launch - their few real paths are short, a second
-                                    // launch over the whole chip costs more than they do (config3_as_reproduce 302-305 -> 308-310 iterations/s); 1: they do
-#endif
-            const bool tail = !hg && DRT_SQ_TAIL && (big || solo) && !dbg(h->debug_flags, 268435456u) && (DRT_SQ_TAIL_THIN || !Q.sq_rounds);
-            if (tail) {
-                const size_t cap = (size_t) h->n_cus * drt::sq_tail_push();
-                const size_t need_b = 256 + cap * drt::sq_tail_entry_quads() * sizeof(uint4);
-                if (need_b > h->sq_tail_bytes) {
-                    if (h->d_sq_tail) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_sq_tail); h->d_sq_tail = nullptr; h->sq_tail_bytes = 0; }
-                    if (hipMalloc(&h->d_sq_tail, need_b) == hipSuccess) h->sq_tail_bytes = need_b; else { (void) hipGetLastError(); h->d_sq_tail = nullptr; }
-                }
-                if (h->d_sq_tail) {
-                    DRT_HIP_CHECK(h, hipMemsetAsync(h->d_sq_tail, 0, 256, h->stream));
-                    Q.tail_count = (uint32_t *) h->d_sq_tail; Q.tail_pool = (uint4 *) ((char *) h->d_sq_tail + 256); Q.tail_cap = (uint32_t) cap; Q.tail_mode = 0;
-                }
-            }
-            if (hg) {
-                Q.tail_pool = nullptr; Q.tail_count = nullptr; Q.tail_cap = 0; Q.tail_mode = 0;
-                if (gg) DRT_HIP_CHECK(h, drt::launch_trace_sq_gg(Q, h->n_cus, h->stream));
-                else DRT_HIP_CHECK(h, drt::launch_trace_sq_hg(Q, adjoint, h->counting, h->n_cus, h->stream));
-            }
-            else DRT_HIP_CHECK(h, drt::launch_trace_sq(Q, adjoint, h->counting, h->n_cus, h->stream));
-            if (tail && Q.tail_pool) {
-                hipEvent_t ta = nullptr, tb = nullptr;
-                if (big) {
-                    if (!h->side) {
-                        int lo = 0, hi = 0;
-                        DRT_HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-                        DRT_HIP_CHECK(h, hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, hi));
-                    }
-                    if (!h->ev_split) {
-                        DRT_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_split, hipEventDisableTiming));
-                        DRT_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_hist, hipEventDisableTiming));
-                    }
-                    // the main launch's records are complete (the tail launch emits none): partition them on the side stream ...
-                    DRT_HIP_CHECK(h, hipEventRecord(h->ev_split, h->stream));
-                    DRT_HIP_CHECK(h, hipStreamWaitEvent(h->side, h->ev_split, 0));
-                    if (h->timing) { DRT_HIP_CHECK(h, hipEventCreate(&ta)); DRT_HIP_CHECK(h, hipEventCreate(&tb)); DRT_HIP_CHECK(h, hipEventRecord(ta, h->side)); }
-                    DRT_HIP_CHECK(h, drt::launch_deferred_reduce(Q, *h->early_plan, h->side, nullptr, false, 1));
-                    if (h->timing) { DRT_HIP_CHECK(h, hipEventRecord(tb, h->side)); h->timed[2].emplace_back(ta, tb); }
-                    DRT_HIP_CHECK(h, hipEventRecord(h->ev_hist, h->side));
-                }
-                // ... beside the tail launch: the pool's records to their ends, splats as direct atomics into the caller's grids (no chunk is
-                // handed out: the cursors it touches are dummies in the pool's header - the partition of the main launch's records is under way)
-                drt::Params T = Q;
-                T.tail_mode = big ? 1 : 2;                                 // (2: nothing runs beside it - over the whole chip)
-                if (big) {                                                 // (a SOLO tail of a small launch appends to the record streams: their reduction follows it)
-                    T.rec_cursor = (uint32_t *) h->d_sq_tail + 8;
-                    T.rec_cap_chunks[0] = T.rec_cap_chunks[1] = 0;
-                }
-                T.order = nullptr; T.unit_empty = nullptr;
-                DRT_HIP_CHECK(h, drt::launch_trace_sq(T, adjoint, h->counting, h->n_cus, h->stream));
-                if (big) { h->early_done = true; h->early_partition = true; }
-            }
-        }
-#ifdef DRT_TEST_HOOKS
-        else DRT_HIP_CHECK(h, drt::launch_trace_super(Q, adjoint, h->counting, h->n_cus, h->stream));
-#endif
-        if (h->timing) {
-            DRT_HIP_CHECK(h, hipEventRecord(b, h->stream));
-            h->timed[which].emplace_back(a, b);
-        }
+    if (P.mgrid) {
+        // supergrid: rays stay in image order - neighbouring pixels walk the same supergrid cells, and sorting them
+        // by path length costs more than it saves (24.6 vs 18.8 ms at majorant_resolution_factor 8)
+        drt::Params Q = PT;
+        Q.ray_perm = nullptr;
+        DRT_HIP_CHECK(h, drt::launch_trace_coop(Q, adjoint, h->counting, h->stream));
         return DRT_OK;
     }
-    // (hooks only: 134217728 = supergrid scenes in the round-2 kernels - the state machine of whole flights for the primal pass, 65536 = that
-    //  kernel for any primal pass, 32 = for the adjoint too)
-    const bool sm_primal = drt::kTestHooks && !adjoint && ((P.mgrid != nullptr && dbg(h->debug_flags, 134217728u)) || dbg(h->debug_flags, 65536u)) && !dbg(h->debug_flags, 8u);
-    const bool sm_adjoint = drt::kTestHooks && adjoint && dbg(h->debug_flags, 32u) && !quadratic && !dbg(h->debug_flags, 8u);
-    const bool wavefront = sm_primal || sm_adjoint;
-    const bool coop = !wavefront && !dbg(h->debug_flags, (adjoint ? 32768u : 8u));
-    if (coop) {
-        // tail pool: room for 1/8 of the launch's rays (a workgroup sends at most DRT_TAIL_PUSH = 24 of its 256; a full pool only means that the rest stays where it is), kept while it is big enough;
-        // without it (allocation failed) the kernels simply finish every path where it is
-        drt::Params PT = P;
-        PT.tail_pool = nullptr; PT.tail_count = nullptr; PT.tail_cap = 0; PT.tail_mode = 0;
-        // (launches of fewer than 1.5 M rays finish every path where it is: the tail launch costs them the job's longest
-        //  path once more - 512^2 x 4 spp, an eighth of the headline: adjoint 1.81 -> 1.65 ms without it, x 8 spp 2.22 / 2.20,
-        //  x 32 spp 5.78 / 6.88; test hook 1073741824: small launches are scheduled like large ones)
-        const bool tail_pays = P.n_rays - P.ray_first >= (3u << 19) || dbg(h->debug_flags, 1073741824u);
-        if (adjoint && !P.mgrid && P.n_rays > P.ray_first && tail_pays) {
-            const size_t want = (((size_t) (P.n_rays - P.ray_first) / 8 + 255) / 256) * 256;
-            if (want > h->tail_entries) {
-                if (h->d_tail) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_tail); h->d_tail = nullptr; h->tail_entries = 0; }
-                if (hipMalloc(&h->d_tail, 256 + want * 128) == hipSuccess) h->tail_entries = want; else { (void) hipGetLastError(); h->d_tail = nullptr; }
-            }
-            if (h->d_tail && want >= 256) {
-                PT.tail_count = (uint32_t *) h->d_tail; PT.tail_pool = (uint4 *) ((char *) h->d_tail + 256); PT.tail_cap = (uint32_t) want;
-            }
-        }
-        if (P.mgrid) {
-            // supergrid: rays stay in image order - neighbouring pixels walk the same supergrid cells, and sorting them
-            // by path length costs more than it saves (24.6 vs 18.8 ms at majorant_resolution_factor 8)
-            drt::Params Q = PT;
-            Q.ray_perm = nullptr;
-            DRT_HIP_CHECK(h, drt::launch_trace_coop(Q, adjoint, h->counting, h->stream));
-        } else {
-            // (test hook 268435456: no early histogram pass)
-            const bool early = adjoint && h->early_plan && PT.rec_buf[0] && PT.tail_pool && !dbg(h->debug_flags, 268435456u);
-            if (early && !h->side) {
-                int lo = 0, hi = 0;
-                DRT_HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-                DRT_HIP_CHECK(h, hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, hi));
-            }
-            if (early && !h->ev_split) {
-                DRT_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_split, hipEventDisableTiming));
-                DRT_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_hist, hipEventDisableTiming));
-            }
-            EarlyCtx ctx{ h, &PT };
-            bool called = false;
-            DRT_HIP_CHECK(h, drt::launch_trace_coop(PT, adjoint, h->counting, h->stream, early ? early_histogram_between : nullptr, &ctx, &called));
-            h->early_done = called;
-        }
+    // (kHookNoTailOverlap: no early histogram pass)
+    const bool early = adjoint && h->early_plan && PT.rec_buf[0] && PT.tail_pool && !dbg(h->debug_flags, kHookNoTailOverlap);
+    if (early) {
+        DRT_TRY(ensure_side_stream(h));
+        DRT_TRY(ensure_event_pair(h, h->ev_split, h->ev_hist));
     }
-#ifdef DRT_TEST_HOOKS
-    else if (!wavefront) {
-        drt::Params Q = P;
-        Q.ray_perm = nullptr;
-        DRT_HIP_CHECK(h, drt::launch_trace(Q, adjoint, h->counting, h->stream));
-    }
-    else {
-        drt::Params Q = P;
-        Q.queues = h->d_queues;
-        DRT_HIP_CHECK(h, hipMemsetAsync(h->d_queues, 0, 8 * sizeof(unsigned long long), h->stream));
-        DRT_HIP_CHECK(h, drt::launch_trace_wavefront(Q, adjoint, h->counting, h->n_cus, h->stream));
-    }
-#endif
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventRecord(b, h->stream));
-        h->timed[which].emplace_back(a, b);
+    EarlyCtx ctx{ h, &PT };
+    bool called = false;
+    DRT_HIP_CHECK(h, drt::launch_trace_coop(PT, adjoint, h->counting, h->stream, early ? early_histogram_between : nullptr, &ctx, &called));
+    h->early_done = called;
+    return DRT_OK;
+}
+
+// queued tracer: flag the pixels whose rays cross only empty supergrid cells (best effort: no memory, no flags)
+int bind_unit_empty(drt_handle h, const drt::Params &P, drt::Params &Q)
+{
+    const uint64_t span = P.n_rays - P.ray_first;
+    // (sensor rays whose units are whole pixels: sub-batches, interleaved chunks and offsets that cut a pixel's rays get no flags)
+    if (!(DRT_SQ_UNIT_EMPTY && P.sensor_flow && P.mocc && P.spp && span < (1ull << 31) && P.ray_first % P.spp == 0 &&
+          P.ray_offset % P.spp == 0 && P.chunk % P.spp == 0 && P.stride % P.spp == 0 && !dbg(h->debug_flags, kHookWalkEmptyPixels)))
+        return DRT_OK;
+    const uint32_t eunits = (uint32_t) ((span + P.spp - 1) / P.spp);
+    DRT_TRY(h->uempty.grow(h, eunits, kBestEffort));
+    if (h->uempty.p) {
+        DRT_HIP_CHECK(h, drt::build_unit_empty(P, P.spp, eunits, h->uempty.as<uint8_t>(), h->stream));
+        Q.unit_empty = h->uempty.as<const uint8_t>(); Q.empty_unit = P.spp;
     }
     return DRT_OK;
 }
 
+// Ray order of the supergrid tracers: the longest paths first - units of one pixel's rays by the majorant optical depth along the pixel's ray
+// (drt_super.hip).  Best effort (no memory: index order); kHookIndexOrder: index order.
+// iters_ok: the launch may order its units by the primal pass's iteration counts (the queued tracer)
+int bind_ray_order(drt_handle h, const drt::Params &P, drt::Params &Q, bool adjoint, bool iters_ok)
+{
+    const uint64_t span = P.n_rays - P.ray_first;
+    const uint32_t unit = P.spp >= 4u ? P.spp : 16u;
+    // (units of more rays than a CU traces at a time - the optimisation loop's primal launches, 1024 rays per pixel -
+    //  are too coarse to be scheduled: measured 3-5 % slower in that order than in index order)
+    // (and launches of fewer than 1.5 M rays - six rounds of the chip's 196 608 lanes - gain nothing: 512^2 x 4 spp 1.53 -> 1.69 ms,
+    //  x 8 spp 1.89 -> 1.79 ms, x 32 spp 4.17 -> 3.75 ms; kHookScheduleSmall orders launches from 4096 rays on)
+    //  round 4, queued tracer: a rank's share of the headline at 8 GPUs, 512^2 x 32 spp / 8 = 1 M rays: step 3.83 -> 3.68 ms in that order)
+    const uint64_t min_span = dbg(h->debug_flags, kHookScheduleSmall) ? 4096u : (1u << 20);
+    if (!(span >= min_span && span < (1ull << 31) && unit <= 256u && !dbg(h->debug_flags, kHookIndexOrder))) return DRT_OK;
+    const uint32_t units = (uint32_t) ((span + unit - 1) / unit);
+    const size_t need = drt::super_order_bytes(units);
+    if (need > h->order.bytes) {
+        h->order_unit = 0;                                       // (the stored order goes with its buffer)
+        DRT_TRY(h->order.resize(h, need, kBestEffort));
+    }
+    if (!h->order.p) return DRT_OK;
+    // (adjoint launches behind the primal pass of the same job: the primal pass counted every ray's bounce-loop iterations -
+    //  units with a long main path start first, whatever the optical depth along their pixel's ray says)
+    const uint8_t *iters = (DRT_ORDER_ITERS && adjoint && P.path_cache_mode == 2 && iters_ok) ? P.ray_iters : nullptr;
+    const bool reuse = !iters && adjoint && P.path_cache_mode == 2 && h->order_unit == unit && h->order_first == P.ray_first && h->order_end == P.n_rays;
+    if (!reuse) DRT_HIP_CHECK(h, drt::build_super_order(P, unit, units, h->order.p, h->stream, iters));
+    h->order_unit = (!adjoint && P.path_cache_mode == 1) || reuse ? unit : 0u;
+    h->order_first = P.ray_first; h->order_end = P.n_rays;
+    Q.order = h->order.as<const uint32_t>(); Q.order_unit = unit; Q.order_units = units;
+    return DRT_OK;
+}
+
+// what the launches of the two supergrid tracers (queued, round 3) share: the XCD queues, the ray order, the thin-medium hint
+int begin_supergrid_launch(drt_handle h, const drt::Params &P, drt::Params &Q, bool adjoint, const Choice &c)
+{
+    Q.queues = h->d_queues;
+    DRT_TRY(bind_ray_order(h, P, Q, adjoint, c.route == Route::kQueued));
+    Q.ray_perm = nullptr; Q.block_order = nullptr;
+    // thin medium (as far as the host has seen its majorant - drt_params_changed - without waiting for anything)?  Primal launches in index order then
+    // run the ROUNDS kernels (drt_sq.hip): an optimisation's first iterations, where nearly every ray is over before it begins
+    if (h->majorant_pending && hipEventQuery(h->ev_majorant) == hipSuccess) { h->majorant_seen = *h->h_majorant; h->majorant_pending = false; }
+    else if (h->majorant_pending) (void) hipGetLastError();                        // (hipErrorNotReady is not an error)
+    const float dx = P.bmax[0] - P.bmin[0], dy = P.bmax[1] - P.bmin[1], dz = P.bmax[2] - P.bmin[2];
+    Q.sq_rounds = (!c.hg && !adjoint && h->majorant_seen >= 0.0f && h->majorant_seen * std::sqrt(dx * dx + dy * dy + dz * dz) < 3.0f) ? 1u : 0u;
+    DRT_HIP_CHECK(h, hipMemsetAsync(h->d_queues, 0, 8 * sizeof(unsigned long long), h->stream));
+    return DRT_OK;
+}
+
+// Tail pool of a queued-tracer launch (best effort: without it the workgroups finish their last records themselves).  *big: the overlapped kind.
+// A tail launch follows where Q carries a pool afterwards.
+int bind_sq_tail(drt_handle h, drt::Params &Q, bool adjoint, bool hg, bool *big)
+{
+    const uint64_t span = Q.n_rays - Q.ray_first;
+    // Tail pool (adjoint, deferred splats, the reduction of this very launch follows on h->stream): the last paths of a launch are latency - a
+    // few records per CU, 0.45 ms of the headline's adjoint launch.  Drained workgroups write them to the pool and end; the partition
+    // passes of the gradient reduction (histogram, offsets, scan, scatter: they do not touch the gradient grids) run on a side stream
+    // BESIDE the tail launch, which finishes the pooled records with its splats as direct atomics; tile_reduce follows both.
+    // Below 2 M rays this overlapped kind does not pay (a rank's share of the headline at 8 GPUs, 1 M rays: 3.19 ms per step without the pool,
+    // 3.31 with it - such a launch IS its longest path, a second launch only adds its own start; at 4 GPUs, 2 M rays: 4.00 / 4.07 ms): those
+    // launches take the SOLO kind below.
+    // (test hooks: kHookNoTailOverlap no tail pool, kHookScheduleSmall launches from 4096 rays on have one)
+    const uint64_t tail_min = dbg(h->debug_flags, kHookScheduleSmall) ? 4096u : (1u << 21);
+    *big = adjoint && h->early_plan && Q.rec_buf[0] && span >= tail_min;
+    // Round 5, SOLO tails: where the majorants fit LDS the tail launch runs its records to their ends in registers, without queue hops
+    // (drt_sq.hip: SOLO) - a lone ray's bounce then costs its lookups and one wave's instructions, not eight hand-overs.  That pays
+    // without anything running beside it: the primal launch and the small adjoint launches (a rank's share at 8 GPUs) hand their last
+    // records to a tail launch over the whole chip.  (kHookNoTailOverlap: no tail pool of either kind)
+    const bool solo = drt::sq_tail_solo(Q) && span >= 8192u && !*big &&
+                      (adjoint ? ((DRT_SQ_TAIL_SOLO & 2) != 0 && Q.rec_buf[0] != nullptr) : (DRT_SQ_TAIL_SOLO & 1) != 0);
+    const bool tail = !hg && DRT_SQ_TAIL && (*big || solo) && !dbg(h->debug_flags, kHookNoTailOverlap) && (DRT_SQ_TAIL_THIN || !Q.sq_rounds);
+    if (!tail) return DRT_OK;
+    const size_t cap = (size_t) h->n_cus * drt::sq_tail_push();
+    DRT_TRY(h->sq_tail.grow(h, 256 + cap * drt::sq_tail_entry_quads() * sizeof(uint4), kBestEffort));
+    if (!h->sq_tail.p) return DRT_OK;
+    DRT_HIP_CHECK(h, hipMemsetAsync(h->sq_tail.p, 0, 256, h->stream));
+    Q.tail_count = h->sq_tail.as<uint32_t>(); Q.tail_pool = (uint4 *) (h->sq_tail.as<char>() + 256); Q.tail_cap = (uint32_t) cap; Q.tail_mode = 0;
+    return DRT_OK;
+}
+
+// The queued tracer (drt_sq.hip; round 4) where the ray records fit LDS next to the majorants; h->sq_cold is there
+int launch_queued(drt_handle h, const drt::Params &P, bool adjoint, const Choice &c)
+{
+    drt::Params Q = P;
+    if (adjoint && P.dL_pix) {
+        // the queued tracer reads δL per ray only: its adjoint instantiations sit at the register limit, and the per-pixel read
+        // (load_dL) measurably slowed the default path - expand the image gradient for it (film_backward_kernel: the same bits)
+        const uint64_t px = (P.n_rays + P.spp - 1) / P.spp;   // the pixels of rays [0, n_rays) (a sub-batch may end mid-pixel)
+        DRT_TRY(h->dl_px.grow(h, (size_t) px * P.spp * 3 * sizeof(float), kMust));
+        DRT_HIP_CHECK(h, drt::launch_film_backward(P.dL_pix, px, P.spp, h->dl_px.as<float>(), h->stream));
+        Q.dL = h->dl_px.as<float>(); Q.dL_pix = nullptr;
+    }
+    DRT_TRY(bind_unit_empty(h, P, Q));
+    DRT_TRY(begin_supergrid_launch(h, P, Q, adjoint, c));
+    Q.sq_cold = h->sq_cold.p;
+    bool big = false;
+    DRT_TRY(bind_sq_tail(h, Q, adjoint, c.hg, &big));
+    if (c.hg) {
+        no_tail(Q);
+        if (c.gg) DRT_HIP_CHECK(h, drt::launch_trace_sq_gg(Q, h->n_cus, h->stream));
+        else DRT_HIP_CHECK(h, drt::launch_trace_sq_hg(Q, adjoint, h->counting, h->n_cus, h->stream));
+    }
+    else DRT_HIP_CHECK(h, drt::launch_trace_sq(Q, adjoint, h->counting, h->n_cus, h->stream));
+    if (!Q.tail_pool) return DRT_OK;
+    if (big) {
+        DRT_TRY(ensure_side_stream(h));
+        DRT_TRY(ensure_event_pair(h, h->ev_split, h->ev_hist));
+        // the main launch's records are complete (the tail launch emits none): partition them on the side stream ...
+        DRT_HIP_CHECK(h, hipEventRecord(h->ev_split, h->stream));
+        DRT_HIP_CHECK(h, hipStreamWaitEvent(h->side, h->ev_split, 0));
+        TimedSpan span;
+        DRT_HIP_CHECK(h, span.begin(h, h->side));
+        DRT_HIP_CHECK(h, drt::launch_deferred_reduce(Q, *h->early_plan, h->side, nullptr, false, 1));
+        DRT_HIP_CHECK(h, span.end(2));
+        DRT_HIP_CHECK(h, hipEventRecord(h->ev_hist, h->side));
+    }
+    // ... beside the tail launch: the pool's records to their ends, splats as direct atomics into the caller's grids (no chunk is
+    // handed out: the cursors it touches are dummies in the pool's header - the partition of the main launch's records is under way)
+    drt::Params T = Q;
+    T.tail_mode = big ? 1 : 2;                                 // (2: nothing runs beside it - over the whole chip)
+    if (big) {                                                 // (a SOLO tail of a small launch appends to the record streams: their reduction follows it)
+        T.rec_cursor = h->sq_tail.as<uint32_t>() + 8;
+        T.rec_cap_chunks[0] = T.rec_cap_chunks[1] = 0;
+    }
+    T.order = nullptr; T.unit_empty = nullptr;
+    DRT_HIP_CHECK(h, drt::launch_trace_sq(T, adjoint, h->counting, h->n_cus, h->stream));
+    if (big) { h->early_done = true; h->early_partition = true; }
+    return DRT_OK;
+}
+
+#ifdef DRT_TEST_HOOKS
+// the older generations, kept in lock-step by the variant tests: the round-3 supergrid kernel (which also serves what the queued one does not
+// take), the round-2 state machine of whole flights and the plain per-lane Tracer
+int launch_older(drt_handle h, const drt::Params &P, bool adjoint, const Choice &c)
+{
+    drt::Params Q = P;
+    if (c.route == Route::kSuper3) {
+        DRT_TRY(begin_supergrid_launch(h, P, Q, adjoint, c));
+        DRT_HIP_CHECK(h, drt::launch_trace_super(Q, adjoint, h->counting, h->n_cus, h->stream));
+    } else if (c.route == Route::kWavefront) {
+        Q.queues = h->d_queues;
+        DRT_HIP_CHECK(h, hipMemsetAsync(h->d_queues, 0, 8 * sizeof(unsigned long long), h->stream));
+        DRT_HIP_CHECK(h, drt::launch_trace_wavefront(Q, adjoint, h->counting, h->n_cus, h->stream));
+    } else {
+        Q.ray_perm = nullptr;
+        DRT_HIP_CHECK(h, drt::launch_trace(Q, adjoint, h->counting, h->stream));
+    }
+    return DRT_OK;
+}
+#endif
+
+// one tracing launch, bracketed by an event pair on the handle's stream when timing is enabled
+int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
+{
+    TimedSpan span;
+    DRT_HIP_CHECK(h, span.begin(h, h->stream));
+    const Choice c = choose_tracer(h, P, adjoint);
+    if (c.hg && dbg(h->debug_flags, kHookOlderTracers))
+        return fail(h, DRT_ERR_UNSUPPORTED, "the Henyey-Greenstein phase function has no code in the older tracer generations: the test hook "
+                                            "routes this launch to one of them (debug flags 0x%x)", h->debug_flags);
+    int rc = DRT_OK;
+    switch (c.route) {
+    case Route::kCoopHG:
+    case Route::kOwn: rc = launch_coop_hg_or_own(h, P, adjoint, c); break;
+    case Route::kQueued:
+        // (the records' global halves, ~44 MB, are allocated only by a launch that will run the queued kernel: not when a test hook or the atomic
+        //  gradient path routes this launch to the older kernels; no memory: the route of a supergrid the queued tracer does not take)
+        DRT_TRY(h->sq_cold.grow(h, drt::sq_cold_bytes(h->n_cus), kBestEffort));
+        rc = h->sq_cold.p ? launch_queued(h, P, adjoint, c) : c.hg ? launch_coop_hg_or_own(h, P, adjoint, c) : launch_coop(h, P, adjoint);
+        break;
+    case Route::kCoop: rc = launch_coop(h, P, adjoint); break;
+#ifdef DRT_TEST_HOOKS
+    case Route::kSuper3:
+    case Route::kWavefront:
+    case Route::kPerLane: rc = launch_older(h, P, adjoint, c); break;
+#endif
+    }
+    if (rc) return rc;
+    DRT_HIP_CHECK(h, span.end(which));
+    return DRT_OK;
+}
+
 // Deferred splatting is used for the one-ray-per-lane adjoint kernel when the grid has at most kMaxBins
-// tiles and the record streams fit the memory budget; otherwise (and with debug bit 128) the tracer
+// tiles and the record streams fit the memory budget; otherwise (and with kHookAtomicGradients) the tracer
 // adds its splats to the apron scratch with atomics and untile_gradients_kernel reduces that.
 constexpr int kNoRecordMemory = -1000;                           // internal: record streams could not be allocated
 constexpr uint64_t kRecBudgetBytes = 48ull << 30;               // record streams (emitted + tile-sorted) per sub-batch
 
 bool want_deferred(drt_handle h, const drt::Params &P)
 {
-    if (dbg(h->debug_flags, (128u | 2u | 32u))) return false;          // 128: atomic path; 2: per-lane atomics; 32: state machine
+    if (dbg(h->debug_flags, kHookAtomicGradients | kHookPerLaneAtomics | kHookWavefrontAdjoint)) return false;
     const int ntx = (P.rx + drt::kTileX - 1) / drt::kTileX, nty = (P.ry + drt::kTileY - 1) / drt::kTileY,
               ntz = (P.rz + drt::kTileZ - 1) / drt::kTileZ;
     return (int64_t) ntx * nty * ntz <= drt::kMaxBins;
@@ -633,8 +728,8 @@ int ensure_deferred(drt_handle h, drt_handle_s::RecSlot &R, drt::Params &P, uint
     DeferredPlan &D = R.plan;
     const int ntx = (P.rx + kTileX - 1) / kTileX, nty = (P.ry + kTileY - 1) / kTileY, ntz = (P.rz + kTileZ - 1) / kTileZ;
     const int n_bins = ntx * nty * ntz;
-    const bool tiny = dbg(h->debug_flags, 256u) != 0;                // test hook: force the out-of-chunks path
-    if (!R.mem || n_rays > R.rays || n_bins != R.bins || tiny != R.tiny || per_ray_sigma > R.per_ray[0] ||
+    const bool tiny = dbg(h->debug_flags, kHookTinyRecordStreams);   // test hook: force the out-of-chunks path
+    if (!R.mem.p || n_rays > R.rays || n_bins != R.bins || tiny != R.tiny || per_ray_sigma > R.per_ray[0] ||
         per_ray_colour > R.per_ray[1]) {
         // capacity: every wave may leave one chunk group partly filled per stream, plus the expected volume;
         // beyond it the tracer falls back to direct atomics (emit_record): a performance choice only
@@ -657,20 +752,15 @@ int ensure_deferred(drt_handle h, drt_handle_s::RecSlot &R, drt::Params &P, uint
             o_in[s] = carve(chunks[s] * kRecChunk * quads[s] * sizeof(float4));
             o_out[s] = carve(chunks[s] * kRecChunk * quads[s] * sizeof(float4));
         }
-        if (off > R.bytes) {
-            if (R.mem) {
-                DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-                if (h->side) DRT_HIP_CHECK(h, hipStreamSynchronize(h->side));
-                (void) hipFree(R.mem); R.mem = nullptr; R.bytes = 0;
-            }
-            if (dbg(h->debug_flags, 262144u) || hipMalloc(&R.mem, off) != hipSuccess) {   // not enough memory for the record streams (bit 262144: simulate):
-                (void) hipGetLastError();                         // this job uses the atomic path instead
-                R.mem = nullptr; R.rays = 0;
+        if (off > R.mem.bytes) {
+            // (the reduction of the slot's last launch may still run on the side stream)
+            DRT_TRY(R.mem.resize(h, off, kBestEffort, true, dbg(h->debug_flags, kHookNoRecordMemory)));
+            if (!R.mem.p) {                                       // not enough memory for the record streams (kHookNoRecordMemory: simulate):
+                R.rays = 0;                                       // this job uses the atomic path instead
                 return kNoRecordMemory;
             }
-            R.bytes = off;
         }
-        char *b = (char *) R.mem;
+        char *b = R.mem.as<char>();
         D.cursor = (uint32_t *) (b + o_cursor);
         D.vmax = D.cursor + 8;
         uint64_t max_chunks = 0;
@@ -690,83 +780,93 @@ int ensure_deferred(drt_handle h, drt_handle_s::RecSlot &R, drt::Params &P, uint
     // (7 x 25 x 25 voxels: 1 x 2 x 1 tiles, then 25 x 3 x 5: 1 x 1 x 2 - the records went to the wrong tiles and part of the gradient was lost;
     //  found by tests/test_gpu_fuzz.py::test_random_sequence_on_one_handle_matches_the_oracle, round 6)
     D.ntx = ntx; D.nty = nty; D.ntz = ntz;
-    DRT_HIP_CHECK(h, hipMemsetAsync(R.mem, 0, R.clear_bytes, h->stream));
+    DRT_HIP_CHECK(h, hipMemsetAsync(R.mem.p, 0, R.clear_bytes, h->stream));
     for (int s = 0; s < 2; ++s) { P.rec_buf[s] = D.in[s]; P.rec_chunk_count[s] = D.chunk_count[s]; P.rec_cap_chunks[s] = D.cap_chunks[s]; }
     P.rec_cursor = D.cursor;
     return DRT_OK;
 }
 
-int timed_reduce(drt_handle h, const drt::Params &P, const drt::DeferredPlan &D, hipStream_t stream, bool early_hist = false, int phase = 0);
-int timed_untile(drt_handle h, const drt::Params &P);
+int timed_reduce(drt_handle h, const drt::Params &P, const drt::DeferredPlan &D, hipStream_t stream, bool early_hist = false, int phase = 0)
+{
+    TimedSpan span;
+    DRT_HIP_CHECK(h, span.begin(h, stream));
+    DRT_HIP_CHECK(h, drt::launch_deferred_reduce(P, D, stream, nullptr, early_hist, phase));
+    DRT_HIP_CHECK(h, span.end(2));
+    return DRT_OK;
+}
+
+int timed_nerf(drt_handle h, int which, const drt::Params &P, bool adjoint, hipStream_t st = nullptr)
+{
+    if (!st) st = h->stream;
+    TimedSpan span;
+    DRT_HIP_CHECK(h, span.begin(h, st));
+    DRT_HIP_CHECK(h, P.colour_own ? drt::launch_nerf_own(P, adjoint, h->counting, st) : drt::launch_nerf(P, adjoint, h->counting, st));
+    DRT_HIP_CHECK(h, span.end(which));
+    return DRT_OK;
+}
+
+int timed_untile(drt_handle h, const drt::Params &P)
+{
+    TimedSpan span;
+    DRT_HIP_CHECK(h, span.begin(h, h->stream));
+    DRT_HIP_CHECK(h, drt::launch_untile(P, h->stream));
+    DRT_HIP_CHECK(h, span.end(2));
+    return DRT_OK;
+}
 
 // Adjoint launch + gradient reduction of one job.  Deferred path: the job is cut into sub-batches of rays
-// whose record streams fit the memory budget.  With DRT_PIPELINE set, large jobs are cut into
+// whose record streams fit the memory budget.  Test hook kHookPipelineBatches: the job is cut into
 // >= kPipeBatches pieces and pipelined over two record slots (tracer of sub-batch b on the caller's stream,
 // partition + reduction of sub-batch b - 1 on a side stream; the caller's stream waits for every
 // reduction at the end) - an experiment that measured slower than running them back to back.
-constexpr uint64_t kPipeBatches = 4, kPipeMinRays = 1ull << 20;
+constexpr uint64_t kPipeBatches = 4;
 
 template <class Launch>
 int run_backward(drt_handle h, drt::Params &P, uint32_t per_ray_sigma, uint32_t per_ray_colour, Launch launch)
 {
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventCreate(&t0));
-        DRT_HIP_CHECK(h, hipEventCreate(&t1));
-        DRT_HIP_CHECK(h, hipEventRecord(t0, h->stream));
-    }
+    TimedSpan whole;
+    DRT_HIP_CHECK(h, whole.begin(h, h->stream));
     if (!want_deferred(h, P)) {
-        int rc = launch(P);
-        if (rc) return rc;
-        rc = timed_untile(h, P);
-        if (rc) return rc;
+        DRT_TRY(launch(P));
+        DRT_TRY(timed_untile(h, P));
     } else {
         const uint64_t n_rays = P.n_rays;
         const uint64_t bytes_per_ray = 32ull * (uint64_t) per_ray_sigma + 64ull * (uint64_t) per_ray_colour + 1024ull;   // streams in + sorted, chunk slack
         // measured on the headline workload: overlapping costs more than it hides (tracer 15.0 -> 19.8 ms
         // with the reductions alongside, step 22.1 -> 24.7 ms), so the overlap is opt-in
-        const bool forced = dbg(h->debug_flags, 2048u);         // test hook: overlap the reductions with the next sub-batch's tracer
-        const bool want_pipe = forced;
-        const uint64_t want_pipe_slots = want_pipe ? 2 : 1;
-        uint64_t budget = dbg(h->debug_flags, 16384u) ? (8ull << 20) : kRecBudgetBytes;   // test hook: 8 MB -> many sub-batches
+        const bool overlap = dbg(h->debug_flags, kHookPipelineBatches);   // test hook: overlap the reductions with the next sub-batch's tracer
+        const uint64_t slots = overlap ? 2 : 1;
+        uint64_t budget = dbg(h->debug_flags, kHookSmallRecordBudget) ? (8ull << 20) : kRecBudgetBytes;   // test hook: 8 MB -> many sub-batches
         {   // never ask for more than the device can give next to the caller's (torch's) allocations: what the slots
             // hold already plus 80 % of what is free now; smaller budgets only mean more ray sub-batches
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                const uint64_t have = (uint64_t) h->rec[0].bytes + (uint64_t) h->rec[1].bytes;
+                const uint64_t have = (uint64_t) h->rec[0].mem.bytes + (uint64_t) h->rec[1].mem.bytes;
                 const uint64_t room = have + (uint64_t) ((double) free_b * 0.8);
                 if (room < budget) budget = room;
             } else (void) hipGetLastError();
-            const uint64_t floor_b = 256ull * bytes_per_ray * want_pipe_slots;     // at least one workgroup of rays per slot
+            const uint64_t floor_b = 256ull * bytes_per_ray * slots;     // at least one workgroup of rays per slot
             if (budget < floor_b) budget = floor_b;
         }
-        uint64_t batch = (budget / want_pipe_slots) / bytes_per_ray;
-        const bool pipe = want_pipe && (forced || n_rays >= kPipeMinRays);
-        if (pipe && batch > (n_rays + kPipeBatches - 1) / kPipeBatches) batch = (n_rays + kPipeBatches - 1) / kPipeBatches;
+        uint64_t batch = (budget / slots) / bytes_per_ray;
+        if (overlap && batch > (n_rays + kPipeBatches - 1) / kPipeBatches) batch = (n_rays + kPipeBatches - 1) / kPipeBatches;
         // whole ray-schedule groups (kPermGroup rays = 4 workgroups) and XCD runs per sub-batch
-        batch = dbg(h->debug_flags, 16384u) ? (batch + drt::kPermGroup - 1) / drt::kPermGroup * drt::kPermGroup : (batch + 65535) / 65536 * 65536;
-        const bool overlap = pipe;
-        if (overlap && !h->side) {
-            int lo = 0, hi = 0;
-            DRT_HIP_CHECK(h, hipDeviceGetStreamPriorityRange(&lo, &hi));
-            DRT_HIP_CHECK(h, hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, hi));
-        }
+        batch = dbg(h->debug_flags, kHookSmallRecordBudget) ? (batch + drt::kPermGroup - 1) / drt::kPermGroup * drt::kPermGroup : (batch + 65535) / 65536 * 65536;
+        if (overlap) DRT_TRY(ensure_side_stream(h));
         int b = 0;
         for (uint64_t first = 0; first < n_rays; first += batch, ++b) {
             auto &R = h->rec[overlap ? (b & 1) : 0];
             const uint64_t count = n_rays - first < batch ? n_rays - first : batch;
             if (R.busy) { DRT_HIP_CHECK(h, hipStreamWaitEvent(h->stream, R.reduced, 0)); R.busy = false; }
             int rc = ensure_deferred(h, R, P, count, per_ray_sigma, per_ray_colour,
-                                     dbg(h->debug_flags, 524288u) && first > 0);   // test hook: memory runs out after the first sub-batch
+                                     dbg(h->debug_flags, kHookNoRecordMemoryLater) && first > 0);   // test hook: memory runs out after the first sub-batch
             if (rc == kNoRecordMemory) {
                 // no memory for the record streams (now): the rays that are left, [first, n_rays), take the
                 // atomic path (splats into the apron scratch + untile) - slower, same gradients
                 for (int s2 = 0; s2 < 2; ++s2) P.rec_buf[s2] = nullptr;
                 P.rec_cursor = nullptr; P.ray_first = first; P.n_rays = n_rays;
-                rc = launch(P);
-                if (rc) return rc;
-                rc = timed_untile(h, P);
-                if (rc) return rc;
+                DRT_TRY(launch(P));
+                DRT_TRY(timed_untile(h, P));
                 break;
             }
             if (rc) return rc;
@@ -778,15 +878,13 @@ int run_backward(drt_handle h, drt::Params &P, uint32_t per_ray_sigma, uint32_t 
                 const bool early = h->early_done, part = h->early_partition;
                 h->early_plan = nullptr; h->early_done = false; h->early_partition = false;
                 if (early) DRT_HIP_CHECK(h, hipStreamWaitEvent(h->stream, h->ev_hist, 0));
-                rc = timed_reduce(h, P, R.plan, h->stream, early && !part, part ? 2 : 0);
-                if (rc) return rc;
+                DRT_TRY(timed_reduce(h, P, R.plan, h->stream, early && !part, part ? 2 : 0));
                 continue;
             }
-            if (!R.traced) { DRT_HIP_CHECK(h, hipEventCreateWithFlags(&R.traced, hipEventDisableTiming)); DRT_HIP_CHECK(h, hipEventCreateWithFlags(&R.reduced, hipEventDisableTiming)); }
+            DRT_TRY(ensure_event_pair(h, R.traced, R.reduced));
             DRT_HIP_CHECK(h, hipEventRecord(R.traced, h->stream));
             DRT_HIP_CHECK(h, hipStreamWaitEvent(h->side, R.traced, 0));
-            rc = timed_reduce(h, P, R.plan, h->side);
-            if (rc) return rc;
+            DRT_TRY(timed_reduce(h, P, R.plan, h->side));
             DRT_HIP_CHECK(h, hipEventRecord(R.reduced, h->side));
             R.busy = true;
         }
@@ -794,59 +892,7 @@ int run_backward(drt_handle h, drt::Params &P, uint32_t per_ray_sigma, uint32_t 
             if (R.busy) { DRT_HIP_CHECK(h, hipStreamWaitEvent(h->stream, R.reduced, 0)); R.busy = false; }
         P.ray_first = 0; P.n_rays = n_rays;
     }
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventRecord(t1, h->stream));
-        h->timed[3].emplace_back(t0, t1);
-    }
-    return DRT_OK;
-}
-
-int timed_reduce(drt_handle h, const drt::Params &P, const drt::DeferredPlan &D, hipStream_t stream, bool early_hist, int phase)
-{
-    hipEvent_t a = nullptr, b = nullptr;
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventCreate(&a));
-        DRT_HIP_CHECK(h, hipEventCreate(&b));
-        DRT_HIP_CHECK(h, hipEventRecord(a, stream));
-    }
-    DRT_HIP_CHECK(h, drt::launch_deferred_reduce(P, D, stream, nullptr, early_hist, phase));
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventRecord(b, stream));
-        h->timed[2].emplace_back(a, b);
-    }
-    return DRT_OK;
-}
-
-int timed_nerf(drt_handle h, int which, const drt::Params &P, bool adjoint, hipStream_t st = nullptr)
-{
-    if (!st) st = h->stream;
-    hipEvent_t a = nullptr, b = nullptr;
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventCreate(&a));
-        DRT_HIP_CHECK(h, hipEventCreate(&b));
-        DRT_HIP_CHECK(h, hipEventRecord(a, st));
-    }
-    DRT_HIP_CHECK(h, P.colour_own ? drt::launch_nerf_own(P, adjoint, h->counting, st) : drt::launch_nerf(P, adjoint, h->counting, st));
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventRecord(b, st));
-        h->timed[which].emplace_back(a, b);
-    }
-    return DRT_OK;
-}
-
-int timed_untile(drt_handle h, const drt::Params &P)
-{
-    hipEvent_t a = nullptr, b = nullptr;
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventCreate(&a));
-        DRT_HIP_CHECK(h, hipEventCreate(&b));
-        DRT_HIP_CHECK(h, hipEventRecord(a, h->stream));
-    }
-    DRT_HIP_CHECK(h, drt::launch_untile(P, h->stream));
-    if (h->timing) {
-        DRT_HIP_CHECK(h, hipEventRecord(b, h->stream));
-        h->timed[2].emplace_back(a, b);
-    }
+    DRT_HIP_CHECK(h, whole.end(3));
     return DRT_OK;
 }
 
@@ -898,38 +944,14 @@ int drt_destroy(drt_handle h)
 {
     if (!h) return DRT_OK;
     DeviceGuard g(h->device);
-    if (h->d_majorant) (void) hipFree(h->d_majorant);
+    // what drt_create and the emitter made, then the events and streams made on demand; every DevBuf frees itself with the handle
+    for (void *p : { (void *) h->d_majorant, (void *) h->d_scratch, (void *) h->d_counters, (void *) h->d_queues, (void *) h->d_occ, (void *) h->d_env })
+        if (p) (void) hipFree(p);
     if (h->h_majorant) (void) hipHostFree(h->h_majorant);
-    if (h->ev_majorant) (void) hipEventDestroy(h->ev_majorant);
-    if (h->d_scratch) (void) hipFree(h->d_scratch);
-    if (h->d_counters) (void) hipFree(h->d_counters);
-    if (h->d_gt) (void) hipFree(h->d_gt);
-    if (h->d_queues) (void) hipFree(h->d_queues);
-    if (h->d_order) (void) hipFree(h->d_order);
-    if (h->d_uempty) (void) hipFree(h->d_uempty);
-    if (h->d_sq_tail) (void) hipFree(h->d_sq_tail);
-    if (h->d_sq_cold) (void) hipFree(h->d_sq_cold);
-    if (h->d_tail) (void) hipFree(h->d_tail);
-    if (h->d_sigma_b) (void) hipFree(h->d_sigma_b);
-    if (h->d_mgrid) (void) hipFree(h->d_mgrid);
-    if (h->d_occ) (void) hipFree(h->d_occ);
-    if (h->d_env) (void) hipFree(h->d_env);
-    if (h->d_grid4) (void) hipFree(h->d_grid4);
-    for (auto &R : h->rec) {
-        if (R.mem) (void) hipFree(R.mem);
-        if (R.traced) (void) hipEventDestroy(R.traced);
-        if (R.reduced) (void) hipEventDestroy(R.reduced);
-    }
-    if (h->side) (void) hipStreamDestroy(h->side);
-    if (h->nerf_stream) (void) hipStreamDestroy(h->nerf_stream);
-    if (h->ev_fork) (void) hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void) hipEventDestroy(h->ev_join);
-    if (h->d_nerf_bounds) (void) hipFree(h->d_nerf_bounds);
-    if (h->d_loss_partials) (void) hipFree(h->d_loss_partials);
-    if (h->d_dl_px) (void) hipFree(h->d_dl_px);
-    if (h->ev_split) (void) hipEventDestroy(h->ev_split);
-    if (h->ev_hist) (void) hipEventDestroy(h->ev_hist);
-    if (h->d_pcache) (void) hipFree(h->d_pcache);
+    for (hipEvent_t e : { h->ev_majorant, h->ev_fork, h->ev_join, h->ev_split, h->ev_hist, h->rec[0].traced, h->rec[0].reduced, h->rec[1].traced, h->rec[1].reduced })
+        if (e) (void) hipEventDestroy(e);
+    for (hipStream_t st : { h->side, h->nerf_stream })
+        if (st) (void) hipStreamDestroy(st);
     clear_timings(h);
     delete h;
     return DRT_OK;
@@ -941,16 +963,16 @@ int drt_release_scratch(drt_handle h)
     DeviceGuard g(h->device);
     DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     if (h->side) DRT_HIP_CHECK(h, hipStreamSynchronize(h->side));
+    // the buffers sized by the job: record slots, path cache, the cooperative kernels' tail pool, the expanded δL.  The queued tracer's
+    // scratch (order, uempty, sq_tail, sq_cold), the loss partials and the copies of the medium stay until the handle goes.
     for (auto &R : h->rec) {
-        if (R.mem) (void) hipFree(R.mem);
-        R.mem = nullptr; R.bytes = 0; R.rays = 0; R.bins = 0; R.busy = false;
+        R.mem.release();
+        R.rays = 0; R.bins = 0; R.busy = false;
     }
-    if (h->d_pcache) (void) hipFree(h->d_pcache);
-    h->d_pcache = nullptr; h->pcache_bytes = 0; h->pcache_sig.valid = false; h->order_valid = false; h->order_rays = 0;
-    if (h->d_tail) (void) hipFree(h->d_tail);
-    h->d_tail = nullptr; h->tail_entries = 0;
-    if (h->d_dl_px) (void) hipFree(h->d_dl_px);
-    h->d_dl_px = nullptr; h->dl_px_bytes = 0;
+    h->pcache.release();
+    h->pcache_sig.valid = false; h->order_valid = false; h->order_rays = 0;
+    h->tail.release();
+    h->dl_px.release();
     return DRT_OK;
 }
 
@@ -989,7 +1011,7 @@ int drt_params_changed(drt_handle h)
     //  less per optimisation step)
     if (h->base.mgrid)
         DRT_HIP_CHECK(h, drt::launch_majorant_grid(h->base.sigma_t, h->base.rx, h->base.ry, h->base.rz, h->base.gx, h->base.gy,
-                                                   h->base.gz, h->base.scale, h->d_mgrid, (uint32_t *) h->base.mocc, h->stream,
+                                                   h->base.gz, h->base.scale, h->mgrid.as<float>(), (uint32_t *) h->base.mocc, h->stream,
                                                    h->d_scratch, h->d_majorant, (uint32_t *) h->base.mocc_dil));
     else
         DRT_HIP_CHECK(h, drt::launch_majorant(h->base.sigma_t, n, h->base.scale, h->d_scratch, h->d_majorant, h->stream));
@@ -1003,7 +1025,7 @@ int drt_params_changed(drt_handle h)
     }
     DRT_HIP_CHECK(h, drt::launch_occupancy(h->base.sigma_t, h->base.rx, h->base.ry, h->base.rz, h->base.occ_shift, h->base.occ_x,
                                            h->base.occ_y, h->occ_z, h->d_occ, h->base.occ_words, h->stream));
-    DRT_HIP_CHECK(h, drt::launch_brick_sigma(h->base.sigma_t, h->d_sigma_b, h->base.rx, h->base.ry, h->base.rz,
+    DRT_HIP_CHECK(h, drt::launch_brick_sigma(h->base.sigma_t, h->sigma_b.as<float>(), h->base.rx, h->base.ry, h->base.rz,
                                              h->base.sb_ystride, h->base.sb_zstride / h->base.sb_ystride, h->stream));
     return DRT_OK;
 }
@@ -1042,28 +1064,25 @@ int drt_set_medium(drt_handle h, const float *sigma_t, const float *albedo, cons
         size_t nbx = ((size_t) res[0] + 2) / 3;
         size_t plane = nbx * (size_t) res[1] * (size_t) res[2] * 16;
         if (plane > 0x7fffffffull) return fail(h, DRT_ERR_UNSUPPORTED, "grid too large for the gradient scratch");
-        if (plane * 4 != h->gt_floats) {
+        if (plane * 4 * sizeof(float) != h->gt.bytes) {
             DeviceGuard g(h->device);
-            if (h->d_gt) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_gt); h->d_gt = nullptr; h->gt_floats = 0; }
-            DRT_HIP_CHECK(h, hipMalloc(&h->d_gt, plane * 4 * sizeof(float)));
-            DRT_HIP_CHECK(h, hipMemsetAsync(h->d_gt, 0, plane * 4 * sizeof(float), h->stream));
-            h->gt_floats = plane * 4;
+            DRT_TRY(h->gt.resize(h, plane * 4 * sizeof(float), kMust));
+            DRT_HIP_CHECK(h, hipMemsetAsync(h->gt.p, 0, h->gt.bytes, h->stream));
         }
-        B.gt = h->d_gt; B.gt_plane = (uint32_t) plane; B.gt_nbx = (int) nbx;
+        B.gt = h->gt.as<float>(); B.gt_plane = (uint32_t) plane; B.gt_nbx = (int) nbx;
     }
     // majorant supergrid (0 = global majorant only)
     if (majorant_resolution_factor > 0) {
         int G[3];
         for (int a = 0; a < 3; ++a) { G[a] = res[a] / majorant_resolution_factor; if (G[a] < 1) G[a] = 1; }
         size_t cells = (size_t) G[0] * G[1] * G[2];
-        if (cells != h->mgrid_cells) {
+        const size_t mgrid_bytes = (cells + 2 * ((cells + 31) / 32)) * sizeof(float);   // majorants | non-empty bitmask | the same, dilated by one cell
+        if (mgrid_bytes != h->mgrid.bytes) {                      // (a size per cell count)
             DeviceGuard g(h->device);
-            if (h->d_mgrid) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_mgrid); h->d_mgrid = nullptr; h->mgrid_cells = 0; }
-            DRT_HIP_CHECK(h, hipMalloc(&h->d_mgrid, (cells + 2 * ((cells + 31) / 32)) * sizeof(float)));   // majorants | non-empty bitmask | the same, dilated by one cell
-            h->mgrid_cells = cells;
+            DRT_TRY(h->mgrid.resize(h, mgrid_bytes, kMust));
         }
-        B.mgrid = h->d_mgrid; B.gx = G[0]; B.gy = G[1]; B.gz = G[2];
-        B.mocc = (const uint32_t *) (h->d_mgrid + cells); B.mocc_words = (int) ((cells + 31) / 32);
+        B.mgrid = h->mgrid.as<float>(); B.gx = G[0]; B.gy = G[1]; B.gz = G[2];
+        B.mocc = (const uint32_t *) (B.mgrid + cells); B.mocc_words = (int) ((cells + 31) / 32);
         B.mocc_dil = B.mocc + B.mocc_words;
     } else {
         B.mgrid = nullptr; B.gx = B.gy = B.gz = 0; B.mocc = nullptr; B.mocc_words = 0; B.mocc_dil = nullptr;
@@ -1089,13 +1108,11 @@ int drt_set_medium(drt_handle h, const float *sigma_t, const float *albedo, cons
         if (nbx * nby * (size_t) res[2] > 0x7ffffffull || res[0] > 21000 || res[1] > 21000 || nbx * nby >= (1u << 24) ||
             res[2] >= (1 << 24))                                   // eval_sigma_t indexes with 24-bit multiplies
             return fail(h, DRT_ERR_UNSUPPORTED, "grid too large for the apron-brick copy");
-        if (floats != h->sigma_b_floats) {
+        if (floats * sizeof(float) != h->sigma_b.bytes) {
             DeviceGuard g(h->device);
-            if (h->d_sigma_b) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_sigma_b); h->d_sigma_b = nullptr; h->sigma_b_floats = 0; }
-            DRT_HIP_CHECK(h, hipMalloc(&h->d_sigma_b, floats * sizeof(float)));
-            h->sigma_b_floats = floats;
+            DRT_TRY(h->sigma_b.resize(h, floats * sizeof(float), kMust));
         }
-        B.sigma_b = h->d_sigma_b;
+        B.sigma_b = h->sigma_b.as<float>();
         B.sb_ystride = (int) nbx; B.sb_zstride = (int) (nby * nbx);
     }
     h->have_medium = true; h->scene_version++;
@@ -1287,8 +1304,7 @@ int drt_render_primal(drt_handle h, const float *rays_o, const float *rays_d, ui
                       uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
 {
     if (h && n_rays == 0) return DRT_OK;    /* empty batch: nothing to enqueue */
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
     if (!L_out && n_rays) return fail(h, DRT_ERR_INVALID_ARGUMENT, "null L_out");
     DeviceGuard g(h->device);
     drt::Params P;
@@ -1298,25 +1314,22 @@ int drt_render_primal(drt_handle h, const float *rays_o, const float *rays_d, ui
     bind_path_cache_write(h, P);                                 // every primal kernel records its walks
     {   // the block order left by the previous primal launch of the same shape predicts this one's heavy blocks
         // (same sensor, next step); an order is only ever a schedule, never a result
-        const bool no_lpt = dbg(h->debug_flags, 16777216u);   // test hook: plain XCD block map
-        const uint64_t n_blocks = (n_rays + 255) / 256;
-        (void) n_blocks;
-        if (!no_lpt && P.block_cost && h->order_rays == n_rays && !P.mgrid &&
-            !dbg(h->debug_flags, (8u | 65536u)))
-            P.block_order = P.block_cost + n_blocks;
+        if (!dbg(h->debug_flags, kHookPlainBlockMap) && P.block_cost && h->order_rays == n_rays && !P.mgrid &&
+            !dbg(h->debug_flags, kHookPrimalNotCoop))
+            P.block_order = P.block_cost + (n_rays + 255) / 256;
     }
-    rc = timed_launch(h, 0, P, false);
+    int rc = timed_launch(h, 0, P, false);
     h->order_valid = false;
     h->perm_valid = false;
     // the cooperative primal kernel (global majorant) and the state machine (supergrid) write the sort keys
     // (only the global-majorant adjoint kernel takes its rays through the schedule: supergrid scenes skip the sort - 0.065 ms of the
     //  factor-8 headline's step)
-    if (rc == DRT_OK && P.ray_iters && !P.mgrid && !dbg(h->debug_flags, 8u)) {   // (the plain per-lane primal kernel, bit 8, does not)
-        const bool coop_costs = P.block_cost && !P.mgrid && !dbg(h->debug_flags, 65536u);        // the cooperative primal filled block_cost
+    if (rc == DRT_OK && P.ray_iters && !P.mgrid && !dbg(h->debug_flags, kHookPerLanePrimal)) {   // (the plain per-lane primal kernel does not)
+        const bool coop_costs = P.block_cost && !P.mgrid && !dbg(h->debug_flags, kHookWavefrontPrimal);        // the cooperative primal filled block_cost
         DRT_HIP_CHECK(h, drt::launch_ray_perm(P.ray_iters, P.n_rays, perm_base(P.ray_hash, P.n_rays), coop_costs ? P.block_cost : nullptr, h->stream));
         h->perm_valid = true;
     }
-    if (rc == DRT_OK && P.block_cost && !P.mgrid && !dbg(h->debug_flags, (8u | 65536u))) {   // cooperative primal: it filled block_cost
+    if (rc == DRT_OK && P.block_cost && !P.mgrid && !dbg(h->debug_flags, kHookPrimalNotCoop)) {   // cooperative primal: it filled block_cost
         const uint32_t n_blocks = (uint32_t) ((P.n_rays + 255) / 256);
         DRT_HIP_CHECK(h, drt::launch_block_order(P.block_cost, n_blocks, P.block_cost + n_blocks, n_blocks <= kHeavyFirstMaxBlocks, h->stream));
         h->order_valid = true; h->order_rays = n_rays;
@@ -1326,7 +1339,7 @@ int drt_render_primal(drt_handle h, const float *rays_o, const float *rays_d, ui
 
 // the adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel, drt_render_backward_px) is given
 // grad_phase_g (drt_render_backward_phase, an HG handle): dLoss/dg is added to *grad_phase_g - it travels in Params::L_out, which no adjoint
-// kernel otherwise reads or writes, and selects the GG kernels (timed_launch)
+// kernel otherwise reads or writes, and selects the GG kernels (choose_tracer)
 static int render_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
                            uint32_t seed, const float *dL, const float *dL_pix, const float *L_in, float *grad_sigma_t, float *grad_albedo,
                            float *grad_phase_g = nullptr)
@@ -1341,7 +1354,7 @@ static int render_backward(drt_handle h, const float *rays_o, const float *rays_
     // tracer falls back to direct atomics (emit_record), so this is a performance choice only
     const uint64_t job_rays = n_rays;
     rc = run_backward(h, P, 48, 6, [&](drt::Params &Q) {
-        if (!dbg(h->debug_flags, 32u) || dbg(h->debug_flags, 8u)) bind_path_cache_read(h, Q, job_rays);      // ... and every adjoint kernel but it
+        if (!dbg(h->debug_flags, kHookWavefrontAdjoint) || dbg(h->debug_flags, kHookPerLanePrimal)) bind_path_cache_read(h, Q, job_rays);      // ... and every adjoint kernel but it
         return timed_launch(h, 1, Q, true);
     });
     h->pcache_sig.valid = false;
@@ -1353,8 +1366,7 @@ int drt_render_backward(drt_handle h, const float *rays_o, const float *rays_d, 
                         const float *L_in, float *grad_sigma_t, float *grad_albedo)
 {
     if (h && n_rays == 0) return DRT_OK;
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
     if (n_rays && (!dL || !L_in || !grad_sigma_t || !grad_albedo))
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward: null dL / L_in / gradient buffer");
     return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo);
@@ -1372,10 +1384,8 @@ static int check_phase_grad(drt_handle h, const char *what, bool wanted)
 int drt_render_backward_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
                               uint32_t seed, const float *dL, const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g)
 {
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
-    rc = check_phase_grad(h, "drt_render_backward_phase", grad_phase_g != nullptr);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
+    DRT_TRY(check_phase_grad(h, "drt_render_backward_phase", grad_phase_g != nullptr));
     if (n_rays == 0) return DRT_OK;
     if (!dL || !L_in || !grad_sigma_t || !grad_albedo)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_phase: null dL / L_in / gradient buffer");
@@ -1400,21 +1410,14 @@ static int ensure_grid4(drt_handle h, drt::Params &P, const float *rgb);
 static int nerf_backward(drt_handle h, drt::Params &P, const drt_nerf_config *cfg, bool g4, hipStream_t st = nullptr)
 {
     if (!st) st = h->stream;
-    if (drt::nerf_tile_supported(P) && !dbg(h->debug_flags, 512u)) {
-        hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };   // (tracer slot and whole-pass slot: the pass is this launch)
-        if (h->timing) {
-            for (auto &e : ev) DRT_HIP_CHECK(h, hipEventCreate(&e));
-            DRT_HIP_CHECK(h, hipEventRecord(ev[0], st));
-            DRT_HIP_CHECK(h, hipEventRecord(ev[2], st));
-        }
-        if (!h->d_nerf_bounds) DRT_HIP_CHECK(h, hipMalloc((void **) &h->d_nerf_bounds, 32));
-        DRT_HIP_CHECK(h, drt::launch_nerf_tile_adjoint(P, g4, h->counting, h->d_nerf_bounds, st));
-        if (h->timing) {
-            DRT_HIP_CHECK(h, hipEventRecord(ev[1], st));
-            DRT_HIP_CHECK(h, hipEventRecord(ev[3], st));
-            h->timed[1].emplace_back(ev[0], ev[1]);
-            h->timed[3].emplace_back(ev[2], ev[3]);
-        }
+    if (drt::nerf_tile_supported(P) && !dbg(h->debug_flags, kHookNerfRecordPath)) {
+        TimedSpan tracer, whole;                                     // (tracer slot and whole-pass slot: the pass is this launch)
+        DRT_HIP_CHECK(h, tracer.begin(h, st));
+        DRT_HIP_CHECK(h, whole.begin(h, st));
+        DRT_TRY(h->nerf_bounds.grow(h, 32, kMust));
+        DRT_HIP_CHECK(h, drt::launch_nerf_tile_adjoint(P, g4, h->counting, h->nerf_bounds.as<uint32_t>(), st));
+        DRT_HIP_CHECK(h, tracer.end(1));
+        DRT_HIP_CHECK(h, whole.end(3));
         return DRT_OK;
     }
     const uint32_t q = (uint32_t) cfg->queries_per_ray;          // at most one splat per query and plane
@@ -1426,14 +1429,12 @@ static int nerf_primal(drt_handle h, const drt_nerf_config *cfg, const float *em
                        float *L_out, bool fused_half, hipStream_t st = nullptr)
 {
     if (h && n_rays == 0) return DRT_OK;
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
     if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "null L_out");
     DeviceGuard g(h->device);
     drt::Params P;
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    rc = nerf_fill(h, P, cfg, emission, fused_half);
-    if (rc) return rc;
+    DRT_TRY(nerf_fill(h, P, cfg, emission, fused_half));
     P.L_out = L_out;
     if (!fused_half) h->pcache_sig.valid = false;
     return timed_nerf(h, 0, P, false, st);
@@ -1446,22 +1447,6 @@ int drt_nerf_render_primal(drt_handle h, const drt_nerf_config *cfg, const float
     return nerf_primal(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_out, false);
 }
 
-static int nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
-                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *dL_pix,
-                                const float *L_in, float *grad_sigma_t, float *grad_emission);
-
-int drt_nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                             const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                             const float *dL, const float *L_in, float *grad_sigma_t, float *grad_emission)
-{
-    if (h && n_rays == 0) return DRT_OK;
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false);
-    if (rc) return rc;
-    if (!dL || !L_in || !grad_sigma_t || !grad_emission)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward: null dL / L_in / gradient buffer");
-    return nerf_render_backward(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_emission);
-}
-
 // the nerf adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given
 static int nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *dL_pix,
@@ -1470,14 +1455,24 @@ static int nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const 
     DeviceGuard g(h->device);
     drt::Params P;
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    int rc = nerf_fill(h, P, cfg, emission);
-    if (rc) return rc;
+    DRT_TRY(nerf_fill(h, P, cfg, emission));
     P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_emission;
     // (sensor rays: sigma_t and the emission of a query from ONE 256-byte block of a four-channel copy made for this call)
-    const bool tile = drt::nerf_tile_supported(P) && !dbg(h->debug_flags, 512u);
+    const bool tile = drt::nerf_tile_supported(P) && !dbg(h->debug_flags, kHookNerfRecordPath);
     const bool g4 = tile && ensure_grid4(h, P, emission) == DRT_OK;   // (no memory / a grid beyond the copy's index range: the separate lookups)
     if (tile && !g4) (void) hipGetLastError();
     return nerf_backward(h, P, cfg, g4);
+}
+
+int drt_nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                             const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                             const float *dL, const float *L_in, float *grad_sigma_t, float *grad_emission)
+{
+    if (h && n_rays == 0) return DRT_OK;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
+    if (!dL || !L_in || !grad_sigma_t || !grad_emission)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward: null dL / L_in / gradient buffer");
+    return nerf_render_backward(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_emission);
 }
 
 // ---- forward mode: one launch over the job's rays, dL_out written once per ray.  No sub-batches (nothing is recorded), no path cache, no
@@ -1489,7 +1484,7 @@ static void forward_params(drt::Params &P, const float *t_sigma, const float *t_
     P.path_cache = nullptr; P.ray_hash = nullptr; P.path_cache_cap = 0; P.path_cache_mode = 0;
     P.block_cost = nullptr; P.block_order = nullptr; P.ray_perm = nullptr; P.ray_iters = nullptr;
     P.rec_buf[0] = P.rec_buf[1] = nullptr; P.rec_cursor = nullptr;
-    P.tail_pool = nullptr; P.tail_count = nullptr; P.tail_cap = 0; P.tail_mode = 0;
+    no_tail(P);
     P.dL = nullptr; P.dL_pix = nullptr; P.gt = nullptr;
 }
 
@@ -1516,8 +1511,7 @@ int drt_render_forward(drt_handle h, const float *rays_o, const float *rays_d, u
                        float *dL_out)
 {
     if (h && n_rays == 0) return DRT_OK;
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
     if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward: null L_in / dL_out");
     return render_forward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_in, t_sigma_t, t_albedo, dL_out, 0.0f);
 }
@@ -1526,11 +1520,9 @@ int drt_render_forward_phase(drt_handle h, const float *rays_o, const float *ray
                              uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
                              float *dL_out, float t_phase_g)
 {
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
     if (!std::isfinite(t_phase_g)) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase: t_phase_g must be finite");
-    rc = check_phase_grad(h, "drt_render_forward_phase", t_phase_g != 0.0f);
-    if (rc) return rc;
+    DRT_TRY(check_phase_grad(h, "drt_render_forward_phase", t_phase_g != 0.0f));
     if (n_rays == 0) return DRT_OK;
     if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase: null L_in / dL_out");
     return render_forward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_in, t_sigma_t, t_albedo, dL_out, t_phase_g);
@@ -1541,14 +1533,12 @@ int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const floa
                             const float *t_sigma_t, const float *t_emission, float *dL_out)
 {
     if (h && n_rays == 0) return DRT_OK;
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
     if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward: null dL_out");
     DeviceGuard g(h->device);
     drt::Params P;
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    rc = nerf_fill(h, P, cfg, emission);
-    if (rc) return rc;
+    DRT_TRY(nerf_fill(h, P, cfg, emission));
     forward_params(P, t_sigma_t, t_emission, dL_out);
     DRT_HIP_CHECK(h, P.colour_own ? drt::launch_nerf_own_fwd(P, h->stream) : drt::launch_nerf_fwd(P, h->stream));
     return DRT_OK;
@@ -1566,16 +1556,15 @@ static int ensure_grid4(drt_handle h, drt::Params &P, const float *rgb)
     if (B.colour_own) return fail(h, DRT_ERR_UNSUPPORTED, "the four-channel copy needs the colour grid on sigma_t's lattice");
     const size_t nbx = ((size_t) B.rx + 2) / 3, quads = nbx * (size_t) B.ry * (size_t) B.rz * 16;
     if (quads > 0x7fffffffull) return fail(h, DRT_ERR_UNSUPPORTED, "grid too large for the four-channel copy");
-    if (quads != h->grid4_quads) {
-        if (h->d_grid4) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(h->d_grid4); h->d_grid4 = nullptr; h->grid4_quads = 0; }
-        DRT_HIP_CHECK(h, hipMalloc(&h->d_grid4, quads * sizeof(float4)));
-        h->grid4_quads = quads; h->grid4_version = 0;
+    if (quads * sizeof(float4) != h->grid4.bytes) {
+        DRT_TRY(h->grid4.resize(h, quads * sizeof(float4), kMust));
+        h->grid4_version = 0;
     }
     if (!own || h->grid4_version != h->medium_version) {   // the parameter grids (may) have changed since the copy was made
-        DRT_HIP_CHECK(h, drt::launch_brick_grid4(B.sigma_t, rgb, h->d_grid4, B.rx, B.ry, B.rz, (int) nbx, h->stream));
+        DRT_HIP_CHECK(h, drt::launch_brick_grid4(B.sigma_t, rgb, h->grid4.as<float4>(), B.rx, B.ry, B.rz, (int) nbx, h->stream));
         h->grid4_version = own ? h->medium_version : 0;
     }
-    P.grid4 = h->d_grid4; P.g4_nbx = (int) nbx;
+    P.grid4 = h->grid4.as<float4>(); P.g4_nbx = (int) nbx;
     return DRT_OK;
 }
 
@@ -1591,11 +1580,8 @@ static int ensure_grid4(drt_handle h, drt::Params &P, const float *rgb)
 // with atomics only (the window flush of drt_nerf_tile.hip, tile_reduce's flush, direct splats): no order between them is needed.
 static int fused_fork(drt_handle h)
 {
-    if (!h->nerf_stream) {
-        DRT_HIP_CHECK(h, hipStreamCreateWithFlags(&h->nerf_stream, hipStreamNonBlocking));
-        DRT_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        DRT_HIP_CHECK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-    }
+    if (!h->nerf_stream) DRT_HIP_CHECK(h, hipStreamCreateWithFlags(&h->nerf_stream, hipStreamNonBlocking));
+    DRT_TRY(ensure_event_pair(h, h->ev_fork, h->ev_join));
     DRT_HIP_CHECK(h, hipEventRecord(h->ev_fork, h->stream));
     DRT_HIP_CHECK(h, hipStreamWaitEvent(h->nerf_stream, h->ev_fork, 0));
     return DRT_OK;
@@ -1612,16 +1598,14 @@ int drt_fused_render_primal(drt_handle h, const drt_nerf_config *cfg, const floa
                             uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_nerf_out, float *L_drt_out)
 {
     if (h && n_rays == 0) return DRT_OK;
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
     if (!L_nerf_out || !L_drt_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_fused_render_primal: null output buffer");
     if (!cfg) return fail(h, DRT_ERR_INVALID_ARGUMENT, "fused: null nerf config");
     {
         DeviceGuard g(h->device);
-        rc = fused_fork(h);
-        if (rc) return rc;
+        DRT_TRY(fused_fork(h));
     }
-    rc = nerf_primal(h, cfg, h->base.albedo, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_nerf_out, true, h->nerf_stream);
+    int rc = nerf_primal(h, cfg, h->base.albedo, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_nerf_out, true, h->nerf_stream);
     int rc2 = rc ? rc : drt_render_primal(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_drt_out);   // (its path cache serves the backward pass)
     {
         DeviceGuard g(h->device);
@@ -1636,28 +1620,23 @@ int drt_fused_render_backward(drt_handle h, const drt_nerf_config *cfg, const fl
                               const float *dL_drt, const float *L_drt_in, float *grad_sigma_t, float *grad_rgb)
 {
     if (h && n_rays == 0) return DRT_OK;
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
     if (!dL_nerf || !L_nerf_in || !dL_drt || !L_drt_in || !grad_sigma_t || !grad_rgb)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_fused_render_backward: null dL / L_in / gradient buffer");
-    hipEvent_t t0 = nullptr, t1 = nullptr;
+    TimedSpan whole;
     size_t n_pass = 0;
+    int rc = DRT_OK;
     {
         DeviceGuard g(h->device);
         drt::Params P;
         fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-        rc = nerf_fill(h, P, cfg, h->base.albedo, true);
-        if (rc) return rc;
+        DRT_TRY(nerf_fill(h, P, cfg, h->base.albedo, true));
         P.dL = dL_nerf; P.L_in = L_nerf_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_rgb;
-        const bool tile = drt::nerf_tile_supported(P) && !dbg(h->debug_flags, 512u);
+        const bool tile = drt::nerf_tile_supported(P) && !dbg(h->debug_flags, kHookNerfRecordPath);
         const bool g4 = tile && ensure_grid4(h, P, nullptr) == DRT_OK;   // (sigma_t and the colour of a query from ONE 256-byte block; else: separate lookups)
         if (tile && !g4) (void) hipGetLastError();
-        if (h->timing) {
-            DRT_HIP_CHECK(h, hipEventCreate(&t0));
-            DRT_HIP_CHECK(h, hipEventCreate(&t1));
-            DRT_HIP_CHECK(h, hipEventRecord(t0, h->stream));
-            n_pass = h->timed[3].size();
-        }
+        DRT_HIP_CHECK(h, whole.begin(h, h->stream));
+        n_pass = h->timed[3].size();
         // the tile kernel (one workgroup of 16 waves and 139 KiB of LDS per CU) leaves room for the wave-cooperative tracer's workgroups beside it;
         // the record path of explicit ray batches shares the handle's record streams with the volpathsimple half: one after the other
         bool forked = false;
@@ -1668,7 +1647,6 @@ int drt_fused_render_backward(drt_handle h, const drt_nerf_config *cfg, const fl
         } else rc = nerf_backward(h, P, cfg, false);
         if (rc) {                                                    // (nothing of the other stream may outlive the call)
             if (forked) (void) fused_join(h);
-            if (t0) { (void) hipEventDestroy(t0); (void) hipEventDestroy(t1); }
             return rc;
         }
         // (launched first: its workgroups need almost a whole CU's LDS, which the other half's many small workgroups would not leave free)
@@ -1677,10 +1655,11 @@ int drt_fused_render_backward(drt_handle h, const drt_nerf_config *cfg, const fl
     {
         DeviceGuard g(h->device);
         if (h->nerf_stream) { const int rj = fused_join(h); if (!rc) rc = rj; }
-        if (h->timing && t0) {                                   // the whole pass as ONE entry (the halves overlap)
-            DRT_HIP_CHECK(h, hipEventRecord(t1, h->stream));
-            while (h->timed[3].size() > n_pass) { (void) hipEventDestroy(h->timed[3].back().first); (void) hipEventDestroy(h->timed[3].back().second); h->timed[3].pop_back(); }
-            h->timed[3].emplace_back(t0, t1);
+        if (whole.a) {                                           // the whole pass as ONE entry (the halves overlap): theirs go
+            DRT_HIP_CHECK(h, whole.end(3));
+            auto &v = h->timed[3];
+            for (size_t i = n_pass; i + 1 < v.size(); ++i) destroy_pair(v[i]);
+            v.erase(v.begin() + n_pass, v.end() - 1);
         }
     }
     return rc;
@@ -1812,12 +1791,12 @@ int drt_nerf_tile_stats(drt_handle h, uint64_t *lds_lane_adds)
 {
     if (!h || !lds_lane_adds) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_tile_stats: null argument");
     *lds_lane_adds = 0;
-    if (!h->d_nerf_bounds) return DRT_OK;                          // (no tile launch yet)
+    if (!h->nerf_bounds.p) return DRT_OK;                          // (no tile launch yet)
     DeviceGuard g(h->device);
     DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     if (h->nerf_stream) DRT_HIP_CHECK(h, hipStreamSynchronize(h->nerf_stream));
     unsigned long long v = 0;
-    DRT_HIP_CHECK(h, hipMemcpy(&v, h->d_nerf_bounds + 6, sizeof v, hipMemcpyDeviceToHost));
+    DRT_HIP_CHECK(h, hipMemcpy(&v, h->nerf_bounds.as<uint32_t>() + 6, sizeof v, hipMemcpyDeviceToHost));
     *lds_lane_adds = (uint64_t) v;
     return DRT_OK;
 }
@@ -1879,16 +1858,6 @@ int drt_read_timings(drt_handle h, int backward, float *out_ms, int capacity)
 // ---- loss-fused film (drt_loss.hip) and the pixel-gradient backward calls ---------------------------------------------------------------------
 namespace {
 
-// a grow-only device buffer of the handle: (re)allocated behind the handle's stream when too small
-int grow_scratch(drt_handle h, void **buf, size_t *have, size_t need)
-{
-    if (need <= *have) return DRT_OK;
-    if (*buf) { DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream)); (void) hipFree(*buf); *buf = nullptr; *have = 0; }
-    DRT_HIP_CHECK(h, hipMalloc(buf, need));
-    *have = need;
-    return DRT_OK;
-}
-
 int loss_args(drt_handle h, const char *what, uint64_t n_pixels, const drt_loss_ref *ref, int32_t kind, float param, drt::LossRef &R)
 {
     if (n_pixels == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: n_pixels must be > 0", what);
@@ -1936,12 +1905,10 @@ int drt_film_loss_forward(drt_handle h, const float *L, uint64_t n_pixels, uint3
     if (spp == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_loss_forward: spp must be > 0");
     if (!L || !image_out || !loss_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_loss_forward: null L / image_out / loss_out");
     drt::LossRef R;
-    int rc = loss_args(h, "drt_film_loss_forward", n_pixels, ref, loss_kind, loss_param, R);
-    if (rc) return rc;
+    DRT_TRY(loss_args(h, "drt_film_loss_forward", n_pixels, ref, loss_kind, loss_param, R));
     DeviceGuard g(h->device);
-    rc = grow_scratch(h, (void **) &h->d_loss_partials, &h->loss_partials_bytes, drt::film_loss_partials(n_pixels, spp) * sizeof(double));
-    if (rc) return rc;
-    DRT_HIP_CHECK(h, drt::launch_film_loss_forward(L, n_pixels, spp, R, loss_kind, loss_param, image_out, loss_out, h->d_loss_partials,
+    DRT_TRY(h->loss_partials.grow(h, drt::film_loss_partials(n_pixels, spp) * sizeof(double), kMust));
+    DRT_HIP_CHECK(h, drt::launch_film_loss_forward(L, n_pixels, spp, R, loss_kind, loss_param, image_out, loss_out, h->loss_partials.as<double>(),
                                                    h->stream));
     return DRT_OK;
 }
@@ -1953,8 +1920,7 @@ int drt_film_loss_grad(drt_handle h, const float *image, uint64_t n_pixels, cons
     if (!image || !upstream || !grad_image_out)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_loss_grad: null image / upstream / grad_image_out");
     drt::LossRef R;
-    int rc = loss_args(h, "drt_film_loss_grad", n_pixels, ref, loss_kind, loss_param, R);
-    if (rc) return rc;
+    DRT_TRY(loss_args(h, "drt_film_loss_grad", n_pixels, ref, loss_kind, loss_param, R));
     DeviceGuard g(h->device);
     DRT_HIP_CHECK(h, drt::launch_film_loss_grad(image, n_pixels, R, loss_kind, loss_param, upstream, grad_image_out, h->stream));
     return DRT_OK;
@@ -1964,12 +1930,10 @@ int drt_render_backward_px(drt_handle h, const float *rays_o, const float *rays_
                            uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
                            const float *L_in, float *grad_sigma_t, float *grad_albedo)
 {
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
     if (!L_in || !grad_sigma_t || !grad_albedo)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_px: null L_in / gradient buffer");
-    rc = check_px(h, "drt_render_backward_px", n_rays, spp, grad_image, n_pixels);
-    if (rc) return rc;
+    DRT_TRY(check_px(h, "drt_render_backward_px", n_rays, spp, grad_image, n_pixels));
     return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo);
 }
 
@@ -1977,14 +1941,11 @@ int drt_render_backward_px_phase(drt_handle h, const float *rays_o, const float 
                                  uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
                                  const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g)
 {
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp);
-    if (rc) return rc;
-    rc = check_phase_grad(h, "drt_render_backward_px_phase", grad_phase_g != nullptr);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
+    DRT_TRY(check_phase_grad(h, "drt_render_backward_px_phase", grad_phase_g != nullptr));
     if (!L_in || !grad_sigma_t || !grad_albedo)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_px_phase: null L_in / gradient buffer");
-    rc = check_px(h, "drt_render_backward_px_phase", n_rays, spp, grad_image, n_pixels);
-    if (rc) return rc;
+    DRT_TRY(check_px(h, "drt_render_backward_px_phase", n_rays, spp, grad_image, n_pixels));
     return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo,
                            grad_phase_g);
 }
@@ -1994,14 +1955,12 @@ int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const 
                                 const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
                                 float *grad_emission)
 {
-    int rc = check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false);
-    if (rc) return rc;
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
     if (!cfg || !emission) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px: null config / emission grid");
     if (cfg->queries_per_ray < 2) return fail(h, DRT_ERR_INVALID_ARGUMENT, "queries_per_ray must be >= 2");
     if (!L_in || !grad_sigma_t || !grad_emission)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px: null L_in / gradient buffer");
-    rc = check_px(h, "drt_nerf_render_backward_px", n_rays, spp, grad_image, n_pixels);
-    if (rc) return rc;
+    DRT_TRY(check_px(h, "drt_nerf_render_backward_px", n_rays, spp, grad_image, n_pixels));
     return nerf_render_backward(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t,
                                 grad_emission);
 }

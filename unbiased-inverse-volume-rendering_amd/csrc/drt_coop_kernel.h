@@ -47,7 +47,7 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
         __shared__ uint32_t wgc_lds[kWgcWords];
         static_assert(DRT_COOP_WAVES >= 1, "");
         if (threadIdx.x < 4) wgc_lds[threadIdx.x] = 0xffffffffu; // nothing published yet (made visible by the barrier below)
-        if (!dbg(P.debug_flags, 33554432u) && !(!ADJ && dbg(P.debug_flags, 67108864u)) && P.max_depth < 32768) tr.wgc = wgc_lds;   // (the path-cache cursor travels in 16 bits)
+        if (!dbg(P.debug_flags, kHookNoHandOff) && !(!ADJ && dbg(P.debug_flags, kHookNoHandOffPrimal)) && P.max_depth < 32768) tr.wgc = wgc_lds;   // (the path-cache cursor travels in 16 bits)
     }
     __shared__ uint64_t jump_lds[2 * (kJumpMax + 1)];
     if (threadIdx.x <= kJumpMax) { jump_lds[2 * threadIdx.x] = kJump.A[threadIdx.x]; jump_lds[2 * threadIdx.x + 1] = kJump.G[threadIdx.x]; }
@@ -63,14 +63,14 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
         tr.rec = coop_rec + (threadIdx.x >> 6) * (64 * kCoopDwords);
     }
     __shared__ uint32_t occ_lds[kOccWords];
-    if (P.occ && !dbg(P.debug_flags, 16u)) {
+    if (P.occ && !dbg(P.debug_flags, kHookNoOccupancy)) {
         for (int w = threadIdx.x; w < P.occ_words; w += blockDim.x) occ_lds[w] = P.occ[w];
         __syncthreads();
         tr.occ = occ_lds;
     }
     if constexpr (SUPER) {                                      // non-empty supergrid cells -> LDS (dda_collision skips the others)
         __shared__ uint32_t mocc_lds[kOccWords];
-        if (P.mocc && P.mocc_words <= kOccWords && !dbg(P.debug_flags, 8388608u)) {
+        if (P.mocc && P.mocc_words <= kOccWords && !dbg(P.debug_flags, kHookNoSupergridMask)) {
             for (int w = threadIdx.x; w < P.mocc_words; w += blockDim.x) mocc_lds[w] = P.mocc[w];
             __syncthreads();
             tr.mocc = mocc_lds;
@@ -181,14 +181,14 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     tr.jump = jump_lds;
     __syncthreads();
     __shared__ uint32_t occ_lds[kOccWords];
-    if (P.occ && !dbg(P.debug_flags, 16u)) {
+    if (P.occ && !dbg(P.debug_flags, kHookNoOccupancy)) {
         for (int w = threadIdx.x; w < P.occ_words; w += blockDim.x) occ_lds[w] = P.occ[w];
         __syncthreads();
         tr.occ = occ_lds;
     }
     if constexpr (SUPER) {
         __shared__ uint32_t mocc_lds[kOccWords];
-        if (P.mocc && P.mocc_words <= kOccWords && !dbg(P.debug_flags, 8388608u)) {
+        if (P.mocc && P.mocc_words <= kOccWords && !dbg(P.debug_flags, kHookNoSupergridMask)) {
             for (int w = threadIdx.x; w < P.mocc_words; w += blockDim.x) mocc_lds[w] = P.mocc[w];
             __syncthreads();
             tr.mocc = mocc_lds;
@@ -226,7 +226,7 @@ hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
     if (P.n_rays <= P.ray_first) return hipSuccess;
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
     const bool env = P.env_pix != nullptr;
-    const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, 2097152u);
+    const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, kHookGenericKernels);
     if (spec) {
         if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, HG, GG>), grid, block, 0, stream, P);
         else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, HG, GG>), grid, block, 0, stream, P);
@@ -247,7 +247,7 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
     const bool env = P.env_pix != nullptr, defer = adjoint && P.rec_buf[0] != nullptr;
 #define DRT_COOP_LAUNCH(A, C, E, D) hipLaunchKernelGGL((trace_coop_kernel<A, C, E, D, false, SUPER, false, HG>), grid, block, 0, stream, P)
     // the registered `volpathsimple-drt` configuration (either emitter): specialised kernels
-    const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !count && !dbg(P.debug_flags, 2097152u);
+    const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !count && !dbg(P.debug_flags, kHookGenericKernels);
 #if DRT_PHASE_PROFILE
     // experiment build: the counting launches run the specialised kernels too (their counters then hold phase cycles)
     if (!HG && P.use_nee && P.use_drt && P.use_drt_subsampling && count && !env) {
@@ -259,7 +259,7 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
     // (adjoint only: a tail launch exposes the longest path of the job - ~0.5 ms - which the primal pass has nothing to
     // hide behind: primal 2.58 -> 2.85 ms with it, adjoint tracer 6.19 -> 5.99 ms)
     // (capacity invariant of the pool's reservation, CoopTracer::wg_handoff: one push of <= DRT_TAIL_PUSH entries per workgroup)
-    const bool tail = !SUPER && !HG && adjoint && P.tail_pool && P.tail_count && P.tail_cap >= 256u && !dbg(P.debug_flags, 33554432u) &&
+    const bool tail = !SUPER && !HG && adjoint && P.tail_pool && P.tail_count && P.tail_cap >= 256u && !dbg(P.debug_flags, kHookNoHandOff) &&
                       (uint64_t) P.tail_cap >= (uint64_t) DRT_TAIL_PUSH * grid.x;
     Params T = P;
     if (spec && (!adjoint || defer)) {
@@ -316,7 +316,7 @@ hipError_t launch_trace_coop_gg_t(const Params &P, hipStream_t stream)
     if (!P.L_out || P.tail_pool) return hipErrorInvalidValue;
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
     const bool env = P.env_pix != nullptr, defer = P.rec_buf[0] != nullptr;
-    const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, 2097152u);
+    const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, kHookGenericKernels);
 #define DRT_COOP_LAUNCH_GG(E, D, SP) hipLaunchKernelGGL((trace_coop_kernel<true, false, E, D, SP, SUPER, false, true, true>), grid, block, 0, stream, P)
     if (spec && defer) { if (env) DRT_COOP_LAUNCH_GG(true, true, true); else DRT_COOP_LAUNCH_GG(false, true, true); }
     else if (defer) { if (env) DRT_COOP_LAUNCH_GG(true, true, false); else DRT_COOP_LAUNCH_GG(false, true, false); }

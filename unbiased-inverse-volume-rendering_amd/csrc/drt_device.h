@@ -34,6 +34,43 @@ constexpr bool kTestHooks = false;
 #endif
 __host__ __device__ __forceinline__ constexpr bool dbg(uint32_t flags, uint32_t bits) { return kTestHooks && (flags & bits) != 0u; }
 
+// Every bit a dbg() call tests.  The values are ABI (tests, tools and `bench.py --debug-flags` pass them as integers): a hook may get a
+// better name, never another number.  include/drt_hip.h (drt_set_debug_flags) carries the same list for callers.
+enum Hook : uint32_t {
+    kHookNoGradAtomics      = 1u << 0,    // skip the gradient atomics (timing only)
+    kHookPerLaneAtomics     = 1u << 1,    // per-lane (uncoalesced) gradient atomics, as the first kernels made them
+    kHookPerLanePrimal      = 1u << 3,    // the plain one-ray-per-lane Tracer (drt_kernels.hip) for primal launches; never the state machine
+    kHookNoOccupancy        = 1u << 4,    // no empty-space bitmask
+    kHookWavefrontAdjoint   = 1u << 5,    // the state machine of whole flights (drt_wavefront.hip) for the adjoint too
+    kHookUntileKeepScratch  = 1u << 6,    // untile pass without re-zeroing the apron scratch it reads (timing only)
+    kHookAtomicGradients    = 1u << 7,    // gradient splats as atomics into the apron scratch + untile instead of deferred records
+    kHookTinyRecordStreams  = 1u << 8,    // two-chunk record streams: exercises the out-of-chunks fallback
+    kHookNerfRecordPath     = 1u << 9,    // the nerf adjoint of sensor rays through the record path instead of drt_nerf_tile.hip
+    kHookReduceNoFlush      = 1u << 10,   // gradient reduction without the flush (timing only)
+    kHookPipelineBatches    = 1u << 11,   // tracer of ray sub-batch b beside the reduction of sub-batch b - 1 on the side stream (measured slower)
+    kHookNoQueuedTracer     = 1u << 12,   // keep supergrid launches off the queued tracer: the round-3 kernel (drt_super.hip) or CoopTracer<SUPER>
+    kHookSmallRecordBudget  = 1u << 14,   // 8 MB record budget: many ray sub-batches
+    kHookPerLaneAdjoint     = 1u << 15,   // the plain one-ray-per-lane Tracer for adjoint launches
+    kHookWavefrontPrimal    = 1u << 16,   // the state machine of whole flights for primal launches
+    kHookNoRecordMemory     = 1u << 18,   // pretend that the record streams cannot be allocated: the job takes the atomic path
+    kHookNoRecordMemoryLater = 1u << 19,  // ... that they cannot be (re)allocated from the second ray sub-batch on
+    kHookNoPathCache        = 1u << 20,   // no path cache: the adjoint pass walks its primal paths again
+    kHookGenericKernels     = 1u << 21,   // generic tracing kernels instead of the ones specialised for `volpathsimple-drt`
+    kHookNoRaySchedule      = 1u << 22,   // no ray schedule from the primal pass's iteration counts (ray_perm, ray_iters)
+    kHookNoSupergridMask    = 1u << 23,   // no LDS copy of the supergrid's non-empty-cell bitmask
+    kHookPlainBlockMap      = 1u << 24,   // plain XCD block map: no heavy-blocks-first order
+    kHookNoHandOff          = 1u << 25,   // no workgroup hand-off of sparse waves' paths, no tail pool (every wave runs its own paths to the end)
+    kHookNoHandOffPrimal    = 1u << 26,   // ... in the primal pass only
+    kHookWavefrontSupergrid = 1u << 27,   // supergrid scenes in the older kernels: the state machine for the primal pass
+    kHookNoTailOverlap      = 1u << 28,   // no early histogram pass beside the adjoint's tail launch; queued tracer: no tail pool of either kind
+    kHookIndexOrder         = 1u << 29,   // the supergrid tracers take their rays in index order (production: thick pixels first)
+    kHookScheduleSmall      = 1u << 30,   // small launches are scheduled like large ones (ray order, tail launches): the tests' scenes cover them
+    kHookWalkEmptyPixels    = 1u << 31,   // the queued tracer walks every flight (production: pixels over empty supergrid cells end at set-up)
+    kHookPrimalNotCoop      = kHookPerLanePrimal | kHookWavefrontPrimal,   // primal launches the cooperative kernel does not serve: it alone fills block_cost
+    // any of the older tracer generations (per-lane Tracer, state machine): no supergrid kernels, no HG code
+    kHookOlderTracers       = kHookPerLanePrimal | kHookPerLaneAdjoint | kHookWavefrontPrimal | kHookWavefrontAdjoint | kHookWavefrontSupergrid,
+};
+
 // Experiment switches (timing / profiling builds made by tools/mk_variant.sh; several of them give WRONG results on purpose)
 // must never leak into a shipped library: they only compile with -DDRT_EXPERIMENT_BUILD.
 #if !defined(DRT_EXPERIMENT_BUILD) && (defined(DRT_FAST_MATH) || defined(DRT_ENV_EXP) || defined(DRT_EXP_ALB) || defined(DRT_EXP_DROP_TAIL) || defined(DRT_NT_STATS) || \
@@ -1113,15 +1150,15 @@ __device__ __forceinline__ void splat_sigma_t(const Params &P, V3 p, float g, ui
 {
     if (g == 0.0f) return;            // adding exact zeros changes nothing: skip the requests
     if constexpr (DEFER) {
-        if (dbg(P.debug_flags, 1u)) return;
+        if (dbg(P.debug_flags, kHookNoGradAtomics)) return;
         emit_record<0>(P, p, g * P.scale, nullptr, rec);
         return;
     }
     float w[8]; int idx[8];
     make_grad_indices(P, p, idx, w);
     float gs = g * P.scale;
-    if (dbg(P.debug_flags, 1u)) return;   // ablation: no gradient atomics
-    if (dbg(P.debug_flags, 2u)) {         // ablation: one lane, eight instructions (round-1 v1 behaviour)
+    if (dbg(P.debug_flags, kHookNoGradAtomics)) return;   // ablation: no gradient atomics
+    if (dbg(P.debug_flags, kHookPerLaneAtomics)) {         // ablation: one lane, eight instructions (round-1 v1 behaviour)
 #pragma unroll
         for (int k = 0; k < 8; ++k) atomicAdd(P.gt + idx[k], w[k] * gs);
         return;
@@ -1139,7 +1176,7 @@ __device__ __forceinline__ void splat_sigma_t(const Params &P, V3 p, float g, ui
 __device__ __forceinline__ void splat_colour_own(const Params &P, V3 p, const float g[3])
 {
     if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f) return;
-    if (dbg(P.debug_flags, 1u)) return;
+    if (dbg(P.debug_flags, kHookNoGradAtomics)) return;
     const Stencil st = make_stencil_colour(P, p);
     float w[8];
     stencil_weights(st, w);
@@ -1165,8 +1202,8 @@ __device__ __forceinline__ void splat_albedo(const Params &P, V3 p, const float 
     if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f) return;   // e.g. nerf queries in empty space (weight 0)
     float w[8]; int idx[8];
     make_grad_indices(P, p, idx, w);
-    if (dbg(P.debug_flags, 1u)) return;
-    if (dbg(P.debug_flags, 2u)) {
+    if (dbg(P.debug_flags, kHookNoGradAtomics)) return;
+    if (dbg(P.debug_flags, kHookPerLaneAtomics)) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             float *dst = P.gt + P.gt_plane + idx[k];
@@ -1194,7 +1231,7 @@ __device__ __forceinline__ void splat_scatter(const Params &P, V3 p, float gs, c
     return;
 #endif
     if constexpr (DEFER) {
-        if (dbg(P.debug_flags, 1u)) return;
+        if (dbg(P.debug_flags, kHookNoGradAtomics)) return;
         const bool colour = ga[0] != 0.0f || ga[1] != 0.0f || ga[2] != 0.0f;
         if (colour) emit_record<1>(P, p, gs * P.scale, ga, rec);
         else if (gs != 0.0f) emit_record<0>(P, p, gs * P.scale, nullptr, rec);

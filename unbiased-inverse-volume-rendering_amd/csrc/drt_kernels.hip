@@ -434,13 +434,13 @@ __global__ void __launch_bounds__(256, DRT_TRACE_WAVES) trace_kernel(const Param
     }
     // empty-space bitmask -> LDS (4 KiB): most lookups of a sparse volume never leave the CU
     __shared__ uint32_t occ_lds[kOccWords];
-    if (P.occ && !dbg(P.debug_flags, 16u)) {
+    if (P.occ && !dbg(P.debug_flags, kHookNoOccupancy)) {
         for (int w = threadIdx.x; w < P.occ_words; w += blockDim.x) occ_lds[w] = P.occ[w];
         __syncthreads();
         tr.occ = occ_lds;
     }
     __shared__ uint32_t mocc_lds[kOccWords];
-    if (P.mgrid && P.mocc && P.mocc_words <= kOccWords && !dbg(P.debug_flags, 8388608u)) {
+    if (P.mgrid && P.mocc && P.mocc_words <= kOccWords && !dbg(P.debug_flags, kHookNoSupergridMask)) {
         for (int w = threadIdx.x; w < P.mocc_words; w += blockDim.x) mocc_lds[w] = P.mocc[w];
         __syncthreads();
         tr.mocc = mocc_lds;
@@ -640,7 +640,7 @@ __device__ __forceinline__ void untile_march(const Params &P, int plane0, int bx
     const bool have_prev = bx > 0;
     const bool keep3 = last_lane && bx + 1 < P.gt_nbx;      // slot 3 is read by another wave's first lane
     const bool has_z = Z > 0;
-    const bool wr = !dbg(P.debug_flags, 64u);
+    const bool wr = !dbg(P.debug_flags, kHookUntileKeepScratch);
     const size_t row = (size_t) P.gt_nbx << 4;              // floats per line-row
     const int X = 3 * bx, nvx = min(3, P.rx - X);           // voxels of this line that exist
     Quad c1[NPL], c3[NPL];                                  // dy = 1 quads of the previous step

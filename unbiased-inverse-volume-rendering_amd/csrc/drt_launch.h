@@ -1,5 +1,5 @@
 // drt_launch.h -- host-side launch interface between the C ABI (drt_capi.cpp)
-// and the kernels (drt_kernels.hip).
+// and the kernels (the drt_*.hip units; each comment names the unit that defines what it describes).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,9 +29,6 @@ hipError_t launch_trace_wavefront(const Params &P, bool adjoint, bool count, int
 // majorant grid in LDS (drt_super.hip); the adjoint needs the record streams (deferred splatting)
 bool super_supported(const Params &P);
 hipError_t launch_trace_super(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
-// Ray order for launch_trace_super (Params::order): units of `unit` consecutive rays of [P.ray_first, P.n_rays) sorted by a
-// cost key - the majorant optical depth along the unit's first ray through the supergrid -, most expensive first.
-// work: super_order_bytes(units) bytes; the permutation is the first `units` words of it.
 // the same scenes as work queues inside a compute unit: rays live in LDS records and belong to no lane, waves take batches of
 // one kind of work (drt_sq.hip; round 4).  Uses the ray order and the XCD queues of launch_trace_super; the adjoint needs
 // Params::sq_cold (sq_cold_bytes(n_cus) bytes)
@@ -43,12 +40,16 @@ hipError_t launch_trace_sq(const Params &P, bool adjoint, bool count, int n_cus,
 uint32_t sq_tail_push();
 bool sq_tail_solo(const Params &P);       // the tail launch finishes its records in registers, no queue hops (supergrids whose majorants fit LDS)
 size_t sq_tail_entry_quads();
+// Ray order for launch_trace_super / launch_trace_sq (Params::order): units of `unit` consecutive rays of [P.ray_first, P.n_rays) sorted by a
+// cost key - the majorant optical depth along the unit's first ray through the supergrid -, most expensive first.
+// work: super_order_bytes(units) bytes; the permutation is the first `units` words of it.
 size_t super_order_bytes(uint32_t units);
+hipError_t build_super_order(const Params &P, uint32_t unit, uint32_t units, void *work, hipStream_t stream, const uint8_t *iters = nullptr);
 // flags[u] = 1: every ray of unit u (the `unit` = spp rays of one pixel, sensor rays only) crosses only empty supergrid cells (Params::unit_empty)
 hipError_t build_unit_empty(const Params &P, uint32_t unit, uint32_t units, uint8_t *flags, hipStream_t stream);
-hipError_t build_super_order(const Params &P, uint32_t unit, uint32_t units, void *work, hipStream_t stream, const uint8_t *iters = nullptr);
-// one ray per lane with wave-cooperative tracking loops (drt_coop.hip); global majorant only (P.mgrid == nullptr)
+// one ray per lane with own-lane tracking steps through the supergrid (drt_coop_super.hip)
 hipError_t launch_trace_coop_super(const Params &P, bool adjoint, bool count, hipStream_t stream);
+// one ray per lane with wave-cooperative tracking loops (drt_coop.hip); global majorant only (P.mgrid == nullptr)
 // `between` (optional): called on the host after the main launch has been enqueued and before the tail launch (adjoint of the
 // specialised kernels with a tail pool); returns whether it was called through *called
 typedef hipError_t (*coop_between_fn)(void *ctx);
