@@ -109,8 +109,20 @@ int drt_set_colour_resolution(drt_handle h, const int32_t res[3]);
  * is refused with DRT_ERR_UNSUPPORTED.  Setting another phase invalidates what the handle planned from earlier paths (path cache, ray
  * order); setting the same one again changes nothing.  The gradient with respect to g: drt_render_backward_phase,
  * drt_render_backward_px_phase and drt_render_forward_phase (an extension of the reference, whose volpathsimple has none). */
-enum { DRT_PHASE_ISOTROPIC = 0, DRT_PHASE_HG = 1 };
+enum { DRT_PHASE_ISOTROPIC = 0, DRT_PHASE_HG = 1, DRT_PHASE_HG2 = 2 };
 int drt_set_phase(drt_handle h, int32_t kind, float g);
+/* Two-lobe Henyey-Greenstein phase function (kind DRT_PHASE_HG2; Mitsuba: `blendphase` over two `hg` children):
+ *   p(mu) = (1 - weight) hg(g1, mu) + weight hg(g2, mu) - `weight` is the share of the SECOND lobe, as blendphase's.
+ * g1, g2 finite with |g| < 1, 0 <= weight <= 1 (anything else, NaN included: DRT_ERR_INVALID_ARGUMENT).  A scatter picks the second lobe
+ * iff the phase site's first draw (which the other phase functions drop) is below `weight`, samples that lobe, and carries the pdf of the
+ * mixture, so a path's sampler stream does not depend on the phase function.  weight 0 / 1 render bit for bit what DRT_PHASE_HG with g1 /
+ * g2 renders.  Kernels: the H2 instantiations of the HG ones (csrc/drt_sq_hg2.hip, drt_coop_hg2.hip, drt_coop_super_hg2.hip,
+ * drt_own_hg2.hip), with the HG routing and the HG invalidation rules: another triple drops path cache and ray orders, the same triple
+ * changes nothing, drt_set_medium leaves it alone, a test hook that routes to an older tracer generation is refused (DRT_ERR_UNSUPPORTED).
+ * drt_set_phase keeps its one-parameter meaning: called with kind 2 it returns DRT_ERR_INVALID_ARGUMENT.  No gradients with respect to
+ * g1, g2 or weight yet: a non-NULL grad_phase_g / non-zero t_phase_g of the *_phase entry points on such a handle returns
+ * DRT_ERR_UNSUPPORTED (NULL / 0 run as the plain calls do). */
+int drt_set_phase_hg2(drt_handle h, float g1, float g2, float weight);
 /* params.update(opt) after an optimizer step (python/optimize.py:354) and
  * medium.set_majorant_resolution_factor (:195-199): refresh the majorant from
  * the (same) parameter buffers.  No host synchronisation. */
@@ -368,7 +380,9 @@ int drt_read_timings(drt_handle h, int backward, float *out_ms, int capacity);
  * rgb + pdf_direction(d), 13 envmap sample_direction(u1, u2) -> d, pdf, 14 Medium::sample_interaction_drt
  * (E2) from o along d to the box exit with the stream PCG32(tea32(0x5eed, item)) -> valid, t', W, maxt,
  * 15 Henyey-Greenstein sample (u1, u2, wi.xyz, g) -> wo.xyz, pdf, 16 Henyey-Greenstein eval (wo.xyz, wi.xyz) with the
- * handle's g (drt_set_phase) -> pdf. */
+ * handle's g (drt_set_phase) -> pdf - on a two-lobe handle (drt_set_phase_hg2) the pdf of the mixture -, 17 Henyey-Greenstein score
+ * (g, mu) -> d/dg log p, p; on a two-lobe handle only: 18 two-lobe sample (u1, ux, uy, wi.xyz) with the handle's (g1, g2, weight)
+ * -> wo.xyz, mixture pdf (u1 < weight picks the second lobe), 19 two-lobe eval (wo.xyz, wi.xyz) -> pdf. */
 int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out);
 
 /* Test hooks: profiling ablations, kernel selection, simulated out-of-memory.  0 in production: only the library flavour built with

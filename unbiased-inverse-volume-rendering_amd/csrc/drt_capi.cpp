@@ -62,7 +62,8 @@ struct drt_handle_s {
     drt_config cfg{};
     drt::Params base{};            // scene part of the kernel parameter block
     bool have_medium = false, have_emitter = false, have_sensor = false;
-    int32_t phase_kind = DRT_PHASE_ISOTROPIC;   // drt_set_phase (the asymmetry g travels in base.phase_g)
+    int32_t phase_kind = DRT_PHASE_ISOTROPIC;   // drt_set_phase / drt_set_phase_hg2 (g travels in base.phase_g; HG2: g1 there, g2 in base.phase_tg,
+                                                // the second lobe's share in base.phase_w)
     float *d_majorant = nullptr;   // [2]
     // the global majorant as the HOST last saw it: drt_params_changed copies it to pinned memory behind the reduction and records an event; launches
     // look at it when the event has completed (never waiting) - a hint for kernel choice only (a thin medium: Params::sq_rounds), stale by design
@@ -400,17 +401,18 @@ hipError_t early_histogram_between(void *ctx)
 // ---- which call reaches which kernel --------------------------------------------------------------------------------------------------------
 enum class Route {
     kCoop,       // CoopTracer / CoopTracer<SUPER> (drt_coop.hip, drt_coop_super.hip)
-    kCoopHG,     // CoopTracer<HG> / <GG> (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip)
+    kCoopHG,     // CoopTracer<HG> / <GG> / <H2> (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip and their _hg2 units)
     kOwn,        // CoopTracer with the colour grids on their own lattice (drt_own.hip)
-    kQueued,     // the queued supergrid tracer (drt_sq.hip, drt_sq_hg.hip)
+    kQueued,     // the queued supergrid tracer (drt_sq.hip, drt_sq_hg.hip, drt_sq_hg2.hip)
 #ifdef DRT_TEST_HOOKS
     kSuper3,     // the round-3 supergrid kernel (drt_super.hip)
     kWavefront,  // the round-2 state machine of whole flights (drt_wavefront.hip)
     kPerLane,    // the plain per-lane Tracer (drt_kernels.hip)
 #endif
 };
-// hg: the HG instantiations (drt_set_phase); gg: ... with the g-gradient, an HG adjoint launch with a sink in Params::L_out
-struct Choice { Route route; bool hg, gg; };
+// hg: the HG instantiations (drt_set_phase, drt_set_phase_hg2); gg: ... with the g-gradient, an HG adjoint launch with a sink in Params::L_out;
+// hg2 (with hg, never with gg): their two-lobe instantiations
+struct Choice { Route route; bool hg, gg, hg2; };
 
 // Kernel choice - which call reaches which kernel (DESIGN.md section 1 has the table); launches nothing, allocates nothing:
 //   global majorant (majorant_resolution_factor 0): CoopTracer (drt_coop.hip: one ray per lane, wave-cooperative tracking rounds), both passes;
@@ -429,11 +431,13 @@ struct Choice { Route route; bool hg, gg; };
 //   hand-off, and no ROUNDS kernels; the older generations have no HG code.
 //   The g-gradient (drt_render_backward_phase: an HG adjoint launch with a sink in Params::L_out) runs the GG instantiations of the same
 //   kernels; the counting kernels have none (such a launch counts nothing).
+//   Two-lobe Henyey-Greenstein phase (drt_set_phase_hg2): the HG choice among the H2 instantiations (drt_sq_hg2.hip, drt_coop_hg2.hip,
+//   drt_coop_super_hg2.hip, drt_own_hg2.hip); no g-gradient kernels.
 Choice choose_tracer(drt_handle h, const drt::Params &P, bool adjoint)
 {
     const uint32_t f = h->debug_flags;
-    const bool hg = h->phase_kind == DRT_PHASE_HG, gg = hg && adjoint && P.L_out != nullptr;
-    auto to = [=](Route r) { return Choice{ r, hg, gg }; };
+    const bool hg2 = h->phase_kind == DRT_PHASE_HG2, hg = hg2 || h->phase_kind == DRT_PHASE_HG, gg = hg && !hg2 && adjoint && P.L_out != nullptr;
+    auto to = [=](Route r) { return Choice{ r, hg, gg, hg2 }; };
     // (kHookNoQueuedTracer: CoopTracer<SUPER, HG> here - the HG kernels' tracer-agreement tests)
     if (hg && (P.colour_own || !P.mgrid || dbg(f, kHookNoQueuedTracer))) return to(Route::kCoopHG);
     if (P.colour_own) return to(Route::kOwn);
@@ -464,6 +468,8 @@ int launch_coop_hg_or_own(drt_handle h, const drt::Params &P, bool adjoint, cons
     if (P.mgrid) Q.ray_perm = nullptr;
     if (c.gg) DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_gg(Q, h->stream) : drt::launch_trace_coop_gg(Q, h->stream));
     else if (!c.hg) DRT_HIP_CHECK(h, drt::launch_trace_own(Q, adjoint, h->counting, h->stream));
+    else if (c.hg2) DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_hg2(Q, adjoint, h->counting, h->stream)
+                                                  : drt::launch_trace_coop_hg2(Q, adjoint, h->counting, h->stream));
     else if (P.colour_own) DRT_HIP_CHECK(h, drt::launch_trace_own_hg(Q, adjoint, h->counting, h->stream));
     else DRT_HIP_CHECK(h, drt::launch_trace_coop_hg(Q, adjoint, h->counting, h->stream));
     return DRT_OK;
@@ -624,6 +630,7 @@ int launch_queued(drt_handle h, const drt::Params &P, bool adjoint, const Choice
     if (c.hg) {
         no_tail(Q);
         if (c.gg) DRT_HIP_CHECK(h, drt::launch_trace_sq_gg(Q, h->n_cus, h->stream));
+        else if (c.hg2) DRT_HIP_CHECK(h, drt::launch_trace_sq_hg2(Q, adjoint, h->counting, h->n_cus, h->stream));
         else DRT_HIP_CHECK(h, drt::launch_trace_sq_hg(Q, adjoint, h->counting, h->n_cus, h->stream));
     }
     else DRT_HIP_CHECK(h, drt::launch_trace_sq(Q, adjoint, h->counting, h->n_cus, h->stream));
@@ -682,7 +689,7 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
     DRT_HIP_CHECK(h, span.begin(h, h->stream));
     const Choice c = choose_tracer(h, P, adjoint);
     if (c.hg && dbg(h->debug_flags, kHookOlderTracers))
-        return fail(h, DRT_ERR_UNSUPPORTED, "the Henyey-Greenstein phase function has no code in the older tracer generations: the test hook "
+        return fail(h, DRT_ERR_UNSUPPORTED, "the Henyey-Greenstein phase functions have no code in the older tracer generations: the test hook "
                                             "routes this launch to one of them (debug flags 0x%x)", h->debug_flags);
     int rc = DRT_OK;
     switch (c.route) {
@@ -1142,6 +1149,9 @@ int drt_set_colour_resolution(drt_handle h, const int32_t res[3])
 int drt_set_phase(drt_handle h, int32_t kind, float g)
 {
     // (the arguments are checked before the handle: a wrong call is refused with its own message even without one)
+    if (kind == DRT_PHASE_HG2)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase: unknown phase kind 2 for this call (0 isotropic, 1 hg) - the two-lobe phase "
+                                                 "function takes three parameters: drt_set_phase_hg2(handle, g1, g2, weight)");
     if (kind != DRT_PHASE_ISOTROPIC && kind != DRT_PHASE_HG)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase: unknown phase kind %d (0 isotropic, 1 hg)", (int) kind);
     if (!std::isfinite(g) || !(std::fabs(g) < 1.0f))
@@ -1152,8 +1162,27 @@ int drt_set_phase(drt_handle h, int32_t kind, float g)
     const float gg = kind == DRT_PHASE_HG ? g : 0.0f;
     if (kind == h->phase_kind && std::memcmp(&gg, &h->base.phase_g, sizeof(float)) == 0) return DRT_OK;   // the same phase: every plan stays
     h->phase_kind = kind; h->base.phase_g = gg;
+    h->base.phase_tg = 0.0f; h->base.phase_w = 0.0f;            // (what a two-lobe phase left)
     // other paths: the path cache and the ray-order permutation of the last primal launch describe the old ones (scene_version is part of
     // the job signature they are tied to), and so does the supergrid ray order an adjoint launch would reuse
+    h->scene_version++;
+    h->pcache_sig.valid = false; h->perm_valid = false; h->order_valid = false; h->order_unit = 0;
+    return DRT_OK;
+}
+
+int drt_set_phase_hg2(drt_handle h, float g1, float g2, float weight)
+{
+    if (!std::isfinite(g1) || !(std::fabs(g1) < 1.0f) || !std::isfinite(g2) || !(std::fabs(g2) < 1.0f))
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase_hg2: g1 and g2 must be finite with |g| < 1 (got %g, %g)", (double) g1, (double) g2);
+    if (!(weight >= 0.0f && weight <= 1.0f))                    // (refuses NaN too)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase_hg2: weight, the share of the second lobe, must lie in [0, 1] (got %g)", (double) weight);
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    drt::Params &B = h->base;
+    if (h->phase_kind == DRT_PHASE_HG2 && std::memcmp(&g1, &B.phase_g, sizeof(float)) == 0 && std::memcmp(&g2, &B.phase_tg, sizeof(float)) == 0 &&
+        std::memcmp(&weight, &B.phase_w, sizeof(float)) == 0)
+        return DRT_OK;                                           // the same phase: every plan stays
+    h->phase_kind = DRT_PHASE_HG2; B.phase_g = g1; B.phase_tg = g2; B.phase_w = weight;
+    // other paths: as drt_set_phase
     h->scene_version++;
     h->pcache_sig.valid = false; h->perm_valid = false; h->order_valid = false; h->order_unit = 0;
     return DRT_OK;
@@ -1375,6 +1404,9 @@ int drt_render_backward(drt_handle h, const float *rays_o, const float *rays_d, 
 // the g-gradient arguments of the *_phase entry points: only an HG handle has a g to differentiate
 static int check_phase_grad(drt_handle h, const char *what, bool wanted)
 {
+    if (wanted && h->phase_kind == DRT_PHASE_HG2)
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the two-lobe Henyey-Greenstein phase function (drt_set_phase_hg2) has no phase-parameter "
+                                            "gradients yet (g1, g2 and weight)", what);
     if (wanted && h->phase_kind != DRT_PHASE_HG)
         return fail(h, DRT_ERR_UNSUPPORTED, "%s: the handle's phase function is isotropic - a gradient with respect to g needs the "
                                             "Henyey-Greenstein phase function (drt_set_phase(DRT_PHASE_HG, 0.0) for an isotropic medium)", what);
@@ -1497,8 +1529,11 @@ static int render_forward(drt_handle h, const float *rays_o, const float *rays_d
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
     forward_params(P, t_sigma_t, t_albedo, dL_out);
     P.L_in = L_in;
-    P.phase_tg = t_phase_g;
-    if (t_phase_g != 0.0f)                                      // (drt_render_forward_phase with a g tangent: an HG handle)
+    const bool hg2 = h->phase_kind == DRT_PHASE_HG2;            // (its g2 travels in phase_tg: t_phase_g is 0, check_phase_grad)
+    if (!hg2) P.phase_tg = t_phase_g;
+    if (hg2)
+        DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_hg2(P, h->stream) : drt::launch_trace_coop_fwd_hg2(P, h->stream));
+    else if (t_phase_g != 0.0f)                                      // (drt_render_forward_phase with a g tangent: an HG handle)
         DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_gg(P, h->stream) : drt::launch_trace_coop_fwd_gg(P, h->stream));
     else if (h->phase_kind == DRT_PHASE_HG)
         DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_hg(P, h->stream) : drt::launch_trace_coop_fwd_hg(P, h->stream));
@@ -1774,6 +1809,9 @@ int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out
     DeviceGuard g(h->device);
     drt::Params P = h->base;
     P.majorant = h->d_majorant;
+    if (h->phase_kind != DRT_PHASE_HG2 && (op == 18 || op == 19))
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_debug_eval: op %d evaluates the handle's two-lobe phase function (drt_set_phase_hg2)", op);
+    if (h->phase_kind == DRT_PHASE_HG2 && op == 16) op = 19;   // "the handle's phase function -> pdf": the mixture
     DRT_HIP_CHECK(h, drt::launch_debug_eval(P, op, in, n, out, h->stream));
     return DRT_OK;
 }

@@ -15,7 +15,9 @@ using namespace coop;
 // (CoopTracer::wg_handoff) instead of from rays, and finish them
 // HG: Henyey-Greenstein phase function (CoopTracer); those kernels run without hand-off and tail pool
 // GG (adjoint, with HG): the g-gradient too - each wave adds the sum of its lanes' terms to *Params::L_out with one atomic at its end
-template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, bool HG = false, bool GG = false>
+// H2 (with HG, never with GG): the two-lobe Henyey-Greenstein mixture (CoopTracer<H2>; drt_set_phase_hg2)
+template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, bool HG = false, bool GG = false,
+          bool H2 = false>
 __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRIMAL) trace_coop_kernel(const Params P)
 {
     if constexpr (TAIL) { if (blockIdx.x * 256u >= *P.tail_count) return; }   // (workgroup-uniform) nothing for this workgroup
@@ -38,7 +40,7 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
         if (P.ray_perm) i = (i_block & ~(uint64_t) (kPermGroup - 1)) + P.ray_perm[i_block + threadIdx.x];
     }
     static_assert(!GG || (ADJ && HG && !TAIL), "the g-gradient kernels are HG adjoint kernels");
-    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, HG, GG> tr(P);
+    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, HG, GG, H2> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     tr.i_block = TAIL ? 0 : i_block;
@@ -158,7 +160,7 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
 // adjoint splats (the tangent grids are Params::g_sigma / g_albedo), and writes J t of its ray to L_out - once, from the ray's own lane (no hand-off, no tail pool, no atomics: the result is
 // bit-reproducible).  The global majorant's NEE walks take every step on the walk's own lane (CoopTracer::coop_rt).
 // GG (with HG): J t includes t_g (Params::phase_tg) times the derivative with respect to g
-template <bool ENV, bool SPEC, bool SUPER, bool HG = false, bool GG = false>
+template <bool ENV, bool SPEC, bool SUPER, bool HG = false, bool GG = false, bool H2 = false>
 __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(const Params P)
 {
     uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map (see trace_coop_kernel)
@@ -173,7 +175,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     }
 #endif
     const uint64_t i = P.ray_first + (uint64_t) b * blockDim.x + threadIdx.x;
-    CoopTracer<false, ENV, false, SPEC, false, SUPER, true, HG, GG> tr(P);
+    CoopTracer<false, ENV, false, SPEC, false, SUPER, true, HG, GG, H2> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     __shared__ uint64_t jump_lds[2 * (kJumpMax + 1)];
@@ -220,7 +222,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     if (job) { P.L_out[3 * i] = tr.tg[0]; P.L_out[3 * i + 1] = tr.tg[1]; P.L_out[3 * i + 2] = tr.tg[2]; }
 }
 
-template <bool SUPER, bool HG = false, bool GG = false>
+template <bool SUPER, bool HG = false, bool GG = false, bool H2 = false>
 hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
@@ -228,24 +230,24 @@ hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
     const bool env = P.env_pix != nullptr;
     const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, kHookGenericKernels);
     if (spec) {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, HG, GG>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, HG, GG>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, HG, GG, H2>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, HG, GG, H2>), grid, block, 0, stream, P);
     } else {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER, HG, GG>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER, HG, GG>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER, HG, GG, H2>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER, HG, GG, H2>), grid, block, 0, stream, P);
     }
     return hipGetLastError();
 }
 
-// launch of the instantiation that fits the job (HG: the Henyey-Greenstein instantiations - no tail pool, no hand-off)
-template <bool SUPER, bool HG = false>
+// launch of the instantiation that fits the job (HG: the Henyey-Greenstein instantiations - no tail pool, no hand-off; H2: their two-lobe ones)
+template <bool SUPER, bool HG = false, bool H2 = false>
 hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between = nullptr,
                                void *between_ctx = nullptr, bool *called = nullptr)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
     const bool env = P.env_pix != nullptr, defer = adjoint && P.rec_buf[0] != nullptr;
-#define DRT_COOP_LAUNCH(A, C, E, D) hipLaunchKernelGGL((trace_coop_kernel<A, C, E, D, false, SUPER, false, HG>), grid, block, 0, stream, P)
+#define DRT_COOP_LAUNCH(A, C, E, D) hipLaunchKernelGGL((trace_coop_kernel<A, C, E, D, false, SUPER, false, HG, false, H2>), grid, block, 0, stream, P)
     // the registered `volpathsimple-drt` configuration (either emitter): specialised kernels
     const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !count && !dbg(P.debug_flags, kHookGenericKernels);
 #if DRT_PHASE_PROFILE
@@ -275,13 +277,13 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
     const dim3 tgrid(tail ? P.tail_cap / 256u : 1u);
     // (pool capacity = 1/8 of the launch's rays; the tail kernel's surplus workgroups return at once)
     if (spec && !adjoint) {
-        if (env) hipLaunchKernelGGL((trace_coop_kernel<false, false, true, false, true, SUPER, false, HG>), grid, block, 0, stream, M);
-        else hipLaunchKernelGGL((trace_coop_kernel<false, false, false, false, true, SUPER, false, HG>), grid, block, 0, stream, M);
+        if (env) hipLaunchKernelGGL((trace_coop_kernel<false, false, true, false, true, SUPER, false, HG, false, H2>), grid, block, 0, stream, M);
+        else hipLaunchKernelGGL((trace_coop_kernel<false, false, false, false, true, SUPER, false, HG, false, H2>), grid, block, 0, stream, M);
         return hipGetLastError();
     }
     if (spec && defer) {
-        if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, SUPER, false, HG>), grid, block, 0, stream, M);
-        else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, SUPER, false, HG>), grid, block, 0, stream, M);
+        if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, SUPER, false, HG, false, H2>), grid, block, 0, stream, M);
+        else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, SUPER, false, HG, false, H2>), grid, block, 0, stream, M);
         if constexpr (!SUPER && !HG) if (tail) {
             if (between) {                                     // (e.g. the early histogram pass of the record streams)
                 hipError_t e = between(between_ctx);

@@ -124,10 +124,14 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 // hg_score of every sampled direction and the explicit terms of the two MIS weights.  Adjoint: g_acc sums <dL, .> of the terms on each lane
 // (the kernel adds a wave's sum to Params::L_out once); forward mode: g_S carries the scores sampled so far and every contribution adds
 // c (g_S + explicit term) t_g (Params::phase_tg) to tg.
+// H2 (with HG, never with GG): the two-lobe mixture (drt_set_phase_hg2; drt_device.h: hg2_eval, hg2_sample) at the same sites - g1 in
+// Params::phase_g, g2 in Params::phase_tg, the second lobe's share in Params::phase_w.  The scatter sites keep the next_1d draw the other
+// instantiations drop: it chooses the lobe.
 template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, bool HG = false,
-          bool GG = false>
+          bool GG = false, bool H2 = false>
 struct CoopTracer {
     static_assert(!GG || HG, "the g-gradient exists for the Henyey-Greenstein phase function only");
+    static_assert(!H2 || (HG && !GG), "the two-lobe kernels are HG kernels without a g-gradient");
     const Params &P;
     float maj, inv_maj;
     const uint32_t *mocc;   // SUPER: non-empty supergrid cells (LDS copy) or nullptr
@@ -492,6 +496,11 @@ struct CoopTracer {
 #pragma unroll
             for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * pv) * w) * emitted[k] : 0.0f;
             gx = (2.0f * w - 1.0f) * hg_score(P.phase_g, mu);
+        } else if constexpr (H2) {                                              // ... of the mixture
+            const float pv = hg2_eval(P.phase_g, P.phase_tg, P.phase_w, hg_wd, hg_wi);
+            float w = mis_weight(ds_pdf, pv);                                   // :391
+#pragma unroll
+            for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * pv) * w) * emitted[k] : 0.0f;
         } else if constexpr (HG) {                                              // phase_val = phase_pdf = eval(wd, wi) (:386-388)
             const float pv = hg_eval(P.phase_g, hg_wd, hg_wi);
             float w = mis_weight(ds_pdf, pv);                                   // :391
@@ -567,9 +576,11 @@ struct CoopTracer {
         ps.depth = depth + 1; ps.last_pdf = kInvFourPi; ps.escaped = false; ps.active = false;
         ps.si.valid = false; ps.si.t = kInf; ps.si.p = v3(0, 0, 0); ps.si.n = v3(0, 0, 0);
         if (job) {
-            (void) A.next_1d();                                                 // :632
+            float u1 = 0.0f;                                                    // :632 (H2: chooses the lobe)
+            if constexpr (H2) u1 = A.next_1d(); else { (void) A.next_1d(); (void) u1; }
             float ux = A.next_1d(), uy = A.next_1d();
-            if constexpr (HG) rr.d = hg_sample(P.phase_g, ux, uy, hg_wi, ps.last_pdf);
+            if constexpr (H2) rr.d = hg2_sample(P.phase_g, P.phase_tg, P.phase_w, u1, ux, uy, hg_wi, ps.last_pdf);
+            else if constexpr (HG) rr.d = hg_sample(P.phase_g, ux, uy, hg_wi, ps.last_pdf);
             else rr.d = square_to_uniform_sphere(ux, uy);
             Hit sn = box_hit(P, p, rr.d);                                       // :637
             rr.maxt = sn.valid ? sn.t : kLargest;                               // :639-640
@@ -1002,9 +1013,14 @@ struct CoopTracer {
 
             if (run) {
                 if (did_scatter) {                                              // :221-230
-                    (void) S.next_1d();
+                    float u1 = 0.0f;                                            // (H2: chooses the lobe)
+                    if constexpr (H2) u1 = S.next_1d(); else { (void) S.next_1d(); (void) u1; }
                     float ux = S.next_1d(), uy = S.next_1d();
-                    if constexpr (kGG) {                                        // the score term: s(mu) times what the path collects after it
+                    if constexpr (H2) {
+                        ray.o = mei.p; ray.d = hg2_sample(P.phase_g, P.phase_tg, P.phase_w, u1, ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf);
+                        ray.maxt = kLargest;
+                    }
+                    else if constexpr (kGG) {                                        // the score term: s(mu) times what the path collects after it
                         float mu;
                         ray.o = mei.p; ray.d = hg_sample(P.phase_g, ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf, mu); ray.maxt = kLargest;
                         s_last = hg_score(P.phase_g, mu);

@@ -285,6 +285,36 @@ __device__ __forceinline__ float hg_score(float g, float mu)
     return (-2.0f * g) / (1.0f - g * g) - (3.0f * (g + mu)) / temp;
 }
 
+// ---------------------------------------------------------------------------
+// Two-lobe Henyey-Greenstein phase function (Mitsuba 3: `blendphase` over two `hg` children; drt_set_phase_hg2):
+//   p(mu) = (1 - w) hg(g1, mu) + w hg(g2, mu),  w = the share of the SECOND lobe (blendphase's `weight`), 0 <= w <= 1
+// float32 operation order (no contraction): a = 1 - w; p1 = hg_eval_cos(g1, mu); p2 = hg_eval_cos(g2, mu); p = (a * p1) + (w * p2).
+// w = 0 gives p1 and w = 1 gives p2 bit for bit (1 * p + 0 * q == p for finite q).
+//   sample(u1, u):  the lobe is the second one iff u1 < w - u1 is the next_1d draw of the phase site, which the single-lobe and isotropic
+//                   sites draw and drop, so the sampler stream of a path does not depend on the phase function; the direction is
+//                   hg_sample(g of that lobe, u); the pdf returned is the MIXTURE at the sampled mu (the sampled weight stays 1).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float hg2_eval_cos(float g1, float g2, float w, float mu)
+{
+    const float a = 1.0f - w;
+    const float p1 = hg_eval_cos(g1, mu), p2 = hg_eval_cos(g2, mu);
+    return a * p1 + w * p2;
+}
+
+__device__ __forceinline__ float hg2_eval(float g1, float g2, float w, V3 wo, V3 wi)
+{
+    return hg2_eval_cos(g1, g2, w, (wo.x * wi.x + wo.y * wi.y) + wo.z * wi.z);
+}
+
+__device__ __forceinline__ V3 hg2_sample(float g1, float g2, float w, float u1, float ux, float uy, V3 wi, float &pdf)
+{
+    const float g = u1 < w ? g2 : g1;
+    float lobe_pdf, mu;
+    const V3 d = hg_sample(g, ux, uy, wi, lobe_pdf, mu);
+    pdf = hg2_eval_cos(g1, g2, w, mu);
+    return d;
+}
+
 // atan2 with a specified instruction sequence (Cephes atanf polynomial on min/max in [0,1]);
 // atan2(0,0) = 0.  Same sequence as the oracle's, so envmap lookups are bit-identical.
 __device__ __forceinline__ float drt_atan2f(float y, float x)
@@ -430,6 +460,9 @@ struct Params {
     // supergrid cells whose majorant is 0 (build_unit_empty): the flights along its primary segment are not walked.  nullptr: no flags
     const uint8_t *unit_empty;
     uint32_t empty_unit;
+    // two-lobe Henyey-Greenstein phase (drt_set_phase_hg2): the share of the second lobe, read only by the HG2 instantiations, which take
+    // g1 from phase_g and g2 from phase_tg (they have no g tangent).  It fills the four bytes of padding in front of sq_cold (no field moves).
+    float phase_w;
     // queued supergrid tracer (drt_sq.hip): per workgroup [3 | 9][sq_rays] uint4 of path state that only the path
     // transitions use (throughput, radiance; adjoint: dL, the sampler clone, the DRT reservoir); library-owned, L2-resident.
     // sq_rays: ray records per workgroup (set by launch_trace_sq: what fits LDS next to the majorants)
@@ -451,6 +484,7 @@ struct Params {
 };
 static_assert(offsetof(Params, majorant) == offsetof(Params, g4_nbx) + 8, "Params::phase_g must stay in the padding in front of majorant");
 static_assert(offsetof(Params, L_out) == offsetof(Params, alt_seed) + 8, "Params::phase_tg must stay in the padding in front of L_out");
+static_assert(offsetof(Params, sq_cold) == offsetof(Params, empty_unit) + 8, "Params::phase_w must stay in the padding in front of sq_cold");
 static_assert(sizeof(Params) == 752, "the kernel parameter block keeps its size");
 
 // ---------------------------------------------------------------------------

@@ -837,6 +837,12 @@ __global__ void __launch_bounds__(256) debug_eval_kernel(const Params P, int op,
         } break;
         case 16: o[0] = hg_eval(P.phase_g, v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5])); break;   // ... eval (wo, wi), the handle's g
         case 17: o[0] = hg_score(a[0], a[1]); o[1] = hg_eval_cos(a[0], a[1]); break;   // ... score d/dg log p and p at (g, mu)
+        case 18: {                                      // two-lobe HG sample (u1, ux, uy, wi) with the handle's (g1, g2, weight) -> wo, mixture pdf
+            float pdf;
+            V3 d = hg2_sample(P.phase_g, P.phase_tg, P.phase_w, a[0], a[1], a[2], v3(a[3], a[4], a[5]), pdf);
+            o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = pdf;
+        } break;
+        case 19: o[0] = hg2_eval(P.phase_g, P.phase_tg, P.phase_w, v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5])); break;   // ... eval (wo, wi)
         case 9: if (P.mgrid) { o[0] = P.mgrid[__float_as_uint(a[0])]; } break;
         case 8: o[0] = mis_weight(a[0], a[1]); o[1] = a[0] / a[1]; o[2] = sqrtf(a[0]); o[3] = fmaf(a[0], a[1], a[2]); break;
         default: break;

@@ -82,6 +82,16 @@ hipError_t launch_trace_coop_fwd_gg(const Params &P, hipStream_t stream);
 hipError_t launch_trace_coop_super_fwd_gg(const Params &P, hipStream_t stream);
 hipError_t launch_trace_own_fwd_gg(const Params &P, hipStream_t stream);
 hipError_t launch_trace_sq_gg(const Params &P, int n_cus, hipStream_t stream);
+// Two-lobe Henyey-Greenstein phase function (drt_set_phase_hg2; Params::phase_g = g1, phase_tg = g2, phase_w = the second lobe's share): the
+// H2 instantiations of the HG kernels, one launcher for each of theirs (drt_coop_hg2.hip, drt_coop_super_hg2.hip, drt_own_hg2.hip,
+// drt_sq_hg2.hip).  No g-gradient kernels.
+hipError_t launch_trace_coop_hg2(const Params &P, bool adjoint, bool count, hipStream_t stream);
+hipError_t launch_trace_coop_super_hg2(const Params &P, bool adjoint, bool count, hipStream_t stream);
+hipError_t launch_trace_own_hg2(const Params &P, bool adjoint, bool count, hipStream_t stream);
+hipError_t launch_trace_coop_fwd_hg2(const Params &P, hipStream_t stream);
+hipError_t launch_trace_coop_super_fwd_hg2(const Params &P, hipStream_t stream);
+hipError_t launch_trace_own_fwd_hg2(const Params &P, hipStream_t stream);
+hipError_t launch_trace_sq_hg2(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
 hipError_t launch_ray_perm(const uint8_t *iters, uint64_t n_rays, uint16_t *perm, uint32_t *block_cost, hipStream_t stream);
 hipError_t launch_block_order(const uint32_t *cost, uint32_t n_blocks, uint32_t *order, bool heavy_first, hipStream_t stream);
 hipError_t launch_untile(const Params &P, hipStream_t stream);

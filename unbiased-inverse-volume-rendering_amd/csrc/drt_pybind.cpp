@@ -84,6 +84,7 @@ public:
     uint64_t nerf_tile_lds_adds() { uint64_t v = 0; check(drt_nerf_tile_stats(h_, &v), "drt_nerf_tile_stats"); return v; }
     void set_colour_resolution(std::array<int32_t, 3> res) { check(drt_set_colour_resolution(h_, res.data()), "drt_set_colour_resolution"); }
     void set_phase(int32_t kind, float g) { check(drt_set_phase(h_, kind, g), "drt_set_phase"); }
+    void set_phase_hg2(float g1, float g2, float weight) { check(drt_set_phase_hg2(h_, g1, g2, weight), "drt_set_phase_hg2"); }
     void params_changed()
     {
         int rc;
@@ -418,6 +419,7 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("set_medium", &Integrator::set_medium)
         .def("set_colour_resolution", &Integrator::set_colour_resolution)
         .def("set_phase", &Integrator::set_phase, py::arg("kind"), py::arg("g") = 0.0f)
+        .def("set_phase_hg2", &Integrator::set_phase_hg2, py::arg("g1"), py::arg("g2"), py::arg("weight"))
         .def("nerf_tile_lds_adds", &Integrator::nerf_tile_lds_adds)
         .def("params_changed", &Integrator::params_changed)
         .def("set_emitter_constant", &Integrator::set_emitter_constant)

@@ -280,9 +280,14 @@ __device__ __forceinline__ void sq_push_all(unsigned long long *ctl, uint16_t *q
 // with respect to g"): the score of each phase sampling times <dL, result> (result: the radiance below the vertex), the NEE term and the escape
 // term.  Each lane sums them over the records it serves; a wave adds its sum to *Params::L_out once, at its end.  A record owns one more uint4 of
 // global memory: {score, pdf} of the main path's last phase sampling (the quadratic detour's recursive paths overwrite the last pdf in {wi, last pdf}).
-template <bool ADJ, bool COUNT, bool ENV, bool MG, bool QUAD = false, bool TAILM = false, bool ROUNDS = false, bool HG = false, bool GG = false>
+// H2 (HG kernels of drt_sq_hg2.hip, never with GG): the mixture of two Henyey-Greenstein lobes (drt_set_phase_hg2; g1 in Params::phase_g, g2 in
+// Params::phase_tg, the second lobe's share in Params::phase_w) at the same three sites.  The record is the HG one: {wi, last pdf} holds the MIXTURE's
+// pdf at the sampled direction, and the lobe is chosen by the next_1d draw the other instantiations drop - nothing else has to travel.
+template <bool ADJ, bool COUNT, bool ENV, bool MG, bool QUAD = false, bool TAILM = false, bool ROUNDS = false, bool HG = false, bool GG = false,
+          bool H2 = false>
 __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P)
 {
+    static_assert(!H2 || (HG && !GG), "the two-lobe kernels are HG kernels without a g-gradient");
     static_assert(!HG || (!TAILM && !ROUNDS), "the HG kernels have no tail launch and no ROUNDS variant");
     static_assert(!GG || (HG && ADJ), "the g-gradient kernels are HG adjoint kernels");
     constexpr int NWV = DRT_SQ_THREADS / 64;
@@ -1023,6 +1028,15 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                         result[k] = (ADJ && !rec_mode) ? result[k] - contrib[k] : result[k] + contrib[k];   // :211-214
                     }
                     if (!rec_mode) g_acc += ((2.0f * w - 1.0f) * hg_score(P.phase_g, mu)) * ((dL[0] * contrib[0] + dL[1] * contrib[1]) + dL[2] * contrib[2]);
+                } else if constexpr (H2) {                                  // ... of the mixture
+                    const float4 hw = cold_h[id];
+                    const float pv = hg2_eval(P.phase_g, P.phase_tg, P.phase_w, rd, v3(hw.x, hw.y, hw.z));
+                    const float w = mis_weight(ds_pdf, pv);                 // :391
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        contrib[k] = ((beta[k] * pv) * w) * (val[k] * wt);
+                        result[k] = (ADJ && !rec_mode) ? result[k] - contrib[k] : result[k] + contrib[k];   // :211-214
+                    }
                 } else if constexpr (HG) {                                  // phase_val = phase_pdf = eval(rd, wi) (:386-388)
                     const float4 hw = cold_h[id];
                     const float pv = hg_eval(P.phase_g, rd, v3(hw.x, hw.y, hw.z));
@@ -1106,12 +1120,14 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                 SQ_BLK(2, ph == SP_PHASE);
                 if (ph == SP_PHASE) {
                     ++pc_it;                                                    // next bounce-loop iteration (path cache index)
-                    (void) S.next_1d();
+                    float u1 = 0.0f;                                            // (H2: chooses the lobe)
+                    if constexpr (H2) u1 = S.next_1d(); else { (void) S.next_1d(); (void) u1; }
                     float ux = S.next_1d(), uy = S.next_1d();
                     if constexpr (HG) {                                         // wi: stored by the emitter-direction block, or -rd without NEE
                         float4 hw = cold_h[id];
                         const V3 wi = P.use_nee ? v3(hw.x, hw.y, hw.z) : v3(-rd.x, -rd.y, -rd.z);
-                        if constexpr (GG) {                                     // the score term: s(mu) <dL, result> (result: L below this vertex)
+                        if constexpr (H2) rd = hg2_sample(P.phase_g, P.phase_tg, P.phase_w, u1, ux, uy, wi, hw.w);
+                        else if constexpr (GG) {                                     // the score term: s(mu) <dL, result> (result: L below this vertex)
                             float mu;
                             rd = hg_sample(P.phase_g, ux, uy, wi, hw.w, mu);
                             if (!rec_mode) {
@@ -1677,7 +1693,8 @@ bool sq_supported(const Params &P)
 
 // HG: the Henyey-Greenstein instantiations (drt_sq_hg.hip): no tail launch, no ROUNDS kernels.  GG: their adjoint launches with the g-gradient
 // (into *Params::L_out), without counting kernels
-template <bool HG, bool GG = false>
+// H2: the two-lobe instantiations of the HG kernels (drt_sq_hg2.hip)
+template <bool HG, bool GG = false, bool H2 = false>
 static hipError_t launch_trace_sq_t(const Params &Pin, bool adjoint, bool count, int n_cus, hipStream_t stream)
 {
     if (Pin.n_rays <= Pin.ray_first) return hipSuccess;
@@ -1717,7 +1734,7 @@ static hipError_t launch_trace_sq_t(const Params &Pin, bool adjoint, bool count,
                                               else DRT_SQ_LAUNCH_R(A, C, E, M, Q, T, false); } while (0)
 #define DRT_SQ_LAUNCH_R(A, C, E, M, Q, T, R)                                                                         \
     do {                                                                                                          \
-        auto kern = trace_sq_kernel<A, C, E, M, Q, (T) && !HG, (R) && !HG, HG, (A) && !(C) && GG>;               \
+        auto kern = trace_sq_kernel<A, C, E, M, Q, (T) && !HG, (R) && !HG, HG, (A) && !(C) && GG, H2>;           \
         static std::atomic<size_t> lds_set[64];                                                                        \
         int dev_ = 0;                                                                                             \
         if (hipGetDevice(&dev_) != hipSuccess || dev_ < 0 || dev_ >= 64) dev_ = 63;                               \
@@ -1750,6 +1767,11 @@ static hipError_t launch_trace_sq_t(const Params &Pin, bool adjoint, bool count,
 hipError_t launch_trace_sq(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream)
 {
     return launch_trace_sq_t<false>(P, adjoint, count, n_cus, stream);
+}
+#elif defined(DRT_SQ_HG2_UNIT)
+hipError_t launch_trace_sq_hg2(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream)
+{
+    return launch_trace_sq_t<true, false, true>(P, adjoint, count, n_cus, stream);
 }
 #else
 hipError_t launch_trace_sq_hg(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream)

@@ -249,9 +249,13 @@ class _DeviceIntegrator:
         # the phase function (drt_set_phase): part of what the handle is bound to, kept apart from the grids' key because
         # changing it rebuilds nothing - the library only drops the plans it made from the old paths
         ph = _check_phase(m.phase)
-        pkey = (int(ph.kind), float(ph.g))
+        two_lobe = int(ph.kind) == 2            # HG2Phase: drt_set_phase_hg2 (three parameters)
+        pkey = (2, float(ph.g1), float(ph.g2), float(ph.weight)) if two_lobe else (int(ph.kind), float(ph.g))
         if self._bound_phase.get(idx) != pkey:
-            h.set_phase(*pkey)
+            if two_lobe:
+                h.set_phase_hg2(*pkey[1:])
+            else:
+                h.set_phase(*pkey)
             self._bound_phase[idx] = pkey
         bound = self._bound.get(idx)
         if bound is None or bound[0] != key:
@@ -378,6 +382,8 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
             tangents = self.check_tangents(scene, tangents)
             if state_in is None:
                 raise ValueError("sample(Forward) needs state_in (the primal radiance of the same rays and seed)")
+        if mode == ADMode.Backward and grads is not None and grads.get(PHASE_G_KEY) is not None:
+            self._refuse_phase_grad(scene)          # (before any device work: a medium without a differentiable g)
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)
@@ -418,6 +424,8 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
         """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] in place of the per-ray δL
         (drt_render_backward_px): the same gradients as with δL = film_backward(grad_image)."""
+        if grads.get(PHASE_G_KEY) is not None:
+            self._refuse_phase_grad(scene)          # (before any device work)
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)

@@ -113,6 +113,8 @@ def render_backward(scene: Scene, integrator, grad_image: torch.Tensor, sensor: 
     `distributed.verify_pending()` (the autograd ops inside an optimisation loop, which ends with `verify_pending`).
     `keys`: the gradients to allocate when `grads` is None (default: integrator.param_keys); with PHASE_G_KEY among them (or in
     `grads`) the result also holds dLoss/dg of an HG medium, a 0-d view of the same flat buffer (one collective when sharded)."""
+    if (keys is not None and PHASE_G_KEY in keys) or (grads is not None and grads.get(PHASE_G_KEY) is not None):
+        integrator._refuse_phase_grad(scene)        # (before the primal pass: a medium or integrator without a differentiable g)
     batch = _sensor_batch(scene, sensor, spp, shard)
     sampler = IndependentSampler(seed, spp)
     L, _, state_out = integrator.sample(ADMode.Primal, scene, sampler.clone(), batch)     # :255-264

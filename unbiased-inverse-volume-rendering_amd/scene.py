@@ -127,6 +127,37 @@ class HGPhase:
         object.__setattr__(self, "g", g)
 
 
+@dataclass(frozen=True)
+class HG2Phase:
+    """Two Henyey-Greenstein lobes, Mitsuba's `blendphase` over two `hg` children:
+    p(mu) = (1 - weight) hg(g1, mu) + weight hg(g2, mu) - `weight` is the share of the SECOND lobe, as `blendphase`'s `weight` is.
+    g1, g2 finite with |g| < 1, 0 <= weight <= 1.  The usual model of a medium that scatters strongly forward and has a back-scatter
+    bump, e.g. HG2Phase(0.8, -0.3, 0.3).  weight 0 / 1 render bit for bit what HGPhase(g1) / HGPhase(g2) render.  No gradients with
+    respect to g1, g2 or weight yet: PHASE_G_KEY is refused for such a medium."""
+    g1: float = 0.8
+    g2: float = -0.3
+    weight: float = 0.3
+    kind = 2        # DRT_PHASE_HG2
+
+    def __post_init__(self):
+        for name in ("g1", "g2", "weight"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)):
+                raise TypeError(f"HG2Phase.{name} must be a real number, got {type(v).__name__}")
+        for name in ("g1", "g2"):
+            g = float(getattr(self, name))
+            if not math.isfinite(g) or not abs(float(np.float32(g))) < 1.0:  # (the kernels take g as float32)
+                raise ValueError(f"HG2Phase.{name} must be finite with |g| < 1 (in float32 too), got {g}")
+            if 0.0 < abs(g) < 1e-3:                                          # (as HGPhase: the inverted CDF cancels in float32)
+                warnings.warn(f"HG2Phase({name}={g}): for 0 < |g| < 1e-3 the published sampling formula loses its precision in float32 "
+                              "(directions off unit length); use 0.0 for an isotropic lobe", RuntimeWarning, stacklevel=3)
+            object.__setattr__(self, name, g)
+        w = float(self.weight)
+        if not (0.0 <= w <= 1.0) or not (0.0 <= float(np.float32(w)) <= 1.0):
+            raise ValueError(f"HG2Phase.weight, the share of the second lobe, must lie in [0, 1], got {w}")
+        object.__setattr__(self, "weight", w)
+
+
 def check_phase_g(g, device=None):
     """A g parameter of render(params={PHASE_G_KEY: g}): a 0-d float32 tensor on the device (it may require grad)."""
     import torch
@@ -141,21 +172,24 @@ def check_phase_g(g, device=None):
 
 def require_hg(scene, what: str):
     """The g-gradient needs a medium with the Henyey-Greenstein phase function."""
+    if isinstance(scene.medium.phase, HG2Phase):
+        raise ValueError(f"{what}: HG2Phase has no phase-parameter gradients yet - {PHASE_G_KEY} (and gradients with respect to g1, g2 "
+                         "and weight) are the follow-up; optimise the grids, or use HGPhase(g) for a single differentiable lobe")
     if not isinstance(scene.medium.phase, HGPhase):
         raise ValueError(f"{what}: a gradient with respect to {PHASE_G_KEY} needs GridMedium(phase=HGPhase(g)); the medium's phase "
                          f"function is {type(scene.medium.phase).__name__} - use HGPhase(0.0) for an isotropic medium whose g is optimised")
 
 
 def _check_phase(phase):
-    if not isinstance(phase, (IsotropicPhase, HGPhase)):
-        raise TypeError(f"GridMedium.phase must be IsotropicPhase() or HGPhase(g), got {type(phase).__name__}")
+    if not isinstance(phase, (IsotropicPhase, HGPhase, HG2Phase)):
+        raise TypeError(f"GridMedium.phase must be IsotropicPhase(), HGPhase(g) or HG2Phase(g1, g2, weight), got {type(phase).__name__}")
     return phase
 
 
 @dataclass
 class GridMedium:
     """`heterogeneous` medium with `gridvolume` sigma_t / albedo and a phase function
-    (`IsotropicPhase()`, the default, or `HGPhase(g)`), bounded by an axis-aligned box
+    (`IsotropicPhase()`, the default, `HGPhase(g)` or `HG2Phase(g1, g2, weight)`), bounded by an axis-aligned box
     (tests/test_integrators.py:79-111).
 
     sigma_t : (Z, Y, X, 1) float32, albedo : (Z, Y, X, 3) float32 - numpy arrays or
