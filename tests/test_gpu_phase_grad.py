@@ -1,4 +1,4 @@
-"""The derivative with respect to the Henyey-Greenstein asymmetry g (drt_render_backward_phase / drt_render_forward_phase, the GG
+"""The derivative with respect to the Henyey-Greenstein asymmetry g (drt_render_backward_phase / drt_render_forward_phase, the Phase::kHGGrad
 kernels).  The estimator is an extension of the reference, so these tests rest on independent checks: the device score against float64
 autograd, single scattering against the derivative of a float64 quadrature, forward / adjoint transposition over every estimator,
 finite differences in a multiple-scattering medium, the queued tracer against CoopTracer<SUPER>, autograd, a small optimisation of g,

@@ -1,4 +1,4 @@
-"""Henyey-Greenstein phase function on the device (drt_set_phase, CoopTracer<HG>).  The CPU oracle is isotropic, so these tests rest on
+"""Henyey-Greenstein phase function on the device (drt_set_phase, CoopTracer<Phase::kHG>).  The CPU oracle is isotropic, so these tests rest on
 independent checks: the device primitive against the numpy restatement of Mitsuba's `hg` plugin, a known answer for single scattering
 (a float64 quadrature over distance x sphere), estimators that must agree with each other (NEE on / off; HG g = 0 against isotropic),
 the forward / adjoint transposition identity, and the handle's state across phase changes."""
@@ -399,7 +399,7 @@ def test_set_phase_refusals_on_a_handle(uivr, gpu):
 @pytest.mark.parametrize("variant", list(VARIANTS))
 @pytest.mark.parametrize("env", [False, True])
 def test_queued_and_coop_super_agree_with_hg(uivr, gpu, variant, env):
-    """Factor > 0 with HG runs trace_sq_kernel<HG>; test hook 4096 keeps the launch off the queued tracer (CoopTracer<SUPER, HG>).  Same
+    """Factor > 0 with HG runs trace_sq_kernel<Phase::kHG>; test hook 4096 keeps the launch off the queued tracer (CoopTracer<SUPER, Phase::kHG>).  Same
     paths, same arithmetic: radiance bit-identical per ray, gradients within the parity tolerance."""
     from test_gpu_envmap import _env_scene
     scene = _env_scene(uivr, film=32, factor=3)

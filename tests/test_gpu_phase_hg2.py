@@ -1,4 +1,4 @@
-"""Two-lobe Henyey-Greenstein phase function on the device (drt_set_phase_hg2; the H2 instantiations of the HG kernels).  The CPU oracle is
+"""Two-lobe Henyey-Greenstein phase function on the device (drt_set_phase_hg2; the Phase::kHG2 instantiations of the tracers).  The CPU oracle is
 isotropic, so these tests rest on the checks of test_gpu_phase_hg.py, with the mixture in place of the single lobe: the device primitive
 against a float32 restatement, exact degeneracy at weight 0 / 1 against HGPhase, a float64 single-scattering quadrature, estimators and
 tracers that must agree, the forward / adjoint transposition identity, finite differences, and the handle's state and refusals."""
@@ -238,7 +238,7 @@ def test_hg2_nee_on_and_off_agree(uivr, gpu, factor):
 @pytest.mark.parametrize("variant", list(VARIANTS))
 @pytest.mark.parametrize("env", [False, True])
 def test_queued_and_coop_super_agree_with_hg2(uivr, gpu, variant, env):
-    """Factor > 0 runs trace_sq_kernel<HG, H2>; test hook 4096 keeps the launch off the queued tracer (CoopTracer<SUPER, HG, H2>).  Same
+    """Factor > 0 runs trace_sq_kernel<Phase::kHG2>; test hook 4096 keeps the launch off the queued tracer (CoopTracer<SUPER, Phase::kHG2>).  Same
     paths, same arithmetic: radiance bit-identical per ray, gradients within the parity tolerance."""
     from test_gpu_envmap import _env_scene
     scene = _env_scene(uivr, film=32, factor=3)

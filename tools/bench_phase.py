@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The Henyey-Greenstein phase function (drt_set_phase; CoopTracer<HG>, trace_sq_kernel<HG>) against the isotropic one on the headline's job.
+"""The Henyey-Greenstein phase function (drt_set_phase; CoopTracer<Phase::kHG>, trace_sq_kernel<Phase::kHG>) against the isotropic one on the headline's job.
 
 Jobs (dust devil 256^3, 512^2 x 32 spp, volpathsimple-drt, one primal + adjoint step as bench.py times it):
   iso     the isotropic phase function (the production kernels)

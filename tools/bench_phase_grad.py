@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The cost of the gradient with respect to the Henyey-Greenstein asymmetry g (the GG kernels) on the headline's job with HGPhase(0.8).
+"""The cost of the gradient with respect to the Henyey-Greenstein asymmetry g (the Phase::kHGGrad kernels) on the headline's job with HGPhase(0.8).
 
 Jobs (dust devil 256^3, 512^2 x 32 spp, volpathsimple-drt, majorant_resolution_factor 8 by default):
   step        render_primal + render_backward as bench.py times them (the backward call's own primal, the adjoint, the reduction)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The two-lobe Henyey-Greenstein phase function (drt_set_phase_hg2; CoopTracer<HG, H2>, trace_sq_kernel<HG, H2>) against the single lobe and
+"""The two-lobe Henyey-Greenstein phase function (drt_set_phase_hg2; CoopTracer<Phase::kHG2>, trace_sq_kernel<Phase::kHG2>) against the single lobe and
 the isotropic phase function on the headline's job.
 
 Jobs (dust devil 256^3, 512^2 x 32 spp, volpathsimple-drt, one primal + adjoint step as bench.py times it):

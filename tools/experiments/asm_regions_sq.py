@@ -1,8 +1,8 @@
 """Static instruction counts per source region of trace_sq_kernel (experiment).
    hipcc ... -gline-tables-only -S --cuda-device-only drt_sq.hip -o sq.s ; python tools/experiments/asm_regions_sq.py sq.s ILb0ELb0ELb0E [src] [kernel-prefix]"""
-import re, sys, collections
+import os, re, sys, collections
 asm, inst = sys.argv[1], sys.argv[2]
-srcf = sys.argv[3] if len(sys.argv) > 3 else '/root/repo/unbiased-inverse-volume-rendering_amd/csrc/drt_sq.hip'
+srcf = sys.argv[3] if len(sys.argv) > 3 else os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'unbiased-inverse-volume-rendering_amd', 'csrc', 'drt_sq_kernel.h')
 prefix = sys.argv[4] if len(sys.argv) > 4 else '_ZN3drt15trace_sq_kernel'
 src = open(srcf).read().split('\n')
 marks = [("prologue", 0)]

@@ -26,8 +26,7 @@ HIP_SOURCES = ["drt_kernels.hip", "drt_deferred.hip", "drt_coop.hip", "drt_coop_
 # older generations of the tracer (round 1/2 state machine of whole flights, round 3 lane state machines with posted flights): no production call
 # reaches them ("which call reaches which kernel"); the flavour with test hooks keeps them in lock-step with the oracle
 HOOKS_ONLY_SOURCES = ["drt_wavefront.hip", "drt_super.hip"]
-# (drt_sq.hip is a dependency of drt_sq_hg.hip and drt_sq_hg2.hip too, which include it)
-HIP_HEADERS = ["drt_sq.hip", "drt_device.h", "drt_launch.h", "drt_coop_tracer.h", "drt_coop_kernel.h", "drt_nerf_kernel.h", "drt_film.h", os.path.join(_ROOT, "include", "drt_hip.h")]
+HIP_HEADERS = ["drt_sq_kernel.h", "drt_device.h", "drt_launch.h", "drt_coop_tracer.h", "drt_coop_kernel.h", "drt_nerf_kernel.h", "drt_film.h", os.path.join(_ROOT, "include", "drt_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
              "-ffp-contract=off", "-munsafe-fp-atomics", "-Wall"]
 

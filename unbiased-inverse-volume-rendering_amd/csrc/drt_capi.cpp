@@ -401,7 +401,7 @@ hipError_t early_histogram_between(void *ctx)
 // ---- which call reaches which kernel --------------------------------------------------------------------------------------------------------
 enum class Route {
     kCoop,       // CoopTracer / CoopTracer<SUPER> (drt_coop.hip, drt_coop_super.hip)
-    kCoopHG,     // CoopTracer<HG> / <GG> / <H2> (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip and their _hg2 units)
+    kCoopHG,     // CoopTracer with a Henyey-Greenstein phase, kHG / kHGGrad / kHG2 (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip and their _hg2 units)
     kOwn,        // CoopTracer with the colour grids on their own lattice (drt_own.hip)
     kQueued,     // the queued supergrid tracer (drt_sq.hip, drt_sq_hg.hip, drt_sq_hg2.hip)
 #ifdef DRT_TEST_HOOKS
@@ -410,9 +410,17 @@ enum class Route {
     kPerLane,    // the plain per-lane Tracer (drt_kernels.hip)
 #endif
 };
-// hg: the HG instantiations (drt_set_phase, drt_set_phase_hg2); gg: ... with the g-gradient, an HG adjoint launch with a sink in Params::L_out;
-// hg2 (with hg, never with gg): their two-lobe instantiations
-struct Choice { Route route; bool hg, gg, hg2; };
+// phase: the instantiations of the handle's phase function (tracer_phase)
+struct Choice { Route route; drt::Phase phase; };
+
+// The phase a tracing launch of this handle runs with.  grad_g: the derivative with respect to g too (kHGGrad: an HG handle only) - an adjoint
+// launch with a sink in Params::L_out (drt_render_backward_phase), a forward launch with a g tangent (drt_render_forward_phase)
+drt::Phase tracer_phase(drt_handle h, bool grad_g)
+{
+    if (h->phase_kind == DRT_PHASE_HG2) return drt::Phase::kHG2;
+    if (h->phase_kind == DRT_PHASE_HG) return grad_g ? drt::Phase::kHGGrad : drt::Phase::kHG;
+    return drt::Phase::kIso;
+}
 
 // Kernel choice - which call reaches which kernel (DESIGN.md section 1 has the table); launches nothing, allocates nothing:
 //   global majorant (majorant_resolution_factor 0): CoopTracer (drt_coop.hip: one ray per lane, wave-cooperative tracking rounds), both passes;
@@ -429,16 +437,17 @@ struct Choice { Route route; bool hg, gg, hg2; };
 //   Henyey-Greenstein phase (drt_set_phase): the same choice among the HG instantiations - the queued tracer (drt_sq_hg.hip) for the
 //   supergrids it takes, CoopTracer<HG> otherwise (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip) - without tail launches or
 //   hand-off, and no ROUNDS kernels; the older generations have no HG code.
-//   The g-gradient (drt_render_backward_phase: an HG adjoint launch with a sink in Params::L_out) runs the GG instantiations of the same
+//   The g-gradient (drt_render_backward_phase: an HG adjoint launch with a sink in Params::L_out) runs the kHGGrad instantiations of the same
 //   kernels; the counting kernels have none (such a launch counts nothing).
-//   Two-lobe Henyey-Greenstein phase (drt_set_phase_hg2): the HG choice among the H2 instantiations (drt_sq_hg2.hip, drt_coop_hg2.hip,
+//   Two-lobe Henyey-Greenstein phase (drt_set_phase_hg2): the HG choice among the kHG2 instantiations (drt_sq_hg2.hip, drt_coop_hg2.hip,
 //   drt_coop_super_hg2.hip, drt_own_hg2.hip); no g-gradient kernels.
 Choice choose_tracer(drt_handle h, const drt::Params &P, bool adjoint)
 {
     const uint32_t f = h->debug_flags;
-    const bool hg2 = h->phase_kind == DRT_PHASE_HG2, hg = hg2 || h->phase_kind == DRT_PHASE_HG, gg = hg && !hg2 && adjoint && P.L_out != nullptr;
-    auto to = [=](Route r) { return Choice{ r, hg, gg, hg2 }; };
-    // (kHookNoQueuedTracer: CoopTracer<SUPER, HG> here - the HG kernels' tracer-agreement tests)
+    const drt::Phase phase = tracer_phase(h, adjoint && P.L_out != nullptr);
+    const bool hg = phase != drt::Phase::kIso;
+    auto to = [=](Route r) { return Choice{ r, phase }; };
+    // (kHookNoQueuedTracer: CoopTracer<SUPER> with the HG phase here - the HG kernels' tracer-agreement tests)
     if (hg && (P.colour_own || !P.mgrid || dbg(f, kHookNoQueuedTracer))) return to(Route::kCoopHG);
     if (P.colour_own) return to(Route::kOwn);
     // a supergrid launch: not when a test hook or the atomic gradient path (an adjoint launch without record streams) routes it to the older kernels
@@ -460,18 +469,13 @@ Choice choose_tracer(drt_handle h, const drt::Params &P, bool adjoint)
     return to(Route::kCoop);
 }
 
-// CoopTracer<HG> / <GG> and the kernels of drt_own.hip: no tail pool, no ray schedule on a supergrid
+// CoopTracer with a Henyey-Greenstein phase, and the kernels of drt_own.hip: no tail pool, no ray schedule on a supergrid
 int launch_coop_hg_or_own(drt_handle h, const drt::Params &P, bool adjoint, const Choice &c)
 {
     drt::Params Q = P;
     no_tail(Q);
     if (P.mgrid) Q.ray_perm = nullptr;
-    if (c.gg) DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_gg(Q, h->stream) : drt::launch_trace_coop_gg(Q, h->stream));
-    else if (!c.hg) DRT_HIP_CHECK(h, drt::launch_trace_own(Q, adjoint, h->counting, h->stream));
-    else if (c.hg2) DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_hg2(Q, adjoint, h->counting, h->stream)
-                                                  : drt::launch_trace_coop_hg2(Q, adjoint, h->counting, h->stream));
-    else if (P.colour_own) DRT_HIP_CHECK(h, drt::launch_trace_own_hg(Q, adjoint, h->counting, h->stream));
-    else DRT_HIP_CHECK(h, drt::launch_trace_coop_hg(Q, adjoint, h->counting, h->stream));
+    DRT_HIP_CHECK(h, drt::launch_trace_coop(Q, c.phase, adjoint, h->counting, h->stream));
     return DRT_OK;
 }
 
@@ -498,7 +502,7 @@ int launch_coop(drt_handle h, const drt::Params &P, bool adjoint)
         // by path length costs more than it saves (24.6 vs 18.8 ms at majorant_resolution_factor 8)
         drt::Params Q = PT;
         Q.ray_perm = nullptr;
-        DRT_HIP_CHECK(h, drt::launch_trace_coop(Q, adjoint, h->counting, h->stream));
+        DRT_HIP_CHECK(h, drt::launch_trace_coop(Q, drt::Phase::kIso, adjoint, h->counting, h->stream));
         return DRT_OK;
     }
     // (kHookNoTailOverlap: no early histogram pass)
@@ -509,7 +513,7 @@ int launch_coop(drt_handle h, const drt::Params &P, bool adjoint)
     }
     EarlyCtx ctx{ h, &PT };
     bool called = false;
-    DRT_HIP_CHECK(h, drt::launch_trace_coop(PT, adjoint, h->counting, h->stream, early ? early_histogram_between : nullptr, &ctx, &called));
+    DRT_HIP_CHECK(h, drt::launch_trace_coop(PT, drt::Phase::kIso, adjoint, h->counting, h->stream, early ? early_histogram_between : nullptr, &ctx, &called));
     h->early_done = called;
     return DRT_OK;
 }
@@ -574,7 +578,7 @@ int begin_supergrid_launch(drt_handle h, const drt::Params &P, drt::Params &Q, b
     if (h->majorant_pending && hipEventQuery(h->ev_majorant) == hipSuccess) { h->majorant_seen = *h->h_majorant; h->majorant_pending = false; }
     else if (h->majorant_pending) (void) hipGetLastError();                        // (hipErrorNotReady is not an error)
     const float dx = P.bmax[0] - P.bmin[0], dy = P.bmax[1] - P.bmin[1], dz = P.bmax[2] - P.bmin[2];
-    Q.sq_rounds = (!c.hg && !adjoint && h->majorant_seen >= 0.0f && h->majorant_seen * std::sqrt(dx * dx + dy * dy + dz * dz) < 3.0f) ? 1u : 0u;
+    Q.sq_rounds = (c.phase == drt::Phase::kIso && !adjoint && h->majorant_seen >= 0.0f && h->majorant_seen * std::sqrt(dx * dx + dy * dy + dz * dz) < 3.0f) ? 1u : 0u;
     DRT_HIP_CHECK(h, hipMemsetAsync(h->d_queues, 0, 8 * sizeof(unsigned long long), h->stream));
     return DRT_OK;
 }
@@ -626,14 +630,10 @@ int launch_queued(drt_handle h, const drt::Params &P, bool adjoint, const Choice
     DRT_TRY(begin_supergrid_launch(h, P, Q, adjoint, c));
     Q.sq_cold = h->sq_cold.p;
     bool big = false;
-    DRT_TRY(bind_sq_tail(h, Q, adjoint, c.hg, &big));
-    if (c.hg) {
-        no_tail(Q);
-        if (c.gg) DRT_HIP_CHECK(h, drt::launch_trace_sq_gg(Q, h->n_cus, h->stream));
-        else if (c.hg2) DRT_HIP_CHECK(h, drt::launch_trace_sq_hg2(Q, adjoint, h->counting, h->n_cus, h->stream));
-        else DRT_HIP_CHECK(h, drt::launch_trace_sq_hg(Q, adjoint, h->counting, h->n_cus, h->stream));
-    }
-    else DRT_HIP_CHECK(h, drt::launch_trace_sq(Q, adjoint, h->counting, h->n_cus, h->stream));
+    const bool hg = c.phase != drt::Phase::kIso;
+    DRT_TRY(bind_sq_tail(h, Q, adjoint, hg, &big));
+    if (hg) no_tail(Q);
+    DRT_HIP_CHECK(h, drt::launch_trace_sq(Q, c.phase, adjoint, h->counting, h->n_cus, h->stream));
     if (!Q.tail_pool) return DRT_OK;
     if (big) {
         DRT_TRY(ensure_side_stream(h));
@@ -656,7 +656,7 @@ int launch_queued(drt_handle h, const drt::Params &P, bool adjoint, const Choice
         T.rec_cap_chunks[0] = T.rec_cap_chunks[1] = 0;
     }
     T.order = nullptr; T.unit_empty = nullptr;
-    DRT_HIP_CHECK(h, drt::launch_trace_sq(T, adjoint, h->counting, h->n_cus, h->stream));
+    DRT_HIP_CHECK(h, drt::launch_trace_sq(T, c.phase, adjoint, h->counting, h->n_cus, h->stream));
     if (big) { h->early_done = true; h->early_partition = true; }
     return DRT_OK;
 }
@@ -688,7 +688,8 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
     TimedSpan span;
     DRT_HIP_CHECK(h, span.begin(h, h->stream));
     const Choice c = choose_tracer(h, P, adjoint);
-    if (c.hg && dbg(h->debug_flags, kHookOlderTracers))
+    const bool hg = c.phase != drt::Phase::kIso;
+    if (hg && dbg(h->debug_flags, kHookOlderTracers))
         return fail(h, DRT_ERR_UNSUPPORTED, "the Henyey-Greenstein phase functions have no code in the older tracer generations: the test hook "
                                             "routes this launch to one of them (debug flags 0x%x)", h->debug_flags);
     int rc = DRT_OK;
@@ -699,7 +700,7 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
         // (the records' global halves, ~44 MB, are allocated only by a launch that will run the queued kernel: not when a test hook or the atomic
         //  gradient path routes this launch to the older kernels; no memory: the route of a supergrid the queued tracer does not take)
         DRT_TRY(h->sq_cold.grow(h, drt::sq_cold_bytes(h->n_cus), kBestEffort));
-        rc = h->sq_cold.p ? launch_queued(h, P, adjoint, c) : c.hg ? launch_coop_hg_or_own(h, P, adjoint, c) : launch_coop(h, P, adjoint);
+        rc = h->sq_cold.p ? launch_queued(h, P, adjoint, c) : hg ? launch_coop_hg_or_own(h, P, adjoint, c) : launch_coop(h, P, adjoint);
         break;
     case Route::kCoop: rc = launch_coop(h, P, adjoint); break;
 #ifdef DRT_TEST_HOOKS
@@ -807,7 +808,7 @@ int timed_nerf(drt_handle h, int which, const drt::Params &P, bool adjoint, hipS
     if (!st) st = h->stream;
     TimedSpan span;
     DRT_HIP_CHECK(h, span.begin(h, st));
-    DRT_HIP_CHECK(h, P.colour_own ? drt::launch_nerf_own(P, adjoint, h->counting, st) : drt::launch_nerf(P, adjoint, h->counting, st));
+    DRT_HIP_CHECK(h, drt::launch_nerf(P, adjoint, h->counting, st));
     DRT_HIP_CHECK(h, span.end(which));
     return DRT_OK;
 }
@@ -1520,7 +1521,7 @@ static void forward_params(drt::Params &P, const float *t_sigma, const float *t_
     P.dL = nullptr; P.dL_pix = nullptr; P.gt = nullptr;
 }
 
-// t_phase_g != 0 (drt_render_forward_phase, an HG handle): the GG kernels, which add t_g dL/dg (Params::phase_tg, in padding of the block)
+// t_phase_g != 0 (drt_render_forward_phase, an HG handle): the kHGGrad kernels, which add t_g dL/dg (Params::phase_tg, in padding of the block)
 static int render_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
                           uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo, float *dL_out, float t_phase_g)
 {
@@ -1529,15 +1530,8 @@ static int render_forward(drt_handle h, const float *rays_o, const float *rays_d
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
     forward_params(P, t_sigma_t, t_albedo, dL_out);
     P.L_in = L_in;
-    const bool hg2 = h->phase_kind == DRT_PHASE_HG2;            // (its g2 travels in phase_tg: t_phase_g is 0, check_phase_grad)
-    if (!hg2) P.phase_tg = t_phase_g;
-    if (hg2)
-        DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_hg2(P, h->stream) : drt::launch_trace_coop_fwd_hg2(P, h->stream));
-    else if (t_phase_g != 0.0f)                                      // (drt_render_forward_phase with a g tangent: an HG handle)
-        DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_gg(P, h->stream) : drt::launch_trace_coop_fwd_gg(P, h->stream));
-    else if (h->phase_kind == DRT_PHASE_HG)
-        DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd_hg(P, h->stream) : drt::launch_trace_coop_fwd_hg(P, h->stream));
-    else DRT_HIP_CHECK(h, P.colour_own ? drt::launch_trace_own_fwd(P, h->stream) : drt::launch_trace_coop_fwd(P, h->stream));
+    if (h->phase_kind != DRT_PHASE_HG2) P.phase_tg = t_phase_g;    // (HG2: its g2 travels in phase_tg, and t_phase_g is 0: check_phase_grad)
+    DRT_HIP_CHECK(h, drt::launch_trace_coop_fwd(P, tracer_phase(h, t_phase_g != 0.0f), h->stream));
     return DRT_OK;
 }
 
@@ -1575,7 +1569,7 @@ int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const floa
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
     DRT_TRY(nerf_fill(h, P, cfg, emission));
     forward_params(P, t_sigma_t, t_emission, dL_out);
-    DRT_HIP_CHECK(h, P.colour_own ? drt::launch_nerf_own_fwd(P, h->stream) : drt::launch_nerf_fwd(P, h->stream));
+    DRT_HIP_CHECK(h, drt::launch_nerf_fwd(P, h->stream));
     return DRT_OK;
 }
 

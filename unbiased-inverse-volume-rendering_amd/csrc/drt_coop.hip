@@ -1,5 +1,6 @@
 // drt_coop.hip -- kernels of the one-ray-per-lane tracer with wave-cooperative tracking loops (CoopTracer,
-// drt_coop_tracer.h): VolpathSimpleIntegrator.sample in both AD modes (volpathsimple.py:38-655).
+// drt_coop_tracer.h): VolpathSimpleIntegrator.sample in both AD modes (volpathsimple.py:38-655) - the isotropic, global-majorant cell - and the
+// kernels behind its block order and ray schedule.
 #include "drt_coop_kernel.h"
 
 namespace drt {
@@ -112,17 +113,6 @@ hipError_t launch_block_order(const uint32_t *cost, uint32_t n_blocks, uint32_t 
     return hipGetLastError();
 }
 
-hipError_t launch_trace_coop(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx,
-                             bool *called)
-{
-    if (P.mgrid) return launch_trace_coop_super(P, adjoint, count, stream);      // drt_coop_super.hip
-    return launch_trace_coop_t<false>(P, adjoint, count, stream, between, between_ctx, called);
-}
-
-hipError_t launch_trace_coop_fwd(const Params &P, hipStream_t stream)
-{
-    if (P.mgrid) return launch_trace_coop_super_fwd(P, stream);      // drt_coop_super.hip
-    return launch_trace_coop_fwd_t<false>(P, stream);
-}
+template struct CoopUnit<Phase::kIso, false, false>;
 
 }  // namespace drt

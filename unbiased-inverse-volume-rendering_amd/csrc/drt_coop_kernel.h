@@ -1,7 +1,7 @@
-// drt_coop_kernel.h -- the kernel of the one-ray-per-lane tracer (CoopTracer, drt_coop_tracer.h) and its launcher,
-// templated on SUPER (majorant supergrid): instantiated by drt_coop.hip (global majorant: wave-cooperative tracking
-// rounds) and drt_coop_super.hip (supergrid: every tracking step on the walk's own lane) - two translation units so
-// that the two sets of kernels compile side by side.
+// drt_coop_kernel.h -- the kernels of the one-ray-per-lane tracer (CoopTracer, drt_coop_tracer.h) and their launchers, templated on
+// SUPER (majorant supergrid) and the phase function: a drt_coop*.hip unit (global majorant: wave-cooperative tracking rounds), a
+// drt_coop_super*.hip unit (supergrid: every tracking step on the walk's own lane) or a drt_own*.hip unit (either, colour grids on their own
+// lattice) instantiates one cell (CoopUnit, at the end) - separate translation units so that the sets of kernels compile side by side.
 #pragma once
 #include "drt_coop_tracer.h"
 
@@ -13,13 +13,12 @@ using namespace coop;
 
 // TAIL: the second launch of a specialised kernel - its workgroups start from 256 paths of the tail pool each
 // (CoopTracer::wg_handoff) instead of from rays, and finish them
-// HG: Henyey-Greenstein phase function (CoopTracer); those kernels run without hand-off and tail pool
-// GG (adjoint, with HG): the g-gradient too - each wave adds the sum of its lanes' terms to *Params::L_out with one atomic at its end
-// H2 (with HG, never with GG): the two-lobe Henyey-Greenstein mixture (CoopTracer<H2>; drt_set_phase_hg2)
-template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, bool HG = false, bool GG = false,
-          bool H2 = false>
+// PH: the phase function (CoopTracer).  kHG, kHGGrad, kHG2: those kernels run without hand-off and tail pool; kHGGrad (adjoint): the
+// g-gradient too - each wave adds the sum of its lanes' terms to *Params::L_out with one atomic at its end
+template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, Phase PH = Phase::kIso>
 __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRIMAL) trace_coop_kernel(const Params P)
 {
+    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad;
     if constexpr (TAIL) { if (blockIdx.x * 256u >= *P.tail_count) return; }   // (workgroup-uniform) nothing for this workgroup
     uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map (see trace_kernel)
     if (P.block_order) b = P.block_order[blockIdx.x];            // heavy blocks first (adjoint: this job's primal costs; primal: the previous launch's)
@@ -39,8 +38,8 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
     if constexpr (ADJ && !SUPER) {                              // rays of similar length share a wave (ray_perm_kernel)
         if (P.ray_perm) i = (i_block & ~(uint64_t) (kPermGroup - 1)) + P.ray_perm[i_block + threadIdx.x];
     }
-    static_assert(!GG || (ADJ && HG && !TAIL), "the g-gradient kernels are HG adjoint kernels");
-    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, HG, GG, H2> tr(P);
+    static_assert(!GG || (ADJ && !TAIL), "the g-gradient kernels (kHGGrad) are adjoint kernels and have no tail launch");
+    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, PH> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     tr.i_block = TAIL ? 0 : i_block;
@@ -159,8 +158,8 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
 // Forward mode (drt_render_forward): CoopTracer<FWD> runs the adjoint's paths with dL = 1, gathering from the tangent grids where the
 // adjoint splats (the tangent grids are Params::g_sigma / g_albedo), and writes J t of its ray to L_out - once, from the ray's own lane (no hand-off, no tail pool, no atomics: the result is
 // bit-reproducible).  The global majorant's NEE walks take every step on the walk's own lane (CoopTracer::coop_rt).
-// GG (with HG): J t includes t_g (Params::phase_tg) times the derivative with respect to g
-template <bool ENV, bool SPEC, bool SUPER, bool HG = false, bool GG = false, bool H2 = false>
+// PH = kHGGrad: J t includes t_g (Params::phase_tg) times the derivative with respect to g
+template <bool ENV, bool SPEC, bool SUPER, Phase PH = Phase::kIso>
 __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(const Params P)
 {
     uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map (see trace_coop_kernel)
@@ -175,7 +174,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     }
 #endif
     const uint64_t i = P.ray_first + (uint64_t) b * blockDim.x + threadIdx.x;
-    CoopTracer<false, ENV, false, SPEC, false, SUPER, true, HG, GG, H2> tr(P);
+    CoopTracer<false, ENV, false, SPEC, false, SUPER, true, PH> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     __shared__ uint64_t jump_lds[2 * (kJumpMax + 1)];
@@ -222,7 +221,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     if (job) { P.L_out[3 * i] = tr.tg[0]; P.L_out[3 * i + 1] = tr.tg[1]; P.L_out[3 * i + 2] = tr.tg[2]; }
 }
 
-template <bool SUPER, bool HG = false, bool GG = false, bool H2 = false>
+template <bool SUPER, Phase PH>
 hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
@@ -230,24 +229,31 @@ hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
     const bool env = P.env_pix != nullptr;
     const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, kHookGenericKernels);
     if (spec) {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, HG, GG, H2>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, HG, GG, H2>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, PH>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, PH>), grid, block, 0, stream, P);
     } else {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER, HG, GG, H2>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER, HG, GG, H2>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER, PH>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER, PH>), grid, block, 0, stream, P);
     }
     return hipGetLastError();
 }
 
-// launch of the instantiation that fits the job (HG: the Henyey-Greenstein instantiations - no tail pool, no hand-off; H2: their two-lobe ones)
-template <bool SUPER, bool HG = false, bool H2 = false>
-hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between = nullptr,
-                               void *between_ctx = nullptr, bool *called = nullptr)
+// launch of the instantiation that fits the job.  kHG, kHGGrad, kHG2: no tail pool, no hand-off.  kHGGrad: the adjoint launch with the
+// g-gradient (dLoss/dg is added to *P.L_out) - the choice of a kHG adjoint launch without the counting kernels (a counting handle's g-gradient
+// launch counts nothing); its primal and counting kernels are kHG's (kPlain)
+template <bool SUPER, Phase PH>
+hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx, bool *called)
 {
+    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad;
+    constexpr Phase kPlain = GG ? Phase::kHG : PH;
     if (P.n_rays <= P.ray_first) return hipSuccess;
+    if (GG) {
+        if (!adjoint || !P.L_out || P.tail_pool) return hipErrorInvalidValue;
+        count = false;
+    }
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
     const bool env = P.env_pix != nullptr, defer = adjoint && P.rec_buf[0] != nullptr;
-#define DRT_COOP_LAUNCH(A, C, E, D) hipLaunchKernelGGL((trace_coop_kernel<A, C, E, D, false, SUPER, false, HG, false, H2>), grid, block, 0, stream, P)
+#define DRT_COOP_LAUNCH(A, C, E, D) hipLaunchKernelGGL((trace_coop_kernel<A, C, E, D, false, SUPER, false, (A) && !(C) ? PH : kPlain>), grid, block, 0, stream, P)
     // the registered `volpathsimple-drt` configuration (either emitter): specialised kernels
     const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !count && !dbg(P.debug_flags, kHookGenericKernels);
 #if DRT_PHASE_PROFILE
@@ -277,13 +283,13 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
     const dim3 tgrid(tail ? P.tail_cap / 256u : 1u);
     // (pool capacity = 1/8 of the launch's rays; the tail kernel's surplus workgroups return at once)
     if (spec && !adjoint) {
-        if (env) hipLaunchKernelGGL((trace_coop_kernel<false, false, true, false, true, SUPER, false, HG, false, H2>), grid, block, 0, stream, M);
-        else hipLaunchKernelGGL((trace_coop_kernel<false, false, false, false, true, SUPER, false, HG, false, H2>), grid, block, 0, stream, M);
+        if (env) hipLaunchKernelGGL((trace_coop_kernel<false, false, true, false, true, SUPER, false, kPlain>), grid, block, 0, stream, M);
+        else hipLaunchKernelGGL((trace_coop_kernel<false, false, false, false, true, SUPER, false, kPlain>), grid, block, 0, stream, M);
         return hipGetLastError();
     }
     if (spec && defer) {
-        if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, SUPER, false, HG, false, H2>), grid, block, 0, stream, M);
-        else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, SUPER, false, HG, false, H2>), grid, block, 0, stream, M);
+        if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, SUPER, false, PH>), grid, block, 0, stream, M);
+        else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, SUPER, false, PH>), grid, block, 0, stream, M);
         if constexpr (!SUPER && !HG) if (tail) {
             if (between) {                                     // (e.g. the early histogram pass of the record streams)
                 hipError_t e = between(between_ctx);
@@ -309,24 +315,23 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
     return hipGetLastError();
 }
 
-// the adjoint launch with the g-gradient (HG + GG instantiations; dLoss/dg is added to *P.L_out): the choice launch_trace_coop_t makes for
-// an HG adjoint launch, without the counting kernels (a counting handle's g-gradient launches count nothing)
-template <bool SUPER>
-hipError_t launch_trace_coop_gg_t(const Params &P, hipStream_t stream)
+}  // namespace
+
+// this unit's cell of launch_trace_coop / launch_trace_coop_fwd (drt_launch.h); a unit instantiates CoopUnit for the cells whose kernels it holds
+template <Phase PH, bool SUPER, bool OWN>
+hipError_t CoopUnit<PH, SUPER, OWN>::trace(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx,
+                                           bool *called)
 {
-    if (P.n_rays <= P.ray_first) return hipSuccess;
-    if (!P.L_out || P.tail_pool) return hipErrorInvalidValue;
-    dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
-    const bool env = P.env_pix != nullptr, defer = P.rec_buf[0] != nullptr;
-    const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, kHookGenericKernels);
-#define DRT_COOP_LAUNCH_GG(E, D, SP) hipLaunchKernelGGL((trace_coop_kernel<true, false, E, D, SP, SUPER, false, true, true>), grid, block, 0, stream, P)
-    if (spec && defer) { if (env) DRT_COOP_LAUNCH_GG(true, true, true); else DRT_COOP_LAUNCH_GG(false, true, true); }
-    else if (defer) { if (env) DRT_COOP_LAUNCH_GG(true, true, false); else DRT_COOP_LAUNCH_GG(false, true, false); }
-    else { if (env) DRT_COOP_LAUNCH_GG(true, false, false); else DRT_COOP_LAUNCH_GG(false, false, false); }
-#undef DRT_COOP_LAUNCH_GG
-    return hipGetLastError();
+    static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
+    if (OWN) between = nullptr;
+    return launch_trace_coop_t<SUPER, PH>(P, adjoint, count, stream, between, between_ctx, called);
 }
 
-}  // namespace
+template <Phase PH, bool SUPER, bool OWN>
+hipError_t CoopUnit<PH, SUPER, OWN>::forward(const Params &P, hipStream_t stream)
+{
+    static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
+    return launch_trace_coop_fwd_t<SUPER, PH>(P, stream);
+}
 
 }  // namespace drt

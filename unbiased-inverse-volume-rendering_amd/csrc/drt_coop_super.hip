@@ -5,11 +5,6 @@
 
 namespace drt {
 
-hipError_t launch_trace_coop_super(const Params &P, bool adjoint, bool count, hipStream_t stream)
-{
-    return launch_trace_coop_t<true>(P, adjoint, count, stream);
-}
-
-hipError_t launch_trace_coop_super_fwd(const Params &P, hipStream_t stream) { return launch_trace_coop_fwd_t<true>(P, stream); }
+template struct CoopUnit<Phase::kIso, true, false>;
 
 }  // namespace drt

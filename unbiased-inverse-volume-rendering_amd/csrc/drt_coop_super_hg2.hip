@@ -4,11 +4,6 @@
 
 namespace drt {
 
-hipError_t launch_trace_coop_super_hg2(const Params &P, bool adjoint, bool count, hipStream_t stream)
-{
-    return launch_trace_coop_t<true, true, true>(P, adjoint, count, stream);
-}
-
-hipError_t launch_trace_coop_super_fwd_hg2(const Params &P, hipStream_t stream) { return launch_trace_coop_fwd_t<true, true, false, true>(P, stream); }
+template struct CoopUnit<Phase::kHG2, true, false>;
 
 }  // namespace drt

@@ -116,22 +116,20 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 // runs with dL = 1 and every splat becomes a gather - same paths, same random numbers.  Where the adjoint has summed the
 // channels before its splat (the NEE walk's a_sum, the scatter sites' gs) the channels are kept apart.  Every ray ends on
 // its own lane: no hand-off (wgc), no tail pool, no path cache, no atomics.
-// HG: the Henyey-Greenstein phase function with asymmetry Params::phase_g (drt_set_phase) instead of the isotropic one, at every site
-// that samples or evaluates the phase function: the scatter sites of main and recursive paths (volpathsimple.py:221-230, 630-646), the
-// NEE phase value and MIS weight (:386-391), and the escape MIS weight through last_pdf (:273-277).  The incoming direction of a
-// scatter is wi = -d of the ray that reached it.  Without hand-off or tail pool: a handed-off path would have to carry its last pdf.
-// GG (with HG): the derivative with respect to g as well, from the main path only ("Gradient with respect to g"): the score
-// hg_score of every sampled direction and the explicit terms of the two MIS weights.  Adjoint: g_acc sums <dL, .> of the terms on each lane
-// (the kernel adds a wave's sum to Params::L_out once); forward mode: g_S carries the scores sampled so far and every contribution adds
-// c (g_S + explicit term) t_g (Params::phase_tg) to tg.
-// H2 (with HG, never with GG): the two-lobe mixture (drt_set_phase_hg2; drt_device.h: hg2_eval, hg2_sample) at the same sites - g1 in
-// Params::phase_g, g2 in Params::phase_tg, the second lobe's share in Params::phase_w.  The scatter sites keep the next_1d draw the other
-// instantiations drop: it chooses the lobe.
-template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, bool HG = false,
-          bool GG = false, bool H2 = false>
+// PH: the phase function, at every site that samples or evaluates it: the scatter sites of main and recursive paths
+// (volpathsimple.py:221-230, 630-646), the NEE phase value and MIS weight (:386-391), and the escape MIS weight through last_pdf (:273-277).
+// The incoming direction of a scatter is wi = -d of the ray that reached it.
+//   kHG (HG below; kHGGrad and kHG2 are HG too): Henyey-Greenstein with asymmetry Params::phase_g instead of the isotropic one.  Without
+//   hand-off or tail pool: a handed-off path would have to carry its last pdf.
+//   kHGGrad (GG): the derivative with respect to g as well, from the main path only ("Gradient with respect to g"): the score
+//   hg_score of every sampled direction and the explicit terms of the two MIS weights.  Adjoint: g_acc sums <dL, .> of the terms on each lane
+//   (the kernel adds a wave's sum to Params::L_out once); forward mode: g_S carries the scores sampled so far and every contribution adds
+//   c (g_S + explicit term) t_g (Params::phase_tg) to tg.
+//   kHG2 (H2): the two-lobe mixture (drt_device.h: hg2_eval, hg2_sample) - g1 in Params::phase_g, g2 in Params::phase_tg, the second lobe's
+//   share in Params::phase_w.  The scatter sites keep the next_1d draw the other instantiations drop: it chooses the lobe.
+template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, Phase PH = Phase::kIso>
 struct CoopTracer {
-    static_assert(!GG || HG, "the g-gradient exists for the Henyey-Greenstein phase function only");
-    static_assert(!H2 || (HG && !GG), "the two-lobe kernels are HG kernels without a g-gradient");
+    static constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2;
     const Params &P;
     float maj, inv_maj;
     const uint32_t *mocc;   // SUPER: non-empty supergrid cells (LDS copy) or nullptr

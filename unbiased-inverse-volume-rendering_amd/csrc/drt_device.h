@@ -340,6 +340,15 @@ __device__ __forceinline__ float mis_weight(float a, float b)
     return isfinite(w) ? w : 0.0f;
 }
 
+// The phase function of a volpathsimple launch: a template argument of the tracers (CoopTracer, trace_sq_kernel) and the `phase` argument of their
+// launchers (drt_launch.h).  Its constants travel in Params::phase_g / phase_tg / phase_w.
+enum class Phase : int {
+    kIso,      // isotropic
+    kHG,       // Henyey-Greenstein (drt_set_phase)
+    kHGGrad,   // ... with the derivative with respect to g (adjoint and forward kernels only)
+    kHG2,      // mixture of two Henyey-Greenstein lobes (drt_set_phase_hg2); no g-gradient
+};
+
 // ---------------------------------------------------------------------------
 // kernel parameter block (passed by value in the kernarg segment)
 // ---------------------------------------------------------------------------
@@ -919,6 +928,13 @@ __device__ __forceinline__ void eval4(const Params &P, V3 p, float &sigma_t, flo
     rgb[1] = trilerp8(s, d0.z, d1.z, d2.z, d3.z, d4.z, d5.z, d6.z, d7.z);
     rgb[2] = trilerp8(s, d0.w, d1.w, d2.w, d3.w, d4.w, d5.w, d6.w, d7.w);
 }
+
+// whether this translation unit is one of those compiled with the colour grids on their own lattice (drt_own*.hip)
+#ifdef DRT_COLOUR_OWN
+constexpr bool kColourOwn = true;
+#else
+constexpr bool kColourOwn = false;
+#endif
 
 // the stencil of a lookup into a COLOUR grid: on sigma_t's lattice everywhere but in drt_own.hip (DRT_COLOUR_OWN), where it is the grids' own
 __device__ __forceinline__ Stencil make_stencil_colour(const Params &P, V3 p)

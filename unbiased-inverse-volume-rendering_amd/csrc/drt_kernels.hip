@@ -948,8 +948,55 @@ hipError_t launch_brick_sigma(const float *src, float *dst, int rx, int ry, int 
     return hipGetLastError();
 }
 
-hipError_t launch_nerf(const Params &P, bool adjoint, bool count, hipStream_t stream) { return launch_nerf_t(P, adjoint, count, stream); }
-hipError_t launch_nerf_fwd(const Params &P, hipStream_t stream) { return launch_nerf_fwd_t(P, stream); }
+// ---- the launchers of drt_launch.h whose kernels are spread over several units: each picks the unit that holds the job's kernels -------------
+template struct NerfUnit<false>;                // (this unit's own; drt_own.hip has the other)
+extern template struct NerfUnit<true>;
+hipError_t launch_nerf(const Params &P, bool adjoint, bool count, hipStream_t stream)
+{
+    return P.colour_own ? NerfUnit<true>::trace(P, adjoint, count, stream) : NerfUnit<false>::trace(P, adjoint, count, stream);
+}
+hipError_t launch_nerf_fwd(const Params &P, hipStream_t stream) { return P.colour_own ? NerfUnit<true>::forward(P, stream) : NerfUnit<false>::forward(P, stream); }
+
+namespace {
+// f(CoopUnit<the job's cell>()): the phase as the caller says, the majorant kind and the colour lattice as Params says
+template <Phase PH, typename F> hipError_t coop_cell(const Params &P, F f)
+{
+    if (P.colour_own) return P.mgrid ? f(CoopUnit<PH, true, true>()) : f(CoopUnit<PH, false, true>());
+    return P.mgrid ? f(CoopUnit<PH, true, false>()) : f(CoopUnit<PH, false, false>());
+}
+template <typename F> hipError_t coop_cell(const Params &P, Phase phase, F f)
+{
+    switch (phase) {
+    case Phase::kIso: return coop_cell<Phase::kIso>(P, f);
+    case Phase::kHG: return coop_cell<Phase::kHG>(P, f);
+    case Phase::kHGGrad: return coop_cell<Phase::kHGGrad>(P, f);
+    case Phase::kHG2: return coop_cell<Phase::kHG2>(P, f);
+    }
+    return hipErrorInvalidValue;
+}
+}  // namespace
+
+hipError_t launch_trace_coop(const Params &P, Phase phase, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx,
+                             bool *called)
+{
+    return coop_cell(P, phase, [&](auto unit) { return decltype(unit)::trace(P, adjoint, count, stream, between, between_ctx, called); });
+}
+
+hipError_t launch_trace_coop_fwd(const Params &P, Phase phase, hipStream_t stream)
+{
+    return coop_cell(P, phase, [&](auto unit) { return decltype(unit)::forward(P, stream); });
+}
+
+hipError_t launch_trace_sq(const Params &P, Phase phase, bool adjoint, bool count, int n_cus, hipStream_t stream)
+{
+    switch (phase) {
+    case Phase::kIso: return SqUnit<Phase::kIso>::trace(P, adjoint, count, n_cus, stream);
+    case Phase::kHG: return SqUnit<Phase::kHG>::trace(P, adjoint, count, n_cus, stream);
+    case Phase::kHGGrad: return SqUnit<Phase::kHGGrad>::trace(P, adjoint, count, n_cus, stream);
+    case Phase::kHG2: return SqUnit<Phase::kHG2>::trace(P, adjoint, count, n_cus, stream);
+    }
+    return hipErrorInvalidValue;
+}
 
 hipError_t launch_untile(const Params &P, hipStream_t stream)
 {

@@ -15,10 +15,15 @@ hipError_t launch_occupancy(const float *sigma_t, int rx, int ry, int rz, int sh
                             uint32_t *occ, int words, hipStream_t stream);
 hipError_t launch_brick_sigma(const float *src, float *dst, int rx, int ry, int rz, int nbx, int nby,
                               hipStream_t stream);
+// the nerf march (drt_nerf_kernel.h), and in forward mode with dual numbers (drt_*render_forward: L_out = J t per ray, the tangent grids in
+// Params::g_sigma / g_albedo, read only).  Params::colour_own: the same kernels with the colour grids on their own lattice (drt_own.hip)
 hipError_t launch_nerf(const Params &P, bool adjoint, bool count, hipStream_t stream);
-// drt_own.hip: the same kernels with the colour grids on their own lattice (Params::colour_own)
-hipError_t launch_nerf_own(const Params &P, bool adjoint, bool count, hipStream_t stream);
-hipError_t launch_trace_own(const Params &P, bool adjoint, bool count, hipStream_t stream);
+hipError_t launch_nerf_fwd(const Params &P, hipStream_t stream);
+// ... what a unit contributes to the two (members defined in drt_nerf_kernel.h; each unit instantiates the lattice it is compiled for)
+template <bool OWN> struct NerfUnit {
+    static hipError_t trace(const Params &P, bool adjoint, bool count, hipStream_t stream);
+    static hipError_t forward(const Params &P, hipStream_t stream);
+};
 // drt_nerf_tile.hip: the nerf adjoint for sensor rays - a workgroup per pixel tile, its splats pre-reduced in an LDS window of 16^3 voxels, no records
 // (g4: lookups from Params::grid4 - the fused pass, emission = the medium's albedo grid - instead of sigma_b + Params::emission)
 bool nerf_tile_supported(const Params &P);
@@ -30,11 +35,16 @@ hipError_t launch_trace_wavefront(const Params &P, bool adjoint, bool count, int
 bool super_supported(const Params &P);
 hipError_t launch_trace_super(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
 // the same scenes as work queues inside a compute unit: rays live in LDS records and belong to no lane, waves take batches of
-// one kind of work (drt_sq.hip; round 4).  Uses the ray order and the XCD queues of launch_trace_super; the adjoint needs
-// Params::sq_cold (sq_cold_bytes(n_cus) bytes)
+// one kind of work (drt_sq_kernel.h; round 4).  Uses the ray order and the XCD queues of launch_trace_super; the adjoint needs
+// Params::sq_cold (sq_cold_bytes(n_cus) bytes).  The kernels of a phase are one unit each (SqUnit: drt_sq.hip isotropic, drt_sq_hg.hip kHG and
+// kHGGrad, drt_sq_hg2.hip kHG2).  kHG, kHGGrad, kHG2: no tail launch (Params::tail_pool / tail_mode must be unset).  kHGGrad: adjoint launches
+// only, `count` is ignored (no counting kernels: such a launch counts nothing); dLoss/dg is added to *Params::L_out, one atomic per wave
 bool sq_supported(const Params &P);
 size_t sq_cold_bytes(int n_cus);
-hipError_t launch_trace_sq(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
+hipError_t launch_trace_sq(const Params &P, Phase phase, bool adjoint, bool count, int n_cus, hipStream_t stream);
+template <Phase PH> struct SqUnit {
+    static hipError_t trace(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
+};
 // tail pool of the queued tracer's adjoint launches (Params::tail_pool / tail_count / tail_cap / tail_mode): a drained workgroup writes its last
 // <= sq_tail_push() records to the pool and ends; launch_trace_sq with tail_mode = 1 finishes them (its splats as direct atomics)
 uint32_t sq_tail_push();
@@ -47,51 +57,26 @@ size_t super_order_bytes(uint32_t units);
 hipError_t build_super_order(const Params &P, uint32_t unit, uint32_t units, void *work, hipStream_t stream, const uint8_t *iters = nullptr);
 // flags[u] = 1: every ray of unit u (the `unit` = spp rays of one pixel, sensor rays only) crosses only empty supergrid cells (Params::unit_empty)
 hipError_t build_unit_empty(const Params &P, uint32_t unit, uint32_t units, uint8_t *flags, hipStream_t stream);
-// one ray per lane with own-lane tracking steps through the supergrid (drt_coop_super.hip)
-hipError_t launch_trace_coop_super(const Params &P, bool adjoint, bool count, hipStream_t stream);
-// one ray per lane with wave-cooperative tracking loops (drt_coop.hip); global majorant only (P.mgrid == nullptr)
-// `between` (optional): called on the host after the main launch has been enqueued and before the tail launch (adjoint of the
-// specialised kernels with a tail pool); returns whether it was called through *called
+// One ray per lane (CoopTracer, drt_coop_tracer.h), every phase function and either AD mode.  The kernels are chosen from Params: the global
+// majorant (P.mgrid == nullptr: wave-cooperative tracking loops) or a majorant supergrid (own-lane tracking steps), the colour grids on sigma_t's
+// lattice or their own (P.colour_own).  kHG, kHGGrad, kHG2: no tail pool, no hand-off.  kHGGrad: adjoint launches only (hipErrorInvalidValue
+// otherwise, without Params::L_out or with a tail pool), `count` is ignored (no counting kernels: such a launch counts nothing); dLoss/dg is
+// added to *Params::L_out, one atomic per wave.
+// `between` (optional; isotropic, global majorant, sigma_t's lattice): called on the host after the main launch has been enqueued and before
+// the tail launch (adjoint of the specialised kernels with a tail pool); returns whether it was called through *called
 typedef hipError_t (*coop_between_fn)(void *ctx);
-hipError_t launch_trace_coop(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between = nullptr,
-                             void *between_ctx = nullptr, bool *called = nullptr);
-// Forward mode (drt_*render_forward): L_out = J t per ray, with the tangent grids in Params::g_sigma / g_albedo (read only).  The volpathsimple kernels are
-// CoopTracer<FWD> for every kind of majorant (drt_coop.hip, drt_coop_super.hip; drt_own.hip for colour grids on their own lattice); the nerf
-// kernel marches with dual numbers (drt_nerf_kernel.h)
-hipError_t launch_trace_coop_fwd(const Params &P, hipStream_t stream);
-hipError_t launch_trace_coop_super_fwd(const Params &P, hipStream_t stream);
-hipError_t launch_trace_own_fwd(const Params &P, hipStream_t stream);
-hipError_t launch_nerf_fwd(const Params &P, hipStream_t stream);
-hipError_t launch_nerf_own_fwd(const Params &P, hipStream_t stream);
-// Henyey-Greenstein phase function (drt_set_phase; Params::phase_g): CoopTracer<HG> for every kind of majorant, both AD modes and forward
-// mode (drt_coop_hg.hip, drt_coop_super_hg.hip; drt_own_hg.hip for colour grids on their own lattice).  No tail pool, no hand-off.
-hipError_t launch_trace_coop_hg(const Params &P, bool adjoint, bool count, hipStream_t stream);
-hipError_t launch_trace_coop_super_hg(const Params &P, bool adjoint, bool count, hipStream_t stream);
-hipError_t launch_trace_own_hg(const Params &P, bool adjoint, bool count, hipStream_t stream);
-hipError_t launch_trace_coop_fwd_hg(const Params &P, hipStream_t stream);
-hipError_t launch_trace_coop_super_fwd_hg(const Params &P, hipStream_t stream);
-hipError_t launch_trace_own_fwd_hg(const Params &P, hipStream_t stream);
-// ... and the queued supergrid tracer's (drt_sq_hg.hip): as launch_trace_sq, without tail launch (Params::tail_pool / tail_mode must be unset)
-hipError_t launch_trace_sq_hg(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
-// ... with the derivative with respect to g (the GG instantiations): the adjoint launches add dLoss/dg to *Params::L_out (one atomic per
-// wave), the forward ones add t_g (Params::phase_tg) times dL/dg to J t.  Without counting kernels.
-hipError_t launch_trace_coop_gg(const Params &P, hipStream_t stream);
-hipError_t launch_trace_coop_super_gg(const Params &P, hipStream_t stream);
-hipError_t launch_trace_own_gg(const Params &P, hipStream_t stream);
-hipError_t launch_trace_coop_fwd_gg(const Params &P, hipStream_t stream);
-hipError_t launch_trace_coop_super_fwd_gg(const Params &P, hipStream_t stream);
-hipError_t launch_trace_own_fwd_gg(const Params &P, hipStream_t stream);
-hipError_t launch_trace_sq_gg(const Params &P, int n_cus, hipStream_t stream);
-// Two-lobe Henyey-Greenstein phase function (drt_set_phase_hg2; Params::phase_g = g1, phase_tg = g2, phase_w = the second lobe's share): the
-// H2 instantiations of the HG kernels, one launcher for each of theirs (drt_coop_hg2.hip, drt_coop_super_hg2.hip, drt_own_hg2.hip,
-// drt_sq_hg2.hip).  No g-gradient kernels.
-hipError_t launch_trace_coop_hg2(const Params &P, bool adjoint, bool count, hipStream_t stream);
-hipError_t launch_trace_coop_super_hg2(const Params &P, bool adjoint, bool count, hipStream_t stream);
-hipError_t launch_trace_own_hg2(const Params &P, bool adjoint, bool count, hipStream_t stream);
-hipError_t launch_trace_coop_fwd_hg2(const Params &P, hipStream_t stream);
-hipError_t launch_trace_coop_super_fwd_hg2(const Params &P, hipStream_t stream);
-hipError_t launch_trace_own_fwd_hg2(const Params &P, hipStream_t stream);
-hipError_t launch_trace_sq_hg2(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
+hipError_t launch_trace_coop(const Params &P, Phase phase, bool adjoint, bool count, hipStream_t stream,
+                             coop_between_fn between = nullptr, void *between_ctx = nullptr, bool *called = nullptr);
+// Forward mode (drt_*render_forward): L_out = J t per ray, with the tangent grids in Params::g_sigma / g_albedo (read only) - CoopTracer<FWD>,
+// chosen from Params likewise.  kHGGrad: J t includes t_g (Params::phase_tg) times dL/dg
+hipError_t launch_trace_coop_fwd(const Params &P, Phase phase, hipStream_t stream);
+// ... what a unit contributes to the two: the kernels of one cell (phase, majorant kind, lattice).  Members defined in drt_coop_kernel.h; the
+// drt_coop*.hip (global majorant), drt_coop_super*.hip (supergrid) and drt_own*.hip (own lattice, both kinds) units instantiate their cells,
+// the plain units kIso, the _hg units kHG and kHGGrad, the _hg2 units kHG2
+template <Phase PH, bool SUPER, bool OWN> struct CoopUnit {
+    static hipError_t trace(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx, bool *called);
+    static hipError_t forward(const Params &P, hipStream_t stream);
+};
 hipError_t launch_ray_perm(const uint8_t *iters, uint64_t n_rays, uint16_t *perm, uint32_t *block_cost, hipStream_t stream);
 hipError_t launch_block_order(const uint32_t *cost, uint32_t n_blocks, uint32_t *order, bool heavy_first, hipStream_t stream);
 hipError_t launch_untile(const Params &P, hipStream_t stream);

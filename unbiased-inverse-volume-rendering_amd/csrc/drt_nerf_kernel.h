@@ -206,16 +206,21 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P)
     P.L_out[3 * i] = dres[0]; P.L_out[3 * i + 1] = dres[1]; P.L_out[3 * i + 2] = dres[2];
 }
 
-hipError_t launch_nerf_fwd_t(const Params &P, hipStream_t stream)
+}  // namespace
+
+// this unit's half of launch_nerf / launch_nerf_fwd (drt_launch.h: NerfUnit; instantiated by drt_kernels.hip and drt_own.hip)
+template <bool OWN> hipError_t NerfUnit<OWN>::forward(const Params &P, hipStream_t stream)
 {
+    static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
     if (P.n_rays <= P.ray_first) return hipSuccess;
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
     hipLaunchKernelGGL(nerf_fwd_kernel, grid, block, 0, stream, P);
     return hipGetLastError();
 }
 
-hipError_t launch_nerf_t(const Params &P, bool adjoint, bool count, hipStream_t stream)
+template <bool OWN> hipError_t NerfUnit<OWN>::trace(const Params &P, bool adjoint, bool count, hipStream_t stream)
 {
+    static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
     if (P.n_rays <= P.ray_first) return hipSuccess;
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
     const bool defer = adjoint && P.rec_buf[0] != nullptr;
@@ -232,5 +237,4 @@ hipError_t launch_nerf_t(const Params &P, bool adjoint, bool count, hipStream_t 
     return hipGetLastError();
 }
 
-}  // namespace
 }  // namespace drt

@@ -2,7 +2,7 @@
 // (drt_set_colour_resolution): Mitsuba interpolates every GridVolume on its own resolution, and the reference's janga-smoke pairs a
 // 264 x 136 x 136 density with 256 x 128 x 128 albedo / emission grids (python/scene_config.py:108-110).
 //
-// The ONE translation unit compiled with DRT_COLOUR_OWN: eval_rgb builds its stencil from Params::crx / cry / crz and the colour gradient
+// Compiled with DRT_COLOUR_OWN (as its _hg and _hg2 flavours): eval_rgb builds its stencil from Params::crx / cry / crz and the colour gradient
 // splats go to the caller's grid as fp32 atomics on that lattice (drt_device.h: make_stencil_colour, splat_colour_own), because the tile
 // partition, the LDS reduction tiles and the apron scratch are laid out on sigma_t's lattice.  Everything else - the wave-cooperative tracer
 // with a global majorant, its own-lane walk through a majorant supergrid, path cache, sigma_t record streams, every estimator, both emitters,
@@ -14,20 +14,8 @@
 
 namespace drt {
 
-hipError_t launch_trace_own(const Params &P, bool adjoint, bool count, hipStream_t stream)
-{
-    if (P.mgrid) return launch_trace_coop_t<true>(P, adjoint, count, stream);
-    return launch_trace_coop_t<false>(P, adjoint, count, stream);
-}
-
-hipError_t launch_nerf_own(const Params &P, bool adjoint, bool count, hipStream_t stream) { return launch_nerf_t(P, adjoint, count, stream); }
-
-hipError_t launch_trace_own_fwd(const Params &P, hipStream_t stream)
-{
-    if (P.mgrid) return launch_trace_coop_fwd_t<true>(P, stream);
-    return launch_trace_coop_fwd_t<false>(P, stream);
-}
-
-hipError_t launch_nerf_own_fwd(const Params &P, hipStream_t stream) { return launch_nerf_fwd_t(P, stream); }
+template struct CoopUnit<Phase::kIso, false, true>;
+template struct CoopUnit<Phase::kIso, true, true>;
+template struct NerfUnit<true>;
 
 }  // namespace drt

@@ -1,32 +1,13 @@
 // drt_own_hg.hip -- the Henyey-Greenstein instantiations of drt_own.hip: colour grids on their own lattice (drt_set_colour_resolution)
-// and the phase function `hg` (drt_set_phase), either kind of majorant.  Compiled with DRT_COLOUR_OWN like drt_own.hip.
+// and the phase function `hg` (drt_set_phase), with (kHGGrad) and without the derivative with respect to g, either kind of majorant.  Compiled with DRT_COLOUR_OWN like drt_own.hip.
 #define DRT_COLOUR_OWN 1
 #include "drt_coop_kernel.h"
 
 namespace drt {
 
-hipError_t launch_trace_own_hg(const Params &P, bool adjoint, bool count, hipStream_t stream)
-{
-    if (P.mgrid) return launch_trace_coop_t<true, true>(P, adjoint, count, stream);
-    return launch_trace_coop_t<false, true>(P, adjoint, count, stream);
-}
-
-hipError_t launch_trace_own_fwd_hg(const Params &P, hipStream_t stream)
-{
-    if (P.mgrid) return launch_trace_coop_fwd_t<true, true>(P, stream);
-    return launch_trace_coop_fwd_t<false, true>(P, stream);
-}
-
-hipError_t launch_trace_own_gg(const Params &P, hipStream_t stream)
-{
-    if (P.mgrid) return launch_trace_coop_gg_t<true>(P, stream);
-    return launch_trace_coop_gg_t<false>(P, stream);
-}
-
-hipError_t launch_trace_own_fwd_gg(const Params &P, hipStream_t stream)
-{
-    if (P.mgrid) return launch_trace_coop_fwd_t<true, true, true>(P, stream);
-    return launch_trace_coop_fwd_t<false, true, true>(P, stream);
-}
+template struct CoopUnit<Phase::kHG, false, true>;
+template struct CoopUnit<Phase::kHG, true, true>;
+template struct CoopUnit<Phase::kHGGrad, false, true>;
+template struct CoopUnit<Phase::kHGGrad, true, true>;
 
 }  // namespace drt

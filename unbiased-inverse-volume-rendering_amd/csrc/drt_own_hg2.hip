@@ -6,16 +6,7 @@
 
 namespace drt {
 
-hipError_t launch_trace_own_hg2(const Params &P, bool adjoint, bool count, hipStream_t stream)
-{
-    if (P.mgrid) return launch_trace_coop_t<true, true, true>(P, adjoint, count, stream);
-    return launch_trace_coop_t<false, true, true>(P, adjoint, count, stream);
-}
-
-hipError_t launch_trace_own_fwd_hg2(const Params &P, hipStream_t stream)
-{
-    if (P.mgrid) return launch_trace_coop_fwd_t<true, true, false, true>(P, stream);
-    return launch_trace_coop_fwd_t<false, true, false, true>(P, stream);
-}
+template struct CoopUnit<Phase::kHG2, false, true>;
+template struct CoopUnit<Phase::kHG2, true, true>;
 
 }  // namespace drt

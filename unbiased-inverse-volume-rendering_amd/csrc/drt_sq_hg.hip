@@ -1,5 +1,11 @@
-// drt_sq_hg.hip -- the Henyey-Greenstein instantiations of the queued supergrid tracer (trace_sq_kernel<HG>, drt_sq.hip): scenes with a majorant
-// supergrid whose phase function is `hg` (drt_set_phase).  A unit of its own, so that the isotropic kernels of drt_sq.hip compile exactly as
-// before and the two units build side by side; it holds the kernels and launch_trace_sq_hg only (DRT_SQ_HG_UNIT).
-#define DRT_SQ_HG_UNIT 1
-#include "drt_sq.hip"
+// drt_sq_hg.hip -- the Henyey-Greenstein instantiations of the queued supergrid tracer (drt_sq_kernel.h), with (kHGGrad) and without the derivative
+// with respect to g: a handle whose phase function is `hg` (drt_set_phase).  Their own translation unit: the isotropic kernels of drt_sq.hip
+// compile exactly as before and the two units build side by side.
+#include "drt_sq_kernel.h"
+
+namespace drt {
+
+template struct SqUnit<Phase::kHG>;
+template struct SqUnit<Phase::kHGGrad>;
+
+}  // namespace drt
