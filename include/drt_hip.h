@@ -223,6 +223,34 @@ int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const floa
                             const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
                             const float *t_sigma_t, const float *t_emission, float *dL_out);
 
+/* The nerf integrator with SPHERICAL-HARMONIC (view-dependent) emission, degree sh_degree in {1, 2}, K = (sh_degree + 1)^2:
+ *     e_c(x, d) = sum_{k<K} Y_k(d) sh[x][k][c],   d = the unit world-space ray direction of the march,
+ * `sh` (Z,Y,X,3K) on sigma_t's lattice with channel index 3k + c, every channel interpolated as the plain emission grid is (no clamp, no
+ * activation: the radiance is linear in sh).  Basis (the svox2 / Plenoxels order): Y_0 = 0.28209479177387814, Y_1 = -0.4886025119029199 y,
+ * Y_2 = 0.4886025119029199 z, Y_3 = -0.4886025119029199 x, Y_4 = 1.0925484305920792 xy, Y_5 = -1.0925484305920792 yz,
+ * Y_6 = 0.31539156525252005 (2zz - xx - yy), Y_7 = -1.0925484305920792 xz, Y_8 = 0.5462742152960396 (xx - yy).
+ * The four calls mirror drt_nerf_render_primal / _backward / _backward_px / _forward: same ray, seed, offset and interleave conventions,
+ * the backward calls accumulate (+=) into grad_sigma_t (Z,Y,X,1) and grad_sh (Z,Y,X,3K), the forward call takes tangents of those shapes
+ * (NULL = zero), writes dL_out once per ray without atomics and repeats bit for bit.  Sensor rays take the LDS-window adjoint kernel
+ * (csrc/drt_nerf_sh.hip); explicit ray batches a one-ray-per-lane kernel with float atomics (untuned).  Refused: sh_degree outside {1, 2}
+ * and a NULL sh (DRT_ERR_INVALID_ARGUMENT); colour grids on their own lattice (drt_set_colour_resolution) and - adjoint calls - debug flags
+ * that route the plain nerf adjoint elsewhere (1, 2, 128, 512), which the SH kernels do not honour (DRT_ERR_UNSUPPORTED).  The counters of
+ * drt_get_counters do not count these calls. */
+int drt_nerf_render_primal_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                              const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out);
+int drt_nerf_render_backward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                                const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL,
+                                const float *L_in, float *grad_sigma_t, float *grad_sh);
+int drt_nerf_render_backward_px_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                                   const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                   const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t, float *grad_sh);
+int drt_nerf_render_forward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                               const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                               const float *t_sigma_t, const float *t_sh, float *dL_out);
+/* With counting enabled (drt_enable_counters): the window phases (flush + move) summed over the workgroups of the last SH adjoint launch
+ * of sensor rays.  Synchronises the handle's stream. */
+int drt_nerf_sh_tile_stats(drt_handle h, uint64_t *window_phases);
+
 /* BASELINE config 5: the `nerf` march and volpathsimple scattering over ONE set of grids [sigma_t, r, g, b] in one call.
  * The reference's scenes bind ONE asset as the medium's albedo and emission grid (python/scene_config.py:109-110), so the
  * colour grid given to drt_set_medium as `albedo` is both.  Per ray, the pass computes NeRFIntegrator.sample (nerf.py:47-148;

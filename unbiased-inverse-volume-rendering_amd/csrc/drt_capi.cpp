@@ -114,6 +114,7 @@ struct drt_handle_s {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     DevBuf loss_partials;                // per-workgroup sums (doubles) of drt_film_loss_forward
     DevBuf dl_px;                        // per-ray dL (floats) for the queued tracer, expanded from Params::dL_pix (drt_render_backward_px)
+    DevBuf sh_vox;                     // interleaved [sigma_t, sh] voxel copy of the drt_nerf_*_sh calls (drt_nerf_sh.hip), made per call
     DevBuf nerf_bounds;                // 32 bytes: max |dL|, |L_in|, |emission|, non-finite flag, largest negative density of a nerf tile adjoint launch (drt_nerf_tile.hip)
     // path cache (drt_coop.hip): written by the primal launch of an H1 step, read by the adjoint launch of the
     // same job if nothing happened to the handle in between
@@ -1995,4 +1996,132 @@ int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const 
     DRT_TRY(check_px(h, "drt_nerf_render_backward_px", n_rays, spp, grad_image, n_pixels));
     return nerf_render_backward(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t,
                                 grad_emission);
+}
+
+// ---- nerf with spherical-harmonic emission (drt_nerf_sh.hip) -------------------------------------------------------------------------------
+// the checks the four *_sh calls share, the job and the interleaved voxel copy of this call's grids.  The test hooks that route the plain nerf
+// adjoint elsewhere (record path, atomic gradients into the apron scratch, per-lane / no gradient atomics) have no SH kernels: refused
+static int nerf_sh_job(drt_handle h, const char *what, drt::Params &P, drt::NerfSh &S, const drt_nerf_config *cfg, const float *sh,
+                       int32_t sh_degree, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                       uint32_t seed, bool adjoint)
+{
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
+    if (sh_degree != 1 && sh_degree != 2)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: sh_degree must be 1 or 2, got %d", what, (int) sh_degree);
+    if (!cfg || !sh) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null config / sh grid", what);
+    if (h->base.colour_own)
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the sh grid must share sigma_t's lattice (drt_set_colour_resolution gave the colour grids "
+                                            "their own: own-lattice SH is not supported)", what);
+    constexpr uint32_t kUnhonoured = drt::kHookNerfRecordPath | drt::kHookAtomicGradients | drt::kHookNoGradAtomics | drt::kHookPerLaneAtomics;
+    if (adjoint && dbg(h->debug_flags, kUnhonoured))
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: debug flags 0x%x route the nerf adjoint through paths the SH kernels do not have", what,
+                    (unsigned) (h->debug_flags & kUnhonoured));
+    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    DRT_TRY(nerf_fill(h, P, cfg, sh));
+    S.K = (sh_degree + 1) * (sh_degree + 1);
+    S.vox = nullptr;
+    if (n_rays == 0) return DRT_OK;
+    const size_t nv = (size_t) P.rx * P.ry * P.rz;
+    if (nv > 0x7fffffffull) return fail(h, DRT_ERR_UNSUPPORTED, "%s: grid too large for the interleaved voxel copy", what);
+    DRT_TRY(h->sh_vox.grow(h, nv * drt::sh_vox_floats(S.K) * sizeof(float), kMust));
+    DRT_HIP_CHECK(h, drt::launch_sh_interleave(P.sigma_t, sh, S.K, h->sh_vox.as<float4>(), nv, h->stream));
+    S.vox = h->sh_vox.as<float4>();
+    return DRT_OK;
+}
+
+int drt_nerf_render_primal_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                              const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
+    DeviceGuard g(h->device);
+    drt::Params P; drt::NerfSh S;
+    DRT_TRY(nerf_sh_job(h, "drt_nerf_render_primal_sh", P, S, cfg, sh, sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, false));
+    if (n_rays == 0) return DRT_OK;
+    if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_primal_sh: null L_out");
+    P.L_out = L_out;
+    h->pcache_sig.valid = false;
+    TimedSpan span;
+    DRT_HIP_CHECK(h, span.begin(h, h->stream));
+    DRT_HIP_CHECK(h, drt::launch_nerf_sh(P, S, false, h->stream));
+    DRT_HIP_CHECK(h, span.end(0));
+    return DRT_OK;
+}
+
+// the SH adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given.  Sensor rays: the LDS-window kernel;
+// explicit ray batches: one ray per lane with fp32 atomics on the caller's grids (the untuned route)
+static int nerf_sh_backward(drt_handle h, drt::Params &P, const drt::NerfSh &S, const float *dL, const float *dL_pix, const float *L_in,
+                            float *grad_sigma_t, float *grad_sh)
+{
+    P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_sh;
+    TimedSpan tracer, whole;
+    DRT_HIP_CHECK(h, tracer.begin(h, h->stream));
+    DRT_HIP_CHECK(h, whole.begin(h, h->stream));
+    if (drt::nerf_tile_supported(P)) {
+        DRT_TRY(h->nerf_bounds.grow(h, 32, kMust));
+        DRT_HIP_CHECK(h, drt::launch_nerf_sh_tile_adjoint(P, S, h->nerf_bounds.as<uint32_t>(), h->stream));
+    } else DRT_HIP_CHECK(h, drt::launch_nerf_sh(P, S, true, h->stream));
+    DRT_HIP_CHECK(h, tracer.end(1));
+    DRT_HIP_CHECK(h, whole.end(3));
+    return DRT_OK;
+}
+
+int drt_nerf_render_backward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                                const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL,
+                                const float *L_in, float *grad_sigma_t, float *grad_sh)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
+    DeviceGuard g(h->device);
+    drt::Params P; drt::NerfSh S;
+    DRT_TRY(nerf_sh_job(h, "drt_nerf_render_backward_sh", P, S, cfg, sh, sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, true));
+    if (n_rays == 0) return DRT_OK;
+    if (!dL || !L_in || !grad_sigma_t || !grad_sh)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_sh: null dL / L_in / gradient buffer");
+    return nerf_sh_backward(h, P, S, dL, nullptr, L_in, grad_sigma_t, grad_sh);
+}
+
+int drt_nerf_render_backward_px_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                                   const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                   const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t, float *grad_sh)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
+    DeviceGuard g(h->device);
+    drt::Params P; drt::NerfSh S;
+    DRT_TRY(nerf_sh_job(h, "drt_nerf_render_backward_px_sh", P, S, cfg, sh, sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, true));
+    if (!L_in || !grad_sigma_t || !grad_sh)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px_sh: null L_in / gradient buffer");
+    DRT_TRY(check_px(h, "drt_nerf_render_backward_px_sh", n_rays, spp, grad_image, n_pixels));
+    if (n_rays == 0) return DRT_OK;
+    return nerf_sh_backward(h, P, S, nullptr, grad_image, L_in, grad_sigma_t, grad_sh);
+}
+
+int drt_nerf_render_forward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                               const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                               const float *t_sigma_t, const float *t_sh, float *dL_out)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
+    DeviceGuard g(h->device);
+    drt::Params P; drt::NerfSh S;
+    DRT_TRY(nerf_sh_job(h, "drt_nerf_render_forward_sh", P, S, cfg, sh, sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, false));
+    if (n_rays == 0) return DRT_OK;
+    if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward_sh: null dL_out");
+    forward_params(P, t_sigma_t, t_sh, dL_out);
+    DRT_HIP_CHECK(h, drt::launch_nerf_sh_fwd(P, S, h->stream));
+    return DRT_OK;
+}
+
+int drt_nerf_sh_tile_stats(drt_handle h, uint64_t *window_phases)
+{
+    if (!h || !window_phases) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_sh_tile_stats: null argument");
+    *window_phases = 0;
+    if (!h->nerf_bounds.p) return DRT_OK;                          // (no tile launch yet)
+    DeviceGuard g(h->device);
+    DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    uint32_t v = 0;
+    DRT_HIP_CHECK(h, hipMemcpy(&v, h->nerf_bounds.as<uint32_t>() + 5, sizeof v, hipMemcpyDeviceToHost));
+    *window_phases = v;
+    return DRT_OK;
 }

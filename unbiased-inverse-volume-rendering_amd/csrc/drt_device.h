@@ -991,6 +991,27 @@ __device__ __forceinline__ void stencil_indices(const Stencil &s, int idx[8])
     idx[4] = c + s.x0; idx[5] = c + s.x1; idx[6] = d + s.x0; idx[7] = d + s.x1;
 }
 
+// Real spherical-harmonic basis of degree D in {1, 2} at the unit direction d, K = (D + 1)^2 values in the svox2 / Plenoxels order and sign
+// convention (drt_nerf_sh.hip: view-dependent emission e_c = sum_k Y_k(d) sh[k][c]).  fp32, one written-down operation order - the host
+// mirror (integrators.sh_basis) performs the same products in the same order, so the two agree bit for bit (-ffp-contract=off).
+template <int K>
+__host__ __device__ __forceinline__ void sh_basis(float x, float y, float z, float Y[K])
+{
+    static_assert(K == 4 || K == 9, "degree 1 or 2");
+    Y[0] = 0.28209479177387814f;
+    Y[1] = -0.4886025119029199f * y;
+    Y[2] = 0.4886025119029199f * z;
+    Y[3] = -0.4886025119029199f * x;
+    if constexpr (K == 9) {
+        const float xx = x * x, yy = y * y, zz = z * z;
+        Y[4] = 1.0925484305920792f * (x * y);
+        Y[5] = -1.0925484305920792f * (y * z);
+        Y[6] = 0.31539156525252005f * ((2.0f * zz - xx) - yy);
+        Y[7] = -1.0925484305920792f * (x * z);
+        Y[8] = 0.5462742152960396f * (xx - yy);
+    }
+}
+
 // Cooperative scatter.  Measured on MI355X (tools/ubench/atomic_*.hip): the fp32
 // atomic path retires ~21 G requests/s chip-wide, where one request = one 64-byte
 // line touched by one wave instruction, whatever the number of lanes that hit it

@@ -29,6 +29,20 @@ template <bool OWN> struct NerfUnit {
 bool nerf_tile_supported(const Params &P);
 // bounds: 32 bytes of device scratch (the fixed-point units of the LDS window follow from max |dL|, max |L_in|, max |emission|, reduced there first)
 hipError_t launch_nerf_tile_adjoint(const Params &P, bool g4, bool count, uint32_t *bounds, hipStream_t stream);
+// drt_nerf_sh.hip: the nerf march with spherical-harmonic (view-dependent) emission, K = (degree + 1)^2 in {4, 9} coefficients per voxel and
+// colour channel.  The caller's sh grid (Z,Y,X,3K) travels in Params::emission, its gradient / tangent grid in Params::g_albedo; lookups
+// come from `vox`, an interleaved copy [sigma_t, sh[0..3K-1], 0..] of sh_vox_floats(K) floats per voxel made by launch_sh_interleave
+struct NerfSh {
+    const float4 *vox;
+    int K;
+};
+size_t sh_vox_floats(int K);
+hipError_t launch_sh_interleave(const float *sigma_t, const float *sh, int K, float4 *vox, size_t n_voxels, hipStream_t stream);
+// one ray per lane: the primal, the adjoint (float atomics on the caller's grids: explicit ray batches - the untuned route) and forward mode
+hipError_t launch_nerf_sh(const Params &P, const NerfSh &S, bool adjoint, hipStream_t stream);
+hipError_t launch_nerf_sh_fwd(const Params &P, const NerfSh &S, hipStream_t stream);
+// the adjoint of sensor rays: drt_nerf_tile.hip's LDS window with 1 + 3K planes (same support predicate: nerf_tile_supported)
+hipError_t launch_nerf_sh_tile_adjoint(const Params &P, const NerfSh &S, uint32_t *bounds, hipStream_t stream);
 hipError_t launch_trace_wavefront(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
 // supergrid scenes (majorant_resolution_factor > 0): lane-level state machine stepping one supergrid cell at a time, the
 // majorant grid in LDS (drt_super.hip); the adjoint needs the record streams (deferred splatting)

@@ -326,6 +326,63 @@ public:
         }
         check(rc, "drt_nerf_render_backward_px");
     }
+    // spherical-harmonic emission (drt_nerf_*_sh): props["sh_degree"] in {1, 2}
+    static int32_t sh_degree(const py::dict &p) { return p.contains("sh_degree") ? py::cast<int>(p["sh_degree"]) : 0; }
+    void nerf_render_primal_sh(const py::dict &props, uintptr_t sh, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                               uint32_t spp, uint32_t seed, uintptr_t L_out)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        const int32_t deg = sh_degree(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_primal_sh(h_, &c, ptr<const float>(sh), deg, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
+                                           spp, seed, ptr<float>(L_out));
+        }
+        check(rc, "drt_nerf_render_primal_sh");
+    }
+    void nerf_render_backward_sh(const py::dict &props, uintptr_t sh, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                 uint32_t spp, uint32_t seed, uintptr_t dL, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_sh)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        const int32_t deg = sh_degree(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_backward_sh(h_, &c, ptr<const float>(sh), deg, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
+                                             spp, seed, ptr<const float>(dL), ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_sh));
+        }
+        check(rc, "drt_nerf_render_backward_sh");
+    }
+    void nerf_render_backward_px_sh(const py::dict &props, uintptr_t sh, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                    uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
+                                    uintptr_t g_sh)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        const int32_t deg = sh_degree(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_backward_px_sh(h_, &c, ptr<const float>(sh), deg, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
+                                                spp, seed, ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in),
+                                                ptr<float>(g_sigma), ptr<float>(g_sh));
+        }
+        check(rc, "drt_nerf_render_backward_px_sh");
+    }
+    void nerf_render_forward_sh(const py::dict &props, uintptr_t sh, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_sh, uintptr_t dL_out)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        const int32_t deg = sh_degree(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_forward_sh(h_, &c, ptr<const float>(sh), deg, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
+                                            spp, seed, ptr<const float>(t_sigma), ptr<const float>(t_sh), ptr<float>(dL_out));
+        }
+        check(rc, "drt_nerf_render_forward_sh");
+    }
+    uint64_t nerf_sh_tile_phases() { uint64_t v = 0; check(drt_nerf_sh_tile_stats(h_, &v), "drt_nerf_sh_tile_stats"); return v; }
     void debug_eval(int op, uintptr_t in, uint64_t n, uintptr_t out)
     {
         int rc;
@@ -445,6 +502,11 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("film_loss_grad", &Integrator::film_loss_grad)
         .def("render_backward_px", &Integrator::render_backward_px)
         .def("nerf_render_backward_px", &Integrator::nerf_render_backward_px)
+        .def("nerf_render_primal_sh", &Integrator::nerf_render_primal_sh)
+        .def("nerf_render_backward_sh", &Integrator::nerf_render_backward_sh)
+        .def("nerf_render_backward_px_sh", &Integrator::nerf_render_backward_px_sh)
+        .def("nerf_render_forward_sh", &Integrator::nerf_render_forward_sh)
+        .def("nerf_sh_tile_phases", &Integrator::nerf_sh_tile_phases)
         .def("debug_eval", &Integrator::debug_eval)
         .def("set_debug_flags", &Integrator::set_debug_flags)
         .def("enable_counters", &Integrator::enable_counters)

@@ -17,6 +17,7 @@ from dataclasses import dataclass
 from enum import IntEnum
 from typing import Callable, Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from ._native import native
@@ -459,9 +460,62 @@ def _check(t: torch.Tensor, shape, dev, name: str):
         raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
 
 
+# Real spherical-harmonic basis constants (the svox2 / Plenoxels order and signs): the host mirror of sh_basis<K> in csrc/drt_device.h
+_SH_C0 = 0.28209479177387814
+_SH_C1 = 0.4886025119029199
+_SH_C2 = 1.0925484305920792
+_SH_C3 = 0.31539156525252005
+_SH_C4 = 0.5462742152960396
+
+
+def _sh_degree(degree) -> int:
+    if isinstance(degree, bool) or int(degree) != degree or int(degree) not in (1, 2):
+        raise ValueError(f"sh degree must be 1 or 2, got {degree!r}")
+    return int(degree)
+
+
+def sh_basis(d, degree: int):
+    """Y_k(d), k < (degree + 1)^2, for unit directions d [..., 3] -> [..., K]: the device basis (csrc/drt_device.h, sh_basis) with the
+    same constants, the same order and - for float32 input - the same float32 operations in the same order.  torch in, torch out;
+    numpy in, numpy out."""
+    degree = _sh_degree(degree)
+    is_np = isinstance(d, np.ndarray)
+    xp = np if is_np else torch
+    if d.shape[-1] != 3:
+        raise ValueError(f"directions must have shape (..., 3), got {tuple(d.shape)}")
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    c = (lambda v: np.asarray(v, dtype=d.dtype)) if is_np else (lambda v: torch.tensor(v, dtype=d.dtype, device=d.device))
+    Y = [c(_SH_C0) + 0 * x, c(-_SH_C1) * y, c(_SH_C1) * z, c(-_SH_C1) * x]
+    if degree == 2:
+        xx, yy, zz = x * x, y * y, z * z
+        Y += [c(_SH_C2) * (x * y), c(-_SH_C2) * (y * z), c(_SH_C3) * ((c(2.0) * zz - xx) - yy), c(-_SH_C2) * (x * z),
+              c(_SH_C4) * (xx - yy)]
+    return xp.stack(Y, -1)
+
+
+def sh_from_rgb(emission, degree: int):
+    """A plain emission grid (Z,Y,X,3) as an sh grid (Z,Y,X,3K) that renders the same from every direction: emission / Y_0 in k = 0,
+    zeros elsewhere.  A starting point for an optimisation with `sh_degree` > 0."""
+    degree = _sh_degree(degree)
+    if emission.ndim != 4 or emission.shape[-1] != 3:
+        raise ValueError(f"emission must have shape (Z,Y,X,3), got {tuple(emission.shape)}")
+    K = (degree + 1) ** 2
+    if isinstance(emission, np.ndarray):
+        out = np.zeros(emission.shape[:3] + (3 * K,), dtype=emission.dtype)
+    else:
+        out = torch.zeros(tuple(emission.shape[:3]) + (3 * K,), dtype=emission.dtype, device=emission.device)
+    out[..., :3] = emission / _SH_C0
+    return out
+
+
 class NeRFIntegrator(_DeviceIntegrator):
     """Simplified NeRF-style integrator: emission accumulated along the ray, no scattering
-    (python/integrators/nerf.py:20-35).  Reads `medium.sigma_t` and `medium.emission`."""
+    (python/integrators/nerf.py:20-35).  Reads `medium.sigma_t` and `medium.emission`.
+
+    `sh_degree` (default 0: the reference's direction-independent emission) in {1, 2}: view-dependent emission
+    e_c(x, d) = sum_k Y_k(d) sh[x][k][c] with K = (sh_degree + 1)^2 spherical-harmonic coefficients per voxel and channel
+    (`sh_basis`); `medium.emission`, its gradients and tangents are then (Z,Y,X,3K), channel index 3k + c, on sigma_t's lattice
+    (csrc/drt_nerf_sh.hip)."""
 
     param_keys = (SIGMA_T_KEY, EMISSION_KEY)
     needs_albedo = False
@@ -478,6 +532,7 @@ class NeRFIntegrator(_DeviceIntegrator):
         self.jittering_enabled = bool(props.get("jittering_enabled", True))
         self.activation_type = str(props.get("activation", "identity")).lower()
         self.test_hooks = bool(props.get("test_hooks", False))
+        self.sh_degree = props.get("sh_degree", 0)
         self.max_depth = int(props.get("max_depth", 6))          # RBIntegrator base; unused (nerf.py)
         self.rr_depth = int(props.get("rr_depth", 5))
         if self.activation_type not in ("identity", "relu"):
@@ -495,17 +550,41 @@ class NeRFIntegrator(_DeviceIntegrator):
     def aovs(self):
         return []
 
+    @property
+    def sh_degree(self) -> int:
+        return self._sh_degree
+
+    @sh_degree.setter
+    def sh_degree(self, degree):
+        if isinstance(degree, bool) or int(degree) != degree or int(degree) not in (0, 1, 2):
+            raise ValueError(f"sh_degree must be 0 (direction-independent emission), 1 or 2, got {degree!r}")
+        self._sh_degree = int(degree)
+
     def props(self) -> dict:
         return dict(hide_emitters=self.hide_emitters, queries_per_ray=self.queries_per_ray,
                     jittering_enabled=self.jittering_enabled, activation=self.activation_type,
-                    density_noise_std=self.density_noise_std)
+                    density_noise_std=self.density_noise_std, sh_degree=self.sh_degree)
 
     def _native_props(self) -> dict:
         return dict(max_depth=0)
 
     def _nerf_props(self) -> dict:
-        return dict(hide_emitters=self.hide_emitters, queries_per_ray=self.queries_per_ray,
-                    jittering_enabled=self.jittering_enabled, activation_relu=self.activation_type == "relu")
+        p = dict(hide_emitters=self.hide_emitters, queries_per_ray=self.queries_per_ray,
+                 jittering_enabled=self.jittering_enabled, activation_relu=self.activation_type == "relu")
+        if self.sh_degree:
+            p["sh_degree"] = self.sh_degree
+        return p
+
+    def _check_sh(self, scene: Scene):
+        """sh_degree > 0: the emission grid's shape, checked on the host before any handle exists."""
+        em, st = scene.medium.emission, scene.medium.sigma_t
+        K = (self.sh_degree + 1) ** 2
+        if em is None or getattr(em, "ndim", 0) != 4 or em.shape[-1] != 3 * K:
+            raise ValueError(f"sh_degree {self.sh_degree} needs medium.emission of shape (Z,Y,X,{3 * K}) - {K} spherical-harmonic "
+                             f"coefficients per colour channel -, got {None if em is None else tuple(em.shape)}")
+        if tuple(em.shape[:3]) != tuple(st.shape[:3]):
+            raise NotImplementedError(f"sh_degree {self.sh_degree}: the sh grid {tuple(em.shape[:3])} must share sigma_t's lattice "
+                                      f"{tuple(st.shape[:3])} (a colour grid on its own lattice is not supported with spherical harmonics)")
 
     def sample(self, mode, scene: Scene, sampler: IndependentSampler, ray: RayBatch,
                δL: Optional[torch.Tensor] = None, state_in: Optional[torch.Tensor] = None,
@@ -519,15 +598,19 @@ class NeRFIntegrator(_DeviceIntegrator):
             tangents = self.check_tangents(scene, tangents)
         if grads is not None and grads.get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)
+        if self.sh_degree:
+            self._check_sh(scene)
         h, dev = self._bind(scene)
         em = scene.medium.emission
         if not isinstance(em, torch.Tensor):
             raise TypeError("the nerf integrator needs medium.emission as a torch device tensor")
         _check(em, None, dev, "emission")
-        if em.dim() != 4 or em.shape[-1] != 3:
+        if not self.sh_degree and (em.dim() != 4 or em.shape[-1] != 3):
             raise ValueError(f"emission must have shape (Z,Y,X,3), got {tuple(em.shape)}")
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)
+        if self.sh_degree:
+            return self._sample_sh(mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents)
         if mode == ADMode.Primal:
             L = torch.empty((n, 3), dtype=torch.float32, device=dev)
             h.nerf_render_primal(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp),
@@ -549,12 +632,37 @@ class NeRFIntegrator(_DeviceIntegrator):
                               _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
         return dL, True, None
 
+    def _sample_sh(self, mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents):
+        """sample() with sh_degree > 0: the drt_nerf_render_*_sh calls (the checks of sample() are done)."""
+        props, off, spp, seed = self._nerf_props(), int(ray.ray_offset), int(ray.spp), sampler.seed_value
+        if mode == ADMode.Primal:
+            L = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            h.nerf_render_primal_sh(props, em.data_ptr(), ro, rd, n, off, spp, seed, L.data_ptr())
+            return L, True, L
+        if mode == ADMode.Backward:
+            if δL is None or state_in is None or grads is None:
+                raise ValueError("sample(Backward) needs δL, state_in and grads")
+            _check(δL, (n, 3), dev, "δL")
+            _check(state_in, (n, 3), dev, "state_in")
+            gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
+            _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
+            _check(ge, tuple(em.shape), dev, "grads[emission]")
+            h.nerf_render_backward_sh(props, em.data_ptr(), ro, rd, n, off, spp, seed, δL.data_ptr(), state_in.data_ptr(),
+                                      gs.data_ptr(), ge.data_ptr())
+            return None, True, None
+        dL = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        h.nerf_render_forward_sh(props, em.data_ptr(), ro, rd, n, off, spp, seed, _ptr(tangents[SIGMA_T_KEY]),
+                                 _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
+        return dL, True, None
+
     def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
         """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] in place of the per-ray δL
         (drt_nerf_render_backward_px)."""
         if grads.get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)
+        if self.sh_degree:
+            self._check_sh(scene)
         h, dev = self._bind(scene)
         em = scene.medium.emission
         _check(em, None, dev, "emission")
@@ -565,8 +673,9 @@ class NeRFIntegrator(_DeviceIntegrator):
         gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
         _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
         _check(ge, tuple(em.shape), dev, "grads[emission]")
-        h.nerf_render_backward_px(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-                                  grad_image.data_ptr(), grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
+        call = h.nerf_render_backward_px_sh if self.sh_degree else h.nerf_render_backward_px
+        call(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
+             grad_image.data_ptr(), grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
 
 
 class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
@@ -584,6 +693,9 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
 
     def __init__(self, props: Optional[dict] = None):
         props = dict(props or {})
+        if props.pop("sh_degree", 0):
+            raise NotImplementedError("nerf+volpathsimple has no spherical-harmonic emission (sh_degree > 0): its one colour grid is "
+                                      "the albedo too; use the 'nerf' integrator")
         self.queries_per_ray = int(props.pop("queries_per_ray", 128))
         self.jittering_enabled = bool(props.pop("jittering_enabled", True))
         self.activation_type = str(props.pop("activation", "identity")).lower()

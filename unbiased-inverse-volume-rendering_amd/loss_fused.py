@@ -84,6 +84,9 @@ def _check_integrator(integrator, what: str):
     if isinstance(integrator, FusedNerfDrtIntegrator):
         raise ValueError(f"{what}: nerf+volpathsimple renders a 6-channel image, which has no 3-channel reference; "
                          "use 'volpathsimple' or 'nerf'")
+    if getattr(integrator, "sh_degree", 0):
+        raise NotImplementedError(f"{what}: spherical-harmonic emission (sh_degree {integrator.sh_degree}) is not supported by the "
+                                  "loss-fused path; use render / render_batch with a loss on the image")
     if not hasattr(integrator, "sample_backward_px"):
         raise ValueError(f"{what}: {type(integrator).__name__} has no loss-fused backward pass")
 

@@ -204,6 +204,7 @@ class GridMedium:
     # use 8 (python/scene_config.py:36).
     majorant_resolution_factor: int = 0
     # (Z, Y, X, 3) emission grid, only read by the `nerf` integrator (medium.get_emission, nerf.py:164)
+    # (NeRFIntegrator.sh_degree in {1, 2}: (Z, Y, X, 3K) spherical-harmonic coefficients, K = (sh_degree + 1)^2, channel 3k + c)
     emission: object = None
     # medium.phase_function() (volpathsimple.py:202-231, 380-392, 616-646); the `nerf` integrator has none
     phase: object = field(default_factory=IsotropicPhase)
