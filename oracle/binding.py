@@ -27,7 +27,20 @@ class Config(C.Structure):
 class Medium(C.Structure):
     _fields_ = [("sigma_t", C.POINTER(C.c_float)), ("albedo", C.POINTER(C.c_float)),
                 ("res", C.c_int32 * 3), ("bbox_min", C.c_float * 3), ("bbox_max", C.c_float * 3),
-                ("scale", C.c_float), ("majorant_factor", C.c_int32), ("res_colour", C.c_int32 * 3)]
+                ("scale", C.c_float), ("majorant_factor", C.c_int32), ("res_colour", C.c_int32 * 3),
+                ("phase_kind", C.c_int32), ("phase_g", C.c_float), ("phase_g2", C.c_float), ("phase_w", C.c_float)]
+
+
+def phase_fields(phase):
+    """(phase_kind, phase_g, phase_g2, phase_w) of a scene phase function (IsotropicPhase / HGPhase / HG2Phase; None: isotropic)."""
+    kind = int(getattr(phase, "kind", 0)) if phase is not None else 0
+    if kind == 0:
+        return 0, 0.0, 0.0, 0.0
+    if kind == 1:
+        return 1, float(phase.g), 0.0, 0.0
+    if kind == 2:
+        return 2, float(phase.g1), float(phase.g2), float(phase.weight)
+    raise ValueError(f"the oracle has no phase function of kind {kind}")
 
 
 class Emitter(C.Structure):
@@ -132,6 +145,17 @@ def lib():
         L.drto_sensor_ray.restype = None
         L.drto_alt_seed.argtypes = [C.c_uint32, C.c_int]
         L.drto_alt_seed.restype = C.c_uint32
+        L.drto_render_forward_g.argtypes = [C.POINTER(Job), fp, fp]
+        L.drto_hg_sample.argtypes = [C.c_float, C.c_float, C.c_float, fp, fp, fp, fp]
+        L.drto_hg_sample.restype = None
+        L.drto_hg_eval.argtypes = [C.c_float, fp, fp]
+        L.drto_hg_eval.restype = C.c_float
+        L.drto_hg_score.argtypes = [C.c_float, C.c_float]
+        L.drto_hg_score.restype = C.c_float
+        L.drto_hg2_sample.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, fp, fp, fp]
+        L.drto_hg2_sample.restype = None
+        L.drto_hg2_eval.argtypes = [C.c_float, C.c_float, C.c_float, fp, fp]
+        L.drto_hg2_eval.restype = C.c_float
         L.drto_atan2f.argtypes = [C.c_float, C.c_float]
         L.drto_atan2f.restype = C.c_float
         L.drto_envmap_eval.argtypes = [C.POINTER(Emitter), fp, fp]
@@ -188,6 +212,7 @@ class OracleScene:
                              (C.c_float * 3)(*m.bbox_min), (C.c_float * 3)(*m.bbox_max),
                              float(m.scale), int(getattr(m, "majorant_resolution_factor", 0)),
                              (C.c_int32 * 3)(*(cshape[2], cshape[1], cshape[0]) if own else (0, 0, 0)))
+        self.set_phase(getattr(m, "phase", None))
         self.emitter, self._emitter_pixels = make_emitter(scene.emitter)
         self.sensor = None
         self.film = None
@@ -198,6 +223,11 @@ class OracleScene:
                                  (C.c_float * 3)(*f["up"]), (C.c_float * 3)(*f["dir"]),
                                  float(f["tan_x"]), float(f["tan_y"]), s.width, s.height)
             self.film = (s.width, s.height)
+
+    def set_phase(self, phase):
+        """The medium's phase function (a medium without the attribute, or None: isotropic)."""
+        k, g, g2, w = phase_fields(phase)
+        self.medium.phase_kind, self.medium.phase_g, self.medium.phase_g2, self.medium.phase_w = k, g, g2, w
 
     def grid_shape(self):
         return self.sigma_t.shape[:3]
@@ -250,6 +280,18 @@ def render_backward(oscene: OracleScene, props: dict, spp: int, seed: int, dL, L
     if rc:
         raise RuntimeError(f"drto_render_backward failed: {rc}")
     return gs, ga, cnt.as_dict()
+
+
+def render_forward_g(oscene: OracleScene, props: dict, spp: int, seed: int, **kw):
+    """Forward-mode derivative of the radiance with respect to the HG asymmetry g, per ray (drto_render_forward_g).
+    -> (dLdg [n,3] float32, mag [n,3] float32: the same sum over absolute values)"""
+    job = oscene.job(make_config(props), spp, seed, **kw)
+    dg = np.zeros((job.n_rays, 3), dtype=np.float32)
+    mag = np.zeros((job.n_rays, 3), dtype=np.float32)
+    rc = lib().drto_render_forward_g(C.byref(job), _fp(dg), _fp(mag))
+    if rc:
+        raise RuntimeError(f"drto_render_forward_g failed: {rc}")
+    return dg, mag
 
 
 def h1_step(oscene: OracleScene, props: dict, spp: int, seed: int, **kw):
@@ -430,3 +472,34 @@ def fused_render_backward(oscene: OracleScene, drt_props: dict, nerf_props: dict
                                L_in=np.ascontiguousarray(L_in[:, :3]), **kw)
     gs_d, ga, cd = render_backward(oscene, drt_props, spp, seed, np.ascontiguousarray(dL[:, 3:]), np.ascontiguousarray(L_in[:, 3:]), **kw)
     return gs_n + gs_d, ge + ga, _fused_counters(cn, cd)
+
+
+# ---- phase-function primitives (test hooks) ---------------------------------------------------
+def hg_sample(g, ux, uy, wi):
+    """hg_sample of one draw -> (wo[3], pdf, mu) in float32"""
+    wi = np.ascontiguousarray(wi, dtype=np.float32)
+    wo, pdf, mu = np.zeros(3, np.float32), C.c_float(0), C.c_float(0)
+    lib().drto_hg_sample(float(g), float(ux), float(uy), _fp(wi), _fp(wo), C.byref(pdf), C.byref(mu))
+    return wo, np.float32(pdf.value), np.float32(mu.value)
+
+
+def hg_eval(g, wo, wi):
+    wo, wi = np.ascontiguousarray(wo, dtype=np.float32), np.ascontiguousarray(wi, dtype=np.float32)
+    return np.float32(lib().drto_hg_eval(float(g), _fp(wo), _fp(wi)))
+
+
+def hg_score(g, mu):
+    return np.float32(lib().drto_hg_score(float(g), float(mu)))
+
+
+def hg2_sample(g1, g2, w, u1, ux, uy, wi):
+    """hg2_sample of one draw -> (wo[3], pdf of the mixture) in float32"""
+    wi = np.ascontiguousarray(wi, dtype=np.float32)
+    wo, pdf = np.zeros(3, np.float32), C.c_float(0)
+    lib().drto_hg2_sample(float(g1), float(g2), float(w), float(u1), float(ux), float(uy), _fp(wi), _fp(wo), C.byref(pdf))
+    return wo, np.float32(pdf.value)
+
+
+def hg2_eval(g1, g2, w, wo, wi):
+    wo, wi = np.ascontiguousarray(wo, dtype=np.float32), np.ascontiguousarray(wi, dtype=np.float32)
+    return np.float32(lib().drto_hg2_eval(float(g1), float(g2), float(w), _fp(wo), _fp(wi)))

@@ -183,6 +183,76 @@ static inline float mis_weight(float a, float b)
     return isfinite(w) ? w : 0.0f;
 }
 
+/* ------------------------------------------------------------------------- */
+/* Henyey-Greenstein phase function (Mitsuba 3 src/phase/hg.cpp) and the       */
+/* two-lobe mixture (`blendphase` over two `hg` children), float32, operation  */
+/* by operation as DESIGN.md "Henyey-Greenstein phase function" / "Two-lobe    */
+/* ..." write them down (no contraction; one explicit fmaf in the frame).      */
+/*   eval(wo, wi) = (1 - g^2) / (4 pi (1 + g^2 + 2 g mu)^(3/2)), mu = wo . wi, */
+/*   wi = -d of the ray that reached the vertex (g > 0 scatters forward).      */
+/* ------------------------------------------------------------------------- */
+#define DRT_HG_EPS 5.9604644775390625e-8f   /* dr::Epsilon<float> = 2^-24 */
+
+static inline float dot3(v3 a, v3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+
+static inline float hg_eval_cos(float g, float mu)
+{
+    const float temp = (1.0f + g * g) + (2.0f * g) * mu;
+    return (DRT_INV_FOURPI * (1.0f - g * g)) / (temp * sqrtf(temp));
+}
+static inline float hg_eval(float g, v3 wo, v3 wi) { return hg_eval_cos(g, dot3(wo, wi)); }
+
+/* the published inverted CDF as it is (for tiny |g| above 2^-24 the difference cancels and |cos_theta| may exceed 1);
+ * *mu: the cosine the pdf is evaluated at (= -cos_theta), what hg_score takes */
+static inline v3 hg_sample(float g, float ux, float uy, v3 wi, float *pdf, float *mu)
+{
+    float cos_t;
+    if (fabsf(g) < DRT_HG_EPS) cos_t = 1.0f - 2.0f * ux;
+    else {
+        const float sqr_term = (1.0f - g * g) / ((1.0f - g) + (2.0f * g) * ux);
+        cos_t = ((1.0f + g * g) - sqr_term * sqr_term) / (2.0f * g);
+    }
+    const float sin_t = sqrtf(fmaxf(0.0f, 1.0f - cos_t * cos_t));
+    float sp, cp;
+    drt_sincos_2pi(uy, &sp, &cp);
+    const float lx = sin_t * cp, ly = sin_t * sp, lz = -cos_t;
+    /* coordinate_system(wi) (Duff et al. 2017): sign = +1 for n.z >= 0, mulsign by the sign BIT of n.z */
+    const float sgn = wi.z >= 0.0f ? 1.0f : -1.0f, msg = copysignf(1.0f, wi.z);
+    const float a = -1.0f / (sgn + wi.z);
+    const float b = (wi.x * wi.y) * a;
+    const v3 s = v3_make(msg * ((wi.x * wi.x) * a) + 1.0f, msg * b, -msg * wi.x);
+    const v3 t = v3_make(b, fmaf(wi.y, wi.y * a, sgn), -wi.y);
+    *mu = -cos_t;
+    *pdf = hg_eval_cos(g, *mu);
+    return v3_make((s.x * lx + t.x * ly) + wi.x * lz, (s.y * lx + t.y * ly) + wi.y * lz, (s.z * lx + t.z * ly) + wi.z * lz);
+}
+
+/* d/dg log hg_eval_cos(g, mu) (DESIGN.md "Gradient with respect to g") */
+static inline float hg_score(float g, float mu)
+{
+    const float temp = (1.0f + g * g) + (2.0f * g) * mu;
+    return (-2.0f * g) / (1.0f - g * g) - (3.0f * (g + mu)) / temp;
+}
+
+/* p = (1 - w) hg(g1) + w hg(g2): w is the share of the SECOND lobe */
+static inline float hg2_eval_cos(float g1, float g2, float w, float mu)
+{
+    const float a = 1.0f - w;
+    const float p1 = hg_eval_cos(g1, mu), p2 = hg_eval_cos(g2, mu);
+    return a * p1 + w * p2;
+}
+static inline float hg2_eval(float g1, float g2, float w, v3 wo, v3 wi) { return hg2_eval_cos(g1, g2, w, dot3(wo, wi)); }
+
+/* the lobe is the second one iff u1 < w; the pdf is the MIXTURE at the sampled cosine */
+static inline v3 hg2_sample(float g1, float g2, float w, float u1, float ux, float uy, v3 wi, float *pdf)
+{
+    const float g = u1 < w ? g2 : g1;
+    float lobe_pdf, mu;
+    const v3 d = hg_sample(g, ux, uy, wi, &lobe_pdf, &mu);
+    *pdf = hg2_eval_cos(g1, g2, w, mu);
+    return d;
+}
+
 /* atan2 with a specified instruction sequence (Cephes atanf polynomial on min/max in [0,1]); the
  * HIP kernels evaluate the same sequence, so envmap lookups are bit-identical.  atan2(0,0) = 0. */
 static inline float drt_atan2f(float y, float x)
@@ -403,7 +473,26 @@ typedef struct {
     float *mgrid;
     float Le[3];
     envmap_t env;                /* env.pix != NULL: envmap emitter instead of the constant Le */
+    int phase_kind;              /* drto_medium::phase_kind: 0 isotropic, 1 HG (phase_g), 2 two-lobe HG (phase_g, phase_g2, phase_w) */
+    float phase_g, phase_g2, phase_w;
 } scene_t;
+
+/* The medium's phase function at a scattering vertex.  Every kind consumes the same three draws (u1, then ux, uy): the isotropic
+ * and single-lobe sites drop u1.  *mu: the sampled cosine (HG only; what hg_score takes). */
+static inline v3 phase_sample(const scene_t *sc, float u1, float ux, float uy, v3 wi, float *pdf, float *mu)
+{
+    *mu = 0.0f;
+    if (sc->phase_kind == 1) return hg_sample(sc->phase_g, ux, uy, wi, pdf, mu);
+    if (sc->phase_kind == 2) return hg2_sample(sc->phase_g, sc->phase_g2, sc->phase_w, u1, ux, uy, wi, pdf);
+    *pdf = DRT_INV_FOURPI;
+    return square_to_uniform_sphere(ux, uy);
+}
+static inline float phase_eval(const scene_t *sc, v3 wo, v3 wi)
+{
+    if (sc->phase_kind == 1) return hg_eval(sc->phase_g, wo, wi);
+    if (sc->phase_kind == 2) return hg2_eval(sc->phase_g, sc->phase_g2, sc->phase_w, wo, wi);
+    return DRT_INV_FOURPI;
+}
 
 /* Thread-local write-combining cache in front of the shared gradient grids (job->grad_cache_log2 > 0; used by
  * the timed CPU-baseline leg only): direct-mapped on the voxel index, a hit accumulates privately, an eviction
@@ -439,7 +528,13 @@ typedef struct {
     gcache_line *gcache;          /* NULL: every splat goes to the shared grids with atomics */
     uint32_t gcache_mask;
     struct gbucket *gbin;         /* job->grad_cache_log2 == -1 (timed CPU-baseline leg): this thread's splat records by z layer, see run_job */
+    struct gfwd *gf;              /* drto_render_forward_g: the current ray's forward-mode accumulators (NULL otherwise) */
 } ctx_t;
+
+/* Forward-mode derivative with respect to the HG asymmetry g of ONE ray, main path only (DESIGN.md "Gradient with respect to g"):
+ * S = running float32 sum of the scores of the sampled directions; every contribution c adds c (S + explicit term) to tg.
+ * mS / mag: the same sums with every factor replaced by its absolute value - the scale rounding is judged against. */
+typedef struct gfwd { float S, tg[3], mS, mag[3]; } gfwd_t;
 
 /* E3: GridVolume::eval, trilinear, clamp, cell-centred (q = p*res - 0.5) */
 typedef struct { int idx[8]; float wx0, wx1, wy0, wy1, wz0, wz1; } stencil_t;
@@ -740,7 +835,7 @@ static float estimate_transmittance(ctx_t *c, v3 o, v3 d, float tmax, pcg32 *S, 
 
 /* A7: sample_emitter (volpathsimple.py:406-433).  Returns emitter_val * transmittance (RGB) in
  * out[] and ds.pdf in *ds_pdf. */
-static void sample_emitter(ctx_t *c, v3 p, pcg32 *S, const float *adj, float out[3], float *ds_pdf)
+static void sample_emitter(ctx_t *c, v3 p, pcg32 *S, const float *adj, float out[3], float *ds_pdf, v3 *wd_out)
 {
     const scene_t *sc = c->sc;
     float ux = next_1d(S), uy = next_1d(S);              /* :418 */
@@ -754,6 +849,7 @@ static void sample_emitter(ctx_t *c, v3 p, pcg32 *S, const float *adj, float out
         for (int k = 0; k < 3; ++k) val[k] = sc->Le[k] * DRT_FOURPI;    /* radiance / pdf */
     }
     *ds_pdf = pdf;
+    *wd_out = wd;
     float T = 0.0f;
     if (pdf != 0.0f) {                                   /* sampling_worked :421-423 */
         si_t si = box_hit(sc, p, wd);                    /* mei.spawn_ray: no offset (n=0) :427-428 */
@@ -763,19 +859,24 @@ static void sample_emitter(ctx_t *c, v3 p, pcg32 *S, const float *adj, float out
 }
 
 /* A7: sample_emitter_for_nee (volpathsimple.py:380-403) */
-static void sample_emitter_for_nee(ctx_t *c, v3 p, pcg32 *S, const float beta[3], const float *dL,
-                                   float contrib[3])
+/* wi: the incoming direction at p, -d of the ray that reached the vertex (:386-388: phase_val = phase_pdf = eval(wo = emitter
+ * direction, wi)).  gx (may be NULL; HG only): the log-derivative of this term with respect to g, (2 w - 1) hg_score(mu_e). */
+static void sample_emitter_for_nee(ctx_t *c, v3 p, v3 wi, pcg32 *S, const float beta[3], const float *dL,
+                                   float contrib[3], float *gx)
 {
     pcg32 clone = *S;                                    /* :383 */
     float emitted[3], ds_pdf;
-    sample_emitter(c, p, S, NULL, emitted, &ds_pdf);     /* :385 */
-    float w = mis_weight(ds_pdf, DRT_INV_FOURPI);        /* ds.pdf vs phase_pdf :391 */
+    v3 wd;
+    sample_emitter(c, p, S, NULL, emitted, &ds_pdf, &wd);   /* :385 */
+    float pv = phase_eval(c->sc, wd, wi);                /* :386-388 */
+    float w = mis_weight(ds_pdf, pv);                    /* ds.pdf vs phase_pdf :391 */
     for (int k = 0; k < 3; ++k)
-        contrib[k] = ((beta[k] * DRT_INV_FOURPI) * w) * emitted[k];
+        contrib[k] = ((beta[k] * pv) * w) * emitted[k];
+    if (gx) *gx = (2.0f * w - 1.0f) * hg_score(c->sc->phase_g, dot3(wd, wi));
     if (dL) {                                            /* :393-401 */
         float adj[3] = { dL[0] * contrib[0], dL[1] * contrib[1], dL[2] * contrib[2] };
         float unused[3], unused_pdf;
-        sample_emitter(c, p, &clone, adj, unused, &unused_pdf);
+        sample_emitter(c, p, &clone, adj, unused, &unused_pdf, &wd);
     }
 }
 
@@ -856,24 +957,26 @@ static void drt_sample(ctx_t *c, pcg32 *S, int adjoint, ray_t ray, const float *
                        const float *state_in, const pstate_t *ps, float out[3]);
 
 /* A10: sample_recursive (volpathsimple.py:610-655) */
-static void sample_recursive(ctx_t *c, pcg32 *A, v3 p, int depth, float Li[3])
+/* wi: the incoming direction at p, -d of the sub-ray the vertex lies on (:566, :630) */
+static void sample_recursive(ctx_t *c, pcg32 *A, v3 p, v3 wi, int depth, float Li[3])
 {
     const scene_t *sc = c->sc;
     Li[0] = Li[1] = Li[2] = 0.0f;
     if (sc->cfg.use_nee) {                               /* :621-624 */
         const float one[3] = { 1.0f, 1.0f, 1.0f };
         float nee[3];
-        sample_emitter_for_nee(c, p, A, one, NULL, nee);
+        sample_emitter_for_nee(c, p, wi, A, one, NULL, nee, NULL);
         for (int k = 0; k < 3; ++k) Li[k] += nee[k];
     }
-    (void) next_1d(A);                                   /* phase.sample sample1 :632 */
+    float u1 = next_1d(A);                               /* phase.sample sample1 :632 (two-lobe: chooses the lobe) */
     float ux = next_1d(A), uy = next_1d(A);
-    v3 wo = square_to_uniform_sphere(ux, uy);
+    float ph_pdf, ph_mu;
+    v3 wo = phase_sample(sc, u1, ux, uy, wi, &ph_pdf, &ph_mu);
     ray_t rr; rr.o = p; rr.d = wo;
     si_t sn = box_hit(sc, p, wo);                        /* :637 */
     rr.maxt = sn.valid ? sn.t : DRT_LARGEST;             /* :639-640 */
     pstate_t ps;
-    ps.depth = depth + 1; ps.si = sn; ps.last_pdf = DRT_INV_FOURPI; ps.escaped = 0;
+    ps.depth = depth + 1; ps.si = sn; ps.last_pdf = ph_pdf; ps.escaped = 0;
     /* DEVIATION: an invalid si_next (fp corner case) deactivates the
      * recursive path instead of tracking forever with maxt = largest. */
     ps.active = (ps.depth < sc->cfg.max_depth) && sn.valid;  /* :647 */
@@ -895,7 +998,7 @@ static void drt_backprop(ctx_t *c, pcg32 *A, const ray_t *ray, const si_t *si, i
     float sig = eval_sigma_t(sc, p);                     /* :553-554 attached */
     c->cnt.n_drt++;
     float Li[3];
-    sample_recursive(c, A, p, depth, Li);                /* :565-568 */
+    sample_recursive(c, A, p, v3_make(-sub.d.x, -sub.d.y, -sub.d.z), depth, Li);   /* :565-568 */
     float w = sc->cfg.use_drt_mis ? 1.0f / (1.0f + sig * sig) : 1.0f;   /* :571-575 */
     float alb[3];
     eval_albedo(sc, p, alb);                             /* :578 */
@@ -955,6 +1058,8 @@ static void drt_sample(ctx_t *c, pcg32 *S, int adjoint, ray_t ray, const float *
     }
     int has_scattered = ps ? (active && !escaped) : 0;   /* :84-89 */
     float last_pdf = ps ? ps->last_pdf : 1.0f;
+    gfwd_t *gf = (!ps && !adjoint) ? c->gf : NULL;       /* forward mode in g: main path of a primal pass */
+    float s_last = 0.0f;                                 /* ... score of the last sampled direction */
 
     reservoir_t R;                                       /* :94-96 */
     memset(&R, 0, sizeof R);
@@ -1023,16 +1128,22 @@ static void drt_sample(ctx_t *c, pcg32 *S, int adjoint, ray_t ray, const float *
         active = did_scatter && (depth < cfg->max_depth);/* :200 */
 
         if (cfg->use_nee && did_scatter && active) {     /* :206-215 */
-            float nee[3];
-            sample_emitter_for_nee(c, mei.p, S, beta, adjoint ? dL : NULL, nee);
+            float nee[3], gx = 0.0f;
+            sample_emitter_for_nee(c, mei.p, v3_make(-ray.d.x, -ray.d.y, -ray.d.z), S, beta, adjoint ? dL : NULL, nee, gf ? &gx : NULL);
             for (int k = 0; k < 3; ++k) result[k] = adjoint ? result[k] - nee[k] : result[k] + nee[k];
+            if (gf) {
+                const float f = gf->S + gx, mf = gf->mS + fabsf(gx);
+                for (int k = 0; k < 3; ++k) { gf->tg[k] += nee[k] * f; gf->mag[k] += fabsf(nee[k]) * mf; }
+            }
         }
 
         if (did_scatter) {                               /* :221-230 */
-            (void) next_1d(S);
+            float u1 = next_1d(S);                       /* (two-lobe: chooses the lobe; dropped otherwise) */
             float ux = next_1d(S), uy = next_1d(S);
-            ray.o = mei.p; ray.d = square_to_uniform_sphere(ux, uy); ray.maxt = DRT_LARGEST;
-            last_pdf = DRT_INV_FOURPI;
+            float mu;
+            ray.d = phase_sample(sc, u1, ux, uy, v3_make(-ray.d.x, -ray.d.y, -ray.d.z), &last_pdf, &mu);
+            ray.o = mei.p; ray.maxt = DRT_LARGEST;
+            if (gf) { s_last = hg_score(sc->phase_g, mu); gf->S += s_last; gf->mS += fabsf(s_last); }
         }
         si = box_hit(sc, ray.o, ray.d);                  /* :233-235 (did_scatter | did_escape) */
         ray.maxt = isfinite(si.t) ? si.t : DRT_LARGEST;
@@ -1061,6 +1172,14 @@ static void drt_sample(ctx_t *c, pcg32 *S, int adjoint, ray_t ray, const float *
             }
             if (sc->env.pix) envmap_eval(&sc->env, ray.d, Le);          /* :284 */
             for (int k = 0; k < 3; ++k) result[k] += (beta[k] * w) * Le[k];
+            if (gf && has_scattered) {                   /* the escape's MIS weight depends on g through last_pdf */
+                const float ex = cfg->use_nee ? (2.0f * (1.0f - w)) * s_last : 0.0f;
+                const float f = gf->S + ex, mf = gf->mS + fabsf(ex);
+                for (int k = 0; k < 3; ++k) {
+                    const float e = (beta[k] * w) * Le[k];
+                    gf->tg[k] += e * f; gf->mag[k] += fabsf(e) * mf;
+                }
+            }
         }
     }
     out[0] = result[0]; out[1] = result[1]; out[2] = result[2];
@@ -1226,6 +1345,8 @@ static int scene_init(scene_t *sc, const drto_job *job)
     sc->inv_majorant = sc->majorant != 0.0f ? 1.0f / sc->majorant : 0.0f;
     for (int k = 0; k < 3; ++k) sc->Le[k] = job->emitter->radiance[k];
     sc->mgrid = NULL; sc->gx = sc->gy = sc->gz = 0;
+    if (m->phase_kind < 0 || m->phase_kind > 2) return -5;
+    sc->phase_kind = m->phase_kind; sc->phase_g = m->phase_g; sc->phase_g2 = m->phase_g2; sc->phase_w = m->phase_w;
     memset(&sc->env, 0, sizeof(sc->env));
     if (job->emitter->pixels) {
         int rc = envmap_from_emitter(&sc->env, job->emitter);
@@ -1321,7 +1442,7 @@ static void cnt_add(drto_counters *a, const drto_counters *b)
 }
 
 static int run_job(const drto_job *job, int adjoint, const float *dL, const float *L_in,
-                   float *L_out, double *g_sigma, double *g_albedo, drto_counters *cnt)
+                   float *L_out, double *g_sigma, double *g_albedo, drto_counters *cnt, float *dLdg_out, float *mag_out)
 {
     scene_t sc;
     if (scene_init(&sc, job)) return -1;
@@ -1366,6 +1487,13 @@ static int run_job(const drto_job *job, int adjoint, const float *dL, const floa
             c.cnt.n_rays++;
             float L[3];
             if (adjoint) drt_sample(&c, &S, 1, ray, dL + 3 * i, L_in + 3 * i, NULL, L);
+            else if (dLdg_out) {
+                gfwd_t gf; memset(&gf, 0, sizeof gf);
+                c.gf = &gf;
+                drt_sample(&c, &S, 0, ray, NULL, NULL, NULL, L);
+                c.gf = NULL;
+                for (int k = 0; k < 3; ++k) { dLdg_out[3 * i + k] = gf.tg[k]; if (mag_out) mag_out[3 * i + k] = gf.mag[k]; }
+            }
             else {
                 drt_sample(&c, &S, 0, ray, NULL, NULL, NULL, L);
                 L_out[3 * i] = L[0]; L_out[3 * i + 1] = L[1]; L_out[3 * i + 2] = L[2];
@@ -1420,13 +1548,21 @@ static int run_job(const drto_job *job, int adjoint, const float *dL, const floa
 
 int drto_render_primal(const drto_job *job, float *L_out, drto_counters *cnt)
 {
-    return run_job(job, 0, NULL, NULL, L_out, NULL, NULL, cnt);
+    return run_job(job, 0, NULL, NULL, L_out, NULL, NULL, cnt, NULL, NULL);
+}
+
+/* Forward-mode derivative of every ray's radiance with respect to the HG asymmetry g (see gfwd_t) */
+int drto_render_forward_g(const drto_job *job, float *dLdg_out, float *mag_out)
+{
+    if (!job || !job->medium || !dLdg_out) return -1;
+    if (job->medium->phase_kind != 1) return -6;
+    return run_job(job, 0, NULL, NULL, NULL, NULL, NULL, NULL, dLdg_out, mag_out);
 }
 
 int drto_render_backward(const drto_job *job, const float *dL, const float *L_in,
                          double *grad_sigma_t, double *grad_albedo, drto_counters *cnt)
 {
-    return run_job(job, 1, dL, L_in, NULL, grad_sigma_t, grad_albedo, cnt);
+    return run_job(job, 1, dL, L_in, NULL, grad_sigma_t, grad_albedo, cnt, NULL, NULL);
 }
 
 int drto_h1_step(const drto_job *job, float *L, float *image, double *loss_out,
@@ -1461,7 +1597,8 @@ int drto_h1_step(const drto_job *job, float *L, float *image, double *loss_out,
 }
 
 /* Textbook analog delta-tracking path tracer: escape -> Le, collide -> albedo,
- * uniform phase.  No NEE/MIS; its own RNG consumption order. */
+ * the medium's phase function sampled perfectly (weight 1).  No NEE/MIS; its own RNG consumption order
+ * (the lobe draw of the two-lobe phase is taken only by that phase). */
 int drto_render_textbook(const drto_job *job, float *L_out)
 {
     scene_t sc;
@@ -1495,8 +1632,11 @@ int drto_render_textbook(const drto_job *job, float *L_out)
             float a[3]; eval_albedo(&sc, p, a);
             beta[0] *= a[0]; beta[1] *= a[1]; beta[2] *= a[2];
             if (++depth >= sc.cfg.max_depth) { alive = 0; break; }
+            float u1 = sc.phase_kind == 2 ? next_1d(&S) : 0.0f;
             float ux = next_1d(&S), uy = next_1d(&S);
-            ray.o = p; ray.d = square_to_uniform_sphere(ux, uy);
+            float ph_pdf, ph_mu;
+            ray.d = phase_sample(&sc, u1, ux, uy, v3_make(-ray.d.x, -ray.d.y, -ray.d.z), &ph_pdf, &ph_mu);
+            ray.o = p;
             si_t sn = box_hit(&sc, ray.o, ray.d);
             if (!sn.valid) { alive = 0; break; }
             ray.maxt = sn.t;
@@ -1570,6 +1710,25 @@ void drto_uniform_sphere(float ux, float uy, float out[3])
 {
     v3 d = square_to_uniform_sphere(ux, uy);
     out[0] = d.x; out[1] = d.y; out[2] = d.z;
+}
+void drto_hg_sample(float g, float ux, float uy, const float wi[3], float wo[3], float *pdf, float *mu)
+{
+    v3 d = hg_sample(g, ux, uy, v3_make(wi[0], wi[1], wi[2]), pdf, mu);
+    wo[0] = d.x; wo[1] = d.y; wo[2] = d.z;
+}
+float drto_hg_eval(float g, const float wo[3], const float wi[3])
+{
+    return hg_eval(g, v3_make(wo[0], wo[1], wo[2]), v3_make(wi[0], wi[1], wi[2]));
+}
+float drto_hg_score(float g, float mu) { return hg_score(g, mu); }
+void drto_hg2_sample(float g1, float g2, float w, float u1, float ux, float uy, const float wi[3], float wo[3], float *pdf)
+{
+    v3 d = hg2_sample(g1, g2, w, u1, ux, uy, v3_make(wi[0], wi[1], wi[2]), pdf);
+    wo[0] = d.x; wo[1] = d.y; wo[2] = d.z;
+}
+float drto_hg2_eval(float g1, float g2, float w, const float wo[3], const float wi[3])
+{
+    return hg2_eval(g1, g2, w, v3_make(wo[0], wo[1], wo[2]), v3_make(wi[0], wi[1], wi[2]));
 }
 float drto_atan2f(float y, float x) { return drt_atan2f(y, x); }
 int drto_envmap_eval(const drto_emitter *em, const float d[3], float out[3])

@@ -7,8 +7,9 @@
  *     /root/reference/python/batched.py:212-326             (primal -> dL -> adjoint sequence)
  * plus the slice of the Mitsuba 3 branch `unbiased-inverse-volume-rendering`
  * that those files call (Medium::sample_interaction[_drt], GridVolume::eval,
- * PCG32 `independent` sampler, sample_tea_32, constant / envmap emitter, isotropic
- * phase, AABB fast-path intersection).
+ * PCG32 `independent` sampler, sample_tea_32, constant / envmap emitter, the
+ * isotropic, `hg` and two-lobe (`blendphase` over two `hg`) phase functions,
+ * AABB fast-path intersection).
  *
  * PARITY UNPINNED: Mitsuba 3 / Dr.Jit are third-party dependencies that are
  * absent from /root/reference and cannot be imported in the authoring
@@ -59,6 +60,11 @@ typedef struct drto_medium {
      * interpolates every GridVolume on its own resolution: the reference's janga-smoke pairs a 264 x 136 x 136 density with
      * 256 x 128 x 128 albedo / emission grids (python/scene_config.py:108-110).  All zero: the lattice of sigma_t (`res`). */
     int32_t res_colour[3];
+    /* Phase function (the numbering of drt_set_phase / DRT_PHASE_HG2 in include/drt_hip.h): 0 isotropic, 1 Henyey-Greenstein with
+     * asymmetry phase_g, 2 two Henyey-Greenstein lobes (1 - phase_w) hg(phase_g) + phase_w hg(phase_g2).  All zero: isotropic.
+     * Every kind consumes the same draws at a phase site, so a path's sampler streams do not depend on it. */
+    int32_t phase_kind;
+    float phase_g, phase_g2, phase_w;
 } drto_medium;
 
 /* The scene's single infinite emitter (volpathsimple.py:16).
@@ -156,7 +162,15 @@ int drto_nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const fl
                      const float *dL, const float *L_in, float *L_out, double *grad_sigma_t,
                      double *grad_emission, drto_counters *cnt);
 
-/* Independent textbook delta-tracking path tracer (no NEE, no MIS, own RNG use):
+/* Forward-mode derivative of sample(Primal) with respect to the Henyey-Greenstein asymmetry g, per ray: dLdg_out[n][3].  The
+ * estimator of DESIGN.md "Gradient with respect to g", main path only: with S the float32 running sum of hg_score over the
+ * directions the main path has sampled, every contribution c adds c (S + explicit), explicit = (2 w - 1) hg_score(mu_e) at an NEE
+ * and 2 (1 - w) hg_score(mu_last) at the escape of a path that has scattered (NEE on).  Nothing comes from sample_recursive, the
+ * cloned NEE replay or a sigma_t estimator.  mag_out[n][3] (may be NULL): the same sum with every factor replaced by its absolute
+ * value - the scale against which rounding is judged.  phase_kind must be 1 (-6 otherwise). */
+int drto_render_forward_g(const drto_job *job, float *dLdg_out, float *mag_out);
+
+/* Independent textbook delta-tracking path tracer (no NEE, no MIS, own RNG use; samples the medium's phase function):
  * plays the role of Mitsuba's builtin `volpath` in tests/test_integrators.py:222-257. */
 int drto_render_textbook(const drto_job *job, float *L_out);
 
@@ -174,6 +188,13 @@ float    drto_logf(float x);
 float    drto_expf(float x);
 void     drto_sincos_2pi(float u, float *s, float *c);
 float    drto_atan2f(float y, float x);
+/* phase-function primitives (test hooks): hg_sample -> direction, pdf and the cosine mu the pdf was evaluated at; eval(wo, wi);
+ * d/dg log p(mu); the two-lobe sample (u1 chooses the lobe, pdf of the mixture) and eval */
+void     drto_hg_sample(float g, float ux, float uy, const float wi[3], float wo[3], float *pdf, float *mu);
+float    drto_hg_eval(float g, const float wo[3], const float wi[3]);
+float    drto_hg_score(float g, float mu);
+void     drto_hg2_sample(float g1, float g2, float w, float u1, float ux, float uy, const float wi[3], float wo[3], float *pdf);
+float    drto_hg2_eval(float g1, float g2, float w, const float wo[3], const float wi[3]);
 /* envmap primitives (test hooks): radiance towards world direction d; solid-angle pdf of sampling d;
  * sample_direction(u1, u2) -> d, pdf, radiance / pdf; the importance-sampling tables
  * (marginal [h+1], conditional [h][w+1]; either may be NULL). */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/cube_golden.npz with the CPU oracle.
+"""Generates tests/golden/cube_golden.npz and tests/golden/phase_golden.npz with the CPU oracle.
 
 The reference stores no golden vectors for this path and cannot be imported here
 (Mitsuba 3 / Dr.Jit absent), so these fixtures are produced by the
@@ -8,6 +8,9 @@ fixture (tests/test_integrators.py:19-116) and pin it against regressions:
 tests/test_oracle_kat.py (CPU) checks the oracle against the committed file, and
 tests/test_gpu_film_shapes.py::test_hip_path_equals_the_committed_golden_* compare the
 HIP path with the committed file directly (without calling the oracle).
+
+phase_golden.npz: the oracle's radiance, gradients, counters (and, for the single lobe, the per-ray derivative with respect to g) of
+one 8^3 Henyey-Greenstein medium and the same medium with a two-lobe phase function; tests/test_oracle_phase.py checks the oracle against it.
 
     python tests/golden/make_golden.py
 """
@@ -24,8 +27,25 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import uivr_amd as u                      # noqa: E402  (scene dataclasses only)
 from conftest import VARIANTS, props_for  # noqa: E402
 from oracle import binding as ob          # noqa: E402
+from test_oracle_phase import PHASE_SEED, PHASE_SPP, phase_scene  # noqa: E402  (the scenes of phase_golden.npz)
 
 RES, SPP, SEED, SCALE = 16, 8, 12345, 2.0
+
+
+def phase_main():
+    out = dict(spp=PHASE_SPP, seed=PHASE_SEED)
+    for name in ("hg", "hg2"):
+        scene = phase_scene(u, name)
+        r = ob.h1_step(ob.OracleScene(scene), props_for("drt"), PHASE_SPP, PHASE_SEED, n_threads=1)
+        for k in ("image", "L", "grad_sigma_t", "grad_albedo"):
+            out[f"{name}/{k}"] = r[k]
+        out[f"{name}/counters"] = np.array([r["counters"][k] for k in sorted(r["counters"])], dtype=np.int64)
+        if name == "hg":
+            out["hg/dLdg"], out["hg/mag"] = ob.render_forward_g(ob.OracleScene(scene), props_for("drt"), PHASE_SPP, PHASE_SEED, n_threads=1)
+    out["counter_names"] = np.array(sorted(r["counters"]))
+    path = os.path.join(HERE, "phase_golden.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path), "bytes")
 
 
 def main():
@@ -56,3 +76,4 @@ def main():
 
 if __name__ == "__main__":
     main()
+    phase_main()

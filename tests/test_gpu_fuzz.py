@@ -128,14 +128,77 @@ def test_random_medium_sized_scene_matches_the_oracle(uivr, oracle, gpu, seed):
     _check(uivr, oracle, gpu, _draw(uivr, seed, medium_size=True), seed)
 
 
-def _check(uivr, oracle, gpu, c, seed):
+def _draw_phase(uivr, rng):
+    """A phase function from a generator of its own (the scene draws of `_draw` stay as they are): a third Henyey-Greenstein with g uniform in
+    (-0.95, 0.95), a third with |g| log-uniform in [1e-4, 0.99] (down to where the published inverted CDF loses its precision in float32), a third
+    two lobes with the weight 0, 1 or uniform."""
+    import warnings
+    k = int(rng.integers(0, 3))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)                             # (tiny |g| warns: those draws are wanted)
+        if k == 0:
+            return uivr.HGPhase(float(rng.uniform(-0.95, 0.95)))
+        if k == 1:
+            g = float(np.exp(rng.uniform(np.log(1e-4), np.log(0.99))))
+            return uivr.HGPhase(g if rng.random() < 0.5 else -g)
+        w = [0.0, 1.0, float(rng.random())][int(rng.integers(0, 3))]
+        return uivr.HG2Phase(float(rng.uniform(-0.95, 0.95)), float(rng.uniform(-0.95, 0.95)), w)
+
+
+def _phase_tag(ph):
+    return f"hg2({ph.g1!r}, {ph.g2!r}, {ph.weight!r})" if int(ph.kind) == 2 else (f"hg({ph.g!r})" if int(ph.kind) == 1 else "isotropic")
+
+
+# the switches of _HOOKS (below) that the Henyey-Greenstein kernels accept - the others route the launch to an older tracer generation, which has no
+# such code and refuses -, no switch at all, and 4096: CoopTracer<SUPER> in place of the queued tracer
+_OLDER = 8 | 32 | 32768 | 65536 | 134217728
+
+
+def _phase_hooks():
+    return [0, 4096] + [f for f in _HOOKS if not f & _OLDER]
+
+
+def _draw_phase_flags(rng):
+    u = rng.random()                                                                # two in five: production's route; one in four: CoopTracer<SUPER>
+    hooks = _phase_hooks()
+    return 0 if u < 0.4 else (4096 if u < 0.65 else int(hooks[int(rng.integers(0, len(hooks)))]))
+
+
+@pytest.mark.parametrize("seed", SEEDS[:max(1, len(SEEDS) // 2)])
+def test_random_scene_with_a_phase_matches_the_oracle(uivr, oracle, gpu, seed):
+    """The draws of test_random_scene_matches_the_oracle with a random anisotropic phase function and, for three in five, one of the schedule switches
+    (`_draw_phase_flags`)
+    the HG kernels accept: the oracle restates those paths to the bit (tests/test_oracle_phase.py), so the bars are the isotropic ones."""
+    c = _draw(uivr, seed)
+    rng = np.random.default_rng(30_000 + seed)
+    c["scene"].medium.phase = _draw_phase(uivr, rng)
+    _check(uivr, oracle, gpu, c, seed, flags=_draw_phase_flags(rng))
+
+
+def test_the_phase_draws_cover_the_tracers():
+    """Among the default seeds: no switch (the production route) and 4096 (CoopTracer<SUPER>) both occur, and each kind of draw does."""
+    class Stub:
+        HGPhase = staticmethod(lambda g: ("hg", g))
+        HG2Phase = staticmethod(lambda a, b, w: ("hg2", a, b, w))
+    flags, kinds = set(), set()
+    for seed in range(24):
+        rng = np.random.default_rng(30_000 + seed)
+        ph = _draw_phase(Stub, rng)
+        kinds.add(ph[0] if ph[0] == "hg2" else ("hg-small" if abs(ph[1]) < 0.05 else "hg"))
+        flags.add(_draw_phase_flags(rng))
+    assert {0, 4096} <= flags and {"hg", "hg2"} <= kinds, (flags, kinds)
+
+
+def _check(uivr, oracle, gpu, c, seed, flags=0):
     scene, props, spp, rs = c["scene"], c["props"], c["spp"], c["seed"]
     tag = f"seed {seed}: {c['variant']} factor {c['factor']} grid {c['shape']} colour {c['cshape']} film {c['film']} spp {spp} env {c['env']} " \
-          f"depth {props['max_depth']} rr {props['rr_depth']} explicit {c['explicit']}"
+          f"depth {props['max_depth']} rr {props['rr_depth']} explicit {c['explicit']} phase {_phase_tag(scene.medium.phase)} flags {flags}"
     import torch
     sg = uivr.scene_to(scene, gpu)
-    integ = uivr.load_dict(dict(type="volpathsimple", **props))
+    integ = uivr.load_dict(dict(type="volpathsimple", **props, **({"test_hooks": True} if flags else {})))
     h = integ.native_handle(sg)
+    if flags:
+        h.set_debug_flags(flags)
     h.enable_counters(True)
     h.reset_counters()
     if c["explicit"]:
@@ -171,6 +234,8 @@ def _check(uivr, oracle, gpu, c, seed):
         expect = {k: ref["counters"][k] + 2 * c_p[k] for k in ref["counters"]}
     cnt = {k: int(v) for k, v in h.get_counters().items()}
     h.enable_counters(False)
+    if flags:
+        h.set_debug_flags(0)
     assert cnt == expect, tag
     _close(grads[uivr.SIGMA_T_KEY], gs, tag + " grad sigma_t")
     _close(grads[uivr.ALBEDO_KEY], ga, tag + " grad albedo")
@@ -405,7 +470,14 @@ def test_one_handle_rebound_to_a_grid_with_as_many_tiles_in_another_arrangement(
     _check_sequence(uivr, oracle, gpu, seed)
 
 
-def _check_sequence(uivr, oracle, gpu, seed):
+@pytest.mark.parametrize("seed", SEEDS[:max(1, len(SEEDS) // 8)])
+def test_random_sequence_with_phase_changes_on_one_handle_matches_the_oracle(uivr, oracle, gpu, seed):
+    """The sequences of test_random_sequence_on_one_handle_matches_the_oracle with the phase function redrawn (isotropic, one lobe, two lobes) between
+    steps: the handle's phase constants and its choice among the isotropic, kHG and kHG2 kernels follow - each step against the oracle with that phase."""
+    _check_sequence(uivr, oracle, gpu, seed, phases=np.random.default_rng(31_000 + seed))
+
+
+def _check_sequence(uivr, oracle, gpu, seed, phases=None):
     import torch
     rng = np.random.default_rng(77_000 + seed)
     c = _draw(uivr, seed + 2600, medium_size=seed % 5 == 4)
@@ -433,10 +505,16 @@ def _check_sequence(uivr, oracle, gpu, seed):
                 else uivr.ConstantEmitter(tuple(float(v) for v in rng.random(3) + 0.1))
             scene = uivr.Scene(medium=scene.medium, emitter=em, sensors=scene.sensors)
             sg = uivr.Scene(medium=sg.medium, emitter=uivr.scene_to(uivr.Scene(medium=scene.medium, emitter=em, sensors=[]), gpu).emitter, sensors=sg.sensors)
+        if phases is not None and (step == 0 or phases.random() < 0.7):              # (the handle's phase follows the scene's at the next launch)
+            ph = uivr.IsotropicPhase() if phases.random() < 0.2 else _draw_phase(uivr, phases)
+            scene.medium.phase = sg.medium.phase = ph
+        elif phases is not None:
+            sg.medium.phase = scene.medium.phase
         spp, rs = int(rng.choice([1, 2, 3, 4, 8])), int(rng.integers(1, 2**31 - 1))
         s = scene.sensors[0]
         n_pix = s.width * s.height
-        tag = f"seed {seed} step {step} kind {k}: grid {tuple(np.asarray(scene.medium.sigma_t).shape[:3])} film {(s.width, s.height)} spp {spp}"
+        tag = f"seed {seed} step {step} kind {k}: grid {tuple(np.asarray(scene.medium.sigma_t).shape[:3])} film {(s.width, s.height)} spp {spp}" \
+              f" phase {_phase_tag(scene.medium.phase)}"
         osc = oracle.OracleScene(scene)
         ref = oracle.h1_step(osc, props, spp, rs)
         batch = uivr.RayBatch(n_rays=n_pix * spp, spp=spp, sensor=sg.sensors[0])

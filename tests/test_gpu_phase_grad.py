@@ -1,5 +1,7 @@
 """The derivative with respect to the Henyey-Greenstein asymmetry g (drt_render_backward_phase / drt_render_forward_phase, the Phase::kHGGrad
-kernels).  The estimator is an extension of the reference, so these tests rest on independent checks: the device score against float64
+kernels).  The estimator is an extension of the reference.  tests/test_gpu_phase_parity.py holds forward mode to the oracle's drto_render_forward_g per ray
+(equal bits) and the adjoint's scalar to its sum; the oracle's own derivative is pinned on the CPU (tests/test_oracle_phase.py).  The tests here are
+the independent checks - the loss-fused, batched and sharded paths keep theirs in tests/test_gpu_phase_grad_paths.py -: the device score against float64
 autograd, single scattering against the derivative of a float64 quadrature, forward / adjoint transposition over every estimator,
 finite differences in a multiple-scattering medium, the queued tracer against CoopTracer<SUPER>, autograd, a small optimisation of g,
 and the refusals."""

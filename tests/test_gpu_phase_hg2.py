@@ -1,5 +1,6 @@
-"""Two-lobe Henyey-Greenstein phase function on the device (drt_set_phase_hg2; the Phase::kHG2 instantiations of the tracers).  The CPU oracle is
-isotropic, so these tests rest on the checks of test_gpu_phase_hg.py, with the mixture in place of the single lobe: the device primitive
+"""Two-lobe Henyey-Greenstein phase function on the device (drt_set_phase_hg2; the Phase::kHG2 instantiations of the tracers).  The kernels are
+held to the CPU oracle ray by ray in tests/test_gpu_phase_parity.py; these tests are the checks of test_gpu_phase_hg.py that do not rest on the
+oracle, with the mixture in place of the single lobe: the device primitive
 against a float32 restatement, exact degeneracy at weight 0 / 1 against HGPhase, a float64 single-scattering quadrature, estimators and
 tracers that must agree, the forward / adjoint transposition identity, finite differences, and the handle's state and refusals."""
 import ctypes
@@ -10,32 +11,13 @@ import pytest
 import torch
 
 from conftest import VARIANTS, props_for
-from test_phase_host import coordinate_system, hg_eval
+from test_phase_host import _hg2, _hg2_f32, _hg_f32, hg_eval, single_scatter_quadrature  # noqa: F401
 from test_gpu_phase_hg import (ALB, BMAX, BMIN, GRAD_RTOL, RAYS_O, RAYS_T, SIG, _cmp_means, _debug, _exit_dist, _hg_sample_f32, _image_stats,
                                _random_medium, _single_scatter_scene, _volpath)
 
 pytestmark = pytest.mark.gpu
 
 TRIPLES = [(0.8, -0.3, 0.3), (0.6, -0.6, 0.5)]
-
-
-def _hg_f32(g, mu):
-    """hg_eval_cos (drt_device.h) in float32, operation by operation."""
-    f = np.float32
-    g, mu = f(g), mu.astype(f)
-    temp = (f(1) + g * g) + (f(2) * g) * mu
-    return (f(1 / (4 * math.pi)) * (f(1) - g * g)) / (temp * np.sqrt(temp))
-
-
-def _hg2_f32(g1, g2, w, mu):
-    """hg2_eval_cos: a = 1 - w; p = (a * p1) + (w * p2)."""
-    f = np.float32
-    a = f(1) - f(w)
-    return a * _hg_f32(g1, mu) + f(w) * _hg_f32(g2, mu)
-
-
-def _hg2(g1, g2, w, mu):
-    return (1.0 - w) * hg_eval(g1, mu) + w * hg_eval(g2, mu)
 
 
 # ---- 1. the primitive ---------------------------------------------------------------------------------------------------------------
@@ -142,34 +124,8 @@ def test_weight_0_and_1_are_the_single_lobes(uivr, gpu, factor, env, variant):
 
 # ---- 3. known answer: single scattering ---------------------------------------------------------------------------------------------
 def _expected(h, gpu, phase, o, d):
-    """test_gpu_phase_hg._expected with the phase function `phase(mu)`, mu = dot(wo, wi): float64, integral over t in the box of
-    sigma_t e^{-sigma_t t} albedo  x  integral over the sphere of p(wo, -d) Le(wo) T(x_t, wo)."""
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t_in = float(np.max(np.minimum((BMIN - o) / d, (BMAX - o) / d)))
-        t_out = float(np.min(np.maximum((BMIN - o) / d, (BMAX - o) / d)))
-    xt, wt = np.polynomial.legendre.leggauss(48)
-    ts = 0.5 * (t_out - t_in) * (xt + 1.0)
-    wts = 0.5 * (t_out - t_in) * wt
-    xm, wm = np.polynomial.legendre.leggauss(160)
-    k = 4.0
-    mu = np.tanh(k * xm) / np.tanh(k)
-    wmu = wm * k * (1.0 - np.tanh(k * xm) ** 2) / np.tanh(k)
-    nphi = 160
-    phi = (np.arange(nphi) + 0.5) / nphi * 2.0 * math.pi
-    s, t = coordinate_system(d[None, :])
-    sin_ = np.sqrt(np.maximum(0.0, 1.0 - mu ** 2))
-    dirs = (s[0] * (sin_[:, None, None] * np.cos(phi)[None, :, None]) + t[0] * (sin_[:, None, None] * np.sin(phi)[None, :, None])
-            + d[None, None, :] * mu[:, None, None]).reshape(-1, 3)
-    w_dir = (wmu[:, None] * np.full(nphi, 2.0 * math.pi / nphi)[None, :]).reshape(-1)
-    Le = _debug(h, gpu, 12, dirs.astype(np.float32))[:, :3].astype(np.float64)
-    ph = phase(-np.repeat(mu, nphi))                                         # mu_phase = dot(wo, wi) = -dot(wo, d)
-    total = np.zeros(3)
-    for ti, wti in zip(ts, wts):
-        x = o + d * (t_in + ti)
-        T = np.exp(-SIG * _exit_dist(x[None, :], dirs))
-        inner = np.sum((w_dir * ph * T)[:, None] * Le, 0)
-        total += wti * SIG * math.exp(-SIG * ti) * ALB * inner
-    return total
+    """single_scatter_quadrature (test_phase_host.py) with the phase function `phase(mu)`, mu = dot(wo, wi); Le from debug op 12."""
+    return single_scatter_quadrature(phase, lambda dirs: _debug(h, gpu, 12, dirs)[:, :3], o, d)
 
 
 @pytest.mark.parametrize("factor", [0, 8])

@@ -48,6 +48,106 @@ def hg_sample(g, u1, u2, wi):
     wo = s * local[:, :1] + t * local[:, 1:2] + np.asarray(wi, np.float64) * local[:, 2:]
     return wo, hg_eval(g, -ct)
 
+# ---- float32 restatements in the device's operation order (shared by the GPU tests and tests/test_oracle_phase.py) ------------------
+def _hg_sample_f32(g, u1, sp, cp, wi):
+    """hg_sample (drt_device.h) in float32, operation by operation; sin / cos of 2 pi u2 are given (the device's debug op 1, or the
+    oracle's drto_sincos_2pi)."""
+    f = np.float32
+    g, u1, wi = f(g), u1.astype(f), wi.astype(f)
+    if abs(float(g)) < 2.0 ** -24:
+        ct = f(1) - f(2) * u1
+    else:
+        sq = (f(1) - g * g) / ((f(1) - g) + (f(2) * g) * u1)
+        ct = ((f(1) + g * g) - sq * sq) / (f(2) * g)
+    st = np.sqrt(np.maximum(f(0), f(1) - ct * ct))
+    lx, ly, lz = st * cp, st * sp, -ct
+    x, y, z = wi[:, 0], wi[:, 1], wi[:, 2]
+    sgn = np.where(z >= 0, f(1), f(-1)).astype(f)
+    msg = np.copysign(f(1), z).astype(f)
+    a = f(-1) / (sgn + z)
+    b = (x * y) * a
+    s = [msg * ((x * x) * a) + f(1), msg * b, -msg * x]
+    t = [b, (y.astype(np.float64) * (y * a).astype(np.float64) + sgn).astype(f), -y]     # fmaf
+    n = [x, y, z]
+    wo = np.stack([(s[k] * lx + t[k] * ly) + n[k] * lz for k in range(3)], 1)
+    temp = (f(1) + g * g) + (f(2) * g) * (-ct)
+    pdf = (f(1 / (4 * math.pi)) * (f(1) - g * g)) / (temp * np.sqrt(temp))
+    return wo, pdf
+
+
+def _hg_f32(g, mu):
+    """hg_eval_cos (drt_device.h) in float32, operation by operation."""
+    f = np.float32
+    g, mu = f(g), mu.astype(f)
+    temp = (f(1) + g * g) + (f(2) * g) * mu
+    return (f(1 / (4 * math.pi)) * (f(1) - g * g)) / (temp * np.sqrt(temp))
+
+
+def _hg2_f32(g1, g2, w, mu):
+    """hg2_eval_cos: a = 1 - w; p = (a * p1) + (w * p2)."""
+    f = np.float32
+    a = f(1) - f(w)
+    return a * _hg_f32(g1, mu) + f(w) * _hg_f32(g2, mu)
+
+
+def _hg2(g1, g2, w, mu):
+    return (1.0 - w) * hg_eval(g1, mu) + w * hg_eval(g2, mu)
+
+
+# ---- known answer: single scattering in a homogeneous unit box ------------------------------------------------------------------
+SIG, ALB = 1.3, 0.8
+BMIN, BMAX = np.zeros(3), np.ones(3)
+
+
+
+def _exit_dist(p, d):
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t1 = (BMIN - p) / d
+        t2 = (BMAX - p) / d
+    return np.min(np.maximum(t1, t2), axis=-1)
+
+
+def single_scatter_quadrature(phase, Le_of, o, d):
+    """Single scattering in the homogeneous unit box (SIG, ALB) seen along the ray (o, d), float64; `phase(mu)`: the phase function at
+    mu = dot(wo, wi); `Le_of(dirs float32 [n, 3]) -> [n, 3]`: the emitter's radiance.  The integral over t in the box of sigma_t e^{-sigma_t t} albedo  x  integral over the sphere of p(wo, -d) Le(wo) T(x_t, wo)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t_in = float(np.max(np.minimum((BMIN - o) / d, (BMAX - o) / d)))
+        t_out = float(np.min(np.maximum((BMIN - o) / d, (BMAX - o) / d)))
+    xt, wt = np.polynomial.legendre.leggauss(48)
+    ts = 0.5 * (t_out - t_in) * (xt + 1.0)                                  # distance travelled in the medium
+    wts = 0.5 * (t_out - t_in) * wt
+    # directions in d's frame: mu = dot(wo, d) on a tanh-stretched Gauss-Legendre rule (the phase peak), phi uniform
+    xm, wm = np.polynomial.legendre.leggauss(160)
+    k = 4.0
+    mu = np.tanh(k * xm) / np.tanh(k)
+    wmu = wm * k * (1.0 - np.tanh(k * xm) ** 2) / np.tanh(k)
+    nphi = 160
+    phi = (np.arange(nphi) + 0.5) / nphi * 2.0 * math.pi
+    s, t = coordinate_system(d[None, :])
+    sin_ = np.sqrt(np.maximum(0.0, 1.0 - mu ** 2))
+    dirs = (s[0] * (sin_[:, None, None] * np.cos(phi)[None, :, None]) + t[0] * (sin_[:, None, None] * np.sin(phi)[None, :, None])
+            + d[None, None, :] * mu[:, None, None]).reshape(-1, 3)
+    w_dir = (wmu[:, None] * np.full(nphi, 2.0 * math.pi / nphi)[None, :]).reshape(-1)
+    Le = np.asarray(Le_of(dirs.astype(np.float32)), np.float64)
+    ph = phase(-np.repeat(mu, nphi))                                   # mu_phase = dot(wo, wi) = -dot(wo, d)
+    total = np.zeros(3)
+    for ti, wti in zip(ts, wts):
+        x = o + d * (t_in + ti)
+        T = np.exp(-SIG * _exit_dist(x[None, :], dirs))
+        inner = np.sum((w_dir * ph * T)[:, None] * Le, 0)
+        total += wti * SIG * math.exp(-SIG * ti) * ALB * inner
+    return total
+
+
+def _cmp_means(a, b, k=5.0):
+    """Two mean images agree: their total within k standard errors, and at most 1 % of the pixel values outside k standard errors (the
+    per-pixel errors come from 8 renders each: a t distribution with 7 degrees of freedom has heavy tails)."""
+    (ma, sa), (mb, sb) = a, b
+    se = np.sqrt(sa ** 2 + sb ** 2)
+    z = np.abs(ma - mb) / np.maximum(se, 1e-12)
+    assert np.mean(z > k) <= 0.01, np.sort(z.reshape(-1))[-20:]
+    assert abs(float((ma - mb).sum())) <= k * float(np.sqrt((se ** 2).sum())), (float((ma - mb).sum()), float(np.sqrt((se ** 2).sum())))
+
 
 # ---- the distribution --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("g", [-0.95, -0.5, 0.0, 0.3, 0.9, 0.99])
