@@ -378,6 +378,25 @@ int drt_adam_step(void *hip_stream, float *p, const float *g, float *m, float *v
 int drt_adam_step_clamped(void *hip_stream, float *p, const float *g, float *m, float *v, uint64_t n, double beta_1, double beta_2,
                           double epsilon, double lr_t, float lo, float hi);
 
+/* Priors on a dense parameter grid p (Z,Y,X,C), float32, channels last and independent of each other, N = Z Y X C entries (no handle,
+ * no state; an extension of the reference, which has no regulariser).  With the forward differences dx = p[z,y,x+1,c] - p[z,y,x,c], dy, dz
+ * (0 where the upper index leaves the grid):
+ *   DRT_PRIOR_TV          R = (1/N) sum sqrt(eps + dx^2 + dy^2 + dz^2)       eps > 0
+ *   DRT_PRIOR_SMOOTHNESS  R = (1/N) sum (dx^2 + dy^2 + dz^2)                 (eps ignored)
+ *   DRT_PRIOR_SPARSITY    R = (1/N) sum |p|, gradient sign(p) / N with sign(0) = 0   (eps ignored)
+ * drt_grid_prior ADDS weight * dR/dp into the gradient grid g (same shape; NULL: value only) and stores weight * R as one double at
+ * `value` (DEVICE pointer; NULL: gradient only), in one pass over p (csrc/drt_priors.hip) followed by a single-workgroup sum of the
+ * per-workgroup partial sums in `scratch` (DEVICE, 8-byte aligned, at least drt_grid_prior_scratch_bytes(nz, ny, nx, nc) bytes, contents
+ * irrelevant before and after): no float atomics, the same bits on every call.  p and g must not overlap; both may be any 4-byte aligned
+ * float pointers (16-byte accesses are used when both are 16-byte aligned and nx * nc is a multiple of 4).  Refused with
+ * DRT_ERR_INVALID_ARGUMENT and a message (drt_last_error(NULL)), before any device work: a NULL or misaligned p, g and value both NULL,
+ * an extent < 1 or > 2^30 (nx * nc likewise), nc outside 1..32, an unknown kind, a non-finite weight, an eps for DRT_PRIOR_TV that
+ * is not a positive normal float (<= 0, NaN, inf, below 1.18e-38), a NULL, misaligned or too small scratch.  drt_grid_prior_scratch_bytes returns 0 for such extents. */
+enum { DRT_PRIOR_TV = 0, DRT_PRIOR_SMOOTHNESS = 1, DRT_PRIOR_SPARSITY = 2 };
+uint64_t drt_grid_prior_scratch_bytes(int32_t nz, int32_t ny, int32_t nx, int32_t nc);
+int drt_grid_prior(void *hip_stream, int32_t kind, const float *p, float *g, double *value, void *scratch, uint64_t scratch_bytes,
+                   int32_t nz, int32_t ny, int32_t nx, int32_t nc, double weight, double eps);
+
 /* Event counting (off by default; enabling selects a counting build of the kernels). */
 int drt_enable_counters(drt_handle h, int enable);
 int drt_reset_counters(drt_handle h);

@@ -1745,6 +1745,39 @@ int drt_adam_step(void *hip_stream, float *p, const float *g, float *m, float *v
     return drt::launch_adam_step(p, g, m, v, n, beta_1, beta_2, epsilon, lr_t, (hipStream_t) hip_stream) == hipSuccess ? DRT_OK : DRT_ERR_HIP;
 }
 
+uint64_t drt_grid_prior_scratch_bytes(int32_t nz, int32_t ny, int32_t nx, int32_t nc)
+{
+    return drt::grid_prior_supported(nz, ny, nx, nc) ? drt::grid_prior_partials(nz, ny, nx, nc) * sizeof(double) : 0;
+}
+
+int drt_grid_prior(void *hip_stream, int32_t kind, const float *p, float *g, double *value, void *scratch, uint64_t scratch_bytes,
+                   int32_t nz, int32_t ny, int32_t nx, int32_t nc, double weight, double eps)
+{
+    if (!p) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: null grid");
+    if (!g && !value) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: null gradient and null value: nothing to compute");
+    if (kind != DRT_PRIOR_TV && kind != DRT_PRIOR_SMOOTHNESS && kind != DRT_PRIOR_SPARSITY)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: unknown kind %d", (int) kind);
+    if (nz < 1 || ny < 1 || nx < 1)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: empty grid %d x %d x %d", (int) nz, (int) ny, (int) nx);
+    if (nc < 1 || nc > drt::kPriorMaxChannels)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: %d channels (1..%d are supported)", (int) nc, drt::kPriorMaxChannels);
+    if (!drt::grid_prior_supported(nz, ny, nx, nc))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: grid %d x %d x %d x %d is too large (an extent, or nx * nc, above 2^30)",
+                    (int) nz, (int) ny, (int) nx, (int) nc);
+    if (!std::isfinite(weight)) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: weight is not finite");
+    if (kind == DRT_PRIOR_TV && !(std::isnormal((float) eps) && eps > 0.0))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: total variation needs eps > 0, a normal float (>= 1.18e-38), got %g", eps);
+    if ((((uintptr_t) p) | ((uintptr_t) g)) & 3u) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: grids must be 4-byte aligned");
+    if (((uintptr_t) value) & 7u) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: value must be 8-byte aligned");
+    const uint64_t need = drt_grid_prior_scratch_bytes(nz, ny, nx, nc);
+    if (!scratch || (((uintptr_t) scratch) & 7u) || scratch_bytes < need)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_grid_prior: scratch must be an 8-byte aligned buffer of at least %llu bytes (got %llu)",
+                    (unsigned long long) need, (unsigned long long) scratch_bytes);
+    DRT_HIP_CHECK(nullptr, drt::launch_grid_prior(kind, p, g, value, (double *) scratch, nz, ny, nx, nc, weight, (float) eps,
+                                                  (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
 int drt_grad_support_mask(void *hip_stream, const float *sigma_t, const int32_t res[3], uint64_t sparse_offset_floats, uint32_t channels,
                           uint64_t n_blocks, uint32_t block_floats, uint32_t *bits_scratch, uint8_t *mask)
 {

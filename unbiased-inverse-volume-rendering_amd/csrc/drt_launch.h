@@ -167,6 +167,16 @@ hipError_t launch_film_loss_forward(const float *L, uint64_t n_pixels, uint32_t 
                                     float *image, float *loss, double *partials, hipStream_t stream);
 hipError_t launch_film_loss_grad(const float *image, uint64_t n_pixels, const LossRef &R, int kind, float param, const float *upstream,
                                  float *grad_image, hipStream_t stream);
+// grid priors (drt_priors.hip): total variation, smoothness and sparsity of a dense grid p (Z,Y,X,C), C <= kPriorMaxChannels.  One pass adds
+// weight * dR/dp into g (nullptr: value only) and writes one double per workgroup to `partials` (grid_prior_partials of them); with `value`
+// a second, single-workgroup launch stores weight * R there.  p and g must not overlap.  16-byte accesses when p and g are 16-byte aligned
+// and X * C is a multiple of 4, scalar ones otherwise.
+enum PriorKind : int { kPriorTV = 0, kPriorSmoothness = 1, kPriorSparsity = 2 };
+constexpr int kPriorMaxChannels = 32;
+bool grid_prior_supported(int64_t nz, int64_t ny, int64_t nx, int64_t nc);
+uint64_t grid_prior_partials(int nz, int ny, int nx, int nc);        // 0: not a grid the kernel takes
+hipError_t launch_grid_prior(int kind, const float *p, float *g, double *value, double *partials, int nz, int ny, int nx, int nc, double weight,
+                             float eps, hipStream_t stream);
 uint32_t host_alt_seed(uint32_t seed, bool sensor_flow);
 hipError_t launch_debug_eval(const Params &P, int op, const float *in, uint64_t n, float *out, hipStream_t stream);
 

@@ -440,6 +440,13 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
                                      reinterpret_cast<float *>(mm), reinterpret_cast<float *>(v), n, b1, b2, eps, lr_t, lo, hi);
         if (rc != DRT_OK) throw std::runtime_error("drt_adam_step_clamped failed (code " + std::to_string(rc) + ")");
     });
+    m.def("grid_prior_scratch_bytes", [](int32_t nz, int32_t ny, int32_t nx, int32_t nc) { return drt_grid_prior_scratch_bytes(nz, ny, nx, nc); });
+    m.def("grid_prior", [](uintptr_t stream, int32_t kind, uintptr_t p, uintptr_t g, uintptr_t value, uintptr_t scratch, uint64_t scratch_bytes,
+                           int32_t nz, int32_t ny, int32_t nx, int32_t nc, double weight, double eps) {
+        const int rc = drt_grid_prior(reinterpret_cast<void *>(stream), kind, reinterpret_cast<const float *>(p), reinterpret_cast<float *>(g),
+                                      reinterpret_cast<double *>(value), reinterpret_cast<void *>(scratch), scratch_bytes, nz, ny, nx, nc, weight, eps);
+        if (rc != DRT_OK) throw std::runtime_error(std::string("drt_grid_prior: ") + drt_last_error(nullptr));
+    });
     m.def("grad_support_mask", [](uintptr_t stream, uintptr_t sigma_t, int rx, int ry, int rz, uint64_t sparse_off, uint32_t channels,
                                   uint64_t n_blocks, uint32_t block_floats, uintptr_t bits, uintptr_t mask) {
         const int32_t res[3] = { rx, ry, rz };

@@ -20,6 +20,7 @@ from .batched import gather_ref_values, render_batch, sensors_to_device
 from .integrators import sample_tea_32
 from .loss_fused import render_batch_loss, render_loss, resolve_loss
 from .opt_config import get_int_config
+from .priors import Prior, prior_value_and_grad_
 from .render import render, render_primal
 from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, require_hg
 from .image_io import read_image, write_image
@@ -56,6 +57,8 @@ class OptimizationConfig:
     # opt-in: film, loss and its gradient fused on the device (loss_fused.render_loss / render_batch_loss); a loss or a run it
     # does not support raises at start-up
     fused_loss: bool = False
+    # opt-in: {parameter key: priors on that grid} (priors.py), added to the objective of every iteration; None: nothing extra runs
+    priors: Optional[Dict[str, List[Prior]]] = None
 
     def __post_init__(self):
         self.upsample_at = set()
@@ -397,10 +400,25 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     `shard` (a `ShardSpec` with world > 1, one process per GPU): the batch / the image pixels of every
     iteration are dealt across the ranks, the local loss is scaled to its share of the global loss and the
     gradient grids are summed with one all-reduce per backward; every rank then takes the identical
-    optimizer step."""
+    optimizer step.
+
+    `opt_config.priors` {grid key: [Prior, ...]}: after the backward pass of every iteration each prior adds its gradient into that
+    parameter's `.grad` (`priors.prior_value_and_grad_`: one kernel pass per prior, at the grid's current resolution, no host wait), and
+    its value into the iteration's entry of the returned history, which then is the objective that is minimised - on the plain, the
+    batched and the `fused_loss` route alike.  A key that is not an optimised grid the integrator reads (PHASE_G_KEY included) raises a
+    ValueError at start-up.  Sharded runs: `.grad` is the all-reduced sum when backward returns, and every rank adds the identical prior
+    gradient on its own - like the rest of distributed.py, this route is unverified on multi-GPU hardware."""
     from .distributed import ShardSpec, allreduce_scalar, local_loss_scale, verify_pending
     from . import losses as _losses
     shard = shard or ShardSpec()
+    priors = {k: list(ps) for k, ps in (opt_config.priors or {}).items()}
+    for k, ps in priors.items():
+        if k == PHASE_G_KEY or k not in scene_config.param_keys or not k.endswith('.data'):
+            raise ValueError(f'priors: "{k}" is not an optimised grid (optimised grid keys: '
+                             f'{[q for q in scene_config.param_keys if q != PHASE_G_KEY]})')
+        for p in ps:
+            if not isinstance(p, Prior):
+                raise ValueError(f'priors["{k}"] must be a list of Prior, got {p!r}')
     if opt_config.fused_loss:
         resolve_loss(opt_config.loss)                                  # (raises for a loss the fused kernels do not have)
         if shard.world > 1:
@@ -436,6 +454,9 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     integrator = int_config.create(max_depth=scene_config.max_depth)
     keys = list(scene_config.param_keys)
     grid_keys = [k for k in keys if k != PHASE_G_KEY]
+    for k in priors:
+        if k not in integrator.param_keys:
+            raise ValueError(f'priors: the integrator "{int_config.name}" does not read "{k}": the grid receives no optimizer step')
     if PHASE_G_KEY in keys:
         require_hg(scene0, "run_optimization")
         integrator._refuse_phase_grad(scene0)                           # (nerf has no phase function)
@@ -564,6 +585,14 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             # the losses normalise by the local entry count: scale to this rank's share of the global loss
             loss_value = opt_config.loss(image, ref_values) * local_loss_scale(image.shape[0], n_global)
         loss_value.backward()                                          # dr.backward (:350)
+        prior_value = None
+        for k, ps in priors.items():                                   # (sharded: .grad is the all-reduced sum here; every rank adds the same)
+            leaf = leaves[k]
+            if leaf.grad is None:
+                leaf.grad = torch.zeros_like(leaf)
+            for p in ps:
+                v = prior_value_and_grad_(leaf.detach(), leaf.grad, p)
+                prior_value = v if prior_value is None else prior_value + v
         done = opt.step({k: leaves[k].grad for k in keys if k in leaves and leaves[k].requires_grad},    # :352
                         bounds=param_bounds(scene_config, keys))
         enforce_valid_params(scene_config, opt, skip=done or ())       # :353 (what the fused step did not clamp itself)
@@ -571,7 +600,7 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         #  a float() here would make the host wait for iteration i before it can enqueue iteration i + 1.  `history` is converted once, behind
         #  the loop; a `progress` callback receives the 0-d device tensor and pays for the wait only if it looks at the value)
         total = allreduce_scalar(loss_value.detach()) if shard.partitioned else loss_value.detach()
-        history.append(total)
+        history.append(total if prior_value is None else total + prior_value)
         if shard.partitioned and opt_config.checkpoint_stride and it_i > 0 and it_i % opt_config.checkpoint_stride == 0:
             verify_pending()                                           # (no checkpoint of parameters that took an unsummed gradient)
         if writer and it_i > 0 and opt_config.checkpoint_stride and it_i % opt_config.checkpoint_stride == 0:
