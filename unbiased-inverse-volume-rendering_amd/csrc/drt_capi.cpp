@@ -77,6 +77,8 @@ struct drt_handle_s {
     unsigned long long *d_queues = nullptr;   // 8 per-XCD ray queue heads (wavefront kernel)
     DevBuf sq_cold;                           // queued supergrid tracer: adjoint path state kept in global memory (drt_sq.hip)
     DevBuf uempty;                            // per pixel: its rays cross only empty supergrid cells (build_unit_empty; queued supergrid tracer)
+    uint64_t uempty_first = 0, uempty_end = 0, uempty_version = 0;   // ... made by the primal launch over these rays of the job the path cache describes, in
+    uint32_t uempty_units = 0, uempty_spp = 0;                       //     this state of the scene: the adjoint launch over the same rays takes them as they are (0: none)
     DevBuf order;                             // ray order of the supergrid tracer's current launch (build_super_order)
     uint64_t order_first = 0, order_end = 0;  // ... made by the primal launch over these rays of the job the path cache describes:
     uint32_t order_unit = 0;                  //     the adjoint launch over the same rays takes it as it is (0: none)
@@ -520,7 +522,7 @@ int launch_coop(drt_handle h, const drt::Params &P, bool adjoint)
 }
 
 // queued tracer: flag the pixels whose rays cross only empty supergrid cells (best effort: no memory, no flags)
-int bind_unit_empty(drt_handle h, const drt::Params &P, drt::Params &Q)
+int bind_unit_empty(drt_handle h, const drt::Params &P, drt::Params &Q, bool adjoint)
 {
     const uint64_t span = P.n_rays - P.ray_first;
     // (sensor rays whose units are whole pixels: sub-batches, interleaved chunks and offsets that cut a pixel's rays get no flags)
@@ -528,11 +530,20 @@ int bind_unit_empty(drt_handle h, const drt::Params &P, drt::Params &Q)
           P.ray_offset % P.spp == 0 && P.chunk % P.spp == 0 && P.stride % P.spp == 0 && !dbg(h->debug_flags, kHookWalkEmptyPixels)))
         return DRT_OK;
     const uint32_t eunits = (uint32_t) ((span + P.spp - 1) / P.spp);
-    DRT_TRY(h->uempty.grow(h, eunits, kBestEffort));
-    if (h->uempty.p) {
+    // (adjoint launches behind the primal pass of the same job - the path cache's signature: the same rays, sensor and medium - over the same window:
+    //  the flags are the primal launch's, as bind_ray_order takes the order; anything that changed the scene since has bumped its version)
+    const bool reuse = adjoint && P.path_cache_mode == 2 && h->uempty.p && h->uempty_units == eunits && h->uempty_spp == P.spp &&
+                       h->uempty_first == P.ray_first && h->uempty_end == P.n_rays && h->uempty_version == h->scene_version;
+    if (!reuse) {
+        h->uempty_units = 0;
+        DRT_TRY(h->uempty.grow(h, eunits, kBestEffort));
+        if (!h->uempty.p) return DRT_OK;
         DRT_HIP_CHECK(h, drt::build_unit_empty(P, P.spp, eunits, h->uempty.as<uint8_t>(), h->stream));
-        Q.unit_empty = h->uempty.as<const uint8_t>(); Q.empty_unit = P.spp;
+        if (!adjoint && P.path_cache_mode == 1) {
+            h->uempty_units = eunits; h->uempty_spp = P.spp; h->uempty_first = P.ray_first; h->uempty_end = P.n_rays; h->uempty_version = h->scene_version;
+        }
     }
+    Q.unit_empty = h->uempty.as<const uint8_t>(); Q.empty_unit = P.spp;
     return DRT_OK;
 }
 
@@ -627,7 +638,7 @@ int launch_queued(drt_handle h, const drt::Params &P, bool adjoint, const Choice
         DRT_HIP_CHECK(h, drt::launch_film_backward(P.dL_pix, px, P.spp, h->dl_px.as<float>(), h->stream));
         Q.dL = h->dl_px.as<float>(); Q.dL_pix = nullptr;
     }
-    DRT_TRY(bind_unit_empty(h, P, Q));
+    DRT_TRY(bind_unit_empty(h, P, Q, adjoint));
     DRT_TRY(begin_supergrid_launch(h, P, Q, adjoint, c));
     Q.sq_cold = h->sq_cold.p;
     bool big = false;
@@ -980,6 +991,7 @@ int drt_release_scratch(drt_handle h)
     }
     h->pcache.release();
     h->pcache_sig.valid = false; h->order_valid = false; h->order_rays = 0;
+    h->uempty_units = 0;                                         // (the flags go with the job that made them)
     h->tail.release();
     h->dl_px.release();
     return DRT_OK;

@@ -1,6 +1,7 @@
 // drt_film.h -- the box film's summation order, shared by the develop kernels (drt_kernels.hip) and the loss-fused film
 // (drt_loss.hip): both must produce the same image bits, so the order is written once, here.
-//   spp <  128: one thread per (pixel, channel), samples summed in index order          (film_develop_kernel)
+//   spp <  128: one thread per (pixel, channel), samples summed in index order          (film_develop_kernel; film_develop_wide_kernel: the
+//               same order over rows staged in LDS)
 //   spp >= 128: one wave per pixel, lane l sums samples l, l + 64, ..., then a fixed-order wave reduction
 //               (film_develop_wave_kernel); the sums are valid in lane 0
 #pragma once

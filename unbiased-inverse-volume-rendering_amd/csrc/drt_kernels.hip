@@ -758,6 +758,45 @@ __global__ void __launch_bounds__(256) film_develop_kernel(const float *L, uint6
     image[t] = film_channel_sum(L, p, c, spp) * (1.0f / (float) spp);
 }
 
+// the same image bits, streamed: a workgroup stages the contiguous [pixels][spp][3] rows of `pb` pixels (a multiple of 4, or the
+// film's last pixels) in LDS with 16-byte coalesced loads, then one thread per (channel, pixel) sums its samples in index order
+// (film_channel_sum's order).  The thread-per-(pixel, channel) kernel above walks 12-byte strides: 1.5 TB/s at 32 spp.  Rows are
+// padded to an odd stride, and a wave holds consecutive pixels of one channel: its lanes read distinct banks.  L must be 16-byte aligned.
+constexpr uint32_t kFilmWideFloats = 8192;     // staged floats per workgroup (without the padding: at most 64 more)
+constexpr uint32_t kFilmWidePixels = 64;       // pixels per workgroup at most
+__global__ void __launch_bounds__(256) film_develop_wide_kernel(const float *__restrict__ L, uint64_t n_pixels, uint32_t spp, uint32_t pb,
+                                                                float *__restrict__ image)
+{
+    __shared__ float rows[kFilmWideFloats + kFilmWidePixels];
+    const uint64_t p0 = (uint64_t) blockIdx.x * pb;
+    const uint32_t np = (uint32_t) (n_pixels - p0 < (uint64_t) pb ? n_pixels - p0 : (uint64_t) pb);
+    const uint32_t rw = 3u * spp, rs = rw | 1u;                      // row width, padded row stride
+    const uint32_t nf = np * rw, n4 = nf >> 2;
+    const float *src = L + p0 * rw;                                  // (p0 * rw is a multiple of 4: pb is)
+    for (uint32_t i = threadIdx.x; i < n4; i += 256u) {
+        const float4 v = ((const float4 *) src)[i];
+        uint32_t row = (4u * i) / rw, col = 4u * i - row * rw;
+        const float e[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            rows[row * rs + col] = e[k];
+            if (++col == rw) { col = 0u; ++row; }
+        }
+    }
+    for (uint32_t f = 4u * n4 + threadIdx.x; f < nf; f += 256u) {    // (the film's last pixels: up to 3 floats)
+        const uint32_t row = f / rw;
+        rows[row * rs + (f - row * rw)] = src[f];
+    }
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < 3u * np; t += 256u) {
+        const uint32_t c = t / np, p = t - c * np;
+        const float *r = rows + p * rs + c;
+        float s = 0.0f;
+        for (uint32_t j = 0; j < spp; ++j) s += r[3u * j];
+        image[3 * (p0 + p) + c] = s * (1.0f / (float) spp);
+    }
+}
+
 // the same for many samples per pixel (the optimisation loop develops 1024 spp): one wave per pixel - lane l sums the
 // samples l, l + 64, ... (coalesced 768-byte rows), then a fixed-order wave reduction; 0.41 -> 0.1 ms for 32768 x 1024
 __global__ void __launch_bounds__(256) film_develop_wave_kernel(const float *L, uint64_t n_pixels, uint32_t spp, float *image)
@@ -780,6 +819,34 @@ __global__ void __launch_bounds__(256) film_backward_kernel(const float *grad_im
     if (t >= n_pixels * spp * 3) return;
     uint64_t i = t / 3; uint32_t c = (uint32_t)(t - i * 3);
     dL[t] = grad_image[3 * (i / spp) + c] * (1.0f / (float) spp);
+}
+
+// the same bits, 16 bytes per lane: a workgroup writes 1024 consecutive floats of dL; where they start - (pixel, sample, channel) - is
+// divided out once per workgroup, a thread's own offset costs one 32-bit division.  dL must be 16-byte aligned.
+__global__ void __launch_bounds__(256) film_backward_wide_kernel(const float *__restrict__ grad_image, uint64_t n_pixels, uint32_t spp,
+                                                                 float *__restrict__ dL)
+{
+    const uint64_t n = n_pixels * spp * 3;
+    const uint64_t t0 = (uint64_t) blockIdx.x * 1024u;              // the workgroup's first float ...
+    const uint64_t i0 = t0 / 3, pix0 = i0 / spp;                    // ... its sample and pixel
+    const uint32_t c0 = (uint32_t) (t0 - 3 * i0), j0 = (uint32_t) (i0 - pix0 * spp);
+    const uint32_t o = 4u * threadIdx.x;
+    const uint64_t t = t0 + o;
+    if (t >= n) return;
+    const uint32_t u = c0 + o, di = u / 3u;                          // samples past the workgroup's first
+    uint32_t c = u - 3u * di;
+    const uint32_t v = j0 + di, dp = v / spp;
+    uint32_t j = v - dp * spp;
+    uint64_t p = pix0 + dp;
+    const float inv = 1.0f / (float) spp;
+    float e[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        e[k] = t + k < n ? grad_image[3 * p + c] * inv : 0.0f;
+        if (++c == 3u) { c = 0u; if (++j == spp) { j = 0u; ++p; } }
+    }
+    if (t + 4 <= n) *(float4 *) (dL + t) = make_float4(e[0], e[1], e[2], e[3]);
+    else for (int k = 0; k < 4 && t + k < n; ++k) dL[t + k] = e[k];
 }
 
 // Primitive evaluation for the parity tests (tests/test_gpu_primitives.py): one
@@ -1037,6 +1104,11 @@ hipError_t launch_film_develop(const float *L, uint64_t n_pixels, uint32_t spp, 
     uint64_t n = n_pixels * 3;
     if (n == 0) return hipSuccess;
     if (spp >= kFilmWaveSpp) hipLaunchKernelGGL(film_develop_wave_kernel, dim3((unsigned)((n_pixels + 3) / 4)), dim3(256), 0, stream, L, n_pixels, spp, image);
+    else if (((uintptr_t) L & 15u) == 0) {
+        uint32_t pb = (kFilmWideFloats / (3u * spp)) & ~3u;       // (spp < kFilmWaveSpp: at least 20)
+        if (pb > kFilmWidePixels) pb = kFilmWidePixels;
+        hipLaunchKernelGGL(film_develop_wide_kernel, dim3((unsigned)((n_pixels + pb - 1) / pb)), dim3(256), 0, stream, L, n_pixels, spp, pb, image);
+    }
     else hipLaunchKernelGGL(film_develop_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, L, n_pixels, spp, image);
     return hipGetLastError();
 }
@@ -1314,7 +1386,9 @@ hipError_t launch_film_backward(const float *grad_image, uint64_t n_pixels, uint
 {
     uint64_t n = n_pixels * spp * 3;
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(film_backward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, grad_image, n_pixels, spp, dL);
+    if (((uintptr_t) dL & 15u) == 0)
+        hipLaunchKernelGGL(film_backward_wide_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, stream, grad_image, n_pixels, spp, dL);
+    else hipLaunchKernelGGL(film_backward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, grad_image, n_pixels, spp, dL);
     return hipGetLastError();
 }
 

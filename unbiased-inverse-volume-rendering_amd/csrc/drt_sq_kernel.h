@@ -122,6 +122,13 @@
 #ifndef DRT_SQ_TAIL_BLOCKS
 #define DRT_SQ_TAIL_BLOCKS 64      // workgroups of the tail launch (the partition passes of the reduction run on the other compute units)
 #endif
+#ifndef DRT_SQ_TAIL_SPREAD
+#define DRT_SQ_TAIL_SPREAD 4       // the SOLO tail launch over the whole chip (tail_mode 2): a wave takes at most its share of the workgroup's pooled records at a
+                                   // time - (records + waves - 1) / waves, at least this many - instead of whatever a queue holds (up to 64): the records then
+                                   // run in all twelve waves, each round of a wave issues the blocks of a few rays, not of every phase.  0: up to 64 (round 5)
+                                   // (headline t_primal_ms on one box, 0 / 2 / 4 / 8: 2.482 / 2.438 / 2.454 / 2.488; on another, 1 / 2 / 4: 2.470 / 2.470 / 2.473 against
+                                   // the parent's 2.519; profiles/r07_between_launches.txt)
+#endif
 constexpr int kSqTailQuads = 20;   // uint4 per pool entry: 7 (the LDS record) + 1 {queue kind} + 3 (global part a) + up to 9 (part b)
 #ifndef DRT_SQ_PROFILE
 #define DRT_SQ_PROFILE 0
@@ -407,12 +414,19 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
     // to the next ones when that one is drained: every ray is traced whatever the placement of the workgroups.  The
     // positions a workgroup has reserved (Params::sq_chunk at a time) are handed out from LDS under a lock: any wave starts rays.
     int polls = 0;
+    uint32_t tail_take = 64u;                                                  // SOLO: records a wave takes from a queue at a time (DRT_SQ_TAIL_SPREAD)
+    (void) tail_take;
     if constexpr (TAILM) {
         // tail mode (Params::tail_mode): this launch finishes the records the main launch's drained workgroups wrote to the pool - workgroup b takes
         // the entries b, b + gridDim.x, ... into free records, each into the queue it was taken from; no ray is started (the ray queues count as drained)
         {
             const uint32_t n_pool = min(*P.tail_count, P.tail_cap);
             const uint32_t n_tail = n_pool > blockIdx.x ? min((uint32_t) NRAY, (n_pool - blockIdx.x + gridDim.x - 1u) / gridDim.x) : 0u;
+            if constexpr (SOLO && DRT_SQ_TAIL_SPREAD > 0) {
+                // over the whole chip: the workgroup's records in equal shares over its waves (a function of the pool's size alone)
+                const uint32_t share = (uint32_t) __builtin_amdgcn_readfirstlane((int) ((n_tail + NWV - 1u) / NWV));
+                if (P.tail_mode == 2u) tail_take = min(64u, max(share, (uint32_t) DRT_SQ_TAIL_SPREAD));
+            }
 #pragma unroll 1
             for (uint32_t k = (uint32_t) wave; k < n_tail; k += NWV) {
                 uint32_t hq;
@@ -499,7 +513,12 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                 const int nfree = 64 - __popcll(flym);
                 if (nfree >= DRT_SQ_REFILL_MIN) {
                     uint32_t h0;
-                    const uint32_t got = sq_pop(ctl, SQ_WALK, (uint32_t) nfree, 1u, lane, h0);
+                    uint32_t want = (uint32_t) nfree;
+                    if constexpr (SOLO) {                                        // (the pooled flights too: no more than the wave's share under way)
+                        const uint32_t nfly = 64u - (uint32_t) nfree;
+                        want = nfly < tail_take ? min(want, tail_take - nfly) : 0u;
+                    }
+                    const uint32_t got = sq_pop(ctl, SQ_WALK, want, 1u, lane, h0);
                     if (got) {
                         const uint32_t frank = (uint32_t) __popcll(~flym & ((1ull << lane) - 1ull));   // my rank among the free lanes
                         if (!fly && frank < got) {
@@ -592,7 +611,9 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
 
         // ================= a heavy batch: up to 64 rays of one kind ==========================================
         uint32_t h0;
-        const uint32_t nb = sq_pop(ctl, kind, 64u, min_n, lane, h0);
+        // (SOLO: these rays run to their ends in this wave - no more than its share; free records are only retired, 64 at a time)
+        const uint32_t max_nb = (SOLO && kind != SQ_REGEN) ? tail_take : 64u;
+        const uint32_t nb = sq_pop(ctl, kind, max_nb, SOLO ? min(min_n, max_nb) : min_n, lane, h0);
         if (!nb) continue;                                                       // (another wave was faster)
         polls = 0;
         const bool act = lane < nb;
