@@ -251,6 +251,33 @@ int drt_nerf_render_forward_sh(drt_handle h, const drt_nerf_config *cfg, const f
  * of sensor rays.  Synchronises the handle's stream. */
 int drt_nerf_sh_tile_stats(drt_handle h, uint64_t *window_phases);
 
+/* The nerf integrator with two more outputs per ray (AOVs), both functions of sigma_t only:
+ *     opacity A = sum_{j+1<N} weight_j            (the weights_sum the emitter behind the medium is composited with, same order of addition)
+ *     depth   D = sum_{j+1<N} weight_j (t_in + t_b,j)   (unnormalised expected distance from the ray's origin; D / A is the mean depth)
+ * with the march, weights and last-query convention of drt_nerf_render_primal, t_in the distance from the ray's origin to the box and t_b,j
+ * the march parameter of query j.  A ray that misses the box has A = D = 0.  Every ray / pixel buffer of these calls holds FIVE interleaved
+ * floats [r, g, b, A, D]: L_out, dL, L_in, grad_image, dL_out; channels 0 - 2 are the bits of the plain calls.  The four calls mirror
+ * drt_nerf_render_primal / _backward / _backward_px / _forward: same ray, seed, offset and interleave conventions, `emission` (Z,Y,X,3), the
+ * backward calls accumulate (+=) into grad_sigma_t (Z,Y,X,1) and grad_emission (Z,Y,X,3) (A and D add to grad_sigma_t only), the forward
+ * call writes dL_out once per ray without atomics and repeats bit for bit.  Sensor rays take the LDS-window adjoint kernel of the plain call
+ * (the same window, one more term in the sigma_t splat; non-finite dL / L_in values mark both gradient grids NaN, as there); explicit ray
+ * batches the record route of the plain call (csrc/drt_nerf_aov.hip).  Refused: NULL buffers (DRT_ERR_INVALID_ARGUMENT); colour
+ * grids on their own lattice (drt_set_colour_resolution) and - adjoint calls - the debug flags the SH calls refuse (1, 2, 128, 512)
+ * (DRT_ERR_UNSUPPORTED).  There is no SH, fused (drt_fused_render_*) or loss-fused (drt_film_loss_*) variant.  The counters of
+ * drt_get_counters do not count these calls. */
+int drt_nerf_render_primal_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                               uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out);
+int drt_nerf_render_backward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
+                                 float *grad_sigma_t, float *grad_emission);
+int drt_nerf_render_backward_px_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                                    const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                    const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
+                                    float *grad_emission);
+int drt_nerf_render_forward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
+                                const float *t_emission, float *dL_out);
+
 /* BASELINE config 5: the `nerf` march and volpathsimple scattering over ONE set of grids [sigma_t, r, g, b] in one call.
  * The reference's scenes bind ONE asset as the medium's albedo and emission grid (python/scene_config.py:109-110), so the
  * colour grid given to drt_set_medium as `albedo` is both.  Per ray, the pass computes NeRFIntegrator.sample (nerf.py:47-148;
@@ -293,6 +320,12 @@ int drt_film_develop(drt_handle h, const float *L, uint64_t n_pixels, uint32_t s
 /* Its adjoint: dL[i] = grad_image[i / spp] / spp (batched.py:298-306). */
 int drt_film_backward(drt_handle h, const float *grad_image, uint64_t n_pixels, uint32_t spp,
                       float *dL);
+
+/* The two film calls for `channels` >= 1 interleaved floats per sample: L [n_pixels*spp][channels] -> image [n_pixels][channels], one thread
+ * per (pixel, channel), samples summed in index order; dL[i][c] = grad_image[i / spp][c] / spp.  channels = 3: the calls above, bit for bit.
+ * channels = 0: DRT_ERR_INVALID_ARGUMENT. */
+int drt_film_develop_n(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image);
+int drt_film_backward_n(drt_handle h, const float *grad_image, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *dL);
 
 /* Loss-fused film (opt-in; the calls above are unchanged).  The pixel-separable image losses of the reference
  * (python/losses.py: average, l1, l2, huber, mean_relative_absolute_error, mean_relative_squared_error), each

@@ -97,7 +97,7 @@ def render_batch(batch_size: int, scene: Scene, sensors=None, film_size=None,
                  pixel_format=None, sampler=None, seed: int = 0, seed_grad: int = 0, spp: int = 0,
                  spp_grad: int = 0, sensor_table: Optional[torch.Tensor] = None, shard: Optional[ShardSpec] = None):
     """Batched (ray-centric) alternative to `render` (python/batched.py:88-131).
-    -> (image [batch_size, 3], film, sampler, sensor_idx [batch_size], pixel_idx [batch_size, 2])
+    -> (image [batch_size, 3] ([batch_size, 5] with a `nerf` integrator's `aovs`), film, sampler, sensor_idx [batch_size], pixel_idx [batch_size, 2])
     (`film` / `sampler` are returned as given: the device film is stateless here).
     `shard` (world > 1): the outputs hold this rank's entries `shard.batch_range(batch_size)` only and the
     backward pass all-reduces the gradient grids; scale the local loss by `local_loss_scale`.
@@ -132,7 +132,8 @@ def render_batch(batch_size: int, scene: Scene, sensors=None, film_size=None,
 
 
 def gather_ref_values(ref_images: torch.Tensor, sensor_idx: torch.Tensor, pixel_idx: torch.Tensor) -> torch.Tensor:
-    """python/optimize.py:90-107: ref_images (n_sensors, H, W, C) -> [batch, C] at (sensor, y, x)."""
-    if ref_images.dim() != 4 or ref_images.shape[-1] not in (3, 4):
-        raise ValueError("ref_images must have shape (n_sensors, H, W, 3|4)")
+    """python/optimize.py:90-107: ref_images (n_sensors, H, W, C) -> [batch, C] at (sensor, y, x).  C: 3 or 4 as in the reference, or 5 -
+    the [r, g, b, opacity, depth] images of a `nerf` integrator with `aovs`."""
+    if ref_images.dim() != 4 or ref_images.shape[-1] not in (3, 4, 5):
+        raise ValueError("ref_images must have shape (n_sensors, H, W, 3|4|5)")
     return ref_images[sensor_idx.long(), pixel_idx[:, 1].long(), pixel_idx[:, 0].long()]

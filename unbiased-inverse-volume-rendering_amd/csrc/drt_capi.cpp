@@ -2158,6 +2158,148 @@ int drt_nerf_render_forward_sh(drt_handle h, const drt_nerf_config *cfg, const f
     return DRT_OK;
 }
 
+// ---- nerf with opacity and depth outputs (drt_nerf_aov.hip): five interleaved floats [r, g, b, A, D] per ray / pixel ---------------------------
+// the checks the four *_aov calls share, and the job.  As the SH calls: no own-lattice colour grids, none of the test hooks that route the
+// plain adjoint elsewhere, no counters
+static int nerf_aov_job(drt_handle h, const char *what, drt::Params &P, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                        const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, bool adjoint)
+{
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
+    if (!cfg || !emission) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null config / emission grid", what);
+    if (h->base.colour_own)
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the emission grid must share sigma_t's lattice (drt_set_colour_resolution gave the colour "
+                                            "grids their own: own-lattice opacity / depth outputs are not supported)", what);
+    constexpr uint32_t kUnhonoured = drt::kHookNerfRecordPath | drt::kHookAtomicGradients | drt::kHookNoGradAtomics | drt::kHookPerLaneAtomics;
+    if (adjoint && dbg(h->debug_flags, kUnhonoured))
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: debug flags 0x%x route the nerf adjoint through paths the opacity / depth kernels do not have",
+                    what, (unsigned) (h->debug_flags & kUnhonoured));
+    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    DRT_TRY(nerf_fill(h, P, cfg, emission));
+    P.counters = nullptr;
+    return DRT_OK;
+}
+
+int drt_nerf_render_primal_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                               uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
+    DeviceGuard g(h->device);
+    drt::Params P;
+    DRT_TRY(nerf_aov_job(h, "drt_nerf_render_primal_aov", P, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, false));
+    if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_primal_aov: null L_out");
+    P.L_out = L_out;
+    h->pcache_sig.valid = false;
+    TimedSpan span;
+    DRT_HIP_CHECK(h, span.begin(h, h->stream));
+    DRT_HIP_CHECK(h, drt::launch_nerf_aov(P, false, h->stream));
+    DRT_HIP_CHECK(h, span.end(0));
+    return DRT_OK;
+}
+
+// the adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given.  Sensor rays: the LDS-window kernel (lookups
+// from the four-channel copy where it can be made, as the plain call); explicit ray batches: the record path, as the plain call
+static int nerf_aov_backward(drt_handle h, drt::Params &P, const float *emission, const float *dL, const float *dL_pix, const float *L_in,
+                             float *grad_sigma_t, float *grad_emission)
+{
+    P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_emission;
+    const bool tile = drt::nerf_tile_supported(P);
+    const bool g4 = tile && ensure_grid4(h, P, emission) == DRT_OK;   // (no memory / a grid beyond the copy's index range: the separate lookups)
+    if (tile && !g4) (void) hipGetLastError();
+    if (tile) {
+        TimedSpan tracer, whole;                                     // (tracer slot and whole-pass slot: the pass is this launch)
+        DRT_HIP_CHECK(h, tracer.begin(h, h->stream));
+        DRT_HIP_CHECK(h, whole.begin(h, h->stream));
+        // a bound of t_in + t_b, a query's distance from the sensor's origin: the origin's distance to the box centre plus the half diagonal
+        // (the spawn offset of the march's origin is 1e-4 of that: the margin covers it)
+        double c2 = 0.0, d2 = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            const double c = 0.5 * ((double) P.bmin[k] + (double) P.bmax[k]) - (double) P.cam_o[k], e = 0.5 * ((double) P.bmax[k] - (double) P.bmin[k]);
+            c2 += c * c; d2 += e * e;
+        }
+        const float t_max = (float) ((std::sqrt(c2) + std::sqrt(d2)) * 1.01);
+        DRT_TRY(h->nerf_bounds.grow(h, 64, kMust));
+        DRT_HIP_CHECK(h, drt::launch_nerf_aov_tile_adjoint(P, g4, h->nerf_bounds.as<uint32_t>(), t_max, h->stream));
+        DRT_HIP_CHECK(h, tracer.end(1));
+        DRT_HIP_CHECK(h, whole.end(3));
+        return DRT_OK;
+    }
+    const uint32_t q = (uint32_t) P.nerf_queries;                 // at most one splat per query and plane
+    return run_backward(h, P, q, q, [&](drt::Params &Q) {
+        TimedSpan span;
+        DRT_HIP_CHECK(h, span.begin(h, h->stream));
+        DRT_HIP_CHECK(h, drt::launch_nerf_aov(Q, true, h->stream));
+        DRT_HIP_CHECK(h, span.end(1));
+        return (int) DRT_OK;
+    });
+}
+
+int drt_nerf_render_backward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
+                                 float *grad_sigma_t, float *grad_emission)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
+    DeviceGuard g(h->device);
+    drt::Params P;
+    DRT_TRY(nerf_aov_job(h, "drt_nerf_render_backward_aov", P, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, true));
+    if (!dL || !L_in || !grad_sigma_t || !grad_emission)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_aov: null dL / L_in / gradient buffer");
+    return nerf_aov_backward(h, P, emission, dL, nullptr, L_in, grad_sigma_t, grad_emission);
+}
+
+int drt_nerf_render_backward_px_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                                    const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                    const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
+                                    float *grad_emission)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
+    DeviceGuard g(h->device);
+    drt::Params P;
+    DRT_TRY(nerf_aov_job(h, "drt_nerf_render_backward_px_aov", P, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, true));
+    if (!L_in || !grad_sigma_t || !grad_emission)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px_aov: null L_in / gradient buffer");
+    DRT_TRY(check_px(h, "drt_nerf_render_backward_px_aov", n_rays, spp, grad_image, n_pixels));
+    return nerf_aov_backward(h, P, emission, nullptr, grad_image, L_in, grad_sigma_t, grad_emission);
+}
+
+int drt_nerf_render_forward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
+                                const float *t_emission, float *dL_out)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
+    DeviceGuard g(h->device);
+    drt::Params P;
+    DRT_TRY(nerf_aov_job(h, "drt_nerf_render_forward_aov", P, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, false));
+    if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward_aov: null dL_out");
+    forward_params(P, t_sigma_t, t_emission, dL_out);
+    DRT_HIP_CHECK(h, drt::launch_nerf_aov_fwd(P, h->stream));
+    return DRT_OK;
+}
+
+int drt_film_develop_n(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (channels == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_develop_n: channels must be > 0");
+    if (spp == 0 || (n_pixels && (!L || !image))) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_develop_n: bad argument (spp 0 or a null buffer)");
+    DeviceGuard g(h->device);
+    DRT_HIP_CHECK(h, drt::launch_film_develop_n(L, n_pixels, spp, channels, image, h->stream));
+    return DRT_OK;
+}
+
+int drt_film_backward_n(drt_handle h, const float *grad_image, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *dL)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (channels == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_backward_n: channels must be > 0");
+    if (spp == 0 || (n_pixels && (!grad_image || !dL)))
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_film_backward_n: bad argument (spp 0 or a null buffer)");
+    DeviceGuard g(h->device);
+    DRT_HIP_CHECK(h, drt::launch_film_backward_n(grad_image, n_pixels, spp, channels, dL, h->stream));
+    return DRT_OK;
+}
+
 int drt_nerf_sh_tile_stats(drt_handle h, uint64_t *window_phases)
 {
     if (!h || !window_phases) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_sh_tile_stats: null argument");

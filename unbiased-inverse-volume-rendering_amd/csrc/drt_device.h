@@ -1424,4 +1424,20 @@ __device__ __forceinline__ void load_dL(const Params &P, I i, float dL[3])
     }
 }
 
+// load_dL for the five interleaved floats [r, g, b, opacity, depth] of the AOV calls: the per-ray buffer, or the image gradient
+// of the ray's pixel times 1/spp - the product film_backward_n_kernel forms
+template <typename I>
+__device__ __forceinline__ void load_dL5(const Params &P, I i, float dL[5])
+{
+    if (P.dL_pix) {
+        const uint64_t p = (uint32_t) i / P.spp;
+        const float inv = 1.0f / (float) P.spp;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) dL[k] = P.dL_pix[5 * p + k] * inv;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) dL[k] = P.dL[5 * i + k];
+    }
+}
+
 }  // namespace drt

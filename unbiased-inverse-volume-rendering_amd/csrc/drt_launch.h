@@ -43,6 +43,16 @@ hipError_t launch_nerf_sh(const Params &P, const NerfSh &S, bool adjoint, hipStr
 hipError_t launch_nerf_sh_fwd(const Params &P, const NerfSh &S, hipStream_t stream);
 // the adjoint of sensor rays: drt_nerf_tile.hip's LDS window with 1 + 3K planes (same support predicate: nerf_tile_supported)
 hipError_t launch_nerf_sh_tile_adjoint(const Params &P, const NerfSh &S, uint32_t *bounds, hipStream_t stream);
+// drt_nerf_aov.hip: the nerf march with two more outputs per ray, opacity A = weights_sum and depth D = sum weight (t_in + t_b): five interleaved
+// floats [r, g, b, A, D] in Params::L_out / dL / dL_pix / L_in.  One ray per lane (nerf_kernel / nerf_fwd_kernel with AOV = true): the primal,
+// forward mode and the adjoint of explicit ray batches (deferred records when Params::rec_buf is set, as launch_nerf); sensor rays: the window kernel of drt_nerf_tile_kernel.h with AOV = true (bounds: 48 bytes;
+// t_max: a bound of a query's distance from the sensor's origin; same support predicate: nerf_tile_supported)
+hipError_t launch_nerf_aov(const Params &P, bool adjoint, hipStream_t stream);
+hipError_t launch_nerf_aov_fwd(const Params &P, hipStream_t stream);
+hipError_t launch_nerf_aov_tile_adjoint(const Params &P, bool g4, uint32_t *bounds, float t_max, hipStream_t stream);
+// box film with `channels` interleaved floats per sample: one thread per (pixel, channel), samples summed in index order / dL = grad / spp
+hipError_t launch_film_develop_n(const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image, hipStream_t stream);
+hipError_t launch_film_backward_n(const float *grad_image, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *dL, hipStream_t stream);
 hipError_t launch_trace_wavefront(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
 // supergrid scenes (majorant_resolution_factor > 0): lane-level state machine stepping one supergrid cell at a time, the
 // majorant grid in LDS (drt_super.hip); the adjoint needs the record streams (deferred splatting)

@@ -12,8 +12,13 @@ namespace {
 // NeRFIntegrator.sample (python/integrators/nerf.py:47-148): emission-absorption ray marching,
 // queries_per_ray jittered queries per ray, PRB-style backward.  One ray per lane; the loop is
 // regular (no divergence besides rays that miss the box).
+// AOV (drt_nerf_aov.hip instantiates it; the plain units keep AOV = false, the statements as they were): two more outputs per ray, both
+// functions of sigma_t only - opacity A = weights_sum and depth D = sum_{j+1<N} weight_j (t_in + t_b,j), t_in the distance from the ray's own
+// origin to the box.  L_out / dL / dL_pix / L_in then hold five interleaved floats [r, g, b, A, D].  A and D are linear in an "emission"
+// q_j = dA + dD (t_in + t_b,j) that no grid holds: the adjoint's sigma_t splat gains q_j (-da T) + (S / safe_a) da, S the running remainder
+// of dA A + dD D as `result` is the colour's; the emission splat is untouched.
 // ---------------------------------------------------------------------------
-template <bool ADJ, bool COUNT, bool DEFER>
+template <bool ADJ, bool COUNT, bool DEFER, bool AOV = false>
 __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
 {
     uint64_t i = P.ray_first + (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -49,7 +54,14 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
         }
         n_rays = 1;
         float result[3] = { 0.0f, 0.0f, 0.0f }, dL[3] = { 0.0f, 0.0f, 0.0f };
-        if constexpr (ADJ) {
+        float dA = 0.0f, dD = 0.0f, Srem = 0.0f, depth_sum = 0.0f, t_in = 0.0f;   // (AOV)
+        if constexpr (ADJ && AOV) {
+            float d5[5];
+            load_dL5(P, i, d5);
+            result[0] = P.L_in[5 * i]; result[1] = P.L_in[5 * i + 1]; result[2] = P.L_in[5 * i + 2];
+            dL[0] = d5[0]; dL[1] = d5[1]; dL[2] = d5[2]; dA = d5[3]; dD = d5[4];
+            Srem = dA * P.L_in[5 * i + 3] + dD * P.L_in[5 * i + 4];
+        } else if constexpr (ADJ) {
             result[0] = P.L_in[3 * i]; result[1] = P.L_in[3 * i + 1]; result[2] = P.L_in[3 * i + 2];
             load_dL(P, i, dL);
         }
@@ -57,6 +69,7 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
         Hit si = box_hit(P, o, d);                                           // nerf.py:67-79
         bool active = si.valid, escaped = !active;
         if (active) {
+            if constexpr (AOV) t_in = si.t;
             o = offset_p(si, d);
             si = box_hit(P, o, d);
             active = si.valid;
@@ -97,11 +110,17 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
                         gs += dL[k] * (em[k] * (-da * throughput) + (result[k] / safe_a) * da);
                         ge[k] = dL[k] * weight;
                     }
+                    if constexpr (AOV) {                                     // (the last query belongs to neither sum, and its da is 0)
+                        const float q = dA + dD * (t_in + t_b);
+                        if (!last) Srem = Srem - weight * q;
+                        gs += q * (-da * throughput) + (Srem / safe_a) * da;
+                    }
                     if (P.nerf_relu && !(raw > 0.0f)) gs = 0.0f;
                     splat_scatter<DEFER>(P, p, gs, ge, rec);   // colour planes = emission gradients here
                 }
                 t_a = t_b;
                 if (!last) { throughput *= safe_a; weights_sum += weight; }  // :117-120
+                if constexpr (AOV && !ADJ) { if (!last) depth_sum += weight * (t_in + t_b); }
             }
         }
         bool active_e = escaped || active;                                   // :131-146
@@ -112,7 +131,10 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
 #pragma unroll
             for (int k = 0; k < 3; ++k) result[k] += (1.0f - weights_sum) * Le[k];
         }
-        if constexpr (!ADJ) { P.L_out[3 * i] = result[0]; P.L_out[3 * i + 1] = result[1]; P.L_out[3 * i + 2] = result[2]; }
+        if constexpr (!ADJ && AOV) {
+            float *out = P.L_out + 5 * i;
+            out[0] = result[0]; out[1] = result[1]; out[2] = result[2]; out[3] = weights_sum; out[4] = depth_sum;
+        } else if constexpr (!ADJ) { P.L_out[3 * i] = result[0]; P.L_out[3 * i + 1] = result[1]; P.L_out[3 * i + 2] = result[2]; }
     }
     if constexpr (ADJ && DEFER) close_records(P, rec);
     if (COUNT) {
@@ -132,8 +154,9 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
 // looks up sigma_t' and emission' in the tangent grids (Params::g_sigma / g_albedo) through the stencils of the adjoint's splats
 // (gather_sigma_t / gather_colour, no occupancy skip), and the derivative is carried through the opacity, the throughput, the weights
 // and the emitter term behind the medium.  The relu kink takes the adjoint's convention: no derivative unless raw > 0.  One ray per
-// lane, one write per ray.
+// lane, one write per ray.  AOV: five floats per ray, dA = dweights_sum and dD = sum dweight (t_in + t_b).
 // ---------------------------------------------------------------------------
+template <bool AOV = false>
 __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P)
 {
     uint64_t i = P.ray_first + (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -158,9 +181,11 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P)
     }
     float dres[3] = { 0.0f, 0.0f, 0.0f };                                // the tangent of `result`
     float throughput = 1.0f, weights_sum = 0.0f, dthroughput = 0.0f, dweights_sum = 0.0f;
+    float ddepth_sum = 0.0f, t_in = 0.0f;                                // (AOV)
     Hit si = box_hit(P, o, d);                                           // nerf.py:67-79
     bool active = si.valid, escaped = !active;
     if (active) {
+        if constexpr (AOV) t_in = si.t;
         o = offset_p(si, d);
         si = box_hit(P, o, d);
         active = si.valid;
@@ -192,6 +217,7 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P)
                 dthroughput = dthroughput * (a + 1e-10f) + throughput * da;
                 throughput *= a + 1e-10f;
                 weights_sum += weight; dweights_sum += dweight;
+                if constexpr (AOV) ddepth_sum += dweight * (t_in + t_b);
             }
         }
     }
@@ -203,7 +229,10 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P)
 #pragma unroll
         for (int k = 0; k < 3; ++k) dres[k] += -dweights_sum * Le[k];
     }
-    P.L_out[3 * i] = dres[0]; P.L_out[3 * i + 1] = dres[1]; P.L_out[3 * i + 2] = dres[2];
+    if constexpr (AOV) {
+        float *out = P.L_out + 5 * i;
+        out[0] = dres[0]; out[1] = dres[1]; out[2] = dres[2]; out[3] = dweights_sum; out[4] = ddepth_sum;
+    } else { P.L_out[3 * i] = dres[0]; P.L_out[3 * i + 1] = dres[1]; P.L_out[3 * i + 2] = dres[2]; }
 }
 
 }  // namespace
@@ -214,7 +243,7 @@ template <bool OWN> hipError_t NerfUnit<OWN>::forward(const Params &P, hipStream
     static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
     if (P.n_rays <= P.ray_first) return hipSuccess;
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
-    hipLaunchKernelGGL(nerf_fwd_kernel, grid, block, 0, stream, P);
+    hipLaunchKernelGGL(nerf_fwd_kernel<false>, grid, block, 0, stream, P);
     return hipGetLastError();
 }
 

@@ -382,6 +382,69 @@ public:
         }
         check(rc, "drt_nerf_render_forward_sh");
     }
+    // opacity and depth outputs (drt_nerf_*_aov): five interleaved floats per ray / pixel
+    void nerf_render_primal_aov(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                uint32_t spp, uint32_t seed, uintptr_t L_out)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_primal_aov(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
+                                            seed, ptr<float>(L_out));
+        }
+        check(rc, "drt_nerf_render_primal_aov");
+    }
+    void nerf_render_backward_aov(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                  uint32_t spp, uint32_t seed, uintptr_t dL, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_emission)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_backward_aov(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
+                                              seed, ptr<const float>(dL), ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_emission));
+        }
+        check(rc, "drt_nerf_render_backward_aov");
+    }
+    void nerf_render_backward_px_aov(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                     uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
+                                     uintptr_t g_emission)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_backward_px_aov(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
+                                                 spp, seed, ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
+                                                 ptr<float>(g_emission));
+        }
+        check(rc, "drt_nerf_render_backward_px_aov");
+    }
+    void nerf_render_forward_aov(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                 uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_emission, uintptr_t dL_out)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_forward_aov(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
+                                             seed, ptr<const float>(t_sigma), ptr<const float>(t_emission), ptr<float>(dL_out));
+        }
+        check(rc, "drt_nerf_render_forward_aov");
+    }
+    void film_develop_n(uintptr_t L, uint64_t n_pixels, uint32_t spp, uint32_t channels, uintptr_t image)
+    {
+        int rc;
+        { py::gil_scoped_release nogil; rc = drt_film_develop_n(h_, ptr<const float>(L), n_pixels, spp, channels, ptr<float>(image)); }
+        check(rc, "drt_film_develop_n");
+    }
+    void film_backward_n(uintptr_t grad_image, uint64_t n_pixels, uint32_t spp, uint32_t channels, uintptr_t dL)
+    {
+        int rc;
+        { py::gil_scoped_release nogil; rc = drt_film_backward_n(h_, ptr<const float>(grad_image), n_pixels, spp, channels, ptr<float>(dL)); }
+        check(rc, "drt_film_backward_n");
+    }
     uint64_t nerf_sh_tile_phases() { uint64_t v = 0; check(drt_nerf_sh_tile_stats(h_, &v), "drt_nerf_sh_tile_stats"); return v; }
     void debug_eval(int op, uintptr_t in, uint64_t n, uintptr_t out)
     {
@@ -514,6 +577,12 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("nerf_render_backward_px_sh", &Integrator::nerf_render_backward_px_sh)
         .def("nerf_render_forward_sh", &Integrator::nerf_render_forward_sh)
         .def("nerf_sh_tile_phases", &Integrator::nerf_sh_tile_phases)
+        .def("nerf_render_primal_aov", &Integrator::nerf_render_primal_aov)
+        .def("nerf_render_backward_aov", &Integrator::nerf_render_backward_aov)
+        .def("nerf_render_backward_px_aov", &Integrator::nerf_render_backward_px_aov)
+        .def("nerf_render_forward_aov", &Integrator::nerf_render_forward_aov)
+        .def("film_develop_n", &Integrator::film_develop_n)
+        .def("film_backward_n", &Integrator::film_backward_n)
         .def("debug_eval", &Integrator::debug_eval)
         .def("set_debug_flags", &Integrator::set_debug_flags)
         .def("enable_counters", &Integrator::enable_counters)

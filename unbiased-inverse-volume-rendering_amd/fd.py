@@ -31,7 +31,7 @@ def fd_gradients(output_dir: Optional[str], scene: Scene, params: Dict[str, torc
                  spp: int = 4096, write_images: bool = False, integrator=None, seed: int = 1234, sensor: int = 0,
                  central: bool = False) -> Dict[str, np.ndarray]:
     """python/fd.py:10-77.  `params`: {key: device grid (Z, Y, X, C)} - the entries to differentiate (they replace the
-    scene's grids); `loss_fn(image)` with image (H, W, 3) -> scalar tensor.  Returns {key: array of d loss / d entry}.
+    scene's grids); `loss_fn(image)` with image (H, W, 3) ((H, W, 5) with a `nerf` integrator's aovs) -> scalar tensor.  Returns {key: array of d loss / d entry}.
     `central=True` uses (loss(+eps) - loss(-eps)) / (2 eps) instead of the reference's forward difference.
     PHASE_G_KEY: the asymmetry g of an HG medium, a 0-d tensor (the result is a 0-d array)."""
     if integrator is None:
@@ -41,9 +41,9 @@ def fd_gradients(output_dir: Optional[str], scene: Scene, params: Dict[str, torc
     s = scene.sensors[sensor]
 
     def loss_of(values, fname=None):
-        img = render_primal(_scene_with(scene, values), integrator, sensor, spp, seed).view(s.height, s.width, 3)
+        img = render_primal(_scene_with(scene, values), integrator, sensor, spp, seed).view(s.height, s.width, -1)
         if write_images and fname:
-            write_image(os.path.join(output_dir, fname), img)
+            write_image(os.path.join(output_dir, fname), img[..., :3])
         return float(loss_fn(img))
 
     values = {k: (v.detach().clone() if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float32))

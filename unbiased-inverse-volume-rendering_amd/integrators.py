@@ -515,7 +515,12 @@ class NeRFIntegrator(_DeviceIntegrator):
     `sh_degree` (default 0: the reference's direction-independent emission) in {1, 2}: view-dependent emission
     e_c(x, d) = sum_k Y_k(d) sh[x][k][c] with K = (sh_degree + 1)^2 spherical-harmonic coefficients per voxel and channel
     (`sh_basis`); `medium.emission`, its gradients and tangents are then (Z,Y,X,3K), channel index 3k + c, on sigma_t's lattice
-    (csrc/drt_nerf_sh.hip)."""
+    (csrc/drt_nerf_sh.hip).
+
+    `aovs` (default False): True adds two outputs per ray and pixel behind the colour, opacity A = sum of the march weights (the alpha the
+    emitter is composited with) and depth D = sum weight x distance from the ray's origin (D / A: the mean depth).  Every radiance, δL,
+    state, image and image-gradient tensor then has five channels [r, g, b, A, D]; the colour channels are the bits of `aovs=False`, and
+    A and D are differentiable with respect to sigma_t in both AD modes (csrc/drt_nerf_aov.hip).  Not with `sh_degree` > 0."""
 
     param_keys = (SIGMA_T_KEY, EMISSION_KEY)
     needs_albedo = False
@@ -533,6 +538,10 @@ class NeRFIntegrator(_DeviceIntegrator):
         self.activation_type = str(props.get("activation", "identity")).lower()
         self.test_hooks = bool(props.get("test_hooks", False))
         self.sh_degree = props.get("sh_degree", 0)
+        self._aovs = bool(props.get("aovs", False))
+        if self._aovs and self.sh_degree:
+            raise NotImplementedError(f"aovs=True with sh_degree {self.sh_degree}: the opacity / depth outputs have no spherical-harmonic "
+                                      "kernels; use sh_degree=0")
         self.max_depth = int(props.get("max_depth", 6))          # RBIntegrator base; unused (nerf.py)
         self.rr_depth = int(props.get("rr_depth", 5))
         if self.activation_type not in ("identity", "relu"):
@@ -548,7 +557,12 @@ class NeRFIntegrator(_DeviceIntegrator):
         self._bound_phase: Dict[int, tuple] = {}
 
     def aovs(self):
-        return []
+        return ["opacity", "depth"] if self._aovs else []
+
+    @property
+    def channels(self) -> int:
+        """Floats per ray and pixel: 3, or 5 with `aovs`."""
+        return 5 if self._aovs else 3
 
     @property
     def sh_degree(self) -> int:
@@ -558,15 +572,48 @@ class NeRFIntegrator(_DeviceIntegrator):
     def sh_degree(self, degree):
         if isinstance(degree, bool) or int(degree) != degree or int(degree) not in (0, 1, 2):
             raise ValueError(f"sh_degree must be 0 (direction-independent emission), 1 or 2, got {degree!r}")
+        if int(degree) and getattr(self, "_aovs", False):
+            raise NotImplementedError(f"sh_degree {int(degree)} with aovs=True: the opacity / depth outputs have no spherical-harmonic kernels")
         self._sh_degree = int(degree)
 
     def props(self) -> dict:
         return dict(hide_emitters=self.hide_emitters, queries_per_ray=self.queries_per_ray,
                     jittering_enabled=self.jittering_enabled, activation=self.activation_type,
-                    density_noise_std=self.density_noise_std, sh_degree=self.sh_degree)
+                    density_noise_std=self.density_noise_std, sh_degree=self.sh_degree, **({"aovs": True} if self._aovs else {}))
 
     def _native_props(self) -> dict:
         return dict(max_depth=0)
+
+    # -- film with the integrator's channel count (aovs: drt_film_*_n with five interleaved channels) -----
+    def develop(self, scene: Scene, L: torch.Tensor, spp: int) -> torch.Tensor:
+        if not self._aovs:
+            return super().develop(scene, L, spp)
+        h, dev = self._bind(scene)
+        _check(L, None, dev, "L")
+        if L.dim() != 2 or L.shape[1] != 5:
+            raise ValueError(f"develop: with aovs the radiance must have shape [n, 5], got {tuple(L.shape)}")
+        n_pix = L.shape[0] // spp
+        img = torch.empty((n_pix, 5), dtype=torch.float32, device=dev)
+        h.film_develop_n(L.data_ptr(), n_pix, int(spp), 5, img.data_ptr())
+        return img
+
+    def film_backward(self, scene: Scene, grad_image: torch.Tensor, spp: int) -> torch.Tensor:
+        if not self._aovs:
+            return super().film_backward(scene, grad_image, spp)
+        h, dev = self._bind(scene)
+        if grad_image.shape[-1] != 5:
+            raise ValueError(f"film_backward: with aovs the image gradient must have 5 channels, got {tuple(grad_image.shape)}")
+        grad_image = grad_image.contiguous().view(-1, 5)
+        _check(grad_image, None, dev, "grad_image")
+        n_pix = grad_image.shape[0]
+        dL = torch.empty((n_pix * spp, 5), dtype=torch.float32, device=dev)
+        h.film_backward_n(grad_image.data_ptr(), n_pix, int(spp), 5, dL.data_ptr())
+        return dL
+
+    def develop_loss(self, *args, **kwargs):
+        if self._aovs:
+            raise NotImplementedError("aovs=True: the loss-fused film compares three-channel images; use the plain develop -> loss chain")
+        return super().develop_loss(*args, **kwargs)
 
     def _nerf_props(self) -> dict:
         p = dict(hide_emitters=self.hide_emitters, queries_per_ray=self.queries_per_ray,
@@ -611,6 +658,8 @@ class NeRFIntegrator(_DeviceIntegrator):
         n, ro, rd = self._ray_ptrs(ray, dev)
         if self.sh_degree:
             return self._sample_sh(mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents)
+        if self._aovs:
+            return self._sample_aov(mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents)
         if mode == ADMode.Primal:
             L = torch.empty((n, 3), dtype=torch.float32, device=dev)
             h.nerf_render_primal(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp),
@@ -655,9 +704,32 @@ class NeRFIntegrator(_DeviceIntegrator):
                                  _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
         return dL, True, None
 
+    def _sample_aov(self, mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents):
+        """sample() with aovs: the drt_nerf_render_*_aov calls, five channels [r, g, b, opacity, depth] (the checks of sample() are done)."""
+        props, off, spp, seed = self._nerf_props(), int(ray.ray_offset), int(ray.spp), sampler.seed_value
+        if mode == ADMode.Primal:
+            L = torch.empty((n, 5), dtype=torch.float32, device=dev)
+            h.nerf_render_primal_aov(props, em.data_ptr(), ro, rd, n, off, spp, seed, L.data_ptr())
+            return L, True, L
+        if mode == ADMode.Backward:
+            if δL is None or state_in is None or grads is None:
+                raise ValueError("sample(Backward) needs δL, state_in and grads")
+            _check(δL, (n, 5), dev, "δL")
+            _check(state_in, (n, 5), dev, "state_in")
+            gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
+            _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
+            _check(ge, tuple(em.shape), dev, "grads[emission]")
+            h.nerf_render_backward_aov(props, em.data_ptr(), ro, rd, n, off, spp, seed, δL.data_ptr(), state_in.data_ptr(),
+                                       gs.data_ptr(), ge.data_ptr())
+            return None, True, None
+        dL = torch.empty((n, 5), dtype=torch.float32, device=dev)
+        h.nerf_render_forward_aov(props, em.data_ptr(), ro, rd, n, off, spp, seed, _ptr(tangents[SIGMA_T_KEY]),
+                                  _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
+        return dL, True, None
+
     def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
-        """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] in place of the per-ray δL
+        """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] ([.., 5] with aovs) in place of the per-ray δL
         (drt_nerf_render_backward_px)."""
         if grads.get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)
@@ -668,12 +740,15 @@ class NeRFIntegrator(_DeviceIntegrator):
         _check(em, None, dev, "emission")
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)
-        _check(grad_image, (n // int(ray.spp), 3), dev, "grad_image")
-        _check(state_in, (n, 3), dev, "state_in")
+        if not self.sh_degree and (em.dim() != 4 or em.shape[-1] != 3) and self._aovs:
+            raise ValueError(f"emission must have shape (Z,Y,X,3), got {tuple(em.shape)}")
+        C = self.channels
+        _check(grad_image, (n // int(ray.spp), C), dev, "grad_image")
+        _check(state_in, (n, C), dev, "state_in")
         gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
         _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
         _check(ge, tuple(em.shape), dev, "grads[emission]")
-        call = h.nerf_render_backward_px_sh if self.sh_degree else h.nerf_render_backward_px
+        call = h.nerf_render_backward_px_sh if self.sh_degree else h.nerf_render_backward_px_aov if self._aovs else h.nerf_render_backward_px
         call(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
              grad_image.data_ptr(), grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
 
@@ -696,6 +771,9 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
         if props.pop("sh_degree", 0):
             raise NotImplementedError("nerf+volpathsimple has no spherical-harmonic emission (sh_degree > 0): its one colour grid is "
                                       "the albedo too; use the 'nerf' integrator")
+        if props.pop("aovs", False):
+            raise NotImplementedError("nerf+volpathsimple has no opacity / depth outputs (aovs=True): its fused pass returns the two "
+                                      "integrators' colours only; use the 'nerf' integrator")
         self.queries_per_ray = int(props.pop("queries_per_ray", 128))
         self.jittering_enabled = bool(props.pop("jittering_enabled", True))
         self.activation_type = str(props.pop("activation", "identity")).lower()

@@ -306,9 +306,9 @@ def render_reference_image(scene_config: SceneConfig, to_render: Dict[int, Optio
         for pass_i in range(pass_count):
             image = render_primal(scene, integrator, s, spp_per_pass, seed + pass_i) / pass_count
             result = image if result is None else result + image
-        result = result.view(sensor.height, sensor.width, 3)
+        result = result.view(sensor.height, sensor.width, -1)        # (3 channels; 5 with a `nerf` integrator's aovs)
         if fname:
-            write_image(fname, result)
+            write_image(fname, result[..., :3])
         out[s] = result
     return out
 
@@ -359,7 +359,7 @@ def render_previews(output_dir: str, opt_config: OptimizationConfig, scene_confi
         sensor = full.sensors[s]
         fname = os.path.join(output_dir, f'opt{suffix}_{s:04d}{IMAGE_EXT}')
         image = render_primal(full, integrator, s, preview_spp, 1234)
-        write_image(fname, image.view(sensor.height, sensor.width, 3))
+        write_image(fname, image[:, :3].reshape(sensor.height, sensor.width, 3))     # (the colour channels of an aovs render)
         written.append(fname)
     return written
 
@@ -452,6 +452,11 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     scene0 = scene_config.scene
     dev = scene0.medium.sigma_t.device
     integrator = int_config.create(max_depth=scene_config.max_depth)
+    n_channels = 3 + len(integrator.aovs())                           # (a `nerf` integrator with aovs renders [r, g, b, opacity, depth])
+    if opt_config.fused_loss and n_channels != 3:
+        raise NotImplementedError("fused_loss=True with aovs: the loss-fused film is three-channel; use fused_loss=False")
+    if ref_images is not None and ref_images.shape[-1] != n_channels and not (n_channels == 3 and ref_images.shape[-1] == 4):
+        raise ValueError(f"ref_images have {ref_images.shape[-1]} channels, the integrator renders {n_channels}")
     keys = list(scene_config.param_keys)
     grid_keys = [k for k in keys if k != PHASE_G_KEY]
     for k in priors:
@@ -536,7 +541,7 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         render_previews(output_dir, opt_config, scene_config, _scene_at_g(scene, params), integrator, 'initial')   # optimize.py:320
         for s in scene_config.preview_sensors:                         # the matching references, for comparison (:321-324)
             if s in scene_config.sensors:
-                write_image(os.path.join(output_dir, f'ref_{s:04d}{IMAGE_EXT}'), ref_images[scene_config.sensors.index(s)])
+                write_image(os.path.join(output_dir, f'ref_{s:04d}{IMAGE_EXT}'), ref_images[scene_config.sensors.index(s)][..., :3])
 
     host_rng = torch.Generator().manual_seed(93483)                    # sensor choice (optimize.py:291,344)
     history = []
@@ -577,7 +582,7 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             s_i = int(torch.rand((), generator=host_rng).item() * n_sensors)
             image = render(scene, params=leaves, integrator=integrator, sensor=s_i, spp=spp_primal,
                            spp_grad=spp_grad, seed=seed, seed_grad=seed_grad, shard=shard if shard.partitioned else None)
-            ref_values = ref_images[s_i].reshape(-1, 3)
+            ref_values = ref_images[s_i].reshape(-1, ref_images.shape[-1])
             n_global = ref_values.shape[0]
             if shard.partitioned:
                 ref_values = ref_values[shard.pixel_indices(n_global, ref_values.device)]
