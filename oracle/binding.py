@@ -109,6 +109,7 @@ def lib():
         L.drto_render_textbook.argtypes = [C.POINTER(Job), fp]
         L.drto_nerf_render.argtypes = [C.POINTER(Job), C.POINTER(NerfConfig), fp, C.c_int, fp, fp, fp, dp, dp,
                                        C.POINTER(Counters)]
+        L.drto_nerf_render_ext.argtypes = [C.POINTER(Job), C.POINTER(NerfConfig), fp, C.c_int, C.c_int, C.c_int, fp, fp, fp, dp, dp]
         L.drto_expf.argtypes = [C.c_float]
         L.drto_expf.restype = C.c_float
         L.drto_batch_sample_rays.argtypes = [C.POINTER(Sensor), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -325,9 +326,14 @@ def make_nerf_config(props: dict) -> NerfConfig:
                       activation_relu=int(act == "relu"))
 
 
-def nerf_render(oscene: OracleScene, emission, props: dict, spp: int, seed: int, dL=None, L_in=None, **kw):
+def nerf_render(oscene: OracleScene, emission, props: dict, spp: int, seed: int, dL=None, L_in=None, sh_degree: int = 0,
+                aovs: bool = False, **kw):
     """NeRFIntegrator.sample over the sensor's rays.  Primal (dL None): -> (L, counters).
-    Backward: -> (grad_sigma_t, grad_emission, counters)."""
+    Backward: -> (grad_sigma_t, grad_emission, counters).
+
+    `sh_degree` 1 or 2: `emission` and its gradient are (Z,Y,X,3K) spherical-harmonic grids, K = (sh_degree + 1)^2, channel 3k + c.
+    `aovs`: L, dL and L_in have five channels [r, g, b, opacity, depth].  Either one goes through drto_nerf_render_ext, which counts
+    no events (the counters come back as None), and needs the emission grid on sigma_t's lattice."""
     cfg = Config(max_depth=0)
     job = oscene.job(cfg, spp, seed, **kw)
     ncfg = make_nerf_config(props)
@@ -336,9 +342,21 @@ def nerf_render(oscene: OracleScene, emission, props: dict, spp: int, seed: int,
     # the colour lattice of THIS call is the emission grid's (the medium's albedo, which the march does not read, may have another one)
     z, y, x = oscene.grid_shape()
     ez, ey, ex = em.shape[:3]
+    sh_degree, aovs = int(sh_degree), bool(aovs)
+    if sh_degree not in (0, 1, 2):
+        raise ValueError(f"sh_degree must be 0, 1 or 2, got {sh_degree}")
+    if sh_degree and aovs:
+        raise NotImplementedError("aovs with sh_degree > 0: the device has no such kernels")
+    if (sh_degree or aovs) and (ez, ey, ex) != (z, y, x):
+        raise NotImplementedError(f"sh_degree {sh_degree} / aovs {aovs}: the emission grid {(ez, ey, ex)} must share sigma_t's lattice {(z, y, x)}")
+    n_coef = 3 * (sh_degree + 1) ** 2
+    if em.ndim != 4 or em.shape[3] != n_coef:
+        raise ValueError(f"emission must have shape (Z,Y,X,{n_coef}), got {em.shape}")
     saved = tuple(oscene.medium.res_colour)
     oscene.medium.res_colour = (C.c_int32 * 3)(*((ex, ey, ez) if (ez, ey, ex) != (z, y, x) else (0, 0, 0)))
     try:
+        if sh_degree or aovs:
+            return _nerf_render_ext(oscene, job, ncfg, em, dL, L_in, sh_degree, aovs)
         return _nerf_render(oscene, job, ncfg, em, cnt, dL, L_in)
     finally:
         oscene.medium.res_colour = (C.c_int32 * 3)(*saved)
@@ -360,6 +378,26 @@ def _nerf_render(oscene, job, ncfg, em, cnt, dL, L_in):
     if rc:
         raise RuntimeError(f"drto_nerf_render failed: {rc}")
     return gs, ge, cnt.as_dict()
+
+
+def _nerf_render_ext(oscene, job, ncfg, em, dL, L_in, sh_degree, aovs):
+    n_ch = 5 if aovs else 3
+    if dL is None:
+        L = np.zeros((job.n_rays, n_ch), dtype=np.float32)
+        rc = lib().drto_nerf_render_ext(C.byref(job), C.byref(ncfg), _fp(em), sh_degree, int(aovs), 0, None, None, _fp(L), None, None)
+        if rc:
+            raise RuntimeError(f"drto_nerf_render_ext failed: {rc}")
+        return L, None
+    dL, L_in = _f32(dL), _f32(L_in)
+    assert dL.shape == (job.n_rays, n_ch) and L_in.shape == (job.n_rays, n_ch), (dL.shape, L_in.shape, job.n_rays, n_ch)
+    z, y, x = oscene.grid_shape()
+    gs = np.zeros((z, y, x, 1), dtype=np.float64)
+    ge = np.zeros(em.shape, dtype=np.float64)
+    rc = lib().drto_nerf_render_ext(C.byref(job), C.byref(ncfg), _fp(em), sh_degree, int(aovs), 1, _fp(dL), _fp(L_in), None,
+                                    _dp(gs), _dp(ge))
+    if rc:
+        raise RuntimeError(f"drto_nerf_render_ext failed: {rc}")
+    return gs, ge, None
 
 
 def make_sensor(s) -> Sensor:

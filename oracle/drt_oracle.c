@@ -1199,18 +1199,48 @@ typedef struct {
     int hide_emitters, queries, jitter, relu;
     const float *emission;
     double *g_emission;
+    /* the two extensions of drto_nerf_render_ext (both 0: the march of nerf.py as it stands):
+     * sh_k   K = 4 or 9: `emission` holds (Z,Y,X,3K) spherical-harmonic coefficients, channel 3k + c, and a query's emission
+     *        is em_c = sum_k Y_k(d) trilerp(plane 3k + c), folded from k = 0 upwards in float32;
+     * aov    two more outputs per ray, opacity A = weights_sum and depth D = sum over the non-last queries of
+     *        weight (t_in + t_b); dL / state_in / out then hold five floats [r, g, b, A, D]. */
+    int sh_k, aov;
 } nerf_t;
 
+/* Real spherical harmonics of degree <= 2 in the svox2 / Plenoxels order and signs, float32, every product rounded on its own. */
+static void sh_basis(int K, v3 d, float Y[9])
+{
+    Y[0] = 0.28209479177387814f;
+    Y[1] = -0.4886025119029199f * d.y;
+    Y[2] = 0.4886025119029199f * d.z;
+    Y[3] = -0.4886025119029199f * d.x;
+    if (K == 9) {
+        const float xx = d.x * d.x, yy = d.y * d.y, zz = d.z * d.z;
+        Y[4] = 1.0925484305920792f * (d.x * d.y);
+        Y[5] = -1.0925484305920792f * (d.y * d.z);
+        Y[6] = 0.31539156525252005f * ((2.0f * zz - xx) - yy);
+        Y[7] = -1.0925484305920792f * (d.x * d.z);
+        Y[8] = 0.5462742152960396f * (xx - yy);
+    }
+}
+
 static void nerf_sample(ctx_t *c, const nerf_t *nf, pcg32 *S, int adjoint, ray_t ray, const float *dL,
-                        const float *state_in, float out[3])
+                        const float *state_in, float *out)
 {
     const scene_t *sc = c->sc;
+    const int K = nf->sh_k;
     float result[3] = { 0, 0, 0 };
     if (adjoint) { result[0] = state_in[0]; result[1] = state_in[1]; result[2] = state_in[2]; }
     float throughput = 1.0f, weights_sum = 0.0f;
+    float Y[9] = { 0 };
+    if (K) sh_basis(K, ray.d, Y);                              /* once per ray */
+    /* aov: the remainder S of dA A + dD D, as `result` is the colour's */
+    float dA = 0.0f, dD = 0.0f, s_rem = 0.0f, depth_sum = 0.0f, t_in = 0.0f;
+    if (nf->aov && adjoint) { dA = dL[3]; dD = dL[4]; s_rem = dA * state_in[3] + dD * state_in[4]; }
     si_t si = box_hit(sc, ray.o, ray.d);                       /* nerf.py:67-79 */
     int active = si.valid, escaped = !active;
     if (active) {
+        t_in = si.t;                                           /* the distance from the ray's own origin to the box */
         ray.o = offset_p(&si, ray.d);
         si = box_hit(sc, ray.o, ray.d);
         active = si.valid;
@@ -1228,7 +1258,14 @@ static void nerf_sample(ctx_t *c, const nerf_t *nf, pcg32 *S, int adjoint, ray_t
             c->cnt.n_dt++;
             float sigma = nf->relu ? fmaxf(0.0f, raw) : raw;
             float em[3];
-            { stencil_t s; make_stencil_colour(sc, p, &s); for (int k = 0; k < 3; ++k) em[k] = trilerp(&s, nf->emission, 3, k); }
+            if (!K) { stencil_t s; make_stencil_colour(sc, p, &s); for (int k = 0; k < 3; ++k) em[k] = trilerp(&s, nf->emission, 3, k); }
+            else {                                            /* every plane by the plain stencil, then the fold over k */
+                stencil_t s; make_stencil_colour(sc, p, &s);
+                for (int ch = 0; ch < 3; ++ch) {
+                    em[ch] = Y[0] * trilerp(&s, nf->emission, 3 * K, ch);
+                    for (int k = 1; k < K; ++k) em[ch] += Y[k] * trilerp(&s, nf->emission, 3 * K, 3 * k + ch);
+                }
+            }
             c->cnt.n_alb++;
             int last = !(j + 1 < N);
             float a = last ? 1.0f : drt_expf(-sigma * dt);    /* :104-106 */
@@ -1244,9 +1281,15 @@ static void nerf_sample(ctx_t *c, const nerf_t *nf, pcg32 *S, int adjoint, ray_t
                     gs += dL[k] * (em[k] * (-da * throughput) + (result[k] / safe_a) * da);
                     ge[k] = dL[k] * weight;
                 }
+                if (nf->aov) {
+                    /* A and D are linear in an "emission" q_j = dA + dD (t_in + t_b) that no grid holds; the last query is in neither sum */
+                    const float q = dA + dD * (t_in + t_b);
+                    if (!last) s_rem = s_rem - weight * q;
+                    gs += q * (-da * throughput) + (s_rem / safe_a) * da;
+                }
                 if (nf->relu && !(raw > 0.0f)) gs = 0.0f;
                 splat_sigma_t(c, p, gs); c->cnt.n_sc++;
-                {
+                if (!K) {
                     stencil_t s; float w[8];
                     make_stencil_colour(sc, p, &s); stencil_weights(&s, w);
                     for (int q = 0; q < 8; ++q) for (int k = 0; k < 3; ++k) {
@@ -1257,10 +1300,19 @@ static void nerf_sample(ctx_t *c, const nerf_t *nf, pcg32 *S, int adjoint, ray_t
                         nf->g_emission[(size_t) s.idx[q] * 3 + k] += v;
                     }
                     c->cnt.n_sc_alb++;
+                } else {                                      /* dL_c weight Y_k into the 3K planes */
+                    stencil_t s; float w[8];
+                    make_stencil_colour(sc, p, &s); stencil_weights(&s, w);
+                    for (int q = 0; q < 8; ++q) for (int k = 0; k < K; ++k) for (int ch = 0; ch < 3; ++ch) {
+                        double v = (double)(w[q] * (ge[ch] * Y[k]));
+                        if (v != 0.0) shared_add(&nf->g_emission[(size_t) s.idx[q] * (size_t)(3 * K) + (size_t)(3 * k + ch)], v);
+                    }
+                    c->cnt.n_sc_alb++;
                 }
             }
             t_a = t_b;
             if (!last) { throughput *= safe_a; weights_sum += weight; }   /* :117-120 (masked by still_walking) */
+            if (nf->aov && !adjoint && !last) depth_sum += weight * (t_in + t_b);
         }
     }
     /* composite with the background emitter (:131-146; executes in both modes, :144) */
@@ -1272,21 +1324,25 @@ static void nerf_sample(ctx_t *c, const nerf_t *nf, pcg32 *S, int adjoint, ray_t
         for (int k = 0; k < 3; ++k) result[k] += (1.0f - weights_sum) * Le[k];
     }
     out[0] = result[0]; out[1] = result[1]; out[2] = result[2];
+    if (nf->aov) { out[3] = weights_sum; out[4] = depth_sum; }   /* (a ray that misses the box: A = D = 0) */
 }
 
-int drto_nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const float *emission, int adjoint,
-                     const float *dL, const float *L_in, float *L_out, double *grad_sigma_t,
-                     double *grad_emission, drto_counters *cnt)
+static int nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const float *emission, int sh_k, int aov, int adjoint,
+                       const float *dL, const float *L_in, float *L_out, double *grad_sigma_t,
+                       double *grad_emission, drto_counters *cnt)
 {
     scene_t sc;
+    const int C = aov ? 5 : 3;                                /* floats per ray of dL / L_in / L_out */
     drto_job j2 = *job;
     drto_config dummy; memset(&dummy, 0, sizeof dummy);
     if (!j2.cfg) j2.cfg = &dummy;
     if (scene_init(&sc, &j2)) return -1;
     if (!emission || !ncfg || ncfg->queries_per_ray < 2) { scene_free(&sc); return -2; }
+    if ((sh_k || aov) && sc.own_colour) { scene_free(&sc); return -3; }   /* both extensions live on sigma_t's lattice */
     nerf_t nf; nf.hide_emitters = ncfg->hide_emitters; nf.queries = ncfg->queries_per_ray;
     nf.jitter = ncfg->jittering_enabled; nf.relu = ncfg->activation_relu;
     nf.emission = emission; nf.g_emission = grad_emission;
+    nf.sh_k = sh_k; nf.aov = aov;
     drto_counters total; memset(&total, 0, sizeof total);
 #ifdef _OPENMP
     int nt = job->n_threads > 0 ? job->n_threads : omp_get_max_threads();
@@ -1302,11 +1358,11 @@ int drto_nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const fl
             pcg32 S; ray_t ray;
             job_ray(job, (uint64_t) i, &S, &ray);
             c.cnt.n_rays++;
-            float L[3];
-            if (adjoint) nerf_sample(&c, &nf, &S, 1, ray, dL + 3 * i, L_in + 3 * i, L);
+            float L[5];
+            if (adjoint) nerf_sample(&c, &nf, &S, 1, ray, dL + C * i, L_in + C * i, L);
             else {
                 nerf_sample(&c, &nf, &S, 0, ray, NULL, NULL, L);
-                L_out[3 * i] = L[0]; L_out[3 * i + 1] = L[1]; L_out[3 * i + 2] = L[2];
+                for (int k = 0; k < C; ++k) L_out[C * i + k] = L[k];
             }
         }
 #ifdef _OPENMP
@@ -1317,6 +1373,22 @@ int drto_nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const fl
     if (cnt) cnt_add(cnt, &total);
     scene_free(&sc);
     return 0;
+}
+
+int drto_nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const float *emission, int adjoint,
+                     const float *dL, const float *L_in, float *L_out, double *grad_sigma_t,
+                     double *grad_emission, drto_counters *cnt)
+{
+    return nerf_render(job, ncfg, emission, 0, 0, adjoint, dL, L_in, L_out, grad_sigma_t, grad_emission, cnt);
+}
+
+int drto_nerf_render_ext(const drto_job *job, const drto_nerf_config *ncfg, const float *emission, int sh_degree, int aovs,
+                         int adjoint, const float *dL, const float *L_in, float *L_out, double *grad_sigma_t,
+                         double *grad_emission)
+{
+    if (sh_degree < 0 || sh_degree > 2 || (sh_degree && aovs)) return -4;
+    return nerf_render(job, ncfg, emission, sh_degree ? (sh_degree + 1) * (sh_degree + 1) : 0, aovs != 0, adjoint, dL, L_in, L_out,
+                       grad_sigma_t, grad_emission, NULL);
 }
 
 /* ------------------------------------------------------------------------- */

@@ -162,6 +162,18 @@ int drto_nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const fl
                      const float *dL, const float *L_in, float *L_out, double *grad_sigma_t,
                      double *grad_emission, drto_counters *cnt);
 
+/* The same march with one of the two extensions of the nerf integrator (neither exists in the reference; DESIGN.md "Oracle"):
+ *   sh_degree 1 or 2: `emission` and grad_emission are (Z,Y,X,3K), K = (sh_degree + 1)^2, channel 3k + c: spherical-harmonic
+ *                     coefficients of a view-dependent emission em_c = sum_k Y_k(d) trilerp(plane 3k + c);
+ *   aovs != 0:        dL / L_in / L_out hold FIVE floats per ray [r, g, b, A, D], A = weights_sum, D = sum over the non-last
+ *                     queries of weight (t_in + t_b), t_in the first box hit's distance; the colour channels are
+ *                     drto_nerf_render's bits.
+ * Both zero: drto_nerf_render without counters.  Both set, or the emission grid on its own lattice (res_colour): refused
+ * (-4, -3), as the device refuses them.  Events are not counted. */
+int drto_nerf_render_ext(const drto_job *job, const drto_nerf_config *ncfg, const float *emission, int sh_degree, int aovs,
+                         int adjoint, const float *dL, const float *L_in, float *L_out, double *grad_sigma_t,
+                         double *grad_emission);
+
 /* Forward-mode derivative of sample(Primal) with respect to the Henyey-Greenstein asymmetry g, per ray: dLdg_out[n][3].  The
  * estimator of DESIGN.md "Gradient with respect to g", main path only: with S the float32 running sum of hg_score over the
  * directions the main path has sampled, every contribution c adds c (S + explicit), explicit = (2 w - 1) hg_score(mu_e) at an NEE

@@ -113,7 +113,8 @@ def _draw(uivr, seed, medium_size=False):
     spp = int(rng.choice([1, 2, 3, 4] if medium_size else [1, 2, 3, 4, 8, 16]))
     explicit = rng.random() < 0.2
     return dict(scene=uivr.Scene(medium=medium, emitter=em, sensors=[sensor]), props=props, spp=spp, seed=int(rng.integers(1, 2**31 - 1)),
-                explicit=explicit, rng=rng, centre=centre, ext=ext, variant=variant, factor=factor, shape=shape, cshape=cshape, film=(w, h), env=env)
+                explicit=explicit, rng=rng, centre=centre, ext=ext, variant=variant, factor=factor, shape=shape, cshape=cshape, film=(w, h), env=env,
+                inside=bool(inside))
 
 
 @pytest.mark.parametrize("seed", SEEDS)

@@ -1,6 +1,8 @@
 """Spherical-harmonic (view-dependent) emission of the nerf integrator on the GPU (csrc/drt_nerf_sh.hip).
 
-No new oracle is needed: the radiance is LINEAR in the emission field and the march weights depend on sigma_t only, so an SH render is a
+The C oracle restates this feature too, and tests/test_gpu_nerf_ext_fuzz.py holds these kernels to it on seeded random scenes (radiance bit-exact,
+gradients within 2e-4 max|oracle|).  The tests here need no oracle, and remain the sharpest statement of plane-wise bit equality with the plain
+path: the radiance is LINEAR in the emission field and the march weights depend on sigma_t only, so an SH render is a
 sum of plain-emission renders weighted per ray by the basis values, and the SH gradients are plain-emission gradients taken with per-ray
 scaled dL.  The plain path is bit-exact against the C oracle (tests/test_gpu_nerf.py): these identities pin the new kernels against
 verified code on spatially varying grids.  The window kernel (sensor rays) is tied to the per-lane kernels by the sensor-flow =
