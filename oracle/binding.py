@@ -147,6 +147,8 @@ def lib():
         L.drto_alt_seed.argtypes = [C.c_uint32, C.c_int]
         L.drto_alt_seed.restype = C.c_uint32
         L.drto_render_forward_g.argtypes = [C.POINTER(Job), fp, fp]
+        L.drto_render_forward.argtypes = [C.POINTER(Job), fp, fp, fp, C.c_uint32, C.c_int, dp, dp]
+        L.drto_nerf_render_forward.argtypes = [C.POINTER(Job), C.POINTER(NerfConfig), fp, C.c_int, C.c_int, fp, fp, fp, C.c_int, C.c_int, dp, dp]
         L.drto_hg_sample.argtypes = [C.c_float, C.c_float, C.c_float, fp, fp, fp, fp]
         L.drto_hg_sample.restype = None
         L.drto_hg_eval.argtypes = [C.c_float, fp, fp]
@@ -295,6 +297,44 @@ def render_forward_g(oscene: OracleScene, props: dict, spp: int, seed: int, **kw
     return dg, mag
 
 
+# one bit per kind of splat site of the adjoint (DRTO_TERM_* in drt_oracle.h)
+TERM_NEE, TERM_SCATTER, TERM_DRT, TERM_TR = 1, 2, 4, 8
+TERM_NAMES = {TERM_NEE: "NEE ratio-tracking walk", TERM_SCATTER: "delta-tracking scatter site", TERM_DRT: "DRT vertex",
+              TERM_TR: "transmittance resampling"}
+TERM_ALL = 0xffffffff
+
+
+def _tangent(t, shape, what):
+    """a tangent grid as float32 of `shape`, or None (a zero tangent)"""
+    if t is None:
+        return None
+    t = _f32(t)
+    if t.shape != tuple(shape):
+        raise ValueError(f"{what} must have shape {tuple(shape)}, got {t.shape}")
+    return t
+
+
+def render_forward(oscene: OracleScene, props: dict, spp: int, seed: int, L_in, t_sigma_t, t_albedo, term_mask: int = TERM_ALL,
+                   acc32: bool = False, **kw):
+    """Forward mode of sample() in the two grids, per ray (drto_render_forward): the adjoint of every ray run with dL = e_k, every
+    splat replaced by a gather from the tangent grids `t_sigma_t` (Z,Y,X,1) and `t_albedo` (the colour lattice, 3 channels); None is
+    a zero tangent.  `L_in`: the primal's output.  `term_mask`: TERM_* bits, a cleared bit drops that kind of splat site.
+    `acc32`: gather and accumulate in float32 (to measure a rounding bar with).
+    -> (Jt [n,3] float64, mag [n,3] float64: the same sum over absolute values)"""
+    job = oscene.job(make_config(props), spp, seed, **kw)
+    L_in = _f32(L_in)
+    assert L_in.shape == (job.n_rays, 3), (L_in.shape, job.n_rays)
+    ts = _tangent(t_sigma_t, tuple(oscene.grid_shape()) + (1,), "t_sigma_t")
+    ta = _tangent(t_albedo, tuple(oscene.colour_shape) + (3,), "t_albedo")
+    jt = np.zeros((job.n_rays, 3), dtype=np.float64)
+    mag = np.zeros((job.n_rays, 3), dtype=np.float64)
+    rc = lib().drto_render_forward(C.byref(job), _fp(L_in), _fp(ts) if ts is not None else None, _fp(ta) if ta is not None else None,
+                                   int(term_mask) & 0xffffffff, int(bool(acc32)), _dp(jt), _dp(mag))
+    if rc:
+        raise RuntimeError(f"drto_render_forward failed: {rc}")
+    return jt, mag
+
+
 def h1_step(oscene: OracleScene, props: dict, spp: int, seed: int, **kw):
     """One primal -> dL -> adjoint step with loss mean((img-0.5)^2).
     -> dict(image, loss, grad_sigma_t, grad_albedo, counters, L)"""
@@ -327,13 +367,18 @@ def make_nerf_config(props: dict) -> NerfConfig:
 
 
 def nerf_render(oscene: OracleScene, emission, props: dict, spp: int, seed: int, dL=None, L_in=None, sh_degree: int = 0,
-                aovs: bool = False, **kw):
+                aovs: bool = False, tangents=None, acc32: bool = False, transposed: bool = False, **kw):
     """NeRFIntegrator.sample over the sensor's rays.  Primal (dL None): -> (L, counters).
     Backward: -> (grad_sigma_t, grad_emission, counters).
 
     `sh_degree` 1 or 2: `emission` and its gradient are (Z,Y,X,3K) spherical-harmonic grids, K = (sh_degree + 1)^2, channel 3k + c.
     `aovs`: L, dL and L_in have five channels [r, g, b, opacity, depth].  Either one goes through drto_nerf_render_ext, which counts
-    no events (the counters come back as None), and needs the emission grid on sigma_t's lattice."""
+    no events (the counters come back as None), and needs the emission grid on sigma_t's lattice.
+
+    Forward (`tangents` = (t_sigma_t, t_emission), either may be None = zero; takes no dL): -> (Jt, mag), float64 of the shape of L,
+    the per-ray tangents of every output channel and the sum of their terms' absolute values (drto_nerf_render_forward): dual numbers
+    through the float32 march, or with `transposed` the adjoint of every ray with dL = e_k and state_in = L_in, its splats turned into
+    gathers.  `acc32`: gathered and accumulated in float32."""
     cfg = Config(max_depth=0)
     job = oscene.job(cfg, spp, seed, **kw)
     ncfg = make_nerf_config(props)
@@ -355,6 +400,10 @@ def nerf_render(oscene: OracleScene, emission, props: dict, spp: int, seed: int,
     saved = tuple(oscene.medium.res_colour)
     oscene.medium.res_colour = (C.c_int32 * 3)(*((ex, ey, ez) if (ez, ey, ex) != (z, y, x) else (0, 0, 0)))
     try:
+        if tangents is not None:
+            if dL is not None or (transposed and L_in is None):
+                raise ValueError("forward mode takes no dL, and its transposed form needs L_in")
+            return _nerf_render_forward(oscene, job, ncfg, em, L_in, tangents, sh_degree, aovs, acc32, transposed)
         if sh_degree or aovs:
             return _nerf_render_ext(oscene, job, ncfg, em, dL, L_in, sh_degree, aovs)
         return _nerf_render(oscene, job, ncfg, em, cnt, dL, L_in)
@@ -378,6 +427,23 @@ def _nerf_render(oscene, job, ncfg, em, cnt, dL, L_in):
     if rc:
         raise RuntimeError(f"drto_nerf_render failed: {rc}")
     return gs, ge, cnt.as_dict()
+
+
+def _nerf_render_forward(oscene, job, ncfg, em, L_in, tangents, sh_degree, aovs, acc32, transposed):
+    n_ch = 5 if aovs else 3
+    if L_in is not None:
+        L_in = _f32(L_in)
+        assert L_in.shape == (job.n_rays, n_ch), (L_in.shape, job.n_rays, n_ch)
+    ts = _tangent(tangents[0], tuple(oscene.grid_shape()) + (1,), "t_sigma_t")
+    te = _tangent(tangents[1], em.shape, "t_emission")
+    jt = np.zeros((job.n_rays, n_ch), dtype=np.float64)
+    mag = np.zeros((job.n_rays, n_ch), dtype=np.float64)
+    rc = lib().drto_nerf_render_forward(C.byref(job), C.byref(ncfg), _fp(em), sh_degree, int(aovs), _fp(L_in) if L_in is not None else None,
+                                        _fp(ts) if ts is not None else None, _fp(te) if te is not None else None,
+                                        int(bool(acc32)), int(bool(transposed)), _dp(jt), _dp(mag))
+    if rc:
+        raise RuntimeError(f"drto_nerf_render_forward failed: {rc}")
+    return jt, mag
 
 
 def _nerf_render_ext(oscene, job, ncfg, em, dL, L_in, sh_degree, aovs):

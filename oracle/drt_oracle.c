@@ -529,7 +529,26 @@ typedef struct {
     uint32_t gcache_mask;
     struct gbucket *gbin;         /* job->grad_cache_log2 == -1 (timed CPU-baseline leg): this thread's splat records by z layer, see run_job */
     struct gfwd *gf;              /* drto_render_forward_g: the current ray's forward-mode accumulators (NULL otherwise) */
+    struct tfwd *tf;              /* drto_render_forward / drto_nerf_render_forward: tangent mode, the current ray's accumulators (NULL otherwise) */
 } ctx_t;
+
+/* Forward mode in the grids, per ray (DESIGN.md "Oracle", forward restatement).  The adjoint is linear in dL and no branch or draw
+ * depends on dL, so the tangent of channel k of a ray is its adjoint run with dL = e_k in which every splat GATHERS from the tangent
+ * grids instead: a splat of the float32 corner values v_q = w_q * g into voxels idx_q adds sum_q (double) v_q * t[idx_q] to `jt` -
+ * the very float32 terms the adjoint adds to the gradient grids, summed in double in path order.  `mag`: the same sum over absolute
+ * values, the scale rounding is judged against.  `jt32`: the float32 rendition a kernel can at best achieve - the tangent grid
+ * gathered by the float32 trilinear lookup, times the float32 splat value, accumulated in float32 in path order (acc32).
+ * `kind` names the splat site the adjoint is at (DRTO_TERM_*); a kind whose bit is cleared in `mask` contributes nothing. */
+typedef struct tfwd {
+    const float *t_sigma, *t_colour;  /* NULL: a zero tangent */
+    int colour_stride;                /* channels per voxel of t_colour: 3, or 3K with spherical harmonics */
+    uint32_t mask, kind;
+    double jt, mag;
+    float jt32;
+    /* g_abs >= 0 (the nerf march sets it ahead of its sigma_t splat, whose value is a SUM of products of either sign): what that
+     * value becomes with every factor replaced by its absolute value, which `mag` then takes in place of |g|.  < 0: |g| */
+    float g_abs;
+} tfwd_t;
 
 /* Forward-mode derivative with respect to the HG asymmetry g of ONE ray, main path only (DESIGN.md "Gradient with respect to g"):
  * S = running float32 sum of the scores of the sampled directions; every contribution c adds c (S + explicit term) to tg.
@@ -645,10 +664,48 @@ static void gcache_flush(ctx_t *c)
     for (uint32_t i = 0; i <= c->gcache_mask; ++i) { gcache_evict(c, &c->gcache[i]); c->gcache[i].tag = 0xffffffffu; }
 }
 
+/* tangent mode of the two splats: gather, touch no grid, no cache and no bucket (see tfwd_t) */
+static void tfwd_sigma_t(ctx_t *c, v3 p, float g)
+{
+    tfwd_t *tf = c->tf;
+    if (!(tf->mask & tf->kind) || !tf->t_sigma) { tf->g_abs = -1.0f; return; }
+    stencil_t s; float w[8];
+    make_stencil(c->sc, p, &s);
+    stencil_weights(&s, w);
+    const float gs = g * c->sc->scale;
+    const float ga = tf->g_abs >= 0.0f ? tf->g_abs * fabsf(c->sc->scale) : fabsf(gs);
+    tf->g_abs = -1.0f;
+    for (int k = 0; k < 8; ++k) {
+        const double v = (double)(w[k] * gs), t = (double) tf->t_sigma[s.idx[k]];
+        tf->jt += v * t; tf->mag += fabs((double)(w[k] * ga)) * fabs(t);
+    }
+    tf->jt32 += gs * trilerp(&s, tf->t_sigma, 1, 0);
+}
+/* colour lattice: value g[ch] * y into channel ch_base + ch of a voxel of `colour_stride` channels (y = 1, ch_base = 0: albedo and the
+ * plain emission - a product by 1 is exact; y = Y_k, ch_base = 3k: plane k of a spherical-harmonic emission) */
+static void tfwd_colour(ctx_t *c, v3 p, const float g[3], float y, int ch_base)
+{
+    tfwd_t *tf = c->tf;
+    if (!(tf->mask & tf->kind) || !tf->t_colour) return;
+    stencil_t s; float w[8];
+    make_stencil_colour(c->sc, p, &s);
+    stencil_weights(&s, w);
+    const int st = tf->colour_stride;
+    for (int ch = 0; ch < 3; ++ch) {
+        const float gy = g[ch] * y;
+        for (int k = 0; k < 8; ++k) {
+            const double v = (double)(w[k] * gy), t = (double) tf->t_colour[(size_t) s.idx[k] * st + ch_base + ch];
+            tf->jt += v * t; tf->mag += fabs(v) * fabs(t);
+        }
+        tf->jt32 += gy * trilerp(&s, tf->t_colour, st, ch_base + ch);
+    }
+}
+
 /* reverse-mode of the trilinear gather = 8-corner scatter_reduce(Add) (E3/E9) */
 static inline void splat_sigma_t(ctx_t *c, v3 p, float g)
 {
     stencil_t s; float w[8];
+    if (c->tf) { tfwd_sigma_t(c, p, g); return; }
     if (c->gbin) {                                           /* binned mode: the record, by its base corner's z layer */
         int z0, z1; float w0, w1;
         axis_setup(p.z, c->sc->bmin.z, c->sc->inv_ext.z, c->sc->rz, &z0, &z1, &w0, &w1);
@@ -667,6 +724,7 @@ static inline void splat_sigma_t(ctx_t *c, v3 p, float g)
 static inline void splat_albedo(ctx_t *c, v3 p, const float g[3])
 {
     stencil_t s; float w[8];
+    if (c->tf) { tfwd_colour(c, p, g, 1.0f, 0); return; }
     if (c->gbin) {
         int z0, z1; float w0, w1;
         axis_setup(p.z, c->sc->bmin.z, c->sc->inv_ext.z, c->sc->crz, &z0, &z1, &w0, &w1);
@@ -824,6 +882,7 @@ static float estimate_transmittance(ctx_t *c, v3 o, v3 d, float tmax, pcg32 *S, 
         if (adj && tr > 0.0f) {                          /* :487-492 */
             float a = (adj[0] + adj[1]) + adj[2];
             c->cnt.n_rt_adj++;
+            if (c->tf) c->tf->kind = DRTO_TERM_NEE;
             splat_sigma_t(c, p, -(a * imaj) / tr);
         }
         T *= tr;                                         /* :495 */
@@ -1010,6 +1069,7 @@ static void drt_backprop(ctx_t *c, pcg32 *A, const ray_t *ray, const si_t *si, i
         gs += a * alb[k];
         ga[k] = a * sig;
     }
+    if (c->tf) c->tf->kind = DRTO_TERM_DRT;
     splat_sigma_t(c, p, gs); c->cnt.n_sc++;              /* :577-581 */
     splat_albedo(c, p, ga);  c->cnt.n_sc_alb++;
 }
@@ -1020,6 +1080,7 @@ static void backprop_transmittance(ctx_t *c, pcg32 *A, const ray_t *ray, float i
 {
     float adjw = (dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2];
     float g = -(adjw * (interval / 4.0f));               /* contribs -= sigma_t; inv_pdf = interval/n */
+    if (c->tf) c->tf->kind = DRTO_TERM_TR;
     for (int j = 0; j < 4; ++j) {
         float t = next_1d(A) * interval;                 /* :595 */
         splat_sigma_t(c, ray_at(ray->o, ray->d, t), g);
@@ -1116,6 +1177,7 @@ static void drt_sample(ctx_t *c, pcg32 *S, int adjoint, ray_t ray, const float *
                     gs += a * albedo[k];
                     ga[k] = a * mei.sigma_t;
                 }
+                if (c->tf) c->tf->kind = DRTO_TERM_SCATTER;
                 splat_sigma_t(c, mei.p, gs); c->cnt.n_sc++;
                 splat_albedo(c, mei.p, ga);  c->cnt.n_sc_alb++;
             }
@@ -1237,6 +1299,13 @@ static void nerf_sample(ctx_t *c, const nerf_t *nf, pcg32 *S, int adjoint, ray_t
     /* aov: the remainder S of dA A + dD D, as `result` is the colour's */
     float dA = 0.0f, dD = 0.0f, s_rem = 0.0f, depth_sum = 0.0f, t_in = 0.0f;
     if (nf->aov && adjoint) { dA = dL[3]; dD = dL[4]; s_rem = dA * state_in[3] + dD * state_in[4]; }
+    /* tangent mode: `result` and s_rem are remainders, state_in minus what has been marched - the scale of their rounding is the sum
+     * of the absolute values of what went into them (tfwd_t::g_abs) */
+    float r_abs[3] = { 0, 0, 0 }, s_abs = 0.0f;
+    if (c->tf) {
+        for (int k = 0; k < 3; ++k) r_abs[k] = fabsf(state_in[k]);
+        if (nf->aov) s_abs = fabsf(dA * state_in[3]) + fabsf(dD * state_in[4]);
+    }
     si_t si = box_hit(sc, ray.o, ray.d);                       /* nerf.py:67-79 */
     int active = si.valid, escaped = !active;
     if (active) {
@@ -1288,8 +1357,24 @@ static void nerf_sample(ctx_t *c, const nerf_t *nf, pcg32 *S, int adjoint, ray_t
                     gs += q * (-da * throughput) + (s_rem / safe_a) * da;
                 }
                 if (nf->relu && !(raw > 0.0f)) gs = 0.0f;
+                if (c->tf) {                                  /* gs with every factor replaced by its absolute value (tfwd_t::g_abs) */
+                    float m = 0.0f;
+                    for (int k = 0; k < 3; ++k) {
+                        r_abs[k] += fabsf(weight * em[k]);
+                        m += fabsf(dL[k]) * (fabsf(em[k]) * fabsf(da * throughput) + fabsf(r_abs[k] / safe_a) * fabsf(da));
+                    }
+                    if (nf->aov) {
+                        const float qa = fabsf(dA) + fabsf(dD * (t_in + t_b));
+                        if (!last) s_abs += fabsf(weight) * qa;
+                        m += qa * fabsf(da * throughput) + fabsf(s_abs / safe_a) * fabsf(da);
+                    }
+                    c->tf->g_abs = (nf->relu && !(raw > 0.0f)) ? 0.0f : m;
+                }
                 splat_sigma_t(c, p, gs); c->cnt.n_sc++;
-                if (!K) {
+                if (c->tf) {                                  /* tangent mode: the two emission splats below as gathers */
+                    if (!K) tfwd_colour(c, p, ge, 1.0f, 0);
+                    else for (int k = 0; k < K; ++k) tfwd_colour(c, p, ge, Y[k], 3 * k);
+                } else if (!K) {
                     stencil_t s; float w[8];
                     make_stencil_colour(sc, p, &s); stencil_weights(&s, w);
                     for (int q = 0; q < 8; ++q) for (int k = 0; k < 3; ++k) {
@@ -1327,9 +1412,120 @@ static void nerf_sample(ctx_t *c, const nerf_t *nf, pcg32 *S, int adjoint, ray_t
     if (nf->aov) { out[3] = weights_sum; out[4] = depth_sum; }   /* (a ray that misses the box: A = D = 0) */
 }
 
+/* tangent mode of a nerf job (drto_nerf_render_forward).  transposed: one adjoint pass per output channel with dL = e_k, see tfwd_t;
+ * otherwise nerf_sample_dual */
+typedef struct { const float *t_sigma, *t_emission; int acc32, transposed; double *jt, *mag; } nerf_fwd_t;
+
+/* sum_q w_q t[idx_q * stride + ch] over a stencil, in double (weights as the exact products of the float32 axis weights); *m: the same
+ * over absolute values.  acc32: the float32 trilinear lookup */
+static double gather_t(const stencil_t *s, const float *t, int stride, int ch, int acc32, double *m)
+{
+    const double wx[2] = { s->wx0, s->wx1 }, wy[2] = { s->wy0, s->wy1 }, wz[2] = { s->wz0, s->wz1 };
+    double v = 0.0, a = 0.0;
+    for (int q = 0; q < 8; ++q) {
+        const double w = (wz[q >> 2] * wy[(q >> 1) & 1]) * wx[q & 1], x = (double) t[(size_t) s->idx[q] * stride + ch];
+        v += w * x; a += fabs(w) * fabs(x);
+    }
+    *m = a;
+    return acc32 ? (double) trilerp(s, t, stride, ch) : v;
+}
+
+/* Forward mode of the nerf march by dual numbers: the float32 march of nerf_sample(Primal), statement by statement, and beside every
+ * float32 value that depends on the grids its derivative along (t_sigma, t_emission) - the derivative of that statement with the
+ * float32 values as they are, carried in double (acc32: every operation rounded to float32, what a kernel can at best do).  out[C]: the
+ * tangents of the C = 3 (5 with aov: A and D) outputs; mag[C]: the same recurrences with every factor replaced by its absolute value.
+ * This, not the transposed adjoint, is what the forward kernels are held to: the adjoint's running remainder `result` = state_in - what
+ * has been marched inherits the cancellation of the float32 primal's (1 - weights_sum) Le on an opaque ray - an error of 2^-24 / (1 - A)
+ * of the term - which a derivative that never forms the remainder does not have (tests/test_oracle_forward.py pins both against a
+ * float64 jvp). */
+#define DRTO_R32(x) (acc32 ? (double)(float)(x) : (double)(x))
+static void nerf_sample_dual(ctx_t *c, const nerf_t *nf, pcg32 *S, ray_t ray, const float *t_sigma, const float *t_em, int acc32,
+                             double *out, double *mag)
+{
+    const scene_t *sc = c->sc;
+    const int K = nf->sh_k, C = nf->aov ? 5 : 3, stride = K ? 3 * K : 3;
+    for (int k = 0; k < C; ++k) out[k] = mag[k] = 0.0;
+    float throughput = 1.0f, weights_sum = 0.0f, t_in = 0.0f;
+    double dT = 0.0, mT = 0.0, dA = 0.0, mA = 0.0, dD = 0.0, mD = 0.0;
+    float Y[9] = { 0 };
+    if (K) sh_basis(K, ray.d, Y);
+    si_t si = box_hit(sc, ray.o, ray.d);
+    int active = si.valid, escaped = !active;
+    if (active) {
+        t_in = si.t;
+        ray.o = offset_p(&si, ray.d);
+        si = box_hit(sc, ray.o, ray.d);
+        active = si.valid;
+    }
+    if (active) {
+        const int N = nf->queries;
+        float step = nf->jitter ? (si.t - 0.0f) / (float) N : (si.t - 0.0f) / (float)(N - 1);
+        float t_a = 0.0f;
+        float jit = next_1d(S);
+        for (int j = 0; j < N; ++j) {
+            float t_b = nf->jitter ? step * ((float)(j + 1) + jit) : step * (float)(j + 1);
+            float dt = t_b - t_a;
+            v3 p = ray_at(ray.o, ray.d, t_b);
+            float raw = eval_sigma_t(sc, p);
+            float sigma = nf->relu ? fmaxf(0.0f, raw) : raw;
+            double ds = 0.0, mds = 0.0;                       /* d sigma: scale * trilerp(t_sigma), 0 where the relu is flat */
+            if (t_sigma && !(nf->relu && !(raw > 0.0f))) {
+                stencil_t s; make_stencil(sc, p, &s);
+                ds = DRTO_R32(gather_t(&s, t_sigma, 1, 0, acc32, &mds) * (double) sc->scale);
+                mds *= fabs((double) sc->scale);
+            }
+            float em[3];
+            double dem[3] = { 0, 0, 0 }, mdem[3] = { 0, 0, 0 };
+            stencil_t cs; make_stencil_colour(sc, p, &cs);
+            if (!K) for (int k = 0; k < 3; ++k) em[k] = trilerp(&cs, nf->emission, 3, k);
+            else for (int ch = 0; ch < 3; ++ch) {
+                em[ch] = Y[0] * trilerp(&cs, nf->emission, 3 * K, ch);
+                for (int k = 1; k < K; ++k) em[ch] += Y[k] * trilerp(&cs, nf->emission, 3 * K, 3 * k + ch);
+            }
+            if (t_em) for (int ch = 0; ch < 3; ++ch) {
+                if (!K) dem[ch] = gather_t(&cs, t_em, stride, ch, acc32, &mdem[ch]);
+                else for (int k = 0; k < K; ++k) {
+                    double m;
+                    const double g = gather_t(&cs, t_em, stride, 3 * k + ch, acc32, &m);
+                    dem[ch] = DRTO_R32(dem[ch] + DRTO_R32((double) Y[k] * g));
+                    mdem[ch] += fabs((double) Y[k]) * m;
+                }
+            }
+            int last = !(j + 1 < N);
+            float a = last ? 1.0f : drt_expf(-sigma * dt);
+            float weight = (1.0f - a) * throughput;
+            float safe_a = a + 1e-10f;
+            const double da = last ? 0.0 : DRTO_R32(DRTO_R32(-(double) dt * (double) a) * ds);
+            const double mda = last ? 0.0 : fabs((double) dt * (double) a) * mds;
+            const double dw = DRTO_R32(DRTO_R32((double)(1.0f - a) * dT) - DRTO_R32(da * (double) throughput));
+            const double mdw = fabs((double)(1.0f - a)) * mT + mda * fabs((double) throughput);
+            for (int k = 0; k < 3; ++k) {
+                out[k] = DRTO_R32(out[k] + DRTO_R32(DRTO_R32(dw * (double) em[k]) + DRTO_R32((double) weight * dem[k])));
+                mag[k] += mdw * fabs((double) em[k]) + fabs((double) weight) * mdem[k];
+            }
+            t_a = t_b;
+            if (!last) {
+                dT = DRTO_R32(DRTO_R32(dT * (double) safe_a) + DRTO_R32((double) throughput * da));
+                mT = mT * fabs((double) safe_a) + fabs((double) throughput) * mda;
+                throughput *= safe_a; weights_sum += weight;
+                dA = DRTO_R32(dA + dw); mA += mdw;
+                if (nf->aov) { dD = DRTO_R32(dD + DRTO_R32(dw * (double)(t_in + t_b))); mD += mdw * fabs((double)(t_in + t_b)); }
+            }
+        }
+    }
+    int active_e = escaped || active;
+    if (nf->hide_emitters) active_e = active_e && (weights_sum > 0.0f);
+    if (active_e) {
+        float Le[3] = { sc->Le[0], sc->Le[1], sc->Le[2] };
+        if (sc->env.pix) envmap_eval(&sc->env, ray.d, Le);
+        for (int k = 0; k < 3; ++k) { out[k] = DRTO_R32(out[k] - DRTO_R32(dA * (double) Le[k])); mag[k] += mA * fabs((double) Le[k]); }
+    }
+    if (nf->aov) { out[3] = dA; mag[3] = mA; out[4] = dD; mag[4] = mD; }
+}
+
 static int nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const float *emission, int sh_k, int aov, int adjoint,
                        const float *dL, const float *L_in, float *L_out, double *grad_sigma_t,
-                       double *grad_emission, drto_counters *cnt)
+                       double *grad_emission, drto_counters *cnt, const nerf_fwd_t *fw)
 {
     scene_t sc;
     const int C = aov ? 5 : 3;                                /* floats per ray of dL / L_in / L_out */
@@ -1359,7 +1555,22 @@ static int nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const 
             job_ray(job, (uint64_t) i, &S, &ray);
             c.cnt.n_rays++;
             float L[5];
-            if (adjoint) nerf_sample(&c, &nf, &S, 1, ray, dL + C * i, L_in + C * i, L);
+            if (fw && !fw->transposed) nerf_sample_dual(&c, &nf, &S, ray, fw->t_sigma, fw->t_emission, fw->acc32, fw->jt + C * i, fw->mag + C * i);
+            else if (fw) {
+                for (int k = 0; k < C; ++k) {
+                    tfwd_t tf; memset(&tf, 0, sizeof tf);
+                    tf.t_sigma = fw->t_sigma; tf.t_colour = fw->t_emission; tf.colour_stride = sh_k ? 3 * sh_k : 3;
+                    tf.mask = tf.kind = ~0u; tf.g_abs = -1.0f;
+                    float e[5] = { 0, 0, 0, 0, 0 }; e[k] = 1.0f;
+                    job_ray(job, (uint64_t) i, &S, &ray);     /* every pass replays the ray's own stream */
+                    c.tf = &tf;
+                    nerf_sample(&c, &nf, &S, 1, ray, e, L_in + C * i, L);
+                    c.tf = NULL;
+                    fw->jt[C * i + k] = fw->acc32 ? (double) tf.jt32 : tf.jt;
+                    fw->mag[C * i + k] = tf.mag;
+                }
+            }
+            else if (adjoint) nerf_sample(&c, &nf, &S, 1, ray, dL + C * i, L_in + C * i, L);
             else {
                 nerf_sample(&c, &nf, &S, 0, ray, NULL, NULL, L);
                 for (int k = 0; k < C; ++k) L_out[C * i + k] = L[k];
@@ -1379,7 +1590,7 @@ int drto_nerf_render(const drto_job *job, const drto_nerf_config *ncfg, const fl
                      const float *dL, const float *L_in, float *L_out, double *grad_sigma_t,
                      double *grad_emission, drto_counters *cnt)
 {
-    return nerf_render(job, ncfg, emission, 0, 0, adjoint, dL, L_in, L_out, grad_sigma_t, grad_emission, cnt);
+    return nerf_render(job, ncfg, emission, 0, 0, adjoint, dL, L_in, L_out, grad_sigma_t, grad_emission, cnt, NULL);
 }
 
 int drto_nerf_render_ext(const drto_job *job, const drto_nerf_config *ncfg, const float *emission, int sh_degree, int aovs,
@@ -1388,7 +1599,19 @@ int drto_nerf_render_ext(const drto_job *job, const drto_nerf_config *ncfg, cons
 {
     if (sh_degree < 0 || sh_degree > 2 || (sh_degree && aovs)) return -4;
     return nerf_render(job, ncfg, emission, sh_degree ? (sh_degree + 1) * (sh_degree + 1) : 0, aovs != 0, adjoint, dL, L_in, L_out,
-                       grad_sigma_t, grad_emission, NULL);
+                       grad_sigma_t, grad_emission, NULL, NULL);
+}
+
+/* Forward mode of the nerf march in its grids, per ray and channel (3, or 5 with aovs): nerf_sample_dual, or the transposed adjoint (tfwd_t) */
+int drto_nerf_render_forward(const drto_job *job, const drto_nerf_config *ncfg, const float *emission, int sh_degree, int aovs,
+                             const float *L_in, const float *t_sigma_t, const float *t_emission, int acc32, int transposed,
+                             double *Jt_out, double *mag_out)
+{
+    if (sh_degree < 0 || sh_degree > 2 || (sh_degree && aovs)) return -4;
+    if ((transposed && !L_in) || !Jt_out || !mag_out) return -1;
+    nerf_fwd_t fw; fw.t_sigma = t_sigma_t; fw.t_emission = t_emission; fw.acc32 = acc32; fw.transposed = transposed; fw.jt = Jt_out; fw.mag = mag_out;
+    return nerf_render(job, ncfg, emission, sh_degree ? (sh_degree + 1) * (sh_degree + 1) : 0, aovs != 0, 1, NULL, L_in, NULL,
+                       NULL, NULL, NULL, &fw);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -1635,6 +1858,47 @@ int drto_render_backward(const drto_job *job, const float *dL, const float *L_in
                          double *grad_sigma_t, double *grad_albedo, drto_counters *cnt)
 {
     return run_job(job, 1, dL, L_in, NULL, grad_sigma_t, grad_albedo, cnt, NULL, NULL);
+}
+
+/* Forward mode of sample() in the two grids, per ray and channel: three adjoint passes of the ray with dL = e_k (multiplying by 1
+ * and adding 0 is exact, so pass k carries channel k's terms unrounded by dL) in tangent mode (tfwd_t).  Sampler streams, alt seed
+ * and state_in are the adjoint's. */
+int drto_render_forward(const drto_job *job, const float *L_in, const float *t_sigma_t, const float *t_albedo,
+                        uint32_t term_mask, int acc32, double *Jt_out, double *mag_out)
+{
+    scene_t sc;
+    if (!job || !L_in || !Jt_out || !mag_out) return -1;
+    if (scene_init(&sc, job)) return -1;
+    if (!sc.albedo) { scene_free(&sc); return -2; }
+    const uint32_t alt_seed = drto_alt_seed(job->seed, job->sensor != NULL);
+#ifdef _OPENMP
+    int nt = job->n_threads > 0 ? job->n_threads : omp_get_max_threads();
+#pragma omp parallel num_threads(nt)
+#endif
+    {
+        ctx_t c; memset(&c, 0, sizeof c);
+        c.sc = &sc; c.alt_seed = alt_seed;
+#ifdef _OPENMP
+#pragma omp for schedule(dynamic, 256)
+#endif
+        for (int64_t i = 0; i < (int64_t) job->n_rays; ++i) {
+            c.ray_index = (uint32_t)(job->ray_offset + (uint64_t) i);
+            for (int k = 0; k < 3; ++k) {
+                pcg32 S; ray_t ray;
+                job_ray(job, (uint64_t) i, &S, &ray);
+                tfwd_t tf; memset(&tf, 0, sizeof tf);
+                tf.t_sigma = t_sigma_t; tf.t_colour = t_albedo; tf.colour_stride = 3; tf.mask = term_mask; tf.g_abs = -1.0f;
+                float e[3] = { 0, 0, 0 }, L[3]; e[k] = 1.0f;
+                c.tf = &tf;
+                drt_sample(&c, &S, 1, ray, e, L_in + 3 * i, NULL, L);
+                c.tf = NULL;
+                Jt_out[3 * i + k] = acc32 ? (double) tf.jt32 : tf.jt;
+                mag_out[3 * i + k] = tf.mag;
+            }
+        }
+    }
+    scene_free(&sc);
+    return 0;
 }
 
 int drto_h1_step(const drto_job *job, float *L, float *image, double *loss_out,

@@ -182,6 +182,37 @@ int drto_nerf_render_ext(const drto_job *job, const drto_nerf_config *ncfg, cons
  * value - the scale against which rounding is judged.  phase_kind must be 1 (-6 otherwise). */
 int drto_render_forward_g(const drto_job *job, float *dLdg_out, float *mag_out);
 
+/* Forward mode of sample(Primal) in the two grids, per ray: Jt_out[n][3] = d L[i][k] along the tangents t_sigma_t (Z,Y,X,1) and
+ * t_albedo (Z,Y,X,3; the colour lattice), either may be NULL (a zero tangent).  The adjoint is linear in dL and none of its branches
+ * or draws depends on dL, so Jt[i][k] is ray i's adjoint with dL = e_k (state_in = L_in, the primal's output, the adjoint's sampler
+ * streams and alt seed) in which every splat of the float32 corner values v_q into voxels idx_q is replaced by the gather
+ * sum_q (double) v_q t[idx_q], summed in double in path order: <grad of drto_render_backward(dL = e_k on ray i), t> term by term.
+ * mag_out[n][3]: the same sum with every factor replaced by its absolute value - the scale rounding is judged against.
+ * term_mask: one bit per kind of splat site, a cleared bit drops that kind's terms (to name the term a kernel disagrees on).
+ * acc32 != 0: Jt is gathered by the float32 trilinear lookup and accumulated in float32 in path order, what a kernel can at best
+ * do - to measure a rounding bar with, nothing else. */
+#define DRTO_TERM_NEE     1u   /* ratio-tracking walk of an NEE (estimate_transmittance, volpathsimple.py:487-492) */
+#define DRTO_TERM_SCATTER 2u   /* delta-tracking scatter site (volpathsimple.py:152-172) */
+#define DRTO_TERM_DRT     4u   /* DRT vertex (backpropagate_scattering_drt, :543-581) */
+#define DRTO_TERM_TR      8u   /* transmittance resampling (backpropagate_transmittance, :584-607) */
+#define DRTO_TERM_ALL     0xffffffffu
+int drto_render_forward(const drto_job *job, const float *L_in, const float *t_sigma_t, const float *t_albedo,
+                        uint32_t term_mask, int acc32, double *Jt_out, double *mag_out);
+
+/* Forward mode of the nerf march (drto_nerf_render / drto_nerf_render_ext: sh_degree, aovs and their refusals as there): Jt_out and
+ * mag_out hold 3 doubles per ray, 5 with aovs (the tangents of A and D with it); t_emission has the emission grid's shape.
+ *   transposed != 0: as drto_render_forward, the adjoint of every ray with dL = e_k (five passes with aovs) and state_in = L_in, its
+ *                    sigma_t splat and its two inline emission splats (plain and spherical harmonics) replaced by gathers: term by term
+ *                    <grad of the adjoint(dL = e_k on ray i), t>.  The sigma_t splat's value is a sum of products of either sign and
+ *                    `result` a running remainder; mag takes both with every factor replaced by its absolute value.
+ *   transposed == 0: dual numbers through the float32 march (L_in is not read): beside every float32 value its derivative along the
+ *                    tangents, in double.  The forward kernels are held to THIS one: on an opaque ray the adjoint's remainder inherits
+ *                    the cancellation of the float32 primal's (1 - A) Le, a relative error of 2^-24 / (1 - A) that no rounding bar
+ *                    on the tangent's own terms covers (DESIGN.md "Oracle"). */
+int drto_nerf_render_forward(const drto_job *job, const drto_nerf_config *ncfg, const float *emission, int sh_degree, int aovs,
+                             const float *L_in, const float *t_sigma_t, const float *t_emission, int acc32, int transposed,
+                             double *Jt_out, double *mag_out);
+
 /* Independent textbook delta-tracking path tracer (no NEE, no MIS, own RNG use; samples the medium's phase function):
  * plays the role of Mitsuba's builtin `volpath` in tests/test_integrators.py:222-257. */
 int drto_render_textbook(const drto_job *job, float *L_out);
