@@ -483,6 +483,9 @@ int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out
  *                                               (measured slower)
  *  bit 12 (4096)       kHookNoQueuedTracer      keep supergrid launches off the queued tracer (drt_sq.hip): the round-3 kernel drt_super.hip
  *                                               where it serves, CoopTracer<SUPER> otherwise
+ *  bit 13 (8192)       kHookFewPartWGs          the partition passes of the gradient reduction (histogram, offsets, scatter) with three
+ *                                               workgroups per stream instead of 384: a scene of a few thousand rays then gives a workgroup
+ *                                               several batches, i.e. exercises the scatter's carry of its cursors from batch to batch
  *  bit 14 (16384)      kHookSmallRecordBudget   8 MB record budget, i.e. many ray sub-batches
  *  bit 15 (32768)      kHookPerLaneAdjoint      plain one-ray-per-lane adjoint kernel instead of the wave-cooperative tracking loops (drt_coop.hip)
  *  bit 16 (65536)      kHookWavefrontPrimal     state-machine kernel for the primal (default: the cooperative kernel, which also writes the

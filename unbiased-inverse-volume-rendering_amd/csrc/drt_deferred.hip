@@ -9,7 +9,9 @@
 //
 //   bin_histogram  records -> per-(workgroup, tile) counts            (LDS histogram)
 //   bin_offsets    counts  -> exclusive offsets, tile bases, reduce units
-//   bin_scatter    records -> tile-sorted copy                         (LDS cursors)
+//   bin_scatter    records -> tile-sorted copy: a workgroup sorts each batch of 2048 records by tile in LDS and writes one run per tile,
+//                  consecutive lanes to consecutive slots (bin_scatter_staged_kernel).  Grids of more than 2368 tiles,
+//                  whose cursors leave no room for the stage: one store per record from LDS cursors (bin_scatter_kernel)
 //   tile_reduce    workgroups walk runs of <= kUnitRecords-record units of ONE tile and ONE gradient plane
 //                  (stream 0 -> sigma_t; stream 1 -> sigma_t, r, g, b: four passes over the sorted records, which
 //                  stay in the memory-side cache): trilinear weights recomputed (same axis_setup / stencil_weights
@@ -39,9 +41,20 @@
                                    // bit 1 the scatter's stores.  Measured, alternating runs on one box (headline Msamples/s / reductions ms; default = 0):
                                    // 0: 939-943 / 1.99   1: 948-962 / 1.82-1.95   4: 947 / 1.94   5: 955-960 / 1.76-1.88   2: 883 / 2.54   3: 886 / 2.52
                                    // - the loads leave the L2 to the scatter's open output lines; non-temporal STORES lose their write combining
+                                   // The staged scatter (ms per headline step / reductions ms, two alternating runs): 5: 8.497 8.506 / 1.68   7: 8.737 8.764 / 1.93
+                                   // - its runs still end inside lines that the workgroup's next batch completes: bit 1 stays off
 #endif
 #ifndef DRT_PART_UNROLL
 #define DRT_PART_UNROLL 4
+#endif
+#ifndef DRT_PART_BATCH
+#define DRT_PART_BATCH 2           // staged scatter: stream-0 records per thread and LDS batch (2: 32 KB of stage; 3 measured the same, 4 - one workgroup per CU - slower)
+#endif
+#ifndef DRT_PART_LDS_KB
+#define DRT_PART_LDS_KB 64         // LDS budget of a staged scatter workgroup: the staged kernel is taken where cursors + counters + stage fit it
+#endif
+#ifndef DRT_PART_STAGED
+#define DRT_PART_STAGED 1          // 0: bin_scatter_kernel for every grid
 #endif
 
 namespace drt {
@@ -170,6 +183,25 @@ __global__ void __launch_bounds__(256) bin_offsets_kernel(const DeferredPlan D, 
     if (lane == 63) D.bin_base[(size_t) s * (D.n_bins + 1) + b] = incl;      // total for now
 }
 
+#ifdef DRT_TEST_HOOKS
+// kHookFewPartWGs: bin_offsets_kernel for a handful of partition workgroups, one row per lane (the production kernel's lanes own kPartWGs / 64 rows each)
+constexpr int kFewPartWGs = 3;
+static_assert(kFewPartWGs <= 64, "bin_offsets_few_kernel: one row per lane of a wave");
+__global__ void __launch_bounds__(256) bin_offsets_few_kernel(const DeferredPlan D, int n_wgs)
+{
+    const int lane = threadIdx.x & 63, s = blockIdx.y;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= D.n_bins) return;
+    uint32_t *col = D.hist + (size_t) s * n_wgs * D.n_bins + b;
+    const uint32_t v = lane < n_wgs ? col[(size_t) lane * D.n_bins] : 0u;   // (n_wgs <= 64: one row per lane)
+    uint32_t incl = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { uint32_t t = __shfl_up(incl, off, 64); if (lane >= off) incl += t; }
+    if (lane < n_wgs) col[(size_t) lane * D.n_bins] = incl - v;
+    if (lane == 63) D.bin_base[(size_t) s * (D.n_bins + 1) + b] = incl;      // total for now
+}
+#endif
+
 // one workgroup per stream: exclusive scan of the tile totals -> bin_base, and of the reduce-unit counts
 __global__ void __launch_bounds__(1024) bin_scan_kernel(const DeferredPlan D)
 {
@@ -256,6 +288,128 @@ __global__ void __launch_bounds__(kPartThreads) bin_scatter_kernel(const Params 
 {
     extern __shared__ uint32_t cur[];
     if (blockIdx.y == 0) bin_scatter_stream<0>(P, D, cur); else bin_scatter_stream<1>(P, D, cur);
+}
+
+// The staged scatter: a batch of kStageQuads float4s (kPartThreads x kPartBatch records of stream 0, half as many of stream 1) is sorted by
+// tile in LDS and leaves as one contiguous run per tile, consecutive lanes writing consecutive 16-byte slots - the same (workgroup, tile)
+// sub-ranges as bin_scatter_stream, the records of a batch in rank order instead of cursor-arrival order.
+//   LDS: cur[n_bins] | cnt[n_bins] | dlt[n_bins] | wsum[64] | stage[kStageQuads] float4 | tid[kStageQuads] uint16  (staged_lds_bytes)
+// Per batch: (1) rank = returning add on cnt[tile]; (2) exclusive scan of cnt over the tiles - thread t owns the bins [t * per, (t + 1) * per),
+// a wave scan of the threads' sums and one cross-wave step -, which leaves start in cnt, dlt = cur - start, cur += count; (3) record -> stage[start
+// + rank], its tile -> tid; (4) staged quad i -> global quad of record dlt[tile] + i / quads, and cnt[tile] = 0 again.  Barriers only.
+constexpr int kPartBatch = DRT_PART_BATCH;                      // stream-0 records per thread and batch
+static_assert(kPartBatch >= 2, "stream 1 takes half as many records per batch (rounded down)");
+constexpr uint32_t kStageQuads = kPartThreads * kPartBatch;
+constexpr int kPartWaves = kPartThreads / 64;
+static_assert(kPartThreads % 64 == 0 && kPartWaves <= 64, "one cross-wave step");
+
+__host__ __device__ constexpr size_t staged_words(int n_bins) { return ((size_t) 3 * n_bins + 64 + 3) & ~(size_t) 3; }   // cur, cnt, dlt, wsum: the stage behind them is 16-byte aligned
+__host__ __device__ constexpr size_t staged_lds_bytes(int n_bins)
+{
+    return staged_words(n_bins) * sizeof(uint32_t) + (size_t) kStageQuads * (sizeof(float4) + sizeof(uint16_t));
+}
+// The host takes the staged kernel where its LDS fits this budget - a function of n_bins alone.  64 KB: two workgroups of kPartThreads = 1024
+// threads fill a CU's 32 wave slots with 120 of its 160 KB (DESIGN.md section 6.7 has the occupancy arithmetic beside the overlapped tail launch)
+constexpr size_t kStagedLdsBudget = (size_t) DRT_PART_LDS_KB << 10;
+static_assert(DRT_PART_LDS_KB <= 64, "dynamic LDS beyond 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize on the kernel (the 78 and 96 KB batches measured that way were not kept)");
+static_assert(kMaxBins <= 65536, "tile ids travel as 16 bits");
+
+template <int S>
+__device__ __forceinline__ void bin_scatter_staged_stream(const Params &P, const DeferredPlan &D, uint32_t *lds)
+{
+    constexpr int kQuads = S == 0 ? 1 : 2;
+    constexpr int kRecs = kPartBatch / kQuads;                   // records per thread and batch (stream 1: the same bytes, rounded down)
+    const int n_bins = D.n_bins;
+    uint32_t *cur = lds, *cnt = lds + n_bins, *dlt = lds + 2 * n_bins, *wsum = lds + 3 * n_bins;
+    float4 *stage = (float4 *) (lds + staged_words(n_bins));
+    uint16_t *tid = (uint16_t *) (stage + kStageQuads);
+    const uint32_t *off = D.hist + ((size_t) S * gridDim.x + blockIdx.x) * n_bins;
+    const uint32_t *base = D.bin_base + (size_t) S * (n_bins + 1);
+    for (int b = threadIdx.x; b < n_bins; b += blockDim.x) { cur[b] = base[b] + off[b]; cnt[b] = 0u; }
+    __syncthreads();
+    const uint32_t used = min(D.cursor[S], D.cap_chunks[S]);
+    float4 *dst = D.out[S];
+    constexpr uint32_t kSub = kPartThreads / 256;
+    const uint32_t sub = threadIdx.x >> 8, rec = threadIdx.x & 255u;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int per = (n_bins + kPartThreads - 1) / kPartThreads, b_lo = min((int) threadIdx.x * per, n_bins), b_hi = min(b_lo + per, n_bins);
+    // Same chunk -> workgroup map as the histogram: this thread's chunks are first + sub + m * step, m = 0, 1, ...  A batch takes kRecs of them;
+    // the next batch's records are in flight while this one is staged.  The loop bound is the WORKGROUP's (barriers inside): a thread's own
+    // chunks end with okn[]
+    const uint32_t first = blockIdx.x * kSub, step = kSub * gridDim.x;
+    float4 rn[kRecs], qn[kRecs]; bool okn[kRecs];
+    auto fetch = [&](uint32_t m0) {
+#pragma unroll
+        for (int j = 0; j < kRecs; ++j) {
+            const uint32_t c = first + sub + (m0 + j) * step;
+            okn[j] = c < used && rec < D.chunk_count[S][c];
+            if (okn[j]) {
+                const float4 *src = D.in[S] + ((size_t) c * kRecChunk + rec) * kQuads;
+                rn[j] = DRT_PART_NT & 1 ? nt_load4(src) : src[0];
+                if constexpr (S == 1) qn[j] = DRT_PART_NT & 1 ? nt_load4(src + 1) : src[1];
+            }
+        }
+    };
+    fetch(0u);
+    for (uint32_t m0 = 0; first + m0 * step < used; m0 += kRecs) {
+        float4 r[kRecs], q[kRecs]; int bin[kRecs]; uint32_t rank[kRecs];
+        // (1) rank within the batch
+#pragma unroll
+        for (int j = 0; j < kRecs; ++j) {
+            r[j] = rn[j];
+            if constexpr (S == 1) q[j] = qn[j];
+            bin[j] = okn[j] ? bin_of(P, D, r[j]) : -1;
+            rank[j] = okn[j] ? atomicAdd(&cnt[bin[j]], 1u) : 0u;
+        }
+        fetch(m0 + kRecs);
+        lds_atomics_barrier();
+        // (2) exclusive scan of the batch counters over the tiles
+        uint32_t sum = 0;
+        for (int b = b_lo; b < b_hi; ++b) sum += cnt[b];
+        uint32_t incl = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o, 64); if (lane >= (uint32_t) o) incl += t; }
+        if (lane == 63u) wsum[wave] = incl;
+        __syncthreads();
+        uint32_t w = lane < (uint32_t) kPartWaves ? wsum[lane] : 0u, winc = w;
+#pragma unroll
+        for (int o = 1; o < kPartWaves; o <<= 1) { const uint32_t t = __shfl_up(winc, o, 64); if (lane >= (uint32_t) o) winc += t; }
+        const uint32_t total = __shfl(winc, kPartWaves - 1, 64);
+        uint32_t run = __shfl(winc - w, (int) wave, 64) + incl - sum;
+        for (int b = b_lo; b < b_hi; ++b) {
+            const uint32_t c = cnt[b];
+            if (c) { cnt[b] = run; dlt[b] = cur[b] - run; cur[b] += c; run += c; }
+        }
+        __syncthreads();
+        // (3) records to their places in the stage
+#pragma unroll
+        for (int j = 0; j < kRecs; ++j) if (bin[j] >= 0) {
+            const uint32_t pos = cnt[bin[j]] + rank[j];
+            stage[pos * kQuads] = r[j];
+            if constexpr (S == 1) stage[pos * kQuads + 1] = q[j];
+            tid[pos] = (uint16_t) bin[j];
+        }
+        __syncthreads();
+        // (4) the stage to the tiles' runs: consecutive lanes, consecutive 16-byte slots
+        const uint32_t n_quads = total * kQuads;
+#pragma unroll
+        for (int j = 0; j < kPartBatch; ++j) {
+            const uint32_t i = threadIdx.x + j * kPartThreads;
+            if (i < n_quads) {
+                const uint32_t rec_i = i / kQuads, t = tid[rec_i];
+                float4 *o = dst + ((size_t) (dlt[t] + rec_i) * kQuads + (i % kQuads));
+                if (DRT_PART_NT & 2) nt_store4(stage[i], o); else *o = stage[i];
+                cnt[t] = 0u;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kPartThreads, 8) bin_scatter_staged_kernel(const Params P, const DeferredPlan D)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // the float4 stage behind the counters is written with 16-byte LDS stores
+    if (blockIdx.y == 0) bin_scatter_staged_stream<0>(P, D, lds); else bin_scatter_staged_stream<1>(P, D, lds);
 }
 
 // blockIdx.y = reduce plane: 0: sigma_t of stream 0 AND of stream 1 (for every tile that has stream-0 records: the
@@ -435,10 +589,21 @@ hipError_t launch_deferred_split(const DeferredPlan &D, hipStream_t stream)
     return hipGetLastError();
 }
 
+// partition workgroups per stream (histogram, offsets, scatter).  kHookFewPartWGs: three, so that a test scene of a few thousand rays gives every
+// workgroup several batches per stream - the carry of the cursors from batch to batch
+inline int part_wgs(const Params &P)
+{
+#ifdef DRT_TEST_HOOKS
+    if (dbg(P.debug_flags, kHookFewPartWGs)) return kFewPartWGs;
+#endif
+    (void) P;
+    return kPartWGs;
+}
+
 hipError_t launch_deferred_early_histogram(const Params &P, const DeferredPlan &D, hipStream_t side)
 {
     const size_t lds = (size_t) D.n_bins * sizeof(uint32_t);
-    hipLaunchKernelGGL(bin_histogram_kernel, dim3(kPartWGs, kRecStreams), dim3(kPartThreads), lds, side, P, D, 1);
+    hipLaunchKernelGGL(bin_histogram_kernel, dim3(part_wgs(P), kRecStreams), dim3(kPartThreads), lds, side, P, D, 1);
     return hipGetLastError();
 }
 
@@ -450,12 +615,23 @@ hipError_t launch_deferred_reduce(const Params &P, const DeferredPlan &D, hipStr
     auto mark = [&](int k) { if (ev) (void) hipEventRecord(ev[k], stream); };
     mark(0);
     if (phase != 2) {
-        hipLaunchKernelGGL(bin_histogram_kernel, dim3(kPartWGs, kRecStreams), dim3(kPartThreads), lds, stream, P, D, early_hist ? 2 : 0);
+        const int wgs = part_wgs(P);
+        hipLaunchKernelGGL(bin_histogram_kernel, dim3(wgs, kRecStreams), dim3(kPartThreads), lds, stream, P, D, early_hist ? 2 : 0);
         mark(1);
+#ifdef DRT_TEST_HOOKS
+        if (wgs != kPartWGs) hipLaunchKernelGGL(bin_offsets_few_kernel, dim3((D.n_bins + 3) / 4, kRecStreams), dim3(256), 0, stream, D, wgs);
+        else
+#endif
         hipLaunchKernelGGL(bin_offsets_kernel, dim3((D.n_bins + 3) / 4, kRecStreams), dim3(256), 0, stream, D, kPartWGs);
         hipLaunchKernelGGL(bin_scan_kernel, dim3(kRecStreams), dim3(1024), 0, stream, D);
         mark(2);
-        hipLaunchKernelGGL(bin_scatter_kernel, dim3(kPartWGs, kRecStreams), dim3(kPartThreads), lds, stream, P, D);
+        // the staged scatter where its cursors, counters and stage fit the LDS budget - a function of n_bins alone (the headline's 2048 tiles: 60.25 KB;
+        // beyond 2368 tiles, 512^3 among them: the per-record scatter, whose cursors alone take up to 64 KB)
+        const size_t staged = staged_lds_bytes(D.n_bins);
+        if (DRT_PART_STAGED && staged <= kStagedLdsBudget) {
+            hipLaunchKernelGGL(bin_scatter_staged_kernel, dim3(wgs, kRecStreams), dim3(kPartThreads), staged, stream, P, D);
+        } else
+            hipLaunchKernelGGL(bin_scatter_kernel, dim3(wgs, kRecStreams), dim3(kPartThreads), lds, stream, P, D);
         mark(3);
     }
     if (phase == 1) return hipGetLastError();

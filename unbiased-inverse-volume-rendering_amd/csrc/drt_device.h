@@ -49,6 +49,7 @@ enum Hook : uint32_t {
     kHookReduceNoFlush      = 1u << 10,   // gradient reduction without the flush (timing only)
     kHookPipelineBatches    = 1u << 11,   // tracer of ray sub-batch b beside the reduction of sub-batch b - 1 on the side stream (measured slower)
     kHookNoQueuedTracer     = 1u << 12,   // keep supergrid launches off the queued tracer: the round-3 kernel (drt_super.hip) or CoopTracer<SUPER>
+    kHookFewPartWGs         = 1u << 13,   // three partition workgroups (histogram, offsets, scatter) instead of kPartWGs: several batches per workgroup in small scenes
     kHookSmallRecordBudget  = 1u << 14,   // 8 MB record budget: many ray sub-batches
     kHookPerLaneAdjoint     = 1u << 15,   // the plain one-ray-per-lane Tracer for adjoint launches
     kHookWavefrontPrimal    = 1u << 16,   // the state machine of whole flights for primal launches

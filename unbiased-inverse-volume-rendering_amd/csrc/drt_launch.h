@@ -112,7 +112,9 @@ constexpr int kTileX = 32, kTileY = 16, kTileZ = 16;   // base-corner cells per 
 constexpr int kMaxBins = 16384;                          // tiles per grid the one-pass partition handles (64 KiB LDS histogram): 512^3
 constexpr uint32_t kUnitRecords = 16384;                 // records per reduce workgroup
 #ifndef DRT_PART_WGS
-#define DRT_PART_WGS 256
+#define DRT_PART_WGS 384           // a multiple of 64 (bin_offsets_kernel).  384 = two workgroups of 1024 threads on each of the 192 CUs that the overlapped
+                                   // tail launch (64 workgroups, a CU's LDS each) leaves free: the staged scatter's 60 KB of LDS do not fit beside a tail
+                                   // workgroup.  Measured (profiles/r08_scatter_runs.txt): 256 / 320 / 384 / 512
 #endif
 #ifndef DRT_PART_THREADS
 #define DRT_PART_THREADS 1024
@@ -121,6 +123,7 @@ constexpr uint32_t kUnitRecords = 16384;                 // records per reduce w
 // one partially written line at a time; few, large workgroups keep that working set (WGs x tiles x 128 B)
 // inside the 256 MB memory-side cache.
 constexpr int kPartWGs = DRT_PART_WGS;
+static_assert(kPartWGs % 64 == 0, "bin_offsets_kernel: every lane of a wave owns kPartWGs / 64 rows");
 constexpr int kPartThreads = DRT_PART_THREADS;
 struct DeferredPlan {
     float4 *in[2], *out[2];          // record streams as emitted / tile-sorted (stream 0: 1 float4 per record, stream 1: 2)
