@@ -109,7 +109,7 @@ int drt_set_colour_resolution(drt_handle h, const int32_t res[3]);
  * is refused with DRT_ERR_UNSUPPORTED.  Setting another phase invalidates what the handle planned from earlier paths (path cache, ray
  * order); setting the same one again changes nothing.  The gradient with respect to g: drt_render_backward_phase,
  * drt_render_backward_px_phase and drt_render_forward_phase (an extension of the reference, whose volpathsimple has none). */
-enum { DRT_PHASE_ISOTROPIC = 0, DRT_PHASE_HG = 1, DRT_PHASE_HG2 = 2 };
+enum { DRT_PHASE_ISOTROPIC = 0, DRT_PHASE_HG = 1, DRT_PHASE_HG2 = 2, DRT_PHASE_TAB = 3 };
 int drt_set_phase(drt_handle h, int32_t kind, float g);
 /* Two-lobe Henyey-Greenstein phase function (kind DRT_PHASE_HG2; Mitsuba: `blendphase` over two `hg` children):
  *   p(mu) = (1 - weight) hg(g1, mu) + weight hg(g2, mu) - `weight` is the share of the SECOND lobe, as blendphase's.
@@ -123,6 +123,22 @@ int drt_set_phase(drt_handle h, int32_t kind, float g);
  * g1, g2 or weight yet: a non-NULL grad_phase_g / non-zero t_phase_g of the *_phase entry points on such a handle returns
  * DRT_ERR_UNSUPPORTED (NULL / 0 run as the plain calls do). */
 int drt_set_phase_hg2(drt_handle h, float g1, float g2, float weight);
+/* Tabulated phase function (kind DRT_PHASE_TAB; Mitsuba: `tabphase`): `values` is a HOST pointer to n numbers v_i >= 0, 2 <= n <= 65536,
+ * all finite and at least one positive, copied by the call.  They sit at the n equally spaced nodes c_i = -1 + 2 i / (n - 1) of the PHYSICS
+ * cosine c = -dot(wo, wi) (wi = -d_in; c = +1 scatters forward), the function is linear in between, and it is normalised by the library:
+ *   eval(wo, wi) = f(c) / (2 pi I),  I = int_{-1}^{1} f dc (trapezoids, float64).
+ * A scatter inverts the piecewise-quadratic CDF exactly (sampled weight 1, pdf = eval) and builds the direction in the frame and azimuth
+ * of the `hg` sampler; it consumes the draws of every other phase function, so a path's sampler stream does not depend on the phase.  A
+ * uniform table evaluates to 1 / (4 pi) bit for bit.  This is how measured and Mie phase functions enter a scene.  Each handle holds its own
+ * table on the device (density and CDF nodes plus a guide table for the search, 12 bytes per node).  Kernels: the kTab instantiations
+ * (csrc/drt_sq_tab.hip, drt_coop_tab.hip, drt_coop_super_tab.hip, drt_own_tab.hip) with the HG routing and the HG invalidation rules:
+ * another table drops path cache and ray orders, the same table changes nothing, drt_set_medium leaves it alone, drt_set_phase /
+ * drt_set_phase_hg2 replace it, a test hook that routes to an older tracer generation is refused (DRT_ERR_UNSUPPORTED).  The call waits
+ * for the handle's stream.  NULL values, n out of range or a negative / non-finite / all-zero table: DRT_ERR_INVALID_ARGUMENT (checked
+ * before the handle).  drt_set_phase called with kind 3 returns DRT_ERR_INVALID_ARGUMENT.  No gradients with respect to the values: a
+ * non-NULL grad_phase_g / non-zero t_phase_g of the *_phase entry points on such a handle returns DRT_ERR_UNSUPPORTED.  Node spacing is
+ * uniform only. */
+int drt_set_phase_tab(drt_handle h, const float *values, int32_t n);
 /* params.update(opt) after an optimizer step (python/optimize.py:354) and
  * medium.set_majorant_resolution_factor (:195-199): refresh the majorant from
  * the (same) parameter buffers.  No host synchronisation. */
@@ -462,7 +478,9 @@ int drt_read_timings(drt_handle h, int backward, float *out_ms, int capacity);
  * 15 Henyey-Greenstein sample (u1, u2, wi.xyz, g) -> wo.xyz, pdf, 16 Henyey-Greenstein eval (wo.xyz, wi.xyz) with the
  * handle's g (drt_set_phase) -> pdf - on a two-lobe handle (drt_set_phase_hg2) the pdf of the mixture -, 17 Henyey-Greenstein score
  * (g, mu) -> d/dg log p, p; on a two-lobe handle only: 18 two-lobe sample (u1, ux, uy, wi.xyz) with the handle's (g1, g2, weight)
- * -> wo.xyz, mixture pdf (u1 < weight picks the second lobe), 19 two-lobe eval (wo.xyz, wi.xyz) -> pdf. */
+ * -> wo.xyz, mixture pdf (u1 < weight picks the second lobe), 19 two-lobe eval (wo.xyz, wi.xyz) -> pdf; on a handle with a tabulated
+ * phase (drt_set_phase_tab) only: 20 sample (ux, uy, wi.xyz) with the handle's table -> wo.xyz, pdf, mu = dot(wo, wi) as sampled,
+ * 21 eval (wo.xyz, wi.xyz) -> pdf (op 16 gives the same there). */
 int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out);
 
 /* Test hooks: profiling ablations, kernel selection, simulated out-of-memory.  0 in production: only the library flavour built with

@@ -6,7 +6,7 @@ hand-written HIP library (csrc/, C ABI in include/drt_hip.h).  Importing this
 package does not need a GPU; creating an integrator handle does.
 """
 from .scene import (ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, ConstantEmitter, EnvmapEmitter, GridMedium, HG2Phase, HGPhase, IsotropicPhase,
-                    PerspectiveSensor, Scene, cube_test_scene, scene_to)
+                    PerspectiveSensor, Scene, TabPhase, cube_test_scene, scene_to)
 from .integrators import (ADMode, FusedNerfDrtIntegrator, IndependentSampler, NeRFIntegrator, RayBatch, VolpathSimpleIntegrator, load_dict,
                           register_integrator, sample_tea_32, sh_basis, sh_from_rgb)
 from .opt_config import IntegratorConfig, add_int_config, get_int_config
@@ -26,7 +26,7 @@ from .fd import fd_gradients
 
 __all__ = [
     "ALBEDO_KEY", "EMISSION_KEY", "PHASE_G_KEY", "SIGMA_T_KEY", "ConstantEmitter", "EnvmapEmitter", "GridMedium", "HG2Phase", "HGPhase", "IsotropicPhase",
-    "PerspectiveSensor",
+    "PerspectiveSensor", "TabPhase",
     "Scene", "cube_test_scene", "scene_to", "ADMode", "IndependentSampler", "RayBatch",
     "VolpathSimpleIntegrator", "NeRFIntegrator", "FusedNerfDrtIntegrator", "load_dict", "register_integrator", "sample_tea_32", "sh_basis", "sh_from_rgb", "IntegratorConfig",
     "add_int_config", "get_int_config", "ShardSpec", "allreduce_gradients", "allreduce_scalar", "GradientSupport", "gradient_support",

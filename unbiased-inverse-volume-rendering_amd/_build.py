@@ -22,7 +22,8 @@ _ROOT = os.path.dirname(_PKG)
 
 HIP_SOURCES = ["drt_kernels.hip", "drt_deferred.hip", "drt_coop.hip", "drt_coop_super.hip", "drt_order.hip", "drt_sq.hip", "drt_nerf_tile.hip", "drt_nerf_sh.hip", "drt_nerf_aov.hip", "drt_own.hip", "drt_loss.hip", "drt_priors.hip",
                "drt_coop_hg.hip", "drt_coop_super_hg.hip", "drt_own_hg.hip", "drt_sq_hg.hip",
-               "drt_coop_hg2.hip", "drt_coop_super_hg2.hip", "drt_own_hg2.hip", "drt_sq_hg2.hip", "drt_capi.cpp"]
+               "drt_coop_hg2.hip", "drt_coop_super_hg2.hip", "drt_own_hg2.hip", "drt_sq_hg2.hip",
+               "drt_coop_tab.hip", "drt_coop_super_tab.hip", "drt_own_tab.hip", "drt_sq_tab.hip", "drt_capi.cpp"]
 # older generations of the tracer (round 1/2 state machine of whole flights, round 3 lane state machines with posted flights): no production call
 # reaches them ("which call reaches which kernel"); the flavour with test hooks keeps them in lock-step with the oracle
 HOOKS_ONLY_SOURCES = ["drt_wavefront.hip", "drt_super.hip"]
@@ -32,7 +33,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
 
 # per-unit flags behind HIP_FLAGS (measured, profiles/r05_sq_experiments.txt): the queued tracer's envmap instantiations come out 12 % smaller at -O2
 # (56.8 instead of 64.7 KB for the adjoint kernel) and 1.5 % faster (headline + envmap + factor 8: 755-757 -> 766-768 Msamples/s); the others the same
-UNIT_FLAGS = {"drt_sq.hip": ["-O2"], "drt_sq_hg.hip": ["-O2"], "drt_sq_hg2.hip": ["-O2"]}
+UNIT_FLAGS = {"drt_sq.hip": ["-O2"], "drt_sq_hg.hip": ["-O2"], "drt_sq_hg2.hip": ["-O2"], "drt_sq_tab.hip": ["-O2"]}
 
 _EXT = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
 LIB_PATH = os.path.join(_CSRC, "libdrt_hip.so")                 # production library: no test hooks

@@ -62,9 +62,11 @@ struct drt_handle_s {
     drt_config cfg{};
     drt::Params base{};            // scene part of the kernel parameter block
     bool have_medium = false, have_emitter = false, have_sensor = false;
-    int32_t phase_kind = DRT_PHASE_ISOTROPIC;   // drt_set_phase / drt_set_phase_hg2 (g travels in base.phase_g; HG2: g1 there, g2 in base.phase_tg,
-                                                // the second lobe's share in base.phase_w)
-    float *d_majorant = nullptr;   // [2]
+    int32_t phase_kind = DRT_PHASE_ISOTROPIC;   // drt_set_phase / drt_set_phase_hg2 / drt_set_phase_tab (g travels in base.phase_g; HG2: g1 there, g2 in
+                                                // base.phase_tg, the second lobe's share in base.phase_w; TAB: the node count as integer bits in base.phase_g)
+    float *d_majorant = nullptr;   // [2]; behind them, from float drt::kTabOffset on, the table of a tabulated phase (drt_set_phase_tab; drt_device.h: TabView)
+    size_t majorant_bytes = 0;     // ... the allocation's size (it grows with the table and never shrinks)
+    std::vector<float> tab_values; // the caller's table as drt_set_phase_tab last took it (the same table again changes nothing)
     // the global majorant as the HOST last saw it: drt_params_changed copies it to pinned memory behind the reduction and records an event; launches
     // look at it when the event has completed (never waiting) - a hint for kernel choice only (a thin medium: Params::sq_rounds), stale by design
     float *h_majorant = nullptr;   // pinned, [1]
@@ -404,9 +406,9 @@ hipError_t early_histogram_between(void *ctx)
 // ---- which call reaches which kernel --------------------------------------------------------------------------------------------------------
 enum class Route {
     kCoop,       // CoopTracer / CoopTracer<SUPER> (drt_coop.hip, drt_coop_super.hip)
-    kCoopHG,     // CoopTracer with a Henyey-Greenstein phase, kHG / kHGGrad / kHG2 (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip and their _hg2 units)
+    kCoopHG,     // CoopTracer with a Henyey-Greenstein phase, kHG / kHGGrad / kHG2 (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip and their _hg2 / _tab units; kTab too)
     kOwn,        // CoopTracer with the colour grids on their own lattice (drt_own.hip)
-    kQueued,     // the queued supergrid tracer (drt_sq.hip, drt_sq_hg.hip, drt_sq_hg2.hip)
+    kQueued,     // the queued supergrid tracer (drt_sq.hip, drt_sq_hg.hip, drt_sq_hg2.hip, drt_sq_tab.hip)
 #ifdef DRT_TEST_HOOKS
     kSuper3,     // the round-3 supergrid kernel (drt_super.hip)
     kWavefront,  // the round-2 state machine of whole flights (drt_wavefront.hip)
@@ -421,6 +423,7 @@ struct Choice { Route route; drt::Phase phase; };
 drt::Phase tracer_phase(drt_handle h, bool grad_g)
 {
     if (h->phase_kind == DRT_PHASE_HG2) return drt::Phase::kHG2;
+    if (h->phase_kind == DRT_PHASE_TAB) return drt::Phase::kTab;
     if (h->phase_kind == DRT_PHASE_HG) return grad_g ? drt::Phase::kHGGrad : drt::Phase::kHG;
     return drt::Phase::kIso;
 }
@@ -444,6 +447,8 @@ drt::Phase tracer_phase(drt_handle h, bool grad_g)
 //   kernels; the counting kernels have none (such a launch counts nothing).
 //   Two-lobe Henyey-Greenstein phase (drt_set_phase_hg2): the HG choice among the kHG2 instantiations (drt_sq_hg2.hip, drt_coop_hg2.hip,
 //   drt_coop_super_hg2.hip, drt_own_hg2.hip); no g-gradient kernels.
+//   Tabulated phase (drt_set_phase_tab): the HG choice among the kTab instantiations (drt_sq_tab.hip, drt_coop_tab.hip, drt_coop_super_tab.hip,
+//   drt_own_tab.hip); no phase-parameter gradient kernels.
 Choice choose_tracer(drt_handle h, const drt::Params &P, bool adjoint)
 {
     const uint32_t f = h->debug_flags;
@@ -945,6 +950,7 @@ int drt_create(const drt_config *cfg, int device, drt_handle *out)
     DeviceGuard g(device);
     if (!g.ok) { delete h; return fail(nullptr, DRT_ERR_HIP, "hipSetDevice(%d) failed", device); }
     hipError_t e = hipMalloc(&h->d_majorant, 2 * sizeof(float));
+    if (e == hipSuccess) h->majorant_bytes = 2 * sizeof(float);
     if (e == hipSuccess) e = hipMalloc(&h->d_scratch, sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&h->d_queues, 8 * sizeof(unsigned long long));
     if (e == hipSuccess) { hipDeviceProp_t prop; e = hipGetDeviceProperties(&prop, device); if (e == hipSuccess) h->n_cus = prop.multiProcessorCount; }
@@ -1202,6 +1208,77 @@ int drt_set_phase_hg2(drt_handle h, float g1, float g2, float weight)
     return DRT_OK;
 }
 
+int drt_set_phase_tab(drt_handle h, const float *values, int32_t n)
+{
+    // (the arguments are checked before the handle, as drt_set_phase does)
+    if (!values) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase_tab: null values");
+    if (n < drt::kTabMinNodes || n > drt::kTabMaxNodes)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase_tab: the table must have between %d and %d nodes (got %d)", drt::kTabMinNodes,
+                    drt::kTabMaxNodes, (int) n);
+    const size_t N = (size_t) n, iv = N - 1;
+    bool positive = false;
+    for (size_t i = 0; i < N; ++i) {
+        if (!std::isfinite(values[i]) || values[i] < 0.0f)
+            return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase_tab: the values must be finite and >= 0 (values[%zu] = %g)", i, (double) values[i]);
+        positive = positive || values[i] > 0.0f;
+    }
+    if (!positive) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase_tab: at least one value must be positive (the table is all zero)");
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (h->phase_kind == DRT_PHASE_TAB && h->tab_values.size() == N && std::memcmp(h->tab_values.data(), values, N * sizeof(float)) == 0)
+        return DRT_OK;                                           // the same phase: every plan stays
+
+    // density and CDF nodes in float64, rounded once (drt_device.h: the tabulated phase function): cum_i = int_{-1}^{c_i} f dc by trapezoids
+    const double delta = 2.0 / (double) iv, two_pi = 6.283185307179586476925286766559;
+    std::vector<double> cum(N, 0.0);
+    for (size_t i = 0; i < iv; ++i) cum[i + 1] = cum[i] + 0.5 * ((double) values[i] + (double) values[i + 1]) * delta;
+    const double I = cum[iv];
+    if (!(I > 0.0) || !std::isfinite(I))
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_set_phase_tab: the table's integral must be positive and finite (got %g)", I);
+    // device layout behind the two majorant scalars (and two floats of padding): float2 {p_i, F_i} x N | guide words x N
+    std::vector<float> nodes(2 * N);
+    for (size_t i = 0; i < N; ++i) {
+        nodes[2 * i] = (float) ((double) values[i] / (two_pi * I));
+        nodes[2 * i + 1] = (float) (cum[i] / I);
+    }
+    nodes[1] = 0.0f; nodes[2 * iv + 1] = 1.0f;
+    // guide[k] = largest index in [0, iv - 1] with F[index] <= k / iv (tab_find; as the envmap's guide tables)
+    std::vector<uint32_t> guide(N);
+    size_t idx = 0;
+    for (size_t k = 0; k <= iv; ++k) {
+        const float x = (float) ((double) k / (double) iv);
+        while (idx + 1 < iv && nodes[2 * (idx + 1) + 1] <= x) ++idx;
+        guide[k] = (uint32_t) idx;
+    }
+
+    DeviceGuard g(h->device);
+    // launches in flight may read the table that is about to change (or the allocation that is about to move)
+    DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    if (h->side) DRT_HIP_CHECK(h, hipStreamSynchronize(h->side));
+    if (h->nerf_stream) DRT_HIP_CHECK(h, hipStreamSynchronize(h->nerf_stream));
+    const size_t head = (size_t) drt::kTabOffset * sizeof(float);
+    const size_t need = head + N * (2 * sizeof(float) + sizeof(uint32_t));
+    if (need > h->majorant_bytes) {                              // grow: the two majorant scalars move along
+        float *fresh = nullptr;
+        DRT_HIP_CHECK(h, hipMalloc(&fresh, need));
+        hipError_t e = hipMemcpy(fresh, h->d_majorant, 2 * sizeof(float), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) { (void) hipFree(fresh); return fail(h, DRT_ERR_HIP, "drt_set_phase_tab: copying the majorant failed: %s", hipGetErrorString(e)); }
+        (void) hipFree(h->d_majorant);
+        h->d_majorant = fresh; h->majorant_bytes = need;
+    }
+    char *base = reinterpret_cast<char *>(h->d_majorant) + head;
+    DRT_HIP_CHECK(h, hipMemcpy(base, nodes.data(), nodes.size() * sizeof(float), hipMemcpyHostToDevice));
+    DRT_HIP_CHECK(h, hipMemcpy(base + nodes.size() * sizeof(float), guide.data(), guide.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    h->tab_values.assign(values, values + N);
+    drt::Params &B = h->base;
+    h->phase_kind = DRT_PHASE_TAB;
+    std::memcpy(&B.phase_g, &n, sizeof(float));                  // the node count, as integer bits (tab_view)
+    B.phase_tg = 0.0f; B.phase_w = 0.0f;
+    // other paths: as drt_set_phase
+    h->scene_version++;
+    h->pcache_sig.valid = false; h->perm_valid = false; h->order_valid = false; h->order_unit = 0;
+    return DRT_OK;
+}
+
 int drt_set_emitter_constant(drt_handle h, const float radiance[3])
 {
     if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
@@ -1421,6 +1498,9 @@ static int check_phase_grad(drt_handle h, const char *what, bool wanted)
     if (wanted && h->phase_kind == DRT_PHASE_HG2)
         return fail(h, DRT_ERR_UNSUPPORTED, "%s: the two-lobe Henyey-Greenstein phase function (drt_set_phase_hg2) has no phase-parameter "
                                             "gradients yet (g1, g2 and weight)", what);
+    if (wanted && h->phase_kind == DRT_PHASE_TAB)
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the tabulated phase function (drt_set_phase_tab) has no phase-parameter gradients (it has no g, "
+                                            "and gradients with respect to the table values are not built)", what);
     if (wanted && h->phase_kind != DRT_PHASE_HG)
         return fail(h, DRT_ERR_UNSUPPORTED, "%s: the handle's phase function is isotropic - a gradient with respect to g needs the "
                                             "Henyey-Greenstein phase function (drt_set_phase(DRT_PHASE_HG, 0.0) for an isotropic medium)", what);
@@ -1852,6 +1932,10 @@ int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out
     if (h->phase_kind != DRT_PHASE_HG2 && (op == 18 || op == 19))
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_debug_eval: op %d evaluates the handle's two-lobe phase function (drt_set_phase_hg2)", op);
     if (h->phase_kind == DRT_PHASE_HG2 && op == 16) op = 19;   // "the handle's phase function -> pdf": the mixture
+    // (the table ops read behind the majorant scalars: only where drt_set_phase_tab has put a table there)
+    if (h->phase_kind != DRT_PHASE_TAB && (op == 20 || op == 21))
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_debug_eval: op %d evaluates the handle's tabulated phase function (drt_set_phase_tab)", op);
+    if (h->phase_kind == DRT_PHASE_TAB && op == 16) op = 21;   // ... the table
     DRT_HIP_CHECK(h, drt::launch_debug_eval(P, op, in, n, out, h->stream));
     return DRT_OK;
 }

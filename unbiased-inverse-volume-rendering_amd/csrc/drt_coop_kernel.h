@@ -13,7 +13,7 @@ using namespace coop;
 
 // TAIL: the second launch of a specialised kernel - its workgroups start from 256 paths of the tail pool each
 // (CoopTracer::wg_handoff) instead of from rays, and finish them
-// PH: the phase function (CoopTracer).  kHG, kHGGrad, kHG2: those kernels run without hand-off and tail pool; kHGGrad (adjoint): the
+// PH: the phase function (CoopTracer).  kHG, kHGGrad, kHG2, kTab: those kernels run without hand-off and tail pool; kHGGrad (adjoint): the
 // g-gradient too - each wave adds the sum of its lanes' terms to *Params::L_out with one atomic at its end
 template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, Phase PH = Phase::kIso>
 __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRIMAL) trace_coop_kernel(const Params P)

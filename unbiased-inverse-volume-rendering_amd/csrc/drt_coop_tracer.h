@@ -127,9 +127,10 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 //   c (g_S + explicit term) t_g (Params::phase_tg) to tg.
 //   kHG2 (H2): the two-lobe mixture (drt_device.h: hg2_eval, hg2_sample) - g1 in Params::phase_g, g2 in Params::phase_tg, the second lobe's
 //   share in Params::phase_w.  The scatter sites keep the next_1d draw the other instantiations drop: it chooses the lobe.
+//   kTab (TB; HG too): the tabulated phase function (drt_device.h: tab_eval, tab_sample) - its table behind Params::majorant (tab_view).
 template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, Phase PH = Phase::kIso>
 struct CoopTracer {
-    static constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2;
+    static constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2, TB = PH == Phase::kTab;
     const Params &P;
     float maj, inv_maj;
     const uint32_t *mocc;   // SUPER: non-empty supergrid cells (LDS copy) or nullptr
@@ -499,6 +500,11 @@ struct CoopTracer {
             float w = mis_weight(ds_pdf, pv);                                   // :391
 #pragma unroll
             for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * pv) * w) * emitted[k] : 0.0f;
+        } else if constexpr (TB) {                                              // ... of the table
+            const float pv = tab_eval(tab_view(P), hg_wd, hg_wi);
+            float w = mis_weight(ds_pdf, pv);                                   // :391
+#pragma unroll
+            for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * pv) * w) * emitted[k] : 0.0f;
         } else if constexpr (HG) {                                              // phase_val = phase_pdf = eval(wd, wi) (:386-388)
             const float pv = hg_eval(P.phase_g, hg_wd, hg_wi);
             float w = mis_weight(ds_pdf, pv);                                   // :391
@@ -578,6 +584,7 @@ struct CoopTracer {
             if constexpr (H2) u1 = A.next_1d(); else { (void) A.next_1d(); (void) u1; }
             float ux = A.next_1d(), uy = A.next_1d();
             if constexpr (H2) rr.d = hg2_sample(P.phase_g, P.phase_tg, P.phase_w, u1, ux, uy, hg_wi, ps.last_pdf);
+            else if constexpr (TB) rr.d = tab_sample(tab_view(P), ux, uy, hg_wi, ps.last_pdf);
             else if constexpr (HG) rr.d = hg_sample(P.phase_g, ux, uy, hg_wi, ps.last_pdf);
             else rr.d = square_to_uniform_sphere(ux, uy);
             Hit sn = box_hit(P, p, rr.d);                                       // :637
@@ -1016,6 +1023,10 @@ struct CoopTracer {
                     float ux = S.next_1d(), uy = S.next_1d();
                     if constexpr (H2) {
                         ray.o = mei.p; ray.d = hg2_sample(P.phase_g, P.phase_tg, P.phase_w, u1, ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf);
+                        ray.maxt = kLargest;
+                    }
+                    else if constexpr (TB) {
+                        ray.o = mei.p; ray.d = tab_sample(tab_view(P), ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf);
                         ray.maxt = kLargest;
                     }
                     else if constexpr (kGG) {                                        // the score term: s(mu) times what the path collects after it

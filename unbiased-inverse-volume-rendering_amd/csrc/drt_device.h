@@ -348,6 +348,7 @@ enum class Phase : int {
     kHG,       // Henyey-Greenstein (drt_set_phase)
     kHGGrad,   // ... with the derivative with respect to g (adjoint and forward kernels only)
     kHG2,      // mixture of two Henyey-Greenstein lobes (drt_set_phase_hg2); no g-gradient
+    kTab,      // tabulated over the cosine of the scattering angle (drt_set_phase_tab; TabView below); no phase-parameter gradient
 };
 
 // ---------------------------------------------------------------------------
@@ -370,8 +371,10 @@ struct Params {
     // Henyey-Greenstein asymmetry g (drt_set_phase): read only by the HG instantiations of CoopTracer; 0 for an isotropic handle.  It
     // fills the four bytes of padding in front of `majorant`: no field moves and the block keeps its size (the kernarg offsets of every
     // kernel stay as they are).
+    // A handle with a tabulated phase (drt_set_phase_tab) keeps the node count N here as integer bits - the kTab instantiations read nothing
+    // else from it - and the table itself behind the two scalars of `majorant` (tab_view): no field is added for it either.
     float phase_g;
-    const float *majorant;     // device: [0] = scale*max(sigma_t), [1] = 1/[0] (0 if [0]==0)
+    const float *majorant;     // device: [0] = scale*max(sigma_t), [1] = 1/[0] (0 if [0]==0); from float kTabOffset on: the phase table (TabView)
     const float *mgrid;        // majorant supergrid, one majorant per cell (x fastest), or nullptr
     const uint32_t *mocc;      // bit c = supergrid cell c has a non-zero majorant (the DDA skips the others without a load)
     const uint32_t *mocc_dil;  // bit c = cell c or one of its 26 neighbours has (build_unit_empty)
@@ -496,6 +499,120 @@ static_assert(offsetof(Params, majorant) == offsetof(Params, g4_nbx) + 8, "Param
 static_assert(offsetof(Params, L_out) == offsetof(Params, alt_seed) + 8, "Params::phase_tg must stay in the padding in front of L_out");
 static_assert(offsetof(Params, sq_cold) == offsetof(Params, empty_unit) + 8, "Params::phase_w must stay in the padding in front of sq_cold");
 static_assert(sizeof(Params) == 752, "the kernel parameter block keeps its size");
+
+// ---------------------------------------------------------------------------
+// Tabulated phase function (Mitsuba 3: `tabphase`; drt_set_phase_tab): N values v_i >= 0 at the equally spaced nodes
+// c_i = -1 + 2 i / (N - 1) of the PHYSICS cosine c = -dot(wo, wi) (wi = -d_in as for hg_eval; c = +1 scatters forward), linear in between.
+//   I = int_{-1}^{1} f dc (trapezoids),  eval(wo, wi) = f(c) / (2 pi I)
+// The host (drt_capi.cpp) prepares, in float64 and rounded once, the density nodes p_i = v_i / (2 pi I) and the CDF nodes
+// F_i = 2 pi int_{-1}^{c_i} p dc with F_0 = 0 and F_{N-1} = 1 exactly, interleaved as float2 {p_i, F_i} (one 8-byte load per probe), and a
+// guide table over the n = N - 1 intervals: guide[k] = largest i in [0, n - 1] with F_i <= k / n, k = 0 .. n (cdf_find_guided's, the envmap's).
+// Where the table lives: behind the handle's two majorant scalars, nodes at Params::majorant + kTabOffset floats, the guide words behind
+// the N nodes; N travels as integer bits in Params::phase_g (no field is added to Params; two handles hold two tables).
+// float32 operation order (no contraction), nf = (float) n, y_i = p_i:
+//   eval_cos(mu):  x = min(max((1 - mu) * (0.5 * nf), 0), nf); i = min((int) x, n - 1); t = x - (float) i; p = y_i + t * (y_{i+1} - y_i)
+//                  (a uniform table gives y_i bit for bit: kInvFourPi)
+//   sample(ux, uy): i = largest index <= n - 1 with F_i <= ux (tab_find: intervals of zero mass are skipped)
+//                  delta = 2 / nf; s = kTabTwoPi * delta; r = ux - F_i
+//                  y_i == y_{i+1}: t = r / (s * y_i)
+//                  otherwise:      rp = r / s; disc = max(0, y_i * y_i + (2 * (y_{i+1} - y_i)) * rp); t = (y_i - sqrt(disc)) / (y_i - y_{i+1})
+//                  t = min(max(t, 0), 1) (a NaN becomes 0); c = min(max(-1 + ((float) i + t) * delta, -1), 1)
+//                  direction: hg_sample's frame and azimuth with cos_t = c (sin_t = sqrt(max(0, 1 - c * c)), phi = 2 pi uy, lz = -c); mu = -c
+//                  pdf = y_i + t * (y_{i+1} - y_i) (the sampled weight stays 1)
+// The phase site consumes the draws of every other phase (next_1d dropped, then next_2d).  No gradient with respect to the values.
+// ---------------------------------------------------------------------------
+constexpr int kTabOffset = 4;                       // floats between Params::majorant and the first node (16 bytes: the float2 nodes stay aligned)
+constexpr int kTabMinNodes = 2, kTabMaxNodes = 65536;
+constexpr float kTabTwoPi = 6.2831853071795865f;
+
+struct TabView {
+    const float2 *nodes;    // [n + 1] {p_i, F_i}
+    const uint32_t *guide;  // [n + 1]
+    int n;                  // intervals = N - 1 >= 1
+};
+
+__device__ __forceinline__ TabView tab_view(const Params &P)
+{
+    // (N is clamped to what the host can have allocated: no read outside the table whatever the bits are)
+    const int N = min(max(__float_as_int(P.phase_g), kTabMinNodes), kTabMaxNodes);
+    TabView T;
+    T.nodes = reinterpret_cast<const float2 *>(P.majorant + kTabOffset);
+    T.guide = reinterpret_cast<const uint32_t *>(T.nodes + N);
+    T.n = N - 1;
+    return T;
+}
+
+__device__ __forceinline__ float tab_eval_cos(const TabView &T, float mu)
+{
+    const float nf = (float) T.n;
+    const float x = fminf(fmaxf((1.0f - mu) * (0.5f * nf), 0.0f), nf);
+    const int i = min((int) x, T.n - 1);
+    const float t = x - (float) i;
+    const float y0 = T.nodes[i].x, y1 = T.nodes[i + 1].x;
+    return y0 + t * (y1 - y0);
+}
+
+__device__ __forceinline__ float tab_eval(const TabView &T, V3 wo, V3 wi)
+{
+    return tab_eval_cos(T, (wo.x * wi.x + wo.y * wi.y) + wo.z * wi.z);
+}
+
+// largest i in [0, n - 1] with F_i <= x, through the guide table (cdf_find_guided over the interleaved nodes): the bracket
+// [guide[k - 1], guide[k + 1]] of x's guide cell holds two to four nodes where the density is high - one round of independent loads -
+// and the bisection starts from it elsewhere, instead of log2(N) dependent loads from [0, n]
+__device__ __forceinline__ int tab_find(const TabView &T, float x)
+{
+    const int n = T.n;
+    const int k = max(min((int) (x * (float) n), n - 1), 0);
+    int lo = min((int) T.guide[max(k - 1, 0)], n - 1), hi = min((int) T.guide[min(k + 1, n)] + 1, n);
+    if (hi - lo <= 4) {
+        const float c1 = T.nodes[min(lo + 1, n)].y, c2 = T.nodes[min(lo + 2, n)].y, c3 = T.nodes[min(lo + 3, n)].y;
+        return lo + ((lo + 1 < hi && c1 <= x) ? 1 : 0) + ((lo + 2 < hi && c2 <= x) ? 1 : 0) + ((lo + 3 < hi && c3 <= x) ? 1 : 0);
+    }
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (T.nodes[mid].y <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// (mu: the cosine dot(wo, wi) of the sampled direction, tab_eval_cos(T, mu) = pdf up to the rounding of c)
+__device__ __forceinline__ V3 tab_sample(const TabView &T, float ux, float uy, V3 wi, float &pdf, float &mu)
+{
+    const int i = tab_find(T, ux);
+    const float2 a = T.nodes[i], b = T.nodes[i + 1];
+    const float delta = 2.0f / (float) T.n;
+    const float s = kTabTwoPi * delta;
+    const float r = ux - a.y;
+    float t;
+    if (a.x == b.x) t = r / (s * a.x);
+    else {
+        const float rp = r / s;
+        const float disc = fmaxf(0.0f, a.x * a.x + (2.0f * (b.x - a.x)) * rp);
+        t = (a.x - sqrtf(disc)) / (a.x - b.x);
+    }
+    t = fminf(fmaxf(t, 0.0f), 1.0f);
+    const float cos_t = fminf(fmaxf(-1.0f + ((float) i + t) * delta, -1.0f), 1.0f);
+    const float sin_t = sqrtf(fmaxf(0.0f, 1.0f - cos_t * cos_t));
+    float sp, cp;
+    drt_sincos_2pi(uy, sp, cp);
+    const float lx = sin_t * cp, ly = sin_t * sp, lz = -cos_t;
+    // Frame3f(wi) as in hg_sample (restated: a helper shared with hg_sample changed the instruction streams of the existing HG kernels)
+    const float sgn = wi.z >= 0.0f ? 1.0f : -1.0f, msg = copysignf(1.0f, wi.z);
+    const float fa = -1.0f / (sgn + wi.z);
+    const float fb = (wi.x * wi.y) * fa;
+    const V3 fs = v3(msg * ((wi.x * wi.x) * fa) + 1.0f, msg * fb, -msg * wi.x);
+    const V3 ft = v3(fb, fmaf(wi.y, wi.y * fa, sgn), -wi.y);
+    mu = -cos_t;
+    pdf = a.x + t * (b.x - a.x);
+    return v3((fs.x * lx + ft.x * ly) + wi.x * lz, (fs.y * lx + ft.y * ly) + wi.y * lz, (fs.z * lx + ft.z * ly) + wi.z * lz);
+}
+
+__device__ __forceinline__ V3 tab_sample(const TabView &T, float ux, float uy, V3 wi, float &pdf)
+{
+    float mu;
+    return tab_sample(T, ux, uy, wi, pdf, mu);
+}
 
 // ---------------------------------------------------------------------------
 // envmap emitter [M3-ext] (volpathsimple.py:273,284,419; include/drt_hip.h: drt_set_emitter_envmap)

@@ -910,6 +910,12 @@ __global__ void __launch_bounds__(256) debug_eval_kernel(const Params P, int op,
             o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = pdf;
         } break;
         case 19: o[0] = hg2_eval(P.phase_g, P.phase_tg, P.phase_w, v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5])); break;   // ... eval (wo, wi)
+        case 20: {                                      // tabulated phase sample (ux, uy, wi) with the handle's table -> wo, pdf; o[4] = mu
+            float pdf, mu;
+            V3 d = tab_sample(tab_view(P), a[0], a[1], v3(a[2], a[3], a[4]), pdf, mu);
+            o[0] = d.x; o[1] = d.y; o[2] = d.z; o[3] = pdf; o[4] = mu;
+        } break;
+        case 21: o[0] = tab_eval(tab_view(P), v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5])); break;   // ... eval (wo, wi)
         case 9: if (P.mgrid) { o[0] = P.mgrid[__float_as_uint(a[0])]; } break;
         case 8: o[0] = mis_weight(a[0], a[1]); o[1] = a[0] / a[1]; o[2] = sqrtf(a[0]); o[3] = fmaf(a[0], a[1], a[2]); break;
         default: break;
@@ -1038,6 +1044,7 @@ template <typename F> hipError_t coop_cell(const Params &P, Phase phase, F f)
     case Phase::kHG: return coop_cell<Phase::kHG>(P, f);
     case Phase::kHGGrad: return coop_cell<Phase::kHGGrad>(P, f);
     case Phase::kHG2: return coop_cell<Phase::kHG2>(P, f);
+    case Phase::kTab: return coop_cell<Phase::kTab>(P, f);
     }
     return hipErrorInvalidValue;
 }
@@ -1061,6 +1068,7 @@ hipError_t launch_trace_sq(const Params &P, Phase phase, bool adjoint, bool coun
     case Phase::kHG: return SqUnit<Phase::kHG>::trace(P, adjoint, count, n_cus, stream);
     case Phase::kHGGrad: return SqUnit<Phase::kHGGrad>::trace(P, adjoint, count, n_cus, stream);
     case Phase::kHG2: return SqUnit<Phase::kHG2>::trace(P, adjoint, count, n_cus, stream);
+    case Phase::kTab: return SqUnit<Phase::kTab>::trace(P, adjoint, count, n_cus, stream);
     }
     return hipErrorInvalidValue;
 }

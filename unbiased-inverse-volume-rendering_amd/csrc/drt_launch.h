@@ -61,7 +61,7 @@ hipError_t launch_trace_super(const Params &P, bool adjoint, bool count, int n_c
 // the same scenes as work queues inside a compute unit: rays live in LDS records and belong to no lane, waves take batches of
 // one kind of work (drt_sq_kernel.h; round 4).  Uses the ray order and the XCD queues of launch_trace_super; the adjoint needs
 // Params::sq_cold (sq_cold_bytes(n_cus) bytes).  The kernels of a phase are one unit each (SqUnit: drt_sq.hip isotropic, drt_sq_hg.hip kHG and
-// kHGGrad, drt_sq_hg2.hip kHG2).  kHG, kHGGrad, kHG2: no tail launch (Params::tail_pool / tail_mode must be unset).  kHGGrad: adjoint launches
+// kHGGrad, drt_sq_hg2.hip kHG2, drt_sq_tab.hip kTab).  kHG, kHGGrad, kHG2, kTab: no tail launch (Params::tail_pool / tail_mode must be unset).  kHGGrad: adjoint launches
 // only, `count` is ignored (no counting kernels: such a launch counts nothing); dLoss/dg is added to *Params::L_out, one atomic per wave
 bool sq_supported(const Params &P);
 size_t sq_cold_bytes(int n_cus);
@@ -83,7 +83,7 @@ hipError_t build_super_order(const Params &P, uint32_t unit, uint32_t units, voi
 hipError_t build_unit_empty(const Params &P, uint32_t unit, uint32_t units, uint8_t *flags, hipStream_t stream);
 // One ray per lane (CoopTracer, drt_coop_tracer.h), every phase function and either AD mode.  The kernels are chosen from Params: the global
 // majorant (P.mgrid == nullptr: wave-cooperative tracking loops) or a majorant supergrid (own-lane tracking steps), the colour grids on sigma_t's
-// lattice or their own (P.colour_own).  kHG, kHGGrad, kHG2: no tail pool, no hand-off.  kHGGrad: adjoint launches only (hipErrorInvalidValue
+// lattice or their own (P.colour_own).  kHG, kHGGrad, kHG2, kTab: no tail pool, no hand-off.  kHGGrad: adjoint launches only (hipErrorInvalidValue
 // otherwise, without Params::L_out or with a tail pool), `count` is ignored (no counting kernels: such a launch counts nothing); dLoss/dg is
 // added to *Params::L_out, one atomic per wave.
 // `between` (optional; isotropic, global majorant, sigma_t's lattice): called on the host after the main launch has been enqueued and before
@@ -96,7 +96,7 @@ hipError_t launch_trace_coop(const Params &P, Phase phase, bool adjoint, bool co
 hipError_t launch_trace_coop_fwd(const Params &P, Phase phase, hipStream_t stream);
 // ... what a unit contributes to the two: the kernels of one cell (phase, majorant kind, lattice).  Members defined in drt_coop_kernel.h; the
 // drt_coop*.hip (global majorant), drt_coop_super*.hip (supergrid) and drt_own*.hip (own lattice, both kinds) units instantiate their cells,
-// the plain units kIso, the _hg units kHG and kHGGrad, the _hg2 units kHG2
+// the plain units kIso, the _hg units kHG and kHGGrad, the _hg2 units kHG2, the _tab units kTab
 template <Phase PH, bool SUPER, bool OWN> struct CoopUnit {
     static hipError_t trace(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx, bool *called);
     static hipError_t forward(const Params &P, hipStream_t stream);

@@ -6,6 +6,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <stdexcept>
@@ -85,6 +86,12 @@ public:
     void set_colour_resolution(std::array<int32_t, 3> res) { check(drt_set_colour_resolution(h_, res.data()), "drt_set_colour_resolution"); }
     void set_phase(int32_t kind, float g) { check(drt_set_phase(h_, kind, g), "drt_set_phase"); }
     void set_phase_hg2(float g1, float g2, float weight) { check(drt_set_phase_hg2(h_, g1, g2, weight), "drt_set_phase_hg2"); }
+    void set_phase_tab(const std::vector<float> &values)        // (a host list, copied by the library)
+    {
+        int rc;
+        { py::gil_scoped_release nogil; rc = drt_set_phase_tab(h_, values.data(), (int32_t) std::min<size_t>(values.size(), 0x7fffffffu)); }
+        check(rc, "drt_set_phase_tab");
+    }
     void params_changed()
     {
         int rc;
@@ -547,6 +554,7 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("set_colour_resolution", &Integrator::set_colour_resolution)
         .def("set_phase", &Integrator::set_phase, py::arg("kind"), py::arg("g") = 0.0f)
         .def("set_phase_hg2", &Integrator::set_phase_hg2, py::arg("g1"), py::arg("g2"), py::arg("weight"))
+        .def("set_phase_tab", &Integrator::set_phase_tab, py::arg("values"))
         .def("nerf_tile_lds_adds", &Integrator::nerf_tile_lds_adds)
         .def("params_changed", &Integrator::params_changed)
         .def("set_emitter_constant", &Integrator::set_emitter_constant)

@@ -285,11 +285,13 @@ __device__ __forceinline__ void sq_push_all(unsigned long long *ctl, uint16_t *q
 // kHG2 (H2; drt_sq_hg2.hip): the mixture of two Henyey-Greenstein lobes (drt_set_phase_hg2; g1 in Params::phase_g, g2 in
 // Params::phase_tg, the second lobe's share in Params::phase_w) at the same three sites.  The record is the HG one: {wi, last pdf} holds the MIXTURE's
 // pdf at the sampled direction, and the lobe is chosen by the next_1d draw the other instantiations drop - nothing else has to travel.
+// kTab (TB; drt_sq_tab.hip): the tabulated phase function (drt_set_phase_tab; drt_device.h: tab_eval, tab_sample) at the same sites, its table
+// behind Params::majorant (tab_view).  The record is the HG one.
 template <bool ADJ, bool COUNT, bool ENV, bool MG, bool QUAD = false, bool TAILM = false, bool ROUNDS = false, Phase PH = Phase::kIso>
 __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P)
 {
-    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2;
-    static_assert(!HG || (!TAILM && !ROUNDS), "the HG kernels (kHG, kHGGrad, kHG2) have no tail launch and no ROUNDS variant");
+    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2, TB = PH == Phase::kTab;
+    static_assert(!HG || (!TAILM && !ROUNDS), "the HG kernels (kHG, kHGGrad, kHG2, kTab) have no tail launch and no ROUNDS variant");
     static_assert(!GG || ADJ, "the g-gradient kernels (kHGGrad) are adjoint kernels");
     constexpr int NWV = DRT_SQ_THREADS / 64;
     constexpr int R4 = 7;                                                    // uint4 per ray record in LDS
@@ -1052,6 +1054,15 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                         contrib[k] = ((beta[k] * pv) * w) * (val[k] * wt);
                         result[k] = (ADJ && !rec_mode) ? result[k] - contrib[k] : result[k] + contrib[k];   // :211-214
                     }
+                } else if constexpr (TB) {                                  // ... of the table
+                    const float4 hw = cold_h[id];
+                    const float pv = tab_eval(tab_view(P), rd, v3(hw.x, hw.y, hw.z));
+                    const float w = mis_weight(ds_pdf, pv);                 // :391
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        contrib[k] = ((beta[k] * pv) * w) * (val[k] * wt);
+                        result[k] = (ADJ && !rec_mode) ? result[k] - contrib[k] : result[k] + contrib[k];   // :211-214
+                    }
                 } else if constexpr (HG) {                                  // phase_val = phase_pdf = eval(rd, wi) (:386-388)
                     const float4 hw = cold_h[id];
                     const float pv = hg_eval(P.phase_g, rd, v3(hw.x, hw.y, hw.z));
@@ -1142,6 +1153,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                         float4 hw = cold_h[id];
                         const V3 wi = P.use_nee ? v3(hw.x, hw.y, hw.z) : v3(-rd.x, -rd.y, -rd.z);
                         if constexpr (H2) rd = hg2_sample(P.phase_g, P.phase_tg, P.phase_w, u1, ux, uy, wi, hw.w);
+                        else if constexpr (TB) rd = tab_sample(tab_view(P), ux, uy, wi, hw.w);
                         else if constexpr (GG) {                                     // the score term: s(mu) <dL, result> (result: L below this vertex)
                             float mu;
                             rd = hg_sample(P.phase_g, ux, uy, wi, hw.w, mu);

@@ -251,9 +251,12 @@ class _DeviceIntegrator:
         # changing it rebuilds nothing - the library only drops the plans it made from the old paths
         ph = _check_phase(m.phase)
         two_lobe = int(ph.kind) == 2            # HG2Phase: drt_set_phase_hg2 (three parameters)
-        pkey = (2, float(ph.g1), float(ph.g2), float(ph.weight)) if two_lobe else (int(ph.kind), float(ph.g))
+        table = int(ph.kind) == 3               # TabPhase: drt_set_phase_tab (a host list, copied by the library)
+        pkey = (3, ph) if table else (2, float(ph.g1), float(ph.g2), float(ph.weight)) if two_lobe else (int(ph.kind), float(ph.g))
         if self._bound_phase.get(idx) != pkey:
-            if two_lobe:
+            if table:
+                h.set_phase_tab(list(ph.values))
+            elif two_lobe:
                 h.set_phase_hg2(*pkey[1:])
             else:
                 h.set_phase(*pkey)

@@ -158,6 +158,150 @@ class HG2Phase:
         object.__setattr__(self, "weight", w)
 
 
+TAB_MIN_NODES, TAB_MAX_NODES = 2, 65536
+
+
+class TabPhase:
+    """Mitsuba's `tabphase`: a phase function given as a table over the cosine of the scattering angle - how measured and Mie phase
+    functions (a diffraction peak plus a fogbow or glory, which no one- or two-lobe HG reproduces) enter a scene.
+
+    `values[i] >= 0`, i = 0 .. N - 1, 2 <= N <= 65536, all finite, at least one positive, at the N equally spaced nodes
+    c_i = -1 + 2 i / (N - 1) of the PHYSICS cosine c = -dot(wo, wi) (wi = -d_in; c = +1 is forward scattering: `tabphase`'s layout).
+    Linear between the nodes and normalised here: eval = f(c) / (2 pi I), I = the trapezoid integral of f over [-1, 1].  The kernels take the
+    values as float32.  Hashable and comparable by its values.  No gradients with respect to the values (PHASE_G_KEY is refused for such
+    a medium); node spacing is uniform only.
+
+    `.eval(mu)` and `.sample(u1, u2, wi)` restate the device functions in float64 for host tests (mu = dot(wo, wi) = -c, as HG's)."""
+    kind = 3        # DRT_PHASE_TAB
+
+    def __init__(self, values):
+        if isinstance(values, (str, bytes)) or np.isscalar(values) or values is None:
+            raise TypeError(f"TabPhase.values must be a sequence of real numbers, got {type(values).__name__}")
+        try:
+            arr = np.asarray(values)
+        except Exception as e:                                               # (ragged input and the like)
+            raise TypeError(f"TabPhase.values must be a sequence of real numbers: {e}") from None
+        if arr.dtype == np.bool_ or not (np.issubdtype(arr.dtype, np.floating) or np.issubdtype(arr.dtype, np.integer)):
+            raise TypeError(f"TabPhase.values must hold real numbers, got dtype {arr.dtype}")
+        if arr.ndim != 1:
+            raise ValueError(f"TabPhase.values must be one-dimensional, got shape {arr.shape}")
+        if not TAB_MIN_NODES <= arr.shape[0] <= TAB_MAX_NODES:
+            raise ValueError(f"TabPhase.values must have between {TAB_MIN_NODES} and {TAB_MAX_NODES} nodes, got {arr.shape[0]}")
+        with np.errstate(over="ignore"):
+            v32 = arr.astype(np.float32)                                     # (the kernels take the values as float32)
+        if not np.all(np.isfinite(v32)) or np.any(v32 < 0):
+            raise ValueError("TabPhase.values must be finite (in float32 too) and >= 0")
+        if not np.any(v32 > 0):
+            raise ValueError("TabPhase.values must hold at least one positive value (the table is all zero)")
+        self._values = tuple(float(v) for v in v32)
+        self._hash = hash((3, v32.tobytes()))
+        # the host's preparation (drt_set_phase_tab), float64: density nodes p_i = v_i / (2 pi I), CDF nodes F_i
+        v = v32.astype(np.float64)
+        n = v.shape[0] - 1
+        cum = np.concatenate([[0.0], np.cumsum(0.5 * (v[:-1] + v[1:]) * (2.0 / n))])
+        self._p = v / (2.0 * math.pi * cum[-1])
+        self._F = cum / cum[-1]
+        self._F[0], self._F[-1] = 0.0, 1.0
+
+    @property
+    def values(self):
+        """The table as the kernels take it (float32 values, as a tuple of floats)."""
+        return self._values
+
+    @property
+    def g(self) -> float:                                                    # (no asymmetry parameter: what the one-parameter helpers read)
+        return 0.0
+
+    def __len__(self):
+        return len(self._values)
+
+    def __eq__(self, other):
+        return isinstance(other, TabPhase) and self._values == other._values
+
+    def __hash__(self):
+        return self._hash
+
+    def __repr__(self):
+        n = len(self._values)
+        body = ", ".join(f"{v:g}" for v in self._values[:4]) + (", ..." if n > 4 else "")
+        return f"TabPhase([{body}], n={n})"
+
+    @classmethod
+    def from_function(cls, f, n: int):
+        """The table of `f(c)`, c the physics cosine (+1 forward), at n equally spaced nodes."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+            raise TypeError(f"TabPhase.from_function: n must be an integer, got {type(n).__name__}")
+        if not TAB_MIN_NODES <= n <= TAB_MAX_NODES:
+            raise ValueError(f"TabPhase.from_function: n must lie in [{TAB_MIN_NODES}, {TAB_MAX_NODES}], got {n}")
+        c = -1.0 + 2.0 * np.arange(int(n), dtype=np.float64) / (int(n) - 1)
+        return cls(np.asarray([float(f(float(x))) for x in c], dtype=np.float64))
+
+    @classmethod
+    def from_hg(cls, g: float, n: int):
+        """Henyey-Greenstein with asymmetry g, tabulated at n nodes (g > 0 scatters forward)."""
+        g = float(g)
+        if not math.isfinite(g) or not abs(g) < 1.0:
+            raise ValueError(f"TabPhase.from_hg: g must be finite with |g| < 1, got {g}")
+        return cls.from_function(lambda c: (1.0 - g * g) / (4.0 * math.pi * (1.0 + g * g - 2.0 * g * c) ** 1.5), n)
+
+    def eval(self, mu):
+        """The density per solid angle at mu = dot(wo, wi) (= -c), float64."""
+        mu = np.asarray(mu, dtype=np.float64)
+        n = len(self._values) - 1
+        x = np.clip((1.0 - mu) * (0.5 * n), 0.0, float(n))
+        i = np.minimum(x.astype(np.int64), n - 1)
+        t = x - i
+        out = self._p[i] + t * (self._p[i + 1] - self._p[i])
+        return float(out) if out.ndim == 0 else out
+
+    def cdf(self, c):
+        """P(cosine <= c) of the physics cosine, float64."""
+        c = np.asarray(c, dtype=np.float64)
+        n = len(self._values) - 1
+        delta = 2.0 / n
+        x = np.clip((c + 1.0) / delta, 0.0, float(n))
+        i = np.minimum(x.astype(np.int64), n - 1)
+        t = x - i
+        y0, y1 = self._p[i], self._p[i + 1]
+        out = self._F[i] + 2.0 * math.pi * delta * (y0 * t + 0.5 * (y1 - y0) * t * t)
+        return float(out) if out.ndim == 0 else out
+
+    def sample_cos(self, u1):
+        """The inverted CDF: the physics cosine c and the pdf of u1 in [0, 1), float64."""
+        u1 = np.asarray(u1, dtype=np.float64)
+        n = len(self._values) - 1
+        delta = 2.0 / n
+        i = np.clip(np.searchsorted(self._F, u1, side="right") - 1, 0, n - 1)
+        y0, y1 = self._p[i], self._p[i + 1]
+        rp = (u1 - self._F[i]) / (2.0 * math.pi * delta)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            flat = rp / y0
+            root = (y0 - np.sqrt(np.maximum(0.0, y0 * y0 + 2.0 * (y1 - y0) * rp))) / (y0 - y1)
+        t = np.where(y0 == y1, flat, root)
+        t = np.clip(np.where(np.isnan(t), 0.0, t), 0.0, 1.0)
+        c = np.clip(-1.0 + (i + t) * delta, -1.0, 1.0)
+        return c, y0 + t * (y1 - y0)
+
+    def sample(self, u1, u2, wi):
+        """Directions wo [n, 3] and their pdf for draws u1, u2 and incoming directions wi = -d_in (unit vectors: one, or a row per draw),
+        float64: the frame and azimuth of the `hg` sampler with cos_theta = c."""
+        c, pdf = self.sample_cos(u1)
+        c, pdf = np.atleast_1d(c), np.atleast_1d(pdf)
+        u2 = np.atleast_1d(np.asarray(u2, dtype=np.float64))
+        wi = np.broadcast_to(np.asarray(wi, dtype=np.float64), (c.shape[0], 3))
+        x, y, z = wi[:, 0], wi[:, 1], wi[:, 2]
+        sin_t = np.sqrt(np.maximum(0.0, 1.0 - c * c))
+        lx, ly, lz = sin_t * np.cos(2.0 * math.pi * u2), sin_t * np.sin(2.0 * math.pi * u2), -c
+        sgn = np.where(z >= 0.0, 1.0, -1.0)
+        msg = np.copysign(1.0, z)
+        a = -1.0 / (sgn + z)
+        b = x * y * a
+        s = [msg * (x * x * a) + 1.0, msg * b, -msg * x]
+        t = [b, y * y * a + sgn, -y]
+        wo = np.stack([s[k] * lx + t[k] * ly + wi[:, k] * lz for k in range(3)], axis=1)
+        return wo, pdf
+
+
 def check_phase_g(g, device=None):
     """A g parameter of render(params={PHASE_G_KEY: g}): a 0-d float32 tensor on the device (it may require grad)."""
     import torch
@@ -175,21 +319,24 @@ def require_hg(scene, what: str):
     if isinstance(scene.medium.phase, HG2Phase):
         raise ValueError(f"{what}: HG2Phase has no phase-parameter gradients yet - {PHASE_G_KEY} (and gradients with respect to g1, g2 "
                          "and weight) are the follow-up; optimise the grids, or use HGPhase(g) for a single differentiable lobe")
+    if isinstance(scene.medium.phase, TabPhase):
+        raise ValueError(f"{what}: TabPhase has no phase-parameter gradients - it has no g, so {PHASE_G_KEY} does not apply, and gradients "
+                         "with respect to the table values are not built; optimise the grids, or use HGPhase(g) for a differentiable lobe")
     if not isinstance(scene.medium.phase, HGPhase):
         raise ValueError(f"{what}: a gradient with respect to {PHASE_G_KEY} needs GridMedium(phase=HGPhase(g)); the medium's phase "
                          f"function is {type(scene.medium.phase).__name__} - use HGPhase(0.0) for an isotropic medium whose g is optimised")
 
 
 def _check_phase(phase):
-    if not isinstance(phase, (IsotropicPhase, HGPhase, HG2Phase)):
-        raise TypeError(f"GridMedium.phase must be IsotropicPhase(), HGPhase(g) or HG2Phase(g1, g2, weight), got {type(phase).__name__}")
+    if not isinstance(phase, (IsotropicPhase, HGPhase, HG2Phase, TabPhase)):
+        raise TypeError(f"GridMedium.phase must be IsotropicPhase(), HGPhase(g), HG2Phase(g1, g2, weight) or TabPhase(values), got {type(phase).__name__}")
     return phase
 
 
 @dataclass
 class GridMedium:
     """`heterogeneous` medium with `gridvolume` sigma_t / albedo and a phase function
-    (`IsotropicPhase()`, the default, `HGPhase(g)` or `HG2Phase(g1, g2, weight)`), bounded by an axis-aligned box
+    (`IsotropicPhase()`, the default, `HGPhase(g)`, `HG2Phase(g1, g2, weight)` or `TabPhase(values)`), bounded by an axis-aligned box
     (tests/test_integrators.py:79-111).
 
     sigma_t : (Z, Y, X, 1) float32, albedo : (Z, Y, X, 3) float32 - numpy arrays or
