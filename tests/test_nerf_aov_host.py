@@ -16,12 +16,12 @@ def test_library_exports_the_aov_calls(uivr, hooks):
     lib = ctypes.CDLL(library_path(hooks))
     for n in AOV_SYMBOLS:
         assert hasattr(lib, n), f"{library_path(hooks)} does not export {n}"
-    # the AOV instantiations of the shared kernels are in the library beside the plain ones: the window kernel for both kinds of lookup,
-    # the per-lane primal, both adjoint routes (records / apron scratch) and forward mode
+    # the AOV instantiations of the shared kernels are in the library beside the plain ones: the window kernel for both kinds of lookup
+    # (PlainWindow<G4>, AOV), the per-lane primal, both adjoint routes (records / apron scratch) and forward mode (PlainEmission, ..., AOV)
     blob = open(library_path(hooks), "rb").read()
-    for k in (b"nerf_tile_adjoint_kernelILb0ELb1EE", b"nerf_tile_adjoint_kernelILb1ELb1EE", b"nerf_tile_adjoint_kernelILb0ELb0EE",
-              b"nerf_tile_adjoint_kernelILb1ELb0EE", b"nerf_kernelILb0ELb0ELb0ELb1EE", b"nerf_kernelILb1ELb0ELb1ELb1EE",
-              b"nerf_kernelILb1ELb0ELb0ELb1EE", b"nerf_kernelILb0ELb0ELb0ELb0EE", b"nerf_fwd_kernelILb1EE", b"nerf_fwd_kernelILb0EE"):
+    for k in (b"nerf_tile_adjoint_kernelINS0_11PlainWindowILb0EEELb1EJEE", b"nerf_tile_adjoint_kernelINS0_11PlainWindowILb1EEELb1EJEE", b"nerf_tile_adjoint_kernelINS0_11PlainWindowILb0EEELb0EJEE",
+              b"nerf_tile_adjoint_kernelINS0_11PlainWindowILb1EEELb0EJEE", b"nerf_kernelINS0_13PlainEmissionELb0ELb0ELb0ELb1EJEE", b"nerf_kernelINS0_13PlainEmissionELb1ELb0ELb1ELb1EJEE",
+              b"nerf_kernelINS0_13PlainEmissionELb1ELb0ELb0ELb1EJEE", b"nerf_kernelINS0_13PlainEmissionELb0ELb0ELb0ELb0EJEE", b"nerf_fwd_kernelINS0_13PlainEmissionELb1EJEE", b"nerf_fwd_kernelINS0_13PlainEmissionELb0EJEE"):
         assert k in blob, k
 
 

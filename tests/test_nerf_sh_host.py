@@ -15,9 +15,9 @@ def test_library_exports_the_sh_calls(uivr, hooks):
     lib = ctypes.CDLL(library_path(hooks))
     for n in SH_SYMBOLS:
         assert hasattr(lib, n), f"{library_path(hooks)} does not export {n}"
-    # the window kernel is in the production library, for both K
+    # the window kernel is in the production library, for both K: the shared kernel with the SH window configuration
     blob = open(library_path(hooks), "rb").read()
-    assert b"nerf_sh_tile_kernelILi4E" in blob and b"nerf_sh_tile_kernelILi9E" in blob
+    assert b"nerf_tile_adjoint_kernelINS0_8ShWindowILi4EEELb0EJ" in blob and b"nerf_tile_adjoint_kernelINS0_8ShWindowILi9EEELb0EJ" in blob
 
 
 def test_sh_basis_is_orthonormal(uivr):

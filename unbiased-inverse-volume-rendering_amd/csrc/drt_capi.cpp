@@ -923,6 +923,21 @@ int run_backward(drt_handle h, drt::Params &P, uint32_t per_ray_sigma, uint32_t 
 
 }  // namespace
 
+// One launch that is a whole nerf adjoint pass - the window kernel of the plain, SH and opacity / depth calls, and the SH calls' per-lane adjoint
+// of explicit ray batches: the tracer slot and the whole-pass slot around it (the pass is this launch), and `bounds_bytes` of device scratch
+// for the window's bounds reduction (0: a launch that needs none, called with nullptr)
+template <class Launch> static int nerf_adjoint_pass(drt_handle h, hipStream_t st, size_t bounds_bytes, Launch launch)
+{
+    TimedSpan tracer, whole;
+    DRT_HIP_CHECK(h, tracer.begin(h, st));
+    DRT_HIP_CHECK(h, whole.begin(h, st));
+    if (bounds_bytes) DRT_TRY(h->nerf_bounds.grow(h, bounds_bytes, kMust));
+    DRT_HIP_CHECK(h, launch(bounds_bytes ? h->nerf_bounds.as<uint32_t>() : nullptr));
+    DRT_HIP_CHECK(h, tracer.end(1));
+    DRT_HIP_CHECK(h, whole.end(3));
+    return DRT_OK;
+}
+
 extern "C" {
 
 const char *drt_version(void) { return drt::kTestHooks ? "drt-hip 0.2 (gfx950, test hooks)" : "drt-hip 0.2 (gfx950)"; }
@@ -1536,16 +1551,8 @@ static int ensure_grid4(drt_handle h, drt::Params &P, const float *rgb);
 static int nerf_backward(drt_handle h, drt::Params &P, const drt_nerf_config *cfg, bool g4, hipStream_t st = nullptr)
 {
     if (!st) st = h->stream;
-    if (drt::nerf_tile_supported(P) && !dbg(h->debug_flags, kHookNerfRecordPath)) {
-        TimedSpan tracer, whole;                                     // (tracer slot and whole-pass slot: the pass is this launch)
-        DRT_HIP_CHECK(h, tracer.begin(h, st));
-        DRT_HIP_CHECK(h, whole.begin(h, st));
-        DRT_TRY(h->nerf_bounds.grow(h, 32, kMust));
-        DRT_HIP_CHECK(h, drt::launch_nerf_tile_adjoint(P, g4, h->counting, h->nerf_bounds.as<uint32_t>(), st));
-        DRT_HIP_CHECK(h, tracer.end(1));
-        DRT_HIP_CHECK(h, whole.end(3));
-        return DRT_OK;
-    }
+    if (drt::nerf_tile_supported(P) && !dbg(h->debug_flags, kHookNerfRecordPath))
+        return nerf_adjoint_pass(h, st, 32, [&](uint32_t *bounds) { return drt::launch_nerf_tile_adjoint(P, g4, h->counting, bounds, st); });
     const uint32_t q = (uint32_t) cfg->queries_per_ray;          // at most one splat per query and plane
     return run_backward(h, P, q, q, [&](drt::Params &Q) { return timed_nerf(h, 1, Q, true); });
 }
@@ -2127,54 +2134,63 @@ int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const 
                                 grad_emission);
 }
 
-// ---- nerf with spherical-harmonic emission (drt_nerf_sh.hip) -------------------------------------------------------------------------------
-// the checks the four *_sh calls share, the job and the interleaved voxel copy of this call's grids.  The test hooks that route the plain nerf
-// adjoint elsewhere (record path, atomic gradients into the apron scratch, per-lane / no gradient atomics) have no SH kernels: refused
-static int nerf_sh_job(drt_handle h, const char *what, drt::Params &P, drt::NerfSh &S, const drt_nerf_config *cfg, const float *sh,
-                       int32_t sh_degree, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
-                       uint32_t seed, bool adjoint)
+// ---- the nerf variants: spherical-harmonic emission (drt_nerf_sh.hip) and opacity / depth outputs (drt_nerf_aov.hip) ---------------------------
+// what the messages of a variant's calls name
+struct NerfVariant { const char *grid, *own_lattice, *kernels; };
+static constexpr NerfVariant kNerfSh = { "sh", "own-lattice SH is not supported", "SH" };
+static constexpr NerfVariant kNerfAov = { "emission", "own-lattice opacity / depth outputs are not supported", "opacity / depth" };
+
+// What the eight *_sh / *_aov calls share: the checks, the job, and - sh_degree given: the SH calls - the interleaved voxel copy of this call's
+// grids; `body(P, S)` then checks the call's own buffers and launches.  Neither variant has own-lattice colour grids, nor kernels for the test
+// hooks that route the plain nerf adjoint elsewhere (record path, atomic gradients into the apron scratch, per-lane / no gradient atomics): refused
+extern "C++" template <class Body>
+static int nerf_variant_call(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid,
+                             const int32_t *sh_degree, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
+                             uint32_t spp, uint32_t seed, bool adjoint, Body body)
 {
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
+    DeviceGuard g(h->device);
     DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
-    if (sh_degree != 1 && sh_degree != 2)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: sh_degree must be 1 or 2, got %d", what, (int) sh_degree);
-    if (!cfg || !sh) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null config / sh grid", what);
+    if (sh_degree && *sh_degree != 1 && *sh_degree != 2)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: sh_degree must be 1 or 2, got %d", what, (int) *sh_degree);
+    if (!cfg || !grid) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null config / %s grid", what, v.grid);
     if (h->base.colour_own)
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the sh grid must share sigma_t's lattice (drt_set_colour_resolution gave the colour grids "
-                                            "their own: own-lattice SH is not supported)", what);
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the %s grid must share sigma_t's lattice (drt_set_colour_resolution gave the colour grids "
+                                            "their own: %s)", what, v.grid, v.own_lattice);
     constexpr uint32_t kUnhonoured = drt::kHookNerfRecordPath | drt::kHookAtomicGradients | drt::kHookNoGradAtomics | drt::kHookPerLaneAtomics;
     if (adjoint && dbg(h->debug_flags, kUnhonoured))
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: debug flags 0x%x route the nerf adjoint through paths the SH kernels do not have", what,
-                    (unsigned) (h->debug_flags & kUnhonoured));
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: debug flags 0x%x route the nerf adjoint through paths the %s kernels do not have", what,
+                    (unsigned) (h->debug_flags & kUnhonoured), v.kernels);
+    drt::Params P;
+    drt::NerfSh S = { nullptr, 0 };
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    DRT_TRY(nerf_fill(h, P, cfg, sh));
-    S.K = (sh_degree + 1) * (sh_degree + 1);
-    S.vox = nullptr;
-    if (n_rays == 0) return DRT_OK;
-    const size_t nv = (size_t) P.rx * P.ry * P.rz;
-    if (nv > 0x7fffffffull) return fail(h, DRT_ERR_UNSUPPORTED, "%s: grid too large for the interleaved voxel copy", what);
-    DRT_TRY(h->sh_vox.grow(h, nv * drt::sh_vox_floats(S.K) * sizeof(float), kMust));
-    DRT_HIP_CHECK(h, drt::launch_sh_interleave(P.sigma_t, sh, S.K, h->sh_vox.as<float4>(), nv, h->stream));
-    S.vox = h->sh_vox.as<float4>();
-    return DRT_OK;
+    DRT_TRY(nerf_fill(h, P, cfg, grid));
+    if (sh_degree) {
+        S.K = (*sh_degree + 1) * (*sh_degree + 1);
+        const size_t nv = (size_t) P.rx * P.ry * P.rz;
+        if (nv > 0x7fffffffull) return fail(h, DRT_ERR_UNSUPPORTED, "%s: grid too large for the interleaved voxel copy", what);
+        DRT_TRY(h->sh_vox.grow(h, nv * drt::sh_vox_floats(S.K) * sizeof(float), kMust));
+        DRT_HIP_CHECK(h, drt::launch_sh_interleave(P.sigma_t, grid, S.K, h->sh_vox.as<float4>(), nv, h->stream));
+        S.vox = h->sh_vox.as<float4>();
+    } else P.counters = nullptr;            // (the opacity / depth calls count nothing; a counting SH launch counts its window phases)
+    return body(P, S);
 }
 
 int drt_nerf_render_primal_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
                               const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
 {
-    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
-    DeviceGuard g(h->device);
-    drt::Params P; drt::NerfSh S;
-    DRT_TRY(nerf_sh_job(h, "drt_nerf_render_primal_sh", P, S, cfg, sh, sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, false));
-    if (n_rays == 0) return DRT_OK;
-    if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_primal_sh: null L_out");
-    P.L_out = L_out;
-    h->pcache_sig.valid = false;
-    TimedSpan span;
-    DRT_HIP_CHECK(h, span.begin(h, h->stream));
-    DRT_HIP_CHECK(h, drt::launch_nerf_sh(P, S, false, h->stream));
-    DRT_HIP_CHECK(h, span.end(0));
-    return DRT_OK;
+    return nerf_variant_call(h, "drt_nerf_render_primal_sh", kNerfSh, cfg, sh, &sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
+                             [&](drt::Params &P, const drt::NerfSh &S) {
+        if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_primal_sh: null L_out");
+        P.L_out = L_out;
+        h->pcache_sig.valid = false;
+        TimedSpan span;
+        DRT_HIP_CHECK(h, span.begin(h, h->stream));
+        DRT_HIP_CHECK(h, drt::launch_nerf_sh(P, S, false, h->stream));
+        DRT_HIP_CHECK(h, span.end(0));
+        return (int) DRT_OK;
+    });
 }
 
 // the SH adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given.  Sensor rays: the LDS-window kernel;
@@ -2183,102 +2199,65 @@ static int nerf_sh_backward(drt_handle h, drt::Params &P, const drt::NerfSh &S, 
                             float *grad_sigma_t, float *grad_sh)
 {
     P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_sh;
-    TimedSpan tracer, whole;
-    DRT_HIP_CHECK(h, tracer.begin(h, h->stream));
-    DRT_HIP_CHECK(h, whole.begin(h, h->stream));
-    if (drt::nerf_tile_supported(P)) {
-        DRT_TRY(h->nerf_bounds.grow(h, 32, kMust));
-        DRT_HIP_CHECK(h, drt::launch_nerf_sh_tile_adjoint(P, S, h->nerf_bounds.as<uint32_t>(), h->stream));
-    } else DRT_HIP_CHECK(h, drt::launch_nerf_sh(P, S, true, h->stream));
-    DRT_HIP_CHECK(h, tracer.end(1));
-    DRT_HIP_CHECK(h, whole.end(3));
-    return DRT_OK;
+    const bool tile = drt::nerf_tile_supported(P);
+    return nerf_adjoint_pass(h, h->stream, tile ? 32 : 0, [&](uint32_t *bounds) {
+        return tile ? drt::launch_nerf_sh_tile_adjoint(P, S, bounds, h->stream) : drt::launch_nerf_sh(P, S, true, h->stream);
+    });
 }
 
 int drt_nerf_render_backward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
                                 const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL,
                                 const float *L_in, float *grad_sigma_t, float *grad_sh)
 {
-    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
-    DeviceGuard g(h->device);
-    drt::Params P; drt::NerfSh S;
-    DRT_TRY(nerf_sh_job(h, "drt_nerf_render_backward_sh", P, S, cfg, sh, sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, true));
-    if (n_rays == 0) return DRT_OK;
-    if (!dL || !L_in || !grad_sigma_t || !grad_sh)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_sh: null dL / L_in / gradient buffer");
-    return nerf_sh_backward(h, P, S, dL, nullptr, L_in, grad_sigma_t, grad_sh);
+    return nerf_variant_call(h, "drt_nerf_render_backward_sh", kNerfSh, cfg, sh, &sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
+                             [&](drt::Params &P, const drt::NerfSh &S) {
+        if (!dL || !L_in || !grad_sigma_t || !grad_sh)
+            return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_sh: null dL / L_in / gradient buffer");
+        return nerf_sh_backward(h, P, S, dL, nullptr, L_in, grad_sigma_t, grad_sh);
+    });
 }
 
 int drt_nerf_render_backward_px_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
                                    const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
                                    const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t, float *grad_sh)
 {
-    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
-    DeviceGuard g(h->device);
-    drt::Params P; drt::NerfSh S;
-    DRT_TRY(nerf_sh_job(h, "drt_nerf_render_backward_px_sh", P, S, cfg, sh, sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, true));
-    if (!L_in || !grad_sigma_t || !grad_sh)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px_sh: null L_in / gradient buffer");
-    DRT_TRY(check_px(h, "drt_nerf_render_backward_px_sh", n_rays, spp, grad_image, n_pixels));
-    if (n_rays == 0) return DRT_OK;
-    return nerf_sh_backward(h, P, S, nullptr, grad_image, L_in, grad_sigma_t, grad_sh);
+    return nerf_variant_call(h, "drt_nerf_render_backward_px_sh", kNerfSh, cfg, sh, &sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
+                             [&](drt::Params &P, const drt::NerfSh &S) {
+        if (!L_in || !grad_sigma_t || !grad_sh)
+            return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px_sh: null L_in / gradient buffer");
+        DRT_TRY(check_px(h, "drt_nerf_render_backward_px_sh", n_rays, spp, grad_image, n_pixels));
+        return nerf_sh_backward(h, P, S, nullptr, grad_image, L_in, grad_sigma_t, grad_sh);
+    });
 }
 
 int drt_nerf_render_forward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
                                const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
                                const float *t_sigma_t, const float *t_sh, float *dL_out)
 {
-    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
-    DeviceGuard g(h->device);
-    drt::Params P; drt::NerfSh S;
-    DRT_TRY(nerf_sh_job(h, "drt_nerf_render_forward_sh", P, S, cfg, sh, sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, false));
-    if (n_rays == 0) return DRT_OK;
-    if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward_sh: null dL_out");
-    forward_params(P, t_sigma_t, t_sh, dL_out);
-    DRT_HIP_CHECK(h, drt::launch_nerf_sh_fwd(P, S, h->stream));
-    return DRT_OK;
+    return nerf_variant_call(h, "drt_nerf_render_forward_sh", kNerfSh, cfg, sh, &sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
+                             [&](drt::Params &P, const drt::NerfSh &S) {
+        if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward_sh: null dL_out");
+        forward_params(P, t_sigma_t, t_sh, dL_out);
+        DRT_HIP_CHECK(h, drt::launch_nerf_sh_fwd(P, S, h->stream));
+        return (int) DRT_OK;
+    });
 }
 
-// ---- nerf with opacity and depth outputs (drt_nerf_aov.hip): five interleaved floats [r, g, b, A, D] per ray / pixel ---------------------------
-// the checks the four *_aov calls share, and the job.  As the SH calls: no own-lattice colour grids, none of the test hooks that route the
-// plain adjoint elsewhere, no counters
-static int nerf_aov_job(drt_handle h, const char *what, drt::Params &P, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                        const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, bool adjoint)
-{
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
-    if (!cfg || !emission) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null config / emission grid", what);
-    if (h->base.colour_own)
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the emission grid must share sigma_t's lattice (drt_set_colour_resolution gave the colour "
-                                            "grids their own: own-lattice opacity / depth outputs are not supported)", what);
-    constexpr uint32_t kUnhonoured = drt::kHookNerfRecordPath | drt::kHookAtomicGradients | drt::kHookNoGradAtomics | drt::kHookPerLaneAtomics;
-    if (adjoint && dbg(h->debug_flags, kUnhonoured))
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: debug flags 0x%x route the nerf adjoint through paths the opacity / depth kernels do not have",
-                    what, (unsigned) (h->debug_flags & kUnhonoured));
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    DRT_TRY(nerf_fill(h, P, cfg, emission));
-    P.counters = nullptr;
-    return DRT_OK;
-}
-
+// ---- opacity and depth outputs: five interleaved floats [r, g, b, A, D] per ray / pixel ------------------------------------------------------
 int drt_nerf_render_primal_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
 {
-    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
-    DeviceGuard g(h->device);
-    drt::Params P;
-    DRT_TRY(nerf_aov_job(h, "drt_nerf_render_primal_aov", P, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, false));
-    if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_primal_aov: null L_out");
-    P.L_out = L_out;
-    h->pcache_sig.valid = false;
-    TimedSpan span;
-    DRT_HIP_CHECK(h, span.begin(h, h->stream));
-    DRT_HIP_CHECK(h, drt::launch_nerf_aov(P, false, h->stream));
-    DRT_HIP_CHECK(h, span.end(0));
-    return DRT_OK;
+    return nerf_variant_call(h, "drt_nerf_render_primal_aov", kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
+                             [&](drt::Params &P, const drt::NerfSh &) {
+        if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_primal_aov: null L_out");
+        P.L_out = L_out;
+        h->pcache_sig.valid = false;
+        TimedSpan span;
+        DRT_HIP_CHECK(h, span.begin(h, h->stream));
+        DRT_HIP_CHECK(h, drt::launch_nerf_aov(P, false, h->stream));
+        DRT_HIP_CHECK(h, span.end(0));
+        return (int) DRT_OK;
+    });
 }
 
 // the adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given.  Sensor rays: the LDS-window kernel (lookups
@@ -2291,9 +2270,6 @@ static int nerf_aov_backward(drt_handle h, drt::Params &P, const float *emission
     const bool g4 = tile && ensure_grid4(h, P, emission) == DRT_OK;   // (no memory / a grid beyond the copy's index range: the separate lookups)
     if (tile && !g4) (void) hipGetLastError();
     if (tile) {
-        TimedSpan tracer, whole;                                     // (tracer slot and whole-pass slot: the pass is this launch)
-        DRT_HIP_CHECK(h, tracer.begin(h, h->stream));
-        DRT_HIP_CHECK(h, whole.begin(h, h->stream));
         // a bound of t_in + t_b, a query's distance from the sensor's origin: the origin's distance to the box centre plus the half diagonal
         // (the spawn offset of the march's origin is 1e-4 of that: the margin covers it)
         double c2 = 0.0, d2 = 0.0;
@@ -2302,11 +2278,7 @@ static int nerf_aov_backward(drt_handle h, drt::Params &P, const float *emission
             c2 += c * c; d2 += e * e;
         }
         const float t_max = (float) ((std::sqrt(c2) + std::sqrt(d2)) * 1.01);
-        DRT_TRY(h->nerf_bounds.grow(h, 64, kMust));
-        DRT_HIP_CHECK(h, drt::launch_nerf_aov_tile_adjoint(P, g4, h->nerf_bounds.as<uint32_t>(), t_max, h->stream));
-        DRT_HIP_CHECK(h, tracer.end(1));
-        DRT_HIP_CHECK(h, whole.end(3));
-        return DRT_OK;
+        return nerf_adjoint_pass(h, h->stream, 64, [&](uint32_t *bounds) { return drt::launch_nerf_aov_tile_adjoint(P, g4, bounds, t_max, h->stream); });
     }
     const uint32_t q = (uint32_t) P.nerf_queries;                 // at most one splat per query and plane
     return run_backward(h, P, q, q, [&](drt::Params &Q) {
@@ -2322,14 +2294,12 @@ int drt_nerf_render_backward_aov(drt_handle h, const drt_nerf_config *cfg, const
                                  uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
                                  float *grad_sigma_t, float *grad_emission)
 {
-    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
-    DeviceGuard g(h->device);
-    drt::Params P;
-    DRT_TRY(nerf_aov_job(h, "drt_nerf_render_backward_aov", P, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, true));
-    if (!dL || !L_in || !grad_sigma_t || !grad_emission)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_aov: null dL / L_in / gradient buffer");
-    return nerf_aov_backward(h, P, emission, dL, nullptr, L_in, grad_sigma_t, grad_emission);
+    return nerf_variant_call(h, "drt_nerf_render_backward_aov", kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
+                             [&](drt::Params &P, const drt::NerfSh &) {
+        if (!dL || !L_in || !grad_sigma_t || !grad_emission)
+            return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_aov: null dL / L_in / gradient buffer");
+        return nerf_aov_backward(h, P, emission, dL, nullptr, L_in, grad_sigma_t, grad_emission);
+    });
 }
 
 int drt_nerf_render_backward_px_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
@@ -2337,30 +2307,26 @@ int drt_nerf_render_backward_px_aov(drt_handle h, const drt_nerf_config *cfg, co
                                     const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
                                     float *grad_emission)
 {
-    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
-    DeviceGuard g(h->device);
-    drt::Params P;
-    DRT_TRY(nerf_aov_job(h, "drt_nerf_render_backward_px_aov", P, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, true));
-    if (!L_in || !grad_sigma_t || !grad_emission)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px_aov: null L_in / gradient buffer");
-    DRT_TRY(check_px(h, "drt_nerf_render_backward_px_aov", n_rays, spp, grad_image, n_pixels));
-    return nerf_aov_backward(h, P, emission, nullptr, grad_image, L_in, grad_sigma_t, grad_emission);
+    return nerf_variant_call(h, "drt_nerf_render_backward_px_aov", kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
+                             [&](drt::Params &P, const drt::NerfSh &) {
+        if (!L_in || !grad_sigma_t || !grad_emission)
+            return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px_aov: null L_in / gradient buffer");
+        DRT_TRY(check_px(h, "drt_nerf_render_backward_px_aov", n_rays, spp, grad_image, n_pixels));
+        return nerf_aov_backward(h, P, emission, nullptr, grad_image, L_in, grad_sigma_t, grad_emission);
+    });
 }
 
 int drt_nerf_render_forward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
                                 const float *t_emission, float *dL_out)
 {
-    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
-    DeviceGuard g(h->device);
-    drt::Params P;
-    DRT_TRY(nerf_aov_job(h, "drt_nerf_render_forward_aov", P, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, false));
-    if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward_aov: null dL_out");
-    forward_params(P, t_sigma_t, t_emission, dL_out);
-    DRT_HIP_CHECK(h, drt::launch_nerf_aov_fwd(P, h->stream));
-    return DRT_OK;
+    return nerf_variant_call(h, "drt_nerf_render_forward_aov", kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
+                             [&](drt::Params &P, const drt::NerfSh &) {
+        if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward_aov: null dL_out");
+        forward_params(P, t_sigma_t, t_emission, dL_out);
+        DRT_HIP_CHECK(h, drt::launch_nerf_aov_fwd(P, h->stream));
+        return (int) DRT_OK;
+    });
 }
 
 int drt_film_develop_n(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image)

@@ -25,23 +25,28 @@ template <bool OWN> struct NerfUnit {
     static hipError_t forward(const Params &P, hipStream_t stream);
 };
 // drt_nerf_tile.hip: the nerf adjoint for sensor rays - a workgroup per pixel tile, its splats pre-reduced in an LDS window of 16^3 voxels, no records
+// (the window kernel itself: drt_nerf_tile_kernel.h, one kernel for the plain, opacity / depth and SH calls, by a compile-time configuration)
 // (g4: lookups from Params::grid4 - the fused pass, emission = the medium's albedo grid - instead of sigma_b + Params::emission)
 bool nerf_tile_supported(const Params &P);
 // bounds: 32 bytes of device scratch (the fixed-point units of the LDS window follow from max |dL|, max |L_in|, max |emission|, reduced there first)
 hipError_t launch_nerf_tile_adjoint(const Params &P, bool g4, bool count, uint32_t *bounds, hipStream_t stream);
 // drt_nerf_sh.hip: the nerf march with spherical-harmonic (view-dependent) emission, K = (degree + 1)^2 in {4, 9} coefficients per voxel and
 // colour channel.  The caller's sh grid (Z,Y,X,3K) travels in Params::emission, its gradient / tangent grid in Params::g_albedo; lookups
-// come from `vox`, an interleaved copy [sigma_t, sh[0..3K-1], 0..] of sh_vox_floats(K) floats per voxel made by launch_sh_interleave
+// come from `vox`, an interleaved copy [sigma_t, sh[0..3K-1], 0..] of sh_vox_floats(K) floats per voxel made by launch_sh_interleave.
+// It reaches the kernels inside their emission policy / window configuration, an argument of its own: Params does not grow (the tracers
+// are sensitive to its size, drt_device.h)
 struct NerfSh {
     const float4 *vox;
     int K;
 };
 size_t sh_vox_floats(int K);
 hipError_t launch_sh_interleave(const float *sigma_t, const float *sh, int K, float4 *vox, size_t n_voxels, hipStream_t stream);
-// one ray per lane: the primal, the adjoint (float atomics on the caller's grids: explicit ray batches - the untuned route) and forward mode
+// one ray per lane (nerf_kernel / nerf_fwd_kernel with the SH emission policy): the primal, the adjoint (float atomics on the caller's grids:
+// explicit ray batches - the untuned route) and forward mode
 hipError_t launch_nerf_sh(const Params &P, const NerfSh &S, bool adjoint, hipStream_t stream);
 hipError_t launch_nerf_sh_fwd(const Params &P, const NerfSh &S, hipStream_t stream);
-// the adjoint of sensor rays: drt_nerf_tile.hip's LDS window with 1 + 3K planes (same support predicate: nerf_tile_supported)
+// the adjoint of sensor rays: the window kernel of drt_nerf_tile_kernel.h with 1 + 3K planes (bounds: 32 bytes; same support predicate:
+// nerf_tile_supported).  With Params::counters set the launch counts its window phases in bounds[5]
 hipError_t launch_nerf_sh_tile_adjoint(const Params &P, const NerfSh &S, uint32_t *bounds, hipStream_t stream);
 // drt_nerf_aov.hip: the nerf march with two more outputs per ray, opacity A = weights_sum and depth D = sum weight (t_in + t_b): five interleaved
 // floats [r, g, b, A, D] in Params::L_out / dL / dL_pix / L_in.  One ray per lane (nerf_kernel / nerf_fwd_kernel with AOV = true): the primal,

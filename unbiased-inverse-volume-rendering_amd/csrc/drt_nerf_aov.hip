@@ -5,7 +5,7 @@
 //
 // t_in = si.t of the first box_hit (the ray's own origin -> the box), t_b the march parameter of query j from the offset point.  A ray that
 // misses the box has A = D = 0.  Every per-ray and per-pixel buffer holds five interleaved floats [r, g, b, A, D]; the colour channels are
-// the bits of the plain calls.  The march is nerf_kernel's (drt_nerf_kernel.h), statement for statement.
+// the bits of the plain calls.
 //
 // A and D are linear in an "emission" q_j = dA + dD (t_in + t_b,j) that no grid holds, so the adjoint adds one term to the sigma_t splat,
 //     q_j (-da T) + (S / safe_a) da,        S = dA A_in + dD D_in - sum_{i<=j, i+1<N} weight_i q_i   (as `result` is the colour's remainder)
@@ -13,14 +13,14 @@
 //
 // Kernels - the march exists once, in the shared headers, templated on an AOV flag; this unit instantiates AOV = true and the plain units
 // keep AOV = false (no copy of the per-lane march, none of the window machinery):
-//   nerf_kernel<false, ., ., true>        primal, one ray per lane, with the occupancy skip                            (drt_nerf_kernel.h)
-//   nerf_fwd_kernel<true>                 forward mode: dual numbers, dA = dweights_sum, dD = sum dweight (t_in + t_b); one write per ray,
+//   nerf_kernel<PlainEmission, false, ., ., true>   primal, one ray per lane, with the occupancy skip                            (drt_nerf_kernel.h)
+//   nerf_fwd_kernel<PlainEmission, true>  forward mode: dual numbers, dA = dweights_sum, dD = sum dweight (t_in + t_b); one write per ray,
 //                                         no atomics: repeats bit for bit                                               (drt_nerf_kernel.h)
-//   nerf_kernel<true, ., DEFER, true>     adjoint of EXPLICIT ray batches: one ray per lane, the RECORD route of the plain call (deferred
+//   nerf_kernel<PlainEmission, true, ., DEFER, true>   adjoint of EXPLICIT ray batches: one ray per lane, the RECORD route of the plain call (deferred
 //                                         splat records, drt_deferred.hip; without record memory the atomic path into the apron scratch).
 //                                         A first version with fp32 atomics on the caller's grids took 78 ms for 2^20 rays at 256^3 where
 //                                         the plain call's record route takes 13.7 ms
-//   nerf_tile_adjoint_kernel<., true>     adjoint of SENSOR rays - the hot path: the LDS-window kernel, 1 + 3 planes as before, the AOV term
+//   nerf_tile_adjoint_kernel<PlainWindow<.>, true>   adjoint of SENSOR rays - the hot path: the LDS-window kernel, 1 + 3 planes as before, the AOV term
 //                                         in the sigma_t splat only                                                     (drt_nerf_tile_kernel.h)
 //   film_develop_n_kernel / film_backward_n_kernel   the box film with a channel count
 #include "drt_device.h"
@@ -64,9 +64,9 @@ hipError_t launch_nerf_aov(const Params &P, bool adjoint, hipStream_t stream)
     if (P.colour_own || !P.emission) return hipErrorInvalidValue;
     if (adjoint ? (!P.g_sigma || !P.g_albedo || !P.L_in || !(P.dL || P.dL_pix)) : !P.L_out) return hipErrorInvalidValue;
     const dim3 block(256), grid((unsigned) ((P.n_rays - P.ray_first + 255) / 256));
-    if (adjoint && P.rec_buf[0] != nullptr) hipLaunchKernelGGL((nerf_kernel<true, false, true, true>), grid, block, 0, stream, P);
-    else if (adjoint)                       hipLaunchKernelGGL((nerf_kernel<true, false, false, true>), grid, block, 0, stream, P);
-    else                                    hipLaunchKernelGGL((nerf_kernel<false, false, false, true>), grid, block, 0, stream, P);
+    if (adjoint && P.rec_buf[0] != nullptr) hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, false, true, true>), grid, block, 0, stream, P);
+    else if (adjoint)                       hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, false, false, true>), grid, block, 0, stream, P);
+    else                                    hipLaunchKernelGGL((nerf_kernel<PlainEmission, false, false, false, true>), grid, block, 0, stream, P);
     return hipGetLastError();
 }
 
@@ -75,14 +75,14 @@ hipError_t launch_nerf_aov_fwd(const Params &P, hipStream_t stream)
     if (P.n_rays <= P.ray_first) return hipSuccess;
     if (P.colour_own || !P.emission || !P.L_out) return hipErrorInvalidValue;
     const dim3 block(256), grid((unsigned) ((P.n_rays - P.ray_first + 255) / 256));
-    hipLaunchKernelGGL(nerf_fwd_kernel<true>, grid, block, 0, stream, P);
+    hipLaunchKernelGGL((nerf_fwd_kernel<PlainEmission, true>), grid, block, 0, stream, P);
     return hipGetLastError();
 }
 
 hipError_t launch_nerf_aov_tile_adjoint(const Params &P, bool g4, uint32_t *bounds, float t_max, hipStream_t stream)
 {
     if (!P.L_in || !(P.dL || P.dL_pix)) return hipErrorInvalidValue;
-    return nerf_tile_launch<true>(P, g4, false, bounds, t_max, stream);
+    return nerf_tile_launch_plain<true>(P, g4, false, bounds, t_max, stream);
 }
 
 hipError_t launch_film_develop_n(const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image, hipStream_t stream)

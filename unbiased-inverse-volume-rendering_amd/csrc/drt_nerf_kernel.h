@@ -1,12 +1,35 @@
 // drt_nerf_kernel.h -- NeRFIntegrator.sample as one ray per lane (the primal pass; the adjoint of explicit ray batches and of the record /
 // atomic gradient paths), shared by drt_kernels.hip and drt_own.hip (the same kernel with the colour grids on their own lattice,
-// DRT_COLOUR_OWN).  Internal linkage: every including unit gets its own instantiations.
+// DRT_COLOUR_OWN), by drt_nerf_aov.hip (AOV = true) and by drt_nerf_sh.hip (spherical-harmonic emission: its own emission policy).  Internal
+// linkage: every including unit gets its own instantiations.
 #pragma once
 #include "drt_device.h"
 #include "drt_launch.h"
 
 namespace drt {
 namespace {
+
+// Where the march gets a query's emission and what it does with the query's gradients: the EMISSION POLICY, a template parameter of the two
+// kernels below, built in the kernel from the kernel's trailing arguments (none here, so the plain kernels keep their argument block;
+// drt_nerf_sh.hip's is built from the interleaved copy - Params does not grow).
+//   Ray      what the policy keeps per ray, built from the ray's direction
+//   Query    what its lookup leaves for the splat / the tangent gather of the same query
+//   lookup   the emission at p                          splat    the adjoint's sigma_t and emission gradients of a query
+//   gather   the emission's tangent at p (forward mode)
+//   kScatter the splats go through splat_scatter: deferred records, or atomics staged per wave in LDS
+// This one: three channels from Params::emission (eval_rgb), gradients through splat_scatter, tangents through gather_colour.
+struct PlainEmission {
+    static constexpr bool kScatter = true;
+    struct Ray { __device__ __forceinline__ explicit Ray(V3) {} };
+    struct Query {};
+    __device__ __forceinline__ void lookup(const Params &P, const Ray &, V3 p, Query &, float em[3]) const { eval_rgb(P, P.emission, p, em); }
+    template <bool DEFER>
+    __device__ __forceinline__ void splat(const Params &P, const Ray &, V3 p, const Query &, float gs, const float ge[3], uint32_t *rec) const
+    {
+        splat_scatter<DEFER>(P, p, gs, ge, rec);                // colour planes = emission gradients here
+    }
+    __device__ __forceinline__ void gather(const Params &P, const Ray &, V3 p, const Query &, float dem[3]) const { gather_colour(P, p, dem); }
+};
 
 // ---------------------------------------------------------------------------
 // NeRFIntegrator.sample (python/integrators/nerf.py:47-148): emission-absorption ray marching,
@@ -18,9 +41,10 @@ namespace {
 // q_j = dA + dD (t_in + t_b,j) that no grid holds: the adjoint's sigma_t splat gains q_j (-da T) + (S / safe_a) da, S the running remainder
 // of dA A + dD D as `result` is the colour's; the emission splat is untouched.
 // ---------------------------------------------------------------------------
-template <bool ADJ, bool COUNT, bool DEFER, bool AOV = false>
-__global__ void __launch_bounds__(256) nerf_kernel(const Params P)
+template <class E, bool ADJ, bool COUNT, bool DEFER, bool AOV = false, class... EArg>
+__global__ void __launch_bounds__(256) nerf_kernel(const Params P, const EArg... earg)
 {
+    const E src{ earg... };
     uint64_t i = P.ray_first + (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     __shared__ uint32_t occ_lds[kOccWords];
     const uint32_t *occ = nullptr;
@@ -35,7 +59,7 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
         rec = rec_state + (threadIdx.x >> 6) * 8;
         if ((threadIdx.x & 63) < 8) rec[threadIdx.x & 63] = 0;
         coop_stage_sync();
-    } else if constexpr (ADJ) {
+    } else if constexpr (ADJ && E::kScatter) {
         __shared__ uint32_t coop_rec[4 * 64 * kCoopDwords];
         rec = coop_rec + (threadIdx.x >> 6) * (64 * kCoopDwords);
     }
@@ -53,6 +77,7 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
             d = v3(P.rays_d[3 * i], P.rays_d[3 * i + 1], P.rays_d[3 * i + 2]);
         }
         n_rays = 1;
+        const typename E::Ray er(d);
         float result[3] = { 0.0f, 0.0f, 0.0f }, dL[3] = { 0.0f, 0.0f, 0.0f };
         float dA = 0.0f, dD = 0.0f, Srem = 0.0f, depth_sum = 0.0f, t_in = 0.0f;   // (AOV)
         if constexpr (ADJ && AOV) {
@@ -99,7 +124,8 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
                 // the primal only needs the emission where the query has weight (adding weight * em with
                 // weight == 0 changes nothing); the adjoint's sigma_t gradient needs it everywhere
                 float em[3] = { 0.0f, 0.0f, 0.0f };
-                if (ADJ || weight != 0.0f) eval_rgb(P, P.emission, p, em);
+                typename E::Query eq;
+                if (ADJ || weight != 0.0f) src.lookup(P, er, p, eq, em);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) result[k] = ADJ ? result[k] - weight * em[k] : result[k] + weight * em[k];
                 if constexpr (ADJ) {                                         // :122-129
@@ -116,7 +142,7 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
                         gs += q * (-da * throughput) + (Srem / safe_a) * da;
                     }
                     if (P.nerf_relu && !(raw > 0.0f)) gs = 0.0f;
-                    splat_scatter<DEFER>(P, p, gs, ge, rec);   // colour planes = emission gradients here
+                    src.template splat<DEFER>(P, er, p, eq, gs, ge, rec);
                 }
                 t_a = t_b;
                 if (!last) { throughput *= safe_a; weights_sum += weight; }  // :117-120
@@ -156,9 +182,10 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P)
 // and the emitter term behind the medium.  The relu kink takes the adjoint's convention: no derivative unless raw > 0.  One ray per
 // lane, one write per ray.  AOV: five floats per ray, dA = dweights_sum and dD = sum dweight (t_in + t_b).
 // ---------------------------------------------------------------------------
-template <bool AOV = false>
-__global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P)
+template <class E, bool AOV = false, class... EArg>
+__global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P, const EArg... earg)
 {
+    const E src{ earg... };
     uint64_t i = P.ray_first + (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     __shared__ uint32_t occ_lds[kOccWords];
     const uint32_t *occ = nullptr;
@@ -179,6 +206,7 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P)
         o = v3(P.rays_o[3 * i], P.rays_o[3 * i + 1], P.rays_o[3 * i + 2]);
         d = v3(P.rays_d[3 * i], P.rays_d[3 * i + 1], P.rays_d[3 * i + 2]);
     }
+    const typename E::Ray er(d);
     float dres[3] = { 0.0f, 0.0f, 0.0f };                                // the tangent of `result`
     float throughput = 1.0f, weights_sum = 0.0f, dthroughput = 0.0f, dweights_sum = 0.0f;
     float ddepth_sum = 0.0f, t_in = 0.0f;                                // (AOV)
@@ -208,8 +236,9 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P)
             const float weight = (1.0f - a) * throughput;
             const float dweight = (1.0f - a) * dthroughput - da * throughput;
             float em[3], dem[3];
-            eval_rgb(P, P.emission, p, em);
-            gather_colour(P, p, dem);
+            typename E::Query eq;
+            src.lookup(P, er, p, eq, em);
+            src.gather(P, er, p, eq, dem);
 #pragma unroll
             for (int k = 0; k < 3; ++k) dres[k] += dweight * em[k] + weight * dem[k];
             t_a = t_b;
@@ -243,7 +272,7 @@ template <bool OWN> hipError_t NerfUnit<OWN>::forward(const Params &P, hipStream
     static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
     if (P.n_rays <= P.ray_first) return hipSuccess;
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
-    hipLaunchKernelGGL(nerf_fwd_kernel<false>, grid, block, 0, stream, P);
+    hipLaunchKernelGGL((nerf_fwd_kernel<PlainEmission, false>), grid, block, 0, stream, P);
     return hipGetLastError();
 }
 
@@ -254,14 +283,14 @@ template <bool OWN> hipError_t NerfUnit<OWN>::trace(const Params &P, bool adjoin
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
     const bool defer = adjoint && P.rec_buf[0] != nullptr;
     if (adjoint && defer) {
-        if (count) hipLaunchKernelGGL((nerf_kernel<true, true, true>), grid, block, 0, stream, P);
-        else       hipLaunchKernelGGL((nerf_kernel<true, false, true>), grid, block, 0, stream, P);
+        if (count) hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, true, true>), grid, block, 0, stream, P);
+        else       hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, false, true>), grid, block, 0, stream, P);
     } else if (adjoint) {
-        if (count) hipLaunchKernelGGL((nerf_kernel<true, true, false>), grid, block, 0, stream, P);
-        else       hipLaunchKernelGGL((nerf_kernel<true, false, false>), grid, block, 0, stream, P);
+        if (count) hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, true, false>), grid, block, 0, stream, P);
+        else       hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, false, false>), grid, block, 0, stream, P);
     } else {
-        if (count) hipLaunchKernelGGL((nerf_kernel<false, true, false>), grid, block, 0, stream, P);
-        else       hipLaunchKernelGGL((nerf_kernel<false, false, false>), grid, block, 0, stream, P);
+        if (count) hipLaunchKernelGGL((nerf_kernel<PlainEmission, false, true, false>), grid, block, 0, stream, P);
+        else       hipLaunchKernelGGL((nerf_kernel<PlainEmission, false, false, false>), grid, block, 0, stream, P);
     }
     return hipGetLastError();
 }

@@ -20,13 +20,14 @@
 // contribution converts exactly down to 2^-44 of that bound and 2^19 of them fit: sums inside a window are exact, whatever their order.
 // Non-finite inputs cannot travel through fixed point: the bounds kernel flags them and the pass marks the gradient grids NaN.
 //
-// Arithmetic per ray: the statements of nerf_kernel<ADJ> (drt_kernels.hip) in the same order - same lookups, same weights
+// Arithmetic per ray: the statements of nerf_kernel<., ADJ> (drt_nerf_kernel.h) in the same order - same lookups, same weights
 // (stencil_weights); gradients differ from the record path by summation order only.  Used for launches of sensor rays
 // (Params::sensor_flow), any spp (a workgroup marches 16 samples of its 64 pixels); explicit ray batches keep the record path.
 //
-// The bounds kernel, the window kernel and their launcher live in drt_nerf_tile_kernel.h, templated on an AOV flag: this unit instantiates
-// AOV = false (the code described above, unchanged), drt_nerf_aov.hip AOV = true (opacity and depth outputs).  Here: the four-channel copy,
-// the support predicate and the plain launch.
+// The bounds kernel, the window kernel and their launcher live in drt_nerf_tile_kernel.h, templated on a window configuration (extents, planes,
+// threads, lookup, colour splat) and an AOV flag: this unit instantiates PlainWindow with AOV = false (the code described above),
+// drt_nerf_aov.hip PlainWindow with AOV = true (opacity and depth outputs), drt_nerf_sh.hip its ShWindow (1 + 3K planes).  Here: the
+// four-channel copy, the support predicate and the plain launch.
 #include <atomic>
 #include "drt_device.h"
 #include "drt_launch.h"
@@ -89,7 +90,7 @@ bool nerf_tile_supported(const Params &P)
 
 hipError_t launch_nerf_tile_adjoint(const Params &P, bool g4, bool count, uint32_t *bounds, hipStream_t stream)
 {
-    return nerf_tile_launch<false>(P, g4, count, bounds, 0.0f, stream);
+    return nerf_tile_launch_plain<false>(P, g4, count, bounds, 0.0f, stream);
 }
 
 }  // namespace drt

@@ -1,7 +1,9 @@
 // drt_nerf_tile_kernel.h -- the LDS-window adjoint of the nerf march for sensor rays (the design: the header of drt_nerf_tile.hip), shared by
-// drt_nerf_tile.hip (the plain calls: AOV = false, the statements as they were) and drt_nerf_aov.hip (AOV = true: five interleaved floats
-// [r, g, b, opacity, depth] per ray in dL / dL_pix / L_in; the two extra outputs depend on sigma_t only, so the window keeps its 1 + 3 planes and
-// the sigma_t splat gains one term).  Internal linkage: every including unit gets its own instantiations.
+// drt_nerf_tile.hip (the plain calls: PlainWindow, AOV = false), drt_nerf_aov.hip (AOV = true: five interleaved floats [r, g, b, opacity, depth]
+// per ray in dL / dL_pix / L_in; the two extra outputs depend on sigma_t only, so the window keeps its 1 + 3 planes and the sigma_t splat gains
+// one term) and drt_nerf_sh.hip (spherical-harmonic emission: a window of 1 + 3K planes, its own lookup and colour splat).  What differs between
+// them is a compile-time WINDOW CONFIGURATION (PlainWindow below); the march, the fixed-point units, the window protocol, the bounds kernel and
+// the launcher exist once.  Internal linkage: every including unit gets its own instantiations.
 #pragma once
 #include <atomic>
 #include "drt_device.h"
@@ -22,20 +24,25 @@ namespace drt {
 
 namespace {
 
-constexpr int kWin = 16;                                   // window edge in voxels (a power of two)
-constexpr int kWinSlots = kWin * kWin * kWin;              // 4096 voxels
-// slot of voxel (x, y, z) = (z & 15) * kSZ + (y & 15) * kSY + (x & 15): row and slab strides that spread a splat neighbourhood over the LDS banks
+// The window of a configuration C: C::WX x C::WY x C::WZ voxels (powers of two), C::kPlanes planes of 64-bit accumulators.
+// slot of voxel (x, y, z) = (z & WZ-1) * kSZ + (y & WY-1) * kSY + (x & WX-1): row and slab strides that spread a splat neighbourhood over the LDS banks
 // (with strides 16 / 256 the rows y, y + 2, ... and EVERY slab z of a column share their banks: the 64 lanes of an add instruction - a few voxels
-// wide, a few deep - met in ~10 banks, SQ_LDS_IDX_ACTIVE was 97 cycles per instruction and the LDS was busy 85 % of the kernel's 72 ms)
-constexpr int kSY = 17, kSZ = 16 * kSY + 5;
-constexpr int kWinStore = kWin * kSZ;                      // 4432 accumulators of 8 bytes per channel: 4 channels = 138.5 KiB, one workgroup of 16 waves per CU
+// wide, a few deep - met in ~10 banks, SQ_LDS_IDX_ACTIVE was 97 cycles per instruction and the LDS was busy 85 % of the kernel's 72 ms).
+// An accumulator is 8 bytes = 2 of the 64 LDS banks, so two slots collide when they agree mod 32: with kSY = WX + 1 and kSZ = WY * kSY + 5 a row
+// step is +17 / +9 and a slab step +13 mod 32 (WX = 16 / 8), so the 2 x 2 x 2 corners of one splat - and the 3 x 3 x 2 voxels a wave's 16 pixels
+// x 4 samples typically touch - fall into distinct bank pairs
+template <class C> struct Window {
+    static constexpr int kSY = C::WX + 1, kSZ = C::WY * kSY + 5;
+    static constexpr int kSlots = C::WX * C::WY * C::WZ, kStore = C::WZ * kSZ;
+    static constexpr size_t kBytes = (size_t) C::kPlanes * kStore * sizeof(unsigned long long);
+};
 constexpr int kFixBits = 44;
 
 struct NerfTile {
     uint32_t tiles_x;              // tiles of 8 x 8 pixels per film row
-    uint32_t groups;               // workgroups per tile: each marches DRT_NT_THREADS / 64 of the pixels' samples
-    uint32_t *bounds;              // [0] max |dL|, [1] max |L_in| over the launch's rays, [2] max |emission| over the grid (float bits), [3] a non-finite one was seen, [4] the largest negative density's magnitude
-    uint32_t g4;                   // lookups from the four-channel copy (Params::grid4) instead of sigma_b + emission
+    uint32_t groups;               // workgroups per tile: each marches C::kThreads / 64 of the pixels' samples
+    uint32_t *bounds;              // [0] max |dL|, [1] max |L_in| over the launch's rays, [2] max |emission| over the grid (float bits), [3] a non-finite one was seen, [4] the largest negative density's magnitude,
+                                   // [5] window phases (configurations without counters, counting launches), [6..7] LDS lane-adds (configurations with counters, counting launches)
     uint32_t count;
     float t_max;                   // AOV: a bound of t_in + t_b, the distance of a query from the sensor's origin (from the host); bounds then holds 12 words:
                                    // [8] max |dA|, [9] max |dD|, [10] max |A_in|, [11] max |D_in| (channels 3 and 4 of dL / dL_pix / L_in; [0], [1]: channels 0 - 2)
@@ -67,6 +74,50 @@ __device__ __forceinline__ void eval4_at(const Params &P, const Stencil &s, floa
     rgb[1] = trilerp8(s, d0.z, d1.z, d2.z, d3.z, d4.z, d5.z, d6.z, d7.z);
     rgb[2] = trilerp8(s, d0.w, d1.w, d2.w, d3.w, d4.w, d5.w, d6.w, d7.w);
 }
+
+// The plain configuration: sigma_t and three colour planes in a 16^3 window (4432 accumulators of 8 bytes per plane: 4 planes = 138.5 KiB, one
+// workgroup of 16 waves per CU).  G4: lookups from the four-channel copy (Params::grid4) instead of sigma_b + Params::emission.
+// What a configuration supplies (drt_nerf_sh.hip holds the other one):
+//   WX, WY, WZ, kPlanes, kThreads      the window and the workgroup                 kChannels   floats per voxel of the colour gradient grid
+//   kEmaxFactor    |em_c| <= max |colour grid| x this                               kOcc        sigma_t lookups use the occupancy words (staged in LDS)
+//   kCounters      counting launches add to Params::counters and bounds[6..7]; without: they count their window phases in bounds[5]
+//   sigma_t        a query's scaled density alone (the pre-march)                   lookup      density and emission at a footprint that is known
+//   splat_colour   a query's colour gradients into planes 1 .. kPlanes - 1
+template <bool G4> struct PlainWindow {
+    static constexpr int WX = 16, WY = 16, WZ = 16, kPlanes = 4, kThreads = DRT_NT_THREADS, kChannels = 3;
+    static constexpr float kEmaxFactor = 1.0f;
+    static constexpr bool kOcc = !G4, kCounters = true;
+    __device__ __forceinline__ float sigma_t(const Params &P, V3 p, const uint32_t *occ) const
+    {
+        if constexpr (G4) {
+            Stencil s4; float raw, em4[3];
+            axis_setup(p.x, P.bmin[0], P.inv_ext[0], P.rx, s4.x0, s4.x1, s4.wx0, s4.wx1);
+            axis_setup(p.y, P.bmin[1], P.inv_ext[1], P.ry, s4.y0, s4.y1, s4.wy0, s4.wy1);
+            axis_setup(p.z, P.bmin[2], P.inv_ext[2], P.rz, s4.z0, s4.z1, s4.wz0, s4.wz1);
+            eval4_at(P, s4, raw, em4);
+            return raw;
+        } else return eval_sigma_t(P, p, occ);
+    }
+    __device__ __forceinline__ void lookup(const Params &P, V3, V3 p, const Stencil &st, const uint32_t *occ, float &raw, float em[3]) const
+    {
+        if constexpr (G4) eval4_at(P, st, raw, em);
+        else { raw = eval_sigma_t(P, p, occ); eval_rgb(P, P.emission, p, em); }
+    }
+    __device__ __forceinline__ void splat_colour(unsigned long long *win, const int sl[8], const float w[8], V3, const float ge[3], double inv_c,
+                                                 bool count, uint32_t &n_adds) const
+    {
+        constexpr int kStore = Window<PlainWindow>::kStore;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (ge[c] != 0.0f) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) atomicAdd(win + (c + 1) * kStore + sl[k], fix64(w[k] * ge[c], inv_c));
+                if (count) n_adds += 8u;
+            }
+        }
+    }
+};
+static_assert(Window<PlainWindow<true>>::kStore == 4432 && Window<PlainWindow<true>>::kBytes == 4 * 4432 * 8, "LDS bytes per workgroup (DESIGN.md)");
 
 // max |dL|, max |L_in| over the rays of the launch and max |emission| over the grid -> out[0..2] (float bits; zeroed by the caller):
 // what the fixed-point units of the window follow from
@@ -138,14 +189,16 @@ __global__ void __launch_bounds__(256) nerf_tile_bounds_aov_kernel(const float *
 // AOV (drt_nerf_aov.hip): dL / dL_pix / L_in hold five floats per ray / pixel, [r, g, b, opacity A, depth D] with A = sum_{j+1<N} weight_j and
 // D = sum_{j+1<N} weight_j (t_in + t_b,j).  Both are linear in an "emission" q_j = dA + dD (t_in + t_b,j) that no grid holds: the colour planes
 // are untouched, and the sigma_t splat gains q_j (-da T) + (S / safe_a) da, S the running remainder of dA A + dD D as `result` is the colour's.
-template <bool G4, bool AOV>
-__global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const Params P, const NerfTile T)
+// (CArg: what the configuration is built from - none for the plain one, whose kernel keeps its argument block)
+template <class C, bool AOV, class... CArg>
+__global__ void __launch_bounds__(C::kThreads) nerf_tile_adjoint_kernel(const Params P, const NerfTile T, const CArg... carg)
 {
-    constexpr int NT = DRT_NT_THREADS;
-    extern __shared__ __attribute__((aligned(16))) unsigned long long win[];   // [4][kWinStore]: sigma_t, r, g, b (two's complement fixed point)
+    const C cfg{ carg... };
+    constexpr int NT = C::kThreads, WX = C::WX, WY = C::WY, WZ = C::WZ, NP = C::kPlanes;
+    constexpr int kSY = Window<C>::kSY, kSZ = Window<C>::kSZ, kStore = Window<C>::kStore;
+    extern __shared__ __attribute__((aligned(16))) unsigned long long win[];   // [NP][kStore]: sigma_t, then the colour planes (two's complement fixed point)
     __shared__ int wctl[16];                                          // [0..2] min, [3..5] max of the waiting splats' corners, [6..8] direction signs, [9..14] footprint of the ray the window moves to
     __shared__ unsigned long long wkey[1];                           // the waiting splat closest to the camera: {distance bits, thread}
-    __shared__ uint32_t occ_lds[kOccWords];
     __shared__ uint32_t wgain[2];                                     // negative densities: the workgroup's M1, W (float bits)
     const uint32_t t = threadIdx.x, lane = t & 63u;
 
@@ -188,10 +241,11 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
     // marches them for the gradients.  (Until round 6 the bound was the launch's worst case exp(2 |sigma|max x diagonal): with a strongly negative
     // region anywhere in the grid the unit came out so coarse that ordinary gradients lost their digits - tests/test_gpu_fuzz.py found it.)
     float unit_s, unit_c; double inv_s, inv_c;
-    const float Dmax = __uint_as_float(T.bounds[0]), Lmax = __uint_as_float(T.bounds[1]), Emax = __uint_as_float(T.bounds[2]);
+    const float Dmax = __uint_as_float(T.bounds[0]), Lmax = __uint_as_float(T.bounds[1]), Emax = __uint_as_float(T.bounds[2]) * C::kEmaxFactor;
     const float neg = P.nerf_relu ? 0.0f : __uint_as_float(T.bounds[4]);
     const float dt_max = 2.0f * sqrtf((P.bmax[0] - P.bmin[0]) * (P.bmax[0] - P.bmin[0]) + (P.bmax[1] - P.bmin[1]) * (P.bmax[1] - P.bmin[1]) +
                                       (P.bmax[2] - P.bmin[2]) * (P.bmax[2] - P.bmin[2])) / (float) (P.nerf_queries - 1);
+    const size_t nv = (size_t) P.rx * P.ry * P.rz;
     // Non-finite dL / L_in / emission / density values (as a diverged optimisation produces them), or bounds that overflow fp32: fixed point
     // cannot carry them.  The march is skipped and BOTH gradient grids are filled with NaN - every voxel, so that a caller (or a masked
     // all-reduce) that looks at any part of the grids sees that this gradient is void, as it would find NaN in the voxels the record path touches.
@@ -205,18 +259,21 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
     if (T.bounds[3] || !(fabsf(P.scale) * 3.0f * Dmax * (2.0f * Emax + Lmax) * dt_max * 1.001f < kInf) || !(Dmax < kInf) ||
         (AOV && !(fabsf(P.scale) * (2.0f * Qb + Sb) * dt_max * 1.001f < kInf))) {
         const float nan = __uint_as_float(0x7fc00000u);
-        const size_t nv = (size_t) P.rx * P.ry * P.rz, i0 = (size_t) blockIdx.x * NT + t, stride = (size_t) gridDim.x * NT;
+        const size_t i0 = (size_t) blockIdx.x * NT + t, stride = (size_t) gridDim.x * NT;
         for (size_t v = i0; v < nv; v += stride) P.g_sigma[v] = nan;
-        for (size_t v = i0; v < 3 * nv; v += stride) P.g_albedo[v] = nan;
+        for (size_t v = i0; v < (size_t) C::kChannels * nv; v += stride) P.g_albedo[v] = nan;
         return;
     }
     if (__syncthreads_count(job) == 0) return;                       // (a launch over a window of the film: most tiles hold none of its rays)
 
-    for (int w = t; w < 4 * kWinStore; w += NT) win[w] = 0ull;
+    for (int w = t; w < NP * kStore; w += NT) win[w] = 0ull;
     const uint32_t *occ = nullptr;
-    if (!G4 && P.occ) {
-        for (int w = t; w < P.occ_words; w += NT) occ_lds[w] = P.occ[w];
-        occ = occ_lds;
+    if constexpr (C::kOcc) {
+        __shared__ uint32_t occ_lds[kOccWords];
+        if (P.occ) {
+            for (int w = t; w < P.occ_words; w += NT) occ_lds[w] = P.occ[w];
+            occ = occ_lds;
+        }
     }
     __syncthreads();
 
@@ -268,14 +325,7 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
                     const float t_b = P.nerf_jitter ? step * ((float) (q + 1) + jit) : step * (float) (q + 1);
                     const float dt = t_b - ta;
                     const V3 p = ray_at(o, d, t_b);
-                    float raw;
-                    if constexpr (G4) {
-                        Stencil s4; float em4[3];
-                        axis_setup(p.x, P.bmin[0], P.inv_ext[0], P.rx, s4.x0, s4.x1, s4.wx0, s4.wx1);
-                        axis_setup(p.y, P.bmin[1], P.inv_ext[1], P.ry, s4.y0, s4.y1, s4.wy0, s4.wy1);
-                        axis_setup(p.z, P.bmin[2], P.inv_ext[2], P.rz, s4.z0, s4.z1, s4.wz0, s4.wz1);
-                        eval4_at(P, s4, raw, em4);
-                    } else raw = eval_sigma_t(P, p, occ);
+                    const float raw = cfg.sigma_t(P, p, occ);
                     const bool last = !(q + 1 < N);
                     const float a = last ? 1.0f : drt_expf(-raw * dt);
                     m1 = fmaxf(m1, fmaxf(a, 1.0f) * thr);
@@ -298,9 +348,8 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
         if constexpr (AOV) Bs += fabsf(P.scale) * (Qb * M1 + Qb * Wm + Sb) * dt_max * 1.001f;
         if (!(Bs < kInf) || !(Bc < kInf)) {                             // this workgroup's rays overflow fp32: its share of the gradient is void - and so is the whole
             const float nan = __uint_as_float(0x7fc00000u);
-            const size_t nv = (size_t) P.rx * P.ry * P.rz;
             for (size_t v = t; v < nv; v += NT) P.g_sigma[v] = nan;
-            for (size_t v = t; v < 3 * nv; v += NT) P.g_albedo[v] = nan;
+            for (size_t v = t; v < (size_t) C::kChannels * nv; v += NT) P.g_albedo[v] = nan;
             return;
         }
         int es = 0, ec = 0;
@@ -309,6 +358,7 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
         unit_s = ldexpf(1.0f, es); inv_s = ldexp(1.0, -es); unit_c = ldexpf(1.0f, ec); inv_c = ldexp(1.0, -ec);
     }
     uint32_t n_adds = 0;                                               // (LDS lane-adds of this ray, counting launches only: bounds[6..7])
+    uint32_t phases = 0;                                               // (window phases, thread 0 of a configuration without counters: bounds[5])
     int Wx = -(1 << 28), Wy = -(1 << 28), Wz = -(1 << 28);             // window origin (workgroup-uniform; none yet: the first splats all wait)
     const int N = P.nerf_queries;
     int j = 0;
@@ -318,17 +368,21 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
     st.x0 = st.x1 = st.y0 = st.y1 = st.z0 = st.z1 = 0; st.wx0 = st.wx1 = st.wy0 = st.wy1 = st.wz0 = st.wz1 = 0.0f;
     float v0 = 0.0f, ge[3] = { 0.0f, 0.0f, 0.0f };
     auto flush = [&]() {                                                // slot -> the voxel it holds under the current origin
-        for (int l = t; l < kWinSlots; l += NT) {
-            const int sx = l & 15, sy = (l >> 4) & 15, sz = l >> 8, s = sz * kSZ + sy * kSY + sx;
-            const unsigned long long a0 = win[s], a1 = win[kWinStore + s], a2 = win[2 * kWinStore + s], a3 = win[3 * kWinStore + s];
-            if ((a0 | a1 | a2 | a3) != 0ull) {
-                const int x = Wx + ((sx - Wx) & 15), y = Wy + ((sy - Wy) & 15), z = Wz + ((sz - Wz) & 15);
+        for (uint32_t l = t; l < (uint32_t) Window<C>::kSlots; l += NT) {
+            const int sx = (int) (l & (WX - 1)), sy = (int) ((l / WX) & (WY - 1)), sz = (int) (l / (WX * WY)), s = sz * kSZ + sy * kSY + sx;
+            unsigned long long a[NP], any = 0ull;
+#pragma unroll
+            for (int pl = 0; pl < NP; ++pl) { a[pl] = win[pl * kStore + s]; any |= a[pl]; }
+            if (any != 0ull) {
+                const int x = Wx + ((sx - Wx) & (WX - 1)), y = Wy + ((sy - Wy) & (WY - 1)), z = Wz + ((sz - Wz) & (WZ - 1));
                 const size_t lin = ((size_t) z * (size_t) P.ry + (size_t) y) * (size_t) P.rx + (size_t) x;
-                if (a0) atomicAdd(P.g_sigma + lin, (float) (long long) a0 * unit_s);
-                if (a1) atomicAdd(P.g_albedo + 3 * lin, (float) (long long) a1 * unit_c);
-                if (a2) atomicAdd(P.g_albedo + 3 * lin + 1, (float) (long long) a2 * unit_c);
-                if (a3) atomicAdd(P.g_albedo + 3 * lin + 2, (float) (long long) a3 * unit_c);
-                win[s] = 0ull; win[kWinStore + s] = 0ull; win[2 * kWinStore + s] = 0ull; win[3 * kWinStore + s] = 0ull;
+                float *gc = P.g_albedo + lin * (size_t) C::kChannels;   // plane 1 + ch holds channel ch of the colour gradient grid
+                if (a[0]) atomicAdd(P.g_sigma + lin, (float) (long long) a[0] * unit_s);
+#pragma unroll
+                for (int pl = 1; pl < NP; ++pl)
+                    if (a[pl]) atomicAdd(gc + (pl - 1), (float) (long long) a[pl] * unit_c);
+#pragma unroll
+                for (int pl = 0; pl < NP; ++pl) win[pl * kStore + s] = 0ull;
             }
         }
     };
@@ -342,10 +396,11 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
     for (;;) {
         for (;;) {
             if (pend) {
-                if (!(st.x0 >= Wx && st.x1 < Wx + kWin && st.y0 >= Wy && st.y1 < Wy + kWin && st.z0 >= Wz && st.z1 < Wz + kWin)) break;
+                if (!(st.x0 >= Wx && st.x1 < Wx + WX && st.y0 >= Wy && st.y1 < Wy + WY && st.z0 >= Wz && st.z1 < Wz + WZ)) break;
                 float w[8];
                 stencil_weights(st, w);
-                const int sx0 = st.x0 & 15, sx1 = st.x1 & 15, sy0 = (st.y0 & 15) * kSY, sy1 = (st.y1 & 15) * kSY, sz0 = (st.z0 & 15) * kSZ, sz1 = (st.z1 & 15) * kSZ;
+                const int sx0 = st.x0 & (WX - 1), sx1 = st.x1 & (WX - 1), sy0 = (st.y0 & (WY - 1)) * kSY, sy1 = (st.y1 & (WY - 1)) * kSY;
+                const int sz0 = (st.z0 & (WZ - 1)) * kSZ, sz1 = (st.z1 & (WZ - 1)) * kSZ;
                 const int sl[8] = { sz0 + sy0 + sx0, sz0 + sy0 + sx1, sz0 + sy1 + sx0, sz0 + sy1 + sx1,
                                     sz1 + sy0 + sx0, sz1 + sy0 + sx1, sz1 + sy1 + sx0, sz1 + sy1 + sx1 };
                 if (v0 != 0.0f) {
@@ -353,16 +408,7 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
                     for (int k = 0; k < 8; ++k) atomicAdd(win + sl[k], fix64(w[k] * v0, inv_s));
                     if (T.count) n_adds += 8u;
                 }
-                if (colour) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        if (ge[c] != 0.0f) {
-#pragma unroll
-                            for (int k = 0; k < 8; ++k) atomicAdd(win + (c + 1) * kWinStore + sl[k], fix64(w[k] * ge[c], inv_c));
-                            if (T.count) n_adds += 8u;
-                        }
-                    }
-                }
+                if (colour) cfg.splat_colour(win, sl, w, d, ge, inv_c, T.count != 0u, n_adds);
                 pend = false;
                 NT_STAT(2, 1);
             }
@@ -375,8 +421,7 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
             axis_setup(p.y, P.bmin[1], P.inv_ext[1], P.ry, st.y0, st.y1, st.wy0, st.wy1);
             axis_setup(p.z, P.bmin[2], P.inv_ext[2], P.rz, st.z0, st.z1, st.wz0, st.wz1);
             float raw, em[3];
-            if constexpr (G4) eval4_at(P, st, raw, em);
-            else { raw = eval_sigma_t(P, p, occ); eval_rgb(P, P.emission, p, em); }
+            cfg.lookup(P, d, p, st, occ, raw, em);
             const float dt = t_b - t_a;
             const float sigma = P.nerf_relu ? fmaxf(0.0f, raw) : raw;
             const bool last = !(j + 1 < N);
@@ -409,7 +454,7 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
         }
         // ---- every ray waits or is done: the waiting splat closest to the camera, the bounding box of the waiting ones -------------------
         if (t < 8) wctl[t] = t < 3 ? 1 << 28 : t < 6 ? -(1 << 28) : 0;
-        if (t == 0) { wkey[0] = ~0ull; NT_STAT(0, 1); }
+        if (t == 0) { wkey[0] = ~0ull; ++phases; NT_STAT(0, 1); }
         __syncthreads();                                                        // (... and the phase's LDS adds are done)
         // (a waiting splat's distance from the camera: ent_t + the t_b of its query, which is t_a by now; distances are positive: ordered like their bits)
         unsigned long long mine = pend ? (((unsigned long long) __float_as_uint(ent_t + t_a) << 32) | t) : ~0ull;
@@ -439,12 +484,15 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
         __syncthreads();
         // per axis: the box's corner on the side the rays come from, moved as far as that ray's footprint allows
         // (workgroup-uniform: scalar registers - 6 vector registers fewer, with the leaner bookkeeping of round 6 119 instead of 127)
-        Wx = __builtin_amdgcn_readfirstlane(wctl[6] >= 0 ? max(wctl[0], wctl[10] - (kWin - 1)) : min(wctl[3] - (kWin - 1), wctl[9]));
-        Wy = __builtin_amdgcn_readfirstlane(wctl[7] >= 0 ? max(wctl[1], wctl[12] - (kWin - 1)) : min(wctl[4] - (kWin - 1), wctl[11]));
-        Wz = __builtin_amdgcn_readfirstlane(wctl[8] >= 0 ? max(wctl[2], wctl[14] - (kWin - 1)) : min(wctl[5] - (kWin - 1), wctl[13]));
+        Wx = __builtin_amdgcn_readfirstlane(wctl[6] >= 0 ? max(wctl[0], wctl[10] - (WX - 1)) : min(wctl[3] - (WX - 1), wctl[9]));
+        Wy = __builtin_amdgcn_readfirstlane(wctl[7] >= 0 ? max(wctl[1], wctl[12] - (WY - 1)) : min(wctl[4] - (WY - 1), wctl[11]));
+        Wz = __builtin_amdgcn_readfirstlane(wctl[8] >= 0 ? max(wctl[2], wctl[14] - (WZ - 1)) : min(wctl[5] - (WZ - 1), wctl[13]));
         __syncthreads();                                                        // (wctl / wkey are reset by the next phase's end)
     }
-    if (T.count && P.counters) {
+    // (a configuration without counters keeps Params::counters out of its code and reports its phases instead: drt_nerf_sh_tile_stats)
+    if constexpr (!C::kCounters) {
+        if (T.count && t == 0) atomicAdd(T.bounds + 5, phases);
+    } else if (T.count && P.counters) {
         // (as nerf_kernel counts: one sigma_t + one colour lookup, one sigma_t + one colour splat per query)
         const uint32_t n_q = (uint32_t) j;                                        // (one lookup and one splat per query of the march)
         uint32_t vals[C_COUNT] = { job && !P.nerf_fused_half ? 1u : 0u, n_q, 0, 0, n_q, 0, 0, n_q, n_q };
@@ -463,60 +511,58 @@ __global__ void __launch_bounds__(DRT_NT_THREADS) nerf_tile_adjoint_kernel(const
     }
 }
 
-// the launch of both units: the bounds reduction(s), then a workgroup per (pixel tile, sample group)
-template <bool AOV>
-hipError_t nerf_tile_launch(const Params &P, bool g4, bool count, uint32_t *bounds, float t_max, hipStream_t stream)
+// the launch of every unit: the bounds reduction(s), then a workgroup per (pixel tile, sample group) of configuration C
+template <class C, bool AOV, class... CArg>
+hipError_t nerf_tile_launch(const Params &P, bool count, uint32_t *bounds, float t_max, hipStream_t stream, CArg... carg)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
-    if (!nerf_tile_supported(P) || (g4 && !P.grid4) || !bounds || !P.emission) return hipErrorInvalidValue;
-    constexpr size_t C = AOV ? 5 : 3;
+    if (!nerf_tile_supported(P) || !bounds || !P.emission) return hipErrorInvalidValue;
+    constexpr size_t F = AOV ? 5 : 3;                                    // floats per ray / pixel
     NerfTile T;
     {
         hipError_t e = hipMemsetAsync(bounds, 0, (AOV ? 12 : 8) * sizeof(uint32_t), stream);
         if (e != hipSuccess) return e;
-        const size_t n_em = (size_t) P.rx * P.ry * P.rz * 3;
+        const size_t nv = (size_t) P.rx * P.ry * P.rz, n_em = nv * (size_t) C::kChannels;
         // (pixel layout: the pixels of rays ray_first .. n_rays - 1, both ends included)
         const uint64_t px_first = P.ray_first / P.spp, px_last = (P.n_rays - 1) / P.spp;
-        const float *dL = P.dL_pix ? nullptr : P.dL + C * P.ray_first, *dL_pix = P.dL_pix ? P.dL_pix + C * px_first : nullptr;
-        const size_t n_ray_floats = (size_t) (P.n_rays - P.ray_first) * C, n_px_floats = (size_t) (px_last - px_first + 1) * C;
+        const float *dL = P.dL_pix ? nullptr : P.dL + F * P.ray_first, *dL_pix = P.dL_pix ? P.dL_pix + F * px_first : nullptr;
+        const size_t n_ray_floats = (size_t) (P.n_rays - P.ray_first) * F, n_px_floats = (size_t) (px_last - px_first + 1) * F;
         if constexpr (AOV) {
-            hipLaunchKernelGGL(nerf_tile_bounds_aov_kernel<5>, dim3(2048), dim3(256), 0, stream, dL, P.L_in + C * P.ray_first, n_ray_floats, dL_pix,
+            hipLaunchKernelGGL(nerf_tile_bounds_aov_kernel<5>, dim3(2048), dim3(256), 0, stream, dL, P.L_in + F * P.ray_first, n_ray_floats, dL_pix,
                                n_px_floats, 1.0f / (float) P.spp, bounds);
             hipLaunchKernelGGL(nerf_tile_bounds_kernel, dim3(2048), dim3(256), 0, stream, (const float *) nullptr, (const float *) nullptr, (size_t) 0,
-                               (const float *) nullptr, (size_t) 0, 1.0f, P.emission, n_em, P.sigma_t, n_em / 3, bounds);
+                               (const float *) nullptr, (size_t) 0, 1.0f, P.emission, n_em, P.sigma_t, nv, bounds);
         } else {
-            hipLaunchKernelGGL(nerf_tile_bounds_kernel, dim3(2048), dim3(256), 0, stream, dL, P.L_in + C * P.ray_first, n_ray_floats, dL_pix,
-                               n_px_floats, 1.0f / (float) P.spp, P.emission, n_em, P.sigma_t, n_em / 3, bounds);
+            hipLaunchKernelGGL(nerf_tile_bounds_kernel, dim3(2048), dim3(256), 0, stream, dL, P.L_in + F * P.ray_first, n_ray_floats, dL_pix,
+                               n_px_floats, 1.0f / (float) P.spp, P.emission, n_em, P.sigma_t, nv, bounds);
         }
         T.bounds = bounds;
     }
     T.tiles_x = ((uint32_t) P.width + 7u) / 8u;
     const uint32_t tiles_y = ((uint32_t) P.height + 7u) / 8u;
-    T.groups = (P.spp + DRT_NT_THREADS / 64 - 1) / (DRT_NT_THREADS / 64);
-    T.g4 = g4 ? 1u : 0u; T.count = count ? 1u : 0u; T.t_max = t_max;
-    const size_t lds = (size_t) 4 * kWinStore * sizeof(unsigned long long);
-    auto set_lds = [&](const void *k) {
-        static std::atomic<bool> done[2][64];
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
-        if (!done[g4 ? 1 : 0][dev] || dev == 63) {
-            const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
-            if (e != hipSuccess) return e;
-            done[g4 ? 1 : 0][dev] = true;
-        }
-        return hipSuccess;
-    };
-    const dim3 grid(T.tiles_x * tiles_y * T.groups), block(DRT_NT_THREADS);
-    if (g4) {
-        const hipError_t e = set_lds((const void *) nerf_tile_adjoint_kernel<true, AOV>);
+    T.groups = (P.spp + C::kThreads / 64 - 1) / (C::kThreads / 64);
+    T.count = count ? 1u : 0u; T.t_max = t_max;
+    // the window is more LDS than a kernel gets by default: raise its limit once per device (and instantiation)
+    constexpr size_t lds = Window<C>::kBytes;
+    static std::atomic<bool> done[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 63;
+    if (!done[dev] || dev == 63) {
+        const hipError_t e = hipFuncSetAttribute((const void *) nerf_tile_adjoint_kernel<C, AOV, CArg...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((nerf_tile_adjoint_kernel<true, AOV>), grid, block, lds, stream, P, T);
-    } else {
-        const hipError_t e = set_lds((const void *) nerf_tile_adjoint_kernel<false, AOV>);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((nerf_tile_adjoint_kernel<false, AOV>), grid, block, lds, stream, P, T);
+        done[dev] = true;
     }
+    hipLaunchKernelGGL((nerf_tile_adjoint_kernel<C, AOV, CArg...>), dim3(T.tiles_x * tiles_y * T.groups), dim3(C::kThreads), lds, stream, P, T, carg...);
     return hipGetLastError();
+}
+
+// ... with the plain configuration, for the kind of lookup the call asks for
+template <bool AOV>
+hipError_t nerf_tile_launch_plain(const Params &P, bool g4, bool count, uint32_t *bounds, float t_max, hipStream_t stream)
+{
+    if (g4 && !P.grid4 && P.n_rays > P.ray_first) return hipErrorInvalidValue;
+    return g4 ? nerf_tile_launch<PlainWindow<true>, AOV>(P, count, bounds, t_max, stream)
+              : nerf_tile_launch<PlainWindow<false>, AOV>(P, count, bounds, t_max, stream);
 }
 
 }  // namespace
