@@ -105,8 +105,8 @@ int drt_set_colour_resolution(drt_handle h, const int32_t res[3]);
 /* Phase function of the medium (the medium's `phase_function()`, volpathsimple.py:202-231, 380-392, 616-646).  A handle starts
  * isotropic; drt_set_medium leaves the phase as it is.  kind DRT_PHASE_ISOTROPIC (g must be 0) or DRT_PHASE_HG, Mitsuba's `hg` plugin
  * with asymmetry g, finite and |g| < 1 (g > 0 scatters forward).  HG runs the HG instantiations of the production tracers (csrc/drt_sq_hg.hip
- * for supergrids, drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip); a test hook that routes a launch to an older tracer generation
- * is refused with DRT_ERR_UNSUPPORTED.  Setting another phase invalidates what the handle planned from earlier paths (path cache, ray
+ * for supergrids, drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip), under every test hook (drt_set_debug_flags).
+ * Setting another phase invalidates what the handle planned from earlier paths (path cache, ray
  * order); setting the same one again changes nothing.  The gradient with respect to g: drt_render_backward_phase,
  * drt_render_backward_px_phase and drt_render_forward_phase (an extension of the reference, whose volpathsimple has none). */
 enum { DRT_PHASE_ISOTROPIC = 0, DRT_PHASE_HG = 1, DRT_PHASE_HG2 = 2, DRT_PHASE_TAB = 3 };
@@ -118,7 +118,7 @@ int drt_set_phase(drt_handle h, int32_t kind, float g);
  * mixture, so a path's sampler stream does not depend on the phase function.  weight 0 / 1 render bit for bit what DRT_PHASE_HG with g1 /
  * g2 renders.  Kernels: the H2 instantiations of the HG ones (csrc/drt_sq_hg2.hip, drt_coop_hg2.hip, drt_coop_super_hg2.hip,
  * drt_own_hg2.hip), with the HG routing and the HG invalidation rules: another triple drops path cache and ray orders, the same triple
- * changes nothing, drt_set_medium leaves it alone, a test hook that routes to an older tracer generation is refused (DRT_ERR_UNSUPPORTED).
+ * changes nothing, drt_set_medium leaves it alone, every test hook that drt_set_debug_flags accepts runs these kernels.
  * drt_set_phase keeps its one-parameter meaning: called with kind 2 it returns DRT_ERR_INVALID_ARGUMENT.  No gradients with respect to
  * g1, g2 or weight yet: a non-NULL grad_phase_g / non-zero t_phase_g of the *_phase entry points on such a handle returns
  * DRT_ERR_UNSUPPORTED (NULL / 0 run as the plain calls do). */
@@ -133,7 +133,7 @@ int drt_set_phase_hg2(drt_handle h, float g1, float g2, float weight);
  * table on the device (density and CDF nodes plus a guide table for the search, 12 bytes per node).  Kernels: the kTab instantiations
  * (csrc/drt_sq_tab.hip, drt_coop_tab.hip, drt_coop_super_tab.hip, drt_own_tab.hip) with the HG routing and the HG invalidation rules:
  * another table drops path cache and ray orders, the same table changes nothing, drt_set_medium leaves it alone, drt_set_phase /
- * drt_set_phase_hg2 replace it, a test hook that routes to an older tracer generation is refused (DRT_ERR_UNSUPPORTED).  The call waits
+ * drt_set_phase_hg2 replace it, every test hook that drt_set_debug_flags accepts runs these kernels.  The call waits
  * for the handle's stream.  NULL values, n out of range or a negative / non-finite / all-zero table: DRT_ERR_INVALID_ARGUMENT (checked
  * before the handle).  drt_set_phase called with kind 3 returns DRT_ERR_INVALID_ARGUMENT.  No gradients with respect to the values: a
  * non-NULL grad_phase_g / non-zero t_phase_g of the *_phase entry points on such a handle returns DRT_ERR_UNSUPPORTED.  Node spacing is
@@ -487,9 +487,7 @@ int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out
  * -DDRT_TEST_HOOKS (libdrt_hip_hooks.so) accepts non-zero flags.  Every bit that is tested, by its name in csrc/drt_device.h (enum Hook):
  *  bit  0 (1)          kHookNoGradAtomics       skip the gradient atomics (timing only)
  *  bit  1 (2)          kHookPerLaneAtomics      per-lane (uncoalesced) gradient atomics
- *  bit  3 (8)          kHookPerLanePrimal       the plain one-ray-per-lane tracing kernel for primal launches; never the state machine
  *  bit  4 (16)         kHookNoOccupancy         no empty-space bitmask
- *  bit  5 (32)         kHookWavefrontAdjoint    the state-machine kernel (drt_wavefront.hip) for the adjoint too
  *  bit  6 (64)         kHookUntileKeepScratch   untile pass without re-zeroing the apron scratch it reads (timing only)
  *  bit  7 (128)        kHookAtomicGradients     gradient splats as atomics into the apron scratch (the path used when the grid has more than
  *                                               16384 tiles or the record streams exceed the memory budget) instead of deferred records
@@ -499,15 +497,13 @@ int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out
  *  bit 10 (1024)       kHookReduceNoFlush       reduction without the flush (timing only)
  *  bit 11 (2048)       kHookPipelineBatches     overlap the tracer of ray sub-batch b with the reduction of sub-batch b - 1 on a side stream
  *                                               (measured slower)
- *  bit 12 (4096)       kHookNoQueuedTracer      keep supergrid launches off the queued tracer (drt_sq.hip): the round-3 kernel drt_super.hip
- *                                               where it serves, CoopTracer<SUPER> otherwise
+ *  bit 12 (4096)       kHookNoQueuedTracer      keep supergrid launches off the queued tracer (drt_sq.hip): every estimator then runs
+ *                                               CoopTracer<SUPER> (drt_coop_super.hip), the production fallback for supergrids beyond the
+ *                                               queued tracer's LDS limit, max_depth > 1000 and jobs without record memory
  *  bit 13 (8192)       kHookFewPartWGs          the partition passes of the gradient reduction (histogram, offsets, scatter) with three
  *                                               workgroups per stream instead of 384: a scene of a few thousand rays then gives a workgroup
  *                                               several batches, i.e. exercises the scatter's carry of its cursors from batch to batch
  *  bit 14 (16384)      kHookSmallRecordBudget   8 MB record budget, i.e. many ray sub-batches
- *  bit 15 (32768)      kHookPerLaneAdjoint      plain one-ray-per-lane adjoint kernel instead of the wave-cooperative tracking loops (drt_coop.hip)
- *  bit 16 (65536)      kHookWavefrontPrimal     state-machine kernel for the primal (default: the cooperative kernel, which also writes the
- *                                               path cache)
  *  bit 18 (262144)     kHookNoRecordMemory      pretend that the record streams cannot be allocated (the job then takes the atomic path, as it
  *                                               does when hipMalloc fails)
  *  bit 19 (524288)     kHookNoRecordMemoryLater pretend that they cannot be (re)allocated from the second ray sub-batch on (the remaining rays
@@ -520,13 +516,14 @@ int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out
  *  bit 24 (16777216)   kHookPlainBlockMap       plain XCD block map (production: heavy blocks of the previous launch first)
  *  bit 25 (33554432)   kHookNoHandOff           no workgroup hand-off of sparse waves' paths (every wave runs its own paths to the end)
  *  bit 26 (67108864)   kHookNoHandOffPrimal     none in the primal pass only
- *  bit 27 (134217728)  kHookWavefrontSupergrid  supergrid scenes in the older kernels instead of the supergrid tracers
  *  bit 28 (268435456)  kHookNoTailOverlap       no early histogram pass beside the adjoint's tail launch (queued tracer: no tail pool)
  *  bit 29 (536870912)  kHookIndexOrder          the supergrid tracer takes its rays in index order (production: thick pixels first)
  *  bit 30 (1073741824) kHookScheduleSmall       launches of fewer than 1.5 M rays are scheduled like large ones (ray order, tail launch) - the
  *                                               small scenes of the tests then cover those schedules
  *  bit 31 (2147483648) kHookWalkEmptyPixels     the queued supergrid tracer walks every flight (production: the primary-segment flights of
- *                                               pixels whose rays cross only empty supergrid cells are ended at their set-up) */
+ *                                               pixels whose rays cross only empty supergrid cells are ended at their set-up)
+ * Bits 3, 5, 15, 16 and 27 (8, 32, 32768, 65536, 134217728) selected the older tracer generations, which have been removed: a word
+ * that contains one of them is refused with DRT_ERR_INVALID_ARGUMENT and leaves the handle's flags as they were. */
 int drt_set_debug_flags(drt_handle h, uint32_t flags);
 
 const char *drt_version(void);

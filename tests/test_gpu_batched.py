@@ -84,7 +84,7 @@ def test_losses(uivr, gpu):
 def test_render_batch_logical_shards_equal_unsharded(uivr, gpu, factor):
     """Sharded render_batch without a process group (SURVEY.md 8e "G logical shards on one device"): the ranks'
     shares, rendered one after the other, tile the unsharded batch bit for bit; gradient shares sum to the
-    unsharded gradient.  Global majorant (cooperative kernels) and supergrid (state machine + per-lane kernels)."""
+    unsharded gradient.  Global majorant (cooperative kernels) and supergrid (the queued tracer)."""
     from uivr_amd import synthetic
     scene = synthetic.smoke_scene(res=24, film=32, device=gpu, optical_side=10.0)
     scene.sensors = synthetic.ring_sensors(5, radius=5.0, height=0.8, fov=30.0, width=32, film_height=32)

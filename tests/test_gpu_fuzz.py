@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import hook_bits as H
 from conftest import VARIANTS, props_for
 from test_oracle_envmap import _blob_map
 
@@ -150,19 +151,16 @@ def _phase_tag(ph):
     return f"hg2({ph.g1!r}, {ph.g2!r}, {ph.weight!r})" if int(ph.kind) == 2 else (f"hg({ph.g!r})" if int(ph.kind) == 1 else "isotropic")
 
 
-# the switches of _HOOKS (below) that the Henyey-Greenstein kernels accept - the others route the launch to an older tracer generation, which has no
-# such code and refuses -, no switch at all, and 4096: CoopTracer<SUPER> in place of the queued tracer
-_OLDER = 8 | 32 | 32768 | 65536 | 134217728
-
-
+# no switch at all, NO_QUEUED_TRACER (CoopTracer<SUPER> in place of the queued tracer), and the other switches of _HOOKS (below): the
+# Henyey-Greenstein kernels run under every one of them
 def _phase_hooks():
-    return [0, 4096] + [f for f in _HOOKS if not f & _OLDER]
+    return [0, H.NO_QUEUED_TRACER] + [f for f in _HOOKS if f != H.NO_QUEUED_TRACER]
 
 
 def _draw_phase_flags(rng):
     u = rng.random()                                                                # two in five: production's route; one in four: CoopTracer<SUPER>
     hooks = _phase_hooks()
-    return 0 if u < 0.4 else (4096 if u < 0.65 else int(hooks[int(rng.integers(0, len(hooks)))]))
+    return 0 if u < 0.4 else (H.NO_QUEUED_TRACER if u < 0.65 else int(hooks[int(rng.integers(0, len(hooks)))]))
 
 
 @pytest.mark.parametrize("seed", SEEDS[:max(1, len(SEEDS) // 2)])
@@ -177,7 +175,7 @@ def test_random_scene_with_a_phase_matches_the_oracle(uivr, oracle, gpu, seed):
 
 
 def test_the_phase_draws_cover_the_tracers():
-    """Among the default seeds: no switch (the production route) and 4096 (CoopTracer<SUPER>) both occur, and each kind of draw does."""
+    """Among the default seeds: no switch (the production route) and NO_QUEUED_TRACER (CoopTracer<SUPER>) both occur, and each kind of draw does."""
     class Stub:
         HGPhase = staticmethod(lambda g: ("hg", g))
         HG2Phase = staticmethod(lambda a, b, w: ("hg2", a, b, w))
@@ -187,7 +185,7 @@ def test_the_phase_draws_cover_the_tracers():
         ph = _draw_phase(Stub, rng)
         kinds.add(ph[0] if ph[0] == "hg2" else ("hg-small" if abs(ph[1]) < 0.05 else "hg"))
         flags.add(_draw_phase_flags(rng))
-    assert {0, 4096} <= flags and {"hg", "hg2"} <= kinds, (flags, kinds)
+    assert {0, H.NO_QUEUED_TRACER} <= flags and {"hg", "hg2"} <= kinds, (flags, kinds)
 
 
 def _check(uivr, oracle, gpu, c, seed, flags=0):
@@ -268,10 +266,11 @@ def test_nerf_with_strongly_negative_densities(uivr, oracle, gpu, seed):
 
 @pytest.mark.parametrize("seed", SEEDS[:max(1, len(SEEDS) // 8)])
 def test_random_nerf_scene_on_the_record_path_matches_the_oracle(uivr, oracle, gpu, seed):
-    """The nerf draws with the adjoint of sensor rays sent through the record path (test hook 512: nerf_kernel + deferred splatting, as explicit ray batches
-    and own-lattice scenes go in production) and its fall-backs: atomics (128), two-chunk streams (256), many sub-batches (16384), memory running out."""
+    """The nerf draws with the adjoint of sensor rays sent through the record path (test hook NERF_RECORD_PATH: nerf_kernel + deferred splatting, as explicit ray batches
+    and own-lattice scenes go in production) and its fall-backs: atomics, two-chunk streams, many sub-batches, memory running out."""
     rng = np.random.default_rng(55_000 + seed)
-    flags = 512 | int(rng.choice([0, 0, 128, 256, 16384, 16384 | 524288, 262144]))
+    flags = H.NERF_RECORD_PATH | int(rng.choice([0, 0, H.ATOMIC_GRADIENTS, H.TINY_RECORD_STREAMS, H.SMALL_RECORD_BUDGET,
+                                                 H.SMALL_RECORD_BUDGET | H.NO_RECORD_MEMORY_LATER, H.NO_RECORD_MEMORY]))
     _check_nerf(uivr, oracle, gpu, seed + 300, flags=flags)
 
 
@@ -653,20 +652,39 @@ def test_random_windows_of_the_wavefront_add_up_to_the_whole(uivr, oracle, gpu, 
 
 # schedules and fall-backs that production takes only at size or under memory pressure, selectable through the library flavour with test hooks
 # (include/drt_hip.h, drt_set_debug_flags): none of them may change a result
-_HOOKS = [16, 128, 256, 2048, 16384, 16384 | 524288, 262144, 1048576, 2097152, 33554432, 67108864, 268435456, 536870912, 1073741824,
-          1073741824 | 268435456, 2147483648, 8, 32, 32768, 65536, 134217728]
+_HOOKS = [H.NO_OCCUPANCY, H.ATOMIC_GRADIENTS, H.TINY_RECORD_STREAMS, H.PIPELINE_BATCHES, H.SMALL_RECORD_BUDGET,
+          H.SMALL_RECORD_BUDGET | H.NO_RECORD_MEMORY_LATER, H.NO_RECORD_MEMORY, H.NO_PATH_CACHE, H.GENERIC_KERNELS, H.NO_HAND_OFF,
+          H.NO_HAND_OFF_PRIMAL, H.NO_TAIL_OVERLAP, H.INDEX_ORDER, H.SCHEDULE_SMALL, H.SCHEDULE_SMALL | H.NO_TAIL_OVERLAP, H.WALK_EMPTY_PIXELS,
+          H.NO_QUEUED_TRACER]
+
+
+def _draw_schedule(uivr, seed):
+    """The scene and the one to three switches of a seed of test_random_scene_under_random_schedules_matches_the_oracle."""
+    rng = np.random.default_rng(99_000 + seed)
+    c = _draw(uivr, seed + 6100, medium_size=seed % 2 == 1)
+    flags = 0
+    for _ in range(int(rng.integers(1, 4))):
+        flags |= int(_HOOKS[int(rng.integers(0, len(_HOOKS)))])
+    return c, flags
+
+
+def test_the_schedule_draws_reach_the_supergrid_fallback(uivr):
+    """Among the default seeds one draws NO_QUEUED_TRACER on a scene with a majorant supergrid - CoopTracer<SUPER> (drt_coop_super.hip), production's
+    fallback for the supergrids the queued tracer does not take: seed 5, SCHEDULE_SMALL | NO_QUEUED_TRACER, factor 4, quadratic DRT."""
+    draws = {seed: _draw_schedule(uivr, seed) for seed in range(12)}
+    assert any(flags & H.NO_QUEUED_TRACER and c["factor"] > 0 for c, flags in draws.values()), {s: (f, c["factor"]) for s, (c, f) in draws.items()}
+    c, flags = draws[5]
+    assert (flags, c["factor"], c["variant"]) == (H.SCHEDULE_SMALL | H.NO_QUEUED_TRACER, 4, "quadratic")
+    assert not any(flags & H.RETIRED for _, flags in draws.values())
 
 
 @pytest.mark.parametrize("seed", SEEDS[:max(1, len(SEEDS) // 4)])
 def test_random_scene_under_random_schedules_matches_the_oracle(uivr, oracle, gpu, seed):
     """The draws under one to three of the schedule / fall-back switches of the test-hooks flavour: splats as atomics, two-chunk record streams, many ray
     sub-batches, record memory 'running out', no path cache, generic kernels, no hand-offs, index order, small launches scheduled like large ones
-    (ray order, tail pool, tail launch beside the partition), every flight walked, the older tracers.  Radiance bit-exact, counters equal, gradients close."""
-    rng = np.random.default_rng(99_000 + seed)
-    c = _draw(uivr, seed + 6100, medium_size=seed % 2 == 1)
-    flags = 0
-    for _ in range(int(rng.integers(1, 4))):
-        flags |= int(_HOOKS[int(rng.integers(0, len(_HOOKS)))])
+    (ray order, tail pool, tail launch beside the partition), every flight walked, supergrids in CoopTracer<SUPER>.  Radiance bit-exact, counters equal,
+    gradients close."""
+    c, flags = _draw_schedule(uivr, seed)
     scene, props, spp, rs = c["scene"], c["props"], c["spp"], c["seed"]
     tag = f"seed {seed} flags {flags}: {c['variant']} factor {c['factor']} grid {c['shape']} colour {c['cshape']} film {c['film']} spp {spp} env {c['env']}"
     s = scene.sensors[0]

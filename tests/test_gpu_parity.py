@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import hook_bits as H
 from conftest import VARIANTS, props_for
 
 pytestmark = pytest.mark.gpu
@@ -146,7 +147,7 @@ def test_multi_tile_grid_gradients_match_oracle(uivr, oracle, gpu):
     batch = uivr.RayBatch(n_rays=n, spp=spp, o=torch.from_numpy(o).to(gpu), d=torch.from_numpy(d).to(gpu))
     samp = uivr.IndependentSampler(seed, spp)
     h = integ.native_handle(sg)
-    for flags in (0, 128):                                               # deferred records / atomics into the apron scratch
+    for flags in (0, H.ATOMIC_GRADIENTS):                                # deferred records / atomics into the apron scratch
         h.set_debug_flags(flags)
         L, _, st = integ.sample(uivr.ADMode.Primal, sg, samp.clone(), batch)
         np.testing.assert_array_equal(L.cpu().numpy().view(np.uint32), Lr.view(np.uint32))
@@ -198,9 +199,9 @@ def test_path_cache_is_tied_to_the_rays(uivr, oracle, gpu):
     _assert_grads_close(grads[uivr.SIGMA_T_KEY], gs, "stale cache: grad sigma_t")
     _assert_grads_close(grads[uivr.ALBEDO_KEY], ga, "stale cache: grad albedo")
 
-    # proper sequence, cache on (0) and off (1048576): same gradients, adjoint counters equal to the oracle's
+    # proper sequence, cache on (0) and off (NO_PATH_CACHE): same gradients, adjoint counters equal to the oracle's
     h = integ.native_handle(sg)
-    for flags in (0, 1048576):
+    for flags in (0, H.NO_PATH_CACHE):
         h.set_debug_flags(flags)
         L, _, st = integ.sample(uivr.ADMode.Primal, sg, samp.clone(), batch)
         np.testing.assert_array_equal(L.cpu().numpy().view(np.uint32), Lb.view(np.uint32))
@@ -328,7 +329,7 @@ def test_error_behaviour(uivr, gpu):
 def test_sharded_equals_unsharded(uivr, gpu, factor):
     """Logical shards on one device: image tiles dealt to `world` ranks,
     global-index random streams => identical pixels, gradients equal up to fp order - with the global majorant
-    (cooperative tracer) and with a majorant supergrid (drt_super.hip: interleaved ray chunks through its ray queues)."""
+    (cooperative tracer) and with a majorant supergrid (the queued tracer, drt_sq.hip: interleaved ray chunks through its ray queues)."""
     scene = uivr.cube_test_scene(32, 32, density_scale=2.0)
     if factor:
         st = np.repeat(np.repeat(np.repeat(np.asarray(scene.medium.sigma_t), 4, 0), 4, 1), 4, 2)     # 3^3 -> 12^3 voxels: 4^3 supergrid cells
@@ -476,28 +477,27 @@ def test_sigma_t_gradient_vs_finite_differences(uivr, gpu, variant):
         assert abs(a - b) <= 5 * np.hypot(sa, sb) + 0.03 * abs(b) + 2e-6, (variant, e, a, sa, b, sb)
 
 
-@pytest.mark.parametrize("flags,variant", [(8, "drt"), (8, "basic"), (32, "drt"), (32, "drt-nomis"), (32, "basic"),
-                                           (2, "drt"), (16, "drt"), (128, "drt"), (128, "quadratic"), (256, "drt"),
-                                           (256, "basic"), (16384, "drt"), (16384 + 2048, "drt"), (2048, "basic"),
-                                           (32768, "drt"), (32768, "quadratic"), (65536, "drt"), (65536, "basic"),
-                                           (65536, "quadratic-nomis"), (262144, "drt"), (1048576, "drt"),
-                                           (16384 + 524288, "drt"), (2097152, "drt"), (2097152 + 128, "drt"), (1073741824, "drt"), (1073741824 + 268435456, "drt")])
+@pytest.mark.parametrize("flags,variant", [(H.PER_LANE_ATOMICS, "drt"), (H.NO_OCCUPANCY, "drt"), (H.ATOMIC_GRADIENTS, "drt"),
+                                           (H.ATOMIC_GRADIENTS, "quadratic"), (H.TINY_RECORD_STREAMS, "drt"), (H.TINY_RECORD_STREAMS, "basic"),
+                                           (H.SMALL_RECORD_BUDGET, "drt"), (H.SMALL_RECORD_BUDGET + H.PIPELINE_BATCHES, "drt"),
+                                           (H.PIPELINE_BATCHES, "basic"), (H.NO_RECORD_MEMORY, "drt"), (H.NO_PATH_CACHE, "drt"),
+                                           (H.SMALL_RECORD_BUDGET + H.NO_RECORD_MEMORY_LATER, "drt"), (H.GENERIC_KERNELS, "drt"),
+                                           (H.GENERIC_KERNELS + H.ATOMIC_GRADIENTS, "drt"), (H.SCHEDULE_SMALL, "drt"),
+                                           (H.SCHEDULE_SMALL + H.NO_TAIL_OVERLAP, "drt")])
 def test_every_kernel_variant_matches_oracle(uivr, oracle, gpu, flags, variant):
-    """The production path uses the wave-synchronous state machine for the primal and the
-    one-ray-per-lane kernel for the adjoint (measured faster).  The other combinations
-    stay verified: 8 = per-lane kernels everywhere, 32 = state machine for the adjoint too,
-    2 = uncoalesced per-lane atomics, 16 = no empty-space bitmask, 128 = gradient splats as atomics
-    into the apron scratch instead of deferred records, 256 = record streams of two chunks, so
-    almost every splat takes the out-of-chunks fallback (direct atomics into the caller's grid),
-    16384 = 8 MB record budget (the 16 k rays are traced in sub-batches of 2560), 2048 = the reduction
-    of sub-batch b - 1 overlapped with the tracer of sub-batch b on a side stream, 32768 = plain per-lane
-    adjoint kernel instead of the wave-cooperative tracking loops (production default for the adjoint),
-    65536 = state-machine kernel for the primal (no path cache), 262144 = record streams "cannot be
-    allocated" (fallback to the atomic path), 1048576 = path cache off, 524288 (with 16384) = the record memory
-    "runs out" after the first ray sub-batch (the rest of the job takes the atomic path), 2097152 = generic
-    instead of the specialised `volpathsimple-drt` kernels, 1073741824 = a launch this small scheduled like the large ones (tail launch for the
-    workgroups' last recursive paths, the histogram of the main launch's records on a side stream next to it), with
-    268435456 = without that early histogram pass."""
+    """A scene with the global majorant runs CoopTracer (drt_coop.hip: one ray per lane, wave-cooperative tracking loops) in both
+    passes; the primal writes the path cache, the ray schedule and the block costs the adjoint reads, and the adjoint's gradient
+    splats travel as deferred records.  What the test hooks change about that stays verified against the oracle:
+    PER_LANE_ATOMICS = uncoalesced per-lane atomics, NO_OCCUPANCY = no empty-space bitmask, ATOMIC_GRADIENTS = gradient splats as
+    atomics into the apron scratch instead of deferred records, TINY_RECORD_STREAMS = record streams of two chunks, so almost every
+    splat takes the out-of-chunks fallback (direct atomics into the caller's grid), SMALL_RECORD_BUDGET = 8 MB record budget (the
+    16 k rays are traced in sub-batches of 2560), PIPELINE_BATCHES = the reduction of sub-batch b - 1 overlapped with the tracer of
+    sub-batch b on a side stream, NO_RECORD_MEMORY = record streams "cannot be allocated" (fallback to the atomic path),
+    NO_PATH_CACHE = path cache off, NO_RECORD_MEMORY_LATER (with SMALL_RECORD_BUDGET) = the record memory "runs out" after the first
+    ray sub-batch (the rest of the job takes the atomic path), GENERIC_KERNELS = generic instead of the specialised
+    `volpathsimple-drt` kernels, SCHEDULE_SMALL = a launch this small scheduled like the large ones (tail launch for the workgroups'
+    last recursive paths, the histogram of the main launch's records on a side stream next to it), with NO_TAIL_OVERLAP = without
+    that early histogram pass."""
     props = props_for(variant)
     scene = uivr.cube_test_scene(32, 32, density_scale=2.0)
     spp, seed = 16, 777
@@ -531,7 +531,7 @@ def test_non_finite_gradients_propagate(uivr, gpu):
     spp, seed = 4, 3
     n = 16 * 16 * spp
     batch = uivr.RayBatch(n_rays=n, spp=spp, sensor=sg.sensors[0])
-    for flags in (0, 128):
+    for flags in (0, H.ATOMIC_GRADIENTS):
         h.set_debug_flags(flags)
         for bad in (float("nan"), float("inf")):
             samp = uivr.IndependentSampler(seed, spp)
@@ -557,9 +557,9 @@ def test_production_library_has_no_test_hooks(uivr, gpu):
     h = _integrator(uivr, props_for("drt")).native_handle(sg)
     h.set_debug_flags(0)
     with pytest.raises(RuntimeError, match="test hooks"):
-        h.set_debug_flags(128)
+        h.set_debug_flags(H.ATOMIC_GRADIENTS)
     hh = _integrator(uivr, props_for("drt"), hooks=True).native_handle(sg)
-    hh.set_debug_flags(128)
+    hh.set_debug_flags(H.ATOMIC_GRADIENTS)
     hh.set_debug_flags(0)
     assert type(h).__module__.endswith("_drt_pybind") and type(hh).__module__.endswith("_drt_pybind_hooks")
 
@@ -569,7 +569,7 @@ def test_workgroup_handoff_of_recursive_paths(uivr, oracle, gpu, factor):
     """The specialised kernels hand the last live paths of waves 1..3 (primal: main paths; adjoint: recursive DRT paths)
     to wave 0 through LDS (CoopTracer::wg_handoff), and the adjoint sends each workgroup's last recursive paths to a
     global pool that a second launch finishes - schedules, not results: with the hand-off (production) and
-    without it (debug bits 33554432 / 67108864, test-hooks flavour) radiance is bit-exact and the gradients are the
+    without it (NO_HAND_OFF / NO_HAND_OFF_PRIMAL, test-hooks flavour) radiance is bit-exact and the gradients are the
     oracle's.  A sparse medium, so that waves do run dry early."""
     rng = np.random.default_rng(21)
     st = rng.random((24, 24, 24, 1), dtype=np.float32) * 6.0
@@ -584,11 +584,12 @@ def test_workgroup_handoff_of_recursive_paths(uivr, oracle, gpu, factor):
     ref = oracle.h1_step(oracle.OracleScene(scene), props, spp, seed)
     sg = uivr.scene_to(scene, gpu)
     got = {}
-    # (1073741824: launches this small are scheduled like the large ones - tail pool + early histogram for the adjoint)
-    for name, hooks, flags in (("production", False, 0), ("hand-off", True, 1073741824), ("no hand-off", True, 33554432),
+    # (SCHEDULE_SMALL: launches this small are scheduled like the large ones - tail pool + early histogram for the adjoint)
+    for name, hooks, flags in (("production", False, 0), ("hand-off", True, H.SCHEDULE_SMALL), ("no hand-off", True, H.NO_HAND_OFF),
                                ("hand-off inside the workgroup only (small launch)", True, 0),
-                               ("tail launch without the early histogram", True, 1073741824 | 268435456),
-                               ("adjoint hand-off only", True, 67108864), ("hand-off, 8 MB record budget: many sub-batches", True, 16384 | 1073741824)):
+                               ("tail launch without the early histogram", True, H.SCHEDULE_SMALL | H.NO_TAIL_OVERLAP),
+                               ("adjoint hand-off only", True, H.NO_HAND_OFF_PRIMAL),
+                               ("hand-off, 8 MB record budget: many sub-batches", True, H.SMALL_RECORD_BUDGET | H.SCHEDULE_SMALL)):
         integ = _integrator(uivr, props, hooks=hooks)
         if hooks:
             integ.native_handle(sg).set_debug_flags(flags)
@@ -612,7 +613,7 @@ def test_heavy_tailed_ratio_tracking_splats_keep_ordinary_voxels_accurate(uivr, 
     typical one.  The deferred reduction quantises every product against the plane's LARGEST record
     (drt_deferred.hip: scale 2^(30-e)); the test checks that this leaves the ORDINARY voxels accurate: per voxel
     |hip - oracle| <= 1e-3 |oracle| wherever |oracle| >= 1e-4 x the median magnitude, for the deferred path and for the
-    atomic path (test hook 128), and that the two agree."""
+    atomic path (test hook ATOMIC_GRADIENTS), and that the two agree."""
     rng = np.random.default_rng(5)
     res = 24
     st = (rng.random((res, res, res, 1), dtype=np.float32) * 2.5 + 0.2).astype(np.float32)
@@ -625,7 +626,7 @@ def test_heavy_tailed_ratio_tracking_splats_keep_ordinary_voxels_accurate(uivr, 
     ref = oracle.h1_step(oracle.OracleScene(scene), props, spp, seed)
     sg = uivr.scene_to(scene, gpu)
     got = {}
-    for name, flags in (("deferred", 0), ("atomic", 128)):
+    for name, flags in (("deferred", 0), ("atomic", H.ATOMIC_GRADIENTS)):
         integ = _integrator(uivr, props, hooks=True)
         integ.native_handle(sg).set_debug_flags(flags)
         img, grads = _h1_gpu(uivr, sg, integ, spp, seed)
@@ -648,11 +649,14 @@ def test_heavy_tailed_ratio_tracking_splats_keep_ordinary_voxels_accurate(uivr, 
             print(key, name, "spread %.1f  rel err: median %.2e  p99.9 %.2e  max %.2e" % (spread, np.median(rel), np.percentile(rel, 99.9), rel.max()))
 
 
-@pytest.mark.parametrize("flags,variant", [(0, "drt"), (0, "drt-nomis"), (0, "basic"), (134217728, "drt"), (128, "drt"),
-                                           (1048576, "drt"), (16384, "drt"), (1073741824, "drt"), (1073741824 | 16384, "drt"),
-                                           (1073741824, "basic"), (0, "quadratic"), (4096, "quadratic"), (1048576, "quadratic"),
-                                           (16384, "quadratic"), (1073741824, "quadratic"), (1073741824, "drt-nomis"),
-                                           (1073741824 | 268435456, "drt"), (1073741824 | 1048576, "drt")])
+@pytest.mark.parametrize("flags,variant", [(0, "drt"), (0, "drt-nomis"), (0, "basic"), (H.ATOMIC_GRADIENTS, "drt"),
+                                           (H.NO_PATH_CACHE, "drt"), (H.SMALL_RECORD_BUDGET, "drt"), (H.SCHEDULE_SMALL, "drt"),
+                                           (H.SCHEDULE_SMALL | H.SMALL_RECORD_BUDGET, "drt"), (H.SCHEDULE_SMALL, "basic"), (0, "quadratic"),
+                                           (H.NO_QUEUED_TRACER, "quadratic"), (H.NO_PATH_CACHE, "quadratic"),
+                                           (H.SMALL_RECORD_BUDGET, "quadratic"), (H.SCHEDULE_SMALL, "quadratic"),
+                                           (H.SCHEDULE_SMALL, "drt-nomis"), (H.SCHEDULE_SMALL | H.NO_TAIL_OVERLAP, "drt"),
+                                           (H.SCHEDULE_SMALL | H.NO_PATH_CACHE, "drt"), (H.NO_QUEUED_TRACER, "drt"),
+                                           (H.NO_QUEUED_TRACER, "basic"), (H.NO_QUEUED_TRACER, "drt-nomis")])
 def test_supergrid_tracer_and_its_fallbacks_match_oracle(uivr, oracle, gpu, flags, variant):
     _supergrid_case(uivr, oracle, gpu, flags, variant, 7.0)
 
@@ -665,7 +669,7 @@ def test_supergrid_flights_that_cannot_collide_are_not_walked(uivr, oracle, gpu,
     _supergrid_case(uivr, oracle, gpu, 0, variant, density)
 
 
-@pytest.mark.parametrize("max_depth,use_nee,flags", [(2, True, 0), (3, True, 0), (5, True, 0), (4, False, 0), (3, True, 4096)])
+@pytest.mark.parametrize("max_depth,use_nee,flags", [(2, True, 0), (3, True, 0), (5, True, 0), (4, False, 0), (3, True, H.NO_QUEUED_TRACER)])
 def test_quadratic_drt_paths_cut_by_max_depth(uivr, oracle, gpu, max_depth, use_nee, flags):
     """Quadratic DRT in the queued tracer (QUAD kernels): a recursive path that is killed by max_depth still makes its phase
     draws (volpathsimple.py:221-222 run for every scatter), and here - unlike at the end of a subsampled path - the main
@@ -674,17 +678,17 @@ def test_quadratic_drt_paths_cut_by_max_depth(uivr, oracle, gpu, max_depth, use_
 
 
 def _supergrid_case(uivr, oracle, gpu, flags, variant, density, **over):
-    """Scenes with a majorant supergrid run in the cell-stepping tracer (drt_super.hip): every estimator it takes
-    (subsampled DRT with / without MIS, basic), with the path cache on and off (1048576), with the job cut into ray
-    sub-batches (16384: launches with ray_first > 0), with its rays started thick pixels first as launches of millions of
-    rays are (1073741824: from 4096 rays on; the at-size tests of test_gpu_configs.py run ordered by default, 536870912
-    would keep index order) - and, in the adjoint launches of the queued tracer, with the drained workgroups' last records handed
-    to the tail pool and finished by the tail launch beside the partition passes of the gradient reduction (round 5; with
-    268435456: without the pool); and what it hands back to the older kernels stays verified:
-    134217728 = the round-2 kernels for both passes, 128 = the atomic gradient path (no record streams).  Quadratic DRT runs
-    in the queued tracer's QUAD adjoint kernels (drt_sq.hip: the main path suspended at every vertex for the DRT walk + the
-    recursive path; with and without the path cache, in ray sub-batches) and, with test hook 4096 (drt_super.hip does not
-    take it), in the round-2 kernels.
+    """Scenes with a majorant supergrid run in the queued tracer (drt_sq.hip): every estimator (subsampled DRT with / without
+    MIS, basic), with the path cache on and off (NO_PATH_CACHE), with the job cut into ray sub-batches (SMALL_RECORD_BUDGET:
+    launches with ray_first > 0), with its rays started thick pixels first as launches of millions of rays are (SCHEDULE_SMALL:
+    from 4096 rays on; the at-size tests of test_gpu_configs.py run ordered by default, INDEX_ORDER would keep index order) - and,
+    in the adjoint launches, with the drained workgroups' last records handed to the tail pool and finished by the tail launch
+    beside the partition passes of the gradient reduction (round 5; with NO_TAIL_OVERLAP: without the pool).  Quadratic DRT runs
+    in the queued tracer's QUAD adjoint kernels (the main path suspended at every vertex for the DRT walk + the recursive path;
+    with and without the path cache, in ray sub-batches).  What the queued tracer does not take runs CoopTracer<SUPER>
+    (drt_coop_super.hip), production's fallback for supergrids beyond the LDS limit, max_depth > 1000 and jobs without record
+    memory: ATOMIC_GRADIENTS = the atomic gradient path (no record streams: the adjoint launch), NO_QUEUED_TRACER = both passes of
+    every estimator.
     Radiance bit-exact, counters equal, gradients close - against the oracle."""
     rng = np.random.default_rng(17)
     res = (24, 20, 28)                                   # X, Y, Z
@@ -718,13 +722,15 @@ def _supergrid_case(uivr, oracle, gpu, flags, variant, density, **over):
     _assert_grads_close(grads[uivr.ALBEDO_KEY], ref["grad_albedo"], "grad albedo")
 
 
-@pytest.mark.parametrize("flags,variant", [(0, "drt"), (4096, "drt"), (0, "basic"), (4096, "quadratic"), (0, "quadratic"), (1073741824, "drt")])
+@pytest.mark.parametrize("flags,variant", [(0, "drt"), (H.NO_QUEUED_TRACER, "drt"), (0, "basic"), (H.NO_QUEUED_TRACER, "quadratic"), (0, "quadratic"),
+                                           (H.SCHEDULE_SMALL, "drt")])
 def test_supergrid_too_large_for_lds_keeps_its_bitmask_there(uivr, oracle, gpu, flags, variant):
     """A supergrid whose majorants do not fit the tracer's LDS next to the ray records (160^3 voxels at factor 4 = 40^3
-    = 64000 cells: 125 KiB as bf16; the reference's default on a 512^3 grid gives 64^3) runs the instantiations that keep the
-    non-empty-cell bitmask in LDS and load the majorants of non-empty cells from L2: the queued tracer's (drt_sq.hip, MG:
-    flags 0) and the round-3 kernel's (drt_super.hip, MGL = false: test hook 4096).  A window of rays against the oracle;
-    counters in a counting launch."""
+    = 64000 cells: 125 KiB as bf16; the reference's default on a 512^3 grid gives 64^3) runs the queued tracer's instantiations
+    that keep the non-empty-cell bitmask in LDS and load the majorants of non-empty cells from L2 (drt_sq.hip, MG: flags 0); with
+    test hook NO_QUEUED_TRACER it runs CoopTracer<SUPER> (drt_coop_super.hip), which reads the majorants from L2 and, beyond the
+    32768 cells its LDS copy of the bitmask holds, the bitmask too.  A window of rays against the oracle; counters in a counting
+    launch."""
     rng = np.random.default_rng(3)
     res = 160
     lat = rng.random((20, 20, 20), dtype=np.float32)

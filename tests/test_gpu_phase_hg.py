@@ -308,10 +308,9 @@ def test_hook_to_older_generation_is_refused(uivr, gpu):
     sg = uivr.scene_to(scene, gpu)
     integ = _volpath(uivr, dict(props_for("drt"), test_hooks=True))
     h = integ.native_handle(sg)
-    for flags in (8, 32768, 65536):
-        h.set_debug_flags(flags)
-        with pytest.raises(RuntimeError, match="Henyey-Greenstein"):
-            uivr.render_primal(sg, integ, 0, 4, 1)
+    for flags in (8, 32768, 65536):                                   # (the kernels those bits selected are gone: set_debug_flags itself refuses)
+        with pytest.raises(RuntimeError, match="older tracer generations"):
+            h.set_debug_flags(flags)
     h.set_debug_flags(0)
     assert np.isfinite(uivr.render_primal(sg, integ, 0, 4, 1).cpu().numpy()).all()
 

@@ -459,10 +459,9 @@ def test_hook_to_older_generation_is_refused(uivr, gpu):
     sg = uivr.scene_to(scene, gpu)
     integ = _volpath(uivr, dict(props_for("drt"), test_hooks=True))
     h = integ.native_handle(sg)
-    for flags in (8, 32768, 65536):
-        h.set_debug_flags(flags)
+    for flags in (8, 32768, 65536):                                   # (the kernels those bits selected are gone: set_debug_flags itself refuses)
         with pytest.raises(RuntimeError, match="older tracer generations"):
-            uivr.render_primal(sg, integ, 0, 4, 1)
+            h.set_debug_flags(flags)
     h.set_debug_flags(0)
     assert np.isfinite(uivr.render_primal(sg, integ, 0, 4, 1).cpu().numpy()).all()
 
@@ -544,7 +543,7 @@ def test_raw_ctypes_statuses(uivr, gpu):
         sg.medium.phase = uivr.IsotropicPhase()
         Li, _, _ = _volpath(uivr, props).sample(uivr.ADMode.Primal, sg, uivr.IndependentSampler(seed, spp), batch)
         assert torch.equal(L, Li) and not torch.equal(Li, Lh)
-        # the hooks of the older generations need the other library flavour: this one refuses any flag
+        # test hooks need the other library flavour: this one refuses any flag
         assert lib.drt_set_debug_flags(h, u32(8)) != 0
     finally:
         lib.drt_destroy(h)

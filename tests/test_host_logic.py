@@ -131,15 +131,40 @@ def test_c_abi_library_exports_every_declared_symbol(uivr):
 
 def test_production_library_holds_no_older_tracer_generation(uivr):
     """a production call reaches CoopTracer (global majorant), the queued tracer (supergrid) or CoopTracer<SUPER>
-    (supergrids beyond it, the atomic gradient path) - the round-2 state machine (drt_wavefront.hip), the round-3 supergrid kernel
-    (drt_super.hip) and the plain per-lane Tracer are compiled only into the flavour with test hooks."""
+    (supergrids beyond it, the atomic gradient path).  The round-2 state machine of whole flights, the round-3 supergrid kernel and the
+    plain per-lane Tracer have been retired: neither library flavour holds their kernels."""
     from uivr_amd import _build
     prod, hooks = (open(p, "rb").read() for p in (_build.LIB_PATH, _build.HOOKS_LIB_PATH))
     for name in (b"trace_wavefront_kernel", b"trace_super_kernel", b"trace_kernelILb"):   # (and no fused_kernel in either: round 5 runs the fused pass as two dense passes)
         assert name not in prod, name
-        assert name in hooks, name
+        assert name not in hooks, name
     for name in (b"trace_sq_kernel", b"trace_coop_kernel", b"nerf_tile_adjoint_kernel", b"tile_reduce_kernel"):
         assert name in prod, name
+
+
+def test_hook_bits_are_listed_alike_everywhere():
+    """The test hooks by name and value: enum Hook (csrc/drt_device.h), the table in the comment of drt_set_debug_flags (include/drt_hip.h)
+    and tests/hook_bits.py list the same bits.  None of them lists a bit of the retired tracer generations; the C ABI names those only where
+    drt_set_debug_flags refuses them."""
+    import hook_bits
+    with open(os.path.join(ROOT, "unbiased-inverse-volume-rendering_amd", "csrc", "drt_device.h")) as f:
+        body = re.search(r"enum Hook : uint32_t \{(.*?)\n\};", f.read(), flags=re.S).group(1)
+    enum = {name: 1 << int(bit) for name, bit in re.findall(r"^\s*(kHook\w+)\s*=\s*1u << (\d+),", body, flags=re.M)}
+    assert len(enum) == len(re.findall(r"^\s*kHook\w+\s*=", body, flags=re.M)), "an enumerator that is not a single bit"
+    with open(os.path.join(ROOT, "include", "drt_hip.h")) as f:
+        comment = re.search(r"/\* Test hooks:(.*?)\*/\s*int drt_set_debug_flags", f.read(), flags=re.S).group(1)
+    rows = re.findall(r"^ \*  bit +(\d+) \((\d+)\) +(kHook\w+) ", comment, flags=re.M)
+    assert all(int(value) == 1 << int(bit) for bit, value, _ in rows), rows
+    table = {name: int(value) for _, value, name in rows}
+    assert len(table) == len(rows) and table == enum, sorted(set(table.items()) ^ set(enum.items()))
+
+    def snake(name):                                     # kHookFewPartWGs -> FEW_PART_WGS
+        return re.sub(r"(?<=[a-z0-9])(?=[A-Z])", "_", name[len("kHook"):]).upper()
+    names = {k: v for k, v in vars(hook_bits).items() if k.isupper() and k != "RETIRED"}
+    assert names == {snake(k): v for k, v in enum.items()}
+    assert hook_bits.RETIRED == 8 | 32 | 32768 | 65536 | 134217728
+    assert not any(v & hook_bits.RETIRED for v in enum.values())
+    assert "older tracer generations" in comment          # (the refusal is documented there)
 
 
 def test_c_abi_argument_errors_without_gpu(uivr):

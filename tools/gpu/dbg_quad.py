@@ -1,4 +1,4 @@
-"""Quadratic DRT through the queued tracer's QUAD kernels (flags 0) against the round-2 kernels (test hook 4096): counters and gradients."""
+"""Quadratic DRT through the queued tracer's QUAD kernels (flags 0) against CoopTracer<SUPER> (drt_coop_super.hip; test hook 4096): counters and gradients."""
 import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import uivr_amd as u

@@ -1,7 +1,7 @@
 #!/bin/bash
-# Usage (here, no GPU needed): tools/mk_variant.sh NAME "-DDRT_SUPER_K=4 ..." [source.hip ...]
+# Usage (here, no GPU needed): tools/mk_variant.sh NAME "-DDRT_SQ_K=4 ..." [source.hip ...]
 # Builds variants/NAME/libdrt_hip.so: the production objects of csrc/_obj with the listed translation units (default:
-# drt_super.hip) recompiled with the extra -D flags.  On the GPU box: LD_LIBRARY_PATH=variants/NAME python bench.py ...
+# drt_sq.hip) recompiled with the extra -D flags.  On the GPU box: LD_LIBRARY_PATH=variants/NAME python bench.py ...
 # (the pybind shim finds libdrt_hip.so through RUNPATH, which LD_LIBRARY_PATH precedes).  variants/ is git-ignored.
 set -e
 name=$1; defs=$2; shift 2 || true

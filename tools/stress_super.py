@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Stress of the supergrid tracer's LDS protocol (drt_super.hip): the headline scene at majorant_resolution_factor 8, the same
-seed over and over - radiance must be bitwise the same every time (a lost or duplicated flight, a stale slot or a missed
-done bit would change rays), gradients the same up to summation order and finite; a few seeds and film sizes so that the
+"""Stress of the queued supergrid tracer's LDS protocol (drt_sq.hip, the production route): the headline scene at
+majorant_resolution_factor 8, the same seed over and over - radiance must be bitwise the same every time (a lost or duplicated
+record, a stale ring entry or a missed hand-over would change rays), gradients the same up to summation order and finite; a few seeds and film sizes so that the
 end-of-kernel phase (few rays left per wave) is hit in different shapes.
 
     python tools/stress_super.py [--reps 20]

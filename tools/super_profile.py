@@ -1,9 +1,9 @@
-"""Raw profile slots of an experiment build of the supergrid tracer (drt_super.hip, -DDRT_SUPER_PROFILE=1|2|4):
+"""Raw profile slots of an experiment build of the queued supergrid tracer (drt_sq.hip, -DDRT_SQ_PROFILE=1|2|3|4):
 
-    tools/mk_variant.sh prof4 "-DDRT_SUPER_PROFILE=4"; LD_LIBRARY_PATH=variants/prof4 python tools/super_profile.py
+    tools/mk_variant.sh sqprof1 "-DDRT_SQ_PROFILE=1" drt_sq.hip; LD_LIBRARY_PATH=variants/sqprof1 DRT_PROFILE_MODE=sq python tools/super_profile.py
 
-(drt_sq.hip: tools/mk_variant.sh sqprof "-DDRT_SQ_PROFILE=1" drt_sq.hip; DRT_PROFILE_MODE=sq)
-(headline scene at majorant_resolution_factor 8; the meaning of the slots is next to DRT_PROF / DRT_PROF4 / DRT_STAMP in the source)
+(DRT_PROFILE_MODE = sq, sq2, sq3, sq4 for -DDRT_SQ_PROFILE = 1, 2, 3, 4; tools/gpu/run.sh sqprof runs all four)
+(headline scene at majorant_resolution_factor 8; the meaning of the slots is next to SQ_PROF / SQ_STAMP / SQ_BLK in csrc/drt_sq_kernel.h)
 """
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,7 +39,7 @@ integ.sample(u.ADMode.Backward, scene, sampler, batch, δL=dL, state_in=state, g
 ca = [int(v) for v in h.get_counters().values()]
 print("primal ", cp)
 print("adjoint", ca)
-mode = os.environ.get("DRT_PROFILE_MODE", "4")
+mode = os.environ.get("DRT_PROFILE_MODE", "sq")
 for tag, c in (("primal", cp), ("adjoint", ca)):
     if mode == "sq":
         print(f"{tag}: lane steps {c[0]/1e6:.1f} M, wave steps {c[1]/1e6:.2f} M -> {c[0]/max(1,c[1]):.1f} lanes per step; collision batches {c[2]/1e6:.3f} M x {c[3]/max(1,c[2]):.1f} rays; "
@@ -51,14 +51,3 @@ for tag, c in (("primal", cp), ("adjoint", ca)):
         tot = sum(c)
         names = ["cell steps", "walker queue work", "load (collision)", "collision code", "load (transition)", "transition code", "flight set-up", "store + push", "looking for work"]
         print(tag, {n: round(v / tot, 3) for n, v in zip(names, c)})
-    elif mode == "4":
-        print(f"{tag}: lane steps {c[0]/1e6:.1f} M, wave steps {c[1]/1e6:.2f} M -> {c[0]/max(1,c[1]):.1f} lanes per step; batches {c[2]/1e6:.2f} M, "
-              f"{c[3]/max(1,c[2]):.1f} flying at batch start, {c[4]/max(1,c[2]):.1f} finish per batch; transition passes {c[6]/1e6:.2f} M with "
-              f"{c[5]/max(1,c[6]):.1f} lanes; regeneration blocks {c[7]/1e6:.3f} M, {c[8]/max(1,c[7]):.1f} rays each")
-    elif mode == "2":
-        tot = sum(c[k] for k in (1, 3, 4, 5, 6, 7, 8))
-        names = {1: "poll/sleep", 3: "epilogue", 4: "regen", 5: "transitions", 8: "set-up", 6: "pull", 7: "steps+writeback"}
-        print(tag, {names[k]: round(c[k] / tot, 3) for k in names}, "heavy runs", c[2])
-    else:
-        print(f"{tag}: cell steps {c[0]/1e6:.1f} M, polls {c[1]/1e6:.2f} M, heavy runs {c[2]/1e6:.2f} M with {c[3]/max(1,c[2]):.1f} lanes ready, "
-              f"epilogue lanes {c[4]/max(1,c[2]):.1f}, posted {c[5]/max(1,c[2]):.1f}; pulls {c[6]/1e6:.2f} M x {c[7]/max(1,c[6]):.1f} flights; transition passes {c[8]/1e6:.2f} M")

@@ -2,7 +2,7 @@
 
   csrc/libdrt_hip.so                  hipcc: kernels + C ABI (include/drt_hip.h) - the production library
   _drt_pybind.<abi>.so                g++:   pybind11 shim linked against it
-  csrc/libdrt_hip_hooks.so            the same sources with -DDRT_TEST_HOOKS: kernel-variant selection, ablations,
+  csrc/libdrt_hip_hooks.so            the same sources (and the same kernels) with -DDRT_TEST_HOOKS: route selection, ablations,
   _drt_pybind_hooks.<abi>.so          simulated out-of-memory (drt_set_debug_flags) for the tests / profiling
 
 The arithmetic specification requires -ffp-contract=off; hardware fp32
@@ -24,9 +24,6 @@ HIP_SOURCES = ["drt_kernels.hip", "drt_deferred.hip", "drt_coop.hip", "drt_coop_
                "drt_coop_hg.hip", "drt_coop_super_hg.hip", "drt_own_hg.hip", "drt_sq_hg.hip",
                "drt_coop_hg2.hip", "drt_coop_super_hg2.hip", "drt_own_hg2.hip", "drt_sq_hg2.hip",
                "drt_coop_tab.hip", "drt_coop_super_tab.hip", "drt_own_tab.hip", "drt_sq_tab.hip", "drt_capi.cpp"]
-# older generations of the tracer (round 1/2 state machine of whole flights, round 3 lane state machines with posted flights): no production call
-# reaches them ("which call reaches which kernel"); the flavour with test hooks keeps them in lock-step with the oracle
-HOOKS_ONLY_SOURCES = ["drt_wavefront.hip", "drt_super.hip"]
 HIP_HEADERS = ["drt_sq_kernel.h", "drt_device.h", "drt_launch.h", "drt_coop_tracer.h", "drt_coop_kernel.h", "drt_nerf_kernel.h", "drt_nerf_tile_kernel.h", "drt_film.h", os.path.join(_ROOT, "include", "drt_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
              "-ffp-contract=off", "-munsafe-fp-atomics", "-Wall"]
@@ -77,7 +74,7 @@ def build_hip(force: bool = False, verbose: bool = False, hooks: bool = True):
         stamp = os.path.join(objdir, "flags.txt")
         flags_now = " ".join(HIP_FLAGS + env_defs + defs + [f"{k}:{' '.join(v)}" for k, v in sorted(UNIT_FLAGS.items())])
         stale = force or not os.path.exists(stamp) or open(stamp).read() != flags_now
-        srcs = [os.path.join(_CSRC, s) for s in HIP_SOURCES + (HOOKS_ONLY_SOURCES if defs else [])]
+        srcs = [os.path.join(_CSRC, s) for s in HIP_SOURCES]
         objs = [os.path.join(objdir, os.path.basename(s) + ".o") for s in srcs]
         todo = [(s, o) for s, o in zip(srcs, objs) if stale or _newer(o, [s] + hdrs)]
         jobs += [(s, o, defs) for s, o in todo]

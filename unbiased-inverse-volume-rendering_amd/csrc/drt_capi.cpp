@@ -76,7 +76,7 @@ struct drt_handle_s {
     uint32_t *d_scratch = nullptr; // [1]
     unsigned long long *d_counters = nullptr;   // [C_COUNT]
     DevBuf gt;                     // gradient scratch, 4 planes of floats (always zero between launches)
-    unsigned long long *d_queues = nullptr;   // 8 per-XCD ray queue heads (wavefront kernel)
+    unsigned long long *d_queues = nullptr;   // 8 per-XCD ray queue heads (queued tracer)
     DevBuf sq_cold;                           // queued supergrid tracer: adjoint path state kept in global memory (drt_sq.hip)
     DevBuf uempty;                            // per pixel: its rays cross only empty supergrid cells (build_unit_empty; queued supergrid tracer)
     uint64_t uempty_first = 0, uempty_end = 0, uempty_version = 0;   // ... made by the primal launch over these rays of the job the path cache describes, in
@@ -409,11 +409,6 @@ enum class Route {
     kCoopHG,     // CoopTracer with a Henyey-Greenstein phase, kHG / kHGGrad / kHG2 (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip and their _hg2 / _tab units; kTab too)
     kOwn,        // CoopTracer with the colour grids on their own lattice (drt_own.hip)
     kQueued,     // the queued supergrid tracer (drt_sq.hip, drt_sq_hg.hip, drt_sq_hg2.hip, drt_sq_tab.hip)
-#ifdef DRT_TEST_HOOKS
-    kSuper3,     // the round-3 supergrid kernel (drt_super.hip)
-    kWavefront,  // the round-2 state machine of whole flights (drt_wavefront.hip)
-    kPerLane,    // the plain per-lane Tracer (drt_kernels.hip)
-#endif
 };
 // phase: the instantiations of the handle's phase function (tracer_phase)
 struct Choice { Route route; drt::Phase phase; };
@@ -434,15 +429,13 @@ drt::Phase tracer_phase(drt_handle h, bool grad_g)
 //   both passes, every estimator - where its records fit LDS next to the supergrid's majorants or cell bitmask (sq_supported: up to ~99^3 cells,
 //   max_depth <= 1000) and the adjoint's splats travel as records; otherwise (larger supergrids, the atomic gradient path of grids beyond 16384
 //   reduction tiles or without record memory): CoopTracer<SUPER> (drt_coop_super.hip: own-lane tracking steps through the supergrid).
-//   Every primal kernel writes the path cache the adjoint pass of the job reads.  Only the library flavour with test hooks also holds the older
-//   generations - the round-3 supergrid kernel (drt_super.hip; kHookNoQueuedTracer), the round-2 state machine of whole flights (drt_wavefront.hip;
-//   kHookWavefrontAdjoint / Primal / Supergrid) and the plain per-lane Tracer (drt_kernels.hip; kHookPerLanePrimal / Adjoint) - where the variant
-//   tests keep them in lock-step.
+//   Every primal kernel writes the path cache the adjoint pass of the job reads.  Both library flavours hold these kernels and no others; the
+//   test hook kHookNoQueuedTracer sends every supergrid launch to CoopTracer<SUPER>.
 //   Colour grids on their own lattice (drt_set_colour_resolution): the kernels of drt_own.hip - CoopTracer with either kind of majorant, compiled
 //   with the colour lookups and splats on that lattice; no tail pool, no queued tracer (correct first: the configurations it serves are rare).
 //   Henyey-Greenstein phase (drt_set_phase): the same choice among the HG instantiations - the queued tracer (drt_sq_hg.hip) for the
 //   supergrids it takes, CoopTracer<HG> otherwise (drt_coop_hg.hip, drt_coop_super_hg.hip, drt_own_hg.hip) - without tail launches or
-//   hand-off, and no ROUNDS kernels; the older generations have no HG code.
+//   hand-off, and no ROUNDS kernels.
 //   The g-gradient (drt_render_backward_phase: an HG adjoint launch with a sink in Params::L_out) runs the kHGGrad instantiations of the same
 //   kernels; the counting kernels have none (such a launch counts nothing).
 //   Two-lobe Henyey-Greenstein phase (drt_set_phase_hg2): the HG choice among the kHG2 instantiations (drt_sq_hg2.hip, drt_coop_hg2.hip,
@@ -458,22 +451,10 @@ Choice choose_tracer(drt_handle h, const drt::Params &P, bool adjoint)
     // (kHookNoQueuedTracer: CoopTracer<SUPER> with the HG phase here - the HG kernels' tracer-agreement tests)
     if (hg && (P.colour_own || !P.mgrid || dbg(f, kHookNoQueuedTracer))) return to(Route::kCoopHG);
     if (P.colour_own) return to(Route::kOwn);
-    // a supergrid launch: not when a test hook or the atomic gradient path (an adjoint launch without record streams) routes it to the older kernels
-    const bool super_path = P.mgrid && !dbg(f, kHookOlderTracers) && (!adjoint || P.rec_buf[0] != nullptr);
+    // a supergrid launch the queued tracer can take: not the atomic gradient path (an adjoint launch without record streams)
+    const bool super_path = P.mgrid && (!adjoint || P.rec_buf[0] != nullptr);
     if (super_path && !dbg(f, kHookNoQueuedTracer) && drt::sq_supported(P)) return to(Route::kQueued);
-#ifdef DRT_TEST_HOOKS
-    const bool quadratic = h->cfg.use_drt && !h->cfg.use_drt_subsampling;
-    if (super_path && !quadratic && dbg(f, kHookNoQueuedTracer) && drt::super_supported(P)) return to(Route::kSuper3);
-#endif
     if (hg) return to(Route::kCoopHG);                                     // (supergrids the queued tracer does not take)
-#ifdef DRT_TEST_HOOKS
-    // (kHookWavefrontSupergrid = supergrid scenes in the round-2 kernels - the state machine of whole flights for the primal pass,
-    //  kHookWavefrontPrimal = that kernel for any primal pass, kHookWavefrontAdjoint = for the adjoint too)
-    const bool sm_primal = !adjoint && ((P.mgrid != nullptr && dbg(f, kHookWavefrontSupergrid)) || dbg(f, kHookWavefrontPrimal)) && !dbg(f, kHookPerLanePrimal);
-    const bool sm_adjoint = adjoint && dbg(f, kHookWavefrontAdjoint) && !quadratic && !dbg(f, kHookPerLanePrimal);
-    if (sm_primal || sm_adjoint) return to(Route::kWavefront);
-    if (dbg(f, adjoint ? kHookPerLaneAdjoint : kHookPerLanePrimal)) return to(Route::kPerLane);
-#endif
     return to(Route::kCoop);
 }
 
@@ -552,10 +533,9 @@ int bind_unit_empty(drt_handle h, const drt::Params &P, drt::Params &Q, bool adj
     return DRT_OK;
 }
 
-// Ray order of the supergrid tracers: the longest paths first - units of one pixel's rays by the majorant optical depth along the pixel's ray
-// (drt_super.hip).  Best effort (no memory: index order); kHookIndexOrder: index order.
-// iters_ok: the launch may order its units by the primal pass's iteration counts (the queued tracer)
-int bind_ray_order(drt_handle h, const drt::Params &P, drt::Params &Q, bool adjoint, bool iters_ok)
+// Ray order of the queued tracer: the longest paths first - units of one pixel's rays by the majorant optical depth along the pixel's ray
+// (drt_order.hip).  Best effort (no memory: index order); kHookIndexOrder: index order.
+int bind_ray_order(drt_handle h, const drt::Params &P, drt::Params &Q, bool adjoint)
 {
     const uint64_t span = P.n_rays - P.ray_first;
     const uint32_t unit = P.spp >= 4u ? P.spp : 16u;
@@ -575,7 +555,7 @@ int bind_ray_order(drt_handle h, const drt::Params &P, drt::Params &Q, bool adjo
     if (!h->order.p) return DRT_OK;
     // (adjoint launches behind the primal pass of the same job: the primal pass counted every ray's bounce-loop iterations -
     //  units with a long main path start first, whatever the optical depth along their pixel's ray says)
-    const uint8_t *iters = (DRT_ORDER_ITERS && adjoint && P.path_cache_mode == 2 && iters_ok) ? P.ray_iters : nullptr;
+    const uint8_t *iters = (DRT_ORDER_ITERS && adjoint && P.path_cache_mode == 2) ? P.ray_iters : nullptr;
     const bool reuse = !iters && adjoint && P.path_cache_mode == 2 && h->order_unit == unit && h->order_first == P.ray_first && h->order_end == P.n_rays;
     if (!reuse) DRT_HIP_CHECK(h, drt::build_super_order(P, unit, units, h->order.p, h->stream, iters));
     h->order_unit = (!adjoint && P.path_cache_mode == 1) || reuse ? unit : 0u;
@@ -584,11 +564,11 @@ int bind_ray_order(drt_handle h, const drt::Params &P, drt::Params &Q, bool adjo
     return DRT_OK;
 }
 
-// what the launches of the two supergrid tracers (queued, round 3) share: the XCD queues, the ray order, the thin-medium hint
+// what a launch of the queued tracer begins with: the XCD queues, the ray order, the thin-medium hint
 int begin_supergrid_launch(drt_handle h, const drt::Params &P, drt::Params &Q, bool adjoint, const Choice &c)
 {
     Q.queues = h->d_queues;
-    DRT_TRY(bind_ray_order(h, P, Q, adjoint, c.route == Route::kQueued));
+    DRT_TRY(bind_ray_order(h, P, Q, adjoint));
     Q.ray_perm = nullptr; Q.block_order = nullptr;
     // thin medium (as far as the host has seen its majorant - drt_params_changed - without waiting for anything)?  Primal launches in index order then
     // run the ROUNDS kernels (drt_sq.hip): an optimisation's first iterations, where nearly every ray is over before it begins
@@ -678,27 +658,6 @@ int launch_queued(drt_handle h, const drt::Params &P, bool adjoint, const Choice
     return DRT_OK;
 }
 
-#ifdef DRT_TEST_HOOKS
-// the older generations, kept in lock-step by the variant tests: the round-3 supergrid kernel (which also serves what the queued one does not
-// take), the round-2 state machine of whole flights and the plain per-lane Tracer
-int launch_older(drt_handle h, const drt::Params &P, bool adjoint, const Choice &c)
-{
-    drt::Params Q = P;
-    if (c.route == Route::kSuper3) {
-        DRT_TRY(begin_supergrid_launch(h, P, Q, adjoint, c));
-        DRT_HIP_CHECK(h, drt::launch_trace_super(Q, adjoint, h->counting, h->n_cus, h->stream));
-    } else if (c.route == Route::kWavefront) {
-        Q.queues = h->d_queues;
-        DRT_HIP_CHECK(h, hipMemsetAsync(h->d_queues, 0, 8 * sizeof(unsigned long long), h->stream));
-        DRT_HIP_CHECK(h, drt::launch_trace_wavefront(Q, adjoint, h->counting, h->n_cus, h->stream));
-    } else {
-        Q.ray_perm = nullptr;
-        DRT_HIP_CHECK(h, drt::launch_trace(Q, adjoint, h->counting, h->stream));
-    }
-    return DRT_OK;
-}
-#endif
-
 // one tracing launch, bracketed by an event pair on the handle's stream when timing is enabled
 int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
 {
@@ -706,25 +665,17 @@ int timed_launch(drt_handle h, int which, const drt::Params &P, bool adjoint)
     DRT_HIP_CHECK(h, span.begin(h, h->stream));
     const Choice c = choose_tracer(h, P, adjoint);
     const bool hg = c.phase != drt::Phase::kIso;
-    if (hg && dbg(h->debug_flags, kHookOlderTracers))
-        return fail(h, DRT_ERR_UNSUPPORTED, "the Henyey-Greenstein phase functions have no code in the older tracer generations: the test hook "
-                                            "routes this launch to one of them (debug flags 0x%x)", h->debug_flags);
     int rc = DRT_OK;
     switch (c.route) {
     case Route::kCoopHG:
     case Route::kOwn: rc = launch_coop_hg_or_own(h, P, adjoint, c); break;
     case Route::kQueued:
         // (the records' global halves, ~44 MB, are allocated only by a launch that will run the queued kernel: not when a test hook or the atomic
-        //  gradient path routes this launch to the older kernels; no memory: the route of a supergrid the queued tracer does not take)
+        //  gradient path routes this launch to CoopTracer<SUPER>; no memory: the route of a supergrid the queued tracer does not take)
         DRT_TRY(h->sq_cold.grow(h, drt::sq_cold_bytes(h->n_cus), kBestEffort));
         rc = h->sq_cold.p ? launch_queued(h, P, adjoint, c) : hg ? launch_coop_hg_or_own(h, P, adjoint, c) : launch_coop(h, P, adjoint);
         break;
     case Route::kCoop: rc = launch_coop(h, P, adjoint); break;
-#ifdef DRT_TEST_HOOKS
-    case Route::kSuper3:
-    case Route::kWavefront:
-    case Route::kPerLane: rc = launch_older(h, P, adjoint, c); break;
-#endif
     }
     if (rc) return rc;
     DRT_HIP_CHECK(h, span.end(which));
@@ -739,7 +690,7 @@ constexpr uint64_t kRecBudgetBytes = 48ull << 30;               // record stream
 
 bool want_deferred(drt_handle h, const drt::Params &P)
 {
-    if (dbg(h->debug_flags, kHookAtomicGradients | kHookPerLaneAtomics | kHookWavefrontAdjoint)) return false;
+    if (dbg(h->debug_flags, kHookAtomicGradients | kHookPerLaneAtomics)) return false;
     const int ntx = (P.rx + drt::kTileX - 1) / drt::kTileX, nty = (P.ry + drt::kTileY - 1) / drt::kTileY,
               ntz = (P.rz + drt::kTileZ - 1) / drt::kTileZ;
     return (int64_t) ntx * nty * ntz <= drt::kMaxBins;
@@ -1449,22 +1400,20 @@ int drt_render_primal(drt_handle h, const float *rays_o, const float *rays_d, ui
     bind_path_cache_write(h, P);                                 // every primal kernel records its walks
     {   // the block order left by the previous primal launch of the same shape predicts this one's heavy blocks
         // (same sensor, next step); an order is only ever a schedule, never a result
-        if (!dbg(h->debug_flags, kHookPlainBlockMap) && P.block_cost && h->order_rays == n_rays && !P.mgrid &&
-            !dbg(h->debug_flags, kHookPrimalNotCoop))
+        if (!dbg(h->debug_flags, kHookPlainBlockMap) && P.block_cost && h->order_rays == n_rays && !P.mgrid)
             P.block_order = P.block_cost + (n_rays + 255) / 256;
     }
     int rc = timed_launch(h, 0, P, false);
     h->order_valid = false;
     h->perm_valid = false;
-    // the cooperative primal kernel (global majorant) and the state machine (supergrid) write the sort keys
+    // the primal kernels write the sort keys
     // (only the global-majorant adjoint kernel takes its rays through the schedule: supergrid scenes skip the sort - 0.065 ms of the
     //  factor-8 headline's step)
-    if (rc == DRT_OK && P.ray_iters && !P.mgrid && !dbg(h->debug_flags, kHookPerLanePrimal)) {   // (the plain per-lane primal kernel does not)
-        const bool coop_costs = P.block_cost && !P.mgrid && !dbg(h->debug_flags, kHookWavefrontPrimal);        // the cooperative primal filled block_cost
-        DRT_HIP_CHECK(h, drt::launch_ray_perm(P.ray_iters, P.n_rays, perm_base(P.ray_hash, P.n_rays), coop_costs ? P.block_cost : nullptr, h->stream));
+    if (rc == DRT_OK && P.ray_iters && !P.mgrid) {
+        DRT_HIP_CHECK(h, drt::launch_ray_perm(P.ray_iters, P.n_rays, perm_base(P.ray_hash, P.n_rays), P.block_cost, h->stream));   // (block_cost: the cooperative primal filled it)
         h->perm_valid = true;
     }
-    if (rc == DRT_OK && P.block_cost && !P.mgrid && !dbg(h->debug_flags, kHookPrimalNotCoop)) {   // cooperative primal: it filled block_cost
+    if (rc == DRT_OK && P.block_cost && !P.mgrid) {   // cooperative primal: it filled block_cost
         const uint32_t n_blocks = (uint32_t) ((P.n_rays + 255) / 256);
         DRT_HIP_CHECK(h, drt::launch_block_order(P.block_cost, n_blocks, P.block_cost + n_blocks, n_blocks <= kHeavyFirstMaxBlocks, h->stream));
         h->order_valid = true; h->order_rays = n_rays;
@@ -1489,7 +1438,7 @@ static int render_backward(drt_handle h, const float *rays_o, const float *rays_
     // tracer falls back to direct atomics (emit_record), so this is a performance choice only
     const uint64_t job_rays = n_rays;
     rc = run_backward(h, P, 48, 6, [&](drt::Params &Q) {
-        if (!dbg(h->debug_flags, kHookWavefrontAdjoint) || dbg(h->debug_flags, kHookPerLanePrimal)) bind_path_cache_read(h, Q, job_rays);      // ... and every adjoint kernel but it
+        bind_path_cache_read(h, Q, job_rays);                    // ... and every adjoint kernel reads them
         return timed_launch(h, 1, Q, true);
     });
     h->pcache_sig.valid = false;
@@ -1952,6 +1901,15 @@ int drt_set_debug_flags(drt_handle h, uint32_t flags)
     if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
     if (!drt::kTestHooks && flags)
         return fail(h, DRT_ERR_UNSUPPORTED, "this is the production library: test hooks are compiled out (use libdrt_hip_hooks.so)");
+    // the bits that chose the per-lane Tracer, the state machine of whole flights and the round-3 supergrid kernel: those kernels are gone, and a
+    // script that still asks for them must not silently measure the production ones
+    static const struct { uint32_t bit; const char *name; } kRetired[] = {
+        { 1u << 3, "kHookPerLanePrimal" }, { 1u << 5, "kHookWavefrontAdjoint" }, { 1u << 15, "kHookPerLaneAdjoint" },
+        { 1u << 16, "kHookWavefrontPrimal" }, { 1u << 27, "kHookWavefrontSupergrid" } };
+    for (const auto &r : kRetired)
+        if (flags & r.bit)
+            return fail(h, DRT_ERR_INVALID_ARGUMENT, "debug flag %u (%s) selected one of the older tracer generations, which have been removed "
+                                                     "(debug flags 0x%x)", r.bit, r.name, flags);
     h->debug_flags = flags; h->scene_version++;
     return DRT_OK;
 }

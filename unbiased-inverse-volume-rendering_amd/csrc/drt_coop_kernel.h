@@ -20,7 +20,7 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
 {
     constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad;
     if constexpr (TAIL) { if (blockIdx.x * 256u >= *P.tail_count) return; }   // (workgroup-uniform) nothing for this workgroup
-    uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map (see trace_kernel)
+    uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map.  Workgroup b runs on XCD b % 8 (observed dispatch order, used for speed only); consecutive ray chunks are spatially coherent, so XCD k is given the k-th contiguous run of DRT_XCD_RUN workgroups of every group of 8 runs: its private 4 MiB L2 then serves one image region instead of every 8th 8-pixel strip (tail blocks keep the identity map)
     if (P.block_order) b = P.block_order[blockIdx.x];            // heavy blocks first (adjoint: this job's primal costs; primal: the previous launch's)
     else
 #if DRT_XCD_RUN > 0

@@ -24,7 +24,7 @@
 // utilisation 15 % -> 64 %, 8.4 G -> 6.1 G wave instructions (still VALU-issue-bound: the replay and the
 // round set-up are pure overhead), 13.9 -> 11.0 ms.
 //
-// Same algorithm and line references as Tracer in drt_kernels.hip (volpathsimple.py:38-655).
+// The algorithm and the line references are VolpathSimpleIntegrator's (volpathsimple.py:38-655).
 #pragma once
 #include "drt_device.h"
 #include "drt_launch.h"
@@ -211,7 +211,7 @@ struct CoopTracer {
     static constexpr bool kSolo = SPEC;
 
     // one free flight from o along d: distance to the tentative collision and the majorant it was sampled with
-    // (global majorant: bit-identical to sample_distance; supergrid: Tracer::sample_collision)
+    // (global majorant: bit-identical to sample_distance; supergrid: dda_collision, drt_device.h)
     __device__ __forceinline__ float flight(V3 o, V3 d, float tmax, float u, float &lm, float &lim) const
     {
         if constexpr (SUPER) return dda_collision(P, P.mgrid, mocc, o, d, tmax, u, lm, lim);

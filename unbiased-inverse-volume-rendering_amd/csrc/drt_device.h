@@ -39,20 +39,16 @@ __host__ __device__ __forceinline__ constexpr bool dbg(uint32_t flags, uint32_t 
 enum Hook : uint32_t {
     kHookNoGradAtomics      = 1u << 0,    // skip the gradient atomics (timing only)
     kHookPerLaneAtomics     = 1u << 1,    // per-lane (uncoalesced) gradient atomics, as the first kernels made them
-    kHookPerLanePrimal      = 1u << 3,    // the plain one-ray-per-lane Tracer (drt_kernels.hip) for primal launches; never the state machine
     kHookNoOccupancy        = 1u << 4,    // no empty-space bitmask
-    kHookWavefrontAdjoint   = 1u << 5,    // the state machine of whole flights (drt_wavefront.hip) for the adjoint too
     kHookUntileKeepScratch  = 1u << 6,    // untile pass without re-zeroing the apron scratch it reads (timing only)
     kHookAtomicGradients    = 1u << 7,    // gradient splats as atomics into the apron scratch + untile instead of deferred records
     kHookTinyRecordStreams  = 1u << 8,    // two-chunk record streams: exercises the out-of-chunks fallback
     kHookNerfRecordPath     = 1u << 9,    // the nerf adjoint of sensor rays through the record path instead of drt_nerf_tile.hip
     kHookReduceNoFlush      = 1u << 10,   // gradient reduction without the flush (timing only)
     kHookPipelineBatches    = 1u << 11,   // tracer of ray sub-batch b beside the reduction of sub-batch b - 1 on the side stream (measured slower)
-    kHookNoQueuedTracer     = 1u << 12,   // keep supergrid launches off the queued tracer: the round-3 kernel (drt_super.hip) or CoopTracer<SUPER>
+    kHookNoQueuedTracer     = 1u << 12,   // keep supergrid launches off the queued tracer: CoopTracer<SUPER> (drt_coop_super.hip), production's fallback, for every estimator
     kHookFewPartWGs         = 1u << 13,   // three partition workgroups (histogram, offsets, scatter) instead of kPartWGs: several batches per workgroup in small scenes
     kHookSmallRecordBudget  = 1u << 14,   // 8 MB record budget: many ray sub-batches
-    kHookPerLaneAdjoint     = 1u << 15,   // the plain one-ray-per-lane Tracer for adjoint launches
-    kHookWavefrontPrimal    = 1u << 16,   // the state machine of whole flights for primal launches
     kHookNoRecordMemory     = 1u << 18,   // pretend that the record streams cannot be allocated: the job takes the atomic path
     kHookNoRecordMemoryLater = 1u << 19,  // ... that they cannot be (re)allocated from the second ray sub-batch on
     kHookNoPathCache        = 1u << 20,   // no path cache: the adjoint pass walks its primal paths again
@@ -62,14 +58,10 @@ enum Hook : uint32_t {
     kHookPlainBlockMap      = 1u << 24,   // plain XCD block map: no heavy-blocks-first order
     kHookNoHandOff          = 1u << 25,   // no workgroup hand-off of sparse waves' paths, no tail pool (every wave runs its own paths to the end)
     kHookNoHandOffPrimal    = 1u << 26,   // ... in the primal pass only
-    kHookWavefrontSupergrid = 1u << 27,   // supergrid scenes in the older kernels: the state machine for the primal pass
     kHookNoTailOverlap      = 1u << 28,   // no early histogram pass beside the adjoint's tail launch; queued tracer: no tail pool of either kind
     kHookIndexOrder         = 1u << 29,   // the supergrid tracers take their rays in index order (production: thick pixels first)
     kHookScheduleSmall      = 1u << 30,   // small launches are scheduled like large ones (ray order, tail launches): the tests' scenes cover them
     kHookWalkEmptyPixels    = 1u << 31,   // the queued tracer walks every flight (production: pixels over empty supergrid cells end at set-up)
-    kHookPrimalNotCoop      = kHookPerLanePrimal | kHookWavefrontPrimal,   // primal launches the cooperative kernel does not serve: it alone fills block_cost
-    // any of the older tracer generations (per-lane Tracer, state machine): no supergrid kernels, no HG code
-    kHookOlderTracers       = kHookPerLanePrimal | kHookPerLaneAdjoint | kHookWavefrontPrimal | kHookWavefrontAdjoint | kHookWavefrontSupergrid,
 };
 
 // Experiment switches (timing / profiling builds made by tools/mk_variant.sh; several of them give WRONG results on purpose)
@@ -462,8 +454,8 @@ struct Params {
     uint4 *tail_pool;              // [tail_cap][8] uint4 or nullptr
     uint32_t *tail_count;          // entries written (zeroed before the main launch)
     uint32_t tail_cap, tail_mode;  // capacity in entries; 1 = this launch finishes the pool's paths
-    unsigned long long *queues;     // 8 per-XCD ray queue heads (wavefront kernel), zeroed per launch
-    // Ray order of the supergrid tracer (drt_super.hip, build_super_order): queue position g takes ray
+    unsigned long long *queues;     // 8 per-XCD ray queue heads (queued tracer), zeroed per launch
+    // Ray order of the queued supergrid tracer (drt_order.hip, build_super_order): queue position g takes ray
     // ray_first + order[g / order_unit] * order_unit + g % order_unit - units of consecutive rays, the expensive ones first, so
     // that the longest paths of a launch start at its beginning instead of running on alone at its end (a schedule
     // only: every ray's result is independent of when it is traced).  nullptr: rays in index order
@@ -816,13 +808,6 @@ __device__ __forceinline__ float emitter_sample_value_with_pdf(const Params &P, 
         for (int k = 0; k < 3; ++k) val[k] = p > 0.0f ? Le[k] / p : 0.0f;
         return p;
     } else return emitter_sample_value<ENV>(P, d, val);
-}
-
-template <bool ENV>
-__device__ __forceinline__ float emitter_pdf(const Params &P, V3 d)
-{
-    if constexpr (ENV) return envmap_pdf(P, d);
-    else return kInvFourPi;
 }
 
 // radiance towards an escaped ray AND the emitter's density of its direction (the escape side of the MIS weight, :273-284)

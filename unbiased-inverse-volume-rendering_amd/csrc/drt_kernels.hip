@@ -1,501 +1,13 @@
 // drt_kernels.hip -- gfx950 kernels around the tracer: the nerf integrator, box film, majorant / supergrid / empty-space
 // reductions, brick layouts, batch ray generation, gradient untiling, the primitive-evaluation kernel of the parity
-// tests - and, ONLY in the library flavour with test hooks (-DDRT_TEST_HOOKS), the plain one-ray-per-lane tracer `Tracer`
-// (v1 of VolpathSimpleIntegrator.sample, python/integrators/volpathsimple.py:38-290): the variant tests keep it in
-// lock-step with the production tracer (CoopTracer, drt_coop_tracer.h), the production library does not contain it.
+// tests.  The tracers themselves are CoopTracer (drt_coop_tracer.h) and the queued tracer (drt_sq_kernel.h).
 #include "drt_device.h"
 #include "drt_launch.h"
 #include "drt_coop_tracer.h"
 #include "drt_nerf_kernel.h"
 #include "drt_film.h"
 
-#ifndef DRT_TRACE_WAVES
-#define DRT_TRACE_WAVES 4      // waves per SIMD the tracing kernels are compiled for (VGPR <= 128)
-#endif
-#ifndef DRT_XCD_RUN
-#define DRT_XCD_RUN 256        // workgroups per XCD-contiguous run (0 = identity block map); swept 16..4096 on MI355X
-#endif
 namespace drt {
-
-struct Ray { V3 o, d; float maxt; };
-struct Mei { bool valid; float t; V3 p; float sigma_t; };
-struct PathState { int depth; Hit si; float last_pdf; bool escaped; bool active; };
-
-#ifdef DRT_TEST_HOOKS
-template <bool COUNT, bool ENV, bool DEFER = false>
-struct Tracer {
-    const Params &P;
-    float maj, inv_maj;
-    uint32_t ray_index;
-    uint32_t *rec;          // wave-private LDS: staging area of the cooperative scatter, or (DEFER) the record-stream state
-    const uint32_t *occ;    // empty-space bitmask (LDS copy) or nullptr
-    const float *mg;        // majorant supergrid as the DDA reads it (global memory, L2-resident; an LDS copy
-                            // was measured slower: it costs a wave per SIMD of occupancy)
-    uint4 *pc;              // this ray's path-cache entries (drt_device.h: Params::path_cache) or nullptr
-    const uint32_t *mocc;   // non-empty supergrid cells (LDS copy) or nullptr
-    uint32_t cnt[C_COUNT];
-
-    __device__ __forceinline__ Tracer(const Params &p) : P(p)
-    {
-        maj = p.majorant[0]; inv_maj = p.majorant[1];
-        ray_index = 0; rec = nullptr; mg = p.mgrid; occ = nullptr; pc = nullptr; mocc = nullptr;
-#pragma unroll
-        for (int i = 0; i < C_COUNT; ++i) cnt[i] = 0;
-    }
-    __device__ __forceinline__ void count(int slot) { if (COUNT) cnt[slot]++; }
-
-    // Medium::sample_interaction free-flight distance with a global majorant
-    // (call sites volpathsimple.py:348,469)
-    __device__ __forceinline__ float sample_distance(float u) const
-    {
-        if (maj == 0.0f) return kInf;
-        return -drt_logf(1.0f - u) * inv_maj;
-    }
-
-    // Medium::sample_interaction with a majorant supergrid (dda_collision, drt_device.h); without a supergrid:
-    // the global majorant (bit-identical to sample_distance).
-    __device__ __forceinline__ float sample_collision(V3 o, V3 d, float tmax, float u, float &m_out, float &im_out) const
-    {
-        if (!P.mgrid) { m_out = maj; im_out = inv_maj; return sample_distance(u); }
-        return dda_collision(P, mg, mocc, o, d, tmax, u, m_out, im_out);
-    }
-
-    // estimate_transmittance: ratio tracking (volpathsimple.py:436-504)
-    template <bool ADJ>
-    __device__ float estimate_transmittance(V3 o, V3 d, float tmax, Pcg32 &S, const float *adj, uint32_t *steps_out = nullptr)
-    {
-        float T = 1.0f;
-        uint32_t steps = 0;
-        for (;;) {
-            float lm, lim;
-            float dt = sample_collision(o, d, tmax, S.next_1d(), lm, lim);
-            if (!(dt <= tmax)) break;                                   // :480-481
-            V3 p = ray_at(o, d, dt);
-            float sig = eval_sigma_t(P, p, occ);
-            float tr = (lm - sig) * lim;                                // :473-476
-            count(C_RT);
-            if constexpr (ADJ) if (tr > 0.0f) {                         // :487-492
-                float a = (adj[0] + adj[1]) + adj[2];
-                splat_sigma_t<DEFER>(P, p, -(a * lim) / tr, rec);
-                count(C_RT_ADJ);
-            }
-            T *= tr;                                                    // :495
-            ++steps;
-            o = p; tmax -= dt;                                          // :497-499
-            if (T == 0.0f) break;                                       // :502
-        }
-        if (steps_out) *steps_out = steps;
-        return T;
-    }
-
-    // sample_emitter (volpathsimple.py:406-433): emitter_val * transmittance in out[], ds.pdf returned
-    template <bool ADJ>
-    __device__ float sample_emitter(V3 p, Pcg32 &S, const float *adj, float out[3], int cmode = 0, uint4 *ce = nullptr)
-    {
-        float ux = S.next_1d(), uy = S.next_1d();                       // :418
-        float val[3];
-        V3 wd = emitter_sample_dir<ENV>(P, ux, uy);                          // Scene::sample_emitter_direction
-        float pdf = emitter_sample_value<ENV>(P, wd, val);                   // ds.pdf, radiance / pdf
-        float T = 0.0f;
-        if (cmode == 2) {                                               // path cache: the primal pass walked this
-            const uint4 e = *ce;
-            T = __uint_as_float(e.x); S.state = ((uint64_t) e.z << 32) | e.y;
-            if (COUNT) cnt[C_RT] += e.w;
-        } else {
-            uint32_t steps = 0;
-            if (pdf != 0.0f) {                                          // sampling_worked :421-423
-                Hit si = box_hit(P, p, wd);                             // :427-428
-                if (si.valid) T = estimate_transmittance<ADJ>(p, wd, si.t, S, adj, &steps);
-            }
-            if (cmode == 1) *ce = make_uint4(__float_as_uint(T), (uint32_t) S.state, (uint32_t) (S.state >> 32), steps);
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) out[k] = val[k] * T;
-        return pdf;
-    }
-
-    // sample_emitter_for_nee (volpathsimple.py:380-403)
-    template <bool ADJ>
-    __device__ void sample_emitter_for_nee(V3 p, Pcg32 &S, const float beta[3], const float *dL,
-                                           float contrib[3], int cmode = 0, uint4 *ce = nullptr)
-    {
-        Pcg32 clone = S;                                                // :383
-        float emitted[3];
-        float ds_pdf = sample_emitter<false>(p, S, nullptr, emitted, cmode, ce);   // :385
-        float w = mis_weight(ds_pdf, kInvFourPi);                       // :391
-#pragma unroll
-        for (int k = 0; k < 3; ++k) contrib[k] = ((beta[k] * kInvFourPi) * w) * emitted[k];
-        if constexpr (ADJ) {                                            // :393-401
-            float adj[3] = { dL[0] * contrib[0], dL[1] * contrib[1], dL[2] * contrib[2] };
-            float unused[3];
-            (void) sample_emitter<true>(p, clone, adj, unused);
-        }
-    }
-
-    // sample_real_interaction: delta tracking (volpathsimple.py:323-377)
-    template <bool ATTACHED>
-    __device__ Mei sample_real_interaction(const Ray &ray, Pcg32 &S, int cmode = 0, uint4 *ce = nullptr)
-    {
-        Mei mei; mei.valid = false; mei.t = kInf; mei.p = v3(0, 0, 0); mei.sigma_t = 0.0f;
-        V3 ro = ray.o; float rmaxt = ray.maxt, running_t = 0.0f;
-        uint32_t steps = 0;
-        if (cmode == 2) {                                               // path cache: the primal pass walked this
-            const uint4 e = *ce;
-            mei.t = __uint_as_float(e.x); mei.valid = mei.t < kInf;
-            S.state = ((uint64_t) e.z << 32) | e.y;
-            if (COUNT) cnt[C_DT] += e.w;
-        } else
-        for (;;) {
-            float lm, lim;
-            float dt = sample_collision(ro, ray.d, rmaxt, S.next_1d(), lm, lim);   // :348
-            if (!(dt <= rmaxt)) break;                                  // :358
-            V3 p = ray_at(ro, ray.d, dt);
-            float sig = eval_sigma_t(P, p, occ);
-            count(C_DT); ++steps;
-            float r = sig * lim;                                        // :354
-            float u = S.next_1d();                                      // :359
-            if (!(u >= r)) { mei.valid = true; mei.t = running_t + dt; break; }   // :351
-            ro = p; rmaxt -= dt; running_t += dt;                       // :364-367
-        }
-        if (cmode == 1) *ce = make_uint4(__float_as_uint(mei.valid ? mei.t : kInf), (uint32_t) S.state, (uint32_t) (S.state >> 32), steps);
-        if (mei.valid) {
-            mei.p = ray_at(ray.o, ray.d, mei.t);                        // :371
-            if (ATTACHED) { mei.sigma_t = eval_sigma_t(P, mei.p, occ); count(C_DT); }   // :373-375
-        }
-        return mei;
-    }
-
-    // Medium::sample_interaction_drt (call site volpathsimple.py:549-551): ratio
-    // tracking over [0,maxt]; tentative collision i has weight T_i/majorant; one
-    // is kept by weighted reservoir sampling; W = sum of weights.
-    __device__ bool sample_interaction_drt(const Ray &ray, Pcg32 &A, float &t_out, float &W_out)
-    {
-        float t = 0.0f, T = 1.0f, wsum = 0.0f, tsel = kInf;
-        bool valid = false;
-        for (;;) {
-            float lm, lim;
-            if (P.mgrid) t += sample_collision(ray_at(ray.o, ray.d, t), ray.d, ray.maxt - t, A.next_1d(), lm, lim);
-            else { t += sample_distance(A.next_1d()); lm = maj; lim = inv_maj; }
-            if (!(t <= ray.maxt)) break;
-            float sig = eval_sigma_t(P, ray_at(ray.o, ray.d, t), occ);
-            count(C_DRT);
-            float w = T * lim;
-            wsum += w;
-            float u = A.next_1d();
-            if (w > 0.0f && u * wsum <= w) { tsel = t; valid = true; }
-            T *= (lm - sig) * lim;
-            if (T == 0.0f) break;
-        }
-        t_out = tsel; W_out = wsum;
-        return valid;
-    }
-
-    // sample_recursive (volpathsimple.py:610-655)
-    __device__ void sample_recursive(Pcg32 &A, V3 p, int depth, float Li[3])
-    {
-        Li[0] = Li[1] = Li[2] = 0.0f;
-        if (P.use_nee) {                                                // :621-624
-            const float one[3] = { 1.0f, 1.0f, 1.0f };
-            float nee[3];
-            sample_emitter_for_nee<false>(p, A, one, nullptr, nee);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) Li[k] += nee[k];
-        }
-        (void) A.next_1d();                                             // :632
-        float ux = A.next_1d(), uy = A.next_1d();
-        Ray rr; rr.o = p; rr.d = square_to_uniform_sphere(ux, uy);
-        Hit sn = box_hit(P, p, rr.d);                                   // :637
-        rr.maxt = sn.valid ? sn.t : kLargest;                           // :639-640
-        PathState ps;
-        ps.depth = depth + 1; ps.si = sn; ps.last_pdf = kInvFourPi; ps.escaped = false;
-        ps.active = (ps.depth < P.max_depth) && sn.valid;               // :647 (+ DESIGN.md deviation)
-        float Lr[3];
-        sample<false, true>(A, rr, nullptr, nullptr, &ps, Lr);          // :651
-#pragma unroll
-        for (int k = 0; k < 3; ++k) Li[k] += Lr[k];
-    }
-
-    // backpropagate_scattering_drt, final / quadratic branch (volpathsimple.py:543-581)
-    __device__ void drt_backprop(Pcg32 &A, const Ray &ray, float si_t, int depth, const float adj[3])
-    {
-        Ray sub = ray;
-        sub.maxt = isfinite(si_t) ? si_t : kLargest;                    // :544-545
-        float tp, W;
-        if (!sample_interaction_drt(sub, A, tp, W)) return;             // :550,558
-        V3 p = ray_at(sub.o, sub.d, tp);
-        float sig = eval_sigma_t(P, p, occ);                                 // :553-554
-        count(C_DRT);
-        float Li[3];
-        sample_recursive(A, p, depth, Li);                              // :565-568
-        float w = P.use_drt_mis ? 1.0f / (1.0f + sig * sig) : 1.0f;     // :571-575
-        float alb[3];
-        eval_albedo(P, p, alb);                                         // :578
-        count(C_ALB);
-        float ww = w * W;
-        float gs = 0.0f, ga[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float a = (ww * adj[k]) * Li[k];
-            gs += a * alb[k];
-            ga[k] = a * sig;
-        }
-        splat_scatter<DEFER>(P, p, gs, ga, rec); count(C_SC); count(C_SC_ALB);   // :577-581
-    }
-
-    // backpropagate_transmittance (volpathsimple.py:584-607)
-    __device__ void backprop_transmittance(Pcg32 &A, const Ray &ray, float interval,
-                                           const float dL[3], const float result[3])
-    {
-        float adjw = (dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2];
-        float g = -(adjw * (interval / 4.0f));
-        for (int j = 0; j < 4; ++j) {
-            float t = A.next_1d() * interval;                           // :595
-            splat_sigma_t<DEFER>(P, ray_at(ray.o, ray.d, t), g, rec);
-            count(C_TR);
-        }
-    }
-
-    // VolpathSimpleIntegrator.sample (volpathsimple.py:38-290)
-    template <bool ADJ, bool RECURSIVE>
-    __device__ void sample(Pcg32 &S, Ray ray, const float *dL, const float *state_in,
-                           const PathState *ps, float out[3])
-    {
-        float result[3] = { 0.0f, 0.0f, 0.0f };
-        float beta[3] = { 1.0f, 1.0f, 1.0f };
-        if (ADJ) { result[0] = state_in[0]; result[1] = state_in[1]; result[2] = state_in[2]; }
-
-        bool active, escaped; int depth; Hit si;
-        if (RECURSIVE) {                                                // :61-67
-            active = ps->active; depth = ps->depth; si = ps->si; escaped = ps->escaped;
-        } else {
-            active = true; depth = 0; escaped = false;
-            (void) S.next_1d();                                         // :71
-            si = box_hit(P, ray.o, ray.d);                              // reach_medium :292-319
-            if (!si.valid) { escaped = true; active = false; }
-            else {
-                ray.o = offset_p(si, ray.d);
-                Hit sn = box_hit(P, ray.o, ray.d);
-                if (!sn.valid) active = false;
-                else { ray.maxt = sn.t; si = sn; }
-            }
-        }
-        bool has_scattered = RECURSIVE ? (active && !escaped) : false;  // :84-89
-        float last_pdf = RECURSIVE ? ps->last_pdf : 1.0f;
-
-        // DRTReservoir(n=1) + DRTPathState (:94-96, :710-765)
-        int r_depth = -1; float r_si_t = kInf; Ray r_ray = ray;
-        float r_wsum[3] = { 0, 0, 0 }, r_cw[3] = { 0, 0, 0 };
-
-        Pcg32 A; A.state = 0; A.inc = 1;
-        if (active) (void) S.next_1d();                                 // :99
-        if constexpr (ADJ) A.seed(P.alt_seed, ray_index);               // :100-107
-
-        int it = 0;                                                     // bounce-loop iterations that reached their walk
-        while (active) {                                                // :114
-            float q = fminf(fmaxf(beta[0], fmaxf(beta[1], beta[2])), 0.99f);   // :117-121
-            bool perform_rr = depth > P.rr_depth;
-            float u_rr = S.next_1d();
-            active = (beta[0] != 0.0f || beta[1] != 0.0f || beta[2] != 0.0f)
-                     && (!perform_rr || (u_rr < q));
-            if (perform_rr) { float iq = 1.0f / q; beta[0] *= iq; beta[1] *= iq; beta[2] *= iq; }
-            if (!active) break;
-
-            const int cmode = (!RECURSIVE && pc && it < (int) P.path_cache_cap) ? (int) P.path_cache_mode : 0;
-            uint4 *ce = cmode ? pc + 2 * it : nullptr;
-            ++it;
-            Mei mei = sample_real_interaction<ADJ>(ray, S, cmode, ce);  // :126
-            bool did_escape = !mei.valid, did_scatter = mei.valid;      // :130-134
-            has_scattered |= did_scatter;
-
-            float albedo[3] = { 1.0f, 1.0f, 1.0f };                     // :141
-            if (did_scatter) { eval_albedo(P, mei.p, albedo); count(C_ALB); }
-
-            if constexpr (ADJ) {
-                if (P.use_drt) {                                        // :143-150
-                    if (P.use_drt_subsampling) {                        // :521-539, :745-753
-                        float u = A.next_1d();
-                        float m = 0.0f;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) { r_wsum[k] += beta[k]; m += beta[k] / r_wsum[k]; }
-                        m = m / 3.0f;
-                        if (u <= m) {
-                            r_cw[0] = beta[0]; r_cw[1] = beta[1]; r_cw[2] = beta[2];
-                            r_depth = depth; r_si_t = si.t; r_ray = ray;
-                        }
-                    } else {
-                        float adj[3] = { dL[0] * beta[0], dL[1] * beta[1], dL[2] * beta[2] };
-                        drt_backprop(A, ray, si.t, depth, adj);
-                    }
-                }
-                if ((!P.use_drt || P.use_drt_mis) && did_scatter) {     // :152-172
-                    float w = 1.0f;
-                    if (P.use_drt && P.use_drt_mis) {
-                        float s2 = mei.sigma_t * mei.sigma_t;
-                        w = s2 / (1.0f + s2);
-                    }
-                    float inv_pdf = 1.0f / mei.sigma_t;
-                    float gs = 0.0f, ga[3];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        float Li = result[k] / fmaxf(1e-8f, albedo[k]); // :167
-                        float a = ((w * dL[k]) * Li) * inv_pdf;
-                        gs += a * albedo[k];
-                        ga[k] = a * mei.sigma_t;
-                    }
-                    splat_scatter<DEFER>(P, mei.p, gs, ga, rec); count(C_SC); count(C_SC_ALB);
-                }
-                backprop_transmittance(A, ray, did_escape ? si.t : mei.t, dL, result);   // :181-189
-            }
-
-            beta[0] *= albedo[0]; beta[1] *= albedo[1]; beta[2] *= albedo[2];           // :193
-            if (did_scatter) depth += 1;                                // :199
-            active = did_scatter && (depth < P.max_depth);              // :200
-
-            if (P.use_nee && did_scatter && active) {                   // :206-215
-                float nee[3];
-                sample_emitter_for_nee<ADJ>(mei.p, S, beta, dL, nee, cmode, ce ? ce + 1 : nullptr);
-#pragma unroll
-                for (int k = 0; k < 3; ++k) result[k] = ADJ ? result[k] - nee[k] : result[k] + nee[k];
-            }
-
-            if (did_scatter) {                                          // :221-230
-                (void) S.next_1d();
-                float ux = S.next_1d(), uy = S.next_1d();
-                ray.o = mei.p; ray.d = square_to_uniform_sphere(ux, uy); ray.maxt = kLargest;
-                last_pdf = kInvFourPi;
-            }
-            si = box_hit(P, ray.o, ray.d);                              // :233-235
-            ray.maxt = isfinite(si.t) ? si.t : kLargest;
-            if (did_scatter && !si.valid) active = false;               // :240-241
-            if (did_escape) {                                           // :244-245
-                if (si.valid) ray.o = offset_p(si, ray.d);
-                escaped = true;
-            }
-        }
-
-        if constexpr (ADJ) {
-            if (P.use_drt && P.use_drt_subsampling && r_depth >= 0) {   // :249-259, :756-760
-                float d = ((r_cw[0] + r_cw[1]) + r_cw[2]) / 3.0f;
-                float ws = ((r_wsum[0] + r_wsum[1]) + r_wsum[2]) / 3.0f;
-                float adj[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) adj[k] = (d != 0.0f ? (ws * r_cw[k]) / d : 0.0f) * dL[k];
-                drt_backprop(A, r_ray, r_si_t, r_depth, adj);
-            }
-        } else {                                                        // :263-287
-            if (escaped && !(depth <= 0 && P.hide_emitters)) {
-                float w = 1.0f, Le[3];
-                if (P.use_nee) {
-                    float epdf = 0.0f;                                  // :273-277
-                    if (has_scattered) epdf = emitter_pdf<ENV>(P, ray.d);
-                    w = mis_weight(last_pdf, epdf);
-                }
-                emitter_eval<ENV>(P, ray.d, Le);                        // :284
-#pragma unroll
-                for (int k = 0; k < 3; ++k) result[k] += (beta[k] * w) * Le[k];
-            }
-        }
-        out[0] = result[0]; out[1] = result[1]; out[2] = result[2];
-    }
-};
-
-template <bool ADJ, bool COUNT, bool ENV, bool DEFER>
-__global__ void __launch_bounds__(256, DRT_TRACE_WAVES) trace_kernel(const Params P)
-{
-    // XCD-aware block -> ray-chunk map.  Workgroup b runs on XCD b % 8 (observed dispatch
-    // order, used for speed only); consecutive ray chunks are spatially coherent, so XCD k is
-    // given the k-th contiguous run of DRT_XCD_RUN workgroups of every group of 8 runs: its
-    // private 4 MiB L2 then serves one image region instead of every 8th 8-pixel strip.
-    uint32_t b = blockIdx.x;
-#if DRT_XCD_RUN > 0
-    {
-        const uint32_t span = 8u * DRT_XCD_RUN;
-        const uint32_t full = (gridDim.x / span) * span;     // tail blocks keep the identity map
-        if (b < full) {
-            uint32_t grp = b / span, r = b % span;
-            b = grp * span + (r % 8u) * DRT_XCD_RUN + r / 8u;
-        }
-    }
-#endif
-    const uint64_t i_block = P.ray_first + (uint64_t) b * blockDim.x;
-    uint64_t i = i_block + threadIdx.x;
-    if constexpr (ADJ) {                                        // rays of similar length share a wave (ray_perm_kernel, drt_coop.hip)
-        if (P.ray_perm) i = (i_block & ~(uint64_t) (kPermGroup - 1)) + P.ray_perm[i_block + threadIdx.x];
-    }
-    Tracer<COUNT, ENV, DEFER> tr(P);
-    if constexpr (ADJ && DEFER) {
-        __shared__ uint32_t rec_state[4 * 8];                   // per wave: cur[4], end[4]
-        tr.rec = rec_state + (threadIdx.x >> 6) * 8;
-        if ((threadIdx.x & 63) < 8) tr.rec[threadIdx.x & 63] = 0;
-        coop_stage_sync();
-    } else if constexpr (ADJ) {
-        __shared__ uint32_t coop_rec[4 * 64 * kCoopDwords];
-        tr.rec = coop_rec + (threadIdx.x >> 6) * (64 * kCoopDwords);
-    }
-    // empty-space bitmask -> LDS (4 KiB): most lookups of a sparse volume never leave the CU
-    __shared__ uint32_t occ_lds[kOccWords];
-    if (P.occ && !dbg(P.debug_flags, kHookNoOccupancy)) {
-        for (int w = threadIdx.x; w < P.occ_words; w += blockDim.x) occ_lds[w] = P.occ[w];
-        __syncthreads();
-        tr.occ = occ_lds;
-    }
-    __shared__ uint32_t mocc_lds[kOccWords];
-    if (P.mgrid && P.mocc && P.mocc_words <= kOccWords && !dbg(P.debug_flags, kHookNoSupergridMask)) {
-        for (int w = threadIdx.x; w < P.mocc_words; w += blockDim.x) mocc_lds[w] = P.mocc[w];
-        __syncthreads();
-        tr.mocc = mocc_lds;
-    }
-    if (i < P.n_rays) {
-        uint64_t g64 = P.chunk ? P.ray_offset + (i / P.chunk) * P.stride + (i % P.chunk) : P.ray_offset + i;
-        uint32_t gi = (uint32_t) g64;
-        tr.ray_index = gi;
-        Pcg32 S; S.seed(P.seed, gi);
-        Ray ray;
-        if (P.sensor_flow) {
-            float ux = S.next_1d(), uy = S.next_1d();
-            sensor_ray(P, gi / P.spp, ux, uy, ray.o, ray.d);
-        } else {
-            ray.o = v3(P.rays_o[3 * i], P.rays_o[3 * i + 1], P.rays_o[3 * i + 2]);
-            ray.d = v3(P.rays_d[3 * i], P.rays_d[3 * i + 1], P.rays_d[3 * i + 2]);
-        }
-        ray.maxt = kLargest;
-        tr.count(C_RAYS);
-        if (P.path_cache_mode) {                                        // see trace_coop_kernel
-            uint32_t hsh = 0x9e3779b9u ^ gi;
-            if (!P.sensor_flow) {
-                const uint32_t w[6] = { __float_as_uint(ray.o.x), __float_as_uint(ray.o.y), __float_as_uint(ray.o.z),
-                                        __float_as_uint(ray.d.x), __float_as_uint(ray.d.y), __float_as_uint(ray.d.z) };
-#pragma unroll
-                for (int k = 0; k < 6; ++k) hsh = (hsh ^ w[k]) * 0x01000193u + (hsh >> 15);
-            }
-            if (P.path_cache_mode == 1) { P.ray_hash[i] = hsh; tr.pc = P.path_cache + (size_t) i * P.path_cache_cap * 2; }
-            else if (P.ray_hash[i] == hsh) tr.pc = P.path_cache + (size_t) i * P.path_cache_cap * 2;
-        }
-        float L[3];
-        if (ADJ) {
-            float dL[3];
-            load_dL(P, i, dL);
-            float Lin[3] = { P.L_in[3 * i], P.L_in[3 * i + 1], P.L_in[3 * i + 2] };
-            tr.template sample<true, false>(S, ray, dL, Lin, nullptr, L);
-        } else {
-            tr.template sample<false, false>(S, ray, nullptr, nullptr, nullptr, L);
-            P.L_out[3 * i] = L[0]; P.L_out[3 * i + 1] = L[1]; P.L_out[3 * i + 2] = L[2];
-        }
-    }
-    if constexpr (ADJ && DEFER) close_records(P, tr.rec);
-    if (COUNT) {
-        // wave reduction, then one device atomic per wave and slot
-#pragma unroll
-        for (int s = 0; s < C_COUNT; ++s) {
-            uint32_t v = tr.cnt[s];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-            if ((threadIdx.x & 63) == 0 && v) atomicAdd(P.counters + s, (unsigned long long) v);
-        }
-    }
-}
-
-#endif  // DRT_TEST_HOOKS (Tracer, trace_kernel)
 
 // majorant = scale * max(sigma_t grid) (Medium::get_majorant with a global
 // majorant; carries no gradient, refreshed on parameter update - optimize.py:195-199)
@@ -542,7 +54,7 @@ __global__ void __launch_bounds__(256) majorant_grid_kernel(const float *sigma_t
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
     if (lane == 0) {
         // rounded UP to the next bf16-representable value (a majorant only has to bound; at most 0.8 % looser): the
-        // supergrid tracer keeps the cells as 16-bit values in LDS (drt_super.hip) - as oracle/drt_oracle.c scene_init
+        // queued tracer keeps the cells as 16-bit values in LDS (drt_sq_kernel.h) - as oracle/drt_oracle.c scene_init
         if (max_bits && __float_as_uint(m) > *(volatile uint32_t *) max_bits) atomicMax(max_bits, __float_as_uint(m));   // (few cells get past the read)
         uint32_t b = __float_as_uint(m * scale);
         if (b & 0xffffu) b = (b | 0xffffu) + 1u;
@@ -932,34 +444,6 @@ hipError_t launch_debug_eval(const Params &P, int op, const float *in, uint64_t 
 // ---------------------------------------------------------------------------
 // launch wrappers (host)
 // ---------------------------------------------------------------------------
-#ifdef DRT_TEST_HOOKS
-hipError_t launch_trace(const Params &P, bool adjoint, bool count, hipStream_t stream)
-{
-    if (P.n_rays <= P.ray_first) return hipSuccess;
-    dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
-    const int variant = (adjoint ? 4 : 0) | (count ? 2 : 0) | (P.env_pix ? 1 : 0);
-    const bool defer = adjoint && P.rec_buf[0] != nullptr;
-    switch (variant) {
-        case 0: hipLaunchKernelGGL((trace_kernel<false, false, false, false>), grid, block, 0, stream, P); break;
-        case 1: hipLaunchKernelGGL((trace_kernel<false, false, true, false>), grid, block, 0, stream, P); break;
-        case 2: hipLaunchKernelGGL((trace_kernel<false, true, false, false>), grid, block, 0, stream, P); break;
-        case 3: hipLaunchKernelGGL((trace_kernel<false, true, true, false>), grid, block, 0, stream, P); break;
-        case 4: if (defer) hipLaunchKernelGGL((trace_kernel<true, false, false, true>), grid, block, 0, stream, P);
-                else hipLaunchKernelGGL((trace_kernel<true, false, false, false>), grid, block, 0, stream, P);
-                break;
-        case 5: if (defer) hipLaunchKernelGGL((trace_kernel<true, false, true, true>), grid, block, 0, stream, P);
-                else hipLaunchKernelGGL((trace_kernel<true, false, true, false>), grid, block, 0, stream, P);
-                break;
-        case 6: if (defer) hipLaunchKernelGGL((trace_kernel<true, true, false, true>), grid, block, 0, stream, P);
-                else hipLaunchKernelGGL((trace_kernel<true, true, false, false>), grid, block, 0, stream, P);
-                break;
-        default: if (defer) hipLaunchKernelGGL((trace_kernel<true, true, true, true>), grid, block, 0, stream, P);
-                 else hipLaunchKernelGGL((trace_kernel<true, true, true, false>), grid, block, 0, stream, P);
-                 break;
-    }
-    return hipGetLastError();
-}
-#endif  // DRT_TEST_HOOKS
 
 // bit c of `dil`: supergrid cell c or one of its 26 neighbours has a non-zero majorant (Params::mocc_dil: the per-pixel emptiness proof of
 // build_unit_empty tests ONE bit per sample of the pixel's centre ray).  One thread per word of 32 cells.

@@ -7,7 +7,6 @@
 
 namespace drt {
 
-hipError_t launch_trace(const Params &P, bool adjoint, bool count, hipStream_t stream);
 hipError_t launch_majorant_grid(const float *sigma_t, int rx, int ry, int rz, int gx, int gy, int gz, float scale,
                                 float *out, uint32_t *mask, hipStream_t stream, uint32_t *max_bits = nullptr, float *majorant = nullptr,
                                 uint32_t *mask_dil = nullptr);
@@ -58,14 +57,9 @@ hipError_t launch_nerf_aov_tile_adjoint(const Params &P, bool g4, uint32_t *boun
 // box film with `channels` interleaved floats per sample: one thread per (pixel, channel), samples summed in index order / dL = grad / spp
 hipError_t launch_film_develop_n(const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image, hipStream_t stream);
 hipError_t launch_film_backward_n(const float *grad_image, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *dL, hipStream_t stream);
-hipError_t launch_trace_wavefront(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
-// supergrid scenes (majorant_resolution_factor > 0): lane-level state machine stepping one supergrid cell at a time, the
-// majorant grid in LDS (drt_super.hip); the adjoint needs the record streams (deferred splatting)
-bool super_supported(const Params &P);
-hipError_t launch_trace_super(const Params &P, bool adjoint, bool count, int n_cus, hipStream_t stream);
-// the same scenes as work queues inside a compute unit: rays live in LDS records and belong to no lane, waves take batches of
-// one kind of work (drt_sq_kernel.h; round 4).  Uses the ray order and the XCD queues of launch_trace_super; the adjoint needs
-// Params::sq_cold (sq_cold_bytes(n_cus) bytes).  The kernels of a phase are one unit each (SqUnit: drt_sq.hip isotropic, drt_sq_hg.hip kHG and
+// supergrid scenes (majorant_resolution_factor > 0) as work queues inside a compute unit: rays live in LDS records and belong to no lane, waves
+// take batches of one kind of work (drt_sq_kernel.h; round 4).  Uses the ray order (build_super_order) and the XCD queues (Params::queues); the
+// adjoint needs the record streams (deferred splatting) and Params::sq_cold (sq_cold_bytes(n_cus) bytes).  The kernels of a phase are one unit each (SqUnit: drt_sq.hip isotropic, drt_sq_hg.hip kHG and
 // kHGGrad, drt_sq_hg2.hip kHG2, drt_sq_tab.hip kTab).  kHG, kHGGrad, kHG2, kTab: no tail launch (Params::tail_pool / tail_mode must be unset).  kHGGrad: adjoint launches
 // only, `count` is ignored (no counting kernels: such a launch counts nothing); dLoss/dg is added to *Params::L_out, one atomic per wave
 bool sq_supported(const Params &P);
@@ -79,7 +73,7 @@ template <Phase PH> struct SqUnit {
 uint32_t sq_tail_push();
 bool sq_tail_solo(const Params &P);       // the tail launch finishes its records in registers, no queue hops (supergrids whose majorants fit LDS)
 size_t sq_tail_entry_quads();
-// Ray order for launch_trace_super / launch_trace_sq (Params::order): units of `unit` consecutive rays of [P.ray_first, P.n_rays) sorted by a
+// Ray order for launch_trace_sq (Params::order; drt_order.hip): units of `unit` consecutive rays of [P.ray_first, P.n_rays) sorted by a
 // cost key - the majorant optical depth along the unit's first ray through the supergrid -, most expensive first.
 // work: super_order_bytes(units) bytes; the permutation is the first `units` words of it.
 size_t super_order_bytes(uint32_t units);

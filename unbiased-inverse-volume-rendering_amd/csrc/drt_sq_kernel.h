@@ -2,7 +2,7 @@
 // python/scene_config.py:36, optimize.py:182-199), round 4: VolpathSimpleIntegrator.sample
 // (python/integrators/volpathsimple.py:38-655), both AD modes, as WORK QUEUES INSIDE A COMPUTE UNIT.
 //
-// Why (measured): the round-3 tracer (drt_super.hip) keeps every ray in the registers of the lane that
+// Why (measured): the round-3 tracer (retired) kept every ray in the registers of the lane that
 // owns it.  Flights travel to whichever wave walks them, but everything else of a ray - the collision a flight ended in,
 // the next flight's set-up, the path transitions, the ray prologue - can only run on the owner lane, so those blocks run
 // when "enough" of a wave's 64 lanes happen to be ready: 23-28 of 64 in the collision / set-up blocks, fewer in the
@@ -18,7 +18,7 @@
 // from a delta-tracking / DRT walk, rays that come from a transmittance walk; only the adjoint kernels use both), free
 // records - say what is to be done; a wave takes up to 64 ids of ONE kind, loads those rays, runs that kind's code with all
 // its lanes, stores them and pushes their ids to the queues of what they need next (one reserving LDS atomic for all kinds).
-// A wave that finds no full batch walks flights (as in drt_super.hip: DRT_SQ_K cells per look, lanes refilled from the
+// A wave that finds no full batch walks flights (DRT_SQ_K cells per look, lanes refilled from the
 // flight queue); the lanes that set a flight up step its first DRT_SQ_INLINE_K cells themselves.  A transition batch runs a
 // second pass only for >= DRT_SQ_T_PASS rays (the others are re-queued: a pass for a few lanes costs as much as one for 64),
 // and the adjoint kernels run the "NEE walk finished" block twice per pass so that a main path whose walks come out of the
@@ -27,7 +27,7 @@
 //
 // Arithmetic, random-number consumption and event counts are those of the scalar restatement (oracle/drt_oracle.c):
 // radiance is bit-exact per ray, counters are equal; gradients differ by summation order only.  A ray computes the same
-// numbers whichever lanes run its pieces.  Not handled here (the host keeps drt_super.hip / the one-ray-per-lane kernels):
+// numbers whichever lanes run its pieces.  Not handled here (the host keeps CoopTracer<SUPER>, drt_coop_super.hip):
 // supergrids of more than 511 cells per axis or whose cell bitmask does not fit LDS either, the atomic gradient path.  Quadratic DRT
 // (the paper's comparison estimator) runs in the QUAD instantiations of the adjoint kernels: the main path is suspended at every
 // vertex for the DRT walk + recursive path the subsampled estimator runs once at the end of a path.  Design history, profiles and what was measured and not kept: DESIGN.md section 6.2, profiles/r04_sq_experiments.txt.
@@ -51,7 +51,7 @@
 #define DRT_SQ_RING 1024           // entries per ring buffer of ids (a power of two >= DRT_SQ_MAX_RAYS)
 #endif
 #ifndef DRT_SQ_MIN_RAYS
-#define DRT_SQ_MIN_RAYS 256        // fewer records than this: the host keeps drt_super.hip
+#define DRT_SQ_MIN_RAYS 256        // fewer records than this: the host keeps CoopTracer<SUPER>
 #endif
 #ifndef DRT_SQ_K
 #define DRT_SQ_K 8                 // cells per walker lane between two looks at the queues
@@ -358,7 +358,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
     }
     __syncthreads();
     // A flight whose target optical depth exceeds (largest majorant) x (length of its segment) cannot end in a collision
-    // whatever cells it crosses: it is not walked (flight set-up below; the bound is drt_super.hip's).
+    // whatever cells it crosses: it is not walked (flight set-up below).
     const float mmax = __uint_as_float(__builtin_amdgcn_readfirstlane((int) misc[1]));
     const uint32_t *occ = nullptr;   // (tentative collisions lie in non-empty supergrid cells: the voxel bitmask would rarely say "empty")
     // (DRT_SQ_REGEN_FINISH) "thin": a flight across the whole box has a fair chance (> e^-3) of an optical-depth target beyond that bound - only then
@@ -538,7 +538,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                 if (!__ballot(fly)) break;                                       // nothing to walk (any more)
                 walked = true;
                 SQ_STAMP(1);
-                // (primal kernels: the steps are not predicated on `fly`, as in drt_super.hip)
+                // (primal kernels: the steps are not predicated on `fly`)
                 constexpr bool kLoose = !ADJ || MG;
                 bool fin = false; float res_mc = 0.0f, res_t = 0.0f, res_acc = 0.0f;
 #pragma unroll
@@ -1671,7 +1671,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
 }
 
 // Records per workgroup that fit LDS next to this supergrid's majorants (a multiple of 64); 0: this supergrid cannot be
-// served (the host keeps drt_super.hip).  *bytes: dynamic LDS of the launch
+// served (the host keeps CoopTracer<SUPER>).  *bytes: dynamic LDS of the launch
 // *global_majorants: the bf16 majorants do not fit (with at least DRT_SQ_MIN_RAYS records) but one bit per cell does - the MG kernels
 static uint32_t sq_rays_for(const Params &P, size_t *bytes, bool *global_majorants = nullptr)
 {
