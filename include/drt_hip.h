@@ -294,6 +294,30 @@ int drt_nerf_render_forward_aov(drt_handle h, const drt_nerf_config *cfg, const 
                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
                                 const float *t_emission, float *dL_out);
 
+/* ... and with a third output that depends on sigma_t only, the distortion regulariser of mip-NeRF 360 in its O(N) form:
+ *     Z = sum_i sum_j w_i w_j |tau_i - tau_j| + (1/3) sum_i w_i^2 dt_i     over the non-last queries; w_j = weight_j, tau_j = t_in + t_b,j,
+ * dt_j the step of query j; world units of length, like D.  A ray that misses the box has Z = 0.  Every ray / pixel buffer of these calls
+ * holds SIX interleaved floats [r, g, b, A, D, Z]; channels 0 - 4 are the bits of the _aov calls.  Primal, per non-last query, with W and Dp
+ * the opacity and depth sums before the query is added, every operation rounded to fp32:
+ *     Z += w_j * (2 * (tau_j * W - Dp) + (w_j * dt_j) / 3)
+ * The backward calls read opacity, depth and distortion of the primal from L_in (channels 3 - 5) and add dZ's share to grad_sigma_t only.
+ * The four calls mirror the _aov calls in everything else: conventions, routes (sensor rays: the LDS-window kernel; explicit ray batches:
+ * the record route; csrc/drt_nerf_dist.hip), the NaN marking for non-finite dL / L_in, and the refusals - NULL buffers
+ * (DRT_ERR_INVALID_ARGUMENT); own-lattice colour grids and, adjoint calls, the debug flags 1, 2, 128, 512 (DRT_ERR_UNSUPPORTED).  There is
+ * no SH, fused or loss-fused variant.  The counters of drt_get_counters do not count these calls. */
+int drt_nerf_render_primal_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out);
+int drt_nerf_render_backward_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                  uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
+                                  float *grad_sigma_t, float *grad_emission);
+int drt_nerf_render_backward_px_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                                     const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                     const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
+                                     float *grad_emission);
+int drt_nerf_render_forward_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
+                                 const float *t_emission, float *dL_out);
+
 /* BASELINE config 5: the `nerf` march and volpathsimple scattering over ONE set of grids [sigma_t, r, g, b] in one call.
  * The reference's scenes bind ONE asset as the medium's albedo and emission grid (python/scene_config.py:109-110), so the
  * colour grid given to drt_set_medium as `albedo` is both.  Per ray, the pass computes NeRFIntegrator.sample (nerf.py:47-148;

@@ -97,7 +97,7 @@ def render_batch(batch_size: int, scene: Scene, sensors=None, film_size=None,
                  pixel_format=None, sampler=None, seed: int = 0, seed_grad: int = 0, spp: int = 0,
                  spp_grad: int = 0, sensor_table: Optional[torch.Tensor] = None, shard: Optional[ShardSpec] = None):
     """Batched (ray-centric) alternative to `render` (python/batched.py:88-131).
-    -> (image [batch_size, 3] ([batch_size, 5] with a `nerf` integrator's `aovs`), film, sampler, sensor_idx [batch_size], pixel_idx [batch_size, 2])
+    -> (image [batch_size, 3] ([batch_size, 5] with a `nerf` integrator's `aovs`, 6 with `distortion`), film, sampler, sensor_idx [batch_size], pixel_idx [batch_size, 2])
     (`film` / `sampler` are returned as given: the device film is stateless here).
     `shard` (world > 1): the outputs hold this rank's entries `shard.batch_range(batch_size)` only and the
     backward pass all-reduces the gradient grids; scale the local loss by `local_loss_scale`.

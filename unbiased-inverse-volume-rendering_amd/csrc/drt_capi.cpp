@@ -2201,18 +2201,21 @@ int drt_nerf_render_forward_sh(drt_handle h, const drt_nerf_config *cfg, const f
     });
 }
 
-// ---- opacity and depth outputs: five interleaved floats [r, g, b, A, D] per ray / pixel ------------------------------------------------------
-int drt_nerf_render_primal_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
-                               uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
+// ---- opacity and depth outputs: five interleaved floats [r, g, b, A, D] per ray / pixel; with the distortion output (drt_nerf_dist.hip) six,
+// [.., Z].  The eight calls are four bodies: `dist` picks the unit whose kernels run, `what` is the call's name in its messages ----------------
+static constexpr NerfVariant kNerfDist = { "emission", "own-lattice opacity / depth / distortion outputs are not supported", "distortion" };
+
+static int nerf_aov_primal(drt_handle h, const char *what, bool dist, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                           const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
 {
-    return nerf_variant_call(h, "drt_nerf_render_primal_aov", kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
+    return nerf_variant_call(h, what, dist ? kNerfDist : kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
                              [&](drt::Params &P, const drt::NerfSh &) {
-        if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_primal_aov: null L_out");
+        if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null L_out", what);
         P.L_out = L_out;
         h->pcache_sig.valid = false;
         TimedSpan span;
         DRT_HIP_CHECK(h, span.begin(h, h->stream));
-        DRT_HIP_CHECK(h, drt::launch_nerf_aov(P, false, h->stream));
+        DRT_HIP_CHECK(h, dist ? drt::launch_nerf_dist(P, false, h->stream) : drt::launch_nerf_aov(P, false, h->stream));
         DRT_HIP_CHECK(h, span.end(0));
         return (int) DRT_OK;
     });
@@ -2220,8 +2223,8 @@ int drt_nerf_render_primal_aov(drt_handle h, const drt_nerf_config *cfg, const f
 
 // the adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given.  Sensor rays: the LDS-window kernel (lookups
 // from the four-channel copy where it can be made, as the plain call); explicit ray batches: the record path, as the plain call
-static int nerf_aov_backward(drt_handle h, drt::Params &P, const float *emission, const float *dL, const float *dL_pix, const float *L_in,
-                             float *grad_sigma_t, float *grad_emission)
+static int nerf_aov_backward(drt_handle h, bool dist, drt::Params &P, const float *emission, const float *dL, const float *dL_pix,
+                             const float *L_in, float *grad_sigma_t, float *grad_emission)
 {
     P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_emission;
     const bool tile = drt::nerf_tile_supported(P);
@@ -2236,28 +2239,71 @@ static int nerf_aov_backward(drt_handle h, drt::Params &P, const float *emission
             c2 += c * c; d2 += e * e;
         }
         const float t_max = (float) ((std::sqrt(c2) + std::sqrt(d2)) * 1.01);
-        return nerf_adjoint_pass(h, h->stream, 64, [&](uint32_t *bounds) { return drt::launch_nerf_aov_tile_adjoint(P, g4, bounds, t_max, h->stream); });
+        return nerf_adjoint_pass(h, h->stream, 64, [&](uint32_t *bounds) {       // (64 bytes: 12 words, 14 with the distortion output)
+            return dist ? drt::launch_nerf_dist_tile_adjoint(P, g4, bounds, t_max, h->stream)
+                        : drt::launch_nerf_aov_tile_adjoint(P, g4, bounds, t_max, h->stream);
+        });
     }
     const uint32_t q = (uint32_t) P.nerf_queries;                 // at most one splat per query and plane
     return run_backward(h, P, q, q, [&](drt::Params &Q) {
         TimedSpan span;
         DRT_HIP_CHECK(h, span.begin(h, h->stream));
-        DRT_HIP_CHECK(h, drt::launch_nerf_aov(Q, true, h->stream));
+        DRT_HIP_CHECK(h, dist ? drt::launch_nerf_dist(Q, true, h->stream) : drt::launch_nerf_aov(Q, true, h->stream));
         DRT_HIP_CHECK(h, span.end(1));
         return (int) DRT_OK;
     });
+}
+
+static int nerf_aov_backward_ray(drt_handle h, const char *what, bool dist, const drt_nerf_config *cfg, const float *emission,
+                                 const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                 const float *dL, const float *L_in, float *grad_sigma_t, float *grad_emission)
+{
+    return nerf_variant_call(h, what, dist ? kNerfDist : kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
+                             [&](drt::Params &P, const drt::NerfSh &) {
+        if (!dL || !L_in || !grad_sigma_t || !grad_emission)
+            return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null dL / L_in / gradient buffer", what);
+        return nerf_aov_backward(h, dist, P, emission, dL, nullptr, L_in, grad_sigma_t, grad_emission);
+    });
+}
+
+static int nerf_aov_backward_px(drt_handle h, const char *what, bool dist, const drt_nerf_config *cfg, const float *emission,
+                                const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t, float *grad_emission)
+{
+    return nerf_variant_call(h, what, dist ? kNerfDist : kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
+                             [&](drt::Params &P, const drt::NerfSh &) {
+        if (!L_in || !grad_sigma_t || !grad_emission)
+            return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null L_in / gradient buffer", what);
+        DRT_TRY(check_px(h, what, n_rays, spp, grad_image, n_pixels));
+        return nerf_aov_backward(h, dist, P, emission, nullptr, grad_image, L_in, grad_sigma_t, grad_emission);
+    });
+}
+
+static int nerf_aov_forward(drt_handle h, const char *what, bool dist, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                            const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
+                            const float *t_emission, float *dL_out)
+{
+    return nerf_variant_call(h, what, dist ? kNerfDist : kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
+                             [&](drt::Params &P, const drt::NerfSh &) {
+        if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null dL_out", what);
+        forward_params(P, t_sigma_t, t_emission, dL_out);
+        DRT_HIP_CHECK(h, dist ? drt::launch_nerf_dist_fwd(P, h->stream) : drt::launch_nerf_aov_fwd(P, h->stream));
+        return (int) DRT_OK;
+    });
+}
+
+int drt_nerf_render_primal_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                               uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
+{
+    return nerf_aov_primal(h, "drt_nerf_render_primal_aov", false, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_out);
 }
 
 int drt_nerf_render_backward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
                                  uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
                                  float *grad_sigma_t, float *grad_emission)
 {
-    return nerf_variant_call(h, "drt_nerf_render_backward_aov", kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
-                             [&](drt::Params &P, const drt::NerfSh &) {
-        if (!dL || !L_in || !grad_sigma_t || !grad_emission)
-            return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_aov: null dL / L_in / gradient buffer");
-        return nerf_aov_backward(h, P, emission, dL, nullptr, L_in, grad_sigma_t, grad_emission);
-    });
+    return nerf_aov_backward_ray(h, "drt_nerf_render_backward_aov", false, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, L_in,
+                                 grad_sigma_t, grad_emission);
 }
 
 int drt_nerf_render_backward_px_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
@@ -2265,26 +2311,47 @@ int drt_nerf_render_backward_px_aov(drt_handle h, const drt_nerf_config *cfg, co
                                     const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
                                     float *grad_emission)
 {
-    return nerf_variant_call(h, "drt_nerf_render_backward_px_aov", kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
-                             [&](drt::Params &P, const drt::NerfSh &) {
-        if (!L_in || !grad_sigma_t || !grad_emission)
-            return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px_aov: null L_in / gradient buffer");
-        DRT_TRY(check_px(h, "drt_nerf_render_backward_px_aov", n_rays, spp, grad_image, n_pixels));
-        return nerf_aov_backward(h, P, emission, nullptr, grad_image, L_in, grad_sigma_t, grad_emission);
-    });
+    return nerf_aov_backward_px(h, "drt_nerf_render_backward_px_aov", false, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed,
+                                grad_image, n_pixels, L_in, grad_sigma_t, grad_emission);
 }
 
 int drt_nerf_render_forward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
                                 const float *t_emission, float *dL_out)
 {
-    return nerf_variant_call(h, "drt_nerf_render_forward_aov", kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
-                             [&](drt::Params &P, const drt::NerfSh &) {
-        if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward_aov: null dL_out");
-        forward_params(P, t_sigma_t, t_emission, dL_out);
-        DRT_HIP_CHECK(h, drt::launch_nerf_aov_fwd(P, h->stream));
-        return (int) DRT_OK;
-    });
+    return nerf_aov_forward(h, "drt_nerf_render_forward_aov", false, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, t_sigma_t,
+                            t_emission, dL_out);
+}
+
+int drt_nerf_render_primal_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
+{
+    return nerf_aov_primal(h, "drt_nerf_render_primal_dist", true, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_out);
+}
+
+int drt_nerf_render_backward_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                  uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
+                                  float *grad_sigma_t, float *grad_emission)
+{
+    return nerf_aov_backward_ray(h, "drt_nerf_render_backward_dist", true, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, L_in,
+                                 grad_sigma_t, grad_emission);
+}
+
+int drt_nerf_render_backward_px_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                                     const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                     const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
+                                     float *grad_emission)
+{
+    return nerf_aov_backward_px(h, "drt_nerf_render_backward_px_dist", true, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed,
+                                grad_image, n_pixels, L_in, grad_sigma_t, grad_emission);
+}
+
+int drt_nerf_render_forward_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
+                                 const float *t_emission, float *dL_out)
+{
+    return nerf_aov_forward(h, "drt_nerf_render_forward_dist", true, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, t_sigma_t,
+                            t_emission, dL_out);
 }
 
 int drt_film_develop_n(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image)

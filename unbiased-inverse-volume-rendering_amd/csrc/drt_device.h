@@ -1527,20 +1527,24 @@ __device__ __forceinline__ void load_dL(const Params &P, I i, float dL[3])
     }
 }
 
-// load_dL for the five interleaved floats [r, g, b, opacity, depth] of the AOV calls: the per-ray buffer, or the image gradient
-// of the ray's pixel times 1/spp - the product film_backward_n_kernel forms
-template <typename I>
-__device__ __forceinline__ void load_dL5(const Params &P, I i, float dL[5])
+// load_dL for the F > 3 interleaved floats of the AOV ([r, g, b, opacity, depth]) and distortion ([.., distortion]) calls: the per-ray buffer,
+// or the image gradient of the ray's pixel times 1/spp - the product film_backward_n_kernel forms
+template <int F, typename I>
+__device__ __forceinline__ void load_dLn(const Params &P, I i, float dL[F])
 {
     if (P.dL_pix) {
         const uint64_t p = (uint32_t) i / P.spp;
         const float inv = 1.0f / (float) P.spp;
 #pragma unroll
-        for (int k = 0; k < 5; ++k) dL[k] = P.dL_pix[5 * p + k] * inv;
+        for (int k = 0; k < F; ++k) dL[k] = P.dL_pix[F * p + k] * inv;
     } else {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) dL[k] = P.dL[5 * i + k];
+        for (int k = 0; k < F; ++k) dL[k] = P.dL[F * i + k];
     }
 }
+
+// Floats per ray / pixel of the nerf march's buffers (L_out / dL / dL_pix / L_in): [r, g, b], with AOV [.., opacity, depth], with a
+// distortion policy (kDist; AOV = true) [.., distortion].  The one place the three counts come from.
+template <bool AOV, bool DIST> constexpr int kNerfRayFloats = DIST ? 6 : AOV ? 5 : 3;
 
 }  // namespace drt

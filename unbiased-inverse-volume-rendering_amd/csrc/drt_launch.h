@@ -54,6 +54,11 @@ hipError_t launch_nerf_sh_tile_adjoint(const Params &P, const NerfSh &S, uint32_
 hipError_t launch_nerf_aov(const Params &P, bool adjoint, hipStream_t stream);
 hipError_t launch_nerf_aov_fwd(const Params &P, hipStream_t stream);
 hipError_t launch_nerf_aov_tile_adjoint(const Params &P, bool g4, uint32_t *bounds, float t_max, hipStream_t stream);
+// drt_nerf_dist.hip: ... and a third, the distortion regulariser Z (quadratic in the march weights): six interleaved floats [r, g, b, A, D, Z],
+// the same kernels with a policy that carries kDist.  The three calls mirror the three above (bounds: 56 bytes)
+hipError_t launch_nerf_dist(const Params &P, bool adjoint, hipStream_t stream);
+hipError_t launch_nerf_dist_fwd(const Params &P, hipStream_t stream);
+hipError_t launch_nerf_dist_tile_adjoint(const Params &P, bool g4, uint32_t *bounds, float t_max, hipStream_t stream);
 // box film with `channels` interleaved floats per sample: one thread per (pixel, channel), samples summed in index order / dL = grad / spp
 hipError_t launch_film_develop_n(const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image, hipStream_t stream);
 hipError_t launch_film_backward_n(const float *grad_image, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *dL, hipStream_t stream);

@@ -1,6 +1,6 @@
 // drt_nerf_kernel.h -- NeRFIntegrator.sample as one ray per lane (the primal pass; the adjoint of explicit ray batches and of the record /
 // atomic gradient paths), shared by drt_kernels.hip and drt_own.hip (the same kernel with the colour grids on their own lattice,
-// DRT_COLOUR_OWN), by drt_nerf_aov.hip (AOV = true) and by drt_nerf_sh.hip (spherical-harmonic emission: its own emission policy).  Internal
+// DRT_COLOUR_OWN), by drt_nerf_aov.hip (AOV = true), by drt_nerf_dist.hip (AOV = true with the DistEmission policy: a distortion output) and by drt_nerf_sh.hip (spherical-harmonic emission: its own emission policy).  Internal
 // linkage: every including unit gets its own instantiations.
 #pragma once
 #include "drt_device.h"
@@ -18,8 +18,9 @@ namespace {
 //   gather   the emission's tangent at p (forward mode)
 //   kScatter the splats go through splat_scatter: deferred records, or atomics staged per wave in LDS
 // This one: three channels from Params::emission (eval_rgb), gradients through splat_scatter, tangents through gather_colour.
+//   kDist    the march also integrates the distortion regulariser Z (below; DistEmission, instantiated with AOV = true by drt_nerf_dist.hip)
 struct PlainEmission {
-    static constexpr bool kScatter = true;
+    static constexpr bool kScatter = true, kDist = false;
     struct Ray { __device__ __forceinline__ explicit Ray(V3) {} };
     struct Query {};
     __device__ __forceinline__ void lookup(const Params &P, const Ray &, V3 p, Query &, float em[3]) const { eval_rgb(P, P.emission, p, em); }
@@ -31,6 +32,9 @@ struct PlainEmission {
     __device__ __forceinline__ void gather(const Params &P, const Ray &, V3 p, const Query &, float dem[3]) const { gather_colour(P, p, dem); }
 };
 
+// the plain emission with the distortion output: six floats [r, g, b, A, D, Z] per ray (drt_nerf_dist.hip)
+struct DistEmission : PlainEmission { static constexpr bool kDist = true; };
+
 // ---------------------------------------------------------------------------
 // NeRFIntegrator.sample (python/integrators/nerf.py:47-148): emission-absorption ray marching,
 // queries_per_ray jittered queries per ray, PRB-style backward.  One ray per lane; the loop is
@@ -40,10 +44,20 @@ struct PlainEmission {
 // origin to the box.  L_out / dL / dL_pix / L_in then hold five interleaved floats [r, g, b, A, D].  A and D are linear in an "emission"
 // q_j = dA + dD (t_in + t_b,j) that no grid holds: the adjoint's sigma_t splat gains q_j (-da T) + (S / safe_a) da, S the running remainder
 // of dA A + dD D as `result` is the colour's; the emission splat is untouched.
+// E::kDist (with AOV; drt_nerf_dist.hip): a sixth float, the distortion regulariser of mip-NeRF 360 in its O(N) form,
+//     Z = sum_i sum_j w_i w_j |tau_i - tau_j| + (1/3) sum_i w_i^2 dt_i     over the non-last queries, w = weight, tau_j = t_in + t_b,j.
+// Primal, per non-last query, W = weights_sum and Dp = depth_sum as they stand BEFORE the query is added, every operation rounded to fp32:
+//     tau = t_in + t_b;  m = tau * W;  m = m - Dp;  m = 2 * m;  s = weight * dt;  s = s / 3;  Z = Z + weight * (m + s)
+// Adjoint: dZ/dw_j = 2 sum_i w_i |tau_j - tau_i| + (2/3) w_j dt_j needs the totals, which L_in holds (A_in, D_in), and prefixes, which
+// the march carries again:  q_Z = dZ * (2 * (tau * (2 * W - A_in) - (2 * Dp - D_in)) + ((2/3) * weight) * dt)  joins q_j.  Z is homogeneous
+// of degree 2 in the weights, sum_i w_i dZ/dw_i = 2 Z, so the remainder S starts from (dA A_in + dD D_in) + (2 dZ) Z_in.
+// Forward mode: dZ += dweight * (2 (tau W - Dp) + ((2/3) weight) dt) + (2 weight) * (tau dW - dDp), prefixes and their tangents likewise.
 // ---------------------------------------------------------------------------
 template <class E, bool ADJ, bool COUNT, bool DEFER, bool AOV = false, class... EArg>
 __global__ void __launch_bounds__(256) nerf_kernel(const Params P, const EArg... earg)
 {
+    static_assert(AOV || !E::kDist, "the distortion march reads opacity and depth: AOV = true");
+    constexpr int F = kNerfRayFloats<AOV, E::kDist>;
     const E src{ earg... };
     uint64_t i = P.ray_first + (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     __shared__ uint32_t occ_lds[kOccWords];
@@ -80,14 +94,19 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P, const EArg...
         const typename E::Ray er(d);
         float result[3] = { 0.0f, 0.0f, 0.0f }, dL[3] = { 0.0f, 0.0f, 0.0f };
         float dA = 0.0f, dD = 0.0f, Srem = 0.0f, depth_sum = 0.0f, t_in = 0.0f;   // (AOV)
+        float dZ = 0.0f, A_in = 0.0f, D_in = 0.0f, dist_sum = 0.0f;                // (E::kDist)
         if constexpr (ADJ && AOV) {
-            float d5[5];
-            load_dL5(P, i, d5);
-            result[0] = P.L_in[5 * i]; result[1] = P.L_in[5 * i + 1]; result[2] = P.L_in[5 * i + 2];
+            float d5[F];
+            load_dLn<F>(P, i, d5);
+            result[0] = P.L_in[F * i]; result[1] = P.L_in[F * i + 1]; result[2] = P.L_in[F * i + 2];
             dL[0] = d5[0]; dL[1] = d5[1]; dL[2] = d5[2]; dA = d5[3]; dD = d5[4];
-            Srem = dA * P.L_in[5 * i + 3] + dD * P.L_in[5 * i + 4];
+            Srem = dA * P.L_in[F * i + 3] + dD * P.L_in[F * i + 4];
+            if constexpr (E::kDist) {
+                dZ = d5[5]; A_in = P.L_in[F * i + 3]; D_in = P.L_in[F * i + 4];
+                Srem = Srem + (2.0f * dZ) * P.L_in[F * i + 5];
+            }
         } else if constexpr (ADJ) {
-            result[0] = P.L_in[3 * i]; result[1] = P.L_in[3 * i + 1]; result[2] = P.L_in[3 * i + 2];
+            result[0] = P.L_in[F * i]; result[1] = P.L_in[F * i + 1]; result[2] = P.L_in[F * i + 2];
             load_dL(P, i, dL);
         }
         float throughput = 1.0f, weights_sum = 0.0f;
@@ -137,7 +156,11 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P, const EArg...
                         ge[k] = dL[k] * weight;
                     }
                     if constexpr (AOV) {                                     // (the last query belongs to neither sum, and its da is 0)
-                        const float q = dA + dD * (t_in + t_b);
+                        float q = dA + dD * (t_in + t_b);
+                        if constexpr (E::kDist) {                            // (weights_sum, depth_sum: the prefixes, this query not yet added)
+                            const float tau = t_in + t_b;
+                            q = q + dZ * (2.0f * (tau * (2.0f * weights_sum - A_in) - (2.0f * depth_sum - D_in)) + ((2.0f / 3.0f) * weight) * dt);
+                        }
                         if (!last) Srem = Srem - weight * q;
                         gs += q * (-da * throughput) + (Srem / safe_a) * da;
                     }
@@ -145,8 +168,14 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P, const EArg...
                     src.template splat<DEFER>(P, er, p, eq, gs, ge, rec);
                 }
                 t_a = t_b;
+                if constexpr (E::kDist && !ADJ) {                            // (before the prefixes take the query; the order: the comment above)
+                    if (!last) {
+                        const float tau = t_in + t_b;
+                        dist_sum = dist_sum + weight * (2.0f * (tau * weights_sum - depth_sum) + (weight * dt) / 3.0f);
+                    }
+                }
                 if (!last) { throughput *= safe_a; weights_sum += weight; }  // :117-120
-                if constexpr (AOV && !ADJ) { if (!last) depth_sum += weight * (t_in + t_b); }
+                if constexpr (AOV && (!ADJ || E::kDist)) { if (!last) depth_sum += weight * (t_in + t_b); }
             }
         }
         bool active_e = escaped || active;                                   // :131-146
@@ -158,9 +187,10 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P, const EArg...
             for (int k = 0; k < 3; ++k) result[k] += (1.0f - weights_sum) * Le[k];
         }
         if constexpr (!ADJ && AOV) {
-            float *out = P.L_out + 5 * i;
+            float *out = P.L_out + F * i;
             out[0] = result[0]; out[1] = result[1]; out[2] = result[2]; out[3] = weights_sum; out[4] = depth_sum;
-        } else if constexpr (!ADJ) { P.L_out[3 * i] = result[0]; P.L_out[3 * i + 1] = result[1]; P.L_out[3 * i + 2] = result[2]; }
+            if constexpr (E::kDist) out[5] = dist_sum;
+        } else if constexpr (!ADJ) { P.L_out[F * i] = result[0]; P.L_out[F * i + 1] = result[1]; P.L_out[F * i + 2] = result[2]; }
     }
     if constexpr (ADJ && DEFER) close_records(P, rec);
     if (COUNT) {
@@ -180,11 +210,14 @@ __global__ void __launch_bounds__(256) nerf_kernel(const Params P, const EArg...
 // looks up sigma_t' and emission' in the tangent grids (Params::g_sigma / g_albedo) through the stencils of the adjoint's splats
 // (gather_sigma_t / gather_colour, no occupancy skip), and the derivative is carried through the opacity, the throughput, the weights
 // and the emitter term behind the medium.  The relu kink takes the adjoint's convention: no derivative unless raw > 0.  One ray per
-// lane, one write per ray.  AOV: five floats per ray, dA = dweights_sum and dD = sum dweight (t_in + t_b).
+// lane, one write per ray.  AOV: five floats per ray, dA = dweights_sum and dD = sum dweight (t_in + t_b).  E::kDist: six, the tangent of Z
+// (the comment of nerf_kernel) from the prefixes W, Dp and their tangents as they stand before the query is added.
 // ---------------------------------------------------------------------------
 template <class E, bool AOV = false, class... EArg>
 __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P, const EArg... earg)
 {
+    static_assert(AOV || !E::kDist, "the distortion march reads opacity and depth: AOV = true");
+    constexpr int F = kNerfRayFloats<AOV, E::kDist>;
     const E src{ earg... };
     uint64_t i = P.ray_first + (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     __shared__ uint32_t occ_lds[kOccWords];
@@ -210,6 +243,7 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P, const EAr
     float dres[3] = { 0.0f, 0.0f, 0.0f };                                // the tangent of `result`
     float throughput = 1.0f, weights_sum = 0.0f, dthroughput = 0.0f, dweights_sum = 0.0f;
     float ddepth_sum = 0.0f, t_in = 0.0f;                                // (AOV)
+    float depth_sum = 0.0f, ddist_sum = 0.0f;                            // (E::kDist)
     Hit si = box_hit(P, o, d);                                           // nerf.py:67-79
     bool active = si.valid, escaped = !active;
     if (active) {
@@ -242,11 +276,19 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P, const EAr
 #pragma unroll
             for (int k = 0; k < 3; ++k) dres[k] += dweight * em[k] + weight * dem[k];
             t_a = t_b;
+            if constexpr (E::kDist) {                                    // (before the prefixes and their tangents take the query)
+                if (!last) {
+                    const float tau = t_in + t_b;
+                    ddist_sum = ddist_sum + (dweight * (2.0f * (tau * weights_sum - depth_sum) + ((2.0f / 3.0f) * weight) * dt) +
+                                             (2.0f * weight) * (tau * dweights_sum - ddepth_sum));
+                }
+            }
             if (!last) {                                                 // :117-120
                 dthroughput = dthroughput * (a + 1e-10f) + throughput * da;
                 throughput *= a + 1e-10f;
                 weights_sum += weight; dweights_sum += dweight;
                 if constexpr (AOV) ddepth_sum += dweight * (t_in + t_b);
+                if constexpr (E::kDist) depth_sum += weight * (t_in + t_b);
             }
         }
     }
@@ -259,9 +301,10 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P, const EAr
         for (int k = 0; k < 3; ++k) dres[k] += -dweights_sum * Le[k];
     }
     if constexpr (AOV) {
-        float *out = P.L_out + 5 * i;
+        float *out = P.L_out + F * i;
         out[0] = dres[0]; out[1] = dres[1]; out[2] = dres[2]; out[3] = dweights_sum; out[4] = ddepth_sum;
-    } else { P.L_out[3 * i] = dres[0]; P.L_out[3 * i + 1] = dres[1]; P.L_out[3 * i + 2] = dres[2]; }
+        if constexpr (E::kDist) out[5] = ddist_sum;
+    } else { P.L_out[F * i] = dres[0]; P.L_out[F * i + 1] = dres[1]; P.L_out[F * i + 2] = dres[2]; }
 }
 
 }  // namespace

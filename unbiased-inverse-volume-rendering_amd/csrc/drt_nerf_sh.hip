@@ -147,7 +147,7 @@ __device__ __forceinline__ void sh_gather(const float *t_sh, const Stencil &s, c
 // the interleaved copy, the splats as fp32 atomics on the caller's grids - sigma_t's eight corners first, then the colour corners -, the tangents
 // from the caller's tangent grid.  No records and no counters: the SH calls count nothing
 template <int K> struct ShEmission {
-    static constexpr bool kScatter = false;
+    static constexpr bool kScatter = false, kDist = false;
     const float4 *vox;
     struct Ray {
         float Y[K];
@@ -198,7 +198,7 @@ template <int K> struct ShEmission {
 template <int K> struct ShWindow {
     static constexpr int WX = ShCfg<K>::WX, WY = ShCfg<K>::WY, WZ = ShCfg<K>::WZ, kPlanes = 1 + 3 * K, kThreads = kShThreads, kChannels = 3 * K;
     static constexpr float kEmaxFactor = sh_abs_sum<K>();
-    static constexpr bool kOcc = false, kCounters = false;
+    static constexpr bool kOcc = false, kCounters = false, kDist = false;
     const float4 *vox;
     __device__ __forceinline__ float sigma_t(const Params &P, V3 p, const uint32_t *) const
     {

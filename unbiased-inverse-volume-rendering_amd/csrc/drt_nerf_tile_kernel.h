@@ -3,7 +3,7 @@
 // per ray in dL / dL_pix / L_in; the two extra outputs depend on sigma_t only, so the window keeps its 1 + 3 planes and the sigma_t splat gains
 // one term) and drt_nerf_sh.hip (spherical-harmonic emission: a window of 1 + 3K planes, its own lookup and colour splat).  What differs between
 // them is a compile-time WINDOW CONFIGURATION (PlainWindow below); the march, the fixed-point units, the window protocol, the bounds kernel and
-// the launcher exist once.  Internal linkage: every including unit gets its own instantiations.
+// the launcher exist once.  drt_nerf_dist.hip: DistWindow (AOV = true and C::kDist: a sixth float per ray, the distortion regulariser Z).  Internal linkage: every including unit gets its own instantiations.
 #pragma once
 #include <atomic>
 #include "drt_device.h"
@@ -46,6 +46,7 @@ struct NerfTile {
     uint32_t count;
     float t_max;                   // AOV: a bound of t_in + t_b, the distance of a query from the sensor's origin (from the host); bounds then holds 12 words:
                                    // [8] max |dA|, [9] max |dD|, [10] max |A_in|, [11] max |D_in| (channels 3 and 4 of dL / dL_pix / L_in; [0], [1]: channels 0 - 2)
+                                   // C::kDist: 14 words, [12] max |dZ|, [13] max |Z_in| (channel 5)
 };
 
 // x * inv (|.| < 2^51) as a two's complement integer, rounded to nearest: the double 1.5 x 2^52 + n holds n in its low mantissa bits
@@ -83,10 +84,11 @@ __device__ __forceinline__ void eval4_at(const Params &P, const Stencil &s, floa
 //   kCounters      counting launches add to Params::counters and bounds[6..7]; without: they count their window phases in bounds[5]
 //   sigma_t        a query's scaled density alone (the pre-march)                   lookup      density and emission at a footprint that is known
 //   splat_colour   a query's colour gradients into planes 1 .. kPlanes - 1
+//   kDist          six floats per ray: the march carries the distortion regulariser's prefixes and its term of the sigma_t splat (DistWindow)
 template <bool G4> struct PlainWindow {
     static constexpr int WX = 16, WY = 16, WZ = 16, kPlanes = 4, kThreads = DRT_NT_THREADS, kChannels = 3;
     static constexpr float kEmaxFactor = 1.0f;
-    static constexpr bool kOcc = !G4, kCounters = true;
+    static constexpr bool kOcc = !G4, kCounters = true, kDist = false;
     __device__ __forceinline__ float sigma_t(const Params &P, V3 p, const uint32_t *occ) const
     {
         if constexpr (G4) {
@@ -117,6 +119,9 @@ template <bool G4> struct PlainWindow {
         }
     }
 };
+// the plain window for the distortion calls (drt_nerf_dist.hip): the same window, planes, lookups and LDS bytes
+template <bool G4> struct DistWindow : PlainWindow<G4> { static constexpr bool kDist = true; };
+static_assert(Window<DistWindow<true>>::kBytes == Window<PlainWindow<true>>::kBytes, "the distortion window is the plain one");
 static_assert(Window<PlainWindow<true>>::kStore == 4432 && Window<PlainWindow<true>>::kBytes == 4 * 4432 * 8, "LDS bytes per workgroup (DESIGN.md)");
 
 // max |dL|, max |L_in| over the rays of the launch and max |emission| over the grid -> out[0..2] (float bits; zeroed by the caller):
@@ -154,19 +159,22 @@ __global__ void __launch_bounds__(256) nerf_tile_bounds_kernel(const float *dL, 
 
 // the ray buffers of an AOV launch: five interleaved floats per ray / pixel.  Channels 0 - 2 -> out[0] (dL), out[1] (L_in) as above;
 // channel 3 (opacity) -> out[8] (dA), out[10] (A_in); channel 4 (depth) -> out[9] (dD), out[11] (D_in); out[3]: a non-finite one was seen.
+// C = 6 (the distortion calls): channel 5 -> out[12] (dZ), out[13] (Z_in).
 // (the grids' maxima out[2], out[4]: nerf_tile_bounds_kernel with empty ray buffers; a template, so that only the unit that launches it holds it)
 template <int C>
 __global__ void __launch_bounds__(256) nerf_tile_bounds_aov_kernel(const float *dL, const float *L_in, size_t n_ray_floats, const float *dL_pix,
                                                                    size_t n_px_floats, float inv_spp, uint32_t *out)
 {
-    float m[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };               // dL, L_in, dA, dD, A_in, D_in
+    static_assert(C == 5 || C == 6, "five floats per ray, or six with the distortion output");
+    constexpr int M = C > 5 ? 8 : 6;
+    float m[M] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };               // dL, L_in, dA, dD, A_in, D_in, (C = 6) dZ, Z_in
     const size_t stride = (size_t) gridDim.x * blockDim.x, i0 = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     bool bad = false;
     for (size_t i = i0; i < n_ray_floats; i += stride) {
         const uint32_t c = (uint32_t) (i % C);
         const float b = fabsf(L_in[i]);
         bad = bad || !(b < kInf);
-        if (c < 3) m[1] = fmaxf(m[1], b); else if (c == 3) m[4] = fmaxf(m[4], b); else m[5] = fmaxf(m[5], b);
+        if (c < 3) m[1] = fmaxf(m[1], b); else if (c == 3) m[4] = fmaxf(m[4], b); else if (C == 5 || c == 4) m[5] = fmaxf(m[5], b); else m[M - 1] = fmaxf(m[M - 1], b);
     }
     const float *g = dL_pix ? dL_pix : dL;
     const size_t n_g = dL_pix ? n_px_floats : n_ray_floats;
@@ -175,24 +183,30 @@ __global__ void __launch_bounds__(256) nerf_tile_bounds_aov_kernel(const float *
         const uint32_t c = (uint32_t) (i % C);
         const float a = fabsf(g[i] * f);
         bad = bad || !(a < kInf);
-        if (c < 3) m[0] = fmaxf(m[0], a); else if (c == 3) m[2] = fmaxf(m[2], a); else m[3] = fmaxf(m[3], a);
+        if (c < 3) m[0] = fmaxf(m[0], a); else if (c == 3) m[2] = fmaxf(m[2], a); else if (C == 5 || c == 4) m[3] = fmaxf(m[3], a); else m[M - 2] = fmaxf(m[M - 2], a);
     }
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(out + 3, 1u);
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
+    for (int k = 0; k < M; ++k) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) m[k] = fmaxf(m[k], __shfl_down(m[k], off, 64));
-        if ((threadIdx.x & 63) == 0 && m[k] > 0.0f) atomicMax(out + (k < 2 ? k : 6 + k), __float_as_uint(m[k]));
+        if ((threadIdx.x & 63) == 0 && m[k] > 0.0f) atomicMax(out + (k < 2 ? k : 6 + k), __float_as_uint(m[k]));   // (m[6], m[7] -> out[12], out[13])
     }
 }
 
 // AOV (drt_nerf_aov.hip): dL / dL_pix / L_in hold five floats per ray / pixel, [r, g, b, opacity A, depth D] with A = sum_{j+1<N} weight_j and
 // D = sum_{j+1<N} weight_j (t_in + t_b,j).  Both are linear in an "emission" q_j = dA + dD (t_in + t_b,j) that no grid holds: the colour planes
 // are untouched, and the sigma_t splat gains q_j (-da T) + (S / safe_a) da, S the running remainder of dA A + dD D as `result` is the colour's.
+// C::kDist (drt_nerf_dist.hip, with AOV): six floats, the sixth the distortion regulariser Z (the comment of nerf_kernel, drt_nerf_kernel.h).  Its
+// gradient dZ joins q_j as q_Z = dZ (2 (tau (2 W - A_in) - (2 Dp - D_in)) + (2/3) weight dt), W and Dp the prefixes of opacity and depth, which the
+// march carries: they, like S, advance where the query is computed - a ray that waits with its splat while the window moves resumes at the splat,
+// not at the query, so nothing advances twice.  S starts from dA A_in + dD D_in + 2 dZ Z_in (Z is homogeneous of degree 2 in the weights).
 // (CArg: what the configuration is built from - none for the plain one, whose kernel keeps its argument block)
 template <class C, bool AOV, class... CArg>
 __global__ void __launch_bounds__(C::kThreads) nerf_tile_adjoint_kernel(const Params P, const NerfTile T, const CArg... carg)
 {
+    static_assert(AOV || !C::kDist, "the distortion march reads opacity and depth: AOV = true");
+    constexpr int F = kNerfRayFloats<AOV, C::kDist>;
     const C cfg{ carg... };
     constexpr int NT = C::kThreads, WX = C::WX, WY = C::WY, WZ = C::WZ, NP = C::kPlanes;
     constexpr int kSY = Window<C>::kSY, kSZ = Window<C>::kSZ, kStore = Window<C>::kStore;
@@ -250,14 +264,25 @@ __global__ void __launch_bounds__(C::kThreads) nerf_tile_adjoint_kernel(const Pa
     // cannot carry them.  The march is skipped and BOTH gradient grids are filled with NaN - every voxel, so that a caller (or a masked
     // all-reduce) that looks at any part of the grids sees that this gradient is void, as it would find NaN in the voxels the record path touches.
     //   AOV: |q_j| <= Qb = dAmax + dDmax t_max, |S| <= Sb + Qb W with Sb = dAmax Amax + dDmax Dmax_in:  |gs_aov| <= dt (Qb M1 + Sb + Qb W)
-    float Qb = 0.0f, Sb = 0.0f;
+    //   kDist: q_j gains q_Z.  With tau <= t_max, |W| <= Wm (W of the workgroup, >= sum |weight|), |Dp| <= t_max Wm, |weight| <= M1, dt <= dt_max and
+    //   ANY A_in, D_in the caller passes:  |q_Z| <= Qz(M1, Wm) = dZmax (2 (t_max (2 Wm + Amax) + (2 t_max Wm + Dmax_in)) + (2/3) M1 dt_max)
+    //   (for the primal's own A_in, D_in the bracket is 2 sum_i w_i |tau_j - tau_i| <= 2 l Wm, l the box diagonal: the bound has the form
+    //   dZmax (2 l (2 Wm) + (2/3) M1 dt_max) with t_max >= l in l's place and room for the inputs), and Sb gains 2 dZmax Zmax_in
+    float Qb = 0.0f, Sb = 0.0f, dZmax = 0.0f, Qz_in = 0.0f;
     if constexpr (AOV) {
         const float dAmax = __uint_as_float(T.bounds[8]), dDmax = __uint_as_float(T.bounds[9]);
         Qb = dAmax + dDmax * T.t_max;
         Sb = dAmax * __uint_as_float(T.bounds[10]) + dDmax * __uint_as_float(T.bounds[11]);
+        if constexpr (C::kDist) {
+            dZmax = __uint_as_float(T.bounds[12]);
+            Sb += 2.0f * dZmax * __uint_as_float(T.bounds[13]);
+            Qz_in = T.t_max * __uint_as_float(T.bounds[10]) + __uint_as_float(T.bounds[11]);   // (the inputs' share of the bracket)
+        }
     }
+    auto Qz = [&](float M1, float Wm) { return dZmax * (2.0f * (4.0f * T.t_max * Wm + Qz_in) + (2.0f / 3.0f) * M1 * dt_max); };
     if (T.bounds[3] || !(fabsf(P.scale) * 3.0f * Dmax * (2.0f * Emax + Lmax) * dt_max * 1.001f < kInf) || !(Dmax < kInf) ||
-        (AOV && !(fabsf(P.scale) * (2.0f * Qb + Sb) * dt_max * 1.001f < kInf))) {
+        (AOV && !(fabsf(P.scale) * (2.0f * Qb + Sb) * dt_max * 1.001f < kInf)) ||
+        (C::kDist && !(fabsf(P.scale) * (2.0f * Qz(1.0f, 1.0f) + Sb) * dt_max * 1.001f < kInf))) {
         const float nan = __uint_as_float(0x7fc00000u);
         const size_t i0 = (size_t) blockIdx.x * NT + t, stride = (size_t) gridDim.x * NT;
         for (size_t v = i0; v < nv; v += stride) P.g_sigma[v] = nan;
@@ -281,6 +306,7 @@ __global__ void __launch_bounds__(C::kThreads) nerf_tile_adjoint_kernel(const Pa
     V3 o = v3(0, 0, 0), d = v3(0, 0, 1);
     float result[3] = { 0, 0, 0 }, dL[3] = { 0, 0, 0 };
     float dA = 0.0f, dD = 0.0f, Srem = 0.0f;                              // AOV: the gradients of opacity and depth, the remainder of dA A + dD D
+    float dZ = 0.0f, A_in = 0.0f, D_in = 0.0f, Wp = 0.0f, Dp = 0.0f;      // kDist: the gradient of Z, the primal's opacity and depth, their prefixes
     float throughput = 1.0f, step = 0.0f, jit = 0.0f, t_a = 0.0f, ent_t = 0.0f;
     bool active = false;
     if (job) {
@@ -288,13 +314,17 @@ __global__ void __launch_bounds__(C::kThreads) nerf_tile_adjoint_kernel(const Pa
         const float ux = S.next_1d(), uy = S.next_1d();
         sensor_ray(P, gi / P.spp, ux, uy, o, d);
         if constexpr (AOV) {
-            float d5[5];
-            load_dL5(P, i, d5);
-            result[0] = P.L_in[5 * i]; result[1] = P.L_in[5 * i + 1]; result[2] = P.L_in[5 * i + 2];
+            float d5[F];
+            load_dLn<F>(P, i, d5);
+            result[0] = P.L_in[F * i]; result[1] = P.L_in[F * i + 1]; result[2] = P.L_in[F * i + 2];
             dL[0] = d5[0]; dL[1] = d5[1]; dL[2] = d5[2]; dA = d5[3]; dD = d5[4];
-            Srem = dA * P.L_in[5 * i + 3] + dD * P.L_in[5 * i + 4];
+            Srem = dA * P.L_in[F * i + 3] + dD * P.L_in[F * i + 4];
+            if constexpr (C::kDist) {
+                dZ = d5[5]; A_in = P.L_in[F * i + 3]; D_in = P.L_in[F * i + 4];
+                Srem = Srem + (2.0f * dZ) * P.L_in[F * i + 5];
+            }
         } else {
-            result[0] = P.L_in[3 * i]; result[1] = P.L_in[3 * i + 1]; result[2] = P.L_in[3 * i + 2];
+            result[0] = P.L_in[F * i]; result[1] = P.L_in[F * i + 1]; result[2] = P.L_in[F * i + 2];
             load_dL(P, i, dL);
         }
         Hit si = box_hit(P, o, d);
@@ -346,6 +376,7 @@ __global__ void __launch_bounds__(C::kThreads) nerf_tile_adjoint_kernel(const Pa
         float Bs = fabsf(P.scale) * 3.0f * Dmax * (Emax * M1 + Emax * Wm + Lmax) * dt_max * 1.001f;
         const float Bc = Dmax * M1;
         if constexpr (AOV) Bs += fabsf(P.scale) * (Qb * M1 + Qb * Wm + Sb) * dt_max * 1.001f;
+        if constexpr (C::kDist) { const float qz = Qz(M1, Wm); Bs += fabsf(P.scale) * (qz * M1 + qz * Wm) * dt_max * 1.001f; }
         if (!(Bs < kInf) || !(Bc < kInf)) {                             // this workgroup's rays overflow fp32: its share of the gradient is void - and so is the whole
             const float nan = __uint_as_float(0x7fc00000u);
             for (size_t v = t; v < nv; v += NT) P.g_sigma[v] = nan;
@@ -438,7 +469,12 @@ __global__ void __launch_bounds__(C::kThreads) nerf_tile_adjoint_kernel(const Pa
                 ge[k] = dL[k] * weight;
             }
             if constexpr (AOV) {                                                // (the last query belongs to neither sum, and its da is 0)
-                const float q = dA + dD * (ent_t + t_b);
+                float q = dA + dD * (ent_t + t_b);
+                if constexpr (C::kDist) {                                       // (Wp, Dp: the prefixes, this query not yet added)
+                    const float tau = ent_t + t_b;
+                    q = q + dZ * (2.0f * (tau * (2.0f * Wp - A_in) - (2.0f * Dp - D_in)) + ((2.0f / 3.0f) * weight) * dt);
+                    if (!last) { Wp += weight; Dp += weight * tau; }
+                }
                 if (!last) Srem = Srem - weight * q;
                 gs += q * (-da * throughput) + (Srem / safe_a) * da;
             }
@@ -517,10 +553,10 @@ hipError_t nerf_tile_launch(const Params &P, bool count, uint32_t *bounds, float
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
     if (!nerf_tile_supported(P) || !bounds || !P.emission) return hipErrorInvalidValue;
-    constexpr size_t F = AOV ? 5 : 3;                                    // floats per ray / pixel
+    constexpr size_t F = kNerfRayFloats<AOV, C::kDist>;                  // floats per ray / pixel
     NerfTile T;
     {
-        hipError_t e = hipMemsetAsync(bounds, 0, (AOV ? 12 : 8) * sizeof(uint32_t), stream);
+        hipError_t e = hipMemsetAsync(bounds, 0, (C::kDist ? 14 : AOV ? 12 : 8) * sizeof(uint32_t), stream);
         if (e != hipSuccess) return e;
         const size_t nv = (size_t) P.rx * P.ry * P.rz, n_em = nv * (size_t) C::kChannels;
         // (pixel layout: the pixels of rays ray_first .. n_rays - 1, both ends included)
@@ -528,7 +564,7 @@ hipError_t nerf_tile_launch(const Params &P, bool count, uint32_t *bounds, float
         const float *dL = P.dL_pix ? nullptr : P.dL + F * P.ray_first, *dL_pix = P.dL_pix ? P.dL_pix + F * px_first : nullptr;
         const size_t n_ray_floats = (size_t) (P.n_rays - P.ray_first) * F, n_px_floats = (size_t) (px_last - px_first + 1) * F;
         if constexpr (AOV) {
-            hipLaunchKernelGGL(nerf_tile_bounds_aov_kernel<5>, dim3(2048), dim3(256), 0, stream, dL, P.L_in + F * P.ray_first, n_ray_floats, dL_pix,
+            hipLaunchKernelGGL(nerf_tile_bounds_aov_kernel<(int) F>, dim3(2048), dim3(256), 0, stream, dL, P.L_in + F * P.ray_first, n_ray_floats, dL_pix,
                                n_px_floats, 1.0f / (float) P.spp, bounds);
             hipLaunchKernelGGL(nerf_tile_bounds_kernel, dim3(2048), dim3(256), 0, stream, (const float *) nullptr, (const float *) nullptr, (size_t) 0,
                                (const float *) nullptr, (size_t) 0, 1.0f, P.emission, n_em, P.sigma_t, nv, bounds);
@@ -557,12 +593,12 @@ hipError_t nerf_tile_launch(const Params &P, bool count, uint32_t *bounds, float
 }
 
 // ... with the plain configuration, for the kind of lookup the call asks for
-template <bool AOV>
+template <bool AOV, template <bool> class W = PlainWindow>
 hipError_t nerf_tile_launch_plain(const Params &P, bool g4, bool count, uint32_t *bounds, float t_max, hipStream_t stream)
 {
     if (g4 && !P.grid4 && P.n_rays > P.ray_first) return hipErrorInvalidValue;
-    return g4 ? nerf_tile_launch<PlainWindow<true>, AOV>(P, count, bounds, t_max, stream)
-              : nerf_tile_launch<PlainWindow<false>, AOV>(P, count, bounds, t_max, stream);
+    return g4 ? nerf_tile_launch<W<true>, AOV>(P, count, bounds, t_max, stream)
+              : nerf_tile_launch<W<false>, AOV>(P, count, bounds, t_max, stream);
 }
 
 }  // namespace

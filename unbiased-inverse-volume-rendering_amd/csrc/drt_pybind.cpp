@@ -440,6 +440,57 @@ public:
         }
         check(rc, "drt_nerf_render_forward_aov");
     }
+    // ... and the distortion output (drt_nerf_*_dist): six
+    void nerf_render_primal_dist(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                uint32_t spp, uint32_t seed, uintptr_t L_out)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_primal_dist(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
+                                            seed, ptr<float>(L_out));
+        }
+        check(rc, "drt_nerf_render_primal_dist");
+    }
+    void nerf_render_backward_dist(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                  uint32_t spp, uint32_t seed, uintptr_t dL, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_emission)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_backward_dist(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
+                                              seed, ptr<const float>(dL), ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_emission));
+        }
+        check(rc, "drt_nerf_render_backward_dist");
+    }
+    void nerf_render_backward_px_dist(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                     uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
+                                     uintptr_t g_emission)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_backward_px_dist(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
+                                                 spp, seed, ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
+                                                 ptr<float>(g_emission));
+        }
+        check(rc, "drt_nerf_render_backward_px_dist");
+    }
+    void nerf_render_forward_dist(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                 uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_emission, uintptr_t dL_out)
+    {
+        drt_nerf_config c = nerf_cfg(props);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_nerf_render_forward_dist(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
+                                             seed, ptr<const float>(t_sigma), ptr<const float>(t_emission), ptr<float>(dL_out));
+        }
+        check(rc, "drt_nerf_render_forward_dist");
+    }
     void film_develop_n(uintptr_t L, uint64_t n_pixels, uint32_t spp, uint32_t channels, uintptr_t image)
     {
         int rc;
@@ -589,6 +640,10 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("nerf_render_backward_aov", &Integrator::nerf_render_backward_aov)
         .def("nerf_render_backward_px_aov", &Integrator::nerf_render_backward_px_aov)
         .def("nerf_render_forward_aov", &Integrator::nerf_render_forward_aov)
+        .def("nerf_render_primal_dist", &Integrator::nerf_render_primal_dist)
+        .def("nerf_render_backward_dist", &Integrator::nerf_render_backward_dist)
+        .def("nerf_render_backward_px_dist", &Integrator::nerf_render_backward_px_dist)
+        .def("nerf_render_forward_dist", &Integrator::nerf_render_forward_dist)
         .def("film_develop_n", &Integrator::film_develop_n)
         .def("film_backward_n", &Integrator::film_backward_n)
         .def("debug_eval", &Integrator::debug_eval)

@@ -31,7 +31,7 @@ def fd_gradients(output_dir: Optional[str], scene: Scene, params: Dict[str, torc
                  spp: int = 4096, write_images: bool = False, integrator=None, seed: int = 1234, sensor: int = 0,
                  central: bool = False) -> Dict[str, np.ndarray]:
     """python/fd.py:10-77.  `params`: {key: device grid (Z, Y, X, C)} - the entries to differentiate (they replace the
-    scene's grids); `loss_fn(image)` with image (H, W, 3) ((H, W, 5) with a `nerf` integrator's aovs) -> scalar tensor.  Returns {key: array of d loss / d entry}.
+    scene's grids); `loss_fn(image)` with image (H, W, 3) ((H, W, 5) with a `nerf` integrator's aovs, (H, W, 6) with its distortion output) -> scalar tensor.  Returns {key: array of d loss / d entry}.
     `central=True` uses (loss(+eps) - loss(-eps)) / (2 eps) instead of the reference's forward difference.
     PHASE_G_KEY: the asymmetry g of an HG medium, a 0-d tensor (the result is a 0-d array)."""
     if integrator is None:

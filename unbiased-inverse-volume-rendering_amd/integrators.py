@@ -523,7 +523,13 @@ class NeRFIntegrator(_DeviceIntegrator):
     `aovs` (default False): True adds two outputs per ray and pixel behind the colour, opacity A = sum of the march weights (the alpha the
     emitter is composited with) and depth D = sum weight x distance from the ray's origin (D / A: the mean depth).  Every radiance, δL,
     state, image and image-gradient tensor then has five channels [r, g, b, A, D]; the colour channels are the bits of `aovs=False`, and
-    A and D are differentiable with respect to sigma_t in both AD modes (csrc/drt_nerf_aov.hip).  Not with `sh_degree` > 0."""
+    A and D are differentiable with respect to sigma_t in both AD modes (csrc/drt_nerf_aov.hip).  Not with `sh_degree` > 0.
+
+    `distortion` (default False; needs `aovs=True`, whose opacity and depth its adjoint reads from the state): True adds a sixth channel,
+    the distortion regulariser of mip-NeRF 360 in its O(N) form, Z = sum_ij w_i w_j |tau_i - tau_j| + (1/3) sum_i w_i^2 dt_i over the
+    march weights, in world units of length like D (a ray that misses the box: 0).  It is small where a ray's weight sits in one place and
+    large for floaters and fog; minimise its image mean (`losses.distortion`, `OptimizationConfig.distortion_weight`).  Differentiable
+    with respect to sigma_t in both AD modes; channels 0 - 4 are the bits of `aovs=True` (csrc/drt_nerf_dist.hip)."""
 
     param_keys = (SIGMA_T_KEY, EMISSION_KEY)
     needs_albedo = False
@@ -545,6 +551,9 @@ class NeRFIntegrator(_DeviceIntegrator):
         if self._aovs and self.sh_degree:
             raise NotImplementedError(f"aovs=True with sh_degree {self.sh_degree}: the opacity / depth outputs have no spherical-harmonic "
                                       "kernels; use sh_degree=0")
+        self._distortion = bool(props.get("distortion", False))
+        if self._distortion and not self._aovs:
+            raise ValueError("distortion=True needs aovs=True: the distortion output's adjoint reads opacity and depth from the state")
         self.max_depth = int(props.get("max_depth", 6))          # RBIntegrator base; unused (nerf.py)
         self.rr_depth = int(props.get("rr_depth", 5))
         if self.activation_type not in ("identity", "relu"):
@@ -560,12 +569,12 @@ class NeRFIntegrator(_DeviceIntegrator):
         self._bound_phase: Dict[int, tuple] = {}
 
     def aovs(self):
-        return ["opacity", "depth"] if self._aovs else []
+        return (["opacity", "depth"] + (["distortion"] if self._distortion else [])) if self._aovs else []
 
     @property
     def channels(self) -> int:
-        """Floats per ray and pixel: 3, or 5 with `aovs`."""
-        return 5 if self._aovs else 3
+        """Floats per ray and pixel: 3, 5 with `aovs`, 6 with `distortion` too."""
+        return 3 + len(self.aovs())
 
     @property
     def sh_degree(self) -> int:
@@ -582,35 +591,38 @@ class NeRFIntegrator(_DeviceIntegrator):
     def props(self) -> dict:
         return dict(hide_emitters=self.hide_emitters, queries_per_ray=self.queries_per_ray,
                     jittering_enabled=self.jittering_enabled, activation=self.activation_type,
-                    density_noise_std=self.density_noise_std, sh_degree=self.sh_degree, **({"aovs": True} if self._aovs else {}))
+                    density_noise_std=self.density_noise_std, sh_degree=self.sh_degree, **({"aovs": True} if self._aovs else {}),
+                    **({"distortion": True} if self._distortion else {}))
 
     def _native_props(self) -> dict:
         return dict(max_depth=0)
 
-    # -- film with the integrator's channel count (aovs: drt_film_*_n with five interleaved channels) -----
+    # -- film with the integrator's channel count (aovs: drt_film_*_n with five interleaved channels, six with distortion) -----
     def develop(self, scene: Scene, L: torch.Tensor, spp: int) -> torch.Tensor:
         if not self._aovs:
             return super().develop(scene, L, spp)
         h, dev = self._bind(scene)
         _check(L, None, dev, "L")
-        if L.dim() != 2 or L.shape[1] != 5:
-            raise ValueError(f"develop: with aovs the radiance must have shape [n, 5], got {tuple(L.shape)}")
+        C = self.channels
+        if L.dim() != 2 or L.shape[1] != C:
+            raise ValueError(f"develop: with aovs the radiance must have shape [n, {C}], got {tuple(L.shape)}")
         n_pix = L.shape[0] // spp
-        img = torch.empty((n_pix, 5), dtype=torch.float32, device=dev)
-        h.film_develop_n(L.data_ptr(), n_pix, int(spp), 5, img.data_ptr())
+        img = torch.empty((n_pix, C), dtype=torch.float32, device=dev)
+        h.film_develop_n(L.data_ptr(), n_pix, int(spp), C, img.data_ptr())
         return img
 
     def film_backward(self, scene: Scene, grad_image: torch.Tensor, spp: int) -> torch.Tensor:
         if not self._aovs:
             return super().film_backward(scene, grad_image, spp)
         h, dev = self._bind(scene)
-        if grad_image.shape[-1] != 5:
-            raise ValueError(f"film_backward: with aovs the image gradient must have 5 channels, got {tuple(grad_image.shape)}")
-        grad_image = grad_image.contiguous().view(-1, 5)
+        C = self.channels
+        if grad_image.shape[-1] != C:
+            raise ValueError(f"film_backward: with aovs the image gradient must have {C} channels, got {tuple(grad_image.shape)}")
+        grad_image = grad_image.contiguous().view(-1, C)
         _check(grad_image, None, dev, "grad_image")
         n_pix = grad_image.shape[0]
-        dL = torch.empty((n_pix * spp, 5), dtype=torch.float32, device=dev)
-        h.film_backward_n(grad_image.data_ptr(), n_pix, int(spp), 5, dL.data_ptr())
+        dL = torch.empty((n_pix * spp, C), dtype=torch.float32, device=dev)
+        h.film_backward_n(grad_image.data_ptr(), n_pix, int(spp), C, dL.data_ptr())
         return dL
 
     def develop_loss(self, *args, **kwargs):
@@ -708,31 +720,33 @@ class NeRFIntegrator(_DeviceIntegrator):
         return dL, True, None
 
     def _sample_aov(self, mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents):
-        """sample() with aovs: the drt_nerf_render_*_aov calls, five channels [r, g, b, opacity, depth] (the checks of sample() are done)."""
+        """sample() with aovs: the drt_nerf_render_*_aov calls, five channels [r, g, b, opacity, depth], or - with distortion - the
+        drt_nerf_render_*_dist calls, six (the checks of sample() are done)."""
         props, off, spp, seed = self._nerf_props(), int(ray.ray_offset), int(ray.spp), sampler.seed_value
+        C = self.channels
+        primal, backward, forward = ((h.nerf_render_primal_dist, h.nerf_render_backward_dist, h.nerf_render_forward_dist) if self._distortion
+                                     else (h.nerf_render_primal_aov, h.nerf_render_backward_aov, h.nerf_render_forward_aov))
         if mode == ADMode.Primal:
-            L = torch.empty((n, 5), dtype=torch.float32, device=dev)
-            h.nerf_render_primal_aov(props, em.data_ptr(), ro, rd, n, off, spp, seed, L.data_ptr())
+            L = torch.empty((n, C), dtype=torch.float32, device=dev)
+            primal(props, em.data_ptr(), ro, rd, n, off, spp, seed, L.data_ptr())
             return L, True, L
         if mode == ADMode.Backward:
             if δL is None or state_in is None or grads is None:
                 raise ValueError("sample(Backward) needs δL, state_in and grads")
-            _check(δL, (n, 5), dev, "δL")
-            _check(state_in, (n, 5), dev, "state_in")
+            _check(δL, (n, C), dev, "δL")
+            _check(state_in, (n, C), dev, "state_in")
             gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
             _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
             _check(ge, tuple(em.shape), dev, "grads[emission]")
-            h.nerf_render_backward_aov(props, em.data_ptr(), ro, rd, n, off, spp, seed, δL.data_ptr(), state_in.data_ptr(),
-                                       gs.data_ptr(), ge.data_ptr())
+            backward(props, em.data_ptr(), ro, rd, n, off, spp, seed, δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
             return None, True, None
-        dL = torch.empty((n, 5), dtype=torch.float32, device=dev)
-        h.nerf_render_forward_aov(props, em.data_ptr(), ro, rd, n, off, spp, seed, _ptr(tangents[SIGMA_T_KEY]),
-                                  _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
+        dL = torch.empty((n, C), dtype=torch.float32, device=dev)
+        forward(props, em.data_ptr(), ro, rd, n, off, spp, seed, _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
         return dL, True, None
 
     def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
-        """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] ([.., 5] with aovs) in place of the per-ray δL
+        """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] ([.., 5] with aovs, [.., 6] with distortion) in place of the per-ray δL
         (drt_nerf_render_backward_px)."""
         if grads.get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)
@@ -751,7 +765,8 @@ class NeRFIntegrator(_DeviceIntegrator):
         gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
         _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
         _check(ge, tuple(em.shape), dev, "grads[emission]")
-        call = h.nerf_render_backward_px_sh if self.sh_degree else h.nerf_render_backward_px_aov if self._aovs else h.nerf_render_backward_px
+        call = (h.nerf_render_backward_px_sh if self.sh_degree else h.nerf_render_backward_px_dist if self._distortion
+                else h.nerf_render_backward_px_aov if self._aovs else h.nerf_render_backward_px)
         call(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
              grad_image.data_ptr(), grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
 
@@ -774,6 +789,9 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
         if props.pop("sh_degree", 0):
             raise NotImplementedError("nerf+volpathsimple has no spherical-harmonic emission (sh_degree > 0): its one colour grid is "
                                       "the albedo too; use the 'nerf' integrator")
+        if props.pop("distortion", False):
+            raise NotImplementedError("nerf+volpathsimple has no distortion output (distortion=True): its fused pass returns the two "
+                                      "integrators' colours only; use the 'nerf' integrator")
         if props.pop("aovs", False):
             raise NotImplementedError("nerf+volpathsimple has no opacity / depth outputs (aovs=True): its fused pass returns the two "
                                       "integrators' colours only; use the 'nerf' integrator")

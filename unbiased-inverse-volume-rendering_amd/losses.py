@@ -11,6 +11,14 @@ def average(img, ref_img=None, shape=None):
     return img.sum() / img.numel()
 
 
+def distortion(img, ref_img=None, shape=None):
+    """The distortion regulariser of an image [..., 6] = [r, g, b, opacity, depth, distortion] rendered by a `nerf` integrator with
+    `aovs=True, distortion=True`: the mean of its sixth channel (world units of length).  No reference image takes part."""
+    if img.shape[-1] != 6:
+        raise ValueError(f"distortion: the image must have 6 channels [r, g, b, opacity, depth, distortion], got {tuple(img.shape)}")
+    return img[..., 5].mean()
+
+
 def l1(img, ref_img, shape=None):
     return (img - ref_img).abs().sum() / img.numel()
 

@@ -59,6 +59,9 @@ class OptimizationConfig:
     fused_loss: bool = False
     # opt-in: {parameter key: priors on that grid} (priors.py), added to the objective of every iteration; None: nothing extra runs
     priors: Optional[Dict[str, List[Prior]]] = None
+    # opt-in: weight of the distortion regulariser, the mean of the sixth image channel of a `nerf` integrator with `distortion=True`
+    # (losses.distortion), added to every iteration's loss; non-zero with an integrator without that output raises at start-up
+    distortion_weight: float = 0.0
 
     def __post_init__(self):
         self.upsample_at = set()
@@ -402,6 +405,9 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     gradient grids are summed with one all-reduce per backward; every rank then takes the identical
     optimizer step.
 
+    `opt_config.distortion_weight` (a `nerf` integrator with `aovs=True, distortion=True`): the run takes the five-channel references of an
+    `aovs` run, and the step's loss is loss(image[:, :5], ref) + distortion_weight x image[:, 5].mean(), both scaled to the rank's share.
+
     `opt_config.priors` {grid key: [Prior, ...]}: after the backward pass of every iteration each prior adds its gradient into that
     parameter's `.grad` (`priors.prior_value_and_grad_`: one kernel pass per prior, at the grid's current resolution, no host wait), and
     its value into the iteration's entry of the returned history, which then is the objective that is minimised - on the plain, the
@@ -455,6 +461,14 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     n_channels = 3 + len(integrator.aovs())                           # (a `nerf` integrator with aovs renders [r, g, b, opacity, depth])
     if opt_config.fused_loss and n_channels != 3:
         raise NotImplementedError("fused_loss=True with aovs: the loss-fused film is three-channel; use fused_loss=False")
+    # the distortion output has no reference image: such an integrator renders six channels and takes the FIVE-channel references of
+    # an aovs run; its sixth channel enters the loss through distortion_weight alone
+    has_distortion = "distortion" in integrator.aovs()
+    if opt_config.distortion_weight != 0.0 and not has_distortion:
+        raise ValueError(f"distortion_weight {opt_config.distortion_weight} needs an integrator with a distortion output "
+                         f"('nerf' with aovs=True, distortion=True); \"{int_config.name}\" renders {integrator.aovs() or 'colour only'}")
+    if has_distortion:
+        n_channels -= 1
     if ref_images is not None and ref_images.shape[-1] != n_channels and not (n_channels == 3 and ref_images.shape[-1] == 4):
         raise ValueError(f"ref_images have {ref_images.shape[-1]} channels, the integrator renders {n_channels}")
     keys = list(scene_config.param_keys)
@@ -588,7 +602,13 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
                 ref_values = ref_values[shard.pixel_indices(n_global, ref_values.device)]
         if not opt_config.fused_loss:
             # the losses normalise by the local entry count: scale to this rank's share of the global loss
-            loss_value = opt_config.loss(image, ref_values) * local_loss_scale(image.shape[0], n_global)
+            scale = local_loss_scale(image.shape[0], n_global)
+            if has_distortion:
+                loss_value = opt_config.loss(image[:, :n_channels], ref_values) * scale
+                if opt_config.distortion_weight != 0.0:
+                    loss_value = loss_value + opt_config.distortion_weight * _losses.distortion(image) * scale
+            else:
+                loss_value = opt_config.loss(image, ref_values) * scale
         loss_value.backward()                                          # dr.backward (:350)
         prior_value = None
         for k, ps in priors.items():                                   # (sharded: .grad is the all-reduced sum here; every rank adds the same)
