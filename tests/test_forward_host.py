@@ -91,3 +91,19 @@ def test_c_abi_forward_refuses_a_null_handle(uivr):
     assert b"handle" in lib.drt_last_error(None)
     assert lib.drt_nerf_render_forward(None, None, None, None, None, u64(4), u64(0), u32(1), u32(0), None, None, out) < 0
     assert b"handle" in lib.drt_last_error(None)
+
+
+@pytest.mark.parametrize("kind", ["", "_sh", "_aov", "_dist"])
+@pytest.mark.parametrize("call", ["primal", "backward", "backward_px", "forward"])
+def test_c_abi_nerf_calls_refuse_a_null_handle(uivr, call, kind):
+    """Each of the sixteen nerf entry points, called without a handle (an empty batch included), returns DRT_ERR_INVALID_ARGUMENT and
+    says why - before it looks at any other argument."""
+    from uivr_amd._native import library_path
+    lib = ctypes.CDLL(library_path())
+    lib.drt_last_error.restype = ctypes.c_char_p
+    u64, u32, i32 = ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32
+    own = {"primal": (None,), "backward": (None,) * 4, "backward_px": (None, u64(4), None, None, None), "forward": (None,) * 3}[call]
+    for n_rays in (4, 0):
+        head = (None, None, None) + ((i32(1),) if kind == "_sh" else ()) + (None, None, u64(n_rays), u64(0), u32(1), u32(0))
+        assert getattr(lib, f"drt_nerf_render_{call}{kind}")(*head, *own) == -1
+        assert b"null handle" in lib.drt_last_error(None)

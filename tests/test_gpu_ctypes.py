@@ -236,10 +236,30 @@ def test_raw_ctypes_misuse_is_refused_with_a_message_and_the_handle_lives_on(uiv
         bad("nerf without a config", lib.drt_nerf_render_primal(h, None, P(alb), None, None, C.c_uint64(n), C.c_uint64(0), C.c_uint32(spp), C.c_uint32(seed), P(L)), h)
         ncfg = (C.c_int32 * 4)(0, 8, 1, 0)
         bad("nerf without an emission grid", lib.drt_nerf_render_primal(h, C.byref(ncfg), None, None, None, C.c_uint64(n), C.c_uint64(0), C.c_uint32(spp), C.c_uint32(seed), P(L)), h)
+        # the plain nerf calls, one fault each: the code and the message (two of them carry no function name)
+        def nerf_bad(what, rc, fragment):
+            assert rc == -1, f"{what}: {rc}"                                     # DRT_ERR_INVALID_ARGUMENT
+            assert fragment in lib.drt_last_error(h), f"{what}: {lib.drt_last_error(h)}"
+            refused.append(what)
+
+        njob = lambda n_=n: (None, None, C.c_uint64(n_), C.c_uint64(0), C.c_uint32(spp), C.c_uint32(seed))
+        gimg = torch.zeros((12 * 9, 3), dtype=torch.float32, device=gpu)
+        nerf_bad("nerf primal without L_out", lib.drt_nerf_render_primal(h, C.byref(ncfg), P(alb), *njob(), None), b"null L_out")
+        assert not lib.drt_last_error(h).startswith(b"drt_")
+        nerf_bad("nerf backward without dL", lib.drt_nerf_render_backward(h, C.byref(ncfg), P(alb), *njob(), None, P(L), P(gs), P(ga)),
+                 b"drt_nerf_render_backward: null dL / L_in / gradient buffer")
+        nerf_bad("nerf backward_px with n_pixels off by one",
+                 lib.drt_nerf_render_backward_px(h, C.byref(ncfg), P(alb), *njob(), P(gimg), C.c_uint64(12 * 9 - 1), P(L), P(gs), P(ga)),
+                 b"drt_nerf_render_backward_px: n_rays (432) must equal n_pixels * spp (107 * 4)")
+        nerf_bad("nerf forward without dL_out", lib.drt_nerf_render_forward(h, C.byref(ncfg), P(alb), *njob(), None, None, None),
+                 b"drt_nerf_render_forward: null dL_out")
+        nerf_bad("nerf backward_px with no rays and no config",
+                 lib.drt_nerf_render_backward_px(h, None, P(alb), *njob(0), P(gimg), C.c_uint64(12 * 9), P(L), P(gs), P(ga)),
+                 b"drt_nerf_render_backward_px: null config / emission grid")
         bad("film_develop with spp 0", lib.drt_film_develop(h, P(L), C.c_uint64(12 * 9), C.c_uint32(0), P(L)), h)
         bad("counters without an output", lib.drt_get_counters(h, None), h)
         bad("interleave with a stride below the chunk", lib.drt_set_ray_interleave(h, C.c_uint64(64), C.c_uint64(32)), h)
-        assert len(refused) == 38, refused
+        assert len(refused) == 43, refused
         # ... and the handle still does its work
         assert primal() == 0, lib.drt_last_error(h)
         assert lib.drt_synchronize(h) == 0

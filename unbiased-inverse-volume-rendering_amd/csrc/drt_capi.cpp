@@ -771,16 +771,6 @@ int timed_reduce(drt_handle h, const drt::Params &P, const drt::DeferredPlan &D,
     return DRT_OK;
 }
 
-int timed_nerf(drt_handle h, int which, const drt::Params &P, bool adjoint, hipStream_t st = nullptr)
-{
-    if (!st) st = h->stream;
-    TimedSpan span;
-    DRT_HIP_CHECK(h, span.begin(h, st));
-    DRT_HIP_CHECK(h, drt::launch_nerf(P, adjoint, h->counting, st));
-    DRT_HIP_CHECK(h, span.end(which));
-    return DRT_OK;
-}
-
 int timed_untile(drt_handle h, const drt::Params &P)
 {
     TimedSpan span;
@@ -1482,81 +1472,6 @@ int drt_render_backward_phase(drt_handle h, const float *rays_o, const float *ra
     return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo, grad_phase_g);
 }
 
-static int nerf_fill(drt_handle h, drt::Params &P, const drt_nerf_config *cfg, const float *emission, bool fused_half = false)
-{
-    P.nerf_fused_half = fused_half ? 1 : 0;
-    if (!cfg || !emission) return fail(h, DRT_ERR_INVALID_ARGUMENT, "nerf: null config / emission grid");
-    if (cfg->queries_per_ray < 2) return fail(h, DRT_ERR_INVALID_ARGUMENT, "queries_per_ray must be >= 2");
-    P.emission = emission; P.nerf_queries = cfg->queries_per_ray; P.nerf_jitter = cfg->jittering_enabled ? 1 : 0;
-    P.nerf_relu = cfg->activation_relu ? 1 : 0; P.hide_emitters = cfg->hide_emitters ? 1 : 0;
-    return DRT_OK;
-}
-
-static int ensure_grid4(drt_handle h, drt::Params &P, const float *rgb);
-
-// The nerf adjoint of a filled job.  Sensor rays: drt_nerf_tile.hip (a workgroup per pixel tile, the splats pre-reduced in an LDS window and
-// flushed with atomics into the caller's grids: no records, no sub-batches); explicit ray batches - the optimisation loop's random pixels -
-// and test hook 512: the record path (nerf_kernel + drt_deferred.hip).  g4: lookups from the four-channel copy (the fused pass).
-static int nerf_backward(drt_handle h, drt::Params &P, const drt_nerf_config *cfg, bool g4, hipStream_t st = nullptr)
-{
-    if (!st) st = h->stream;
-    if (drt::nerf_tile_supported(P) && !dbg(h->debug_flags, kHookNerfRecordPath))
-        return nerf_adjoint_pass(h, st, 32, [&](uint32_t *bounds) { return drt::launch_nerf_tile_adjoint(P, g4, h->counting, bounds, st); });
-    const uint32_t q = (uint32_t) cfg->queries_per_ray;          // at most one splat per query and plane
-    return run_backward(h, P, q, q, [&](drt::Params &Q) { return timed_nerf(h, 1, Q, true); });
-}
-
-static int nerf_primal(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                       const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                       float *L_out, bool fused_half, hipStream_t st = nullptr)
-{
-    if (h && n_rays == 0) return DRT_OK;
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
-    if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "null L_out");
-    DeviceGuard g(h->device);
-    drt::Params P;
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    DRT_TRY(nerf_fill(h, P, cfg, emission, fused_half));
-    P.L_out = L_out;
-    if (!fused_half) h->pcache_sig.valid = false;
-    return timed_nerf(h, 0, P, false, st);
-}
-
-int drt_nerf_render_primal(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                           const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                           float *L_out)
-{
-    return nerf_primal(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_out, false);
-}
-
-// the nerf adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given
-static int nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
-                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *dL_pix,
-                                const float *L_in, float *grad_sigma_t, float *grad_emission)
-{
-    DeviceGuard g(h->device);
-    drt::Params P;
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    DRT_TRY(nerf_fill(h, P, cfg, emission));
-    P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_emission;
-    // (sensor rays: sigma_t and the emission of a query from ONE 256-byte block of a four-channel copy made for this call)
-    const bool tile = drt::nerf_tile_supported(P) && !dbg(h->debug_flags, kHookNerfRecordPath);
-    const bool g4 = tile && ensure_grid4(h, P, emission) == DRT_OK;   // (no memory / a grid beyond the copy's index range: the separate lookups)
-    if (tile && !g4) (void) hipGetLastError();
-    return nerf_backward(h, P, cfg, g4);
-}
-
-int drt_nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                             const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                             const float *dL, const float *L_in, float *grad_sigma_t, float *grad_emission)
-{
-    if (h && n_rays == 0) return DRT_OK;
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
-    if (!dL || !L_in || !grad_sigma_t || !grad_emission)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward: null dL / L_in / gradient buffer");
-    return nerf_render_backward(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_emission);
-}
-
 // ---- forward mode: one launch over the job's rays, dL_out written once per ray.  No sub-batches (nothing is recorded), no path cache, no
 // ray schedule from a primal pass (the forward kernels finish every path on its own lane; an order would only be a schedule anyway)
 static void forward_params(drt::Params &P, const float *t_sigma, const float *t_colour, float *dL_out)
@@ -1606,22 +1521,6 @@ int drt_render_forward_phase(drt_handle h, const float *rays_o, const float *ray
     return render_forward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_in, t_sigma_t, t_albedo, dL_out, t_phase_g);
 }
 
-int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                            const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                            const float *t_sigma_t, const float *t_emission, float *dL_out)
-{
-    if (h && n_rays == 0) return DRT_OK;
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
-    if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward: null dL_out");
-    DeviceGuard g(h->device);
-    drt::Params P;
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    DRT_TRY(nerf_fill(h, P, cfg, emission));
-    forward_params(P, t_sigma_t, t_emission, dL_out);
-    DRT_HIP_CHECK(h, drt::launch_nerf_fwd(P, h->stream));
-    return DRT_OK;
-}
-
 // ---- nerf + volpathsimple over one set of grids (BASELINE config 5): two dense passes on two streams, see drt_fused_render_* below ------------
 // the interleaved four-channel apron-brick copy [sigma_t, r, g, b] (eval4): (re)built when the parameter grids changed since the last copy
 // `rgb`: the colour grid of the copy - the medium's albedo (the fused pass: the copy is kept until the parameters change) or the caller's emission
@@ -1646,7 +1545,291 @@ static int ensure_grid4(drt_handle h, drt::Params &P, const float *rgb)
     return DRT_OK;
 }
 
-// The fused pass = the two integrators over the SAME rays and the same four grids, each on its own copy of the sampler stream (round 5: as two
+// ---- the nerf integrator: every output kind (drt::NerfOut) through one job set-up and three bodies (DESIGN.md "Nerf outputs as one enum") --------
+// What differs between the kinds on the host, and nothing else: one row per kind.
+struct NerfVariant {
+    drt::NerfOut kind;
+    const char *grid;            // what the messages call the colour grid
+    const char *own_lattice;     // why a colour grid on its own lattice is refused (DRT_ERR_UNSUPPORTED); nullptr: the kind has such kernels
+    const char *kernels;         // whose kernels lack the paths of the routing test hooks, which the adjoint then refuses; nullptr: it honours them
+    bool named;                  // the null-config and null-L_out messages carry the call's name (the plain calls' predate that convention)
+    bool counts;                 // drt_get_counters counts the call: the plain kernels' counters, the SH window's phases (else: Params::counters cleared)
+    bool four_channel;           // the gradients are [sigma_t, r, g, b]: the adjoint tries the four-channel copy, and explicit rays take the record
+                                 // streams (which are four-channel); else separate lookups, and explicit rays splat with per-lane atomics
+    bool t_max;                  // the window kernel wants a bound of a query's distance from the sensor
+    size_t bounds_bytes;         // device scratch of the window kernel's bounds reduction (drt_launch.h)
+};
+static constexpr NerfVariant kNerfPlain = { drt::NerfOut::kPlain, "emission", nullptr, nullptr, false, true, true, false, 32 };
+static constexpr NerfVariant kNerfSh = { drt::NerfOut::kSh, "sh", "own-lattice SH is not supported", "SH", true, true, false, false, 32 };
+static constexpr NerfVariant kNerfAov = { drt::NerfOut::kAov, "emission", "own-lattice opacity / depth outputs are not supported",
+                                          "opacity / depth", true, false, true, true, 64 };
+static constexpr NerfVariant kNerfDist = { drt::NerfOut::kDist, "emission", "own-lattice opacity / depth / distortion outputs are not supported",
+                                           "distortion", true, false, true, true, 64 };
+
+struct NerfRays { const float *o, *d; uint64_t n, offset; uint32_t spp, seed; };
+enum : unsigned {
+    kNerfAdjoint = 1,            // the job is an adjoint: the routing test hooks matter
+    kNerfFusedHalf = 2,          // the nerf half of drt_fused_render_*: its rays are counted by the other half, the path cache is that half's
+    kNerfCheckEmpty = 4,         // drt_nerf_render_backward_px only, kept for compatibility: it always checked its arguments before it looked at
+                                 // n_rays, so an empty batch is refused (n_rays != n_pixels * spp at the latest), and named itself in the null-config message
+};
+namespace { int check_px(drt_handle h, const char *what, uint64_t n_rays, uint32_t spp, const float *grad_image, uint64_t n_pixels); }
+
+// The job set-up of every nerf call: the checks, the job, and - sh_degree given: the SH calls - the interleaved voxel copy of this call's grids;
+// `body(P, S)` then checks the call's own buffers and launches.  `what`: the call's name in its messages
+extern "C++" template <class Body>
+static int nerf_job(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid, const int32_t *sh_degree,
+                    const NerfRays &R, unsigned flags, Body body)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    if (R.n == 0 && !(flags & kNerfCheckEmpty)) return DRT_OK;         /* empty batch: nothing to enqueue */
+    DeviceGuard g(h->device);
+    DRT_TRY(check_job(h, R.o, R.d, R.n, R.offset, R.spp, false));
+    if (sh_degree && *sh_degree != 1 && *sh_degree != 2)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: sh_degree must be 1 or 2, got %d", what, (int) *sh_degree);
+    if (!cfg || !grid)
+        return v.named || (flags & kNerfCheckEmpty) ? fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null config / %s grid", what, v.grid)
+                                                    : fail(h, DRT_ERR_INVALID_ARGUMENT, "nerf: null config / emission grid");
+    if (h->base.colour_own && v.own_lattice)
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the %s grid must share sigma_t's lattice (drt_set_colour_resolution gave the colour grids "
+                                            "their own: %s)", what, v.grid, v.own_lattice);
+    // hooks that route the plain nerf adjoint elsewhere (record path, atomic gradients into the apron scratch, per-lane / no gradient atomics)
+    constexpr uint32_t kUnhonoured = drt::kHookNerfRecordPath | drt::kHookAtomicGradients | drt::kHookNoGradAtomics | drt::kHookPerLaneAtomics;
+    if ((flags & kNerfAdjoint) && v.kernels && dbg(h->debug_flags, kUnhonoured))
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: debug flags 0x%x route the nerf adjoint through paths the %s kernels do not have", what,
+                    (unsigned) (h->debug_flags & kUnhonoured), v.kernels);
+    drt::Params P;
+    drt::NerfSh S = { nullptr, 0 };
+    fill_job(h, P, R.o, R.d, R.n, R.offset, R.spp, R.seed);
+    P.nerf_fused_half = (flags & kNerfFusedHalf) ? 1 : 0;
+    if (cfg->queries_per_ray < 2) return fail(h, DRT_ERR_INVALID_ARGUMENT, "queries_per_ray must be >= 2");
+    P.emission = grid; P.nerf_queries = cfg->queries_per_ray; P.nerf_jitter = cfg->jittering_enabled ? 1 : 0;
+    P.nerf_relu = cfg->activation_relu ? 1 : 0; P.hide_emitters = cfg->hide_emitters ? 1 : 0;
+    if (sh_degree) {
+        S.K = (*sh_degree + 1) * (*sh_degree + 1);
+        const size_t nv = (size_t) P.rx * P.ry * P.rz;
+        if (nv > 0x7fffffffull) return fail(h, DRT_ERR_UNSUPPORTED, "%s: grid too large for the interleaved voxel copy", what);
+        DRT_TRY(h->sh_vox.grow(h, nv * drt::sh_vox_floats(S.K) * sizeof(float), kMust));
+        DRT_HIP_CHECK(h, drt::launch_sh_interleave(P.sigma_t, grid, S.K, h->sh_vox.as<float4>(), nv, h->stream));
+        S.vox = h->sh_vox.as<float4>();
+    }
+    if (!v.counts) P.counters = nullptr;
+    return body(P, S);
+}
+
+// one ray per lane, timed: the primal (slot 0) and the record route's adjoint tracer (slot 1)
+static int nerf_lanes(drt_handle h, int which, const NerfVariant &v, const drt::Params &P, const drt::NerfSh &S, bool adjoint, hipStream_t st)
+{
+    TimedSpan span;
+    DRT_HIP_CHECK(h, span.begin(h, st));
+    DRT_HIP_CHECK(h, drt::launch_nerf(P, v.kind, S, adjoint, P.counters != nullptr, st));
+    DRT_HIP_CHECK(h, span.end(which));
+    return DRT_OK;
+}
+
+// st (the fused pass): the stream of the launch, the handle's otherwise
+static int nerf_run_primal(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid,
+                           const int32_t *sh_degree, const NerfRays &R, float *L_out, unsigned flags = 0, hipStream_t st = nullptr)
+{
+    return nerf_job(h, what, v, cfg, grid, sh_degree, R, flags, [&](drt::Params &P, const drt::NerfSh &S) {
+        if (!L_out) return v.named ? fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null L_out", what) : fail(h, DRT_ERR_INVALID_ARGUMENT, "null L_out");
+        P.L_out = L_out;
+        if (!(flags & kNerfFusedHalf)) h->pcache_sig.valid = false;
+        return nerf_lanes(h, 0, v, P, S, false, st ? st : h->stream);
+    });
+}
+
+// The route of a filled adjoint job.  tile: sensor rays go through the window kernel (a workgroup per pixel tile, the splats pre-reduced in an LDS
+// window and flushed with atomics into the caller's grids: no records, no sub-batches) unless test hook kHookNerfRecordPath sends them the way of
+// explicit ray batches - the optimisation loop's random pixels.  g4: sigma_t and the emission of a query from ONE 256-byte block of the
+// four-channel copy, made for this call or - emission = the medium's albedo: the fused pass - kept until the parameters change (no memory / a
+// grid beyond the copy's index range: the separate lookups)
+struct NerfRoute { bool tile, g4; };
+static NerfRoute nerf_adjoint_route(drt_handle h, const NerfVariant &v, drt::Params &P)
+{
+    NerfRoute r;
+    r.tile = drt::nerf_tile_supported(P) && !dbg(h->debug_flags, kHookNerfRecordPath);
+    r.g4 = r.tile && v.four_channel && ensure_grid4(h, P, P.emission) == DRT_OK;
+    if (r.tile && v.four_channel && !r.g4) (void) hipGetLastError();
+    return r;
+}
+
+// ... and its launch on `st` (the record route: always the handle's stream, whose record slots it shares with every other adjoint)
+static int nerf_adjoint_launch(drt_handle h, const NerfVariant &v, drt::Params &P, const drt::NerfSh &S, NerfRoute r, hipStream_t st)
+{
+    if (!r.tile && v.four_channel) {
+        const uint32_t q = (uint32_t) P.nerf_queries;            // at most one splat per query and plane
+        return run_backward(h, P, q, q, [&](drt::Params &Q) { return nerf_lanes(h, 1, v, Q, S, true, h->stream); });
+    }
+    float t_max = 0.0f;
+    if (r.tile && v.t_max) {
+        // a bound of t_in + t_b, a query's distance from the sensor's origin: the origin's distance to the box centre plus the half diagonal
+        // (the spawn offset of the march's origin is 1e-4 of that: the margin covers it)
+        double c2 = 0.0, d2 = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            const double c = 0.5 * ((double) P.bmin[k] + (double) P.bmax[k]) - (double) P.cam_o[k], e = 0.5 * ((double) P.bmax[k] - (double) P.bmin[k]);
+            c2 += c * c; d2 += e * e;
+        }
+        t_max = (float) ((std::sqrt(c2) + std::sqrt(d2)) * 1.01);
+    }
+    return nerf_adjoint_pass(h, st, r.tile ? v.bounds_bytes : 0, [&](uint32_t *bounds) {
+        return r.tile ? drt::launch_nerf_tile_adjoint(P, v.kind, S, r.g4, P.counters != nullptr, bounds, t_max, st)
+                      : drt::launch_nerf(P, v.kind, S, true, P.counters != nullptr, st);
+    });
+}
+
+// exactly one of dL (per ray) and grad_image with n_pixels (per pixel: the *_backward_px calls) is given
+static int nerf_run_adjoint(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid,
+                            const int32_t *sh_degree, const NerfRays &R, const float *dL, const float *grad_image, const uint64_t *n_pixels,
+                            const float *L_in, float *grad_sigma_t, float *grad_colour, unsigned flags = 0)
+{
+    return nerf_job(h, what, v, cfg, grid, sh_degree, R, flags | kNerfAdjoint, [&](drt::Params &P, const drt::NerfSh &S) {
+        if ((!n_pixels && !dL) || !L_in || !grad_sigma_t || !grad_colour)
+            return fail(h, DRT_ERR_INVALID_ARGUMENT, n_pixels ? "%s: null L_in / gradient buffer" : "%s: null dL / L_in / gradient buffer", what);
+        if (n_pixels) DRT_TRY(check_px(h, what, R.n, R.spp, grad_image, *n_pixels));
+        P.dL = n_pixels ? nullptr : dL; P.dL_pix = n_pixels ? grad_image : nullptr;
+        P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_colour;
+        return nerf_adjoint_launch(h, v, P, S, nerf_adjoint_route(h, v, P), h->stream);
+    });
+}
+
+// forward mode: one launch, untimed
+static int nerf_run_forward(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid,
+                            const int32_t *sh_degree, const NerfRays &R, const float *t_sigma_t, const float *t_colour, float *dL_out)
+{
+    return nerf_job(h, what, v, cfg, grid, sh_degree, R, 0, [&](drt::Params &P, const drt::NerfSh &S) {
+        if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null dL_out", what);
+        forward_params(P, t_sigma_t, t_colour, dL_out);
+        DRT_HIP_CHECK(h, drt::launch_nerf_fwd(P, v.kind, S, h->stream));
+        return (int) DRT_OK;
+    });
+}
+
+// the sixteen calls: kind x (primal, backward, backward_px, forward)
+int drt_nerf_render_primal(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                           uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
+{
+    return nerf_run_primal(h, "drt_nerf_render_primal", kNerfPlain, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, L_out);
+}
+
+int drt_nerf_render_backward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                             uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
+                             float *grad_sigma_t, float *grad_emission)
+{
+    return nerf_run_adjoint(h, "drt_nerf_render_backward", kNerfPlain, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            dL, nullptr, nullptr, L_in, grad_sigma_t, grad_emission);
+}
+
+int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
+                                const float *L_in, float *grad_sigma_t, float *grad_emission)
+{
+    return nerf_run_adjoint(h, "drt_nerf_render_backward_px", kNerfPlain, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            nullptr, grad_image, &n_pixels, L_in, grad_sigma_t, grad_emission, kNerfCheckEmpty);
+}
+
+int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                            uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t, const float *t_emission,
+                            float *dL_out)
+{
+    return nerf_run_forward(h, "drt_nerf_render_forward", kNerfPlain, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            t_sigma_t, t_emission, dL_out);
+}
+
+int drt_nerf_render_primal_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                              const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
+{
+    return nerf_run_primal(h, "drt_nerf_render_primal_sh", kNerfSh, cfg, sh, &sh_degree, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, L_out);
+}
+
+int drt_nerf_render_backward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                                const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL,
+                                const float *L_in, float *grad_sigma_t, float *grad_sh)
+{
+    return nerf_run_adjoint(h, "drt_nerf_render_backward_sh", kNerfSh, cfg, sh, &sh_degree, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            dL, nullptr, nullptr, L_in, grad_sigma_t, grad_sh);
+}
+
+int drt_nerf_render_backward_px_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                                   const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                   const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t, float *grad_sh)
+{
+    return nerf_run_adjoint(h, "drt_nerf_render_backward_px_sh", kNerfSh, cfg, sh, &sh_degree, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            nullptr, grad_image, &n_pixels, L_in, grad_sigma_t, grad_sh);
+}
+
+int drt_nerf_render_forward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
+                               const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                               const float *t_sigma_t, const float *t_sh, float *dL_out)
+{
+    return nerf_run_forward(h, "drt_nerf_render_forward_sh", kNerfSh, cfg, sh, &sh_degree, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            t_sigma_t, t_sh, dL_out);
+}
+
+// opacity and depth outputs: five interleaved floats [r, g, b, A, D] per ray / pixel; with the distortion output six, [.., Z]
+int drt_nerf_render_primal_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                               uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
+{
+    return nerf_run_primal(h, "drt_nerf_render_primal_aov", kNerfAov, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, L_out);
+}
+
+int drt_nerf_render_backward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
+                                 float *grad_sigma_t, float *grad_emission)
+{
+    return nerf_run_adjoint(h, "drt_nerf_render_backward_aov", kNerfAov, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            dL, nullptr, nullptr, L_in, grad_sigma_t, grad_emission);
+}
+
+int drt_nerf_render_backward_px_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                                    const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                    const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
+                                    float *grad_emission)
+{
+    return nerf_run_adjoint(h, "drt_nerf_render_backward_px_aov", kNerfAov, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            nullptr, grad_image, &n_pixels, L_in, grad_sigma_t, grad_emission);
+}
+
+int drt_nerf_render_forward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
+                                const float *t_emission, float *dL_out)
+{
+    return nerf_run_forward(h, "drt_nerf_render_forward_aov", kNerfAov, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            t_sigma_t, t_emission, dL_out);
+}
+
+int drt_nerf_render_primal_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
+{
+    return nerf_run_primal(h, "drt_nerf_render_primal_dist", kNerfDist, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, L_out);
+}
+
+int drt_nerf_render_backward_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                  uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
+                                  float *grad_sigma_t, float *grad_emission)
+{
+    return nerf_run_adjoint(h, "drt_nerf_render_backward_dist", kNerfDist, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            dL, nullptr, nullptr, L_in, grad_sigma_t, grad_emission);
+}
+
+int drt_nerf_render_backward_px_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
+                                     const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                                     const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
+                                     float *grad_emission)
+{
+    return nerf_run_adjoint(h, "drt_nerf_render_backward_px_dist", kNerfDist, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            nullptr, grad_image, &n_pixels, L_in, grad_sigma_t, grad_emission);
+}
+
+int drt_nerf_render_forward_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
+                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
+                                 const float *t_emission, float *dL_out)
+{
+    return nerf_run_forward(h, "drt_nerf_render_forward_dist", kNerfDist, cfg, emission, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                            t_sigma_t, t_emission, dL_out);
+}
+
+// The fused pass =the two integrators over the SAME rays and the same four grids, each on its own copy of the sampler stream (round 5: as two
 // dense passes - rounds 3/4 ran both halves in one kernel, drt_fused*.hip, whose nerf half emitted one gradient record per query: 907 M
 // records per step of config 5, 25 of the adjoint pass's 46 ms in the reduction; and whose volpathsimple half ran one path per lane at a third
 // of the lanes).  Now: the nerf march as the stand-alone integrator with emission = the medium's albedo grid (primal: nerf_kernel; adjoint for
@@ -1683,7 +1866,8 @@ int drt_fused_render_primal(drt_handle h, const drt_nerf_config *cfg, const floa
         DeviceGuard g(h->device);
         DRT_TRY(fused_fork(h));
     }
-    int rc = nerf_primal(h, cfg, h->base.albedo, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_nerf_out, true, h->nerf_stream);
+    int rc = nerf_run_primal(h, "drt_fused_render_primal", kNerfPlain, cfg, h->base.albedo, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                             L_nerf_out, kNerfFusedHalf, h->nerf_stream);
     int rc2 = rc ? rc : drt_render_primal(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_drt_out);   // (its path cache serves the backward pass)
     {
         DeviceGuard g(h->device);
@@ -1703,32 +1887,23 @@ int drt_fused_render_backward(drt_handle h, const drt_nerf_config *cfg, const fl
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_fused_render_backward: null dL / L_in / gradient buffer");
     TimedSpan whole;
     size_t n_pass = 0;
-    int rc = DRT_OK;
-    {
-        DeviceGuard g(h->device);
-        drt::Params P;
-        fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-        DRT_TRY(nerf_fill(h, P, cfg, h->base.albedo, true));
+    // the nerf half: the plain adjoint's job, route and launch (the four-channel copy is the medium's own, kept until the parameters change)
+    int rc = nerf_job(h, "drt_fused_render_backward", kNerfPlain, cfg, h->base.albedo, nullptr, { rays_o, rays_d, n_rays, ray_offset, spp, seed },
+                      kNerfAdjoint | kNerfFusedHalf, [&](drt::Params &P, const drt::NerfSh &S) {
         P.dL = dL_nerf; P.L_in = L_nerf_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_rgb;
-        const bool tile = drt::nerf_tile_supported(P) && !dbg(h->debug_flags, kHookNerfRecordPath);
-        const bool g4 = tile && ensure_grid4(h, P, nullptr) == DRT_OK;   // (sigma_t and the colour of a query from ONE 256-byte block; else: separate lookups)
-        if (tile && !g4) (void) hipGetLastError();
+        const NerfRoute r = nerf_adjoint_route(h, kNerfPlain, P);
         DRT_HIP_CHECK(h, whole.begin(h, h->stream));
         n_pass = h->timed[3].size();
         // the tile kernel (one workgroup of 16 waves and 139 KiB of LDS per CU) leaves room for the wave-cooperative tracer's workgroups beside it;
         // the record path of explicit ray batches shares the handle's record streams with the volpathsimple half: one after the other
-        bool forked = false;
-        if (tile) {
-            rc = fused_fork(h);
-            forked = rc == DRT_OK;
-            if (!rc) rc = nerf_backward(h, P, cfg, g4, h->nerf_stream);
-        } else rc = nerf_backward(h, P, cfg, false);
-        if (rc) {                                                    // (nothing of the other stream may outlive the call)
-            if (forked) (void) fused_join(h);
-            return rc;
-        }
         // (launched first: its workgroups need almost a whole CU's LDS, which the other half's many small workgroups would not leave free)
-    }
+        int rn = r.tile ? fused_fork(h) : (int) DRT_OK;
+        const bool forked = r.tile && rn == DRT_OK;
+        if (!rn) rn = nerf_adjoint_launch(h, kNerfPlain, P, S, r, r.tile ? h->nerf_stream : h->stream);
+        if (rn && forked) (void) fused_join(h);                      // (nothing of the other stream may outlive the call)
+        return rn;
+    });
+    if (rc) return rc;
     rc = drt_render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL_drt, L_drt_in, grad_sigma_t, grad_rgb);
     {
         DeviceGuard g(h->device);
@@ -2075,283 +2250,6 @@ int drt_render_backward_px_phase(drt_handle h, const float *rays_o, const float 
     DRT_TRY(check_px(h, "drt_render_backward_px_phase", n_rays, spp, grad_image, n_pixels));
     return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo,
                            grad_phase_g);
-}
-
-int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                                const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                                const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
-                                float *grad_emission)
-{
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
-    if (!cfg || !emission) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px: null config / emission grid");
-    if (cfg->queries_per_ray < 2) return fail(h, DRT_ERR_INVALID_ARGUMENT, "queries_per_ray must be >= 2");
-    if (!L_in || !grad_sigma_t || !grad_emission)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px: null L_in / gradient buffer");
-    DRT_TRY(check_px(h, "drt_nerf_render_backward_px", n_rays, spp, grad_image, n_pixels));
-    return nerf_render_backward(h, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t,
-                                grad_emission);
-}
-
-// ---- the nerf variants: spherical-harmonic emission (drt_nerf_sh.hip) and opacity / depth outputs (drt_nerf_aov.hip) ---------------------------
-// what the messages of a variant's calls name
-struct NerfVariant { const char *grid, *own_lattice, *kernels; };
-static constexpr NerfVariant kNerfSh = { "sh", "own-lattice SH is not supported", "SH" };
-static constexpr NerfVariant kNerfAov = { "emission", "own-lattice opacity / depth outputs are not supported", "opacity / depth" };
-
-// What the eight *_sh / *_aov calls share: the checks, the job, and - sh_degree given: the SH calls - the interleaved voxel copy of this call's
-// grids; `body(P, S)` then checks the call's own buffers and launches.  Neither variant has own-lattice colour grids, nor kernels for the test
-// hooks that route the plain nerf adjoint elsewhere (record path, atomic gradients into the apron scratch, per-lane / no gradient atomics): refused
-extern "C++" template <class Body>
-static int nerf_variant_call(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid,
-                             const int32_t *sh_degree, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
-                             uint32_t spp, uint32_t seed, bool adjoint, Body body)
-{
-    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (n_rays == 0) return DRT_OK;         /* empty batch: nothing to enqueue (as the plain calls) */
-    DeviceGuard g(h->device);
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false));
-    if (sh_degree && *sh_degree != 1 && *sh_degree != 2)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: sh_degree must be 1 or 2, got %d", what, (int) *sh_degree);
-    if (!cfg || !grid) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null config / %s grid", what, v.grid);
-    if (h->base.colour_own)
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the %s grid must share sigma_t's lattice (drt_set_colour_resolution gave the colour grids "
-                                            "their own: %s)", what, v.grid, v.own_lattice);
-    constexpr uint32_t kUnhonoured = drt::kHookNerfRecordPath | drt::kHookAtomicGradients | drt::kHookNoGradAtomics | drt::kHookPerLaneAtomics;
-    if (adjoint && dbg(h->debug_flags, kUnhonoured))
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: debug flags 0x%x route the nerf adjoint through paths the %s kernels do not have", what,
-                    (unsigned) (h->debug_flags & kUnhonoured), v.kernels);
-    drt::Params P;
-    drt::NerfSh S = { nullptr, 0 };
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    DRT_TRY(nerf_fill(h, P, cfg, grid));
-    if (sh_degree) {
-        S.K = (*sh_degree + 1) * (*sh_degree + 1);
-        const size_t nv = (size_t) P.rx * P.ry * P.rz;
-        if (nv > 0x7fffffffull) return fail(h, DRT_ERR_UNSUPPORTED, "%s: grid too large for the interleaved voxel copy", what);
-        DRT_TRY(h->sh_vox.grow(h, nv * drt::sh_vox_floats(S.K) * sizeof(float), kMust));
-        DRT_HIP_CHECK(h, drt::launch_sh_interleave(P.sigma_t, grid, S.K, h->sh_vox.as<float4>(), nv, h->stream));
-        S.vox = h->sh_vox.as<float4>();
-    } else P.counters = nullptr;            // (the opacity / depth calls count nothing; a counting SH launch counts its window phases)
-    return body(P, S);
-}
-
-int drt_nerf_render_primal_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
-                              const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
-{
-    return nerf_variant_call(h, "drt_nerf_render_primal_sh", kNerfSh, cfg, sh, &sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
-                             [&](drt::Params &P, const drt::NerfSh &S) {
-        if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_primal_sh: null L_out");
-        P.L_out = L_out;
-        h->pcache_sig.valid = false;
-        TimedSpan span;
-        DRT_HIP_CHECK(h, span.begin(h, h->stream));
-        DRT_HIP_CHECK(h, drt::launch_nerf_sh(P, S, false, h->stream));
-        DRT_HIP_CHECK(h, span.end(0));
-        return (int) DRT_OK;
-    });
-}
-
-// the SH adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given.  Sensor rays: the LDS-window kernel;
-// explicit ray batches: one ray per lane with fp32 atomics on the caller's grids (the untuned route)
-static int nerf_sh_backward(drt_handle h, drt::Params &P, const drt::NerfSh &S, const float *dL, const float *dL_pix, const float *L_in,
-                            float *grad_sigma_t, float *grad_sh)
-{
-    P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_sh;
-    const bool tile = drt::nerf_tile_supported(P);
-    return nerf_adjoint_pass(h, h->stream, tile ? 32 : 0, [&](uint32_t *bounds) {
-        return tile ? drt::launch_nerf_sh_tile_adjoint(P, S, bounds, h->stream) : drt::launch_nerf_sh(P, S, true, h->stream);
-    });
-}
-
-int drt_nerf_render_backward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
-                                const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL,
-                                const float *L_in, float *grad_sigma_t, float *grad_sh)
-{
-    return nerf_variant_call(h, "drt_nerf_render_backward_sh", kNerfSh, cfg, sh, &sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
-                             [&](drt::Params &P, const drt::NerfSh &S) {
-        if (!dL || !L_in || !grad_sigma_t || !grad_sh)
-            return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_sh: null dL / L_in / gradient buffer");
-        return nerf_sh_backward(h, P, S, dL, nullptr, L_in, grad_sigma_t, grad_sh);
-    });
-}
-
-int drt_nerf_render_backward_px_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
-                                   const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                                   const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t, float *grad_sh)
-{
-    return nerf_variant_call(h, "drt_nerf_render_backward_px_sh", kNerfSh, cfg, sh, &sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
-                             [&](drt::Params &P, const drt::NerfSh &S) {
-        if (!L_in || !grad_sigma_t || !grad_sh)
-            return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_backward_px_sh: null L_in / gradient buffer");
-        DRT_TRY(check_px(h, "drt_nerf_render_backward_px_sh", n_rays, spp, grad_image, n_pixels));
-        return nerf_sh_backward(h, P, S, nullptr, grad_image, L_in, grad_sigma_t, grad_sh);
-    });
-}
-
-int drt_nerf_render_forward_sh(drt_handle h, const drt_nerf_config *cfg, const float *sh, int32_t sh_degree, const float *rays_o,
-                               const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                               const float *t_sigma_t, const float *t_sh, float *dL_out)
-{
-    return nerf_variant_call(h, "drt_nerf_render_forward_sh", kNerfSh, cfg, sh, &sh_degree, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
-                             [&](drt::Params &P, const drt::NerfSh &S) {
-        if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_nerf_render_forward_sh: null dL_out");
-        forward_params(P, t_sigma_t, t_sh, dL_out);
-        DRT_HIP_CHECK(h, drt::launch_nerf_sh_fwd(P, S, h->stream));
-        return (int) DRT_OK;
-    });
-}
-
-// ---- opacity and depth outputs: five interleaved floats [r, g, b, A, D] per ray / pixel; with the distortion output (drt_nerf_dist.hip) six,
-// [.., Z].  The eight calls are four bodies: `dist` picks the unit whose kernels run, `what` is the call's name in its messages ----------------
-static constexpr NerfVariant kNerfDist = { "emission", "own-lattice opacity / depth / distortion outputs are not supported", "distortion" };
-
-static int nerf_aov_primal(drt_handle h, const char *what, bool dist, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                           const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
-{
-    return nerf_variant_call(h, what, dist ? kNerfDist : kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
-                             [&](drt::Params &P, const drt::NerfSh &) {
-        if (!L_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null L_out", what);
-        P.L_out = L_out;
-        h->pcache_sig.valid = false;
-        TimedSpan span;
-        DRT_HIP_CHECK(h, span.begin(h, h->stream));
-        DRT_HIP_CHECK(h, dist ? drt::launch_nerf_dist(P, false, h->stream) : drt::launch_nerf_aov(P, false, h->stream));
-        DRT_HIP_CHECK(h, span.end(0));
-        return (int) DRT_OK;
-    });
-}
-
-// the adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel) is given.  Sensor rays: the LDS-window kernel (lookups
-// from the four-channel copy where it can be made, as the plain call); explicit ray batches: the record path, as the plain call
-static int nerf_aov_backward(drt_handle h, bool dist, drt::Params &P, const float *emission, const float *dL, const float *dL_pix,
-                             const float *L_in, float *grad_sigma_t, float *grad_emission)
-{
-    P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_emission;
-    const bool tile = drt::nerf_tile_supported(P);
-    const bool g4 = tile && ensure_grid4(h, P, emission) == DRT_OK;   // (no memory / a grid beyond the copy's index range: the separate lookups)
-    if (tile && !g4) (void) hipGetLastError();
-    if (tile) {
-        // a bound of t_in + t_b, a query's distance from the sensor's origin: the origin's distance to the box centre plus the half diagonal
-        // (the spawn offset of the march's origin is 1e-4 of that: the margin covers it)
-        double c2 = 0.0, d2 = 0.0;
-        for (int k = 0; k < 3; ++k) {
-            const double c = 0.5 * ((double) P.bmin[k] + (double) P.bmax[k]) - (double) P.cam_o[k], e = 0.5 * ((double) P.bmax[k] - (double) P.bmin[k]);
-            c2 += c * c; d2 += e * e;
-        }
-        const float t_max = (float) ((std::sqrt(c2) + std::sqrt(d2)) * 1.01);
-        return nerf_adjoint_pass(h, h->stream, 64, [&](uint32_t *bounds) {       // (64 bytes: 12 words, 14 with the distortion output)
-            return dist ? drt::launch_nerf_dist_tile_adjoint(P, g4, bounds, t_max, h->stream)
-                        : drt::launch_nerf_aov_tile_adjoint(P, g4, bounds, t_max, h->stream);
-        });
-    }
-    const uint32_t q = (uint32_t) P.nerf_queries;                 // at most one splat per query and plane
-    return run_backward(h, P, q, q, [&](drt::Params &Q) {
-        TimedSpan span;
-        DRT_HIP_CHECK(h, span.begin(h, h->stream));
-        DRT_HIP_CHECK(h, dist ? drt::launch_nerf_dist(Q, true, h->stream) : drt::launch_nerf_aov(Q, true, h->stream));
-        DRT_HIP_CHECK(h, span.end(1));
-        return (int) DRT_OK;
-    });
-}
-
-static int nerf_aov_backward_ray(drt_handle h, const char *what, bool dist, const drt_nerf_config *cfg, const float *emission,
-                                 const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                                 const float *dL, const float *L_in, float *grad_sigma_t, float *grad_emission)
-{
-    return nerf_variant_call(h, what, dist ? kNerfDist : kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
-                             [&](drt::Params &P, const drt::NerfSh &) {
-        if (!dL || !L_in || !grad_sigma_t || !grad_emission)
-            return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null dL / L_in / gradient buffer", what);
-        return nerf_aov_backward(h, dist, P, emission, dL, nullptr, L_in, grad_sigma_t, grad_emission);
-    });
-}
-
-static int nerf_aov_backward_px(drt_handle h, const char *what, bool dist, const drt_nerf_config *cfg, const float *emission,
-                                const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                                const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t, float *grad_emission)
-{
-    return nerf_variant_call(h, what, dist ? kNerfDist : kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, true,
-                             [&](drt::Params &P, const drt::NerfSh &) {
-        if (!L_in || !grad_sigma_t || !grad_emission)
-            return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null L_in / gradient buffer", what);
-        DRT_TRY(check_px(h, what, n_rays, spp, grad_image, n_pixels));
-        return nerf_aov_backward(h, dist, P, emission, nullptr, grad_image, L_in, grad_sigma_t, grad_emission);
-    });
-}
-
-static int nerf_aov_forward(drt_handle h, const char *what, bool dist, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                            const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
-                            const float *t_emission, float *dL_out)
-{
-    return nerf_variant_call(h, what, dist ? kNerfDist : kNerfAov, cfg, emission, nullptr, rays_o, rays_d, n_rays, ray_offset, spp, seed, false,
-                             [&](drt::Params &P, const drt::NerfSh &) {
-        if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null dL_out", what);
-        forward_params(P, t_sigma_t, t_emission, dL_out);
-        DRT_HIP_CHECK(h, dist ? drt::launch_nerf_dist_fwd(P, h->stream) : drt::launch_nerf_aov_fwd(P, h->stream));
-        return (int) DRT_OK;
-    });
-}
-
-int drt_nerf_render_primal_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
-                               uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
-{
-    return nerf_aov_primal(h, "drt_nerf_render_primal_aov", false, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_out);
-}
-
-int drt_nerf_render_backward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
-                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
-                                 float *grad_sigma_t, float *grad_emission)
-{
-    return nerf_aov_backward_ray(h, "drt_nerf_render_backward_aov", false, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, L_in,
-                                 grad_sigma_t, grad_emission);
-}
-
-int drt_nerf_render_backward_px_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                                    const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                                    const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
-                                    float *grad_emission)
-{
-    return nerf_aov_backward_px(h, "drt_nerf_render_backward_px_aov", false, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed,
-                                grad_image, n_pixels, L_in, grad_sigma_t, grad_emission);
-}
-
-int drt_nerf_render_forward_aov(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
-                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
-                                const float *t_emission, float *dL_out)
-{
-    return nerf_aov_forward(h, "drt_nerf_render_forward_aov", false, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, t_sigma_t,
-                            t_emission, dL_out);
-}
-
-int drt_nerf_render_primal_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
-                                uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
-{
-    return nerf_aov_primal(h, "drt_nerf_render_primal_dist", true, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_out);
-}
-
-int drt_nerf_render_backward_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
-                                  uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL, const float *L_in,
-                                  float *grad_sigma_t, float *grad_emission)
-{
-    return nerf_aov_backward_ray(h, "drt_nerf_render_backward_dist", true, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, L_in,
-                                 grad_sigma_t, grad_emission);
-}
-
-int drt_nerf_render_backward_px_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
-                                     const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
-                                     const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
-                                     float *grad_emission)
-{
-    return nerf_aov_backward_px(h, "drt_nerf_render_backward_px_dist", true, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed,
-                                grad_image, n_pixels, L_in, grad_sigma_t, grad_emission);
-}
-
-int drt_nerf_render_forward_dist(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o, const float *rays_d,
-                                 uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *t_sigma_t,
-                                 const float *t_emission, float *dL_out)
-{
-    return nerf_aov_forward(h, "drt_nerf_render_forward_dist", true, cfg, emission, rays_o, rays_d, n_rays, ray_offset, spp, seed, t_sigma_t,
-                            t_emission, dL_out);
 }
 
 int drt_film_develop_n(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image)

@@ -343,6 +343,15 @@ enum class Phase : int {
     kTab,      // tabulated over the cosine of the scattering angle (drt_set_phase_tab; TabView below); no phase-parameter gradient
 };
 
+// What a nerf launch writes per ray: the `kind` argument of the nerf launchers (drt_launch.h), which pick the unit that holds the kind's kernels.
+// Host-side only: no kernel reads it and it is not in Params - the kernels differ by their emission policy / window configuration and AOV flag.
+enum class NerfOut : int {
+    kPlain,    // [r, g, b] from a three-channel emission grid (drt_kernels.hip / drt_own.hip; sensor rays' adjoint: drt_nerf_tile.hip)
+    kSh,       // [r, g, b] from spherical-harmonic emission (drt_nerf_sh.hip)
+    kAov,      // [r, g, b, opacity, depth] (drt_nerf_aov.hip)
+    kDist,     // [r, g, b, opacity, depth, distortion] (drt_nerf_dist.hip)
+};
+
 // ---------------------------------------------------------------------------
 // kernel parameter block (passed by value in the kernarg segment)
 // ---------------------------------------------------------------------------

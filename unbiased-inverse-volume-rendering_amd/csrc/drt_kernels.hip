@@ -506,13 +506,35 @@ hipError_t launch_brick_sigma(const float *src, float *dst, int rx, int ry, int 
 }
 
 // ---- the launchers of drt_launch.h whose kernels are spread over several units: each picks the unit that holds the job's kernels -------------
-template struct NerfUnit<false>;                // (this unit's own; drt_own.hip has the other)
-extern template struct NerfUnit<true>;
-hipError_t launch_nerf(const Params &P, bool adjoint, bool count, hipStream_t stream)
+template struct NerfLaneUnit<NerfOut::kPlain, false>;           // (this unit's own; the others: drt_own.hip, drt_nerf_aov.hip, drt_nerf_dist.hip)
+extern template struct NerfLaneUnit<NerfOut::kPlain, true>;
+extern template struct NerfLaneUnit<NerfOut::kAov, false>;
+extern template struct NerfLaneUnit<NerfOut::kDist, false>;
+
+namespace {
+// f(NerfLaneUnit<the job's cell>()): the kind as the caller says, the colour lattice as Params says (kPlain only: the other kinds have no
+// own-lattice kernels, and their launch refuses such a job)
+template <typename F> hipError_t nerf_cell(const Params &P, NerfOut kind, F f)
 {
-    return P.colour_own ? NerfUnit<true>::trace(P, adjoint, count, stream) : NerfUnit<false>::trace(P, adjoint, count, stream);
+    switch (kind) {
+    case NerfOut::kPlain: return P.colour_own ? f(NerfLaneUnit<NerfOut::kPlain, true>()) : f(NerfLaneUnit<NerfOut::kPlain, false>());
+    case NerfOut::kSh: return f(NerfLaneUnit<NerfOut::kSh, false>());
+    case NerfOut::kAov: return f(NerfLaneUnit<NerfOut::kAov, false>());
+    case NerfOut::kDist: return f(NerfLaneUnit<NerfOut::kDist, false>());
+    }
+    return hipErrorInvalidValue;
 }
-hipError_t launch_nerf_fwd(const Params &P, hipStream_t stream) { return P.colour_own ? NerfUnit<true>::forward(P, stream) : NerfUnit<false>::forward(P, stream); }
+}  // namespace
+
+hipError_t launch_nerf(const Params &P, NerfOut kind, const NerfSh &S, bool adjoint, bool count, hipStream_t stream)
+{
+    return nerf_cell(P, kind, [&](auto unit) { return decltype(unit)::trace(P, S, adjoint, count, stream); });
+}
+
+hipError_t launch_nerf_fwd(const Params &P, NerfOut kind, const NerfSh &S, hipStream_t stream)
+{
+    return nerf_cell(P, kind, [&](auto unit) { return decltype(unit)::forward(P, S, stream); });
+}
 
 namespace {
 // f(CoopUnit<the job's cell>()): the phase as the caller says, the majorant kind and the colour lattice as Params says

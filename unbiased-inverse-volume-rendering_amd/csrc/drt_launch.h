@@ -14,51 +14,58 @@ hipError_t launch_occupancy(const float *sigma_t, int rx, int ry, int rz, int sh
                             uint32_t *occ, int words, hipStream_t stream);
 hipError_t launch_brick_sigma(const float *src, float *dst, int rx, int ry, int rz, int nbx, int nby,
                               hipStream_t stream);
-// the nerf march (drt_nerf_kernel.h), and in forward mode with dual numbers (drt_*render_forward: L_out = J t per ray, the tangent grids in
-// Params::g_sigma / g_albedo, read only).  Params::colour_own: the same kernels with the colour grids on their own lattice (drt_own.hip)
-hipError_t launch_nerf(const Params &P, bool adjoint, bool count, hipStream_t stream);
-hipError_t launch_nerf_fwd(const Params &P, hipStream_t stream);
-// ... what a unit contributes to the two (members defined in drt_nerf_kernel.h; each unit instantiates the lattice it is compiled for)
-template <bool OWN> struct NerfUnit {
-    static hipError_t trace(const Params &P, bool adjoint, bool count, hipStream_t stream);
-    static hipError_t forward(const Params &P, hipStream_t stream);
-};
-// drt_nerf_tile.hip: the nerf adjoint for sensor rays - a workgroup per pixel tile, its splats pre-reduced in an LDS window of 16^3 voxels, no records
-// (the window kernel itself: drt_nerf_tile_kernel.h, one kernel for the plain, opacity / depth and SH calls, by a compile-time configuration)
-// (g4: lookups from Params::grid4 - the fused pass, emission = the medium's albedo grid - instead of sigma_b + Params::emission)
-bool nerf_tile_supported(const Params &P);
-// bounds: 32 bytes of device scratch (the fixed-point units of the LDS window follow from max |dL|, max |L_in|, max |emission|, reduced there first)
-hipError_t launch_nerf_tile_adjoint(const Params &P, bool g4, bool count, uint32_t *bounds, hipStream_t stream);
-// drt_nerf_sh.hip: the nerf march with spherical-harmonic (view-dependent) emission, K = (degree + 1)^2 in {4, 9} coefficients per voxel and
-// colour channel.  The caller's sh grid (Z,Y,X,3K) travels in Params::emission, its gradient / tangent grid in Params::g_albedo; lookups
-// come from `vox`, an interleaved copy [sigma_t, sh[0..3K-1], 0..] of sh_vox_floats(K) floats per voxel made by launch_sh_interleave.
-// It reaches the kernels inside their emission policy / window configuration, an argument of its own: Params does not grow (the tracers
-// are sensitive to its size, drt_device.h)
+// The nerf march (drt_nerf_kernel.h, drt_nerf_tile_kernel.h), every output kind (NerfOut, drt_device.h) through three launchers.  What a kind
+// writes per ray - Params::L_out / dL / dL_pix / L_in hold that many interleaved floats:
+//   kPlain  [r, g, b]             emission (Z,Y,X,3) in Params::emission.  Params::colour_own: the same per-lane kernels with the colour grid on
+//                                 its own lattice (drt_own.hip); every other kind needs sigma_t's lattice (hipErrorInvalidValue otherwise)
+//   kSh     [r, g, b]             spherical-harmonic (view-dependent) emission, K = (degree + 1)^2 in {4, 9} coefficients per voxel and colour
+//                                 channel.  The caller's sh grid (Z,Y,X,3K) travels in Params::emission, its gradient / tangent grid in
+//                                 Params::g_albedo; lookups come from NerfSh::vox, an interleaved copy [sigma_t, sh[0..3K-1], 0..] of
+//                                 sh_vox_floats(K) floats per voxel made by launch_sh_interleave.  It reaches the kernels inside their emission
+//                                 policy / window configuration, an argument of its own: Params does not grow (the tracers are sensitive to
+//                                 its size, drt_device.h)
+//   kAov    [r, g, b, A, D]       opacity A = weights_sum and depth D = sum weight (t_in + t_b)
+//   kDist   [r, g, b, A, D, Z]    ... and the distortion regulariser Z (quadratic in the march weights)
+// `S`: the interleaved copy of a kSh launch, { nullptr, 0 } for every other kind (which ignore it).
 struct NerfSh {
     const float4 *vox;
     int K;
 };
 size_t sh_vox_floats(int K);
 hipError_t launch_sh_interleave(const float *sigma_t, const float *sh, int K, float4 *vox, size_t n_voxels, hipStream_t stream);
-// one ray per lane (nerf_kernel / nerf_fwd_kernel with the SH emission policy): the primal, the adjoint (float atomics on the caller's grids:
-// explicit ray batches - the untuned route) and forward mode
-hipError_t launch_nerf_sh(const Params &P, const NerfSh &S, bool adjoint, hipStream_t stream);
-hipError_t launch_nerf_sh_fwd(const Params &P, const NerfSh &S, hipStream_t stream);
-// the adjoint of sensor rays: the window kernel of drt_nerf_tile_kernel.h with 1 + 3K planes (bounds: 32 bytes; same support predicate:
-// nerf_tile_supported).  With Params::counters set the launch counts its window phases in bounds[5]
-hipError_t launch_nerf_sh_tile_adjoint(const Params &P, const NerfSh &S, uint32_t *bounds, hipStream_t stream);
-// drt_nerf_aov.hip: the nerf march with two more outputs per ray, opacity A = weights_sum and depth D = sum weight (t_in + t_b): five interleaved
-// floats [r, g, b, A, D] in Params::L_out / dL / dL_pix / L_in.  One ray per lane (nerf_kernel / nerf_fwd_kernel with AOV = true): the primal,
-// forward mode and the adjoint of explicit ray batches (deferred records when Params::rec_buf is set, as launch_nerf); sensor rays: the window kernel of drt_nerf_tile_kernel.h with AOV = true (bounds: 48 bytes;
-// t_max: a bound of a query's distance from the sensor's origin; same support predicate: nerf_tile_supported)
-hipError_t launch_nerf_aov(const Params &P, bool adjoint, hipStream_t stream);
-hipError_t launch_nerf_aov_fwd(const Params &P, hipStream_t stream);
-hipError_t launch_nerf_aov_tile_adjoint(const Params &P, bool g4, uint32_t *bounds, float t_max, hipStream_t stream);
-// drt_nerf_dist.hip: ... and a third, the distortion regulariser Z (quadratic in the march weights): six interleaved floats [r, g, b, A, D, Z],
-// the same kernels with a policy that carries kDist.  The three calls mirror the three above (bounds: 56 bytes)
-hipError_t launch_nerf_dist(const Params &P, bool adjoint, hipStream_t stream);
-hipError_t launch_nerf_dist_fwd(const Params &P, hipStream_t stream);
-hipError_t launch_nerf_dist_tile_adjoint(const Params &P, bool g4, uint32_t *bounds, float t_max, hipStream_t stream);
+// One ray per lane (nerf_kernel): the primal, or the adjoint - of explicit ray batches and of the record / atomic gradient paths.  The adjoint
+// emits deferred records when Params::rec_buf is set (kSh: never; its splats are float atomics on the caller's grids - the untuned route).
+// `count`: the counting kernels (kPlain only; the other kinds have none and ignore it: such a launch counts nothing).
+hipError_t launch_nerf(const Params &P, NerfOut kind, const NerfSh &S, bool adjoint, bool count, hipStream_t stream);
+// ... and in forward mode with dual numbers (nerf_fwd_kernel; drt_*render_forward: L_out = J t per ray, the tangent grids in Params::g_sigma /
+// g_albedo, read only)
+hipError_t launch_nerf_fwd(const Params &P, NerfOut kind, const NerfSh &S, hipStream_t stream);
+// ... what a unit contributes to the two: the per-lane kernels of one cell (kind, lattice).  Members defined in drt_nerf_kernel.h; drt_kernels.hip
+// and drt_own.hip instantiate kPlain for the lattice they are compiled for, drt_nerf_aov.hip kAov, drt_nerf_dist.hip kDist; drt_nerf_sh.hip, where
+// the SH emission policy lives, specialises kSh
+template <NerfOut K, bool OWN> struct NerfLaneUnit {
+    static hipError_t trace(const Params &P, const NerfSh &S, bool adjoint, bool count, hipStream_t stream);
+    static hipError_t forward(const Params &P, const NerfSh &S, hipStream_t stream);
+};
+template <> hipError_t NerfLaneUnit<NerfOut::kSh, false>::trace(const Params &P, const NerfSh &S, bool adjoint, bool count, hipStream_t stream);
+template <> hipError_t NerfLaneUnit<NerfOut::kSh, false>::forward(const Params &P, const NerfSh &S, hipStream_t stream);
+// The nerf adjoint for sensor rays - a workgroup per pixel tile, its splats pre-reduced in an LDS window of voxels, no records (drt_nerf_tile.hip
+// tells why; the window kernel itself: drt_nerf_tile_kernel.h, one kernel for every kind, by a compile-time configuration).
+//   g4      lookups from Params::grid4 - the four-channel copy [sigma_t, r, g, b] - instead of sigma_b + Params::emission (kSh: ignored)
+//   count   kPlain: the launch counts as the per-lane kernels do; kSh: it counts its window phases in bounds[5]; kAov, kDist: ignored
+//   bounds  device scratch: 32 bytes for kPlain and kSh, 48 for kAov, 56 for kDist (the fixed-point units of the LDS window follow from
+//           max |dL|, max |L_in|, max |emission|, ..., reduced there first)
+//   t_max   kAov, kDist: a bound of a query's distance from the sensor's origin (the others ignore it)
+bool nerf_tile_supported(const Params &P);
+hipError_t launch_nerf_tile_adjoint(const Params &P, NerfOut kind, const NerfSh &S, bool g4, bool count, uint32_t *bounds, float t_max,
+                                    hipStream_t stream);
+// ... what a unit contributes to it: the window kernels of one kind.  Member defined in drt_nerf_tile_kernel.h; drt_nerf_tile.hip instantiates
+// kPlain, drt_nerf_aov.hip kAov, drt_nerf_dist.hip kDist; drt_nerf_sh.hip, where the SH window configuration lives, specialises kSh
+template <NerfOut K> struct NerfTileUnit {
+    static hipError_t adjoint(const Params &P, const NerfSh &S, bool g4, bool count, uint32_t *bounds, float t_max, hipStream_t stream);
+};
+template <> hipError_t NerfTileUnit<NerfOut::kSh>::adjoint(const Params &P, const NerfSh &S, bool g4, bool count, uint32_t *bounds, float t_max,
+                                                           hipStream_t stream);
 // box film with `channels` interleaved floats per sample: one thread per (pixel, channel), samples summed in index order / dL = grad / spp
 hipError_t launch_film_develop_n(const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image, hipStream_t stream);
 hipError_t launch_film_backward_n(const float *grad_image, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *dL, hipStream_t stream);

@@ -34,32 +34,8 @@
 
 namespace drt {
 
-// (launch_nerf_aov's dispatch: no counting variants - drt_get_counters does not count these calls)
-hipError_t launch_nerf_dist(const Params &P, bool adjoint, hipStream_t stream)
-{
-    if (P.n_rays <= P.ray_first) return hipSuccess;
-    if (P.colour_own || !P.emission) return hipErrorInvalidValue;
-    if (adjoint ? (!P.g_sigma || !P.g_albedo || !P.L_in || !(P.dL || P.dL_pix)) : !P.L_out) return hipErrorInvalidValue;
-    const dim3 block(256), grid((unsigned) ((P.n_rays - P.ray_first + 255) / 256));
-    if (adjoint && P.rec_buf[0] != nullptr) hipLaunchKernelGGL((nerf_kernel<DistEmission, true, false, true, true>), grid, block, 0, stream, P);
-    else if (adjoint)                       hipLaunchKernelGGL((nerf_kernel<DistEmission, true, false, false, true>), grid, block, 0, stream, P);
-    else                                    hipLaunchKernelGGL((nerf_kernel<DistEmission, false, false, false, true>), grid, block, 0, stream, P);
-    return hipGetLastError();
-}
-
-hipError_t launch_nerf_dist_fwd(const Params &P, hipStream_t stream)
-{
-    if (P.n_rays <= P.ray_first) return hipSuccess;
-    if (P.colour_own || !P.emission || !P.L_out) return hipErrorInvalidValue;
-    const dim3 block(256), grid((unsigned) ((P.n_rays - P.ray_first + 255) / 256));
-    hipLaunchKernelGGL((nerf_fwd_kernel<DistEmission, true>), grid, block, 0, stream, P);
-    return hipGetLastError();
-}
-
-hipError_t launch_nerf_dist_tile_adjoint(const Params &P, bool g4, uint32_t *bounds, float t_max, hipStream_t stream)
-{
-    if (!P.L_in || !(P.dL || P.dL_pix)) return hipErrorInvalidValue;
-    return nerf_tile_launch_plain<true, DistWindow>(P, g4, false, bounds, t_max, stream);
-}
+// this unit's cells of the three nerf launchers (no counting kernels: drt_get_counters does not count these calls)
+template struct NerfLaneUnit<NerfOut::kDist, false>;
+template struct NerfTileUnit<NerfOut::kDist>;
 
 }  // namespace drt

@@ -307,35 +307,72 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P, const EAr
     } else { P.L_out[F * i] = dres[0]; P.L_out[F * i + 1] = dres[1]; P.L_out[F * i + 2] = dres[2]; }
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------
+// The launch of every kind (drt_launch.h: launch_nerf / launch_nerf_fwd), once.  A LANE describes a kind's kernels:
+//   E, kAov          the emission policy and the AOV flag its kernels are instantiated with
+//   kCount, kDefer   the cells of the adjoint / records / count ladder it HAS: counting kernels (COUNT = true), a record-emitting adjoint
+//                    (DEFER = true).  A cell it does not have is never instantiated - a new instantiation is a new kernel -: `count` is
+//                    ignored, and an adjoint with Params::rec_buf set runs the atomic one
+//   kChecked         the launch refuses (hipErrorInvalidValue) a colour grid on its own lattice and a job without the buffers it writes
+//   kNeedsDL         ... and one without an emission grid or, the adjoint, without dL / dL_pix
+// (the plain launch never checked its job and the SH one does not ask for dL: each kind keeps the refusals it came with)
+// earg: the kernels' trailing arguments, from which they build E.
+// ---------------------------------------------------------------------------
+template <NerfOut K> struct NerfLane;                            // (kSh: drt_nerf_sh.hip has its own, per K)
+template <> struct NerfLane<NerfOut::kPlain> { using E = PlainEmission; static constexpr bool kAov = false, kCount = true, kDefer = true, kChecked = false, kNeedsDL = false; };
+template <> struct NerfLane<NerfOut::kAov> { using E = PlainEmission; static constexpr bool kAov = true, kCount = false, kDefer = true, kChecked = true, kNeedsDL = true; };
+template <> struct NerfLane<NerfOut::kDist> { using E = DistEmission; static constexpr bool kAov = true, kCount = false, kDefer = true, kChecked = true, kNeedsDL = true; };
 
-// this unit's half of launch_nerf / launch_nerf_fwd (drt_launch.h: NerfUnit; instantiated by drt_kernels.hip and drt_own.hip)
-template <bool OWN> hipError_t NerfUnit<OWN>::forward(const Params &P, hipStream_t stream)
+template <class L, bool ADJ, bool DEFER, class... EArg>
+void nerf_lane_launch(const Params &P, bool count, dim3 grid, hipStream_t stream, EArg... earg)
 {
-    static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
+    if constexpr (L::kCount) {
+        if (count) {
+            hipLaunchKernelGGL((nerf_kernel<typename L::E, ADJ, true, DEFER, L::kAov, EArg...>), grid, dim3(256), 0, stream, P, earg...);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((nerf_kernel<typename L::E, ADJ, false, DEFER, L::kAov, EArg...>), grid, dim3(256), 0, stream, P, earg...);
+}
+
+template <class L, class... EArg>
+hipError_t nerf_lane_trace(const Params &P, bool adjoint, bool count, hipStream_t stream, EArg... earg)
+{
     if (P.n_rays <= P.ray_first) return hipSuccess;
-    dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
-    hipLaunchKernelGGL((nerf_fwd_kernel<PlainEmission, false>), grid, block, 0, stream, P);
+    if (L::kChecked && (P.colour_own || (adjoint ? (!P.g_sigma || !P.g_albedo || !P.L_in) : !P.L_out))) return hipErrorInvalidValue;
+    if (L::kNeedsDL && (!P.emission || (adjoint && !(P.dL || P.dL_pix)))) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
+    const bool defer = L::kDefer && adjoint && P.rec_buf[0] != nullptr;
+    if (!adjoint) nerf_lane_launch<L, false, false>(P, count, grid, stream, earg...);
+    else if (!defer) nerf_lane_launch<L, true, false>(P, count, grid, stream, earg...);
+    else if constexpr (L::kDefer) nerf_lane_launch<L, true, true>(P, count, grid, stream, earg...);
     return hipGetLastError();
 }
 
-template <bool OWN> hipError_t NerfUnit<OWN>::trace(const Params &P, bool adjoint, bool count, hipStream_t stream)
+template <class L, class... EArg>
+hipError_t nerf_lane_forward(const Params &P, hipStream_t stream, EArg... earg)
 {
-    static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
     if (P.n_rays <= P.ray_first) return hipSuccess;
-    dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
-    const bool defer = adjoint && P.rec_buf[0] != nullptr;
-    if (adjoint && defer) {
-        if (count) hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, true, true>), grid, block, 0, stream, P);
-        else       hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, false, true>), grid, block, 0, stream, P);
-    } else if (adjoint) {
-        if (count) hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, true, false>), grid, block, 0, stream, P);
-        else       hipLaunchKernelGGL((nerf_kernel<PlainEmission, true, false, false>), grid, block, 0, stream, P);
-    } else {
-        if (count) hipLaunchKernelGGL((nerf_kernel<PlainEmission, false, true, false>), grid, block, 0, stream, P);
-        else       hipLaunchKernelGGL((nerf_kernel<PlainEmission, false, false, false>), grid, block, 0, stream, P);
-    }
+    if (L::kChecked && (P.colour_own || !P.L_out)) return hipErrorInvalidValue;
+    if (L::kNeedsDL && !P.emission) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
+    hipLaunchKernelGGL((nerf_fwd_kernel<typename L::E, L::kAov, EArg...>), grid, dim3(256), 0, stream, P, earg...);
     return hipGetLastError();
+}
+
+}  // namespace
+
+// this unit's cell of launch_nerf / launch_nerf_fwd (drt_launch.h: NerfLaneUnit).  kSh: drt_nerf_sh.hip's own definitions
+template <NerfOut K, bool OWN> hipError_t NerfLaneUnit<K, OWN>::trace(const Params &P, const NerfSh &, bool adjoint, bool count, hipStream_t stream)
+{
+    static_assert(OWN == kColourOwn && K != NerfOut::kSh, "a unit instantiates the kernels of its own lattice");
+    return nerf_lane_trace<NerfLane<K>>(P, adjoint, count, stream);
+}
+
+template <NerfOut K, bool OWN> hipError_t NerfLaneUnit<K, OWN>::forward(const Params &P, const NerfSh &, hipStream_t stream)
+{
+    static_assert(OWN == kColourOwn && K != NerfOut::kSh, "a unit instantiates the kernels of its own lattice");
+    return nerf_lane_forward<NerfLane<K>>(P, stream);
 }
 
 }  // namespace drt

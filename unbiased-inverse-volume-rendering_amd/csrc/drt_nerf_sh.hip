@@ -26,7 +26,8 @@
 //                                (ShCfg below)
 //   nerf_kernel<ShEmission<K>, true, ..>           adjoint of EXPLICIT ray batches: one ray per lane, fp32 atomics on the caller's grids.  The
 //                                untuned route: the record streams of drt_deferred.hip are four-channel, and widening them is out of scope
-// Here besides: the interleave kernel, the footprint / lookup / gather helpers (sh_stencil, sh_corners, sh_eval, sh_gather) and the launches.
+// Here besides: the interleave kernel, the footprint / lookup / gather helpers (sh_stencil, sh_corners, sh_eval, sh_gather) and this unit's cells of
+// the nerf launchers (NerfLaneUnit<kSh, false>, NerfTileUnit<kSh>: drt_launch.h).
 #include "drt_device.h"
 #include "drt_launch.h"
 #include "drt_nerf_kernel.h"
@@ -255,39 +256,33 @@ hipError_t launch_sh_interleave(const float *sigma_t, const float *sh, int K, fl
     return hipGetLastError();
 }
 
-hipError_t launch_nerf_sh(const Params &P, const NerfSh &S, bool adjoint, hipStream_t stream)
+// This unit's cells of the three nerf launchers (drt_launch.h), for the K of the call's copy.  The per-lane kernels (drt_nerf_kernel.h: NerfLane
+// names the parts): no counting kernels, no records, and the adjoint does not ask for dL
+namespace {
+template <int K> struct ShLane { using E = ShEmission<K>; static constexpr bool kAov = false, kCount = false, kDefer = false, kChecked = true, kNeedsDL = false; };
+}  // namespace
+
+template <> hipError_t NerfLaneUnit<NerfOut::kSh, false>::trace(const Params &P, const NerfSh &S, bool adjoint, bool count, hipStream_t stream)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
-    if ((S.K != 4 && S.K != 9) || !S.vox || P.colour_own) return hipErrorInvalidValue;
-    if (adjoint ? (!P.g_sigma || !P.g_albedo || !P.L_in) : !P.L_out) return hipErrorInvalidValue;
-    const dim3 block(256), grid((unsigned) ((P.n_rays - P.ray_first + 255) / 256));
-    if (S.K == 4) {
-        if (adjoint) hipLaunchKernelGGL((nerf_kernel<ShEmission<4>, true, false, false>), grid, block, 0, stream, P, S.vox);
-        else         hipLaunchKernelGGL((nerf_kernel<ShEmission<4>, false, false, false>), grid, block, 0, stream, P, S.vox);
-    } else {
-        if (adjoint) hipLaunchKernelGGL((nerf_kernel<ShEmission<9>, true, false, false>), grid, block, 0, stream, P, S.vox);
-        else         hipLaunchKernelGGL((nerf_kernel<ShEmission<9>, false, false, false>), grid, block, 0, stream, P, S.vox);
-    }
-    return hipGetLastError();
+    if ((S.K != 4 && S.K != 9) || !S.vox) return hipErrorInvalidValue;
+    return S.K == 4 ? nerf_lane_trace<ShLane<4>>(P, adjoint, count, stream, S.vox) : nerf_lane_trace<ShLane<9>>(P, adjoint, count, stream, S.vox);
 }
 
-hipError_t launch_nerf_sh_fwd(const Params &P, const NerfSh &S, hipStream_t stream)
+template <> hipError_t NerfLaneUnit<NerfOut::kSh, false>::forward(const Params &P, const NerfSh &S, hipStream_t stream)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
-    if ((S.K != 4 && S.K != 9) || !S.vox || P.colour_own || !P.L_out) return hipErrorInvalidValue;
-    const dim3 block(256), grid((unsigned) ((P.n_rays - P.ray_first + 255) / 256));
-    if (S.K == 4) hipLaunchKernelGGL((nerf_fwd_kernel<ShEmission<4>>), grid, block, 0, stream, P, S.vox);
-    else          hipLaunchKernelGGL((nerf_fwd_kernel<ShEmission<9>>), grid, block, 0, stream, P, S.vox);
-    return hipGetLastError();
+    if ((S.K != 4 && S.K != 9) || !S.vox) return hipErrorInvalidValue;
+    return S.K == 4 ? nerf_lane_forward<ShLane<4>>(P, stream, S.vox) : nerf_lane_forward<ShLane<9>>(P, stream, S.vox);
 }
 
-// (a launch counts its window phases when the handle counts: bounds[5], drt_nerf_sh_tile_stats)
-hipError_t launch_nerf_sh_tile_adjoint(const Params &P, const NerfSh &S, uint32_t *bounds, hipStream_t stream)
+// (count: the launch counts its window phases in bounds[5], drt_nerf_sh_tile_stats)
+template <> hipError_t NerfTileUnit<NerfOut::kSh>::adjoint(const Params &P, const NerfSh &S, bool, bool count, uint32_t *bounds, float, hipStream_t stream)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
     if ((S.K != 4 && S.K != 9) || !S.vox || !P.L_in) return hipErrorInvalidValue;
-    return S.K == 4 ? nerf_tile_launch<ShWindow<4>, false>(P, P.counters != nullptr, bounds, 0.0f, stream, S.vox)
-                    : nerf_tile_launch<ShWindow<9>, false>(P, P.counters != nullptr, bounds, 0.0f, stream, S.vox);
+    return S.K == 4 ? nerf_tile_launch<ShWindow<4>, false>(P, count, bounds, 0.0f, stream, S.vox)
+                    : nerf_tile_launch<ShWindow<9>, false>(P, count, bounds, 0.0f, stream, S.vox);
 }
 
 }  // namespace drt

@@ -27,7 +27,7 @@
 // The bounds kernel, the window kernel and their launcher live in drt_nerf_tile_kernel.h, templated on a window configuration (extents, planes,
 // threads, lookup, colour splat) and an AOV flag: this unit instantiates PlainWindow with AOV = false (the code described above),
 // drt_nerf_aov.hip PlainWindow with AOV = true (opacity and depth outputs), drt_nerf_sh.hip its ShWindow (1 + 3K planes).  Here: the
-// four-channel copy, the support predicate and the plain launch.
+// four-channel copy, the support predicate, the plain kind's cell (NerfTileUnit<kPlain>) and launch_nerf_tile_adjoint, which picks the kind's unit.
 #include <atomic>
 #include "drt_device.h"
 #include "drt_launch.h"
@@ -88,9 +88,19 @@ bool nerf_tile_supported(const Params &P)
            (uint64_t) P.width * (uint64_t) P.height * P.spp < (1ull << 32) && (!P.chunk || P.stride >= P.chunk);
 }
 
-hipError_t launch_nerf_tile_adjoint(const Params &P, bool g4, bool count, uint32_t *bounds, hipStream_t stream)
+template struct NerfTileUnit<NerfOut::kPlain>;                  // (this unit's own; the others: drt_nerf_aov.hip, drt_nerf_dist.hip)
+extern template struct NerfTileUnit<NerfOut::kAov>;
+extern template struct NerfTileUnit<NerfOut::kDist>;
+hipError_t launch_nerf_tile_adjoint(const Params &P, NerfOut kind, const NerfSh &S, bool g4, bool count, uint32_t *bounds, float t_max,
+                                    hipStream_t stream)
 {
-    return nerf_tile_launch_plain<false>(P, g4, count, bounds, 0.0f, stream);
+    switch (kind) {
+    case NerfOut::kPlain: return NerfTileUnit<NerfOut::kPlain>::adjoint(P, S, g4, count, bounds, t_max, stream);
+    case NerfOut::kSh: return NerfTileUnit<NerfOut::kSh>::adjoint(P, S, g4, count, bounds, t_max, stream);
+    case NerfOut::kAov: return NerfTileUnit<NerfOut::kAov>::adjoint(P, S, g4, count, bounds, t_max, stream);
+    case NerfOut::kDist: return NerfTileUnit<NerfOut::kDist>::adjoint(P, S, g4, count, bounds, t_max, stream);
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace drt

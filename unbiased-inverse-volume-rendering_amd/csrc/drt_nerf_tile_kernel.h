@@ -6,6 +6,7 @@
 // the launcher exist once.  drt_nerf_dist.hip: DistWindow (AOV = true and C::kDist: a sixth float per ray, the distortion regulariser Z).  Internal linkage: every including unit gets its own instantiations.
 #pragma once
 #include <atomic>
+#include <type_traits>
 #include "drt_device.h"
 #include "drt_launch.h"
 
@@ -592,15 +593,21 @@ hipError_t nerf_tile_launch(const Params &P, bool count, uint32_t *bounds, float
     return hipGetLastError();
 }
 
-// ... with the plain configuration, for the kind of lookup the call asks for
-template <bool AOV, template <bool> class W = PlainWindow>
-hipError_t nerf_tile_launch_plain(const Params &P, bool g4, bool count, uint32_t *bounds, float t_max, hipStream_t stream)
-{
-    if (g4 && !P.grid4 && P.n_rays > P.ray_first) return hipErrorInvalidValue;
-    return g4 ? nerf_tile_launch<W<true>, AOV>(P, count, bounds, t_max, stream)
-              : nerf_tile_launch<W<false>, AOV>(P, count, bounds, t_max, stream);
-}
-
 }  // namespace
+
+// this unit's cell of launch_nerf_tile_adjoint (drt_launch.h: NerfTileUnit) for the kinds of the plain window - kPlain, kAov with AOV = true,
+// kDist with DistWindow too -, for the kind of lookup the call asks for.  The AOV kinds came with two refusals and no counting kernels; kPlain has
+// no t_max.  kSh: drt_nerf_sh.hip's own definition
+template <NerfOut K> hipError_t NerfTileUnit<K>::adjoint(const Params &P, const NerfSh &, bool g4, bool count, uint32_t *bounds, float t_max, hipStream_t stream)
+{
+    static_assert(K != NerfOut::kSh, "the SH window is drt_nerf_sh.hip's");
+    constexpr bool AOV = K != NerfOut::kPlain, DIST = K == NerfOut::kDist;
+    using W4 = std::conditional_t<DIST, DistWindow<true>, PlainWindow<true>>;
+    using W1 = std::conditional_t<DIST, DistWindow<false>, PlainWindow<false>>;
+    if (AOV && (!P.L_in || !(P.dL || P.dL_pix))) return hipErrorInvalidValue;
+    if (g4 && !P.grid4 && P.n_rays > P.ray_first) return hipErrorInvalidValue;
+    return g4 ? nerf_tile_launch<W4, AOV>(P, !AOV && count, bounds, AOV ? t_max : 0.0f, stream)
+              : nerf_tile_launch<W1, AOV>(P, !AOV && count, bounds, AOV ? t_max : 0.0f, stream);
+}
 
 }  // namespace drt

@@ -16,6 +16,6 @@ namespace drt {
 
 template struct CoopUnit<Phase::kIso, false, true>;
 template struct CoopUnit<Phase::kIso, true, true>;
-template struct NerfUnit<true>;
+template struct NerfLaneUnit<NerfOut::kPlain, true>;
 
 }  // namespace drt

@@ -160,31 +160,71 @@ public:
         c.activation_relu = p.contains("activation_relu") && py::cast<bool>(p["activation_relu"]);
         return c;
     }
-    void nerf_render_primal(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n,
-                            uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_out)
+    // The nerf calls: `kind` is the output kind - 0 plain, 1 spherical-harmonic emission (props["sh_degree"] in {1, 2}), 2 opacity and depth (five
+    // interleaved floats per ray / pixel), 3 ... and distortion (six) - and picks the C function, drt_nerf_render_<pass><suffix of the kind>.
+    // The steps every one of them takes: the config from the props, the GIL released around `call(config, sh_degree)`, the status checked
+    // under the C function's name
+    template <class Call> void nerf_call(int kind, const py::dict &props, const char *pass, Call call)
     {
-        drt_nerf_config c = nerf_cfg(props);
+        static const char *const suffix[] = { "", "_sh", "_aov", "_dist" };
+        if (kind < 0 || kind > 3) throw std::invalid_argument("nerf output kind must be 0 (plain), 1 (sh), 2 (aov) or 3 (dist)");
+        const drt_nerf_config c = nerf_cfg(props);
+        const int32_t deg = props.contains("sh_degree") ? py::cast<int>(props["sh_degree"]) : 0;
         int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_primal(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o),
-                                        ptr<const float>(rays_d), n, off, spp, seed, ptr<float>(L_out));
-        }
-        check(rc, "drt_nerf_render_primal");
+        { py::gil_scoped_release nogil; rc = call(&c, deg); }
+        check(rc, (std::string("drt_nerf_render_") + pass + suffix[kind]).c_str());
     }
-    void nerf_render_backward(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n,
-                              uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dL, uintptr_t L_in,
-                              uintptr_t g_sigma, uintptr_t g_emission)
+    void nerf_render_primal(int kind, const py::dict &props, uintptr_t grid, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                            uint32_t spp, uint32_t seed, uintptr_t L_out)
     {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_backward(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o),
-                                          ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
-                                          ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_emission));
-        }
-        check(rc, "drt_nerf_render_backward");
+        nerf_call(kind, props, "primal", [&](const drt_nerf_config *c, int32_t deg) {
+            const float *g = ptr<const float>(grid), *ro = ptr<const float>(rays_o), *rd = ptr<const float>(rays_d);
+            float *L = ptr<float>(L_out);
+            return kind == 1 ? drt_nerf_render_primal_sh(h_, c, g, deg, ro, rd, n, off, spp, seed, L)
+                 : kind == 2 ? drt_nerf_render_primal_aov(h_, c, g, ro, rd, n, off, spp, seed, L)
+                 : kind == 3 ? drt_nerf_render_primal_dist(h_, c, g, ro, rd, n, off, spp, seed, L)
+                             : drt_nerf_render_primal(h_, c, g, ro, rd, n, off, spp, seed, L);
+        });
+    }
+    void nerf_render_backward(int kind, const py::dict &props, uintptr_t grid, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                              uint32_t spp, uint32_t seed, uintptr_t dL, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_colour)
+    {
+        nerf_call(kind, props, "backward", [&](const drt_nerf_config *c, int32_t deg) {
+            const float *g = ptr<const float>(grid), *ro = ptr<const float>(rays_o), *rd = ptr<const float>(rays_d);
+            const float *d = ptr<const float>(dL), *Li = ptr<const float>(L_in);
+            float *gs = ptr<float>(g_sigma), *gc = ptr<float>(g_colour);
+            return kind == 1 ? drt_nerf_render_backward_sh(h_, c, g, deg, ro, rd, n, off, spp, seed, d, Li, gs, gc)
+                 : kind == 2 ? drt_nerf_render_backward_aov(h_, c, g, ro, rd, n, off, spp, seed, d, Li, gs, gc)
+                 : kind == 3 ? drt_nerf_render_backward_dist(h_, c, g, ro, rd, n, off, spp, seed, d, Li, gs, gc)
+                             : drt_nerf_render_backward(h_, c, g, ro, rd, n, off, spp, seed, d, Li, gs, gc);
+        });
+    }
+    void nerf_render_backward_px(int kind, const py::dict &props, uintptr_t grid, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                                 uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
+                                 uintptr_t g_colour)
+    {
+        nerf_call(kind, props, "backward_px", [&](const drt_nerf_config *c, int32_t deg) {
+            const float *g = ptr<const float>(grid), *ro = ptr<const float>(rays_o), *rd = ptr<const float>(rays_d);
+            const float *gi = ptr<const float>(grad_image), *Li = ptr<const float>(L_in);
+            float *gs = ptr<float>(g_sigma), *gc = ptr<float>(g_colour);
+            return kind == 1 ? drt_nerf_render_backward_px_sh(h_, c, g, deg, ro, rd, n, off, spp, seed, gi, n_pixels, Li, gs, gc)
+                 : kind == 2 ? drt_nerf_render_backward_px_aov(h_, c, g, ro, rd, n, off, spp, seed, gi, n_pixels, Li, gs, gc)
+                 : kind == 3 ? drt_nerf_render_backward_px_dist(h_, c, g, ro, rd, n, off, spp, seed, gi, n_pixels, Li, gs, gc)
+                             : drt_nerf_render_backward_px(h_, c, g, ro, rd, n, off, spp, seed, gi, n_pixels, Li, gs, gc);
+        });
+    }
+    void nerf_render_forward(int kind, const py::dict &props, uintptr_t grid, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
+                             uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_colour, uintptr_t dL_out)
+    {
+        nerf_call(kind, props, "forward", [&](const drt_nerf_config *c, int32_t deg) {
+            const float *g = ptr<const float>(grid), *ro = ptr<const float>(rays_o), *rd = ptr<const float>(rays_d);
+            const float *ts = ptr<const float>(t_sigma), *tc = ptr<const float>(t_colour);
+            float *dL = ptr<float>(dL_out);
+            return kind == 1 ? drt_nerf_render_forward_sh(h_, c, g, deg, ro, rd, n, off, spp, seed, ts, tc, dL)
+                 : kind == 2 ? drt_nerf_render_forward_aov(h_, c, g, ro, rd, n, off, spp, seed, ts, tc, dL)
+                 : kind == 3 ? drt_nerf_render_forward_dist(h_, c, g, ro, rd, n, off, spp, seed, ts, tc, dL)
+                             : drt_nerf_render_forward(h_, c, g, ro, rd, n, off, spp, seed, ts, tc, dL);
+        });
     }
     void render_forward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
                         uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out)
@@ -207,18 +247,6 @@ public:
                                           ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), t_phase);
         }
         check(rc, "drt_render_forward_phase");
-    }
-    void nerf_render_forward(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                             uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_emission, uintptr_t dL_out)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_forward(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
-                                         spp, seed, ptr<const float>(t_sigma), ptr<const float>(t_emission), ptr<float>(dL_out));
-        }
-        check(rc, "drt_nerf_render_forward");
     }
     void fused_render_primal(const py::dict &props, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp,
                              uint32_t seed, uintptr_t L_nerf, uintptr_t L_drt)
@@ -318,178 +346,6 @@ public:
                                               ptr<float>(g_albedo), ptr<float>(g_phase));
         }
         check(rc, "drt_render_backward_px_phase");
-    }
-    void nerf_render_backward_px(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                 uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
-                                 uintptr_t g_emission)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_backward_px(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
-                                             seed, ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
-                                             ptr<float>(g_emission));
-        }
-        check(rc, "drt_nerf_render_backward_px");
-    }
-    // spherical-harmonic emission (drt_nerf_*_sh): props["sh_degree"] in {1, 2}
-    static int32_t sh_degree(const py::dict &p) { return p.contains("sh_degree") ? py::cast<int>(p["sh_degree"]) : 0; }
-    void nerf_render_primal_sh(const py::dict &props, uintptr_t sh, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                               uint32_t spp, uint32_t seed, uintptr_t L_out)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        const int32_t deg = sh_degree(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_primal_sh(h_, &c, ptr<const float>(sh), deg, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
-                                           spp, seed, ptr<float>(L_out));
-        }
-        check(rc, "drt_nerf_render_primal_sh");
-    }
-    void nerf_render_backward_sh(const py::dict &props, uintptr_t sh, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                 uint32_t spp, uint32_t seed, uintptr_t dL, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_sh)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        const int32_t deg = sh_degree(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_backward_sh(h_, &c, ptr<const float>(sh), deg, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
-                                             spp, seed, ptr<const float>(dL), ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_sh));
-        }
-        check(rc, "drt_nerf_render_backward_sh");
-    }
-    void nerf_render_backward_px_sh(const py::dict &props, uintptr_t sh, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                    uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
-                                    uintptr_t g_sh)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        const int32_t deg = sh_degree(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_backward_px_sh(h_, &c, ptr<const float>(sh), deg, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
-                                                spp, seed, ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in),
-                                                ptr<float>(g_sigma), ptr<float>(g_sh));
-        }
-        check(rc, "drt_nerf_render_backward_px_sh");
-    }
-    void nerf_render_forward_sh(const py::dict &props, uintptr_t sh, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_sh, uintptr_t dL_out)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        const int32_t deg = sh_degree(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_forward_sh(h_, &c, ptr<const float>(sh), deg, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
-                                            spp, seed, ptr<const float>(t_sigma), ptr<const float>(t_sh), ptr<float>(dL_out));
-        }
-        check(rc, "drt_nerf_render_forward_sh");
-    }
-    // opacity and depth outputs (drt_nerf_*_aov): five interleaved floats per ray / pixel
-    void nerf_render_primal_aov(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                uint32_t spp, uint32_t seed, uintptr_t L_out)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_primal_aov(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
-                                            seed, ptr<float>(L_out));
-        }
-        check(rc, "drt_nerf_render_primal_aov");
-    }
-    void nerf_render_backward_aov(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                  uint32_t spp, uint32_t seed, uintptr_t dL, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_emission)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_backward_aov(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
-                                              seed, ptr<const float>(dL), ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_emission));
-        }
-        check(rc, "drt_nerf_render_backward_aov");
-    }
-    void nerf_render_backward_px_aov(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                     uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
-                                     uintptr_t g_emission)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_backward_px_aov(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
-                                                 spp, seed, ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
-                                                 ptr<float>(g_emission));
-        }
-        check(rc, "drt_nerf_render_backward_px_aov");
-    }
-    void nerf_render_forward_aov(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                 uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_emission, uintptr_t dL_out)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_forward_aov(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
-                                             seed, ptr<const float>(t_sigma), ptr<const float>(t_emission), ptr<float>(dL_out));
-        }
-        check(rc, "drt_nerf_render_forward_aov");
-    }
-    // ... and the distortion output (drt_nerf_*_dist): six
-    void nerf_render_primal_dist(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                uint32_t spp, uint32_t seed, uintptr_t L_out)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_primal_dist(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
-                                            seed, ptr<float>(L_out));
-        }
-        check(rc, "drt_nerf_render_primal_dist");
-    }
-    void nerf_render_backward_dist(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                  uint32_t spp, uint32_t seed, uintptr_t dL, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_emission)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_backward_dist(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
-                                              seed, ptr<const float>(dL), ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_emission));
-        }
-        check(rc, "drt_nerf_render_backward_dist");
-    }
-    void nerf_render_backward_px_dist(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                     uint32_t spp, uint32_t seed, uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma,
-                                     uintptr_t g_emission)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_backward_px_dist(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off,
-                                                 spp, seed, ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
-                                                 ptr<float>(g_emission));
-        }
-        check(rc, "drt_nerf_render_backward_px_dist");
-    }
-    void nerf_render_forward_dist(const py::dict &props, uintptr_t emission, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
-                                 uint32_t spp, uint32_t seed, uintptr_t t_sigma, uintptr_t t_emission, uintptr_t dL_out)
-    {
-        drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_nerf_render_forward_dist(h_, &c, ptr<const float>(emission), ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp,
-                                             seed, ptr<const float>(t_sigma), ptr<const float>(t_emission), ptr<float>(dL_out));
-        }
-        check(rc, "drt_nerf_render_forward_dist");
     }
     void film_develop_n(uintptr_t L, uint64_t n_pixels, uint32_t spp, uint32_t channels, uintptr_t image)
     {
@@ -631,19 +487,7 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("film_loss_grad", &Integrator::film_loss_grad)
         .def("render_backward_px", &Integrator::render_backward_px)
         .def("nerf_render_backward_px", &Integrator::nerf_render_backward_px)
-        .def("nerf_render_primal_sh", &Integrator::nerf_render_primal_sh)
-        .def("nerf_render_backward_sh", &Integrator::nerf_render_backward_sh)
-        .def("nerf_render_backward_px_sh", &Integrator::nerf_render_backward_px_sh)
-        .def("nerf_render_forward_sh", &Integrator::nerf_render_forward_sh)
         .def("nerf_sh_tile_phases", &Integrator::nerf_sh_tile_phases)
-        .def("nerf_render_primal_aov", &Integrator::nerf_render_primal_aov)
-        .def("nerf_render_backward_aov", &Integrator::nerf_render_backward_aov)
-        .def("nerf_render_backward_px_aov", &Integrator::nerf_render_backward_px_aov)
-        .def("nerf_render_forward_aov", &Integrator::nerf_render_forward_aov)
-        .def("nerf_render_primal_dist", &Integrator::nerf_render_primal_dist)
-        .def("nerf_render_backward_dist", &Integrator::nerf_render_backward_dist)
-        .def("nerf_render_backward_px_dist", &Integrator::nerf_render_backward_px_dist)
-        .def("nerf_render_forward_dist", &Integrator::nerf_render_forward_dist)
         .def("film_develop_n", &Integrator::film_develop_n)
         .def("film_backward_n", &Integrator::film_backward_n)
         .def("debug_eval", &Integrator::debug_eval)

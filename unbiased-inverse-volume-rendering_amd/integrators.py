@@ -577,6 +577,12 @@ class NeRFIntegrator(_DeviceIntegrator):
         return 3 + len(self.aovs())
 
     @property
+    def _kind(self) -> int:
+        """The output kind, first argument of the handle's nerf_render_* methods: 0 plain, 1 spherical harmonics, 2 opacity and depth,
+        3 ... and distortion (csrc/drt_device.h: NerfOut)."""
+        return 1 if self.sh_degree else 3 if self._distortion else 2 if self._aovs else 0
+
+    @property
     def sh_degree(self) -> int:
         return self._sh_degree
 
@@ -671,64 +677,11 @@ class NeRFIntegrator(_DeviceIntegrator):
             raise ValueError(f"emission must have shape (Z,Y,X,3), got {tuple(em.shape)}")
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)
-        if self.sh_degree:
-            return self._sample_sh(mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents)
-        if self._aovs:
-            return self._sample_aov(mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents)
-        if mode == ADMode.Primal:
-            L = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            h.nerf_render_primal(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp),
-                                 sampler.seed_value, L.data_ptr())
-            return L, True, L
-        if mode == ADMode.Backward:
-            if δL is None or state_in is None or grads is None:
-                raise ValueError("sample(Backward) needs δL, state_in and grads")
-            _check(δL, (n, 3), dev, "δL")
-            _check(state_in, (n, 3), dev, "state_in")
-            gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
-            _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
-            _check(ge, tuple(em.shape), dev, "grads[emission]")
-            h.nerf_render_backward(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp),
-                                   sampler.seed_value, δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
-            return None, True, None
-        dL = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        h.nerf_render_forward(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-                              _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
-        return dL, True, None
-
-    def _sample_sh(self, mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents):
-        """sample() with sh_degree > 0: the drt_nerf_render_*_sh calls (the checks of sample() are done)."""
-        props, off, spp, seed = self._nerf_props(), int(ray.ray_offset), int(ray.spp), sampler.seed_value
-        if mode == ADMode.Primal:
-            L = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            h.nerf_render_primal_sh(props, em.data_ptr(), ro, rd, n, off, spp, seed, L.data_ptr())
-            return L, True, L
-        if mode == ADMode.Backward:
-            if δL is None or state_in is None or grads is None:
-                raise ValueError("sample(Backward) needs δL, state_in and grads")
-            _check(δL, (n, 3), dev, "δL")
-            _check(state_in, (n, 3), dev, "state_in")
-            gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
-            _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
-            _check(ge, tuple(em.shape), dev, "grads[emission]")
-            h.nerf_render_backward_sh(props, em.data_ptr(), ro, rd, n, off, spp, seed, δL.data_ptr(), state_in.data_ptr(),
-                                      gs.data_ptr(), ge.data_ptr())
-            return None, True, None
-        dL = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        h.nerf_render_forward_sh(props, em.data_ptr(), ro, rd, n, off, spp, seed, _ptr(tangents[SIGMA_T_KEY]),
-                                 _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
-        return dL, True, None
-
-    def _sample_aov(self, mode, scene, sampler, ray, h, dev, em, n, ro, rd, δL, state_in, grads, tangents):
-        """sample() with aovs: the drt_nerf_render_*_aov calls, five channels [r, g, b, opacity, depth], or - with distortion - the
-        drt_nerf_render_*_dist calls, six (the checks of sample() are done)."""
-        props, off, spp, seed = self._nerf_props(), int(ray.ray_offset), int(ray.spp), sampler.seed_value
         C = self.channels
-        primal, backward, forward = ((h.nerf_render_primal_dist, h.nerf_render_backward_dist, h.nerf_render_forward_dist) if self._distortion
-                                     else (h.nerf_render_primal_aov, h.nerf_render_backward_aov, h.nerf_render_forward_aov))
+        job = (self._kind, self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value)
         if mode == ADMode.Primal:
             L = torch.empty((n, C), dtype=torch.float32, device=dev)
-            primal(props, em.data_ptr(), ro, rd, n, off, spp, seed, L.data_ptr())
+            h.nerf_render_primal(*job, L.data_ptr())
             return L, True, L
         if mode == ADMode.Backward:
             if δL is None or state_in is None or grads is None:
@@ -738,10 +691,10 @@ class NeRFIntegrator(_DeviceIntegrator):
             gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
             _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
             _check(ge, tuple(em.shape), dev, "grads[emission]")
-            backward(props, em.data_ptr(), ro, rd, n, off, spp, seed, δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
+            h.nerf_render_backward(*job, δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
             return None, True, None
         dL = torch.empty((n, C), dtype=torch.float32, device=dev)
-        forward(props, em.data_ptr(), ro, rd, n, off, spp, seed, _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
+        h.nerf_render_forward(*job, _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[EMISSION_KEY]), dL.data_ptr())
         return dL, True, None
 
     def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
@@ -765,10 +718,8 @@ class NeRFIntegrator(_DeviceIntegrator):
         gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
         _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
         _check(ge, tuple(em.shape), dev, "grads[emission]")
-        call = (h.nerf_render_backward_px_sh if self.sh_degree else h.nerf_render_backward_px_dist if self._distortion
-                else h.nerf_render_backward_px_aov if self._aovs else h.nerf_render_backward_px)
-        call(self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-             grad_image.data_ptr(), grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
+        h.nerf_render_backward_px(self._kind, self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
+                                  grad_image.data_ptr(), grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
 
 
 class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
