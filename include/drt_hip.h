@@ -135,9 +135,10 @@ int drt_set_phase_hg2(drt_handle h, float g1, float g2, float weight);
  * another table drops path cache and ray orders, the same table changes nothing, drt_set_medium leaves it alone, drt_set_phase /
  * drt_set_phase_hg2 replace it, every test hook that drt_set_debug_flags accepts runs these kernels.  The call waits
  * for the handle's stream.  NULL values, n out of range or a negative / non-finite / all-zero table: DRT_ERR_INVALID_ARGUMENT (checked
- * before the handle).  drt_set_phase called with kind 3 returns DRT_ERR_INVALID_ARGUMENT.  No gradients with respect to the values: a
- * non-NULL grad_phase_g / non-zero t_phase_g of the *_phase entry points on such a handle returns DRT_ERR_UNSUPPORTED.  Node spacing is
- * uniform only. */
+ * before the handle).  drt_set_phase called with kind 3 returns DRT_ERR_INVALID_ARGUMENT.  The table has no g: a non-NULL grad_phase_g /
+ * non-zero t_phase_g of the *_phase entry points on such a handle returns DRT_ERR_UNSUPPORTED.  The gradient with respect to the values:
+ * drt_render_backward_phase_tab, drt_render_backward_px_phase_tab and drt_render_forward_phase_tab (the handle keeps I for them).  Node
+ * spacing is uniform only. */
 int drt_set_phase_tab(drt_handle h, const float *values, int32_t n);
 /* params.update(opt) after an optimizer step (python/optimize.py:354) and
  * medium.set_majorant_resolution_factor (:195-199): refresh the majorant from
@@ -197,6 +198,18 @@ int drt_render_backward(drt_handle h, const float *rays_o, const float *rays_d, 
  * grad_phase_g adds nothing to the counters (so does drt_render_forward_phase with t_phase_g != 0). */
 int drt_render_backward_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
                               uint32_t seed, const float *dL, const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g);
+/* drt_render_backward that also differentiates with respect to the RAW values v_0 .. v_{n-1} of a tabulated phase function
+ * (drt_set_phase_tab, before normalisation): grad_values is a DEVICE pointer to n floats, accumulated with += (NULL: exactly
+ * drt_render_backward).  Estimator: the one of drt_render_backward_phase with the score
+ *   d log p(c) / d v_k = h_k(c) / (2 pi I p(c)) - m_k / I     (h_k: the hat function of node k, m_k its integral, I = sum v_k m_k)
+ * from the main path only, so sum_k v_k grad_k = 0 up to rounding (the phase function does not depend on the table's scale).  The kernels
+ * (kTabGrad instantiations in the _tab units) add two hat-function shares per event to a handle-owned sink of 8 replicas (64 for tables of up to 255 nodes) of n + 1 floats
+ * - lanes of a wave that hit the same interval are combined first - with global float atomics: like the grid gradients, the result is NOT
+ * bit-reproducible from run to run.  A small kernel then sums the replicas in a fixed order and applies the affine map above.
+ * A non-NULL grad_values on a handle without a table, or with a table whose smallest value is 0 (the score would be 0 / 0 at an NEE site),
+ * is refused with DRT_ERR_UNSUPPORTED.  No counting variants: such a call on a counting handle counts nothing. */
+int drt_render_backward_phase_tab(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                                  uint32_t seed, const float *dL, const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_values);
 
 /* NeRFIntegrator properties (python/integrators/nerf.py:30-35; density_noise_std is
  * effectively unsupported in the reference, nerf.py:160-162, and is not exposed). */
@@ -233,6 +246,14 @@ int drt_render_forward(drt_handle h, const float *rays_o, const float *rays_d, u
 int drt_render_forward_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
                              uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
                              float *dL_out, float t_phase_g);
+/* drt_render_forward with a tangent of the table values as well: t_values is a DEVICE pointer to n floats (NULL: exactly
+ * drt_render_forward; refused as drt_render_backward_phase_tab refuses grad_values).  The call reads the n floats to the host (it waits
+ * for the handle's stream: the cost of differentiating the table), prepares tau_k = t_k / (2 pi I) and kappa = sum t_k m_k / I in float64
+ * and runs the kTabGrad forward kernels, whose score along the tangent is lerp(tau)(c) / p(c) - kappa: the transpose of
+ * drt_render_backward_phase_tab's estimator, written per ray without atomics - it repeats bit for bit. */
+int drt_render_forward_phase_tab(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
+                                 uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
+                                 float *dL_out, const float *t_values);
 /* Forward mode of the nerf march: dL_out[n][3] = J(ray) . (t_sigma_t, t_emission), by dual numbers through the march (no
  * L_in needed).  At the relu kink the derivative is taken as the adjoint takes it (none unless the raw density is > 0). */
 int drt_nerf_render_forward(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
@@ -409,6 +430,10 @@ int drt_render_backward_px(drt_handle h, const float *rays_o, const float *rays_
 int drt_render_backward_px_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
                                  uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
                                  const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g);
+/* ... and with grad_values as in drt_render_backward_phase_tab */
+int drt_render_backward_px_phase_tab(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
+                                     uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
+                                     const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_values);
 int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const float *emission, const float *rays_o,
                                 const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
                                 const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,

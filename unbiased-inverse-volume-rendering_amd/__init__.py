@@ -5,7 +5,7 @@ Host-side mirror of the reference's plugin surface for the hot path
 hand-written HIP library (csrc/, C ABI in include/drt_hip.h).  Importing this
 package does not need a GPU; creating an integrator handle does.
 """
-from .scene import (ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, ConstantEmitter, EnvmapEmitter, GridMedium, HG2Phase, HGPhase, IsotropicPhase,
+from .scene import (ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, PHASE_TAB_KEY, SIGMA_T_KEY, ConstantEmitter, EnvmapEmitter, GridMedium, HG2Phase, HGPhase, IsotropicPhase,
                     PerspectiveSensor, Scene, TabPhase, cube_test_scene, scene_to)
 from .integrators import (ADMode, FusedNerfDrtIntegrator, IndependentSampler, NeRFIntegrator, RayBatch, VolpathSimpleIntegrator, load_dict,
                           register_integrator, sample_tea_32, sh_basis, sh_from_rgb)
@@ -25,7 +25,7 @@ from .image_io import read_image, write_image
 from .fd import fd_gradients
 
 __all__ = [
-    "ALBEDO_KEY", "EMISSION_KEY", "PHASE_G_KEY", "SIGMA_T_KEY", "ConstantEmitter", "EnvmapEmitter", "GridMedium", "HG2Phase", "HGPhase", "IsotropicPhase",
+    "ALBEDO_KEY", "EMISSION_KEY", "PHASE_G_KEY", "PHASE_TAB_KEY", "SIGMA_T_KEY", "ConstantEmitter", "EnvmapEmitter", "GridMedium", "HG2Phase", "HGPhase", "IsotropicPhase",
     "PerspectiveSensor", "TabPhase",
     "Scene", "cube_test_scene", "scene_to", "ADMode", "IndependentSampler", "RayBatch",
     "VolpathSimpleIntegrator", "NeRFIntegrator", "FusedNerfDrtIntegrator", "load_dict", "register_integrator", "sample_tea_32", "sh_basis", "sh_from_rgb", "IntegratorConfig",

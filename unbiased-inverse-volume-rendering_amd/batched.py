@@ -16,8 +16,8 @@ import torch
 
 from .distributed import ShardSpec, allreduce_gradients
 from .integrators import ADMode, IndependentSampler, RayBatch, sample_tea_32
-from .render import _grid, _with_params, alloc_grads, g_grad, grad_keys, phase_param, sharded_support
-from .scene import PerspectiveSensor, Scene
+from .render import _grid, _with_params, alloc_grads, g_grad, grad_keys, phase_param, phase_tab_param, sharded_support
+from .scene import PHASE_TAB_KEY, PerspectiveSensor, Scene
 
 
 def sensors_to_device(sensors: Sequence[PerspectiveSensor], device) -> torch.Tensor:
@@ -58,11 +58,14 @@ class _BatchedRenderOp(torch.autograd.Function):
     rank are rendered - random streams keyed by the GLOBAL entry / ray index, so the union over ranks is
     the unsharded batch bit for bit - and the backward pass sums the gradient grids over the ranks with
     ONE all-reduce.  Unsharded calls never communicate.  `g`: the HG asymmetry (PHASE_G_KEY, a 0-d tensor read to the host once
-    per call) or None - the medium's phase as it is; its gradient travels in the same all-reduce as the grids'."""
+    per call) or None - the medium's phase as it is; its gradient travels in the same all-reduce as the grids'.  `tab` (a TabPhase):
+    `g` is then the 1-D tensor of that table's raw values (PHASE_TAB_KEY, read to the host by the caller; unsharded only)."""
 
     @staticmethod
-    def forward(ctx, p0, p1, g, scene, integrator, sensor_table, batch_size, spp, spp_grad, seed, seed_grad, shard):
-        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()), None if g is None else float(g.detach()))
+    def forward(ctx, p0, p1, g, scene, integrator, sensor_table, batch_size, spp, spp_grad, seed, seed_grad, shard, tab):
+        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()),
+                          None if g is None or tab is not None else float(g.detach()), phase_tab=tab)
+        ctx.tab = tab is not None
         first, count = shard.batch_range(batch_size)
         ro, rd, sidx, pix = sample_batch(integrator, sc, sensor_table, count, spp, seed, 1, first)
         batch = RayBatch(n_rays=count * spp, spp=spp, o=ro, d=rd, ray_offset=first * spp)
@@ -83,13 +86,14 @@ class _BatchedRenderOp(torch.autograd.Function):
         sampler = IndependentSampler(ctx.seed_grad, ctx.spp_grad)
         L, _, state = integ.sample(ADMode.Primal, sc, sampler.clone(), batch)                    # :255-264
         dL = integ.film_backward(sc, grad_image.contiguous(), ctx.spp_grad)                      # :272-306
-        want_g = ctx.needs_input_grad[2]
-        grads = alloc_grads(sc, grad_keys(integ, want_g))
+        want_g = ctx.needs_input_grad[2] and not ctx.tab
+        want_tab = ctx.needs_input_grad[2] and ctx.tab
+        grads = alloc_grads(sc, grad_keys(integ, want_g) + ((PHASE_TAB_KEY,) if want_tab else ()))
         support = sharded_support(sc, grads, ctx.shard)
         integ.sample(ADMode.Backward, sc, sampler, batch, δL=dL, state_in=state, grads=grads)    # :309-318
         allreduce_gradients(grads, shard=ctx.shard, support=support)
         k0, k1 = integ.param_keys
-        return (grads[k0], grads[k1], g_grad(grads, want_g)) + (None,) * 9
+        return (grads[k0], grads[k1], grads[PHASE_TAB_KEY].clone() if want_tab else g_grad(grads, want_g)) + (None,) * 10
 
 
 def render_batch(batch_size: int, scene: Scene, sensors=None, film_size=None,
@@ -101,7 +105,8 @@ def render_batch(batch_size: int, scene: Scene, sensors=None, film_size=None,
     (`film` / `sampler` are returned as given: the device film is stateless here).
     `shard` (world > 1): the outputs hold this rank's entries `shard.batch_range(batch_size)` only and the
     backward pass all-reduces the gradient grids; scale the local loss by `local_loss_scale`.
-    `params[PHASE_G_KEY]`: the HG asymmetry g as in `render` (overrides `medium.phase.g`, differentiable)."""
+    `params[PHASE_G_KEY]`: the HG asymmetry g as in `render` (overrides `medium.phase.g`, differentiable).  `params[PHASE_TAB_KEY]`:
+    the raw values of a TabPhase table as in `render` (differentiable; unsharded)."""
     if integrator is None:
         raise ValueError("render_batch: an integrator is required")
     if spp <= 0:
@@ -122,12 +127,13 @@ def render_batch(batch_size: int, scene: Scene, sensors=None, film_size=None,
     for k in keys:
         if not isinstance(params[k], torch.Tensor):
             raise TypeError(f"render_batch: params['{k}'] must be a torch device tensor")
-    g = phase_param(scene, integrator, params, params[keys[0]].device)
+    tab = phase_tab_param(scene, integrator, params, params[keys[0]].device, shard, "render_batch")
+    g = tab[0] if tab is not None else phase_param(scene, integrator, params, params[keys[0]].device)
     if sensor_table is None:
         sensor_table = sensors_to_device(sensors, params[keys[0]].device)
     image, sidx, pix = _BatchedRenderOp.apply(params[keys[0]], params[keys[1]], g, scene, integrator, sensor_table,
                                               int(batch_size), int(spp), int(spp_grad), int(seed), int(seed_grad),
-                                              shard or ShardSpec())
+                                              shard or ShardSpec(), None if tab is None else tab[1])
     return image, film, sampler, sidx, pix
 
 

@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cmath>
@@ -67,6 +68,9 @@ struct drt_handle_s {
     float *d_majorant = nullptr;   // [2]; behind them, from float drt::kTabOffset on, the table of a tabulated phase (drt_set_phase_tab; drt_device.h: TabView)
     size_t majorant_bytes = 0;     // ... the allocation's size (it grows with the table and never shrinks)
     std::vector<float> tab_values; // the caller's table as drt_set_phase_tab last took it (the same table again changes nothing)
+    double tab_I = 0.0;            // ... its integral I = sum v_k m_k (float64) and its smallest value: the table-value gradient
+    float tab_min = 0.0f;          //     (drt_render_*_phase_tab) maps its sink with I and needs a strictly positive table
+    DevBuf tab_sink;               // the adjoint's sink block of that gradient: R replicas of N + 1 floats (drt_device.h: TabSink)
     // the global majorant as the HOST last saw it: drt_params_changed copies it to pinned memory behind the reduction and records an event; launches
     // look at it when the event has completed (never waiting) - a hint for kernel choice only (a thin medium: Params::sq_rounds), stale by design
     float *h_majorant = nullptr;   // pinned, [1]
@@ -413,12 +417,13 @@ enum class Route {
 // phase: the instantiations of the handle's phase function (tracer_phase)
 struct Choice { Route route; drt::Phase phase; };
 
-// The phase a tracing launch of this handle runs with.  grad_g: the derivative with respect to g too (kHGGrad: an HG handle only) - an adjoint
-// launch with a sink in Params::L_out (drt_render_backward_phase), a forward launch with a g tangent (drt_render_forward_phase)
+// The phase a tracing launch of this handle runs with.  grad_g: the derivative with respect to the phase parameter too (kHGGrad: an HG handle's g,
+// kTabGrad: a tabulated handle's values) - an adjoint launch with a sink in Params::L_out (drt_render_backward_phase / _phase_tab), a forward
+// launch with a phase tangent (drt_render_forward_phase / _phase_tab)
 drt::Phase tracer_phase(drt_handle h, bool grad_g)
 {
     if (h->phase_kind == DRT_PHASE_HG2) return drt::Phase::kHG2;
-    if (h->phase_kind == DRT_PHASE_TAB) return drt::Phase::kTab;
+    if (h->phase_kind == DRT_PHASE_TAB) return grad_g ? drt::Phase::kTabGrad : drt::Phase::kTab;
     if (h->phase_kind == DRT_PHASE_HG) return grad_g ? drt::Phase::kHGGrad : drt::Phase::kHG;
     return drt::Phase::kIso;
 }
@@ -441,7 +446,8 @@ drt::Phase tracer_phase(drt_handle h, bool grad_g)
 //   Two-lobe Henyey-Greenstein phase (drt_set_phase_hg2): the HG choice among the kHG2 instantiations (drt_sq_hg2.hip, drt_coop_hg2.hip,
 //   drt_coop_super_hg2.hip, drt_own_hg2.hip); no g-gradient kernels.
 //   Tabulated phase (drt_set_phase_tab): the HG choice among the kTab instantiations (drt_sq_tab.hip, drt_coop_tab.hip, drt_coop_super_tab.hip,
-//   drt_own_tab.hip); no phase-parameter gradient kernels.
+//   drt_own_tab.hip).  The table-value gradient (drt_render_backward_phase_tab: a sink block in Params::L_out) runs the kTabGrad instantiations
+//   of the same kernels, as the g-gradient does.
 Choice choose_tracer(drt_handle h, const drt::Params &P, bool adjoint)
 {
     const uint32_t f = h->debug_flags;
@@ -1212,7 +1218,8 @@ int drt_set_phase_tab(drt_handle h, const float *values, int32_t n)
     if (h->side) DRT_HIP_CHECK(h, hipStreamSynchronize(h->side));
     if (h->nerf_stream) DRT_HIP_CHECK(h, hipStreamSynchronize(h->nerf_stream));
     const size_t head = (size_t) drt::kTabOffset * sizeof(float);
-    const size_t need = head + N * (2 * sizeof(float) + sizeof(uint32_t));
+    // (... | tangent nodes x N: written by drt_render_forward_phase_tab, read by the kTabGrad forward kernels only)
+    const size_t need = head + N * (2 * sizeof(float) + sizeof(uint32_t) + sizeof(float));
     if (need > h->majorant_bytes) {                              // grow: the two majorant scalars move along
         float *fresh = nullptr;
         DRT_HIP_CHECK(h, hipMalloc(&fresh, need));
@@ -1225,6 +1232,7 @@ int drt_set_phase_tab(drt_handle h, const float *values, int32_t n)
     DRT_HIP_CHECK(h, hipMemcpy(base, nodes.data(), nodes.size() * sizeof(float), hipMemcpyHostToDevice));
     DRT_HIP_CHECK(h, hipMemcpy(base + nodes.size() * sizeof(float), guide.data(), guide.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     h->tab_values.assign(values, values + N);
+    h->tab_I = I; h->tab_min = *std::min_element(values, values + N);
     drt::Params &B = h->base;
     h->phase_kind = DRT_PHASE_TAB;
     std::memcpy(&B.phase_g, &n, sizeof(float));                  // the node count, as integer bits (tab_view)
@@ -1411,12 +1419,25 @@ int drt_render_primal(drt_handle h, const float *rays_o, const float *rays_d, ui
     return rc;
 }
 
+// Replicas of the table-value gradient's sink (drt_device.h: TabSink; a workgroup adds to replica blockIdx.x % R): one per XCD's worth of
+// workgroups - consecutive workgroups are dispatched round-robin over the eight XCDs, so the atomics on one replica come from one XCD and
+// meet in that XCD's L2 slice of requests instead of eight.  ("Gradient with respect to the table values")
+#ifndef DRT_TAB_REPLICAS
+#define DRT_TAB_REPLICAS 8          // measured: 1 / 8 / 32
+#endif
+constexpr int kTabReplicas = DRT_TAB_REPLICAS;
+static_assert(kTabReplicas <= drt::kTabMaxReplicas, "tab_sink clamps the replica count");
+// ... and a coarse table (up to kTabCoarseNodes nodes: the whole launch adds to a few dozen addresses per replica, and the wave-level combine
+// cannot take all of that away) gets the most replicas tab_sink takes: 64 replicas of 256 floats are 64 KiB
+constexpr int kTabCoarseNodes = 255;
+static int tab_replicas(int n_nodes) { return n_nodes <= kTabCoarseNodes ? drt::kTabMaxReplicas : kTabReplicas; }
+
 // the adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel, drt_render_backward_px) is given
 // grad_phase_g (drt_render_backward_phase, an HG handle): dLoss/dg is added to *grad_phase_g - it travels in Params::L_out, which no adjoint
 // kernel otherwise reads or writes, and selects the GG kernels (choose_tracer)
 static int render_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
                            uint32_t seed, const float *dL, const float *dL_pix, const float *L_in, float *grad_sigma_t, float *grad_albedo,
-                           float *grad_phase_g = nullptr)
+                           float *grad_phase_g = nullptr, float *grad_tab = nullptr)
 {
     int rc;
     DeviceGuard g(h->device);
@@ -1424,6 +1445,18 @@ static int render_backward(drt_handle h, const float *rays_o, const float *rays_
     fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
     P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_albedo;
     P.L_out = grad_phase_g;
+    // grad_tab (drt_render_backward_phase_tab, a tabulated handle): the kTabGrad kernels add to a zeroed sink block of tab_replicas(N) replicas
+    // (Params::L_out; the replica count as integer bits in Params::phase_tg), which launch_tab_finalise maps into grad_tab behind the launches
+    const int tab_n = grad_tab ? (int) h->tab_values.size() : 0;
+    const int tab_r = tab_replicas(tab_n);
+    if (grad_tab) {
+        const size_t bytes = (size_t) tab_r * (size_t) (tab_n + 1) * sizeof(float);
+        DRT_TRY(h->tab_sink.grow(h, bytes, kMust));
+        DRT_HIP_CHECK(h, hipMemsetAsync(h->tab_sink.p, 0, bytes, h->stream));
+        P.L_out = h->tab_sink.as<float>();
+        const int32_t reps = tab_r;
+        std::memcpy(&P.phase_tg, &reps, sizeof(float));
+    }
     // capacity: 48 sigma_t and 6 colour records per ray (headline workload: 12.3 and 1.4); beyond it the
     // tracer falls back to direct atomics (emit_record), so this is a performance choice only
     const uint64_t job_rays = n_rays;
@@ -1432,6 +1465,11 @@ static int render_backward(drt_handle h, const float *rays_o, const float *rays_
         return timed_launch(h, 1, Q, true);
     });
     h->pcache_sig.valid = false;
+    if (rc == DRT_OK && grad_tab) {
+        const double delta = 2.0 / (double) (tab_n - 1), I = h->tab_I;
+        DRT_HIP_CHECK(h, drt::launch_tab_finalise(h->tab_sink.as<float>(), tab_r, tab_n, (float) (1.0 / (6.283185307179586476925286766559 * I)),
+                                                  (float) (delta / I), (float) (0.5 * delta / I), grad_tab, h->stream));
+    }
     return rc;
 }
 
@@ -1472,6 +1510,30 @@ int drt_render_backward_phase(drt_handle h, const float *rays_o, const float *ra
     return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo, grad_phase_g);
 }
 
+// the table-value gradient arguments of the *_phase_tab entry points: only a tabulated handle has values to differentiate, and they must be
+// strictly positive (the score is h_k / (2 pi I p) - m_k / I: p = 0 at an NEE site would make it 0 / 0)
+static int check_phase_tab_grad(drt_handle h, const char *what, bool wanted)
+{
+    if (wanted && h->phase_kind != DRT_PHASE_TAB)
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the handle's phase function is not tabulated - a gradient with respect to the table values needs "
+                                            "drt_set_phase_tab", what);
+    if (wanted && !(h->tab_min > 0.0f))
+        return fail(h, DRT_ERR_UNSUPPORTED, "%s: a differentiated table must be strictly positive (its smallest value is %g)", what,
+                    (double) h->tab_min);
+    return DRT_OK;
+}
+
+int drt_render_backward_phase_tab(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                                  uint32_t seed, const float *dL, const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_values)
+{
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
+    DRT_TRY(check_phase_tab_grad(h, "drt_render_backward_phase_tab", grad_values != nullptr));
+    if (n_rays == 0) return DRT_OK;
+    if (!dL || !L_in || !grad_sigma_t || !grad_albedo)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_phase_tab: null dL / L_in / gradient buffer");
+    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo, nullptr, grad_values);
+}
+
 // ---- forward mode: one launch over the job's rays, dL_out written once per ray.  No sub-batches (nothing is recorded), no path cache, no
 // ray schedule from a primal pass (the forward kernels finish every path on its own lane; an order would only be a schedule anyway)
 static void forward_params(drt::Params &P, const float *t_sigma, const float *t_colour, float *dL_out)
@@ -1496,6 +1558,41 @@ static int render_forward(drt_handle h, const float *rays_o, const float *rays_d
     P.L_in = L_in;
     if (h->phase_kind != DRT_PHASE_HG2) P.phase_tg = t_phase_g;    // (HG2: its g2 travels in phase_tg, and t_phase_g is 0: check_phase_grad)
     DRT_HIP_CHECK(h, drt::launch_trace_coop_fwd(P, tracer_phase(h, t_phase_g != 0.0f), h->stream));
+    return DRT_OK;
+}
+
+// t_values (device, N floats): the tangent of the table values.  tau_k = t_k / (2 pi I) and kappa = sum t_k m_k / I are prepared on the host in
+// float64 and rounded once (one read-back of N floats per call: the synchronisation is the cost of differentiating the table); tau goes behind
+// the guide words of the table block, kappa into Params::phase_tg, and the kTabGrad forward kernels run
+int drt_render_forward_phase_tab(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
+                                 uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
+                                 float *dL_out, const float *t_values)
+{
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
+    DRT_TRY(check_phase_tab_grad(h, "drt_render_forward_phase_tab", t_values != nullptr));
+    if (n_rays == 0) return DRT_OK;
+    if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase_tab: null L_in / dL_out");
+    if (!t_values) return render_forward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_in, t_sigma_t, t_albedo, dL_out, 0.0f);
+    DeviceGuard g(h->device);
+    const size_t N = h->tab_values.size();
+    std::vector<float> tv(N);
+    DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream));           // (a forward launch in flight may still read the tangent nodes)
+    DRT_HIP_CHECK(h, hipMemcpy(tv.data(), t_values, N * sizeof(float), hipMemcpyDeviceToHost));
+    const double delta = 2.0 / (double) (N - 1), I = h->tab_I, two_pi = 6.283185307179586476925286766559;
+    double kappa = 0.0;
+    for (size_t k = 0; k < N; ++k) {
+        if (!std::isfinite(tv[k])) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase_tab: t_values[%zu] is not finite", k);
+        kappa += (double) tv[k] * ((k == 0 || k + 1 == N) ? 0.5 * delta : delta);
+        tv[k] = (float) ((double) tv[k] / (two_pi * I));
+    }
+    char *tau = reinterpret_cast<char *>(h->d_majorant) + (size_t) drt::kTabOffset * sizeof(float) + N * (2 * sizeof(float) + sizeof(uint32_t));
+    DRT_HIP_CHECK(h, hipMemcpy(tau, tv.data(), N * sizeof(float), hipMemcpyHostToDevice));
+    drt::Params P;
+    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    forward_params(P, t_sigma_t, t_albedo, dL_out);
+    P.L_in = L_in;
+    P.phase_tg = (float) (kappa / I);
+    DRT_HIP_CHECK(h, drt::launch_trace_coop_fwd(P, drt::Phase::kTabGrad, h->stream));
     return DRT_OK;
 }
 
@@ -2250,6 +2347,19 @@ int drt_render_backward_px_phase(drt_handle h, const float *rays_o, const float 
     DRT_TRY(check_px(h, "drt_render_backward_px_phase", n_rays, spp, grad_image, n_pixels));
     return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo,
                            grad_phase_g);
+}
+
+int drt_render_backward_px_phase_tab(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
+                                     uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
+                                     const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_values)
+{
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
+    DRT_TRY(check_phase_tab_grad(h, "drt_render_backward_px_phase_tab", grad_values != nullptr));
+    if (!L_in || !grad_sigma_t || !grad_albedo)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_px_phase_tab: null L_in / gradient buffer");
+    DRT_TRY(check_px(h, "drt_render_backward_px_phase_tab", n_rays, spp, grad_image, n_pixels));
+    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo, nullptr,
+                           grad_values);
 }
 
 int drt_film_develop_n(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, uint32_t channels, float *image)

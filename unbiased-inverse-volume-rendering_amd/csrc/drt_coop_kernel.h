@@ -14,11 +14,12 @@ using namespace coop;
 // TAIL: the second launch of a specialised kernel - its workgroups start from 256 paths of the tail pool each
 // (CoopTracer::wg_handoff) instead of from rays, and finish them
 // PH: the phase function (CoopTracer).  kHG, kHGGrad, kHG2, kTab: those kernels run without hand-off and tail pool; kHGGrad (adjoint): the
-// g-gradient too - each wave adds the sum of its lanes' terms to *Params::L_out with one atomic at its end
+// g-gradient too - each wave adds the sum of its lanes' terms to *Params::L_out with one atomic at its end; kTabGrad (adjoint): the table-value
+// gradient - Params::L_out is the sink block (drt_device.h: TabSink), each wave adds the sum of its lanes' coefficients to its replica's W
 template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, Phase PH = Phase::kIso>
 __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRIMAL) trace_coop_kernel(const Params P)
 {
-    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad;
+    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, TG = PH == Phase::kTabGrad;
     if constexpr (TAIL) { if (blockIdx.x * 256u >= *P.tail_count) return; }   // (workgroup-uniform) nothing for this workgroup
     uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map.  Workgroup b runs on XCD b % 8 (observed dispatch order, used for speed only); consecutive ray chunks are spatially coherent, so XCD k is given the k-th contiguous run of DRT_XCD_RUN workgroups of every group of 8 runs: its private 4 MiB L2 then serves one image region instead of every 8th 8-pixel strip (tail blocks keep the identity map)
     if (P.block_order) b = P.block_order[blockIdx.x];            // heavy blocks first (adjoint: this job's primal costs; primal: the previous launch's)
@@ -38,7 +39,7 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
     if constexpr (ADJ && !SUPER) {                              // rays of similar length share a wave (ray_perm_kernel)
         if (P.ray_perm) i = (i_block & ~(uint64_t) (kPermGroup - 1)) + P.ray_perm[i_block + threadIdx.x];
     }
-    static_assert(!GG || (ADJ && !TAIL), "the g-gradient kernels (kHGGrad) are adjoint kernels and have no tail launch");
+    static_assert(!(GG || TG) || (ADJ && !TAIL), "the phase-gradient kernels (kHGGrad, kTabGrad) are adjoint kernels and have no tail launch");
     CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, PH> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
@@ -134,6 +135,13 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
         if ((threadIdx.x & 63) == 0 && v != 0.0f) atomicAdd(P.L_out, v);
     }
+    if constexpr (TG) {                                         // W of this workgroup's replica, likewise
+        float v = tr.g_acc;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        const TabSink K = tab_sink(P);
+        if ((threadIdx.x & 63) == 0 && v != 0.0f) atomicAdd(K.rep + K.N, v);
+    }
     if constexpr (!ADJ) {
         if (P.ray_iters && job && !(SPEC && tr.wgc)) P.ray_iters[i] = (uint8_t) (tr.iters < 255u ? tr.iters : 255u);   // sort key of ray_perm_kernel
         if (P.block_cost && !TAIL) {
@@ -158,7 +166,8 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
 // Forward mode (drt_render_forward): CoopTracer<FWD> runs the adjoint's paths with dL = 1, gathering from the tangent grids where the
 // adjoint splats (the tangent grids are Params::g_sigma / g_albedo), and writes J t of its ray to L_out - once, from the ray's own lane (no hand-off, no tail pool, no atomics: the result is
 // bit-reproducible).  The global majorant's NEE walks take every step on the walk's own lane (CoopTracer::coop_rt).
-// PH = kHGGrad: J t includes t_g (Params::phase_tg) times the derivative with respect to g
+// PH = kHGGrad: J t includes t_g (Params::phase_tg) times the derivative with respect to g; kTabGrad: the derivative along the table tangent
+// (tau behind the guide words of the table block, kappa in Params::phase_tg: tab_tangent_score)
 template <bool ENV, bool SPEC, bool SUPER, Phase PH = Phase::kIso>
 __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(const Params P)
 {
@@ -244,8 +253,8 @@ hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
 template <bool SUPER, Phase PH>
 hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx, bool *called)
 {
-    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad;
-    constexpr Phase kPlain = GG ? Phase::kHG : PH;
+    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad || PH == Phase::kTabGrad;   // (GG: a phase-gradient launch of either kind)
+    constexpr Phase kPlain = PH == Phase::kHGGrad ? Phase::kHG : PH == Phase::kTabGrad ? Phase::kTab : PH;
     if (P.n_rays <= P.ray_first) return hipSuccess;
     if (GG) {
         if (!adjoint || !P.L_out || P.tail_pool) return hipErrorInvalidValue;

@@ -5,5 +5,6 @@
 namespace drt {
 
 template struct CoopUnit<Phase::kTab, true, false>;
+template struct CoopUnit<Phase::kTabGrad, true, false>;     // adjoint and forward kernels with the gradient with respect to the table values
 
 }  // namespace drt

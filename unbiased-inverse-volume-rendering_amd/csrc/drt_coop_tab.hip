@@ -7,5 +7,6 @@
 namespace drt {
 
 template struct CoopUnit<Phase::kTab, false, false>;
+template struct CoopUnit<Phase::kTabGrad, false, false>;     // adjoint and forward kernels with the gradient with respect to the table values
 
 }  // namespace drt

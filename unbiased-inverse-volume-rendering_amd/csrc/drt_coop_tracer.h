@@ -128,9 +128,14 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 //   kHG2 (H2): the two-lobe mixture (drt_device.h: hg2_eval, hg2_sample) - g1 in Params::phase_g, g2 in Params::phase_tg, the second lobe's
 //   share in Params::phase_w.  The scatter sites keep the next_1d draw the other instantiations drop: it chooses the lobe.
 //   kTab (TB; HG too): the tabulated phase function (drt_device.h: tab_eval, tab_sample) - its table behind Params::majorant (tab_view).
+//   kTabGrad (TG; TB too): the derivative with respect to the table values as well, from the main path only, at the three sites of kHGGrad
+//   (drt_device.h: TabSink).  Adjoint: every term adds its two hat-function shares to the sink (tab_sink_add, at wave-uniform places) and its
+//   coefficient to g_acc (the kernel adds a wave's sum to the replica's W once); forward mode: g_S carries the scores along the tangent
+//   (tab_tangent_score) and every contribution adds c (g_S + explicit term) to tg.
 template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, Phase PH = Phase::kIso>
 struct CoopTracer {
-    static constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2, TB = PH == Phase::kTab;
+    static constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2, TG = PH == Phase::kTabGrad,
+                          TB = PH == Phase::kTab || TG;
     const Params &P;
     float maj, inv_maj;
     const uint32_t *mocc;   // SUPER: non-empty supergrid cells (LDS copy) or nullptr
@@ -150,8 +155,8 @@ struct CoopTracer {
     float fsum;             // FWD: sum over the steps of the current transmittance walk of -(1/maj) / tr * sigma_t'(p)
     V3 hg_wi, hg_wd;        // HG: the incoming direction at the current vertex (set before each NEE / recursive path), the emitter direction
                             // sample_emitter drew (members, not parameters: the isotropic instantiations keep the signatures they compile from)
-    float g_acc;            // GG, adjoint: this lane's share of dLoss/dg
-    float g_S;              // GG, forward mode: sum of the scores of the directions the main path has sampled
+    float g_acc;            // GG, adjoint: this lane's share of dLoss/dg; TG: of W, the sum of the terms' coefficients
+    float g_S;              // GG / TG, forward mode: sum of the scores of the directions the main path has sampled
 
     __device__ __forceinline__ CoopTracer(const Params &p) : P(p)
     {
@@ -159,7 +164,7 @@ struct CoopTracer {
         ray_index = 0; rec = nullptr; slots = nullptr; occ = nullptr; jump = nullptr; pc = nullptr; work = 0; iters = 0;
         mocc = nullptr; wgc = nullptr; i_block = 0; tail_load = false;
         if constexpr (HG) { hg_wi = v3(0, 0, 1); hg_wd = v3(0, 0, 1); }
-        if constexpr (GG) { g_acc = 0.0f; g_S = 0.0f; }
+        if constexpr (GG || TG) { g_acc = 0.0f; g_S = 0.0f; }
 #if DRT_PHASE_PROFILE
         ph_t = __builtin_readcyclecounter();
 #endif
@@ -488,7 +493,19 @@ struct CoopTracer {
         if constexpr (kFwd) fsum = 0.0f;
         float ds_pdf = sample_emitter<kFwd>(job, p, S, nullptr, emitted, cmode, ce);   // :385
         float gx = 0.0f;                                                        // GG (main path): (2w - 1) hg_score(mu_e), the NEE term's log-derivative
-        if constexpr (GG && ADJ) {
+        int nee_i = 0; float nee_t = 0.0f, nee_p = 1.0f;                        // TG (main path): interval, fraction and density of the emitter direction
+        (void) nee_i; (void) nee_t; (void) nee_p;
+        if constexpr (TG && ADJ) {
+            const float mu = (hg_wd.x * hg_wi.x + hg_wd.y * hg_wi.y) + hg_wd.z * hg_wi.z;
+            const TabView T = tab_view(P);
+            const float pv = tab_eval_cos(T, mu, nee_i, nee_t);
+            float w = mis_weight(ds_pdf, pv);                                   // :391
+#pragma unroll
+            for (int k = 0; k < 3; ++k) contrib[k] = job ? ((beta[k] * pv) * w) * emitted[k] : 0.0f;
+            nee_p = pv;
+            gx = 2.0f * w - 1.0f;                                               // adjoint: the coefficient's factor; forward mode: times the score along the tangent
+            if constexpr (FWD) { if (job) gx *= tab_tangent_score(P, T, nee_i, nee_t, pv); }
+        } else if constexpr (GG && ADJ) {
             const float mu = (hg_wd.x * hg_wi.x + hg_wd.y * hg_wi.y) + hg_wd.z * hg_wi.z;
             const float pv = hg_eval_cos(P.phase_g, mu);
             float w = mis_weight(ds_pdf, pv);                                   // :391
@@ -524,11 +541,22 @@ struct CoopTracer {
 #pragma unroll
                     for (int k = 0; k < 3; ++k) tg[k] += (dL[k] * contrib[k]) * f;
                 }
+                if constexpr (TG) {
+                    const float f = g_S + gx;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) tg[k] += (dL[k] * contrib[k]) * f;
+                }
             }
         } else if constexpr (ADJ) {                                             // :393-401
             float adj[3] = { 0.0f, 0.0f, 0.0f };
             if (job) { adj[0] = dL[0] * contrib[0]; adj[1] = dL[1] * contrib[1]; adj[2] = dL[2] * contrib[2]; }
             if constexpr (GG) { if (job) g_acc += gx * ((adj[0] + adj[1]) + adj[2]); }
+            if constexpr (TG) {                                                 // (every lane of the wave is here: `job` carries the divergence)
+                const float c = job ? gx * ((adj[0] + adj[1]) + adj[2]) : 0.0f;
+                g_acc += c;
+                const float cp = c / nee_p;
+                tab_sink_add(tab_sink(P), job, nee_i, cp * (1.0f - nee_t), cp * nee_t);
+            }
             float unused[3];
             (void) sample_emitter<true>(job, p, clone, adj, unused);
         }
@@ -879,6 +907,9 @@ struct CoopTracer {
         float last_pdf = RECURSIVE ? ps->last_pdf : 1.0f;
         constexpr bool kGG = GG && ADJ && !RECURSIVE;                           // the g-gradient terms: main path of the adjoint / forward pass
         float s_last = 0.0f;                                                    // kGG: score of the last sampled direction
+        constexpr bool kTG = TG && ADJ && !RECURSIVE;                           // the table-value gradient terms, likewise
+        int tab_i = -1; float tab_t = 0.0f;                                     // kTG: interval and fraction of the last sampled direction (its density: last_pdf)
+        (void) tab_i; (void) tab_t;
 
         // DRTReservoir(n=1) + DRTPathState (:94-96, :710-765)
         int r_depth = -1; float r_si_t = kInf; Ray r_ray = ray;
@@ -1016,6 +1047,8 @@ struct CoopTracer {
                 }
             }
 
+            float dep_c = 0.0f; bool dep = false;                               // kTG, adjoint: the phase site's term, added to the sink behind the divergent block
+            (void) dep_c; (void) dep;
             if (run) {
                 if (did_scatter) {                                              // :221-230
                     float u1 = 0.0f;                                            // (H2: chooses the lobe)
@@ -1024,6 +1057,14 @@ struct CoopTracer {
                     if constexpr (H2) {
                         ray.o = mei.p; ray.d = hg2_sample(P.phase_g, P.phase_tg, P.phase_w, u1, ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf);
                         ray.maxt = kLargest;
+                    }
+                    else if constexpr (kTG) {                                        // the score term: d log p / dv times what the path collects after it
+                        float mu;
+                        const TabView T = tab_view(P);
+                        ray.o = mei.p; ray.d = tab_sample(T, ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf, mu, tab_i, tab_t);
+                        ray.maxt = kLargest;
+                        if constexpr (FWD) { s_last = tab_tangent_score(P, T, tab_i, tab_t, last_pdf); g_S += s_last; }
+                        else { dep_c = (dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2]; dep = true; }   // result: L below this vertex
                     }
                     else if constexpr (TB) {
                         ray.o = mei.p; ray.d = tab_sample(tab_view(P), ux, uy, v3(-ray.d.x, -ray.d.y, -ray.d.z), last_pdf);
@@ -1050,6 +1091,11 @@ struct CoopTracer {
                     escaped = true;
                 }
                 ++it;
+            }
+            if constexpr (kTG && !FWD) {                                        // (wave-uniform: inside `if (any_active)` only)
+                g_acc += dep_c;
+                const float cp = dep ? dep_c / last_pdf : 0.0f;
+                tab_sink_add(tab_sink(P), dep, tab_i, cp * (1.0f - tab_t), cp * tab_t);
             }
             }
             if (any_active) round_end(RECURSIVE ? 4 : 5, Jit);
@@ -1081,6 +1127,27 @@ struct CoopTracer {
 #pragma unroll
                         for (int k = 0; k < 3; ++k) tg[k] += (dL[k] * ((beta[k] * w) * Le[k])) * f;
                     } else g_acc += ex * ((dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2]);   // result: that emission
+                }
+            }
+            if constexpr (kTG) {                                                // the escape hit, as above: 2 (1 - w) times the last sampled direction's score
+                const bool esc = job && escaped && has_scattered && tab_i >= 0;
+                float w = 1.0f, Le[3] = { 0.0f, 0.0f, 0.0f };
+                if (esc) {
+                    const float e_pdf = emitter_eval_pdf<ENV>(P, ray.d, Le);
+                    w = use_nee() ? mis_weight(last_pdf, e_pdf) : 1.0f;
+                }
+                const float ew = use_nee() ? 2.0f * (1.0f - w) : 0.0f;          // the MIS weight's log-derivative, up to the score
+                if constexpr (FWD) {                                            // c (g_S + ex), c = the emission the primal pass added
+                    if (esc) {
+                        const float f = g_S + ew * s_last;
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) tg[k] += (dL[k] * ((beta[k] * w) * Le[k])) * f;
+                    }
+                } else {                                                        // (every lane of the wave is here)
+                    const float c = esc ? ew * ((dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2]) : 0.0f;   // result: that emission
+                    g_acc += c;
+                    const float cp = esc ? c / last_pdf : 0.0f;
+                    tab_sink_add(tab_sink(P), esc, tab_i, cp * (1.0f - tab_t), cp * tab_t);
                 }
             }
         } else {                                                                // :263-287

@@ -340,7 +340,8 @@ enum class Phase : int {
     kHG,       // Henyey-Greenstein (drt_set_phase)
     kHGGrad,   // ... with the derivative with respect to g (adjoint and forward kernels only)
     kHG2,      // mixture of two Henyey-Greenstein lobes (drt_set_phase_hg2); no g-gradient
-    kTab,      // tabulated over the cosine of the scattering angle (drt_set_phase_tab; TabView below); no phase-parameter gradient
+    kTab,      // tabulated over the cosine of the scattering angle (drt_set_phase_tab; TabView below)
+    kTabGrad,  // ... with the derivative with respect to the table values (adjoint and forward kernels only; TabSink below)
 };
 
 // What a nerf launch writes per ray: the `kind` argument of the nerf launchers (drt_launch.h), which pick the unit that holds the kind's kernels.
@@ -520,7 +521,7 @@ static_assert(sizeof(Params) == 752, "the kernel parameter block keeps its size"
 //                  t = min(max(t, 0), 1) (a NaN becomes 0); c = min(max(-1 + ((float) i + t) * delta, -1), 1)
 //                  direction: hg_sample's frame and azimuth with cos_t = c (sin_t = sqrt(max(0, 1 - c * c)), phi = 2 pi uy, lz = -c); mu = -c
 //                  pdf = y_i + t * (y_{i+1} - y_i) (the sampled weight stays 1)
-// The phase site consumes the draws of every other phase (next_1d dropped, then next_2d).  No gradient with respect to the values.
+// The phase site consumes the draws of every other phase (next_1d dropped, then next_2d).  The gradient with respect to the values: TabSink below.
 // ---------------------------------------------------------------------------
 constexpr int kTabOffset = 4;                       // floats between Params::majorant and the first node (16 bytes: the float2 nodes stay aligned)
 constexpr int kTabMinNodes = 2, kTabMaxNodes = 65536;
@@ -543,14 +544,22 @@ __device__ __forceinline__ TabView tab_view(const Params &P)
     return T;
 }
 
-__device__ __forceinline__ float tab_eval_cos(const TabView &T, float mu)
+// (i, t: the interval of the physics cosine c = -mu and the fraction inside it - the two hat functions that are non-zero there are
+//  h_i = 1 - t and h_{i+1} = t: what the table-value gradient takes)
+__device__ __forceinline__ float tab_eval_cos(const TabView &T, float mu, int &i, float &t)
 {
     const float nf = (float) T.n;
     const float x = fminf(fmaxf((1.0f - mu) * (0.5f * nf), 0.0f), nf);
-    const int i = min((int) x, T.n - 1);
-    const float t = x - (float) i;
+    i = min((int) x, T.n - 1);
+    t = x - (float) i;
     const float y0 = T.nodes[i].x, y1 = T.nodes[i + 1].x;
     return y0 + t * (y1 - y0);
+}
+
+__device__ __forceinline__ float tab_eval_cos(const TabView &T, float mu)
+{
+    int i; float t;
+    return tab_eval_cos(T, mu, i, t);
 }
 
 __device__ __forceinline__ float tab_eval(const TabView &T, V3 wo, V3 wi)
@@ -578,14 +587,14 @@ __device__ __forceinline__ int tab_find(const TabView &T, float x)
 }
 
 // (mu: the cosine dot(wo, wi) of the sampled direction, tab_eval_cos(T, mu) = pdf up to the rounding of c)
-__device__ __forceinline__ V3 tab_sample(const TabView &T, float ux, float uy, V3 wi, float &pdf, float &mu)
+// (i, t: the sampled interval and the fraction inside it, as tab_eval_cos returns them)
+__device__ __forceinline__ V3 tab_sample(const TabView &T, float ux, float uy, V3 wi, float &pdf, float &mu, int &i, float &t)
 {
-    const int i = tab_find(T, ux);
+    i = tab_find(T, ux);
     const float2 a = T.nodes[i], b = T.nodes[i + 1];
     const float delta = 2.0f / (float) T.n;
     const float s = kTabTwoPi * delta;
     const float r = ux - a.y;
-    float t;
     if (a.x == b.x) t = r / (s * a.x);
     else {
         const float rp = r / s;
@@ -609,10 +618,89 @@ __device__ __forceinline__ V3 tab_sample(const TabView &T, float ux, float uy, V
     return v3((fs.x * lx + ft.x * ly) + wi.x * lz, (fs.y * lx + ft.y * ly) + wi.y * lz, (fs.z * lx + ft.z * ly) + wi.z * lz);
 }
 
+__device__ __forceinline__ V3 tab_sample(const TabView &T, float ux, float uy, V3 wi, float &pdf, float &mu)
+{
+    int i; float t;
+    return tab_sample(T, ux, uy, wi, pdf, mu, i, t);
+}
+
 __device__ __forceinline__ V3 tab_sample(const TabView &T, float ux, float uy, V3 wi, float &pdf)
 {
     float mu;
     return tab_sample(T, ux, uy, wi, pdf, mu);
+}
+
+// ---------------------------------------------------------------------------
+// Gradient with respect to the table values v_k (Phase::kTabGrad; DESIGN.md, "Gradient with respect to the table values").  With the hat
+// functions h_k, m_k = int h_k (delta inside, delta / 2 at the two ends) and I = sum v_k m_k the score of the density is
+//   d log p(c) / d v_k = h_k(c) / (2 pi I p(c)) - m_k / I
+// so an event with coefficient w (phase site <dL, result>, NEE (2 w_mis - 1) <dL, contrib>, escape 2 (1 - w_mis) <dL, result>) in interval i
+// at fraction t with density p adds  S_i += w (1 - t) / p,  S_{i+1} += w t / p  and  W += w;  tab_finalise_kernel (drt_kernels.hip) then adds
+// S_k / (2 pi I) - (m_k / I) W to the caller's gradient.
+// The adjoint's sink (Params::L_out) is a block of R replicas of N + 1 floats, {S_0 .. S_{N-1}, W} each; R travels as integer bits in
+// Params::phase_tg (which a tabulated handle does not use otherwise).  A workgroup adds to replica blockIdx.x % R.  Before anything leaves
+// the wave, lanes that hit the same interval are combined (tab_sink_add): on a forward-peaked table nearly every event of a wave falls
+// into the same few intervals.  The adds are global float atomics: the table gradient, like the grid gradients, is not bit-reproducible
+// from run to run.
+// Forward mode: the tangent t_v enters through tau_k = t_k / (2 pi I) (N floats behind the guide words) and kappa = sum t_k m_k / I
+// (Params::phase_tg); the score along the tangent is lerp(tau)(c) / p(c) - kappa (tab_tangent_score).  No atomics: bit-reproducible.
+// ---------------------------------------------------------------------------
+#ifndef DRT_TAB_COMBINE
+#define DRT_TAB_COMBINE 1           // 0 (tools/bench_phase_tab_grad.py's ablation build): every lane adds its own two values
+#endif
+constexpr int kTabCombineRounds = 4;                // leader rounds of tab_sink_add; lanes still unmatched after them add on their own
+constexpr int kTabCombineMin = 4;                   // ... and a round whose leader shares its interval with fewer lanes than this ends the rounds: on a fine
+                                                    // table (1025 nodes and more) a wave's events rarely share an interval, and the cross-lane sums then cost
+                                                    // more than the atomics they save (measured: DESIGN.md)
+constexpr int kTabMaxReplicas = 64;
+
+struct TabSink {
+    float *rep;             // this workgroup's replica: [N] S | [1] W
+    int N;
+};
+
+__device__ __forceinline__ TabSink tab_sink(const Params &P)
+{
+    const int N = min(max(__float_as_int(P.phase_g), kTabMinNodes), kTabMaxNodes);
+    const int R = min(max(__float_as_int(P.phase_tg), 1), kTabMaxReplicas);
+    TabSink K;
+    K.rep = P.L_out + (size_t) (blockIdx.x % (unsigned) R) * (size_t) (N + 1);
+    K.N = N;
+    return K;
+}
+
+// S_i += a0, S_{i+1} += a1 for every lane with `on` set.  Called by EVERY lane of the wave (wave-uniform control flow; `on` carries the
+// divergence).  Round r: the first lane still waiting is the leader, the lanes waiting for the leader's interval are summed across the wave
+// and retired, the leader adds the two sums.  What is left after kTabCombineRounds rounds - or after a round that found fewer than
+// kTabCombineMin lanes on the leader's interval - is added lane by lane.
+__device__ __forceinline__ void tab_sink_add(const TabSink &K, bool on, int i, float a0, float a1)
+{
+    int key = (on && i >= 0 && i < K.N - 1 && (a0 != 0.0f || a1 != 0.0f)) ? i : -1;   // (the bound: no write outside the replica whatever i is)
+#if DRT_TAB_COMBINE
+    const int lane = (int) (threadIdx.x & 63u);
+    for (int r = 0; r < kTabCombineRounds; ++r) {
+        const unsigned long long live = __ballot(key >= 0);
+        if (!live) break;                                                      // (wave-uniform)
+        const int leader = __ffsll((long long) live) - 1;
+        const int lk = __shfl(key, leader, 64);
+        const bool m = key == lk;
+        if (__popcll(__ballot(m)) < kTabCombineMin) break;                     // (wave-uniform) a sparse wave: every lane for itself
+        float s0 = m ? a0 : 0.0f, s1 = m ? a1 : 0.0f;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_xor(s0, off, 64); s1 += __shfl_xor(s1, off, 64); }
+        if (lane == leader) { atomicAdd(K.rep + lk, s0); atomicAdd(K.rep + lk + 1, s1); }
+        if (m) key = -1;
+    }
+#endif
+    if (key >= 0) { atomicAdd(K.rep + key, a0); atomicAdd(K.rep + key + 1, a1); }
+}
+
+// the tangent nodes tau behind the guide words of the handle's table block (drt_render_forward_phase_tab)
+__device__ __forceinline__ float tab_tangent_score(const Params &P, const TabView &T, int i, float t, float pdf)
+{
+    const float *tau = reinterpret_cast<const float *>(T.guide + (T.n + 1));
+    const float a = tau[i], b = tau[i + 1];
+    return (a + t * (b - a)) / pdf - P.phase_tg;
 }
 
 // ---------------------------------------------------------------------------

@@ -551,6 +551,7 @@ template <typename F> hipError_t coop_cell(const Params &P, Phase phase, F f)
     case Phase::kHGGrad: return coop_cell<Phase::kHGGrad>(P, f);
     case Phase::kHG2: return coop_cell<Phase::kHG2>(P, f);
     case Phase::kTab: return coop_cell<Phase::kTab>(P, f);
+    case Phase::kTabGrad: return coop_cell<Phase::kTabGrad>(P, f);
     }
     return hipErrorInvalidValue;
 }
@@ -575,6 +576,7 @@ hipError_t launch_trace_sq(const Params &P, Phase phase, bool adjoint, bool coun
     case Phase::kHGGrad: return SqUnit<Phase::kHGGrad>::trace(P, adjoint, count, n_cus, stream);
     case Phase::kHG2: return SqUnit<Phase::kHG2>::trace(P, adjoint, count, n_cus, stream);
     case Phase::kTab: return SqUnit<Phase::kTab>::trace(P, adjoint, count, n_cus, stream);
+    case Phase::kTabGrad: return SqUnit<Phase::kTabGrad>::trace(P, adjoint, count, n_cus, stream);
     }
     return hipErrorInvalidValue;
 }
@@ -903,6 +905,29 @@ hipError_t launch_film_backward(const float *grad_image, uint64_t n_pixels, uint
     if (((uintptr_t) dL & 15u) == 0)
         hipLaunchKernelGGL(film_backward_wide_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, stream, grad_image, n_pixels, spp, dL);
     else hipLaunchKernelGGL(film_backward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, grad_image, n_pixels, spp, dL);
+    return hipGetLastError();
+}
+
+// The table-value gradient's last step (drt_device.h: TabSink): the R replicas of the sink block are summed in index order and mapped to
+//   grad_k += S_k / (2 pi I) - (m_k / I) W,   m_k = delta inside, delta / 2 at the two ends
+// (inv_two_pi_I = 1 / (2 pi I), m_in = delta / I, m_end = delta / (2 I): from the host's float64 preparation, rounded once).  One thread per node.
+__global__ void __launch_bounds__(256) tab_finalise_kernel(const float *sink, int R, int N, float inv_two_pi_I, float m_in, float m_end, float *grad)
+{
+    const int k = (int) (blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= N) return;
+    float S = 0.0f, W = 0.0f;
+    for (int r = 0; r < R; ++r) {
+        const float *rep = sink + (size_t) r * (size_t) (N + 1);
+        S += rep[k]; W += rep[N];
+    }
+    const float m = (k == 0 || k == N - 1) ? m_end : m_in;
+    grad[k] += S * inv_two_pi_I - m * W;
+}
+
+hipError_t launch_tab_finalise(const float *sink, int R, int N, float inv_two_pi_I, float m_in, float m_end, float *grad, hipStream_t stream)
+{
+    if (N <= 0 || R <= 0) return hipSuccess;
+    hipLaunchKernelGGL(tab_finalise_kernel, dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, stream, sink, R, N, inv_two_pi_I, m_in, m_end, grad);
     return hipGetLastError();
 }
 

@@ -112,6 +112,12 @@ template <Phase PH, bool SUPER, bool OWN> struct CoopUnit {
     static hipError_t trace(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx, bool *called);
     static hipError_t forward(const Params &P, hipStream_t stream);
 };
+// The gradient with respect to the values of a tabulated phase function (Phase::kTabGrad; drt_device.h: TabSink): an adjoint launch takes the
+// sink block in Params::L_out - R replicas of N + 1 floats {S_0 .. S_{N-1}, W}, zeroed by the caller, R as integer bits in Params::phase_tg -
+// and adds to it with float atomics (run-to-run non-deterministic, as the grid gradients are); launch_tab_finalise then sums the replicas in
+// index order and adds S_k / (2 pi I) - (m_k / I) W to grad[k].  A forward launch reads the tangent nodes tau behind the guide words of the
+// table block and kappa from Params::phase_tg; it uses no atomics and repeats bit for bit.
+hipError_t launch_tab_finalise(const float *sink, int R, int N, float inv_two_pi_I, float m_in, float m_end, float *grad, hipStream_t stream);
 hipError_t launch_ray_perm(const uint8_t *iters, uint64_t n_rays, uint16_t *perm, uint32_t *block_cost, hipStream_t stream);
 hipError_t launch_block_order(const uint32_t *cost, uint32_t n_blocks, uint32_t *order, bool heavy_first, hipStream_t stream);
 hipError_t launch_untile(const Params &P, hipStream_t stream);

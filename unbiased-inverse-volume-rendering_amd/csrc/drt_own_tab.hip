@@ -8,5 +8,7 @@ namespace drt {
 
 template struct CoopUnit<Phase::kTab, false, true>;
 template struct CoopUnit<Phase::kTab, true, true>;
+template struct CoopUnit<Phase::kTabGrad, false, true>;      // adjoint and forward kernels with the gradient with respect to the table values
+template struct CoopUnit<Phase::kTabGrad, true, true>;
 
 }  // namespace drt

@@ -151,6 +151,17 @@ public:
         }
         check(rc, "drt_render_backward_phase");
     }
+    void render_backward_phase_tab(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dL,
+                                   uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_values)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_render_backward_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
+                                               ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo), ptr<float>(g_values));
+        }
+        check(rc, "drt_render_backward_phase_tab");
+    }
     static drt_nerf_config nerf_cfg(const py::dict &p)
     {
         drt_nerf_config c{};
@@ -247,6 +258,17 @@ public:
                                           ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), t_phase);
         }
         check(rc, "drt_render_forward_phase");
+    }
+    void render_forward_phase_tab(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
+                                  uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out, uintptr_t t_values)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_render_forward_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
+                                              ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), ptr<const float>(t_values));
+        }
+        check(rc, "drt_render_forward_phase_tab");
     }
     void fused_render_primal(const py::dict &props, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp,
                              uint32_t seed, uintptr_t L_nerf, uintptr_t L_drt)
@@ -346,6 +368,18 @@ public:
                                               ptr<float>(g_albedo), ptr<float>(g_phase));
         }
         check(rc, "drt_render_backward_px_phase");
+    }
+    void render_backward_px_phase_tab(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed,
+                                      uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_values)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_render_backward_px_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
+                                                  ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
+                                                  ptr<float>(g_albedo), ptr<float>(g_values));
+        }
+        check(rc, "drt_render_backward_px_phase_tab");
     }
     void film_develop_n(uintptr_t L, uint64_t n_pixels, uint32_t spp, uint32_t channels, uintptr_t image)
     {
@@ -472,6 +506,9 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("render_backward_phase", &Integrator::render_backward_phase)
         .def("render_forward_phase", &Integrator::render_forward_phase)
         .def("render_backward_px_phase", &Integrator::render_backward_px_phase)
+        .def("render_backward_phase_tab", &Integrator::render_backward_phase_tab)
+        .def("render_forward_phase_tab", &Integrator::render_forward_phase_tab)
+        .def("render_backward_px_phase_tab", &Integrator::render_backward_px_phase_tab)
         .def("nerf_render_primal", &Integrator::nerf_render_primal)
         .def("nerf_render_backward", &Integrator::nerf_render_backward)
         .def("render_forward", &Integrator::render_forward)

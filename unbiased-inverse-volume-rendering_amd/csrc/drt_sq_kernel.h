@@ -287,12 +287,17 @@ __device__ __forceinline__ void sq_push_all(unsigned long long *ctl, uint16_t *q
 // pdf at the sampled direction, and the lobe is chosen by the next_1d draw the other instantiations drop - nothing else has to travel.
 // kTab (TB; drt_sq_tab.hip): the tabulated phase function (drt_set_phase_tab; drt_device.h: tab_eval, tab_sample) at the same sites, its table
 // behind Params::majorant (tab_view).  The record is the HG one.
+// kTabGrad (TG, TB too; adjoint kernels of drt_sq_tab.hip): the derivative with respect to the table values of the main paths as well (DESIGN.md,
+// "Gradient with respect to the table values"; drt_device.h: TabSink) - the three terms of kHGGrad, each added to the sink block behind
+// Params::L_out right behind its block of the pass (tab_sink_add: the lanes of a wave that hit the same interval are combined first - a batch
+// is 64 events of one kind), the coefficients summed per lane and added to the replica's W once per wave.  The record's extra uint4 holds
+// {interval, fraction, pdf} of the main path's last phase sampling where kHGGrad keeps {score, pdf}.
 template <bool ADJ, bool COUNT, bool ENV, bool MG, bool QUAD = false, bool TAILM = false, bool ROUNDS = false, Phase PH = Phase::kIso>
 __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P)
 {
-    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2, TB = PH == Phase::kTab;
+    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2, TG = PH == Phase::kTabGrad, TB = PH == Phase::kTab || TG;
     static_assert(!HG || (!TAILM && !ROUNDS), "the HG kernels (kHG, kHGGrad, kHG2, kTab) have no tail launch and no ROUNDS variant");
-    static_assert(!GG || ADJ, "the g-gradient kernels (kHGGrad) are adjoint kernels");
+    static_assert(!(GG || TG) || ADJ, "the phase-gradient kernels (kHGGrad, kTabGrad) are adjoint kernels");
     constexpr int NWV = DRT_SQ_THREADS / 64;
     constexpr int R4 = 7;                                                    // uint4 per ray record in LDS
     static_assert(ADJ || !QUAD, "the primal pass of the quadratic estimator is the ordinary one");
@@ -303,7 +308,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
     constexpr bool SOLO = TAILM && !MG;
     constexpr int NB = QUAD ? 9 : 6;                                         // uint4 of part b of the global record (adjoint)
     constexpr int NC = ADJ ? 3 + NB : 3;                                     // uint4 per ray in global memory (Params::sq_cold)
-    constexpr int NCW = NC + (HG ? 1 : 0) + (GG ? 1 : 0);                    // ... HG: + {wi, last pdf}; GG: + {score, pdf} of the main path
+    constexpr int NCW = NC + (HG ? 1 : 0) + ((GG || TG) ? 1 : 0);            // ... HG: + {wi, last pdf}; GG: + {score, pdf} of the main path (TG: {interval, fraction, pdf})
     // LDS record: [0] {tn.x, tn.y, tn.z, cell} [1] {td.x, td.y, td.z, steps left (9 bits per axis) + direction signs}
     // [2] {tau, tmax, t, acc} - the flight (a finished flight leaves its cell's majorant, 0: left the segment, in [0].x) -
     // [3] {rd, wmax} [4] {wo, wt} [5] {G.state, G.inc}: the generator the current walk draws from (the alt sampler in the main
@@ -407,7 +412,9 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
     (void) cold_h;
     float2 *cold_g = (float2 *) (cold_a + (NC + 1) * NRAY);                   // GG: [NRAY] {score, pdf} of the main path's last phase sampling
     (void) cold_g;
-    float g_acc = 0.0f;                                                        // GG: this lane's share of dLoss/dg
+    float4 *cold_t = (float4 *) (cold_a + (NC + 1) * NRAY);                   // TG: [NRAY] {interval (integer bits), fraction, pdf, -} likewise
+    (void) cold_t;
+    float g_acc = 0.0f;                                                        // GG: this lane's share of dLoss/dg; TG: of W, the sum of the terms' coefficients
     const uint32_t xcc = sq_xcc_id();
     // (with a ray order the queue positions cover whole units: the last unit may reach past the launch's last ray)
     const uint64_t span = P.order ? (uint64_t) P.order_units * P.order_unit : P.n_rays - P.ray_first;
@@ -846,6 +853,9 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                         if constexpr (ADJ) {
                             dL[0] = P.dL[3 * i]; dL[1] = P.dL[3 * i + 1]; dL[2] = P.dL[3 * i + 2];
                             result[0] = P.L_in[3 * i]; result[1] = P.L_in[3 * i + 1]; result[2] = P.L_in[3 * i + 2];
+                            // TG: no phase sampling of this ray's main path yet - interval -1 (tab_sink_add takes none), pdf 1: the escape term
+                            // never reads what an earlier ray left in the record
+                            if constexpr (TG) cold_t[id] = make_float4(__int_as_float(-1), 0.0f, 1.0f, 0.0f);
                         }
                         depth = 0; escaped = false; has_scattered = false; scat_once = false;
                         rec_mode = false; rec_first = false;
@@ -1024,6 +1034,8 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
         // emitter direction, this block) in ONE pass
         float nee_pdf = 0.0f; bool nee_pdf_ok = false;                          // ENV: the emitter density of the direction the NEE block of THIS pass sampled
         auto rt_end_block = [&](bool behind_nee) {
+            int tg_i = -1; float tg_a0 = 0.0f, tg_a1 = 0.0f;                    // TG: this block's term, added to the sink behind it
+            (void) tg_i; (void) tg_a0; (void) tg_a1;
             if constexpr (!ADJ) {
                 if (ph == SP_RT_END && pc_on && pc_it < (int) P.path_cache_cap)
                     P.path_cache[((size_t) li * P.path_cache_cap + pc_it) * 2 + 1] =
@@ -1045,6 +1057,23 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                         result[k] = (ADJ && !rec_mode) ? result[k] - contrib[k] : result[k] + contrib[k];   // :211-214
                     }
                     if (!rec_mode) g_acc += ((2.0f * w - 1.0f) * hg_score(P.phase_g, mu)) * ((dL[0] * contrib[0] + dL[1] * contrib[1]) + dL[2] * contrib[2]);
+                } else if constexpr (TG) {                                  // ... and the NEE term of the table-value gradient: (2w - 1) <dL, contrib>
+                    const float4 hw = cold_h[id];
+                    const float mu = (rd.x * hw.x + rd.y * hw.y) + rd.z * hw.z;
+                    int ti; float tt;
+                    const float pv = tab_eval_cos(tab_view(P), mu, ti, tt);
+                    const float w = mis_weight(ds_pdf, pv);                 // :391
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        contrib[k] = ((beta[k] * pv) * w) * (val[k] * wt);
+                        result[k] = (ADJ && !rec_mode) ? result[k] - contrib[k] : result[k] + contrib[k];   // :211-214
+                    }
+                    if (!rec_mode) {
+                        const float c = (2.0f * w - 1.0f) * ((dL[0] * contrib[0] + dL[1] * contrib[1]) + dL[2] * contrib[2]);
+                        g_acc += c;
+                        const float cp = c / pv;
+                        tg_i = ti; tg_a0 = cp * (1.0f - tt); tg_a1 = cp * tt;
+                    }
                 } else if constexpr (H2) {                                  // ... of the mixture
                     const float4 hw = cold_h[id];
                     const float pv = hg2_eval(P.phase_g, P.phase_tg, P.phase_w, rd, v3(hw.x, hw.y, hw.z));
@@ -1091,6 +1120,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                     }
                 }
             }
+            if constexpr (TG) tab_sink_add(tab_sink(P), tg_i >= 0, tg_i, tg_a0, tg_a1);   // (every lane of the wave is here)
         };
         // QUAD: the main path comes back from the DRT detour of a vertex (no vertex selected, or the recursive path has ended): the alt
         // sampler continues where the detour left it, everything else is as it was in the middle of the collision block
@@ -1144,6 +1174,8 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
 
                 // ---- phase sampling + new segment (:221-246) -------------------------------------------------------
                 SQ_BLK(2, ph == SP_PHASE);
+                int tg_i = -1; float tg_a0 = 0.0f, tg_a1 = 0.0f;               // TG: the term of the phase-sampling block / of the end-of-path block
+                (void) tg_i; (void) tg_a0; (void) tg_a1;
                 if (ph == SP_PHASE) {
                     ++pc_it;                                                    // next bounce-loop iteration (path cache index)
                     float u1 = 0.0f;                                            // (H2: chooses the lobe)
@@ -1153,6 +1185,17 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                         float4 hw = cold_h[id];
                         const V3 wi = P.use_nee ? v3(hw.x, hw.y, hw.z) : v3(-rd.x, -rd.y, -rd.z);
                         if constexpr (H2) rd = hg2_sample(P.phase_g, P.phase_tg, P.phase_w, u1, ux, uy, wi, hw.w);
+                        else if constexpr (TG) {                                     // the score term: d log p / dv <dL, result> (result: L below this vertex)
+                            float mu, tt; int ti;
+                            rd = tab_sample(tab_view(P), ux, uy, wi, hw.w, mu, ti, tt);
+                            if (!rec_mode) {
+                                const float c = (dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2];
+                                g_acc += c;
+                                const float cp = c / hw.w;
+                                tg_i = ti; tg_a0 = cp * (1.0f - tt); tg_a1 = cp * tt;
+                                cold_t[id] = make_float4(__int_as_float(ti), tt, hw.w, 0.0f);
+                            }
+                        }
                         else if constexpr (TB) rd = tab_sample(tab_view(P), ux, uy, wi, hw.w);
                         else if constexpr (GG) {                                     // the score term: s(mu) <dL, result> (result: L below this vertex)
                             float mu;
@@ -1179,6 +1222,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                     }
                     ph = active ? SP_HEAD : SP_END;
                 }
+                if constexpr (TG) { tab_sink_add(tab_sink(P), tg_i >= 0, tg_i, tg_a0, tg_a1); tg_i = -1; }   // (every lane of the wave is here)
 
                 // ---- loop head: Russian roulette, start delta tracking (:116-127) -------------------------------------
                 SQ_BLK(3, ph == SP_HEAD);
@@ -1345,6 +1389,20 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                             g_acc += ((2.0f * (1.0f - w)) * sg.x) * ((dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2]);
                         }
                     }
+                    if constexpr (TG) {                                         // the escape term, likewise, at the last sampled direction
+                        if (!rec_mode && escaped && has_scattered && P.use_nee) {   // (result: the emission the primal pass added, :263-287)
+                            float Le[3];
+                            const float e_pdf = emitter_eval_pdf<ENV>(P, rd, Le);
+                            const float4 lt = cold_t[id];
+                            if (__float_as_int(lt.x) >= 0) {                        // (a phase sampling of this main path wrote it: CoopTracer's tab_i >= 0)
+                                const float w = mis_weight(lt.z, e_pdf);
+                                const float c = (2.0f * (1.0f - w)) * ((dL[0] * result[0] + dL[1] * result[1]) + dL[2] * result[2]);
+                                g_acc += c;
+                                const float cp = c / lt.z;
+                                tg_i = __float_as_int(lt.x); tg_a0 = cp * (1.0f - lt.y); tg_a1 = cp * lt.y;
+                            }
+                        }
+                    }
                     if constexpr (!ADJ) {
                         const size_t o3 = 3 * (size_t) li;
                         P.L_out[o3] = result[0]; P.L_out[o3 + 1] = result[1]; P.L_out[o3 + 2] = result[2];
@@ -1401,6 +1459,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                         }
                     }
                 }
+                if constexpr (TG) tab_sink_add(tab_sink(P), tg_i >= 0, tg_i, tg_a0, tg_a1);   // (every lane of the wave is here)
             }
 
             // ================= (Fs) the next flight: set up and post =========================================
@@ -1664,6 +1723,13 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
         if (lane == 0 && v != 0.0f) atomicAdd(P.L_out, v);
     }
+    if constexpr (TG) {                                                        // W of this workgroup's replica, likewise
+        float v = g_acc;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        const TabSink K = tab_sink(P);
+        if (lane == 0 && v != 0.0f) atomicAdd(K.rep + K.N, v);
+    }
 #undef SQ_COUNT
 #undef SQ_PROF
 #undef SQ_STAMP
@@ -1697,12 +1763,12 @@ static uint32_t sq_rays_for(const Params &P, size_t *bytes, bool *global_majoran
 }
 
 // kHG, kHGGrad, kHG2: no tail launch, no ROUNDS kernels.  kHGGrad: the adjoint launches with the g-gradient (into *Params::L_out), without counting
-// kernels (such a launch counts nothing); its primal and counting kernels are kHG's (kPlain)
+// kernels (such a launch counts nothing); its primal and counting kernels are kHG's (kPlain).  kTabGrad: the same over kTab, Params::L_out the sink block
 template <Phase PH>
 static hipError_t launch_trace_sq_t(const Params &Pin, bool adjoint, bool count, int n_cus, hipStream_t stream)
 {
-    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad;
-    constexpr Phase kPlain = GG ? Phase::kHG : PH;
+    constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad || PH == Phase::kTabGrad;   // (GG: a phase-gradient launch of either kind)
+    constexpr Phase kPlain = PH == Phase::kHGGrad ? Phase::kHG : PH == Phase::kTabGrad ? Phase::kTab : PH;
     if (Pin.n_rays <= Pin.ray_first) return hipSuccess;
     if (HG && (Pin.tail_mode || Pin.tail_pool)) return hipErrorInvalidValue;
     if (GG) {

@@ -5,5 +5,6 @@
 namespace drt {
 
 template struct SqUnit<Phase::kTab>;
+template struct SqUnit<Phase::kTabGrad>;     // the adjoint kernels with the gradient with respect to the table values
 
 }  // namespace drt

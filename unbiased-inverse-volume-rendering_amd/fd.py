@@ -15,7 +15,7 @@ import torch
 
 from .image_io import write_image
 from .render import render_primal
-from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, require_hg
+from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, PHASE_TAB_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, TabPhase, require_hg, require_tab
 
 
 def _scene_with(scene: Scene, values: Dict[str, torch.Tensor]) -> Scene:
@@ -23,7 +23,8 @@ def _scene_with(scene: Scene, values: Dict[str, torch.Tensor]) -> Scene:
     medium = GridMedium(sigma_t=values.get(SIGMA_T_KEY, m.sigma_t), albedo=values.get(ALBEDO_KEY, m.albedo),
                         bbox_min=m.bbox_min, bbox_max=m.bbox_max, scale=m.scale,
                         majorant_resolution_factor=m.majorant_resolution_factor, emission=values.get(EMISSION_KEY, m.emission),
-                        phase=HGPhase(float(values[PHASE_G_KEY])) if PHASE_G_KEY in values else m.phase)
+                        phase=HGPhase(float(values[PHASE_G_KEY])) if PHASE_G_KEY in values
+                        else TabPhase(values[PHASE_TAB_KEY].detach().cpu().numpy()) if PHASE_TAB_KEY in values else m.phase)
     return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
 
 
@@ -33,11 +34,21 @@ def fd_gradients(output_dir: Optional[str], scene: Scene, params: Dict[str, torc
     """python/fd.py:10-77.  `params`: {key: device grid (Z, Y, X, C)} - the entries to differentiate (they replace the
     scene's grids); `loss_fn(image)` with image (H, W, 3) ((H, W, 5) with a `nerf` integrator's aovs, (H, W, 6) with its distortion output) -> scalar tensor.  Returns {key: array of d loss / d entry}.
     `central=True` uses (loss(+eps) - loss(-eps)) / (2 eps) instead of the reference's forward difference.
-    PHASE_G_KEY: the asymmetry g of an HG medium, a 0-d tensor (the result is a 0-d array)."""
+    PHASE_G_KEY: the asymmetry g of an HG medium, a 0-d tensor (the result is a 0-d array).  PHASE_TAB_KEY: the raw values of a
+    TabPhase medium, a 1-D tensor of the table's length (they stay positive under the offsets: eps below the smallest value)."""
     if integrator is None:
         raise ValueError("fd_gradients needs the integrator to render with")
+    if PHASE_G_KEY in params and PHASE_TAB_KEY in params:
+        raise ValueError(f"fd_gradients: {PHASE_G_KEY} and {PHASE_TAB_KEY} cannot be differentiated together (a medium has one phase function)")
     if PHASE_G_KEY in params:
         require_hg(scene, "fd_gradients")
+    if PHASE_TAB_KEY in params:
+        require_tab(scene, "fd_gradients")
+        v = params[PHASE_TAB_KEY]
+        if not isinstance(v, torch.Tensor) or v.dim() != 1 or v.shape[0] != len(scene.medium.phase):
+            raise ValueError(f"fd_gradients: params['{PHASE_TAB_KEY}'] must be a 1-D tensor of the table's {len(scene.medium.phase)} values")
+        if not float(v.min()) > (eps if central else 0.0):
+            raise ValueError(f"fd_gradients: params['{PHASE_TAB_KEY}'] must stay strictly positive under the offset eps = {eps}")
     s = scene.sensors[sensor]
 
     def loss_of(values, fname=None):

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from ._native import native
-from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, PerspectiveSensor, Scene, _check_phase, require_hg
+from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, PHASE_TAB_KEY, SIGMA_T_KEY, PerspectiveSensor, Scene, _check_phase, require_hg, require_tab
 
 
 class ADMode(IntEnum):
@@ -171,8 +171,8 @@ class _DeviceIntegrator:
             tangents = {}
         if not isinstance(tangents, dict):
             raise TypeError("tangents must be a dict {parameter key: tensor}")
-        tg = tangents.get(PHASE_G_KEY)
-        extra = sorted(set(tangents) - set(self.param_keys) - {PHASE_G_KEY})
+        tg, tv = tangents.get(PHASE_G_KEY), tangents.get(PHASE_TAB_KEY)
+        extra = sorted(set(tangents) - set(self.param_keys) - {PHASE_G_KEY, PHASE_TAB_KEY})
         if extra:
             raise ValueError(f"tangents for unknown parameters {extra} (this integrator's parameters: {list(self.param_keys)})")
         out = {}
@@ -189,6 +189,11 @@ class _DeviceIntegrator:
                     raise TypeError(f"tangents['{PHASE_G_KEY}'] must be a number or a 1-element float tensor, got shape {tuple(tg.shape)} {tg.dtype}")
                 tg = tg.item()
             out[PHASE_G_KEY] = float(tg)
+        if tv is not None:                       # the table tangent: N floats on the device (read to the host once by the library)
+            self._refuse_phase_tab_grad(scene, tg is not None)
+            grid = _grid_of(scene, self.param_keys[0])
+            _check(tv, (len(scene.medium.phase),), grid.device if isinstance(grid, torch.Tensor) else tv.device, f"tangents['{PHASE_TAB_KEY}']")
+            out[PHASE_TAB_KEY] = tv
         return out
 
     def _refuse_phase_grad(self, scene: Scene):
@@ -196,6 +201,25 @@ class _DeviceIntegrator:
             raise ValueError(f"the {self.__class__.__name__} has no gradient with respect to {PHASE_G_KEY} (only volpathsimple samples "
                              "a phase function)")
         require_hg(scene, self.__class__.__name__)
+
+    def _refuse_phase_tab_grad(self, scene: Scene, with_g: bool = False):
+        """The table-value gradient (PHASE_TAB_KEY), refused on the host before any device work where it is not built."""
+        if not self.phase_grad:
+            raise ValueError(f"the {self.__class__.__name__} has no gradient with respect to {PHASE_TAB_KEY} (only volpathsimple samples "
+                             "a phase function; table gradients for the nerf and fused integrators are a follow-up)")
+        if with_g:
+            raise ValueError(f"{PHASE_G_KEY} and {PHASE_TAB_KEY} cannot be differentiated together: a medium has one phase function "
+                             "(a table with a differentiable analytic lobe beside it is a follow-up)")
+        require_tab(scene, self.__class__.__name__)
+
+    def _phase_tab_grad_ptr(self, scene: Scene, grads: Dict[str, torch.Tensor], dev) -> int:
+        """The device address of grads[PHASE_TAB_KEY] (N float32, accumulated), or 0 when the table gradient is not asked for."""
+        gv = grads.get(PHASE_TAB_KEY)
+        if gv is None:
+            return 0
+        self._refuse_phase_tab_grad(scene, grads.get(PHASE_G_KEY) is not None)
+        _check(gv, (len(scene.medium.phase),), dev, f"grads['{PHASE_TAB_KEY}']")
+        return gv.data_ptr()
 
     def _phase_grad_ptr(self, scene: Scene, grads: Dict[str, torch.Tensor], dev) -> int:
         """The device address of grads[PHASE_G_KEY] (one float32, accumulated), or 0 when the g-gradient is not asked for."""
@@ -380,7 +404,9 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         with dL [n,3] = J t per ray (drt_render_forward).  Extra kwargs (`depth`, `reparam`)
         are absorbed like the reference does (volpathsimple.py:47).
         With an HG medium, grads[PHASE_G_KEY] (one float32 on the device, accumulated) receives dLoss/dg
-        and tangents[PHASE_G_KEY] (a number) adds t_g dL/dg to the forward result."""
+        and tangents[PHASE_G_KEY] (a number) adds t_g dL/dg to the forward result.  With a strictly positive TabPhase medium,
+        grads[PHASE_TAB_KEY] (N float32 on the device, accumulated; not bit-reproducible: float atomics) receives dLoss/dvalues and
+        tangents[PHASE_TAB_KEY] (N float32 on the device) adds the derivative along that tangent."""
         mode = ADMode(int(mode))
         if mode == ADMode.Forward:
             tangents = self.check_tangents(scene, tangents)
@@ -388,6 +414,8 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
                 raise ValueError("sample(Forward) needs state_in (the primal radiance of the same rays and seed)")
         if mode == ADMode.Backward and grads is not None and grads.get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)          # (before any device work: a medium without a differentiable g)
+        if mode == ADMode.Backward and grads is not None and grads.get(PHASE_TAB_KEY) is not None:
+            self._refuse_phase_tab_grad(scene, grads.get(PHASE_G_KEY) is not None)
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)
@@ -405,8 +433,11 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
             gs, ga = grads[SIGMA_T_KEY], grads[ALBEDO_KEY]
             _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
             _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
-            gp = self._phase_grad_ptr(scene, grads, dev)
-            if gp:
+            gp, gv = self._phase_grad_ptr(scene, grads, dev), self._phase_tab_grad_ptr(scene, grads, dev)
+            if gv:
+                h.render_backward_phase_tab(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
+                                            δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gv)
+            elif gp:
                 h.render_backward_phase(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
                                         δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gp)
             else:
@@ -415,8 +446,11 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
             return None, True, None
         _check(state_in, (n, 3), dev, "state_in")
         dL = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        tg = tangents.get(PHASE_G_KEY)
-        if tg:
+        tg, tv = tangents.get(PHASE_G_KEY), tangents.get(PHASE_TAB_KEY)
+        if tv is not None:
+            h.render_forward_phase_tab(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
+                                       _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr(), tv.data_ptr())
+        elif tg:
             h.render_forward_phase(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
                                    _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr(), tg)
         else:
@@ -430,6 +464,8 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         (drt_render_backward_px): the same gradients as with δL = film_backward(grad_image)."""
         if grads.get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)          # (before any device work)
+        if grads.get(PHASE_TAB_KEY) is not None:
+            self._refuse_phase_tab_grad(scene, grads.get(PHASE_G_KEY) is not None)
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)
@@ -438,8 +474,11 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         gs, ga = grads[SIGMA_T_KEY], grads[ALBEDO_KEY]
         _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
         _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
-        gp = self._phase_grad_ptr(scene, grads, dev)
-        if gp:
+        gp, gv = self._phase_grad_ptr(scene, grads, dev), self._phase_tab_grad_ptr(scene, grads, dev)
+        if gv:
+            h.render_backward_px_phase_tab(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
+                                           grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gv)
+        elif gp:
             h.render_backward_px_phase(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
                                        grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gp)
         else:
@@ -666,6 +705,8 @@ class NeRFIntegrator(_DeviceIntegrator):
             tangents = self.check_tangents(scene, tangents)
         if grads is not None and grads.get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)
+        if grads is not None and grads.get(PHASE_TAB_KEY) is not None:
+            self._refuse_phase_tab_grad(scene)
         if self.sh_degree:
             self._check_sh(scene)
         h, dev = self._bind(scene)
@@ -703,6 +744,8 @@ class NeRFIntegrator(_DeviceIntegrator):
         (drt_nerf_render_backward_px)."""
         if grads.get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)
+        if grads.get(PHASE_TAB_KEY) is not None:
+            self._refuse_phase_tab_grad(scene)
         if self.sh_degree:
             self._check_sh(scene)
         h, dev = self._bind(scene)
@@ -786,6 +829,8 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
         mode = ADMode(int(mode))
         if (grads is not None and grads.get(PHASE_G_KEY) is not None) or (kwargs.get("tangents") or {}).get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)
+        if (grads is not None and grads.get(PHASE_TAB_KEY) is not None) or (kwargs.get("tangents") or {}).get(PHASE_TAB_KEY) is not None:
+            self._refuse_phase_tab_grad(scene)
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)

@@ -24,6 +24,7 @@ from . import losses
 from .batched import sample_batch, sensors_to_device
 from .integrators import ADMode, FusedNerfDrtIntegrator, IndependentSampler, RayBatch, sample_tea_32
 from .render import _grid, _sensor_batch, _with_params, alloc_grads, g_grad, grad_keys, phase_param
+from .scene import PHASE_TAB_KEY
 
 # name -> (drt_loss_kind, keyword of its parameter, default of the parameter)
 LOSS_KINDS = {
@@ -97,6 +98,12 @@ def _check_integrator(integrator, what: str):
 def _check_shard(shard, what: str):
     if shard is not None and getattr(shard, "world", 1) > 1:
         raise ValueError(f"{what}: sharded runs (world > 1) are not supported by the loss-fused path")
+
+
+def _refuse_tab(params, what: str):
+    if params.get(PHASE_TAB_KEY) is not None:
+        raise ValueError(f"{what}: {PHASE_TAB_KEY} is not supported by the loss-fused path yet (a follow-up); differentiate the table "
+                         "through render / render_batch and a loss on the image")
 
 
 def _ref_tensor(t: torch.Tensor, dev, name: str) -> torch.Tensor:
@@ -175,6 +182,7 @@ def render_loss(scene, ref_image, loss=losses.l1, params: Optional[Dict[str, tor
     dense = _ref_tensor(ref_image, params[keys[0]].device, "ref_image").reshape(-1, 3)
     if dense.shape[0] != n_pix:
         raise ValueError(f"{what}: ref_image holds {dense.shape[0]} pixels, the sensor {n_pix}")
+    _refuse_tab(params, "render_loss")
     g = phase_param(scene, integrator, params, params[keys[0]].device)
     return _LossRenderOp.apply(params[keys[0]], params[keys[1]], g, scene, integrator, int(sensor), int(spp), spp_grad, int(seed),
                                seed_grad, LossRef(dense=dense), kind, param)
@@ -233,6 +241,7 @@ def render_batch_loss(batch_size: int, scene, ref_images, loss=losses.l1, sensor
     if (ref_images.shape[0], ref_images.shape[1], ref_images.shape[2]) != (len(sensors), sensors[0].height, sensors[0].width):
         raise ValueError(f"{what}: ref_images of shape {tuple(ref_images.shape)} do not match {len(sensors)} sensors of "
                          f"{sensors[0].width}x{sensors[0].height}")
+    _refuse_tab(params, "render_batch_loss")
     g = phase_param(scene, integrator, params, dev)
     if sensor_table is None:
         sensor_table = sensors_to_device(sensors, dev)

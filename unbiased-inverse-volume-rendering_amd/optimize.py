@@ -12,6 +12,7 @@ from dataclasses import dataclass, field
 from enum import IntEnum
 from typing import Callable, Dict, List, Optional
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -22,7 +23,7 @@ from .loss_fused import render_batch_loss, render_loss, resolve_loss
 from .opt_config import get_int_config
 from .priors import Prior, prior_value_and_grad_
 from .render import render, render_primal
-from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, require_hg
+from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, PHASE_TAB_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, TabPhase, require_hg
 from .image_io import read_image, write_image
 from .volume_io import write_vol
 
@@ -178,7 +179,7 @@ class Adam:
             t += 1
             lr = self.lr.get(k, self.lr_default)
             lr_t = lr * (1 - self.beta_2 ** t) ** 0.5 / (1 - self.beta_1 ** t)
-            if k != PHASE_G_KEY and _fused_adam_ok(p, g, m, v):     # (the scalar g takes the torch ops: the kernel is for grids)
+            if k not in (PHASE_G_KEY, PHASE_TAB_KEY) and _fused_adam_ok(p, g, m, v):     # (the scalar g and the 1-D table take the torch ops: the kernel is for grids)
                 # one fused pass on the device (drt_adam_step) instead of seven elementwise kernels
                 from ._native import native
                 with torch.cuda.device(p.device):
@@ -211,6 +212,7 @@ class SGD(Adam):
         return set()
 
 
+PHASE_TAB_FLOOR = 1e-4    # smallest value of an optimised TabPhase table: a differentiated table must stay strictly positive (its score divides by the density)
 PHASE_G_LIMIT = 0.99      # |g| of an optimised HG asymmetry: HGPhase needs |g| < 1, and the phase function degenerates towards it
 
 
@@ -226,6 +228,8 @@ def param_bounds(scene_config: SceneConfig, keys) -> Dict[str, tuple]:
             out[k] = (0.0, 1.0)
         elif k == PHASE_G_KEY:
             out[k] = (-PHASE_G_LIMIT, PHASE_G_LIMIT)
+        elif k == PHASE_TAB_KEY:
+            out[k] = (PHASE_TAB_FLOOR, None)
     return out
 
 
@@ -243,6 +247,8 @@ def enforce_valid_params(scene_config: SceneConfig, opt, skip=()) -> None:
             v.clamp_(0, 1)
         elif k == PHASE_G_KEY:
             v.clamp_(-PHASE_G_LIMIT, PHASE_G_LIMIT)
+        elif k == PHASE_TAB_KEY:
+            v.clamp_(min=PHASE_TAB_FLOOR)
         else:
             raise ValueError(k)
 
@@ -280,6 +286,9 @@ def save_params(output_dir: str, scene_config: SceneConfig, params: Dict[str, to
         if key == PHASE_G_KEY:                                        # a scalar: one line of text, `<name>-medium1_phase_function_g.txt`
             with open(os.path.join(output_dir, f'{name}-medium1_phase_function_g.txt'), 'w') as f:
                 f.write(f'{float(params[key]):.9g}\n')
+            continue
+        if key == PHASE_TAB_KEY:                                      # a 1-D table: `<name>-medium1_phase_function_values.npy`
+            np.save(os.path.join(output_dir, f'{name}-medium1_phase_function_values.npy'), params[key].detach().cpu().numpy())
             continue
         if not key.endswith('.data'):
             raise NotImplementedError(f'Checkpointing of parameter {key}')
@@ -376,13 +385,14 @@ def _scene_with(scene: Scene, params: Dict[str, torch.Tensor], factor: int) -> S
 
 
 def _scene_at_g(scene: Scene, params: Dict[str, torch.Tensor]) -> Scene:
-    """`scene` with the optimised HG asymmetry params[PHASE_G_KEY] (read to the host), or `scene` itself when g is not optimised."""
-    if PHASE_G_KEY not in params:
+    """`scene` with the optimised HG asymmetry params[PHASE_G_KEY] or the optimised table params[PHASE_TAB_KEY] (read to the host), or
+    `scene` itself when neither is optimised."""
+    if PHASE_G_KEY not in params and PHASE_TAB_KEY not in params:
         return scene
     m = scene.medium
+    phase = HGPhase(float(params[PHASE_G_KEY])) if PHASE_G_KEY in params else TabPhase(params[PHASE_TAB_KEY].detach().cpu().numpy())
     medium = GridMedium(sigma_t=m.sigma_t, albedo=m.albedo, bbox_min=m.bbox_min, bbox_max=m.bbox_max, scale=m.scale,
-                        majorant_resolution_factor=m.majorant_resolution_factor, emission=m.emission,
-                        phase=HGPhase(float(params[PHASE_G_KEY])))
+                        majorant_resolution_factor=m.majorant_resolution_factor, emission=m.emission, phase=phase)
     return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
 
 
@@ -399,6 +409,10 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     PHASE_G_KEY optimises the HG asymmetry g of a medium with `HGPhase` (volpathsimple only), starting from
     `start_from_value[PHASE_G_KEY]` (None: the scene's g), clamped to |g| <= 0.99 after each step.  Its cost: every
     render reads the new g to the host once (the handle takes g by value), one device synchronisation per iteration.
+    PHASE_TAB_KEY optimises the raw values of a medium with `TabPhase` (volpathsimple, unsharded, not with `fused_loss`): a 1-D
+    parameter on the unfused Adam path, starting from `start_from_value[PHASE_TAB_KEY]` (None: the scene's table; a number: a uniform
+    table of the scene's length; a sequence: those values), clamped to >= PHASE_TAB_FLOOR after each step, checkpointed as `.npy`.
+    Its cost is g's: every render reads the table to the host once - one device synchronisation per iteration.
 
     `shard` (a `ShardSpec` with world > 1, one process per GPU): the batch / the image pixels of every
     iteration are dealt across the ranks, the local loss is scaled to its share of the global loss and the
@@ -419,9 +433,9 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     shard = shard or ShardSpec()
     priors = {k: list(ps) for k, ps in (opt_config.priors or {}).items()}
     for k, ps in priors.items():
-        if k == PHASE_G_KEY or k not in scene_config.param_keys or not k.endswith('.data'):
+        if k in (PHASE_G_KEY, PHASE_TAB_KEY) or k not in scene_config.param_keys or not k.endswith('.data'):
             raise ValueError(f'priors: "{k}" is not an optimised grid (optimised grid keys: '
-                             f'{[q for q in scene_config.param_keys if q != PHASE_G_KEY]})')
+                             f'{[q for q in scene_config.param_keys if q not in (PHASE_G_KEY, PHASE_TAB_KEY)]})')
         for p in ps:
             if not isinstance(p, Prior):
                 raise ValueError(f'priors["{k}"] must be a list of Prior, got {p!r}')
@@ -472,13 +486,22 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     if ref_images is not None and ref_images.shape[-1] != n_channels and not (n_channels == 3 and ref_images.shape[-1] == 4):
         raise ValueError(f"ref_images have {ref_images.shape[-1]} channels, the integrator renders {n_channels}")
     keys = list(scene_config.param_keys)
-    grid_keys = [k for k in keys if k != PHASE_G_KEY]
+    grid_keys = [k for k in keys if k not in (PHASE_G_KEY, PHASE_TAB_KEY)]
     for k in priors:
         if k not in integrator.param_keys:
             raise ValueError(f'priors: the integrator "{int_config.name}" does not read "{k}": the grid receives no optimizer step')
+    if PHASE_G_KEY in keys and PHASE_TAB_KEY in keys:
+        integrator._refuse_phase_tab_grad(scene0, True)                 # (a medium has one phase function)
     if PHASE_G_KEY in keys:
         require_hg(scene0, "run_optimization")
         integrator._refuse_phase_grad(scene0)                           # (nerf has no phase function)
+    if PHASE_TAB_KEY in keys:
+        integrator._refuse_phase_tab_grad(scene0, PHASE_G_KEY in keys)  # (nerf, g beside the table, a medium without a positive table)
+        if opt_config.fused_loss:
+            raise ValueError(f"fused_loss=True: {PHASE_TAB_KEY} is not supported by the loss-fused path yet (a follow-up); use fused_loss=False")
+        if shard.partitioned:
+            raise ValueError(f"{PHASE_TAB_KEY} is not supported in sharded runs yet (the table gradient's place in the packed gradient "
+                             "all-reduce is a follow-up); optimise the table on one device")
     sensors = [scene0.sensors[i] for i in scene_config.sensors]
     n_sensors = len(sensors)
     film = (sensors[0].width, sensors[0].height)
@@ -510,6 +533,13 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         if not abs(v) <= PHASE_G_LIMIT:
             raise ValueError(f'start value of "{PHASE_G_KEY}" must satisfy |g| <= {PHASE_G_LIMIT}, got {v}')
         params[PHASE_G_KEY] = torch.tensor(v, dtype=torch.float32, device=dev)
+    if PHASE_TAB_KEY in keys:
+        v = scene_config.start_from_value[PHASE_TAB_KEY]
+        n_tab = len(scene0.medium.phase)
+        v = scene0.medium.phase.values if v is None else [float(v)] * n_tab if np.isscalar(v) else [float(x) for x in v]
+        if len(v) != n_tab or not min(v) >= PHASE_TAB_FLOOR:
+            raise ValueError(f'start value of "{PHASE_TAB_KEY}" must hold the table\'s {n_tab} values, all >= {PHASE_TAB_FLOOR}')
+        params[PHASE_TAB_KEY] = torch.tensor(v, dtype=torch.float32, device=dev)
     for k in grid_keys:
         if k not in full:
             raise ValueError(f'Unknown parameter key "{k}" (known: {sorted(full)})')
@@ -577,6 +607,8 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
                   for k in integrator.param_keys}
         if PHASE_G_KEY in params:
             leaves[PHASE_G_KEY] = params[PHASE_G_KEY].detach().requires_grad_(True)
+        if PHASE_TAB_KEY in params:
+            leaves[PHASE_TAB_KEY] = params[PHASE_TAB_KEY].detach().requires_grad_(True)
         if opt_config.fused_loss and opt_config.batch_size is not None:   # the same step, film + loss + gather fused (loss_fused.py)
             loss_value, image, _, _ = render_batch_loss(
                 opt_config.batch_size, scene, ref_images, loss=opt_config.loss, sensors=sensors, params=leaves, integrator=integrator,

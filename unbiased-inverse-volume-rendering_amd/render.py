@@ -22,7 +22,8 @@ import torch
 
 from .distributed import COMPACT_BLOCK_FLOATS, ShardSpec, allreduce_gradients, gradient_support
 from .integrators import ADMode, IndependentSampler, RayBatch, sample_tea_32
-from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, check_phase_g
+from .scene import (ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, PHASE_TAB_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, TabPhase, check_phase_g,
+                    check_phase_tab)
 
 
 def _grid(scene: Scene, key: str):
@@ -36,8 +37,8 @@ def alloc_grads(scene: Scene, keys=(SIGMA_T_KEY, ALBEDO_KEY)) -> Dict[str, torch
     collective.  (A fresh buffer per backward: autograd hands these tensors out as `.grad`, so they cannot
     be pooled; the cost is one caching-allocator hit plus a 256 MiB memset = 0.05 ms at 256^3, and the
     benchmark's step pays the same memset.)"""
-    want_g = PHASE_G_KEY in keys
-    keys = [k for k in keys if k != PHASE_G_KEY]
+    want_g, want_tab = PHASE_G_KEY in keys, PHASE_TAB_KEY in keys
+    keys = [k for k in keys if k not in (PHASE_G_KEY, PHASE_TAB_KEY)]
     grids = [_grid(scene, k) for k in keys]
     # every grid starts at a multiple of 4 floats: its view is 16-byte aligned whatever the voxel counts (the fused Adam
     # step and the block-mask kernel read float4s); the up to 3 padding floats per grid stay zero
@@ -48,6 +49,11 @@ def alloc_grads(scene: Scene, keys=(SIGMA_T_KEY, ALBEDO_KEY)) -> Dict[str, torch
     g_off = (size + COMPACT_BLOCK_FLOATS - 1) // COMPACT_BLOCK_FLOATS * COMPACT_BLOCK_FLOATS
     if want_g:
         size = g_off + COMPACT_BLOCK_FLOATS
+    # PHASE_TAB_KEY: N more floats (a 1-D view) behind the grids and the g slot, in whole compaction blocks of their own, likewise
+    n_tab = len(scene.medium.phase) if want_tab else 0
+    t_off = (size + COMPACT_BLOCK_FLOATS - 1) // COMPACT_BLOCK_FLOATS * COMPACT_BLOCK_FLOATS
+    if want_tab:
+        size = t_off + (n_tab + COMPACT_BLOCK_FLOATS - 1) // COMPACT_BLOCK_FLOATS * COMPACT_BLOCK_FLOATS
     flat = torch.zeros(size, dtype=torch.float32, device=grids[0].device)
     out, off = {"_flat": flat}, 0
     for k, g in zip(keys, grids):
@@ -55,6 +61,8 @@ def alloc_grads(scene: Scene, keys=(SIGMA_T_KEY, ALBEDO_KEY)) -> Dict[str, torch
         off += pad(g.numel())
     if want_g:
         out[PHASE_G_KEY] = flat[g_off:g_off + 1].view(())
+    if want_tab:
+        out[PHASE_TAB_KEY] = flat[t_off:t_off + n_tab]
     return out
 
 
@@ -71,13 +79,14 @@ def sharded_support(scene: Scene, grads: Dict[str, torch.Tensor], shard: Optiona
     return gradient_support(scene.medium.sigma_t, grads, sparse_keys=(ALBEDO_KEY,))
 
 
-def _with_params(scene: Scene, keys, tensors, phase_g: Optional[float] = None) -> Scene:
+def _with_params(scene: Scene, keys, tensors, phase_g: Optional[float] = None, phase_tab: Optional[TabPhase] = None) -> Scene:
     m = scene.medium
     vals = {SIGMA_T_KEY: m.sigma_t, ALBEDO_KEY: m.albedo, EMISSION_KEY: m.emission}
     vals.update(dict(zip(keys, tensors)))
     medium = GridMedium(sigma_t=vals[SIGMA_T_KEY], albedo=vals[ALBEDO_KEY], bbox_min=m.bbox_min, bbox_max=m.bbox_max,
                         scale=m.scale, majorant_resolution_factor=m.majorant_resolution_factor,
-                        emission=vals[EMISSION_KEY], phase=m.phase if phase_g is None else HGPhase(phase_g))
+                        emission=vals[EMISSION_KEY],
+                        phase=phase_tab if phase_tab is not None else m.phase if phase_g is None else HGPhase(phase_g))
     return Scene(medium=medium, emitter=scene.emitter, sensors=scene.sensors)
 
 
@@ -112,9 +121,14 @@ def render_backward(scene: Scene, integrator, grad_image: torch.Tensor, sensor: 
     call returns (a one-off call has no next call that would look); False / None - it is left to the next backward pass or
     `distributed.verify_pending()` (the autograd ops inside an optimisation loop, which ends with `verify_pending`).
     `keys`: the gradients to allocate when `grads` is None (default: integrator.param_keys); with PHASE_G_KEY among them (or in
-    `grads`) the result also holds dLoss/dg of an HG medium, a 0-d view of the same flat buffer (one collective when sharded)."""
-    if (keys is not None and PHASE_G_KEY in keys) or (grads is not None and grads.get(PHASE_G_KEY) is not None):
+    `grads`) the result also holds dLoss/dg of an HG medium, a 0-d view of the same flat buffer (one collective when sharded); with
+    PHASE_TAB_KEY, dLoss/dvalues of a strictly positive TabPhase medium, a 1-D view of it (unsharded calls only)."""
+    want_g = (keys is not None and PHASE_G_KEY in keys) or (grads is not None and grads.get(PHASE_G_KEY) is not None)
+    if want_g:
         integrator._refuse_phase_grad(scene)        # (before the primal pass: a medium or integrator without a differentiable g)
+    if (keys is not None and PHASE_TAB_KEY in keys) or (grads is not None and grads.get(PHASE_TAB_KEY) is not None):
+        integrator._refuse_phase_tab_grad(scene, want_g)
+        refuse_sharded_tab(shard, "render_backward")
     batch = _sensor_batch(scene, sensor, spp, shard)
     sampler = IndependentSampler(seed, spp)
     L, _, state_out = integrator.sample(ADMode.Primal, scene, sampler.clone(), batch)     # :255-264
@@ -129,15 +143,24 @@ def render_backward(scene: Scene, integrator, grad_image: torch.Tensor, sensor: 
     return grads
 
 
+def refuse_sharded_tab(shard: Optional[ShardSpec], what: str):
+    """The table-value gradient is built for unsharded work (its slot in the packed all-reduce is a follow-up)."""
+    if shard is not None and shard.partitioned:
+        raise ValueError(f"{what}: {PHASE_TAB_KEY} is not supported in sharded runs yet (the table gradient's place in the packed "
+                         "gradient all-reduce is a follow-up); differentiate the table on one device")
+
+
 def render_forward(scene: Scene, integrator, tangents: Optional[Dict[str, torch.Tensor]], sensor: int = 0, spp: int = 1,
                    seed: int = 0, shard: Optional[ShardSpec] = None) -> torch.Tensor:
     """Forward-mode derivative image of the local pixels, [n_local_pixels, 3]: J·t for the tangents `tangents`
-    ({key of integrator.param_keys: tensor shaped like that grid, PHASE_G_KEY: a number for an HG medium}; a missing key or None
-    is a zero tangent).  The primal
+    ({key of integrator.param_keys: tensor shaped like that grid, PHASE_G_KEY: a number for an HG medium, PHASE_TAB_KEY: N float32
+    on the device for a strictly positive TabPhase medium}; a missing key or None is a zero tangent).  The primal
     pass at (seed, spp) gives the tangent pass its state_in; both trace the same paths, and the film develops the per-ray
     tangents with its summation order.  For any image gradient g, <g, render_forward(t)> equals <render_backward(g), t> at
     the same seed and spp up to float summation order.  A sharded call returns its local pixels and never communicates."""
     tangents = integrator.check_tangents(scene, tangents)
+    if tangents.get(PHASE_TAB_KEY) is not None:
+        refuse_sharded_tab(shard, "render_forward")
     batch = _sensor_batch(scene, sensor, spp, shard)
     sampler = IndependentSampler(seed, spp)
     state = None
@@ -217,6 +240,49 @@ class _RenderOpG(torch.autograd.Function):
         return render_forward(ctx.scene, ctx.integrator, tangents, ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard)
 
 
+class _RenderOpTab(torch.autograd.Function):
+    """_RenderOp with the raw values of a tabulated phase function (PHASE_TAB_KEY) as a third input: a 1-D device tensor, read to the
+    host once per call (check_phase_tab: the handle takes the table from the host) - that synchronisation is the cost of optimising it."""
+
+    @staticmethod
+    def forward(ctx, p0, p1, v, tab, scene, integrator, sensor, spp, spp_grad, seed, seed_grad, shard):
+        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()), phase_tab=tab)
+        ctx.scene, ctx.integrator, ctx.sensor = sc, integrator, sensor
+        ctx.spp_grad, ctx.seed_grad, ctx.shard = spp_grad, seed_grad, shard
+        return render_primal(sc, integrator, sensor, spp, seed, shard)
+
+    @staticmethod
+    def backward(ctx, grad_image):
+        k0, k1 = ctx.integrator.param_keys
+        want = ctx.needs_input_grad[2]
+        gr = render_backward(ctx.scene, ctx.integrator, grad_image.contiguous(), ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard,
+                             strict=False, keys=tuple(ctx.integrator.param_keys) + ((PHASE_TAB_KEY,) if want else ()))
+        # (a copy: `v.grad` does not keep the flat gradient buffer alive)
+        return (gr[k0], gr[k1], gr[PHASE_TAB_KEY].clone() if want else None) + (None,) * 9
+
+    @staticmethod
+    def jvp(ctx, t0, t1, tv, *_):
+        k0, k1 = ctx.integrator.param_keys
+        tangents = {k: (t.contiguous() if t is not None else None) for k, t in ((k0, t0), (k1, t1))}
+        tangents[PHASE_TAB_KEY] = tv.contiguous() if tv is not None else None
+        return render_forward(ctx.scene, ctx.integrator, tangents, ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard)
+
+
+def phase_tab_param(scene: Scene, integrator, params: Dict[str, torch.Tensor], device, shard=None, what: str = "render"):
+    """params[PHASE_TAB_KEY], checked on the host before any device work (volpathsimple, a TabPhase medium of the same length, a 1-D
+    float32 tensor of strictly positive values on `device`, no g beside it, unsharded) -> (tensor, its TabPhase), or None when absent."""
+    if params.get(PHASE_TAB_KEY) is None:
+        return None
+    if not integrator.phase_grad:
+        integrator._refuse_phase_tab_grad(scene)
+    if params.get(PHASE_G_KEY) is not None:
+        integrator._refuse_phase_tab_grad(scene, True)
+    if not isinstance(scene.medium.phase, TabPhase):
+        integrator._refuse_phase_tab_grad(scene)
+    refuse_sharded_tab(shard, what)
+    return params[PHASE_TAB_KEY], check_phase_tab(params[PHASE_TAB_KEY], scene, device)
+
+
 def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integrator=None,
            sensor: int = 0, spp: int = 1, spp_grad: int = 0, seed: int = 0, seed_grad: int = 0,
            shard: Optional[ShardSpec] = None) -> torch.Tensor:
@@ -225,7 +291,10 @@ def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integ
     the integrator's `param_keys` (sigma_t + albedo for `volpathsimple`, sigma_t + emission
     for `nerf`), in reverse mode and - dual tensors of `torch.autograd.forward_ad` - in forward mode.  With
     `params[PHASE_G_KEY] = g` (a 0-d float32 device tensor; volpathsimple and a medium with `HGPhase`) the image is rendered
-    with that g, which overrides `medium.phase.g`, and is differentiable with respect to it as well."""
+    with that g, which overrides `medium.phase.g`, and is differentiable with respect to it as well.  With `params[PHASE_TAB_KEY] = v`
+    (a 1-D float32 device tensor of strictly positive values, as long as the medium's `TabPhase` table; volpathsimple, unsharded) the
+    image is rendered with that table and is differentiable with respect to its raw values (`v.grad`, or a dual `v`); the table is read
+    to the host once per call."""
     if integrator is None:
         raise ValueError("render: an integrator is required")
     if spp_grad == 0:
@@ -243,6 +312,10 @@ def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integ
         if not isinstance(params[k], torch.Tensor):
             raise TypeError(f"render: params['{k}'] must be a torch device tensor "
                             "(the DRT integrator has no CPU path; use scene_to(scene, device))")
+    tab = phase_tab_param(scene, integrator, params, params[keys[0]].device, shard)
+    if tab is not None:
+        return _RenderOpTab.apply(params[keys[0]], params[keys[1]], tab[0], tab[1], scene, integrator, sensor,
+                                  int(spp), int(spp_grad), int(seed), int(seed_grad), shard)
     g = phase_param(scene, integrator, params, params[keys[0]].device)
     if g is not None:
         return _RenderOpG.apply(params[keys[0]], params[keys[1]], g, scene, integrator, sensor,

@@ -23,6 +23,7 @@ EMISSION_KEY = "medium1.emission.data"
 # the Henyey-Greenstein asymmetry of the medium's phase function (`mi.traverse`: medium1.phase_function.g) - a 0-d float32 device tensor in
 # render(params=...), never one of an integrator's `param_keys` (those are the grids)
 PHASE_G_KEY = "medium1.phase_function.g"
+PHASE_TAB_KEY = "medium1.phase_function.values"      # the raw values of a TabPhase table (before normalisation), differentiable
 
 
 def _normalize(v):
@@ -168,10 +169,12 @@ class TabPhase:
     `values[i] >= 0`, i = 0 .. N - 1, 2 <= N <= 65536, all finite, at least one positive, at the N equally spaced nodes
     c_i = -1 + 2 i / (N - 1) of the PHYSICS cosine c = -dot(wo, wi) (wi = -d_in; c = +1 is forward scattering: `tabphase`'s layout).
     Linear between the nodes and normalised here: eval = f(c) / (2 pi I), I = the trapezoid integral of f over [-1, 1].  The kernels take the
-    values as float32.  Hashable and comparable by its values.  No gradients with respect to the values (PHASE_G_KEY is refused for such
-    a medium); node spacing is uniform only.
+    values as float32.  Hashable and comparable by its values.  It has no g (PHASE_G_KEY is refused for such a medium); the raw values are
+    differentiable through `PHASE_TAB_KEY` (render(params=...), render_backward(keys=...), tangents of forward mode) when they are all
+    strictly positive.  Node spacing is uniform only.
 
-    `.eval(mu)` and `.sample(u1, u2, wi)` restate the device functions in float64 for host tests (mu = dot(wo, wi) = -c, as HG's)."""
+    `.eval(mu)`, `.score(mu)` and `.sample(u1, u2, wi)` restate the device functions in float64 for host tests (mu = dot(wo, wi) = -c,
+    as HG's)."""
     kind = 3        # DRT_PHASE_TAB
 
     def __init__(self, values):
@@ -254,6 +257,30 @@ class TabPhase:
         out = self._p[i] + t * (self._p[i + 1] - self._p[i])
         return float(out) if out.ndim == 0 else out
 
+    def score(self, mu):
+        """d log eval(mu) / d values, float64: an N-vector (one row per mu for an array).  With the hat functions h_k, their integrals
+        m_k (delta inside, delta / 2 at the two ends) and I = sum v_k m_k:  h_k(c) / (2 pi I eval) - m_k / I  at c = -mu.  Its inner
+        product with the values is 0: the density does not depend on the table's scale."""
+        mu = np.asarray(mu, dtype=np.float64)
+        v = np.asarray(self._values, dtype=np.float64)
+        N = v.shape[0]
+        n = N - 1
+        delta = 2.0 / n
+        m = np.full(N, delta)
+        m[0] = m[-1] = 0.5 * delta
+        I = float(np.dot(v, m))
+        x = np.clip((1.0 - mu) * (0.5 * n), 0.0, float(n))
+        i = np.minimum(x.astype(np.int64), n - 1)
+        t = x - i
+        p = self._p[i] + t * (self._p[i + 1] - self._p[i])
+        flat_i, flat_t, flat_p = np.atleast_1d(i), np.atleast_1d(t), np.atleast_1d(p)
+        out = np.tile(-m / I, (flat_i.shape[0], 1))
+        rows = np.arange(flat_i.shape[0])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[rows, flat_i] += (1.0 - flat_t) / (2.0 * math.pi * I * flat_p)
+            out[rows, flat_i + 1] += flat_t / (2.0 * math.pi * I * flat_p)
+        return out[0] if mu.ndim == 0 else out.reshape(mu.shape + (N,))
+
     def cdf(self, c):
         """P(cosine <= c) of the physics cosine, float64."""
         c = np.asarray(c, dtype=np.float64)
@@ -312,6 +339,39 @@ def check_phase_g(g, device=None):
     if g.device.type == "cpu" or (device is not None and g.device != torch.device(device)):
         raise ValueError(f"params['{PHASE_G_KEY}'] is on {g.device}: it must be on the scene's device" + (f" ({device})" if device is not None else ""))
     return g
+
+
+def check_phase_tab(v, scene=None, device=None):
+    """A table parameter of render(params={PHASE_TAB_KEY: v}): a 1-D float32 device tensor of 2 .. 65536 strictly positive values (it may
+    require grad), of the bound table's length when the scene's medium has a TabPhase.  -> the TabPhase of those values (ONE read of the
+    table to the host: the synchronisation is the cost of optimising it, as for g)."""
+    import torch
+    if not isinstance(v, torch.Tensor):
+        raise TypeError(f"params['{PHASE_TAB_KEY}'] must be a 1-D float32 device tensor, got {type(v).__name__}")
+    if v.dtype != torch.float32 or v.dim() != 1:
+        raise TypeError(f"params['{PHASE_TAB_KEY}'] must be a 1-D float32 tensor, got dtype {v.dtype} and shape {tuple(v.shape)}")
+    if not TAB_MIN_NODES <= v.shape[0] <= TAB_MAX_NODES:
+        raise ValueError(f"params['{PHASE_TAB_KEY}'] must have between {TAB_MIN_NODES} and {TAB_MAX_NODES} values, got {v.shape[0]}")
+    if scene is not None and isinstance(scene.medium.phase, TabPhase) and len(scene.medium.phase) != v.shape[0]:
+        raise ValueError(f"params['{PHASE_TAB_KEY}'] has {v.shape[0]} values, the medium's table {len(scene.medium.phase)}: the lengths must agree")
+    host = v.detach().cpu().numpy()
+    if not np.all(np.isfinite(host)) or not np.all(host > 0):
+        raise ValueError(f"params['{PHASE_TAB_KEY}']: a differentiated table must be finite and strictly positive (the score of a zero "
+                         "density is 0 / 0); clamp the values to a positive floor")
+    if v.device.type == "cpu" or (device is not None and v.device != torch.device(device)):
+        raise ValueError(f"params['{PHASE_TAB_KEY}'] is on {v.device}: it must be on the scene's device" + (f" ({device})" if device is not None else ""))
+    return TabPhase(host)
+
+
+def require_tab(scene, what: str):
+    """The gradient with respect to the table values needs a medium with a strictly positive TabPhase."""
+    ph = scene.medium.phase
+    if not isinstance(ph, TabPhase):
+        raise ValueError(f"{what}: a gradient with respect to {PHASE_TAB_KEY} needs GridMedium(phase=TabPhase(values)); the medium's phase "
+                         f"function is {type(ph).__name__} (gradients of analytic lobes: {PHASE_G_KEY} with HGPhase)")
+    if not min(ph.values) > 0.0:
+        raise ValueError(f"{what}: a differentiated table must be strictly positive (the score of a zero density is 0 / 0); the medium's "
+                         f"table has a value {min(ph.values):g}")
 
 
 def require_hg(scene, what: str):
