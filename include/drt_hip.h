@@ -551,7 +551,9 @@ int drt_debug_eval(drt_handle h, int op, const float *in, uint64_t n, float *out
  *                                               queued tracer's LDS limit, max_depth > 1000 and jobs without record memory
  *  bit 13 (8192)       kHookFewPartWGs          the partition passes of the gradient reduction (histogram, offsets, scatter) with three
  *                                               workgroups per stream instead of 384: a scene of a few thousand rays then gives a workgroup
- *                                               several batches, i.e. exercises the scatter's carry of its cursors from batch to batch
+ *                                               several batches, i.e. exercises the scatter's carry of its cursors from batch to batch.
+ *                                               Also three tile_reduce workgroups per plane instead of min(units, 1024): their slices of
+ *                                               the sorted records then span reduce units and tile boundaries
  *  bit 14 (16384)      kHookSmallRecordBudget   8 MB record budget, i.e. many ray sub-batches
  *  bit 18 (262144)     kHookNoRecordMemory      pretend that the record streams cannot be allocated (the job then takes the atomic path, as it
  *                                               does when hipMalloc fails)

@@ -78,7 +78,12 @@ __device__ __forceinline__ void lds_atomics_barrier()
 }
 constexpr int kPartUnroll = DRT_PART_UNROLL;   // chunks a partition thread keeps in flight
 constexpr uint32_t kRideRecords = 4096;  // stream-1 records per tile that plane 0 takes along (a quarter of a reduce unit)
-constexpr uint32_t kReduceWGs = 1024;   // per plane: 4 workgroups per CU, looping over the reduce units (512 .. 4096: the same)
+#ifndef DRT_REDUCE_WGS
+#define DRT_REDUCE_WGS 512         // tile_reduce workgroups per plane, each a contiguous slice of the plane's reduce units: one round of the 2 x 256 that are resident at once.
+                                   // A slice boundary inside a tile costs a second zero and flush of that tile.  Reductions ms per headline step, two alternating runs on
+                                   // one box: 256: 1.542 1.539   512: 1.536 1.540 / 1.536 1.533   1024: 1.562 1.555   2048: 1.580 1.575
+#endif
+constexpr uint32_t kReduceWGs = DRT_REDUCE_WGS;
 
 struct Cell { int x0, x1, y0, y1, z0, z1; float w[8]; };
 
@@ -415,88 +420,224 @@ __global__ void __launch_bounds__(kPartThreads, 8) bin_scatter_staged_kernel(con
 // blockIdx.y = reduce plane: 0: sigma_t of stream 0 AND of stream 1 (for every tile that has stream-0 records: the
 // workgroup that starts such a tile's first unit also adds stream 1's sigma_t values of that tile - one zero / flush
 // of the LDS tile instead of two); 1: sigma_t of stream 1 for the tiles WITHOUT stream-0 records; 2..4: r, g, b of stream 1
+//
+// A workgroup owns the reduce units [u_begin, u_end) of its plane's stream.  bin_base is a prefix sum and the units are consecutive, so
+// these are ONE contiguous slice of the sorted records: the workgroup finds its first tile once (unit_tile), then walks forward - tile ends
+// from bin_base, 64 entries per load where tiles are empty -, and only a tile boundary (flush, zero) interrupts the record loop.  That loop
+// is software-pipelined: the loads of group n + 1 (four records per thread) are issued before the adds of group n, with clamped addresses
+// instead of branches (a lane past its end re-reads the unit's last record and adds a zero), and it runs on across the unit boundaries
+// inside a tile.  The body is compiled per plane kind (reduce_slice<KIND, FINITE>): no run-time choice of stream, quads or path per record.
 #ifndef DRT_REDUCE_TRANSPOSE
 #define DRT_REDUCE_TRANSPOSE 1     // 0: every unit in arrival order
+#endif
+#ifndef DRT_REDUCE_PLANE_ORDER
+#define DRT_REDUCE_PLANE_ORDER 0   // 0: plane 0's workgroups (stream 0: four fifths of the records) are dispatched first; 1: last
 #endif
 #ifndef DRT_REDUCE_THREADS
 #define DRT_REDUCE_THREADS 512      // (256: 1.15 ms per headline launch, 512 / 1024: 0.85 ms - more waves per CU behind the LDS tile)
 #endif
-__global__ void __launch_bounds__(DRT_REDUCE_THREADS) tile_reduce_kernel(const Params P, const DeferredPlan D)
+constexpr int kKindS0 = 0, kKindS1Sigma = 1, kKindS1Colour = 2;   // stream 0 (one quad, non-temporal) | stream 1's sigma_t | stream 1's r, g or b
+constexpr int kLdsRowBytes = (kTileX + 1) * 8, kLdsSlabBytes = (kTileX + 1) * (kTileY + 1) * 8;
+typedef float rec_f3 __attribute__((ext_vector_type(3)));
+
+// largest tile with ustart[tile] <= u (u < ustart[n_bins]): a 64-ary search, one load per lane and step - two dependent loads for 2048 tiles
+__device__ __forceinline__ int unit_tile(const uint32_t *ustart, int n_bins, uint32_t u)
 {
-    extern __shared__ unsigned long long tile[];                 // kLdsTile signed 64-bit fixed-point accumulators
-    const int plane = blockIdx.y;
-    const int s = plane == 0 ? 0 : 1, ch = plane == 0 ? 0 : plane - 1;        // stream, channel of the record
-    const int quads = s == 0 ? 1 : 2;
+    const int lane = threadIdx.x & 63;
+    int lo = 0, hi = n_bins;                                      // ustart[lo] <= u < ustart[hi]
+    while (hi - lo > 1) {
+        const int step = (hi - lo + 63) >> 6, idx = lo + lane * step;
+        const bool le = idx < hi && ustart[idx] <= u;             // (lane 0 reads ustart[lo]: at least one lane holds)
+        const int cnt = __popcll(__ballot(le));                   // ustart is non-decreasing: the lanes that hold are a prefix
+        lo = __builtin_amdgcn_readfirstlane(lo + (cnt - 1) * step);
+        hi = min(hi, lo + step);
+    }
+    return lo;
+}
+
+// one record {position, value}: 8 LDS adds of round(w * (val * scale)) - vs is val * scale, the power-of-two scale applied once per record,
+// which gives the bits of (w * val) * scale wherever w * val is a normal number - or, on the non-finite path (vs is val), 8 float atomics
+// into the caller's grid, as the atomic path does: NaN / inf propagate instead of being clamped away
+template <bool FINITE>
+__device__ __forceinline__ void add_record(const Params &P, unsigned long long *tile, float px, float py, float pz, float vs,
+                                           int X0, int Y0, int Z0, float *dst, int stride)
+{
+    if (vs == 0.0f) return;                                       // adding exact zeros changes nothing
+    Stencil st;
+    axis_setup(px, P.bmin[0], P.inv_ext[0], P.rx, st.x0, st.x1, st.wx0, st.wx1);
+    axis_setup(py, P.bmin[1], P.inv_ext[1], P.ry, st.y0, st.y1, st.wy0, st.wy1);
+    axis_setup(pz, P.bmin[2], P.inv_ext[2], P.rz, st.z0, st.z1, st.wz0, st.wz1);
+    float w[8];
+    stencil_weights(st, w);
+    if constexpr (!FINITE) {
+        const int gx[2] = { st.x0, st.x1 }, gy[2] = { st.y0, st.y1 }, gz[2] = { st.z0, st.z1 };
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const size_t vox = ((size_t) gz[c >> 2] * P.ry + gy[(c >> 1) & 1]) * P.rx + gx[c & 1];
+            atomicAdd(dst + (size_t) stride * vox, w[c] * vs);
+        }
+    } else {
+        // byte offsets into the LDS tile; the row and slab strides as 24-bit multiplies (full rate; the operands are below 2^6)
+        const int x0 = (st.x0 - X0) << 3, x1 = (st.x1 - X0) << 3;
+        const int y0 = __mul24(st.y0 - Y0, kLdsRowBytes), y1 = __mul24(st.y1 - Y0, kLdsRowBytes);
+        const int z0 = __mul24(st.z0 - Z0, kLdsSlabBytes), z1 = __mul24(st.z1 - Z0, kLdsSlabBytes);
+        const int o[8] = { z0 + y0 + x0, z0 + y0 + x1, z0 + y1 + x0, z0 + y1 + x1,
+                           z1 + y0 + x0, z1 + y0 + x1, z1 + y1 + x0, z1 + y1 + x1 };
+        char *tb = (char *) tile;
+#pragma unroll
+        for (int c = 0; c < 8; ++c)                               // |w * vs| < 2^30: round to nearest even, sign-extend
+            atomicAdd((unsigned long long *) (tb + o[c]), (unsigned long long) (long long) __float2int_rn(w[c] * vs));
+    }
+}
+
+template <int KIND, bool FINITE>
+__device__ __forceinline__ void reduce_slice(const Params &P, const DeferredPlan &D, unsigned long long *tile, const int plane, const float vmax)
+{
+    constexpr int s = KIND == kKindS0 ? 0 : 1, quads = s == 0 ? 1 : 2;
+    const int ch = KIND == kKindS1Colour ? plane - 1 : 0;        // channel of the record: 0 sigma_t, 1..3 r, g, b
     // scale = 2^(30 - e) with max|v| < 2^e: every product |w * v| * scale < 2^30 is rounded to a 32-bit integer (one
     // multiply + one conversion; the 64-bit route through double cost ~12 instructions per corner, i.e. most of this
     // kernel's VALU time) and sign-extended into the 64-bit accumulator, which holds 2^33 such adds.  Quantisation
     // 2^-31 max|v| per add (an fp32 atomic add rounds at 2^-24 of the running sum).  The two sigma_t planes share one
     // scale (plane 0 adds values of both streams)
-    const float vmax = plane <= 1 ? fmaxf(__uint_as_float(D.vmax[0]), __uint_as_float(D.vmax[1])) : __uint_as_float(D.vmax[plane]);
-    if (vmax == 0.0f) return;                                    // nothing but zeros in this plane
-    const bool finite = vmax <= 3.0e38f;                         // a NaN / inf anywhere in the plane: float path below
     int e = 0;
-    (void) frexpf(finite ? vmax : 1.0f, &e);
-    const float scale = ldexpf(1.0f, 30 - e);
+    (void) frexpf(FINITE ? vmax : 1.0f, &e);
+    const float scale = FINITE ? ldexpf(1.0f, 30 - e) : 1.0f;
     const double inv_scale = ldexp(1.0, e - 30);
-    const uint32_t *base = D.bin_base + (size_t) s * (D.n_bins + 1);
-    const uint32_t *ustart = D.unit_start + (size_t) s * (D.n_bins + 1);
-    const uint32_t *base0 = D.bin_base, *base1 = D.bin_base + (D.n_bins + 1);
-    const uint32_t n_units = ustart[D.n_bins];
+    const int n_bins = D.n_bins, lane = threadIdx.x & 63;
+    const uint32_t *base = D.bin_base + (size_t) s * (n_bins + 1);
+    const uint32_t *ustart = D.unit_start + (size_t) s * (n_bins + 1);
+    const uint32_t *base0 = D.bin_base, *base1 = D.bin_base + (n_bins + 1);
+    const uint32_t n_units = ustart[n_bins];
     // persistent workgroups (empty ones are not free to dispatch), each a CONTIGUOUS run of units: the
     // units of a heavy tile follow one another, so the LDS tile is zeroed / flushed once per run
     const uint32_t u_begin = (uint32_t) (((uint64_t) n_units * blockIdx.x) / gridDim.x);
     const uint32_t u_end = (uint32_t) (((uint64_t) n_units * (blockIdx.x + 1)) / gridDim.x);
+    if (u_begin >= u_end) return;                                 // no units at all for this workgroup
     float *dst = ch == 0 ? P.g_sigma : P.g_albedo + (ch - 1);
     const int stride = ch == 0 ? 1 : 3;
     const float4 *src = D.out[s];
-    int b = -1, X0 = 0, Y0 = 0, Z0 = 0;
-    bool live = false;                                            // the LDS tile holds sums of tile b that must be flushed
+    const uint32_t T = blockDim.x;
 
-    // one record {position r.xyz, value}: 8 LDS adds (or, on the non-finite path, 8 float atomics into the grid)
-    auto add_record = [&](const float4 r, const float val) {
-        if (val == 0.0f) return;                                  // adding exact zeros changes nothing
-        Stencil st;
-        axis_setup(r.x, P.bmin[0], P.inv_ext[0], P.rx, st.x0, st.x1, st.wx0, st.wx1);
-        axis_setup(r.y, P.bmin[1], P.inv_ext[1], P.ry, st.y0, st.y1, st.wy0, st.wy1);
-        axis_setup(r.z, P.bmin[2], P.inv_ext[2], P.rz, st.z0, st.z1, st.wz0, st.wz1);
-        float w[8];
-        stencil_weights(st, w);
-        if (!finite) {
-            // a non-finite gradient value somewhere in this plane: add the float products straight to the
-            // caller's grid, as the atomic path does - NaN / inf propagate instead of being clamped away
-            const int gx[2] = { st.x0, st.x1 }, gy[2] = { st.y0, st.y1 }, gz[2] = { st.z0, st.z1 };
+    int b = unit_tile(ustart, n_bins, u_begin);                   // the slice's first tile: it holds records
+    uint32_t t_begin = base[b];
+    uint32_t pos = t_begin + (u_begin - ustart[b]) * kUnitRecords;   // the slice is [pos, ...): n_left units, walked tile by tile
+    uint32_t n_left = u_end - u_begin;
+
+    // this thread's records of a unit [first, last): group g is a + (4 g + k) * step, k < 4, where that is below lim.  Arrival order: lane
+    // after lane (a = first + thread, step = threads).  Transposed: one contiguous segment of n_rows records per thread
+    uint32_t first = 0, last = 0, a = 0, step = 0, lim = 0, g = 0, n_groups = 0;
+    auto unit_setup = [&](uint32_t f, uint32_t p_end, bool transposed) {
+        first = f; last = p_end - f > kUnitRecords ? f + kUnitRecords : p_end;
+        const uint32_t n_rows = (last - first + T - 1) / T;
+        n_groups = (n_rows + 3) >> 2; g = 0;
+        if (transposed) { a = first + threadIdx.x * n_rows; step = 1; lim = min(last, a + n_rows); }
+        else { a = first + threadIdx.x; step = T; lim = last; }
+    };
+    // Records that arrive together may share their voxels - one march step of neighbouring nerf rays: 64 lanes on the same
+    // LDS words, the adds serialise (nerf: 3.75 ms per plane and sub-batch).  Every wave looks at the unit's first 64 records
+    // (the same records, so the same answer in every wave): when a quarter of them fall into their neighbour's cell the unit
+    // is read TRANSPOSED - one contiguous segment per thread, so that the records a wave adds together lie n_rows apart in
+    // arrival order (nerf 174 -> 203, fused nerf + DRT 142 -> 163 Msamples/s).  Scatter-event records do not (headline:
+    // coalesced order 2.42 ms, transposed 2.66 ms).  The probe of a unit is loaded while the unit before it is reduced.
+    auto probed = [&](uint32_t f, uint32_t p_end) { return DRT_REDUCE_TRANSPOSE && p_end - f >= 4096u; };   // (the unit [f, ...) holds >= 4096 records)
+    auto probe_load = [&](uint32_t f) { return *(const rec_f3 *) (src + (size_t) (f + lane) * quads); };
+    auto probe_eval = [&](const rec_f3 r) {
+        int x0, y0, z0;
+        cell_of(P, r.x, r.y, r.z, x0, y0, z0);
+        const int id = (z0 * P.ry + y0) * P.rx + x0, left = __shfl_up(id, 1, 64);
+        return __popcll(__ballot(lane > 0 && id == left)) >= 16;
+    };
+    // one group: four loads per thread, no branches and nothing that waits for them.  .w is the plane's value; bit k of the mask: record k is
+    // this thread's to add (a lane past its end holds a copy of the unit's last record)
+    auto load_group = [&](float4 (&r)[4], uint32_t &okm) {
+        okm = 0u;
 #pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const size_t vox = ((size_t) gz[c >> 2] * P.ry + gy[(c >> 1) & 1]) * P.rx + gx[c & 1];
-                atomicAdd(dst + (size_t) stride * vox, w[c] * val);
-            }
-            return;
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t i = a + k * step;
+            const bool ok = i < lim;
+            const float4 *rp = src + (size_t) (ok ? i : last - 1u) * quads;
+            if constexpr (KIND == kKindS1Colour) {
+                const rec_f3 p = *(const rec_f3 *) rp;
+                r[k] = make_float4(p.x, p.y, p.z, ((const float *) rp)[3 + ch]);
+            } else r[k] = (DRT_PART_NT & 4) && KIND == kKindS0 ? nt_load4(rp) : rp[0];
+            okm |= ok ? 1u << k : 0u;
         }
-        const int x0 = st.x0 - X0, x1 = st.x1 - X0;
-        const int y0 = (st.y0 - Y0) * (kTileX + 1), y1 = (st.y1 - Y0) * (kTileX + 1);
-        const int z0 = (st.z0 - Z0) * ((kTileX + 1) * (kTileY + 1)), z1 = (st.z1 - Z0) * ((kTileX + 1) * (kTileY + 1));
-        const int o[8] = { z0 + y0 + x0, z0 + y0 + x1, z0 + y1 + x0, z0 + y1 + x1,
-                           z1 + y0 + x0, z1 + y0 + x1, z1 + y1 + x0, z1 + y1 + x1 };
+        a += 4 * step; ++g;
+    };
+    auto add_group = [&](const float4 (&r)[4], const uint32_t okm, int X0, int Y0, int Z0) {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const float pv = w[c] * val;                           // the float product the atomic path adds (|pv| <= vmax)
-            atomicAdd(&tile[o[c]], (unsigned long long) (long long) __float2int_rn(pv * scale));
-        }
+        for (int k = 0; k < 4; ++k)
+            add_record<FINITE>(P, tile, r[k].x, r[k].y, r[k].z, (okm >> k) & 1u ? r[k].w * scale : 0.0f, X0, Y0, Z0, dst, stride);
     };
 
-    for (uint32_t u = u_begin; u <= u_end; ++u) {
-        int nb = -1;
-        if (u < u_end) {
-            int lo = b < 0 ? 0 : b, hi = D.n_bins;                // largest tile with ustart[tile] <= u
-            while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (ustart[mid] <= u) lo = mid; else hi = mid; }
-            nb = lo;
+    while (n_left > 0) {
+        // tile b holds the records [t_begin, t_end), the slice's next one is pos.  One load per lane: the ends of the tiles b .. b + 63 -
+        // this tile's end and, past the empty tiles, the next tile with records
+        int X0 = 0, Y0 = 0, Z0 = 0, b_next = -1;
+        uint32_t t_end;
+        {
+            const uint32_t en = base[min(b + 1 + lane, n_bins)];
+            t_end = __builtin_amdgcn_readfirstlane(en);
+            const unsigned long long m = __ballot(en > t_end);
+            if (m) b_next = b + (int) __ffsll(m) - 1;
         }
-        if (nb == b && nb < 0) break;                             // no units at all for this workgroup
-        if (nb != b) {
-            if (b >= 0 && live && finite && !dbg(P.debug_flags, kHookReduceNoFlush)) {   // flush the finished tile (+=)
+        const uint64_t want = (uint64_t) pos + (uint64_t) n_left * kUnitRecords;
+        const uint32_t p_end = want < t_end ? (uint32_t) want : t_end;   // the slice's part of this tile: [pos, p_end), whole units or up to the tile's end
+        n_left -= (p_end - pos + kUnitRecords - 1) / kUnitRecords;
+        // stream 1's sigma_t values of tile b ride along with stream 0's when they are few (scatter events next to
+        // the transmittance splats); when they are many (nerf queries) they keep their own plane and units
+        bool ride = false;
+        uint32_t r1_begin = 0, r1_end = 0;
+        if constexpr (KIND == kKindS0) { r1_begin = base1[b]; r1_end = base1[b + 1]; ride = r1_end - r1_begin <= kRideRecords; }
+        if constexpr (KIND == kKindS1Sigma) ride = base0[b + 1] > base0[b] && t_end - t_begin <= kRideRecords;
+        const bool live = !(KIND == kKindS1Sigma && ride);       // the LDS tile will hold sums of tile b that must be flushed
+        if (live) {
+            rec_f3 probe = { 0.f, 0.f, 0.f };
+            bool transposed = false;
+            const bool probe_first = probed(pos, p_end);
+            if (probe_first) probe = probe_load(pos);
+            X0 = (b % D.ntx) * kTileX; Y0 = ((b / D.ntx) % D.nty) * kTileY; Z0 = (b / (D.ntx * D.nty)) * kTileZ;
+            if constexpr (FINITE) {
+                for (int j = threadIdx.x; j < kLdsTile; j += T) tile[j] = 0ull;
+                __syncthreads();
+            }
+            if (KIND == kKindS0 && ride && pos == t_begin) {     // first unit of this tile: stream 1's sigma_t values come along
+                const float4 *src1 = D.out[1];
+                for (uint32_t i0 = r1_begin + threadIdx.x; i0 < r1_end; i0 += 4 * T) {
+                    float4 r[4]; uint32_t okm = 0u;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t i = i0 + k * T;
+                        r[k] = src1[2 * (size_t) (i < r1_end ? i : r1_end - 1u)];
+                        okm |= i < r1_end ? 1u << k : 0u;
+                    }
+                    add_group(r, okm, X0, Y0, Z0);
+                }
+            }
+            if (probe_first) transposed = probe_eval(probe);
+            unit_setup(pos, p_end, transposed);
+            float4 nxt[4]; uint32_t nxt_ok;
+            load_group(nxt, nxt_ok);
+            bool probe_next = last < p_end && probed(last, p_end);
+            if (probe_next) probe = probe_load(last);
+            for (bool more = true; more; ) {
+                float4 cur[4]; const uint32_t cur_ok = nxt_ok;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
+                if (g == n_groups) {                              // the unit's last group is in cur: on to the next unit of this tile
+                    if (last < p_end) {
+                        unit_setup(last, p_end, probe_next && probe_eval(probe));
+                        probe_next = last < p_end && probed(last, p_end);
+                        if (probe_next) probe = probe_load(last);
+                    } else more = false;
+                }
+                if (more) load_group(nxt, nxt_ok);
+                add_group(cur, cur_ok, X0, Y0, Z0);
+            }
+            if (FINITE && !dbg(P.debug_flags, kHookReduceNoFlush)) {   // flush the finished tile (+=)
                 lds_atomics_barrier();
-                for (int j = threadIdx.x; j < kLdsTile; j += blockDim.x) {
+                for (int j = threadIdx.x; j < kLdsTile; j += T) {
                     const long long q = (long long) tile[j];
                     if (q == 0) continue;
                     const float v = (float) ((double) q * inv_scale);
@@ -506,77 +647,36 @@ __global__ void __launch_bounds__(DRT_REDUCE_THREADS) tile_reduce_kernel(const P
                 }
                 __syncthreads();
             }
-            if (nb < 0) break;
-            b = nb;
-            X0 = (b % D.ntx) * kTileX; Y0 = ((b / D.ntx) % D.nty) * kTileY; Z0 = (b / (D.ntx * D.nty)) * kTileZ;
-            // stream 1's sigma_t values of tile b ride along with stream 0's when they are few (scatter events next to
-            // the transmittance splats); when they are many (nerf queries) they keep their own plane and units
-            const bool ride = base0[b + 1] > base0[b] && base1[b + 1] - base1[b] <= kRideRecords;
-            live = !(plane == 1 && ride);
-            if (live && finite) {
-                for (int j = threadIdx.x; j < kLdsTile; j += blockDim.x) tile[j] = 0ull;
-                __syncthreads();
-            }
-            if (plane == 0 && ride && u == ustart[b]) {           // first unit of this tile: stream 1's sigma_t values come along
-                const float4 *src1 = D.out[1];
-                for (uint32_t i1 = base1[b] + threadIdx.x; i1 < base1[b + 1]; i1 += blockDim.x) {
-                    const float4 r = src1[2 * (size_t) i1];
-                    add_record(r, r.w);
-                }
-            }
         }
-        if (!live) continue;
-        const uint32_t first = base[b] + (u - ustart[b]) * kUnitRecords;
-        const uint32_t last = min(first + kUnitRecords, base[b + 1]);
-        // Records that arrive together may share their voxels - one march step of neighbouring nerf rays: 64 lanes on the same
-        // LDS words, the adds serialise (nerf: 3.75 ms per plane and sub-batch).  Every wave looks at the unit's first 64 records
-        // (the same records, so the same answer in every wave): when a quarter of them fall into their neighbour's cell the unit
-        // is read TRANSPOSED - one contiguous segment per thread, so that the records a wave adds together lie n_rows apart in
-        // arrival order (nerf 174 -> 203, fused nerf + DRT 142 -> 163 Msamples/s).  Scatter-event records do not (headline:
-        // coalesced order 2.42 ms, transposed 2.66 ms).
-        bool transposed = false;
-        if (DRT_REDUCE_TRANSPOSE && last - first >= 4096u) {
-            const uint32_t lane = threadIdx.x & 63u;
-            const float4 r = src[(size_t) (first + lane) * quads];
-            int x0, y0, z0;
-            cell_of(P, r.x, r.y, r.z, x0, y0, z0);
-            const int id = (z0 * P.ry + y0) * P.rx + x0, left = __shfl_up(id, 1, 64);
-            transposed = __popcll(__ballot(lane > 0u && id == left)) >= 16;
+        if (n_left == 0) break;
+        // units are left, so the slice took this tile to its end and a later tile holds records: past a stretch of more than 63 empty
+        // tiles, 64 tile ends per step
+        for (int j = b + 64; b_next < 0 && j < n_bins; j += 64) {
+            const unsigned long long m = __ballot(base[min(j + 1 + lane, n_bins)] > t_end);
+            if (m) b_next = j + (int) __ffsll(m) - 1;
         }
-        if (transposed) {
-            const uint32_t n_rows = (last - first + blockDim.x - 1) / blockDim.x;
-            for (uint32_t r0 = 0; r0 < n_rows; r0 += 4) {
-                float4 rr[4]; float vv[4]; bool ok[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t i = first + threadIdx.x * n_rows + r0 + k;
-                    ok[k] = r0 + k < n_rows && i < last;
-                    if (ok[k]) {
-                        const float4 *rp = src + (size_t) i * quads;
-                        rr[k] = (DRT_PART_NT & 4) && s == 0 ? nt_load4(rp) : rp[0];
-                        vv[k] = rr[k].w;
-                        if (s == 1 && ch > 0) { const float4 c4 = rp[1]; vv[k] = ch == 1 ? c4.x : (ch == 2 ? c4.y : c4.z); }
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) if (ok[k]) add_record(rr[k], vv[k]);
-            }
-            continue;
+        if (b_next < 0) break;                                    // (cannot happen: unit_start and bin_base come from the same counts)
+        b = b_next; t_begin = t_end; pos = t_end;
+    }
+}
+
+__global__ void __launch_bounds__(DRT_REDUCE_THREADS) tile_reduce_kernel(const Params P, const DeferredPlan D)
+{
+    extern __shared__ unsigned long long tile[];                 // kLdsTile signed 64-bit fixed-point accumulators
+    const int plane = DRT_REDUCE_PLANE_ORDER ? 4 - (int) blockIdx.y : (int) blockIdx.y;
+    const float vmax = plane <= 1 ? fmaxf(__uint_as_float(D.vmax[0]), __uint_as_float(D.vmax[1])) : __uint_as_float(D.vmax[plane]);
+    if (vmax == 0.0f) return;                                    // nothing but zeros in this plane
+    if (vmax <= 3.0e38f) {
+        switch (plane) {
+        case 0: reduce_slice<kKindS0, true>(P, D, tile, plane, vmax); break;
+        case 1: reduce_slice<kKindS1Sigma, true>(P, D, tile, plane, vmax); break;
+        default: reduce_slice<kKindS1Colour, true>(P, D, tile, plane, vmax); break;
         }
-        for (uint32_t i0 = first + threadIdx.x; i0 < last; i0 += 4 * blockDim.x) {
-            float4 rr[4]; float vv[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) if (i0 + k * blockDim.x < last) {
-                const float4 *rp = src + (size_t) (i0 + k * blockDim.x) * quads;
-                rr[k] = (DRT_PART_NT & 4) && s == 0 ? nt_load4(rp) : rp[0];
-                vv[k] = rr[k].w;
-                if (s == 1 && ch > 0) { const float4 c4 = rp[1]; vv[k] = ch == 1 ? c4.x : (ch == 2 ? c4.y : c4.z); }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (i0 + k * blockDim.x >= last) break;
-                add_record(rr[k], vv[k]);
-            }
+    } else {                                                     // a NaN / inf anywhere in the plane: the float path, a loop of its own
+        switch (plane) {
+        case 0: reduce_slice<kKindS0, false>(P, D, tile, plane, vmax); break;
+        case 1: reduce_slice<kKindS1Sigma, false>(P, D, tile, plane, vmax); break;
+        default: reduce_slice<kKindS1Colour, false>(P, D, tile, plane, vmax); break;
         }
     }
 }
@@ -645,7 +745,10 @@ hipError_t launch_deferred_reduce(const Params &P, const DeferredPlan &D, hipStr
             attr_set[dev] = true;
         }
     }
-    const uint32_t wgs = D.max_units < kReduceWGs ? D.max_units : kReduceWGs;
+    uint32_t wgs = D.max_units < kReduceWGs ? D.max_units : kReduceWGs;
+#ifdef DRT_TEST_HOOKS
+    if (dbg(P.debug_flags, kHookFewPartWGs)) wgs = kFewPartWGs;  // a small scene's slices then span units and tiles (a workgroup without units returns)
+#endif
     hipLaunchKernelGGL(tile_reduce_kernel, dim3(wgs, 5), dim3(DRT_REDUCE_THREADS), (size_t) kLdsTile * 8, stream, P, D);
     mark(4);
     return hipGetLastError();

@@ -47,7 +47,7 @@ enum Hook : uint32_t {
     kHookReduceNoFlush      = 1u << 10,   // gradient reduction without the flush (timing only)
     kHookPipelineBatches    = 1u << 11,   // tracer of ray sub-batch b beside the reduction of sub-batch b - 1 on the side stream (measured slower)
     kHookNoQueuedTracer     = 1u << 12,   // keep supergrid launches off the queued tracer: CoopTracer<SUPER> (drt_coop_super.hip), production's fallback, for every estimator
-    kHookFewPartWGs         = 1u << 13,   // three partition workgroups (histogram, offsets, scatter) instead of kPartWGs: several batches per workgroup in small scenes
+    kHookFewPartWGs         = 1u << 13,   // three partition workgroups (histogram, offsets, scatter) instead of kPartWGs: several batches per workgroup in small scenes; and three tile_reduce workgroups per plane: slices that span units and tiles
     kHookSmallRecordBudget  = 1u << 14,   // 8 MB record budget: many ray sub-batches
     kHookNoRecordMemory     = 1u << 18,   // pretend that the record streams cannot be allocated: the job takes the atomic path
     kHookNoRecordMemoryLater = 1u << 19,  // ... that they cannot be (re)allocated from the second ray sub-batch on
