@@ -375,6 +375,38 @@ int drt_batch_sample_rays_range(drt_handle h, const float *sensors, int32_t n_se
                                 uint32_t batch_count, uint32_t spp, uint32_t sub_seed_pixels, uint32_t sub_seed_rays,
                                 float *rays_o, float *rays_d, uint32_t *sensor_idx, uint32_t *pixels);
 
+/* Importance-sampled pixel batches (opt-in; the calls above are unchanged; an extension of the reference, whose batches are uniform).
+ * A pixel distribution covers the n = n_sensors * height * width film entries i = (s * height + y) * width + x, 0 < n < 2^31: a caller-owned
+ * DEVICE float32 weight map w[n] (an error map) and a table built from it.  Integer masses: wmax = max_i w_i, where entries that are not finite
+ * or not > 0 count as 0; r = 65535.0f / wmax (one fp32 division); a_i = min((uint32) (w_i * r), 65535); A = sum a_i (uint64); wmax == 0 gives
+ * A = 0, "uniform only".  Selection and pdf are exact functions of these integers.
+ * drt_pixel_dist_build (no handle, on `hip_stream`): first w_i <- w_i * decay in place (decay in (0, 1]; 1: the map is not touched), then the
+ * table of the decayed map: one pass for the maximum, one for the masses and the sums of blocks of 256 of them, one single-workgroup scan of the
+ * block sums.  No float atomics: equal maps give equal tables, byte for byte.  `table`: DEVICE, 16-byte aligned, at least
+ * drt_pixel_dist_table_bytes(n) bytes (0 for n = 0 or n >= 2^31).
+ * drt_batch_sample_rays_weighted: the sibling of drt_batch_sample_rays_range (same outputs, same GLOBAL lanes; sensor_idx and pixels are
+ * required).  Lane b of the pixel wavefront draws us, ux, uy as there, then three more next_u32: u3, u4, u5.  If (u3 >> 16) < uniform_q or A == 0
+ * the entry is that call's uniform pick from us, ux, uy; otherwise target = mulhi64((u4 << 32) | u5, A) and the entry is the smallest i with
+ * C_i > target, C the inclusive prefix of the masses.  uniform_q in [0, 65536] is the uniform share alpha = uniform_q / 65536 of the defensive
+ * mixture; 65536 returns drt_batch_sample_rays_range's bits.  A table of another film size than the sensors' is never searched (uniform picks).
+ * drt_pixel_dist_inv_pdf: out[b] = 1 / (n p_i) for entry i = (sensor_idx[b], pixel_idx[2b] = x, pixel_idx[2b + 1] = y), with
+ * p_i = alpha / n + (1 - alpha) a_i / A (A == 0: 1 / n), computed in double and rounded once; NaN for an index outside the film or a table of
+ * another film size.
+ * drt_pixel_dist_update: w_i <- max(w_i, err[b]) for every batch entry - an integer atomic max on the bit patterns (non-negative floats order
+ * like them), order-independent: duplicates give the same bits on every run.  An err that is negative, inf or NaN changes nothing; an index
+ * outside the film is skipped.
+ * Refused with DRT_ERR_INVALID_ARGUMENT and a message (drt_last_error), before any device work: null pointers, n = 0 or >= 2^31 (as n or as
+ * n_sensors * height * width), uniform_q > 65536, decay outside (0, 1], a table_bytes that is too small, a misaligned table, count >= 2^31. */
+uint64_t drt_pixel_dist_table_bytes(uint64_t n);
+int drt_pixel_dist_build(void *hip_stream, float *weights, uint64_t n, float decay, void *table, uint64_t table_bytes);
+int drt_batch_sample_rays_weighted(drt_handle h, const float *sensors, int32_t n_sensors, uint32_t batch_first, uint32_t batch_count, uint32_t spp,
+                                   uint32_t sub_seed_pixels, uint32_t sub_seed_rays, const void *table, uint32_t uniform_q, float *rays_o,
+                                   float *rays_d, uint32_t *sensor_idx, uint32_t *pixels);
+int drt_pixel_dist_inv_pdf(void *hip_stream, const void *table, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,
+                           const int32_t *pixel_idx, uint64_t count, uint32_t uniform_q, float *out);
+int drt_pixel_dist_update(void *hip_stream, float *weights, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,
+                          const int32_t *pixel_idx, const float *err, uint64_t count);
+
 /* Box-filter film: image[p] = mean over the pixel's spp samples
  * (block.put + film.develop, batched.py:176-197).  L: [n_pixels*spp][3]. */
 int drt_film_develop(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, float *image);

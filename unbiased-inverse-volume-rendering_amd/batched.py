@@ -35,11 +35,12 @@ def sensors_to_device(sensors: Sequence[PerspectiveSensor], device) -> torch.Ten
 
 
 def sample_batch(integrator, scene: Scene, sensor_table: torch.Tensor, batch_size: int, spp: int, seed: int,
-                 which: int, batch_first: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                 which: int, batch_first: int = 0, pixel_distribution=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """sample_batch_pixels + sample_batch_rays (batched.py:397-467) -> rays_o, rays_d, sensor_idx, pixels.
     `which` = 1 for the primal rays, 2 for the adjoint rays (batch_samplers[which]).
     `batch_first` / `batch_size`: the range of GLOBAL batch entries to generate (one rank's share of a
-    sharded batch; the samplers' lanes are the global entry / ray indices)."""
+    sharded batch; the samplers' lanes are the global entry / ray indices).
+    `pixel_distribution` (a `PixelDistribution`): the pixels are drawn from its table (drt_batch_sample_rays_weighted) instead of uniformly."""
     h, dev = integrator._bind(scene)
     n = batch_size * spp
     ro = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -48,6 +49,14 @@ def sample_batch(integrator, scene: Scene, sensor_table: torch.Tensor, batch_siz
     pix = torch.empty((batch_size, 2), dtype=torch.int32, device=dev)
     sub0 = sample_tea_32(seed, 17 * 0 + 5)[0]
     subk = sample_tea_32(seed, 17 * which + 5)[0]
+    if pixel_distribution is not None:
+        if pixel_distribution.device != dev or pixel_distribution.n_sensors != int(sensor_table.shape[0]):
+            raise ValueError(f"sample_batch: the pixel distribution covers {pixel_distribution.n_sensors} sensors on {pixel_distribution.device}, "
+                             f"the batch {int(sensor_table.shape[0])} sensors on {dev}")
+        h.batch_sample_rays_weighted(sensor_table.data_ptr(), int(sensor_table.shape[0]), int(batch_size), int(spp), sub0, subk,
+                                     pixel_distribution.table_ptr(), int(pixel_distribution.uniform_q), ro.data_ptr(), rd.data_ptr(),
+                                     sidx.data_ptr(), pix.data_ptr(), int(batch_first))
+        return ro, rd, sidx, pix
     h.batch_sample_rays(sensor_table.data_ptr(), int(sensor_table.shape[0]), int(batch_size), int(spp), sub0, subk,
                         ro.data_ptr(), rd.data_ptr(), sidx.data_ptr(), pix.data_ptr(), int(batch_first))
     return ro, rd, sidx, pix
@@ -59,15 +68,17 @@ class _BatchedRenderOp(torch.autograd.Function):
     the unsharded batch bit for bit - and the backward pass sums the gradient grids over the ranks with
     ONE all-reduce.  Unsharded calls never communicate.  `g`: the HG asymmetry (PHASE_G_KEY, a 0-d tensor read to the host once
     per call) or None - the medium's phase as it is; its gradient travels in the same all-reduce as the grids'.  `tab` (a TabPhase):
-    `g` is then the 1-D tensor of that table's raw values (PHASE_TAB_KEY, read to the host by the caller; unsharded only)."""
+    `g` is then the 1-D tensor of that table's raw values (PHASE_TAB_KEY, read to the host by the caller; unsharded only).
+    `dist` (a `PixelDistribution` or None): both passes draw the pixels from it; the backward pass raises if it changed in between."""
 
     @staticmethod
-    def forward(ctx, p0, p1, g, scene, integrator, sensor_table, batch_size, spp, spp_grad, seed, seed_grad, shard, tab):
+    def forward(ctx, p0, p1, g, scene, integrator, sensor_table, batch_size, spp, spp_grad, seed, seed_grad, shard, tab, dist=None):
         sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()),
                           None if g is None or tab is not None else float(g.detach()), phase_tab=tab)
         ctx.tab = tab is not None
         first, count = shard.batch_range(batch_size)
-        ro, rd, sidx, pix = sample_batch(integrator, sc, sensor_table, count, spp, seed, 1, first)
+        ro, rd, sidx, pix = sample_batch(integrator, sc, sensor_table, count, spp, seed, 1, first, dist)
+        ctx.dist, ctx.dist_version = dist, None if dist is None else dist.version
         batch = RayBatch(n_rays=count * spp, spp=spp, o=ro, d=rd, ray_offset=first * spp)
         L, _, _ = integrator.sample(ADMode.Primal, sc, IndependentSampler(seed, spp), batch)    # :163-173
         image = integrator.develop(sc, L, spp)                                                   # :176-197
@@ -81,7 +92,10 @@ class _BatchedRenderOp(torch.autograd.Function):
         sc, integ = ctx.scene, ctx.integrator
         first, count = ctx.range
         # decorrelated rays through the same pixels (:69-82); same pixel sampler 0 => same pixels
-        ro, rd, _, _ = sample_batch(integ, sc, ctx.sensor_table, count, ctx.spp_grad, ctx.seed, 2, first)
+        if ctx.dist is not None and ctx.dist.version != ctx.dist_version:
+            raise RuntimeError("render_batch: the pixel distribution changed (update / rebuild) between the forward and the backward pass, "
+                               "which re-samples the same pixels from it: update it only after backward()")
+        ro, rd, _, _ = sample_batch(integ, sc, ctx.sensor_table, count, ctx.spp_grad, ctx.seed, 2, first, ctx.dist)
         batch = RayBatch(n_rays=count * ctx.spp_grad, spp=ctx.spp_grad, o=ro, d=rd, ray_offset=first * ctx.spp_grad)
         sampler = IndependentSampler(ctx.seed_grad, ctx.spp_grad)
         L, _, state = integ.sample(ADMode.Primal, sc, sampler.clone(), batch)                    # :255-264
@@ -93,20 +107,24 @@ class _BatchedRenderOp(torch.autograd.Function):
         integ.sample(ADMode.Backward, sc, sampler, batch, δL=dL, state_in=state, grads=grads)    # :309-318
         allreduce_gradients(grads, shard=ctx.shard, support=support)
         k0, k1 = integ.param_keys
-        return (grads[k0], grads[k1], grads[PHASE_TAB_KEY].clone() if want_tab else g_grad(grads, want_g)) + (None,) * 10
+        return (grads[k0], grads[k1], grads[PHASE_TAB_KEY].clone() if want_tab else g_grad(grads, want_g)) + (None,) * 11
 
 
 def render_batch(batch_size: int, scene: Scene, sensors=None, film_size=None,
                  params: Optional[Dict[str, torch.Tensor]] = None, integrator=None, film=None,
                  pixel_format=None, sampler=None, seed: int = 0, seed_grad: int = 0, spp: int = 0,
-                 spp_grad: int = 0, sensor_table: Optional[torch.Tensor] = None, shard: Optional[ShardSpec] = None):
+                 spp_grad: int = 0, sensor_table: Optional[torch.Tensor] = None, shard: Optional[ShardSpec] = None,
+                 pixel_distribution=None):
     """Batched (ray-centric) alternative to `render` (python/batched.py:88-131).
     -> (image [batch_size, 3] ([batch_size, 5] with a `nerf` integrator's `aovs`, 6 with `distortion`), film, sampler, sensor_idx [batch_size], pixel_idx [batch_size, 2])
     (`film` / `sampler` are returned as given: the device film is stateless here).
     `shard` (world > 1): the outputs hold this rank's entries `shard.batch_range(batch_size)` only and the
     backward pass all-reduces the gradient grids; scale the local loss by `local_loss_scale`.
     `params[PHASE_G_KEY]`: the HG asymmetry g as in `render` (overrides `medium.phase.g`, differentiable).  `params[PHASE_TAB_KEY]`:
-    the raw values of a TabPhase table as in `render` (differentiable; unsharded)."""
+    the raw values of a TabPhase table as in `render` (differentiable; unsharded).
+    `pixel_distribution` (a `PixelDistribution`, pixel_dist.py; unsharded): both passes draw the batch's pixels from it instead of uniformly.
+    The outputs are unchanged; multiply per-pixel losses (`losses.pixelwise`) by `pixel_distribution.inv_pdf(sensor_idx, pixel_idx)`, and
+    update / rebuild the distribution only after `backward()`."""
     if integrator is None:
         raise ValueError("render_batch: an integrator is required")
     if spp <= 0:
@@ -121,6 +139,13 @@ def render_batch(batch_size: int, scene: Scene, sensors=None, film_size=None,
     sensors = list(sensors) if sensors is not None else list(scene.sensors)
     if film_size is not None and tuple(film_size) != (sensors[0].width, sensors[0].height):
         raise ValueError("film_size does not match the sensors' film")
+    if pixel_distribution is not None:
+        if shard is not None and shard.world > 1:
+            raise ValueError("render_batch: pixel_distribution is not supported in sharded runs yet: every rank would need the same map, "
+                             "i.e. an all-reduce(max) of the weight map after every update - the follow-up")
+        if (pixel_distribution.n_sensors, pixel_distribution.height, pixel_distribution.width) != (len(sensors), sensors[0].height, sensors[0].width):
+            raise ValueError(f"render_batch: the pixel distribution covers a film of (sensors, height, width) = {pixel_distribution.film}, "
+                             f"the batch is drawn over {(len(sensors), sensors[0].height, sensors[0].width)}")
     keys = integrator.param_keys
     if params is None:
         params = {k: _grid(scene, k) for k in keys}
@@ -133,7 +158,7 @@ def render_batch(batch_size: int, scene: Scene, sensors=None, film_size=None,
         sensor_table = sensors_to_device(sensors, params[keys[0]].device)
     image, sidx, pix = _BatchedRenderOp.apply(params[keys[0]], params[keys[1]], g, scene, integrator, sensor_table,
                                               int(batch_size), int(spp), int(spp_grad), int(seed), int(seed_grad),
-                                              shard or ShardSpec(), None if tab is None else tab[1])
+                                              shard or ShardSpec(), None if tab is None else tab[1], pixel_distribution)
     return image, film, sampler, sidx, pix
 
 

@@ -2038,6 +2038,89 @@ int drt_batch_sample_rays(drt_handle h, const float *sensors, int32_t n_sensors,
                                        rays_d, sensor_idx, pixels);
 }
 
+uint64_t drt_pixel_dist_table_bytes(uint64_t n)
+{
+    return drt::pixel_dist_table_bytes(n);
+}
+
+namespace {
+
+// the film of a pixel distribution: n = n_sensors * height * width entries, 0 < n < 2^31; 0 and a message otherwise
+uint64_t pixel_dist_film(const char *who, int32_t n_sensors, int32_t height, int32_t width)
+{
+    if (n_sensors < 1 || height < 1 || width < 1) {
+        fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: empty film %d x %d x %d", who, (int) n_sensors, (int) height, (int) width);
+        return 0;
+    }
+    const uint64_t rows = (uint64_t) n_sensors * (uint64_t) height;
+    if (rows >= (1ull << 31) || rows * (uint64_t) width >= (1ull << 31)) {
+        fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: %d x %d x %d film entries: n >= 2^31 is not supported", who, (int) n_sensors, (int) height,
+             (int) width);
+        return 0;
+    }
+    return rows * (uint64_t) width;
+}
+
+}  // namespace
+
+int drt_pixel_dist_build(void *hip_stream, float *weights, uint64_t n, float decay, void *table, uint64_t table_bytes)
+{
+    if (!weights || !table) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_build: null weights / table");
+    if (n == 0) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_build: empty map");
+    if (n >= (1ull << 31)) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_build: %llu entries: n >= 2^31 is not supported", (unsigned long long) n);
+    if (!(decay > 0.0f && decay <= 1.0f)) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_build: decay must lie in (0, 1], got %g", (double) decay);
+    if (((uintptr_t) weights & 3u) || ((uintptr_t) table & 15u))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_build: weights must be 4-byte aligned, the table 16-byte aligned");
+    const uint64_t need = drt::pixel_dist_table_bytes(n);
+    if (table_bytes < need)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_build: table_bytes %llu is too small: %llu entries need %llu", (unsigned long long) table_bytes,
+                    (unsigned long long) n, (unsigned long long) need);
+    DRT_HIP_CHECK(nullptr, drt::launch_pixel_dist_build(weights, (uint32_t) n, decay, table, (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
+int drt_batch_sample_rays_weighted(drt_handle h, const float *sensors, int32_t n_sensors, uint32_t batch_first, uint32_t batch_count, uint32_t spp,
+                                   uint32_t sub_seed_pixels, uint32_t sub_seed_rays, const void *table, uint32_t uniform_q, float *rays_o,
+                                   float *rays_d, uint32_t *sensor_idx, uint32_t *pixels)
+{
+    // (the argument checks come first and need no handle: fail() takes a null one)
+    if (!sensors || n_sensors < 1 || spp == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_batch_sample_rays_weighted: bad sensors / spp");
+    if (!table || ((uintptr_t) table & 15u)) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_batch_sample_rays_weighted: null or misaligned table");
+    if (uniform_q > 65536u) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_batch_sample_rays_weighted: uniform_q %u > 65536", (unsigned) uniform_q);
+    if (((uint64_t) batch_first + batch_count) * spp > 0xffffffffull)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "batch_size * spp exceeds 2^32 - 1");
+    if (!rays_o || !rays_d || !sensor_idx || !pixels)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_batch_sample_rays_weighted: null rays_o / rays_d / sensor_idx / pixels (the rays are formed from the stored picks)");
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    DeviceGuard g(h->device);
+    DRT_HIP_CHECK(h, drt::launch_pixel_dist_sample(sensors, n_sensors, batch_first, batch_count, spp, sub_seed_pixels, sub_seed_rays, table, uniform_q,
+                                                   rays_o, rays_d, sensor_idx, pixels, h->stream));
+    return DRT_OK;
+}
+
+int drt_pixel_dist_inv_pdf(void *hip_stream, const void *table, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,
+                           const int32_t *pixel_idx, uint64_t count, uint32_t uniform_q, float *out)
+{
+    if (!table || !sensor_idx || !pixel_idx || !out) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_inv_pdf: null table / sensor_idx / pixel_idx / out");
+    if ((uintptr_t) table & 15u) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_inv_pdf: the table must be 16-byte aligned");
+    if (uniform_q > 65536u) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_inv_pdf: uniform_q %u > 65536", (unsigned) uniform_q);
+    if (count >= (1ull << 31)) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_inv_pdf: count >= 2^31");
+    if (!pixel_dist_film("drt_pixel_dist_inv_pdf", n_sensors, height, width)) return DRT_ERR_INVALID_ARGUMENT;
+    DRT_HIP_CHECK(nullptr, drt::launch_pixel_dist_inv_pdf(table, n_sensors, height, width, sensor_idx, pixel_idx, count, uniform_q, out, (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
+int drt_pixel_dist_update(void *hip_stream, float *weights, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,
+                          const int32_t *pixel_idx, const float *err, uint64_t count)
+{
+    if (!weights || !sensor_idx || !pixel_idx || !err) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_update: null weights / sensor_idx / pixel_idx / err");
+    if ((uintptr_t) weights & 3u) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_update: weights must be 4-byte aligned");
+    if (count >= (1ull << 31)) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_pixel_dist_update: count >= 2^31");
+    if (!pixel_dist_film("drt_pixel_dist_update", n_sensors, height, width)) return DRT_ERR_INVALID_ARGUMENT;
+    DRT_HIP_CHECK(nullptr, drt::launch_pixel_dist_update(weights, n_sensors, height, width, sensor_idx, pixel_idx, err, count, (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
 int drt_film_develop(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, float *image)
 {
     if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");

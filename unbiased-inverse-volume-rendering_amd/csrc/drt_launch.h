@@ -207,6 +207,27 @@ bool grid_prior_supported(int64_t nz, int64_t ny, int64_t nx, int64_t nc);
 uint64_t grid_prior_partials(int nz, int ny, int nx, int nc);        // 0: not a grid the kernel takes
 hipError_t launch_grid_prior(int kind, const float *p, float *g, double *value, double *partials, int nz, int ny, int nx, int nc, double weight,
                              float eps, hipStream_t stream);
+// importance-sampled pixel batches (drt_pixel_dist.hip): a table over n < 2^31 film entries = this header, the exclusive uint64 prefix of the
+// sums of blocks of kDistBlock masses [n_blocks + 1], then the 16-bit masses padded to whole blocks (16-byte aligned)
+constexpr uint32_t kDistBlock = 256;
+constexpr uint32_t kDistMagic = 0x50445431u;
+struct DistHeader {
+    uint64_t total;                  // A = the sum of all masses
+    uint32_t n, n_blocks;
+    uint32_t wmax_bits;              // bit pattern of the largest clean weight
+    uint32_t magic;                  // kDistMagic once a build was enqueued
+    uint32_t pad[10];                // 64 bytes
+};
+static_assert(sizeof(DistHeader) == 64, "the table's prefix array starts 64 bytes in");
+uint64_t pixel_dist_table_bytes(uint64_t n);                         // 0: n is 0 or >= 2^31
+hipError_t launch_pixel_dist_build(float *weights, uint32_t n, float decay, void *table, hipStream_t stream);
+hipError_t launch_pixel_dist_sample(const float *sensors, int n_sensors, uint32_t batch_first, uint32_t batch_count, uint32_t spp,
+                                    uint32_t seed_pixels, uint32_t seed_rays, const void *table, uint32_t uniform_q, float *rays_o, float *rays_d,
+                                    uint32_t *sensor_idx, uint32_t *pixels, hipStream_t stream);
+hipError_t launch_pixel_dist_inv_pdf(const void *table, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,
+                                     const int32_t *pixel_idx, uint64_t count, uint32_t uniform_q, float *out, hipStream_t stream);
+hipError_t launch_pixel_dist_update(float *weights, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,
+                                    const int32_t *pixel_idx, const float *err, uint64_t count, hipStream_t stream);
 uint32_t host_alt_seed(uint32_t seed, bool sensor_flow);
 hipError_t launch_debug_eval(const Params &P, int op, const float *in, uint64_t n, float *out, hipStream_t stream);
 

@@ -307,6 +307,18 @@ public:
         }
         check(rc, "drt_batch_sample_rays_range");
     }
+    void batch_sample_rays_weighted(uintptr_t sensors, int n_sensors, uint32_t batch, uint32_t spp, uint32_t seed_px, uint32_t seed_rays,
+                                    uintptr_t table, uint32_t uniform_q, uintptr_t ro, uintptr_t rd, uintptr_t sidx, uintptr_t pix, uint32_t batch_first)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_batch_sample_rays_weighted(h_, ptr<const float>(sensors), n_sensors, batch_first, batch, spp, seed_px, seed_rays,
+                                                ptr<const void>(table), uniform_q, ptr<float>(ro), ptr<float>(rd), ptr<uint32_t>(sidx),
+                                                ptr<uint32_t>(pix));
+        }
+        check(rc, "drt_batch_sample_rays_weighted");
+    }
     void film_develop(uintptr_t L, uint64_t n_pixels, uint32_t spp, uintptr_t image)
     {
         int rc;
@@ -458,6 +470,26 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
                                       reinterpret_cast<double *>(value), reinterpret_cast<void *>(scratch), scratch_bytes, nz, ny, nx, nc, weight, eps);
         if (rc != DRT_OK) throw std::runtime_error(std::string("drt_grid_prior: ") + drt_last_error(nullptr));
     });
+    m.def("pixel_dist_table_bytes", [](uint64_t n) { return drt_pixel_dist_table_bytes(n); });
+    m.def("pixel_dist_build", [](uintptr_t stream, uintptr_t weights, uint64_t n, float decay, uintptr_t table, uint64_t table_bytes) {
+        const int rc = drt_pixel_dist_build(reinterpret_cast<void *>(stream), reinterpret_cast<float *>(weights), n, decay,
+                                            reinterpret_cast<void *>(table), table_bytes);
+        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+    });
+    m.def("pixel_dist_inv_pdf", [](uintptr_t stream, uintptr_t table, int32_t n_sensors, int32_t height, int32_t width, uintptr_t sidx, uintptr_t pix,
+                                   uint64_t count, uint32_t uniform_q, uintptr_t out) {
+        const int rc = drt_pixel_dist_inv_pdf(reinterpret_cast<void *>(stream), reinterpret_cast<const void *>(table), n_sensors, height, width,
+                                              reinterpret_cast<const int32_t *>(sidx), reinterpret_cast<const int32_t *>(pix), count, uniform_q,
+                                              reinterpret_cast<float *>(out));
+        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+    });
+    m.def("pixel_dist_update", [](uintptr_t stream, uintptr_t weights, int32_t n_sensors, int32_t height, int32_t width, uintptr_t sidx, uintptr_t pix,
+                                  uintptr_t err, uint64_t count) {
+        const int rc = drt_pixel_dist_update(reinterpret_cast<void *>(stream), reinterpret_cast<float *>(weights), n_sensors, height, width,
+                                             reinterpret_cast<const int32_t *>(sidx), reinterpret_cast<const int32_t *>(pix),
+                                             reinterpret_cast<const float *>(err), count);
+        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+    });
     m.def("grad_support_mask", [](uintptr_t stream, uintptr_t sigma_t, int rx, int ry, int rz, uint64_t sparse_off, uint32_t channels,
                                   uint64_t n_blocks, uint32_t block_floats, uintptr_t bits, uintptr_t mask) {
         const int32_t res[3] = { rx, ry, rz };
@@ -518,6 +550,9 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("batch_sample_rays", &Integrator::batch_sample_rays, py::arg("sensors"), py::arg("n_sensors"), py::arg("batch"),
              py::arg("spp"), py::arg("seed_px"), py::arg("seed_rays"), py::arg("ro"), py::arg("rd"), py::arg("sidx"),
              py::arg("pix"), py::arg("batch_first") = 0)
+        .def("batch_sample_rays_weighted", &Integrator::batch_sample_rays_weighted, py::arg("sensors"), py::arg("n_sensors"), py::arg("batch"),
+             py::arg("spp"), py::arg("seed_px"), py::arg("seed_rays"), py::arg("table"), py::arg("uniform_q"), py::arg("ro"), py::arg("rd"),
+             py::arg("sidx"), py::arg("pix"), py::arg("batch_first") = 0)
         .def("film_develop", &Integrator::film_develop)
         .def("film_backward", &Integrator::film_backward)
         .def("film_loss_forward", &Integrator::film_loss_forward)

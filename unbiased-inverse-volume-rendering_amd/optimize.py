@@ -21,6 +21,7 @@ from .batched import gather_ref_values, render_batch, sensors_to_device
 from .integrators import sample_tea_32
 from .loss_fused import render_batch_loss, render_loss, resolve_loss
 from .opt_config import get_int_config
+from .pixel_dist import PixelDistribution, PixelImportance
 from .priors import Prior, prior_value_and_grad_
 from .render import render, render_primal
 from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, PHASE_TAB_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, TabPhase, require_hg
@@ -63,6 +64,9 @@ class OptimizationConfig:
     # opt-in: weight of the distortion regulariser, the mean of the sixth image channel of a `nerf` integrator with `distortion=True`
     # (losses.distortion), added to every iteration's loss; non-zero with an integrator without that output raises at start-up
     distortion_weight: float = 0.0
+    # opt-in: draw the batches from a per-pixel error map instead of uniformly (pixel_dist.py; batched, unsharded, unfused runs with a
+    # pixel-separable loss); None: the uniform batches of the reference
+    pixel_importance: Optional[PixelImportance] = None
 
     def __post_init__(self):
         self.upsample_at = set()
@@ -427,7 +431,13 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     its value into the iteration's entry of the returned history, which then is the objective that is minimised - on the plain, the
     batched and the `fused_loss` route alike.  A key that is not an optimised grid the integrator reads (PHASE_G_KEY included) raises a
     ValueError at start-up.  Sharded runs: `.grad` is the all-reduced sum when backward returns, and every rank adds the identical prior
-    gradient on its own - like the rest of distributed.py, this route is unverified on multi-GPU hardware."""
+    gradient on its own - like the rest of distributed.py, this route is unverified on multi-GPU hardware.
+
+    `opt_config.pixel_importance` (a `PixelImportance`; batched, unsharded, not with `fused_loss` or the distortion term, a pixel-separable
+    loss): the batch of every iteration is drawn from a `PixelDistribution` over the sensors' film, the step's loss is
+    sum_b inv_pdf_b * ell_b / image.numel() with ell = `losses.pixelwise(loss)(image, ref)` - an unbiased estimate of the loss a uniform batch
+    estimates -, and after `backward()` the map takes max(map, ell) at the batch's pixels and is decayed and rebuilt every `rebuild_every`
+    iterations.  Priors compose unchanged; grid upsampling does not touch the map."""
     from .distributed import ShardSpec, allreduce_scalar, local_loss_scale, verify_pending
     from . import losses as _losses
     shard = shard or ShardSpec()
@@ -439,6 +449,24 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         for p in ps:
             if not isinstance(p, Prior):
                 raise ValueError(f'priors["{k}"] must be a list of Prior, got {p!r}')
+    importance = opt_config.pixel_importance
+    pixel_loss = None
+    if importance is not None:
+        if not isinstance(importance, PixelImportance):
+            raise ValueError(f"pixel_importance must be a PixelImportance, got {importance!r}")
+        if opt_config.fused_loss:
+            raise ValueError("pixel_importance: fused_loss=True is not supported (the loss-fused film sums the loss without per-pixel weights); "
+                             "use fused_loss=False")
+        if shard.world > 1:
+            raise ValueError("pixel_importance: sharded runs are not supported yet: every rank would need the same map, i.e. an "
+                             "all-reduce(max) of the weight map after every update - the follow-up")
+        if opt_config.batch_size is None:
+            raise ValueError("pixel_importance: sensor-based rendering (batch_size=None) renders every pixel of one sensor; importance-sampled "
+                             "pixels need batched rendering: set batch_size")
+        if opt_config.distortion_weight != 0.0:
+            raise ValueError("pixel_importance: the distortion term (distortion_weight != 0) is a mean over uniformly drawn pixels and is not "
+                             "supported with importance-sampled batches")
+        pixel_loss = losses.pixelwise(opt_config.loss)                 # (raises for a loss that is not a sum over pixels)
     if opt_config.fused_loss:
         resolve_loss(opt_config.loss)                                  # (raises for a loss the fused kernels do not have)
         if shard.world > 1:
@@ -578,6 +606,11 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     opt = opt_config.optimizer(params)
     scene = _scene_with(Scene(scene0.medium, scene0.emitter, sensors), grids, factor)
     table = sensors_to_device(sensors, dev)
+    dist = None
+    if importance is not None:                                         # one map per film: created here, where the film is fixed for the run
+        dist = PixelDistribution(n_sensors, sensors[0].height, sensors[0].width, dev, uniform_fraction=importance.uniform_fraction,
+                                 decay=importance.decay)
+        importance.distribution = dist
     writer = bool(output_dir) and shard.rank == 0                      # one rank writes checkpoints and previews
     if writer and opt_config.checkpoint_initial:
         save_params(os.path.join(output_dir, 'params'), scene_config, params, 'initial', scene.medium)
@@ -621,7 +654,8 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         elif opt_config.batch_size is not None:                        # batched rendering (:332-341)
             image, _, _, sensor_idx, pixel_idx = render_batch(
                 opt_config.batch_size, scene, sensors=sensors, params=leaves, integrator=integrator,
-                spp=spp_primal, spp_grad=spp_grad, seed=seed, seed_grad=seed_grad, sensor_table=table, shard=shard)
+                spp=spp_primal, spp_grad=spp_grad, seed=seed, seed_grad=seed_grad, sensor_table=table, shard=shard,
+                pixel_distribution=dist)
             ref_values = gather_ref_values(ref_images, sensor_idx, pixel_idx)
             n_global = opt_config.batch_size
         else:                                                          # sensor-based rendering (:342-348)
@@ -632,7 +666,11 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             n_global = ref_values.shape[0]
             if shard.partitioned:
                 ref_values = ref_values[shard.pixel_indices(n_global, ref_values.device)]
-        if not opt_config.fused_loss:
+        if dist is not None:
+            # importance-sampled batch: per-pixel losses weighted by 1 / (n pdf) - unbiased for what the uniform batch's loss estimates
+            ell = pixel_loss(image[:, :n_channels], ref_values[:, :n_channels])
+            loss_value = (dist.inv_pdf(sensor_idx, pixel_idx) * ell).sum() / image[:, :n_channels].numel()
+        elif not opt_config.fused_loss:
             # the losses normalise by the local entry count: scale to this rank's share of the global loss
             scale = local_loss_scale(image.shape[0], n_global)
             if has_distortion:
@@ -642,6 +680,11 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             else:
                 loss_value = opt_config.loss(image, ref_values) * scale
         loss_value.backward()                                          # dr.backward (:350)
+        if dist is not None:                                           # only now: the backward pass re-sampled the pixels from the table
+            importance.last_pixel_loss = ell.detach()
+            dist.update(sensor_idx, pixel_idx, importance.last_pixel_loss)
+            if (it_i + 1) % importance.rebuild_every == 0:
+                dist.rebuild()
         prior_value = None
         for k, ps in priors.items():                                   # (sharded: .grad is the all-reduced sum here; every rank adds the same)
             leaf = leaves[k]
