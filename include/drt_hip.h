@@ -527,6 +527,22 @@ uint64_t drt_grid_prior_scratch_bytes(int32_t nz, int32_t ny, int32_t nx, int32_
 int drt_grid_prior(void *hip_stream, int32_t kind, const float *p, float *g, double *value, void *scratch, uint64_t scratch_bytes,
                    int32_t nz, int32_t ny, int32_t nx, int32_t nc, double weight, double eps);
 
+/* Resampling of a dense grid onto another lattice of the same box, and the transpose of that linear map (no handle, no state, no scratch,
+ * no host wait; csrc/drt_resample.hip, DESIGN.md "Resampled colour grids").  src is (Z,Y,X,C) float32 with src_res = {X,Y,Z} (the order of
+ * drt_set_medium), dst likewise with dst_res; C = channels.  dst = R src is the source grid evaluated by the lookup convention of the
+ * tracers (cell-centred, clamped, trilinear) at the centres of the target's voxels.  Per axis with ns source and nt target voxels, target
+ * index t takes num = (2t + 1) ns - nt, den = 2 nt, f = floor(num / den), r = num - f den, w1 = float(r) / float(den), w0 = 1 - w1 and the
+ * source indices clamp(f), clamp(f + 1): no weight depends on the rounding of a coordinate.  Interpolation runs along x, then y, then z,
+ * each step a w0 + b w1 rounded per operation; a term of weight exactly 0 is not added, so equal lattices copy the words.
+ * drt_grid_resample_transpose computes g_src = R^T g_dst (accumulate 0) or g_src += R^T g_dst (accumulate != 0; what an optimiser's
+ * gradient buffer wants) as a gather: every source entry sums its targets in ascending (z, y, x) order, each term ((wz wy) wx) g - no
+ * atomics, the same bits on every call.  Any 4-byte aligned float pointers; 16-byte accesses are used when both are 16-byte aligned and
+ * channels is a multiple of 4.  Refused with DRT_ERR_INVALID_ARGUMENT and a message (drt_last_error(NULL)), before any device work: a NULL
+ * or misaligned pointer, NULL extents, an extent outside 1..4096, channels outside 1..32, source and destination that overlap. */
+int drt_grid_resample(void *hip_stream, const float *src, const int32_t src_res[3], float *dst, const int32_t dst_res[3], int32_t channels);
+int drt_grid_resample_transpose(void *hip_stream, const float *g_dst, const int32_t dst_res[3], float *g_src, const int32_t src_res[3],
+                                int32_t channels, int accumulate);
+
 /* Event counting (off by default; enabling selects a counting build of the kernels). */
 int drt_enable_counters(drt_handle h, int enable);
 int drt_reset_counters(drt_handle h);

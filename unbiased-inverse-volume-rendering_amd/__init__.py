@@ -21,6 +21,7 @@ from .optimize import (Adam, OptimizationConfig, SGD, SceneConfig, Schedule, adj
                        render_reference_image, run_optimization, save_params, upsample_grid)
 from .pixel_dist import PixelDistribution, PixelImportance
 from .priors import Prior, prior_value_and_grad_, smoothness, sparsity, total_variation
+from .resample import resample_grid, resample_grid_transpose
 from .volume_io import medium_from_vol, read_vol, write_vol
 from .image_io import read_image, write_image
 from .fd import fd_gradients
@@ -38,5 +39,6 @@ __all__ = [
     "save_params", "upsample_grid", "read_vol", "write_vol", "medium_from_vol", "read_image", "write_image", "get_reference_image_paths",
     "load_reference_images", "render_previews", "render_reference_image", "fd_gradients",
     "Prior", "prior_value_and_grad_", "total_variation", "smoothness", "sparsity",
+    "resample_grid", "resample_grid_transpose",
     "PixelDistribution", "PixelImportance",
 ]

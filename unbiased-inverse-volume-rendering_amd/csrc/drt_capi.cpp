@@ -2181,6 +2181,44 @@ int drt_grid_prior(void *hip_stream, int32_t kind, const float *p, float *g, dou
     return DRT_OK;
 }
 
+// the checks that drt_grid_resample and its transpose share; `a` is the grid on the lattice a_res, `b` the one on b_res
+static int grid_resample_check(const char *who, const float *a, const int32_t a_res[3], const float *b, const int32_t b_res[3], int32_t channels)
+{
+    if (!a || !b) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null grid", who);
+    if (!a_res || !b_res) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null extents", who);
+    for (int i = 0; i < 3; ++i)
+        if (a_res[i] < 1 || a_res[i] > drt::kResampleMaxExtent || b_res[i] < 1 || b_res[i] > drt::kResampleMaxExtent)
+            return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: extents {%d,%d,%d} and {%d,%d,%d} (every extent must lie in 1..%d)", who, (int) a_res[0],
+                        (int) a_res[1], (int) a_res[2], (int) b_res[0], (int) b_res[1], (int) b_res[2], drt::kResampleMaxExtent);
+    if (channels < 1 || channels > drt::kPriorMaxChannels)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: %d channels (1..%d are supported)", who, (int) channels, drt::kPriorMaxChannels);
+    if ((((uintptr_t) a) | ((uintptr_t) b)) & 3u) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: grids must be 4-byte aligned", who);
+    const uint64_t a_bytes = (uint64_t) a_res[0] * (uint64_t) a_res[1] * (uint64_t) a_res[2] * (uint64_t) channels * sizeof(float);
+    const uint64_t b_bytes = (uint64_t) b_res[0] * (uint64_t) b_res[1] * (uint64_t) b_res[2] * (uint64_t) channels * sizeof(float);
+    if ((uintptr_t) a < (uintptr_t) b + b_bytes && (uintptr_t) b < (uintptr_t) a + a_bytes)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: source and destination overlap", who);
+    return DRT_OK;
+}
+
+int drt_grid_resample(void *hip_stream, const float *src, const int32_t src_res[3], float *dst, const int32_t dst_res[3], int32_t channels)
+{
+    const int rc = grid_resample_check("drt_grid_resample", src, src_res, dst, dst_res, channels);
+    if (rc != DRT_OK) return rc;
+    DRT_HIP_CHECK(nullptr, drt::launch_grid_resample(src, src_res[2], src_res[1], src_res[0], dst, dst_res[2], dst_res[1], dst_res[0], channels,
+                                                     (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
+int drt_grid_resample_transpose(void *hip_stream, const float *g_dst, const int32_t dst_res[3], float *g_src, const int32_t src_res[3],
+                                int32_t channels, int accumulate)
+{
+    const int rc = grid_resample_check("drt_grid_resample_transpose", g_dst, dst_res, g_src, src_res, channels);
+    if (rc != DRT_OK) return rc;
+    DRT_HIP_CHECK(nullptr, drt::launch_grid_resample_transpose(g_dst, dst_res[2], dst_res[1], dst_res[0], g_src, src_res[2], src_res[1], src_res[0],
+                                                               channels, accumulate != 0, (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
 int drt_grad_support_mask(void *hip_stream, const float *sigma_t, const int32_t res[3], uint64_t sparse_offset_floats, uint32_t channels,
                           uint64_t n_blocks, uint32_t block_floats, uint32_t *bits_scratch, uint8_t *mask)
 {

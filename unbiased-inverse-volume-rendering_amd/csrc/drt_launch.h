@@ -207,6 +207,15 @@ bool grid_prior_supported(int64_t nz, int64_t ny, int64_t nx, int64_t nc);
 uint64_t grid_prior_partials(int nz, int ny, int nx, int nc);        // 0: not a grid the kernel takes
 hipError_t launch_grid_prior(int kind, const float *p, float *g, double *value, double *partials, int nz, int ny, int nx, int nc, double weight,
                              float eps, hipStream_t stream);
+// grid resampling (drt_resample.hip): the grid src (sz,sy,sx,nc) evaluated by the lookup convention of axis_setup at the voxel centres of the
+// lattice (tz,ty,tx), with integer-derived weights, and the transpose of that linear map as a gather (g_src = or += R^T g_dst; no atomics,
+// the same bits on every call).  Extents 1..kResampleMaxExtent, nc 1..kPriorMaxChannels; source and destination must not overlap.  16-byte
+// accesses when both pointers are 16-byte aligned and nc is a multiple of 4, 4-byte ones otherwise.
+constexpr int kResampleMaxExtent = 4096;
+bool grid_resample_supported(int64_t sz, int64_t sy, int64_t sx, int64_t tz, int64_t ty, int64_t tx, int64_t nc);
+hipError_t launch_grid_resample(const float *src, int sz, int sy, int sx, float *dst, int tz, int ty, int tx, int nc, hipStream_t stream);
+hipError_t launch_grid_resample_transpose(const float *g_dst, int tz, int ty, int tx, float *g_src, int sz, int sy, int sx, int nc,
+                                          bool accumulate, hipStream_t stream);
 // importance-sampled pixel batches (drt_pixel_dist.hip): a table over n < 2^31 film entries = this header, the exclusive uint64 prefix of the
 // sums of blocks of kDistBlock masses [n_blocks + 1], then the 16-bit masses padded to whole blocks (16-byte aligned)
 constexpr uint32_t kDistBlock = 256;

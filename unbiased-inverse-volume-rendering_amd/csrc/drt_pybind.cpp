@@ -470,6 +470,21 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
                                       reinterpret_cast<double *>(value), reinterpret_cast<void *>(scratch), scratch_bytes, nz, ny, nx, nc, weight, eps);
         if (rc != DRT_OK) throw std::runtime_error(std::string("drt_grid_prior: ") + drt_last_error(nullptr));
     });
+    // grids are (Z,Y,X,C): the extents arrive in tensor order and go to the C ABI as {X,Y,Z}
+    m.def("grid_resample", [](uintptr_t stream, uintptr_t src, int32_t sz, int32_t sy, int32_t sx, uintptr_t dst, int32_t tz, int32_t ty, int32_t tx,
+                              int32_t channels) {
+        const int32_t sres[3] = {sx, sy, sz}, tres[3] = {tx, ty, tz};
+        const int rc = drt_grid_resample(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(src), sres, reinterpret_cast<float *>(dst),
+                                         tres, channels);
+        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+    });
+    m.def("grid_resample_transpose", [](uintptr_t stream, uintptr_t g_dst, int32_t tz, int32_t ty, int32_t tx, uintptr_t g_src, int32_t sz, int32_t sy,
+                                        int32_t sx, int32_t channels, bool accumulate) {
+        const int32_t sres[3] = {sx, sy, sz}, tres[3] = {tx, ty, tz};
+        const int rc = drt_grid_resample_transpose(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(g_dst), tres,
+                                                   reinterpret_cast<float *>(g_src), sres, channels, accumulate ? 1 : 0);
+        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+    });
     m.def("pixel_dist_table_bytes", [](uint64_t n) { return drt_pixel_dist_table_bytes(n); });
     m.def("pixel_dist_build", [](uintptr_t stream, uintptr_t weights, uint64_t n, float decay, uintptr_t table, uint64_t table_bytes) {
         const int rc = drt_pixel_dist_build(reinterpret_cast<void *>(stream), reinterpret_cast<float *>(weights), n, decay,

@@ -24,6 +24,7 @@ from .opt_config import get_int_config
 from .pixel_dist import PixelDistribution, PixelImportance
 from .priors import Prior, prior_value_and_grad_
 from .render import render, render_primal
+from .resample import MAX_CHANNELS as RESAMPLE_MAX_CHANNELS, resample_grid
 from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, PHASE_TAB_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, TabPhase, require_hg
 from .image_io import read_image, write_image
 from .volume_io import write_vol
@@ -67,6 +68,10 @@ class OptimizationConfig:
     # opt-in: draw the batches from a per-pixel error map instead of uniformly (pixel_dist.py; batched, unsharded, unfused runs with a
     # pixel-separable loss); None: the uniform batches of the reference
     pixel_importance: Optional[PixelImportance] = None
+    # opt-in: render every colour grid (albedo, emission) whose lattice differs from sigma_t's through resample.resample_grid onto
+    # sigma_t's lattice, so that the run takes the equal-lattice kernels; the parameters stay on their own lattices.  False, or equal
+    # lattices: nothing extra runs
+    resample_colour: bool = False
 
     def __post_init__(self):
         self.upsample_at = set()
@@ -437,7 +442,18 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     loss): the batch of every iteration is drawn from a `PixelDistribution` over the sensors' film, the step's loss is
     sum_b inv_pdf_b * ell_b / image.numel() with ell = `losses.pixelwise(loss)(image, ref)` - an unbiased estimate of the loss a uniform batch
     estimates -, and after `backward()` the map takes max(map, ell) at the batch's pixels and is decayed and rebuilt every `rebuild_every`
-    iterations.  Priors compose unchanged; grid upsampling does not touch the map."""
+    iterations.  Priors compose unchanged; grid upsampling does not touch the map.
+
+    `opt_config.resample_colour`: every colour grid (albedo, emission - SH coefficients included) whose lattice differs from sigma_t's is
+    rendered through `resample_grid(grid, sigma_t.shape[:3])`, optimised or fixed, so the scene bound to the integrator has equal lattices
+    (the production kernels; `sh_degree`, `aovs`, `distortion` become usable on an own-lattice emission asset).  An optimised colour grid
+    stays a leaf on ITS lattice: the resample runs inside the iteration, `backward()` reaches the leaf through the transpose kernel, and
+    priors, the optimizer, the clamps, `upsample` and the checkpoints act on the leaf; fixed grids are resampled once, and again after
+    sigma_t is upsampled.  Every route goes through autograd (plain, batched, `fused_loss`, `pixel_importance`, sharded: the all-reduced
+    gradient on sigma_t's lattice is transposed by every rank alike), so all of them see the operator.  `params` comes back on its own
+    lattices; the returned scene carries the RENDERED (resampled) colour grids, detached.  This is one extra trilinear interpolation of
+    the colour grids, not what Mitsuba renders from such an asset.  With equal lattices the flag launches nothing and the run's bits are
+    those of a run without it."""
     from .distributed import ShardSpec, allreduce_scalar, local_loss_scale, verify_pending
     from . import losses as _losses
     shard = shard or ShardSpec()
@@ -601,10 +617,38 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
                 out[k] = full[k]
         return out
 
+    resample = opt_config.resample_colour
+    if not isinstance(resample, bool):
+        raise ValueError(f"resample_colour must be a bool, got {resample!r}")
+
+    def off_lattice(grids):
+        """The colour grids of `grids` that `resample_colour` renders through the resampling operator."""
+        res = tuple(grids[SIGMA_T_KEY].shape[:3])
+        return [k for k in (ALBEDO_KEY, EMISSION_KEY) if resample and k in grids and tuple(grids[k].shape[:3]) != res]
+
+    @torch.no_grad()
+    def bound_grids(grids):
+        """`grids` as the scene bound to the integrator holds them: with `resample_colour` the colour grids off sigma_t's lattice are
+        resampled onto it (detached copies; an optimised one is the state of this moment), everything else is the tensor itself."""
+        off = off_lattice(grids)
+        res = tuple(grids[SIGMA_T_KEY].shape[:3])
+        return {k: (resample_grid(g.detach(), res) if k in off else g) for k, g in grids.items()}
+
     grids = current_grids()
+    for k in off_lattice(grids):
+        if grids[k].shape[-1] > RESAMPLE_MAX_CHANNELS:
+            raise ValueError(f'resample_colour: "{k}" has {grids[k].shape[-1]} channels on the lattice {tuple(grids[k].shape[:3])}; the '
+                             f'resampling operator takes 1..{RESAMPLE_MAX_CHANNELS} (spherical harmonics up to degree 2)')
     factor = adjusted_majorant_res_factor(scene_config.majorant_resolution_factor, grids[SIGMA_T_KEY].shape)
     opt = opt_config.optimizer(params)
-    scene = _scene_with(Scene(scene0.medium, scene0.emitter, sensors), grids, factor)
+    bound = bound_grids(grids)
+    scene = _scene_with(Scene(scene0.medium, scene0.emitter, sensors), bound, factor)
+
+    def rendered_scene():
+        """`scene`, with the optimised colour grids that are rendered through the operator as they are NOW (previews, the result)."""
+        if not any(k in params for k in off_lattice(grids)):
+            return scene
+        return _scene_with(scene, bound_grids(grids), factor)
     table = sensors_to_device(sensors, dev)
     dist = None
     if importance is not None:                                         # one map per film: created here, where the film is fixed for the run
@@ -634,33 +678,38 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
                 params[k] = opt[k]
             grids = current_grids()
             factor = adjusted_majorant_res_factor(scene_config.majorant_resolution_factor, grids[SIGMA_T_KEY].shape)
-            scene = _scene_with(scene, grids, factor)
+            bound = bound_grids(grids)                                 # (fixed colour grids follow sigma_t's new lattice)
+            scene = _scene_with(scene, bound, factor)
         # leaves: what the integrator differentiates; only the optimised ones require (and receive) gradients
-        leaves = {k: (params[k].detach().requires_grad_(True) if k in params else grids[k].detach())
+        leaves = {k: (params[k].detach().requires_grad_(True) if k in params else bound[k].detach())
                   for k in integrator.param_keys}
         if PHASE_G_KEY in params:
             leaves[PHASE_G_KEY] = params[PHASE_G_KEY].detach().requires_grad_(True)
         if PHASE_TAB_KEY in params:
             leaves[PHASE_TAB_KEY] = params[PHASE_TAB_KEY].detach().requires_grad_(True)
+        # what the integrator reads: the leaves - an optimised colour grid off sigma_t's lattice through the operator, inside autograd
+        rendered = dict(leaves)
+        for k in off_lattice(leaves):
+            rendered[k] = resample_grid(leaves[k], tuple(leaves[SIGMA_T_KEY].shape[:3]))
         if opt_config.fused_loss and opt_config.batch_size is not None:   # the same step, film + loss + gather fused (loss_fused.py)
             loss_value, image, _, _ = render_batch_loss(
-                opt_config.batch_size, scene, ref_images, loss=opt_config.loss, sensors=sensors, params=leaves, integrator=integrator,
+                opt_config.batch_size, scene, ref_images, loss=opt_config.loss, sensors=sensors, params=rendered, integrator=integrator,
                 spp=spp_primal, spp_grad=spp_grad, seed=seed, seed_grad=seed_grad, sensor_table=table)
         elif opt_config.fused_loss:
             s_i = int(torch.rand((), generator=host_rng).item() * n_sensors)
-            loss_value, image = render_loss(scene, ref_images[s_i].reshape(-1, 3), loss=opt_config.loss, params=leaves,
+            loss_value, image = render_loss(scene, ref_images[s_i].reshape(-1, 3), loss=opt_config.loss, params=rendered,
                                             integrator=integrator, sensor=s_i, spp=spp_primal, spp_grad=spp_grad, seed=seed,
                                             seed_grad=seed_grad)
         elif opt_config.batch_size is not None:                        # batched rendering (:332-341)
             image, _, _, sensor_idx, pixel_idx = render_batch(
-                opt_config.batch_size, scene, sensors=sensors, params=leaves, integrator=integrator,
+                opt_config.batch_size, scene, sensors=sensors, params=rendered, integrator=integrator,
                 spp=spp_primal, spp_grad=spp_grad, seed=seed, seed_grad=seed_grad, sensor_table=table, shard=shard,
                 pixel_distribution=dist)
             ref_values = gather_ref_values(ref_images, sensor_idx, pixel_idx)
             n_global = opt_config.batch_size
         else:                                                          # sensor-based rendering (:342-348)
             s_i = int(torch.rand((), generator=host_rng).item() * n_sensors)
-            image = render(scene, params=leaves, integrator=integrator, sensor=s_i, spp=spp_primal,
+            image = render(scene, params=rendered, integrator=integrator, sensor=s_i, spp=spp_primal,
                            spp_grad=spp_grad, seed=seed, seed_grad=seed_grad, shard=shard if shard.partitioned else None)
             ref_values = ref_images[s_i].reshape(-1, ref_images.shape[-1])
             n_global = ref_values.shape[0]
@@ -706,13 +755,13 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         if writer and it_i > 0 and opt_config.checkpoint_stride and it_i % opt_config.checkpoint_stride == 0:
             save_params(os.path.join(output_dir, 'params'), scene_config, params, f'{it_i:08d}', scene.medium)
         if writer and it_i > 0 and opt_config.preview_stride and it_i % opt_config.preview_stride == 0:   # :357-358
-            render_previews(output_dir, opt_config, scene_config, _scene_at_g(scene, params), integrator, it_i)
+            render_previews(output_dir, opt_config, scene_config, _scene_at_g(rendered_scene(), params), integrator, it_i)
         if progress:
             progress(it_i, history[-1])
     if shard.partitioned:
         # the packed all-reduce of the last backward pass left its check to "the next call": this is it (raised, never silent)
         verify_pending()
-    scene = _scene_at_g(scene, params)                                 # the scene returned (and previewed) carries the optimised g
+    scene = _scene_at_g(rendered_scene(), params)                      # the scene returned (and previewed) carries the optimised g
     if writer and opt_config.checkpoint_final:
         save_params(os.path.join(output_dir, 'params'), scene_config, params, 'final', scene.medium)
     if writer:

@@ -51,7 +51,7 @@ def read_vol(path: str):
 
 
 def medium_from_vol(medium_filename: str, albedo_filename=None, emission_filename=None, albedo_value: float = 0.6,
-                    scale: float = 1.0, majorant_resolution_factor: int = 0, device=None, phase=None):
+                    scale: float = 1.0, majorant_resolution_factor: int = 0, device=None, phase=None, resample_colour: bool = False):
     """A `GridMedium` from `.vol` files - the `medium_filename` / `albedo_filename` / `emission_filename` variables of
     the reference's scene descriptions (python/scene_config.py:84-141), e.g. the checkpoints of a previous run for a
     warm start (`janga-smoke-from-nerf`: `<output>/<run>/nerf/params/final-medium1_sigma_t.vol`, :123-141).
@@ -60,7 +60,12 @@ def medium_from_vol(medium_filename: str, albedo_filename=None, emission_filenam
     `albedo_value` on sigma_t's lattice.  An albedo / emission file keeps ITS OWN resolution (the reference pairs a
     264x136x136 density with 256x128x128 albedo / emission grids, :108-110; Mitsuba interpolates every grid on its own
     lattice): the integrators then run the own-lattice kernels (drt_set_colour_resolution, csrc/drt_own.hip).  Albedo and
-    emission files must share one lattice.  `phase`: the medium's phase function (default IsotropicPhase())."""
+    emission files must share one lattice.  `phase`: the medium's phase function (default IsotropicPhase()).
+
+    `resample_colour=True` (opt-in): an albedo / emission file whose lattice differs from the density's is resampled onto the density's
+    lattice at load time (`resample.resample_grid`, on `device`), and a constant albedo is made on it; the medium then has equal lattices
+    and takes the production kernels and every nerf output.  This is ONE EXTRA trilinear interpolation of the colour grids and not what
+    Mitsuba renders from these files: Mitsuba interpolates each grid on its own lattice, which is what the default (False) keeps."""
     import torch
     from .scene import GridMedium, IsotropicPhase
     sig, bmin, bmax = read_vol(medium_filename)
@@ -89,6 +94,11 @@ def medium_from_vol(medium_filename: str, albedo_filename=None, emission_filenam
     if emission is not None and albedo_filename is None:                  # (a constant albedo follows the emission's lattice)
         albedo = torch.full(tuple(emission.shape[:3]) + (3,), float(albedo_value), dtype=torch.float32)
     to = (lambda t: t.to(device)) if device is not None else (lambda t: t)
+    if resample_colour:
+        from .resample import resample_grid
+        res = tuple(int(r) for r in res3)
+        albedo = resample_grid(to(albedo), res) if albedo_filename is not None else torch.full(res + (3,), float(albedo_value), dtype=torch.float32)
+        emission = resample_grid(to(emission), res) if emission is not None else None
     return GridMedium(sigma_t=to(torch.from_numpy(sig.copy())), albedo=to(albedo), bbox_min=bmin, bbox_max=bmax, scale=scale,
                       majorant_resolution_factor=majorant_resolution_factor,
                       emission=to(emission) if emission is not None else None, phase=IsotropicPhase() if phase is None else phase)
