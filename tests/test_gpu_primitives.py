@@ -123,6 +123,30 @@ def test_grid_lookup_and_box(uivr, oracle, gpu):
     np.testing.assert_array_equal(_bits(got[:, :5]), _bits(ref))
 
 
+@pytest.mark.parametrize("shape, colour_shape", [((6, 7, 5), (4, 5, 3)),      # (Z,Y,X); the albedo grid smaller on every axis
+                                                 ((4, 5, 3), (6, 7, 5))])     # ... and larger
+def test_albedo_lookup_on_its_own_lattice(uivr, oracle, gpu, shape, colour_shape):
+    """Debug op 4 (eval_albedo) on a handle whose albedo grid has its own lattice (drt_set_colour_resolution) reads that lattice: bit-equal
+    to the oracle, which interpolates the albedo on res_colour."""
+    L = oracle.lib()
+    rng = np.random.default_rng(14)
+    sigma_t = rng.random(shape + (1,), dtype=np.float32) * 3
+    albedo = rng.random(colour_shape + (3,), dtype=np.float32)
+    medium = uivr.GridMedium(sigma_t=sigma_t, albedo=albedo, bbox_min=(-1, 0, 2), bbox_max=(1.5, 3, 2.5), scale=1.7)
+    scene = uivr.Scene(medium=medium, emitter=uivr.ConstantEmitter(), sensors=[])
+    osc = oracle.OracleScene(scene, sensor_index=None)
+    assert tuple(osc.medium.res_colour) == colour_shape[::-1] and tuple(osc.medium.res) == shape[::-1]
+    lo, hi = np.float32(medium.bbox_min), np.float32(medium.bbox_max)
+    p = (lo + (hi - lo) * (rng.random((2000, 3), dtype=np.float32) * 1.1 - 0.05)).astype(np.float32)  # incl. slightly outside
+    got = _eval(uivr, gpu, scene, 4, p)[:, :3]
+    out = (C.c_float * 3)()
+    ref = np.zeros_like(got)
+    for i, q in enumerate(p):
+        L.drto_eval_albedo(C.byref(osc.medium), (C.c_float * 3)(*q), out)
+        ref[i] = out[:]
+    np.testing.assert_array_equal(_bits(got), _bits(ref))
+
+
 def test_ieee_div_sqrt(uivr, gpu):
     scene = uivr.cube_test_scene(8, 8)
     rng = np.random.default_rng(5)

@@ -17,11 +17,11 @@ def test_library_exports_the_aov_calls(uivr, hooks):
     for n in AOV_SYMBOLS:
         assert hasattr(lib, n), f"{library_path(hooks)} does not export {n}"
     # the AOV instantiations of the shared kernels are in the library beside the plain ones: the window kernel for both kinds of lookup
-    # (PlainWindow<G4>, AOV), the per-lane primal, both adjoint routes (records / apron scratch) and forward mode (PlainEmission, ..., AOV)
+    # (PlainWindow<G4>, AOV), the per-lane primal, both adjoint routes (records / apron scratch) and forward mode (PlainEmission<false>: sigma_t's lattice, ..., AOV)
     blob = open(library_path(hooks), "rb").read()
     for k in (b"nerf_tile_adjoint_kernelINS0_11PlainWindowILb0EEELb1EJEE", b"nerf_tile_adjoint_kernelINS0_11PlainWindowILb1EEELb1EJEE", b"nerf_tile_adjoint_kernelINS0_11PlainWindowILb0EEELb0EJEE",
-              b"nerf_tile_adjoint_kernelINS0_11PlainWindowILb1EEELb0EJEE", b"nerf_kernelINS0_13PlainEmissionELb0ELb0ELb0ELb1EJEE", b"nerf_kernelINS0_13PlainEmissionELb1ELb0ELb1ELb1EJEE",
-              b"nerf_kernelINS0_13PlainEmissionELb1ELb0ELb0ELb1EJEE", b"nerf_kernelINS0_13PlainEmissionELb0ELb0ELb0ELb0EJEE", b"nerf_fwd_kernelINS0_13PlainEmissionELb1EJEE", b"nerf_fwd_kernelINS0_13PlainEmissionELb0EJEE"):
+              b"nerf_tile_adjoint_kernelINS0_11PlainWindowILb1EEELb0EJEE", b"nerf_kernelINS0_13PlainEmissionILb0EEELb0ELb0ELb0ELb1EJEE", b"nerf_kernelINS0_13PlainEmissionILb0EEELb1ELb0ELb1ELb1EJEE",
+              b"nerf_kernelINS0_13PlainEmissionILb0EEELb1ELb0ELb0ELb1EJEE", b"nerf_kernelINS0_13PlainEmissionILb0EEELb0ELb0ELb0ELb0EJEE", b"nerf_fwd_kernelINS0_13PlainEmissionILb0EEELb1EJEE", b"nerf_fwd_kernelINS0_13PlainEmissionILb0EEELb0EJEE"):
         assert k in blob, k
 
 

@@ -16,7 +16,8 @@ using namespace coop;
 // PH: the phase function (CoopTracer).  kHG, kHGGrad, kHG2, kTab: those kernels run without hand-off and tail pool; kHGGrad (adjoint): the
 // g-gradient too - each wave adds the sum of its lanes' terms to *Params::L_out with one atomic at its end; kTabGrad (adjoint): the table-value
 // gradient - Params::L_out is the sink block (drt_device.h: TabSink), each wave adds the sum of its lanes' coefficients to its replica's W
-template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool SUPER = false, bool TAIL = false, Phase PH = Phase::kIso>
+// OWN: the albedo grid on its own lattice (CoopTracer)
+template <bool ADJ, bool COUNT, bool ENV, bool DEFER, bool SPEC, bool SUPER, bool TAIL, Phase PH, bool OWN>
 __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRIMAL) trace_coop_kernel(const Params P)
 {
     constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, TG = PH == Phase::kTabGrad;
@@ -40,7 +41,7 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
         if (P.ray_perm) i = (i_block & ~(uint64_t) (kPermGroup - 1)) + P.ray_perm[i_block + threadIdx.x];
     }
     static_assert(!(GG || TG) || (ADJ && !TAIL), "the phase-gradient kernels (kHGGrad, kTabGrad) are adjoint kernels and have no tail launch");
-    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, PH> tr(P);
+    CoopTracer<COUNT, ENV, DEFER, SPEC, false, SUPER, false, PH, OWN> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     tr.i_block = TAIL ? 0 : i_block;
@@ -168,7 +169,7 @@ __global__ void __launch_bounds__(256, ADJ ? DRT_COOP_WAVES : DRT_COOP_WAVES_PRI
 // bit-reproducible).  The global majorant's NEE walks take every step on the walk's own lane (CoopTracer::coop_rt).
 // PH = kHGGrad: J t includes t_g (Params::phase_tg) times the derivative with respect to g; kTabGrad: the derivative along the table tangent
 // (tau behind the guide words of the table block, kappa in Params::phase_tg: tab_tangent_score)
-template <bool ENV, bool SPEC, bool SUPER, Phase PH = Phase::kIso>
+template <bool ENV, bool SPEC, bool SUPER, Phase PH, bool OWN>
 __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(const Params P)
 {
     uint32_t b = blockIdx.x;                                    // XCD-aware block -> ray-chunk map (see trace_coop_kernel)
@@ -183,7 +184,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     }
 #endif
     const uint64_t i = P.ray_first + (uint64_t) b * blockDim.x + threadIdx.x;
-    CoopTracer<false, ENV, false, SPEC, false, SUPER, true, PH> tr(P);
+    CoopTracer<false, ENV, false, SPEC, false, SUPER, true, PH, OWN> tr(P);
     __shared__ uint32_t slot_lds[4 * 64];
     tr.slots = slot_lds + (threadIdx.x >> 6) * 64;
     __shared__ uint64_t jump_lds[2 * (kJumpMax + 1)];
@@ -230,7 +231,7 @@ __global__ void __launch_bounds__(256, DRT_COOP_WAVES) trace_coop_fwd_kernel(con
     if (job) { P.L_out[3 * i] = tr.tg[0]; P.L_out[3 * i + 1] = tr.tg[1]; P.L_out[3 * i + 2] = tr.tg[2]; }
 }
 
-template <bool SUPER, Phase PH>
+template <bool SUPER, Phase PH, bool OWN>
 hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
 {
     if (P.n_rays <= P.ray_first) return hipSuccess;
@@ -238,11 +239,11 @@ hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
     const bool env = P.env_pix != nullptr;
     const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !dbg(P.debug_flags, kHookGenericKernels);
     if (spec) {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, PH>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, PH>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, true, SUPER, PH, OWN>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, true, SUPER, PH, OWN>), grid, block, 0, stream, P);
     } else {
-        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER, PH>), grid, block, 0, stream, P);
-        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER, PH>), grid, block, 0, stream, P);
+        if (env) hipLaunchKernelGGL((trace_coop_fwd_kernel<true, false, SUPER, PH, OWN>), grid, block, 0, stream, P);
+        else hipLaunchKernelGGL((trace_coop_fwd_kernel<false, false, SUPER, PH, OWN>), grid, block, 0, stream, P);
     }
     return hipGetLastError();
 }
@@ -250,7 +251,7 @@ hipError_t launch_trace_coop_fwd_t(const Params &P, hipStream_t stream)
 // launch of the instantiation that fits the job.  kHG, kHGGrad, kHG2: no tail pool, no hand-off.  kHGGrad: the adjoint launch with the
 // g-gradient (dLoss/dg is added to *P.L_out) - the choice of a kHG adjoint launch without the counting kernels (a counting handle's g-gradient
 // launch counts nothing); its primal and counting kernels are kHG's (kPlain)
-template <bool SUPER, Phase PH>
+template <bool SUPER, Phase PH, bool OWN>
 hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx, bool *called)
 {
     constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad || PH == Phase::kTabGrad;   // (GG: a phase-gradient launch of either kind)
@@ -262,14 +263,14 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
     }
     dim3 block(256), grid((unsigned)((P.n_rays - P.ray_first + 255) / 256));
     const bool env = P.env_pix != nullptr, defer = adjoint && P.rec_buf[0] != nullptr;
-#define DRT_COOP_LAUNCH(A, C, E, D) hipLaunchKernelGGL((trace_coop_kernel<A, C, E, D, false, SUPER, false, (A) && !(C) ? PH : kPlain>), grid, block, 0, stream, P)
+#define DRT_COOP_LAUNCH(A, C, E, D) hipLaunchKernelGGL((trace_coop_kernel<A, C, E, D, false, SUPER, false, (A) && !(C) ? PH : kPlain, OWN>), grid, block, 0, stream, P)
     // the registered `volpathsimple-drt` configuration (either emitter): specialised kernels
     const bool spec = P.use_nee && P.use_drt && P.use_drt_subsampling && !count && !dbg(P.debug_flags, kHookGenericKernels);
 #if DRT_PHASE_PROFILE
     // experiment build: the counting launches run the specialised kernels too (their counters then hold phase cycles)
     if (!HG && P.use_nee && P.use_drt && P.use_drt_subsampling && count && !env) {
-        if (!adjoint) { hipLaunchKernelGGL((trace_coop_kernel<false, true, false, false, true, SUPER>), grid, block, 0, stream, P); return hipGetLastError(); }
-        if (defer) { hipLaunchKernelGGL((trace_coop_kernel<true, true, false, true, true, SUPER>), grid, block, 0, stream, P); return hipGetLastError(); }
+        if (!adjoint) { hipLaunchKernelGGL((trace_coop_kernel<false, true, false, false, true, SUPER, false, Phase::kIso, OWN>), grid, block, 0, stream, P); return hipGetLastError(); }
+        if (defer) { hipLaunchKernelGGL((trace_coop_kernel<true, true, false, true, true, SUPER, false, Phase::kIso, OWN>), grid, block, 0, stream, P); return hipGetLastError(); }
     }
 #endif
     // ... each followed by its tail launch (the workgroups' last few paths, pooled: wg_handoff) when the caller gave a pool
@@ -292,21 +293,21 @@ hipError_t launch_trace_coop_t(const Params &P, bool adjoint, bool count, hipStr
     const dim3 tgrid(tail ? P.tail_cap / 256u : 1u);
     // (pool capacity = 1/8 of the launch's rays; the tail kernel's surplus workgroups return at once)
     if (spec && !adjoint) {
-        if (env) hipLaunchKernelGGL((trace_coop_kernel<false, false, true, false, true, SUPER, false, kPlain>), grid, block, 0, stream, M);
-        else hipLaunchKernelGGL((trace_coop_kernel<false, false, false, false, true, SUPER, false, kPlain>), grid, block, 0, stream, M);
+        if (env) hipLaunchKernelGGL((trace_coop_kernel<false, false, true, false, true, SUPER, false, kPlain, OWN>), grid, block, 0, stream, M);
+        else hipLaunchKernelGGL((trace_coop_kernel<false, false, false, false, true, SUPER, false, kPlain, OWN>), grid, block, 0, stream, M);
         return hipGetLastError();
     }
     if (spec && defer) {
-        if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, SUPER, false, PH>), grid, block, 0, stream, M);
-        else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, SUPER, false, PH>), grid, block, 0, stream, M);
+        if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, SUPER, false, PH, OWN>), grid, block, 0, stream, M);
+        else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, SUPER, false, PH, OWN>), grid, block, 0, stream, M);
         if constexpr (!SUPER && !HG) if (tail) {
             if (between) {                                     // (e.g. the early histogram pass of the record streams)
                 hipError_t e = between(between_ctx);
                 if (e != hipSuccess) return e;
                 if (called) *called = true;
             }
-            if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, false, true>), tgrid, block, 0, stream, T);
-            else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, false, true>), tgrid, block, 0, stream, T);
+            if (env) hipLaunchKernelGGL((trace_coop_kernel<true, false, true, true, true, false, true, Phase::kIso, OWN>), tgrid, block, 0, stream, T);
+            else hipLaunchKernelGGL((trace_coop_kernel<true, false, false, true, true, false, true, Phase::kIso, OWN>), tgrid, block, 0, stream, T);
         }
         return hipGetLastError();
     }
@@ -331,16 +332,14 @@ template <Phase PH, bool SUPER, bool OWN>
 hipError_t CoopUnit<PH, SUPER, OWN>::trace(const Params &P, bool adjoint, bool count, hipStream_t stream, coop_between_fn between, void *between_ctx,
                                            bool *called)
 {
-    static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
     if (OWN) between = nullptr;
-    return launch_trace_coop_t<SUPER, PH>(P, adjoint, count, stream, between, between_ctx, called);
+    return launch_trace_coop_t<SUPER, PH, OWN>(P, adjoint, count, stream, between, between_ctx, called);
 }
 
 template <Phase PH, bool SUPER, bool OWN>
 hipError_t CoopUnit<PH, SUPER, OWN>::forward(const Params &P, hipStream_t stream)
 {
-    static_assert(OWN == kColourOwn, "a unit instantiates the kernels of its own lattice");
-    return launch_trace_coop_fwd_t<SUPER, PH>(P, stream);
+    return launch_trace_coop_fwd_t<SUPER, PH, OWN>(P, stream);
 }
 
 }  // namespace drt

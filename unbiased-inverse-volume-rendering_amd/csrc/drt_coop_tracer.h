@@ -132,7 +132,8 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 //   (drt_device.h: TabSink).  Adjoint: every term adds its two hat-function shares to the sink (tab_sink_add, at wave-uniform places) and its
 //   coefficient to g_acc (the kernel adds a wave's sum to the replica's W once); forward mode: g_S carries the scores along the tangent
 //   (tab_tangent_score) and every contribution adds c (g_S + explicit term) to tg.
-template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, Phase PH = Phase::kIso>
+// OWN: the albedo grid and its gradient / tangent grid on their own lattice (drt_device.h: make_stencil_colour).
+template <bool COUNT, bool ENV, bool DEFER, bool SPEC = false, bool G4 = false, bool SUPER = false, bool FWD = false, Phase PH = Phase::kIso, bool OWN = false>
 struct CoopTracer {
     static constexpr bool HG = PH != Phase::kIso, GG = PH == Phase::kHGGrad, H2 = PH == Phase::kHG2, TG = PH == Phase::kTabGrad,
                           TB = PH == Phase::kTab || TG;
@@ -651,7 +652,7 @@ struct CoopTracer {
                 // hand-off mode: everything the final splat needs is computed now and travels with the recursive path
                 Tail tl;
                 tl.p = p; tl.sig = sig;
-                if (found) { if constexpr (!G4) eval_albedo(P, p, alb); count(C_ALB); }
+                if (found) { if constexpr (!G4) eval_albedo<OWN>(P, p, alb); count(C_ALB); }
                 const float w = P.use_drt_mis ? 1.0f / (1.0f + sig * sig) : 1.0f;   // :571-575
                 const float ww = w * W;
 #pragma unroll
@@ -664,13 +665,13 @@ struct CoopTracer {
         sample_recursive(found, A, p, depth, Li);                               // :565-568
         if (found) {
             float w = P.use_drt_mis ? 1.0f / (1.0f + sig * sig) : 1.0f;         // :571-575
-            if constexpr (!G4) eval_albedo(P, p, alb);                          // :578
+            if constexpr (!G4) eval_albedo<OWN>(P, p, alb);                     // :578
             count(C_ALB);
             float ww = w * W;
             if constexpr (FWD) {                                                // :577-581 transposed: (sigma_t albedo_k)' per channel
                 const float ts = gather_sigma_t(P, p);
                 float ta[3];
-                gather_colour(P, p, ta);
+                gather_colour<OWN>(P, p, ta);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) tg[k] += ((ww * adj[k]) * Li[k]) * (alb[k] * ts + sig * ta[k]);
                 return;
@@ -682,7 +683,7 @@ struct CoopTracer {
                 gs += a * alb[k];
                 ga[k] = a * sig;
             }
-            splat_scatter<DEFER>(P, p, gs, ga, rec); count(C_SC); count(C_SC_ALB);   // :577-581
+            splat_scatter<DEFER, OWN>(P, p, gs, ga, rec); count(C_SC); count(C_SC_ALB);   // :577-581
         }
     }
 
@@ -807,7 +808,7 @@ struct CoopTracer {
                 gs += a * tl.alb[k];
                 ga[k] = a * tl.sig;
             }
-            splat_scatter<DEFER>(P, tl.p, gs, ga, rec); count(C_SC); count(C_SC_ALB);
+            splat_scatter<DEFER, OWN>(P, tl.p, gs, ga, rec); count(C_SC); count(C_SC_ALB);
             job = false;
         }
         uint64_t am = __ballot(active);
@@ -975,7 +976,7 @@ struct CoopTracer {
             const bool did_escape = run && !mei.valid, did_scatter = run && mei.valid;   // :130-134
             has_scattered |= did_scatter;
 
-            if (did_scatter) { if constexpr (!G4) eval_albedo(P, mei.p, albedo); count(C_ALB); }
+            if (did_scatter) { if constexpr (!G4) eval_albedo<OWN>(P, mei.p, albedo); count(C_ALB); }
 
             if constexpr (ADJ) {
                 if (use_drt()) {                                                // :143-150
@@ -1007,7 +1008,7 @@ struct CoopTracer {
                     if constexpr (FWD) {                                        // :170 transposed: (sigma_t albedo_k)' per channel
                         const float ts = gather_sigma_t(P, mei.p);
                         float ta[3];
-                        gather_colour(P, mei.p, ta);
+                        gather_colour<OWN>(P, mei.p, ta);
 #pragma unroll
                         for (int k = 0; k < 3; ++k) {
                             float Li = result[k] / fmaxf(1e-8f, albedo[k]);     // :167
@@ -1022,7 +1023,7 @@ struct CoopTracer {
                             gs += a * albedo[k];
                             ga[k] = a * mei.sigma_t;
                         }
-                        splat_scatter<DEFER>(P, mei.p, gs, ga, rec); count(C_SC); count(C_SC_ALB);
+                        splat_scatter<DEFER, OWN>(P, mei.p, gs, ga, rec); count(C_SC); count(C_SC_ALB);
                     }
                 }
                 if (run) backprop_transmittance(A, ray, did_escape ? si.t : mei.t, dL, result);   // :181-189

@@ -489,8 +489,8 @@ struct Params {
     // The colour grids - `albedo`, the nerf integrator's `emission` - on their OWN lattice (drt_set_colour_resolution): Mitsuba interpolates every
     // GridVolume on its own resolution, and the reference's janga-smoke pairs a 264 x 136 x 136 density with 256 x 128 x 128 albedo / emission grids
     // (python/scene_config.py:108-110).  colour_own = 0: the lattice of sigma_t (crx = rx, ...), every kernel as before.  colour_own = 1: the job
-    // runs the kernels of drt_own.hip - the only translation unit compiled with DRT_COLOUR_OWN, in which eval_rgb and the colour splats read
-    // crx / cry / crz; in every other unit these fields are never read.  (At the end of the block: no other field moves.)
+    // runs the OWN = true instantiations (drt_own*.hip), in which eval_rgb and the colour splats read crx / cry / crz; no other kernel but the debug
+    // one reads these fields.  (At the end of the block: no other field moves.)
     int crx, cry, crz, colour_own;
     uint32_t sq_rounds;             // queued tracer, primal launches in index order: the medium is thin as far as the host knows (drt_capi.cpp: majorant read-back) - the ROUNDS kernels
     // loss-fused backward (drt_*render_backward_px): set instead of dL - the image gradient [pixels][3]; local ray i reads pixel i / spp (load_dL).
@@ -1129,33 +1129,30 @@ __device__ __forceinline__ void eval4(const Params &P, V3 p, float &sigma_t, flo
     rgb[2] = trilerp8(s, d0.w, d1.w, d2.w, d3.w, d4.w, d5.w, d6.w, d7.w);
 }
 
-// whether this translation unit is one of those compiled with the colour grids on their own lattice (drt_own*.hip)
-#ifdef DRT_COLOUR_OWN
-constexpr bool kColourOwn = true;
-#else
-constexpr bool kColourOwn = false;
-#endif
-
-// the stencil of a lookup into a COLOUR grid: on sigma_t's lattice everywhere but in drt_own.hip (DRT_COLOUR_OWN), where it is the grids' own
+// The lattice of the COLOUR grids (albedo / emission) is a template argument of everything that reads or splats them, without a default: OWN =
+// false is sigma_t's lattice, OWN = true the grids' own (Params::crx / cry / crz; the kernels instantiated in drt_own*.hip, which the host picks
+// with Params::colour_own).  Every call says which one it reads.
+template <bool OWN>
 __device__ __forceinline__ Stencil make_stencil_colour(const Params &P, V3 p)
 {
-#ifdef DRT_COLOUR_OWN
-    Stencil s;
-    axis_setup(p.x, P.bmin[0], P.inv_ext[0], P.crx, s.x0, s.x1, s.wx0, s.wx1);
-    axis_setup(p.y, P.bmin[1], P.inv_ext[1], P.cry, s.y0, s.y1, s.wy0, s.wy1);
-    axis_setup(p.z, P.bmin[2], P.inv_ext[2], P.crz, s.z0, s.z1, s.wz0, s.wz1);
-    s.y0 *= P.crx; s.y1 *= P.crx;
-    int sz = P.crx * P.cry;
-    s.z0 *= sz; s.z1 *= sz;
-    return s;
-#else
-    return make_stencil(P, p);
-#endif
+    if constexpr (OWN) {
+        Stencil s;
+        axis_setup(p.x, P.bmin[0], P.inv_ext[0], P.crx, s.x0, s.x1, s.wx0, s.wx1);
+        axis_setup(p.y, P.bmin[1], P.inv_ext[1], P.cry, s.y0, s.y1, s.wy0, s.wy1);
+        axis_setup(p.z, P.bmin[2], P.inv_ext[2], P.crz, s.z0, s.z1, s.wz0, s.wz1);
+        s.y0 *= P.crx; s.y1 *= P.crx;
+        int sz = P.crx * P.cry;
+        s.z0 *= sz; s.z1 *= sz;
+        return s;
+    } else {
+        return make_stencil(P, p);
+    }
 }
 
+template <bool OWN>
 __device__ __forceinline__ void eval_rgb(const Params &P, const float *g, V3 p, float out[3])
 {
-    Stencil s = make_stencil_colour(P, p);
+    Stencil s = make_stencil_colour<OWN>(P, p);
     int a = s.z0 + s.y0, b = s.z0 + s.y1, c = s.z1 + s.y0, d = s.z1 + s.y1;
     int i0 = 3 * (a + s.x0), i1 = 3 * (a + s.x1), i2 = 3 * (b + s.x0), i3 = 3 * (b + s.x1);
     int i4 = 3 * (c + s.x0), i5 = 3 * (c + s.x1), i6 = 3 * (d + s.x0), i7 = 3 * (d + s.x1);
@@ -1165,12 +1162,13 @@ __device__ __forceinline__ void eval_rgb(const Params &P, const float *g, V3 p, 
                            g[i4 + ch], g[i5 + ch], g[i6 + ch], g[i7 + ch]);
 }
 
+template <bool OWN>
 __device__ __forceinline__ void eval_albedo(const Params &P, V3 p, float out[3])
 {
 #if defined(DRT_EXP_ALB) && DRT_EXP_ALB == 1       // timing experiment: no albedo loads at all (results are wrong)
     out[0] = 0.8f; out[1] = 0.65f; out[2] = 0.45f + 1e-9f * p.x; return;
 #endif
-    eval_rgb(P, P.albedo, p, out);
+    eval_rgb<OWN>(P, P.albedo, p, out);
 }
 
 // Reverse mode of the trilinear gather = 8-corner scatter-add.  gfx950 has a
@@ -1440,15 +1438,14 @@ __device__ __forceinline__ void splat_sigma_t(const Params &P, V3 p, float g, ui
     coop_scatter<1>(P.gt, 0, idx, val, rec);
 }
 
-#ifdef DRT_COLOUR_OWN
-// drt_own.hip: the colour grids have their own lattice, which the tile partition, the LDS tiles and the apron scratch (all laid out on
+// OWN (drt_own*.hip): the colour grids have their own lattice, which the tile partition, the LDS tiles and the apron scratch (all laid out on
 // sigma_t's) do not know - the 8 x 3 corner products go straight to the caller's colour gradient grid (fp32 atomics).  Slow and correct: this
-// unit serves the configurations whose grids differ in resolution, not the benchmark.
+// route serves the configurations whose grids differ in resolution, not the benchmark.
 __device__ __forceinline__ void splat_colour_own(const Params &P, V3 p, const float g[3])
 {
     if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f) return;
     if (dbg(P.debug_flags, kHookNoGradAtomics)) return;
-    const Stencil st = make_stencil_colour(P, p);
+    const Stencil st = make_stencil_colour<true>(P, p);
     float w[8];
     stencil_weights(st, w);
     const int idx[8] = { st.z0 + st.y0 + st.x0, st.z0 + st.y0 + st.x1, st.z0 + st.y1 + st.x0, st.z0 + st.y1 + st.x1,
@@ -1460,16 +1457,15 @@ __device__ __forceinline__ void splat_colour_own(const Params &P, V3 p, const fl
         for (int c = 0; c < 3; ++c) if (g[c] != 0.0f) atomicAdd(dst + c, w[k] * g[c]);
     }
 }
-#endif
 
-template <bool DEFER = false>
+template <bool DEFER, bool OWN>
 __device__ __forceinline__ void splat_albedo(const Params &P, V3 p, const float g[3], uint32_t *rec)
 {
     static_assert(!DEFER, "deferred colour splats travel with their sigma_t splat: splat_scatter");
-#ifdef DRT_COLOUR_OWN
-    splat_colour_own(P, p, g);
-    return;
-#endif
+    if constexpr (OWN) {
+        splat_colour_own(P, p, g);
+        return;
+    }
     if (g[0] == 0.0f && g[1] == 0.0f && g[2] == 0.0f) return;   // e.g. nerf queries in empty space (weight 0)
     float w[8]; int idx[8];
     make_grad_indices(P, p, idx, w);
@@ -1493,14 +1489,14 @@ __device__ __forceinline__ void splat_albedo(const Params &P, V3 p, const float 
 // A sigma_t splat and a colour (albedo / emission) splat at the SAME point: scatter events
 // (volpathsimple.py:170,580) and nerf queries (nerf.py:122-129).  Deferred: ONE 32-byte record when any colour
 // channel is non-zero, the 16-byte sigma_t record otherwise (nerf queries in empty space), nothing if all are zero.
-template <bool DEFER = false>
+template <bool DEFER, bool OWN>
 __device__ __forceinline__ void splat_scatter(const Params &P, V3 p, float gs, const float ga[3], uint32_t *rec)
 {
-#ifdef DRT_COLOUR_OWN
-    splat_sigma_t<DEFER>(P, p, gs, rec);         // (its record / its scratch line: sigma_t's lattice, as everywhere)
-    splat_colour_own(P, p, ga);
-    return;
-#endif
+    if constexpr (OWN) {
+        splat_sigma_t<DEFER>(P, p, gs, rec);         // (its record / its scratch line: sigma_t's lattice, as everywhere)
+        splat_colour_own(P, p, ga);
+        return;
+    }
     if constexpr (DEFER) {
         if (dbg(P.debug_flags, kHookNoGradAtomics)) return;
         const bool colour = ga[0] != 0.0f || ga[1] != 0.0f || ga[2] != 0.0f;
@@ -1508,7 +1504,7 @@ __device__ __forceinline__ void splat_scatter(const Params &P, V3 p, float gs, c
         else if (gs != 0.0f) emit_record<0>(P, p, gs * P.scale, nullptr, rec);
     } else {
         splat_sigma_t<false>(P, p, gs, rec);
-        splat_albedo<false>(P, p, ga, rec);
+        splat_albedo<false, false>(P, p, ga, rec);
     }
 }
 
@@ -1529,12 +1525,13 @@ __device__ __forceinline__ float gather_sigma_t(const Params &P, V3 p)
     return v * P.scale;
 }
 
-// colour (albedo / emission) tangent at p: the transpose of splat_albedo / splat_colour_own (make_stencil_colour: the own lattice in drt_own.hip)
+// colour (albedo / emission) tangent at p: the transpose of splat_albedo / splat_colour_own (make_stencil_colour<OWN>)
+template <bool OWN>
 __device__ __forceinline__ void gather_colour(const Params &P, V3 p, float out[3])
 {
     out[0] = out[1] = out[2] = 0.0f;
     if (!P.g_albedo) return;
-    const Stencil s = make_stencil_colour(P, p);
+    const Stencil s = make_stencil_colour<OWN>(P, p);
     float w[8]; int idx[8];
     stencil_weights(s, w);
     stencil_indices(s, idx);

@@ -375,7 +375,7 @@ __global__ void __launch_bounds__(256) debug_eval_kernel(const Params P, int op,
         case 1: drt_sincos_2pi(a[0], o[0], o[1]); break;
         case 2: { V3 d = square_to_uniform_sphere(a[0], a[1]); o[0] = d.x; o[1] = d.y; o[2] = d.z; } break;
         case 3: o[0] = eval_sigma_t(P, v3(a[0], a[1], a[2]), P.occ); break;
-        case 4: eval_albedo(P, v3(a[0], a[1], a[2]), o); break;
+        case 4: if (P.colour_own) eval_albedo<true>(P, v3(a[0], a[1], a[2]), o); else eval_albedo<false>(P, v3(a[0], a[1], a[2]), o); break;   // (the handle's lattice)
         case 5: {
             Hit h = box_hit(P, v3(a[0], a[1], a[2]), v3(a[3], a[4], a[5]));
             o[0] = h.valid ? 1.0f : 0.0f; o[1] = h.t; o[2] = h.n.x; o[3] = h.n.y; o[4] = h.n.z;

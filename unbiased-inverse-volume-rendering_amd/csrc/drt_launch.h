@@ -41,7 +41,7 @@ hipError_t launch_nerf(const Params &P, NerfOut kind, const NerfSh &S, bool adjo
 // g_albedo, read only)
 hipError_t launch_nerf_fwd(const Params &P, NerfOut kind, const NerfSh &S, hipStream_t stream);
 // ... what a unit contributes to the two: the per-lane kernels of one cell (kind, lattice).  Members defined in drt_nerf_kernel.h; drt_kernels.hip
-// and drt_own.hip instantiate kPlain for the lattice they are compiled for, drt_nerf_aov.hip kAov, drt_nerf_dist.hip kDist; drt_nerf_sh.hip, where
+// and drt_own.hip instantiate kPlain for sigma_t's lattice and the colour grid's own, drt_nerf_aov.hip kAov, drt_nerf_dist.hip kDist; drt_nerf_sh.hip, where
 // the SH emission policy lives, specialises kSh
 template <NerfOut K, bool OWN> struct NerfLaneUnit {
     static hipError_t trace(const Params &P, const NerfSh &S, bool adjoint, bool count, hipStream_t stream);

@@ -13,10 +13,10 @@
 //
 // Kernels - the march exists once, in the shared headers, templated on an AOV flag; this unit instantiates AOV = true and the plain units
 // keep AOV = false (no copy of the per-lane march, none of the window machinery):
-//   nerf_kernel<PlainEmission, false, ., ., true>   primal, one ray per lane, with the occupancy skip                            (drt_nerf_kernel.h)
-//   nerf_fwd_kernel<PlainEmission, true>  forward mode: dual numbers, dA = dweights_sum, dD = sum dweight (t_in + t_b); one write per ray,
+//   nerf_kernel<PlainEmission<false>, false, ., ., true>   primal, one ray per lane, with the occupancy skip                            (drt_nerf_kernel.h)
+//   nerf_fwd_kernel<PlainEmission<false>, true>  forward mode: dual numbers, dA = dweights_sum, dD = sum dweight (t_in + t_b); one write per ray,
 //                                         no atomics: repeats bit for bit                                               (drt_nerf_kernel.h)
-//   nerf_kernel<PlainEmission, true, ., DEFER, true>   adjoint of EXPLICIT ray batches: one ray per lane, the RECORD route of the plain call (deferred
+//   nerf_kernel<PlainEmission<false>, true, ., DEFER, true>   adjoint of EXPLICIT ray batches: one ray per lane, the RECORD route of the plain call (deferred
 //                                         splat records, drt_deferred.hip; without record memory the atomic path into the apron scratch).
 //                                         A first version with fp32 atomics on the caller's grids took 78 ms for 2^20 rays at 256^3 where
 //                                         the plain call's record route takes 13.7 ms

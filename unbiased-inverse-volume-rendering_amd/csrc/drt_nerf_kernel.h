@@ -1,6 +1,6 @@
 // drt_nerf_kernel.h -- NeRFIntegrator.sample as one ray per lane (the primal pass; the adjoint of explicit ray batches and of the record /
-// atomic gradient paths), shared by drt_kernels.hip and drt_own.hip (the same kernel with the colour grids on their own lattice,
-// DRT_COLOUR_OWN), by drt_nerf_aov.hip (AOV = true), by drt_nerf_dist.hip (AOV = true with the DistEmission policy: a distortion output) and by drt_nerf_sh.hip (spherical-harmonic emission: its own emission policy).  Internal
+// atomic gradient paths), shared by drt_kernels.hip and drt_own.hip (the same kernel with the colour grids on their own lattice:
+// PlainEmission<true>), by drt_nerf_aov.hip (AOV = true), by drt_nerf_dist.hip (AOV = true with the DistEmission policy: a distortion output) and by drt_nerf_sh.hip (spherical-harmonic emission: its own emission policy).  Internal
 // linkage: every including unit gets its own instantiations.
 #pragma once
 #include "drt_device.h"
@@ -17,23 +17,24 @@ namespace {
 //   lookup   the emission at p                          splat    the adjoint's sigma_t and emission gradients of a query
 //   gather   the emission's tangent at p (forward mode)
 //   kScatter the splats go through splat_scatter: deferred records, or atomics staged per wave in LDS
-// This one: three channels from Params::emission (eval_rgb), gradients through splat_scatter, tangents through gather_colour.
+// This one: three channels from Params::emission (eval_rgb), gradients through splat_scatter, tangents through gather_colour - the grid on
+// sigma_t's lattice or (OWN) on its own.
 //   kDist    the march also integrates the distortion regulariser Z (below; DistEmission, instantiated with AOV = true by drt_nerf_dist.hip)
-struct PlainEmission {
+template <bool OWN> struct PlainEmission {
     static constexpr bool kScatter = true, kDist = false;
     struct Ray { __device__ __forceinline__ explicit Ray(V3) {} };
     struct Query {};
-    __device__ __forceinline__ void lookup(const Params &P, const Ray &, V3 p, Query &, float em[3]) const { eval_rgb(P, P.emission, p, em); }
+    __device__ __forceinline__ void lookup(const Params &P, const Ray &, V3 p, Query &, float em[3]) const { eval_rgb<OWN>(P, P.emission, p, em); }
     template <bool DEFER>
     __device__ __forceinline__ void splat(const Params &P, const Ray &, V3 p, const Query &, float gs, const float ge[3], uint32_t *rec) const
     {
-        splat_scatter<DEFER>(P, p, gs, ge, rec);                // colour planes = emission gradients here
+        splat_scatter<DEFER, OWN>(P, p, gs, ge, rec);           // colour planes = emission gradients here
     }
-    __device__ __forceinline__ void gather(const Params &P, const Ray &, V3 p, const Query &, float dem[3]) const { gather_colour(P, p, dem); }
+    __device__ __forceinline__ void gather(const Params &P, const Ray &, V3 p, const Query &, float dem[3]) const { gather_colour<OWN>(P, p, dem); }
 };
 
 // the plain emission with the distortion output: six floats [r, g, b, A, D, Z] per ray (drt_nerf_dist.hip)
-struct DistEmission : PlainEmission { static constexpr bool kDist = true; };
+struct DistEmission : PlainEmission<false> { static constexpr bool kDist = true; };
 
 // ---------------------------------------------------------------------------
 // NeRFIntegrator.sample (python/integrators/nerf.py:47-148): emission-absorption ray marching,
@@ -318,10 +319,10 @@ __global__ void __launch_bounds__(256) nerf_fwd_kernel(const Params P, const EAr
 // (the plain launch never checked its job and the SH one does not ask for dL: each kind keeps the refusals it came with)
 // earg: the kernels' trailing arguments, from which they build E.
 // ---------------------------------------------------------------------------
-template <NerfOut K> struct NerfLane;                            // (kSh: drt_nerf_sh.hip has its own, per K)
-template <> struct NerfLane<NerfOut::kPlain> { using E = PlainEmission; static constexpr bool kAov = false, kCount = true, kDefer = true, kChecked = false, kNeedsDL = false; };
-template <> struct NerfLane<NerfOut::kAov> { using E = PlainEmission; static constexpr bool kAov = true, kCount = false, kDefer = true, kChecked = true, kNeedsDL = true; };
-template <> struct NerfLane<NerfOut::kDist> { using E = DistEmission; static constexpr bool kAov = true, kCount = false, kDefer = true, kChecked = true, kNeedsDL = true; };
+template <NerfOut K, bool OWN> struct NerfLane;                  // (kSh: drt_nerf_sh.hip has its own, per K; kAov, kDist: sigma_t's lattice only)
+template <bool OWN> struct NerfLane<NerfOut::kPlain, OWN> { using E = PlainEmission<OWN>; static constexpr bool kAov = false, kCount = true, kDefer = true, kChecked = false, kNeedsDL = false; };
+template <> struct NerfLane<NerfOut::kAov, false> { using E = PlainEmission<false>; static constexpr bool kAov = true, kCount = false, kDefer = true, kChecked = true, kNeedsDL = true; };
+template <> struct NerfLane<NerfOut::kDist, false> { using E = DistEmission; static constexpr bool kAov = true, kCount = false, kDefer = true, kChecked = true, kNeedsDL = true; };
 
 template <class L, bool ADJ, bool DEFER, class... EArg>
 void nerf_lane_launch(const Params &P, bool count, dim3 grid, hipStream_t stream, EArg... earg)
@@ -365,14 +366,14 @@ hipError_t nerf_lane_forward(const Params &P, hipStream_t stream, EArg... earg)
 // this unit's cell of launch_nerf / launch_nerf_fwd (drt_launch.h: NerfLaneUnit).  kSh: drt_nerf_sh.hip's own definitions
 template <NerfOut K, bool OWN> hipError_t NerfLaneUnit<K, OWN>::trace(const Params &P, const NerfSh &, bool adjoint, bool count, hipStream_t stream)
 {
-    static_assert(OWN == kColourOwn && K != NerfOut::kSh, "a unit instantiates the kernels of its own lattice");
-    return nerf_lane_trace<NerfLane<K>>(P, adjoint, count, stream);
+    static_assert(K != NerfOut::kSh, "drt_nerf_sh.hip defines its own");
+    return nerf_lane_trace<NerfLane<K, OWN>>(P, adjoint, count, stream);
 }
 
 template <NerfOut K, bool OWN> hipError_t NerfLaneUnit<K, OWN>::forward(const Params &P, const NerfSh &, hipStream_t stream)
 {
-    static_assert(OWN == kColourOwn && K != NerfOut::kSh, "a unit instantiates the kernels of its own lattice");
-    return nerf_lane_forward<NerfLane<K>>(P, stream);
+    static_assert(K != NerfOut::kSh, "drt_nerf_sh.hip defines its own");
+    return nerf_lane_forward<NerfLane<K, OWN>>(P, stream);
 }
 
 }  // namespace drt

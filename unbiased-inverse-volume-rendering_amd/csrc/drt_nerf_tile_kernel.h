@@ -104,7 +104,7 @@ template <bool G4> struct PlainWindow {
     __device__ __forceinline__ void lookup(const Params &P, V3, V3 p, const Stencil &st, const uint32_t *occ, float &raw, float em[3]) const
     {
         if constexpr (G4) eval4_at(P, st, raw, em);
-        else { raw = eval_sigma_t(P, p, occ); eval_rgb(P, P.emission, p, em); }
+        else { raw = eval_sigma_t(P, p, occ); eval_rgb<false>(P, P.emission, p, em); }
     }
     __device__ __forceinline__ void splat_colour(unsigned long long *win, const int sl[8], const float w[8], V3, const float ge[3], double inv_c,
                                                  bool count, uint32_t &n_adds) const

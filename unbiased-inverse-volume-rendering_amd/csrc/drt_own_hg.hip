@@ -1,6 +1,5 @@
 // drt_own_hg.hip -- the Henyey-Greenstein instantiations of drt_own.hip: colour grids on their own lattice (drt_set_colour_resolution)
-// and the phase function `hg` (drt_set_phase), with (kHGGrad) and without the derivative with respect to g, either kind of majorant.  Compiled with DRT_COLOUR_OWN like drt_own.hip.
-#define DRT_COLOUR_OWN 1
+// and the phase function `hg` (drt_set_phase), with (kHGGrad) and without the derivative with respect to g, either kind of majorant: the OWN = true cells.
 #include "drt_coop_kernel.h"
 
 namespace drt {

@@ -1,7 +1,6 @@
 // drt_own_tab.hip -- the tabulated-phase instantiations of drt_own.hip: colour grids on their own lattice
-// (drt_set_colour_resolution) and a phase function given as a table (drt_set_phase_tab), either kind of majorant.  Compiled with
-// DRT_COLOUR_OWN like drt_own.hip.
-#define DRT_COLOUR_OWN 1
+// (drt_set_colour_resolution) and a phase function given as a table (drt_set_phase_tab), either kind of majorant: the OWN = true
+// cells.
 #include "drt_coop_kernel.h"
 
 namespace drt {

@@ -1262,7 +1262,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                         mp = ray_at(ro, rd, wt);                                // :371
                         has_scattered = true;
                         if (adj_lane) { mei_sig = eval_sigma_t(P, mp, occ); if (!resumed) SQ_COUNT(C_DT); }   // :373-375
-                        eval_albedo(P, mp, albedo);                             // :141
+                        eval_albedo<false>(P, mp, albedo);                      // :141
                         if (!resumed) SQ_COUNT(C_ALB);
                     }
                     bool detour = false;
@@ -1308,7 +1308,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                                     gs += a * albedo[k];
                                     ga[k] = a * mei_sig;
                                 }
-                                splat_scatter<true>(P, mp, gs, ga, rec); SQ_COUNT(C_SC); SQ_COUNT(C_SC_ALB);
+                                splat_scatter<true, false>(P, mp, gs, ga, rec); SQ_COUNT(C_SC); SQ_COUNT(C_SC_ALB);
                             }
                             // backpropagate_transmittance: 4 resampled points on the segment (:181-189, :584-607)
                             const float tr_int = scat ? wt : si_t;
@@ -1433,7 +1433,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                                 }
                             }
                             float alb[3];
-                            eval_albedo(P, r_o, alb);                           // :578
+                            eval_albedo<false>(P, r_o, alb);                    // :578
                             SQ_COUNT(C_ALB);
                             float gs = 0.0f, ga[3];
 #pragma unroll
@@ -1442,7 +1442,7 @@ __global__ void __launch_bounds__(DRT_SQ_THREADS) trace_sq_kernel(const Params P
                                 gs += a * alb[k];
                                 ga[k] = a * r_si_t;
                             }
-                            splat_scatter<true>(P, r_o, gs, ga, rec); SQ_COUNT(C_SC); SQ_COUNT(C_SC_ALB);
+                            splat_scatter<true, false>(P, r_o, gs, ga, rec); SQ_COUNT(C_SC); SQ_COUNT(C_SC_ALB);
                             if constexpr (QUAD) quad_resume(true); else ph = SP_IDLE;
                         } else if (!QUAD && P.use_drt && r_depth >= 0) {        // :249-259, DRTReservoir.get :756-760
                             const float d = ((r_cw[0] + r_cw[1]) + r_cw[2]) / 3.0f;
