@@ -471,6 +471,41 @@ int drt_nerf_render_backward_px(drt_handle h, const drt_nerf_config *cfg, const 
                                 const float *grad_image, uint64_t n_pixels, const float *L_in, float *grad_sigma_t,
                                 float *grad_emission);
 
+/* Opacity of camera rays for volpathsimple, and the raw transmittance walk (csrc/drt_opacity.hip; DESIGN.md "Opacity output of
+ * volpathsimple").  A_i = 1 - T_i, T_i the ratio-tracking estimate of the transmittance through the medium box along ray i
+ * (estimate_transmittance, volpathsimple.py:436-504): unbiased, one walk per ray.  The calls read the medium only - no phase function,
+ * albedo, emitter or colour lattice - and work on every handle that has one; they honour drt_set_stream and drt_set_ray_interleave,
+ * keep their own scratch (freed by drt_release_scratch) and leave the path cache, ray orders and record slots of drt_render_* alone.
+ *
+ * Rays: as drt_render_primal takes them.  rays_o == NULL: ray i is the sensor ray drt_render_primal generates for global index i (the
+ * same two draws of PCG32(tea32(seed, i)), pixel i / spp).  Set-up is the tracers' (box hit, spawn offset, box hit); a ray that misses
+ * the box or that the tracers would deactivate (a camera inside the box) has A = 0 and no derivative.  Walk i draws from
+ * PCG32(tea32(opacity_seed, i)) with opacity_seed = the first word of tea32(seed, 0x6F706163): the tracer's streams are not touched.
+ *
+ * drt_opacity_primal:   A_out[n_rays].
+ * drt_opacity_backward: ADDS dA[i] * dA_i/dsigma_t into grad_sigma_t (Z,Y,X,1).  The walk is replayed from its stream, and T = 1 - A_in[i]
+ *                       is taken from the primal's output (the L_in convention of drt_render_backward): exact for T >= 0.5, within 2^-24
+ *                       absolute below that.  The sum over rays goes through the record reduction of drt_render_backward: not bit-reproducible.
+ * drt_opacity_backward_px: the same with dA[i] = grad_image[i / spp] / spp (grad_image [n_pixels], n_rays == n_pixels * spp), bit for bit.
+ * drt_opacity_forward:  dA_out[i] = the derivative of A_i along the tangent grid t_sigma_t (Z,Y,X,1; NULL: zero), T = 1 - A_in[i] likewise.
+ *                       One write per ray, no atomics: the same bits on every call.
+ * Refused with a message before any device work: a NULL buffer, spp == 0, n_rays != n_pixels * spp, a handle without a medium (or, with
+ * rays_o == NULL, without a sensor).
+ *
+ * drt_transmittance_segments: T_out[k] = the walk's estimate over segment k, from o[k] along d[k] (as given, not normalised) over
+ * [0, tmax[k]], with the stream PCG32(tea32(seed, first_index + k)) - no set-up, no seed derivation: shadow and visibility queries
+ * between two points inside the box.  o, d: [n][3], tmax, T_out: [n]; first_index + n <= 2^32. */
+int drt_transmittance_segments(drt_handle h, const float *o, const float *d, const float *tmax, uint64_t n, uint64_t first_index,
+                               uint32_t seed, float *T_out);
+int drt_opacity_primal(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                       uint32_t seed, float *A_out);
+int drt_opacity_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                         uint32_t seed, const float *dA, const float *A_in, float *grad_sigma_t);
+int drt_opacity_backward_px(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                            uint32_t seed, const float *grad_image, uint64_t n_pixels, const float *A_in, float *grad_sigma_t);
+int drt_opacity_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                        uint32_t seed, const float *A_in, const float *t_sigma_t, float *dA_out);
+
 /* Multi-GPU gradient exchange (no handle: works on any gradient buffer of the current device, on `hip_stream`).
  * mask[b] = 1 if block b (block_floats = 64 | 128 | 256 consecutive floats, buf 16-byte aligned) holds anything but
  * zeros (NaN / inf count), else 0.  The host side (distributed.py) all-reduces the masks (MAX) and then only the

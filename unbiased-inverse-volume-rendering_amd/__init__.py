@@ -8,7 +8,7 @@ package does not need a GPU; creating an integrator handle does.
 from .scene import (ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, PHASE_TAB_KEY, SIGMA_T_KEY, ConstantEmitter, EnvmapEmitter, GridMedium, HG2Phase, HGPhase, IsotropicPhase,
                     PerspectiveSensor, Scene, TabPhase, cube_test_scene, scene_to)
 from .integrators import (ADMode, FusedNerfDrtIntegrator, IndependentSampler, NeRFIntegrator, RayBatch, VolpathSimpleIntegrator, load_dict,
-                          register_integrator, sample_tea_32, sh_basis, sh_from_rgb)
+                          opacity_seed, register_integrator, sample_tea_32, sh_basis, sh_from_rgb, transmittance)
 from .opt_config import IntegratorConfig, add_int_config, get_int_config
 from .distributed import (GradientSupport, ShardSpec, allreduce_gradients, allreduce_scalar, from_environment, gradient_support,
                           local_loss_scale, reset_allreduce_state, verify_pending)
@@ -30,7 +30,7 @@ __all__ = [
     "ALBEDO_KEY", "EMISSION_KEY", "PHASE_G_KEY", "PHASE_TAB_KEY", "SIGMA_T_KEY", "ConstantEmitter", "EnvmapEmitter", "GridMedium", "HG2Phase", "HGPhase", "IsotropicPhase",
     "PerspectiveSensor", "TabPhase",
     "Scene", "cube_test_scene", "scene_to", "ADMode", "IndependentSampler", "RayBatch",
-    "VolpathSimpleIntegrator", "NeRFIntegrator", "FusedNerfDrtIntegrator", "load_dict", "register_integrator", "sample_tea_32", "sh_basis", "sh_from_rgb", "IntegratorConfig",
+    "VolpathSimpleIntegrator", "NeRFIntegrator", "FusedNerfDrtIntegrator", "load_dict", "register_integrator", "sample_tea_32", "opacity_seed", "transmittance", "sh_basis", "sh_from_rgb", "IntegratorConfig",
     "add_int_config", "get_int_config", "ShardSpec", "allreduce_gradients", "allreduce_scalar", "GradientSupport", "gradient_support",
     "reset_allreduce_state", "verify_pending",
     "from_environment", "local_loss_scale", "alloc_grads", "render", "render_backward", "render_forward", "render_primal", "render_batch",

@@ -110,6 +110,10 @@ struct drt_handle_s {
         hipEvent_t traced = nullptr, reduced = nullptr;
         bool busy = false;             // `reduced` is pending on the side stream
     } rec[2];
+    // the opacity calls' own record slot (drt_opacity_backward*): the slots of drt_render_* stay as their last job left them.  The key is the
+    // grid the slot was carved for - shape and tile arrangement -, compared on every use: another grid carves it again
+    RecSlot opacity_rec;
+    int opacity_key[6] = {0, 0, 0, 0, 0, 0};   // rx, ry, rz, tiles along x, y, z
     hipStream_t side = nullptr;        // high-priority stream of the overlapped reductions / of the early histogram pass
     // early histogram (drt_deferred.hip: launch_deferred_early_histogram): run_backward names the plan of the launch that
     // follows; the adjoint launcher takes the histogram of the main launch's records on `side` next to the tail launch
@@ -179,11 +183,11 @@ struct DeviceGuard {
 };
 
 int check_job(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
-              uint64_t ray_offset, uint32_t spp, bool need_albedo = true)
+              uint64_t ray_offset, uint32_t spp, bool need_albedo = true, bool need_emitter = true)
 {
     if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
     if (!h->have_medium) return fail(h, DRT_ERR_NOT_CONFIGURED, "no medium: call drt_set_medium first");
-    if (!h->have_emitter) return fail(h, DRT_ERR_NOT_CONFIGURED, "no emitter: call drt_set_emitter_constant first");
+    if (need_emitter && !h->have_emitter) return fail(h, DRT_ERR_NOT_CONFIGURED, "no emitter: call drt_set_emitter_constant first");
     if (need_albedo && !h->base.albedo) return fail(h, DRT_ERR_NOT_CONFIGURED, "the medium has no albedo grid");
     if ((rays_o == nullptr) != (rays_d == nullptr))
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "rays_o and rays_d must both be given or both be NULL");
@@ -793,8 +797,9 @@ int timed_untile(drt_handle h, const drt::Params &P)
 // reduction at the end) - an experiment that measured slower than running them back to back.
 constexpr uint64_t kPipeBatches = 4;
 
+// own: the record slot of a caller that keeps its own (the opacity calls) instead of the handle's two; never overlapped
 template <class Launch>
-int run_backward(drt_handle h, drt::Params &P, uint32_t per_ray_sigma, uint32_t per_ray_colour, Launch launch)
+int run_backward(drt_handle h, drt::Params &P, uint32_t per_ray_sigma, uint32_t per_ray_colour, Launch launch, drt_handle_s::RecSlot *own = nullptr)
 {
     TimedSpan whole;
     DRT_HIP_CHECK(h, whole.begin(h, h->stream));
@@ -806,14 +811,14 @@ int run_backward(drt_handle h, drt::Params &P, uint32_t per_ray_sigma, uint32_t 
         const uint64_t bytes_per_ray = 32ull * (uint64_t) per_ray_sigma + 64ull * (uint64_t) per_ray_colour + 1024ull;   // streams in + sorted, chunk slack
         // measured on the headline workload: overlapping costs more than it hides (tracer 15.0 -> 19.8 ms
         // with the reductions alongside, step 22.1 -> 24.7 ms), so the overlap is opt-in
-        const bool overlap = dbg(h->debug_flags, kHookPipelineBatches);   // test hook: overlap the reductions with the next sub-batch's tracer
+        const bool overlap = !own && dbg(h->debug_flags, kHookPipelineBatches);   // test hook: overlap the reductions with the next sub-batch's tracer
         const uint64_t slots = overlap ? 2 : 1;
         uint64_t budget = dbg(h->debug_flags, kHookSmallRecordBudget) ? (8ull << 20) : kRecBudgetBytes;   // test hook: 8 MB -> many sub-batches
         {   // never ask for more than the device can give next to the caller's (torch's) allocations: what the slots
             // hold already plus 80 % of what is free now; smaller budgets only mean more ray sub-batches
             size_t free_b = 0, total_b = 0;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                const uint64_t have = (uint64_t) h->rec[0].mem.bytes + (uint64_t) h->rec[1].mem.bytes;
+                const uint64_t have = own ? (uint64_t) own->mem.bytes : (uint64_t) h->rec[0].mem.bytes + (uint64_t) h->rec[1].mem.bytes;
                 const uint64_t room = have + (uint64_t) ((double) free_b * 0.8);
                 if (room < budget) budget = room;
             } else (void) hipGetLastError();
@@ -827,7 +832,7 @@ int run_backward(drt_handle h, drt::Params &P, uint32_t per_ray_sigma, uint32_t 
         if (overlap) DRT_TRY(ensure_side_stream(h));
         int b = 0;
         for (uint64_t first = 0; first < n_rays; first += batch, ++b) {
-            auto &R = h->rec[overlap ? (b & 1) : 0];
+            auto &R = own ? *own : h->rec[overlap ? (b & 1) : 0];
             const uint64_t count = n_rays - first < batch ? n_rays - first : batch;
             if (R.busy) { DRT_HIP_CHECK(h, hipStreamWaitEvent(h->stream, R.reduced, 0)); R.busy = false; }
             int rc = ensure_deferred(h, R, P, count, per_ray_sigma, per_ray_colour,
@@ -843,7 +848,7 @@ int run_backward(drt_handle h, drt::Params &P, uint32_t per_ray_sigma, uint32_t 
             }
             if (rc) return rc;
             P.ray_first = first; P.n_rays = first + count;
-            h->early_plan = overlap ? nullptr : &R.plan; h->early_done = false; h->early_partition = false;
+            h->early_plan = (overlap || own) ? nullptr : &R.plan; h->early_done = false; h->early_partition = false;
             rc = launch(P);
             if (rc) { h->early_plan = nullptr; return rc; }
             if (!overlap) {
@@ -953,9 +958,9 @@ int drt_release_scratch(drt_handle h)
     if (h->side) DRT_HIP_CHECK(h, hipStreamSynchronize(h->side));
     // the buffers sized by the job: record slots, path cache, the cooperative kernels' tail pool, the expanded δL.  The queued tracer's
     // scratch (order, uempty, sq_tail, sq_cold), the loss partials and the copies of the medium stay until the handle goes.
-    for (auto &R : h->rec) {
-        R.mem.release();
-        R.rays = 0; R.bins = 0; R.busy = false;
+    for (auto *R : { &h->rec[0], &h->rec[1], &h->opacity_rec }) {
+        R->mem.release();
+        R->rays = 0; R->bins = 0; R->busy = false;
     }
     h->pcache.release();
     h->pcache_sig.valid = false; h->order_valid = false; h->order_rays = 0;
@@ -2516,3 +2521,116 @@ int drt_nerf_sh_tile_stats(drt_handle h, uint64_t *window_phases)
     *window_phases = v;
     return DRT_OK;
 }
+
+// ---- opacity of camera rays and the raw transmittance walk (drt_opacity.hip) ---------------------------------------------------------------
+namespace {
+
+// the checks and the job of an opacity call: a medium is all the handle needs (no phase function, albedo, emitter or colour lattice is read)
+int opacity_job(drt_handle h, const char *what, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                uint32_t seed, drt::Params &P)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null handle", what);
+    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false, false));
+    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    P.alt_seed = drt::host_opacity_seed(seed);                   // the walks' streams: PCG32(tea32(opacity_seed, global ray index))
+    P.g_albedo = nullptr;
+    return DRT_OK;
+}
+
+// records per ray the opacity adjoint's stream is sized for: one per collision with tr > 0.  Supergrid: the local majorants follow the medium,
+// a few collisions per ray; global majorant: majorant x box diagonal bounds the mean, as far as the host has seen the majorant.  Beyond the
+// capacity the splats are direct atomics (emit_record): a performance choice only
+uint32_t opacity_records_per_ray(drt_handle h, const drt::Params &P)
+{
+    if (P.mgrid) return 24;
+    if (h->majorant_seen < 0.0f) return 48;
+    const float dx = P.bmax[0] - P.bmin[0], dy = P.bmax[1] - P.bmin[1], dz = P.bmax[2] - P.bmin[2];
+    const float n = h->majorant_seen * std::sqrt(dx * dx + dy * dy + dz * dz);
+    return n < 8.0f ? 8u : n > 128.0f ? 128u : (uint32_t) n;
+}
+
+int opacity_backward(drt_handle h, const char *what, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                     uint32_t seed, const float *dA, const float *grad_image, const uint64_t *n_pixels, const float *A_in, float *grad_sigma_t)
+{
+    drt::Params P;
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null handle", what);
+    if (n_rays == 0) return DRT_OK;                              /* empty batch: nothing to enqueue */
+    if ((!n_pixels && !dA) || !A_in || !grad_sigma_t)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, n_pixels ? "%s: null A_in / grad_sigma_t" : "%s: null dA / A_in / grad_sigma_t", what);
+    DRT_TRY(opacity_job(h, what, rays_o, rays_d, n_rays, ray_offset, spp, seed, P));
+    if (n_pixels) DRT_TRY(check_px(h, what, n_rays, spp, grad_image, *n_pixels));
+    DeviceGuard g(h->device);
+    P.dL = n_pixels ? nullptr : dA; P.dL_pix = n_pixels ? grad_image : nullptr;
+    P.L_in = A_in; P.g_sigma = grad_sigma_t;
+    // the slot's key: carved for another grid (or another arrangement of as many tiles), it is carved again
+    const int key[6] = { P.rx, P.ry, P.rz, (P.rx + drt::kTileX - 1) / drt::kTileX, (P.ry + drt::kTileY - 1) / drt::kTileY,
+                         (P.rz + drt::kTileZ - 1) / drt::kTileZ };
+    if (std::memcmp(key, h->opacity_key, sizeof key) != 0) { h->opacity_rec.rays = 0; std::memcpy(h->opacity_key, key, sizeof key); }
+    return run_backward(h, P, opacity_records_per_ray(h, P), 0, [&](drt::Params &Q) {
+        DRT_HIP_CHECK(h, drt::launch_opacity_adjoint(Q, Q.counters != nullptr, h->stream));
+        return (int) DRT_OK;
+    }, &h->opacity_rec);
+}
+
+}  // namespace
+
+extern "C" {
+
+int drt_transmittance_segments(drt_handle h, const float *o, const float *d, const float *tmax, uint64_t n, uint64_t first_index, uint32_t seed,
+                               float *T_out)
+{
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_transmittance_segments: null handle");
+    if (!h->have_medium) return fail(h, DRT_ERR_NOT_CONFIGURED, "drt_transmittance_segments: no medium: call drt_set_medium first");
+    if (!o || !d || !tmax || !T_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_transmittance_segments: null o / d / tmax / T_out");
+    if (first_index + n > 0x100000000ull || first_index + n < first_index)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_transmittance_segments: walk index exceeds 2^32 - 1");
+    if (n == 0) return DRT_OK;
+    DeviceGuard g(h->device);
+    drt::Params P;
+    fill_job(h, P, nullptr, nullptr, 0, 0, 1, seed);
+    DRT_HIP_CHECK(h, drt::launch_transmittance_segments(P, o, d, tmax, n, first_index, seed, T_out, P.counters != nullptr, h->stream));
+    return DRT_OK;
+}
+
+int drt_opacity_primal(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                       float *A_out)
+{
+    drt::Params P;
+    if (h && n_rays == 0) return DRT_OK;                         /* empty batch: nothing to enqueue (as drt_render_primal) */
+    if (h && !A_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_opacity_primal: null A_out");
+    DRT_TRY(opacity_job(h, "drt_opacity_primal", rays_o, rays_d, n_rays, ray_offset, spp, seed, P));
+    if (n_rays == 0) return DRT_OK;
+    DeviceGuard g(h->device);
+    P.L_out = A_out;
+    DRT_HIP_CHECK(h, drt::launch_opacity_primal(P, P.counters != nullptr, h->stream));
+    return DRT_OK;
+}
+
+int drt_opacity_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                         const float *dA, const float *A_in, float *grad_sigma_t)
+{
+    return opacity_backward(h, "drt_opacity_backward", rays_o, rays_d, n_rays, ray_offset, spp, seed, dA, nullptr, nullptr, A_in, grad_sigma_t);
+}
+
+int drt_opacity_backward_px(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
+                            uint32_t seed, const float *grad_image, uint64_t n_pixels, const float *A_in, float *grad_sigma_t)
+{
+    return opacity_backward(h, "drt_opacity_backward_px", rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, &n_pixels, A_in,
+                            grad_sigma_t);
+}
+
+int drt_opacity_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
+                        const float *A_in, const float *t_sigma_t, float *dA_out)
+{
+    drt::Params P;
+    if (h && n_rays == 0) return DRT_OK;
+    if (h && (!A_in || !dA_out)) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_opacity_forward: null A_in / dA_out");
+    DRT_TRY(opacity_job(h, "drt_opacity_forward", rays_o, rays_d, n_rays, ray_offset, spp, seed, P));
+    if (n_rays == 0) return DRT_OK;
+    DeviceGuard g(h->device);
+    P.L_in = A_in; P.g_sigma = const_cast<float *>(t_sigma_t); P.L_out = dA_out;   // (the tangent grid is read only; nullptr: zero tangent)
+    DRT_HIP_CHECK(h, drt::launch_opacity_forward(P, h->stream));
+    return DRT_OK;
+}
+
+}  // extern "C"

@@ -238,6 +238,23 @@ hipError_t launch_pixel_dist_inv_pdf(const void *table, int32_t n_sensors, int32
 hipError_t launch_pixel_dist_update(float *weights, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,
                                     const int32_t *pixel_idx, const float *err, uint64_t count, hipStream_t stream);
 uint32_t host_alt_seed(uint32_t seed, bool sensor_flow);
+// Opacity of camera rays (drt_opacity.hip): A = 1 - T, T the ratio-tracking estimate of the transmittance through the box along the ray
+// (estimate_transmittance, volpathsimple.py:436-504), one walk per lane.  The job is a filled Params (fill_job): the rays, the interleave
+// and ray_first / n_rays as the tracers read them; walk i draws from PCG32(tea32(host_opacity_seed(seed), i)), which the launcher puts in
+// Params::alt_seed, the camera ray's film position from the tracer's stream tea32(seed, i).  One float per ray:
+//   primal   L_out[i] = A_i
+//   adjoint  L_in[i] = A_i of the primal, dL[i] = dA_i or dL_pix[i / spp] / spp; the splats go to stream 0 of the record streams in
+//            rec_buf (rec_buf[0] == nullptr: through the apron scratch, launch_untile behind it), out of chunks straight to g_sigma
+//   forward  L_in[i] = A_i, g_sigma = the sigma_t tangent grid (read only, may be nullptr), L_out[i] = dA_i; no atomics
+// count: the COUNT instantiations add to the counters n_rays, n_rt and (adjoint) n_rt_adj.
+uint32_t host_opacity_seed(uint32_t seed);
+hipError_t launch_opacity_primal(const Params &P, bool count, hipStream_t stream);
+hipError_t launch_opacity_adjoint(const Params &P, bool count, hipStream_t stream);
+hipError_t launch_opacity_forward(const Params &P, hipStream_t stream);
+// The raw walk: segment k from o[k] along d[k] over [0, tmax[k]] with the stream PCG32(tea32(seed, first_index + k)), T_out[k] = T.  Reads the
+// medium from P only (no rays, no set-up, no seed derivation).
+hipError_t launch_transmittance_segments(const Params &P, const float *o, const float *d, const float *tmax, uint64_t n, uint64_t first_index,
+                                         uint32_t seed, float *T_out, bool count, hipStream_t stream);
 hipError_t launch_debug_eval(const Params &P, int op, const float *in, uint64_t n, float *out, hipStream_t stream);
 
 }  // namespace drt

@@ -405,6 +405,55 @@ public:
         { py::gil_scoped_release nogil; rc = drt_film_backward_n(h_, ptr<const float>(grad_image), n_pixels, spp, channels, ptr<float>(dL)); }
         check(rc, "drt_film_backward_n");
     }
+    // opacity of camera rays / the raw transmittance walk (drt_opacity.hip): one float per ray or segment
+    void transmittance_segments(uintptr_t o, uintptr_t d, uintptr_t tmax, uint64_t n, uint64_t first_index, uint32_t seed, uintptr_t T_out)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_transmittance_segments(h_, ptr<const float>(o), ptr<const float>(d), ptr<const float>(tmax), n, first_index, seed, ptr<float>(T_out));
+        }
+        check(rc, "drt_transmittance_segments");
+    }
+    void opacity_primal(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t A_out)
+    {
+        int rc;
+        { py::gil_scoped_release nogil; rc = drt_opacity_primal(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<float>(A_out)); }
+        check(rc, "drt_opacity_primal");
+    }
+    void opacity_backward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dA, uintptr_t A_in,
+                          uintptr_t g_sigma)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_opacity_backward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dA),
+                                      ptr<const float>(A_in), ptr<float>(g_sigma));
+        }
+        check(rc, "drt_opacity_backward");
+    }
+    void opacity_backward_px(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t grad_image,
+                             uint64_t n_pixels, uintptr_t A_in, uintptr_t g_sigma)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_opacity_backward_px(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(grad_image),
+                                         n_pixels, ptr<const float>(A_in), ptr<float>(g_sigma));
+        }
+        check(rc, "drt_opacity_backward_px");
+    }
+    void opacity_forward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t A_in, uintptr_t t_sigma,
+                         uintptr_t dA_out)
+    {
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = drt_opacity_forward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(A_in),
+                                     ptr<const float>(t_sigma), ptr<float>(dA_out));
+        }
+        check(rc, "drt_opacity_forward");
+    }
     uint64_t nerf_sh_tile_phases() { uint64_t v = 0; check(drt_nerf_sh_tile_stats(h_, &v), "drt_nerf_sh_tile_stats"); return v; }
     void debug_eval(int op, uintptr_t in, uint64_t n, uintptr_t out)
     {
@@ -577,6 +626,11 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("nerf_sh_tile_phases", &Integrator::nerf_sh_tile_phases)
         .def("film_develop_n", &Integrator::film_develop_n)
         .def("film_backward_n", &Integrator::film_backward_n)
+        .def("transmittance_segments", &Integrator::transmittance_segments)
+        .def("opacity_primal", &Integrator::opacity_primal)
+        .def("opacity_backward", &Integrator::opacity_backward)
+        .def("opacity_backward_px", &Integrator::opacity_backward_px)
+        .def("opacity_forward", &Integrator::opacity_forward)
         .def("debug_eval", &Integrator::debug_eval)
         .def("set_debug_flags", &Integrator::set_debug_flags)
         .def("enable_counters", &Integrator::enable_counters)

@@ -362,11 +362,18 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
 
     Assumptions inherited from the reference: no surfaces, a single medium inside a
     convex (here: axis-aligned box) boundary with a null BSDF, one infinite emitter.
+
+    `opacity` (default False; not a reference property): True adds one output per ray and pixel behind the colour, the opacity
+    A = 1 - T of the camera ray, T the ratio-tracking estimate of the transmittance through the medium along it - unbiased, like the
+    colour.  Every radiance, δL, state, image and image-gradient tensor then has four channels [r, g, b, A]; channels 0 - 2 are the
+    bits of `opacity=False`, and A is differentiable with respect to sigma_t in both AD modes (csrc/drt_opacity.hip).  It depends on
+    sigma_t alone: the albedo and phase-function gradients come from the colour channels only.
     """
     phase_grad = True
 
     def __init__(self, props: Optional[dict] = None):
         props = dict(props or {})
+        self._opacity = bool(props.get("opacity", False))
         self.hide_emitters = bool(props.get("hide_emitters", False))
         self.use_nee = bool(props.get("use_nee", True))
         self.use_drt = bool(props.get("use_drt", True))
@@ -386,18 +393,55 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
 
     # -- reference surface ---------------------------------------------------
     def aovs(self):
-        return []
+        return ["opacity"] if self._opacity else []
+
+    @property
+    def channels(self) -> int:
+        """Floats per ray and pixel: 3, 4 with `opacity`."""
+        return 3 + len(self.aovs())
 
     def props(self) -> dict:
         return dict(hide_emitters=self.hide_emitters, use_nee=self.use_nee, use_drt=self.use_drt,
                     use_drt_subsampling=self.use_drt_subsampling, use_drt_mis=self.use_drt_mis,
-                    max_depth=self.max_depth, rr_depth=self.rr_depth)
+                    max_depth=self.max_depth, rr_depth=self.rr_depth, **({"opacity": True} if self._opacity else {}))
+
+    # -- film with the integrator's channel count (opacity: drt_film_*_n with four interleaved channels) -----
+    def develop(self, scene: Scene, L: torch.Tensor, spp: int) -> torch.Tensor:
+        if not self._opacity:
+            return super().develop(scene, L, spp)
+        h, dev = self._bind(scene)
+        _check(L, None, dev, "L")
+        if L.dim() != 2 or L.shape[1] != 4:
+            raise ValueError(f"develop: with opacity the radiance must have shape [n, 4], got {tuple(L.shape)}")
+        n_pix = L.shape[0] // spp
+        img = torch.empty((n_pix, 4), dtype=torch.float32, device=dev)
+        h.film_develop_n(L.data_ptr(), n_pix, int(spp), 4, img.data_ptr())
+        return img
+
+    def film_backward(self, scene: Scene, grad_image: torch.Tensor, spp: int) -> torch.Tensor:
+        if not self._opacity:
+            return super().film_backward(scene, grad_image, spp)
+        h, dev = self._bind(scene)
+        if grad_image.shape[-1] != 4:
+            raise ValueError(f"film_backward: with opacity the image gradient must have 4 channels, got {tuple(grad_image.shape)}")
+        grad_image = grad_image.contiguous().view(-1, 4)
+        _check(grad_image, None, dev, "grad_image")
+        n_pix = grad_image.shape[0]
+        dL = torch.empty((n_pix * spp, 4), dtype=torch.float32, device=dev)
+        h.film_backward_n(grad_image.data_ptr(), n_pix, int(spp), 4, dL.data_ptr())
+        return dL
+
+    def develop_loss(self, *args, **kwargs):
+        if self._opacity:
+            raise NotImplementedError("opacity=True: the loss-fused film compares three-channel images; use the plain develop -> loss chain")
+        return super().develop_loss(*args, **kwargs)
 
     def sample(self, mode, scene: Scene, sampler: IndependentSampler, ray: RayBatch,
                δL: Optional[torch.Tensor] = None, state_in: Optional[torch.Tensor] = None,
                active=None, grads: Optional[Dict[str, torch.Tensor]] = None,
                tangents: Optional[Dict[str, torch.Tensor]] = None, **kwargs):
-        """-> (L, valid, state_out).  Primal: L = state_out = radiance [n,3].
+        """-> (L, valid, state_out).  Primal: L = state_out = radiance [n,3] ([n,4] with `opacity`, as δL, state_in and dL then are: the
+        three-channel calls run on channels 0 - 2, the opacity calls (drt_opacity_*) on channel 3, into the same grads[sigma_t]).
         Backward: gradients are ACCUMULATED into `grads[key]` (tensors shaped like the
         parameters); returns (None, True, None).  Forward: state_in = the primal radiance of the
         same rays / seed, `tangents` = {key: tangent grid} (missing: zero); returns (dL, True, None)
@@ -419,21 +463,31 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)
+        C = self.channels
+        job = (ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value)
         if mode == ADMode.Primal:
             L = torch.empty((n, 3), dtype=torch.float32, device=dev)
             h.render_primal(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, L.data_ptr())
+            if self._opacity:
+                A = torch.empty((n, 1), dtype=torch.float32, device=dev)
+                h.opacity_primal(*job, A.data_ptr())
+                L = torch.cat([L, A], dim=1)
             return L, True, L
         if mode == ADMode.Backward:
             if δL is None or state_in is None:
                 raise ValueError("sample(Backward) needs δL and state_in")
             if grads is None:
                 raise ValueError("sample(Backward) needs `grads` (dict of accumulation tensors)")
-            _check(δL, (n, 3), dev, "δL")
-            _check(state_in, (n, 3), dev, "state_in")
+            _check(δL, (n, C), dev, "δL")
+            _check(state_in, (n, C), dev, "state_in")
             gs, ga = grads[SIGMA_T_KEY], grads[ALBEDO_KEY]
             _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
             _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
             gp, gv = self._phase_grad_ptr(scene, grads, dev), self._phase_tab_grad_ptr(scene, grads, dev)
+            if self._opacity:            # channel 3 through the opacity adjoint (sigma_t only), channels 0 - 2 as without it
+                dA, A_in = δL[:, 3].contiguous(), state_in[:, 3].contiguous()
+                δL, state_in = δL[:, :3].contiguous(), state_in[:, :3].contiguous()
+                h.opacity_backward(*job, dA.data_ptr(), A_in.data_ptr(), gs.data_ptr())
             if gv:
                 h.render_backward_phase_tab(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
                                             δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gv)
@@ -444,9 +498,14 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
                 h.render_backward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
                                   δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
             return None, True, None
-        _check(state_in, (n, 3), dev, "state_in")
+        _check(state_in, (n, C), dev, "state_in")
         dL = torch.empty((n, 3), dtype=torch.float32, device=dev)
         tg, tv = tangents.get(PHASE_G_KEY), tangents.get(PHASE_TAB_KEY)
+        dA = None
+        if self._opacity:
+            A_in, state_in = state_in[:, 3].contiguous(), state_in[:, :3].contiguous()
+            dA = torch.empty((n, 1), dtype=torch.float32, device=dev)
+            h.opacity_forward(*job, A_in.data_ptr(), _ptr(tangents[SIGMA_T_KEY]), dA.data_ptr())
         if tv is not None:
             h.render_forward_phase_tab(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
                                        _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr(), tv.data_ptr())
@@ -456,12 +515,14 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         else:
             h.render_forward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
                              _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr())
+        if dA is not None:
+            dL = torch.cat([dL, dA], dim=1)
         return dL, True, None
 
     def sample_backward_px(self, scene: Scene, sampler: IndependentSampler, ray: RayBatch, grad_image: torch.Tensor,
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
-        """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] in place of the per-ray δL
-        (drt_render_backward_px): the same gradients as with δL = film_backward(grad_image)."""
+        """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] ([.., 4] with `opacity`) in place of the per-ray δL
+        (drt_render_backward_px, drt_opacity_backward_px): the same gradients as with δL = film_backward(grad_image)."""
         if grads.get(PHASE_G_KEY) is not None:
             self._refuse_phase_grad(scene)          # (before any device work)
         if grads.get(PHASE_TAB_KEY) is not None:
@@ -469,12 +530,18 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
         n, ro, rd = self._ray_ptrs(ray, dev)
-        _check(grad_image, (n // int(ray.spp), 3), dev, "grad_image")
-        _check(state_in, (n, 3), dev, "state_in")
+        C = self.channels
+        _check(grad_image, (n // int(ray.spp), C), dev, "grad_image")
+        _check(state_in, (n, C), dev, "state_in")
         gs, ga = grads[SIGMA_T_KEY], grads[ALBEDO_KEY]
         _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
         _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
         gp, gv = self._phase_grad_ptr(scene, grads, dev), self._phase_tab_grad_ptr(scene, grads, dev)
+        if self._opacity:
+            gA, A_in = grad_image[:, 3].contiguous(), state_in[:, 3].contiguous()
+            grad_image, state_in = grad_image[:, :3].contiguous(), state_in[:, :3].contiguous()
+            h.opacity_backward_px(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, gA.data_ptr(), gA.shape[0],
+                                  A_in.data_ptr(), gs.data_ptr())
         if gv:
             h.render_backward_px_phase_tab(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
                                            grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gv)
@@ -486,7 +553,47 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
                                  grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
 
     def _native_props(self) -> dict:
-        return self.props()
+        return {k: v for k, v in self.props().items() if k != "opacity"}     # (a property of this layer: the library has separate calls)
+
+
+OPACITY_SEED_TAG = 0x6F706163      # "opac"
+
+
+def opacity_seed(seed: int) -> int:
+    """The seed of the opacity walks of a job rendered with `seed` (csrc/drt_opacity.hip: host_opacity_seed): walk i draws from
+    PCG32(tea32(opacity_seed, i)), apart from the tracer's stream PCG32(tea32(seed, i))."""
+    return sample_tea_32(int(seed) & 0xffffffff, OPACITY_SEED_TAG)[0]
+
+
+class _TransmittanceProbe(_DeviceIntegrator):
+    """The handle behind `transmittance`: a medium is all it binds to."""
+    needs_albedo = False
+
+    def __init__(self):
+        self._handles, self._bound, self._bound_emitter, self._bound_phase = {}, {}, {}, {}
+
+    def _native_props(self) -> dict:
+        return dict(max_depth=0)
+
+
+_PROBE = _TransmittanceProbe()
+
+
+def transmittance(scene: Scene, o: torch.Tensor, d: torch.Tensor, tmax: torch.Tensor, seed: int = 0, first_index: int = 0) -> torch.Tensor:
+    """Ratio-tracking estimates of the transmittance of `scene`'s medium over n segments (drt_transmittance_segments): segment k runs from
+    o[k] along d[k] (as given) over [0, tmax[k]] and draws from PCG32(tea32(seed, first_index + k)).  o, d: [n, 3], tmax: [n], float32 on
+    sigma_t's device; the points must lie inside the medium's box (the walk looks up sigma_t with clamped indices outside it).  Returns T [n];
+    unbiased, in [0, 1] for a majorant that bounds sigma_t.  No autograd: shadow and visibility queries."""
+    h, dev = _PROBE._bind(scene)
+    n = int(tmax.shape[0]) if isinstance(tmax, torch.Tensor) and tmax.dim() == 1 else -1
+    _check(tmax, (max(n, 0),), dev, "tmax")
+    _check(o, (n, 3), dev, "o")
+    _check(d, (n, 3), dev, "d")
+    T = torch.empty((n,), dtype=torch.float32, device=dev)
+    if n == 0:
+        return T
+    h.transmittance_segments(o.data_ptr(), d.data_ptr(), tmax.data_ptr(), n, int(first_index), int(seed) & 0xffffffff, T.data_ptr())
+    return T
 
 
 def _check(t: torch.Tensor, shape, dev, name: str):
@@ -786,6 +893,9 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
         if props.pop("distortion", False):
             raise NotImplementedError("nerf+volpathsimple has no distortion output (distortion=True): its fused pass returns the two "
                                       "integrators' colours only; use the 'nerf' integrator")
+        if props.pop("opacity", False):
+            raise NotImplementedError("nerf+volpathsimple has no opacity output (opacity=True): its fused pass returns the two "
+                                      "integrators' colours only; use the 'volpathsimple' integrator")
         if props.pop("aovs", False):
             raise NotImplementedError("nerf+volpathsimple has no opacity / depth outputs (aovs=True): its fused pass returns the two "
                                       "integrators' colours only; use the 'nerf' integrator")

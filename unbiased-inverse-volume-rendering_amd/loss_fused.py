@@ -89,8 +89,9 @@ def _check_integrator(integrator, what: str):
         raise NotImplementedError(f"{what}: spherical-harmonic emission (sh_degree {integrator.sh_degree}) is not supported by the "
                                   "loss-fused path; use render / render_batch with a loss on the image")
     if integrator.aovs():
-        raise NotImplementedError(f"{what}: opacity / depth outputs (aovs=True) are not supported by the loss-fused path, whose film and "
-                                  "losses are three-channel; use render / render_batch with a loss on the five-channel image")
+        raise NotImplementedError(f"{what}: outputs beyond the colour ({', '.join(integrator.aovs())}: aovs=True of 'nerf', opacity=True of "
+                                  "'volpathsimple') are not supported by the loss-fused path, whose film and losses are three-channel; "
+                                  f"use render / render_batch with a loss on the {3 + len(integrator.aovs())}-channel image")
     if not hasattr(integrator, "sample_backward_px"):
         raise ValueError(f"{what}: {type(integrator).__name__} has no loss-fused backward pass")
 
