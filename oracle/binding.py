@@ -28,11 +28,13 @@ class Medium(C.Structure):
     _fields_ = [("sigma_t", C.POINTER(C.c_float)), ("albedo", C.POINTER(C.c_float)),
                 ("res", C.c_int32 * 3), ("bbox_min", C.c_float * 3), ("bbox_max", C.c_float * 3),
                 ("scale", C.c_float), ("majorant_factor", C.c_int32), ("res_colour", C.c_int32 * 3),
-                ("phase_kind", C.c_int32), ("phase_g", C.c_float), ("phase_g2", C.c_float), ("phase_w", C.c_float)]
+                ("phase_kind", C.c_int32), ("phase_g", C.c_float), ("phase_g2", C.c_float), ("phase_w", C.c_float),
+                ("phase_tab", C.POINTER(C.c_float)), ("phase_tab_n", C.c_int32)]
 
 
 def phase_fields(phase):
-    """(phase_kind, phase_g, phase_g2, phase_w) of a scene phase function (IsotropicPhase / HGPhase / HG2Phase; None: isotropic)."""
+    """(phase_kind, phase_g, phase_g2, phase_w) of a scene phase function (IsotropicPhase / HGPhase / HG2Phase / TabPhase; None:
+    isotropic).  A TabPhase's table travels beside them (phase_table)."""
     kind = int(getattr(phase, "kind", 0)) if phase is not None else 0
     if kind == 0:
         return 0, 0.0, 0.0, 0.0
@@ -40,7 +42,16 @@ def phase_fields(phase):
         return 1, float(phase.g), 0.0, 0.0
     if kind == 2:
         return 2, float(phase.g1), float(phase.g2), float(phase.weight)
+    if kind == 3:
+        return 3, 0.0, 0.0, 0.0
     raise ValueError(f"the oracle has no phase function of kind {kind}")
+
+
+def phase_table(phase):
+    """The float32 values of a TabPhase (kind 3), None for every other phase function."""
+    if phase is None or int(getattr(phase, "kind", 0)) != 3:
+        return None
+    return np.ascontiguousarray(np.asarray(phase.values, dtype=np.float32))
 
 
 class Emitter(C.Structure):
@@ -147,6 +158,11 @@ def lib():
         L.drto_alt_seed.argtypes = [C.c_uint32, C.c_int]
         L.drto_alt_seed.restype = C.c_uint32
         L.drto_render_forward_g.argtypes = [C.POINTER(Job), fp, fp]
+        L.drto_render_forward_tab.argtypes = [C.POINTER(Job), fp, fp, fp]
+        L.drto_tab_sample.argtypes = [fp, C.c_int32, C.c_float, C.c_float, fp, fp, fp, fp, C.POINTER(C.c_int32), fp]
+        L.drto_tab_eval.argtypes = [fp, C.c_int32, fp, fp]
+        L.drto_tab_eval.restype = C.c_float
+        L.drto_tab_nodes.argtypes = [fp, C.c_int32, fp, fp]
         L.drto_render_forward.argtypes = [C.POINTER(Job), fp, fp, fp, C.c_uint32, C.c_int, dp, dp]
         L.drto_nerf_render_forward.argtypes = [C.POINTER(Job), C.POINTER(NerfConfig), fp, C.c_int, C.c_int, fp, fp, fp, C.c_int, C.c_int, dp, dp]
         L.drto_hg_sample.argtypes = [C.c_float, C.c_float, C.c_float, fp, fp, fp, fp]
@@ -231,6 +247,11 @@ class OracleScene:
         """The medium's phase function (a medium without the attribute, or None: isotropic)."""
         k, g, g2, w = phase_fields(phase)
         self.medium.phase_kind, self.medium.phase_g, self.medium.phase_g2, self.medium.phase_w = k, g, g2, w
+        self._phase_tab = phase_table(phase)                  # (kept alive next to the struct that points into it)
+        if self._phase_tab is None:
+            self.medium.phase_tab, self.medium.phase_tab_n = None, 0
+        else:
+            self.medium.phase_tab, self.medium.phase_tab_n = _fp(self._phase_tab), int(self._phase_tab.shape[0])
 
     def grid_shape(self):
         return self.sigma_t.shape[:3]
@@ -295,6 +316,21 @@ def render_forward_g(oscene: OracleScene, props: dict, spp: int, seed: int, **kw
     if rc:
         raise RuntimeError(f"drto_render_forward_g failed: {rc}")
     return dg, mag
+
+
+def render_forward_tab(oscene: OracleScene, props: dict, spp: int, seed: int, t_values, **kw):
+    """Forward-mode derivative of the radiance along the tangent `t_values` of a TabPhase medium's table values, per ray
+    (drto_render_forward_tab).  -> (dLdt [n,3] float32, mag [n,3] float32: the same sum over absolute values)"""
+    job = oscene.job(make_config(props), spp, seed, **kw)
+    t = _f32(t_values)
+    if t.shape != (int(oscene.medium.phase_tab_n),) and int(oscene.medium.phase_kind) == 3:
+        raise ValueError(f"t_values must have shape ({int(oscene.medium.phase_tab_n)},), got {t.shape}")
+    dt = np.zeros((job.n_rays, 3), dtype=np.float32)
+    mag = np.zeros((job.n_rays, 3), dtype=np.float32)
+    rc = lib().drto_render_forward_tab(C.byref(job), _fp(t), _fp(dt), _fp(mag))
+    if rc:
+        raise RuntimeError(f"drto_render_forward_tab failed: {rc}")
+    return dt, mag
 
 
 # one bit per kind of splat site of the adjoint (DRTO_TERM_* in drt_oracle.h)
@@ -607,3 +643,34 @@ def hg2_sample(g1, g2, w, u1, ux, uy, wi):
 def hg2_eval(g1, g2, w, wo, wi):
     wo, wi = np.ascontiguousarray(wo, dtype=np.float32), np.ascontiguousarray(wi, dtype=np.float32)
     return np.float32(lib().drto_hg2_eval(float(g1), float(g2), float(w), _fp(wo), _fp(wi)))
+
+
+def _tab_values(values):
+    return np.ascontiguousarray(np.asarray(values, dtype=np.float32))
+
+
+def tab_sample(values, ux, uy, wi):
+    """tab_sample of one draw over the table `values` -> (wo[3], pdf, mu, interval, fraction) in float32"""
+    v, wi = _tab_values(values), np.ascontiguousarray(wi, dtype=np.float32)
+    wo, pdf, mu, i, t = np.zeros(3, np.float32), C.c_float(0), C.c_float(0), C.c_int32(0), C.c_float(0)
+    rc = lib().drto_tab_sample(_fp(v), int(v.shape[0]), float(ux), float(uy), _fp(wi), _fp(wo), C.byref(pdf), C.byref(mu),
+                               C.byref(i), C.byref(t))
+    if rc:
+        raise RuntimeError(f"drto_tab_sample failed: {rc}")
+    return wo, np.float32(pdf.value), np.float32(mu.value), int(i.value), np.float32(t.value)
+
+
+def tab_eval(values, wo, wi):
+    v = _tab_values(values)
+    wo, wi = np.ascontiguousarray(wo, dtype=np.float32), np.ascontiguousarray(wi, dtype=np.float32)
+    return np.float32(lib().drto_tab_eval(_fp(v), int(v.shape[0]), _fp(wo), _fp(wi)))
+
+
+def tab_nodes(values):
+    """-> (p [N], F [N]) float32: the density and CDF nodes as the oracle prepares them"""
+    v = _tab_values(values)
+    p, F = np.zeros(v.shape[0], np.float32), np.zeros(v.shape[0], np.float32)
+    rc = lib().drto_tab_nodes(_fp(v), int(v.shape[0]), _fp(p), _fp(F))
+    if rc:
+        raise RuntimeError(f"drto_tab_nodes failed: {rc}")
+    return p, F

@@ -253,6 +253,121 @@ static inline v3 hg2_sample(float g1, float g2, float w, float u1, float ux, flo
     return d;
 }
 
+/* ------------------------------------------------------------------------- */
+/* Tabulated phase function (DESIGN.md "Tabulated phase function"): N values   */
+/* v_i >= 0 at the equally spaced nodes c_i = -1 + 2 i / (N - 1) of the PHYSICS */
+/* cosine c = -dot(wo, wi), linear in between, normalised by the trapezoid      */
+/* integral I.  Written from that section: the preparation in float64, rounded  */
+/* once; eval and sample in its float32 operation order.  The interval search   */
+/* is the DEFINITION - the largest i <= n - 1 with F_i <= ux, by bisection over */
+/* the nodes - and knows nothing of the guide table the device searches with.   */
+/* ------------------------------------------------------------------------- */
+#define DRT_TAB_MIN_NODES 2
+#define DRT_TAB_MAX_NODES 65536
+#define DRT_TAB_TWOPI 6.2831853071795865f
+
+/* p[N], F[N]: density and CDF nodes; tau (NULL unless forward mode in the table values): the tangent's nodes t_k / (2 pi I), and
+ * kappa = sum_k t_k m_k / I */
+typedef struct { const float *p, *F, *tau; float kappa; int n; /* intervals, N - 1 */ } tab_t;
+
+/* 0, or why the table is refused: -1 no table, -2 node count, -3 a negative or non-finite value, -4 no mass.  I_out: the integral. */
+static int tab_prepare(const float *values, int N, float *p, float *F, double *I_out)
+{
+    if (!values) return -1;
+    if (N < DRT_TAB_MIN_NODES || N > DRT_TAB_MAX_NODES) return -2;
+    for (int i = 0; i < N; ++i) if (!isfinite(values[i]) || values[i] < 0.0f) return -3;
+    const int n = N - 1;
+    const double delta = 2.0 / (double) n, two_pi = 6.283185307179586476925286766559;
+    double I = 0.0;
+    for (int i = 0; i < n; ++i) I += (0.5 * ((double) values[i] + (double) values[i + 1])) * delta;
+    if (!(I > 0.0) || !isfinite(I)) return -4;
+    double cum = 0.0;
+    for (int i = 0; i < N; ++i) {
+        if (p) p[i] = (float) ((double) values[i] / (two_pi * I));
+        if (F) F[i] = (float) (cum / I);
+        if (i < n) cum += (0.5 * ((double) values[i] + (double) values[i + 1])) * delta;
+    }
+    if (F) { F[0] = 0.0f; F[n] = 1.0f; }
+    if (I_out) *I_out = I;
+    return 0;
+}
+
+/* tangent nodes and kappa of a tangent t of the table values (m_k: delta inside, delta / 2 at the two ends; summed in index order) */
+static void tab_prepare_tangent(const float *t_values, int N, double I, float *tau, float *kappa)
+{
+    const double delta = 2.0 / (double) (N - 1), two_pi = 6.283185307179586476925286766559;
+    double k = 0.0;
+    for (int i = 0; i < N; ++i) {
+        const double m = (i == 0 || i == N - 1) ? 0.5 * delta : delta;
+        k += (double) t_values[i] * m;
+        tau[i] = (float) ((double) t_values[i] / (two_pi * I));
+    }
+    *kappa = (float) (k / I);
+}
+
+/* the interval of the physics cosine c = -mu, the fraction inside it and the density there */
+static inline float tab_eval_cos(const tab_t *T, float mu, int *i_out, float *t_out)
+{
+    const float nf = (float) T->n;
+    const float x = fminf(fmaxf((1.0f - mu) * (0.5f * nf), 0.0f), nf);
+    int i = (int) x;
+    if (i > T->n - 1) i = T->n - 1;
+    const float t = x - (float) i;
+    *i_out = i; *t_out = t;
+    return T->p[i] + t * (T->p[i + 1] - T->p[i]);
+}
+
+/* largest i <= n - 1 with F_i <= ux (F_0 = 0; equal neighbours - intervals without mass - are skipped) */
+static inline int tab_search(const tab_t *T, float ux)
+{
+    int lo = 0, hi = T->n;
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (T->F[mid] <= ux) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+/* the inverted piecewise-quadratic CDF, then hg_sample's frame and azimuth with cos_theta = c; *mu = -c */
+static inline v3 tab_sample(const tab_t *T, float ux, float uy, v3 wi, float *pdf, float *mu, int *i_out, float *t_out)
+{
+    const int i = tab_search(T, ux);
+    const float y0 = T->p[i], y1 = T->p[i + 1];
+    const float delta = 2.0f / (float) T->n;
+    const float s = DRT_TAB_TWOPI * delta;
+    const float r = ux - T->F[i];
+    float t;
+    if (y0 == y1) t = r / (s * y0);
+    else {
+        const float rp = r / s;
+        t = (y0 - sqrtf(fmaxf(0.0f, y0 * y0 + (2.0f * (y1 - y0)) * rp))) / (y0 - y1);
+    }
+    t = fminf(fmaxf(t, 0.0f), 1.0f);                     /* (fmaxf drops a NaN: 0) */
+    const float c = fminf(fmaxf(-1.0f + ((float) i + t) * delta, -1.0f), 1.0f);
+    const float sin_t = sqrtf(fmaxf(0.0f, 1.0f - c * c));
+    float sp, cp;
+    drt_sincos_2pi(uy, &sp, &cp);
+    const float lx = sin_t * cp, ly = sin_t * sp, lz = -c;
+    const float sgn = wi.z >= 0.0f ? 1.0f : -1.0f, msg = copysignf(1.0f, wi.z);
+    const float a = -1.0f / (sgn + wi.z);
+    const float b = (wi.x * wi.y) * a;
+    const v3 fs = v3_make(msg * ((wi.x * wi.x) * a) + 1.0f, msg * b, -msg * wi.x);
+    const v3 ft = v3_make(b, fmaf(wi.y, wi.y * a, sgn), -wi.y);
+    *mu = -c;
+    *pdf = y0 + t * (y1 - y0);
+    *i_out = i; *t_out = t;
+    return v3_make((fs.x * lx + ft.x * ly) + wi.x * lz, (fs.y * lx + ft.y * ly) + wi.y * lz, (fs.z * lx + ft.z * ly) + wi.z * lz);
+}
+
+/* d log p / d(table values) along the tangent, at interval i, fraction t, density p (DESIGN.md "Gradient with respect to the table
+ * values"); *abs_out: the same with both terms replaced by their absolute values */
+static inline float tab_score(const tab_t *T, int i, float t, float p, float *abs_out)
+{
+    const float l = T->tau[i] + t * (T->tau[i + 1] - T->tau[i]);
+    *abs_out = fabsf(l) / p + fabsf(T->kappa);
+    return l / p - T->kappa;
+}
+
 /* atan2 with a specified instruction sequence (Cephes atanf polynomial on min/max in [0,1]); the
  * HIP kernels evaluate the same sequence, so envmap lookups are bit-identical.  atan2(0,0) = 0. */
 static inline float drt_atan2f(float y, float x)
@@ -473,25 +588,50 @@ typedef struct {
     float *mgrid;
     float Le[3];
     envmap_t env;                /* env.pix != NULL: envmap emitter instead of the constant Le */
-    int phase_kind;              /* drto_medium::phase_kind: 0 isotropic, 1 HG (phase_g), 2 two-lobe HG (phase_g, phase_g2, phase_w) */
+    int phase_kind;              /* drto_medium::phase_kind: 0 isotropic, 1 HG (phase_g), 2 two-lobe HG (phase_g, phase_g2, phase_w), 3 tabulated (tab) */
     float phase_g, phase_g2, phase_w;
+    tab_t tab;                   /* phase_kind 3: the prepared table */
+    float *tab_store;            /* ... its nodes p[N] | F[N] | tau[N] (owned) */
+    double tab_I;                /* ... its integral */
 } scene_t;
 
-/* The medium's phase function at a scattering vertex.  Every kind consumes the same three draws (u1, then ux, uy): the isotropic
- * and single-lobe sites drop u1.  *mu: the sampled cosine (HG only; what hg_score takes). */
-static inline v3 phase_sample(const scene_t *sc, float u1, float ux, float uy, v3 wi, float *pdf, float *mu)
+/* The medium's phase function at a scattering vertex.  Every kind consumes the same three draws (u1, then ux, uy): every kind but
+ * the two-lobe one drops u1.  score / score_abs (may be NULL; forward mode in a phase parameter): the log-derivative of the sampled
+ * density along that parameter - hg_score for g, tab_score for the table values - and the magnitude rounding is judged against. */
+static inline v3 phase_sample(const scene_t *sc, float u1, float ux, float uy, v3 wi, float *pdf, float *score, float *score_abs)
 {
-    *mu = 0.0f;
-    if (sc->phase_kind == 1) return hg_sample(sc->phase_g, ux, uy, wi, pdf, mu);
-    if (sc->phase_kind == 2) return hg2_sample(sc->phase_g, sc->phase_g2, sc->phase_w, u1, ux, uy, wi, pdf);
-    *pdf = DRT_INV_FOURPI;
-    return square_to_uniform_sphere(ux, uy);
+    float mu = 0.0f, s = 0.0f, sa = 0.0f;
+    v3 d;
+    if (sc->phase_kind == 1) {
+        d = hg_sample(sc->phase_g, ux, uy, wi, pdf, &mu);
+        if (score) { s = hg_score(sc->phase_g, mu); sa = fabsf(s); }
+    }
+    else if (sc->phase_kind == 2) d = hg2_sample(sc->phase_g, sc->phase_g2, sc->phase_w, u1, ux, uy, wi, pdf);
+    else if (sc->phase_kind == 3) {
+        int i; float t;
+        d = tab_sample(&sc->tab, ux, uy, wi, pdf, &mu, &i, &t);
+        if (score && sc->tab.tau) s = tab_score(&sc->tab, i, t, *pdf, &sa);
+    }
+    else { *pdf = DRT_INV_FOURPI; d = square_to_uniform_sphere(ux, uy); }
+    if (score) { *score = s; *score_abs = sa; }
+    return d;
 }
-static inline float phase_eval(const scene_t *sc, v3 wo, v3 wi)
+/* ... and its value for the pair (wo, wi); score as above, at the evaluated direction */
+static inline float phase_eval(const scene_t *sc, v3 wo, v3 wi, float *score, float *score_abs)
 {
-    if (sc->phase_kind == 1) return hg_eval(sc->phase_g, wo, wi);
-    if (sc->phase_kind == 2) return hg2_eval(sc->phase_g, sc->phase_g2, sc->phase_w, wo, wi);
-    return DRT_INV_FOURPI;
+    float s = 0.0f, sa = 0.0f, pv = DRT_INV_FOURPI;
+    if (sc->phase_kind == 1) {
+        pv = hg_eval(sc->phase_g, wo, wi);
+        if (score) { s = hg_score(sc->phase_g, dot3(wo, wi)); sa = fabsf(s); }
+    }
+    else if (sc->phase_kind == 2) pv = hg2_eval(sc->phase_g, sc->phase_g2, sc->phase_w, wo, wi);
+    else if (sc->phase_kind == 3) {
+        int i; float t;
+        pv = tab_eval_cos(&sc->tab, dot3(wo, wi), &i, &t);
+        if (score && sc->tab.tau) s = tab_score(&sc->tab, i, t, pv, &sa);
+    }
+    if (score) { *score = s; *score_abs = sa; }
+    return pv;
 }
 
 /* Thread-local write-combining cache in front of the shared gradient grids (job->grad_cache_log2 > 0; used by
@@ -919,19 +1059,21 @@ static void sample_emitter(ctx_t *c, v3 p, pcg32 *S, const float *adj, float out
 
 /* A7: sample_emitter_for_nee (volpathsimple.py:380-403) */
 /* wi: the incoming direction at p, -d of the ray that reached the vertex (:386-388: phase_val = phase_pdf = eval(wo = emitter
- * direction, wi)).  gx (may be NULL; HG only): the log-derivative of this term with respect to g, (2 w - 1) hg_score(mu_e). */
+ * direction, wi)).  gx / gx_abs (may be NULL): the log-derivative of this term along the phase parameter of forward mode,
+ * (2 w - 1) score(emitter direction), and the same with the score replaced by its magnitude. */
 static void sample_emitter_for_nee(ctx_t *c, v3 p, v3 wi, pcg32 *S, const float beta[3], const float *dL,
-                                   float contrib[3], float *gx)
+                                   float contrib[3], float *gx, float *gx_abs)
 {
     pcg32 clone = *S;                                    /* :383 */
     float emitted[3], ds_pdf;
     v3 wd;
     sample_emitter(c, p, S, NULL, emitted, &ds_pdf, &wd);   /* :385 */
-    float pv = phase_eval(c->sc, wd, wi);                /* :386-388 */
+    float sc_e = 0.0f, sc_abs = 0.0f;
+    float pv = phase_eval(c->sc, wd, wi, gx ? &sc_e : NULL, &sc_abs);   /* :386-388 */
     float w = mis_weight(ds_pdf, pv);                    /* ds.pdf vs phase_pdf :391 */
     for (int k = 0; k < 3; ++k)
         contrib[k] = ((beta[k] * pv) * w) * emitted[k];
-    if (gx) *gx = (2.0f * w - 1.0f) * hg_score(c->sc->phase_g, dot3(wd, wi));
+    if (gx) { *gx = (2.0f * w - 1.0f) * sc_e; *gx_abs = fabsf(2.0f * w - 1.0f) * sc_abs; }
     if (dL) {                                            /* :393-401 */
         float adj[3] = { dL[0] * contrib[0], dL[1] * contrib[1], dL[2] * contrib[2] };
         float unused[3], unused_pdf;
@@ -1024,13 +1166,13 @@ static void sample_recursive(ctx_t *c, pcg32 *A, v3 p, v3 wi, int depth, float L
     if (sc->cfg.use_nee) {                               /* :621-624 */
         const float one[3] = { 1.0f, 1.0f, 1.0f };
         float nee[3];
-        sample_emitter_for_nee(c, p, wi, A, one, NULL, nee, NULL);
+        sample_emitter_for_nee(c, p, wi, A, one, NULL, nee, NULL, NULL);
         for (int k = 0; k < 3; ++k) Li[k] += nee[k];
     }
     float u1 = next_1d(A);                               /* phase.sample sample1 :632 (two-lobe: chooses the lobe) */
     float ux = next_1d(A), uy = next_1d(A);
-    float ph_pdf, ph_mu;
-    v3 wo = phase_sample(sc, u1, ux, uy, wi, &ph_pdf, &ph_mu);
+    float ph_pdf;
+    v3 wo = phase_sample(sc, u1, ux, uy, wi, &ph_pdf, NULL, NULL);
     ray_t rr; rr.o = p; rr.d = wo;
     si_t sn = box_hit(sc, p, wo);                        /* :637 */
     rr.maxt = sn.valid ? sn.t : DRT_LARGEST;             /* :639-640 */
@@ -1120,7 +1262,7 @@ static void drt_sample(ctx_t *c, pcg32 *S, int adjoint, ray_t ray, const float *
     int has_scattered = ps ? (active && !escaped) : 0;   /* :84-89 */
     float last_pdf = ps ? ps->last_pdf : 1.0f;
     gfwd_t *gf = (!ps && !adjoint) ? c->gf : NULL;       /* forward mode in g: main path of a primal pass */
-    float s_last = 0.0f;                                 /* ... score of the last sampled direction */
+    float s_last = 0.0f, s_last_abs = 0.0f;              /* ... score of the last sampled direction, and its magnitude */
 
     reservoir_t R;                                       /* :94-96 */
     memset(&R, 0, sizeof R);
@@ -1190,11 +1332,11 @@ static void drt_sample(ctx_t *c, pcg32 *S, int adjoint, ray_t ray, const float *
         active = did_scatter && (depth < cfg->max_depth);/* :200 */
 
         if (cfg->use_nee && did_scatter && active) {     /* :206-215 */
-            float nee[3], gx = 0.0f;
-            sample_emitter_for_nee(c, mei.p, v3_make(-ray.d.x, -ray.d.y, -ray.d.z), S, beta, adjoint ? dL : NULL, nee, gf ? &gx : NULL);
+            float nee[3], gx = 0.0f, gx_abs = 0.0f;
+            sample_emitter_for_nee(c, mei.p, v3_make(-ray.d.x, -ray.d.y, -ray.d.z), S, beta, adjoint ? dL : NULL, nee, gf ? &gx : NULL, &gx_abs);
             for (int k = 0; k < 3; ++k) result[k] = adjoint ? result[k] - nee[k] : result[k] + nee[k];
             if (gf) {
-                const float f = gf->S + gx, mf = gf->mS + fabsf(gx);
+                const float f = gf->S + gx, mf = gf->mS + gx_abs;
                 for (int k = 0; k < 3; ++k) { gf->tg[k] += nee[k] * f; gf->mag[k] += fabsf(nee[k]) * mf; }
             }
         }
@@ -1202,10 +1344,9 @@ static void drt_sample(ctx_t *c, pcg32 *S, int adjoint, ray_t ray, const float *
         if (did_scatter) {                               /* :221-230 */
             float u1 = next_1d(S);                       /* (two-lobe: chooses the lobe; dropped otherwise) */
             float ux = next_1d(S), uy = next_1d(S);
-            float mu;
-            ray.d = phase_sample(sc, u1, ux, uy, v3_make(-ray.d.x, -ray.d.y, -ray.d.z), &last_pdf, &mu);
+            ray.d = phase_sample(sc, u1, ux, uy, v3_make(-ray.d.x, -ray.d.y, -ray.d.z), &last_pdf, gf ? &s_last : NULL, &s_last_abs);
             ray.o = mei.p; ray.maxt = DRT_LARGEST;
-            if (gf) { s_last = hg_score(sc->phase_g, mu); gf->S += s_last; gf->mS += fabsf(s_last); }
+            if (gf) { gf->S += s_last; gf->mS += s_last_abs; }
         }
         si = box_hit(sc, ray.o, ray.d);                  /* :233-235 (did_scatter | did_escape) */
         ray.maxt = isfinite(si.t) ? si.t : DRT_LARGEST;
@@ -1236,7 +1377,8 @@ static void drt_sample(ctx_t *c, pcg32 *S, int adjoint, ray_t ray, const float *
             for (int k = 0; k < 3; ++k) result[k] += (beta[k] * w) * Le[k];
             if (gf && has_scattered) {                   /* the escape's MIS weight depends on g through last_pdf */
                 const float ex = cfg->use_nee ? (2.0f * (1.0f - w)) * s_last : 0.0f;
-                const float f = gf->S + ex, mf = gf->mS + fabsf(ex);
+                const float ex_abs = cfg->use_nee ? fabsf(2.0f * (1.0f - w)) * s_last_abs : 0.0f;
+                const float f = gf->S + ex, mf = gf->mS + ex_abs;
                 for (int k = 0; k < 3; ++k) {
                     const float e = (beta[k] * w) * Le[k];
                     gf->tg[k] += e * f; gf->mag[k] += fabsf(e) * mf;
@@ -1620,6 +1762,7 @@ int drto_nerf_render_forward(const drto_job *job, const drto_nerf_config *ncfg, 
 static int scene_init(scene_t *sc, const drto_job *job)
 {
     const drto_medium *m = job->medium;
+    sc->mgrid = NULL; sc->tab_store = NULL; memset(&sc->env, 0, sizeof(sc->env));   /* (scene_free is safe after any return) */
     if (!job->cfg || !m || !job->emitter || !m->sigma_t) return -1;
     sc->cfg = *job->cfg;
     sc->sigma_t = m->sigma_t; sc->albedo = m->albedo;
@@ -1640,9 +1783,18 @@ static int scene_init(scene_t *sc, const drto_job *job)
     sc->inv_majorant = sc->majorant != 0.0f ? 1.0f / sc->majorant : 0.0f;
     for (int k = 0; k < 3; ++k) sc->Le[k] = job->emitter->radiance[k];
     sc->mgrid = NULL; sc->gx = sc->gy = sc->gz = 0;
-    if (m->phase_kind < 0 || m->phase_kind > 2) return -5;
-    sc->phase_kind = m->phase_kind; sc->phase_g = m->phase_g; sc->phase_g2 = m->phase_g2; sc->phase_w = m->phase_w;
     memset(&sc->env, 0, sizeof(sc->env));
+    memset(&sc->tab, 0, sizeof(sc->tab)); sc->tab_store = NULL; sc->tab_I = 0.0;
+    if (m->phase_kind < 0 || m->phase_kind > 3) return -5;
+    sc->phase_kind = m->phase_kind; sc->phase_g = m->phase_g; sc->phase_g2 = m->phase_g2; sc->phase_w = m->phase_w;
+    if (m->phase_kind == 3) {                             /* refused: no table, a bad node count, a bad value, no mass */
+        const int N = m->phase_tab_n;
+        if (!m->phase_tab || N < DRT_TAB_MIN_NODES || N > DRT_TAB_MAX_NODES) return -5;
+        sc->tab_store = (float *) malloc(sizeof(float) * 3 * (size_t) N);
+        if (!sc->tab_store) return -4;
+        if (tab_prepare(m->phase_tab, N, sc->tab_store, sc->tab_store + N, &sc->tab_I)) { free(sc->tab_store); sc->tab_store = NULL; return -5; }
+        sc->tab.p = sc->tab_store; sc->tab.F = sc->tab_store + N; sc->tab.n = N - 1;
+    }
     if (job->emitter->pixels) {
         int rc = envmap_from_emitter(&sc->env, job->emitter);
         if (rc) return rc;
@@ -1682,7 +1834,12 @@ static int scene_init(scene_t *sc, const drto_job *job)
     return 0;
 }
 
-static void scene_free(scene_t *sc) { free(sc->mgrid); sc->mgrid = NULL; envmap_free(&sc->env); }
+static void scene_free(scene_t *sc)
+{
+    free(sc->mgrid); sc->mgrid = NULL;
+    free(sc->tab_store); sc->tab_store = NULL; memset(&sc->tab, 0, sizeof(sc->tab));
+    envmap_free(&sc->env);
+}
 
 /* perspective sensor (tests/test_integrators.py:46-67): sample position in
  * [0,1]^2, (0,0) = top-left; camera x axis = `left`. */
@@ -1737,11 +1894,17 @@ static void cnt_add(drto_counters *a, const drto_counters *b)
 }
 
 static int run_job(const drto_job *job, int adjoint, const float *dL, const float *L_in,
-                   float *L_out, double *g_sigma, double *g_albedo, drto_counters *cnt, float *dLdg_out, float *mag_out)
+                   float *L_out, double *g_sigma, double *g_albedo, drto_counters *cnt, float *dLdg_out, float *mag_out,
+                   const float *t_values)
 {
     scene_t sc;
     if (scene_init(&sc, job)) return -1;
     if (!sc.albedo) { scene_free(&sc); return -2; }
+    if (t_values) {                                       /* forward mode in the table values: the tangent's nodes and kappa */
+        float *tau = sc.tab_store + 2 * (size_t) (sc.tab.n + 1);
+        tab_prepare_tangent(t_values, sc.tab.n + 1, sc.tab_I, tau, &sc.tab.kappa);
+        sc.tab.tau = tau;
+    }
     uint32_t alt_seed = drto_alt_seed(job->seed, job->sensor != NULL);
     drto_counters total; memset(&total, 0, sizeof total);
 #ifdef _OPENMP
@@ -1843,7 +2006,7 @@ static int run_job(const drto_job *job, int adjoint, const float *dL, const floa
 
 int drto_render_primal(const drto_job *job, float *L_out, drto_counters *cnt)
 {
-    return run_job(job, 0, NULL, NULL, L_out, NULL, NULL, cnt, NULL, NULL);
+    return run_job(job, 0, NULL, NULL, L_out, NULL, NULL, cnt, NULL, NULL, NULL);
 }
 
 /* Forward-mode derivative of every ray's radiance with respect to the HG asymmetry g (see gfwd_t) */
@@ -1851,13 +2014,29 @@ int drto_render_forward_g(const drto_job *job, float *dLdg_out, float *mag_out)
 {
     if (!job || !job->medium || !dLdg_out) return -1;
     if (job->medium->phase_kind != 1) return -6;
-    return run_job(job, 0, NULL, NULL, NULL, NULL, NULL, NULL, dLdg_out, mag_out);
+    return run_job(job, 0, NULL, NULL, NULL, NULL, NULL, NULL, dLdg_out, mag_out, NULL);
+}
+
+/* Forward-mode derivative of every ray's radiance along a tangent of the table values of a tabulated phase function: the g pass
+ * with the table's score (gfwd_t; DESIGN.md "Gradient with respect to the table values").  The NEE log-derivative divides by the
+ * density at the emitter direction, so the table must be strictly positive. */
+int drto_render_forward_tab(const drto_job *job, const float *t_values, float *dLdt_out, float *mag_out)
+{
+    if (!job || !job->medium || !dLdt_out || !t_values) return -1;
+    const drto_medium *m = job->medium;
+    if (m->phase_kind != 3) return -6;
+    if (!m->phase_tab || m->phase_tab_n < DRT_TAB_MIN_NODES || m->phase_tab_n > DRT_TAB_MAX_NODES) return -5;
+    for (int i = 0; i < m->phase_tab_n; ++i) {
+        if (!(m->phase_tab[i] > 0.0f)) return -7;
+        if (!isfinite(t_values[i])) return -8;
+    }
+    return run_job(job, 0, NULL, NULL, NULL, NULL, NULL, NULL, dLdt_out, mag_out, t_values);
 }
 
 int drto_render_backward(const drto_job *job, const float *dL, const float *L_in,
                          double *grad_sigma_t, double *grad_albedo, drto_counters *cnt)
 {
-    return run_job(job, 1, dL, L_in, NULL, grad_sigma_t, grad_albedo, cnt, NULL, NULL);
+    return run_job(job, 1, dL, L_in, NULL, grad_sigma_t, grad_albedo, cnt, NULL, NULL, NULL);
 }
 
 /* Forward mode of sample() in the two grids, per ray and channel: three adjoint passes of the ray with dL = e_k (multiplying by 1
@@ -1970,8 +2149,8 @@ int drto_render_textbook(const drto_job *job, float *L_out)
             if (++depth >= sc.cfg.max_depth) { alive = 0; break; }
             float u1 = sc.phase_kind == 2 ? next_1d(&S) : 0.0f;
             float ux = next_1d(&S), uy = next_1d(&S);
-            float ph_pdf, ph_mu;
-            ray.d = phase_sample(&sc, u1, ux, uy, v3_make(-ray.d.x, -ray.d.y, -ray.d.z), &ph_pdf, &ph_mu);
+            float ph_pdf;
+            ray.d = phase_sample(&sc, u1, ux, uy, v3_make(-ray.d.x, -ray.d.y, -ray.d.z), &ph_pdf, NULL, NULL);
             ray.o = p;
             si_t sn = box_hit(&sc, ray.o, ray.d);
             if (!sn.valid) { alive = 0; break; }
@@ -2065,6 +2244,43 @@ void drto_hg2_sample(float g1, float g2, float w, float u1, float ux, float uy, 
 float drto_hg2_eval(float g1, float g2, float w, const float wo[3], const float wi[3])
 {
     return hg2_eval(g1, g2, w, v3_make(wo[0], wo[1], wo[2]), v3_make(wi[0], wi[1], wi[2]));
+}
+/* tabulated phase function: the table is prepared per call (status as tab_prepare's; drto_tab_eval: NaN for a refused table) */
+int drto_tab_nodes(const float *values, int32_t n, float *p_out, float *F_out)
+{
+    return tab_prepare(values, n, p_out, F_out, NULL);
+}
+int drto_tab_sample(const float *values, int32_t n, float ux, float uy, const float wi[3], float wo[3], float *pdf, float *mu,
+                    int32_t *i, float *t)
+{
+    if (!values || n < DRT_TAB_MIN_NODES || n > DRT_TAB_MAX_NODES) return values ? -2 : -1;
+    float *store = (float *) malloc(sizeof(float) * 2 * (size_t) n);
+    if (!store) return -9;
+    int rc = tab_prepare(values, n, store, store + n, NULL);
+    if (!rc) {
+        tab_t T; memset(&T, 0, sizeof T); T.p = store; T.F = store + n; T.n = n - 1;
+        int ii; float tt;
+        v3 d = tab_sample(&T, ux, uy, v3_make(wi[0], wi[1], wi[2]), pdf, mu, &ii, &tt);
+        wo[0] = d.x; wo[1] = d.y; wo[2] = d.z;
+        if (i) *i = ii;
+        if (t) *t = tt;
+    }
+    free(store);
+    return rc;
+}
+float drto_tab_eval(const float *values, int32_t n, const float wo[3], const float wi[3])
+{
+    if (!values || n < DRT_TAB_MIN_NODES || n > DRT_TAB_MAX_NODES) return NAN;
+    float *store = (float *) malloc(sizeof(float) * 2 * (size_t) n);
+    if (!store) return NAN;
+    float r = NAN;
+    if (!tab_prepare(values, n, store, store + n, NULL)) {
+        tab_t T; memset(&T, 0, sizeof T); T.p = store; T.F = store + n; T.n = n - 1;
+        int ii; float tt;
+        r = tab_eval_cos(&T, dot3(v3_make(wo[0], wo[1], wo[2]), v3_make(wi[0], wi[1], wi[2])), &ii, &tt);
+    }
+    free(store);
+    return r;
 }
 float drto_atan2f(float y, float x) { return drt_atan2f(y, x); }
 int drto_envmap_eval(const drto_emitter *em, const float d[3], float out[3])

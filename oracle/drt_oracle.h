@@ -9,7 +9,13 @@
  * that those files call (Medium::sample_interaction[_drt], GridVolume::eval,
  * PCG32 `independent` sampler, sample_tea_32, constant / envmap emitter, the
  * isotropic, `hg` and two-lobe (`blendphase` over two `hg`) phase functions,
- * AABB fast-path intersection).
+ * AABB fast-path intersection), and the tabulated phase function with its
+ * table-value derivative, which have no counterpart in those files: they are
+ * written from DESIGN.md "Tabulated phase function" and "Gradient with respect
+ * to the table values" - the float64 preparation, the float32 operation order
+ * of eval and sample, and an interval search that is the DEFINITION (the
+ * largest i <= n - 1 with F_i <= ux, by bisection; no guide table), so parity
+ * with the kernels also tests their guided search.
  *
  * PARITY UNPINNED: Mitsuba 3 / Dr.Jit are third-party dependencies that are
  * absent from /root/reference and cannot be imported in the authoring
@@ -61,10 +67,14 @@ typedef struct drto_medium {
      * 256 x 128 x 128 albedo / emission grids (python/scene_config.py:108-110).  All zero: the lattice of sigma_t (`res`). */
     int32_t res_colour[3];
     /* Phase function (the numbering of drt_set_phase / DRT_PHASE_HG2 in include/drt_hip.h): 0 isotropic, 1 Henyey-Greenstein with
-     * asymmetry phase_g, 2 two Henyey-Greenstein lobes (1 - phase_w) hg(phase_g) + phase_w hg(phase_g2).  All zero: isotropic.
-     * Every kind consumes the same draws at a phase site, so a path's sampler streams do not depend on it. */
+     * asymmetry phase_g, 2 two Henyey-Greenstein lobes (1 - phase_w) hg(phase_g) + phase_w hg(phase_g2), 3 tabulated (phase_tab below).
+     * All zero: isotropic.  Every kind consumes the same draws at a phase site, so a path's sampler streams do not depend on it. */
     int32_t phase_kind;
     float phase_g, phase_g2, phase_w;
+    /* phase_kind 3: phase_tab_n values >= 0 at the equally spaced nodes c_i = -1 + 2 i / (n - 1) of the physics cosine (+1 forward),
+     * 2 <= n <= 65536, finite, not all zero; anything else is refused (a negative status).  Ignored by the other kinds. */
+    const float *phase_tab;
+    int32_t phase_tab_n;
 } drto_medium;
 
 /* The scene's single infinite emitter (volpathsimple.py:16).
@@ -182,6 +192,15 @@ int drto_nerf_render_ext(const drto_job *job, const drto_nerf_config *ncfg, cons
  * value - the scale against which rounding is judged.  phase_kind must be 1 (-6 otherwise). */
 int drto_render_forward_g(const drto_job *job, float *dLdg_out, float *mag_out);
 
+/* Forward-mode derivative of sample(Primal) along a tangent t_values[phase_tab_n] of the table values of a tabulated phase function,
+ * per ray: dLdt_out[n][3].  drto_render_forward_g's structure - S, explicit terms, main path only - with the score
+ * s = (tau_i + t (tau_{i+1} - tau_i)) / p - kappa, tau_k = (float) (t_k / (2 pi I)), kappa = (float) (sum_k t_k m_k / I) summed in
+ * float64 in index order, m_k = delta inside and delta / 2 at the two ends; i, t, p those of the sampling at a phase site and at the
+ * escape term (present only when the main path has sampled a direction), those of the evaluation at an NEE.  mag_out (may be NULL):
+ * the same sum over absolute values, |s| taken as |lerp tau| / p + |kappa|.  Refused: phase_kind != 3 (-6), NULL t_values (-1), a
+ * table with a value <= 0 (-7: the NEE term divides by the density), a non-finite tangent (-8). */
+int drto_render_forward_tab(const drto_job *job, const float *t_values, float *dLdt_out, float *mag_out);
+
 /* Forward mode of sample(Primal) in the two grids, per ray: Jt_out[n][3] = d L[i][k] along the tangents t_sigma_t (Z,Y,X,1) and
  * t_albedo (Z,Y,X,3; the colour lattice), either may be NULL (a zero tangent).  The adjoint is linear in dL and none of its branches
  * or draws depends on dL, so Jt[i][k] is ray i's adjoint with dL = e_k (state_in = L_in, the primal's output, the adjoint's sampler
@@ -238,6 +257,13 @@ float    drto_hg_eval(float g, const float wo[3], const float wi[3]);
 float    drto_hg_score(float g, float mu);
 void     drto_hg2_sample(float g1, float g2, float w, float u1, float ux, float uy, const float wi[3], float wo[3], float *pdf);
 float    drto_hg2_eval(float g1, float g2, float w, const float wo[3], const float wi[3]);
+/* the tabulated phase function over values[n] (prepared per call; a refused table: a negative status, drto_tab_eval NaN): one draw ->
+ * direction, pdf, mu = dot(wo, wi), the sampled interval i and the fraction t inside it; eval(wo, wi); the float32 density and CDF
+ * nodes p_i, F_i (either may be NULL) */
+int      drto_tab_sample(const float *values, int32_t n, float ux, float uy, const float wi[3], float wo[3], float *pdf, float *mu,
+                         int32_t *i, float *t);
+float    drto_tab_eval(const float *values, int32_t n, const float wo[3], const float wi[3]);
+int      drto_tab_nodes(const float *values, int32_t n, float *p_out, float *F_out);
 /* envmap primitives (test hooks): radiance towards world direction d; solid-angle pdf of sampling d;
  * sample_direction(u1, u2) -> d, pdf, radiance / pdf; the importance-sampling tables
  * (marginal [h+1], conditional [h][w+1]; either may be NULL). */

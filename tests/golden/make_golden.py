@@ -11,6 +11,8 @@ HIP path with the committed file directly (without calling the oracle).
 
 phase_golden.npz: the oracle's radiance, gradients, counters (and, for the single lobe, the per-ray derivative with respect to g) of
 one 8^3 Henyey-Greenstein medium and the same medium with a two-lobe phase function; tests/test_oracle_phase.py checks the oracle against it.
+The same medium with two tabulated phase functions: radiance and counters of the table [0, 0, 0, .5, 1], and of the 33-node peaked table
+with the per-ray derivative along a fixed signed tangent of its values; tests/test_oracle_phase_tab.py checks the oracle against those.
 
     python tests/golden/make_golden.py
 """
@@ -27,7 +29,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import uivr_amd as u                      # noqa: E402  (scene dataclasses only)
 from conftest import VARIANTS, props_for  # noqa: E402
 from oracle import binding as ob          # noqa: E402
-from test_oracle_phase import PHASE_SEED, PHASE_SPP, phase_scene  # noqa: E402  (the scenes of phase_golden.npz)
+from test_oracle_phase import PHASE_SEED, PHASE_SPP, phase_scene, tab_golden_tangent  # noqa: E402  (the scenes of phase_golden.npz)
 
 RES, SPP, SEED, SCALE = 16, 8, 12345, 2.0
 
@@ -42,6 +44,13 @@ def phase_main():
         out[f"{name}/counters"] = np.array([r["counters"][k] for k in sorted(r["counters"])], dtype=np.int64)
         if name == "hg":
             out["hg/dLdg"], out["hg/mag"] = ob.render_forward_g(ob.OracleScene(scene), props_for("drt"), PHASE_SPP, PHASE_SEED, n_threads=1)
+    for name in ("tab-zeros", "tab-peaked"):
+        osc = ob.OracleScene(phase_scene(u, name))
+        out[f"{name}/L"], cnt = ob.render_primal(osc, props_for("drt"), PHASE_SPP, PHASE_SEED, n_threads=1)
+        out[f"{name}/counters"] = np.array([cnt[k] for k in sorted(cnt)], dtype=np.int64)
+        if name == "tab-peaked":
+            out[f"{name}/dLdt"], out[f"{name}/mag"] = ob.render_forward_tab(osc, props_for("drt"), PHASE_SPP, PHASE_SEED,
+                                                                            tab_golden_tangent(33), n_threads=1)
     out["counter_names"] = np.array(sorted(r["counters"]))
     path = os.path.join(HERE, "phase_golden.npz")
     np.savez_compressed(path, **out)

@@ -40,6 +40,8 @@ def _phase(uivr, p):
         with warnings.catch_warnings():                                      # (tiny |g|: the warning is the point of those cases)
             warnings.simplefilter("ignore", RuntimeWarning)
             return uivr.HGPhase(p[1])
+    if p[0] == "tab":                                                        # ("tab", values): tests/test_gpu_phase_tab_parity.py
+        return uivr.TabPhase(p[1])
     return uivr.HG2Phase(*p[1:])
 
 

@@ -1,6 +1,7 @@
-"""Tabulated phase function on the device (drt_set_phase_tab; the Phase::kTab instantiations of the tracers).  The oracle does not know
-this phase yet, so the kernels are pinned by identities and known answers - the battery of test_gpu_phase_hg.py / test_gpu_phase_hg2.py
-with a table in place of the lobes: the device primitive against a float32 restatement in the operation order of drt_device.h, a float64
+"""Tabulated phase function on the device (drt_set_phase_tab; the Phase::kTab instantiations of the tracers).  Per-ray parity with the
+oracle is tests/test_gpu_phase_tab_parity.py; here the kernels are pinned by identities and known answers that do not rest on it (they
+guard oracle and device jointly against a shared misreading; the primitive is compared with both) - the battery of
+test_gpu_phase_hg.py / test_gpu_phase_hg2.py with a table in place of the lobes: the device primitive against a float32 restatement in the operation order of drt_device.h, a float64
 single-scattering quadrature, estimators and tracers that must agree, the forward / adjoint transposition identity, finite differences,
 and the handle's state and refusals."""
 import math
@@ -75,7 +76,7 @@ def _mirror(uivr, ph):
 
 # ---- 1. the primitive ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", NAMES)
-def test_tab_primitive_matches_restatement(uivr, gpu, name):
+def test_tab_primitive_matches_restatement(uivr, oracle, gpu, name):
     ph = tables(uivr)[name]
     p32, F32 = _nodes_f32(ph)
     N = len(ph)
@@ -104,6 +105,12 @@ def test_tab_primitive_matches_restatement(uivr, gpu, name):
     assert np.all(np.abs(wo - wo_r) <= 8 * 2.0 ** -24), float(np.abs(wo - wo_r).max())
     assert np.all(np.abs(pdf - pdf_r) <= 8 * np.spacing(np.abs(pdf_r))), float(np.abs(pdf - pdf_r).max())
     assert np.all(np.abs(mu_dev - mu_r) <= 8 * 2.0 ** -24)
+    # ... and the oracle's restatement in C (oracle/drt_oracle.c, whose interval search is a bisection over the nodes): equal bits
+    ref = [oracle.tab_sample(ph.values, u[k, 0], u[k, 1], wi[k]) for k in range(n)]
+    bits = lambda a: np.ascontiguousarray(a, dtype=F).view(np.uint32)
+    assert np.array_equal(bits(wo), bits(np.stack([r[0] for r in ref])))
+    assert np.array_equal(bits(pdf), bits([r[1] for r in ref])) and np.array_equal(bits(mu_dev), bits([r[2] for r in ref]))
+    assert np.array_equal(np.array([r[3] for r in ref]), i_r)
     assert np.allclose(np.linalg.norm(wo.astype(np.float64), axis=1), 1.0, atol=4e-7)
     assert np.all(pdf > 0.0) or name in ("linear", "zeros")                  # (ux = 0 lands on a node of zero density there)
     # the pdf is the float64 table at the returned direction (the float32 direction shifts mu by ~1e-7: the table's local slope - the
@@ -121,6 +128,7 @@ def test_tab_primitive_matches_restatement(uivr, gpu, name):
     mu32 = (wo[:, 0] * wi[:, 0] + wo[:, 1] * wi[:, 1]) + wo[:, 2] * wi[:, 2]
     ev_r = _tab_eval_f32(ph, mu32)
     assert np.all(np.abs(ev21 - ev_r) <= 8 * np.spacing(np.abs(ev_r))), float(np.abs(ev21 - ev_r).max())
+    assert np.array_equal(bits(ev21), bits([oracle.tab_eval(ph.values, wo[k], wi[k]) for k in range(n)]))
     assert np.all(np.abs(ev21 - ev) <= 2e-5 * ev + slope * 1e-6)
     if name == "uniform":                                                   # kInvFourPi bit for bit, sampled and evaluated
         assert np.all(ev21 == INV_4PI) and np.all(pdf == INV_4PI) and p32[0] == INV_4PI

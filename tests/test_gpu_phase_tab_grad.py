@@ -1,9 +1,9 @@
 """The derivative with respect to the raw values of a tabulated phase function (PHASE_TAB_KEY; drt_render_backward_phase_tab /
 drt_render_backward_px_phase_tab / drt_render_forward_phase_tab, the Phase::kTabGrad kernels).  The estimator is the g-gradient's (score
-function on the main path, NEE term, escape term) with the score h_k / (2 pi I p) - m_k / I; the oracle does not know the tabulated phase,
-so there is no per-ray parity here.  The independent checks: forward / adjoint transposition over every estimator, the scale invariance
-sum_k v_k grad_k = 0, single scattering against central differences of a float64 quadrature, finite differences in a multiple-scattering
-medium, the queued tracer against CoopTracer<SUPER>, the chain rule through TabPhase.from_hg against the g-gradient, exact zeros, the
+function on the main path, NEE term, escape term) with the score h_k / (2 pi I p) - m_k / I; per-ray parity with the oracle is
+tests/test_gpu_phase_tab_parity.py.  Here, the checks that do not rest on the oracle: forward / adjoint transposition over every
+estimator, the scale invariance sum_k v_k grad_k = 0, single scattering against central differences of a float64 quadrature, finite
+differences in a multiple-scattering medium, the queued tracer against CoopTracer<SUPER>, the chain rule through TabPhase.from_hg against the g-gradient, exact zeros, the
 65536-node table, autograd / forward_ad / render_batch, a small run_optimization, and the raw C ABI.  The bars are those of
 tests/test_gpu_phase_grad.py (transposition 1e-4, tracer agreement GRAD_RTOL = 2e-4, 5 standard errors)."""
 import ctypes as C

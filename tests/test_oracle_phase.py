@@ -399,7 +399,11 @@ PHASE_SPP, PHASE_SEED = 4, 4321
 
 def phase_scene(u, name):
     """The scenes of tests/golden/phase_golden.npz (written by tests/golden/make_golden.py): an 8^3 random medium, a third of it empty, seen by
-    an 8 x 8 film, with HGPhase(0.6) (`hg`) or HG2Phase(0.8, -0.3, 0.3) (`hg2`)."""
+    an 8 x 8 film, with HGPhase(0.6) (`hg`), HG2Phase(0.8, -0.3, 0.3) (`hg2`), the table [0, 0, 0, .5, 1] (`tab-zeros`) or the 33-node
+    peaked table of the tab tests (`tab-peaked`)."""
+    from test_phase_tab_host import tables
+    phases = {"hg": lambda: u.HGPhase(0.6), "hg2": lambda: u.HG2Phase(0.8, -0.3, 0.3), "tab-zeros": lambda: tables(u)["zeros"],
+              "tab-peaked": lambda: tables(u)["peaked"]}
     rng = np.random.default_rng(808)
     st = (rng.random((8, 8, 8, 1), dtype=np.float32) * 3.0).astype(np.float32)
     st[rng.random(st.shape) < 0.33] = 0.0
@@ -407,8 +411,13 @@ def phase_scene(u, name):
     scene = u.cube_test_scene(8, 8)
     b0, b1 = scene.medium.bbox_min, scene.medium.bbox_max
     scene.medium = u.GridMedium(sigma_t=st, albedo=al, bbox_min=b0, bbox_max=b1, scale=1.5,
-                                phase=u.HGPhase(0.6) if name == "hg" else u.HG2Phase(0.8, -0.3, 0.3))
+                                phase=phases[name]())
     return scene
+
+
+def tab_golden_tangent(n):
+    """The signed tangent of the table values behind `tab-peaked/dLdt` of phase_golden.npz."""
+    return np.random.default_rng(909).standard_normal(n).astype(np.float32)
 
 
 @pytest.mark.parametrize("name", ["hg", "hg2"])
