@@ -543,6 +543,33 @@ int drt_adam_step(void *hip_stream, float *p, const float *g, float *m, float *v
 int drt_adam_step_clamped(void *hip_stream, float *p, const float *g, float *m, float *v, uint64_t n, double beta_1, double beta_2,
                           double epsilon, double lr_t, float lo, float hi);
 
+/* The clamped step restricted to a support (opt-in; csrc/drt_hull.hip, DESIGN.md "Visual-hull support"): p, g, m, v hold n_voxels x channels
+ * floats, channels last.  An entry whose voxel has support[voxel] == 0 is not touched: p, m and v keep their bits (support NULL: every voxel
+ * is inside); where a whole 16-byte group lies outside, nothing but the mask is read.  With skip_zero_grad != 0 an entry whose gradient is
+ * exactly 0 keeps p, m and v as well - `mask_updates=True` of Mitsuba 3's Adam: moments and update frozen where the gradient is zero, the
+ * step count t (inside lr_t) global.  Every other entry takes the update of drt_adam_step_clamped, bit for bit.  Any 4-byte aligned float
+ * pointers (16-byte accesses when all four are 16-byte aligned).  Refused with DRT_ERR_INVALID_ARGUMENT and a message
+ * (drt_last_error(NULL)), before any device work: a NULL or misaligned p, g, m or v, channels outside 1..32, n_voxels above 2^56, lo > hi. */
+int drt_adam_step_masked(void *hip_stream, float *p, const float *g, float *m, float *v, uint64_t n_voxels, int32_t channels,
+                         const uint8_t *support, int32_t skip_zero_grad, double beta_1, double beta_2, double epsilon, double lr_t, float lo,
+                         float hi);
+
+/* Visual hull of a box from alpha mattes (no handle, no state, on `hip_stream`; csrc/drt_hull.hip, DESIGN.md "Visual-hull support"; an
+ * extension of the reference).  `sensors`: the DEVICE table of drt_batch_sample_rays, 16 floats per sensor; `mask_sat`: DEVICE int32
+ * (n_sensors, height + 1, width + 1) summed-area tables of the binary mattes - first row and column 0, entry [s][y + 1][x + 1] the number of
+ * set pixels in rows <= y and columns <= x of sensor s; only read.  res = {X, Y, Z}; counts: DEVICE int32 (Z, Y, X, 2) = {seen, hit}.
+ * Lattice node (i, j, k), 0 <= i <= X ..., lies at bbox_min + (i / X, j / Y, k / Z) (bbox_max - bbox_min).  For sensor s and node p:
+ * v = p - origin, z = v . dir, a = (v . left) / z, b = (v . up) / z, fx = (1 - a / tan_x) 0.5 width, fy = (1 - b / tan_y) 0.5 height (float32,
+ * each operation rounded); the node is in front iff z > 1e-3 x the box's longest side.  Sensor s SEES voxel (x, y, z) iff all 8 of its nodes
+ * are in front and the pixel rectangle [floor(min fx) - margin, floor(max fx) + margin] x [floor(min fy) - margin, floor(max fy) + margin]
+ * lies inside [0, width - 1] x [0, height - 1] (conservative: a sensor that cannot see all of a voxel never carves it), and HITS it iff it
+ * sees it and the matte has a set pixel in the rectangle.  A sensor whose table entries differ from width / height sees nothing.  Integers
+ * only: equal inputs give equal bytes.  Refused with DRT_ERR_INVALID_ARGUMENT and a message (drt_last_error(NULL)), before any device work:
+ * NULL or 4-byte-misaligned pointers, n_sensors outside 1..65535, an extent outside 1..4096, height * width < 1 or >= 2^31, margin outside
+ * 0..64, a box with a non-finite or non-positive side. */
+int drt_visual_hull(void *hip_stream, const float *sensors, int32_t n_sensors, const int32_t *mask_sat, int32_t height, int32_t width,
+                    const float bbox_min[3], const float bbox_max[3], const int32_t res[3], int32_t margin, int32_t *counts);
+
 /* Priors on a dense parameter grid p (Z,Y,X,C), float32, channels last and independent of each other, N = Z Y X C entries (no handle,
  * no state; an extension of the reference, which has no regulariser).  With the forward differences dx = p[z,y,x+1,c] - p[z,y,x,c], dy, dz
  * (0 where the upper index leaves the grid):

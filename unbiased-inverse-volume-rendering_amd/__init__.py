@@ -20,6 +20,7 @@ from .optimize import (Adam, OptimizationConfig, SGD, SceneConfig, Schedule, adj
                        enforce_valid_params, get_reference_image_paths, load_reference_images, render_previews,
                        render_reference_image, run_optimization, save_params, upsample_grid)
 from .pixel_dist import PixelDistribution, PixelImportance
+from .hull import HullSupport, VisualHull, mask_tables, visual_hull
 from .priors import Prior, prior_value_and_grad_, smoothness, sparsity, total_variation
 from .resample import resample_grid, resample_grid_transpose
 from .volume_io import medium_from_vol, read_vol, write_vol
@@ -41,4 +42,5 @@ __all__ = [
     "Prior", "prior_value_and_grad_", "total_variation", "smoothness", "sparsity",
     "resample_grid", "resample_grid_transpose",
     "PixelDistribution", "PixelImportance",
+    "HullSupport", "VisualHull", "mask_tables", "visual_hull",
 ]

@@ -2153,6 +2153,49 @@ int drt_adam_step(void *hip_stream, float *p, const float *g, float *m, float *v
     return drt::launch_adam_step(p, g, m, v, n, beta_1, beta_2, epsilon, lr_t, (hipStream_t) hip_stream) == hipSuccess ? DRT_OK : DRT_ERR_HIP;
 }
 
+int drt_adam_step_masked(void *hip_stream, float *p, const float *g, float *m, float *v, uint64_t n_voxels, int32_t channels,
+                         const uint8_t *support, int32_t skip_zero_grad, double beta_1, double beta_2, double epsilon, double lr_t, float lo, float hi)
+{
+    if (!p || !g || !m || !v) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_adam_step_masked: null buffer");
+    if ((((uintptr_t) p) | ((uintptr_t) g) | ((uintptr_t) m) | ((uintptr_t) v)) & 3u)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_adam_step_masked: buffers must be 4-byte aligned");
+    if (channels < 1 || channels > drt::kPriorMaxChannels)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_adam_step_masked: %d channels (1..%d are supported)", (int) channels,
+                    drt::kPriorMaxChannels);
+    if (n_voxels > (1ull << 56))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_adam_step_masked: %llu voxels are too many", (unsigned long long) n_voxels);
+    if (!(lo <= hi)) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_adam_step_masked: lo > hi");
+    DRT_HIP_CHECK(nullptr, drt::launch_adam_step_masked(p, g, m, v, n_voxels, channels, support, skip_zero_grad != 0, beta_1, beta_2, epsilon, lr_t,
+                                                        lo, hi, (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
+int drt_visual_hull(void *hip_stream, const float *sensors, int32_t n_sensors, const int32_t *mask_sat, int32_t height, int32_t width,
+                    const float bbox_min[3], const float bbox_max[3], const int32_t res[3], int32_t margin, int32_t *counts)
+{
+    if (!sensors || !mask_sat || !counts) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_visual_hull: null buffer");
+    if (!bbox_min || !bbox_max || !res) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_visual_hull: null box or extents");
+    if ((((uintptr_t) sensors) | ((uintptr_t) mask_sat) | ((uintptr_t) counts)) & 3u)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_visual_hull: buffers must be 4-byte aligned");
+    if (n_sensors < 1 || n_sensors > drt::kHullMaxSensors)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_visual_hull: %d sensors (1..%d are supported)", (int) n_sensors, drt::kHullMaxSensors);
+    for (int a = 0; a < 3; ++a)
+        if (res[a] < 1 || res[a] > drt::kResampleMaxExtent)
+            return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_visual_hull: extents {%d,%d,%d} (every extent must lie in 1..%d)", (int) res[0],
+                        (int) res[1], (int) res[2], drt::kResampleMaxExtent);
+    if (height < 1 || width < 1 || (int64_t) height * (int64_t) width >= (1ll << 31))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_visual_hull: film %d x %d (height * width must lie in 1..2^31 - 1)", (int) height,
+                    (int) width);
+    if (margin < 0 || margin > drt::kHullMaxMargin)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_visual_hull: margin %d (0..%d are supported)", (int) margin, drt::kHullMaxMargin);
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(bbox_min[a]) || !std::isfinite(bbox_max[a]) || !std::isfinite(bbox_max[a] - bbox_min[a]) || !(bbox_max[a] > bbox_min[a]))
+            return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "drt_visual_hull: the box must have finite, positive sides");
+    DRT_HIP_CHECK(nullptr, drt::launch_visual_hull(sensors, n_sensors, mask_sat, height, width, bbox_min, bbox_max, res[0], res[1], res[2], margin,
+                                                   counts, (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
 uint64_t drt_grid_prior_scratch_bytes(int32_t nz, int32_t ny, int32_t nx, int32_t nc)
 {
     return drt::grid_prior_supported(nz, ny, nx, nc) ? drt::grid_prior_partials(nz, ny, nx, nc) * sizeof(double) : 0;

@@ -216,6 +216,16 @@ bool grid_resample_supported(int64_t sz, int64_t sy, int64_t sx, int64_t tz, int
 hipError_t launch_grid_resample(const float *src, int sz, int sy, int sx, float *dst, int tz, int ty, int tx, int nc, hipStream_t stream);
 hipError_t launch_grid_resample_transpose(const float *g_dst, int tz, int ty, int tx, float *g_src, int sz, int sy, int sx, int nc,
                                           bool accumulate, hipStream_t stream);
+// visual-hull support (drt_hull.hip): counts (Z,Y,X,2) = {seen, hit} of every voxel of the box over the sensors' mattes, given as summed-area
+// tables `sat` (n_sensors, height + 1, width + 1); extents 1..kResampleMaxExtent, margin 0..kHullMaxMargin, height * width < 2^31.  And the
+// Adam step of launch_adam_step on the entries whose voxel has support != 0 (nullptr: all) and, with skip_zero_grad, a gradient != 0; the
+// others keep their bits.  Any 4-byte aligned float pointers (16-byte accesses when all four are 16-byte aligned), channels 1..kPriorMaxChannels.
+constexpr int kHullMaxMargin = 64;
+constexpr int kHullMaxSensors = 65535;
+hipError_t launch_visual_hull(const float *sensors, int n_sensors, const int32_t *sat, int height, int width, const float bbox_min[3],
+                              const float bbox_max[3], int X, int Y, int Z, int margin, int32_t *counts, hipStream_t stream);
+hipError_t launch_adam_step_masked(float *p, const float *g, float *m, float *v, uint64_t n_voxels, int channels, const uint8_t *support,
+                                   bool skip_zero_grad, double b1, double b2, double eps, double lr_t, float lo, float hi, hipStream_t stream);
 // importance-sampled pixel batches (drt_pixel_dist.hip): a table over n < 2^31 film entries = this header, the exclusive uint64 prefix of the
 // sums of blocks of kDistBlock masses [n_blocks + 1], then the 16-bit masses padded to whole blocks (16-byte aligned)
 constexpr uint32_t kDistBlock = 256;

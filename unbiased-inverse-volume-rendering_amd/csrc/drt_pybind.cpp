@@ -512,6 +512,23 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
                                      reinterpret_cast<float *>(mm), reinterpret_cast<float *>(v), n, b1, b2, eps, lr_t, lo, hi);
         if (rc != DRT_OK) throw std::runtime_error("drt_adam_step_clamped failed (code " + std::to_string(rc) + ")");
     });
+    m.def("adam_step_masked", [](uintptr_t stream, uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uint64_t n_voxels, int32_t channels,
+                                 uintptr_t support, bool skip_zero_grad, double b1, double b2, double eps, double lr_t, float lo, float hi) {
+        const int rc = drt_adam_step_masked(reinterpret_cast<void *>(stream), reinterpret_cast<float *>(p), reinterpret_cast<const float *>(g),
+                                            reinterpret_cast<float *>(mm), reinterpret_cast<float *>(v), n_voxels, channels,
+                                            reinterpret_cast<const uint8_t *>(support), skip_zero_grad ? 1 : 0, b1, b2, eps, lr_t, lo, hi);
+        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+    });
+    // counts is (Z,Y,X,2): the extents arrive in tensor order and go to the C ABI as {X,Y,Z}
+    m.def("visual_hull", [](uintptr_t stream, uintptr_t sensors, int32_t n_sensors, uintptr_t sat, int32_t height, int32_t width,
+                            std::array<float, 3> bbox_min, std::array<float, 3> bbox_max, int32_t nz, int32_t ny, int32_t nx, int32_t margin,
+                            uintptr_t counts) {
+        const int32_t res[3] = {nx, ny, nz};
+        const int rc = drt_visual_hull(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(sensors), n_sensors,
+                                       reinterpret_cast<const int32_t *>(sat), height, width, bbox_min.data(), bbox_max.data(), res, margin,
+                                       reinterpret_cast<int32_t *>(counts));
+        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+    });
     m.def("grid_prior_scratch_bytes", [](int32_t nz, int32_t ny, int32_t nx, int32_t nc) { return drt_grid_prior_scratch_bytes(nz, ny, nx, nc); });
     m.def("grid_prior", [](uintptr_t stream, int32_t kind, uintptr_t p, uintptr_t g, uintptr_t value, uintptr_t scratch, uint64_t scratch_bytes,
                            int32_t nz, int32_t ny, int32_t nx, int32_t nc, double weight, double eps) {

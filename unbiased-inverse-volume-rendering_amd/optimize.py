@@ -27,6 +27,7 @@ from .render import render, render_primal
 from .resample import MAX_CHANNELS as RESAMPLE_MAX_CHANNELS, resample_grid
 from .scene import ALBEDO_KEY, EMISSION_KEY, PHASE_G_KEY, PHASE_TAB_KEY, SIGMA_T_KEY, GridMedium, HGPhase, Scene, TabPhase, require_hg
 from .image_io import read_image, write_image
+from .hull import HullSupport, carve, mask_tables
 from .volume_io import write_vol
 
 
@@ -72,6 +73,8 @@ class OptimizationConfig:
     # sigma_t's lattice, so that the run takes the equal-lattice kernels; the parameters stay on their own lattices.  False, or equal
     # lattices: nothing extra runs
     resample_colour: bool = False
+    # opt-in: start from the visual hull of alpha mattes and keep the optimizer inside it (hull.py); None: nothing extra runs
+    support: Optional[HullSupport] = None
 
     def __post_init__(self):
         self.upsample_at = set()
@@ -149,9 +152,10 @@ class Adam:
     bias-corrected Adam (beta1 0.9, beta2 0.999, epsilon 1e-8), per-parameter learning rates, state
     dropped when a parameter changes shape (upsampling)."""
 
-    def __init__(self, lr, params: Dict[str, torch.Tensor], beta_1=0.9, beta_2=0.999, epsilon=1e-8):
+    def __init__(self, lr, params: Dict[str, torch.Tensor], beta_1=0.9, beta_2=0.999, epsilon=1e-8, mask_updates=False):
         self.lr_default = lr
         self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
+        self.mask_updates = bool(mask_updates)      # mi.ad.Adam's: moments and update frozen where the gradient is exactly 0, t global
         self.variables: Dict[str, torch.Tensor] = dict(params)
         self.lr: Dict[str, float] = {}
         self.state: Dict[str, tuple] = {}
@@ -174,11 +178,18 @@ class Adam:
             self.lr_default = lr
 
     @torch.no_grad()
-    def step(self, grads: Dict[str, torch.Tensor], bounds: Optional[Dict[str, tuple]] = None):
+    def step(self, grads: Dict[str, torch.Tensor], bounds: Optional[Dict[str, tuple]] = None,
+             support: Optional[Dict[str, torch.Tensor]] = None):
         """`bounds` {key: (lo, hi)} (None = open): the parameter's valid range, applied to the updated value in the SAME device
         pass where the fused kernel takes the parameter (drt_adam_step_clamped) - opt.step() + enforce_valid_params
         (python/optimize.py:352-353) in one pass over p, g, m, v instead of that plus a clamp kernel per grid.  Returns the
-        keys whose bounds were applied here (the caller clamps the others)."""
+        keys whose bounds were applied here (the caller clamps the others).
+        `support` {key: bool or uint8 (Z, Y, X) tensor}: the voxels of that grid the step may touch; everywhere else p, m and v keep
+        their bits.  With `support` or `mask_updates` the grids the fused kernel takes run drt_adam_step_masked (the same update, bit
+        for bit, where it acts; its bounds apply where it acts), the rest torch ops of the same meaning; with neither, nothing differs
+        from a step without them."""
+        if support or self.mask_updates:
+            return self._step_masked(grads, bounds, support or {})
         clamped = set()
         for k, p in self.variables.items():
             g = grads.get(k)
@@ -209,15 +220,64 @@ class Adam:
             self.state[k] = (t, m, v)
         return clamped
 
+    @staticmethod
+    def _support_of(support, k, p):
+        """support[k] as a contiguous uint8 (Z, Y, X) tensor on p's device, or None."""
+        s = support.get(k)
+        if s is None:
+            return None
+        if not isinstance(s, torch.Tensor) or s.dtype not in (torch.bool, torch.uint8) or p.dim() != 4 or tuple(s.shape) != tuple(p.shape[:3]):
+            raise ValueError(f'support["{k}"] must be a bool or uint8 tensor of the grid\'s voxels {tuple(p.shape[:3])}, got '
+                             f'{getattr(s, "dtype", type(s).__name__)} {tuple(getattr(s, "shape", ()))}')
+        s = s.to(p.device).contiguous()
+        return s.view(torch.uint8) if s.dtype == torch.bool else s
+
+    def _step_masked(self, grads, bounds, support):
+        clamped = set()
+        for k, p in self.variables.items():
+            g = grads.get(k)
+            if g is None:
+                continue
+            t, m, v = self.state.get(k, (0, torch.zeros_like(p), torch.zeros_like(p)))
+            t += 1
+            lr = self.lr.get(k, self.lr_default)
+            lr_t = lr * (1 - self.beta_2 ** t) ** 0.5 / (1 - self.beta_1 ** t)
+            sup = self._support_of(support, k, p)
+            if k not in (PHASE_G_KEY, PHASE_TAB_KEY) and p.dim() == 4 and _fused_adam_ok(p, g, m, v):
+                from ._native import native
+                lo, hi = bounds[k] if bounds and k in bounds else (None, None)
+                with torch.cuda.device(p.device):
+                    native().adam_step_masked(torch.cuda.current_stream().cuda_stream, p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                              p.numel() // p.shape[3], p.shape[3], 0 if sup is None else sup.data_ptr(), self.mask_updates,
+                                              self.beta_1, self.beta_2, self.epsilon, lr_t,
+                                              float("-inf") if lo is None else float(lo), float("inf") if hi is None else float(hi))
+                if bounds and k in bounds:
+                    clamped.add(k)
+                p.view(-1)[:0].zero_()                                     # bumps the tensor version (the medium is re-bound), no work
+            else:
+                act = None if sup is None else (sup != 0).unsqueeze(-1).expand_as(p)
+                if self.mask_updates:
+                    act = (g != 0) if act is None else act & (g != 0)
+                m_new = m * self.beta_1 + (1 - self.beta_1) * g
+                v_new = v * self.beta_2 + (1 - self.beta_2) * (g * g)
+                p_new = p - lr_t * (m_new / (v_new.sqrt() + self.epsilon))
+                m.copy_(m_new if act is None else torch.where(act, m_new, m))
+                v.copy_(v_new if act is None else torch.where(act, v_new, v))
+                p.copy_(p_new if act is None else torch.where(act, p_new, p))
+            self.state[k] = (t, m, v)
+        return clamped
+
 
 class SGD(Adam):
-    """mi.ad.SGD without momentum."""
+    """mi.ad.SGD without momentum (`mask_updates` changes nothing: a zero gradient moves nothing)."""
 
     @torch.no_grad()
-    def step(self, grads, bounds=None):
+    def step(self, grads, bounds=None, support=None):
         for k, p in self.variables.items():
             if grads.get(k) is not None:
-                p.add_(grads[k], alpha=-self.lr.get(k, self.lr_default))
+                sup = self._support_of(support, k, p) if support else None
+                g = grads[k] if sup is None else torch.where((sup != 0).unsqueeze(-1), grads[k], torch.zeros_like(grads[k]))
+                p.add_(g, alpha=-self.lr.get(k, self.lr_default))
         return set()
 
 
@@ -453,7 +513,16 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     gradient on sigma_t's lattice is transposed by every rank alike), so all of them see the operator.  `params` comes back on its own
     lattices; the returned scene carries the RENDERED (resampled) colour grids, detached.  This is one extra trilinear interpolation of
     the colour grids, not what Mitsuba renders from such an asset.  With equal lattices the flag launches nothing and the run's bits are
-    those of a run without it."""
+    those of a run without it.
+
+    `opt_config.support` (a `HullSupport`; every route, sharded ones too - each rank carves the same integers; like the rest of
+    distributed.py that is unverified on multi-GPU hardware): at initialisation and after every `upsample` the visual hull of the mattes
+    (`masks`, or channel 3 of the references > `threshold`) is carved from the scene's box and the run's sensors at the current resolution
+    of every grid in `keys` (a colour grid on its own lattice on that lattice), the grid is multiplied by `inside`, and every optimizer
+    step leaves the voxels outside untouched (`Adam.step(support=...)`): sigma_t stays exactly 0 there, so the tracers' majorants vanish
+    and empty pixels are flagged as for any empty medium.  Three-channel references without `masks`, mattes of another film than the
+    sensors', and keys that are not optimised grids the integrator reads raise a ValueError at start-up.  `support.hull` is the latest
+    `VisualHull` of `keys[0]`.  None launches nothing and leaves the run's bits as they are."""
     from .distributed import ShardSpec, allreduce_scalar, local_loss_scale, verify_pending
     from . import losses as _losses
     shard = shard or ShardSpec()
@@ -465,6 +534,14 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         for p in ps:
             if not isinstance(p, Prior):
                 raise ValueError(f'priors["{k}"] must be a list of Prior, got {p!r}')
+    hull_cfg = opt_config.support
+    if hull_cfg is not None:
+        if not isinstance(hull_cfg, HullSupport):
+            raise ValueError(f"support must be a HullSupport, got {hull_cfg!r}")
+        for k in hull_cfg.keys:
+            if k in (PHASE_G_KEY, PHASE_TAB_KEY) or k not in scene_config.param_keys or not k.endswith('.data'):
+                raise ValueError(f'support: "{k}" is not an optimised grid (optimised grid keys: '
+                                 f'{[q for q in scene_config.param_keys if q not in (PHASE_G_KEY, PHASE_TAB_KEY)]})')
     importance = opt_config.pixel_importance
     pixel_loss = None
     if importance is not None:
@@ -534,6 +611,9 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     for k in priors:
         if k not in integrator.param_keys:
             raise ValueError(f'priors: the integrator "{int_config.name}" does not read "{k}": the grid receives no optimizer step')
+    for k in (hull_cfg.keys if hull_cfg is not None else ()):
+        if k not in integrator.param_keys:
+            raise ValueError(f'support: the integrator "{int_config.name}" does not read "{k}": the grid receives no optimizer step')
     if PHASE_G_KEY in keys and PHASE_TAB_KEY in keys:
         integrator._refuse_phase_tab_grad(scene0, True)                 # (a medium has one phase function)
     if PHASE_G_KEY in keys:
@@ -549,6 +629,14 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     sensors = [scene0.sensors[i] for i in scene_config.sensors]
     n_sensors = len(sensors)
     film = (sensors[0].width, sensors[0].height)
+    if hull_cfg is not None and hull_cfg.masks is not None:
+        mk = hull_cfg.masks
+        want = (n_sensors, sensors[0].height, sensors[0].width)
+        if not isinstance(mk, torch.Tensor) or mk.dim() != 3:
+            raise ValueError(f"support: masks must be a (n_sensors, H, W) tensor, got {getattr(mk, 'shape', mk)!r}")
+        if any((s.height, s.width) != want[1:] for s in sensors) or tuple(mk.shape) != want:
+            raise ValueError(f"support: the mattes' film {tuple(mk.shape)} differs from the run's sensors' (n_sensors, H, W) = {want} "
+                             f"(sensors of differing film sizes are not supported)")
     spp_grad = opt_config.spp
     spp_primal = spp_grad * opt_config.primal_spp_factor
     if output_dir:
@@ -603,6 +691,36 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     for k in integrator.param_keys:
         if k not in params and full[k] is None:
             raise ValueError(f'The integrator reads "{k}" but it is neither optimised nor present in the scene')
+
+    # --- visual-hull support (hull.py): the mattes' tables once, the hull per lattice at initialisation and after every upsample
+    support_masks: Dict[str, torch.Tensor] = {}
+    if hull_cfg is not None:
+        if hull_cfg.masks is None and ref_images.shape[-1] < 4:
+            raise ValueError(f"support: HullSupport(masks=None) takes the mattes from channel 3 of the references, which have "
+                             f"{ref_images.shape[-1]} channels; render them with an opacity output (VolpathSimpleIntegrator(opacity=True), "
+                             f"NeRFIntegrator(aovs=True)) or pass masks")
+        mattes = (ref_images[..., 3] > hull_cfg.threshold) if hull_cfg.masks is None else hull_cfg.masks
+        hull_sat = mask_tables(mattes.to(dev))
+        hull_table = sensors_to_device(sensors, dev)
+        hull_box = (np.asarray(scene0.medium.bbox_min, np.float32), np.asarray(scene0.medium.bbox_max, np.float32))
+
+    @torch.no_grad()
+    def apply_support():
+        """Carve the hull on the lattice of every supported grid (one carve per lattice), zero the grid outside it - a constant start, and
+        the trilinear upsampling, reach across the hull's surface - and keep the masks for the optimizer's steps."""
+        hulls = {}
+        for k in hull_cfg.keys:
+            z, y, x = params[k].shape[:3]
+            if (z, y, x) not in hulls:
+                hulls[(z, y, x)] = carve(hull_table, hull_sat, sensors[0].height, sensors[0].width, hull_box[0], hull_box[1], (x, y, z),
+                                         hull_cfg.margin, hull_cfg.min_views)
+            inside = hulls[(z, y, x)].inside
+            params[k].mul_(inside.unsqueeze(-1).to(torch.float32))
+            support_masks[k] = inside
+        hull_cfg.hull = hulls[tuple(params[hull_cfg.keys[0]].shape[:3])]
+
+    if hull_cfg is not None:
+        apply_support()
 
     def current_grids():
         """The grids the integrator reads: optimised ones from `params`, the others from the scene AS THEY ARE - a fixed grid next to
@@ -676,6 +794,8 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
                 new_res = tuple(2 * r for r in old.shape[:3]) + (old.shape[-1],)
                 opt[k] = upsample_grid(old, new_res)
                 params[k] = opt[k]
+            if hull_cfg is not None:
+                apply_support()                                        # (before the grids are bound: fixed colour grids resample what is left)
             grids = current_grids()
             factor = adjusted_majorant_res_factor(scene_config.majorant_resolution_factor, grids[SIGMA_T_KEY].shape)
             bound = bound_grids(grids)                                 # (fixed colour grids follow sigma_t's new lattice)
@@ -743,7 +863,7 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
                 v = prior_value_and_grad_(leaf.detach(), leaf.grad, p)
                 prior_value = v if prior_value is None else prior_value + v
         done = opt.step({k: leaves[k].grad for k in keys if k in leaves and leaves[k].requires_grad},    # :352
-                        bounds=param_bounds(scene_config, keys))
+                        bounds=param_bounds(scene_config, keys), **({'support': support_masks} if support_masks else {}))
         enforce_valid_params(scene_config, opt, skip=done or ())       # :353 (what the fused step did not clamp itself)
         # (the loss stays on the device: the reference does not read it back at all - python/optimize.py:325-358 logs nothing per iteration -, and
         #  a float() here would make the host wait for iteration i before it can enqueue iteration i + 1.  `history` is converted once, behind
