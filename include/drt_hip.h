@@ -605,6 +605,37 @@ int drt_grid_resample(void *hip_stream, const float *src, const int32_t src_res[
 int drt_grid_resample_transpose(void *hip_stream, const float *g_dst, const int32_t dst_res[3], float *g_src, const int32_t src_res[3],
                                 int32_t channels, int accumulate);
 
+/* SSIM: structural similarity (Wang et al. 2004) of two films, and what its gradient needs (no handle, no state, no host wait, everything
+ * on `hip_stream`; csrc/drt_ssim.hip, DESIGN.md "SSIM and D-SSIM"; an extension of the reference).  THE DEFINITION, referred to everywhere else:
+ *   Images   x (img) and y (ref) are (n, h, w, c) float32, contiguous, channels last.
+ *   Window   11 taps g[i] = exp(-(i - 5)^2 / (2 1.5^2)), i = 0..10, normalised to sum 1 in float64 on the host, then rounded to float32,
+ *            applied separably along w, then along h.
+ *   Moments  mu_x = g*x, mu_y = g*y, Exx = g*(x x), Eyy = g*(y y), Exy = g*(x y); the image counts as 0 outside the film (conv2d(padding=5)).
+ *   Index    S = ((2 mu_x mu_y + C1)(2 s_xy + C2)) / ((mu_x^2 + mu_y^2 + C1)(s_x^2 + s_y^2 + C2)) per entry, with s_x^2 = Exx - mu_x^2,
+ *            s_y^2 = Eyy - mu_y^2, s_xy = Exy - mu_x mu_y, C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = data_range.
+ *   Mean     ssim = mean of S: over all n h w c entries (valid == 0, "same"), or over the entries whose window lies wholly on the film,
+ *            rows 5..h-6 and columns 5..w-6 (valid != 0; needs h, w >= 11).
+ *   Arithmetic  float32 throughout, every operation rounded (-ffp-contract=off); every windowed sum is acc = acc + g[i] v in ascending i,
+ *            and Exy takes the operations of Exx and Eyy in their order: S is exactly 1.0f wherever x and y hold the same bits.
+ * drt_ssim_forward stores the mean as one double at `value` (DEVICE), S per entry in `map` (n h w c floats; NULL: not stored) and in `dmaps`
+ * (3 n h w c floats; NULL: a value-only call) three planes of n h w c floats each: the total derivatives of S with respect to mu_x (the
+ * -2 mu_x and -mu_y terms of the covariances folded in), Exx and Exy.  Per-workgroup sums go as doubles to `scratch` (DEVICE, 8-byte aligned,
+ * at least drt_ssim_scratch_bytes(n, h, w, c) bytes, contents irrelevant before and after) and ONE workgroup adds them in a fixed order:
+ * no float atomics, equal inputs give equal bits on every call.
+ * drt_ssim_backward STORES grad = u [ g*(m dmu) + 2 x g*(m dExx) + y g*(m dExy) ] (n h w c floats; the gradient of u ssim with respect to
+ * img), m = 1 / count on the entries of the mean, else 0, u = upstream[0] read on the device, the maps 0 outside the film (the window is
+ * symmetric: the transpose of the stencil is the stencil).  A gather, no atomics: bit-reproducible.  No gradient with respect to ref: S is
+ * symmetric, swap the arguments.
+ * Both are refused with DRT_ERR_INVALID_ARGUMENT and a message (drt_last_error(NULL)), before any device work, for: a NULL or misaligned
+ * pointer (floats 4, value and scratch 8 bytes), n, h or w below 1, n h w c >= 2^31, c outside 1..8, valid with h < 11 or w < 11, a
+ * data_range that is not a positive finite number, a scratch that is missing or too small, grad overlapping an input.
+ * drt_ssim_scratch_bytes returns 0 for extents the calls refuse. */
+uint64_t drt_ssim_scratch_bytes(int32_t n, int32_t h, int32_t w, int32_t c);
+int drt_ssim_forward(void *hip_stream, const float *img, const float *ref, int32_t n, int32_t h, int32_t w, int32_t c, double data_range,
+                     int32_t valid, double *value, float *map, float *dmaps, void *scratch, uint64_t scratch_bytes);
+int drt_ssim_backward(void *hip_stream, const float *img, const float *ref, const float *dmaps, const float *upstream, int32_t n, int32_t h,
+                      int32_t w, int32_t c, int32_t valid, float *grad);
+
 /* Event counting (off by default; enabling selects a counting build of the kernels). */
 int drt_enable_counters(drt_handle h, int enable);
 int drt_reset_counters(drt_handle h);

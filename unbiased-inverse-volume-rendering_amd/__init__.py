@@ -17,12 +17,13 @@ from .batched import gather_ref_values, render_batch, sample_batch, sensors_to_d
 from . import losses
 from .loss_fused import render_batch_loss, render_loss
 from .optimize import (Adam, OptimizationConfig, SGD, SceneConfig, Schedule, adjusted_majorant_res_factor,
-                       enforce_valid_params, get_reference_image_paths, load_reference_images, render_previews,
+                       enforce_valid_params, evaluate_views, get_reference_image_paths, load_reference_images, render_previews,
                        render_reference_image, run_optimization, save_params, upsample_grid)
 from .pixel_dist import PixelDistribution, PixelImportance
 from .hull import HullSupport, VisualHull, mask_tables, visual_hull
 from .priors import Prior, prior_value_and_grad_, smoothness, sparsity, total_variation
 from .resample import resample_grid, resample_grid_transpose
+from .ssim import dssim, ssim, ssim_map
 from .volume_io import medium_from_vol, read_vol, write_vol
 from .image_io import read_image, write_image
 from .fd import fd_gradients
@@ -43,4 +44,5 @@ __all__ = [
     "resample_grid", "resample_grid_transpose",
     "PixelDistribution", "PixelImportance",
     "HullSupport", "VisualHull", "mask_tables", "visual_hull",
+    "ssim", "dssim", "ssim_map", "evaluate_views",
 ]

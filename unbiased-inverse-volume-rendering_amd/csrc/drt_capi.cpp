@@ -2229,6 +2229,74 @@ int drt_grid_prior(void *hip_stream, int32_t kind, const float *p, float *g, dou
     return DRT_OK;
 }
 
+uint64_t drt_ssim_scratch_bytes(int32_t n, int32_t h, int32_t w, int32_t c)
+{
+    return drt::ssim_partials(n, h, w, c) * sizeof(double);
+}
+
+// the checks that drt_ssim_forward and drt_ssim_backward share
+static int ssim_check(const char *who, const float *img, const float *ref, int32_t n, int32_t h, int32_t w, int32_t c, int32_t valid)
+{
+    if (!img || !ref) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null image", who);
+    if ((((uintptr_t) img) | ((uintptr_t) ref)) & 3u) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: images must be 4-byte aligned", who);
+    if (n < 1 || h < 1 || w < 1)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: empty film %d x %d x %d (n, h and w must be at least 1)", who, (int) n, (int) h, (int) w);
+    if (c < 1 || c > drt::kSsimMaxChannels)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: %d channels (1..%d are supported)", who, (int) c, drt::kSsimMaxChannels);
+    if (!drt::ssim_supported(n, h, w, c))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: films %d x %d x %d x %d are too large (n h w c must stay below 2^31)", who, (int) n,
+                    (int) h, (int) w, (int) c);
+    if (valid && (h < 11 || w < 11))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: valid padding needs h and w of at least 11 (the window), got %d x %d", who, (int) h,
+                    (int) w);
+    return DRT_OK;
+}
+
+int drt_ssim_forward(void *hip_stream, const float *img, const float *ref, int32_t n, int32_t h, int32_t w, int32_t c, double data_range,
+                     int32_t valid, double *value, float *map, float *dmaps, void *scratch, uint64_t scratch_bytes)
+{
+    const char *who = "drt_ssim_forward";
+    const int rc = ssim_check(who, img, ref, n, h, w, c, valid);
+    if (rc != DRT_OK) return rc;
+    if (!value || (((uintptr_t) value) & 7u)) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: value must be an 8-byte aligned pointer", who);
+    if ((((uintptr_t) map) | ((uintptr_t) dmaps)) & 3u) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: maps must be 4-byte aligned", who);
+    if (!(std::isfinite(data_range) && data_range > 0.0 && std::isfinite((float) ((0.03 * data_range) * (0.03 * data_range))) &&
+          (float) ((0.01 * data_range) * (0.01 * data_range)) > 0.0f))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: data_range must be a positive finite number (with C1, C2 positive finite floats), got %g",
+                    who, data_range);
+    const uint64_t need = drt_ssim_scratch_bytes(n, h, w, c);
+    if (!scratch || (((uintptr_t) scratch) & 7u) || scratch_bytes < need)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: scratch must be an 8-byte aligned buffer of at least %llu bytes (got %llu)", who,
+                    (unsigned long long) need, (unsigned long long) scratch_bytes);
+    const uint64_t bytes = (uint64_t) n * (uint64_t) h * (uint64_t) w * (uint64_t) c * sizeof(float);
+    const struct { const void *p; uint64_t size; } outs[] = { { value, sizeof(double) }, { map, bytes }, { dmaps, 3 * bytes }, { scratch, need } };
+    for (const auto &o : outs)
+        for (const float *in : { img, ref })
+            if (o.p && (uintptr_t) o.p < (uintptr_t) in + bytes && (uintptr_t) in < (uintptr_t) o.p + o.size)
+                return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: an output overlaps an input image", who);
+    DRT_HIP_CHECK(nullptr, drt::launch_ssim_forward(img, ref, n, h, w, c, data_range, valid != 0, value, map, dmaps, (double *) scratch,
+                                                    (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
+int drt_ssim_backward(void *hip_stream, const float *img, const float *ref, const float *dmaps, const float *upstream, int32_t n, int32_t h,
+                      int32_t w, int32_t c, int32_t valid, float *grad)
+{
+    const char *who = "drt_ssim_backward";
+    const int rc = ssim_check(who, img, ref, n, h, w, c, valid);
+    if (rc != DRT_OK) return rc;
+    if (!dmaps || !upstream || !grad) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null derivative maps, upstream or grad", who);
+    if ((((uintptr_t) dmaps) | ((uintptr_t) upstream) | ((uintptr_t) grad)) & 3u)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: derivative maps, upstream and grad must be 4-byte aligned", who);
+    const uint64_t bytes = (uint64_t) n * (uint64_t) h * (uint64_t) w * (uint64_t) c * sizeof(float);
+    const struct { const void *p; uint64_t size; } ins[] = { { img, bytes }, { ref, bytes }, { dmaps, 3 * bytes }, { upstream, sizeof(float) } };
+    for (const auto &i : ins)
+        if ((uintptr_t) grad < (uintptr_t) i.p + i.size && (uintptr_t) i.p < (uintptr_t) grad + bytes)
+            return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: grad overlaps an input", who);
+    DRT_HIP_CHECK(nullptr, drt::launch_ssim_backward(img, ref, dmaps, upstream, n, h, w, c, valid != 0, grad, (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
 // the checks that drt_grid_resample and its transpose share; `a` is the grid on the lattice a_res, `b` the one on b_res
 static int grid_resample_check(const char *who, const float *a, const int32_t a_res[3], const float *b, const int32_t b_res[3], int32_t channels)
 {

@@ -226,6 +226,19 @@ hipError_t launch_visual_hull(const float *sensors, int n_sensors, const int32_t
                               const float bbox_max[3], int X, int Y, int Z, int margin, int32_t *counts, hipStream_t stream);
 hipError_t launch_adam_step_masked(float *p, const float *g, float *m, float *v, uint64_t n_voxels, int channels, const uint8_t *support,
                                    bool skip_zero_grad, double b1, double b2, double eps, double lr_t, float lo, float hi, hipStream_t stream);
+// structural similarity (drt_ssim.hip; the definition: include/drt_hip.h "SSIM") of two films (N,H,W,C), C <= kSsimMaxChannels, N H W C < 2^31.
+// Forward: one double per workgroup to `partials` (ssim_partials of them), summed by a second, single-workgroup launch into `value`; `map`
+// (S per entry) and `dmaps` (three planes of N H W C floats: dS/dmu_x, dS/dExx, dS/dExy) may be nullptr.  Backward: grad = upstream[0] / count
+// times the transposed stencil of the masked derivative maps, stored (not added).  ssim_window: the 11 taps; ssim_count: the entries of the mean.
+constexpr int kSsimMaxChannels = 8;
+void ssim_window(float g[11]);
+double ssim_count(int n, int h, int w, int c, bool valid);
+bool ssim_supported(int64_t n, int64_t h, int64_t w, int64_t c);
+uint64_t ssim_partials(int n, int h, int w, int c);                  // 0: not a film the kernels take
+hipError_t launch_ssim_forward(const float *x, const float *y, int n, int h, int w, int c, double data_range, bool valid, double *value,
+                               float *map, float *dmaps, double *partials, hipStream_t stream);
+hipError_t launch_ssim_backward(const float *x, const float *y, const float *dmaps, const float *upstream, int n, int h, int w, int c, bool valid,
+                                float *grad, hipStream_t stream);
 // importance-sampled pixel batches (drt_pixel_dist.hip): a table over n < 2^31 film entries = this header, the exclusive uint64 prefix of the
 // sums of blocks of kDistBlock masses [n_blocks + 1], then the 16-bit masses padded to whole blocks (16-byte aligned)
 constexpr uint32_t kDistBlock = 256;

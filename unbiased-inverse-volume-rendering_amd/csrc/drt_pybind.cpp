@@ -536,6 +536,21 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
                                       reinterpret_cast<double *>(value), reinterpret_cast<void *>(scratch), scratch_bytes, nz, ny, nx, nc, weight, eps);
         if (rc != DRT_OK) throw std::runtime_error(std::string("drt_grid_prior: ") + drt_last_error(nullptr));
     });
+    m.def("ssim_scratch_bytes", [](int32_t n, int32_t h, int32_t w, int32_t c) { return drt_ssim_scratch_bytes(n, h, w, c); });
+    m.def("ssim_forward", [](uintptr_t stream, uintptr_t img, uintptr_t ref, int32_t n, int32_t h, int32_t w, int32_t c, double data_range,
+                             bool valid, uintptr_t value, uintptr_t map, uintptr_t dmaps, uintptr_t scratch, uint64_t scratch_bytes) {
+        const int rc = drt_ssim_forward(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(img), reinterpret_cast<const float *>(ref),
+                                        n, h, w, c, data_range, valid ? 1 : 0, reinterpret_cast<double *>(value), reinterpret_cast<float *>(map),
+                                        reinterpret_cast<float *>(dmaps), reinterpret_cast<void *>(scratch), scratch_bytes);
+        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+    });
+    m.def("ssim_backward", [](uintptr_t stream, uintptr_t img, uintptr_t ref, uintptr_t dmaps, uintptr_t upstream, int32_t n, int32_t h, int32_t w,
+                              int32_t c, bool valid, uintptr_t grad) {
+        const int rc = drt_ssim_backward(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(img), reinterpret_cast<const float *>(ref),
+                                         reinterpret_cast<const float *>(dmaps), reinterpret_cast<const float *>(upstream), n, h, w, c,
+                                         valid ? 1 : 0, reinterpret_cast<float *>(grad));
+        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+    });
     // grids are (Z,Y,X,C): the extents arrive in tensor order and go to the C ABI as {X,Y,Z}
     m.def("grid_resample", [](uintptr_t stream, uintptr_t src, int32_t sz, int32_t sy, int32_t sx, uintptr_t dst, int32_t tz, int32_t ty, int32_t tx,
                               int32_t channels) {

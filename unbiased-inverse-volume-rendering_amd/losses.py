@@ -1,10 +1,13 @@
 """Image losses of the reference (python/losses.py) on torch tensors.  `img` and `ref_img` have the
-same shape; every loss is normalised by `dr.width(img)` = the number of entries."""
+same shape; every loss is normalised by `dr.width(img)` = the number of entries.  Beside them `ssim`, `dssim` and `ssim_map` (ssim.py): the
+structural similarity index, the one loss here that is not a sum over independent pixels."""
 from __future__ import annotations
 
 import math
 
 import torch
+
+from .ssim import dssim, ssim, ssim_map      # structural similarity: not a sum over pixels (ssim.py)
 
 
 def average(img, ref_img=None, shape=None):
@@ -81,7 +84,8 @@ def pixelwise(loss):
     summand = _summand(fn, kwargs) if fn is not None and callable(fn) and set(kwargs) <= {"delta", "epsilon", "shape"} else None
     if summand is None:
         raise ValueError(f"pixelwise: {getattr(loss, '__name__', loss)!r} is not a sum over pixels; the pixel-separable losses are l1, l2, "
-                         f"huber, mean_relative_absolute_error, mean_relative_squared_error and average")
+                         f"huber, mean_relative_absolute_error, mean_relative_squared_error and average (ssim and dssim read an 11 x 11 "
+                         f"neighbourhood of every pixel: they are not pixel-separable)")
 
     def per_pixel(img, ref_img=None):
         if img.dim() < 1:

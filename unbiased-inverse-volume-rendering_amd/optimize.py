@@ -75,6 +75,10 @@ class OptimizationConfig:
     resample_colour: bool = False
     # opt-in: start from the visual hull of alpha mattes and keep the optimizer inside it (hull.py); None: nothing extra runs
     support: Optional[HullSupport] = None
+    # opt-in: weight of the D-SSIM term 1 - ssim (losses.dssim) over the colour channels of the full image, added to every iteration's loss
+    # of a sensor-mode (batch_size=None), unfused, unsharded run; `dssim_data_range` is its L.  0: nothing extra runs
+    dssim_weight: float = 0.0
+    dssim_data_range: float = 1.0
 
     def __post_init__(self):
         self.upsample_at = set()
@@ -445,6 +449,31 @@ def render_previews(output_dir: str, opt_config: OptimizationConfig, scene_confi
     return written
 
 
+@torch.no_grad()
+def evaluate_views(scene: Scene, integrator, sensors, references, spp: int, seed: int = 0, data_range: float = 1.0) -> Dict[str, List[float]]:
+    """PSNR and SSIM (include/drt_hip.h "SSIM", the "same" mean) of `scene` against reference images, the two numbers of an inverse-rendering
+    table: {"psnr": [...], "ssim": [...]}, one entry per sensor, over the colour channels.  `sensors`: indices into `scene.sensors`;
+    `references`: one (H, W, >= 3) image per entry of `sensors` (a tensor (n, H, W, C) or a sequence); `integrator`: an integrator, or the name
+    / IntegratorConfig of one.  One render per sensor at `spp` and `seed`, and ONE device -> host copy at the end: no host wait in between."""
+    if isinstance(integrator, str) or hasattr(integrator, 'create'):
+        integrator = get_int_config(integrator).create(max_depth=64)
+    sensors = list(sensors)
+    if len(references) != len(sensors):
+        raise ValueError(f"evaluate_views: {len(references)} references for {len(sensors)} sensors")
+    values = []
+    for i, s in enumerate(sensors):
+        sensor = scene.sensors[s]
+        ref = references[i]
+        if tuple(ref.shape[:2]) != (sensor.height, sensor.width) or ref.shape[-1] < 3:
+            raise ValueError(f"evaluate_views: reference {i} is {tuple(ref.shape)}, sensor {s} renders ({sensor.height}, {sensor.width}, 3)")
+        image = render_primal(scene, integrator, s, spp, seed)[:, :3]
+        ref = ref[..., :3].reshape(-1, 3).to(image.device)
+        values.append(losses.psnr(image, ref, max_value=data_range).to(torch.float32))
+        values.append(losses.ssim(image, ref, shape=(sensor.height, sensor.width), data_range=data_range).to(torch.float32))
+    flat = torch.stack(values).tolist() if values else []
+    return {"psnr": flat[0::2], "ssim": flat[1::2]}
+
+
 def _scene_with(scene: Scene, params: Dict[str, torch.Tensor], factor: int) -> Scene:
     m = scene.medium
     medium = GridMedium(sigma_t=params.get(SIGMA_T_KEY, m.sigma_t), albedo=params.get(ALBEDO_KEY, m.albedo),
@@ -515,6 +544,11 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     the colour grids, not what Mitsuba renders from such an asset.  With equal lattices the flag launches nothing and the run's bits are
     those of a run without it.
 
+    `opt_config.dssim_weight` (sensor mode, i.e. `batch_size=None`; not with `fused_loss`, not sharded - each raises a ValueError at
+    start-up): the step's loss gains dssim_weight x losses.dssim(image[:, :3], ref[:, :3], shape=(H, W), data_range=dssim_data_range), scaled
+    as the loss is - the 0.8 l1 + 0.2 (1 - SSIM) objective of full-image reconstruction with loss=l1 scaled by 0.8.  On the device that is
+    one stencil pass forward and one backward (csrc/drt_ssim.hip), no host wait.  0 (the default) runs nothing and leaves the run's bits.
+
     `opt_config.support` (a `HullSupport`; every route, sharded ones too - each rank carves the same integers; like the rest of
     distributed.py that is unverified on multi-GPU hardware): at initialisation and after every `upsample` the visual hull of the mattes
     (`masks`, or channel 3 of the references > `threshold`) is carved from the scene's box and the run's sensors at the current resolution
@@ -542,6 +576,19 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             if k in (PHASE_G_KEY, PHASE_TAB_KEY) or k not in scene_config.param_keys or not k.endswith('.data'):
                 raise ValueError(f'support: "{k}" is not an optimised grid (optimised grid keys: '
                                  f'{[q for q in scene_config.param_keys if q not in (PHASE_G_KEY, PHASE_TAB_KEY)]})')
+    dssim_weight = opt_config.dssim_weight
+    if isinstance(dssim_weight, bool) or not isinstance(dssim_weight, (int, float)) or not np.isfinite(dssim_weight):
+        raise ValueError(f"dssim_weight must be a finite number, got {dssim_weight!r}")
+    if dssim_weight != 0.0:
+        if opt_config.batch_size is not None:
+            raise ValueError("dssim_weight: batched rendering (batch_size set) draws random pixels, which have no neighbourhoods for a structural "
+                             "index to read; use sensor-based rendering (batch_size=None)")
+        if opt_config.fused_loss:
+            raise ValueError("dssim_weight: fused_loss=True is not supported (the loss-fused film sums a pixel-separable loss and never holds "
+                             "the image the D-SSIM term differentiates); use fused_loss=False")
+        if shard.partitioned:
+            raise ValueError("dssim_weight: sharded runs are not supported: every rank renders a share of the image's pixels, and the "
+                             "structural index needs the whole neighbourhood of each")
     importance = opt_config.pixel_importance
     pixel_loss = None
     if importance is not None:
@@ -848,6 +895,9 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
                     loss_value = loss_value + opt_config.distortion_weight * _losses.distortion(image) * scale
             else:
                 loss_value = opt_config.loss(image, ref_values) * scale
+            if dssim_weight != 0.0:                                    # (sensor mode, unsharded: the whole image of sensor s_i, flat)
+                loss_value = loss_value + dssim_weight * _losses.dssim(image[:, :3], ref_values[:, :3], shape=(sensors[s_i].height, sensors[s_i].width),
+                                                                       data_range=opt_config.dssim_data_range) * scale
         loss_value.backward()                                          # dr.backward (:350)
         if dist is not None:                                           # only now: the backward pass re-sampled the pixels from the table
             importance.last_pixel_loss = ell.detach()
