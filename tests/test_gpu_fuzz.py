@@ -465,7 +465,7 @@ def test_random_sequence_on_one_handle_matches_the_oracle(uivr, oracle, gpu, see
 def test_one_handle_rebound_to_a_grid_with_as_many_tiles_in_another_arrangement(uivr, oracle, gpu, seed):
     """What the sequences found (round 6; 15 of the first 400): the record slot of the deferred gradient reduction was re-planned when the NUMBER of its
     32 x 16 x 16-voxel tiles changed, not when their arrangement did - 7 x 25 x 25 voxels are 1 x 2 x 1 tiles, 25 x 3 x 5 voxels 1 x 1 x 2 - so a handle
-    rebound to such a grid sorted its splat records by the old arrangement and lost part of the gradient (radiance unaffected).  csrc/drt_capi.cpp:
+    rebound to such a grid sorted its splat records by the old arrangement and lost part of the gradient (radiance unaffected).  csrc/drt_capi_volpath.cpp:
     ensure_deferred."""
     _check_sequence(uivr, oracle, gpu, seed)
 

@@ -1,6 +1,6 @@
 """Round 6: the primal kernels of the queued supergrid tracer finish a ray in the regeneration block when it is over before it begins (box
 miss, flagged-empty pixel, a first flight whose optical-depth target exceeds largest majorant x segment), and launches in index order over a
-medium the HOST has seen to be thin run the ROUNDS instantiation (drt_sq.hip; the hint is a majorant read-back nothing waits for, drt_capi.cpp).
+medium the HOST has seen to be thin run the ROUNDS instantiation (drt_sq.hip; the hint is a majorant read-back nothing waits for, drt_capi.cpp: drt_params_changed, read in drt_capi_volpath.cpp).
 Both against the oracle: radiance bit-exact, counters equal, the adjoint pass that follows (path cache entries written by the finished rays)
 within 2e-4 - before the hint can have arrived and after a synchronisation has made sure it has."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The queued tracer's adjoint launch reuses the per-pixel emptiness flags of the primal launch of the same job (drt_capi.cpp:
+"""The queued tracer's adjoint launch reuses the per-pixel emptiness flags of the primal launch of the same job (drt_capi_volpath.cpp:
 bind_unit_empty) - and only of the same job.  Flags that outlived a change of the medium or of the sensor would cut short the first
 flight of a pixel that is no longer empty.
 

@@ -23,8 +23,9 @@ _ROOT = os.path.dirname(_PKG)
 HIP_SOURCES = ["drt_kernels.hip", "drt_deferred.hip", "drt_coop.hip", "drt_coop_super.hip", "drt_order.hip", "drt_sq.hip", "drt_nerf_tile.hip", "drt_nerf_sh.hip", "drt_nerf_aov.hip", "drt_nerf_dist.hip", "drt_own.hip", "drt_loss.hip", "drt_priors.hip", "drt_resample.hip", "drt_pixel_dist.hip", "drt_opacity.hip", "drt_hull.hip", "drt_ssim.hip",
                "drt_coop_hg.hip", "drt_coop_super_hg.hip", "drt_own_hg.hip", "drt_sq_hg.hip",
                "drt_coop_hg2.hip", "drt_coop_super_hg2.hip", "drt_own_hg2.hip", "drt_sq_hg2.hip",
-               "drt_coop_tab.hip", "drt_coop_super_tab.hip", "drt_own_tab.hip", "drt_sq_tab.hip", "drt_capi.cpp"]
-HIP_HEADERS = ["drt_sq_kernel.h", "drt_device.h", "drt_launch.h", "drt_coop_tracer.h", "drt_coop_kernel.h", "drt_nerf_kernel.h", "drt_nerf_tile_kernel.h", "drt_film.h", os.path.join(_ROOT, "include", "drt_hip.h")]
+               "drt_coop_tab.hip", "drt_coop_super_tab.hip", "drt_own_tab.hip", "drt_sq_tab.hip",
+               "drt_capi.cpp", "drt_capi_volpath.cpp", "drt_capi_nerf.cpp", "drt_capi_opacity.cpp", "drt_capi_film.cpp", "drt_capi_ops.cpp"]
+HIP_HEADERS = ["drt_sq_kernel.h", "drt_device.h", "drt_launch.h", "drt_host.h", "drt_coop_tracer.h", "drt_coop_kernel.h", "drt_nerf_kernel.h", "drt_nerf_tile_kernel.h", "drt_film.h", os.path.join(_ROOT, "include", "drt_hip.h")]
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
              "-ffp-contract=off", "-munsafe-fp-atomics", "-Wall"]
 

@@ -1,4 +1,4 @@
-// drt_launch.h -- host-side launch interface between the C ABI (drt_capi.cpp)
+// drt_launch.h -- host-side launch interface between the C ABI (the drt_capi*.cpp host units, drt_host.h)
 // and the kernels (the drt_*.hip units; each comment names the unit that defines what it describes).
 #pragma once
 #include <hip/hip_runtime.h>

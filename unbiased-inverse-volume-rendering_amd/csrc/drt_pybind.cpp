@@ -22,6 +22,15 @@ namespace {
 template <typename T>
 T *ptr(uintptr_t p) { return reinterpret_cast<T *>(p); }
 
+// The module-level functions (no handle): a non-zero status becomes RuntimeError.  `coded`: the name of a C function that sets no message -
+// it is reported as "<name> failed (code N)"; otherwise the library's message for this thread, behind `prefix`
+void ok(int rc, const char *coded = nullptr, const char *prefix = "")
+{
+    if (rc == DRT_OK) return;
+    if (coded) throw std::runtime_error(std::string(coded) + " failed (code " + std::to_string(rc) + ")");
+    throw std::runtime_error(std::string(prefix) + drt_last_error(nullptr));
+}
+
 class Integrator {
 public:
     Integrator(const py::dict &props, int device)
@@ -52,21 +61,17 @@ public:
     {
         if (rc) throw std::runtime_error(std::string(what) + ": " + drt_last_error(h_));
     }
-
-    void release_scratch()
+    // a call that enqueues or waits for device work: the GIL released around `call()`, then its status checked under the C function's name
+    template <class Call> void nogil(const char *what, Call call) const
     {
         int rc;
-        { py::gil_scoped_release nogil; rc = drt_release_scratch(h_); }
-        check(rc, "drt_release_scratch");
+        { py::gil_scoped_release release; rc = call(); }
+        check(rc, what);
     }
+
+    void release_scratch() { nogil("drt_release_scratch", [&] { return drt_release_scratch(h_); }); }
     void set_stream(uintptr_t s) { check(drt_set_stream(h_, ptr<void>(s)), "drt_set_stream"); }
-    void synchronize()
-    {
-        py::gil_scoped_release nogil;
-        int rc = drt_synchronize(h_);
-        py::gil_scoped_acquire gil;
-        check(rc, "drt_synchronize");
-    }
+    void synchronize() { nogil("drt_synchronize", [&] { return drt_synchronize(h_); }); }
     void set_ray_interleave(uint64_t chunk, uint64_t stride)
     {
         check(drt_set_ray_interleave(h_, chunk, stride), "drt_set_ray_interleave");
@@ -74,13 +79,9 @@ public:
     void set_medium(uintptr_t sigma_t, uintptr_t albedo, std::array<int32_t, 3> res,
                     std::array<float, 3> bmin, std::array<float, 3> bmax, float scale, int factor)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_set_medium(h_, ptr<const float>(sigma_t), ptr<const float>(albedo), res.data(),
-                                bmin.data(), bmax.data(), scale, factor);
-        }
-        check(rc, "drt_set_medium");
+        nogil("drt_set_medium", [&] {
+            return drt_set_medium(h_, ptr<const float>(sigma_t), ptr<const float>(albedo), res.data(), bmin.data(), bmax.data(), scale, factor);
+        });
     }
     uint64_t nerf_tile_lds_adds() { uint64_t v = 0; check(drt_nerf_tile_stats(h_, &v), "drt_nerf_tile_stats"); return v; }
     void set_colour_resolution(std::array<int32_t, 3> res) { check(drt_set_colour_resolution(h_, res.data()), "drt_set_colour_resolution"); }
@@ -88,28 +89,16 @@ public:
     void set_phase_hg2(float g1, float g2, float weight) { check(drt_set_phase_hg2(h_, g1, g2, weight), "drt_set_phase_hg2"); }
     void set_phase_tab(const std::vector<float> &values)        // (a host list, copied by the library)
     {
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_set_phase_tab(h_, values.data(), (int32_t) std::min<size_t>(values.size(), 0x7fffffffu)); }
-        check(rc, "drt_set_phase_tab");
+        nogil("drt_set_phase_tab", [&] { return drt_set_phase_tab(h_, values.data(), (int32_t) std::min<size_t>(values.size(), 0x7fffffffu)); });
     }
-    void params_changed()
-    {
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_params_changed(h_); }
-        check(rc, "drt_params_changed");
-    }
+    void params_changed() { nogil("drt_params_changed", [&] { return drt_params_changed(h_); }); }
     void set_emitter_constant(std::array<float, 3> rgb)
     {
         check(drt_set_emitter_constant(h_, rgb.data()), "drt_set_emitter_constant");
     }
     void set_emitter_envmap(uintptr_t pixels, int w, int hgt, std::array<float, 9> to_world, float scale)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_set_emitter_envmap(h_, (const float *) pixels, w, hgt, to_world.data(), scale);
-        }
-        check(rc, "drt_set_emitter_envmap");
+        nogil("drt_set_emitter_envmap", [&] { return drt_set_emitter_envmap(h_, (const float *) pixels, w, hgt, to_world.data(), scale); });
     }
     void set_sensor_perspective(std::array<float, 3> o, std::array<float, 3> left, std::array<float, 3> up,
                                 std::array<float, 3> dir, float tan_x, float tan_y, int w, int hgt)
@@ -120,47 +109,31 @@ public:
     void render_primal(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp,
                        uint32_t seed, uintptr_t L_out)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_primal(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
-                                   ptr<float>(L_out));
-        }
-        check(rc, "drt_render_primal");
+        nogil("drt_render_primal", [&] { return drt_render_primal(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<float>(L_out)); });
     }
     void render_backward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp,
                          uint32_t seed, uintptr_t dL, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_backward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
-                                     ptr<const float>(dL), ptr<const float>(L_in), ptr<float>(g_sigma),
-                                     ptr<float>(g_albedo));
-        }
-        check(rc, "drt_render_backward");
+        nogil("drt_render_backward", [&] {
+            return drt_render_backward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
+                                       ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo));
+        });
     }
     void render_backward_phase(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dL,
                                uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_phase)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_backward_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
-                                           ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo), ptr<float>(g_phase));
-        }
-        check(rc, "drt_render_backward_phase");
+        nogil("drt_render_backward_phase", [&] {
+            return drt_render_backward_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
+                                             ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo), ptr<float>(g_phase));
+        });
     }
     void render_backward_phase_tab(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dL,
                                    uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_values)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_backward_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
-                                               ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo), ptr<float>(g_values));
-        }
-        check(rc, "drt_render_backward_phase_tab");
+        nogil("drt_render_backward_phase_tab", [&] {
+            return drt_render_backward_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
+                                                 ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo), ptr<float>(g_values));
+        });
     }
     static drt_nerf_config nerf_cfg(const py::dict &p)
     {
@@ -181,9 +154,7 @@ public:
         if (kind < 0 || kind > 3) throw std::invalid_argument("nerf output kind must be 0 (plain), 1 (sh), 2 (aov) or 3 (dist)");
         const drt_nerf_config c = nerf_cfg(props);
         const int32_t deg = props.contains("sh_degree") ? py::cast<int>(props["sh_degree"]) : 0;
-        int rc;
-        { py::gil_scoped_release nogil; rc = call(&c, deg); }
-        check(rc, (std::string("drt_nerf_render_") + pass + suffix[kind]).c_str());
+        nogil((std::string("drt_nerf_render_") + pass + suffix[kind]).c_str(), [&] { return call(&c, deg); });
     }
     void nerf_render_primal(int kind, const py::dict &props, uintptr_t grid, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off,
                             uint32_t spp, uint32_t seed, uintptr_t L_out)
@@ -240,96 +211,71 @@ public:
     void render_forward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
                         uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_forward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
-                                    ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out));
-        }
-        check(rc, "drt_render_forward");
+        nogil("drt_render_forward", [&] {
+            return drt_render_forward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
+                                      ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out));
+        });
     }
     void render_forward_phase(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
                               uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out, float t_phase)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_forward_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
-                                          ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), t_phase);
-        }
-        check(rc, "drt_render_forward_phase");
+        nogil("drt_render_forward_phase", [&] {
+            return drt_render_forward_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
+                                            ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), t_phase);
+        });
     }
     void render_forward_phase_tab(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
                                   uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out, uintptr_t t_values)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_forward_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
-                                              ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), ptr<const float>(t_values));
-        }
-        check(rc, "drt_render_forward_phase_tab");
+        nogil("drt_render_forward_phase_tab", [&] {
+            return drt_render_forward_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
+                                                ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), ptr<const float>(t_values));
+        });
     }
     void fused_render_primal(const py::dict &props, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp,
                              uint32_t seed, uintptr_t L_nerf, uintptr_t L_drt)
     {
         drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_fused_render_primal(h_, &c, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
-                                         ptr<float>(L_nerf), ptr<float>(L_drt));
-        }
-        check(rc, "drt_fused_render_primal");
+        nogil("drt_fused_render_primal", [&] {
+            return drt_fused_render_primal(h_, &c, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<float>(L_nerf),
+                                           ptr<float>(L_drt));
+        });
     }
     void fused_render_backward(const py::dict &props, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp,
                                uint32_t seed, uintptr_t dL_nerf, uintptr_t L_nerf_in, uintptr_t dL_drt, uintptr_t L_drt_in,
                                uintptr_t g_sigma, uintptr_t g_rgb)
     {
         drt_nerf_config c = nerf_cfg(props);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_fused_render_backward(h_, &c, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
-                                           ptr<const float>(dL_nerf), ptr<const float>(L_nerf_in), ptr<const float>(dL_drt),
-                                           ptr<const float>(L_drt_in), ptr<float>(g_sigma), ptr<float>(g_rgb));
-        }
-        check(rc, "drt_fused_render_backward");
+        nogil("drt_fused_render_backward", [&] {
+            return drt_fused_render_backward(h_, &c, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
+                                             ptr<const float>(dL_nerf), ptr<const float>(L_nerf_in), ptr<const float>(dL_drt),
+                                             ptr<const float>(L_drt_in), ptr<float>(g_sigma), ptr<float>(g_rgb));
+        });
     }
     void batch_sample_rays(uintptr_t sensors, int n_sensors, uint32_t batch, uint32_t spp, uint32_t seed_px, uint32_t seed_rays,
                            uintptr_t ro, uintptr_t rd, uintptr_t sidx, uintptr_t pix, uint32_t batch_first)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_batch_sample_rays_range(h_, ptr<const float>(sensors), n_sensors, batch_first, batch, spp, seed_px, seed_rays,
-                                             ptr<float>(ro), ptr<float>(rd), ptr<uint32_t>(sidx), ptr<uint32_t>(pix));
-        }
-        check(rc, "drt_batch_sample_rays_range");
+        nogil("drt_batch_sample_rays_range", [&] {
+            return drt_batch_sample_rays_range(h_, ptr<const float>(sensors), n_sensors, batch_first, batch, spp, seed_px, seed_rays,
+                                               ptr<float>(ro), ptr<float>(rd), ptr<uint32_t>(sidx), ptr<uint32_t>(pix));
+        });
     }
     void batch_sample_rays_weighted(uintptr_t sensors, int n_sensors, uint32_t batch, uint32_t spp, uint32_t seed_px, uint32_t seed_rays,
                                     uintptr_t table, uint32_t uniform_q, uintptr_t ro, uintptr_t rd, uintptr_t sidx, uintptr_t pix, uint32_t batch_first)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_batch_sample_rays_weighted(h_, ptr<const float>(sensors), n_sensors, batch_first, batch, spp, seed_px, seed_rays,
-                                                ptr<const void>(table), uniform_q, ptr<float>(ro), ptr<float>(rd), ptr<uint32_t>(sidx),
-                                                ptr<uint32_t>(pix));
-        }
-        check(rc, "drt_batch_sample_rays_weighted");
+        nogil("drt_batch_sample_rays_weighted", [&] {
+            return drt_batch_sample_rays_weighted(h_, ptr<const float>(sensors), n_sensors, batch_first, batch, spp, seed_px, seed_rays,
+                                                  ptr<const void>(table), uniform_q, ptr<float>(ro), ptr<float>(rd), ptr<uint32_t>(sidx),
+                                                  ptr<uint32_t>(pix));
+        });
     }
     void film_develop(uintptr_t L, uint64_t n_pixels, uint32_t spp, uintptr_t image)
     {
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_film_develop(h_, ptr<const float>(L), n_pixels, spp, ptr<float>(image)); }
-        check(rc, "drt_film_develop");
+        nogil("drt_film_develop", [&] { return drt_film_develop(h_, ptr<const float>(L), n_pixels, spp, ptr<float>(image)); });
     }
     void film_backward(uintptr_t grad_image, uint64_t n_pixels, uint32_t spp, uintptr_t dL)
     {
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_film_backward(h_, ptr<const float>(grad_image), n_pixels, spp, ptr<float>(dL)); }
-        check(rc, "drt_film_backward");
+        nogil("drt_film_backward", [&] { return drt_film_backward(h_, ptr<const float>(grad_image), n_pixels, spp, ptr<float>(dL)); });
     }
     static drt_loss_ref loss_ref(uintptr_t dense, uintptr_t images, std::array<int32_t, 4> shape, uintptr_t sensor_idx, uintptr_t pixel_idx)
     {
@@ -343,123 +289,91 @@ public:
                            uintptr_t sensor_idx, uintptr_t pixel_idx, int kind, float param, uintptr_t image, uintptr_t loss)
     {
         const drt_loss_ref r = loss_ref(dense, images, shape, sensor_idx, pixel_idx);
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_film_loss_forward(h_, ptr<const float>(L), n_pixels, spp, &r, kind, param, ptr<float>(image), ptr<float>(loss)); }
-        check(rc, "drt_film_loss_forward");
+        nogil("drt_film_loss_forward", [&] {
+            return drt_film_loss_forward(h_, ptr<const float>(L), n_pixels, spp, &r, kind, param, ptr<float>(image), ptr<float>(loss));
+        });
     }
     void film_loss_grad(uintptr_t image, uint64_t n_pixels, uintptr_t dense, uintptr_t images, std::array<int32_t, 4> shape,
                         uintptr_t sensor_idx, uintptr_t pixel_idx, int kind, float param, uintptr_t upstream, uintptr_t grad_image)
     {
         const drt_loss_ref r = loss_ref(dense, images, shape, sensor_idx, pixel_idx);
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_film_loss_grad(h_, ptr<const float>(image), n_pixels, &r, kind, param, ptr<const float>(upstream), ptr<float>(grad_image));
-        }
-        check(rc, "drt_film_loss_grad");
+        nogil("drt_film_loss_grad", [&] {
+            return drt_film_loss_grad(h_, ptr<const float>(image), n_pixels, &r, kind, param, ptr<const float>(upstream), ptr<float>(grad_image));
+        });
     }
     void render_backward_px(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed,
                             uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_backward_px(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(grad_image),
-                                        n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo));
-        }
-        check(rc, "drt_render_backward_px");
+        nogil("drt_render_backward_px", [&] {
+            return drt_render_backward_px(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(grad_image),
+                                          n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo));
+        });
     }
     void render_backward_px_phase(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed,
                                   uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_phase)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_backward_px_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
-                                              ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
-                                              ptr<float>(g_albedo), ptr<float>(g_phase));
-        }
-        check(rc, "drt_render_backward_px_phase");
+        nogil("drt_render_backward_px_phase", [&] {
+            return drt_render_backward_px_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
+                                                ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
+                                                ptr<float>(g_albedo), ptr<float>(g_phase));
+        });
     }
     void render_backward_px_phase_tab(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed,
                                       uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_values)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_render_backward_px_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
-                                                  ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
-                                                  ptr<float>(g_albedo), ptr<float>(g_values));
-        }
-        check(rc, "drt_render_backward_px_phase_tab");
+        nogil("drt_render_backward_px_phase_tab", [&] {
+            return drt_render_backward_px_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
+                                                    ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
+                                                    ptr<float>(g_albedo), ptr<float>(g_values));
+        });
     }
     void film_develop_n(uintptr_t L, uint64_t n_pixels, uint32_t spp, uint32_t channels, uintptr_t image)
     {
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_film_develop_n(h_, ptr<const float>(L), n_pixels, spp, channels, ptr<float>(image)); }
-        check(rc, "drt_film_develop_n");
+        nogil("drt_film_develop_n", [&] { return drt_film_develop_n(h_, ptr<const float>(L), n_pixels, spp, channels, ptr<float>(image)); });
     }
     void film_backward_n(uintptr_t grad_image, uint64_t n_pixels, uint32_t spp, uint32_t channels, uintptr_t dL)
     {
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_film_backward_n(h_, ptr<const float>(grad_image), n_pixels, spp, channels, ptr<float>(dL)); }
-        check(rc, "drt_film_backward_n");
+        nogil("drt_film_backward_n", [&] { return drt_film_backward_n(h_, ptr<const float>(grad_image), n_pixels, spp, channels, ptr<float>(dL)); });
     }
     // opacity of camera rays / the raw transmittance walk (drt_opacity.hip): one float per ray or segment
     void transmittance_segments(uintptr_t o, uintptr_t d, uintptr_t tmax, uint64_t n, uint64_t first_index, uint32_t seed, uintptr_t T_out)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_transmittance_segments(h_, ptr<const float>(o), ptr<const float>(d), ptr<const float>(tmax), n, first_index, seed, ptr<float>(T_out));
-        }
-        check(rc, "drt_transmittance_segments");
+        nogil("drt_transmittance_segments", [&] {
+            return drt_transmittance_segments(h_, ptr<const float>(o), ptr<const float>(d), ptr<const float>(tmax), n, first_index, seed, ptr<float>(T_out));
+        });
     }
     void opacity_primal(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t A_out)
     {
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_opacity_primal(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<float>(A_out)); }
-        check(rc, "drt_opacity_primal");
+        nogil("drt_opacity_primal", [&] { return drt_opacity_primal(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<float>(A_out)); });
     }
     void opacity_backward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dA, uintptr_t A_in,
                           uintptr_t g_sigma)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_opacity_backward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dA),
-                                      ptr<const float>(A_in), ptr<float>(g_sigma));
-        }
-        check(rc, "drt_opacity_backward");
+        nogil("drt_opacity_backward", [&] {
+            return drt_opacity_backward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dA),
+                                        ptr<const float>(A_in), ptr<float>(g_sigma));
+        });
     }
     void opacity_backward_px(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t grad_image,
                              uint64_t n_pixels, uintptr_t A_in, uintptr_t g_sigma)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_opacity_backward_px(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(grad_image),
-                                         n_pixels, ptr<const float>(A_in), ptr<float>(g_sigma));
-        }
-        check(rc, "drt_opacity_backward_px");
+        nogil("drt_opacity_backward_px", [&] {
+            return drt_opacity_backward_px(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(grad_image),
+                                           n_pixels, ptr<const float>(A_in), ptr<float>(g_sigma));
+        });
     }
     void opacity_forward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t A_in, uintptr_t t_sigma,
                          uintptr_t dA_out)
     {
-        int rc;
-        {
-            py::gil_scoped_release nogil;
-            rc = drt_opacity_forward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(A_in),
-                                     ptr<const float>(t_sigma), ptr<float>(dA_out));
-        }
-        check(rc, "drt_opacity_forward");
+        nogil("drt_opacity_forward", [&] {
+            return drt_opacity_forward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(A_in),
+                                       ptr<const float>(t_sigma), ptr<float>(dA_out));
+        });
     }
     uint64_t nerf_sh_tile_phases() { uint64_t v = 0; check(drt_nerf_sh_tile_stats(h_, &v), "drt_nerf_sh_tile_stats"); return v; }
     void debug_eval(int op, uintptr_t in, uint64_t n, uintptr_t out)
     {
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_debug_eval(h_, op, ptr<const float>(in), n, ptr<float>(out)); }
-        check(rc, "drt_debug_eval");
+        nogil("drt_debug_eval", [&] { return drt_debug_eval(h_, op, ptr<const float>(in), n, ptr<float>(out)); });
     }
     void set_debug_flags(uint32_t f) { check(drt_set_debug_flags(h_, f), "drt_set_debug_flags"); }
     void enable_counters(bool on) { check(drt_enable_counters(h_, on ? 1 : 0), "drt_enable_counters"); }
@@ -467,9 +381,7 @@ public:
     py::dict get_counters()
     {
         drt_counters c{};
-        int rc;
-        { py::gil_scoped_release nogil; rc = drt_get_counters(h_, &c); }
-        check(rc, "drt_get_counters");
+        nogil("drt_get_counters", [&] { return drt_get_counters(h_, &c); });
         py::dict d;
         d["n_rays"] = c.n_rays; d["n_dt"] = c.n_dt; d["n_rt"] = c.n_rt; d["n_drt"] = c.n_drt;
         d["n_alb"] = c.n_alb; d["n_tr"] = c.n_tr; d["n_rt_adj"] = c.n_rt_adj; d["n_sc"] = c.n_sc;
@@ -503,115 +415,89 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
     m.doc() = "pybind11 shim over libdrt_hip.so (C ABI in include/drt_hip.h)";
     m.def("version", []() { return std::string(drt_version()); });
     m.def("adam_step", [](uintptr_t stream, uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uint64_t n, double b1, double b2, double eps, double lr_t) {
-        const int rc = drt_adam_step(reinterpret_cast<void *>(stream), reinterpret_cast<float *>(p), reinterpret_cast<const float *>(g),
-                                     reinterpret_cast<float *>(mm), reinterpret_cast<float *>(v), n, b1, b2, eps, lr_t);
-        if (rc != DRT_OK) throw std::runtime_error("drt_adam_step failed (code " + std::to_string(rc) + ")");
+        ok(drt_adam_step(ptr<void>(stream), ptr<float>(p), ptr<const float>(g), ptr<float>(mm), ptr<float>(v), n, b1, b2, eps, lr_t), "drt_adam_step");
     });
     m.def("adam_step_clamped", [](uintptr_t stream, uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uint64_t n, double b1, double b2, double eps, double lr_t, float lo, float hi) {
-        const int rc = drt_adam_step_clamped(reinterpret_cast<void *>(stream), reinterpret_cast<float *>(p), reinterpret_cast<const float *>(g),
-                                     reinterpret_cast<float *>(mm), reinterpret_cast<float *>(v), n, b1, b2, eps, lr_t, lo, hi);
-        if (rc != DRT_OK) throw std::runtime_error("drt_adam_step_clamped failed (code " + std::to_string(rc) + ")");
+        ok(drt_adam_step_clamped(ptr<void>(stream), ptr<float>(p), ptr<const float>(g), ptr<float>(mm), ptr<float>(v), n, b1, b2, eps, lr_t, lo, hi),
+           "drt_adam_step_clamped");
     });
     m.def("adam_step_masked", [](uintptr_t stream, uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uint64_t n_voxels, int32_t channels,
                                  uintptr_t support, bool skip_zero_grad, double b1, double b2, double eps, double lr_t, float lo, float hi) {
-        const int rc = drt_adam_step_masked(reinterpret_cast<void *>(stream), reinterpret_cast<float *>(p), reinterpret_cast<const float *>(g),
-                                            reinterpret_cast<float *>(mm), reinterpret_cast<float *>(v), n_voxels, channels,
-                                            reinterpret_cast<const uint8_t *>(support), skip_zero_grad ? 1 : 0, b1, b2, eps, lr_t, lo, hi);
-        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+        ok(drt_adam_step_masked(ptr<void>(stream), ptr<float>(p), ptr<const float>(g), ptr<float>(mm), ptr<float>(v), n_voxels, channels,
+                                ptr<const uint8_t>(support), skip_zero_grad ? 1 : 0, b1, b2, eps, lr_t, lo, hi));
     });
     // counts is (Z,Y,X,2): the extents arrive in tensor order and go to the C ABI as {X,Y,Z}
     m.def("visual_hull", [](uintptr_t stream, uintptr_t sensors, int32_t n_sensors, uintptr_t sat, int32_t height, int32_t width,
                             std::array<float, 3> bbox_min, std::array<float, 3> bbox_max, int32_t nz, int32_t ny, int32_t nx, int32_t margin,
                             uintptr_t counts) {
         const int32_t res[3] = {nx, ny, nz};
-        const int rc = drt_visual_hull(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(sensors), n_sensors,
-                                       reinterpret_cast<const int32_t *>(sat), height, width, bbox_min.data(), bbox_max.data(), res, margin,
-                                       reinterpret_cast<int32_t *>(counts));
-        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+        ok(drt_visual_hull(ptr<void>(stream), ptr<const float>(sensors), n_sensors, ptr<const int32_t>(sat), height, width, bbox_min.data(),
+                           bbox_max.data(), res, margin, ptr<int32_t>(counts)));
     });
     m.def("grid_prior_scratch_bytes", [](int32_t nz, int32_t ny, int32_t nx, int32_t nc) { return drt_grid_prior_scratch_bytes(nz, ny, nx, nc); });
     m.def("grid_prior", [](uintptr_t stream, int32_t kind, uintptr_t p, uintptr_t g, uintptr_t value, uintptr_t scratch, uint64_t scratch_bytes,
                            int32_t nz, int32_t ny, int32_t nx, int32_t nc, double weight, double eps) {
-        const int rc = drt_grid_prior(reinterpret_cast<void *>(stream), kind, reinterpret_cast<const float *>(p), reinterpret_cast<float *>(g),
-                                      reinterpret_cast<double *>(value), reinterpret_cast<void *>(scratch), scratch_bytes, nz, ny, nx, nc, weight, eps);
-        if (rc != DRT_OK) throw std::runtime_error(std::string("drt_grid_prior: ") + drt_last_error(nullptr));
+        ok(drt_grid_prior(ptr<void>(stream), kind, ptr<const float>(p), ptr<float>(g), ptr<double>(value), ptr<void>(scratch), scratch_bytes, nz, ny,
+                          nx, nc, weight, eps),
+           nullptr, "drt_grid_prior: ");
     });
     m.def("ssim_scratch_bytes", [](int32_t n, int32_t h, int32_t w, int32_t c) { return drt_ssim_scratch_bytes(n, h, w, c); });
     m.def("ssim_forward", [](uintptr_t stream, uintptr_t img, uintptr_t ref, int32_t n, int32_t h, int32_t w, int32_t c, double data_range,
                              bool valid, uintptr_t value, uintptr_t map, uintptr_t dmaps, uintptr_t scratch, uint64_t scratch_bytes) {
-        const int rc = drt_ssim_forward(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(img), reinterpret_cast<const float *>(ref),
-                                        n, h, w, c, data_range, valid ? 1 : 0, reinterpret_cast<double *>(value), reinterpret_cast<float *>(map),
-                                        reinterpret_cast<float *>(dmaps), reinterpret_cast<void *>(scratch), scratch_bytes);
-        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+        ok(drt_ssim_forward(ptr<void>(stream), ptr<const float>(img), ptr<const float>(ref), n, h, w, c, data_range, valid ? 1 : 0,
+                            ptr<double>(value), ptr<float>(map), ptr<float>(dmaps), ptr<void>(scratch), scratch_bytes));
     });
     m.def("ssim_backward", [](uintptr_t stream, uintptr_t img, uintptr_t ref, uintptr_t dmaps, uintptr_t upstream, int32_t n, int32_t h, int32_t w,
                               int32_t c, bool valid, uintptr_t grad) {
-        const int rc = drt_ssim_backward(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(img), reinterpret_cast<const float *>(ref),
-                                         reinterpret_cast<const float *>(dmaps), reinterpret_cast<const float *>(upstream), n, h, w, c,
-                                         valid ? 1 : 0, reinterpret_cast<float *>(grad));
-        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+        ok(drt_ssim_backward(ptr<void>(stream), ptr<const float>(img), ptr<const float>(ref), ptr<const float>(dmaps), ptr<const float>(upstream),
+                             n, h, w, c, valid ? 1 : 0, ptr<float>(grad)));
     });
     // grids are (Z,Y,X,C): the extents arrive in tensor order and go to the C ABI as {X,Y,Z}
     m.def("grid_resample", [](uintptr_t stream, uintptr_t src, int32_t sz, int32_t sy, int32_t sx, uintptr_t dst, int32_t tz, int32_t ty, int32_t tx,
                               int32_t channels) {
         const int32_t sres[3] = {sx, sy, sz}, tres[3] = {tx, ty, tz};
-        const int rc = drt_grid_resample(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(src), sres, reinterpret_cast<float *>(dst),
-                                         tres, channels);
-        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+        ok(drt_grid_resample(ptr<void>(stream), ptr<const float>(src), sres, ptr<float>(dst), tres, channels));
     });
     m.def("grid_resample_transpose", [](uintptr_t stream, uintptr_t g_dst, int32_t tz, int32_t ty, int32_t tx, uintptr_t g_src, int32_t sz, int32_t sy,
                                         int32_t sx, int32_t channels, bool accumulate) {
         const int32_t sres[3] = {sx, sy, sz}, tres[3] = {tx, ty, tz};
-        const int rc = drt_grid_resample_transpose(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(g_dst), tres,
-                                                   reinterpret_cast<float *>(g_src), sres, channels, accumulate ? 1 : 0);
-        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+        ok(drt_grid_resample_transpose(ptr<void>(stream), ptr<const float>(g_dst), tres, ptr<float>(g_src), sres, channels, accumulate ? 1 : 0));
     });
     m.def("pixel_dist_table_bytes", [](uint64_t n) { return drt_pixel_dist_table_bytes(n); });
     m.def("pixel_dist_build", [](uintptr_t stream, uintptr_t weights, uint64_t n, float decay, uintptr_t table, uint64_t table_bytes) {
-        const int rc = drt_pixel_dist_build(reinterpret_cast<void *>(stream), reinterpret_cast<float *>(weights), n, decay,
-                                            reinterpret_cast<void *>(table), table_bytes);
-        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+        ok(drt_pixel_dist_build(ptr<void>(stream), ptr<float>(weights), n, decay, ptr<void>(table), table_bytes));
     });
     m.def("pixel_dist_inv_pdf", [](uintptr_t stream, uintptr_t table, int32_t n_sensors, int32_t height, int32_t width, uintptr_t sidx, uintptr_t pix,
                                    uint64_t count, uint32_t uniform_q, uintptr_t out) {
-        const int rc = drt_pixel_dist_inv_pdf(reinterpret_cast<void *>(stream), reinterpret_cast<const void *>(table), n_sensors, height, width,
-                                              reinterpret_cast<const int32_t *>(sidx), reinterpret_cast<const int32_t *>(pix), count, uniform_q,
-                                              reinterpret_cast<float *>(out));
-        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+        ok(drt_pixel_dist_inv_pdf(ptr<void>(stream), ptr<const void>(table), n_sensors, height, width, ptr<const int32_t>(sidx),
+                                  ptr<const int32_t>(pix), count, uniform_q, ptr<float>(out)));
     });
     m.def("pixel_dist_update", [](uintptr_t stream, uintptr_t weights, int32_t n_sensors, int32_t height, int32_t width, uintptr_t sidx, uintptr_t pix,
                                   uintptr_t err, uint64_t count) {
-        const int rc = drt_pixel_dist_update(reinterpret_cast<void *>(stream), reinterpret_cast<float *>(weights), n_sensors, height, width,
-                                             reinterpret_cast<const int32_t *>(sidx), reinterpret_cast<const int32_t *>(pix),
-                                             reinterpret_cast<const float *>(err), count);
-        if (rc != DRT_OK) throw std::runtime_error(drt_last_error(nullptr));
+        ok(drt_pixel_dist_update(ptr<void>(stream), ptr<float>(weights), n_sensors, height, width, ptr<const int32_t>(sidx), ptr<const int32_t>(pix),
+                                 ptr<const float>(err), count));
     });
     m.def("grad_support_mask", [](uintptr_t stream, uintptr_t sigma_t, int rx, int ry, int rz, uint64_t sparse_off, uint32_t channels,
                                   uint64_t n_blocks, uint32_t block_floats, uintptr_t bits, uintptr_t mask) {
         const int32_t res[3] = { rx, ry, rz };
-        const int rc = drt_grad_support_mask(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(sigma_t), res, sparse_off, channels,
-                                             n_blocks, block_floats, reinterpret_cast<uint32_t *>(bits), reinterpret_cast<uint8_t *>(mask));
-        if (rc != DRT_OK) throw std::runtime_error("drt_grad_support_mask failed (code " + std::to_string(rc) + ")");
+        ok(drt_grad_support_mask(ptr<void>(stream), ptr<const float>(sigma_t), res, sparse_off, channels, n_blocks, block_floats, ptr<uint32_t>(bits),
+                                 ptr<uint8_t>(mask)),
+           "drt_grad_support_mask");
     });
     m.def("grad_block_mask", [](uintptr_t stream, uintptr_t buf, uint64_t n_blocks, uint32_t block_floats, uintptr_t mask) {
-        const int rc = drt_grad_block_mask(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(buf), n_blocks,
-                                           block_floats, reinterpret_cast<uint8_t *>(mask));
-        if (rc != DRT_OK) throw std::runtime_error("drt_grad_block_mask failed (code " + std::to_string(rc) + ")");
+        ok(drt_grad_block_mask(ptr<void>(stream), ptr<const float>(buf), n_blocks, block_floats, ptr<uint8_t>(mask)), "drt_grad_block_mask");
     });
     m.def("grad_block_positions", [](uintptr_t stream, uintptr_t mask, uint64_t n_blocks, uintptr_t pos, uintptr_t count, uintptr_t scratch) {
-        const int rc = drt_grad_block_positions(reinterpret_cast<void *>(stream), reinterpret_cast<const uint8_t *>(mask), n_blocks,
-                                                reinterpret_cast<int32_t *>(pos), reinterpret_cast<int32_t *>(count), reinterpret_cast<uint32_t *>(scratch));
-        if (rc != DRT_OK) throw std::runtime_error("drt_grad_block_positions failed (code " + std::to_string(rc) + ")");
+        ok(drt_grad_block_positions(ptr<void>(stream), ptr<const uint8_t>(mask), n_blocks, ptr<int32_t>(pos), ptr<int32_t>(count), ptr<uint32_t>(scratch)),
+           "drt_grad_block_positions");
     });
     m.def("grad_pack", [](uintptr_t stream, uintptr_t flat, uintptr_t pos, uint64_t n_blocks, uint32_t block_floats, uintptr_t packed, uintptr_t check) {
-        const int rc = drt_grad_pack(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(flat), reinterpret_cast<const int32_t *>(pos), n_blocks,
-                                     block_floats, reinterpret_cast<float *>(packed), reinterpret_cast<float *>(check));
-        if (rc != DRT_OK) throw std::runtime_error("drt_grad_pack failed (code " + std::to_string(rc) + ")");
+        ok(drt_grad_pack(ptr<void>(stream), ptr<const float>(flat), ptr<const int32_t>(pos), n_blocks, block_floats, ptr<float>(packed), ptr<float>(check)),
+           "drt_grad_pack");
     });
     m.def("grad_unpack", [](uintptr_t stream, uintptr_t packed, uintptr_t pos, uint64_t n_blocks, uint32_t block_floats, uintptr_t flat) {
-        const int rc = drt_grad_unpack(reinterpret_cast<void *>(stream), reinterpret_cast<const float *>(packed), reinterpret_cast<const int32_t *>(pos), n_blocks,
-                                       block_floats, reinterpret_cast<float *>(flat));
-        if (rc != DRT_OK) throw std::runtime_error("drt_grad_unpack failed (code " + std::to_string(rc) + ")");
+        ok(drt_grad_unpack(ptr<void>(stream), ptr<const float>(packed), ptr<const int32_t>(pos), n_blocks, block_floats, ptr<float>(flat)),
+           "drt_grad_unpack");
     });
     py::class_<Integrator>(m, "Integrator", py::module_local())   // (two flavours of this module can live in one process)
         .def(py::init<const py::dict &, int>(), py::arg("props"), py::arg("device") = 0)
