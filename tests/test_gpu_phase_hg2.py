@@ -453,13 +453,13 @@ def test_refusals_on_a_handle(uivr, gpu):
     gg = torch.zeros((), device=gpu)
     out = torch.zeros((n, 3), device=gpu)
     with pytest.raises(RuntimeError, match="no phase-parameter gradients yet"):
-        h.render_backward_phase(ro, rd, n, 0, spp, 3, dL.data_ptr(), L.data_ptr(), gs.data_ptr(), ga.data_ptr(), gg.data_ptr())
+        h.render_backward(ro, rd, n, 0, spp, 3, dL.data_ptr(), L.data_ptr(), gs.data_ptr(), ga.data_ptr(), grad_phase_g=gg.data_ptr())
     with pytest.raises(RuntimeError, match="no phase-parameter gradients yet"):
-        h.render_backward_px_phase(ro, rd, n, 0, spp, 3, gpix.data_ptr(), n // spp, L.data_ptr(), gs.data_ptr(), ga.data_ptr(), gg.data_ptr())
+        h.render_backward_px(ro, rd, n, 0, spp, 3, gpix.data_ptr(), n // spp, L.data_ptr(), gs.data_ptr(), ga.data_ptr(), grad_phase_g=gg.data_ptr())
     with pytest.raises(RuntimeError, match="no phase-parameter gradients yet"):
-        h.render_forward_phase(ro, rd, n, 0, spp, 3, L.data_ptr(), gs.data_ptr(), ga.data_ptr(), out.data_ptr(), 1.0)
+        h.render_forward(ro, rd, n, 0, spp, 3, L.data_ptr(), gs.data_ptr(), ga.data_ptr(), out.data_ptr(), t_phase_g=1.0)
     assert float(gg) == 0.0 and float(gs.abs().sum()) == 0.0
-    h.render_backward_phase(ro, rd, n, 0, spp, 3, dL.data_ptr(), L.data_ptr(), gs.data_ptr(), ga.data_ptr(), 0)
+    h.render_backward(ro, rd, n, 0, spp, 3, dL.data_ptr(), L.data_ptr(), gs.data_ptr(), ga.data_ptr(), grad_phase_g=0)
     ref = uivr.alloc_grads(sg)
     h.render_backward(ro, rd, n, 0, spp, 3, dL.data_ptr(), L.data_ptr(), ref[uivr.SIGMA_T_KEY].data_ptr(), ref[uivr.ALBEDO_KEY].data_ptr())
     torch.cuda.synchronize()
@@ -468,7 +468,7 @@ def test_refusals_on_a_handle(uivr, gpu):
     # a tangent of zero is the plain forward pass: bit-reproducible
     t = torch.ones_like(gs)
     a, b = torch.zeros((n, 3), device=gpu), torch.zeros((n, 3), device=gpu)
-    h.render_forward_phase(ro, rd, n, 0, spp, 3, L.data_ptr(), t.data_ptr(), 0, a.data_ptr(), 0.0)
+    h.render_forward(ro, rd, n, 0, spp, 3, L.data_ptr(), t.data_ptr(), 0, a.data_ptr(), t_phase_g=0.0)
     h.render_forward(ro, rd, n, 0, spp, 3, L.data_ptr(), t.data_ptr(), 0, b.data_ptr())
     assert torch.equal(a, b) and float(a.abs().sum()) > 0
 

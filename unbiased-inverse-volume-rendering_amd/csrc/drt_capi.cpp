@@ -46,45 +46,43 @@ int fail(drt_handle h, int code, const char *fmt, ...)
     return code;
 }
 
-int check_job(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
-              uint64_t ray_offset, uint32_t spp, bool need_albedo, bool need_emitter)
+int check_job(drt_handle h, const Job &job, bool need_albedo, bool need_emitter)
 {
     if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
     if (!h->have_medium) return fail(h, DRT_ERR_NOT_CONFIGURED, "no medium: call drt_set_medium first");
     if (need_emitter && !h->have_emitter) return fail(h, DRT_ERR_NOT_CONFIGURED, "no emitter: call drt_set_emitter_constant first");
     if (need_albedo && !h->base.albedo) return fail(h, DRT_ERR_NOT_CONFIGURED, "the medium has no albedo grid");
-    if ((rays_o == nullptr) != (rays_d == nullptr))
+    if ((job.rays_o == nullptr) != (job.rays_d == nullptr))
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "rays_o and rays_d must both be given or both be NULL");
-    if (!rays_o && !h->have_sensor)
+    if (!job.rays_o && !h->have_sensor)
         return fail(h, DRT_ERR_NOT_CONFIGURED, "no rays and no sensor: call drt_set_sensor_perspective");
-    if (spp == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "spp must be > 0");
+    if (job.spp == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "spp must be > 0");
     // wavefront size limit of the reference (batched.py:378-388): ray indices are 32-bit
-    uint64_t last = ray_offset + n_rays;   // one past the largest global index
-    if (h->chunk && n_rays)
-        last = ray_offset + ((n_rays - 1) / h->chunk) * h->stride + ((n_rays - 1) % h->chunk) + 1;
+    uint64_t last = job.ray_offset + job.n_rays;   // one past the largest global index
+    if (h->chunk && job.n_rays)
+        last = job.ray_offset + ((job.n_rays - 1) / h->chunk) * h->stride + ((job.n_rays - 1) % h->chunk) + 1;
     if (last > 0xffffffffull)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "global ray index exceeds 2^32 - 1 (render in several passes)");
-    if (!rays_o) {
-        uint64_t total = (uint64_t) h->base.width * (uint64_t) h->base.height * spp;
+    if (!job.rays_o) {
+        uint64_t total = (uint64_t) h->base.width * (uint64_t) h->base.height * job.spp;
         if (last > total)
             return fail(h, DRT_ERR_INVALID_ARGUMENT, "ray range exceeds width*height*spp");
     }
     return DRT_OK;
 }
 
-void fill_job(drt_handle h, drt::Params &P, const float *rays_o, const float *rays_d, uint64_t n_rays,
-              uint64_t ray_offset, uint32_t spp, uint32_t seed)
+void fill_job(drt_handle h, drt::Params &P, const Job &job)
 {
     P = h->base;
     P.majorant = h->d_majorant;
     P.hide_emitters = h->cfg.hide_emitters; P.use_nee = h->cfg.use_nee; P.use_drt = h->cfg.use_drt;
     P.use_drt_subsampling = h->cfg.use_drt_subsampling; P.use_drt_mis = h->cfg.use_drt_mis;
     P.max_depth = h->cfg.max_depth; P.rr_depth = h->cfg.rr_depth;
-    P.sensor_flow = rays_o ? 0 : 1;
-    P.rays_o = rays_o; P.rays_d = rays_d;
-    P.n_rays = n_rays; P.ray_offset = ray_offset; P.spp = spp; P.seed = seed;
+    P.sensor_flow = job.rays_o ? 0 : 1;
+    P.rays_o = job.rays_o; P.rays_d = job.rays_d;
+    P.n_rays = job.n_rays; P.ray_offset = job.ray_offset; P.spp = job.spp; P.seed = job.seed;
     P.chunk = h->chunk; P.stride = h->stride;
-    P.alt_seed = drt::host_alt_seed(seed, rays_o == nullptr);
+    P.alt_seed = drt::host_alt_seed(job.seed, job.rays_o == nullptr);
     P.counters = h->counting ? h->d_counters : nullptr;
     P.debug_flags = h->debug_flags;
     P.order = nullptr; P.order_unit = 1; P.order_units = 0;

@@ -67,7 +67,6 @@ static constexpr NerfVariant kNerfAov = { drt::NerfOut::kAov, "emission", "own-l
 static constexpr NerfVariant kNerfDist = { drt::NerfOut::kDist, "emission", "own-lattice opacity / depth / distortion outputs are not supported",
                                            "distortion", true, false, true, true, 64 };
 
-struct NerfRays { const float *o, *d; uint64_t n, offset; uint32_t spp, seed; };
 enum : unsigned {
     kNerfAdjoint = 1,            // the job is an adjoint: the routing test hooks matter
     kNerfFusedHalf = 2,          // the nerf half of drt_fused_render_*: its rays are counted by the other half, the path cache is that half's
@@ -79,12 +78,12 @@ enum : unsigned {
 // `body(P, S)` then checks the call's own buffers and launches.  `what`: the call's name in its messages
 template <class Body>
 static int nerf_job(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid, const int32_t *sh_degree,
-                    const NerfRays &R, unsigned flags, Body body)
+                    const Job &R, unsigned flags, Body body)
 {
     if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
-    if (R.n == 0 && !(flags & kNerfCheckEmpty)) return DRT_OK;         /* empty batch: nothing to enqueue */
+    if (R.n_rays == 0 && !(flags & kNerfCheckEmpty)) return DRT_OK;         /* empty batch: nothing to enqueue */
     DeviceGuard g(h->device);
-    DRT_TRY(check_job(h, R.o, R.d, R.n, R.offset, R.spp, false));
+    DRT_TRY(check_job(h, R, false));
     if (sh_degree && *sh_degree != 1 && *sh_degree != 2)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: sh_degree must be 1 or 2, got %d", what, (int) *sh_degree);
     if (!cfg || !grid)
@@ -100,7 +99,7 @@ static int nerf_job(drt_handle h, const char *what, const NerfVariant &v, const 
                     (unsigned) (h->debug_flags & kUnhonoured), v.kernels);
     drt::Params P;
     drt::NerfSh S = { nullptr, 0 };
-    fill_job(h, P, R.o, R.d, R.n, R.offset, R.spp, R.seed);
+    fill_job(h, P, R);
     P.nerf_fused_half = (flags & kNerfFusedHalf) ? 1 : 0;
     if (cfg->queries_per_ray < 2) return fail(h, DRT_ERR_INVALID_ARGUMENT, "queries_per_ray must be >= 2");
     P.emission = grid; P.nerf_queries = cfg->queries_per_ray; P.nerf_jitter = cfg->jittering_enabled ? 1 : 0;
@@ -129,7 +128,7 @@ static int nerf_lanes(drt_handle h, int which, const NerfVariant &v, const drt::
 
 // st (the fused pass): the stream of the launch, the handle's otherwise
 static int nerf_run_primal(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid,
-                           const int32_t *sh_degree, const NerfRays &R, float *L_out, unsigned flags = 0, hipStream_t st = nullptr)
+                           const int32_t *sh_degree, const Job &R, float *L_out, unsigned flags = 0, hipStream_t st = nullptr)
 {
     return nerf_job(h, what, v, cfg, grid, sh_degree, R, flags, [&](drt::Params &P, const drt::NerfSh &S) {
         if (!L_out) return v.named ? fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null L_out", what) : fail(h, DRT_ERR_INVALID_ARGUMENT, "null L_out");
@@ -180,13 +179,13 @@ static int nerf_adjoint_launch(drt_handle h, const NerfVariant &v, drt::Params &
 
 // exactly one of dL (per ray) and grad_image with n_pixels (per pixel: the *_backward_px calls) is given
 static int nerf_run_adjoint(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid,
-                            const int32_t *sh_degree, const NerfRays &R, const float *dL, const float *grad_image, const uint64_t *n_pixels,
+                            const int32_t *sh_degree, const Job &R, const float *dL, const float *grad_image, const uint64_t *n_pixels,
                             const float *L_in, float *grad_sigma_t, float *grad_colour, unsigned flags = 0)
 {
     return nerf_job(h, what, v, cfg, grid, sh_degree, R, flags | kNerfAdjoint, [&](drt::Params &P, const drt::NerfSh &S) {
         if ((!n_pixels && !dL) || !L_in || !grad_sigma_t || !grad_colour)
             return fail(h, DRT_ERR_INVALID_ARGUMENT, n_pixels ? "%s: null L_in / gradient buffer" : "%s: null dL / L_in / gradient buffer", what);
-        if (n_pixels) DRT_TRY(check_px(h, what, R.n, R.spp, grad_image, *n_pixels));
+        if (n_pixels) DRT_TRY(check_px(h, what, R.n_rays, R.spp, grad_image, *n_pixels));
         P.dL = n_pixels ? nullptr : dL; P.dL_pix = n_pixels ? grad_image : nullptr;
         P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_colour;
         return nerf_adjoint_launch(h, v, P, S, nerf_adjoint_route(h, v, P), h->stream);
@@ -195,7 +194,7 @@ static int nerf_run_adjoint(drt_handle h, const char *what, const NerfVariant &v
 
 // forward mode: one launch, untimed
 static int nerf_run_forward(drt_handle h, const char *what, const NerfVariant &v, const drt_nerf_config *cfg, const float *grid,
-                            const int32_t *sh_degree, const NerfRays &R, const float *t_sigma_t, const float *t_colour, float *dL_out)
+                            const int32_t *sh_degree, const Job &R, const float *t_sigma_t, const float *t_colour, float *dL_out)
 {
     return nerf_job(h, what, v, cfg, grid, sh_degree, R, 0, [&](drt::Params &P, const drt::NerfSh &S) {
         if (!dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null dL_out", what);
@@ -365,7 +364,7 @@ int drt_fused_render_primal(drt_handle h, const drt_nerf_config *cfg, const floa
                             uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_nerf_out, float *L_drt_out)
 {
     if (h && n_rays == 0) return DRT_OK;
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
+    DRT_TRY(check_job(h, { rays_o, rays_d, n_rays, ray_offset, spp, seed }));
     if (!L_nerf_out || !L_drt_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_fused_render_primal: null output buffer");
     if (!cfg) return fail(h, DRT_ERR_INVALID_ARGUMENT, "fused: null nerf config");
     {
@@ -388,7 +387,7 @@ int drt_fused_render_backward(drt_handle h, const drt_nerf_config *cfg, const fl
                               const float *dL_drt, const float *L_drt_in, float *grad_sigma_t, float *grad_rgb)
 {
     if (h && n_rays == 0) return DRT_OK;
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
+    DRT_TRY(check_job(h, { rays_o, rays_d, n_rays, ray_offset, spp, seed }));
     if (!dL_nerf || !L_nerf_in || !dL_drt || !L_drt_in || !grad_sigma_t || !grad_rgb)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_fused_render_backward: null dL / L_in / gradient buffer");
     TimedSpan whole;

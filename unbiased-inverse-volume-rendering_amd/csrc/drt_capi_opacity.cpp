@@ -11,13 +11,12 @@ using namespace drt::host;
 namespace {
 
 // the checks and the job of an opacity call: a medium is all the handle needs (no phase function, albedo, emitter or colour lattice is read)
-int opacity_job(drt_handle h, const char *what, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
-                uint32_t seed, drt::Params &P)
+int opacity_job(drt_handle h, const char *what, const Job &job, drt::Params &P)
 {
     if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null handle", what);
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp, false, false));
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    P.alt_seed = drt::host_opacity_seed(seed);                   // the walks' streams: PCG32(tea32(opacity_seed, global ray index))
+    DRT_TRY(check_job(h, job, false, false));
+    fill_job(h, P, job);
+    P.alt_seed = drt::host_opacity_seed(job.seed);                   // the walks' streams: PCG32(tea32(opacity_seed, global ray index))
     P.g_albedo = nullptr;
     return DRT_OK;
 }
@@ -34,16 +33,16 @@ uint32_t opacity_records_per_ray(drt_handle h, const drt::Params &P)
     return n < 8.0f ? 8u : n > 128.0f ? 128u : (uint32_t) n;
 }
 
-int opacity_backward(drt_handle h, const char *what, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
-                     uint32_t seed, const float *dA, const float *grad_image, const uint64_t *n_pixels, const float *A_in, float *grad_sigma_t)
+int opacity_backward(drt_handle h, const char *what, const Job &job, const float *dA, const float *grad_image, const uint64_t *n_pixels,
+                     const float *A_in, float *grad_sigma_t)
 {
     drt::Params P;
     if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null handle", what);
-    if (n_rays == 0) return DRT_OK;                              /* empty batch: nothing to enqueue */
+    if (job.n_rays == 0) return DRT_OK;                              /* empty batch: nothing to enqueue */
     if ((!n_pixels && !dA) || !A_in || !grad_sigma_t)
         return fail(h, DRT_ERR_INVALID_ARGUMENT, n_pixels ? "%s: null A_in / grad_sigma_t" : "%s: null dA / A_in / grad_sigma_t", what);
-    DRT_TRY(opacity_job(h, what, rays_o, rays_d, n_rays, ray_offset, spp, seed, P));
-    if (n_pixels) DRT_TRY(check_px(h, what, n_rays, spp, grad_image, *n_pixels));
+    DRT_TRY(opacity_job(h, what, job, P));
+    if (n_pixels) DRT_TRY(check_px(h, what, job.n_rays, job.spp, grad_image, *n_pixels));
     DeviceGuard g(h->device);
     P.dL = n_pixels ? nullptr : dA; P.dL_pix = n_pixels ? grad_image : nullptr;
     P.L_in = A_in; P.g_sigma = grad_sigma_t;
@@ -72,7 +71,7 @@ int drt_transmittance_segments(drt_handle h, const float *o, const float *d, con
     if (n == 0) return DRT_OK;
     DeviceGuard g(h->device);
     drt::Params P;
-    fill_job(h, P, nullptr, nullptr, 0, 0, 1, seed);
+    fill_job(h, P, { nullptr, nullptr, 0, 0, 1, seed });
     DRT_HIP_CHECK(h, drt::launch_transmittance_segments(P, o, d, tmax, n, first_index, seed, T_out, P.counters != nullptr, h->stream));
     return DRT_OK;
 }
@@ -83,7 +82,7 @@ int drt_opacity_primal(drt_handle h, const float *rays_o, const float *rays_d, u
     drt::Params P;
     if (h && n_rays == 0) return DRT_OK;                         /* empty batch: nothing to enqueue (as drt_render_primal) */
     if (h && !A_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_opacity_primal: null A_out");
-    DRT_TRY(opacity_job(h, "drt_opacity_primal", rays_o, rays_d, n_rays, ray_offset, spp, seed, P));
+    DRT_TRY(opacity_job(h, "drt_opacity_primal", { rays_o, rays_d, n_rays, ray_offset, spp, seed }, P));
     if (n_rays == 0) return DRT_OK;
     DeviceGuard g(h->device);
     P.L_out = A_out;
@@ -94,13 +93,13 @@ int drt_opacity_primal(drt_handle h, const float *rays_o, const float *rays_d, u
 int drt_opacity_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp, uint32_t seed,
                          const float *dA, const float *A_in, float *grad_sigma_t)
 {
-    return opacity_backward(h, "drt_opacity_backward", rays_o, rays_d, n_rays, ray_offset, spp, seed, dA, nullptr, nullptr, A_in, grad_sigma_t);
+    return opacity_backward(h, "drt_opacity_backward", { rays_o, rays_d, n_rays, ray_offset, spp, seed }, dA, nullptr, nullptr, A_in, grad_sigma_t);
 }
 
 int drt_opacity_backward_px(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
                             uint32_t seed, const float *grad_image, uint64_t n_pixels, const float *A_in, float *grad_sigma_t)
 {
-    return opacity_backward(h, "drt_opacity_backward_px", rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, &n_pixels, A_in,
+    return opacity_backward(h, "drt_opacity_backward_px", { rays_o, rays_d, n_rays, ray_offset, spp, seed }, nullptr, grad_image, &n_pixels, A_in,
                             grad_sigma_t);
 }
 
@@ -110,7 +109,7 @@ int drt_opacity_forward(drt_handle h, const float *rays_o, const float *rays_d, 
     drt::Params P;
     if (h && n_rays == 0) return DRT_OK;
     if (h && (!A_in || !dA_out)) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_opacity_forward: null A_in / dA_out");
-    DRT_TRY(opacity_job(h, "drt_opacity_forward", rays_o, rays_d, n_rays, ray_offset, spp, seed, P));
+    DRT_TRY(opacity_job(h, "drt_opacity_forward", { rays_o, rays_d, n_rays, ray_offset, spp, seed }, P));
     if (n_rays == 0) return DRT_OK;
     DeviceGuard g(h->device);
     P.L_in = A_in; P.g_sigma = const_cast<float *>(t_sigma_t); P.L_out = dA_out;   // (the tangent grid is read only; nullptr: zero tangent)

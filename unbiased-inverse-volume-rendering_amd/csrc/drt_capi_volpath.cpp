@@ -608,11 +608,12 @@ int drt_render_primal(drt_handle h, const float *rays_o, const float *rays_d, ui
                       uint64_t ray_offset, uint32_t spp, uint32_t seed, float *L_out)
 {
     if (h && n_rays == 0) return DRT_OK;    /* empty batch: nothing to enqueue */
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
+    const Job job = { rays_o, rays_d, n_rays, ray_offset, spp, seed };
+    DRT_TRY(check_job(h, job));
     if (!L_out && n_rays) return fail(h, DRT_ERR_INVALID_ARGUMENT, "null L_out");
     DeviceGuard g(h->device);
     drt::Params P;
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    fill_job(h, P, job);
     P.L_out = L_out;
     h->pcache_sig.valid = false;
     bind_path_cache_write(h, P);                                 // every primal kernel records its walks
@@ -654,21 +655,21 @@ static_assert(kTabReplicas <= drt::kTabMaxReplicas, "tab_sink clamps the replica
 constexpr int kTabCoarseNodes = 255;
 static int tab_replicas(int n_nodes) { return n_nodes <= kTabCoarseNodes ? drt::kTabMaxReplicas : kTabReplicas; }
 
-// the adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel, drt_render_backward_px) is given
-// grad_phase_g (drt_render_backward_phase, an HG handle): dLoss/dg is added to *grad_phase_g - it travels in Params::L_out, which no adjoint
-// kernel otherwise reads or writes, and selects the GG kernels (choose_tracer)
-static int render_backward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
-                           uint32_t seed, const float *dL, const float *dL_pix, const float *L_in, float *grad_sigma_t, float *grad_albedo,
-                           float *grad_phase_g = nullptr, float *grad_tab = nullptr)
+// The adjoint of a checked job; exactly one of dL (per ray) and dL_pix (per pixel, the *_px calls) is given.
+// target kG (an HG handle): dLoss/dg is added to *target.sink - it travels in Params::L_out, which no adjoint kernel otherwise reads or
+// writes, and selects the GG kernels (choose_tracer).
+// target kTab (a tabulated handle): the kTabGrad kernels add to a zeroed sink block of tab_replicas(N) replicas (Params::L_out; the replica
+// count as integer bits in Params::phase_tg), which launch_tab_finalise maps into target.sink behind the launches
+static int render_backward(drt_handle h, const Job &job, const float *dL, const float *dL_pix, const float *L_in, float *grad_sigma_t,
+                           float *grad_albedo, const PhaseTarget &target)
 {
     int rc;
     DeviceGuard g(h->device);
     drt::Params P;
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    fill_job(h, P, job);
     P.dL = dL; P.dL_pix = dL_pix; P.L_in = L_in; P.g_sigma = grad_sigma_t; P.g_albedo = grad_albedo;
-    P.L_out = grad_phase_g;
-    // grad_tab (drt_render_backward_phase_tab, a tabulated handle): the kTabGrad kernels add to a zeroed sink block of tab_replicas(N) replicas
-    // (Params::L_out; the replica count as integer bits in Params::phase_tg), which launch_tab_finalise maps into grad_tab behind the launches
+    P.L_out = target.kind == PhaseTarget::kG ? target.sink : nullptr;
+    float *grad_tab = target.kind == PhaseTarget::kTab ? target.sink : nullptr;
     const int tab_n = grad_tab ? (int) h->tab_values.size() : 0;
     const int tab_r = tab_replicas(tab_n);
     if (grad_tab) {
@@ -681,7 +682,7 @@ static int render_backward(drt_handle h, const float *rays_o, const float *rays_
     }
     // capacity: 48 sigma_t and 6 colour records per ray (headline workload: 12.3 and 1.4); beyond it the
     // tracer falls back to direct atomics (emit_record), so this is a performance choice only
-    const uint64_t job_rays = n_rays;
+    const uint64_t job_rays = job.n_rays;
     rc = run_backward(h, P, 48, 6, [&](drt::Params &Q) {
         bind_path_cache_read(h, Q, job_rays);                    // ... and every adjoint kernel reads them
         return timed_launch(h, 1, Q, true);
@@ -695,31 +696,31 @@ static int render_backward(drt_handle h, const float *rays_o, const float *rays_
     return rc;
 }
 
-// the g-gradient arguments of the *_phase entry points: only an HG handle has a g to differentiate
-static int check_phase_grad(drt_handle h, const char *what, bool wanted)
+// What a call may differentiate on this handle, under the entry point's name.  g: only an HG handle has one (and its tangent is a finite
+// number).  The table values: only a tabulated handle has them, and they must be strictly positive (the score is
+// h_k / (2 pi I p) - m_k / I: p = 0 at an NEE site would make it 0 / 0)
+static int check_phase(drt_handle h, const char *what, const PhaseTarget &target)
 {
-    if (wanted && h->phase_kind == DRT_PHASE_HG2)
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the two-lobe Henyey-Greenstein phase function (drt_set_phase_hg2) has no phase-parameter "
-                                            "gradients yet (g1, g2 and weight)", what);
-    if (wanted && h->phase_kind == DRT_PHASE_TAB)
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the tabulated phase function (drt_set_phase_tab) has no phase-parameter gradients (it has no g, "
-                                            "and gradients with respect to the table values are not built)", what);
-    if (wanted && h->phase_kind != DRT_PHASE_HG)
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the handle's phase function is isotropic - a gradient with respect to g needs the "
-                                            "Henyey-Greenstein phase function (drt_set_phase(DRT_PHASE_HG, 0.0) for an isotropic medium)", what);
-    return DRT_OK;
-}
-
-// the table-value gradient arguments of the *_phase_tab entry points: only a tabulated handle has values to differentiate, and they must be
-// strictly positive (the score is h_k / (2 pi I p) - m_k / I: p = 0 at an NEE site would make it 0 / 0)
-static int check_phase_tab_grad(drt_handle h, const char *what, bool wanted)
-{
-    if (wanted && h->phase_kind != DRT_PHASE_TAB)
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: the handle's phase function is not tabulated - a gradient with respect to the table values needs "
-                                            "drt_set_phase_tab", what);
-    if (wanted && !(h->tab_min > 0.0f))
-        return fail(h, DRT_ERR_UNSUPPORTED, "%s: a differentiated table must be strictly positive (its smallest value is %g)", what,
-                    (double) h->tab_min);
+    if (target.kind == PhaseTarget::kG) {
+        if (!std::isfinite(target.t_g)) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: t_phase_g must be finite", what);
+        if (h->phase_kind == DRT_PHASE_HG2)
+            return fail(h, DRT_ERR_UNSUPPORTED, "%s: the two-lobe Henyey-Greenstein phase function (drt_set_phase_hg2) has no phase-parameter "
+                                                "gradients yet (g1, g2 and weight)", what);
+        if (h->phase_kind == DRT_PHASE_TAB)
+            return fail(h, DRT_ERR_UNSUPPORTED, "%s: the tabulated phase function (drt_set_phase_tab) has no phase-parameter gradients (it has no g, "
+                                                "and gradients with respect to the table values are not built)", what);
+        if (h->phase_kind != DRT_PHASE_HG)
+            return fail(h, DRT_ERR_UNSUPPORTED, "%s: the handle's phase function is isotropic - a gradient with respect to g needs the "
+                                                "Henyey-Greenstein phase function (drt_set_phase(DRT_PHASE_HG, 0.0) for an isotropic medium)", what);
+    }
+    if (target.kind == PhaseTarget::kTab) {
+        if (h->phase_kind != DRT_PHASE_TAB)
+            return fail(h, DRT_ERR_UNSUPPORTED, "%s: the handle's phase function is not tabulated - a gradient with respect to the table values "
+                                                "needs drt_set_phase_tab", what);
+        if (!(h->tab_min > 0.0f))
+            return fail(h, DRT_ERR_UNSUPPORTED, "%s: a differentiated table must be strictly positive (its smallest value is %g)", what,
+                        (double) h->tab_min);
+    }
     return DRT_OK;
 }
 
@@ -736,18 +737,69 @@ void drt::host::forward_params(drt::Params &P, const float *t_sigma, const float
     P.dL = nullptr; P.dL_pix = nullptr; P.gt = nullptr;
 }
 
-// t_phase_g != 0 (drt_render_forward_phase, an HG handle): the kHGGrad kernels, which add t_g dL/dg (Params::phase_tg, in padding of the block)
-static int render_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
-                          uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo, float *dL_out, float t_phase_g)
+// The forward pass of a checked job.
+// target kG (an HG handle): the kHGGrad kernels, which add t_g dL/dg (Params::phase_tg, in padding of the block).
+// target kTab (a tabulated handle; t_tab: N floats on the device): tau_k = t_k / (2 pi I) and kappa = sum t_k m_k / I are prepared on the host
+// in float64 and rounded once (one read-back of N floats per call: the synchronisation is the cost of differentiating the table); tau goes
+// behind the guide words of the table block, kappa into Params::phase_tg, and the kTabGrad kernels run
+static int render_forward(drt_handle h, const Job &job, const float *L_in, const float *t_sigma_t, const float *t_albedo, float *dL_out,
+                          const PhaseTarget &target)
 {
     DeviceGuard g(h->device);
+    float phase_tg = target.t_g;
+    if (target.kind == PhaseTarget::kTab) {
+        const size_t N = h->tab_values.size();
+        std::vector<float> tv(N);
+        DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream));           // (a forward launch in flight may still read the tangent nodes)
+        DRT_HIP_CHECK(h, hipMemcpy(tv.data(), target.t_tab, N * sizeof(float), hipMemcpyDeviceToHost));
+        const double delta = 2.0 / (double) (N - 1), I = h->tab_I, two_pi = 6.283185307179586476925286766559;
+        double kappa = 0.0;
+        for (size_t k = 0; k < N; ++k) {
+            if (!std::isfinite(tv[k])) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase_tab: t_values[%zu] is not finite", k);
+            kappa += (double) tv[k] * ((k == 0 || k + 1 == N) ? 0.5 * delta : delta);
+            tv[k] = (float) ((double) tv[k] / (two_pi * I));
+        }
+        char *tau = reinterpret_cast<char *>(h->d_majorant) + (size_t) drt::kTabOffset * sizeof(float) + N * (2 * sizeof(float) + sizeof(uint32_t));
+        DRT_HIP_CHECK(h, hipMemcpy(tau, tv.data(), N * sizeof(float), hipMemcpyHostToDevice));
+        phase_tg = (float) (kappa / I);
+    }
     drt::Params P;
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
+    fill_job(h, P, job);
     forward_params(P, t_sigma_t, t_albedo, dL_out);
     P.L_in = L_in;
-    if (h->phase_kind != DRT_PHASE_HG2) P.phase_tg = t_phase_g;    // (HG2: its g2 travels in phase_tg, and t_phase_g is 0: check_phase_grad)
-    DRT_HIP_CHECK(h, drt::launch_trace_coop_fwd(P, tracer_phase(h, t_phase_g != 0.0f), h->stream));
+    if (h->phase_kind != DRT_PHASE_HG2) P.phase_tg = phase_tg;     // (HG2: its g2 travels in phase_tg, and nothing is asked of it: check_phase)
+    DRT_HIP_CHECK(h, drt::launch_trace_coop_fwd(P, tracer_phase(h, target.kind != PhaseTarget::kNone), h->stream));
     return DRT_OK;
+}
+
+// ---- the nine adjoint / forward entry points: one order of checks per pass, written here once.  What differs between them is said in the
+// arguments: the entry point's name (`what`, in every message), per-ray dL or the image gradient (n_pixels given: the *_px calls), the
+// phase target, and `empty_first`: drt_render_backward and drt_render_forward return DRT_OK for an empty job BEFORE the job is looked at,
+// as drt_render_primal above does (kept for compatibility: on an unconfigured handle they succeed where the *_phase calls report what is
+// missing); the *_phase calls take that exit behind the job and phase checks, and the *_px calls, drt_render_backward_px included, never
+// take it (check_px refuses their empty job)
+static int backward_entry(drt_handle h, const char *what, bool empty_first, const Job &job, const float *dL, const float *grad_image,
+                          const uint64_t *n_pixels, const float *L_in, float *grad_sigma_t, float *grad_albedo, const PhaseTarget &target)
+{
+    if (empty_first && h && job.n_rays == 0) return DRT_OK;
+    DRT_TRY(check_job(h, job));
+    DRT_TRY(check_phase(h, what, target));
+    if (!n_pixels && job.n_rays == 0) return DRT_OK;
+    if ((!n_pixels && !dL) || !L_in || !grad_sigma_t || !grad_albedo)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, n_pixels ? "%s: null L_in / gradient buffer" : "%s: null dL / L_in / gradient buffer", what);
+    if (n_pixels) DRT_TRY(check_px(h, what, job.n_rays, job.spp, grad_image, *n_pixels));
+    return render_backward(h, job, n_pixels ? nullptr : dL, n_pixels ? grad_image : nullptr, L_in, grad_sigma_t, grad_albedo, target);
+}
+
+static int forward_entry(drt_handle h, const char *what, bool empty_first, const Job &job, const float *L_in, const float *t_sigma_t,
+                         const float *t_albedo, float *dL_out, const PhaseTarget &target)
+{
+    if (empty_first && h && job.n_rays == 0) return DRT_OK;
+    DRT_TRY(check_job(h, job));
+    DRT_TRY(check_phase(h, what, target));
+    if (job.n_rays == 0) return DRT_OK;
+    if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "%s: null L_in / dL_out", what);
+    return render_forward(h, job, L_in, t_sigma_t, t_albedo, dL_out, target);
 }
 
 extern "C" {
@@ -756,127 +808,69 @@ int drt_render_backward(drt_handle h, const float *rays_o, const float *rays_d, 
                         uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *dL,
                         const float *L_in, float *grad_sigma_t, float *grad_albedo)
 {
-    if (h && n_rays == 0) return DRT_OK;
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
-    if (n_rays && (!dL || !L_in || !grad_sigma_t || !grad_albedo))
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward: null dL / L_in / gradient buffer");
-    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo);
+    return backward_entry(h, "drt_render_backward", true, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, dL, nullptr, nullptr, L_in,
+                          grad_sigma_t, grad_albedo, {});
 }
 
 int drt_render_backward_px(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
                            uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
                            const float *L_in, float *grad_sigma_t, float *grad_albedo)
 {
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
-    if (!L_in || !grad_sigma_t || !grad_albedo)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_px: null L_in / gradient buffer");
-    DRT_TRY(check_px(h, "drt_render_backward_px", n_rays, spp, grad_image, n_pixels));
-    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo);
+    return backward_entry(h, "drt_render_backward_px", false, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, nullptr, grad_image, &n_pixels,
+                          L_in, grad_sigma_t, grad_albedo, {});
 }
 
 int drt_render_backward_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
                               uint32_t seed, const float *dL, const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g)
 {
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
-    DRT_TRY(check_phase_grad(h, "drt_render_backward_phase", grad_phase_g != nullptr));
-    if (n_rays == 0) return DRT_OK;
-    if (!dL || !L_in || !grad_sigma_t || !grad_albedo)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_phase: null dL / L_in / gradient buffer");
-    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo, grad_phase_g);
+    return backward_entry(h, "drt_render_backward_phase", false, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, dL, nullptr, nullptr, L_in,
+                          grad_sigma_t, grad_albedo, PhaseTarget::g_sink(grad_phase_g));
 }
 
 int drt_render_backward_px_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
                                  uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
                                  const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_phase_g)
 {
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
-    DRT_TRY(check_phase_grad(h, "drt_render_backward_px_phase", grad_phase_g != nullptr));
-    if (!L_in || !grad_sigma_t || !grad_albedo)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_px_phase: null L_in / gradient buffer");
-    DRT_TRY(check_px(h, "drt_render_backward_px_phase", n_rays, spp, grad_image, n_pixels));
-    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo,
-                           grad_phase_g);
+    return backward_entry(h, "drt_render_backward_px_phase", false, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, nullptr, grad_image,
+                          &n_pixels, L_in, grad_sigma_t, grad_albedo, PhaseTarget::g_sink(grad_phase_g));
 }
 
 int drt_render_backward_phase_tab(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset, uint32_t spp,
                                   uint32_t seed, const float *dL, const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_values)
 {
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
-    DRT_TRY(check_phase_tab_grad(h, "drt_render_backward_phase_tab", grad_values != nullptr));
-    if (n_rays == 0) return DRT_OK;
-    if (!dL || !L_in || !grad_sigma_t || !grad_albedo)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_phase_tab: null dL / L_in / gradient buffer");
-    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, dL, nullptr, L_in, grad_sigma_t, grad_albedo, nullptr, grad_values);
+    return backward_entry(h, "drt_render_backward_phase_tab", false, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, dL, nullptr, nullptr, L_in,
+                          grad_sigma_t, grad_albedo, PhaseTarget::tab_sink(grad_values));
 }
 
 int drt_render_backward_px_phase_tab(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
                                      uint64_t ray_offset, uint32_t spp, uint32_t seed, const float *grad_image, uint64_t n_pixels,
                                      const float *L_in, float *grad_sigma_t, float *grad_albedo, float *grad_values)
 {
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
-    DRT_TRY(check_phase_tab_grad(h, "drt_render_backward_px_phase_tab", grad_values != nullptr));
-    if (!L_in || !grad_sigma_t || !grad_albedo)
-        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_backward_px_phase_tab: null L_in / gradient buffer");
-    DRT_TRY(check_px(h, "drt_render_backward_px_phase_tab", n_rays, spp, grad_image, n_pixels));
-    return render_backward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, nullptr, grad_image, L_in, grad_sigma_t, grad_albedo, nullptr,
-                           grad_values);
+    return backward_entry(h, "drt_render_backward_px_phase_tab", false, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, nullptr, grad_image,
+                          &n_pixels, L_in, grad_sigma_t, grad_albedo, PhaseTarget::tab_sink(grad_values));
 }
 
 int drt_render_forward(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
                        uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
                        float *dL_out)
 {
-    if (h && n_rays == 0) return DRT_OK;
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
-    if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward: null L_in / dL_out");
-    return render_forward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_in, t_sigma_t, t_albedo, dL_out, 0.0f);
+    return forward_entry(h, "drt_render_forward", true, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, L_in, t_sigma_t, t_albedo, dL_out, {});
 }
 
 int drt_render_forward_phase(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
                              uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
                              float *dL_out, float t_phase_g)
 {
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
-    if (!std::isfinite(t_phase_g)) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase: t_phase_g must be finite");
-    DRT_TRY(check_phase_grad(h, "drt_render_forward_phase", t_phase_g != 0.0f));
-    if (n_rays == 0) return DRT_OK;
-    if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase: null L_in / dL_out");
-    return render_forward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_in, t_sigma_t, t_albedo, dL_out, t_phase_g);
+    return forward_entry(h, "drt_render_forward_phase", false, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, L_in, t_sigma_t, t_albedo,
+                         dL_out, PhaseTarget::g_tangent(t_phase_g));
 }
 
-// t_values (device, N floats): the tangent of the table values.  tau_k = t_k / (2 pi I) and kappa = sum t_k m_k / I are prepared on the host in
-// float64 and rounded once (one read-back of N floats per call: the synchronisation is the cost of differentiating the table); tau goes behind
-// the guide words of the table block, kappa into Params::phase_tg, and the kTabGrad forward kernels run
 int drt_render_forward_phase_tab(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays, uint64_t ray_offset,
                                  uint32_t spp, uint32_t seed, const float *L_in, const float *t_sigma_t, const float *t_albedo,
                                  float *dL_out, const float *t_values)
 {
-    DRT_TRY(check_job(h, rays_o, rays_d, n_rays, ray_offset, spp));
-    DRT_TRY(check_phase_tab_grad(h, "drt_render_forward_phase_tab", t_values != nullptr));
-    if (n_rays == 0) return DRT_OK;
-    if (!L_in || !dL_out) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase_tab: null L_in / dL_out");
-    if (!t_values) return render_forward(h, rays_o, rays_d, n_rays, ray_offset, spp, seed, L_in, t_sigma_t, t_albedo, dL_out, 0.0f);
-    DeviceGuard g(h->device);
-    const size_t N = h->tab_values.size();
-    std::vector<float> tv(N);
-    DRT_HIP_CHECK(h, hipStreamSynchronize(h->stream));           // (a forward launch in flight may still read the tangent nodes)
-    DRT_HIP_CHECK(h, hipMemcpy(tv.data(), t_values, N * sizeof(float), hipMemcpyDeviceToHost));
-    const double delta = 2.0 / (double) (N - 1), I = h->tab_I, two_pi = 6.283185307179586476925286766559;
-    double kappa = 0.0;
-    for (size_t k = 0; k < N; ++k) {
-        if (!std::isfinite(tv[k])) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_render_forward_phase_tab: t_values[%zu] is not finite", k);
-        kappa += (double) tv[k] * ((k == 0 || k + 1 == N) ? 0.5 * delta : delta);
-        tv[k] = (float) ((double) tv[k] / (two_pi * I));
-    }
-    char *tau = reinterpret_cast<char *>(h->d_majorant) + (size_t) drt::kTabOffset * sizeof(float) + N * (2 * sizeof(float) + sizeof(uint32_t));
-    DRT_HIP_CHECK(h, hipMemcpy(tau, tv.data(), N * sizeof(float), hipMemcpyHostToDevice));
-    drt::Params P;
-    fill_job(h, P, rays_o, rays_d, n_rays, ray_offset, spp, seed);
-    forward_params(P, t_sigma_t, t_albedo, dL_out);
-    P.L_in = L_in;
-    P.phase_tg = (float) (kappa / I);
-    DRT_HIP_CHECK(h, drt::launch_trace_coop_fwd(P, drt::Phase::kTabGrad, h->stream));
-    return DRT_OK;
+    return forward_entry(h, "drt_render_forward_phase_tab", false, { rays_o, rays_d, n_rays, ray_offset, spp, seed }, L_in, t_sigma_t, t_albedo,
+                         dL_out, PhaseTarget::tab_tangent(t_values));
 }
 
 }  // extern "C"

@@ -147,11 +147,27 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void) hipSetDevice(prev); }
 };
 
+// One job over rays, as every render entry point of the C ABI takes it: explicit rays (or none: the handle's sensor makes them), their
+// count and place in the global wavefront, samples per pixel, the sampler's seed
+struct Job { const float *rays_o, *rays_d; uint64_t n_rays, ray_offset; uint32_t spp, seed; };
+
+// What a volpathsimple adjoint or forward call differentiates besides the two grids: nothing, the Henyey-Greenstein g, or the values of a
+// tabulated phase function.  The adjoint adds to `sink` (device: one float / N floats); forward mode reads the tangent, `t_g` by value or
+// `t_tab` (device, N floats).  A NULL sink, a zero t_g and a NULL t_tab ask for nothing: the plain call's work
+struct PhaseTarget {
+    enum Kind { kNone, kG, kTab } kind = kNone;
+    float *sink = nullptr;
+    float t_g = 0.0f;
+    const float *t_tab = nullptr;
+    static PhaseTarget g_sink(float *p) { return { p ? kG : kNone, p, 0.0f, nullptr }; }
+    static PhaseTarget tab_sink(float *p) { return { p ? kTab : kNone, p, 0.0f, nullptr }; }
+    static PhaseTarget g_tangent(float t) { return { t != 0.0f ? kG : kNone, nullptr, t, nullptr }; }   // (NaN != 0: refused by the check)
+    static PhaseTarget tab_tangent(const float *t) { return { t ? kTab : kNone, nullptr, 0.0f, t }; }
+};
+
 // the checks and the parameter block of one job over rays (drt_capi.cpp)
-int check_job(drt_handle h, const float *rays_o, const float *rays_d, uint64_t n_rays,
-              uint64_t ray_offset, uint32_t spp, bool need_albedo = true, bool need_emitter = true);
-void fill_job(drt_handle h, drt::Params &P, const float *rays_o, const float *rays_d, uint64_t n_rays,
-              uint64_t ray_offset, uint32_t spp, uint32_t seed);
+int check_job(drt_handle h, const Job &job, bool need_albedo = true, bool need_emitter = true);
+void fill_job(drt_handle h, drt::Params &P, const Job &job);
 // the pixel-gradient arguments of drt_*render_backward_px (drt_capi.cpp)
 int check_px(drt_handle h, const char *what, uint64_t n_rays, uint32_t spp, const float *grad_image, uint64_t n_pixels);
 

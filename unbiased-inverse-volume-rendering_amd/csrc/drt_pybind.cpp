@@ -111,28 +111,40 @@ public:
     {
         nogil("drt_render_primal", [&] { return drt_render_primal(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<float>(L_out)); });
     }
-    void render_backward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp,
-                         uint32_t seed, uintptr_t dL, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo)
+    // The volpathsimple adjoint and forward calls.  grad_phase_g / grad_phase_tab (device addresses, 0: none) and t_phase_g / t_phase_tab pick
+    // the C function: the table's if it is given, else g's if it is given, else the plain one - whose name the error then carries
+    void render_backward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dL, uintptr_t L_in,
+                         uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_phase, uintptr_t g_tab)
     {
-        nogil("drt_render_backward", [&] {
-            return drt_render_backward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
-                                       ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo));
+        const float *ro = ptr<const float>(rays_o), *rd = ptr<const float>(rays_d), *d = ptr<const float>(dL), *Li = ptr<const float>(L_in);
+        float *gs = ptr<float>(g_sigma), *ga = ptr<float>(g_albedo);
+        nogil(g_tab ? "drt_render_backward_phase_tab" : g_phase ? "drt_render_backward_phase" : "drt_render_backward", [&] {
+            return g_tab   ? drt_render_backward_phase_tab(h_, ro, rd, n, off, spp, seed, d, Li, gs, ga, ptr<float>(g_tab))
+                 : g_phase ? drt_render_backward_phase(h_, ro, rd, n, off, spp, seed, d, Li, gs, ga, ptr<float>(g_phase))
+                           : drt_render_backward(h_, ro, rd, n, off, spp, seed, d, Li, gs, ga);
         });
     }
-    void render_backward_phase(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dL,
-                               uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_phase)
+    void render_backward_px(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t grad_image,
+                            uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_phase, uintptr_t g_tab)
     {
-        nogil("drt_render_backward_phase", [&] {
-            return drt_render_backward_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
-                                             ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo), ptr<float>(g_phase));
+        const float *ro = ptr<const float>(rays_o), *rd = ptr<const float>(rays_d), *gi = ptr<const float>(grad_image), *Li = ptr<const float>(L_in);
+        float *gs = ptr<float>(g_sigma), *ga = ptr<float>(g_albedo);
+        nogil(g_tab ? "drt_render_backward_px_phase_tab" : g_phase ? "drt_render_backward_px_phase" : "drt_render_backward_px", [&] {
+            return g_tab   ? drt_render_backward_px_phase_tab(h_, ro, rd, n, off, spp, seed, gi, n_pixels, Li, gs, ga, ptr<float>(g_tab))
+                 : g_phase ? drt_render_backward_px_phase(h_, ro, rd, n, off, spp, seed, gi, n_pixels, Li, gs, ga, ptr<float>(g_phase))
+                           : drt_render_backward_px(h_, ro, rd, n, off, spp, seed, gi, n_pixels, Li, gs, ga);
         });
     }
-    void render_backward_phase_tab(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t dL,
-                                   uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_values)
+    void render_forward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
+                        uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out, float t_phase, uintptr_t t_tab)
     {
-        nogil("drt_render_backward_phase_tab", [&] {
-            return drt_render_backward_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(dL),
-                                                 ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo), ptr<float>(g_values));
+        const float *ro = ptr<const float>(rays_o), *rd = ptr<const float>(rays_d), *Li = ptr<const float>(L_in);
+        const float *ts = ptr<const float>(t_sigma), *ta = ptr<const float>(t_albedo);
+        float *dL = ptr<float>(dL_out);
+        nogil(t_tab ? "drt_render_forward_phase_tab" : t_phase != 0.0f ? "drt_render_forward_phase" : "drt_render_forward", [&] {
+            return t_tab           ? drt_render_forward_phase_tab(h_, ro, rd, n, off, spp, seed, Li, ts, ta, dL, ptr<const float>(t_tab))
+                 : t_phase != 0.0f ? drt_render_forward_phase(h_, ro, rd, n, off, spp, seed, Li, ts, ta, dL, t_phase)
+                                   : drt_render_forward(h_, ro, rd, n, off, spp, seed, Li, ts, ta, dL);
         });
     }
     static drt_nerf_config nerf_cfg(const py::dict &p)
@@ -208,30 +220,6 @@ public:
                              : drt_nerf_render_forward(h_, c, g, ro, rd, n, off, spp, seed, ts, tc, dL);
         });
     }
-    void render_forward(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
-                        uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out)
-    {
-        nogil("drt_render_forward", [&] {
-            return drt_render_forward(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
-                                      ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out));
-        });
-    }
-    void render_forward_phase(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
-                              uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out, float t_phase)
-    {
-        nogil("drt_render_forward_phase", [&] {
-            return drt_render_forward_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
-                                            ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), t_phase);
-        });
-    }
-    void render_forward_phase_tab(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed, uintptr_t L_in,
-                                  uintptr_t t_sigma, uintptr_t t_albedo, uintptr_t dL_out, uintptr_t t_values)
-    {
-        nogil("drt_render_forward_phase_tab", [&] {
-            return drt_render_forward_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(L_in),
-                                                ptr<const float>(t_sigma), ptr<const float>(t_albedo), ptr<float>(dL_out), ptr<const float>(t_values));
-        });
-    }
     void fused_render_primal(const py::dict &props, uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp,
                              uint32_t seed, uintptr_t L_nerf, uintptr_t L_drt)
     {
@@ -299,32 +287,6 @@ public:
         const drt_loss_ref r = loss_ref(dense, images, shape, sensor_idx, pixel_idx);
         nogil("drt_film_loss_grad", [&] {
             return drt_film_loss_grad(h_, ptr<const float>(image), n_pixels, &r, kind, param, ptr<const float>(upstream), ptr<float>(grad_image));
-        });
-    }
-    void render_backward_px(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed,
-                            uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo)
-    {
-        nogil("drt_render_backward_px", [&] {
-            return drt_render_backward_px(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed, ptr<const float>(grad_image),
-                                          n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma), ptr<float>(g_albedo));
-        });
-    }
-    void render_backward_px_phase(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed,
-                                  uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_phase)
-    {
-        nogil("drt_render_backward_px_phase", [&] {
-            return drt_render_backward_px_phase(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
-                                                ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
-                                                ptr<float>(g_albedo), ptr<float>(g_phase));
-        });
-    }
-    void render_backward_px_phase_tab(uintptr_t rays_o, uintptr_t rays_d, uint64_t n, uint64_t off, uint32_t spp, uint32_t seed,
-                                      uintptr_t grad_image, uint64_t n_pixels, uintptr_t L_in, uintptr_t g_sigma, uintptr_t g_albedo, uintptr_t g_values)
-    {
-        nogil("drt_render_backward_px_phase_tab", [&] {
-            return drt_render_backward_px_phase_tab(h_, ptr<const float>(rays_o), ptr<const float>(rays_d), n, off, spp, seed,
-                                                    ptr<const float>(grad_image), n_pixels, ptr<const float>(L_in), ptr<float>(g_sigma),
-                                                    ptr<float>(g_albedo), ptr<float>(g_values));
         });
     }
     void film_develop_n(uintptr_t L, uint64_t n_pixels, uint32_t spp, uint32_t channels, uintptr_t image)
@@ -516,16 +478,14 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("set_emitter_envmap", &Integrator::set_emitter_envmap)
         .def("set_sensor_perspective", &Integrator::set_sensor_perspective)
         .def("render_primal", &Integrator::render_primal)
-        .def("render_backward", &Integrator::render_backward)
-        .def("render_backward_phase", &Integrator::render_backward_phase)
-        .def("render_forward_phase", &Integrator::render_forward_phase)
-        .def("render_backward_px_phase", &Integrator::render_backward_px_phase)
-        .def("render_backward_phase_tab", &Integrator::render_backward_phase_tab)
-        .def("render_forward_phase_tab", &Integrator::render_forward_phase_tab)
-        .def("render_backward_px_phase_tab", &Integrator::render_backward_px_phase_tab)
+        .def("render_backward", &Integrator::render_backward, py::arg("rays_o"), py::arg("rays_d"), py::arg("n_rays"), py::arg("ray_offset"),
+             py::arg("spp"), py::arg("seed"), py::arg("dL"), py::arg("L_in"), py::arg("grad_sigma_t"), py::arg("grad_albedo"),
+             py::arg("grad_phase_g") = 0, py::arg("grad_phase_tab") = 0)
         .def("nerf_render_primal", &Integrator::nerf_render_primal)
         .def("nerf_render_backward", &Integrator::nerf_render_backward)
-        .def("render_forward", &Integrator::render_forward)
+        .def("render_forward", &Integrator::render_forward, py::arg("rays_o"), py::arg("rays_d"), py::arg("n_rays"), py::arg("ray_offset"),
+             py::arg("spp"), py::arg("seed"), py::arg("L_in"), py::arg("t_sigma_t"), py::arg("t_albedo"), py::arg("dL_out"),
+             py::arg("t_phase_g") = 0.0f, py::arg("t_phase_tab") = 0)
         .def("nerf_render_forward", &Integrator::nerf_render_forward)
         .def("fused_render_primal", &Integrator::fused_render_primal)
         .def("fused_render_backward", &Integrator::fused_render_backward)
@@ -539,7 +499,9 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("film_backward", &Integrator::film_backward)
         .def("film_loss_forward", &Integrator::film_loss_forward)
         .def("film_loss_grad", &Integrator::film_loss_grad)
-        .def("render_backward_px", &Integrator::render_backward_px)
+        .def("render_backward_px", &Integrator::render_backward_px, py::arg("rays_o"), py::arg("rays_d"), py::arg("n_rays"),
+             py::arg("ray_offset"), py::arg("spp"), py::arg("seed"), py::arg("grad_image"), py::arg("n_pixels"), py::arg("L_in"),
+             py::arg("grad_sigma_t"), py::arg("grad_albedo"), py::arg("grad_phase_g") = 0, py::arg("grad_phase_tab") = 0)
         .def("nerf_render_backward_px", &Integrator::nerf_render_backward_px)
         .def("nerf_sh_tile_phases", &Integrator::nerf_sh_tile_phases)
         .def("film_develop_n", &Integrator::film_develop_n)

@@ -117,24 +117,50 @@ class _DeviceIntegrator:
     param_keys = (SIGMA_T_KEY, ALBEDO_KEY)       # the differentiable grids this integrator reads
     phase_grad = False                           # differentiable with respect to the phase function's g (PHASE_G_KEY) as well
     needs_albedo = True
+    channels = 3                                 # floats per ray and pixel; more with the outputs a subclass adds behind the colour ...
+    wide_film = ""                               # ... and what the film's errors call the property that added them
+
+    def __init__(self):
+        # per device index: the native handle, and what it is bound to (the entries hold the bound tensors, see _bind)
+        self._handles: Dict[int, object] = {}
+        self._bound: Dict[int, tuple] = {}
+        self._bound_emitter: Dict[int, tuple] = {}
+        self._bound_phase: Dict[int, tuple] = {}
 
     def _native_props(self) -> dict:
         raise NotImplementedError
 
-    # -- film helpers (hdrfilm + box filter, batched.py:176-197 / 298-306) -----
+    # -- film helpers (hdrfilm + box filter, batched.py:176-197 / 298-306) over the integrator's channel count: drt_film_*, and
+    #    drt_film_*_n with `channels` interleaved channels for a wider film -----
     def develop(self, scene: Scene, L: torch.Tensor, spp: int) -> torch.Tensor:
         h, dev = self._bind(scene)
+        C = self.channels
+        if C != 3:
+            _check(L, None, dev, "L")
+            if L.dim() != 2 or L.shape[1] != C:
+                raise ValueError(f"develop: with {self.wide_film} the radiance must have shape [n, {C}], got {tuple(L.shape)}")
         n_pix = L.shape[0] // spp
-        img = torch.empty((n_pix, 3), dtype=torch.float32, device=dev)
-        h.film_develop(L.data_ptr(), n_pix, int(spp), img.data_ptr())
+        img = torch.empty((n_pix, C), dtype=torch.float32, device=dev)
+        if C == 3:
+            h.film_develop(L.data_ptr(), n_pix, int(spp), img.data_ptr())
+        else:
+            h.film_develop_n(L.data_ptr(), n_pix, int(spp), C, img.data_ptr())
         return img
 
     def film_backward(self, scene: Scene, grad_image: torch.Tensor, spp: int) -> torch.Tensor:
         h, dev = self._bind(scene)
-        grad_image = grad_image.contiguous().view(-1, 3)
+        C = self.channels
+        if C != 3 and grad_image.shape[-1] != C:
+            raise ValueError(f"film_backward: with {self.wide_film} the image gradient must have {C} channels, got {tuple(grad_image.shape)}")
+        grad_image = grad_image.contiguous().view(-1, C)
+        if C != 3:
+            _check(grad_image, None, dev, "grad_image")
         n_pix = grad_image.shape[0]
-        dL = torch.empty((n_pix * spp, 3), dtype=torch.float32, device=dev)
-        h.film_backward(grad_image.data_ptr(), n_pix, int(spp), dL.data_ptr())
+        dL = torch.empty((n_pix * spp, C), dtype=torch.float32, device=dev)
+        if C == 3:
+            h.film_backward(grad_image.data_ptr(), n_pix, int(spp), dL.data_ptr())
+        else:
+            h.film_backward_n(grad_image.data_ptr(), n_pix, int(spp), C, dL.data_ptr())
         return dL
 
     # -- loss-fused film (drt_film_loss_*, csrc/drt_loss.hip): `ref` = loss_fused.LossRef ----------------------
@@ -212,25 +238,42 @@ class _DeviceIntegrator:
                              "(a table with a differentiable analytic lobe beside it is a follow-up)")
         require_tab(scene, self.__class__.__name__)
 
-    def _phase_tab_grad_ptr(self, scene: Scene, grads: Dict[str, torch.Tensor], dev) -> int:
-        """The device address of grads[PHASE_TAB_KEY] (N float32, accumulated), or 0 when the table gradient is not asked for."""
-        gv = grads.get(PHASE_TAB_KEY)
-        if gv is None:
-            return 0
-        self._refuse_phase_tab_grad(scene, grads.get(PHASE_G_KEY) is not None)
-        _check(gv, (len(scene.medium.phase),), dev, f"grads['{PHASE_TAB_KEY}']")
-        return gv.data_ptr()
+    def _refuse_phase_grads(self, scene: Scene, wanted, keys=()) -> bool:
+        """The phase derivatives a call asks for - entries of the `grads` / `tangents` mapping `wanted` (None: no mapping) or names among
+        `keys` -, refused on the host before any handle exists where they are not built.  -> the table's is among them."""
+        want_g = PHASE_G_KEY in keys or (wanted is not None and wanted.get(PHASE_G_KEY) is not None)
+        want_tab = PHASE_TAB_KEY in keys or (wanted is not None and wanted.get(PHASE_TAB_KEY) is not None)
+        if want_g:
+            self._refuse_phase_grad(scene)
+        if want_tab:
+            self._refuse_phase_tab_grad(scene, want_g)
+        return want_tab
 
-    def _phase_grad_ptr(self, scene: Scene, grads: Dict[str, torch.Tensor], dev) -> int:
-        """The device address of grads[PHASE_G_KEY] (one float32, accumulated), or 0 when the g-gradient is not asked for."""
-        gg = grads.get(PHASE_G_KEY)
-        if gg is None:
-            return 0
-        self._refuse_phase_grad(scene)
-        _check(gg, None, dev, f"grads['{PHASE_G_KEY}']")
-        if gg.numel() != 1:
-            raise ValueError(f"grads['{PHASE_G_KEY}'] must hold one float, got shape {tuple(gg.shape)}")
-        return gg.data_ptr()
+    def _check_adjoint(self, scene: Scene, dev, n: int, lead: torch.Tensor, lead_rows: int, lead_name: str, state_in: torch.Tensor,
+                       grads: Dict[str, torch.Tensor]):
+        """The adjoint's arguments, in the order sample(Backward) and sample_backward_px refuse them: `lead` - δL [n, C] or grad_image
+        [n / spp, C] -, state_in [n, C], then the gradient grids of `param_keys`, shaped like their parameters.  -> the two grids."""
+        C = self.channels
+        _check(lead, (lead_rows, C), dev, lead_name)
+        _check(state_in, (n, C), dev, "state_in")
+        k0, k1 = self.param_keys
+        g0, g1 = grads[k0], grads[k1]
+        _check(g0, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
+        _check(g1, tuple(self._colour_grid(scene).shape), dev, "grads[emission]" if k1 == EMISSION_KEY else "grads[albedo]")
+        return g0, g1
+
+    @staticmethod
+    def _phase_sinks(scene: Scene, grads: Dict[str, torch.Tensor], dev) -> Tuple[int, int]:
+        """The device addresses of grads[PHASE_G_KEY] (one float32) and grads[PHASE_TAB_KEY] (N float32), both accumulated; 0 where the
+        gradient is not asked for (_refuse_phase_grads has looked at the scene already)."""
+        gg, gv = grads.get(PHASE_G_KEY), grads.get(PHASE_TAB_KEY)
+        if gg is not None:
+            _check(gg, None, dev, f"grads['{PHASE_G_KEY}']")
+            if gg.numel() != 1:
+                raise ValueError(f"grads['{PHASE_G_KEY}'] must hold one float, got shape {tuple(gg.shape)}")
+        if gv is not None:
+            _check(gv, (len(scene.medium.phase),), dev, f"grads['{PHASE_TAB_KEY}']")
+        return _ptr(gg), _ptr(gv)
 
     def _colour_grid(self, scene: Scene):
         """The colour grid whose lattice the handle is told about (drt_set_colour_resolution): the albedo here, the emission for `nerf`."""
@@ -344,6 +387,12 @@ class _DeviceIntegrator:
             return n, ray.o.data_ptr(), ray.d.data_ptr()
         return n, 0, 0
 
+    @classmethod
+    def _job(cls, ray: RayBatch, sampler: IndependentSampler, dev) -> tuple:
+        """(rays_o, rays_d, n_rays, ray_offset, spp, seed): the arguments every render call of the handle starts with."""
+        n, ro, rd = cls._ray_ptrs(ray, dev)
+        return ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value
+
 
 def _grid_of(scene: Scene, key: str):
     m = scene.medium
@@ -370,6 +419,7 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
     sigma_t alone: the albedo and phase-function gradients come from the colour channels only.
     """
     phase_grad = True
+    wide_film = "opacity"
 
     def __init__(self, props: Optional[dict] = None):
         props = dict(props or {})
@@ -386,50 +436,17 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
         self.rr_depth = int(props.get("rr_depth", 5))
         if self.max_depth < 0:
             raise ValueError("max_depth must be >= 0 (unbounded depth is not supported)")
-        self._handles: Dict[int, object] = {}
-        self._bound: Dict[int, tuple] = {}
-        self._bound_emitter: Dict[int, tuple] = {}
-        self._bound_phase: Dict[int, tuple] = {}
+        self.channels = 3 + len(self.aovs())        # floats per ray and pixel: 3, 4 with `opacity`
+        super().__init__()
 
     # -- reference surface ---------------------------------------------------
     def aovs(self):
         return ["opacity"] if self._opacity else []
 
-    @property
-    def channels(self) -> int:
-        """Floats per ray and pixel: 3, 4 with `opacity`."""
-        return 3 + len(self.aovs())
-
     def props(self) -> dict:
         return dict(hide_emitters=self.hide_emitters, use_nee=self.use_nee, use_drt=self.use_drt,
                     use_drt_subsampling=self.use_drt_subsampling, use_drt_mis=self.use_drt_mis,
                     max_depth=self.max_depth, rr_depth=self.rr_depth, **({"opacity": True} if self._opacity else {}))
-
-    # -- film with the integrator's channel count (opacity: drt_film_*_n with four interleaved channels) -----
-    def develop(self, scene: Scene, L: torch.Tensor, spp: int) -> torch.Tensor:
-        if not self._opacity:
-            return super().develop(scene, L, spp)
-        h, dev = self._bind(scene)
-        _check(L, None, dev, "L")
-        if L.dim() != 2 or L.shape[1] != 4:
-            raise ValueError(f"develop: with opacity the radiance must have shape [n, 4], got {tuple(L.shape)}")
-        n_pix = L.shape[0] // spp
-        img = torch.empty((n_pix, 4), dtype=torch.float32, device=dev)
-        h.film_develop_n(L.data_ptr(), n_pix, int(spp), 4, img.data_ptr())
-        return img
-
-    def film_backward(self, scene: Scene, grad_image: torch.Tensor, spp: int) -> torch.Tensor:
-        if not self._opacity:
-            return super().film_backward(scene, grad_image, spp)
-        h, dev = self._bind(scene)
-        if grad_image.shape[-1] != 4:
-            raise ValueError(f"film_backward: with opacity the image gradient must have 4 channels, got {tuple(grad_image.shape)}")
-        grad_image = grad_image.contiguous().view(-1, 4)
-        _check(grad_image, None, dev, "grad_image")
-        n_pix = grad_image.shape[0]
-        dL = torch.empty((n_pix * spp, 4), dtype=torch.float32, device=dev)
-        h.film_backward_n(grad_image.data_ptr(), n_pix, int(spp), 4, dL.data_ptr())
-        return dL
 
     def develop_loss(self, *args, **kwargs):
         if self._opacity:
@@ -456,18 +473,15 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
             tangents = self.check_tangents(scene, tangents)
             if state_in is None:
                 raise ValueError("sample(Forward) needs state_in (the primal radiance of the same rays and seed)")
-        if mode == ADMode.Backward and grads is not None and grads.get(PHASE_G_KEY) is not None:
-            self._refuse_phase_grad(scene)          # (before any device work: a medium without a differentiable g)
-        if mode == ADMode.Backward and grads is not None and grads.get(PHASE_TAB_KEY) is not None:
-            self._refuse_phase_tab_grad(scene, grads.get(PHASE_G_KEY) is not None)
+        if mode == ADMode.Backward:
+            self._refuse_phase_grads(scene, grads)  # (before any device work: a medium without that differentiable phase parameter)
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
-        n, ro, rd = self._ray_ptrs(ray, dev)
-        C = self.channels
-        job = (ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value)
+        job = self._job(ray, sampler, dev)
+        n = job[2]
         if mode == ADMode.Primal:
             L = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            h.render_primal(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, L.data_ptr())
+            h.render_primal(*job, L.data_ptr())
             if self._opacity:
                 A = torch.empty((n, 1), dtype=torch.float32, device=dev)
                 h.opacity_primal(*job, A.data_ptr())
@@ -478,43 +492,19 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
                 raise ValueError("sample(Backward) needs δL and state_in")
             if grads is None:
                 raise ValueError("sample(Backward) needs `grads` (dict of accumulation tensors)")
-            _check(δL, (n, C), dev, "δL")
-            _check(state_in, (n, C), dev, "state_in")
-            gs, ga = grads[SIGMA_T_KEY], grads[ALBEDO_KEY]
-            _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
-            _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
-            gp, gv = self._phase_grad_ptr(scene, grads, dev), self._phase_tab_grad_ptr(scene, grads, dev)
-            if self._opacity:            # channel 3 through the opacity adjoint (sigma_t only), channels 0 - 2 as without it
-                dA, A_in = δL[:, 3].contiguous(), state_in[:, 3].contiguous()
-                δL, state_in = δL[:, :3].contiguous(), state_in[:, :3].contiguous()
-                h.opacity_backward(*job, dA.data_ptr(), A_in.data_ptr(), gs.data_ptr())
-            if gv:
-                h.render_backward_phase_tab(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-                                            δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gv)
-            elif gp:
-                h.render_backward_phase(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-                                        δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gp)
-            else:
-                h.render_backward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-                                  δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
+            self._adjoint(h, dev, scene, job, δL, "δL", state_in, grads, px=False)
             return None, True, None
-        _check(state_in, (n, C), dev, "state_in")
+        _check(state_in, (n, self.channels), dev, "state_in")
         dL = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        tg, tv = tangents.get(PHASE_G_KEY), tangents.get(PHASE_TAB_KEY)
+        ts = _ptr(tangents[SIGMA_T_KEY])
         dA = None
         if self._opacity:
             A_in, state_in = state_in[:, 3].contiguous(), state_in[:, :3].contiguous()
             dA = torch.empty((n, 1), dtype=torch.float32, device=dev)
-            h.opacity_forward(*job, A_in.data_ptr(), _ptr(tangents[SIGMA_T_KEY]), dA.data_ptr())
-        if tv is not None:
-            h.render_forward_phase_tab(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
-                                       _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr(), tv.data_ptr())
-        elif tg:
-            h.render_forward_phase(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
-                                   _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr(), tg)
-        else:
-            h.render_forward(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, state_in.data_ptr(),
-                             _ptr(tangents[SIGMA_T_KEY]), _ptr(tangents[ALBEDO_KEY]), dL.data_ptr())
+            h.opacity_forward(*job, A_in.data_ptr(), ts, dA.data_ptr())
+        # (the handle runs the table's call if that tangent is given, else g's if it is not zero, else the plain one)
+        h.render_forward(*job, state_in.data_ptr(), ts, _ptr(tangents[ALBEDO_KEY]), dL.data_ptr(), tangents.get(PHASE_G_KEY) or 0.0,
+                         _ptr(tangents.get(PHASE_TAB_KEY)))
         if dA is not None:
             dL = torch.cat([dL, dA], dim=1)
         return dL, True, None
@@ -523,34 +513,30 @@ class VolpathSimpleIntegrator(_DeviceIntegrator):
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
         """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] ([.., 4] with `opacity`) in place of the per-ray δL
         (drt_render_backward_px, drt_opacity_backward_px): the same gradients as with δL = film_backward(grad_image)."""
-        if grads.get(PHASE_G_KEY) is not None:
-            self._refuse_phase_grad(scene)          # (before any device work)
-        if grads.get(PHASE_TAB_KEY) is not None:
-            self._refuse_phase_tab_grad(scene, grads.get(PHASE_G_KEY) is not None)
+        self._refuse_phase_grads(scene, grads)      # (before any device work)
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
-        n, ro, rd = self._ray_ptrs(ray, dev)
-        C = self.channels
-        _check(grad_image, (n // int(ray.spp), C), dev, "grad_image")
-        _check(state_in, (n, C), dev, "state_in")
-        gs, ga = grads[SIGMA_T_KEY], grads[ALBEDO_KEY]
-        _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
-        _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
-        gp, gv = self._phase_grad_ptr(scene, grads, dev), self._phase_tab_grad_ptr(scene, grads, dev)
-        if self._opacity:
-            gA, A_in = grad_image[:, 3].contiguous(), state_in[:, 3].contiguous()
-            grad_image, state_in = grad_image[:, :3].contiguous(), state_in[:, :3].contiguous()
-            h.opacity_backward_px(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, gA.data_ptr(), gA.shape[0],
-                                  A_in.data_ptr(), gs.data_ptr())
-        if gv:
-            h.render_backward_px_phase_tab(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
-                                           grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gv)
-        elif gp:
-            h.render_backward_px_phase(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
-                                       grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gp)
+        self._adjoint(h, dev, scene, self._job(ray, sampler, dev), grad_image, "grad_image", state_in, grads, px=True)
+
+    def _adjoint(self, h, dev, scene: Scene, job: tuple, lead: torch.Tensor, lead_name: str, state_in: torch.Tensor,
+                 grads: Dict[str, torch.Tensor], px: bool):
+        """The adjoint pass of `job` behind sample(Backward) - `lead` is δL, per ray - and sample_backward_px - `lead` is grad_image, per
+        pixel: the checks, the opacity channel through its own adjoint, one call of the handle (which runs the table's C function if
+        that sink is given, else g's, else the plain one)."""
+        n, spp = job[2], job[4]
+        gs, ga = self._check_adjoint(scene, dev, n, lead, n // spp if px else n, lead_name, state_in, grads)
+        gp, gv = self._phase_sinks(scene, grads, dev)
+        if self._opacity:                # channel 3 through the opacity adjoint (sigma_t only), channels 0 - 2 as without it
+            dA, A_in = lead[:, 3].contiguous(), state_in[:, 3].contiguous()
+            lead, state_in = lead[:, :3].contiguous(), state_in[:, :3].contiguous()
+            if px:
+                h.opacity_backward_px(*job, dA.data_ptr(), dA.shape[0], A_in.data_ptr(), gs.data_ptr())
+            else:
+                h.opacity_backward(*job, dA.data_ptr(), A_in.data_ptr(), gs.data_ptr())
+        if px:
+            h.render_backward_px(*job, lead.data_ptr(), lead.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gp, gv)
         else:
-            h.render_backward_px(ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value, grad_image.data_ptr(),
-                                 grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ga.data_ptr())
+            h.render_backward(*job, lead.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ga.data_ptr(), gp, gv)
 
     def _native_props(self) -> dict:
         return {k: v for k, v in self.props().items() if k != "opacity"}     # (a property of this layer: the library has separate calls)
@@ -568,9 +554,6 @@ def opacity_seed(seed: int) -> int:
 class _TransmittanceProbe(_DeviceIntegrator):
     """The handle behind `transmittance`: a medium is all it binds to."""
     needs_albedo = False
-
-    def __init__(self):
-        self._handles, self._bound, self._bound_emitter, self._bound_phase = {}, {}, {}, {}
 
     def _native_props(self) -> dict:
         return dict(max_depth=0)
@@ -679,6 +662,7 @@ class NeRFIntegrator(_DeviceIntegrator):
 
     param_keys = (SIGMA_T_KEY, EMISSION_KEY)
     needs_albedo = False
+    wide_film = "aovs"
     forward_needs_state = False     # the forward march carries its own dual numbers
 
     def _colour_grid(self, scene: Scene):
@@ -709,18 +693,11 @@ class NeRFIntegrator(_DeviceIntegrator):
                                       "(nerf.py:160-162) and is not supported")
         if self.queries_per_ray < 2:
             raise ValueError("queries_per_ray must be >= 2")
-        self._handles: Dict[int, object] = {}
-        self._bound: Dict[int, tuple] = {}
-        self._bound_emitter: Dict[int, tuple] = {}
-        self._bound_phase: Dict[int, tuple] = {}
+        self.channels = 3 + len(self.aovs())        # floats per ray and pixel: 3, 5 with `aovs`, 6 with `distortion` too
+        super().__init__()
 
     def aovs(self):
         return (["opacity", "depth"] + (["distortion"] if self._distortion else [])) if self._aovs else []
-
-    @property
-    def channels(self) -> int:
-        """Floats per ray and pixel: 3, 5 with `aovs`, 6 with `distortion` too."""
-        return 3 + len(self.aovs())
 
     @property
     def _kind(self) -> int:
@@ -748,34 +725,6 @@ class NeRFIntegrator(_DeviceIntegrator):
 
     def _native_props(self) -> dict:
         return dict(max_depth=0)
-
-    # -- film with the integrator's channel count (aovs: drt_film_*_n with five interleaved channels, six with distortion) -----
-    def develop(self, scene: Scene, L: torch.Tensor, spp: int) -> torch.Tensor:
-        if not self._aovs:
-            return super().develop(scene, L, spp)
-        h, dev = self._bind(scene)
-        _check(L, None, dev, "L")
-        C = self.channels
-        if L.dim() != 2 or L.shape[1] != C:
-            raise ValueError(f"develop: with aovs the radiance must have shape [n, {C}], got {tuple(L.shape)}")
-        n_pix = L.shape[0] // spp
-        img = torch.empty((n_pix, C), dtype=torch.float32, device=dev)
-        h.film_develop_n(L.data_ptr(), n_pix, int(spp), C, img.data_ptr())
-        return img
-
-    def film_backward(self, scene: Scene, grad_image: torch.Tensor, spp: int) -> torch.Tensor:
-        if not self._aovs:
-            return super().film_backward(scene, grad_image, spp)
-        h, dev = self._bind(scene)
-        C = self.channels
-        if grad_image.shape[-1] != C:
-            raise ValueError(f"film_backward: with aovs the image gradient must have {C} channels, got {tuple(grad_image.shape)}")
-        grad_image = grad_image.contiguous().view(-1, C)
-        _check(grad_image, None, dev, "grad_image")
-        n_pix = grad_image.shape[0]
-        dL = torch.empty((n_pix * spp, C), dtype=torch.float32, device=dev)
-        h.film_backward_n(grad_image.data_ptr(), n_pix, int(spp), C, dL.data_ptr())
-        return dL
 
     def develop_loss(self, *args, **kwargs):
         if self._aovs:
@@ -810,10 +759,7 @@ class NeRFIntegrator(_DeviceIntegrator):
         mode = ADMode(int(mode))
         if mode == ADMode.Forward:
             tangents = self.check_tangents(scene, tangents)
-        if grads is not None and grads.get(PHASE_G_KEY) is not None:
-            self._refuse_phase_grad(scene)
-        if grads is not None and grads.get(PHASE_TAB_KEY) is not None:
-            self._refuse_phase_tab_grad(scene)
+        self._refuse_phase_grads(scene, grads)
         if self.sh_degree:
             self._check_sh(scene)
         h, dev = self._bind(scene)
@@ -824,9 +770,8 @@ class NeRFIntegrator(_DeviceIntegrator):
         if not self.sh_degree and (em.dim() != 4 or em.shape[-1] != 3):
             raise ValueError(f"emission must have shape (Z,Y,X,3), got {tuple(em.shape)}")
         self._set_rays(h, ray)
-        n, ro, rd = self._ray_ptrs(ray, dev)
-        C = self.channels
-        job = (self._kind, self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value)
+        job = (self._kind, self._nerf_props(), em.data_ptr()) + self._job(ray, sampler, dev)
+        n, C = job[5], self.channels
         if mode == ADMode.Primal:
             L = torch.empty((n, C), dtype=torch.float32, device=dev)
             h.nerf_render_primal(*job, L.data_ptr())
@@ -834,11 +779,7 @@ class NeRFIntegrator(_DeviceIntegrator):
         if mode == ADMode.Backward:
             if δL is None or state_in is None or grads is None:
                 raise ValueError("sample(Backward) needs δL, state_in and grads")
-            _check(δL, (n, C), dev, "δL")
-            _check(state_in, (n, C), dev, "state_in")
-            gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
-            _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
-            _check(ge, tuple(em.shape), dev, "grads[emission]")
+            gs, ge = self._check_adjoint(scene, dev, n, δL, n, "δL", state_in, grads)
             h.nerf_render_backward(*job, δL.data_ptr(), state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
             return None, True, None
         dL = torch.empty((n, C), dtype=torch.float32, device=dev)
@@ -849,27 +790,20 @@ class NeRFIntegrator(_DeviceIntegrator):
                            state_in: torch.Tensor, grads: Dict[str, torch.Tensor]):
         """sample(Backward) with the image gradient grad_image [n_rays / spp, 3] ([.., 5] with aovs, [.., 6] with distortion) in place of the per-ray δL
         (drt_nerf_render_backward_px)."""
-        if grads.get(PHASE_G_KEY) is not None:
-            self._refuse_phase_grad(scene)
-        if grads.get(PHASE_TAB_KEY) is not None:
-            self._refuse_phase_tab_grad(scene)
+        self._refuse_phase_grads(scene, grads)
         if self.sh_degree:
             self._check_sh(scene)
         h, dev = self._bind(scene)
         em = scene.medium.emission
         _check(em, None, dev, "emission")
         self._set_rays(h, ray)
-        n, ro, rd = self._ray_ptrs(ray, dev)
+        job = self._job(ray, sampler, dev)
+        n = job[2]
         if not self.sh_degree and (em.dim() != 4 or em.shape[-1] != 3) and self._aovs:
             raise ValueError(f"emission must have shape (Z,Y,X,3), got {tuple(em.shape)}")
-        C = self.channels
-        _check(grad_image, (n // int(ray.spp), C), dev, "grad_image")
-        _check(state_in, (n, C), dev, "state_in")
-        gs, ge = grads[SIGMA_T_KEY], grads[EMISSION_KEY]
-        _check(gs, tuple(scene.medium.sigma_t.shape), dev, "grads[sigma_t]")
-        _check(ge, tuple(em.shape), dev, "grads[emission]")
-        h.nerf_render_backward_px(self._kind, self._nerf_props(), em.data_ptr(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-                                  grad_image.data_ptr(), grad_image.shape[0], state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
+        gs, ge = self._check_adjoint(scene, dev, n, grad_image, n // job[4], "grad_image", state_in, grads)
+        h.nerf_render_backward_px(self._kind, self._nerf_props(), em.data_ptr(), *job, grad_image.data_ptr(), grad_image.shape[0],
+                                  state_in.data_ptr(), gs.data_ptr(), ge.data_ptr())
 
 
 class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
@@ -937,18 +871,16 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
         """-> (L [n, 6], valid, state_out); Backward: δL / state_in are [n, 6], gradients accumulate into
         grads[sigma_t] and grads[albedo] (= the colour grid: albedo and emission are one parameter)."""
         mode = ADMode(int(mode))
-        if (grads is not None and grads.get(PHASE_G_KEY) is not None) or (kwargs.get("tangents") or {}).get(PHASE_G_KEY) is not None:
-            self._refuse_phase_grad(scene)
-        if (grads is not None and grads.get(PHASE_TAB_KEY) is not None) or (kwargs.get("tangents") or {}).get(PHASE_TAB_KEY) is not None:
-            self._refuse_phase_tab_grad(scene)
+        tangents = kwargs.get("tangents") or ()         # (refused all the same: this integrator has no forward mode, and no phase derivative)
+        self._refuse_phase_grads(scene, grads, [k for k in (PHASE_G_KEY, PHASE_TAB_KEY) if k in tangents and tangents[k] is not None])
         h, dev = self._bind(scene)
         self._set_rays(h, ray)
-        n, ro, rd = self._ray_ptrs(ray, dev)
+        job = self._job(ray, sampler, dev)
+        n = job[2]
         if mode == ADMode.Primal:
             Ln = torch.empty((n, 3), dtype=torch.float32, device=dev)
             Ld = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            h.fused_render_primal(self._nerf_props(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-                                  Ln.data_ptr(), Ld.data_ptr())
+            h.fused_render_primal(self._nerf_props(), *job, Ln.data_ptr(), Ld.data_ptr())
             L = torch.cat([Ln, Ld], dim=1)
             return L, True, L
         if mode == ADMode.Backward:
@@ -961,8 +893,8 @@ class FusedNerfDrtIntegrator(VolpathSimpleIntegrator):
             _check(ga, tuple(scene.medium.albedo.shape), dev, "grads[albedo]")
             dLn, dLd = δL[:, :3].contiguous(), δL[:, 3:].contiguous()
             Ln, Ld = state_in[:, :3].contiguous(), state_in[:, 3:].contiguous()
-            h.fused_render_backward(self._nerf_props(), ro, rd, n, int(ray.ray_offset), int(ray.spp), sampler.seed_value,
-                                    dLn.data_ptr(), Ln.data_ptr(), dLd.data_ptr(), Ld.data_ptr(), gs.data_ptr(), ga.data_ptr())
+            h.fused_render_backward(self._nerf_props(), *job, dLn.data_ptr(), Ln.data_ptr(), dLd.data_ptr(), Ld.data_ptr(), gs.data_ptr(),
+                                    ga.data_ptr())
             return None, True, None
         raise NotImplementedError("forward-mode differentiation is not supported")
 

@@ -22,8 +22,8 @@ import torch
 
 from . import losses
 from .batched import sample_batch, sensors_to_device
-from .integrators import ADMode, FusedNerfDrtIntegrator, IndependentSampler, RayBatch, sample_tea_32
-from .render import _grid, _sensor_batch, _with_params, alloc_grads, g_grad, grad_keys, phase_param
+from .integrators import ADMode, FusedNerfDrtIntegrator, IndependentSampler, RayBatch
+from .render import _grid, _sensor_batch, _with_params, alloc_grads, g_grad, grad_keys, grad_seeds, phase_param
 from .scene import PHASE_TAB_KEY
 
 # name -> (drt_loss_kind, keyword of its parameter, default of the parameter)
@@ -115,17 +115,6 @@ def _ref_tensor(t: torch.Tensor, dev, name: str) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
 
-def _seeds(seed: int, seed_grad: int, spp: int, spp_grad: int):
-    if spp_grad == 0:
-        spp_grad = spp
-    if seed_grad == 0:
-        seed_grad = sample_tea_32(seed, 1)[0]          # batched.py:117-122, as render / render_batch
-    elif seed_grad == seed:
-        raise Exception('The primal and differential seed should be different '
-                        'to ensure unbiased gradient computation!')
-    return int(spp_grad), int(seed_grad)
-
-
 def _params(scene, integrator, params, what):
     keys = integrator.param_keys
     if params is None:
@@ -175,7 +164,7 @@ def render_loss(scene, ref_image, loss=losses.l1, params: Optional[Dict[str, tor
     _check_integrator(integrator, what)
     _check_shard(shard, what)
     kind, param = resolve_loss(loss, loss_args)
-    spp_grad, seed_grad = _seeds(seed, seed_grad, spp, spp_grad)
+    spp_grad, seed_grad = grad_seeds(seed, seed_grad, spp, spp_grad)
     params = _params(scene, integrator, params, what)
     keys = integrator.param_keys
     sen = scene.sensors[sensor]
@@ -231,7 +220,7 @@ def render_batch_loss(batch_size: int, scene, ref_images, loss=losses.l1, sensor
     kind, param = resolve_loss(loss, loss_args)
     if spp <= 0:
         raise ValueError(f"{what}: spp must be > 0")
-    spp_grad, seed_grad = _seeds(seed, seed_grad, spp, spp_grad)
+    spp_grad, seed_grad = grad_seeds(seed, seed_grad, spp, spp_grad)
     sensors = list(sensors) if sensors is not None else list(scene.sensors)
     params = _params(scene, integrator, params, what)
     keys = integrator.param_keys

@@ -123,11 +123,12 @@ def render_backward(scene: Scene, integrator, grad_image: torch.Tensor, sensor: 
     `keys`: the gradients to allocate when `grads` is None (default: integrator.param_keys); with PHASE_G_KEY among them (or in
     `grads`) the result also holds dLoss/dg of an HG medium, a 0-d view of the same flat buffer (one collective when sharded); with
     PHASE_TAB_KEY, dLoss/dvalues of a strictly positive TabPhase medium, a 1-D view of it (unsharded calls only)."""
-    want_g = (keys is not None and PHASE_G_KEY in keys) or (grads is not None and grads.get(PHASE_G_KEY) is not None)
-    if want_g:
-        integrator._refuse_phase_grad(scene)        # (before the primal pass: a medium or integrator without a differentiable g)
-    if (keys is not None and PHASE_TAB_KEY in keys) or (grads is not None and grads.get(PHASE_TAB_KEY) is not None):
-        integrator._refuse_phase_tab_grad(scene, want_g)
+    # a phase gradient named in `keys` or present in `grads` (only then is the integrator asked: any object with `sample`, `develop`,
+    # `film_backward` and `param_keys` serves a plain backward pass): refused before the primal pass where it is not built
+    asked = (PHASE_G_KEY in keys or PHASE_TAB_KEY in keys) if keys else False
+    if not asked and grads is not None:
+        asked = grads.get(PHASE_G_KEY) is not None or grads.get(PHASE_TAB_KEY) is not None
+    if asked and integrator._refuse_phase_grads(scene, grads, keys or ()):
         refuse_sharded_tab(shard, "render_backward")
     batch = _sensor_batch(scene, sensor, spp, shard)
     sampler = IndependentSampler(seed, spp)
@@ -170,31 +171,6 @@ def render_forward(scene: Scene, integrator, tangents: Optional[Dict[str, torch.
     return integrator.develop(scene, dL, spp)
 
 
-class _RenderOp(torch.autograd.Function):
-    """Counterpart of `mi._RenderOp` / `_BatchedRenderOp` (batched.py:13-85)."""
-
-    @staticmethod
-    def forward(ctx, p0, p1, scene, integrator, sensor, spp, spp_grad, seed, seed_grad, shard):
-        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()))
-        ctx.scene, ctx.integrator, ctx.sensor = sc, integrator, sensor
-        ctx.spp_grad, ctx.seed_grad, ctx.shard = spp_grad, seed_grad, shard
-        return render_primal(sc, integrator, sensor, spp, seed, shard)
-
-    @staticmethod
-    def backward(ctx, grad_image):
-        g = render_backward(ctx.scene, ctx.integrator, grad_image.contiguous(), ctx.sensor,
-                            ctx.spp_grad, ctx.seed_grad, ctx.shard, strict=False)   # (run_optimization ends with verify_pending)
-        k0, k1 = ctx.integrator.param_keys
-        return g[k0], g[k1], None, None, None, None, None, None, None, None
-
-    @staticmethod
-    def jvp(ctx, t0, t1, *_):
-        # Mitsuba's convention: the tangent image is its own estimate at (seed_grad, spp_grad), as the gradient is (batched.py:58-66)
-        k0, k1 = ctx.integrator.param_keys
-        tangents = {k: (t.contiguous() if t is not None else None) for k, t in ((k0, t0), (k1, t1))}
-        return render_forward(ctx.scene, ctx.integrator, tangents, ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard)
-
-
 def phase_param(scene: Scene, integrator, params: Dict[str, torch.Tensor], device):
     """params[PHASE_G_KEY], checked (volpathsimple, an HG medium, a 0-d float32 tensor on `device`), or None when absent."""
     if params.get(PHASE_G_KEY) is None:
@@ -213,42 +189,20 @@ def g_grad(grads: Dict[str, torch.Tensor], want_g: bool):
     return grads[PHASE_G_KEY].clone() if want_g else None
 
 
-class _RenderOpG(torch.autograd.Function):
-    """_RenderOp with the Henyey-Greenstein asymmetry g (PHASE_G_KEY) as a third input: a 0-d device tensor, read to the host once
-    per call (the handle takes g by value)."""
+class _RenderOp(torch.autograd.Function):
+    """Counterpart of `mi._RenderOp` / `_BatchedRenderOp` (batched.py:13-85).  `ph`, the third input, is the phase parameter the image
+    is rendered with and differentiable in: None - the medium's phase as it is -, the Henyey-Greenstein asymmetry g (PHASE_G_KEY: a 0-d
+    device tensor, read to the host once per call - the handle takes g by value), or the raw values of a tabulated phase function
+    (PHASE_TAB_KEY: a 1-D device tensor) with `tab`, the TabPhase the caller made of them on the host (check_phase_tab: the handle takes
+    the table from the host - that synchronisation is the cost of optimising it)."""
 
     @staticmethod
-    def forward(ctx, p0, p1, g, scene, integrator, sensor, spp, spp_grad, seed, seed_grad, shard):
-        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()), float(g.detach()))
+    def forward(ctx, p0, p1, ph, tab, scene, integrator, sensor, spp, spp_grad, seed, seed_grad, shard):
+        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()),
+                          None if ph is None or tab is not None else float(ph.detach()), phase_tab=tab)
         ctx.scene, ctx.integrator, ctx.sensor = sc, integrator, sensor
         ctx.spp_grad, ctx.seed_grad, ctx.shard = spp_grad, seed_grad, shard
-        return render_primal(sc, integrator, sensor, spp, seed, shard)
-
-    @staticmethod
-    def backward(ctx, grad_image):
-        k0, k1 = ctx.integrator.param_keys
-        want_g = ctx.needs_input_grad[2]
-        gr = render_backward(ctx.scene, ctx.integrator, grad_image.contiguous(), ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard,
-                             strict=False, keys=grad_keys(ctx.integrator, want_g))
-        return gr[k0], gr[k1], g_grad(gr, want_g), None, None, None, None, None, None, None, None
-
-    @staticmethod
-    def jvp(ctx, t0, t1, tg, *_):
-        k0, k1 = ctx.integrator.param_keys
-        tangents = {k: (t.contiguous() if t is not None else None) for k, t in ((k0, t0), (k1, t1))}
-        tangents[PHASE_G_KEY] = tg                 # (read to the host by check_tangents)
-        return render_forward(ctx.scene, ctx.integrator, tangents, ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard)
-
-
-class _RenderOpTab(torch.autograd.Function):
-    """_RenderOp with the raw values of a tabulated phase function (PHASE_TAB_KEY) as a third input: a 1-D device tensor, read to the
-    host once per call (check_phase_tab: the handle takes the table from the host) - that synchronisation is the cost of optimising it."""
-
-    @staticmethod
-    def forward(ctx, p0, p1, v, tab, scene, integrator, sensor, spp, spp_grad, seed, seed_grad, shard):
-        sc = _with_params(scene, integrator.param_keys, (p0.detach(), p1.detach()), phase_tab=tab)
-        ctx.scene, ctx.integrator, ctx.sensor = sc, integrator, sensor
-        ctx.spp_grad, ctx.seed_grad, ctx.shard = spp_grad, seed_grad, shard
+        ctx.phase_key = None if ph is None else PHASE_G_KEY if tab is None else PHASE_TAB_KEY
         return render_primal(sc, integrator, sensor, spp, seed, shard)
 
     @staticmethod
@@ -256,15 +210,20 @@ class _RenderOpTab(torch.autograd.Function):
         k0, k1 = ctx.integrator.param_keys
         want = ctx.needs_input_grad[2]
         gr = render_backward(ctx.scene, ctx.integrator, grad_image.contiguous(), ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard,
-                             strict=False, keys=tuple(ctx.integrator.param_keys) + ((PHASE_TAB_KEY,) if want else ()))
-        # (a copy: `v.grad` does not keep the flat gradient buffer alive)
-        return (gr[k0], gr[k1], gr[PHASE_TAB_KEY].clone() if want else None) + (None,) * 9
+                             strict=False,                       # (run_optimization ends with verify_pending)
+                             keys=(k0, k1, ctx.phase_key) if want else None)
+        # (a copy of the phase slot: `g.grad` / `v.grad` does not keep the flat gradient buffer alive)
+        return (gr[k0], gr[k1], gr[ctx.phase_key].clone() if want else None) + (None,) * 9
 
     @staticmethod
-    def jvp(ctx, t0, t1, tv, *_):
+    def jvp(ctx, t0, t1, tph, *_):
+        # Mitsuba's convention: the tangent image is its own estimate at (seed_grad, spp_grad), as the gradient is (batched.py:58-66)
         k0, k1 = ctx.integrator.param_keys
         tangents = {k: (t.contiguous() if t is not None else None) for k, t in ((k0, t0), (k1, t1))}
-        tangents[PHASE_TAB_KEY] = tv.contiguous() if tv is not None else None
+        if ctx.phase_key == PHASE_G_KEY:
+            tangents[PHASE_G_KEY] = tph                # (read to the host by check_tangents)
+        elif ctx.phase_key == PHASE_TAB_KEY:
+            tangents[PHASE_TAB_KEY] = tph.contiguous() if tph is not None else None
         return render_forward(ctx.scene, ctx.integrator, tangents, ctx.sensor, ctx.spp_grad, ctx.seed_grad, ctx.shard)
 
 
@@ -283,6 +242,19 @@ def phase_tab_param(scene: Scene, integrator, params: Dict[str, torch.Tensor], d
     return params[PHASE_TAB_KEY], check_phase_tab(params[PHASE_TAB_KEY], scene, device)
 
 
+def grad_seeds(seed: int, seed_grad: int, spp: int, spp_grad: int):
+    """(spp_grad, seed_grad) of the differential phase as `render`, `render_loss` and `render_batch_loss` default them: the primal
+    phase's spp, and a seed derived from the primal one - de-correlated from it (batched.py:117-122)."""
+    if spp_grad == 0:
+        spp_grad = spp
+    if seed_grad == 0:
+        seed_grad = sample_tea_32(seed, 1)[0]
+    elif seed_grad == seed:
+        raise Exception('The primal and differential seed should be different '
+                        'to ensure unbiased gradient computation!')
+    return int(spp_grad), int(seed_grad)
+
+
 def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integrator=None,
            sensor: int = 0, spp: int = 1, spp_grad: int = 0, seed: int = 0, seed_grad: int = 0,
            shard: Optional[ShardSpec] = None) -> torch.Tensor:
@@ -297,14 +269,7 @@ def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integ
     to the host once per call."""
     if integrator is None:
         raise ValueError("render: an integrator is required")
-    if spp_grad == 0:
-        spp_grad = spp
-    if seed_grad == 0:
-        # de-correlate the primal and differential phases (batched.py:117-122)
-        seed_grad = sample_tea_32(seed, 1)[0]
-    elif seed_grad == seed:
-        raise Exception('The primal and differential seed should be different '
-                        'to ensure unbiased gradient computation!')
+    spp_grad, seed_grad = grad_seeds(seed, seed_grad, spp, spp_grad)
     keys = integrator.param_keys
     if params is None:
         params = {k: _grid(scene, k) for k in keys}
@@ -312,13 +277,9 @@ def render(scene: Scene, params: Optional[Dict[str, torch.Tensor]] = None, integ
         if not isinstance(params[k], torch.Tensor):
             raise TypeError(f"render: params['{k}'] must be a torch device tensor "
                             "(the DRT integrator has no CPU path; use scene_to(scene, device))")
-    tab = phase_tab_param(scene, integrator, params, params[keys[0]].device, shard)
-    if tab is not None:
-        return _RenderOpTab.apply(params[keys[0]], params[keys[1]], tab[0], tab[1], scene, integrator, sensor,
-                                  int(spp), int(spp_grad), int(seed), int(seed_grad), shard)
-    g = phase_param(scene, integrator, params, params[keys[0]].device)
-    if g is not None:
-        return _RenderOpG.apply(params[keys[0]], params[keys[1]], g, scene, integrator, sensor,
-                                int(spp), int(spp_grad), int(seed), int(seed_grad), shard)
-    return _RenderOp.apply(params[keys[0]], params[keys[1]], scene, integrator, sensor,
-                           int(spp), int(spp_grad), int(seed), int(seed_grad), shard)
+    # the phase input of the op: the table's values and their TabPhase, else g, else nothing
+    ph, tab = phase_tab_param(scene, integrator, params, params[keys[0]].device, shard) or (None, None)
+    if tab is None:
+        ph = phase_param(scene, integrator, params, params[keys[0]].device)
+    return _RenderOp.apply(params[keys[0]], params[keys[1]], ph, tab, scene, integrator, sensor,
+                           int(spp), spp_grad, int(seed), seed_grad, shard)
