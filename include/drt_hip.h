@@ -636,6 +636,43 @@ int drt_ssim_forward(void *hip_stream, const float *img, const float *ref, int32
 int drt_ssim_backward(void *hip_stream, const float *img, const float *ref, const float *dmaps, const float *upstream, int32_t n, int32_t h,
                       int32_t w, int32_t c, int32_t valid, float *grad);
 
+/* Pyramid losses: a residual loss summed over the levels of a box pyramid of img - ref (no handle, no state, no host wait, everything on
+ * `hip_stream`; csrc/drt_pyramid.hip, DESIGN.md "Multi-scale pyramid losses"; an extension of the reference).  THE DEFINITION, referred to
+ * everywhere else:
+ *   Films     x (img) and y (ref) are (n, h, w, c) float32, contiguous, channels last.
+ *   Sizes     h_0 = h, h_l = ceil(h_{l-1} / 2), w_l likewise; `levels` L in 0..5 gives the levels 0..L.
+ *   Residual  r_0 = x - y, one float32 subtraction per entry.  Every channel is pooled on its own: r_l[i, j] is the mean of the children
+ *             of r_{l-1} that exist, (2i, 2j), (2i, 2j+1), (2i+1, 2j), (2i+1, 2j+1), added in that order in float32 and then multiplied by
+ *             1, 0.5 or 0.25 (1, 2 or 4 children) - avg_pool2d(r, 2, ceil_mode=True, count_include_pad=False).
+ *   Summand   DRT_PYR_L1     rho = |r|, rho' = sign(r) with sign(0) = 0
+ *             DRT_PYR_L2     rho = r^2
+ *             DRT_PYR_HUBER  rho = r < delta ? 0.5 r^2 : delta |r| - 0.5 delta (the SIGNED comparison of the reference's huber), delta and
+ *                            0.5 delta rounded to float32
+ *             evaluated in float32, every operation rounded (-ffp-contract=off).
+ *   Level     loss_l = (1 / N_l) sum rho(r_l), N_l = n h_l w_l c, summed in float64; loss_0 is the plain loss.
+ *   Total     sum_l weight_l loss_l in float64, weights finite and >= 0; a level of weight exactly 0 is not added.
+ *   Gradient  d total / d x[p] = sum_l (weight_l / N_l) rho'(r_l[cell_l(p)]) prod_{k=1..l} 1 / count_k(ancestor_k(p)), count_k the number
+ *             of children of the level-k ancestor (at the film's odd edges the product is not 4^-l).  In float32 it is accumulated from
+ *             the coarsest level down: a_L = k_L rho'(r_L), a_l = k_l rho'(r_l) + a_{l+1}[parent] / count_{l+1}(parent), gradient = a_0,
+ *             with k_l = weight_l / N_l rounded to float32 and the division an exact power of two.
+ * drt_pyramid_loss stores loss_0 .. loss_L and then the total as levels + 2 doubles at `values` (DEVICE) and, unless `grad` is NULL, STORES
+ * the gradient for upstream 1 in `grad` (n h w c floats; scale it by the upstream value).  `weights` are levels + 1 doubles on the HOST,
+ * read before the call returns.  A workgroup holds a 32 x 32-pixel tile of the residual and all its coarser levels in LDS - no level map
+ * goes to memory -; per-tile, per-level sums go as doubles to `scratch` (DEVICE, 8-byte aligned, at least
+ * drt_pyramid_loss_scratch_bytes(n, h, w, c, levels) bytes, contents irrelevant before and after) and ONE workgroup adds them in a fixed
+ * order: no float atomics, equal inputs give equal bits on every call.  Any 4-byte aligned float pointers; 16-byte accesses are used when
+ * img, ref and grad are 16-byte aligned and w c is a multiple of 4.  No gradient with respect to ref.
+ * Refused with DRT_ERR_INVALID_ARGUMENT and a message (drt_last_error(NULL)), before any device work: a NULL or misaligned pointer (floats
+ * 4, values and scratch 8 bytes; grad alone may be NULL), n, h or w below 1, n h w c >= 2^31, c outside 1..8, levels outside 0..5, an
+ * unknown kind, a weight that is negative or not finite, for DRT_PYR_HUBER a delta that is not finite, a scratch that is missing or too
+ * small, values, grad or scratch overlapping an input.  drt_pyramid_loss_scratch_bytes returns 0 for extents the call refuses. */
+enum { DRT_PYR_L1 = 0, DRT_PYR_L2 = 1, DRT_PYR_HUBER = 2 };
+uint64_t drt_pyramid_loss_scratch_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t levels);
+int drt_pyramid_loss(void *hip_stream, int32_t kind, const float *img, const float *ref, int32_t n, int32_t h, int32_t w, int32_t c,
+                     int32_t levels, const double *weights /* HOST, levels + 1 */, double delta,
+                     double *values /* DEVICE, levels + 2: the level losses, then the total */, float *grad /* DEVICE n h w c, or NULL */,
+                     void *scratch, uint64_t scratch_bytes);
+
 /* Event counting (off by default; enabling selects a counting build of the kernels). */
 int drt_enable_counters(drt_handle h, int enable);
 int drt_reset_counters(drt_handle h);

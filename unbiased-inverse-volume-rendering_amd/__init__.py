@@ -24,6 +24,7 @@ from .hull import HullSupport, VisualHull, mask_tables, visual_hull
 from .priors import Prior, prior_value_and_grad_, smoothness, sparsity, total_variation
 from .resample import resample_grid, resample_grid_transpose
 from .ssim import dssim, ssim, ssim_map
+from .pyramid import downsample2, multiscale
 from .volume_io import medium_from_vol, read_vol, write_vol
 from .image_io import read_image, write_image
 from .fd import fd_gradients
@@ -45,4 +46,5 @@ __all__ = [
     "PixelDistribution", "PixelImportance",
     "HullSupport", "VisualHull", "mask_tables", "visual_hull",
     "ssim", "dssim", "ssim_map", "evaluate_views",
+    "multiscale", "downsample2",
 ]

@@ -20,7 +20,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 _ROOT = os.path.dirname(_PKG)
 
-HIP_SOURCES = ["drt_kernels.hip", "drt_deferred.hip", "drt_coop.hip", "drt_coop_super.hip", "drt_order.hip", "drt_sq.hip", "drt_nerf_tile.hip", "drt_nerf_sh.hip", "drt_nerf_aov.hip", "drt_nerf_dist.hip", "drt_own.hip", "drt_loss.hip", "drt_priors.hip", "drt_resample.hip", "drt_pixel_dist.hip", "drt_opacity.hip", "drt_hull.hip", "drt_ssim.hip",
+HIP_SOURCES = ["drt_kernels.hip", "drt_deferred.hip", "drt_coop.hip", "drt_coop_super.hip", "drt_order.hip", "drt_sq.hip", "drt_nerf_tile.hip", "drt_nerf_sh.hip", "drt_nerf_aov.hip", "drt_nerf_dist.hip", "drt_own.hip", "drt_loss.hip", "drt_priors.hip", "drt_resample.hip", "drt_pixel_dist.hip", "drt_opacity.hip", "drt_hull.hip", "drt_ssim.hip", "drt_pyramid.hip",
                "drt_coop_hg.hip", "drt_coop_super_hg.hip", "drt_own_hg.hip", "drt_sq_hg.hip",
                "drt_coop_hg2.hip", "drt_coop_super_hg2.hip", "drt_own_hg2.hip", "drt_sq_hg2.hip",
                "drt_coop_tab.hip", "drt_coop_super_tab.hip", "drt_own_tab.hip", "drt_sq_tab.hip",

@@ -1,5 +1,5 @@
 // drt_capi_ops.cpp -- the entry points of include/drt_hip.h that take a stream and no handle: Adam, the visual hull, the grid priors,
-// SSIM, the grid resampler, the pixel distribution and the gradient packing.  Their messages go to the thread's last-error string.
+// SSIM, the pyramid losses, the grid resampler, the pixel distribution and the gradient packing.  Their messages go to the thread's last-error string.
 #include "drt_host.h"
 
 #include <cmath>
@@ -207,6 +207,51 @@ int drt_ssim_backward(void *hip_stream, const float *img, const float *ref, cons
         if ((uintptr_t) grad < (uintptr_t) i.p + i.size && (uintptr_t) i.p < (uintptr_t) grad + bytes)
             return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: grad overlaps an input", who);
     DRT_HIP_CHECK(nullptr, drt::launch_ssim_backward(img, ref, dmaps, upstream, n, h, w, c, valid != 0, grad, (hipStream_t) hip_stream));
+    return DRT_OK;
+}
+
+uint64_t drt_pyramid_loss_scratch_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t levels)
+{
+    return drt::pyramid_supported(n, h, w, c, levels) ? drt::pyramid_tiles(n, h, w) * (uint64_t) (levels + 1) * sizeof(double) : 0;
+}
+
+int drt_pyramid_loss(void *hip_stream, int32_t kind, const float *img, const float *ref, int32_t n, int32_t h, int32_t w, int32_t c,
+                     int32_t levels, const double *weights, double delta, double *values, float *grad, void *scratch, uint64_t scratch_bytes)
+{
+    const char *who = "drt_pyramid_loss";
+    if (!img || !ref) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null image", who);
+    if ((((uintptr_t) img) | ((uintptr_t) ref) | ((uintptr_t) grad)) & 3u)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: images and grad must be 4-byte aligned", who);
+    if (kind != DRT_PYR_L1 && kind != DRT_PYR_L2 && kind != DRT_PYR_HUBER)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: unknown kind %d", who, (int) kind);
+    if (n < 1 || h < 1 || w < 1)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: empty film %d x %d x %d (n, h and w must be at least 1)", who, (int) n, (int) h, (int) w);
+    if (c < 1 || c > drt::kPyramidMaxChannels)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: %d channels (1..%d are supported)", who, (int) c, drt::kPyramidMaxChannels);
+    if (levels < 0 || levels > drt::kPyramidMaxLevels)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: %d levels (0..%d are supported)", who, (int) levels, drt::kPyramidMaxLevels);
+    if (!drt::pyramid_supported(n, h, w, c, levels))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: films %d x %d x %d x %d are too large (n h w c must stay below 2^31)", who, (int) n,
+                    (int) h, (int) w, (int) c);
+    if (!weights) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: null weights", who);
+    for (int l = 0; l <= levels; ++l)
+        if (!(std::isfinite(weights[l]) && weights[l] >= 0.0))
+            return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: weight %d is %g (weights must be finite and >= 0)", who, l, weights[l]);
+    if (kind == DRT_PYR_HUBER && !(std::isfinite(delta) && std::isfinite((float) delta)))
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: huber needs a finite delta, got %g", who, delta);
+    if (!values || (((uintptr_t) values) & 7u)) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: values must be an 8-byte aligned pointer", who);
+    const uint64_t need = drt_pyramid_loss_scratch_bytes(n, h, w, c, levels);
+    if (!scratch || (((uintptr_t) scratch) & 7u) || scratch_bytes < need)
+        return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: scratch must be an 8-byte aligned buffer of at least %llu bytes (got %llu)", who,
+                    (unsigned long long) need, (unsigned long long) scratch_bytes);
+    const uint64_t bytes = (uint64_t) n * (uint64_t) h * (uint64_t) w * (uint64_t) c * sizeof(float);
+    const struct { const void *p; uint64_t size; } outs[] = { { values, (uint64_t) (levels + 2) * sizeof(double) }, { grad, bytes }, { scratch, need } };
+    for (const auto &o : outs)
+        for (const float *in : { img, ref })
+            if (o.p && (uintptr_t) o.p < (uintptr_t) in + bytes && (uintptr_t) in < (uintptr_t) o.p + o.size)
+                return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "%s: an output (values, grad or scratch) overlaps an input image", who);
+    DRT_HIP_CHECK(nullptr, drt::launch_pyramid_loss(kind, img, ref, n, h, w, c, levels, weights, delta, values, grad, (double *) scratch,
+                                                    (hipStream_t) hip_stream));
     return DRT_OK;
 }
 

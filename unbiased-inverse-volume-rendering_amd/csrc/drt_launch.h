@@ -239,6 +239,18 @@ hipError_t launch_ssim_forward(const float *x, const float *y, int n, int h, int
                                float *map, float *dmaps, double *partials, hipStream_t stream);
 hipError_t launch_ssim_backward(const float *x, const float *y, const float *dmaps, const float *upstream, int n, int h, int w, int c, bool valid,
                                 float *grad, hipStream_t stream);
+// multi-scale residual losses (drt_pyramid.hip; the definition: include/drt_hip.h "Pyramid losses") of two films (N,H,W,C),
+// C <= kPyramidMaxChannels, N H W C < 2^31, levels 0..kPyramidMaxLevels.  One tile launch writes (levels + 1) doubles per 32 x 32 tile to
+// `partials` (pyramid_tiles of them) and STORES the gradient for upstream 1 (grad may be nullptr); a second, single-workgroup launch leaves
+// the level losses and the weighted total in values[0 .. levels + 1].  `weights`: HOST, levels + 1, read before the call returns.
+enum PyramidKind : int { kPyramidL1 = 0, kPyramidL2 = 1, kPyramidHuber = 2 };
+constexpr int kPyramidMaxChannels = 8;
+constexpr int kPyramidMaxLevels = 5;
+bool pyramid_supported(int64_t n, int64_t h, int64_t w, int64_t c, int64_t levels);
+uint64_t pyramid_tiles(int n, int h, int w);
+double pyramid_count(int n, int h, int w, int c, int level);         // N_l
+hipError_t launch_pyramid_loss(int kind, const float *x, const float *y, int n, int h, int w, int c, int levels, const double *weights,
+                               double delta, double *values, float *grad, double *partials, hipStream_t stream);
 // importance-sampled pixel batches (drt_pixel_dist.hip): a table over n < 2^31 film entries = this header, the exclusive uint64 prefix of the
 // sums of blocks of kDistBlock masses [n_blocks + 1], then the 16-bit masses padded to whole blocks (16-byte aligned)
 constexpr uint32_t kDistBlock = 256;

@@ -414,6 +414,16 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         ok(drt_ssim_backward(ptr<void>(stream), ptr<const float>(img), ptr<const float>(ref), ptr<const float>(dmaps), ptr<const float>(upstream),
                              n, h, w, c, valid ? 1 : 0, ptr<float>(grad)));
     });
+    m.def("pyramid_loss_scratch_bytes", [](int32_t n, int32_t h, int32_t w, int32_t c, int32_t levels) {
+        return drt_pyramid_loss_scratch_bytes(n, h, w, c, levels);
+    });
+    m.def("pyramid_loss", [](uintptr_t stream, int32_t kind, uintptr_t img, uintptr_t ref, int32_t n, int32_t h, int32_t w, int32_t c,
+                             int32_t levels, std::vector<double> weights, double delta, uintptr_t values, uintptr_t grad, uintptr_t scratch,
+                             uint64_t scratch_bytes) {
+        if (levels < 0 || weights.size() != (size_t) levels + 1) throw std::invalid_argument("pyramid_loss: weights must hold levels + 1 numbers");
+        ok(drt_pyramid_loss(ptr<void>(stream), kind, ptr<const float>(img), ptr<const float>(ref), n, h, w, c, levels, weights.data(), delta,
+                            ptr<double>(values), ptr<float>(grad), ptr<void>(scratch), scratch_bytes));
+    });
     // grids are (Z,Y,X,C): the extents arrive in tensor order and go to the C ABI as {X,Y,Z}
     m.def("grid_resample", [](uintptr_t stream, uintptr_t src, int32_t sz, int32_t sy, int32_t sx, uintptr_t dst, int32_t tz, int32_t ty, int32_t tx,
                               int32_t channels) {

@@ -1,6 +1,7 @@
 """Image losses of the reference (python/losses.py) on torch tensors.  `img` and `ref_img` have the
 same shape; every loss is normalised by `dr.width(img)` = the number of entries.  Beside them `ssim`, `dssim` and `ssim_map` (ssim.py): the
-structural similarity index, the one loss here that is not a sum over independent pixels."""
+structural similarity index, the one loss here that is not a sum over independent pixels, and `multiscale` / `downsample2` (pyramid.py): any
+of these losses summed over the levels of a box pyramid of the film."""
 from __future__ import annotations
 
 import math
@@ -8,6 +9,7 @@ import math
 import torch
 
 from .ssim import dssim, ssim, ssim_map      # structural similarity: not a sum over pixels (ssim.py)
+from .pyramid import downsample2, multiscale # a loss summed over the levels of a box pyramid (pyramid.py)
 
 
 def average(img, ref_img=None, shape=None):

@@ -79,6 +79,10 @@ class OptimizationConfig:
     # of a sensor-mode (batch_size=None), unfused, unsharded run; `dssim_data_range` is its L.  0: nothing extra runs
     dssim_weight: float = 0.0
     dssim_data_range: float = 1.0
+    # opt-in: evaluate `loss` over a box pyramid of the rendered film (losses.multiscale: levels 0..pyramid_levels, `pyramid_weights` or
+    # 1 / (pyramid_levels + 1) each) in a sensor-mode (batch_size=None), unfused, unsharded run.  0: nothing extra runs
+    pyramid_levels: int = 0
+    pyramid_weights: Optional[List[float]] = None
 
     def __post_init__(self):
         self.upsample_at = set()
@@ -549,6 +553,12 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     as the loss is - the 0.8 l1 + 0.2 (1 - SSIM) objective of full-image reconstruction with loss=l1 scaled by 0.8.  On the device that is
     one stencil pass forward and one backward (csrc/drt_ssim.hip), no host wait.  0 (the default) runs nothing and leaves the run's bits.
 
+    `opt_config.pyramid_levels` (sensor mode, i.e. `batch_size=None`; not with `fused_loss`, not sharded - each raises a ValueError at
+    start-up): the step's loss is losses.multiscale(opt_config.loss, pyramid_levels, pyramid_weights)(image, ref, shape=(H, W)) over all the
+    channels the plain loss covers (include/drt_hip.h "Pyramid losses"), beside `dssim_weight`, `priors`, `support` and `distortion_weight`.
+    For l1, l2 and huber that is one fused kernel call (csrc/drt_pyramid.hip), no host wait.  0 (the default) runs nothing extra and leaves
+    the run's bits.
+
     `opt_config.support` (a `HullSupport`; every route, sharded ones too - each rank carves the same integers; like the rest of
     distributed.py that is unverified on multi-GPU hardware): at initialisation and after every `upsample` the visual hull of the mattes
     (`masks`, or channel 3 of the references > `threshold`) is carved from the scene's box and the run's sensors at the current resolution
@@ -589,6 +599,21 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         if shard.partitioned:
             raise ValueError("dssim_weight: sharded runs are not supported: every rank renders a share of the image's pixels, and the "
                              "structural index needs the whole neighbourhood of each")
+    pyramid_levels = opt_config.pyramid_levels
+    if isinstance(pyramid_levels, bool) or not isinstance(pyramid_levels, int) or pyramid_levels < 0:
+        raise ValueError(f"pyramid_levels must be an integer >= 0, got {pyramid_levels!r}")
+    film_loss = None                                                   # the loss over the pyramid of a whole film (sensor mode)
+    if pyramid_levels > 0:
+        if opt_config.batch_size is not None:
+            raise ValueError("pyramid_levels: batched rendering (batch_size set) draws scattered pixels, which have no cells for a pyramid to "
+                             "pool; use sensor-based rendering (batch_size=None).  Block-shaped batches are the follow-up")
+        if opt_config.fused_loss:
+            raise ValueError("pyramid_levels: fused_loss=True is not supported (the loss-fused film sums a pixel-separable loss per pixel and "
+                             "never pools the image); use fused_loss=False")
+        if shard.partitioned:
+            raise ValueError("pyramid_levels: sharded runs are not supported: every rank renders a share of the image's pixels, and a "
+                             "pyramid cell needs all of its children")
+        film_loss = _losses.multiscale(opt_config.loss, pyramid_levels, opt_config.pyramid_weights)   # (raises for bad levels / weights)
     importance = opt_config.pixel_importance
     pixel_loss = None
     if importance is not None:
@@ -889,12 +914,16 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         elif not opt_config.fused_loss:
             # the losses normalise by the local entry count: scale to this rank's share of the global loss
             scale = local_loss_scale(image.shape[0], n_global)
+            if film_loss is not None:                                  # (sensor mode, unsharded: the whole image of sensor s_i, flat)
+                step_loss = lambda img, ref: film_loss(img, ref, shape=(sensors[s_i].height, sensors[s_i].width))
+            else:
+                step_loss = opt_config.loss
             if has_distortion:
-                loss_value = opt_config.loss(image[:, :n_channels], ref_values) * scale
+                loss_value = step_loss(image[:, :n_channels], ref_values) * scale
                 if opt_config.distortion_weight != 0.0:
                     loss_value = loss_value + opt_config.distortion_weight * _losses.distortion(image) * scale
             else:
-                loss_value = opt_config.loss(image, ref_values) * scale
+                loss_value = step_loss(image, ref_values) * scale
             if dssim_weight != 0.0:                                    # (sensor mode, unsharded: the whole image of sensor s_i, flat)
                 loss_value = loss_value + dssim_weight * _losses.dssim(image[:, :3], ref_values[:, :3], shape=(sensors[s_i].height, sensors[s_i].width),
                                                                        data_range=opt_config.dssim_data_range) * scale
