@@ -407,6 +407,34 @@ int drt_pixel_dist_inv_pdf(void *hip_stream, const void *table, int32_t n_sensor
 int drt_pixel_dist_update(void *hip_stream, float *weights, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,
                           const int32_t *pixel_idx, const float *err, uint64_t count);
 
+/* Patch batches (opt-in; the calls above are unchanged; an extension of the reference, whose batches are scattered pixels).  The batch is drawn
+ * as rectangular patches, so that a batch is a stack of small films and losses over neighbourhoods (SSIM, image pyramids) apply to it.
+ * Inputs: the sensors table of drt_batch_sample_rays (S = n_sensors, one film size W = width, H = height) and a patch of pw = patch_w by
+ * ph = patch_h pixels, 1 <= pw <= W, 1 <= ph <= H, area a = pw * ph.
+ * GLOBAL batch entry b: patch q = b / a, position t = b % a, ty = t / pw, tx = t % pw.  Lane q of the pixel wavefront
+ * (Pcg32::seed(sub_seed_pixels, q)) draws us, ux, uy with next_1d - what lane b of drt_batch_sample_rays draws.
+ *   si = min((uint32) ((float) S * us), S - 1)
+ *   ex = min((uint32) ((float) (W + pw - 1) * ux), W + pw - 2),  x0 = clamp((int) ex - (pw - 1), 0, W - pw)
+ *   ey, y0 the same from uy, H and ph
+ * The entry is sensor si, pixel (x0 + tx, y0 + ty): entries are patch-major, then row-major inside a patch.  Ray r = b * spp + j takes its
+ * sub-pixel offset from lane r of the ray wavefront (sub_seed_rays), exactly as in drt_batch_sample_rays.  With pw = ph = 1 this is
+ * drt_batch_sample_rays_range bit for bit, in all four outputs.
+ * Coverage: the origin's range is extended by pw - 1 and then clamped (not drawn uniformly over [0, W - pw], which would visit a corner pixel
+ * pw * ph times less often than an inner one).  Per axis c_x(x) = the number of ex in [0, W + pw - 2] whose clamped origin has
+ * x0 <= x < x0 + pw; pw <= c_x(x) <= 3 pw - 2 and sum_x c_x = pw (W + pw - 1).  The probability that a uniformly chosen entry of a batch is
+ * pixel (s, x, y) is p = c_x(x) c_y(y) / (S (W + pw - 1) (H + ph - 1) pw ph), and weighting entry b's pixel-separable loss by
+ * 1 / (S W H p) (Python: patch_inv_pdf) gives the batch mean the expectation of the uniform batch's.
+ * drt_batch_sample_rays_patches: batch_first / batch_count are a range of GLOBAL entries as in _range (it may begin or end inside a patch);
+ * outputs as there, all four required: rays_o / rays_d [batch_count*spp][3], sensor_idx [batch_count], pixels [batch_count][2] (x, y).  Every
+ * pixel is also clamped to the table's own film, so no ray is formed off the film whatever width / height are passed.  Integers and fp32
+ * products only, no atomics: equal inputs give equal bytes.
+ * Refused with DRT_ERR_INVALID_ARGUMENT and a message (drt_last_error), before any device work and before the handle is looked at: null
+ * pointers, n_sensors < 1, spp == 0, width or height < 1 (or >= 2^30), a patch side of 0 or larger than the film,
+ * (batch_first + batch_count) * spp > 2^32 - 1. */
+int drt_batch_sample_rays_patches(drt_handle h, const float *sensors, int32_t n_sensors, int32_t width, int32_t height,
+    uint32_t patch_w, uint32_t patch_h, uint32_t batch_first, uint32_t batch_count, uint32_t spp,
+    uint32_t sub_seed_pixels, uint32_t sub_seed_rays, float *rays_o, float *rays_d, uint32_t *sensor_idx, uint32_t *pixels);
+
 /* Box-filter film: image[p] = mean over the pixel's spp samples
  * (block.put + film.develop, batched.py:176-197).  L: [n_pixels*spp][3]. */
 int drt_film_develop(drt_handle h, const float *L, uint64_t n_pixels, uint32_t spp, float *image);

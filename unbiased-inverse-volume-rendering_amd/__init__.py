@@ -13,7 +13,7 @@ from .opt_config import IntegratorConfig, add_int_config, get_int_config
 from .distributed import (GradientSupport, ShardSpec, allreduce_gradients, allreduce_scalar, from_environment, gradient_support,
                           local_loss_scale, reset_allreduce_state, verify_pending)
 from .render import alloc_grads, render, render_backward, render_forward, render_primal
-from .batched import gather_ref_values, render_batch, sample_batch, sensors_to_device
+from .batched import as_patches, gather_ref_values, patch_coverage, patch_inv_pdf, render_batch, sample_batch, sensors_to_device
 from . import losses
 from .loss_fused import render_batch_loss, render_loss
 from .optimize import (Adam, OptimizationConfig, SGD, SceneConfig, Schedule, adjusted_majorant_res_factor,
@@ -37,7 +37,7 @@ __all__ = [
     "add_int_config", "get_int_config", "ShardSpec", "allreduce_gradients", "allreduce_scalar", "GradientSupport", "gradient_support",
     "reset_allreduce_state", "verify_pending",
     "from_environment", "local_loss_scale", "alloc_grads", "render", "render_backward", "render_forward", "render_primal", "render_batch",
-    "gather_ref_values", "sample_batch", "render_loss", "render_batch_loss", "sensors_to_device", "losses", "Adam", "SGD", "OptimizationConfig",
+    "gather_ref_values", "sample_batch", "as_patches", "patch_coverage", "patch_inv_pdf", "render_loss", "render_batch_loss", "sensors_to_device", "losses", "Adam", "SGD", "OptimizationConfig",
     "SceneConfig", "Schedule", "adjusted_majorant_res_factor", "enforce_valid_params", "run_optimization",
     "save_params", "upsample_grid", "read_vol", "write_vol", "medium_from_vol", "read_image", "write_image", "get_reference_image_paths",
     "load_reference_images", "render_previews", "render_reference_image", "fd_gradients",

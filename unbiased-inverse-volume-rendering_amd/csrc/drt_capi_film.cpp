@@ -150,4 +150,30 @@ int drt_batch_sample_rays_weighted(drt_handle h, const float *sensors, int32_t n
     return DRT_OK;
 }
 
+int drt_batch_sample_rays_patches(drt_handle h, const float *sensors, int32_t n_sensors, int32_t width, int32_t height, uint32_t patch_w,
+                                  uint32_t patch_h, uint32_t batch_first, uint32_t batch_count, uint32_t spp, uint32_t sub_seed_pixels,
+                                  uint32_t sub_seed_rays, float *rays_o, float *rays_d, uint32_t *sensor_idx, uint32_t *pixels)
+{
+    // (the argument checks come first and need no handle: fail() takes a null one)
+    if (!sensors || n_sensors < 1 || spp == 0) return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_batch_sample_rays_patches: bad sensors / spp");
+    if (width < 1 || height < 1 || width >= (1 << 30) || height >= (1 << 30))
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_batch_sample_rays_patches: a film of %d x %d (width x height must be in [1, 2^30))", (int) width,
+                    (int) height);
+    if (patch_w < 1 || patch_h < 1 || patch_w > (uint32_t) width || patch_h > (uint32_t) height)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_batch_sample_rays_patches: a patch of %u x %u does not fit a film of %d x %d (each side must be "
+                    "in [1, the film's])", (unsigned) patch_w, (unsigned) patch_h, (int) width, (int) height);
+    if ((uint64_t) patch_w * patch_h > 0xffffffffull)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_batch_sample_rays_patches: a patch of %u x %u has more than 2^32 - 1 entries",
+                    (unsigned) patch_w, (unsigned) patch_h);
+    if (((uint64_t) batch_first + batch_count) * spp > 0xffffffffull)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "batch_size * spp exceeds 2^32 - 1");
+    if (!rays_o || !rays_d || !sensor_idx || !pixels)
+        return fail(h, DRT_ERR_INVALID_ARGUMENT, "drt_batch_sample_rays_patches: null rays_o / rays_d / sensor_idx / pixels (the rays are formed from the stored picks)");
+    if (!h) return fail(nullptr, DRT_ERR_INVALID_ARGUMENT, "null handle");
+    DeviceGuard g(h->device);
+    DRT_HIP_CHECK(h, drt::launch_patch_sample(sensors, n_sensors, (uint32_t) width, (uint32_t) height, patch_w, patch_h, batch_first, batch_count,
+                                              spp, sub_seed_pixels, sub_seed_rays, rays_o, rays_d, sensor_idx, pixels, h->stream));
+    return DRT_OK;
+}
+
 }  // extern "C"

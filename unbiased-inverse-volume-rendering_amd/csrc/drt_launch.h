@@ -268,6 +268,11 @@ hipError_t launch_pixel_dist_build(float *weights, uint32_t n, float decay, void
 hipError_t launch_pixel_dist_sample(const float *sensors, int n_sensors, uint32_t batch_first, uint32_t batch_count, uint32_t spp,
                                     uint32_t seed_pixels, uint32_t seed_rays, const void *table, uint32_t uniform_q, float *rays_o, float *rays_d,
                                     uint32_t *sensor_idx, uint32_t *pixels, hipStream_t stream);
+// patch batches (include/drt_hip.h "Patch batches"): the entries [batch_first, batch_first + batch_count) of a batch of patch_w x patch_h
+// patches over films of width x height; sensor_idx and pixels are required (the rays are formed from the stored picks)
+hipError_t launch_patch_sample(const float *sensors, int n_sensors, uint32_t width, uint32_t height, uint32_t patch_w, uint32_t patch_h,
+                               uint32_t batch_first, uint32_t batch_count, uint32_t spp, uint32_t seed_pixels, uint32_t seed_rays, float *rays_o,
+                               float *rays_d, uint32_t *sensor_idx, uint32_t *pixels, hipStream_t stream);
 hipError_t launch_pixel_dist_inv_pdf(const void *table, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,
                                      const int32_t *pixel_idx, uint64_t count, uint32_t uniform_q, float *out, hipStream_t stream);
 hipError_t launch_pixel_dist_update(float *weights, int32_t n_sensors, int32_t height, int32_t width, const int32_t *sensor_idx,

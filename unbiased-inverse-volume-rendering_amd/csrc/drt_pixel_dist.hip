@@ -8,6 +8,8 @@
 //            sums (one workgroup pass per block, fixed-order tree), exclusive scan of the block sums by ONE workgroup.  No float atomics.
 //   sample   one thread per batch entry picks (sensor, pixel) - the uniform pick of batch_raygen_kernel, or the two-level CDF search -, then
 //            one thread per ray forms the ray exactly as batch_raygen_kernel does (same draws, same sensor_ray).
+//   patches  patch_pick_kernel (include/drt_hip.h "Patch batches"): the batch as pw x ph patches; one thread per entry recomputes its patch's
+//            three draws (lane q = b / area of the pixel wavefront) and stores its pixel of the patch; the rays are dist_rays_kernel's.
 #include "drt_launch.h"
 
 namespace drt {
@@ -195,6 +197,42 @@ __global__ void __launch_bounds__(kDT) dist_pick_kernel(const float *sensors, in
     pixels[2 * bl] = px; pixels[2 * bl + 1] = py;
 }
 
+// the origin of a patch along one axis: e = min((uint32) ((float) (extent + patch - 1) * u), extent + patch - 2) and
+// clamp((int) e - (patch - 1), 0, extent - patch).  1 <= patch <= extent < 2^30 (the host checks both).
+__device__ __forceinline__ uint32_t patch_origin(float u, uint32_t extent, uint32_t patch)
+{
+    uint32_t e = (uint32_t) ((float) (extent + patch - 1) * u);
+    if (e > extent + patch - 2) e = extent + patch - 2;
+    const int o = (int) e - (int) (patch - 1);
+    return o < 0 ? 0u : ((uint32_t) o > extent - patch ? extent - patch : (uint32_t) o);
+}
+
+// one thread per batch entry b: patch q = b / area, position t = b % area; lane q of the pixel wavefront draws us, ux, uy (what lane b of
+// batch_raygen_kernel draws), the entry is pixel (x0 + t % pw, y0 + t / pw) of sensor si.  No LDS, no traffic between threads: the threads
+// of a patch repeat its three draws.  Every pixel is clamped to the table's own film, so dist_rays_kernel forms no ray off it.
+__global__ void __launch_bounds__(kDT) patch_pick_kernel(const float *sensors, int n_sensors, uint32_t width, uint32_t height, uint32_t pw,
+                                                         uint32_t ph, uint32_t batch_first, uint32_t batch_count, uint32_t seed_pixels,
+                                                         uint32_t *sensor_idx, uint32_t *pixels)
+{
+    const uint32_t bl = blockIdx.x * blockDim.x + threadIdx.x;
+    if (bl >= batch_count) return;
+    const uint32_t b = bl + batch_first;
+    const uint32_t area = pw * ph;
+    const uint32_t q = b / area, t = b - q * area;
+    const uint32_t ty = t / pw, tx = t - ty * pw;
+    Pcg32 S0; S0.seed(seed_pixels, q);
+    const float us = S0.next_1d(), ux = S0.next_1d(), uy = S0.next_1d();
+    uint32_t si = (uint32_t)((float) n_sensors * us);
+    if (si >= (uint32_t) n_sensors) si = (uint32_t) n_sensors - 1;
+    uint32_t px = patch_origin(ux, width, pw) + tx, py = patch_origin(uy, height, ph) + ty;
+    const float *sn = sensors + 16 * si;
+    const int fw = (int) sn[14], fh = (int) sn[15];
+    if (px >= (uint32_t) (fw > 0 ? fw : 1)) px = (uint32_t) (fw > 0 ? fw : 1) - 1;
+    if (py >= (uint32_t) (fh > 0 ? fh : 1)) py = (uint32_t) (fh > 0 ? fh : 1) - 1;
+    sensor_idx[bl] = si;
+    pixels[2 * bl] = px; pixels[2 * bl + 1] = py;
+}
+
 // one thread per ray: the ray of batch_raygen_kernel through the picked pixel
 __global__ void __launch_bounds__(kDT) dist_rays_kernel(const float *sensors, int n_sensors, uint32_t batch_first, uint32_t batch_count,
                                                         uint32_t spp, uint32_t seed_rays, const uint32_t *sensor_idx, const uint32_t *pixels,
@@ -297,6 +335,19 @@ hipError_t launch_pixel_dist_sample(const float *sensors, int n_sensors, uint32_
     if (batch_count == 0) return hipSuccess;
     hipLaunchKernelGGL(dist_pick_kernel, dim3((batch_count + kDT - 1) / kDT), dim3(kDT), 0, stream, sensors, n_sensors, batch_first, batch_count,
                        seed_pixels, table, uniform_q, sensor_idx, pixels);
+    const uint64_t n = (uint64_t) batch_count * spp;
+    hipLaunchKernelGGL(dist_rays_kernel, dim3((unsigned) ((n + kDT - 1) / kDT)), dim3(kDT), 0, stream, sensors, n_sensors, batch_first, batch_count,
+                       spp, seed_rays, (const uint32_t *) sensor_idx, (const uint32_t *) pixels, rays_o, rays_d);
+    return hipGetLastError();
+}
+
+hipError_t launch_patch_sample(const float *sensors, int n_sensors, uint32_t width, uint32_t height, uint32_t patch_w, uint32_t patch_h,
+                               uint32_t batch_first, uint32_t batch_count, uint32_t spp, uint32_t seed_pixels, uint32_t seed_rays, float *rays_o,
+                               float *rays_d, uint32_t *sensor_idx, uint32_t *pixels, hipStream_t stream)
+{
+    if (batch_count == 0) return hipSuccess;
+    hipLaunchKernelGGL(patch_pick_kernel, dim3((batch_count + kDT - 1) / kDT), dim3(kDT), 0, stream, sensors, n_sensors, width, height, patch_w,
+                       patch_h, batch_first, batch_count, seed_pixels, sensor_idx, pixels);
     const uint64_t n = (uint64_t) batch_count * spp;
     hipLaunchKernelGGL(dist_rays_kernel, dim3((unsigned) ((n + kDT - 1) / kDT)), dim3(kDT), 0, stream, sensors, n_sensors, batch_first, batch_count,
                        spp, seed_rays, (const uint32_t *) sensor_idx, (const uint32_t *) pixels, rays_o, rays_d);

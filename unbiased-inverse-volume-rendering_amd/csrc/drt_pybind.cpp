@@ -257,6 +257,15 @@ public:
                                                   ptr<uint32_t>(pix));
         });
     }
+    void batch_sample_rays_patches(uintptr_t sensors, int n_sensors, int width, int height, uint32_t patch_w, uint32_t patch_h, uint32_t batch,
+                                   uint32_t spp, uint32_t seed_px, uint32_t seed_rays, uintptr_t ro, uintptr_t rd, uintptr_t sidx, uintptr_t pix,
+                                   uint32_t batch_first)
+    {
+        nogil("drt_batch_sample_rays_patches", [&] {
+            return drt_batch_sample_rays_patches(h_, ptr<const float>(sensors), n_sensors, width, height, patch_w, patch_h, batch_first, batch, spp,
+                                                 seed_px, seed_rays, ptr<float>(ro), ptr<float>(rd), ptr<uint32_t>(sidx), ptr<uint32_t>(pix));
+        });
+    }
     void film_develop(uintptr_t L, uint64_t n_pixels, uint32_t spp, uintptr_t image)
     {
         nogil("drt_film_develop", [&] { return drt_film_develop(h_, ptr<const float>(L), n_pixels, spp, ptr<float>(image)); });
@@ -505,6 +514,9 @@ PYBIND11_MODULE(DRT_PYBIND_NAME, m)
         .def("batch_sample_rays_weighted", &Integrator::batch_sample_rays_weighted, py::arg("sensors"), py::arg("n_sensors"), py::arg("batch"),
              py::arg("spp"), py::arg("seed_px"), py::arg("seed_rays"), py::arg("table"), py::arg("uniform_q"), py::arg("ro"), py::arg("rd"),
              py::arg("sidx"), py::arg("pix"), py::arg("batch_first") = 0)
+        .def("batch_sample_rays_patches", &Integrator::batch_sample_rays_patches, py::arg("sensors"), py::arg("n_sensors"), py::arg("width"),
+             py::arg("height"), py::arg("patch_w"), py::arg("patch_h"), py::arg("batch"), py::arg("spp"), py::arg("seed_px"), py::arg("seed_rays"),
+             py::arg("ro"), py::arg("rd"), py::arg("sidx"), py::arg("pix"), py::arg("batch_first") = 0)
         .def("film_develop", &Integrator::film_develop)
         .def("film_backward", &Integrator::film_backward)
         .def("film_loss_forward", &Integrator::film_loss_forward)

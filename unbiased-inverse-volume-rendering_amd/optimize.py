@@ -10,14 +10,14 @@ from __future__ import annotations
 import os
 from dataclasses import dataclass, field
 from enum import IntEnum
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from . import losses
-from .batched import gather_ref_values, render_batch, sensors_to_device
+from .batched import _check_patch, as_patches, gather_ref_values, patch_inv_pdf, render_batch, sensors_to_device
 from .integrators import sample_tea_32
 from .loss_fused import render_batch_loss, render_loss, resolve_loss
 from .opt_config import get_int_config
@@ -83,6 +83,11 @@ class OptimizationConfig:
     # 1 / (pyramid_levels + 1) each) in a sensor-mode (batch_size=None), unfused, unsharded run.  0: nothing extra runs
     pyramid_levels: int = 0
     pyramid_weights: Optional[List[float]] = None
+    # opt-in: draw every batch as rectangular patches of patch_size (an int, or (patch_w, patch_h)) instead of scattered pixels
+    # (batched.render_batch's patch_size; batched, unsharded, unfused runs, batch_size a multiple of the patch area).  The loss is weighted
+    # by batched.patch_inv_pdf, and `dssim_weight` (patch sides >= 11) and `pyramid_levels` then apply to the patches.  None: the
+    # scattered batches of the reference, nothing extra runs
+    patch_size: Optional[Union[int, Tuple[int, int]]] = None
 
     def __post_init__(self):
         self.upsample_at = set()
@@ -559,6 +564,16 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
     For l1, l2 and huber that is one fused kernel call (csrc/drt_pyramid.hip), no host wait.  0 (the default) runs nothing extra and leaves
     the run's bits.
 
+    `opt_config.patch_size` (an int or (patch_w, patch_h); batched, i.e. `batch_size` set and a multiple of the patch area; not with
+    `fused_loss`, `pixel_importance`, the distortion term or a shard - each raises a ValueError at start-up): every batch is drawn as
+    rectangular patches (include/drt_hip.h "Patch batches"), and `dssim_weight` and `pyramid_levels` apply to the (N, ph, pw, C) stack
+    `as_patches(image)`.  The step's loss is sum_b patch_inv_pdf_b * ell_b / image.numel() with ell = `losses.pixelwise(loss)(image, ref)` -
+    the expectation of the loss a uniform batch estimates.  With `pyramid_levels > 0` losses.multiscale(loss, pyramid_levels,
+    pyramid_weights) over the patches and the gathered reference patches REPLACES that term: an unweighted mean over patches, which
+    weights the film's border by the coverage ratio c_x c_y / (pw ph) against the interior (at most 9, DESIGN.md "Patch batches").  With
+    `dssim_weight != 0` the loss gains dssim_weight x losses.dssim(patches[..., :3], ref_patches[..., :3], padding="valid") - "valid" so that
+    no window reads zero padding at a patch's edge; both patch sides must be >= 11.  None runs nothing extra and leaves the run's bits.
+
     `opt_config.support` (a `HullSupport`; every route, sharded ones too - each rank carves the same integers; like the rest of
     distributed.py that is unverified on multi-GPU hardware): at initialisation and after every `upsample` the visual hull of the mattes
     (`masks`, or channel 3 of the references > `threshold`) is carved from the scene's box and the run's sensors at the current resolution
@@ -586,13 +601,35 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             if k in (PHASE_G_KEY, PHASE_TAB_KEY) or k not in scene_config.param_keys or not k.endswith('.data'):
                 raise ValueError(f'support: "{k}" is not an optimised grid (optimised grid keys: '
                                  f'{[q for q in scene_config.param_keys if q not in (PHASE_G_KEY, PHASE_TAB_KEY)]})')
+    patch = opt_config.patch_size
+    if patch is not None:
+        if opt_config.batch_size is None:
+            raise ValueError("patch_size: sensor-based rendering (batch_size=None) renders every pixel of one sensor; patches are how a batch "
+                             "is drawn: set batch_size")
+        if opt_config.fused_loss:
+            raise ValueError("patch_size: fused_loss=True is not supported (the loss-fused film sums the loss without per-pixel weights and "
+                             "never holds the patches); use fused_loss=False")
+        if opt_config.pixel_importance is not None:
+            raise ValueError("patch_size: pixel_importance is not supported with patch batches (importance-sampled patch origins are a "
+                             "follow-up)")
+        if shard.world > 1:
+            raise ValueError("patch_size: sharded runs are not supported yet: a rank's share of the entries may split a patch, and whole "
+                             "patches per rank are the follow-up")
+        if opt_config.distortion_weight != 0.0:
+            raise ValueError("patch_size: the distortion term (distortion_weight != 0) is a mean over uniformly drawn pixels and is not "
+                             "supported with patch batches")
+        sen0 = scene_config.scene.sensors[scene_config.sensors[0]]
+        patch = _check_patch(patch, opt_config.batch_size, (sen0.width, sen0.height), "patch_size")     # (patch_w, patch_h)
     dssim_weight = opt_config.dssim_weight
     if isinstance(dssim_weight, bool) or not isinstance(dssim_weight, (int, float)) or not np.isfinite(dssim_weight):
         raise ValueError(f"dssim_weight must be a finite number, got {dssim_weight!r}")
     if dssim_weight != 0.0:
-        if opt_config.batch_size is not None:
+        if opt_config.batch_size is not None and patch is None:
             raise ValueError("dssim_weight: batched rendering (batch_size set) draws random pixels, which have no neighbourhoods for a structural "
-                             "index to read; use sensor-based rendering (batch_size=None)")
+                             "index to read; use sensor-based rendering (batch_size=None), or draw the batch as patches (patch_size)")
+        if patch is not None and min(patch) < 11:
+            raise ValueError(f"dssim_weight: patch_size {patch[0]} x {patch[1]} is smaller than the structural index's 11 x 11 window "
+                             f"(padding=\"valid\": no window reads zero padding at a patch's edge); both sides must be >= 11")
         if opt_config.fused_loss:
             raise ValueError("dssim_weight: fused_loss=True is not supported (the loss-fused film sums a pixel-separable loss and never holds "
                              "the image the D-SSIM term differentiates); use fused_loss=False")
@@ -604,9 +641,9 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
         raise ValueError(f"pyramid_levels must be an integer >= 0, got {pyramid_levels!r}")
     film_loss = None                                                   # the loss over the pyramid of a whole film (sensor mode)
     if pyramid_levels > 0:
-        if opt_config.batch_size is not None:
+        if opt_config.batch_size is not None and patch is None:
             raise ValueError("pyramid_levels: batched rendering (batch_size set) draws scattered pixels, which have no cells for a pyramid to "
-                             "pool; use sensor-based rendering (batch_size=None).  Block-shaped batches are the follow-up")
+                             "pool; use sensor-based rendering (batch_size=None).  Block-shaped batches are the follow-up: set patch_size")
         if opt_config.fused_loss:
             raise ValueError("pyramid_levels: fused_loss=True is not supported (the loss-fused film sums a pixel-separable loss per pixel and "
                              "never pools the image); use fused_loss=False")
@@ -632,6 +669,11 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             raise ValueError("pixel_importance: the distortion term (distortion_weight != 0) is a mean over uniformly drawn pixels and is not "
                              "supported with importance-sampled batches")
         pixel_loss = losses.pixelwise(opt_config.loss)                 # (raises for a loss that is not a sum over pixels)
+    if patch is not None and film_loss is None:
+        try:
+            pixel_loss = losses.pixelwise(opt_config.loss)             # (the term patch_inv_pdf weights: a sum over pixels)
+        except ValueError as e:
+            raise ValueError(f"patch_size: {e}") from e
     if opt_config.fused_loss:
         resolve_loss(opt_config.loss)                                  # (raises for a loss the fused kernels do not have)
         if shard.world > 1:
@@ -896,7 +938,7 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             image, _, _, sensor_idx, pixel_idx = render_batch(
                 opt_config.batch_size, scene, sensors=sensors, params=rendered, integrator=integrator,
                 spp=spp_primal, spp_grad=spp_grad, seed=seed, seed_grad=seed_grad, sensor_table=table, shard=shard,
-                pixel_distribution=dist)
+                pixel_distribution=dist, patch_size=patch)
             ref_values = gather_ref_values(ref_images, sensor_idx, pixel_idx)
             n_global = opt_config.batch_size
         else:                                                          # sensor-based rendering (:342-348)
@@ -911,6 +953,18 @@ def run_optimization(output_dir: Optional[str], opt_config: OptimizationConfig, 
             # importance-sampled batch: per-pixel losses weighted by 1 / (n pdf) - unbiased for what the uniform batch's loss estimates
             ell = pixel_loss(image[:, :n_channels], ref_values[:, :n_channels])
             loss_value = (dist.inv_pdf(sensor_idx, pixel_idx) * ell).sum() / image[:, :n_channels].numel()
+        elif patch is not None:
+            # patch batch: the pixel-separable term weighted by 1 / (n p) - the expectation of the uniform batch's loss -, or the loss over
+            # the patches' pyramids in its place; the structural term reads each patch as a small film, windows inside it only
+            if film_loss is not None:
+                loss_value = film_loss(as_patches(image[:, :n_channels], patch), as_patches(ref_values[:, :n_channels], patch))
+            else:
+                ell = pixel_loss(image[:, :n_channels], ref_values[:, :n_channels])
+                loss_value = (patch_inv_pdf(sensor_idx, pixel_idx, (n_sensors, sensors[0].height, sensors[0].width), patch) * ell).sum() \
+                    / image[:, :n_channels].numel()
+            if dssim_weight != 0.0:
+                loss_value = loss_value + dssim_weight * _losses.dssim(as_patches(image, patch)[..., :3], as_patches(ref_values, patch)[..., :3],
+                                                                       data_range=opt_config.dssim_data_range, padding="valid")
         elif not opt_config.fused_loss:
             # the losses normalise by the local entry count: scale to this rank's share of the global loss
             scale = local_loss_scale(image.shape[0], n_global)
